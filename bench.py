@@ -9,6 +9,9 @@ with --gpus N > 1 it starts the N ranks itself (fresh child processes through to
 anything in this process has touched a GPU) and relays rank 0's line.
 Strong scaling as configs[3] states it: the ONE 100k-utterance set (the N = 1 workload, same seeds, same
 frames) is dealt to the N ranks by total frames (kaldi_hmm_gmm_amd.dist.shard_utterances).
+A plain run sets up, warms up, times --steps steps and prints the headline (value, ms_per_step, kernel_ms_per_step, ...);
+--full adds every side measurement and check (roofline, side lines, M-step, CPU baseline, oracle check, per-call line).
+--dump-outputs DIR writes what the last timed step computed (timed_outputs) for output-by-output comparison of two builds.
 """
 import argparse
 import json
@@ -70,7 +73,50 @@ def parse():
     ap.add_argument("--c1-parts", type=int, default=4,
                     help="--allreduce khg: C1 pipelined behind K3 in this many pdf ranges (khg_acc_stats_reduce); 1 = one all-reduce of the "
                          "whole block behind K3 (khg_accs_allreduce)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline, fp32_mfma_line, recipe_beam_line, flat_start_line, "
+                         "m_step, cpu_baseline, check, per_call_line, and at N > 1 scaling_efficiency_vs_n1_shard and rccl.c1_ms_alone.  Without it "
+                         "a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB "
+                         "in all; see timed_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_PART_BYTES = 12 << 20     # per array of --dump-outputs: five arrays and a pair of totals stay under 64 MB
+
+
+def _sample(n, per_item_bytes, rng):
+    """Sorted indices of a seeded sample of n items within DUMP_PART_BYTES (all n when they fit)."""
+    k = DUMP_PART_BYTES // per_item_bytes
+    return np.arange(n) if n <= k else np.sort(rng.choice(n, size=k, replace=False))
+
+
+def timed_outputs(accs, sets, frame_off, D):
+    """What the timed path hands its caller after its last step, for --dump-outputs: the accumulator block (occupancies, transition
+    counts, [total frames, total log-likelihood], mean and variance accumulators) and the alignments (transition ids, exact in float32)
+    of this rank's utterances.  Larger arrays are cut to a sample drawn with a fixed seed -- mean_acc / var_acc by Gaussian rows,
+    ali by whole utterances -- so that two builds run with the same arguments write the same elements.  -> {name: array}"""
+    rng = np.random.default_rng(20240601)
+    res = accs.download()
+    G = res["occ"].shape[0]
+    rows = _sample(G, 8 * D, rng)
+    occ_rows = _sample(G, 8, rng)
+    tr_rows = _sample(res["trans_acc"].shape[0], 8, rng)
+    ali = np.concatenate([np.asarray(s_.download_ali()) for s_ in sets])
+    T = np.diff(frame_off)
+    order = rng.permutation(len(T))
+    keep = np.sort(order[: int(np.searchsorted(np.cumsum(T[order]), DUMP_PART_BYTES // 4, side="right"))])
+    fidx = np.concatenate([np.arange(frame_off[u], frame_off[u + 1]) for u in keep]) if len(keep) else np.zeros(0, np.int64)
+    out = {"occ": res["occ"][occ_rows], "mean_acc": res["mean_acc"][rows], "var_acc": res["var_acc"][rows],
+           "trans_acc": res["trans_acc"][tr_rows], "totals": np.array([res["total_frames"], res["total_log_like"]], np.float64),
+           "ali": ali[fidx].astype(np.float32)}
+    out = {k: np.ascontiguousarray(v, dtype=v.dtype if v.dtype == np.float32 else np.float64) for k, v in out.items()}
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    return out
 
 
 def main():
@@ -259,7 +305,8 @@ def main():
     k1_flops = float((T * npdf).sum()) * (4.0 * D * G + 5.0 * G)  # alignment log-likes
     # cells K1 leaves out with khg_loglikes_reachable: whole 16-frame tiles before a pdf's first readable frame
     skipped_cells = 0.0
-    if not args.full_loglikes:
+    band = (not args.full_loglikes) and (not args.no_band) and k1_form == "f16x2s" and args.beam >= 100.0
+    if args.full and not args.full_loglikes:             # (only the roofline reads the executed share)
         for s_ in sets:
             poff_, _ = s_.pdf_lists()
             first = s_.pdf_first_frames().astype(np.int64)
@@ -270,8 +317,7 @@ def main():
                 skipped_cells += float(np.minimum(32 * (np.minimum(first // 16, 127) // 2), Tu).sum())
             else:
                 skipped_cells += float(np.minimum(16 * (first // 16), Tu).sum())
-    band = (not args.full_loglikes) and (not args.no_band) and k1_form == "f16x2s" and args.beam >= 100.0
-    if band:                                        # + whole 32-frame tiles past the last useful frame of a pdf
+    if args.full and band:                          # + whole 32-frame tiles past the last useful frame of a pdf
         for s_ in sets:
             poff_, _ = s_.pdf_lists()
             last = s_.pdf_last_frames().astype(np.int64)
@@ -402,10 +448,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         dt = float(tmax[0])
         frames_total = int(t[1])
+    # what the last timed step computed, fetched before anything below runs the step again
+    dumped = timed_outputs(accs, sets, ut.frame_off, D) if (args.dump_outputs and rank == 0) else None
     # The same shards WITHOUT the exchange, in this very run (round 4 compared with a committed N = 1 line of another box and session):
     # two steps, every rank alone on its shard, slowest rank's time -- what an N-rank run would cost if C1 were free
     alone_ms = None
-    if dist_on and world > 1:
+    if args.full and dist_on and world > 1:
         step(exchange=False)
         torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
         ta = time.perf_counter()
@@ -424,7 +472,7 @@ def main():
     rccl_info = None
     if dist_on and args.allreduce in ("khg", "khg-f32"):
         c1_alone = None
-        if comm is not None:
+        if comm is not None and args.full:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             dist.barrier()
@@ -452,8 +500,10 @@ def main():
     B = types.SimpleNamespace(args=args, ctxs=ctxs, sets=sets, dm=dm, tm=tm, accs=accs, step=step, dist_on=dist_on, dist=dist, dev=dev, backend=backend,
                               nb=nb, k1_form=k1_form, split_form=split_form, frames_total=frames_total, k1_flops_per_launch=k1_flops_per_launch,
                               ar_events=ar_events, n_local=n_local, model=model, gc=gc, D=D)
-    fp32_line = bench_lines.fp32_mfma_line(B)
-    recipe_line, flat_line = bench_lines.recipe_and_flat_start_lines(B)
+    fp32_line, recipe_line, flat_line = None, None, None
+    if args.full:
+        fp32_line = bench_lines.fp32_mfma_line(B)
+        recipe_line, flat_line = bench_lines.recipe_and_flat_start_lines(B)
     if recipe_line is not None or fp32_line is not None or flat_line is not None:
         step()                                        # the block holds the headline configuration's sums (over all shards) again
         torch.cuda.synchronize()
@@ -469,7 +519,7 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine_info)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         tm0 = time.perf_counter()
         res = accs.download()
         tm1 = time.perf_counter()
@@ -585,6 +635,7 @@ def main():
                                          "busbw_GBps": bus / (rccl_info["c1_ms_alone"] * 1e-3) / 1e9 if rccl_info and rccl_info.get("c1_ms_alone") else None,
                                          "frac_xgmi": bus / (rccl_info["c1_ms_alone"] * 1e-3) / 1e9 / PEAK_XGMI_GBPS if rccl_info and rccl_info.get("c1_ms_alone") else None,
                                          "note": "ring all-reduce: 2 (N - 1) / N x block bytes leave every GPU; against 7 links x 153 GB/s"}
+    if rank == 0:
         out = {
             "metric": "frames/sec (whole node) per EM iter (align+acc-stats), 5k-pdf x 64-Gauss",
             "value": frames_total * args.steps / dt,
@@ -604,21 +655,19 @@ def main():
                 "term plus an absolute floor the library keeps under 2e-6 (else it runs the two-accumulator f16x2 form, else fp32 MFMA); "
                 "measured error vs fp64: max 2.1e-7 B (tools/k1lab.hip; the fp32 fmaf chain of the fp32-MFMA kernels: 7.4e-7 B), every "
                 "fp64-bound tolerance test (1e-5 + 1e-6 B) unchanged; everything else fp32 / fp64 as the reference; the fp32-MFMA K1 is "
-                "timed beside it in fp32_mfma_line (--k1 pdf runs it as the whole bench)" if k1_form == "f16x2s" else
+                "timed beside it in fp32_mfma_line under --full (--k1 pdf runs it as the whole bench)" if k1_form == "f16x2s" else
                 "log-likelihood contraction: fp32 operands rescaled per k by an exact power of two and written as v1 + v2 2^-11 with two fp16 "
                 "pieces (|v - (v1 + v2 2^-11)| <= 2^-23 |v|: 11 + 11 significant bits), the three partial products w1 x1, w1 x2, w2 x1 on the "
                 "fp16 matrix cores with fp32 accumulators; the dropped w2 x2 is <= 2^-22 of the term -- worst case 2^-21 per term, measured "
                 "error vs fp64 max 3.0e-7 B (the fp32 fmaf chain: 7.4e-7 B, profiles/r2_probe_f16x2.txt), every fp64-bound tolerance test "
                 "unchanged; everything else fp32 / fp64 as the reference; the fp32-MFMA K1 is timed beside it in fp32_mfma_line "
-                "(--k1 pdf runs it as the whole bench)" if k1_form == "f16x2" else
+                "under --full (--k1 pdf runs it as the whole bench)" if k1_form == "f16x2" else
                 "fp32 MFMA (v_mfma_f32_16x16x4_f32): the reference's per-Gaussian fmaf chain bit for bit"),
             "data": "synthetic",
             "config": {"workload": f"{args.config}: {P} pdfs x {G} Gauss, dim {D}, {args.utts} utterances "
                                    f"({frames_total} frames) sharded over {world} GPU(s), beam {args.beam:g}, "
                                    f"acoustic_scale 0.1, mean pdfs/utt {npdf.mean():.1f}" + (", Zipf-lexicon transcripts" if args.transcripts == "zipf" else ""),
                        "frames_per_step": frames_total, "utterances": args.utts},
-            "roofline": roofline,
-            "fp32_mfma_line": fp32_line,
             "kernel_ms_per_step": {k: v / args.steps for k, v in sorted(kernel_ms.items())},
             "prep_ms": {"kernels": prep_ms, "total": sum(prep_ms.values()),
                         "note": "once per UTTERANCE SET (the features' column maxima -- k1_absmax here also covers the model's columns of the "
@@ -627,23 +676,26 @@ def main():
                                 "every timed step since round 5 (khg_model_invalidate at the top of the step) and listed in kernel_ms_per_step"},
             "allreduce_ms_per_step": (sum(a_.elapsed_time(b_) for a_, b_ in ar_events) / max(len(ar_events), 1)) if ar_events else None,
             "allreduce_bytes": int(accs.size) * 8 if dist_on else None,
-            "m_step": m_step,
-            "check": {"acc_total_frames": res["total_frames"], "frames_in_set": frames_global, "avg_loglike_per_frame":
-                      res["total_log_like"] / max(res["total_frames"], 1.0)},
             "allreduce": args.allreduce if dist_on else None,
             "allreduce_fallback_in_process": inproc_fallback,
             "rccl": rccl_info,
-            "scaling_efficiency_vs_n1_shard": None if alone_ms is None else {
-                "value": alone_ms / (dt / args.steps * 1e3), "shards_without_exchange_ms_per_step": alone_ms, "ms_per_step": dt / args.steps * 1e3,
-                "note": "measured in THIS run: two extra steps with every rank alone on its shard (no C1), slowest rank, over the timed "
-                        "ms_per_step -- 1.0 = the exchange is fully hidden; what is left of the N-fold speed-up besides this is the small-shard "
-                        "effect (fewer, shorter launches per kernel), visible as N x shards_without_exchange_ms_per_step against the N = 1 line"},
             "c1_pipelined_parts": args.c1_parts if (dist_on and args.allreduce == "khg" and args.c1_parts > 1 and len(streams) == 1) else None,
             "per_rank": per_rank if world > 1 else None,
         }
         if out["c1_pipelined_parts"]:
             out["allreduce_note"] = ("allreduce_ms_per_step spans the LAST set's K3 with the exchange pipelined behind it in %d pdf ranges "
                                      "(khg_acc_stats_reduce); the RCCL pieces alone are kernel_ms_per_step['c1_allreduce']" % args.c1_parts)
+    if rank == 0 and args.full:
+        out["roofline"] = roofline
+        out["fp32_mfma_line"] = fp32_line
+        out["m_step"] = m_step
+        out["check"] = {"acc_total_frames": res["total_frames"], "frames_in_set": frames_global, "avg_loglike_per_frame":
+                        res["total_log_like"] / max(res["total_frames"], 1.0)}
+        out["scaling_efficiency_vs_n1_shard"] = None if alone_ms is None else {
+            "value": alone_ms / (dt / args.steps * 1e3), "shards_without_exchange_ms_per_step": alone_ms, "ms_per_step": dt / args.steps * 1e3,
+            "note": "measured in THIS run: two extra steps with every rank alone on its shard (no C1), slowest rank, over the timed "
+                    "ms_per_step -- 1.0 = the exchange is fully hidden; what is left of the N-fold speed-up besides this is the small-shard "
+                    "effect (fewer, shorter launches per kernel), visible as N x shards_without_exchange_ms_per_step against the N = 1 line"}
         if not args.no_cpu_baseline and world == 1:      # the CPU baseline belongs to the N = 1 line only: at N > 1 the other ranks would sit
                                                           # at the closing barrier for its 15 s (and the oracle check that rides on it)
             ncpu = min(n_local, 40000)     # enough work for a few seconds of every host core
@@ -658,6 +710,11 @@ def main():
         out["flat_start_line"] = flat_line
         if args.per_call_utts > 0 and world == 1:
             out["per_call_line"] = per_call_line(args, model, ut, feats, D, ctxs[0], out.get("cpu_baseline"))
+    if rank == 0:
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
         record = json.dumps(out)
     if dist_on:
         dist.barrier()

@@ -13,6 +13,7 @@ import hashlib
 import json
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -133,6 +134,14 @@ def main():
         json.dump({"source": "oracle/_ref/hashlist_ref = /root/reference/kaldi-hmm-gmm/csrc/hash-list.h compiled as it lies "
                              "(oracle/ref_hashlist_harness.cc, make -C oracle ref)", "cases": out}, fh, separators=(",", ":"))
     print(len(out), "cases,", sum(len(c["script"]) for c in out), "commands,", sum(len(c["answers"]) for c in out), "answers")
+    # the fresh script of tests/test_oracle_pins.py, for machines where the reference binary cannot be built
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    from test_oracle_pins import _fresh_hashlist_script
+    script = _fresh_hashlist_script()
+    with open(os.path.join(ROOT, "tests", "golden", "hashlist_ref_fresh.json"), "w") as fh:
+        json.dump({"source": "oracle/_ref/hashlist_ref on tests/test_oracle_pins.py:_fresh_hashlist_script()",
+                   "script_sha1": hashlib.sha1("\n".join(script).encode()).hexdigest(), "answers": pack_answers(run(script))},
+                  fh, separators=(",", ":"))
 
 
 if __name__ == "__main__":

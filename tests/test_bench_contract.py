@@ -1,4 +1,4 @@
-"""bench.py's output contract: stdout is exactly ONE JSON line with the fields the driver reads (plus `roofline` and
+"""bench.py's output contract: stdout is exactly ONE JSON line with the fields the driver reads (plus, with --full, `roofline` and
 `cpu_baseline`), also when the collective code path runs (KHG_BENCH_FORCE_DIST=1: a one-rank RCCL group on a one-GPU
 box -- RCCL's version banner must not reach stdout)."""
 import json
@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,7 +16,7 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 
 def _run(extra_env, *flags):
     env = dict(os.environ, **extra_env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--utts", "2000", "--steps", "2", "--warmup", "1", *flags],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--utts", "2000", "--steps", "2", "--warmup", "1", "--full", *flags],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -114,3 +115,30 @@ def test_in_process_fallback_when_the_library_communicator_cannot_be_formed():
     fb = d["allreduce_fallback_in_process"]
     assert fb["now"] == "--allreduce torch" and "KHG_BENCH_FAIL_COMM=2" in fb["error"]
     assert d["check"]["acc_total_frames"] == d["config"]["frames_per_step"] and d["allreduce_ms_per_step"] is not None
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_the_timed_step_computed(tmp_path):
+    """Without --full the line holds the headline alone; --dump-outputs writes the last timed step's accumulators and alignments
+    (float32 / float64, under 64 MB), the same for two runs with the same arguments."""
+    got = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--utts", "2000", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == 1, r.stdout[:2000]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32 via f16x2s"
+        assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(d["config"]["frames_per_step"] / (d["ms_per_step"] * 1e-3))
+        assert not {"roofline", "cpu_baseline", "check", "m_step", "fp32_mfma_line", "recipe_beam_line", "flat_start_line", "per_call_line"} & set(d)
+        files = {f.name: np.load(f) for f in (tmp_path / tag).iterdir()}
+        assert set(files) == {"occ.npy", "mean_acc.npy", "var_acc.npy", "trans_acc.npy", "totals.npy", "ali.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+        n = d["config"]["frames_per_step"]                  # (the default model: occ and trans_acc whole, mean / var rows sampled)
+        assert files["totals.npy"][0] == n == files["trans_acc.npy"].sum() and files["occ.npy"].sum() == pytest.approx(n, rel=1e-6)
+        assert files["ali.npy"].size > 0 and files["ali.npy"].min() >= 1
+        got.append(files)
+    assert np.array_equal(got[0]["ali.npy"], got[1]["ali.npy"])
+    for name in ("occ.npy", "mean_acc.npy", "var_acc.npy", "trans_acc.npy", "totals.npy"):
+        np.testing.assert_allclose(got[0][name], got[1][name], rtol=1e-12, atol=1e-12 * np.abs(got[0][name]).max(), err_msg=name)

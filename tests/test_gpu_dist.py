@@ -222,7 +222,7 @@ def test_bench_launches_its_own_ranks_and_shards_the_one_set():
     JSON line; the two ranks own the frames of the N = 1 set (same seeds) and the summed accumulators count all of
     them.  KHG_BENCH_SHARE_GPU=1: both ranks on GPU 0, block summed on the host."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--utts", "3000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--utts", "3000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r1 = subprocess.run(base, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r1.returncode == 0, r1.stderr[-3000:]
     d1 = json.loads(r1.stdout.strip().splitlines()[-1])

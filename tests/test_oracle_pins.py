@@ -279,18 +279,34 @@ def test_hash_list_against_answers_recorded_from_the_reference_itself():
     assert shared > 100
 
 
-def test_hash_list_against_the_reference_binary_when_it_is_here():
-    """Where oracle/_ref/hashlist_ref exists (this container: `make -C oracle ref` compiles the reference's header from
-    /root/reference), a fresh random script goes through the reference binary and the oracle side by side."""
-    import subprocess
-    binary = os.path.join(ROOT, "oracle", "_ref", "hashlist_ref")
-    if not os.path.exists(binary):
-        pytest.skip("oracle/_ref/hashlist_ref not built (no /root/reference here)")
+def _fresh_hashlist_script():
+    """60 decoder-like frames: drop the list, grow the hash, insert a few hundred random keys, list, find five."""
     rng = np.random.default_rng(77)
     script = ["S 64"]
     for f in range(60):
         script += ["D", f"S {64 + 8 * f}"] + [f"I {int(k)} {f}" for k in rng.integers(0, 3000, size=int(rng.integers(5, 400)))] + ["L"]
         script += [f"F {int(k)}" for k in rng.integers(0, 3000, size=5)]
+    return script
+
+
+def test_hash_list_against_the_reference_binary_when_it_is_here():
+    """A fresh random script goes through the reference's HashList and the oracle side by side: through the binary where
+    oracle/_ref/hashlist_ref exists (`make -C oracle ref` compiles the reference's header), else against that binary's answers to
+    the same script as recorded in tests/golden/hashlist_ref_fresh.json (tests/golden/make_hashlist_golden.py)."""
+    import hashlib
+    import json
+    import subprocess
+    script = _fresh_hashlist_script()
+    binary = os.path.join(ROOT, "oracle", "_ref", "hashlist_ref")
+    if not os.path.exists(binary):
+        with open(os.path.join(ROOT, "tests", "golden", "hashlist_ref_fresh.json")) as fh:
+            gold = json.load(fh)
+        assert gold["script_sha1"] == hashlib.sha1("\n".join(script).encode()).hexdigest(), "recorded from another script"
+        h = orc.OHashList()
+        got = _hl_replay(script, h)
+        h.close()
+        assert got == gold["answers"]
+        return
     r = subprocess.run([binary], input="\n".join(script) + "\n", capture_output=True, text=True, check=True)
     want = r.stdout.splitlines()
 

@@ -137,7 +137,7 @@ with open(os.path.join(DST, f"{TAG}_pmc_summary.json"), "w") as fh:
 
 lines = [f"# Round {TAG[1:]} rocprofv3 summaries (MI355X, gfx950)", "",
          f"Produced by `tools/profile_{TAG}.sh` on the GPU box and `tools/summarize_prof.py` here: one",
-         "`rocprofv3 --kernel-trace --stats` run of `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline`",
+         "`rocprofv3 --kernel-trace --stats` run of `python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline`",
          "(the default workload: 100 000 utterances, one launch of each kernel per step), then three separate",
          "`--pmc` runs of the same command (FETCH_SIZE | WRITE_SIZE | SQ_* + GRBM_GUI_ACTIVE).", "",
          f"## Kernel trace ({TAG}_kernel_stats.csv)", "", "| kernel | calls | avg ms | % |", "|---|---|---|---|"]
