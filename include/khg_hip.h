@@ -266,6 +266,53 @@ int khg_ali_upload(khg_ctx *ctx, khg_utts *u, const int32_t *ali_h);
 /* the resident alignment back (0 on the frames of utterances that failed to align) */
 int khg_ali_download(khg_ctx *ctx, khg_utts *u, int32_t *ali_h);
 
+/* ---- K2L: LatticeFasterDecoder + DecodeUtteranceLatticeFaster ------------------------------------------------------------------ */
+typedef struct {
+  /* LatticeFasterDecoderConfig (csrc/lattice-faster-decoder.h:45-105; pybind defaults python/csrc/lattice-faster-decoder.cc:20-31) */
+  float beam;             /* 16 */
+  int32_t max_active;     /* INT32_MAX */
+  int32_t min_active;     /* 200 */
+  float lattice_beam;     /* 10 */
+  int32_t prune_interval; /* 25 */
+  float beam_delta;       /* 0.5 */
+  float hash_ratio;       /* 2 */
+  float prune_scale;      /* 0.1 */
+  /* DecodableAmDiagGmmScaled's scale (csrc/decodable-am-diag-gmm.h:83-103): the score read for (frame, tid) is
+   * acoustic_scale * loglike(frame, id2pdf[tid]); 1 for scores that were scaled before khg_loglikes_upload */
+  float acoustic_scale;   /* 1 */
+  /* DecodeUtteranceLatticeFaster's allow_partial (csrc/decoder-wrappers.cc:200-211) */
+  int32_t allow_partial;  /* 1 */
+  /* forward-link / token scratch per utterance and frame.  0: min(num_states, 256) tokens and min(num_arcs, 1024) links per frame,
+   * plus one frame's worth, and every utterance that runs out of that is decoded again with room for all states and arcs on every
+   * frame (a frame never holds more), so only the queue / sort bounds can still give KHG_LAT_SCRATCH.  > 0: exactly that many
+   * tokens and links per frame, no second pass; an utterance that runs out gets KHG_LAT_SCRATCH and no output */
+  int32_t scratch_per_frame; /* 0 */
+} khg_lattice_faster_config;
+void khg_lattice_faster_config_default(khg_lattice_faster_config *c);
+
+/* per-utterance status bits of khg_decode_lattice_faster */
+#define KHG_LAT_SUCCEEDED 1  /* DecodeUtteranceLatticeFaster returned true: alignment, words and like are valid          */
+#define KHG_LAT_PARTIAL 2    /* no final state reached (ReachedFinal() false); output only with allow_partial            */
+#define KHG_LAT_SCRATCH 4    /* out of token / forward-link scratch (scratch_per_frame): decoding stopped, no output       */
+#define KHG_LAT_NO_PATH 8    /* Decode() false: no token survived to the last frame (lattice-faster-decoder.cc:97)         */
+#define KHG_LAT_EPS_LOOP 16  /* an epsilon cycle among one frame's tokens (TopSortTokens, :1004-1006)                      */
+#define KHG_LAT_WORDS 32     /* more words on the best path than frames + states + 64: no output                          */
+#define KHG_LAT_NO_TRACEBACK 64 /* GetBestPath failed after a successful Decode (decoder-wrappers.cc:213-215)             */
+
+/* LatticeFasterDecoder::Decode (csrc/lattice-faster-decoder.cc:86-98) + GetBestPath (:101-192: GetRawLattice + OpenFst ShortestPath)
+ * + DecodeUtteranceLatticeFaster (csrc/decoder-wrappers.cc:186-224) for every utterance of the set, each on a fresh decoder
+ * (HashList size 1000, :36).  Requires khg_loglikes(), khg_loglikes_reachable() or khg_loglikes_upload first -- not
+ * khg_loglikes_band, whose cells past the band hold bounds, not scores (KHG_E_ARG); the graphs' own weights are used (plus the
+ * table's trans_cost when one is set, as in khg_align).  Outputs (host, may be NULL):
+ *   ali_h[frame_off[n_utt]]  transition-ids of the best path, 0 where the utterance has no output
+ *   words_h / words_off_h[n_utt+1]: olabels != 0 along the best path (words_cap = capacity)
+ *   like_h[n_utt]   double `like` = -(Value1 + Value2) of the path's LatticeWeight (float sum), not divided by any scale
+ *   status_h[n_utt] KHG_LAT_* bits.
+ * Synchronous.  Does not touch the set's resident alignment. */
+int khg_decode_lattice_faster(khg_ctx *ctx, const khg_tm *tm, khg_utts *u, const khg_lattice_faster_config *cfg,
+                              int32_t *ali_h, int32_t *words_h, int64_t *words_off_h, int64_t words_cap,
+                              double *like_h, int32_t *status_h);
+
 /* ---- K3: sufficient statistics ---------------------------------------------------------- */
 /* AccumAmDiagGmm (csrc/mle-am-diag-gmm.h:93-96) + transition stats (csrc/transition-model.h:176-189)
  * as ONE contiguous fp64 device buffer (a single RCCL all-reduce sums it across GPUs =

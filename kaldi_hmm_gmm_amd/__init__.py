@@ -8,6 +8,8 @@ from ._lib import KhgError  # noqa: F401
 from .align import (AlignConfig, DecodableAmDiagGmmScaled, DecodableAmDiagGmmUnmapped, DecodableInterface, FasterDecoder,  # noqa: F401
                     FasterDecoderOptions, LatticeArc, LatticeWeight, LinearLattice, add_transition_probs, align_batch,
                     align_utterance_wrapper)
+from .align import (DeterminizeLatticePhonePrunedOptions, LatticeFasterDecoder, LatticeFasterDecoderConfig,  # noqa: F401
+                    LatticeFasterDecoderStdVectorFst, decode_lattice_faster_batch, decode_utterance_lattice_faster)
 from .context_dep import (ContextDependency, ContextDependencyInterface, monophone_context_dependency,  # noqa: F401
                           monophone_context_dependency_shared)
 from .device import (ALIGN_DONE, ALIGN_ERROR, ALIGN_EXACT_DP, ALIGN_FALLBACK, ALIGN_RETRIED, Comm, Context, DeviceAccs,  # noqa: F401

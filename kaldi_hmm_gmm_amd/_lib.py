@@ -59,6 +59,22 @@ class AlignConfigC(C.Structure):
     ]
 
 
+class LatticeFasterConfigC(C.Structure):
+    _fields_ = [
+        ("beam", C.c_float),
+        ("max_active", C.c_int32),
+        ("min_active", C.c_int32),
+        ("lattice_beam", C.c_float),
+        ("prune_interval", C.c_int32),
+        ("beam_delta", C.c_float),
+        ("hash_ratio", C.c_float),
+        ("prune_scale", C.c_float),
+        ("acoustic_scale", C.c_float),
+        ("allow_partial", C.c_int32),
+        ("scratch_per_frame", C.c_int32),
+    ]
+
+
 class MleOptionsC(C.Structure):
     _fields_ = [
         ("min_gaussian_weight", C.c_float),
@@ -108,6 +124,9 @@ SIGNATURES = {
     "khg_align_config_default": (None, [C.POINTER(AlignConfigC)]),
     "khg_align": (C.c_int, [vp, vp, vp, C.POINTER(AlignConfigC), c_i32p, c_i32p, c_i64p, C.c_int64, c_f32p, c_i32p]),
     "khg_ali_upload": (C.c_int, [vp, vp, c_i32p]),
+    "khg_lattice_faster_config_default": (None, [C.POINTER(LatticeFasterConfigC)]),
+    "khg_decode_lattice_faster": (C.c_int, [vp, vp, vp, C.POINTER(LatticeFasterConfigC), c_i32p, c_i32p, c_i64p, C.c_int64, c_f64p,
+                                            c_i32p]),
     "khg_ali_download": (C.c_int, [vp, vp, c_i32p]),
     "khg_accs_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     "khg_accs_destroy": (C.c_int, [vp]),

@@ -2,6 +2,7 @@
 #include "khg_host_align.hpp"
 
 #include <cstdio>
+#include <sstream>
 
 namespace khg {
 
@@ -33,6 +34,29 @@ float DecodableAmDiagGmmUnmapped::ZeroBased(int frame, int state) const {
 bool DecodableAmDiagGmmUnmapped::IsLastFrame(int frame) const {
   KHG_REQUIRE(frame < NumFramesReady(), "frame < NumFramesReady() assertion failed");
   return frame == NumFramesReady() - 1;
+}
+
+std::string DeterminizeLatticePhonePrunedOptions::ToString() const {
+  std::ostringstream os;                       // determinize-lattice-pruned.h:85-94
+  os << "DeterminizeLatticePhonePrunedOptions(" << "delta=" << delta << ", " << "max_mem=" << max_mem << ", "
+     << "phone_determinize=" << (phone_determinize ? "True" : "False") << ", " << "word_determinize=" << (word_determinize ? "True" : "False")
+     << ", " << "minimize=" << (minimize ? "True" : "False") << ")";
+  return os.str();
+}
+std::string LatticeFasterDecoderConfig::ToString() const {
+  std::ostringstream os;                       // lattice-faster-decoder.h:77-97
+  os << "LatticeFasterDecoderConfig(" << "beam=" << beam << ", " << "max_active=" << max_active << ", " << "min_active=" << min_active << ", "
+     << "lattice_beam=" << lattice_beam << ", " << "prune_interval=" << prune_interval << ", "
+     << "determinize_lattice=" << (determinize_lattice ? "True" : "False") << ", " << "beam_delta=" << beam_delta << ", "
+     << "hash_ratio=" << hash_ratio << ", " << "prune_scale=" << prune_scale << ", " << "memory_pool_tokens_block_size=" << memory_pool_tokens_block_size
+     << ", " << "memory_pool_links_block_size=" << memory_pool_links_block_size << ")";
+  return os.str();
+}
+void LatticeFasterDecoderConfig::Check() const {    // lattice-faster-decoder.h:99-104
+  KHG_REQUIRE(beam > 0.0 && max_active > 1 && lattice_beam > 0.0 && min_active <= max_active && prune_interval > 0 && beam_delta > 0.0 &&
+                  hash_ratio >= 1.0 && prune_scale > 0.0 && prune_scale < 1.0,
+              "beam > 0.0 && max_active > 1 && lattice_beam > 0.0 && min_active <= max_active && prune_interval > 0 && beam_delta > 0.0 && "
+              "hash_ratio >= 1.0 && prune_scale > 0.0 && prune_scale < 1.0 assertion failed");
 }
 
 namespace {
@@ -108,6 +132,83 @@ std::vector<AlignResult> AlignBatch(const AmDiagGmm& am, const TransitionModel& 
       r.like = like[(size_t)u];
     }
     if (return_scores) {
+      const int64_t T = nframes[(size_t)u], tpad = (T + 31) & ~int64_t(31);
+      const int npdf = (int)(pdf_off[(size_t)u + 1] - pdf_off[(size_t)u]);
+      r.pdfs.assign(pdfs.begin() + pdf_off[(size_t)u], pdfs.begin() + pdf_off[(size_t)u + 1]);
+      r.loglikes.resize((size_t)npdf * (size_t)T);
+      for (int j = 0; j < npdf; ++j)
+        if (T > 0) std::memcpy(r.loglikes.data() + (size_t)j * T, scores.data() + ll_off[(size_t)u] + (size_t)j * tpad, sizeof(float) * (size_t)T);
+    }
+  }
+  return out;
+}
+
+std::vector<LatticeResult> DecodeLatticeOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
+                                              const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial, int scratch_per_frame,
+                                              int64_t total_states) {
+  const int n_utt = (int)frame_off.size() - 1;
+  khg_lattice_faster_config c;
+  khg_lattice_faster_config_default(&c);
+  c.beam = config.beam; c.max_active = config.max_active; c.min_active = config.min_active; c.lattice_beam = config.lattice_beam;
+  c.prune_interval = config.prune_interval; c.beam_delta = config.beam_delta; c.hash_ratio = config.hash_ratio; c.prune_scale = config.prune_scale;
+  c.acoustic_scale = acoustic_scale; c.allow_partial = allow_partial ? 1 : 0; c.scratch_per_frame = scratch_per_frame;
+  const int64_t N = frame_off[(size_t)n_utt];
+  std::vector<int64_t> woff((size_t)n_utt + 1, 0);
+  std::vector<int32_t> ali((size_t)std::max<int64_t>(N, 1)), status((size_t)n_utt);
+  std::vector<double> like((size_t)n_utt);
+  // words: the C-ABI keeps at most frames + states + 64 per utterance
+  std::vector<int32_t> words((size_t)(N + total_states + 64 * (int64_t)n_utt + 16));
+  CApi(khg_decode_lattice_faster(ctx, tm, us, &c, ali.data(), words.data(), woff.data(), (int64_t)words.size(), like.data(), status.data()));
+  std::vector<LatticeResult> out((size_t)n_utt);
+  for (int u = 0; u < n_utt; ++u) {
+    LatticeResult& r = out[(size_t)u];
+    r.status = status[(size_t)u];
+    r.succeeded = (r.status & KHG_LAT_SUCCEEDED) != 0;
+    r.partial = (r.status & KHG_LAT_PARTIAL) != 0;
+    r.num_frames = (int)(frame_off[(size_t)u + 1] - frame_off[(size_t)u]);
+    if (r.succeeded) {
+      r.alignment.assign(ali.begin() + frame_off[(size_t)u], ali.begin() + frame_off[(size_t)u + 1]);
+      r.words.assign(words.begin() + woff[(size_t)u], words.begin() + woff[(size_t)u + 1]);
+      r.like = like[(size_t)u];
+    }
+  }
+  return out;
+}
+
+std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g, const std::vector<const float*>& feats,
+                                              const std::vector<int64_t>& nframes, const LatticeFasterDecoderConfig& config, float acoustic_scale,
+                                              bool allow_partial, bool return_scores, int scratch_per_frame) {
+  config.Check();
+  const int n_utt = (int)feats.size(), D = am.Dim();
+  KHG_REQUIRE((int)nframes.size() == n_utt && (int)g.start.size() == n_utt && (int)g.state_off.size() == n_utt + 1,
+              "decode_lattice_faster_batch: one graph and one feature matrix per utterance");
+  for (int64_t T : nframes) KHG_REQUIRE(T > 0, "num_frames > 0 assertion failed");     // GetRawLattice (lattice-faster-decoder.cc:137)
+  khg_ctx* ctx = DefaultCtx();
+  khg_model* dm = am.DeviceModel(ctx);
+  khg_tm* dt = tm.DeviceTm(ctx);
+  UttsH us;
+  CApi(khg_tm_set_trans_cost(dt, nullptr));       // the graph's own weights (HCLG carries its transition probabilities)
+  std::vector<int64_t> frame_off((size_t)n_utt + 1, 0);
+  for (int u = 0; u < n_utt; ++u) frame_off[(size_t)u + 1] = frame_off[(size_t)u] + nframes[(size_t)u];
+  std::vector<float> all((size_t)std::max<int64_t>(frame_off[(size_t)n_utt], 1) * D);
+  for (int u = 0; u < n_utt; ++u)
+    if (nframes[(size_t)u] > 0) std::memcpy(all.data() + (size_t)frame_off[(size_t)u] * D, feats[(size_t)u], sizeof(float) * (size_t)nframes[(size_t)u] * D);
+  CApi(khg_utts_create(ctx, dt, n_utt, D, frame_off.data(), all.data(), nullptr, g.state_off.data(), g.start.data(), g.arc_off.data(), g.ilabel.data(),
+                       g.olabel.data(), g.weight.data(), g.nextstate.data(), g.final_w.data(), &us.h));
+  CApi(khg_loglikes(ctx, dm, us.h));              // every cell: a partial path may read any (frame, pdf) of the graph
+  std::vector<LatticeResult> out = DecodeLatticeOnSet(ctx, dt, us.h, frame_off, config, acoustic_scale, allow_partial, scratch_per_frame,
+                                                      g.state_off[(size_t)n_utt]);
+  if (return_scores) {
+    std::vector<int64_t> ll_off((size_t)n_utt + 1, 0), pdf_off((size_t)n_utt + 1, 0);
+    int64_t total = 0;
+    CApi(khg_loglikes_layout(us.h, ll_off.data(), &total));
+    std::vector<float> scores((size_t)std::max<int64_t>(total, 1));
+    CApi(khg_loglikes_download(ctx, us.h, scores.data()));
+    CApi(khg_utts_num_pdfs(us.h, pdf_off.data()));
+    std::vector<int32_t> pdfs((size_t)std::max<int64_t>(pdf_off[(size_t)n_utt], 1));
+    CApi(khg_utts_pdfs(us.h, pdfs.data()));
+    for (int u = 0; u < n_utt; ++u) {
+      LatticeResult& r = out[(size_t)u];
       const int64_t T = nframes[(size_t)u], tpad = (T + 31) & ~int64_t(31);
       const int npdf = (int)(pdf_off[(size_t)u + 1] - pdf_off[(size_t)u]);
       r.pdfs.assign(pdfs.begin() + pdf_off[(size_t)u], pdfs.begin() + pdf_off[(size_t)u + 1]);

@@ -26,6 +26,36 @@ struct FasterDecoderOptions {        // csrc/faster-decoder.h:24-63
   std::string ToString() const;
 };
 
+struct DeterminizeLatticePhonePrunedOptions {   // csrc/determinize-lattice-pruned.h:53-95 (stored only: nothing determinises)
+  float delta = 1.0f / 1024.0f;                  // fst::kDelta
+  int32_t max_mem = 50000000;
+  bool phone_determinize = true, word_determinize = true, minimize = false;
+  std::string ToString() const;
+};
+
+struct LatticeFasterDecoderConfig {             // csrc/lattice-faster-decoder.h:30-105
+  float beam = 16.0f;
+  int32_t max_active = std::numeric_limits<int32_t>::max(), min_active = 200;
+  float lattice_beam = 10.0f;
+  int32_t prune_interval = 25;
+  bool determinize_lattice = true;
+  float beam_delta = 0.5f, hash_ratio = 2.0f, prune_scale = 0.1f;
+  int32_t memory_pool_tokens_block_size = 1 << 8, memory_pool_links_block_size = 1 << 8;
+  DeterminizeLatticePhonePrunedOptions det_opts;
+  std::string ToString() const;
+  void Check() const;
+};
+
+struct LatticeResult {               // DecodeUtteranceLatticeFaster's (succeeded, alignment, words, like) + the KHG_LAT_* bits
+  int status = 0;
+  bool succeeded = false, partial = false;
+  std::vector<int32_t> alignment, words;
+  double like = 0.0;
+  int num_frames = 0;
+  std::vector<float> loglikes;       // [npdf][T] (return_scores)
+  std::vector<int32_t> pdfs;
+};
+
 struct GraphsCsr {                   // fst::VectorFst<StdArc> per utterance, concatenated as khg_utts_create takes them
   std::vector<int64_t> state_off, arc_off;
   std::vector<int32_t> start, ilabel, olabel, nextstate;
@@ -101,5 +131,16 @@ std::vector<AlignResult> AlignBatch(const AmDiagGmm& am, const TransitionModel& 
                                     const FasterDecoderOptions* decoder_opts, bool return_scores, float like_scale = 0.0f);
 // (like_scale: divisor of `like` when it is not the score scale -- a decodable whose own scale differs from the wrapper's
 // acoustic_scale argument, csrc/decoder-wrappers.cc:95; 0 = acoustic_scale)
+
+// DecodeUtteranceLatticeFaster (csrc/decoder-wrappers.cc:186-224) for a batch: K1 (every pdf of each utterance's graph) + the lattice
+// decoder (khg_decode_lattice_faster), each utterance on a fresh decoder; scores scaled by acoustic_scale (DecodableAmDiagGmmScaled).
+// scratch_per_frame: 0 = the C-ABI's automatic size.
+std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& graphs, const std::vector<const float*>& feats,
+                                              const std::vector<int64_t>& nframes, const LatticeFasterDecoderConfig& config, float acoustic_scale,
+                                              bool allow_partial, bool return_scores, int scratch_per_frame = 0);
+// the C-ABI call on a prepared set (scores resident) -> results without scores
+std::vector<LatticeResult> DecodeLatticeOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
+                                              const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial, int scratch_per_frame,
+                                              int64_t total_states);
 
 }  // namespace khg

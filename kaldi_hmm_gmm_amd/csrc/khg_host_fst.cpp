@@ -156,6 +156,47 @@ AlignResult AlignDecodable(const StdVectorFst& fst, const DecodableInterface& de
   return r;
 }
 
+LatticeResult DecodeLatticeDecodable(const StdVectorFst& fst, const DecodableInterface& dec, const LatticeFasterDecoderConfig& config,
+                                     bool allow_partial, int scratch_per_frame) {
+  config.Check();
+  KHG_REQUIRE(fst.Start() != kNoStateId, "start_state != fst::kNoStateId assertion failed");   // lattice-faster-decoder.cc:72
+  const int64_t T = dec.NumFramesReady();
+  KHG_REQUIRE(T > 0, "num_frames > 0 assertion failed");     // GetRawLattice (lattice-faster-decoder.cc:137)
+  LatticeResult r;
+  r.num_frames = (int)T;
+  const GraphsCsr g = ConcatGraphs({&fst});
+  int max_index = 0;
+  for (int32_t l : g.ilabel) {
+    KHG_REQUIRE(l >= 0, "decode_utterance_lattice_faster: negative input label on the graph");
+    max_index = std::max(max_index, (int)l);
+  }
+  KHG_REQUIRE(max_index <= dec.NumIndices(), "decode_utterance_lattice_faster: the graph carries index " + std::to_string(max_index) +
+                                                 " but the decodable has " + std::to_string(dec.NumIndices()));
+  std::vector<int32_t> id2pdf((size_t)max_index + 1);
+  id2pdf[0] = -1;
+  for (int i = 1; i <= max_index; ++i) id2pdf[(size_t)i] = i - 1;
+  khg_ctx* ctx = DefaultCtx();
+  TmH dt; UttsH us;
+  CApi(khg_tm_create(ctx, std::max(max_index, 1), id2pdf.data(), &dt.h));
+  const int64_t frame_off[2] = {0, T};
+  const std::vector<float> no_feats((size_t)std::max<int64_t>(T, 1), 0.0f);
+  CApi(khg_utts_create(ctx, dt.h, 1, 1, frame_off, no_feats.data(), nullptr, g.state_off.data(), g.start.data(), g.arc_off.data(), g.ilabel.data(),
+                       g.olabel.data(), g.weight.data(), g.nextstate.data(), g.final_w.data(), &us.h));
+  int64_t pdf_off[2] = {0, 0}, ll_off[2] = {0, 0}, total = 0;
+  CApi(khg_utts_num_pdfs(us.h, pdf_off));
+  const int n = (int)pdf_off[1];
+  std::vector<int32_t> pdfs((size_t)std::max(n, 1));
+  CApi(khg_utts_pdfs(us.h, pdfs.data()));
+  CApi(khg_loglikes_layout(us.h, ll_off, &total));
+  const int64_t tpad = (T + 31) & ~int64_t(31);
+  std::vector<float> scores((size_t)std::max<int64_t>(total, 1), 0.0f);
+  for (int j = 0; j < n; ++j)
+    for (int64_t t = 0; t < T; ++t) scores[(size_t)(ll_off[0] + (int64_t)j * tpad + t)] = dec.LogLikelihood((int)t, pdfs[(size_t)j] + 1);
+  CApi(khg_loglikes_upload(ctx, us.h, scores.data()));
+  // 1.0f * s == s: the decodable scaled its scores itself
+  return DecodeLatticeOnSet(ctx, dt.h, us.h, {0, T}, config, 1.0f, allow_partial, scratch_per_frame, (int64_t)fst.NumStates())[0];
+}
+
 void FasterDecoder::AdvanceDecoding(const std::shared_ptr<DecodableInterface>& dec, int max_num_frames) {
   KHG_REQUIRE(dec != nullptr, "FasterDecoder: no decodable");
   KHG_REQUIRE(!(max_num_frames >= 0 && max_num_frames < dec->NumFramesReady()),

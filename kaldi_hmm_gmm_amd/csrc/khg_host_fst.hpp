@@ -58,6 +58,18 @@ void AddTransitionProbs(const TransitionModel& tm, const std::vector<int>& disam
 AlignResult AlignDecodable(const StdVectorFst& fst, const DecodableInterface& decodable, const AlignConfig& config, float like_scale,
                            const FasterDecoderOptions* decoder_opts);
 
+// DecodeUtteranceLatticeFaster for ANY DecodableInterface: scores of every (frame, index on the graph) sampled through the interface
+// (as AlignDecodable does) and decoded unscaled by the lattice decoder.
+LatticeResult DecodeLatticeDecodable(const StdVectorFst& fst, const DecodableInterface& decodable, const LatticeFasterDecoderConfig& config,
+                                     bool allow_partial, int scratch_per_frame = 0);
+
+// python/csrc/lattice-faster-decoder.cc:46-56: the decoder object holds its graph and configuration; the work is done by
+// decode_utterance_lattice_faster (DecodeUtteranceLatticeFaster), each call on a fresh decoder state.
+struct LatticeFasterDecoder {
+  std::shared_ptr<StdVectorFst> fst;
+  LatticeFasterDecoderConfig config;
+};
+
 struct LatticeWeight {        // kaldifst LatticeWeight (graph cost, acoustic cost); Times adds component-wise
   double value1 = 0.0, value2 = 0.0;
 };

@@ -1,8 +1,10 @@
 // kaldi_hmm_gmm_amd/csrc/khg_k2.hip -- C-ABI (include/khg_hip.h): K2, Viterbi forced alignment (khg_align): kernel selection by graph
-// shape, LDS budgets, the exact DP on the main stream and the order-faithful decoder on a side stream.  gfx950 only.
+// shape, LDS budgets, the exact DP on the main stream and the order-faithful decoder on a side stream; and the lattice decoder
+// (khg_decode_lattice_faster, khg_k2_lattice.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
 
 #include "khg_k2_viterbi.hip.inc"
+#include "khg_k2_lattice.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // K2
@@ -342,5 +344,156 @@ extern "C" int khg_ali_download(khg_ctx* ctx, khg_utts* u, int32_t* ali) {
   if (rc) return rc;
   if (u->N) HIPCHK(hipMemcpyAsync(ali, u->ali_d, sizeof(int32_t) * (size_t)u->N, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2L: LatticeFasterDecoder (khg_k2_lattice.hip.inc)
+extern "C" void khg_lattice_faster_config_default(khg_lattice_faster_config* c) {
+  c->beam = 16.0f; c->max_active = INT32_MAX; c->min_active = 200; c->lattice_beam = 10.0f; c->prune_interval = 25;
+  c->beam_delta = 0.5f; c->hash_ratio = 2.0f; c->prune_scale = 0.1f; c->acoustic_scale = 1.0f; c->allow_partial = 1;
+  c->scratch_per_frame = 0;
+}
+
+extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_faster_config* cfg,
+                                         int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                         double* like_h, int32_t* status_h) {
+  if (ctx_dead(ctx) || !tm || !u || !cfg) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: bad arguments");
+  { int rf = utts_foreign_ctx(ctx, u, "khg_decode_lattice_faster"); if (rf) return rf; }
+  if (!u->has_graphs) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: the utterance set has no decoding graphs");
+  if (!u->ll_valid) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: call khg_loglikes first");
+  // khg_loglikes_band leaves upper bounds in the cells past the band: a token of a partial (or pruned-late) path may read any cell
+  if (u->ll_mode == 2)
+    return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: the scores come from khg_loglikes_band; call khg_loglikes (every cell) first");
+  // LatticeFasterDecoderConfig::Check (csrc/lattice-faster-decoder.h:99-104)
+  if (!(cfg->beam > 0.0f && cfg->max_active > 1 && cfg->lattice_beam > 0.0f && cfg->min_active <= cfg->max_active &&
+        cfg->prune_interval > 0 && cfg->beam_delta > 0.0f && cfg->hash_ratio >= 1.0f && cfg->prune_scale > 0.0f && cfg->prune_scale < 1.0f) ||
+      cfg->min_active < 0 || cfg->scratch_per_frame < 0)
+    return khg_set_error(KHG_E_RUNTIME, "LatticeFasterDecoderConfig assertion failed");
+  int rc = wait_ali(ctx, u);
+  if (!rc) rc = k1_band_check(ctx, u);
+  if (rc) return rc;
+  const int U = u->n_utt;
+  if (U == 0) return KHG_OK;
+  const int64_t hb = std::max<int64_t>(1000, (int64_t)((float)u->max_states * cfg->hash_ratio)) + 1;
+  const int64_t Amax = u->max_inarcs;     // (the kernel lays every slice out with the same arc bound)
+  std::vector<int64_t> wcap_off((size_t)U + 1, 0);
+  for (int i = 0; i < U; ++i) wcap_off[(size_t)i + 1] = wcap_off[(size_t)i] + (u->frame_off[i + 1] - u->frame_off[i]) + (u->state_off[i + 1] - u->state_off[i]) + 64;
+  const int64_t N = u->N, NW = wcap_off[(size_t)U];
+  struct Dev {
+    std::vector<void*> p;
+    ~Dev() { for (void* q : p) if (q) (void)hipFree(q); }
+  } dv;
+  auto dalloc = [&](size_t n, void** out) -> int {
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, std::max<size_t>(n, 16)));
+    dv.p.push_back(q);
+    *out = q;
+    return KHG_OK;
+  };
+  int32_t *ali_d, *words_d, *nw_d, *status_d; double* like_d; int64_t* woff_d;
+  if ((rc = dalloc(4 * (size_t)std::max<int64_t>(N, 1), reinterpret_cast<void**>(&ali_d))) ||
+      (rc = dalloc(4 * (size_t)std::max<int64_t>(NW, 1), reinterpret_cast<void**>(&words_d))) ||
+      (rc = dalloc(4 * (size_t)U, reinterpret_cast<void**>(&nw_d))) || (rc = dalloc(4 * (size_t)U, reinterpret_cast<void**>(&status_d))) ||
+      (rc = dalloc(8 * (size_t)U, reinterpret_cast<void**>(&like_d))) || (rc = dalloc(8 * ((size_t)U + 1), reinterpret_cast<void**>(&woff_d))))
+    return rc;
+  rc = arena_flush(ctx);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(woff_d, wcap_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>(N, 1), ctx->stream));
+  LatArgs a;
+  a.frame_off = u->frame_off_d; a.state_off = u->state_off_d; a.start = u->start_d;
+  a.in_off = u->in_off_d; a.in_col = u->in_col_d; a.in_tid = u->in_tid_d; a.in_olabel = u->in_olabel_d; a.in_w = u->in_w_d;
+  a.out_off = u->out_off_d; a.out_inidx = u->out_inidx_d; a.final_w = u->final_d;
+  a.trans_cost = tm->has_trans_cost ? tm->trans_cost_d : nullptr;
+  a.ll = u->ll_d; a.ll_off = u->ll_off_d;
+  a.hb = (int32_t)hb; a.amax = (int32_t)Amax;
+  a.ali = ali_d; a.words = words_d; a.words_off = woff_d; a.num_words = nw_d; a.like = like_d; a.status = status_d;
+  a.beam = cfg->beam; a.lattice_beam = cfg->lattice_beam; a.beam_delta = cfg->beam_delta; a.hash_ratio = cfg->hash_ratio;
+  a.prune_scale = cfg->prune_scale; a.acoustic_scale = cfg->acoustic_scale;
+  a.max_active = cfg->max_active; a.min_active = cfg->min_active; a.prune_interval = cfg->prune_interval; a.allow_partial = cfg->allow_partial ? 1 : 0;
+  // One pass over a list of utterances: each gets a scratch slice of `per_frame` tokens / links per frame (0: the automatic size,
+  // -1: the whole graph per frame, i.e. an utterance can never run out); slices are grouped into launches of <= 4 GiB of scratch.
+  auto run = [&](const std::vector<int32_t>& list, int64_t per_frame) -> int {
+    const size_t L = list.size();
+    std::vector<int32_t> tcap(L), lcap(L);
+    std::vector<int64_t> bytes(L);
+    for (size_t k = 0; k < L; ++k) {
+      const int i = list[k];
+      const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = u->state_off[i + 1] - u->state_off[i], A = std::max<int64_t>(Amax, 1);
+      const int64_t pt = per_frame > 0 ? per_frame : per_frame < 0 ? S : std::min<int64_t>(S, 256);
+      const int64_t pl = per_frame > 0 ? per_frame : per_frame < 0 ? A : std::min<int64_t>(A, 1024);
+      const int64_t tc = (T + 1) * pt + (per_frame > 0 ? 0 : S) + 1, lc = (T + 1) * pl + (per_frame > 0 ? 0 : A) + 1;
+      if (tc > INT32_MAX / 2 || lc > INT32_MAX / 2) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: utterance too large for the scratch");
+      tcap[k] = (int32_t)tc; lcap[k] = (int32_t)lc;
+      bytes[k] = (lat_layout(T, S, Amax, hb, tc, lc).total + 255) & ~int64_t(255);
+    }
+    const int64_t budget = int64_t(4) << 30;
+    std::vector<size_t> cb{0};
+    std::vector<int64_t> rel(L);
+    int64_t acc = 0, max_chunk = 0;
+    for (size_t k = 0; k < L; ++k) {
+      if (acc > 0 && acc + bytes[k] > budget) { max_chunk = std::max(max_chunk, acc); cb.push_back(k); acc = 0; }
+      rel[k] = acc;                    // relative to the launch's first slice
+      acc += bytes[k];
+    }
+    max_chunk = std::max(max_chunk, acc);
+    cb.push_back(L);
+    unsigned char* scratch; int64_t* scr_off_d; int32_t *tcap_d, *lcap_d, *list_d;
+    int r;
+    if ((r = dalloc((size_t)max_chunk, reinterpret_cast<void**>(&scratch))) || (r = dalloc(8 * L, reinterpret_cast<void**>(&scr_off_d))) ||
+        (r = dalloc(4 * L, reinterpret_cast<void**>(&tcap_d))) || (r = dalloc(4 * L, reinterpret_cast<void**>(&lcap_d))) ||
+        (r = dalloc(4 * L, reinterpret_cast<void**>(&list_d))))
+      return r;
+    HIPCHK(hipMemcpyAsync(scr_off_d, rel.data(), 8 * L, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tcap_d, tcap.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(lcap_d, lcap.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(list_d, list.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
+    a.scratch = scratch; a.scr_off = scr_off_d; a.tok_cap = tcap_d; a.link_cap = lcap_d; a.list = list_d;
+    for (size_t c = 0; c + 1 < cb.size(); ++c) {
+      KernelTimer kt(ctx, "k2_lattice_faster");
+      KHG_LAUNCH(ctx, k2_lattice_faster, dim3((unsigned)(cb[c + 1] - cb[c])), dim3(64), 0, ctx->stream, a, (int)cb[c]);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));    // the slices are freed with `dv` or reused by the next pass
+    return KHG_OK;
+  };
+  std::vector<int32_t> all((size_t)U);
+  for (int i = 0; i < U; ++i) all[(size_t)i] = i;
+  rc = run(all, cfg->scratch_per_frame);
+  if (!rc) rc = check_err_flag(ctx, "khg_decode_lattice_faster");     // synchronises
+  if (rc) return rc;
+  std::vector<int32_t> st((size_t)U), nw((size_t)U), w((size_t)std::max<int64_t>(NW, 1));
+  HIPCHK(hipMemcpy(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost));
+  if (cfg->scratch_per_frame == 0) {
+    // the automatic size ran out: those utterances again with room for every state and arc on every frame (a frame never holds more)
+    std::vector<int32_t> again;
+    for (int i = 0; i < U; ++i) if (st[(size_t)i] & KHG_LAT_SCRATCH) again.push_back(i);
+    if (!again.empty()) {
+      rc = run(again, -1);
+      if (!rc) rc = check_err_flag(ctx, "khg_decode_lattice_faster");
+      if (rc) return rc;
+      HIPCHK(hipMemcpy(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost));
+    }
+  }
+  if (ali_h && N) HIPCHK(hipMemcpyAsync(ali_h, ali_d, 4 * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
+  if (like_h) HIPCHK(hipMemcpyAsync(like_h, like_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  if (words_h && words_off_h) {
+    HIPCHK(hipMemcpyAsync(nw.data(), nw_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(w.data(), words_d, 4 * (size_t)std::max<int64_t>(NW, 1), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (words_h && words_off_h) {
+    int64_t o = 0;
+    for (int i = 0; i < U; ++i) {
+      words_off_h[i] = o;
+      const int64_t n = (st[(size_t)i] & KHG_LAT_SUCCEEDED) ? nw[(size_t)i] : 0;
+      if (o + n > words_cap) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: words_cap too small");
+      std::copy(w.begin() + wcap_off[(size_t)i], w.begin() + wcap_off[(size_t)i] + n, words_h + o);
+      o += n;
+    }
+    words_off_h[U] = o;
+  }
   return KHG_OK;
 }

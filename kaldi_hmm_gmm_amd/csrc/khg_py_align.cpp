@@ -118,7 +118,129 @@ py::list AlignBatchPy(std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionM
   }
   return ResultsToList(rs, nf, return_scores);
 }
+py::dict LatticeToDict(const LatticeResult& r, int64_t T, bool return_scores) {
+  py::dict d;
+  d["succeeded"] = r.succeeded; d["partial"] = r.partial; d["status"] = r.status;
+  d["alignment"] = py::cast(r.alignment); d["words"] = py::cast(r.words); d["like"] = r.like; d["num_frames"] = r.num_frames;
+  if (return_scores) {
+    Arr<float> m({(py::ssize_t)r.pdfs.size(), (py::ssize_t)T});
+    if (!r.loglikes.empty()) std::memcpy(m.mutable_data(), r.loglikes.data(), sizeof(float) * r.loglikes.size());
+    d["loglikes"] = m;
+    d["pdfs"] = Vec1(r.pdfs);
+  }
+  return d;
+}
 }  // namespace
+
+void BindLattice(py::module_& m) {
+  // python/csrc/determinize-lattice-pruned.cc:13-25
+  py::class_<DeterminizeLatticePhonePrunedOptions>(m, "DeterminizeLatticePhonePrunedOptions")
+      .def(py::init([](float delta, int32_t max_mem, bool pd, bool wd, bool mn) {
+             DeterminizeLatticePhonePrunedOptions o;
+             o.delta = delta; o.max_mem = max_mem; o.phone_determinize = pd; o.word_determinize = wd; o.minimize = mn;
+             return o;
+           }), py::arg("delta") = 1.0f / 1024.0f, py::arg("max_mem") = 50000000, py::arg("phone_determinize") = true, py::arg("word_determinize") = true,
+           py::arg("minimize") = false)
+      .def_readwrite("delta", &DeterminizeLatticePhonePrunedOptions::delta).def_readwrite("max_mem", &DeterminizeLatticePhonePrunedOptions::max_mem)
+      .def_readwrite("phone_determinize", &DeterminizeLatticePhonePrunedOptions::phone_determinize)
+      .def_readwrite("word_determinize", &DeterminizeLatticePhonePrunedOptions::word_determinize)
+      .def_readwrite("minimize", &DeterminizeLatticePhonePrunedOptions::minimize)
+      .def("__str__", &DeterminizeLatticePhonePrunedOptions::ToString);
+
+  // python/csrc/lattice-faster-decoder.cc:14-44
+  using Cfg = LatticeFasterDecoderConfig;
+  py::class_<Cfg>(m, "LatticeFasterDecoderConfig")
+      .def(py::init([](float beam, int32_t max_active, int32_t min_active, float lattice_beam, int32_t prune_interval, bool determinize_lattice,
+                       float beam_delta, float hash_ratio, float prune_scale, int32_t tb, int32_t lb, const DeterminizeLatticePhonePrunedOptions& det) {
+             Cfg c;
+             c.beam = beam; c.max_active = max_active; c.min_active = min_active;
+             c.lattice_beam = lattice_beam; c.prune_interval = prune_interval; c.determinize_lattice = determinize_lattice; c.beam_delta = beam_delta;
+             c.hash_ratio = hash_ratio; c.prune_scale = prune_scale; c.memory_pool_tokens_block_size = tb; c.memory_pool_links_block_size = lb;
+             c.det_opts = det;
+             return c;
+           }), py::arg("beam") = 16.0f, py::arg("max_active") = std::numeric_limits<int32_t>::max(), py::arg("min_active") = 200,
+           py::arg("lattice_beam") = 10.0f, py::arg("prune_interval") = 25, py::arg("determinize_lattice") = true, py::arg("beam_delta") = 0.5f,
+           py::arg("hash_ratio") = 2.0f, py::arg("prune_scale") = 0.1f, py::arg("memory_pool_tokens_block_size") = 1 << 8,
+           py::arg("memory_pool_links_block_size") = 1 << 8, py::arg("det_opts") = DeterminizeLatticePhonePrunedOptions{})
+      .def_readwrite("beam", &Cfg::beam).def_readwrite("max_active", &Cfg::max_active).def_readwrite("min_active", &Cfg::min_active)
+      .def_readwrite("lattice_beam", &Cfg::lattice_beam).def_readwrite("prune_interval", &Cfg::prune_interval)
+      .def_readwrite("determinize_lattice", &Cfg::determinize_lattice).def_readwrite("beam_delta", &Cfg::beam_delta)
+      .def_readwrite("hash_ratio", &Cfg::hash_ratio).def_readwrite("prune_scale", &Cfg::prune_scale)
+      .def_readwrite("memory_pool_tokens_block_size", &Cfg::memory_pool_tokens_block_size)
+      .def_readwrite("memory_pool_links_block_size", &Cfg::memory_pool_links_block_size)
+      .def_readwrite("det_opts", &Cfg::det_opts)
+      .def("__str__", &Cfg::ToString);
+
+  // python/csrc/lattice-faster-decoder.cc:46-66 (the StdVectorFst instantiation is the same class here)
+  py::class_<LatticeFasterDecoder>(m, "LatticeFasterDecoder")
+      .def(py::init([](std::shared_ptr<StdVectorFst> fst, const Cfg& config) {
+             if (!fst) throw Error("LatticeFasterDecoder: fst is None");
+             config.Check();
+             return LatticeFasterDecoder{std::move(fst), config};
+           }), py::arg("fst"), py::arg("config"))
+      .def_property_readonly("_config", [](const LatticeFasterDecoder& d) { return d.config; });
+  m.attr("LatticeFasterDecoderStdVectorFst") = m.attr("LatticeFasterDecoder");
+
+  // python/csrc/decoder-wrappers.cc:70-90 -> (succeeded, alignment, words, like)
+  m.def("decode_utterance_lattice_faster", [](LatticeFasterDecoder& decoder, std::shared_ptr<DecodableInterface> decodable,
+                                              const TransitionInformation& /*trans_model: the reference only passes it on*/,
+                                              const std::string& utt, bool allow_partial) {
+    if (!decodable) throw Error("decode_utterance_lattice_faster: decodable is None");
+    LatticeResult r;
+    if (auto dec = std::dynamic_pointer_cast<DecodableAmDiagGmmScaled>(decodable)) {
+      py::gil_scoped_release nogil;
+      r = DecodeLatticeBatch(*dec->am(), *dec->tm(), ConcatGraphs({decoder.fst.get()}), {dec->feats().data()}, {(int64_t)dec->NumFramesReady()},
+                             decoder.config, dec->scale(), allow_partial, false)[0];
+    } else {
+      r = DecodeLatticeDecodable(*decoder.fst, *decodable, decoder.config, allow_partial);     // GIL held: the scores may come from Python
+    }
+    // what the reference stops on (KHG_ERR / KHG_ASSERT) raises here too
+    if (r.status & KHG_LAT_EPS_LOOP) throw Error("Epsilon loops exist in your decoding graph (this is not allowed!)");
+    if (r.status & KHG_LAT_NO_TRACEBACK) throw Error("Failed to get traceback for utterance " + utt);
+    if (r.status & KHG_LAT_SCRATCH) throw Error("decode_utterance_lattice_faster: out of lattice scratch (queue / sort bound) for utterance " + utt);
+    if (r.status & KHG_LAT_WORDS) throw Error("decode_utterance_lattice_faster: more words on the best path than the output holds for utterance " + utt);
+    return py::make_tuple(r.succeeded, r.alignment, r.words, r.like);
+  }, py::arg("decoder"), py::arg("decodable"), py::arg("trans_model"), py::arg("utt"), py::arg("allow_partial"));
+
+  // the batched form: decode_lattice_faster_batch(am, tm, fsts, feats_list, config, acoustic_scale, allow_partial=True, return_scores=False)
+  // -> one dict per utterance (succeeded, partial, status, alignment, words, like, num_frames[, loglikes, pdfs]); fsts may be one graph
+  m.def("decode_lattice_faster_batch", [](std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, py::object fsts, py::list feats_list,
+                                          const Cfg& config, float acoustic_scale, bool allow_partial, bool return_scores, int scratch_per_frame) {
+    const int D = am->Dim();
+    std::vector<Arr<float>> keep;
+    std::vector<const float*> fp;
+    std::vector<int64_t> nf;
+    for (py::handle f : feats_list) {
+      Arr<float> a = f.cast<Arr<float>>();
+      if (D <= 0 || a.size() % D != 0) throw Error("Dim mismatch: data dim vs. model dim = " + std::to_string(D));
+      keep.push_back(a);
+      fp.push_back(a.data());
+      nf.push_back((int64_t)(a.size() / D));
+    }
+    std::vector<const StdVectorFst*> gp;
+    std::vector<std::shared_ptr<StdVectorFst>> hold;
+    if (py::isinstance<StdVectorFst>(fsts)) {
+      hold.push_back(fsts.cast<std::shared_ptr<StdVectorFst>>());
+      for (size_t i = 0; i < fp.size(); ++i) gp.push_back(hold[0].get());
+    } else {
+      hold = fsts.cast<std::vector<std::shared_ptr<StdVectorFst>>>();
+      if (hold.size() == 1) for (size_t i = 0; i < fp.size(); ++i) gp.push_back(hold[0].get());
+      else for (auto& f : hold) gp.push_back(f.get());
+    }
+    if (gp.size() != fp.size()) throw Error("decode_lattice_faster_batch: one graph, or one graph per utterance");
+    for (auto* g : gp) if (!g || g->Start() == kNoStateId) throw Error("start_state != fst::kNoStateId assertion failed");
+    std::vector<LatticeResult> rs;
+    {
+      const GraphsCsr csr = ConcatGraphs(gp);
+      py::gil_scoped_release nogil;
+      rs = DecodeLatticeBatch(*am, *tm, csr, fp, nf, config, acoustic_scale, allow_partial, return_scores, scratch_per_frame);
+    }
+    py::list out;
+    for (size_t u = 0; u < rs.size(); ++u) out.append(LatticeToDict(rs[u], nf[u], return_scores));
+    return out;
+  }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"), py::arg("allow_partial") = true,
+     py::arg("return_scores") = false, py::arg("scratch_per_frame") = 0);
+}
 
 void BindAlign(py::module_& m) {
   py::class_<AlignConfig>(m, "AlignConfig")      // csrc/decoder-wrappers.h:23-37

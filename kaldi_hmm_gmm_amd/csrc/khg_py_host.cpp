@@ -471,6 +471,7 @@ void BindGmm(py::module_& m) {
 
 void BindHmm(py::module_& m);      // khg_py_hmm.cpp
 void BindAlign(py::module_& m);    // khg_py_align.cpp
+void BindLattice(py::module_& m);  // khg_py_align.cpp
 
 void BindHost(py::module_& m, py::object* error_class) {
   static py::object* err = error_class;
@@ -485,4 +486,5 @@ void BindHost(py::module_& m, py::object* error_class) {
   BindGmm(m);
   BindHmm(m);
   BindAlign(m);
+  BindLattice(m);
 }

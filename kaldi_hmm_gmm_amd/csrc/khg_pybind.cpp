@@ -479,6 +479,27 @@ struct KUtts {
     }
     Check(NoGil([&] { return khg_loglikes_upload(ctx->h, h, buf.data()); }));
   }
+  // khg_decode_lattice_faster on the resident scores (which must not come from loglikes(band=True))
+  py::dict decode_lattice_faster(KTransitions& tm, float beam, int32_t max_active, int32_t min_active, float lattice_beam, int32_t prune_interval,
+                                 float beam_delta, float hash_ratio, float prune_scale, float acoustic_scale, bool allow_partial, int32_t scratch_per_frame) {
+    khg_lattice_faster_config c;
+    khg_lattice_faster_config_default(&c);
+    c.beam = beam; c.max_active = max_active; c.min_active = min_active; c.lattice_beam = lattice_beam; c.prune_interval = prune_interval;
+    c.beam_delta = beam_delta; c.hash_ratio = hash_ratio; c.prune_scale = prune_scale; c.acoustic_scale = acoustic_scale;
+    c.allow_partial = allow_partial ? 1 : 0; c.scratch_per_frame = scratch_per_frame;
+    const int64_t N = frame_off.at(n_utt), wcap = 2 * N + 1024 * (int64_t)n_utt + 1024;
+    Arr<int32_t> ali({(py::ssize_t)(N > 0 ? N : 1)}), words({(py::ssize_t)wcap}), status({(py::ssize_t)n_utt});
+    Arr<int64_t> woff({(py::ssize_t)n_utt + 1});
+    Arr<double> like({(py::ssize_t)n_utt});
+    Check(NoGil([&] { return khg_decode_lattice_faster(ctx->h, tm.h, h, &c, ali.mutable_data(), words.mutable_data(), woff.mutable_data(), wcap,
+                                                       like.mutable_data(), status.mutable_data()); }));
+    py::dict d;
+    d["ali"] = py::array(ali)[py::slice(0, N, 1)];
+    d["like"] = like; d["status"] = status;
+    d["words"] = py::array(words)[py::slice(0, woff.at(n_utt), 1)];
+    d["words_off"] = woff;
+    return d;
+  }
   py::object align(KTransitions& tm, float beam, float retry_beam, float acoustic_scale, bool careful, int64_t max_active, int min_active,
                    float beam_delta, float hash_ratio, py::object download) {
     khg_align_config c;
@@ -606,6 +627,10 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("align", &KUtts::align, py::arg("tm"), py::arg("beam") = 200.0f, py::arg("retry_beam") = 0.0f, py::arg("acoustic_scale") = 1.0f,
            py::arg("careful") = false, py::arg("max_active") = (int64_t)std::numeric_limits<int32_t>::max(), py::arg("min_active") = 20,
            py::arg("beam_delta") = 0.5f, py::arg("hash_ratio") = 2.0f, py::arg("download") = true)
+      .def("decode_lattice_faster", &KUtts::decode_lattice_faster, py::arg("tm"), py::arg("beam") = 16.0f,
+           py::arg("max_active") = std::numeric_limits<int32_t>::max(), py::arg("min_active") = 200, py::arg("lattice_beam") = 10.0f,
+           py::arg("prune_interval") = 25, py::arg("beam_delta") = 0.5f, py::arg("hash_ratio") = 2.0f, py::arg("prune_scale") = 0.1f,
+           py::arg("acoustic_scale") = 1.0f, py::arg("allow_partial") = true, py::arg("scratch_per_frame") = 0)
       .def("upload_ali", &KUtts::upload_ali).def("download_ali", &KUtts::download_ali)
       .def("acc_stats", &KUtts::acc_stats, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f)
       .def("acc_stats_reduce", &KUtts::acc_stats_reduce, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f,
