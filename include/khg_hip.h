@@ -313,6 +313,41 @@ int khg_decode_lattice_faster(khg_ctx *ctx, const khg_tm *tm, khg_utts *u, const
                               int32_t *ali_h, int32_t *words_h, int64_t *words_off_h, int64_t words_cap,
                               double *like_h, int32_t *status_h);
 
+/* ---- K2S: LatticeSimpleDecoder + DecodeUtteranceLatticeSimple --------------------------------------------------------------- */
+typedef struct {
+  /* LatticeSimpleDecoderConfig (csrc/lattice-simple-decoder.h:26-79; pybind defaults python/csrc/lattice-simple-decoder.cc:15-21) */
+  float beam;             /* 16 */
+  float lattice_beam;     /* 10 */
+  int32_t prune_interval; /* 25 */
+  float prune_scale;      /* 0.1 (interval pruning never changes the answer; kept for the reference's Check and ToString) */
+  /* DecodableAmDiagGmmScaled's scale, as in khg_lattice_faster_config */
+  float acoustic_scale;   /* 1 */
+  /* DecodeUtteranceLatticeSimple's allow_partial (csrc/decoder-wrappers.cc:142-182): accepted and ignored -- Decode() is false
+   * whenever no final state is live on the last frame, and the wrapper stops there (no partial output) */
+  int32_t allow_partial;  /* 1 */
+  /* the most live tokens one frame may hold: an utterance with a frame over it gets KHG_LAT_SCRATCH and no output.  0: no limit
+   * (the per-frame rows are dense, so an utterance never runs out) */
+  int32_t scratch_per_frame; /* 0 */
+} khg_lattice_simple_config;
+void khg_lattice_simple_config_default(khg_lattice_simple_config *c);
+
+/* further status bits of khg_decode_lattice_simple (with KHG_LAT_SUCCEEDED, _SCRATCH, _NO_PATH, _EPS_LOOP, _WORDS, _NO_TRACEBACK,
+ * which mean here: _NO_PATH Decode() false, no final state live on the last frame (lattice-simple-decoder.cc:160-164), or no start
+ * state (start < 0; the reference asserts start_state != kNoStateId, :52);
+ * _EPS_LOOP a negative-cost epsilon cycle, on which the reference's ProcessNonemitting never ends; _NO_TRACEBACK also a zero-frame
+ * utterance whose start closure is final: GetRawLattice's KHG_ASSERT(num_frames > 0), "Check failed!" (:680)) */
+#define KHG_LAT_NO_EPS_TOKEN 128 /* "Error in ProcessNonEmitting: no surviving tokens: frame is <err_frame>" (:95-101)       */
+#define KHG_LAT_NAN 256          /* a NaN forward link reached PruneForwardLinks' KHG_ASSERT (:261): "Check failed!"       */
+
+/* LatticeSimpleDecoder::Decode (csrc/lattice-simple-decoder.cc:144-165) + GetBestPath (:644-735: GetRawLattice + OpenFst
+ * ShortestPath) + DecodeUtteranceLatticeSimple (csrc/decoder-wrappers.cc:142-182) for every utterance of the set, each on a fresh
+ * decoder.  Scores as for khg_decode_lattice_faster (KHG_E_ARG for khg_loglikes_band).  Outputs (host, may be NULL) as there, plus
+ *   err_frame_h[n_utt]  the frame of KHG_LAT_NO_EPS_TOKEN's message (-1 at InitDecoding), -1 otherwise.
+ * Synchronous.  Does not touch the set's resident alignment. */
+int khg_decode_lattice_simple(khg_ctx *ctx, const khg_tm *tm, khg_utts *u, const khg_lattice_simple_config *cfg,
+                              int32_t *ali_h, int32_t *words_h, int64_t *words_off_h, int64_t words_cap,
+                              double *like_h, int32_t *status_h, int32_t *err_frame_h);
+
 /* ---- K3: sufficient statistics ---------------------------------------------------------- */
 /* AccumAmDiagGmm (csrc/mle-am-diag-gmm.h:93-96) + transition stats (csrc/transition-model.h:176-189)
  * as ONE contiguous fp64 device buffer (a single RCCL all-reduce sums it across GPUs =

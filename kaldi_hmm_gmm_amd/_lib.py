@@ -75,6 +75,18 @@ class LatticeFasterConfigC(C.Structure):
     ]
 
 
+class LatticeSimpleConfigC(C.Structure):
+    _fields_ = [
+        ("beam", C.c_float),
+        ("lattice_beam", C.c_float),
+        ("prune_interval", C.c_int32),
+        ("prune_scale", C.c_float),
+        ("acoustic_scale", C.c_float),
+        ("allow_partial", C.c_int32),
+        ("scratch_per_frame", C.c_int32),
+    ]
+
+
 class MleOptionsC(C.Structure):
     _fields_ = [
         ("min_gaussian_weight", C.c_float),
@@ -127,6 +139,9 @@ SIGNATURES = {
     "khg_lattice_faster_config_default": (None, [C.POINTER(LatticeFasterConfigC)]),
     "khg_decode_lattice_faster": (C.c_int, [vp, vp, vp, C.POINTER(LatticeFasterConfigC), c_i32p, c_i32p, c_i64p, C.c_int64, c_f64p,
                                             c_i32p]),
+    "khg_lattice_simple_config_default": (None, [C.POINTER(LatticeSimpleConfigC)]),
+    "khg_decode_lattice_simple": (C.c_int, [vp, vp, vp, C.POINTER(LatticeSimpleConfigC), c_i32p, c_i32p, c_i64p, C.c_int64, c_f64p,
+                                            c_i32p, c_i32p]),
     "khg_ali_download": (C.c_int, [vp, vp, c_i32p]),
     "khg_accs_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     "khg_accs_destroy": (C.c_int, [vp]),

@@ -59,6 +59,23 @@ void LatticeFasterDecoderConfig::Check() const {    // lattice-faster-decoder.h:
               "hash_ratio >= 1.0 && prune_scale > 0.0 && prune_scale < 1.0 assertion failed");
 }
 
+std::string LatticeSimpleDecoderConfig::ToString() const {
+  std::ostringstream os;                       // lattice-simple-decoder.h:59-74
+  os << "LatticeSimpleDecoderConfig(" << "beam=" << beam << ", " << "lattice_beam=" << lattice_beam << ", " << "prune_interval=" << prune_interval
+     << ", " << "determinize_lattice=" << (determinize_lattice ? "True" : "False") << ", " << "prune_lattice=" << (prune_lattice ? "True" : "False")
+     << ", " << "beam_ratio=" << beam_ratio << ", " << "prune_scale=" << prune_scale << ", " << "det_opts=" << det_opts.ToString() << ")";
+  return os.str();
+}
+void LatticeSimpleDecoderConfig::Check() const {    // lattice-simple-decoder.h:76-78 (KHG_ASSERT)
+  KHG_REQUIRE(beam > 0.0 && lattice_beam > 0.0 && prune_interval > 0, "Check failed!\nx: beam > 0.0 && lattice_beam > 0.0 && prune_interval > 0");
+}
+
+float DecodableCtc::LogLikelihood(int frame, int index) const {    // decodable-ctc.cc:15-22 (its assert is compiled out there)
+  KHG_REQUIRE(index >= 1, "DecodableCtc: index >= 1 assertion failed");
+  KHG_REQUIRE(frame >= 0 && frame < rows_ && index <= cols_, "DecodableCtc: (frame, index) out of range");
+  return Row(frame)[index - 1];
+}
+
 namespace {
 struct UttsH { khg_utts* h = nullptr; ~UttsH() { if (h) khg_utts_destroy(h); } };
 std::string G(double x) { char b[64]; std::snprintf(b, sizeof(b), "%g", x); return b; }
@@ -175,14 +192,14 @@ std::vector<LatticeResult> DecodeLatticeOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts
   return out;
 }
 
-std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g, const std::vector<const float*>& feats,
-                                              const std::vector<int64_t>& nframes, const LatticeFasterDecoderConfig& config, float acoustic_scale,
-                                              bool allow_partial, bool return_scores, int scratch_per_frame) {
-  config.Check();
+namespace {
+// K1 (every pdf of each utterance's graph) on a fresh set, then `on_set(ctx, tm, set, frame_off)`; scores copied back when asked
+template <class OnSet>
+std::vector<LatticeResult> K1ThenDecode(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g, const std::vector<const float*>& feats,
+                                        const std::vector<int64_t>& nframes, bool return_scores, const std::string& name, OnSet on_set) {
   const int n_utt = (int)feats.size(), D = am.Dim();
   KHG_REQUIRE((int)nframes.size() == n_utt && (int)g.start.size() == n_utt && (int)g.state_off.size() == n_utt + 1,
-              "decode_lattice_faster_batch: one graph and one feature matrix per utterance");
-  for (int64_t T : nframes) KHG_REQUIRE(T > 0, "num_frames > 0 assertion failed");     // GetRawLattice (lattice-faster-decoder.cc:137)
+              name + ": one graph and one feature matrix per utterance");
   khg_ctx* ctx = DefaultCtx();
   khg_model* dm = am.DeviceModel(ctx);
   khg_tm* dt = tm.DeviceTm(ctx);
@@ -196,8 +213,7 @@ std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const Transit
   CApi(khg_utts_create(ctx, dt, n_utt, D, frame_off.data(), all.data(), nullptr, g.state_off.data(), g.start.data(), g.arc_off.data(), g.ilabel.data(),
                        g.olabel.data(), g.weight.data(), g.nextstate.data(), g.final_w.data(), &us.h));
   CApi(khg_loglikes(ctx, dm, us.h));              // every cell: a partial path may read any (frame, pdf) of the graph
-  std::vector<LatticeResult> out = DecodeLatticeOnSet(ctx, dt, us.h, frame_off, config, acoustic_scale, allow_partial, scratch_per_frame,
-                                                      g.state_off[(size_t)n_utt]);
+  std::vector<LatticeResult> out = on_set(ctx, dt, us.h, frame_off);
   if (return_scores) {
     std::vector<int64_t> ll_off((size_t)n_utt + 1, 0), pdf_off((size_t)n_utt + 1, 0);
     int64_t total = 0;
@@ -218,6 +234,63 @@ std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const Transit
     }
   }
   return out;
+}
+}  // namespace
+
+std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g, const std::vector<const float*>& feats,
+                                              const std::vector<int64_t>& nframes, const LatticeFasterDecoderConfig& config, float acoustic_scale,
+                                              bool allow_partial, bool return_scores, int scratch_per_frame) {
+  config.Check();
+  for (int64_t T : nframes) KHG_REQUIRE(T > 0, "num_frames > 0 assertion failed");     // GetRawLattice (lattice-faster-decoder.cc:137)
+  return K1ThenDecode(am, tm, g, feats, nframes, return_scores, "decode_lattice_faster_batch",
+                      [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
+                        return DecodeLatticeOnSet(ctx, dt, us, frame_off, config, acoustic_scale, allow_partial, scratch_per_frame,
+                                                  g.state_off.back());
+                      });
+}
+
+std::vector<LatticeResult> DecodeLatticeSimpleOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
+                                                    const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool allow_partial,
+                                                    int scratch_per_frame, int64_t total_states) {
+  const int n_utt = (int)frame_off.size() - 1;
+  khg_lattice_simple_config c;
+  khg_lattice_simple_config_default(&c);
+  c.beam = config.beam; c.lattice_beam = config.lattice_beam; c.prune_interval = config.prune_interval; c.prune_scale = config.prune_scale;
+  c.acoustic_scale = acoustic_scale; c.allow_partial = allow_partial ? 1 : 0; c.scratch_per_frame = scratch_per_frame;
+  const int64_t N = frame_off[(size_t)n_utt];
+  std::vector<int64_t> woff((size_t)n_utt + 1, 0);
+  std::vector<int32_t> ali((size_t)std::max<int64_t>(N, 1)), status((size_t)n_utt), ef((size_t)n_utt);
+  std::vector<double> like((size_t)n_utt);
+  // words: the C-ABI keeps at most frames + states + 64 per utterance
+  std::vector<int32_t> words((size_t)(N + total_states + 64 * (int64_t)n_utt + 16));
+  CApi(khg_decode_lattice_simple(ctx, tm, us, &c, ali.data(), words.data(), woff.data(), (int64_t)words.size(), like.data(), status.data(), ef.data()));
+  std::vector<LatticeResult> out((size_t)n_utt);
+  for (int u = 0; u < n_utt; ++u) {
+    LatticeResult& r = out[(size_t)u];
+    r.status = status[(size_t)u];
+    r.err_frame = ef[(size_t)u];
+    r.succeeded = (r.status & KHG_LAT_SUCCEEDED) != 0;
+    r.num_frames = (int)(frame_off[(size_t)u + 1] - frame_off[(size_t)u]);
+    if (r.succeeded) {
+      r.alignment.assign(ali.begin() + frame_off[(size_t)u], ali.begin() + frame_off[(size_t)u + 1]);
+      r.words.assign(words.begin() + woff[(size_t)u], words.begin() + woff[(size_t)u + 1]);
+      r.like = like[(size_t)u];
+    }
+  }
+  return out;
+}
+
+std::vector<LatticeResult> DecodeLatticeSimpleBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g,
+                                                    const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                    const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool allow_partial,
+                                                    bool return_scores, int scratch_per_frame) {
+  config.Check();
+  for (int64_t T : nframes) KHG_REQUIRE(T > 0, "decode_lattice_simple_batch: an utterance without frames");
+  return K1ThenDecode(am, tm, g, feats, nframes, return_scores, "decode_lattice_simple_batch",
+                      [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
+                        return DecodeLatticeSimpleOnSet(ctx, dt, us, frame_off, config, acoustic_scale, allow_partial, scratch_per_frame,
+                                                        g.state_off.back());
+                      });
 }
 
 // scripts/gmm_acc_stats_ali.py:46-58 through K3, into the accumulators' device block (khg_host_gmm.hpp)

@@ -46,8 +46,21 @@ struct LatticeFasterDecoderConfig {             // csrc/lattice-faster-decoder.h
   void Check() const;
 };
 
+struct LatticeSimpleDecoderConfig {            // csrc/lattice-simple-decoder.h:26-79
+  float beam = 16.0f, lattice_beam = 10.0f;
+  int32_t prune_interval = 25;
+  bool determinize_lattice = true;
+  // the reference's ToString prints prune_lattice, which its constructor never initialises and pybind never binds: False here
+  bool prune_lattice = false;
+  float beam_ratio = 0.9f, prune_scale = 0.1f;
+  DeterminizeLatticePhonePrunedOptions det_opts;
+  std::string ToString() const;
+  void Check() const;
+};
+
 struct LatticeResult {               // DecodeUtteranceLatticeFaster's (succeeded, alignment, words, like) + the KHG_LAT_* bits
   int status = 0;
+  int err_frame = -1;                // the lattice-simple decoder's KHG_LAT_NO_EPS_TOKEN frame
   bool succeeded = false, partial = false;
   std::vector<int32_t> alignment, words;
   double like = 0.0;
@@ -113,6 +126,26 @@ class DecodableAmDiagGmmScaled : public DecodableAmDiagGmmUnmapped {
   float scale_;
 };
 
+// csrc/decodable-ctc.{h,cc}: LogLikelihood(frame, index) = feats(frame, index - 1) of a [frames][indices] matrix.  The decode paths
+// copy the matrix straight into the score layout (Row), with no call per cell.
+class DecodableCtc : public DecodableInterface {
+ public:
+  DecodableCtc(const float* feats, int64_t rows, int64_t cols) : m_(feats, feats + rows * cols), rows_((int)rows), cols_((int)cols) {}
+  float LogLikelihood(int frame, int index) const override;
+  int NumFramesReady() const override { return rows_; }
+  int NumIndices() const override { return cols_; }
+  bool IsLastFrame(int frame) const override { return frame == rows_ - 1; }
+  const float* Row(int frame) const { return m_.data() + (size_t)frame * (size_t)cols_; }
+
+ private:
+  std::vector<float> m_;
+  int rows_, cols_;
+};
+// score of (frame, index) for the decode paths: DecodableCtc's matrix read directly (ctc from one dynamic_cast), else the interface
+inline float DecodableScore(const DecodableInterface& dec, const DecodableCtc* ctc, int frame, int index) {
+  return ctc ? ctc->Row(frame)[index - 1] : dec.LogLikelihood(frame, index);
+}
+
 struct AlignResult {
   bool ok = false, retried = false;
   int status = 0;
@@ -142,5 +175,15 @@ std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const Transit
 std::vector<LatticeResult> DecodeLatticeOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
                                               const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial, int scratch_per_frame,
                                               int64_t total_states);
+
+// DecodeUtteranceLatticeSimple (csrc/decoder-wrappers.cc:142-182) for a batch: K1 as in DecodeLatticeBatch + the data-parallel
+// lattice-simple decoder (khg_decode_lattice_simple).  scratch_per_frame: the most live tokens a frame may hold (0: no limit).
+std::vector<LatticeResult> DecodeLatticeSimpleBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& graphs,
+                                                    const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                    const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool allow_partial,
+                                                    bool return_scores, int scratch_per_frame = 0);
+std::vector<LatticeResult> DecodeLatticeSimpleOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
+                                                    const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool allow_partial,
+                                                    int scratch_per_frame, int64_t total_states);
 
 }  // namespace khg

@@ -126,9 +126,10 @@ AlignResult AlignDecodable(const StdVectorFst& fst, const DecodableInterface& de
   KHG_REQUIRE(total >= (int64_t)n * tpad, "AlignDecodable: unexpected score layout");
   std::vector<float> scores((size_t)total, 0.0f);
   r.loglikes.resize((size_t)n * (size_t)T);
+  const DecodableCtc* ctc = dynamic_cast<const DecodableCtc*>(&dec);
   for (int j = 0; j < n; ++j)
     for (int64_t t = 0; t < T; ++t) {
-      const float s = dec.LogLikelihood((int)t, r.pdfs[(size_t)j] + 1);
+      const float s = DecodableScore(dec, ctc, (int)t, r.pdfs[(size_t)j] + 1);
       scores[(size_t)(ll_off[0] + (int64_t)j * tpad + t)] = s;
       r.loglikes[(size_t)j * (size_t)T + (size_t)t] = s;
     }
@@ -156,21 +157,19 @@ AlignResult AlignDecodable(const StdVectorFst& fst, const DecodableInterface& de
   return r;
 }
 
-LatticeResult DecodeLatticeDecodable(const StdVectorFst& fst, const DecodableInterface& dec, const LatticeFasterDecoderConfig& config,
-                                     bool allow_partial, int scratch_per_frame) {
-  config.Check();
-  KHG_REQUIRE(fst.Start() != kNoStateId, "start_state != fst::kNoStateId assertion failed");   // lattice-faster-decoder.cc:72
+namespace {
+// the graph's index table and the decodable's scores of every (frame, index on the graph), sampled through the interface (as
+// AlignDecodable does), on a one-utterance set; then `on_set(ctx, tm, set, T)`
+template <class OnSet>
+LatticeResult WithDecodableSet(const StdVectorFst& fst, const DecodableInterface& dec, const std::string& name, OnSet on_set) {
   const int64_t T = dec.NumFramesReady();
-  KHG_REQUIRE(T > 0, "num_frames > 0 assertion failed");     // GetRawLattice (lattice-faster-decoder.cc:137)
-  LatticeResult r;
-  r.num_frames = (int)T;
   const GraphsCsr g = ConcatGraphs({&fst});
   int max_index = 0;
   for (int32_t l : g.ilabel) {
-    KHG_REQUIRE(l >= 0, "decode_utterance_lattice_faster: negative input label on the graph");
+    KHG_REQUIRE(l >= 0, name + ": negative input label on the graph");
     max_index = std::max(max_index, (int)l);
   }
-  KHG_REQUIRE(max_index <= dec.NumIndices(), "decode_utterance_lattice_faster: the graph carries index " + std::to_string(max_index) +
+  KHG_REQUIRE(max_index <= dec.NumIndices(), name + ": the graph carries index " + std::to_string(max_index) +
                                                  " but the decodable has " + std::to_string(dec.NumIndices()));
   std::vector<int32_t> id2pdf((size_t)max_index + 1);
   id2pdf[0] = -1;
@@ -190,11 +189,35 @@ LatticeResult DecodeLatticeDecodable(const StdVectorFst& fst, const DecodableInt
   CApi(khg_loglikes_layout(us.h, ll_off, &total));
   const int64_t tpad = (T + 31) & ~int64_t(31);
   std::vector<float> scores((size_t)std::max<int64_t>(total, 1), 0.0f);
+  const DecodableCtc* ctc = dynamic_cast<const DecodableCtc*>(&dec);
   for (int j = 0; j < n; ++j)
-    for (int64_t t = 0; t < T; ++t) scores[(size_t)(ll_off[0] + (int64_t)j * tpad + t)] = dec.LogLikelihood((int)t, pdfs[(size_t)j] + 1);
+    for (int64_t t = 0; t < T; ++t)
+      scores[(size_t)(ll_off[0] + (int64_t)j * tpad + t)] = DecodableScore(dec, ctc, (int)t, pdfs[(size_t)j] + 1);
   CApi(khg_loglikes_upload(ctx, us.h, scores.data()));
-  // 1.0f * s == s: the decodable scaled its scores itself
-  return DecodeLatticeOnSet(ctx, dt.h, us.h, {0, T}, config, 1.0f, allow_partial, scratch_per_frame, (int64_t)fst.NumStates())[0];
+  LatticeResult r = on_set(ctx, dt.h, us.h, T);
+  r.num_frames = (int)T;
+  return r;
+}
+}  // namespace
+
+LatticeResult DecodeLatticeDecodable(const StdVectorFst& fst, const DecodableInterface& dec, const LatticeFasterDecoderConfig& config,
+                                     bool allow_partial, int scratch_per_frame) {
+  config.Check();
+  KHG_REQUIRE(fst.Start() != kNoStateId, "start_state != fst::kNoStateId assertion failed");   // lattice-faster-decoder.cc:72
+  KHG_REQUIRE(dec.NumFramesReady() > 0, "num_frames > 0 assertion failed");     // GetRawLattice (lattice-faster-decoder.cc:137)
+  return WithDecodableSet(fst, dec, "decode_utterance_lattice_faster", [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, int64_t T) {
+    // 1.0f * s == s: the decodable scaled its scores itself
+    return DecodeLatticeOnSet(ctx, dt, us, {0, T}, config, 1.0f, allow_partial, scratch_per_frame, (int64_t)fst.NumStates())[0];
+  });
+}
+
+LatticeResult DecodeLatticeSimpleDecodable(const StdVectorFst& fst, const DecodableInterface& dec, const LatticeSimpleDecoderConfig& config,
+                                           bool allow_partial, int scratch_per_frame) {
+  config.Check();
+  KHG_REQUIRE(fst.Start() != kNoStateId, "Check failed!\nx: start_state != fst::kNoStateId");   // lattice-simple-decoder.cc:52
+  return WithDecodableSet(fst, dec, "decode_utterance_lattice_simple", [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, int64_t T) {
+    return DecodeLatticeSimpleOnSet(ctx, dt, us, {0, T}, config, 1.0f, allow_partial, scratch_per_frame, (int64_t)fst.NumStates())[0];
+  });
 }
 
 void FasterDecoder::AdvanceDecoding(const std::shared_ptr<DecodableInterface>& dec, int max_num_frames) {

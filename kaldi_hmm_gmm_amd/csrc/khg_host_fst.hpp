@@ -70,6 +70,16 @@ struct LatticeFasterDecoder {
   LatticeFasterDecoderConfig config;
 };
 
+// DecodeUtteranceLatticeSimple for ANY DecodableInterface, the same way (zero frames allowed: the decoder itself decides)
+LatticeResult DecodeLatticeSimpleDecodable(const StdVectorFst& fst, const DecodableInterface& decodable, const LatticeSimpleDecoderConfig& config,
+                                           bool allow_partial, int scratch_per_frame = 0);
+
+// python/csrc/lattice-simple-decoder.cc:33-37: the graph and configuration; decode_utterance_lattice_simple does the work
+struct LatticeSimpleDecoder {
+  std::shared_ptr<StdVectorFst> fst;
+  LatticeSimpleDecoderConfig config;
+};
+
 struct LatticeWeight {        // kaldifst LatticeWeight (graph cost, acoustic cost); Times adds component-wise
   double value1 = 0.0, value2 = 0.0;
 };

@@ -1,10 +1,12 @@
 // kaldi_hmm_gmm_amd/csrc/khg_k2.hip -- C-ABI (include/khg_hip.h): K2, Viterbi forced alignment (khg_align): kernel selection by graph
 // shape, LDS budgets, the exact DP on the main stream and the order-faithful decoder on a side stream; and the lattice decoder
-// (khg_decode_lattice_faster, khg_k2_lattice.hip.inc).  gfx950 only.
+// (khg_decode_lattice_faster, khg_k2_lattice.hip.inc) and the data-parallel LatticeSimpleDecoder (khg_decode_lattice_simple,
+// khg_k2_lattice_simple.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
 
 #include "khg_k2_viterbi.hip.inc"
 #include "khg_k2_lattice.hip.inc"
+#include "khg_k2_lattice_simple.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // K2
@@ -490,6 +492,128 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
       words_off_h[i] = o;
       const int64_t n = (st[(size_t)i] & KHG_LAT_SUCCEEDED) ? nw[(size_t)i] : 0;
       if (o + n > words_cap) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: words_cap too small");
+      std::copy(w.begin() + wcap_off[(size_t)i], w.begin() + wcap_off[(size_t)i] + n, words_h + o);
+      o += n;
+    }
+    words_off_h[U] = o;
+  }
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2S: LatticeSimpleDecoder (khg_k2_lattice_simple.hip.inc)
+extern "C" void khg_lattice_simple_config_default(khg_lattice_simple_config* c) {
+  c->beam = 16.0f; c->lattice_beam = 10.0f; c->prune_interval = 25; c->prune_scale = 0.1f; c->acoustic_scale = 1.0f;
+  c->allow_partial = 1; c->scratch_per_frame = 0;
+}
+
+extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_simple_config* cfg,
+                                         int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                         double* like_h, int32_t* status_h, int32_t* err_frame_h) {
+  if (ctx_dead(ctx) || !tm || !u || !cfg) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple: bad arguments");
+  { int rf = utts_foreign_ctx(ctx, u, "khg_decode_lattice_simple"); if (rf) return rf; }
+  if (!u->has_graphs) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple: the utterance set has no decoding graphs");
+  if (!u->ll_valid) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple: call khg_loglikes first");
+  // khg_loglikes_band leaves upper bounds in the cells past the band: a token the beam keeps may read any cell
+  if (u->ll_mode == 2)
+    return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple: the scores come from khg_loglikes_band; call khg_loglikes (every cell) first");
+  // LatticeSimpleDecoderConfig::Check (csrc/lattice-simple-decoder.h:76-78)
+  if (!(cfg->beam > 0.0f && cfg->lattice_beam > 0.0f && cfg->prune_interval > 0) || cfg->scratch_per_frame < 0)
+    return khg_set_error(KHG_E_RUNTIME, "LatticeSimpleDecoderConfig assertion failed");
+  int rc = wait_ali(ctx, u);
+  if (!rc) rc = k1_band_check(ctx, u);
+  if (rc) return rc;
+  const int U = u->n_utt;
+  if (U == 0) return KHG_OK;
+  std::vector<int64_t> wcap_off((size_t)U + 1, 0);
+  for (int i = 0; i < U; ++i) wcap_off[(size_t)i + 1] = wcap_off[(size_t)i] + (u->frame_off[i + 1] - u->frame_off[i]) + (u->state_off[i + 1] - u->state_off[i]) + 64;
+  const int64_t N = u->N, NW = wcap_off[(size_t)U];
+  struct Dev {
+    std::vector<void*> p;
+    ~Dev() { for (void* q : p) if (q) (void)hipFree(q); }
+  } dv;
+  auto dalloc = [&](size_t n, void** out) -> int {
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, std::max<size_t>(n, 16)));
+    dv.p.push_back(q);
+    *out = q;
+    return KHG_OK;
+  };
+  int32_t *ali_d, *words_d, *nw_d, *status_d, *ef_d; double* like_d; int64_t* woff_d;
+  if ((rc = dalloc(4 * (size_t)std::max<int64_t>(N, 1), reinterpret_cast<void**>(&ali_d))) ||
+      (rc = dalloc(4 * (size_t)std::max<int64_t>(NW, 1), reinterpret_cast<void**>(&words_d))) ||
+      (rc = dalloc(4 * (size_t)U, reinterpret_cast<void**>(&nw_d))) || (rc = dalloc(4 * (size_t)U, reinterpret_cast<void**>(&status_d))) ||
+      (rc = dalloc(4 * (size_t)U, reinterpret_cast<void**>(&ef_d))) ||
+      (rc = dalloc(8 * (size_t)U, reinterpret_cast<void**>(&like_d))) || (rc = dalloc(8 * ((size_t)U + 1), reinterpret_cast<void**>(&woff_d))))
+    return rc;
+  rc = arena_flush(ctx);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(woff_d, wcap_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>(N, 1), ctx->stream));
+  LsArgs a;
+  a.frame_off = u->frame_off_d; a.state_off = u->state_off_d; a.start = u->start_d;
+  a.in_off = u->in_off_d; a.in_src = u->in_src_d; a.in_col = u->in_col_d; a.in_tid = u->in_tid_d; a.in_olabel = u->in_olabel_d;
+  a.in_w = u->in_w_d; a.out_off = u->out_off_d; a.out_inidx = u->out_inidx_d; a.final_w = u->final_d;
+  a.trans_cost = tm->has_trans_cost ? tm->trans_cost_d : nullptr;
+  a.ll = u->ll_d; a.ll_off = u->ll_off_d;
+  a.ali = ali_d; a.words = words_d; a.words_off = woff_d; a.num_words = nw_d; a.like = like_d; a.status = status_d; a.err_frame = ef_d;
+  a.beam = cfg->beam; a.lattice_beam = cfg->lattice_beam; a.acoustic_scale = cfg->acoustic_scale;
+  a.prune_interval = cfg->prune_interval; a.tok_cap = cfg->scratch_per_frame; a.amax = u->max_inarcs;
+  // every utterance's dense rows, grouped into launches of <= 4 GiB of scratch (an utterance larger than that alone is refused)
+  std::vector<int64_t> bytes((size_t)U);
+  for (int i = 0; i < U; ++i) {
+    const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = u->state_off[i + 1] - u->state_off[i];
+    bytes[(size_t)i] = ls_layout(T, S, u->max_inarcs).total;     // (the kernel lays every slice out with the same arc bound)
+  }
+  const int64_t budget = int64_t(4) << 30;
+  std::vector<size_t> cb{0};
+  std::vector<int64_t> rel((size_t)U);
+  int64_t acc = 0, max_chunk = 0;
+  for (int i = 0; i < U; ++i) {
+    if (bytes[(size_t)i] > budget)
+      return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple: utterance " + std::to_string(i) + " needs more than 4 GiB of lattice scratch");
+    if (acc > 0 && acc + bytes[(size_t)i] > budget) { max_chunk = std::max(max_chunk, acc); cb.push_back((size_t)i); acc = 0; }
+    rel[(size_t)i] = acc;
+    acc += bytes[(size_t)i];
+  }
+  max_chunk = std::max(max_chunk, acc);
+  cb.push_back((size_t)U);
+  unsigned char* scratch; int64_t* scr_off_d; int32_t* list_d;
+  if ((rc = dalloc((size_t)max_chunk, reinterpret_cast<void**>(&scratch))) || (rc = dalloc(8 * (size_t)U, reinterpret_cast<void**>(&scr_off_d))) ||
+      (rc = dalloc(4 * (size_t)U, reinterpret_cast<void**>(&list_d))))
+    return rc;
+  std::vector<int32_t> all((size_t)U);
+  for (int i = 0; i < U; ++i) all[(size_t)i] = i;
+  HIPCHK(hipMemcpyAsync(scr_off_d, rel.data(), 8 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(list_d, all.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+  a.scratch = scratch; a.scr_off = scr_off_d; a.list = list_d;
+  // one wave for small graphs, up to four for larger ones (a lane owns states s = lane, lane + NT, ...)
+  const int nt = u->max_states <= 64 ? 64 : u->max_states <= 128 ? 128 : LS_NT;
+  for (size_t c = 0; c + 1 < cb.size(); ++c) {
+    KernelTimer kt(ctx, "k2_lattice_simple");
+    KHG_LAUNCH(ctx, k2_lattice_simple, dim3((unsigned)(cb[c + 1] - cb[c])), dim3(nt), 0, ctx->stream, a, (int)cb[c]);
+    HIPCHK(hipGetLastError());
+    if (c + 2 < cb.size()) HIPCHK(hipStreamSynchronize(ctx->stream));     // the next launch reuses the slices
+  }
+  rc = check_err_flag(ctx, "khg_decode_lattice_simple");     // synchronises
+  if (rc) return rc;
+  std::vector<int32_t> st((size_t)U), nw((size_t)U), w((size_t)std::max<int64_t>(NW, 1));
+  HIPCHK(hipMemcpy(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost));
+  if (ali_h && N) HIPCHK(hipMemcpyAsync(ali_h, ali_d, 4 * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
+  if (like_h) HIPCHK(hipMemcpyAsync(like_h, like_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  if (err_frame_h) HIPCHK(hipMemcpyAsync(err_frame_h, ef_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  if (words_h && words_off_h) {
+    HIPCHK(hipMemcpyAsync(nw.data(), nw_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(w.data(), words_d, 4 * (size_t)std::max<int64_t>(NW, 1), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (words_h && words_off_h) {
+    int64_t o = 0;
+    for (int i = 0; i < U; ++i) {
+      words_off_h[i] = o;
+      const int64_t n = (st[(size_t)i] & KHG_LAT_SUCCEEDED) ? nw[(size_t)i] : 0;
+      if (o + n > words_cap) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple: words_cap too small");
       std::copy(w.begin() + wcap_off[(size_t)i], w.begin() + wcap_off[(size_t)i] + n, words_h + o);
       o += n;
     }

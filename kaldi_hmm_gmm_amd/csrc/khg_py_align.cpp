@@ -130,6 +130,53 @@ py::dict LatticeToDict(const LatticeResult& r, int64_t T, bool return_scores) {
   }
   return d;
 }
+// the batched lattice calls' (fsts, feats_list): one graph for all utterances or one each; feature matrices of the model's dimension
+struct BatchArgs {
+  std::vector<Arr<float>> keep;
+  std::vector<const float*> fp;
+  std::vector<int64_t> nf;
+  std::vector<const StdVectorFst*> gp;
+  std::vector<std::shared_ptr<StdVectorFst>> hold;
+  BatchArgs(const AmDiagGmm& am, py::object fsts, py::list feats_list, const std::string& name) {
+    const int D = am.Dim();
+    for (py::handle f : feats_list) {
+      Arr<float> a = f.cast<Arr<float>>();
+      if (D <= 0 || a.size() % D != 0) throw Error("Dim mismatch: data dim vs. model dim = " + std::to_string(D));
+      keep.push_back(a);
+      fp.push_back(a.data());
+      nf.push_back((int64_t)(a.size() / D));
+    }
+    if (py::isinstance<StdVectorFst>(fsts)) {
+      hold.push_back(fsts.cast<std::shared_ptr<StdVectorFst>>());
+      for (size_t i = 0; i < fp.size(); ++i) gp.push_back(hold[0].get());
+    } else {
+      hold = fsts.cast<std::vector<std::shared_ptr<StdVectorFst>>>();
+      if (hold.size() == 1) for (size_t i = 0; i < fp.size(); ++i) gp.push_back(hold[0].get());
+      else for (auto& f : hold) gp.push_back(f.get());
+    }
+    if (gp.size() != fp.size()) throw Error(name + ": one graph, or one graph per utterance");
+    for (auto* g : gp) if (!g || g->Start() == kNoStateId) throw Error("start_state != fst::kNoStateId assertion failed");
+  }
+};
+// what the reference stops on in DecodeUtteranceLatticeSimple (KHG_ERR / KHG_ASSERT), raised with its message
+void RaiseLatticeSimple(const LatticeResult& r, const std::string& utt) {
+  if (r.status & KHG_LAT_NO_EPS_TOKEN) throw Error("Error in ProcessNonEmitting: no surviving tokens: frame is " + std::to_string(r.err_frame));
+  if (r.status & KHG_LAT_NAN) throw Error("Check failed!\nx: link_extra_cost == link_extra_cost");
+  if (r.status & KHG_LAT_EPS_LOOP)
+    throw Error("decode_utterance_lattice_simple: a negative-cost epsilon cycle in the decoding graph for utterance " + utt +
+                " (the reference's ProcessNonemitting never returns)");
+  if (r.status & KHG_LAT_NO_TRACEBACK) {
+    if (r.num_frames == 0) throw Error("Check failed!\nx: num_frames > 0");
+    throw Error("Failed to get traceback for utterance " + utt);
+  }
+  if (r.status & KHG_LAT_SCRATCH) throw Error("decode_utterance_lattice_simple: more live tokens on a frame than scratch_per_frame for utterance " + utt);
+  if (r.status & KHG_LAT_WORDS) throw Error("decode_utterance_lattice_simple: more words on the best path than the output holds for utterance " + utt);
+}
+py::dict LatticeSimpleToDict(const LatticeResult& r, int64_t T, bool return_scores) {
+  py::dict d = LatticeToDict(r, T, return_scores);
+  d["error_frame"] = r.err_frame;
+  return d;
+}
 }  // namespace
 
 void BindLattice(py::module_& m) {
@@ -206,37 +253,78 @@ void BindLattice(py::module_& m) {
   // -> one dict per utterance (succeeded, partial, status, alignment, words, like, num_frames[, loglikes, pdfs]); fsts may be one graph
   m.def("decode_lattice_faster_batch", [](std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, py::object fsts, py::list feats_list,
                                           const Cfg& config, float acoustic_scale, bool allow_partial, bool return_scores, int scratch_per_frame) {
-    const int D = am->Dim();
-    std::vector<Arr<float>> keep;
-    std::vector<const float*> fp;
-    std::vector<int64_t> nf;
-    for (py::handle f : feats_list) {
-      Arr<float> a = f.cast<Arr<float>>();
-      if (D <= 0 || a.size() % D != 0) throw Error("Dim mismatch: data dim vs. model dim = " + std::to_string(D));
-      keep.push_back(a);
-      fp.push_back(a.data());
-      nf.push_back((int64_t)(a.size() / D));
-    }
-    std::vector<const StdVectorFst*> gp;
-    std::vector<std::shared_ptr<StdVectorFst>> hold;
-    if (py::isinstance<StdVectorFst>(fsts)) {
-      hold.push_back(fsts.cast<std::shared_ptr<StdVectorFst>>());
-      for (size_t i = 0; i < fp.size(); ++i) gp.push_back(hold[0].get());
-    } else {
-      hold = fsts.cast<std::vector<std::shared_ptr<StdVectorFst>>>();
-      if (hold.size() == 1) for (size_t i = 0; i < fp.size(); ++i) gp.push_back(hold[0].get());
-      else for (auto& f : hold) gp.push_back(f.get());
-    }
-    if (gp.size() != fp.size()) throw Error("decode_lattice_faster_batch: one graph, or one graph per utterance");
-    for (auto* g : gp) if (!g || g->Start() == kNoStateId) throw Error("start_state != fst::kNoStateId assertion failed");
+    BatchArgs b(*am, fsts, feats_list, "decode_lattice_faster_batch");
+    const std::vector<const float*>& fp = b.fp;
+    const std::vector<int64_t>& nf = b.nf;
     std::vector<LatticeResult> rs;
     {
-      const GraphsCsr csr = ConcatGraphs(gp);
+      const GraphsCsr csr = ConcatGraphs(b.gp);
       py::gil_scoped_release nogil;
       rs = DecodeLatticeBatch(*am, *tm, csr, fp, nf, config, acoustic_scale, allow_partial, return_scores, scratch_per_frame);
     }
     py::list out;
     for (size_t u = 0; u < rs.size(); ++u) out.append(LatticeToDict(rs[u], nf[u], return_scores));
+    return out;
+  }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"), py::arg("allow_partial") = true,
+     py::arg("return_scores") = false, py::arg("scratch_per_frame") = 0);
+  // python/csrc/lattice-simple-decoder.cc:11-31
+  using SCfg = LatticeSimpleDecoderConfig;
+  py::class_<SCfg>(m, "LatticeSimpleDecoderConfig")
+      .def(py::init([](float beam, float lattice_beam, int32_t prune_interval, bool determinize_lattice, float beam_ratio, float prune_scale,
+                       const DeterminizeLatticePhonePrunedOptions& det) {
+             SCfg c;
+             c.beam = beam; c.lattice_beam = lattice_beam; c.prune_interval = prune_interval; c.determinize_lattice = determinize_lattice;
+             c.beam_ratio = beam_ratio; c.prune_scale = prune_scale; c.det_opts = det;
+             return c;
+           }), py::arg("beam") = 16.0f, py::arg("lattice_beam") = 10.0f, py::arg("prune_interval") = 25, py::arg("determinize_lattice") = true,
+           py::arg("beam_ratio") = 0.9f, py::arg("prune_scale") = 0.1f, py::arg("det_opts") = DeterminizeLatticePhonePrunedOptions{})
+      .def_readwrite("beam", &SCfg::beam).def_readwrite("lattice_beam", &SCfg::lattice_beam).def_readwrite("prune_interval", &SCfg::prune_interval)
+      .def_readwrite("determinize_lattice", &SCfg::determinize_lattice).def_readwrite("beam_ratio", &SCfg::beam_ratio)
+      .def_readwrite("prune_scale", &SCfg::prune_scale).def_readwrite("det_opts", &SCfg::det_opts)
+      .def("__str__", &SCfg::ToString);
+
+  // python/csrc/lattice-simple-decoder.cc:33-37: the constructor runs config.Check() (lattice-simple-decoder.h:93-97)
+  py::class_<LatticeSimpleDecoder>(m, "LatticeSimpleDecoder")
+      .def(py::init([](std::shared_ptr<StdVectorFst> fst, const SCfg& config) {
+             if (!fst) throw Error("LatticeSimpleDecoder: fst is None");
+             config.Check();
+             return LatticeSimpleDecoder{std::move(fst), config};
+           }), py::arg("fst"), py::arg("config"))
+      .def_property_readonly("_config", [](const LatticeSimpleDecoder& d) { return d.config; });
+
+  // python/csrc/decoder-wrappers.cc:49-68 -> (succeeded, alignment, words, like)
+  m.def("decode_utterance_lattice_simple", [](LatticeSimpleDecoder& decoder, std::shared_ptr<DecodableInterface> decodable,
+                                              const TransitionInformation& /*trans_model: the reference only passes it on*/,
+                                              const std::string& utt, bool allow_partial) {
+    if (!decodable) throw Error("decode_utterance_lattice_simple: decodable is None");
+    LatticeResult r;
+    auto dec = std::dynamic_pointer_cast<DecodableAmDiagGmmScaled>(decodable);
+    if (dec && dec->NumFramesReady() > 0) {
+      decoder.config.Check();
+      if (decoder.fst->Start() == kNoStateId) throw Error("Check failed!\nx: start_state != fst::kNoStateId");
+      py::gil_scoped_release nogil;
+      r = DecodeLatticeSimpleBatch(*dec->am(), *dec->tm(), ConcatGraphs({decoder.fst.get()}), {dec->feats().data()}, {(int64_t)dec->NumFramesReady()},
+                                   decoder.config, dec->scale(), allow_partial, false)[0];
+    } else {
+      r = DecodeLatticeSimpleDecodable(*decoder.fst, *decodable, decoder.config, allow_partial);     // GIL held: the scores may come from Python
+    }
+    RaiseLatticeSimple(r, utt);
+    return py::make_tuple(r.succeeded, r.alignment, r.words, r.like);
+  }, py::arg("decoder"), py::arg("decodable"), py::arg("trans_model"), py::arg("utt"), py::arg("allow_partial"));
+
+  // decode_lattice_simple_batch(am, tm, fsts, feats_list, config, acoustic_scale, allow_partial=True, return_scores=False,
+  // scratch_per_frame=0) -> one dict per utterance, as decode_lattice_faster_batch's plus error_frame; nothing raises per utterance
+  m.def("decode_lattice_simple_batch", [](std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, py::object fsts, py::list feats_list,
+                                          const SCfg& config, float acoustic_scale, bool allow_partial, bool return_scores, int scratch_per_frame) {
+    BatchArgs b(*am, fsts, feats_list, "decode_lattice_simple_batch");
+    std::vector<LatticeResult> rs;
+    {
+      const GraphsCsr csr = ConcatGraphs(b.gp);
+      py::gil_scoped_release nogil;
+      rs = DecodeLatticeSimpleBatch(*am, *tm, csr, b.fp, b.nf, config, acoustic_scale, allow_partial, return_scores, scratch_per_frame);
+    }
+    py::list out;
+    for (size_t u = 0; u < rs.size(); ++u) out.append(LatticeSimpleToDict(rs[u], b.nf[u], return_scores));
     return out;
   }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"), py::arg("allow_partial") = true,
      py::arg("return_scores") = false, py::arg("scratch_per_frame") = 0);
@@ -298,6 +386,13 @@ void BindAlign(py::module_& m) {
       .def_property_readonly("transition_model", [](DecodableAmDiagGmmScaled& d) { return d.tm(); })
       .def_property_readonly("_tm", [](DecodableAmDiagGmmScaled& d) { return d.tm(); })
       .def_property_readonly("_scale", [](DecodableAmDiagGmmScaled& d) { return (double)d.scale(); });
+
+  // python/csrc/decodable-ctc.cc:11-15
+  py::class_<DecodableCtc, DecodableInterface, std::shared_ptr<DecodableCtc>>(m, "DecodableCtc")
+      .def(py::init([](Arr<float> feats) {
+             if (feats.ndim() != 2) throw Error("feats must be a 2-D float matrix");
+             return std::make_shared<DecodableCtc>(feats.data(), (int64_t)feats.shape(0), (int64_t)feats.shape(1));
+           }), py::arg("feats"));
 
   m.def("align_batch", &AlignBatchPy, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"),
         py::arg("trans_cost") = py::none(), py::arg("decoder_opts") = py::none(), py::arg("return_scores") = false);

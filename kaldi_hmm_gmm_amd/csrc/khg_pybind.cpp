@@ -379,6 +379,7 @@ struct KUtts {
   KContext* ctx;
   Arr<int64_t> frame_off;
   int n_utt = 0, dim = 0;
+  int64_t state_total = 0;     // states over all graphs (bounds the words of a lattice decode)
   KUtts(py::object ctx_o, py::object tm, Arr<int64_t> fo, py::object feats, py::object dim_o, py::object graphs)
       : ctx_obj(ctx_o), ctx(ctx_o.cast<KContext*>()), frame_off(fo) {
     n_utt = (int)fo.shape(0) - 1;
@@ -409,6 +410,7 @@ struct KUtts {
       auto ns = g["nextstate"].cast<Arr<int32_t>>(); auto fin = g["final"].cast<Arr<float>>();
       Check(khg_utts_create(ctx->h, tmh, n_utt, dim, fo.data(), feats_h, feats_d, so.data(), st.data(), ao.data(), il.data(), ol.data(),
                             w.data(), ns.data(), fin.data(), &h));
+      state_total = so.at(n_utt);
     }
   }
   ~KUtts() { close(); }
@@ -496,6 +498,26 @@ struct KUtts {
     py::dict d;
     d["ali"] = py::array(ali)[py::slice(0, N, 1)];
     d["like"] = like; d["status"] = status;
+    d["words"] = py::array(words)[py::slice(0, woff.at(n_utt), 1)];
+    d["words_off"] = woff;
+    return d;
+  }
+  // khg_decode_lattice_simple on the resident scores (which must not come from loglikes(band=True))
+  py::dict decode_lattice_simple(KTransitions& tm, float beam, float lattice_beam, int32_t prune_interval, float prune_scale, float acoustic_scale,
+                                 bool allow_partial, int32_t scratch_per_frame) {
+    khg_lattice_simple_config c;
+    khg_lattice_simple_config_default(&c);
+    c.beam = beam; c.lattice_beam = lattice_beam; c.prune_interval = prune_interval; c.prune_scale = prune_scale; c.acoustic_scale = acoustic_scale;
+    c.allow_partial = allow_partial ? 1 : 0; c.scratch_per_frame = scratch_per_frame;
+    const int64_t N = frame_off.at(n_utt), wcap = 2 * N + 1024 * (int64_t)n_utt + 1024 + state_total;
+    Arr<int32_t> ali({(py::ssize_t)(N > 0 ? N : 1)}), words({(py::ssize_t)wcap}), status({(py::ssize_t)n_utt}), ef({(py::ssize_t)n_utt});
+    Arr<int64_t> woff({(py::ssize_t)n_utt + 1});
+    Arr<double> like({(py::ssize_t)n_utt});
+    Check(NoGil([&] { return khg_decode_lattice_simple(ctx->h, tm.h, h, &c, ali.mutable_data(), words.mutable_data(), woff.mutable_data(), wcap,
+                                                       like.mutable_data(), status.mutable_data(), ef.mutable_data()); }));
+    py::dict d;
+    d["ali"] = py::array(ali)[py::slice(0, N, 1)];
+    d["like"] = like; d["status"] = status; d["error_frame"] = ef;
     d["words"] = py::array(words)[py::slice(0, woff.at(n_utt), 1)];
     d["words_off"] = woff;
     return d;
@@ -631,6 +653,9 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
            py::arg("max_active") = std::numeric_limits<int32_t>::max(), py::arg("min_active") = 200, py::arg("lattice_beam") = 10.0f,
            py::arg("prune_interval") = 25, py::arg("beam_delta") = 0.5f, py::arg("hash_ratio") = 2.0f, py::arg("prune_scale") = 0.1f,
            py::arg("acoustic_scale") = 1.0f, py::arg("allow_partial") = true, py::arg("scratch_per_frame") = 0)
+      .def("decode_lattice_simple", &KUtts::decode_lattice_simple, py::arg("tm"), py::arg("beam") = 16.0f, py::arg("lattice_beam") = 10.0f,
+           py::arg("prune_interval") = 25, py::arg("prune_scale") = 0.1f, py::arg("acoustic_scale") = 1.0f, py::arg("allow_partial") = true,
+           py::arg("scratch_per_frame") = 0)
       .def("upload_ali", &KUtts::upload_ali).def("download_ali", &KUtts::download_ali)
       .def("acc_stats", &KUtts::acc_stats, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f)
       .def("acc_stats_reduce", &KUtts::acc_stats_reduce, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f,
