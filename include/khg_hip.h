@@ -110,7 +110,10 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
 #define KHG_OPT_K2_SPLIT 16      /* an asynchronous khg_align (no host outputs) on a set of > 64 utterances lets the order-faithful decoders write to a
                                     second alignment buffer, so that khg_acc_stats can accumulate the certified utterances while they still
                                     run and add the others in a second pass: 0 (DEFAULT) on, 1 off                       [KHG_K2_SPLIT=off] */
-#define KHG_OPT_COUNT 17
+#define KHG_OPT_K2S_HUB 17       /* khg_decode_lattice_simple: a state with more than this many in-arcs (out-arcs in the backward pass) has its arc
+                                    loops strided over by a whole wave instead of walked by one lane (a word loop's hub state); same results
+                                    bit for bit.  0: off (every state on one lane).  Default 32                              [KHG_K2S_HUB] */
+#define KHG_OPT_COUNT 18
 /* Read-only figures (khg_ctx_get_option only): the per-call scratch block behind small utterance sets (DESIGN.md "per-utterance calls"). */
 #define KHG_INFO_SCRATCH_BYTES 100   /* bytes of the block in use (its top), 0 before the first small set */
 #define KHG_INFO_SCRATCH_BLOCKS 101  /* live allocations inside it */
@@ -162,6 +165,33 @@ int khg_utts_create(khg_ctx *ctx, const khg_tm *tm, int32_t n_utt, int32_t dim,
                     const int32_t *ilabel_h, const int32_t *olabel_h, const float *weight_h,
                     const int32_t *nextstate_h, const float *final_h, khg_utts **out);
 int khg_utts_destroy(khg_utts *u);
+/* ---- one decoding graph shared by many utterances ---------------------------------------
+ * Decoding (egs/yesno/decode.py:143-179: one HCLG, one decoder object, every utterance) is the opposite of training: ONE graph,
+ * many utterances.  khg_graph_create plans a graph once (in-arc CSR, pdf list, first / last useful frames) and uploads its tables
+ * once; khg_utts_create_on_graph builds a set whose utterances all decode on it and that stores, per utterance, only what depends
+ * on its length.  The graph is in the CSR-by-source layout of khg_utts_create for a single graph (arc_off_h[0] = 0, nextstate
+ * graph-local, final_h[s] = +inf for non-final, start = -1 for an empty FST); argument checks as there.
+ * Limits: khg_utts_create refuses a state with more than 254 incoming arcs and a graph of more than 65 535 states, which are the exact-DP
+ * aligner's (one-byte back-pointers, 16-bit arc sources).  A khg_graph may exceed both: the lattice decoders take any in-degree and
+ * any state count their scratch checks admit, and khg_align on such a set returns KHG_E_UNSUPPORTED naming the limit and leaves
+ * the set usable.  More than 32 767 distinct pdfs on the graph: KHG_E_UNSUPPORTED, as in khg_utts_create.
+ * Lifetime: every set holds a reference to its graph, so khg_graph_destroy before khg_utts_destroy is legal; the tables are freed
+ * with the last holder.  Several live sets may share one graph.  A graph belongs to the context that created it (KHG_E_ARG from
+ * khg_utts_create_on_graph otherwise); its tables are never taken from the per-context arena.  Every entry point that takes a
+ * khg_utts works on such a set and gives the results of the same utterances on U copies of the graph, bit for bit. */
+typedef struct khg_graph khg_graph;
+int khg_graph_create(khg_ctx *ctx, const khg_tm *tm, int32_t num_states, int32_t start, const int64_t *arc_off_h,
+                     const int32_t *ilabel_h, const int32_t *olabel_h, const float *weight_h,
+                     const int32_t *nextstate_h, const float *final_h, khg_graph **out);
+int khg_graph_destroy(khg_graph *g);
+/* any output may be NULL; device_bytes: the graph tables in HBM (independent of how many utterances decode on it) */
+int khg_graph_info(const khg_graph *g, int64_t *num_states, int64_t *num_arcs, int32_t *num_pdfs,
+                   int32_t *max_in_degree, int64_t *device_bytes);
+/* khg_utts_create with every utterance decoding on `g` (features as there) */
+int khg_utts_create_on_graph(khg_ctx *ctx, const khg_tm *tm, khg_graph *g, int32_t n_utt, int32_t dim,
+                             const int64_t *frame_off_h, const float *feats_h, const float *feats_d, khg_utts **out);
+/* device bytes of graph tables this set owns itself: 0 for a set created on a khg_graph, and for a features-only set */
+int khg_utts_graph_bytes(const khg_utts *u, int64_t *bytes);
 /* number of distinct pdfs on each utterance's graph, and the list itself (sorted) */
 int khg_utts_num_pdfs(const khg_utts *u, int64_t *pdf_off_h /* [n_utt+1] */);
 int khg_utts_pdfs(const khg_utts *u, int32_t *pdfs_h /* [pdf_off[n_utt]] */);

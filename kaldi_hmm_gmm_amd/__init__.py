@@ -15,7 +15,7 @@ from .align import (DecodableCtc, LatticeSimpleDecoder, LatticeSimpleDecoderConf
 from .context_dep import (ContextDependency, ContextDependencyInterface, monophone_context_dependency,  # noqa: F401
                           monophone_context_dependency_shared)
 from .device import (ALIGN_DONE, ALIGN_ERROR, ALIGN_EXACT_DP, ALIGN_FALLBACK, ALIGN_RETRIED, Comm, Context, DeviceAccs,  # noqa: F401
-                     DeviceModel, DeviceTransitions, UtteranceSet)
+                     DecodingGraph, DeviceModel, DeviceTransitions, UtteranceSet)
 from .diag_gmm import AmDiagGmm, DiagGmm  # noqa: F401
 from .fst import StdArc, StdVectorFst, modify_graph_for_careful_alignment  # noqa: F401
 from .hmm_topology import HmmState, HmmTopology  # noqa: F401

@@ -120,6 +120,11 @@ SIGNATURES = {
          c_f32p, C.POINTER(vp)],
     ),
     "khg_utts_destroy": (C.c_int, [vp]),
+    "khg_graph_create": (C.c_int, [vp, vp, C.c_int32, C.c_int32, c_i64p, c_i32p, c_i32p, c_f32p, c_i32p, c_f32p, C.POINTER(vp)]),
+    "khg_graph_destroy": (C.c_int, [vp]),
+    "khg_graph_info": (C.c_int, [vp, c_i64p, c_i64p, c_i32p, c_i32p, c_i64p]),
+    "khg_utts_create_on_graph": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, c_i64p, c_f32p, vp, C.POINTER(vp)]),
+    "khg_utts_graph_bytes": (C.c_int, [vp, c_i64p]),
     "khg_utts_num_pdfs": (C.c_int, [vp, c_i64p]),
     "khg_utts_pdfs": (C.c_int, [vp, c_i32p]),
     "khg_utts_pdf_first": (C.c_int, [vp, c_i32p]),

@@ -81,13 +81,43 @@ struct UttsH { khg_utts* h = nullptr; ~UttsH() { if (h) khg_utts_destroy(h); } }
 std::string G(double x) { char b[64]; std::snprintf(b, sizeof(b), "%g", x); return b; }
 }  // namespace
 
+void CreateBatchSet(khg_ctx* ctx, khg_tm* tm, const GraphsCsr& g, int n_utt, int dim, const int64_t* frame_off, const float* feats, khg_utts** out) {
+  if (!g.shared) {
+    CApi(khg_utts_create(ctx, tm, n_utt, dim, frame_off, feats, nullptr, g.state_off.data(), g.start.data(), g.arc_off.data(), g.ilabel.data(),
+                         g.olabel.data(), g.weight.data(), g.nextstate.data(), g.final_w.data(), out));
+    return;
+  }
+  struct GraphH { khg_graph* h = nullptr; ~GraphH() { if (h) khg_graph_destroy(h); } } own;     // (the set keeps its own reference)
+  khg_graph* dg = g.device;
+  if (!dg) {
+    CApi(khg_graph_create(ctx, tm, (int32_t)g.state_off.back(), g.start[0], g.arc_off.data(), g.ilabel.data(), g.olabel.data(), g.weight.data(),
+                          g.nextstate.data(), g.final_w.data(), &own.h));
+    dg = own.h;
+  }
+  CApi(khg_utts_create_on_graph(ctx, tm, dg, n_utt, dim, frame_off, feats, nullptr, out));
+}
+namespace {
+// one graph per utterance, or one for all of them
+bool GraphsFit(const GraphsCsr& g, int n_utt) {
+  if (g.shared) return g.device || (g.start.size() == 1 && g.state_off.size() == 2);
+  return (int)g.start.size() == n_utt && (int)g.state_off.size() == n_utt + 1;
+}
+// bound on the states under all utterances (the words a lattice decode can return: frames + states + 64 per utterance)
+int64_t BatchStates(const GraphsCsr& g, int n_utt) {
+  if (!g.shared) return g.state_off.back();
+  int64_t S = g.state_off.empty() ? 0 : g.state_off.back();
+  if (g.device) CApi(khg_graph_info(g.device, &S, nullptr, nullptr, nullptr, nullptr));
+  return S * (int64_t)n_utt;
+}
+}  // namespace
+
 std::vector<AlignResult> AlignBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g, const std::vector<const float*>& feats,
                                     const std::vector<int64_t>& nframes, const AlignConfig& config, float acoustic_scale, const float* trans_cost,
                                     const FasterDecoderOptions* dopts, bool return_scores, float like_scale) {
   KHG_REQUIRE(!((config.retry_beam != 0 && config.retry_beam <= config.beam) || config.beam <= 0.0f),
               "Beams do not make sense: beam " + G(config.beam) + ", retry-beam " + G(config.retry_beam));   // csrc/decoder-wrappers.cc:29-33
   const int n_utt = (int)feats.size(), D = am.Dim();
-  KHG_REQUIRE((int)nframes.size() == n_utt && (int)g.start.size() == n_utt && (int)g.state_off.size() == n_utt + 1, "AlignBatch: one graph and one feature matrix per utterance");
+  KHG_REQUIRE((int)nframes.size() == n_utt && GraphsFit(g, n_utt), "AlignBatch: one graph and one feature matrix per utterance");
   khg_ctx* ctx = DefaultCtx();
   // the model and the transition table live on the device across calls: cached on the host objects, uploaded again only when they
   // changed (AmDiagGmm::DeviceModel / TransitionModel::DeviceTm) -- the scripts call this once per utterance
@@ -108,8 +138,7 @@ std::vector<AlignResult> AlignBatch(const AmDiagGmm& am, const TransitionModel& 
   }
   static const float kNoFrames[1] = {0.0f};
   if (!fp) fp = kNoFrames;
-  CApi(khg_utts_create(ctx, dt.h, n_utt, D, frame_off.data(), fp, nullptr, g.state_off.data(), g.start.data(), g.arc_off.data(), g.ilabel.data(),
-                       g.olabel.data(), g.weight.data(), g.nextstate.data(), g.final_w.data(), &us.h));
+  CreateBatchSet(ctx, dt.h, g, n_utt, D, frame_off.data(), fp, &us.h);
   // only the cells a decoder token can read; with a wide beam (few failed beam certificates to repair) also not the cells that only
   // tokens past any accepting path read (khg_loglikes_band: identical alignments, ~13 % fewer cells on chain graphs)
   if (config.beam >= 100.0f) CApi(khg_loglikes_band(ctx, dm.h, us.h));
@@ -198,8 +227,7 @@ template <class OnSet>
 std::vector<LatticeResult> K1ThenDecode(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g, const std::vector<const float*>& feats,
                                         const std::vector<int64_t>& nframes, bool return_scores, const std::string& name, OnSet on_set) {
   const int n_utt = (int)feats.size(), D = am.Dim();
-  KHG_REQUIRE((int)nframes.size() == n_utt && (int)g.start.size() == n_utt && (int)g.state_off.size() == n_utt + 1,
-              name + ": one graph and one feature matrix per utterance");
+  KHG_REQUIRE((int)nframes.size() == n_utt && GraphsFit(g, n_utt), name + ": one graph and one feature matrix per utterance");
   khg_ctx* ctx = DefaultCtx();
   khg_model* dm = am.DeviceModel(ctx);
   khg_tm* dt = tm.DeviceTm(ctx);
@@ -210,8 +238,7 @@ std::vector<LatticeResult> K1ThenDecode(const AmDiagGmm& am, const TransitionMod
   std::vector<float> all((size_t)std::max<int64_t>(frame_off[(size_t)n_utt], 1) * D);
   for (int u = 0; u < n_utt; ++u)
     if (nframes[(size_t)u] > 0) std::memcpy(all.data() + (size_t)frame_off[(size_t)u] * D, feats[(size_t)u], sizeof(float) * (size_t)nframes[(size_t)u] * D);
-  CApi(khg_utts_create(ctx, dt, n_utt, D, frame_off.data(), all.data(), nullptr, g.state_off.data(), g.start.data(), g.arc_off.data(), g.ilabel.data(),
-                       g.olabel.data(), g.weight.data(), g.nextstate.data(), g.final_w.data(), &us.h));
+  CreateBatchSet(ctx, dt, g, n_utt, D, frame_off.data(), all.data(), &us.h);
   CApi(khg_loglikes(ctx, dm, us.h));              // every cell: a partial path may read any (frame, pdf) of the graph
   std::vector<LatticeResult> out = on_set(ctx, dt, us.h, frame_off);
   if (return_scores) {
@@ -245,7 +272,7 @@ std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const Transit
   return K1ThenDecode(am, tm, g, feats, nframes, return_scores, "decode_lattice_faster_batch",
                       [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
                         return DecodeLatticeOnSet(ctx, dt, us, frame_off, config, acoustic_scale, allow_partial, scratch_per_frame,
-                                                  g.state_off.back());
+                                                  BatchStates(g, (int)feats.size()));
                       });
 }
 
@@ -289,7 +316,7 @@ std::vector<LatticeResult> DecodeLatticeSimpleBatch(const AmDiagGmm& am, const T
   return K1ThenDecode(am, tm, g, feats, nframes, return_scores, "decode_lattice_simple_batch",
                       [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
                         return DecodeLatticeSimpleOnSet(ctx, dt, us, frame_off, config, acoustic_scale, allow_partial, scratch_per_frame,
-                                                        g.state_off.back());
+                                                        BatchStates(g, (int)feats.size()));
                       });
 }
 

@@ -73,7 +73,14 @@ struct GraphsCsr {                   // fst::VectorFst<StdArc> per utterance, co
   std::vector<int64_t> state_off, arc_off;
   std::vector<int32_t> start, ilabel, olabel, nextstate;
   std::vector<float> weight, final_w;
+  // One decoding graph for the whole batch (decoding: one HCLG, many utterances): the arrays above hold that ONE graph
+  // (state_off = {0, S}), or nothing when `device` is a graph already resident (khg_graph_create; borrowed).  The batch entry
+  // points then build their set with khg_utts_create_on_graph: planned and uploaded once, not once per utterance.
+  bool shared = false;
+  khg_graph* device = nullptr;
 };
+// the batch's utterance set: khg_utts_create (one graph per utterance), or khg_utts_create_on_graph for a shared graph
+void CreateBatchSet(khg_ctx* ctx, khg_tm* tm, const GraphsCsr& g, int n_utt, int dim, const int64_t* frame_off, const float* feats, khg_utts** out);
 
 // csrc/decodable-itf.h: what a decoder asks of an acoustic model (1-based index, 0-based frame).  The HIP kernels read scores from
 // K1's matrices, so the classes below are what the alignment entry points accept; the interface itself is there for callers

@@ -209,8 +209,26 @@ struct khg_tm {
   bool has_trans_cost = false;
 };
 
+// One decoding graph planned and uploaded once (khg_graph_create); utterance sets made by khg_utts_create_on_graph borrow its tables.
+// Reference-counted: the creator's handle and every set on it hold one reference, the tables go with the last.  Never arena memory.
+struct khg_graph {
+  khg_ctx* ctx = nullptr;
+  int32_t refs = 1;
+  int64_t S = 0, A = 0, nwords = 0, device_bytes = 0;
+  int32_t start = -1, max_indeg = 0, max_outdeg = 0;
+  bool same_col = true, has_eps = false;
+  std::vector<int32_t> pdfs, pdf_first, pdf_dfin;   // sorted pdf list; per pdf: first frame it can be read at, fewest emitting arcs left after an arc carrying it (INT32_MAX: never)
+  int64_t *state_off_d = nullptr, *in_off_d = nullptr, *out_off_d = nullptr;    // state_off_d = {0, S}
+  int32_t *start_d = nullptr, *in_src_d = nullptr, *in_col_d = nullptr, *in_tid_d = nullptr, *in_olabel_d = nullptr, *out_inidx_d = nullptr;
+  float *in_w_d = nullptr, *final_d = nullptr;
+};
+void khg_graph_release(khg_graph* g);                      // khg_utts.hip: drops one reference
+
 struct khg_utts {
   khg_ctx* ctx = nullptr;
+  khg_graph* graph = nullptr;    // set created by khg_utts_create_on_graph: the graph tables below are the graph's (borrowed), state_off = {0, S}
+  int32_t* gidx_d = nullptr;     // [U] row of state_off_d / start_d an utterance decodes on: identity, or zeros on a shared graph
+  int64_t graph_bytes = 0;       // device bytes of the graph tables the set owns itself
   bool small = false;            // scratch from the context's arena (KhgArena): few utterances, one call each
   int32_t n_utt = 0, D = 0;
   int64_t N = 0;  // total frames
@@ -285,6 +303,9 @@ struct khg_utts {
   int64_t* pdf_start_d = nullptr; unsigned long long* tid_count_d = nullptr;
   int32_t k3_P = 0, k3_tids = 0;
 };
+
+// states of utterance i's decoding graph (host code sizing scratch)
+static inline int64_t utt_states(const khg_utts* u, int i) { return u->graph ? u->state_off[1] : u->state_off[(size_t)i + 1] - u->state_off[(size_t)i]; }
 
 struct khg_accs {
   khg_ctx* ctx = nullptr;

@@ -40,6 +40,12 @@ extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_
   { int rf = utts_foreign_ctx(ctx, u, "khg_align"); if (rf) return rf; }
   if (!u->has_graphs) return khg_set_error(KHG_E_ARG, "khg_align: the utterance set has no decoding graphs");
   if (!u->ll_valid) return khg_set_error(KHG_E_ARG, "khg_align: call khg_loglikes first");
+  // the exact DP's back-pointers are one byte and its arc sources 16 bits: khg_utts_create refuses such graphs, a khg_graph may hold one
+  // (the lattice decoders have neither field).  Nothing was touched: the set stays usable.
+  if (u->max_states > 65535)
+    return khg_set_error(KHG_E_UNSUPPORTED, "khg_align: more than 65535 states in one decoding graph (" + std::to_string(u->max_states) + "); the aligner's limit");
+  if (u->max_indeg > 254)
+    return khg_set_error(KHG_E_UNSUPPORTED, "khg_align: a state has more than 254 incoming arcs (" + std::to_string(u->max_indeg) + "); the aligner's limit");
   // decoder-wrappers.cc:29-33
   if ((cfg->retry_beam != 0 && cfg->retry_beam <= cfg->beam) || cfg->beam <= 0.0)
     return khg_set_error(KHG_E_RUNTIME, "Beams do not make sense: beam " + std::to_string(cfg->beam) + ", retry-beam " + std::to_string(cfg->retry_beam));
@@ -67,7 +73,7 @@ extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_
   if (rc) return rc;
   HIPCHK(hipMemsetAsync(u->ali_d, 0, sizeof(int32_t) * (size_t)u->N, ctx->stream));
   K2Args a;
-  a.frame_off = u->frame_off_d; a.state_off = u->state_off_d; a.start = u->start_d;
+  a.frame_off = u->frame_off_d; a.gidx = u->gidx_d; a.state_off = u->state_off_d; a.start = u->start_d;
   a.in_off = u->in_off_d; a.in_src = u->in_src_d; a.in_col = u->in_col_d; a.in_tid = u->in_tid_d;
   a.in_olabel = u->in_olabel_d; a.in_w = u->in_w_d; a.out_off = u->out_off_d; a.out_inidx = u->out_inidx_d;
   a.final_w = u->final_d; a.trans_cost = tm->has_trans_cost ? tm->trans_cost_d : nullptr;
@@ -380,7 +386,7 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
   const int64_t hb = std::max<int64_t>(1000, (int64_t)((float)u->max_states * cfg->hash_ratio)) + 1;
   const int64_t Amax = u->max_inarcs;     // (the kernel lays every slice out with the same arc bound)
   std::vector<int64_t> wcap_off((size_t)U + 1, 0);
-  for (int i = 0; i < U; ++i) wcap_off[(size_t)i + 1] = wcap_off[(size_t)i] + (u->frame_off[i + 1] - u->frame_off[i]) + (u->state_off[i + 1] - u->state_off[i]) + 64;
+  for (int i = 0; i < U; ++i) wcap_off[(size_t)i + 1] = wcap_off[(size_t)i] + (u->frame_off[i + 1] - u->frame_off[i]) + utt_states(u, i) + 64;
   const int64_t N = u->N, NW = wcap_off[(size_t)U];
   struct Dev {
     std::vector<void*> p;
@@ -404,7 +410,7 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
   HIPCHK(hipMemcpyAsync(woff_d, wcap_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>(N, 1), ctx->stream));
   LatArgs a;
-  a.frame_off = u->frame_off_d; a.state_off = u->state_off_d; a.start = u->start_d;
+  a.frame_off = u->frame_off_d; a.gidx = u->gidx_d; a.state_off = u->state_off_d; a.start = u->start_d;
   a.in_off = u->in_off_d; a.in_col = u->in_col_d; a.in_tid = u->in_tid_d; a.in_olabel = u->in_olabel_d; a.in_w = u->in_w_d;
   a.out_off = u->out_off_d; a.out_inidx = u->out_inidx_d; a.final_w = u->final_d;
   a.trans_cost = tm->has_trans_cost ? tm->trans_cost_d : nullptr;
@@ -422,7 +428,7 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
     std::vector<int64_t> bytes(L);
     for (size_t k = 0; k < L; ++k) {
       const int i = list[k];
-      const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = u->state_off[i + 1] - u->state_off[i], A = std::max<int64_t>(Amax, 1);
+      const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = utt_states(u, i), A = std::max<int64_t>(Amax, 1);
       const int64_t pt = per_frame > 0 ? per_frame : per_frame < 0 ? S : std::min<int64_t>(S, 256);
       const int64_t pl = per_frame > 0 ? per_frame : per_frame < 0 ? A : std::min<int64_t>(A, 1024);
       const int64_t tc = (T + 1) * pt + (per_frame > 0 ? 0 : S) + 1, lc = (T + 1) * pl + (per_frame > 0 ? 0 : A) + 1;
@@ -526,7 +532,7 @@ extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utt
   const int U = u->n_utt;
   if (U == 0) return KHG_OK;
   std::vector<int64_t> wcap_off((size_t)U + 1, 0);
-  for (int i = 0; i < U; ++i) wcap_off[(size_t)i + 1] = wcap_off[(size_t)i] + (u->frame_off[i + 1] - u->frame_off[i]) + (u->state_off[i + 1] - u->state_off[i]) + 64;
+  for (int i = 0; i < U; ++i) wcap_off[(size_t)i + 1] = wcap_off[(size_t)i] + (u->frame_off[i + 1] - u->frame_off[i]) + utt_states(u, i) + 64;
   const int64_t N = u->N, NW = wcap_off[(size_t)U];
   struct Dev {
     std::vector<void*> p;
@@ -551,7 +557,7 @@ extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utt
   HIPCHK(hipMemcpyAsync(woff_d, wcap_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>(N, 1), ctx->stream));
   LsArgs a;
-  a.frame_off = u->frame_off_d; a.state_off = u->state_off_d; a.start = u->start_d;
+  a.frame_off = u->frame_off_d; a.gidx = u->gidx_d; a.state_off = u->state_off_d; a.start = u->start_d;
   a.in_off = u->in_off_d; a.in_src = u->in_src_d; a.in_col = u->in_col_d; a.in_tid = u->in_tid_d; a.in_olabel = u->in_olabel_d;
   a.in_w = u->in_w_d; a.out_off = u->out_off_d; a.out_inidx = u->out_inidx_d; a.final_w = u->final_d;
   a.trans_cost = tm->has_trans_cost ? tm->trans_cost_d : nullptr;
@@ -559,10 +565,11 @@ extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utt
   a.ali = ali_d; a.words = words_d; a.words_off = woff_d; a.num_words = nw_d; a.like = like_d; a.status = status_d; a.err_frame = ef_d;
   a.beam = cfg->beam; a.lattice_beam = cfg->lattice_beam; a.acoustic_scale = cfg->acoustic_scale;
   a.prune_interval = cfg->prune_interval; a.tok_cap = cfg->scratch_per_frame; a.amax = u->max_inarcs;
+  a.hub = ctx->opt[KHG_OPT_K2S_HUB];
   // every utterance's dense rows, grouped into launches of <= 4 GiB of scratch (an utterance larger than that alone is refused)
   std::vector<int64_t> bytes((size_t)U);
   for (int i = 0; i < U; ++i) {
-    const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = u->state_off[i + 1] - u->state_off[i];
+    const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = utt_states(u, i);
     bytes[(size_t)i] = ls_layout(T, S, u->max_inarcs).total;     // (the kernel lays every slice out with the same arc bound)
   }
   const int64_t budget = int64_t(4) << 30;

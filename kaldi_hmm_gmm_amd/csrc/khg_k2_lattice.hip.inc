@@ -21,7 +21,8 @@
 
 struct LatArgs {
   const int64_t* frame_off;   // [U+1]
-  const int64_t* state_off;   // [U+1]
+  const int32_t* gidx;        // [U] the row of state_off / start an utterance decodes on (identity; zeros on a shared graph)
+  const int64_t* state_off;   // [rows+1]
   const int32_t* start;       // [U]
   const int64_t* in_off;      // [sumS+1]
   const int32_t* in_col;      // -1: epsilon input
@@ -130,8 +131,8 @@ __global__ __launch_bounds__(64) void k2_lattice_faster(LatArgs a, int u0) {
   const int64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const int tpad = (T + 31) & ~31;
-  const int64_t s0 = a.state_off[u];
-  const int S = (int)(a.state_off[u + 1] - s0);
+  const int64_t s0 = a.state_off[a.gidx[u]];
+  const int S = (int)(a.state_off[a.gidx[u] + 1] - s0);
   const int64_t in0 = a.in_off[s0];
   const int A = (int)(a.in_off[s0 + S] - in0);
   const float* llu = a.ll + a.ll_off[u];
@@ -306,7 +307,7 @@ __global__ __launch_bounds__(64) void k2_lattice_faster(LatArgs a, int u0) {
   {
     const int st = new_tok(0.0f, 0);
     bool nw;
-    const int e = hl_insert(a.start[u], &nw);
+    const int e = hl_insert(a.start[a.gidx[u]], &nw);
     pools[cur][e].val = st;
     process_nonemitting(a.beam, 0);
   }

@@ -19,10 +19,16 @@
 // Jacobi rounds (each round reads the previous round's distances); inside a round a destination takes its in-links in the in-arc
 // CSR order of khg_utts_create (source state, then arc index) and changes only on a strictly better LatticeWeight (Value1 + Value2,
 // then Value1).  The final state is the lowest-numbered one among exactly tied totals.
+//
+// Hub states (a.hub > 0): a state with more than a.hub in-arcs -- out-arcs in the backward pass -- (a word loop's loop state: one
+// arc per word) does not have its arcs walked by the one lane that owns it; the waves of the workgroup take such states in turn,
+// the 64 lanes stride over the arcs and combine by shuffles.  Every combination carries (key, position in the arc list) and prefers
+// the lower position among equal keys, which is what the serial loop's strict comparisons keep: the same answer, bit for bit.
 
 struct LsArgs {
   const int64_t* frame_off;   // [U+1]
-  const int64_t* state_off;   // [U+1]
+  const int32_t* gidx;        // [U] the row of state_off / start an utterance decodes on (identity; zeros on a shared graph)
+  const int64_t* state_off;   // [rows+1]
   const int32_t* start;       // [U]
   const int64_t* in_off;      // [sumS+1]
   const int32_t* in_src;
@@ -52,11 +58,12 @@ struct LsArgs {
   float beam, lattice_beam, acoustic_scale;
   int32_t prune_interval, tok_cap;   // tok_cap: most live tokens on one frame (0: no limit)
   int32_t amax;               // arc bound the slices were laid out with (>= every utterance's arc count)
+  int32_t hub;                // arc loops of states with more arcs than this are walked by a wave (0: never)
 };
 
 // the per-utterance slice: dense rows [T+1][S] of D, X, BP (best-path in-arc), R (byte), per-frame cutoffs, the graph tables, and
 // six working rows of the best-path distances (frame f, frame f+1, Jacobi round buffer; Value1 and Value2 each)
-struct LsLayout { int64_t D, X, BP, R, pcut, ecut, dst, nieps, w, total; };
+struct LsLayout { int64_t D, X, BP, R, pcut, ecut, dst, nieps, w, hub, total; };
 __host__ __device__ inline LsLayout ls_layout(int64_t T, int64_t S, int64_t A) {
   LsLayout L;
   int64_t o = 0;
@@ -71,6 +78,7 @@ __host__ __device__ inline LsLayout ls_layout(int64_t T, int64_t S, int64_t A) {
   L.dst = take(4 * A);
   L.nieps = take(4 * S);
   L.w = take(4 * 6 * S);
+  L.hub = take(4 * 2 * S);      // the hub states by in-degree, then by out-degree
   L.total = o;
   return L;
 }
@@ -95,17 +103,37 @@ __device__ __forceinline__ bool ls_less(float a1, float a2, float b1, float b2) 
   return a1 < b1;
 }
 
+#define LS_NONE 0x7fffffff
+// over the wave: the least v and, among equal v, the least pos (the serial loop's strict `<` keeps the first of equals); identity (INF, LS_NONE)
+__device__ __forceinline__ void ls_wave_min_first(float& v, int& pos) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o);
+    const int op = __shfl_xor(pos, o);
+    if (ov < v || (ov == v && op < pos)) { v = ov; pos = op; }
+  }
+}
+// the same for LatticeWeight pairs under ls_less; pos == LS_NONE: no candidate
+__device__ __forceinline__ void ls_wave_best_first(float& b1, float& b2, int& pos) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const float o1 = __shfl_xor(b1, o), o2 = __shfl_xor(b2, o);
+    const int op = __shfl_xor(pos, o);
+    if (op != LS_NONE && (pos == LS_NONE || ls_less(o1, o2, b1, b2) || (!ls_less(b1, b2, o1, o2) && op < pos))) { b1 = o1; b2 = o2; pos = op; }
+  }
+}
+
 __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
 #pragma clang fp contract(off)
   __shared__ float red[LS_NW];
+  __shared__ int hcnt[2][LS_NW];
   const int NT = (int)blockDim.x, tid = (int)threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6, nwave = NT >> 6;
   const int k = u0 + (int)blockIdx.x;
   const int u = a.list[k];
   const int64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const int tpad = (T + 31) & ~31;
-  const int64_t s0 = a.state_off[u];
-  const int S = (int)(a.state_off[u + 1] - s0);
+  const int64_t s0 = a.state_off[a.gidx[u]];
+  const int S = (int)(a.state_off[a.gidx[u] + 1] - s0);
   const int64_t in0 = a.in_off[s0];
   const float* llu = a.ll + a.ll_off[u];
   const LsLayout L = ls_layout(T, S, a.amax);
@@ -119,8 +147,11 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
   int32_t* dst = reinterpret_cast<int32_t*>(base + L.dst);
   int32_t* nieps = reinterpret_cast<int32_t*>(base + L.nieps);
   float* wrk = reinterpret_cast<float*>(base + L.w);
+  int32_t* hub_in = reinterpret_cast<int32_t*>(base + L.hub);
+  int32_t* hub_out = hub_in + S;
+  const int64_t hub_thr = a.hub > 0 ? a.hub : INT64_MAX;
   const float INF = __builtin_huge_valf();
-  const int start = a.start[u];
+  const int start = a.start[a.gidx[u]];
   // khg_utts_create refuses start >= S only: a graph without a start state (kNoStateId, the reference's KHG_ASSERT at :52) has no path
   if (start < 0 || start >= S) {
     for (int t = tid; t < T; t += NT) a.ali[f0 + t] = 0;
@@ -142,13 +173,48 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
   // -1 * LogLikelihood(frame, ilabel) with DecodableAmDiagGmmScaled's scale (1 for scores uploaded already scaled)
   auto ac_cost = [&](int ai, int frame) { return -(a.acoustic_scale * llu[(int64_t)a.in_col[in0 + ai] * tpad + frame]); };
 
+  // the hub states, in state order: in-degree above the threshold, then out-degree above it (the counts are workgroup-uniform)
+  int nhub_in = 0, nhub_out = 0;
+  if (a.hub > 0) {
+    for (int sb = 0; sb < S; sb += NT) {
+      const int s = sb + tid;
+      const bool hi = s < S && a.in_off[s0 + s + 1] - a.in_off[s0 + s] > hub_thr;
+      const bool ho = s < S && a.out_off[s0 + s + 1] - a.out_off[s0 + s] > hub_thr;
+      const unsigned long long bi = __ballot(hi), bo = __ballot(ho);
+      if (lane == 0) { hcnt[0][wave] = __popcll(bi); hcnt[1][wave] = __popcll(bo); }
+      __syncthreads();
+      int oi = nhub_in, oo = nhub_out;
+      for (int j = 0; j < nwave; ++j) {
+        if (j < wave) { oi += hcnt[0][j]; oo += hcnt[1][j]; }
+        nhub_in += hcnt[0][j]; nhub_out += hcnt[1][j];
+      }
+      const unsigned long long below = (1ull << lane) - 1ull;
+      if (hi) hub_in[oi + __popcll(bi & below)] = s;
+      if (ho) hub_out[oo + __popcll(bo & below)] = s;
+      __syncthreads();
+    }
+  }
   // graph tables: destination of every in-arc, fst_.NumInputEpsilons of every state
   for (int s = tid; s < S; s += NT) {
-    for (int64_t i = a.in_off[s0 + s]; i < a.in_off[s0 + s + 1]; ++i) dst[i - in0] = s;
-    int n = 0;
-    for (int64_t oa = a.out_off[s0 + s]; oa < a.out_off[s0 + s + 1]; ++oa) n += a.in_col[in0 + a.out_inidx[oa]] < 0;
-    nieps[s] = n;
     Drow[s] = s == start ? 0.0f : INF;   // InitDecoding: the start token, cost 0
+    const int64_t i0 = a.in_off[s0 + s], i1 = a.in_off[s0 + s + 1], o0 = a.out_off[s0 + s], o1 = a.out_off[s0 + s + 1];
+    if (i1 - i0 <= hub_thr)
+      for (int64_t i = i0; i < i1; ++i) dst[i - in0] = s;
+    if (o1 - o0 > hub_thr) continue;
+    int n = 0;
+    for (int64_t oa = o0; oa < o1; ++oa) n += a.in_col[in0 + a.out_inidx[oa]] < 0;
+    nieps[s] = n;
+  }
+  for (int h = wave; h < nhub_in; h += nwave) {
+    const int s = hub_in[h];
+    for (int64_t i = a.in_off[s0 + s] + lane; i < a.in_off[s0 + s + 1]; i += 64) dst[i - in0] = s;
+  }
+  for (int h = wave; h < nhub_out; h += nwave) {
+    const int s = hub_out[h];
+    int n = 0;
+    for (int64_t oa = a.out_off[s0 + s] + lane; oa < a.out_off[s0 + s + 1]; oa += 64) n += a.in_col[in0 + a.out_inidx[oa]] < 0;
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    if (lane == 0) nieps[s] = n;
   }
   __syncthreads();
 
@@ -159,9 +225,11 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
     for (int round = 0;; ++round) {
       int changed = 0;
       for (int n = tid; n < S; n += NT) {
+        const int64_t i0 = a.in_off[s0 + n], i1 = a.in_off[s0 + n + 1];
+        if (i1 - i0 > hub_thr) continue;       // a hub state: below
         const float cur = D[n];
         float best = cur;
-        for (int64_t i = a.in_off[s0 + n]; i < a.in_off[s0 + n + 1]; ++i) {
+        for (int64_t i = i0; i < i1; ++i) {
           const int ai = (int)(i - in0);
           if (a.in_col[i] >= 0) continue;
           const float dm = D[a.in_src[i]];
@@ -170,6 +238,22 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
           if (tot < cut && tot < best) best = tot;
         }
         if (best < cur) { D[n] = best; changed = 1; }
+      }
+      for (int h = wave; h < nhub_in; h += nwave) {
+        const int n = hub_in[h];
+        const int64_t i0 = a.in_off[s0 + n], i1 = a.in_off[s0 + n + 1];
+        const float cur = D[n];
+        float best = INF;
+        int pos = LS_NONE;
+        for (int64_t i = i0 + lane; i < i1; i += 64) {
+          if (a.in_col[i] >= 0) continue;
+          const float dm = D[a.in_src[i]];
+          if (dm == INF) continue;
+          const float tot = dm + arc_w((int)(i - in0));
+          if (tot < cut && tot < best) { best = tot; pos = (int)(i - i0); }
+        }
+        ls_wave_min_first(best, pos);
+        if (lane == 0 && best < cur) { D[n] = best; changed = 1; }
       }
       if (!__syncthreads_or(changed)) return true;
       if (round > S) return false;
@@ -203,8 +287,10 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
     float lmin = INF;
     int nan = 0;
     for (int n = tid; n < S; n += NT) {
+      const int64_t i0 = a.in_off[s0 + n], i1 = a.in_off[s0 + n + 1];
+      if (i1 - i0 > hub_thr) continue;       // a hub state: below
       float c = INF;
-      for (int64_t i = a.in_off[s0 + n]; i < a.in_off[s0 + n + 1]; ++i) {
+      for (int64_t i = i0; i < i1; ++i) {
         if (a.in_col[i] < 0) continue;
         const float dm = Dp[a.in_src[i]];
         if (dm == INF) continue;
@@ -215,6 +301,23 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
       }
       Dn[n] = c;
       lmin = fminf(lmin, c);
+    }
+    for (int h = wave; h < nhub_in; h += nwave) {
+      const int n = hub_in[h];
+      const int64_t i0 = a.in_off[s0 + n], i1 = a.in_off[s0 + n + 1];
+      float c = INF;
+      int pos = LS_NONE;
+      for (int64_t i = i0 + lane; i < i1; i += 64) {
+        if (a.in_col[i] < 0) continue;
+        const float dm = Dp[a.in_src[i]];
+        if (dm == INF) continue;
+        const int ai = (int)(i - in0);
+        const float tot = (dm + ac_cost(ai, t)) + arc_w(ai);
+        if (tot != tot) nan = 1;
+        else if (tot < c) { c = tot; pos = (int)(i - i0); }
+      }
+      ls_wave_min_first(c, pos);
+      if (lane == 0) { Dn[n] = c; lmin = fminf(lmin, c); }
     }
     const float best = ls_block_min(lmin, red);
     if (__syncthreads_or(nan) && nan_frame < 0) nan_frame = t;
@@ -275,9 +378,46 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
     __syncthreads();
     for (;;) {
       int changed = 0;
+      for (int h = wave; h < nhub_out; h += nwave) {       // the hub states (by out-degree)
+        const int m = hub_out[h];
+        const float dm = D[m];
+        if (dm == INF) continue;
+        const int64_t o0 = a.out_off[s0 + m], o1 = a.out_off[s0 + m + 1];
+        float te = INF;
+        int pos = LS_NONE;
+        for (int64_t oa = o0 + lane; oa < o1; oa += 64) {
+          const int ai = a.out_inidx[oa];
+          const int kk = dst[ai];
+          const float g = arc_w(ai);
+          float le;
+          if (a.in_col[in0 + ai] >= 0) {
+            if (last) continue;
+            const float tot = (dm + ac_cost(ai, f)) + g;
+            if (!(tot < pcut[f + 1]) || !Rn[kk]) continue;
+            le = Xn[kk] + (tot - Dn[kk]);
+          } else {
+            if (!(dm + g < ecut[f])) continue;
+            le = X[kk] + (((dm + 0.0f) + g) - D[kk]);
+          }
+          if (le > beamL) continue;
+          if (le < 0.0f) le = 0.0f;
+          if (le < te) { te = le; pos = (int)(oa - o0); }
+        }
+        ls_wave_min_first(te, pos);
+        if (lane == 0) {
+          if (last) {   // the final-cost term comes first in the serial order: it stays on a tie
+            const float fc = a.final_w[s0 + m];
+            const float ft = dm + fc - final_best_cost;
+            if (!(te < ft)) te = ft;
+            if (te > beamL) te = INF;
+          }
+          if (te != X[m]) { X[m] = te; changed = 1; }
+        }
+      }
       for (int m = tid; m < S; m += NT) {
         const float dm = D[m];
         if (dm == INF) continue;
+        if (a.out_off[s0 + m + 1] - a.out_off[s0 + m] > hub_thr) continue;       // a hub state: above
         float te = INF;
         if (last) {   // PruneForwardLinksFinal (:483-582): a term for the final cost
           const float fc = a.final_w[s0 + m];
@@ -334,7 +474,28 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
     int32_t* BP = BProw + (int64_t)f * S;
     for (int round = 0;; ++round) {
       int changed = 0;
+      for (int h = wave; h < nhub_in; h += nwave) {        // the hub states
+        const int n = hub_in[h];
+        float b1 = INF, b2 = INF;
+        int pos = LS_NONE;
+        for (int64_t i = a.in_off[s0 + n] + lane; i < a.in_off[s0 + n + 1]; i += 64) {
+          if (a.in_col[i] >= 0) continue;
+          const int m = a.in_src[i];
+          if (B1[m] == INF) continue;
+          float g;
+          if (!eps_ok(i, D, X, ecut[f], n, &g)) continue;
+          const float c1 = B1[m] + g, c2 = B2[m] + 0.0f;
+          if (pos == LS_NONE || ls_less(c1, c2, b1, b2)) { b1 = c1; b2 = c2; pos = (int)(i - in0); }
+        }
+        ls_wave_best_first(b1, b2, pos);
+        if (lane == 0) {
+          const float o1 = B1[n], o2 = B2[n];
+          if (pos != LS_NONE && (o1 == INF || ls_less(b1, b2, o1, o2))) { N1[n] = b1; N2[n] = b2; BP[n] = pos; changed = 1; }
+          else { N1[n] = o1; N2[n] = o2; }
+        }
+      }
       for (int n = tid; n < S; n += NT) {
+        if (a.in_off[s0 + n + 1] - a.in_off[s0 + n] > hub_thr) continue;       // a hub state: above
         float b1 = B1[n], b2 = B2[n];
         int bp = -2;
         for (int64_t i = a.in_off[s0 + n]; i < a.in_off[s0 + n + 1]; ++i) {
@@ -368,7 +529,32 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_simple(LsArgs a, int u0) {
     const float* Xn = Xrow + (int64_t)(f + 1) * S;
     const unsigned char* Rn = Rrow + (int64_t)(f + 1) * S;
     int32_t* BPn = BProw + (int64_t)(f + 1) * S;
+    for (int h = wave; h < nhub_in; h += nwave) {          // the hub states
+      const int n = hub_in[h];
+      float b1 = INF, b2 = INF;
+      int pos = LS_NONE;
+      if (Rn[n] && Xn[n] != INF) {
+        for (int64_t i = a.in_off[s0 + n] + lane; i < a.in_off[s0 + n + 1]; i += 64) {
+          if (a.in_col[i] < 0) continue;
+          const int m = a.in_src[i];
+          if (P1[m] == INF) continue;
+          const int ai = (int)(i - in0);
+          const float ac = ac_cost(ai, f), g = arc_w(ai), tot = (D[m] + ac) + g;
+          if (!(tot < pcut[f + 1])) continue;
+          const float le = Xn[n] + (tot - Dn[n]);
+          if (!(le <= beamL)) continue;
+          const float c1 = P1[m] + g, c2 = P2[m] + ac;
+          if (pos == LS_NONE || ls_less(c1, c2, b1, b2)) { b1 = c1; b2 = c2; pos = ai; }
+        }
+        ls_wave_best_first(b1, b2, pos);
+      }
+      if (lane == 0) {
+        Q1[n] = b1; Q2[n] = b2;
+        if (pos != LS_NONE) BPn[n] = pos;
+      }
+    }
     for (int n = tid; n < S; n += NT) {
+      if (a.in_off[s0 + n + 1] - a.in_off[s0 + n] > hub_thr) continue;       // a hub state: above
       float b1 = INF, b2 = INF;
       if (Rn[n] && Xn[n] != INF) {
         for (int64_t i = a.in_off[s0 + n]; i < a.in_off[s0 + n + 1]; ++i) {

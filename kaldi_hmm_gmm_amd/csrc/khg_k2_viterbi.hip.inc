@@ -23,7 +23,8 @@
 struct K2Args {
   // utterance set
   const int64_t* frame_off;   // [U+1]
-  const int64_t* state_off;   // [U+1]
+  const int32_t* gidx;        // [U] the row of state_off / start an utterance decodes on (identity; zeros on a shared graph)
+  const int64_t* state_off;   // [rows+1]
   const int32_t* start;       // [U]
   const int64_t* in_off;      // [sumS+1]  in-arcs (by destination), global offsets
   const int32_t* in_src;      // local source state
@@ -97,8 +98,8 @@ __device__ int k2_finish(const K2Args& a, int u, int best_state, const int32_t* 
   const int64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const int tpad = (T + 31) & ~31;
-  const int S = (int)(a.state_off[u + 1] - a.state_off[u]);
-  const int64_t in0 = a.in_off[a.state_off[u]];
+  const int S = (int)(a.state_off[a.gidx[u] + 1] - a.state_off[a.gidx[u]]);
+  const int64_t in0 = a.in_off[a.state_off[a.gidx[u]]];
   const uint8_t* bp = a.bp + a.bp_off[u];
   int32_t* path = a.path + a.path_off[u];
   const int path_cap = (int)(a.path_off[u + 1] - a.path_off[u]);
@@ -153,7 +154,7 @@ __device__ int k2_finish(const K2Args& a, int u, int best_state, const int32_t* 
     cost = ncost;
     if (certify && ok) ok = node_ok(cost, t);
   }
-  v1 = a.final_w[a.state_off[u] + best_state] + v1;  // faster-decoder.cc:415-417
+  v1 = a.final_w[a.state_off[a.gidx[u]] + best_state] + v1;  // faster-decoder.cc:415-417
   v2 = 0.0f + v2;
   a.num_words[u] = nw;
   a.like[u] = -(v1 + v2) / a.like_scale;         // decoder-wrappers.cc:95
@@ -246,17 +247,17 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
   // the remaining waves.  Every per-block quantity below (strides, reductions, the packed back-pointer pitch)
   // uses this utterance's own nthr / nwave.
   const int tid = threadIdx.x, lane = tid & 63;
-  const int nthr = min((int)blockDim.x, max(64, (((int)(a.state_off[u + 1] - a.state_off[u]) + (FAST ? KS : 1) - 1) / (FAST ? KS : 1) + 63) & ~63));
+  const int nthr = min((int)blockDim.x, max(64, (((int)(a.state_off[a.gidx[u] + 1] - a.state_off[a.gidx[u]]) + (FAST ? KS : 1) - 1) / (FAST ? KS : 1) + 63) & ~63));
   if (tid >= nthr) return;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwave = nthr >> 6;
   const int64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const int tpad = (T + 31) & ~31;
-  const int64_t s0 = a.state_off[u];
-  const int S = (int)(a.state_off[u + 1] - s0);
+  const int64_t s0 = a.state_off[a.gidx[u]];
+  const int S = (int)(a.state_off[a.gidx[u] + 1] - s0);
   const int64_t in0 = a.in_off[s0];
   const int A = (int)(a.in_off[s0 + S] - in0);
-  const int start = a.start[u];
+  const int start = a.start[a.gidx[u]];
   const int npdf = (int)((a.ll_off[u + 1] - a.ll_off[u]) / (tpad > 0 ? tpad : 1));
   const int PP = npdf | 1;   // odd pitch: the frame-major score block is bank-conflict free
   const int Sp = (S + 15) & ~15;                       // generic back-pointer row pitch (bytes)
@@ -954,11 +955,11 @@ __global__ void k2_viterbi_faithful(K2Args a) {
   const int64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const int tpad = (T + 31) & ~31;
-  const int64_t s0 = a.state_off[u];
-  const int S = (int)(a.state_off[u + 1] - s0);
+  const int64_t s0 = a.state_off[a.gidx[u]];
+  const int S = (int)(a.state_off[a.gidx[u] + 1] - s0);
   const int64_t in0 = a.in_off[s0];
   const int A = (int)(a.in_off[s0 + S] - in0);
-  const int start = a.start[u];
+  const int start = a.start[a.gidx[u]];
   const float* llu = a.ll + a.ll_off[u];
   uint8_t* bp = a.bp + a.bp_off[u];
 
@@ -1223,12 +1224,12 @@ __global__ __launch_bounds__(64) void k2_viterbi_faithful_wave(K2Args a, int eps
   const int64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const int tpad = (T + 31) & ~31;
-  const int64_t s0 = a.state_off[u];
-  const int S = (int)(a.state_off[u + 1] - s0);
+  const int64_t s0 = a.state_off[a.gidx[u]];
+  const int S = (int)(a.state_off[a.gidx[u] + 1] - s0);
   const int64_t in0 = a.in_off[s0];
   const int A = (int)(a.in_off[s0 + S] - in0);
   const int64_t o0 = a.out_off[s0];
-  const int start = a.start[u];
+  const int start = a.start[a.gidx[u]];
   const float* llu = a.ll + a.ll_off[u];
   uint8_t* bp = a.bp + a.bp_off[u];
   const int Sp = (S + 15) & ~15;
@@ -1755,9 +1756,9 @@ __device__ int k2_finish_wave(const K2Args& a, int u, int best_state, const int3
   const int64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const int tpad = (T + 31) & ~31;
-  const int S = (int)(a.state_off[u + 1] - a.state_off[u]);
+  const int S = (int)(a.state_off[a.gidx[u] + 1] - a.state_off[a.gidx[u]]);
   const int Sp = (S + 15) & ~15;
-  const int64_t in0 = a.in_off[a.state_off[u]];
+  const int64_t in0 = a.in_off[a.state_off[a.gidx[u]]];
   const uint8_t* bp = a.bp + a.bp_off[u];
   int32_t* path = a.path + a.path_off[u];
   const int path_cap = (int)(a.path_off[u + 1] - a.path_off[u]);
@@ -1836,7 +1837,7 @@ __device__ int k2_finish_wave(const K2Args& a, int u, int best_state, const int3
       v2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ac_cost), k)) + v2;
     }
   }
-  v1 = a.final_w[a.state_off[u] + best_state] + v1;  // faster-decoder.cc:415-417
+  v1 = a.final_w[a.state_off[a.gidx[u]] + best_state] + v1;  // faster-decoder.cc:415-417
   v2 = 0.0f + v2;
   if (lane == 0) {
     a.num_words[u] = nw;
@@ -1887,12 +1888,12 @@ __global__ __launch_bounds__(64) void k2_viterbi_faithful_chain(K2Args a, int ma
   const int64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const int tpad = (T + 31) & ~31;
-  const int64_t s0 = a.state_off[u];
-  const int S = (int)(a.state_off[u + 1] - s0);
+  const int64_t s0 = a.state_off[a.gidx[u]];
+  const int S = (int)(a.state_off[a.gidx[u] + 1] - s0);
   const int64_t in0 = a.in_off[s0];
   const int A = (int)(a.in_off[s0 + S] - in0);
   const int64_t o0 = a.out_off[s0];
-  const int start = a.start[u];
+  const int start = a.start[a.gidx[u]];
   const float* llu = a.ll + a.ll_off[u];
   uint8_t* bp = a.bp + a.bp_off[u];
   const int Sp = (S + 15) & ~15;

@@ -28,6 +28,40 @@ py::dict CsrToDict(const GraphsCsr& c) {
   return d;
 }
 
+// DecodingGraph(fst, tm, ctx=None): one decoding graph resident in HBM (khg_graph_create) that any number of utterance sets and
+// batch calls decode on.  tm: a TransitionModel (its cached device table on `ctx`, default: the default context) or a
+// DeviceTransitions (then the graph lives on that table's context).
+struct PyDecodingGraph {
+  khg_graph* h = nullptr;
+  py::object keep_ctx, keep_tm;
+  int64_t num_states = 0, num_arcs = 0, device_bytes = 0;
+  int32_t num_pdfs = 0, max_in_degree = 0;
+  PyDecodingGraph(std::shared_ptr<StdVectorFst> fst, py::object tm, py::object ctx) : keep_ctx(ctx), keep_tm(tm) {
+    if (!fst) throw Error("DecodingGraph: fst is None");
+    if (fst->Start() == kNoStateId) throw Error("start_state != fst::kNoStateId assertion failed");
+    khg_ctx* c = nullptr;
+    khg_tm* t = nullptr;
+    if (py::isinstance<TransitionModel>(tm)) {
+      c = ctx.is_none() ? DefaultCtx() : reinterpret_cast<khg_ctx*>(ctx.attr("h").cast<uintptr_t>());
+      t = tm.cast<std::shared_ptr<TransitionModel>>()->DeviceTm(c);
+    } else {
+      if (ctx.is_none()) keep_ctx = tm.attr("ctx");
+      c = reinterpret_cast<khg_ctx*>(keep_ctx.attr("h").cast<uintptr_t>());
+      t = reinterpret_cast<khg_tm*>(tm.attr("h").cast<uintptr_t>());
+    }
+    const GraphsCsr g = ConcatGraphs({fst.get()});
+    {
+      py::gil_scoped_release nogil;
+      CApi(khg_graph_create(c, t, (int32_t)g.state_off.back(), g.start[0], g.arc_off.data(), g.ilabel.data(), g.olabel.data(), g.weight.data(),
+                            g.nextstate.data(), g.final_w.data(), &h));
+    }
+    CApi(khg_graph_info(h, &num_states, &num_arcs, &num_pdfs, &max_in_degree, &device_bytes));
+  }
+  PyDecodingGraph(const PyDecodingGraph&) = delete;
+  ~PyDecodingGraph() { close(); }
+  void close() { if (h) { khg_graph_destroy(h); h = nullptr; } }
+};
+
 // python/csrc/decodable-itf.cc:14-53: a decodable written in Python overrides these four
 class PyDecodableInterface : public DecodableInterface {
  public:
@@ -73,23 +107,40 @@ py::list ResultsToList(const std::vector<AlignResult>& rs, const std::vector<int
 }
 
 // align_batch(am, tm, fsts, feats_list, config, acoustic_scale, trans_cost=None, decoder_opts=None, return_scores=False)
-py::list AlignBatchPy(std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, std::vector<std::shared_ptr<StdVectorFst>> fsts, py::list feats_list,
+// fsts: one graph per utterance; or ONE for all of them -- a StdVectorFst, a list of one, or a DecodingGraph -- which the batch then
+// shares (GraphsCsr::shared: planned and uploaded once)
+py::list AlignBatchPy(std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, py::object fsts_o, py::list feats_list,
                       py::object config, float acoustic_scale, py::object trans_cost, py::object decoder_opts, bool return_scores) {
   const AlignConfig cfg = ConfigFrom(config);
   CheckBeams(cfg);
-  std::vector<StdVectorFst> careful;           // on copies: the batch entry point leaves the caller's graphs alone
-  std::vector<const StdVectorFst*> gp;
-  if (cfg.careful) {
-    careful.reserve(fsts.size());
-    for (auto& f : fsts) {
-      careful.push_back(*f);
-      if (careful.back().Start() != kNoStateId) ModifyGraphForCarefulAlignment(&careful.back());
-    }
-    for (auto& f : careful) gp.push_back(&f);
+  GraphsCsr csr;
+  if (py::isinstance<PyDecodingGraph>(fsts_o)) {
+    if (cfg.careful) throw Error("align_batch: careful alignment modifies the graph; pass the StdVectorFst, not a DecodingGraph");
+    PyDecodingGraph& dg = fsts_o.cast<PyDecodingGraph&>();
+    if (!dg.h) throw Error("align_batch: the DecodingGraph is closed");
+    csr.shared = true; csr.device = dg.h;
   } else {
-    for (auto& f : fsts) gp.push_back(f.get());
+    std::vector<std::shared_ptr<StdVectorFst>> fsts;
+    if (py::isinstance<StdVectorFst>(fsts_o)) fsts.push_back(fsts_o.cast<std::shared_ptr<StdVectorFst>>());
+    else fsts = fsts_o.cast<std::vector<std::shared_ptr<StdVectorFst>>>();
+    const bool shared = (py::isinstance<StdVectorFst>(fsts_o) || (fsts.size() == 1 && py::len(feats_list) >= 1)) && fsts[0] &&
+                        fsts[0]->Start() != kNoStateId;       // (an empty graph: the per-utterance path reports it per utterance)
+    std::vector<StdVectorFst> careful;           // on copies: the batch entry point leaves the caller's graphs alone
+    std::vector<const StdVectorFst*> gp;
+    if (cfg.careful) {
+      careful.reserve(fsts.size());
+      for (auto& f : fsts) {
+        careful.push_back(*f);
+        if (careful.back().Start() != kNoStateId) ModifyGraphForCarefulAlignment(&careful.back());
+      }
+      for (auto& f : careful) gp.push_back(&f);
+    } else {
+      for (auto& f : fsts) gp.push_back(f.get());
+    }
+    if (!shared && py::isinstance<StdVectorFst>(fsts_o)) for (size_t i = 1; i < py::len(feats_list); ++i) gp.push_back(gp[0]);
+    csr = ConcatGraphs(gp);
+    csr.shared = shared;
   }
-  const GraphsCsr csr = ConcatGraphs(gp);
   const int D = am->Dim();
   std::vector<Arr<float>> keep;
   std::vector<const float*> fp;
@@ -137,6 +188,8 @@ struct BatchArgs {
   std::vector<int64_t> nf;
   std::vector<const StdVectorFst*> gp;
   std::vector<std::shared_ptr<StdVectorFst>> hold;
+  bool shared = false;
+  khg_graph* device = nullptr;
   BatchArgs(const AmDiagGmm& am, py::object fsts, py::list feats_list, const std::string& name) {
     const int D = am.Dim();
     for (py::handle f : feats_list) {
@@ -146,16 +199,29 @@ struct BatchArgs {
       fp.push_back(a.data());
       nf.push_back((int64_t)(a.size() / D));
     }
+    if (py::isinstance<PyDecodingGraph>(fsts)) {
+      PyDecodingGraph& dg = fsts.cast<PyDecodingGraph&>();
+      if (!dg.h) throw Error(name + ": the DecodingGraph is closed");
+      shared = true; device = dg.h;
+      return;
+    }
     if (py::isinstance<StdVectorFst>(fsts)) {
       hold.push_back(fsts.cast<std::shared_ptr<StdVectorFst>>());
-      for (size_t i = 0; i < fp.size(); ++i) gp.push_back(hold[0].get());
+      shared = true;
     } else {
       hold = fsts.cast<std::vector<std::shared_ptr<StdVectorFst>>>();
-      if (hold.size() == 1) for (size_t i = 0; i < fp.size(); ++i) gp.push_back(hold[0].get());
-      else for (auto& f : hold) gp.push_back(f.get());
+      shared = hold.size() == 1;
     }
-    if (gp.size() != fp.size()) throw Error(name + ": one graph, or one graph per utterance");
+    for (auto& f : hold) gp.push_back(f.get());
+    if (!shared && gp.size() != fp.size()) throw Error(name + ": one graph, or one graph per utterance");
     for (auto* g : gp) if (!g || g->Start() == kNoStateId) throw Error("start_state != fst::kNoStateId assertion failed");
+  }
+  // one graph for all utterances is shared, not repeated: planned and uploaded once (khg_utts_create_on_graph)
+  GraphsCsr Csr() const {
+    GraphsCsr c;
+    if (!device) c = ConcatGraphs(gp);
+    c.shared = shared; c.device = device;
+    return c;
   }
 };
 // what the reference stops on in DecodeUtteranceLatticeSimple (KHG_ERR / KHG_ASSERT), raised with its message
@@ -258,7 +324,7 @@ void BindLattice(py::module_& m) {
     const std::vector<int64_t>& nf = b.nf;
     std::vector<LatticeResult> rs;
     {
-      const GraphsCsr csr = ConcatGraphs(b.gp);
+      const GraphsCsr csr = b.Csr();
       py::gil_scoped_release nogil;
       rs = DecodeLatticeBatch(*am, *tm, csr, fp, nf, config, acoustic_scale, allow_partial, return_scores, scratch_per_frame);
     }
@@ -319,7 +385,7 @@ void BindLattice(py::module_& m) {
     BatchArgs b(*am, fsts, feats_list, "decode_lattice_simple_batch");
     std::vector<LatticeResult> rs;
     {
-      const GraphsCsr csr = ConcatGraphs(b.gp);
+      const GraphsCsr csr = b.Csr();
       py::gil_scoped_release nogil;
       rs = DecodeLatticeSimpleBatch(*am, *tm, csr, b.fp, b.nf, config, acoustic_scale, allow_partial, return_scores, scratch_per_frame);
     }
@@ -393,6 +459,15 @@ void BindAlign(py::module_& m) {
              if (feats.ndim() != 2) throw Error("feats must be a 2-D float matrix");
              return std::make_shared<DecodableCtc>(feats.data(), (int64_t)feats.shape(0), (int64_t)feats.shape(1));
            }), py::arg("feats"));
+
+  py::class_<PyDecodingGraph>(m, "DecodingGraph")
+      .def(py::init<std::shared_ptr<StdVectorFst>, py::object, py::object>(), py::arg("fst"), py::arg("tm"), py::arg("ctx") = py::none())
+      .def_property_readonly("h", [](PyDecodingGraph& g) { return reinterpret_cast<uintptr_t>(g.h); })
+      .def_readonly("ctx", &PyDecodingGraph::keep_ctx)
+      .def_readonly("num_states", &PyDecodingGraph::num_states).def_readonly("num_arcs", &PyDecodingGraph::num_arcs)
+      .def_readonly("num_pdfs", &PyDecodingGraph::num_pdfs).def_readonly("max_in_degree", &PyDecodingGraph::max_in_degree)
+      .def_readonly("device_bytes", &PyDecodingGraph::device_bytes)
+      .def("close", &PyDecodingGraph::close);
 
   m.def("align_batch", &AlignBatchPy, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"),
         py::arg("trans_cost") = py::none(), py::arg("decoder_opts") = py::none(), py::arg("return_scores") = false);

@@ -75,7 +75,7 @@ struct KContext {
   static int opt_id(const py::object& o) {
     if (py::isinstance<py::int_>(o)) return o.cast<int>();
     static const char* names[KHG_OPT_COUNT] = {"k1_form", "k1_order", "k1_nf", "k1p_ts", "k1_interleave", "k1_dbg", "k2_inorder", "k2_ks", "k2_serial",
-                                               "k2_prof", "k3_bucket", "k3_form", "k3_phase_b", "k3_ny", "debug", "k3_phase_a", "k2_split"};
+                                               "k2_prof", "k3_bucket", "k3_form", "k3_phase_b", "k3_ny", "debug", "k3_phase_a", "k2_split", "k2s_hub"};
     const std::string n = o.cast<std::string>();
     for (int i = 0; i < KHG_OPT_COUNT; ++i) if (n == names[i]) return i;
     if (n == "scratch_bytes") return KHG_INFO_SCRATCH_BYTES;       // read-only
@@ -380,8 +380,9 @@ struct KUtts {
   Arr<int64_t> frame_off;
   int n_utt = 0, dim = 0;
   int64_t state_total = 0;     // states over all graphs (bounds the words of a lattice decode)
-  KUtts(py::object ctx_o, py::object tm, Arr<int64_t> fo, py::object feats, py::object dim_o, py::object graphs)
+  KUtts(py::object ctx_o, py::object tm, Arr<int64_t> fo, py::object feats, py::object dim_o, py::object graphs, py::object graph)
       : ctx_obj(ctx_o), ctx(ctx_o.cast<KContext*>()), frame_off(fo) {
+    if (!graphs.is_none() && !graph.is_none()) throw py::value_error("UtteranceSet: exactly one of graphs / graph");
     n_utt = (int)fo.shape(0) - 1;
     const float* feats_h = nullptr;
     const float* feats_d = nullptr;
@@ -399,7 +400,12 @@ struct KUtts {
       feats_h = fh.data();
     }
     const khg_tm* tmh = tm.is_none() ? nullptr : tm.cast<KTransitions*>()->h;
-    if (graphs.is_none()) {
+    if (!graph.is_none()) {          // a DecodingGraph: every utterance decodes on it (the set holds its own reference to the tables)
+      khg_graph* gh = reinterpret_cast<khg_graph*>(graph.attr("h").cast<uintptr_t>());
+      if (!gh) throw py::value_error("UtteranceSet: the DecodingGraph is closed");
+      Check(khg_utts_create_on_graph(ctx->h, tmh, gh, n_utt, dim, fo.data(), feats_h, feats_d, &h));
+      state_total = graph.attr("num_states").cast<int64_t>() * n_utt;
+    } else if (graphs.is_none()) {
       Check(khg_utts_create(ctx->h, tmh, n_utt, dim, fo.data(), feats_h, feats_d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                             nullptr, nullptr, &h));
     } else {
@@ -636,8 +642,9 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("close", &KAccs::close);
 
   py::class_<KUtts>(m, "UtteranceSet")
-      .def(py::init<py::object, py::object, Arr<int64_t>, py::object, py::object, py::object>(), py::arg("ctx"), py::arg("tm"), py::arg("frame_off"),
-           py::arg("feats"), py::arg("dim") = py::none(), py::arg("graphs") = py::none())
+      .def(py::init<py::object, py::object, Arr<int64_t>, py::object, py::object, py::object, py::object>(), py::arg("ctx"), py::arg("tm"), py::arg("frame_off"),
+           py::arg("feats"), py::arg("dim") = py::none(), py::arg("graphs") = py::none(), py::arg("graph") = py::none())
+      .def_property_readonly("graph_bytes", [](KUtts& x) { int64_t b = 0; Check(khg_utts_graph_bytes(x.h, &b)); return b; })
       .def_property_readonly("h", [](KUtts& x) { return reinterpret_cast<uintptr_t>(x.h); })
       .def_readonly("ctx", &KUtts::ctx_obj).def_readonly("frame_off", &KUtts::frame_off).def_readonly("n_utt", &KUtts::n_utt)
       .def_readonly("dim", &KUtts::dim)

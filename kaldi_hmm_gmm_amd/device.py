@@ -25,6 +25,7 @@ Comm = _ext.Comm                            # an RCCL communicator owned by the 
 DeviceModel = _ext.DeviceModel              # AmDiagGmm resident in HBM (+ mle_update, split, scale_weights)
 DeviceTransitions = _ext.DeviceTransitions  # TransitionIdToPdf + scaled transition costs
 UtteranceSet = _ext.UtteranceSet            # features + compiled graphs of a shard; loglikes / align / acc_stats
+DecodingGraph = _ext.DecodingGraph          # khg_graph: ONE decoding graph resident in HBM, shared by sets (graph=) and batch calls
 
 
 class DeviceAccs(_ext.DeviceAccs):

@@ -12,7 +12,18 @@ self-loop added on every state: no path's weight changes, and the simple decoder
 --check N (with --decoder simple) also decodes the first N utterances with their K1 scores returned and compares them, outside the
 timing, with the plain-Python restatement of the reference (tests/lattice_simple_ref.py): succeeded, alignment, words, like.
 
+--shared-graph --words W is the decoding case: ONE W-word unigram loop over the model's phones (each word a seeded random string
+of 3-6 phones, expanded to transition-id arcs with self-loops the way synth.make_utts expands its transcripts, word ids on the
+output side, an epsilon arc from a word's last state back to the loop state) and --utts utterances sampled from random word
+sequences of that lexicon.  Both lattice decoders run on the resident scores of a set created on a shared DecodingGraph and, while
+U copies of the tables stay under 8 GiB, of a set created from a list of U copies; the simple decoder (every state also carries
+an epsilon self-loop) with its hub form off and at each threshold of --hub.  Paths and options alternate inside every
+repetition.  The JSON line reports the graph, per path the set creation time, the graph bytes and the decode times (median, min,
+max), and the share of utterances that succeeded.  --check N compares the first N with both restatements.  --yesno times the simple
+decoder at the same thresholds on the 46-state word loop of examples/decode_synthetic.py instead.
+
 Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N]
+       python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
 import json
@@ -44,14 +55,218 @@ def with_eps_self_loops(graphs, u):
                                      np.asarray(w, np.float32), np.asarray(ns, np.int32), np.asarray(graphs["final"][s0:s1], np.float32))
 
 
+def word_loop(m, W, seed, eps_self_loops, loops=1):
+    """-> (graph dict, lexicon): state 0 is the loop state (start, final); word w enters its chain on the forward transition-id of
+    its first HMM state, carrying the word id w + 1, every chain state has its self-loop, the last one an epsilon arc back to 0.
+    loops = K > 1: K copies of the loop state (states 0 .. K - 1, all final, each with an arc into every word), word w returning to
+    copy w mod K -- the in-degree W divided among the copies, as with compile_word_loop_graph's loop state per final transition-state."""
+    rng = np.random.default_rng(seed)
+    nphones = m.num_pdfs // 3
+    lex = [rng.integers(0, nphones, size=int(rng.integers(3, 7))) for _ in range(W)]
+    pdfs = [(3 * np.repeat(ph, 3) + np.tile(np.arange(3), len(ph))).astype(np.int64) for ph in lex]
+    il, ol, w, ns, off = [], [], [], [], [0]
+    first, nxt = [], loops
+    for p in pdfs:
+        first.append(nxt)
+        nxt += len(p)
+    cost = float(np.log(W))
+    for c in range(loops):
+        for k, p in enumerate(pdfs):                       # a loop state: one arc per word
+            il.append(2 * int(p[0]) + 2); ol.append(k + 1); w.append(cost); ns.append(first[k])
+        if eps_self_loops:
+            il.append(0); ol.append(0); w.append(0.0); ns.append(c)
+        off.append(len(il))
+    for k, p in enumerate(pdfs):
+        for i in range(len(p)):                            # chain state i + 1 of the word: [forward (or the way back), self-loop]
+            s = first[k] + i
+            if i + 1 < len(p):
+                il.append(2 * int(p[i + 1]) + 2); ol.append(0); w.append(0.0); ns.append(s + 1)
+            else:
+                il.append(0); ol.append(0); w.append(0.0); ns.append(k % loops)
+            il.append(2 * int(p[i]) + 1); ol.append(0); w.append(0.0); ns.append(s)
+            if eps_self_loops:
+                il.append(0); ol.append(0); w.append(0.0); ns.append(s)
+            off.append(len(il))
+    final = np.full(nxt, np.inf, np.float32)
+    final[:loops] = 0.0
+    g = {"start": 0, "arc_off": np.asarray(off, np.int64), "ilabel": np.asarray(il, np.int32), "olabel": np.asarray(ol, np.int32),
+         "weight": np.asarray(w, np.float32), "nextstate": np.asarray(ns, np.int32), "final": final}
+    return g, pdfs
+
+
+def tiled(g, U):
+    """U copies of one graph dict in the CSR layout UtteranceSet(graphs=) takes."""
+    S, A = len(g["final"]), len(g["ilabel"])
+    out = {k: np.tile(g[k], U) for k in ("ilabel", "olabel", "weight", "nextstate", "final")}
+    out["arc_off"] = np.concatenate([[0], (g["arc_off"][1:][None, :] + A * np.arange(U, dtype=np.int64)[:, None]).ravel()]).astype(np.int64)
+    out["state_off"] = (S * np.arange(U + 1)).astype(np.int64)
+    out["start"] = np.full(U, g["start"], np.int32)
+    return out
+
+
+def fst_of(g):
+    return khg.StdVectorFst.from_csr(int(g["start"]), g["arc_off"], g["ilabel"], g["olabel"], g["weight"], g["nextstate"], g["final"])
+
+
+def med(xs):
+    return {"median_s": float(np.median(xs)), "min_s": float(min(xs)), "max_s": float(max(xs))}
+
+
+def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True):
+    """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
+    after one warm-up round; and the last results."""
+    times = {p: {} for p in sets}
+    last = {}
+    default = ctx.get_option("k2s_hub")
+    try:
+        for rep in range(reps + 1):
+            for p, us in sets.items():
+                if with_faster:
+                    ctx.sync(); t0 = time.time()
+                    last[(p, "faster")] = us.decode_lattice_faster(dtm, beam=13.0, max_active=7000, lattice_beam=6.0, acoustic_scale=0.1)
+                    if rep:
+                        times[p].setdefault("lattice_faster", []).append(time.time() - t0)
+                for h in hubs:
+                    ctx.set_option("k2s_hub", h)
+                    ctx.sync(); t0 = time.time()
+                    last[(p, "simple", h)] = us.decode_lattice_simple(dtm, beam=13.0, lattice_beam=6.0, acoustic_scale=0.1)
+                    if rep:
+                        times[p].setdefault("lattice_simple_hub_%d" % h, []).append(time.time() - t0)
+    finally:
+        ctx.set_option("k2s_hub", default)
+    return times, last
+
+
+def shared_graph_main(args):
+    from kaldi_hmm_gmm_amd import _gpu
+    from kaldi_hmm_gmm_amd import _kaldi_hmm_gmm_amd as ext
+    hubs = [int(x) for x in args.hub.split(",")]
+    ctx = _gpu.default_context()
+    out = {"mode": "yesno" if args.yesno else "shared-graph", "utterances": args.utts, "hub_thresholds": hubs, "hub_default": ctx.get_option("k2s_hub")}
+    if args.yesno:                      # the trained monophone model and the 46-state YES/NO word loop of examples/decode_synthetic.py
+        import types
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+        import decode_synthetic as dx
+        from kaldi_hmm_gmm_amd.training_graph import TrainingGraphCompiler, TrainingGraphCompilerOptions
+        tm, tree, am, lexicon, test_utts = dx.train(types.SimpleNamespace(utts=200, test_utts=30, iters=80, dim=23, seed=3), log=lambda *a: None)
+        gc = TrainingGraphCompiler(tm, tree, lexicon, sil_phone=dx.tr.SIL, sil_prob=0.5,
+                                   opts=TrainingGraphCompilerOptions(transition_scale=1.0, self_loop_scale=1.0))
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import lattice_simple_ref as ref
+        gl = ref.add_eps_self_loops(gc.compile_word_loop_graph().to_csr(), 0.0)
+        feats = [np.ascontiguousarray(test_utts[u % len(test_utts)][2], np.float32) for u in range(args.utts)]
+        dg = khg.DecodingGraph(fst_of(gl), tm)
+        out.update(states=dg.num_states, arcs=dg.num_arcs, max_in_degree=dg.max_in_degree)
+        scfg = khg.LatticeSimpleDecoderConfig(beam=13.0, lattice_beam=6.0)
+        times = {}
+        khg.decode_lattice_simple_batch(am, tm, dg, feats, scfg, 0.1)
+        for rep in range(args.reps):
+            for h in hubs:
+                ctx.set_option("k2s_hub", h)
+                t0 = time.time()
+                res = khg.decode_lattice_simple_batch(am, tm, dg, feats, scfg, 0.1)
+                times.setdefault("lattice_simple_batch_hub_%d" % h, []).append(time.time() - t0)
+        ctx.set_option("k2s_hub", out["hub_default"])
+        out["shared"] = {k: med(v) for k, v in times.items()}
+        out["succeeded_share"] = sum(1 for r in res if r["succeeded"]) / len(res)
+        print(json.dumps(out))
+        return
+    m = synth.make_model(5000, 64, 40, seed=args.seed)
+    g, pdfs = word_loop(m, args.words, args.seed + 7, False, args.loop_states)
+    gl, _ = word_loop(m, args.words, args.seed + 7, True, args.loop_states)
+    rng = np.random.default_rng(args.seed + 1000)
+    seqs = [np.concatenate([pdfs[int(k)] for k in rng.integers(0, args.words, size=int(rng.integers(2, 5)))]) for _ in range(args.utts)]
+    durs = [rng.geometric(0.25, size=len(sq)) for sq in seqs]
+    frame_pdf = np.concatenate([np.repeat(sq, d) for sq, d in zip(seqs, durs)])
+    fo = np.concatenate([[0], np.cumsum([int(d.sum()) for d in durs])]).astype(np.int64)
+    feats = synth.sample_feats(m, frame_pdf, rng)
+    gcs, bad = ext.compute_gconsts(m.gauss_off, m.weights, m.inv_vars, m.means_invvars)
+    dm = khg.DeviceModel(ctx, m.gauss_off, gcs, m.means_invvars, m.inv_vars)
+    dtm = khg.DeviceTransitions(ctx, m.id2pdf)
+    U = args.utts
+    out.update(words=args.words, loop_states=args.loop_states, frames=int(fo[-1]))
+    res = {}
+    for name, gg in (("faster", g), ("simple", gl)):       # the simple decoder's graph carries the epsilon self-loops
+        S, A = len(gg["final"]), len(gg["ilabel"])
+        rep_bytes = 8 * (U + 1) + 4 * U + 16 * (U * S + 1) + 24 * U * A + 4 * U * S          # from the shapes, before anything is allocated
+        ctx.sync(); t0 = time.time()
+        dg = khg.DecodingGraph(fst_of(gg), dtm)
+        sh = khg.UtteranceSet(ctx, dtm, fo, feats, graph=dg)
+        ctx.sync(); t_sh = time.time() - t0
+        entry = {"states": S, "arcs": A, "max_in_degree": dg.max_in_degree, "num_pdfs": dg.num_pdfs,
+                 "shared": {"create_s": t_sh, "graph_bytes_graph": dg.device_bytes, "graph_bytes_set": sh.graph_bytes}}
+        sets = {"shared": sh}
+        if dg.max_in_degree > 254 or S > 65535:
+            entry["replicated"] = "not run: the list-of-graphs path refuses this graph (the aligner's limits)"
+        elif rep_bytes < (8 << 30) and not args.no_replicated:
+            tg = tiled(gg, U)
+            ctx.sync(); t0 = time.time()
+            rp = khg.UtteranceSet(ctx, dtm, fo, feats, graphs=tg)
+            ctx.sync()
+            entry["replicated"] = {"create_s": time.time() - t0, "graph_bytes_set": rp.graph_bytes}
+            entry["create_ratio"] = entry["replicated"]["create_s"] / t_sh
+            entry["bytes_ratio"] = rp.graph_bytes / dg.device_bytes
+            sets["replicated"] = rp
+            del tg
+        else:
+            entry["replicated"] = "not run: %.1f GiB of tables" % (rep_bytes / 2.0 ** 30)
+        for us in sets.values():
+            us.loglikes(dm)
+        ctx.sync()
+        times, last = time_paths(ctx, dtm, sets, hubs if name == "simple" else [], args.reps, with_faster=name == "faster")
+        for p in sets:
+            entry[p].update({k: med(v) for k, v in times[p].items()})
+        key = ("shared", "faster") if name == "faster" else ("shared", "simple", hubs[0])
+        entry["succeeded_share"] = float(((last[key]["status"] & 1) != 0).mean())
+        same = all(last[key][f].tobytes() == r[f].tobytes() for r in last.values() for f in ("ali", "like", "status", "words", "words_off"))
+        entry["all_paths_and_thresholds_identical"] = bool(same)
+        if args.check > 0:
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+            import lattice_faster_ref as fref
+            import lattice_simple_ref as sref
+            am, tmh = synth.host_objects(m)
+            n = min(args.check, U)
+            fl = [feats[fo[u]: fo[u + 1]] for u in range(n)]
+            if name == "faster":
+                chk = khg.decode_lattice_faster_batch(am, tmh, dg, fl, khg.LatticeFasterDecoderConfig(max_active=7000, beam=13.0, lattice_beam=6.0), 0.1,
+                                                      return_scores=True)
+            else:
+                chk = khg.decode_lattice_simple_batch(am, tmh, dg, fl, khg.LatticeSimpleDecoderConfig(beam=13.0, lattice_beam=6.0), 0.1, return_scores=True)
+            match = 0
+            for u, r in enumerate(chk):
+                ll = fref.score_fn(r["loglikes"], r["pdfs"], m.id2pdf, 0.1)
+                if name == "faster":
+                    want = fref.decode_utterance_lattice_faster(fref.Graph.from_dict(gg), fref.Config(max_active=7000, beam=13.0, lattice_beam=6.0), ll, len(fl[u]))
+                else:
+                    want = sref.decode_utterance_lattice_simple(fref.Graph.from_dict(gg), sref.Config(beam=13.0, lattice_beam=6.0), ll, len(fl[u]))
+                match += (r["succeeded"], r["alignment"], r["words"], r["like"]) == (want["succeeded"], want["alignment"], want["words"], want["like"]) \
+                    and last[key]["ali"][fo[u]: fo[u + 1]].tolist() == r["alignment"]
+            entry.update(checked_against_restatement=n, restatement_matches=match)
+        for us in sets.values():
+            us.close()
+        dg.close()
+        res[name] = entry
+    out.update(res)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--shared-graph", action="store_true")
+    ap.add_argument("--words", type=int, default=1000)
+    ap.add_argument("--hub", default="0,32", help="thresholds of the simple decoder's hub form to time (0 = off)")
+    ap.add_argument("--no-replicated", action="store_true")
+    ap.add_argument("--loop-states", type=int, default=1, help="copies of the loop state the words' in-arcs are divided among")
+    ap.add_argument("--yesno", action="store_true")
     ap.add_argument("--utts", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--decoder", choices=("faster", "simple"), default="faster")
     ap.add_argument("--check", type=int, default=0)
     args = ap.parse_args()
+    if args.shared_graph or args.yesno:
+        shared_graph_main(args)
+        return
     m = synth.make_model(5000, 64, 40, seed=args.seed)
     am, tm = synth.host_objects(m)
     ut = synth.make_utts(m, args.utts, seed=args.seed + 1000)
