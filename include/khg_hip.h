@@ -378,6 +378,41 @@ int khg_decode_lattice_simple(khg_ctx *ctx, const khg_tm *tm, khg_utts *u, const
                               int32_t *ali_h, int32_t *words_h, int64_t *words_off_h, int64_t words_cap,
                               double *like_h, int32_t *status_h, int32_t *err_frame_h);
 
+/* ---- K2R: the raw lattice of the lattice-simple decoder ------------------------------------------------------------------------ */
+/* The raw lattices of one batch, resident on the device: what LatticeSimpleDecoder::GetRawLattice (csrc/lattice-simple-decoder.cc:
+ * 654-735) builds as an fst::VectorFst<LatticeArc> per utterance, as flat arrays.  The reference's lattice depends on the order its
+ * unordered_maps are walked in; this is the order-independent one (a subset of every walk's, equal to it whenever the walk kept no
+ * emitting link of cost >= its frame's fl(best + beam)):
+ *   states  one per (frame f in 0..T, graph state s) whose token survived FinalizeDecoding, numbered by frame, then by graph state
+ *           (:684-690); each carries frame, graph_state, tot_cost, extra_cost, final_cost (+inf unless f == T and s is final, :723-733)
+ *           and arc_begin, the index of its first arc among the utterance's (its arcs end where the next state's begin)
+ *   arcs    one per surviving forward link (:700-722), per state in the order of the graph's arcs in that state: ilabel (the
+ *           transition-id, 0 for epsilon), olabel, graph_cost (with the table's trans_cost when one is set), acoustic_cost (0 for
+ *           epsilon), nextstate (a state number of the same utterance)
+ *   start   the state of (0, graph start); -1 for an empty lattice
+ * An utterance whose status lacks KHG_LAT_SUCCEEDED has an empty lattice (GetRawLattice is only reached when Decode() is true). */
+typedef struct khg_lattices khg_lattices;
+
+/* khg_decode_lattice_simple (same arguments, same outputs) that also keeps the raw lattice of every utterance (GetRawLattice, :654-735)
+ * in *out: emitted on the device from the decoder's rows, while they are alive, with one more synchronisation per <= 4 GiB chunk of
+ * scratch slices.  An utterance whose lattice has more than 2^31 - 1 states or arcs: KHG_E_ARG, naming it.  Scores from
+ * khg_loglikes_band are refused (KHG_E_ARG).  Free *out with khg_lattices_destroy. */
+int khg_decode_lattice_simple_raw(khg_ctx *ctx, const khg_tm *tm, khg_utts *u, const khg_lattice_simple_config *cfg,
+                                  int32_t *ali_h, int32_t *words_h, int64_t *words_off_h, int64_t words_cap,
+                                  double *like_h, int32_t *status_h, int32_t *err_frame_h, khg_lattices **out);
+/* NumStates / the arc count of every utterance's lattice (:684-690, :700-722) as offsets into the flat arrays:
+ * state_off_h[n_utt + 1], arc_off_h[n_utt + 1] (either may be NULL) */
+int khg_lattices_sizes(const khg_lattices *l, int64_t *state_off_h, int64_t *arc_off_h);
+/* the lattices to host arrays (any may be NULL): per state (state_off[n_utt] entries) frame, graph_state, tot_cost, extra_cost,
+ * final_cost (Final(s).Value1(), :723-733; +inf: not final), arc_begin; per arc (arc_off[n_utt] entries) ilabel, olabel, graph_cost,
+ * acoustic_cost, nextstate (:700-722); per utterance start (SetStart, :691-692).  Synchronous. */
+int khg_lattices_download(khg_ctx *ctx, const khg_lattices *l, int32_t *frame_h, int32_t *graph_state_h, float *tot_cost_h,
+                          float *extra_cost_h, float *final_cost_h, int32_t *arc_begin_h, int32_t *ilabel_h, int32_t *olabel_h,
+                          float *graph_cost_h, float *acoustic_cost_h, int32_t *nextstate_h, int32_t *start_h);
+/* device bytes the handle owns */
+int khg_lattices_device_bytes(const khg_lattices *l, int64_t *bytes);
+int khg_lattices_destroy(khg_lattices *l);
+
 /* ---- K3: sufficient statistics ---------------------------------------------------------- */
 /* AccumAmDiagGmm (csrc/mle-am-diag-gmm.h:93-96) + transition stats (csrc/transition-model.h:176-189)
  * as ONE contiguous fp64 device buffer (a single RCCL all-reduce sums it across GPUs =

@@ -147,6 +147,13 @@ SIGNATURES = {
     "khg_lattice_simple_config_default": (None, [C.POINTER(LatticeSimpleConfigC)]),
     "khg_decode_lattice_simple": (C.c_int, [vp, vp, vp, C.POINTER(LatticeSimpleConfigC), c_i32p, c_i32p, c_i64p, C.c_int64, c_f64p,
                                             c_i32p, c_i32p]),
+    "khg_decode_lattice_simple_raw": (C.c_int, [vp, vp, vp, C.POINTER(LatticeSimpleConfigC), c_i32p, c_i32p, c_i64p, C.c_int64, c_f64p,
+                                                c_i32p, c_i32p, C.POINTER(vp)]),
+    "khg_lattices_sizes": (C.c_int, [vp, c_i64p, c_i64p]),
+    "khg_lattices_download": (C.c_int, [vp, vp, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p,
+                                        c_i32p]),
+    "khg_lattices_device_bytes": (C.c_int, [vp, c_i64p]),
+    "khg_lattices_destroy": (C.c_int, [vp]),
     "khg_ali_download": (C.c_int, [vp, vp, c_i32p]),
     "khg_accs_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     "khg_accs_destroy": (C.c_int, [vp]),

@@ -1,8 +1,11 @@
 // Implementation of khg_host_align.hpp: see the header for what each piece mirrors in the reference.
 #include "khg_host_align.hpp"
 
+#include <chrono>
 #include <cstdio>
 #include <sstream>
+
+#include "khg_host_fst.hpp"
 
 namespace khg {
 
@@ -278,7 +281,7 @@ std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const Transit
 
 std::vector<LatticeResult> DecodeLatticeSimpleOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
                                                     const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool allow_partial,
-                                                    int scratch_per_frame, int64_t total_states) {
+                                                    int scratch_per_frame, int64_t total_states, khg_lattices** lattices) {
   const int n_utt = (int)frame_off.size() - 1;
   khg_lattice_simple_config c;
   khg_lattice_simple_config_default(&c);
@@ -290,7 +293,11 @@ std::vector<LatticeResult> DecodeLatticeSimpleOnSet(khg_ctx* ctx, khg_tm* tm, kh
   std::vector<double> like((size_t)n_utt);
   // words: the C-ABI keeps at most frames + states + 64 per utterance
   std::vector<int32_t> words((size_t)(N + total_states + 64 * (int64_t)n_utt + 16));
-  CApi(khg_decode_lattice_simple(ctx, tm, us, &c, ali.data(), words.data(), woff.data(), (int64_t)words.size(), like.data(), status.data(), ef.data()));
+  if (lattices)
+    CApi(khg_decode_lattice_simple_raw(ctx, tm, us, &c, ali.data(), words.data(), woff.data(), (int64_t)words.size(), like.data(), status.data(),
+                                       ef.data(), lattices));
+  else
+    CApi(khg_decode_lattice_simple(ctx, tm, us, &c, ali.data(), words.data(), woff.data(), (int64_t)words.size(), like.data(), status.data(), ef.data()));
   std::vector<LatticeResult> out((size_t)n_utt);
   for (int u = 0; u < n_utt; ++u) {
     LatticeResult& r = out[(size_t)u];
@@ -317,6 +324,52 @@ std::vector<LatticeResult> DecodeLatticeSimpleBatch(const AmDiagGmm& am, const T
                       [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
                         return DecodeLatticeSimpleOnSet(ctx, dt, us, frame_off, config, acoustic_scale, allow_partial, scratch_per_frame,
                                                         BatchStates(g, (int)feats.size()));
+                      });
+}
+
+std::vector<LatticeResult> GetRawLatticeSimpleBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g,
+                                                    const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                    const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool return_scores,
+                                                    int scratch_per_frame, std::vector<std::shared_ptr<Lattice>>* lattices, double* seconds) {
+  config.Check();
+  KHG_REQUIRE(lattices != nullptr, "get_raw_lattice_simple_batch: no place for the lattices");
+  for (int64_t T : nframes) KHG_REQUIRE(T > 0, "get_raw_lattice_simple_batch: an utterance without frames");
+  const int n_utt = (int)feats.size();
+  lattices->assign((size_t)n_utt, nullptr);
+  struct LatH { khg_lattices* h = nullptr; ~LatH() { if (h) khg_lattices_destroy(h); } } lh;
+  using Clock = std::chrono::steady_clock;
+  return K1ThenDecode(am, tm, g, feats, nframes, return_scores, "get_raw_lattice_simple_batch",
+                      [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
+                        const Clock::time_point t0 = Clock::now();
+                        std::vector<LatticeResult> out = DecodeLatticeSimpleOnSet(ctx, dt, us, frame_off, config, acoustic_scale, true, scratch_per_frame,
+                                                                                  BatchStates(g, n_utt), &lh.h);
+                        const Clock::time_point t1 = Clock::now();
+                        std::vector<int64_t> so((size_t)n_utt + 1, 0), ao((size_t)n_utt + 1, 0);
+                        CApi(khg_lattices_sizes(lh.h, so.data(), ao.data()));
+                        const size_t NS = (size_t)so[(size_t)n_utt], NA = (size_t)ao[(size_t)n_utt];
+                        std::vector<int32_t> frame(NS + 1), gstate(NS + 1), abeg(NS + 1), il(NA + 1), ol(NA + 1), ns(NA + 1), start((size_t)n_utt + 1);
+                        std::vector<float> tot(NS + 1), extra(NS + 1), fin(NS + 1), gc(NA + 1), ac(NA + 1);
+                        CApi(khg_lattices_download(ctx, lh.h, frame.data(), gstate.data(), tot.data(), extra.data(), fin.data(), abeg.data(), il.data(),
+                                                   ol.data(), gc.data(), ac.data(), ns.data(), start.data()));
+                        if (seconds) {
+                          seconds[0] = std::chrono::duration<double>(t1 - t0).count();
+                          seconds[1] = std::chrono::duration<double>(Clock::now() - t1).count();
+                        }
+                        for (int u = 0; u < n_utt; ++u) {
+                          auto l = std::make_shared<Lattice>();
+                          const size_t s0 = (size_t)so[(size_t)u], s1 = (size_t)so[(size_t)u + 1], a0 = (size_t)ao[(size_t)u], a1 = (size_t)ao[(size_t)u + 1];
+                          l->frame.assign(frame.begin() + s0, frame.begin() + s1); l->graph_state.assign(gstate.begin() + s0, gstate.begin() + s1);
+                          l->tot_cost.assign(tot.begin() + s0, tot.begin() + s1); l->extra_cost.assign(extra.begin() + s0, extra.begin() + s1);
+                          l->final_cost.assign(fin.begin() + s0, fin.begin() + s1);
+                          l->arc_begin.assign(abeg.begin() + s0, abeg.begin() + s1);
+                          l->arc_begin.push_back((int32_t)(a1 - a0));
+                          l->ilabel.assign(il.begin() + a0, il.begin() + a1); l->olabel.assign(ol.begin() + a0, ol.begin() + a1);
+                          l->nextstate.assign(ns.begin() + a0, ns.begin() + a1);
+                          l->graph_cost.assign(gc.begin() + a0, gc.begin() + a1); l->acoustic_cost.assign(ac.begin() + a0, ac.begin() + a1);
+                          l->start = s1 > s0 ? start[(size_t)u] : kNoStateId;
+                          (*lattices)[(size_t)u] = std::move(l);
+                        }
+                        return out;
                       });
 }
 

@@ -191,6 +191,7 @@ std::vector<LatticeResult> DecodeLatticeSimpleBatch(const AmDiagGmm& am, const T
                                                     bool return_scores, int scratch_per_frame = 0);
 std::vector<LatticeResult> DecodeLatticeSimpleOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
                                                     const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool allow_partial,
-                                                    int scratch_per_frame, int64_t total_states);
+                                                    int scratch_per_frame, int64_t total_states, khg_lattices** lattices = nullptr);
+// (lattices: khg_decode_lattice_simple_raw instead, the batch's raw lattices left on the device for the caller to download and destroy)
 
 }  // namespace khg

@@ -1,6 +1,7 @@
 // Implementation of khg_host_fst.hpp: see the header for what each piece mirrors in the reference.
 #include "khg_host_fst.hpp"
 
+#include <algorithm>
 #include <cstdio>
 
 namespace khg {
@@ -70,6 +71,128 @@ bool LinearLattice::GetLinearSymbolSequence(std::vector<int>* il, std::vector<in
   }
   *total = w;
   return true;
+}
+
+std::vector<LatticeArc> Lattice::Arcs(int s) const {
+  Check(s);
+  std::vector<LatticeArc> out;
+  for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a)
+    out.push_back(LatticeArc{ilabel[(size_t)a], olabel[(size_t)a], LatticeWeight{(double)graph_cost[(size_t)a], (double)acoustic_cost[(size_t)a]},
+                             nextstate[(size_t)a]});
+  return out;
+}
+
+LatticeWeight Lattice::Final(int s) const {
+  Check(s);
+  const double inf = std::numeric_limits<double>::infinity();
+  if (final_cost[(size_t)s] == std::numeric_limits<float>::infinity()) return LatticeWeight{inf, inf};
+  return LatticeWeight{(double)final_cost[(size_t)s], 0.0};
+}
+
+std::string Lattice::ToText() const {
+  std::string out;
+  char b[160];
+  for (int s = 0; s < NumStates(); ++s)
+    for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) {
+      std::snprintf(b, sizeof(b), "%d %d %d %d %.9g,%.9g\n", s, nextstate[(size_t)a], ilabel[(size_t)a], olabel[(size_t)a],
+                    (double)graph_cost[(size_t)a], (double)acoustic_cost[(size_t)a]);
+      out += b;
+    }
+  for (int s = 0; s < NumStates(); ++s)
+    if (final_cost[(size_t)s] != std::numeric_limits<float>::infinity()) {
+      std::snprintf(b, sizeof(b), "%d %.9g,%.9g\n", s, (double)final_cost[(size_t)s], 0.0);
+      out += b;
+    }
+  return out;
+}
+
+LinearLattice Lattice::ShortestPath() const {
+  LinearLattice out;
+  const int N = NumStates();
+  if (N == 0 || start < 0) return out;
+  const float INF = std::numeric_limits<float>::infinity();
+  auto less = [](float a1, float a2, float b1, float b2) {       // NaturalLess: (a1, a2) strictly better
+    const float fa = a1 + a2, fb = b1 + b2;
+    if (fa < fb) return true;
+    if (fa > fb) return false;
+    return a1 < b1;
+  };
+  // in-links of every state, stable by (source state, arc): the in-arc order of the decoder kernel
+  const int64_t A = NumArcs();
+  std::vector<int64_t> in_off((size_t)N + 1, 0);
+  for (int64_t a = 0; a < A; ++a) in_off[(size_t)nextstate[(size_t)a] + 1]++;
+  for (int s = 0; s < N; ++s) in_off[(size_t)s + 1] += in_off[(size_t)s];
+  std::vector<int32_t> in_arc((size_t)A), in_src((size_t)A);
+  {
+    std::vector<int64_t> cur(in_off.begin(), in_off.end() - 1);
+    for (int s = 0; s < N; ++s)
+      for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) {
+        const int64_t pos = cur[(size_t)nextstate[(size_t)a]]++;
+        in_arc[(size_t)pos] = a; in_src[(size_t)pos] = s;
+      }
+  }
+  std::vector<float> d1((size_t)N, INF), d2((size_t)N, INF), n1((size_t)N), n2((size_t)N);
+  std::vector<int32_t> bp((size_t)N, -1);
+  d1[(size_t)start] = 0.0f; d2[(size_t)start] = 0.0f;
+  const int T = frame[(size_t)N - 1];
+  int lo = 0;
+  for (int f = 0; f <= T; ++f) {
+    int hi = lo;
+    while (hi < N && frame[(size_t)hi] == f) ++hi;
+    if (f > 0)
+      for (int n = lo; n < hi; ++n) {          // emitting in-links, from the frame before
+        float b1 = INF, b2 = INF;
+        for (int64_t i = in_off[(size_t)n]; i < in_off[(size_t)n + 1]; ++i) {
+          const int a = in_arc[(size_t)i], m = in_src[(size_t)i];
+          if (ilabel[(size_t)a] == 0 || d1[(size_t)m] == INF) continue;
+          const float c1 = d1[(size_t)m] + graph_cost[(size_t)a], c2 = d2[(size_t)m] + acoustic_cost[(size_t)a];
+          if (b1 == INF || less(c1, c2, b1, b2)) { b1 = c1; b2 = c2; bp[(size_t)n] = a; }
+        }
+        d1[(size_t)n] = b1; d2[(size_t)n] = b2;
+      }
+    for (int round = 0;; ++round) {            // epsilon in-links: Jacobi rounds
+      bool changed = false;
+      for (int n = lo; n < hi; ++n) {
+        float b1 = d1[(size_t)n], b2 = d2[(size_t)n];
+        for (int64_t i = in_off[(size_t)n]; i < in_off[(size_t)n + 1]; ++i) {
+          const int a = in_arc[(size_t)i], m = in_src[(size_t)i];
+          if (ilabel[(size_t)a] != 0 || d1[(size_t)m] == INF) continue;
+          const float c1 = d1[(size_t)m] + graph_cost[(size_t)a], c2 = d2[(size_t)m] + 0.0f;
+          if (b1 == INF || less(c1, c2, b1, b2)) { b1 = c1; b2 = c2; bp[(size_t)n] = a; changed = true; }
+        }
+        n1[(size_t)n] = b1; n2[(size_t)n] = b2;
+      }
+      for (int n = lo; n < hi; ++n) { d1[(size_t)n] = n1[(size_t)n]; d2[(size_t)n] = n2[(size_t)n]; }
+      if (!changed) break;
+      KHG_REQUIRE(round <= hi - lo, "Lattice::ShortestPath: a negative-cost epsilon cycle");
+    }
+    lo = hi;
+  }
+  int fin = -1;
+  float f1 = INF, f2 = INF;
+  for (int n = 0; n < N; ++n) {
+    if (frame[(size_t)n] != T || d1[(size_t)n] == INF || final_cost[(size_t)n] == INF) continue;
+    const float w1 = d1[(size_t)n] + final_cost[(size_t)n], w2 = d2[(size_t)n] + 0.0f;
+    if (fin < 0 || less(w1, w2, f1, f2)) { f1 = w1; f2 = w2; fin = n; }
+  }
+  if (fin < 0) return out;
+  std::vector<int32_t> path;
+  for (int n = fin; n != start || bp[(size_t)n] >= 0;) {
+    const int a = bp[(size_t)n];
+    if (a < 0 || (int64_t)path.size() > A) return out;
+    path.push_back(a);
+    // the source of arc a: the state whose arc range holds it
+    n = (int)(std::upper_bound(arc_begin.begin(), arc_begin.end(), a) - arc_begin.begin()) - 1;
+    if (n == start && frame[(size_t)n] == 0 && bp[(size_t)n] < 0) break;
+  }
+  out.start = 0;
+  for (size_t i = path.size(); i-- > 0;) {
+    const int a = path[i];
+    out.arcs.push_back(LatticeArc{ilabel[(size_t)a], olabel[(size_t)a], LatticeWeight{(double)graph_cost[(size_t)a], (double)acoustic_cost[(size_t)a]},
+                                  (int)(path.size() - i)});
+  }
+  out.final_w = LatticeWeight{(double)final_cost[(size_t)fin], 0.0};
+  return out;
 }
 
 void FasterDecoder::SetOptions(const FasterDecoderOptions& c) {

@@ -99,6 +99,48 @@ struct LinearLattice {
   bool GetLinearSymbolSequence(std::vector<int>* ilabels, std::vector<int>* olabels, LatticeWeight* total) const;
 };
 
+// The fst::VectorFst<LatticeArc> LatticeSimpleDecoder::GetRawLattice builds (csrc/lattice-simple-decoder.cc:654-735), as the flat arrays
+// khg_lattices_download hands back: a state per surviving token, numbered by frame, then by graph state (:684-690); state s owns arcs
+// arc_begin[s] .. arc_begin[s + 1], one per surviving forward link in the order of the graph's arcs in its state (:700-722); the last
+// frame's final tokens are final with (final_cost, 0) (:723-733).  Which lattice that is (the order-independent one): DESIGN.md 7d.
+class Lattice {
+ public:
+  // per state
+  std::vector<int32_t> frame, graph_state;
+  std::vector<float> tot_cost, extra_cost, final_cost;     // final_cost: +inf unless the state is final
+  std::vector<int32_t> arc_begin;                          // [NumStates() + 1]
+  // per arc
+  std::vector<int32_t> ilabel, olabel, nextstate;
+  std::vector<float> graph_cost, acoustic_cost;
+  int start = kNoStateId;
+
+  int NumStates() const { return (int)frame.size(); }
+  int Start() const { return start; }
+  int64_t NumArcs() const { return (int64_t)ilabel.size(); }
+  int NumArcs(int s) const { Check(s); return arc_begin[(size_t)s + 1] - arc_begin[(size_t)s]; }
+  std::vector<LatticeArc> Arcs(int s) const;
+  LatticeWeight Final(int s) const;      // LatticeWeight::Zero() = (+inf, +inf) for a state that is not final
+  // OpenFst ShortestPath over the lattice by the tie rule of the decoder kernel: frame by frame, emitting in-links
+  // first, then epsilon in-links in Jacobi rounds; a state takes its in-links ordered by (source state, arc) and changes only on a
+  // strictly better LatticeWeight; the final state is the lowest among exact ties.  Distances are float sums, left to right, as in
+  // the kernel.  Every arc of the path is kept (epsilons too).  An empty lattice, or none of its final states reached: start == -1.
+  LinearLattice ShortestPath() const;
+  // Kaldi's text form of a lattice: "src dst ilabel olabel graph,acoustic" per arc, "state graph,acoustic" per final state
+  std::string ToText() const;
+
+ private:
+  void Check(int s) const { KHG_REQUIRE(s >= 0 && s < NumStates(), "Lattice: bad state"); }
+};
+
+// GetRawLattice for a batch (the data-parallel lattice-simple decoder, khg_decode_lattice_simple_raw): what DecodeLatticeSimpleBatch
+// returns, and in (*lattices)[u] the raw lattice of utterance u (no states unless it succeeded).  seconds (optional, 2 entries): the
+// time of the C-ABI decode call and of the download of the lattices.
+std::vector<LatticeResult> GetRawLatticeSimpleBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& graphs,
+                                                    const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                    const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool return_scores,
+                                                    int scratch_per_frame, std::vector<std::shared_ptr<Lattice>>* lattices,
+                                                    double* seconds = nullptr);
+
 // python/csrc/faster-decoder.cc:33-53 on the GPU path: Decode runs K1 + K2 for the utterance of a DecodableAmDiagGmmScaled (any other
 // DecodableInterface: its sampled scores + K2, AlignDecodable above) with the options' beam / max_active / min_active / beam_delta /
 // hash_ratio (no retry); GetBestPath rebuilds the linear lattice of

@@ -1,12 +1,15 @@
 // kaldi_hmm_gmm_amd/csrc/khg_k2.hip -- C-ABI (include/khg_hip.h): K2, Viterbi forced alignment (khg_align): kernel selection by graph
 // shape, LDS budgets, the exact DP on the main stream and the order-faithful decoder on a side stream; and the lattice decoder
 // (khg_decode_lattice_faster, khg_k2_lattice.hip.inc) and the data-parallel LatticeSimpleDecoder (khg_decode_lattice_simple,
-// khg_k2_lattice_simple.hip.inc).  gfx950 only.
+// khg_k2_lattice_simple.hip.inc) with its raw lattice (khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
+
+#include <memory>
 
 #include "khg_k2_viterbi.hip.inc"
 #include "khg_k2_lattice.hip.inc"
 #include "khg_k2_lattice_simple.hip.inc"
+#include "khg_k2_lattice_raw.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // K2
@@ -513,9 +516,64 @@ extern "C" void khg_lattice_simple_config_default(khg_lattice_simple_config* c) 
   c->allow_partial = 1; c->scratch_per_frame = 0;
 }
 
-extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_simple_config* cfg,
-                                         int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
-                                         double* like_h, int32_t* status_h, int32_t* err_frame_h) {
+// The raw lattices of one batch (khg_decode_lattice_simple_raw): per chunk of scratch slices one exactly-sized device block holding
+// the six per-state and five per-arc arrays of the chunk's utterances, one after the other.
+struct LatChunk {
+  int u0 = 0, n = 0;              // utterances u0 .. u0 + n
+  int64_t ns = 0, na = 0;         // states, arcs
+  unsigned char* buf = nullptr;
+  // byte offsets of the arrays inside buf: frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin | ilabel, olabel, graph_cost,
+  // acoustic_cost, nextstate
+  int64_t st[6] = {0, 0, 0, 0, 0, 0}, ar[5] = {0, 0, 0, 0, 0};
+};
+struct khg_lattices {
+  int U = 0;
+  std::vector<int64_t> state_off, arc_off;       // [U + 1]
+  std::vector<LatChunk> chunks;
+  int32_t* start_d = nullptr;                    // [U]
+  int64_t bytes = 0;
+};
+
+extern "C" int khg_lattices_destroy(khg_lattices* l) {
+  if (!l) return KHG_OK;
+  for (LatChunk& c : l->chunks) if (c.buf) (void)hipFree(c.buf);
+  if (l->start_d) (void)hipFree(l->start_d);
+  delete l;
+  return KHG_OK;
+}
+extern "C" int khg_lattices_sizes(const khg_lattices* l, int64_t* state_off_h, int64_t* arc_off_h) {
+  if (!l) return khg_set_error(KHG_E_ARG, "khg_lattices_sizes: bad arguments");
+  if (state_off_h) std::copy(l->state_off.begin(), l->state_off.end(), state_off_h);
+  if (arc_off_h) std::copy(l->arc_off.begin(), l->arc_off.end(), arc_off_h);
+  return KHG_OK;
+}
+extern "C" int khg_lattices_device_bytes(const khg_lattices* l, int64_t* bytes) {
+  if (!l || !bytes) return khg_set_error(KHG_E_ARG, "khg_lattices_device_bytes: bad arguments");
+  *bytes = l->bytes;
+  return KHG_OK;
+}
+extern "C" int khg_lattices_download(khg_ctx* ctx, const khg_lattices* l, int32_t* frame_h, int32_t* graph_state_h, float* tot_cost_h,
+                                     float* extra_cost_h, float* final_cost_h, int32_t* arc_begin_h, int32_t* ilabel_h, int32_t* olabel_h,
+                                     float* graph_cost_h, float* acoustic_cost_h, int32_t* nextstate_h, int32_t* start_h) {
+  if (ctx_dead(ctx) || !l) return khg_set_error(KHG_E_ARG, "khg_lattices_download: bad arguments");
+  void* st_h[6] = {frame_h, graph_state_h, tot_cost_h, extra_cost_h, final_cost_h, arc_begin_h};
+  void* ar_h[5] = {ilabel_h, olabel_h, graph_cost_h, acoustic_cost_h, nextstate_h};
+  for (const LatChunk& c : l->chunks) {
+    const int64_t s0 = l->state_off[(size_t)c.u0], a0 = l->arc_off[(size_t)c.u0];
+    for (int k = 0; k < 6; ++k)
+      if (st_h[k] && c.ns) HIPCHK(hipMemcpyAsync(static_cast<char*>(st_h[k]) + 4 * s0, c.buf + c.st[k], 4 * (size_t)c.ns, hipMemcpyDeviceToHost, ctx->stream));
+    for (int k = 0; k < 5; ++k)
+      if (ar_h[k] && c.na) HIPCHK(hipMemcpyAsync(static_cast<char*>(ar_h[k]) + 4 * a0, c.buf + c.ar[k], 4 * (size_t)c.na, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (start_h && l->U) HIPCHK(hipMemcpyAsync(start_h, l->start_d, 4 * (size_t)l->U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
+
+// khg_decode_lattice_simple (lat_out == nullptr: nothing below about lattices runs) and khg_decode_lattice_simple_raw
+static int decode_lattice_simple_impl(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_simple_config* cfg,
+                                      int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                      double* like_h, int32_t* status_h, int32_t* err_frame_h, khg_lattices** lat_out) {
   if (ctx_dead(ctx) || !tm || !u || !cfg) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple: bad arguments");
   { int rf = utts_foreign_ctx(ctx, u, "khg_decode_lattice_simple"); if (rf) return rf; }
   if (!u->has_graphs) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple: the utterance set has no decoding graphs");
@@ -530,7 +588,16 @@ extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utt
   if (!rc) rc = k1_band_check(ctx, u);
   if (rc) return rc;
   const int U = u->n_utt;
-  if (U == 0) return KHG_OK;
+  const bool lat = lat_out != nullptr;
+  struct LatFree { void operator()(khg_lattices* l) const { (void)khg_lattices_destroy(l); } };
+  std::unique_ptr<khg_lattices, LatFree> lats;
+  if (lat) {
+    lats.reset(new khg_lattices);
+    lats->U = U;
+    lats->state_off.assign((size_t)U + 1, 0);
+    lats->arc_off.assign((size_t)U + 1, 0);
+  }
+  if (U == 0) { if (lat) *lat_out = lats.release(); return KHG_OK; }
   std::vector<int64_t> wcap_off((size_t)U + 1, 0);
   for (int i = 0; i < U; ++i) wcap_off[(size_t)i + 1] = wcap_off[(size_t)i] + (u->frame_off[i + 1] - u->frame_off[i]) + utt_states(u, i) + 64;
   const int64_t N = u->N, NW = wcap_off[(size_t)U];
@@ -545,6 +612,13 @@ extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utt
     *out = q;
     return KHG_OK;
   };
+  int64_t *lat_tot_d = nullptr, *lat_off_d = nullptr;
+  if (lat) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&lats->start_d), 4 * (size_t)U));
+    lats->bytes += 4 * (int64_t)U;
+    if ((rc = dalloc(16 * (size_t)U, reinterpret_cast<void**>(&lat_tot_d))) || (rc = dalloc(16 * ((size_t)U + 1), reinterpret_cast<void**>(&lat_off_d))))
+      return rc;
+  }
   int32_t *ali_d, *words_d, *nw_d, *status_d, *ef_d; double* like_d; int64_t* woff_d;
   if ((rc = dalloc(4 * (size_t)std::max<int64_t>(N, 1), reinterpret_cast<void**>(&ali_d))) ||
       (rc = dalloc(4 * (size_t)std::max<int64_t>(NW, 1), reinterpret_cast<void**>(&words_d))) ||
@@ -570,7 +644,7 @@ extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utt
   std::vector<int64_t> bytes((size_t)U);
   for (int i = 0; i < U; ++i) {
     const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = utt_states(u, i);
-    bytes[(size_t)i] = ls_layout(T, S, u->max_inarcs).total;     // (the kernel lays every slice out with the same arc bound)
+    bytes[(size_t)i] = ls_layout(T, S, u->max_inarcs, lat).total;     // (the kernel lays every slice out with the same arc bound)
   }
   const int64_t budget = int64_t(4) << 30;
   std::vector<size_t> cb{0};
@@ -596,10 +670,65 @@ extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utt
   a.scratch = scratch; a.scr_off = scr_off_d; a.list = list_d;
   // one wave for small graphs, up to four for larger ones (a lane owns states s = lane, lane + NT, ...)
   const int nt = u->max_states <= 64 ? 64 : u->max_states <= 128 ? 128 : LS_NT;
+  int64_t max_T = 0;
+  for (int i = 0; i < U; ++i) max_T = std::max<int64_t>(max_T, u->frame_off[i + 1] - u->frame_off[i]);
+  std::vector<int64_t> lat_off_h;
   for (size_t c = 0; c + 1 < cb.size(); ++c) {
-    KernelTimer kt(ctx, "k2_lattice_simple");
-    KHG_LAUNCH(ctx, k2_lattice_simple, dim3((unsigned)(cb[c + 1] - cb[c])), dim3(nt), 0, ctx->stream, a, (int)cb[c]);
-    HIPCHK(hipGetLastError());
+    {
+      KernelTimer kt(ctx, "k2_lattice_simple");
+      KHG_LAUNCH(ctx, k2_lattice_simple, dim3((unsigned)(cb[c + 1] - cb[c])), dim3(nt), 0, ctx->stream, a, (int)cb[c]);
+      HIPCHK(hipGetLastError());
+    }
+    if (lat) {
+      // the chunk's lattices, while its slices are alive: count, the two scans, ONE synchronisation to size the output, the fill
+      const int n = (int)(cb[c + 1] - cb[c]), u0 = (int)cb[c];
+      LrArgs p;
+      std::memset(&p, 0, sizeof(p));
+      p.a = a; p.n = n; p.utt_tot = lat_tot_d; p.utt_off = lat_off_d; p.start_out = lats->start_d;
+      // frames are independent: stripes of them go to workgroups of their own while the chunk has few utterances
+      const unsigned gy = (unsigned)std::min<int64_t>(max_T + 1, std::max<int64_t>(1, 1024 / n));
+      {
+        KernelTimer kt(ctx, "k2_lattice_raw_count");
+        KHG_LAUNCH(ctx, k2_lattice_raw_count, dim3((unsigned)n, gy), dim3(nt), 0, ctx->stream, p, u0);
+        HIPCHK(hipGetLastError());
+      }
+      {
+        KernelTimer kt(ctx, "k2_lattice_raw_scan");
+        KHG_LAUNCH(ctx, k2_lattice_raw_scan_frames, dim3((unsigned)n), dim3(64), 0, ctx->stream, p, u0);
+        KHG_LAUNCH(ctx, k2_lattice_raw_scan_utts, dim3(1), dim3(64), 0, ctx->stream, p);
+        HIPCHK(hipGetLastError());
+      }
+      lat_off_h.assign(2 * ((size_t)n + 1), 0);
+      HIPCHK(hipMemcpyAsync(lat_off_h.data(), lat_off_d, 16 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      LatChunk ch;
+      ch.u0 = u0; ch.n = n; ch.ns = lat_off_h[(size_t)n]; ch.na = lat_off_h[2 * (size_t)n + 1];
+      for (int b = 0; b < n; ++b) {
+        const int64_t ns = lat_off_h[(size_t)b + 1] - lat_off_h[(size_t)b], na = lat_off_h[(size_t)n + 2 + b] - lat_off_h[(size_t)n + 1 + b];
+        if (ns > INT32_MAX || na > INT32_MAX)
+          return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple_raw: the lattice of utterance " + std::to_string(u0 + b) + " has more than 2^31 - 1 states or arcs");
+        lats->state_off[(size_t)u0 + b + 1] = lats->state_off[(size_t)u0 + b] + ns;
+        lats->arc_off[(size_t)u0 + b + 1] = lats->arc_off[(size_t)u0 + b] + na;
+      }
+      int64_t o = 0;
+      auto take = [&](int64_t cnt) { const int64_t r = o; o += (4 * cnt + 255) & ~int64_t(255); return r; };
+      for (int k = 0; k < 6; ++k) ch.st[k] = take(ch.ns);
+      for (int k = 0; k < 5; ++k) ch.ar[k] = take(ch.na);
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&ch.buf), (size_t)std::max<int64_t>(o, 16)));
+      lats->chunks.push_back(ch);
+      lats->bytes += o;
+      p.st_frame = reinterpret_cast<int32_t*>(ch.buf + ch.st[0]); p.st_gstate = reinterpret_cast<int32_t*>(ch.buf + ch.st[1]);
+      p.st_tot = reinterpret_cast<float*>(ch.buf + ch.st[2]); p.st_extra = reinterpret_cast<float*>(ch.buf + ch.st[3]);
+      p.st_final = reinterpret_cast<float*>(ch.buf + ch.st[4]); p.st_arc_begin = reinterpret_cast<int32_t*>(ch.buf + ch.st[5]);
+      p.arc_ilabel = reinterpret_cast<int32_t*>(ch.buf + ch.ar[0]); p.arc_olabel = reinterpret_cast<int32_t*>(ch.buf + ch.ar[1]);
+      p.arc_g = reinterpret_cast<float*>(ch.buf + ch.ar[2]); p.arc_ac = reinterpret_cast<float*>(ch.buf + ch.ar[3]);
+      p.arc_next = reinterpret_cast<int32_t*>(ch.buf + ch.ar[4]);
+      {
+        KernelTimer kt(ctx, "k2_lattice_raw_fill");
+        KHG_LAUNCH(ctx, k2_lattice_raw_fill, dim3((unsigned)n, gy), dim3(nt), 0, ctx->stream, p, u0);
+        HIPCHK(hipGetLastError());
+      }
+    }
     if (c + 2 < cb.size()) HIPCHK(hipStreamSynchronize(ctx->stream));     // the next launch reuses the slices
   }
   rc = check_err_flag(ctx, "khg_decode_lattice_simple");     // synchronises
@@ -626,5 +755,19 @@ extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utt
     }
     words_off_h[U] = o;
   }
+  if (lat) *lat_out = lats.release();
   return KHG_OK;
+}
+
+extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_simple_config* cfg,
+                                         int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                         double* like_h, int32_t* status_h, int32_t* err_frame_h) {
+  return decode_lattice_simple_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, err_frame_h, nullptr);
+}
+extern "C" int khg_decode_lattice_simple_raw(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_simple_config* cfg,
+                                             int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                             double* like_h, int32_t* status_h, int32_t* err_frame_h, khg_lattices** out) {
+  if (!out) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple_raw: out is NULL");
+  *out = nullptr;
+  return decode_lattice_simple_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, err_frame_h, out);
 }

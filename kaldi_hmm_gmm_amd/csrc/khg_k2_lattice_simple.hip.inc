@@ -62,9 +62,11 @@ struct LsArgs {
 };
 
 // the per-utterance slice: dense rows [T+1][S] of D, X, BP (best-path in-arc), R (byte), per-frame cutoffs, the graph tables, and
-// six working rows of the best-path distances (frame f, frame f+1, Jacobi round buffer; Value1 and Value2 each)
-struct LsLayout { int64_t D, X, BP, R, pcut, ecut, dst, nieps, w, hub, total; };
-__host__ __device__ inline LsLayout ls_layout(int64_t T, int64_t S, int64_t A) {
+// six working rows of the best-path distances (frame f, frame f+1, Jacobi round buffer; Value1 and Value2 each).  lat (a raw lattice
+// was asked for, khg_k2_lattice_raw.hip.inc): behind those, two more dense rows -- the rank of (f, s) among its frame's surviving
+// states, the prefix of its surviving out-links -- and the per-frame state / link counts; the rows above stay where they are
+struct LsLayout { int64_t D, X, BP, R, pcut, ecut, dst, nieps, w, hub, rank, aoff, ftok, flink, total; };
+__host__ __device__ inline LsLayout ls_layout(int64_t T, int64_t S, int64_t A, bool lat = false) {
   LsLayout L;
   int64_t o = 0;
   auto take = [&](int64_t bytes) { int64_t r = o; o += (bytes + 255) & ~int64_t(255); return r; };
@@ -79,6 +81,13 @@ __host__ __device__ inline LsLayout ls_layout(int64_t T, int64_t S, int64_t A) {
   L.nieps = take(4 * S);
   L.w = take(4 * 6 * S);
   L.hub = take(4 * 2 * S);      // the hub states by in-degree, then by out-degree
+  L.rank = L.aoff = L.ftok = L.flink = -1;
+  if (lat) {
+    L.rank = take(4 * rows);
+    L.aoff = take(4 * rows);
+    L.ftok = take(4 * (T + 2));
+    L.flink = take(4 * (T + 2));
+  }
   L.total = o;
   return L;
 }

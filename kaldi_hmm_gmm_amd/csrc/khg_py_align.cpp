@@ -243,9 +243,96 @@ py::dict LatticeSimpleToDict(const LatticeResult& r, int64_t T, bool return_scor
   d["error_frame"] = r.err_frame;
   return d;
 }
+// a read-only numpy view of one of a Lattice's arrays; the Lattice stays alive as its base
+template <class T>
+py::array LatView(py::object self, const std::vector<T>& v, size_t n) {
+  py::array_t<T> a({(py::ssize_t)n}, {(py::ssize_t)sizeof(T)}, v.data(), self);
+  py::detail::array_proxy(a.ptr())->flags &= ~py::detail::npy_api::NPY_ARRAY_WRITEABLE_;
+  return std::move(a);
+}
+template <class T>
+std::vector<T> VecOf(py::object o) {
+  Arr<T> a = o.cast<Arr<T>>();
+  return std::vector<T>(a.data(), a.data() + a.size());
+}
 }  // namespace
 
 void BindLattice(py::module_& m) {
+  // fst::VectorFst<LatticeArc> as LatticeSimpleDecoder::GetRawLattice builds it (csrc/lattice-simple-decoder.cc:654-735; the reference's
+  // Python binding does not expose the call): kaldifst's method names, plus the flat arrays as read-only numpy views
+  py::class_<Lattice, std::shared_ptr<Lattice>>(m, "Lattice")
+      .def_static("from_arrays", [](py::object frame, py::object graph_state, py::object tot_cost, py::object extra_cost, py::object final_cost,
+                                    py::object arc_begin, py::object ilabel, py::object olabel, py::object graph_cost, py::object acoustic_cost,
+                                    py::object nextstate, int start) {
+        auto l = std::make_shared<Lattice>();
+        l->frame = VecOf<int32_t>(frame); l->graph_state = VecOf<int32_t>(graph_state); l->tot_cost = VecOf<float>(tot_cost);
+        l->extra_cost = VecOf<float>(extra_cost); l->final_cost = VecOf<float>(final_cost); l->arc_begin = VecOf<int32_t>(arc_begin);
+        l->ilabel = VecOf<int32_t>(ilabel); l->olabel = VecOf<int32_t>(olabel); l->graph_cost = VecOf<float>(graph_cost);
+        l->acoustic_cost = VecOf<float>(acoustic_cost); l->nextstate = VecOf<int32_t>(nextstate); l->start = start;
+        const size_t N = l->frame.size(), A = l->ilabel.size();
+        if (l->graph_state.size() != N || l->tot_cost.size() != N || l->extra_cost.size() != N || l->final_cost.size() != N || l->arc_begin.size() != N + 1 ||
+            l->olabel.size() != A || l->graph_cost.size() != A || l->acoustic_cost.size() != A || l->nextstate.size() != A)
+          throw Error("Lattice.from_arrays: one entry per state (arc_begin: one more) and one per arc");
+        if (l->arc_begin[0] != 0 || (size_t)l->arc_begin[N] != A) throw Error("Lattice.from_arrays: arc_begin must run from 0 to the number of arcs");
+        for (size_t s = 0; s < N; ++s) {
+          if (l->arc_begin[s] > l->arc_begin[s + 1]) throw Error("Lattice.from_arrays: arc_begin not monotone");
+          if (s > 0 && l->frame[s] < l->frame[s - 1]) throw Error("Lattice.from_arrays: states must be ordered by frame");
+        }
+        for (int32_t n : l->nextstate) if (n < 0 || (size_t)n >= N) throw Error("Lattice.from_arrays: nextstate out of range");
+        if (N == 0 ? start != kNoStateId : (start < 0 || (size_t)start >= N)) throw Error("Lattice.from_arrays: start out of range");
+        return l;
+      }, py::arg("frame"), py::arg("graph_state"), py::arg("tot_cost"), py::arg("extra_cost"), py::arg("final_cost"), py::arg("arc_begin"),
+         py::arg("ilabel"), py::arg("olabel"), py::arg("graph_cost"), py::arg("acoustic_cost"), py::arg("nextstate"), py::arg("start"))
+      .def_property_readonly("num_states", &Lattice::NumStates)
+      .def_property_readonly("start", &Lattice::Start)
+      .def_property_readonly("num_arcs_total", [](const Lattice& l) { return l.NumArcs(); })
+      .def("num_arcs", [](const Lattice& l, int s) { return l.NumArcs(s); }, py::arg("state"))
+      .def("arcs", &Lattice::Arcs, py::arg("state"))
+      .def("final", &Lattice::Final, py::arg("state"))
+      .def("shortest_path", &Lattice::ShortestPath)
+      .def("to_text", &Lattice::ToText)
+      .def("__str__", &Lattice::ToText)
+      .def_property_readonly("frame", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.frame, l.frame.size()); })
+      .def_property_readonly("graph_state", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.graph_state, l.graph_state.size()); })
+      .def_property_readonly("tot_cost", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.tot_cost, l.tot_cost.size()); })
+      .def_property_readonly("extra_cost", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.extra_cost, l.extra_cost.size()); })
+      .def_property_readonly("final_cost", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.final_cost, l.final_cost.size()); })
+      .def_property_readonly("arc_begin", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.arc_begin, l.arc_begin.size()); })
+      .def_property_readonly("ilabel", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.ilabel, l.ilabel.size()); })
+      .def_property_readonly("olabel", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.olabel, l.olabel.size()); })
+      .def_property_readonly("graph_cost", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.graph_cost, l.graph_cost.size()); })
+      .def_property_readonly("acoustic_cost", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.acoustic_cost, l.acoustic_cost.size()); })
+      .def_property_readonly("nextstate", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.nextstate, l.nextstate.size()); });
+
+  // get_raw_lattice_simple_batch(am, tm, fsts, feats_list, config, acoustic_scale, scratch_per_frame=0, return_scores=False,
+  // return_times=False) -> one dict per utterance: decode_lattice_simple_batch's keys plus "lattice" (a Lattice; no states unless
+  // the utterance succeeded).  fsts as there: a list of graphs, one StdVectorFst or a DecodingGraph (shared, nothing repeated).
+  // return_times: (dicts, {"decode_s", "download_s"}) -- the C-ABI decode call and the download of the lattices.
+  m.def("get_raw_lattice_simple_batch", [](std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, py::object fsts, py::list feats_list,
+                                           const LatticeSimpleDecoderConfig& config, float acoustic_scale, int scratch_per_frame, bool return_scores,
+                                           bool return_times) -> py::object {
+    BatchArgs b(*am, fsts, feats_list, "get_raw_lattice_simple_batch");
+    std::vector<LatticeResult> rs;
+    std::vector<std::shared_ptr<Lattice>> lats;
+    double sec[2] = {0.0, 0.0};
+    {
+      const GraphsCsr csr = b.Csr();
+      py::gil_scoped_release nogil;
+      rs = GetRawLatticeSimpleBatch(*am, *tm, csr, b.fp, b.nf, config, acoustic_scale, return_scores, scratch_per_frame, &lats, sec);
+    }
+    py::list out;
+    for (size_t u = 0; u < rs.size(); ++u) {
+      py::dict d = LatticeSimpleToDict(rs[u], b.nf[u], return_scores);
+      d["lattice"] = lats[u];
+      out.append(d);
+    }
+    if (!return_times) return std::move(out);
+    py::dict t;
+    t["decode_s"] = sec[0]; t["download_s"] = sec[1];
+    return py::make_tuple(out, t);
+  }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"),
+     py::arg("scratch_per_frame") = 0, py::arg("return_scores") = false, py::arg("return_times") = false);
+
   // python/csrc/determinize-lattice-pruned.cc:13-25
   py::class_<DeterminizeLatticePhonePrunedOptions>(m, "DeterminizeLatticePhonePrunedOptions")
       .def(py::init([](float delta, int32_t max_mem, bool pd, bool wd, bool mn) {

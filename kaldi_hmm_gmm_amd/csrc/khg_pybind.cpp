@@ -9,6 +9,8 @@
 // kaldi_hmm_gmm_amd/*.py re-export them.
 // Errors: a non-zero C-ABI status becomes a Python RuntimeError subclass (KhgError), as KHG_ERR does in the reference
 // (csrc/log.h:46-53 -> std::runtime_error -> RuntimeError).
+#include <chrono>
+
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -528,6 +530,48 @@ struct KUtts {
     d["words_off"] = woff;
     return d;
   }
+  // khg_decode_lattice_simple_raw on the resident scores: decode_lattice_simple's outputs plus the batch's raw lattices as flat arrays
+  // (state_off / arc_off [n_utt + 1]; per state frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin; per arc ilabel, olabel,
+  // graph_cost, acoustic_cost, nextstate; per utterance start), the bytes they took on the device and the seconds of the decode call
+  // and of the download
+  py::dict raw_lattice_simple(KTransitions& tm, float beam, float lattice_beam, int32_t prune_interval, float prune_scale, float acoustic_scale,
+                              int32_t scratch_per_frame) {
+    khg_lattice_simple_config c;
+    khg_lattice_simple_config_default(&c);
+    c.beam = beam; c.lattice_beam = lattice_beam; c.prune_interval = prune_interval; c.prune_scale = prune_scale; c.acoustic_scale = acoustic_scale;
+    c.scratch_per_frame = scratch_per_frame;
+    const int64_t N = frame_off.at(n_utt), wcap = 2 * N + 1024 * (int64_t)n_utt + 1024 + state_total;
+    Arr<int32_t> ali({(py::ssize_t)(N > 0 ? N : 1)}), words({(py::ssize_t)wcap}), status({(py::ssize_t)n_utt}), ef({(py::ssize_t)n_utt});
+    Arr<int64_t> woff({(py::ssize_t)n_utt + 1}), so({(py::ssize_t)n_utt + 1}), ao({(py::ssize_t)n_utt + 1});
+    Arr<double> like({(py::ssize_t)n_utt});
+    struct LatH { khg_lattices* h = nullptr; ~LatH() { if (h) khg_lattices_destroy(h); } } lh;
+    const auto t0 = std::chrono::steady_clock::now();
+    Check(NoGil([&] { return khg_decode_lattice_simple_raw(ctx->h, tm.h, h, &c, ali.mutable_data(), words.mutable_data(), woff.mutable_data(), wcap,
+                                                           like.mutable_data(), status.mutable_data(), ef.mutable_data(), &lh.h); }));
+    const auto t1 = std::chrono::steady_clock::now();
+    Check(khg_lattices_sizes(lh.h, so.mutable_data(), ao.mutable_data()));
+    const py::ssize_t NS = (py::ssize_t)so.at(n_utt), NA = (py::ssize_t)ao.at(n_utt);
+    Arr<int32_t> frame({NS}), gstate({NS}), abeg({NS}), il({NA}), ol({NA}), ns({NA}), start({(py::ssize_t)n_utt});
+    Arr<float> tot({NS}), extra({NS}), fin({NS}), gc({NA}), ac({NA});
+    Check(NoGil([&] { return khg_lattices_download(ctx->h, lh.h, frame.mutable_data(), gstate.mutable_data(), tot.mutable_data(), extra.mutable_data(),
+                                                   fin.mutable_data(), abeg.mutable_data(), il.mutable_data(), ol.mutable_data(), gc.mutable_data(),
+                                                   ac.mutable_data(), ns.mutable_data(), start.mutable_data()); }));
+    const auto t2 = std::chrono::steady_clock::now();
+    int64_t bytes = 0;
+    Check(khg_lattices_device_bytes(lh.h, &bytes));
+    py::dict d;
+    d["ali"] = py::array(ali)[py::slice(0, N, 1)];
+    d["like"] = like; d["status"] = status; d["error_frame"] = ef;
+    d["words"] = py::array(words)[py::slice(0, woff.at(n_utt), 1)];
+    d["words_off"] = woff;
+    d["state_off"] = so; d["arc_off"] = ao; d["start"] = start;
+    d["frame"] = frame; d["graph_state"] = gstate; d["tot_cost"] = tot; d["extra_cost"] = extra; d["final_cost"] = fin; d["arc_begin"] = abeg;
+    d["ilabel"] = il; d["olabel"] = ol; d["graph_cost"] = gc; d["acoustic_cost"] = ac; d["nextstate"] = ns;
+    d["device_bytes"] = bytes;
+    d["decode_s"] = std::chrono::duration<double>(t1 - t0).count();
+    d["download_s"] = std::chrono::duration<double>(t2 - t1).count();
+    return d;
+  }
   py::object align(KTransitions& tm, float beam, float retry_beam, float acoustic_scale, bool careful, int64_t max_active, int min_active,
                    float beam_delta, float hash_ratio, py::object download) {
     khg_align_config c;
@@ -663,6 +707,8 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("decode_lattice_simple", &KUtts::decode_lattice_simple, py::arg("tm"), py::arg("beam") = 16.0f, py::arg("lattice_beam") = 10.0f,
            py::arg("prune_interval") = 25, py::arg("prune_scale") = 0.1f, py::arg("acoustic_scale") = 1.0f, py::arg("allow_partial") = true,
            py::arg("scratch_per_frame") = 0)
+      .def("raw_lattice_simple", &KUtts::raw_lattice_simple, py::arg("tm"), py::arg("beam") = 16.0f, py::arg("lattice_beam") = 10.0f,
+           py::arg("prune_interval") = 25, py::arg("prune_scale") = 0.1f, py::arg("acoustic_scale") = 1.0f, py::arg("scratch_per_frame") = 0)
       .def("upload_ali", &KUtts::upload_ali).def("download_ali", &KUtts::download_ali)
       .def("acc_stats", &KUtts::acc_stats, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f)
       .def("acc_stats_reduce", &KUtts::acc_stats_reduce, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f,

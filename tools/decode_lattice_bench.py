@@ -22,7 +22,12 @@ repetition.  The JSON line reports the graph, per path the set creation time, th
 max), and the share of utterances that succeeded.  --check N compares the first N with both restatements.  --yesno times the simple
 decoder at the same thresholds on the 46-state word loop of examples/decode_synthetic.py instead.
 
-Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N]
+--lattices (with --decoder simple, or with --shared-graph) also times the raw-lattice call beside the old one, alternated inside
+every repetition: get_raw_lattice_simple_batch (UtteranceSet.raw_lattice_simple on the shared-graph sets).  It reports the states,
+arcs and bytes per utterance, the download apart from the decode call (seconds, bytes, effective GB/s), and -- from one more pass of
+each call under the context's kernel timing -- the device time of k2_lattice_simple and of the emission kernels (count, scans, fill).
+
+Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices]
        python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
@@ -112,7 +117,38 @@ def med(xs):
     return {"median_s": float(np.median(xs)), "min_s": float(min(xs)), "max_s": float(max(xs))}
 
 
-def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True):
+def kernel_ms(ctx, call):
+    """One run of `call` under the context's kernel timing -> {kernel name: milliseconds, summed over its launches}."""
+    ctx.sync()
+    ctx.timings()
+    ctx.set_timing(True)
+    try:
+        call()
+        out = {}
+        for name, ms in ctx.timings():
+            out[name] = out.get(name, 0.0) + float(ms)
+    finally:
+        ctx.set_timing(False)
+    return out
+
+
+def lattice_sizes(state_counts, arc_counts, download_s):
+    """Per-utterance sizes of a batch's raw lattices (24 bytes a state, 20 an arc) and the download's rate."""
+    st, ar = np.asarray(state_counts, np.int64), np.asarray(arc_counts, np.int64)
+    nbytes = int(24 * st.sum() + 20 * ar.sum())
+    return {"states_per_utt": {"mean": float(st.mean()), "max": int(st.max())}, "arcs_per_utt": {"mean": float(ar.mean()), "max": int(ar.max())},
+            "bytes_per_utt": nbytes / max(len(st), 1), "download_bytes": nbytes, "download": med(download_s),
+            "download_GB_per_s": nbytes / float(np.median(download_s)) / 1e9, "empty_lattices": int((st == 0).sum())}
+
+
+def emission_summary(k_old, k_new):
+    """Kernel milliseconds of the old call and of the raw-lattice call -> the decoder's and the emission's device time."""
+    emit = sum(v for k, v in k_new.items() if k.startswith("k2_lattice_raw"))
+    return {"old_call_kernels_ms": k_old, "raw_call_kernels_ms": k_new, "k2_lattice_simple_ms": k_old.get("k2_lattice_simple"),
+            "emission_ms": emit, "emission_over_decoder": emit / k_old["k2_lattice_simple"] if k_old.get("k2_lattice_simple") else None}
+
+
+def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
     """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
     after one warm-up round; and the last results."""
     times = {p: {} for p in sets}
@@ -132,6 +168,14 @@ def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True):
                     last[(p, "simple", h)] = us.decode_lattice_simple(dtm, beam=13.0, lattice_beam=6.0, acoustic_scale=0.1)
                     if rep:
                         times[p].setdefault("lattice_simple_hub_%d" % h, []).append(time.time() - t0)
+                    if lattices:
+                        ctx.sync(); t0 = time.time()
+                        r = us.raw_lattice_simple(dtm, beam=13.0, lattice_beam=6.0, acoustic_scale=0.1)
+                        last[(p, "raw", h)] = r
+                        if rep:
+                            times[p].setdefault("raw_lattice_simple_hub_%d" % h, []).append(time.time() - t0)
+                            times[p].setdefault("raw_decode_call_hub_%d" % h, []).append(r["decode_s"])
+                            times[p].setdefault("raw_download_hub_%d" % h, []).append(r["download_s"])
     finally:
         ctx.set_option("k2s_hub", default)
     return times, last
@@ -213,13 +257,30 @@ def shared_graph_main(args):
         for us in sets.values():
             us.loglikes(dm)
         ctx.sync()
-        times, last = time_paths(ctx, dtm, sets, hubs if name == "simple" else [], args.reps, with_faster=name == "faster")
+        lat = args.lattices and name == "simple"
+        times, last = time_paths(ctx, dtm, sets, hubs if name == "simple" else [], args.reps, with_faster=name == "faster", lattices=lat)
         for p in sets:
             entry[p].update({k: med(v) for k, v in times[p].items()})
         key = ("shared", "faster") if name == "faster" else ("shared", "simple", hubs[0])
         entry["succeeded_share"] = float(((last[key]["status"] & 1) != 0).mean())
         same = all(last[key][f].tobytes() == r[f].tobytes() for r in last.values() for f in ("ali", "like", "status", "words", "words_off"))
         entry["all_paths_and_thresholds_identical"] = bool(same)
+        if lat:
+            raws = [r for k, r in last.items() if k[1] == "raw"]
+            fields = ("state_off", "arc_off", "start", "frame", "graph_state", "tot_cost", "extra_cost", "final_cost", "arc_begin", "ilabel", "olabel",
+                      "graph_cost", "acoustic_cost", "nextstate")
+            entry["lattices_identical_across_paths_and_thresholds"] = bool(all(raws[0][f].tobytes() == r[f].tobytes() for r in raws for f in fields))
+            h = hubs[-1]
+            r = last[("shared", "raw", h)]
+            entry["lattices"] = lattice_sizes(np.diff(r["state_off"]), np.diff(r["arc_off"]), times["shared"]["raw_download_hub_%d" % h])
+            entry["lattices"]["device_bytes"] = int(r["device_bytes"])
+            ctx.set_option("k2s_hub", h)
+            try:
+                k_old = kernel_ms(ctx, lambda: sh.decode_lattice_simple(dtm, beam=13.0, lattice_beam=6.0, acoustic_scale=0.1))
+                k_new = kernel_ms(ctx, lambda: sh.raw_lattice_simple(dtm, beam=13.0, lattice_beam=6.0, acoustic_scale=0.1))
+            finally:
+                ctx.set_option("k2s_hub", out["hub_default"])
+            entry["lattices"].update(emission_summary(k_old, k_new), hub=h)
         if args.check > 0:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
             import lattice_faster_ref as fref
@@ -263,7 +324,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--decoder", choices=("faster", "simple"), default="faster")
     ap.add_argument("--check", type=int, default=0)
+    ap.add_argument("--lattices", action="store_true", help="also time the raw-lattice call (simple decoder) and report the lattices")
     args = ap.parse_args()
+    if args.lattices and not (args.shared_graph or args.decoder == "simple"):
+        ap.error("--lattices needs --decoder simple or --shared-graph")
     if args.shared_graph or args.yesno:
         shared_graph_main(args)
         return
@@ -282,10 +346,17 @@ def main():
         scfg = khg.LatticeSimpleDecoderConfig(beam=13.0, lattice_beam=6.0)
         simple_s = []
         khg.decode_lattice_simple_batch(am, tm, fsts[:64], feats[:64], scfg, 0.1)          # warm-up
+        raw_s, raw_dec_s, raw_dl_s, raw = [], [], [], None
+        if args.lattices:
+            khg.get_raw_lattice_simple_batch(am, tm, fsts[:64], feats[:64], scfg, 0.1)     # warm-up
         for _ in range(args.reps):
             t0 = time.time()
             res = khg.decode_lattice_simple_batch(am, tm, fsts, feats, scfg, 0.1)
             simple_s.append(time.time() - t0)
+            if args.lattices:
+                t0 = time.time()
+                raw, t = khg.get_raw_lattice_simple_batch(am, tm, fsts, feats, scfg, 0.1, return_times=True)
+                raw_s.append(time.time() - t0); raw_dec_s.append(t["decode_s"]); raw_dl_s.append(t["download_s"])
     for _ in range(args.reps):
         t0 = time.time()
         fres = khg.decode_lattice_faster_batch(am, tm, fsts, feats, cfg, 0.1)
@@ -304,6 +375,17 @@ def main():
         out.update(simple_s=min(simple_s), simple_frames_per_s=frames / min(simple_s), simple_over_lattice_faster=min(simple_s) / min(lat_s),
                    simple_over_faster_decoder=min(simple_s) / min(ali_s),
                    same_best_paths_as_lattice_faster=sum(1 for a, b in zip(res, fres) if a["alignment"] == b["alignment"]))
+        out["simple"] = med(simple_s)
+        if args.lattices:
+            from kaldi_hmm_gmm_amd import _gpu
+            ctx = _gpu.default_context()
+            lat = lattice_sizes([r["lattice"].num_states for r in raw], [r["lattice"].num_arcs_total for r in raw], raw_dl_s)
+            lat.update(raw_call=med(raw_s), raw_decode_call=med(raw_dec_s),
+                       same_best_paths_as_old_call=sum(1 for a, b in zip(res, raw) if all(a[k] == b[k] for k in a)))
+            k_old = kernel_ms(ctx, lambda: khg.decode_lattice_simple_batch(am, tm, fsts, feats, scfg, 0.1))
+            k_new = kernel_ms(ctx, lambda: khg.get_raw_lattice_simple_batch(am, tm, fsts, feats, scfg, 0.1))
+            lat.update(emission_summary(k_old, k_new))
+            out["lattices"] = lat
         if args.check > 0:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
             import lattice_simple_ref as ref
