@@ -14,7 +14,12 @@ decode_utterance_lattice_simple and decode_lattice_simple_batch.  The word loop 
 LatticeSimpleDecoder stops at InitDecoding ("no surviving tokens"), so that decoder gets a copy of it with a zero-weight
 input-epsilon self-loop on every state: no path's weight changes.
 
-Usage: python examples/decode_lattice_synthetic.py [--utts 200] [--iters 80] [--decoder faster|simple]
+--decoder simple --sweep 7:17 also keeps the batch's raw lattices on the device (get_raw_lattice_simple_device_batch) and prints the
+WER at every integer language-model weight w in 7..17 (graph_scale 1, acoustic_scale 1 / w; the lattices hold costs at acoustic
+scale 0.1, i.e. weight 10 is acoustic_scale 1.0 here) from that ONE decode: one DeviceLattices.best_path call, no lattice leaves the
+device.
+
+Usage: python examples/decode_lattice_synthetic.py [--utts 200] [--iters 80] [--decoder faster|simple] [--sweep 7:17]
 """
 import argparse
 import os
@@ -36,7 +41,10 @@ def main():
     ap.add_argument("--dim", type=int, default=23)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--decoder", choices=("faster", "simple"), default="faster")
+    ap.add_argument("--sweep", default=None, metavar="LO:HI", help="with --decoder simple: WER at every integer LM weight, from one decode")
     args = ap.parse_args()
+    if args.sweep and args.decoder != "simple":
+        ap.error("--sweep needs --decoder simple (the raw lattice is the lattice-simple decoder's)")
     tm, tree, am, lexicon, test_utts = dx.train(args)
     # decode.py:112,135: transition_scale 1.0, self_loop_scale 1.0 go into the graph
     gc = TrainingGraphCompiler(tm, tree, lexicon, sil_phone=dx.tr.SIL, sil_prob=0.5,
@@ -70,6 +78,23 @@ def main():
           f"WER {100.0 * errs / max(nref, 1):.2f}% ({errs} / {nref}), {failed} failed, {t1 - t0:.2f} s through the per-utterance calls; "
           f"batched decode {'identical' if same else 'DIFFERENT'}")
     print(f"{test_utts[0][0]}: words {hyps[0][2]} (truth {test_utts[0][1]}), like {hyps[0][3]:.4f}")
+    if args.sweep:
+        import numpy as np
+        lo, hi = (int(x) for x in args.sweep.split(":"))
+        ws = np.arange(lo, hi + 1)
+        # the lattices were decoded at acoustic scale 0.1 = LM weight 10: weight w re-weights their acoustic costs by 10 / w
+        _, lats = khg.get_raw_lattice_simple_device_batch(am, tm, graph, [u[2] for u in test_utts], config, 0.1)
+        bp = lats.best_path(np.ones(len(ws), np.float32), (10.0 / ws).astype(np.float32))
+        U = len(test_utts)
+        for k, w in enumerate(ws):
+            e = n = 0
+            for u, (_, ref_words, _) in enumerate(test_utts):
+                o = k * U + u
+                hyp = bp["words"][bp["words_off"][o]: bp["words_off"][o + 1]].tolist() if bp["status"][o] & 1 else []
+                e += dx.edit_distance(ref_words, hyp)
+                n += len(ref_words)
+            print(f"LM weight {w:2d}: WER {100.0 * e / max(n, 1):.2f}% ({e} / {n})")
+        lats.close()
     return 0 if errs <= 0.05 * nref and same and (failed == 0 or args.decoder == "faster") else 1
 
 

@@ -113,7 +113,10 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
 #define KHG_OPT_K2S_HUB 17       /* khg_decode_lattice_simple: a state with more than this many in-arcs (out-arcs in the backward pass) has its arc
                                     loops strided over by a whole wave instead of walked by one lane (a word loop's hub state); same results
                                     bit for bit.  0: off (every state on one lane).  Default 32                              [KHG_K2S_HUB] */
-#define KHG_OPT_COUNT 18
+#define KHG_OPT_LAT_OPS_LDS 18   /* khg_lattices_best_path / khg_lattices_prune: 0 (DEFAULT) an utterance's lattice is staged into LDS when it takes
+                                    at most 48 KiB there, 1 never (every lattice is read from its HBM arrays); same results bit for
+                                    bit                                                                              [KHG_LAT_OPS_LDS] */
+#define KHG_OPT_COUNT 19
 /* Read-only figures (khg_ctx_get_option only): the per-call scratch block behind small utterance sets (DESIGN.md "per-utterance calls"). */
 #define KHG_INFO_SCRATCH_BYTES 100   /* bytes of the block in use (its top), 0 before the first small set */
 #define KHG_INFO_SCRATCH_BLOCKS 101  /* live allocations inside it */
@@ -412,6 +415,44 @@ int khg_lattices_download(khg_ctx *ctx, const khg_lattices *l, int32_t *frame_h,
 /* device bytes the handle owns */
 int khg_lattices_device_bytes(const khg_lattices *l, int64_t *bytes);
 int khg_lattices_destroy(khg_lattices *l);
+
+/* ---- K2O: best path under scales and beam pruning of resident lattices ---------------------------------------------------------- */
+/* A handle from host arrays, in the layout khg_lattices_download writes: state_off_h / arc_off_h [n_utt + 1], the six per-state and
+ * five per-arc arrays, start_h[n_utt].  Every utterance is checked (KHG_E_ARG names the utterance and the check): one arc_begin per
+ * state running from 0, monotone, within the arcs; states ordered by frame; nextstate in range; start in range (-1 for an empty
+ * lattice) and on frame 0; an emitting arc (ilabel != 0) goes from frame f to frame f + 1, an epsilon arc stays in its frame.
+ * khg_lattices_validate runs the checks alone (no device).  Free *out with khg_lattices_destroy. */
+int khg_lattices_validate(int32_t n_utt, const int64_t *state_off_h, const int64_t *arc_off_h, const int32_t *frame_h,
+                          const int32_t *graph_state_h, const float *tot_cost_h, const float *extra_cost_h, const float *final_cost_h,
+                          const int32_t *arc_begin_h, const int32_t *ilabel_h, const int32_t *olabel_h, const float *graph_cost_h,
+                          const float *acoustic_cost_h, const int32_t *nextstate_h, const int32_t *start_h);
+int khg_lattices_upload(khg_ctx *ctx, int32_t n_utt, const int64_t *state_off_h, const int64_t *arc_off_h, const int32_t *frame_h,
+                        const int32_t *graph_state_h, const float *tot_cost_h, const float *extra_cost_h, const float *final_cost_h,
+                        const int32_t *arc_begin_h, const int32_t *ilabel_h, const int32_t *olabel_h, const float *graph_cost_h,
+                        const float *acoustic_cost_h, const int32_t *nextstate_h, const int32_t *start_h, khg_lattices **out);
+/* the number of utterances of a handle; the layout of khg_lattices_best_path's alignments: ali_off_h[n_utt + 1], utterance u owns
+ * ali_off_h[u + 1] - ali_off_h[u] = the frame of its last state (0 for an empty lattice) entries of every pair's row */
+int khg_lattices_num_utts(const khg_lattices *l, int32_t *n_utt);
+int khg_lattices_ali_layout(khg_ctx *ctx, const khg_lattices *l, int64_t *ali_off_h);
+/* lattice-scale | lattice-best-path for n_scales (graph_scale, acoustic_scale) pairs in one call (finite, >= 0; else KHG_E_ARG): an
+ * arc weighs (fl(graph_scale * graph_cost), fl(acoustic_scale * acoustic_cost)), a final state (fl(graph_scale * final_cost), 0), and
+ * the best path is OpenFst ShortestPath by the decoder kernel's tie rule (float, no contraction; at (1, 1) the decoder's own path).
+ * Outputs (host, may be NULL), pair k, utterance u at index k * n_utt + u:
+ *   ali_h[n_scales][sum over utterances of the last state's frame]   the path's transition-ids by frame, 0 without a path
+ *   words_h / words_off_h[n_scales * n_utt + 1]  its olabels != 0 (words_cap = capacity; an entry that does not fit gets KHG_LAT_WORDS
+ *                                                and no words)
+ *   weight_h[n_scales * n_utt][2]  the path's two sums, float, left to right from One(), the final weight last (+inf without a path)
+ *   status_h[n_scales * n_utt]     KHG_LAT_SUCCEEDED, or KHG_LAT_NO_PATH (an empty lattice, no final state reached), KHG_LAT_EPS_LOOP
+ *                                  (a negative-cost epsilon cycle under these scales), KHG_LAT_WORDS
+ * Synchronous.  The handle's lattices are not changed. */
+int khg_lattices_best_path(khg_ctx *ctx, const khg_lattices *l, int32_t n_scales, const float *graph_scale, const float *acoustic_scale,
+                           int32_t *ali_h, int32_t *words_h, int64_t *words_off_h, int64_t words_cap, float *weight_h, int32_t *status_h);
+/* lattice-prune under one scale pair: a new handle with the states and arcs whose best path through them costs at most
+ * fl(best + beam) (beam >= 0, +inf allowed), plus the best path itself; states and arcs keep their order, nextstate / start are
+ * renumbered, every cost is copied as stored (unscaled).  An utterance without a path (KHG_LAT_NO_PATH) or with a negative epsilon
+ * cycle (KHG_LAT_EPS_LOOP) gets an empty lattice.  status_h[n_utt] (may be NULL).  Synchronous; the input is untouched. */
+int khg_lattices_prune(khg_ctx *ctx, const khg_lattices *l, float graph_scale, float acoustic_scale, float beam, int32_t *status_h,
+                       khg_lattices **out);
 
 /* ---- K3: sufficient statistics ---------------------------------------------------------- */
 /* AccumAmDiagGmm (csrc/mle-am-diag-gmm.h:93-96) + transition stats (csrc/transition-model.h:176-189)

@@ -154,6 +154,14 @@ SIGNATURES = {
                                         c_i32p]),
     "khg_lattices_device_bytes": (C.c_int, [vp, c_i64p]),
     "khg_lattices_destroy": (C.c_int, [vp]),
+    "khg_lattices_validate": (C.c_int, [C.c_int32, c_i64p, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p,
+                                        c_f32p, c_i32p, c_i32p]),
+    "khg_lattices_upload": (C.c_int, [vp, C.c_int32, c_i64p, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p,
+                                      c_f32p, c_i32p, c_i32p, C.POINTER(vp)]),
+    "khg_lattices_num_utts": (C.c_int, [vp, c_i32p]),
+    "khg_lattices_ali_layout": (C.c_int, [vp, vp, c_i64p]),
+    "khg_lattices_best_path": (C.c_int, [vp, vp, C.c_int32, c_f32p, c_f32p, c_i32p, c_i32p, c_i64p, C.c_int64, c_f32p, c_i32p]),
+    "khg_lattices_prune": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_float, c_i32p, C.POINTER(vp)]),
     "khg_ali_download": (C.c_int, [vp, vp, c_i32p]),
     "khg_accs_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     "khg_accs_destroy": (C.c_int, [vp]),

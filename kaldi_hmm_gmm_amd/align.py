@@ -17,4 +17,5 @@ from ._kaldi_hmm_gmm_amd import (DeterminizeLatticePhonePrunedOptions, LatticeFa
 from ._kaldi_hmm_gmm_amd import (DecodableCtc, LatticeSimpleDecoder, LatticeSimpleDecoderConfig, decode_lattice_simple_batch,  # noqa: F401
                                  decode_utterance_lattice_simple)
 from ._kaldi_hmm_gmm_amd import Lattice, get_raw_lattice_simple_batch  # noqa: F401
+from ._kaldi_hmm_gmm_amd import DeviceLattices, get_raw_lattice_simple_device_batch  # noqa: F401
 from .device import ALIGN_ERROR, ALIGN_RETRIED, INT32_MAX  # noqa: F401

@@ -373,6 +373,50 @@ std::vector<LatticeResult> GetRawLatticeSimpleBatch(const AmDiagGmm& am, const T
                       });
 }
 
+std::vector<std::shared_ptr<Lattice>> DownloadLattices(khg_ctx* ctx, const khg_lattices* h) {
+  int32_t n_utt = 0;
+  CApi(khg_lattices_num_utts(h, &n_utt));
+  std::vector<int64_t> so((size_t)n_utt + 1, 0), ao((size_t)n_utt + 1, 0);
+  CApi(khg_lattices_sizes(h, so.data(), ao.data()));
+  const size_t NS = (size_t)so[(size_t)n_utt], NA = (size_t)ao[(size_t)n_utt];
+  std::vector<int32_t> frame(NS + 1), gstate(NS + 1), abeg(NS + 1), il(NA + 1), ol(NA + 1), ns(NA + 1), start((size_t)n_utt + 1);
+  std::vector<float> tot(NS + 1), extra(NS + 1), fin(NS + 1), gc(NA + 1), ac(NA + 1);
+  CApi(khg_lattices_download(ctx, h, frame.data(), gstate.data(), tot.data(), extra.data(), fin.data(), abeg.data(), il.data(), ol.data(), gc.data(),
+                             ac.data(), ns.data(), start.data()));
+  std::vector<std::shared_ptr<Lattice>> out((size_t)n_utt);
+  for (int u = 0; u < n_utt; ++u) {
+    auto l = std::make_shared<Lattice>();
+    const size_t s0 = (size_t)so[(size_t)u], s1 = (size_t)so[(size_t)u + 1], a0 = (size_t)ao[(size_t)u], a1 = (size_t)ao[(size_t)u + 1];
+    l->frame.assign(frame.begin() + s0, frame.begin() + s1); l->graph_state.assign(gstate.begin() + s0, gstate.begin() + s1);
+    l->tot_cost.assign(tot.begin() + s0, tot.begin() + s1); l->extra_cost.assign(extra.begin() + s0, extra.begin() + s1);
+    l->final_cost.assign(fin.begin() + s0, fin.begin() + s1);
+    l->arc_begin.assign(abeg.begin() + s0, abeg.begin() + s1);
+    l->arc_begin.push_back((int32_t)(a1 - a0));
+    l->ilabel.assign(il.begin() + a0, il.begin() + a1); l->olabel.assign(ol.begin() + a0, ol.begin() + a1);
+    l->nextstate.assign(ns.begin() + a0, ns.begin() + a1);
+    l->graph_cost.assign(gc.begin() + a0, gc.begin() + a1); l->acoustic_cost.assign(ac.begin() + a0, ac.begin() + a1);
+    l->start = s1 > s0 ? start[(size_t)u] : kNoStateId;
+    out[(size_t)u] = std::move(l);
+  }
+  return out;
+}
+
+std::vector<LatticeResult> GetRawLatticeSimpleDeviceBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g,
+                                                          const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                          const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool return_scores,
+                                                          int scratch_per_frame, khg_lattices** lattices) {
+  config.Check();
+  KHG_REQUIRE(lattices != nullptr, "get_raw_lattice_simple_device_batch: no place for the lattices");
+  *lattices = nullptr;
+  for (int64_t T : nframes) KHG_REQUIRE(T > 0, "get_raw_lattice_simple_device_batch: an utterance without frames");
+  const int n_utt = (int)feats.size();
+  return K1ThenDecode(am, tm, g, feats, nframes, return_scores, "get_raw_lattice_simple_device_batch",
+                      [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
+                        return DecodeLatticeSimpleOnSet(ctx, dt, us, frame_off, config, acoustic_scale, true, scratch_per_frame,
+                                                        BatchStates(g, n_utt), lattices);
+                      });
+}
+
 // scripts/gmm_acc_stats_ali.py:46-58 through K3, into the accumulators' device block (khg_host_gmm.hpp)
 double AccumAmDiagGmm::AccumulateAli(const AmDiagGmm& model, const TransitionModel& tm, const float* feats, const int64_t* frame_off, int n_utt,
                                      const int32_t* ali, float weight) {

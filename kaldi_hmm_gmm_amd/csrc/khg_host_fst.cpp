@@ -106,17 +106,20 @@ std::string Lattice::ToText() const {
   return out;
 }
 
-LinearLattice Lattice::ShortestPath() const {
-  LinearLattice out;
+namespace {
+// NaturalLess of LatticeWeight on float pairs: (a1, a2) strictly better than (b1, b2)
+inline bool LatLess(float a1, float a2, float b1, float b2) {
+  const float fa = a1 + a2, fb = b1 + b2;
+  if (fa < fb) return true;
+  if (fa > fb) return false;
+  return a1 < b1;
+}
+}  // namespace
+
+// the forward pairs and back-pointers under (gs, as); false: a negative-cost epsilon cycle
+bool Lattice::Forward(float gs, float as, std::vector<float>* d1p, std::vector<float>* d2p, std::vector<int32_t>* bpp) const {
   const int N = NumStates();
-  if (N == 0 || start < 0) return out;
   const float INF = std::numeric_limits<float>::infinity();
-  auto less = [](float a1, float a2, float b1, float b2) {       // NaturalLess: (a1, a2) strictly better
-    const float fa = a1 + a2, fb = b1 + b2;
-    if (fa < fb) return true;
-    if (fa > fb) return false;
-    return a1 < b1;
-  };
   // in-links of every state, stable by (source state, arc): the in-arc order of the decoder kernel
   const int64_t A = NumArcs();
   std::vector<int64_t> in_off((size_t)N + 1, 0);
@@ -131,8 +134,9 @@ LinearLattice Lattice::ShortestPath() const {
         in_arc[(size_t)pos] = a; in_src[(size_t)pos] = s;
       }
   }
-  std::vector<float> d1((size_t)N, INF), d2((size_t)N, INF), n1((size_t)N), n2((size_t)N);
-  std::vector<int32_t> bp((size_t)N, -1);
+  std::vector<float>& d1 = *d1p; std::vector<float>& d2 = *d2p; std::vector<int32_t>& bp = *bpp;
+  d1.assign((size_t)N, INF); d2.assign((size_t)N, INF); bp.assign((size_t)N, -1);
+  std::vector<float> n1((size_t)N), n2((size_t)N);
   d1[(size_t)start] = 0.0f; d2[(size_t)start] = 0.0f;
   const int T = frame[(size_t)N - 1];
   int lo = 0;
@@ -145,8 +149,9 @@ LinearLattice Lattice::ShortestPath() const {
         for (int64_t i = in_off[(size_t)n]; i < in_off[(size_t)n + 1]; ++i) {
           const int a = in_arc[(size_t)i], m = in_src[(size_t)i];
           if (ilabel[(size_t)a] == 0 || d1[(size_t)m] == INF) continue;
-          const float c1 = d1[(size_t)m] + graph_cost[(size_t)a], c2 = d2[(size_t)m] + acoustic_cost[(size_t)a];
-          if (b1 == INF || less(c1, c2, b1, b2)) { b1 = c1; b2 = c2; bp[(size_t)n] = a; }
+          const float w1 = gs * graph_cost[(size_t)a], w2 = as * acoustic_cost[(size_t)a];
+          const float c1 = d1[(size_t)m] + w1, c2 = d2[(size_t)m] + w2;
+          if (b1 == INF || LatLess(c1, c2, b1, b2)) { b1 = c1; b2 = c2; bp[(size_t)n] = a; }
         }
         d1[(size_t)n] = b1; d2[(size_t)n] = b2;
       }
@@ -157,41 +162,185 @@ LinearLattice Lattice::ShortestPath() const {
         for (int64_t i = in_off[(size_t)n]; i < in_off[(size_t)n + 1]; ++i) {
           const int a = in_arc[(size_t)i], m = in_src[(size_t)i];
           if (ilabel[(size_t)a] != 0 || d1[(size_t)m] == INF) continue;
-          const float c1 = d1[(size_t)m] + graph_cost[(size_t)a], c2 = d2[(size_t)m] + 0.0f;
-          if (b1 == INF || less(c1, c2, b1, b2)) { b1 = c1; b2 = c2; bp[(size_t)n] = a; changed = true; }
+          const float w1 = gs * graph_cost[(size_t)a];
+          const float c1 = d1[(size_t)m] + w1, c2 = d2[(size_t)m] + 0.0f;
+          if (b1 == INF || LatLess(c1, c2, b1, b2)) { b1 = c1; b2 = c2; bp[(size_t)n] = a; changed = true; }
         }
         n1[(size_t)n] = b1; n2[(size_t)n] = b2;
       }
       for (int n = lo; n < hi; ++n) { d1[(size_t)n] = n1[(size_t)n]; d2[(size_t)n] = n2[(size_t)n]; }
       if (!changed) break;
-      KHG_REQUIRE(round <= hi - lo, "Lattice::ShortestPath: a negative-cost epsilon cycle");
+      if (round > hi - lo) return false;
     }
     lo = hi;
   }
+  return true;
+}
+
+// the backward pairs: the mirror image of Forward, over out-arcs
+bool Lattice::Backward(float gs, float as, std::vector<float>* e1p, std::vector<float>* e2p) const {
+  const int N = NumStates();
+  const float INF = std::numeric_limits<float>::infinity();
+  std::vector<float>& e1 = *e1p; std::vector<float>& e2 = *e2p;
+  e1.assign((size_t)N, INF); e2.assign((size_t)N, INF);
+  std::vector<float> n1((size_t)N), n2((size_t)N);
+  const int T = frame[(size_t)N - 1];
+  int hi = N;
+  while (hi > 0) {
+    const int f = frame[(size_t)hi - 1];
+    int lo = hi;
+    while (lo > 0 && frame[(size_t)lo - 1] == f) --lo;
+    for (int n = lo; n < hi; ++n) {
+      float b1 = INF, b2 = INF;
+      if (f == T && final_cost[(size_t)n] != INF) { b1 = gs * final_cost[(size_t)n]; b2 = 0.0f; }
+      for (int a = arc_begin[(size_t)n]; a < arc_begin[(size_t)n + 1]; ++a) {
+        const int k = nextstate[(size_t)a];
+        if (ilabel[(size_t)a] == 0 || e1[(size_t)k] == INF) continue;
+        const float w1 = gs * graph_cost[(size_t)a], w2 = as * acoustic_cost[(size_t)a];
+        const float c1 = w1 + e1[(size_t)k], c2 = w2 + e2[(size_t)k];
+        if (b1 == INF || LatLess(c1, c2, b1, b2)) { b1 = c1; b2 = c2; }
+      }
+      e1[(size_t)n] = b1; e2[(size_t)n] = b2;
+    }
+    for (int round = 0;; ++round) {
+      bool changed = false;
+      for (int n = lo; n < hi; ++n) {
+        float b1 = e1[(size_t)n], b2 = e2[(size_t)n];
+        for (int a = arc_begin[(size_t)n]; a < arc_begin[(size_t)n + 1]; ++a) {
+          const int k = nextstate[(size_t)a];
+          if (ilabel[(size_t)a] != 0 || e1[(size_t)k] == INF) continue;
+          const float w1 = gs * graph_cost[(size_t)a];
+          const float c1 = w1 + e1[(size_t)k], c2 = 0.0f + e2[(size_t)k];
+          if (b1 == INF || LatLess(c1, c2, b1, b2)) { b1 = c1; b2 = c2; changed = true; }
+        }
+        n1[(size_t)n] = b1; n2[(size_t)n] = b2;
+      }
+      for (int n = lo; n < hi; ++n) { e1[(size_t)n] = n1[(size_t)n]; e2[(size_t)n] = n2[(size_t)n]; }
+      if (!changed) break;
+      if (round > hi - lo) return false;
+    }
+    hi = lo;
+  }
+  return true;
+}
+
+LatticeBestPath Lattice::BestPath(float gs, float as) const {
+  KHG_REQUIRE(gs >= 0.0f && as >= 0.0f, "Lattice: graph_scale and acoustic_scale must be >= 0");
+  LatticeBestPath out;
+  const float INF = std::numeric_limits<float>::infinity();
+  out.v1 = out.v2 = out.f1 = out.f2 = INF;
+  out.status = KHG_LAT_NO_PATH;
+  const int N = NumStates();
+  if (N == 0 || start < 0) return out;
+  if (!Forward(gs, as, &out.alpha1, &out.alpha2, &out.bp)) { out.status = KHG_LAT_EPS_LOOP; return out; }
+  const std::vector<float>&d1 = out.alpha1, &d2 = out.alpha2;
+  const std::vector<int32_t>& bp = out.bp;
+  const int64_t A = NumArcs();
+  const int T = frame[(size_t)N - 1];
   int fin = -1;
   float f1 = INF, f2 = INF;
   for (int n = 0; n < N; ++n) {
     if (frame[(size_t)n] != T || d1[(size_t)n] == INF || final_cost[(size_t)n] == INF) continue;
-    const float w1 = d1[(size_t)n] + final_cost[(size_t)n], w2 = d2[(size_t)n] + 0.0f;
-    if (fin < 0 || less(w1, w2, f1, f2)) { f1 = w1; f2 = w2; fin = n; }
+    const float fw = gs * final_cost[(size_t)n];
+    const float w1 = d1[(size_t)n] + fw, w2 = d2[(size_t)n] + 0.0f;
+    if (fin < 0 || LatLess(w1, w2, f1, f2)) { f1 = w1; f2 = w2; fin = n; }
   }
   if (fin < 0) return out;
   std::vector<int32_t> path;
-  for (int n = fin; n != start || bp[(size_t)n] >= 0;) {
+  for (int n = fin; !(n == start && bp[(size_t)n] < 0);) {
     const int a = bp[(size_t)n];
     if (a < 0 || (int64_t)path.size() > A) return out;
     path.push_back(a);
     // the source of arc a: the state whose arc range holds it
     n = (int)(std::upper_bound(arc_begin.begin(), arc_begin.end(), a) - arc_begin.begin()) - 1;
-    if (n == start && frame[(size_t)n] == 0 && bp[(size_t)n] < 0) break;
   }
+  std::reverse(path.begin(), path.end());
+  float v1 = 0.0f, v2 = 0.0f;
+  for (int a : path) {
+    const float w1 = gs * graph_cost[(size_t)a], w2 = ilabel[(size_t)a] != 0 ? as * acoustic_cost[(size_t)a] : 0.0f;
+    v1 = v1 + w1; v2 = v2 + w2;
+    if (ilabel[(size_t)a]) out.ali.push_back(ilabel[(size_t)a]);
+    if (olabel[(size_t)a]) out.words.push_back(olabel[(size_t)a]);
+  }
+  const float fw = gs * final_cost[(size_t)fin];
+  out.v1 = v1 + fw; out.v2 = v2 + 0.0f;
+  out.f1 = f1; out.f2 = f2;
+  out.arcs = std::move(path);
+  out.final_state = fin;
+  out.status = KHG_LAT_SUCCEEDED;
+  return out;
+}
+
+LinearLattice Lattice::ShortestPath(float gs, float as) const {
+  LinearLattice out;
+  const LatticeBestPath b = BestPath(gs, as);
+  KHG_REQUIRE(!(b.status & KHG_LAT_EPS_LOOP), "Lattice::ShortestPath: a negative-cost epsilon cycle");
+  if (!(b.status & KHG_LAT_SUCCEEDED)) return out;
   out.start = 0;
-  for (size_t i = path.size(); i-- > 0;) {
-    const int a = path[i];
-    out.arcs.push_back(LatticeArc{ilabel[(size_t)a], olabel[(size_t)a], LatticeWeight{(double)graph_cost[(size_t)a], (double)acoustic_cost[(size_t)a]},
-                                  (int)(path.size() - i)});
+  for (size_t i = 0; i < b.arcs.size(); ++i) {
+    const int a = b.arcs[i];
+    const float w1 = gs * graph_cost[(size_t)a], w2 = as * acoustic_cost[(size_t)a];
+    out.arcs.push_back(LatticeArc{ilabel[(size_t)a], olabel[(size_t)a], LatticeWeight{(double)w1, (double)w2}, (int)i + 1});
   }
-  out.final_w = LatticeWeight{(double)final_cost[(size_t)fin], 0.0};
+  const float fw = gs * final_cost[(size_t)b.final_state];
+  out.final_w = LatticeWeight{(double)fw, 0.0};
+  return out;
+}
+
+std::shared_ptr<Lattice> Lattice::Prune(float beam, float gs, float as, int* status) const {
+  KHG_REQUIRE(beam >= 0.0f, "Lattice::Prune: beam must be >= 0");
+  auto out = std::make_shared<Lattice>();
+  out->arc_begin.push_back(0);
+  const LatticeBestPath b = BestPath(gs, as);
+  int st = b.status;
+  std::vector<float> e1, e2;
+  if ((st & KHG_LAT_SUCCEEDED) && !Backward(gs, as, &e1, &e2)) st = KHG_LAT_EPS_LOOP;
+  if (status) *status = st;
+  if (!(st & KHG_LAT_SUCCEEDED)) return out;
+  const float INF = std::numeric_limits<float>::infinity();
+  const int N = NumStates();
+  const std::vector<float>&d1 = b.alpha1, &d2 = b.alpha2;
+  const float best = b.f1 + b.f2;
+  const float limit = best + beam;
+  // the best path: its states, and per state the arc it leaves by
+  std::vector<int32_t> path_arc((size_t)N, -1);
+  std::vector<char> on((size_t)N, 0);
+  on[(size_t)start] = 1; on[(size_t)b.final_state] = 1;
+  {
+    int n = start;
+    for (int a : b.arcs) { path_arc[(size_t)n] = a; on[(size_t)n] = 1; n = nextstate[(size_t)a]; on[(size_t)n] = 1; }
+  }
+  std::vector<int32_t> newid((size_t)N, -1);
+  int kept = 0;
+  for (int s = 0; s < N; ++s) {
+    bool k = on[(size_t)s] != 0;
+    if (!k && d1[(size_t)s] != INF && e1[(size_t)s] != INF) {
+      const float t1 = d1[(size_t)s] + e1[(size_t)s], t2 = d2[(size_t)s] + e2[(size_t)s];
+      const float tot = t1 + t2;
+      k = tot <= limit;
+    }
+    if (k) newid[(size_t)s] = kept++;
+  }
+  out->arc_begin.clear();
+  for (int s = 0; s < N; ++s) {
+    if (newid[(size_t)s] < 0) continue;
+    out->frame.push_back(frame[(size_t)s]); out->graph_state.push_back(graph_state[(size_t)s]); out->tot_cost.push_back(tot_cost[(size_t)s]);
+    out->extra_cost.push_back(extra_cost[(size_t)s]); out->final_cost.push_back(final_cost[(size_t)s]);
+    out->arc_begin.push_back((int32_t)out->ilabel.size());
+    for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) {
+      const int k = nextstate[(size_t)a];
+      if (newid[(size_t)k] < 0) continue;
+      const float w1 = gs * graph_cost[(size_t)a], w2 = ilabel[(size_t)a] != 0 ? as * acoustic_cost[(size_t)a] : 0.0f;
+      const float p1 = d1[(size_t)s] + w1, p2 = d2[(size_t)s] + w2;
+      const float t1 = p1 + e1[(size_t)k], t2 = p2 + e2[(size_t)k];
+      const float tot = t1 + t2;
+      if (!(tot <= limit) && path_arc[(size_t)s] != a) continue;
+      out->ilabel.push_back(ilabel[(size_t)a]); out->olabel.push_back(olabel[(size_t)a]); out->graph_cost.push_back(graph_cost[(size_t)a]);
+      out->acoustic_cost.push_back(acoustic_cost[(size_t)a]); out->nextstate.push_back(newid[(size_t)k]);
+    }
+  }
+  out->arc_begin.push_back((int32_t)out->ilabel.size());
+  out->start = newid[(size_t)start];
   return out;
 }
 

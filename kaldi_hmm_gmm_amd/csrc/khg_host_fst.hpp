@@ -99,6 +99,18 @@ struct LinearLattice {
   bool GetLinearSymbolSequence(std::vector<int>* ilabels, std::vector<int>* olabels, LatticeWeight* total) const;
 };
 
+// Lattice::BestPath: KHG_LAT_* status (SUCCEEDED, NO_PATH, EPS_LOOP); the path's non-zero ilabels and olabels, its lattice arcs, its two
+// float sums taken left to right from One() with the final weight last (v1, v2), the final state and its forward pair plus final weight
+// (f1, f2), and the forward pairs / back-pointers of every state
+struct LatticeBestPath {
+  int status = 0;
+  std::vector<int32_t> ali, words, arcs;
+  float v1 = 0.0f, v2 = 0.0f, f1 = 0.0f, f2 = 0.0f;
+  int final_state = -1;
+  std::vector<float> alpha1, alpha2;
+  std::vector<int32_t> bp;
+};
+
 // The fst::VectorFst<LatticeArc> LatticeSimpleDecoder::GetRawLattice builds (csrc/lattice-simple-decoder.cc:654-735), as the flat arrays
 // khg_lattices_download hands back: a state per surviving token, numbered by frame, then by graph state (:684-690); state s owns arcs
 // arc_begin[s] .. arc_begin[s + 1], one per surviving forward link in the order of the graph's arcs in its state (:700-722); the last
@@ -124,12 +136,22 @@ class Lattice {
   // first, then epsilon in-links in Jacobi rounds; a state takes its in-links ordered by (source state, arc) and changes only on a
   // strictly better LatticeWeight; the final state is the lowest among exact ties.  Distances are float sums, left to right, as in
   // the kernel.  Every arc of the path is kept (epsilons too).  An empty lattice, or none of its final states reached: start == -1.
-  LinearLattice ShortestPath() const;
+  // The same under scales: every arc weighs (fl(graph_scale * graph_cost), fl(acoustic_scale * acoustic_cost)), a final
+  // state (fl(graph_scale * final_cost), 0); at (1, 1) the products are exact.  The linear lattice carries the scaled weights.
+  LinearLattice ShortestPath(float graph_scale = 1.0f, float acoustic_scale = 1.0f) const;
+  // What khg_lattices_best_path gives for one lattice and one scale pair; nothing throws on a negative epsilon cycle (KHG_LAT_EPS_LOOP)
+  LatticeBestPath BestPath(float graph_scale = 1.0f, float acoustic_scale = 1.0f) const;
+  // lattice-prune under scales (what khg_lattices_prune gives): the states and arcs whose best path through them is within `beam` of the
+  // best path (sums in the association order of DESIGN.md 7e), plus the best path itself; states and arcs keep their order, costs
+  // stay unscaled.  No reachable final state, or a negative epsilon cycle: an empty lattice; *status the KHG_LAT_* bits.
+  std::shared_ptr<Lattice> Prune(float beam, float graph_scale = 1.0f, float acoustic_scale = 1.0f, int* status = nullptr) const;
   // Kaldi's text form of a lattice: "src dst ilabel olabel graph,acoustic" per arc, "state graph,acoustic" per final state
   std::string ToText() const;
 
  private:
   void Check(int s) const { KHG_REQUIRE(s >= 0 && s < NumStates(), "Lattice: bad state"); }
+  bool Forward(float gs, float as, std::vector<float>* d1, std::vector<float>* d2, std::vector<int32_t>* bp) const;
+  bool Backward(float gs, float as, std::vector<float>* e1, std::vector<float>* e2) const;
 };
 
 // GetRawLattice for a batch (the data-parallel lattice-simple decoder, khg_decode_lattice_simple_raw): what DecodeLatticeSimpleBatch
@@ -140,6 +162,15 @@ std::vector<LatticeResult> GetRawLatticeSimpleBatch(const AmDiagGmm& am, const T
                                                     const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool return_scores,
                                                     int scratch_per_frame, std::vector<std::shared_ptr<Lattice>>* lattices,
                                                     double* seconds = nullptr);
+
+// every utterance's lattice of a khg_lattices handle, downloaded (khg_lattices_download)
+std::vector<std::shared_ptr<Lattice>> DownloadLattices(khg_ctx* ctx, const khg_lattices* h);
+// The same decode that keeps the batch's raw lattices on the device: *lattices is the khg_lattices handle (the caller frees it with
+// khg_lattices_destroy), on the default context; nothing is downloaded.
+std::vector<LatticeResult> GetRawLatticeSimpleDeviceBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& graphs,
+                                                          const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                          const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool return_scores,
+                                                          int scratch_per_frame, khg_lattices** lattices);
 
 // python/csrc/faster-decoder.cc:33-53 on the GPU path: Decode runs K1 + K2 for the utterance of a DecodableAmDiagGmmScaled (any other
 // DecodableInterface: its sampled scores + K2, AlignDecodable above) with the options' beam / max_active / min_active / beam_delta /

@@ -10,6 +10,7 @@
 #include "khg_k2_lattice.hip.inc"
 #include "khg_k2_lattice_simple.hip.inc"
 #include "khg_k2_lattice_raw.hip.inc"
+#include "khg_k2_lattice_ops.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // K2
@@ -532,12 +533,17 @@ struct khg_lattices {
   std::vector<LatChunk> chunks;
   int32_t* start_d = nullptr;                    // [U]
   int64_t bytes = 0;
+  // what the operations on a handle need (khg_lattices_best_path / _prune), made at the first of them: state_off | arc_off on the
+  // device, the frame of every utterance's last state as offsets (the layout of an alignment)
+  int64_t* off_d = nullptr;                      // [2 * (U + 1)]
+  std::vector<int64_t> ali_off;                  // [U + 1]
 };
 
 extern "C" int khg_lattices_destroy(khg_lattices* l) {
   if (!l) return KHG_OK;
   for (LatChunk& c : l->chunks) if (c.buf) (void)hipFree(c.buf);
   if (l->start_d) (void)hipFree(l->start_d);
+  if (l->off_d) (void)hipFree(l->off_d);
   delete l;
   return KHG_OK;
 }
@@ -770,4 +776,343 @@ extern "C" int khg_decode_lattice_simple_raw(khg_ctx* ctx, const khg_tm* tm, khg
   if (!out) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple_raw: out is NULL");
   *out = nullptr;
   return decode_lattice_simple_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, err_frame_h, out);
+}
+
+// ------------------------------------------------------------------------------------------
+// K2O: operations on device-resident lattices (khg_k2_lattice_ops.hip.inc)
+namespace {
+struct LatFree { void operator()(khg_lattices* l) const { (void)khg_lattices_destroy(l); } };
+struct DevBlocks {
+  std::vector<void*> p;
+  ~DevBlocks() { for (void* q : p) if (q) (void)hipFree(q); }
+  template <class T>
+  int alloc(int64_t count, T** out) {
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, (size_t)std::max<int64_t>(count * (int64_t)sizeof(T), 16)));
+    p.push_back(q);
+    *out = static_cast<T*>(q);
+    return KHG_OK;
+  }
+};
+const int64_t kLatOpsLds = 48 << 10;        // an utterance's lattice is staged into LDS up to this many bytes
+
+void lat_chunk_layout(LatChunk* ch, int64_t* total) {
+  int64_t o = 0;
+  auto take = [&](int64_t cnt) { const int64_t r = o; o += (4 * cnt + 255) & ~int64_t(255); return r; };
+  for (int k = 0; k < 6; ++k) ch->st[k] = take(ch->ns);
+  for (int k = 0; k < 5; ++k) ch->ar[k] = take(ch->na);
+  *total = o;
+}
+void lat_chunk_args(const khg_lattices* l, const LatChunk& c, LoArgs* p) {
+  p->st_frame = reinterpret_cast<const int32_t*>(c.buf + c.st[0]); p->st_gstate = reinterpret_cast<const int32_t*>(c.buf + c.st[1]);
+  p->st_tot = reinterpret_cast<const float*>(c.buf + c.st[2]); p->st_extra = reinterpret_cast<const float*>(c.buf + c.st[3]);
+  p->st_final = reinterpret_cast<const float*>(c.buf + c.st[4]); p->st_arc_begin = reinterpret_cast<const int32_t*>(c.buf + c.st[5]);
+  p->arc_ilabel = reinterpret_cast<const int32_t*>(c.buf + c.ar[0]); p->arc_olabel = reinterpret_cast<const int32_t*>(c.buf + c.ar[1]);
+  p->arc_g = reinterpret_cast<const float*>(c.buf + c.ar[2]); p->arc_ac = reinterpret_cast<const float*>(c.buf + c.ar[3]);
+  p->arc_next = reinterpret_cast<const int32_t*>(c.buf + c.ar[4]);
+  p->start = l->start_d; p->state_off = l->off_d; p->arc_off = l->off_d + l->U + 1;
+  p->s_base = l->state_off[(size_t)c.u0]; p->a_base = l->arc_off[(size_t)c.u0];
+  p->u0 = c.u0; p->n = c.n; p->U = l->U;
+}
+// the dynamic LDS a launch over chunk c asks for: the largest lattice of the chunk that still fits
+int lat_chunk_lds(const khg_ctx* ctx, const khg_lattices* l, const LatChunk& c) {
+  if (ctx->opt[KHG_OPT_LAT_OPS_LDS] == 1) return 0;
+  int64_t best = 0;
+  for (int u = c.u0; u < c.u0 + c.n; ++u) {
+    const int64_t need = 4 * (3 * (l->state_off[(size_t)u + 1] - l->state_off[(size_t)u]) + 4 * (l->arc_off[(size_t)u + 1] - l->arc_off[(size_t)u]));
+    if (need <= kLatOpsLds) best = std::max(best, need);
+  }
+  return (int)best;
+}
+// the offsets on the device and the alignment layout, once per handle
+int lat_meta(khg_ctx* ctx, khg_lattices* l) {
+  if (l->off_d || l->U == 0) { if (l->ali_off.empty()) l->ali_off.assign((size_t)l->U + 1, 0); return KHG_OK; }
+  const size_t U = (size_t)l->U;
+  int64_t* off_d = nullptr;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&off_d), 16 * (U + 1)));
+  l->off_d = off_d;
+  l->bytes += 16 * (int64_t)(U + 1);
+  HIPCHK(hipMemcpyAsync(off_d, l->state_off.data(), 8 * (U + 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(off_d + U + 1, l->arc_off.data(), 8 * (U + 1), hipMemcpyHostToDevice, ctx->stream));
+  DevBlocks dv;
+  int32_t* t_d = nullptr;
+  int rc = dv.alloc((int64_t)U, &t_d);
+  if (rc) return rc;
+  for (const LatChunk& c : l->chunks) {
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    KHG_LAUNCH(ctx, k2_lattice_ops_last_frame, dim3((unsigned)((c.n + LO_NT - 1) / LO_NT)), dim3(LO_NT), 0, ctx->stream, p, t_d);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<int32_t> t(U);
+  HIPCHK(hipMemcpyAsync(t.data(), t_d, 4 * U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  l->ali_off.assign(U + 1, 0);
+  for (size_t u = 0; u < U; ++u) l->ali_off[u + 1] = l->ali_off[u] + std::max(t[u], 0);
+  return KHG_OK;
+}
+bool bad_scale(float x) { return !(x >= 0.0f) || x == std::numeric_limits<float>::infinity(); }
+}  // namespace
+
+extern "C" int khg_lattices_validate(int32_t n_utt, const int64_t* state_off, const int64_t* arc_off, const int32_t* frame, const int32_t* graph_state,
+                                     const float* tot_cost, const float* extra_cost, const float* final_cost, const int32_t* arc_begin,
+                                     const int32_t* ilabel, const int32_t* olabel, const float* graph_cost, const float* acoustic_cost,
+                                     const int32_t* nextstate, const int32_t* start) {
+  if (n_utt < 0 || !state_off || !arc_off || state_off[0] != 0 || arc_off[0] != 0)
+    return khg_set_error(KHG_E_ARG, "khg_lattices_upload: bad arguments (offsets start at 0)");
+  const int64_t NS = state_off[n_utt], NA = arc_off[n_utt];
+  if ((NS > 0 && (!frame || !graph_state || !tot_cost || !extra_cost || !final_cost || !arc_begin)) ||
+      (NA > 0 && (!ilabel || !olabel || !graph_cost || !acoustic_cost || !nextstate)) || (n_utt > 0 && !start))
+    return khg_set_error(KHG_E_ARG, "khg_lattices_upload: bad arguments (an array is NULL)");
+  for (int u = 0; u < n_utt; ++u) {
+    const std::string who = "khg_lattices_upload: utterance " + std::to_string(u) + ": ";
+    const int64_t s0 = state_off[u], a0 = arc_off[u], N = state_off[u + 1] - s0, A = arc_off[u + 1] - a0;
+    if (N < 0 || A < 0 || N > INT32_MAX || A > INT32_MAX) return khg_set_error(KHG_E_ARG, who + "state_off / arc_off must not decrease (and stay below 2^31 per utterance)");
+    if (N == 0) {
+      if (A != 0) return khg_set_error(KHG_E_ARG, who + "arcs without states");
+      if (start[u] != -1) return khg_set_error(KHG_E_ARG, who + "start out of range (an empty lattice has start -1)");
+      continue;
+    }
+    if (arc_begin[s0] != 0) return khg_set_error(KHG_E_ARG, who + "arc_begin must run from 0 to the number of arcs");
+    for (int64_t s = 0; s < N; ++s) {
+      const int64_t end = s + 1 < N ? arc_begin[s0 + s + 1] : A;
+      if (arc_begin[s0 + s] > end) return khg_set_error(KHG_E_ARG, who + "arc_begin not monotone");
+      if (frame[s0 + s] < 0 || (s > 0 && frame[s0 + s] < frame[s0 + s - 1])) return khg_set_error(KHG_E_ARG, who + "states must be ordered by frame");
+    }
+    if (start[u] < 0 || start[u] >= N) return khg_set_error(KHG_E_ARG, who + "start out of range");
+    if (frame[s0 + start[u]] != 0) return khg_set_error(KHG_E_ARG, who + "start must be on frame 0");
+    for (int64_t s = 0; s < N; ++s) {
+      const int64_t end = s + 1 < N ? arc_begin[s0 + s + 1] : A;
+      for (int64_t a = arc_begin[s0 + s]; a < end; ++a) {
+        const int32_t k = nextstate[a0 + a];
+        if (k < 0 || k >= N) return khg_set_error(KHG_E_ARG, who + "nextstate out of range");
+        if (ilabel[a0 + a] != 0 && frame[s0 + k] != frame[s0 + s] + 1)
+          return khg_set_error(KHG_E_ARG, who + "an emitting arc must go from frame f to frame f + 1 (arc " + std::to_string(a) + ")");
+        if (ilabel[a0 + a] == 0 && frame[s0 + k] != frame[s0 + s])
+          return khg_set_error(KHG_E_ARG, who + "an epsilon arc must stay in its frame (arc " + std::to_string(a) + ")");
+      }
+    }
+  }
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_num_utts(const khg_lattices* l, int32_t* n_utt) {
+  if (!l || !n_utt) return khg_set_error(KHG_E_ARG, "khg_lattices_num_utts: bad arguments");
+  *n_utt = l->U;
+  return KHG_OK;
+}
+extern "C" int khg_lattices_ali_layout(khg_ctx* ctx, const khg_lattices* lc, int64_t* ali_off_h) {
+  if (ctx_dead(ctx) || !lc || !ali_off_h) return khg_set_error(KHG_E_ARG, "khg_lattices_ali_layout: bad arguments");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (rc) return rc;
+  std::copy(l->ali_off.begin(), l->ali_off.end(), ali_off_h);
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_upload(khg_ctx* ctx, int32_t n_utt, const int64_t* state_off, const int64_t* arc_off, const int32_t* frame,
+                                   const int32_t* graph_state, const float* tot_cost, const float* extra_cost, const float* final_cost,
+                                   const int32_t* arc_begin, const int32_t* ilabel, const int32_t* olabel, const float* graph_cost,
+                                   const float* acoustic_cost, const int32_t* nextstate, const int32_t* start, khg_lattices** out) {
+  if (ctx_dead(ctx) || !out) return khg_set_error(KHG_E_ARG, "khg_lattices_upload: bad arguments");
+  *out = nullptr;
+  int rc = khg_lattices_validate(n_utt, state_off, arc_off, frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin, ilabel, olabel,
+                                 graph_cost, acoustic_cost, nextstate, start);
+  if (rc) return rc;
+  std::unique_ptr<khg_lattices, LatFree> l(new khg_lattices);
+  l->U = n_utt;
+  l->state_off.assign(state_off, state_off + n_utt + 1);
+  l->arc_off.assign(arc_off, arc_off + n_utt + 1);
+  if (n_utt == 0) { *out = l.release(); return KHG_OK; }
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&l->start_d), 4 * (size_t)n_utt));
+  l->bytes += 4 * (int64_t)n_utt;
+  LatChunk ch;
+  ch.u0 = 0; ch.n = n_utt; ch.ns = state_off[n_utt]; ch.na = arc_off[n_utt];
+  int64_t total = 0;
+  lat_chunk_layout(&ch, &total);
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&ch.buf), (size_t)std::max<int64_t>(total, 16)));
+  l->chunks.push_back(ch);
+  l->bytes += total;
+  rc = arena_flush(ctx);
+  if (rc) return rc;
+  const void* st_h[6] = {frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin};
+  const void* ar_h[5] = {ilabel, olabel, graph_cost, acoustic_cost, nextstate};
+  for (int k = 0; k < 6; ++k) if (ch.ns) HIPCHK(hipMemcpyAsync(ch.buf + ch.st[k], st_h[k], 4 * (size_t)ch.ns, hipMemcpyHostToDevice, ctx->stream));
+  for (int k = 0; k < 5; ++k) if (ch.na) HIPCHK(hipMemcpyAsync(ch.buf + ch.ar[k], ar_h[k], 4 * (size_t)ch.na, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(l->start_d, start, 4 * (size_t)n_utt, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));        // the host arrays are the caller's again
+  *out = l.release();
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_best_path(khg_ctx* ctx, const khg_lattices* lc, int32_t n_scales, const float* graph_scale, const float* acoustic_scale,
+                                      int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap, float* weight_h, int32_t* status_h) {
+  if (ctx_dead(ctx) || !lc || n_scales < 1 || !graph_scale || !acoustic_scale) return khg_set_error(KHG_E_ARG, "khg_lattices_best_path: bad arguments");
+  for (int k = 0; k < n_scales; ++k)
+    if (bad_scale(graph_scale[k]) || bad_scale(acoustic_scale[k]))
+      return khg_set_error(KHG_E_ARG, "khg_lattices_best_path: scale pair " + std::to_string(k) + ": graph_scale and acoustic_scale must be finite and >= 0");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U, K = n_scales;
+  if (words_off_h) std::fill(words_off_h, words_off_h + (int64_t)K * U + 1, 0);
+  if (U == 0) return KHG_OK;
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (rc) return rc;
+  const int64_t KU = (int64_t)K * U, AT = l->ali_off[(size_t)U];
+  DevBlocks dv;
+  int32_t *ali_d, *nw_d, *status_d, *packed_d;
+  float *weight_d, *gs_d, *as_d;
+  int64_t *ali_off_d, *woff_d;
+  if ((rc = dv.alloc(std::max<int64_t>((int64_t)K * AT, 1), &ali_d)) || (rc = dv.alloc(KU, &nw_d)) || (rc = dv.alloc(KU, &status_d)) ||
+      (rc = dv.alloc(2 * KU, &weight_d)) || (rc = dv.alloc(K, &gs_d)) || (rc = dv.alloc(K, &as_d)) || (rc = dv.alloc(U + 1, &ali_off_d)) ||
+      (rc = dv.alloc(KU + 1, &woff_d)))
+    return rc;
+  HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>((int64_t)K * AT, 1), ctx->stream));
+  HIPCHK(hipMemcpyAsync(gs_d, graph_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(as_d, acoustic_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  std::vector<LoArgs> pcs;
+  for (const LatChunk& c : l->chunks) {
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    p.lds_bytes = lat_chunk_lds(ctx, l, c);
+    p.K = K; p.gs = gs_d; p.as = as_d; p.ali = ali_d; p.ali_off = ali_off_d; p.ali_total = AT;
+    p.nwords = nw_d; p.weight = weight_d; p.status = status_d;
+    const int64_t cells = std::max<int64_t>(c.ns * K, 1);
+    if ((rc = dv.alloc(cells, &p.d1)) || (rc = dv.alloc(cells, &p.d2)) || (rc = dv.alloc(cells, &p.n1)) || (rc = dv.alloc(cells, &p.n2)) ||
+        (rc = dv.alloc(cells, &p.bp)) || (rc = dv.alloc(cells, &p.words)))
+      return rc;
+    {
+      KernelTimer kt(ctx, "k2_lattice_best_path");
+      KHG_LAUNCH(ctx, k2_lattice_best_path, dim3((unsigned)c.n, (unsigned)((K + LO_NT - 1) / LO_NT)), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    pcs.push_back(p);
+  }
+  // the words, packed on the device: a scan of the counts, one synchronisation to size the block, the copy
+  std::vector<int64_t> woff((size_t)KU + 1, 0);
+  std::vector<int32_t> packed, st((size_t)KU);
+  if (words_h && words_off_h) {
+    {
+      KernelTimer kt(ctx, "k2_lattice_ops_words");
+      KHG_LAUNCH(ctx, k2_lattice_ops_scan, dim3(1), dim3(64), 0, ctx->stream, nw_d, woff_d, KU);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(woff.data(), woff_d, 8 * ((size_t)KU + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const int64_t NW = woff[(size_t)KU];
+    if ((rc = dv.alloc(std::max<int64_t>(NW, 1), &packed_d))) return rc;
+    if (NW > 0) {
+      KernelTimer kt(ctx, "k2_lattice_ops_words");
+      for (const LoArgs& p : pcs)
+        KHG_LAUNCH(ctx, k2_lattice_ops_pack_words, dim3((unsigned)p.n, (unsigned)std::min(K, 64)), dim3(LO_NT), 0, ctx->stream, p, woff_d, packed_d);
+      HIPCHK(hipGetLastError());
+      packed.resize((size_t)NW);
+      HIPCHK(hipMemcpyAsync(packed.data(), packed_d, 4 * (size_t)NW, hipMemcpyDeviceToHost, ctx->stream));
+    }
+  }
+  if (ali_h && AT) HIPCHK(hipMemcpyAsync(ali_h, ali_d, 4 * (size_t)((int64_t)K * AT), hipMemcpyDeviceToHost, ctx->stream));
+  if (weight_h) HIPCHK(hipMemcpyAsync(weight_h, weight_d, 8 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
+  rc = check_err_flag(ctx, "khg_lattices_best_path");     // synchronises
+  if (rc) return rc;
+  if (words_h && words_off_h) {
+    int64_t o = 0;
+    for (int64_t i = 0; i < KU; ++i) {
+      words_off_h[i] = o;
+      int64_t n = (st[(size_t)i] & KHG_LAT_SUCCEEDED) ? woff[(size_t)i + 1] - woff[(size_t)i] : 0;
+      if (o + n > words_cap) { st[(size_t)i] = KHG_LAT_WORDS; n = 0; }      // the path's words do not fit: none of them
+      std::copy(packed.begin() + woff[(size_t)i], packed.begin() + woff[(size_t)i] + n, words_h + o);
+      o += n;
+    }
+    words_off_h[KU] = o;
+  }
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_prune(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, float beam, int32_t* status_h,
+                                  khg_lattices** out) {
+  if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, "khg_lattices_prune: bad arguments");
+  *out = nullptr;
+  if (bad_scale(graph_scale) || bad_scale(acoustic_scale))
+    return khg_set_error(KHG_E_ARG, "khg_lattices_prune: graph_scale and acoustic_scale must be finite and >= 0");
+  if (!(beam >= 0.0f)) return khg_set_error(KHG_E_ARG, "khg_lattices_prune: beam must be >= 0 (+inf allowed)");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  std::unique_ptr<khg_lattices, LatFree> res(new khg_lattices);
+  res->U = U;
+  res->state_off.assign((size_t)U + 1, 0);
+  res->arc_off.assign((size_t)U + 1, 0);
+  if (U == 0) { *out = res.release(); return KHG_OK; }
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (rc) return rc;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&res->start_d), 4 * (size_t)U));
+  res->bytes += 4 * (int64_t)U;
+  DevBlocks dv;
+  int32_t* status_d;
+  if ((rc = dv.alloc(U, &status_d))) return rc;
+  std::vector<int64_t> off_h;
+  for (const LatChunk& c : l->chunks) {
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    p.lds_bytes = lat_chunk_lds(ctx, l, c);
+    p.K = 1; p.gs1 = graph_scale; p.as1 = acoustic_scale; p.beam = beam; p.status = status_d; p.o_start = res->start_d;
+    const int64_t cells = std::max<int64_t>(c.ns, 1);
+    if ((rc = dv.alloc(cells, &p.d1)) || (rc = dv.alloc(cells, &p.d2)) || (rc = dv.alloc(cells, &p.n1)) || (rc = dv.alloc(cells, &p.n2)) ||
+        (rc = dv.alloc(cells, &p.e1)) || (rc = dv.alloc(cells, &p.e2)) || (rc = dv.alloc(cells, &p.bp)) || (rc = dv.alloc(cells, &p.pn)) ||
+        (rc = dv.alloc(cells, &p.newid)) || (rc = dv.alloc(cells, &p.nab)) || (rc = dv.alloc(c.n, &p.limit)) ||
+        (rc = dv.alloc(2 * (int64_t)c.n, &p.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.utt_off)))
+      return rc;
+    {
+      KernelTimer kt(ctx, "k2_lattice_prune_mark");
+      KHG_LAUNCH(ctx, k2_lattice_prune_mark, dim3((unsigned)c.n), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    {
+      KernelTimer kt(ctx, "k2_lattice_prune_scan");
+      KHG_LAUNCH(ctx, k2_lattice_prune_scan, dim3(1), dim3(64), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    off_h.assign(2 * ((size_t)c.n + 1), 0);
+    HIPCHK(hipMemcpyAsync(off_h.data(), p.utt_off, 16 * ((size_t)c.n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));        // the one synchronisation that sizes the output
+    LatChunk ch;
+    ch.u0 = c.u0; ch.n = c.n; ch.ns = off_h[(size_t)c.n]; ch.na = off_h[2 * (size_t)c.n + 1];
+    for (int b = 0; b < c.n; ++b) {
+      res->state_off[(size_t)c.u0 + b + 1] = res->state_off[(size_t)c.u0 + b] + (off_h[(size_t)b + 1] - off_h[(size_t)b]);
+      res->arc_off[(size_t)c.u0 + b + 1] = res->arc_off[(size_t)c.u0 + b] + (off_h[(size_t)c.n + 2 + b] - off_h[(size_t)c.n + 1 + b]);
+    }
+    int64_t total = 0;
+    lat_chunk_layout(&ch, &total);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&ch.buf), (size_t)std::max<int64_t>(total, 16)));
+    res->chunks.push_back(ch);
+    res->bytes += total;
+    p.o_frame = reinterpret_cast<int32_t*>(ch.buf + ch.st[0]); p.o_gstate = reinterpret_cast<int32_t*>(ch.buf + ch.st[1]);
+    p.o_tot = reinterpret_cast<float*>(ch.buf + ch.st[2]); p.o_extra = reinterpret_cast<float*>(ch.buf + ch.st[3]);
+    p.o_final = reinterpret_cast<float*>(ch.buf + ch.st[4]); p.o_arc_begin = reinterpret_cast<int32_t*>(ch.buf + ch.st[5]);
+    p.o_ilabel = reinterpret_cast<int32_t*>(ch.buf + ch.ar[0]); p.o_olabel = reinterpret_cast<int32_t*>(ch.buf + ch.ar[1]);
+    p.o_g = reinterpret_cast<float*>(ch.buf + ch.ar[2]); p.o_ac = reinterpret_cast<float*>(ch.buf + ch.ar[3]);
+    p.o_next = reinterpret_cast<int32_t*>(ch.buf + ch.ar[4]);
+    int64_t max_n = 0;
+    for (int b = 0; b < c.n; ++b) max_n = std::max(max_n, l->state_off[(size_t)c.u0 + b + 1] - l->state_off[(size_t)c.u0 + b]);
+    const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_n + LO_NT - 1) / LO_NT, std::max<int64_t>(1, 4096 / c.n)));
+    {
+      KernelTimer kt(ctx, "k2_lattice_prune_fill");
+      KHG_LAUNCH(ctx, k2_lattice_prune_fill, dim3((unsigned)c.n, gy), dim3(LO_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  std::vector<int32_t> st((size_t)U);
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  rc = check_err_flag(ctx, "khg_lattices_prune");     // synchronises: the scratch goes with `dv`
+  if (rc) return rc;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  *out = res.release();
+  return KHG_OK;
 }

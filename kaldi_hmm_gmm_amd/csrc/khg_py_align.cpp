@@ -6,6 +6,7 @@
 #include <pybind11/stl.h>
 
 #include "khg_host_fst.hpp"
+#include "khg_py_lattices.hpp"
 
 namespace py = pybind11;
 using namespace khg;
@@ -255,6 +256,47 @@ std::vector<T> VecOf(py::object o) {
   Arr<T> a = o.cast<Arr<T>>();
   return std::vector<T>(a.data(), a.data() + a.size());
 }
+// a list of Lattice as the flat arrays of khg_lattices_upload; ctx == nullptr: the checks alone
+khg_lattices* UploadLattices(khg_ctx* ctx, const std::vector<std::shared_ptr<Lattice>>& lats) {
+  const int U = (int)lats.size();
+  std::vector<int64_t> so((size_t)U + 1, 0), ao((size_t)U + 1, 0);
+  std::vector<int32_t> frame, gstate, abeg, il, ol, ns, start;
+  std::vector<float> tot, extra, fin, gc, ac;
+  for (int u = 0; u < U; ++u) {
+    if (!lats[(size_t)u]) throw Error("DeviceLattices.from_lattices: lattice " + std::to_string(u) + " is None");
+    const Lattice& l = *lats[(size_t)u];
+    so[(size_t)u + 1] = so[(size_t)u] + l.NumStates();
+    ao[(size_t)u + 1] = ao[(size_t)u] + l.NumArcs();
+    frame.insert(frame.end(), l.frame.begin(), l.frame.end()); gstate.insert(gstate.end(), l.graph_state.begin(), l.graph_state.end());
+    tot.insert(tot.end(), l.tot_cost.begin(), l.tot_cost.end()); extra.insert(extra.end(), l.extra_cost.begin(), l.extra_cost.end());
+    fin.insert(fin.end(), l.final_cost.begin(), l.final_cost.end());
+    abeg.insert(abeg.end(), l.arc_begin.begin(), l.arc_begin.begin() + l.NumStates());
+    il.insert(il.end(), l.ilabel.begin(), l.ilabel.end()); ol.insert(ol.end(), l.olabel.begin(), l.olabel.end());
+    gc.insert(gc.end(), l.graph_cost.begin(), l.graph_cost.end()); ac.insert(ac.end(), l.acoustic_cost.begin(), l.acoustic_cost.end());
+    ns.insert(ns.end(), l.nextstate.begin(), l.nextstate.end());
+    start.push_back(l.NumStates() ? l.start : kNoStateId);
+  }
+  for (auto* v : {&frame, &gstate, &abeg, &il, &ol, &ns, &start}) v->push_back(0);      // (never a NULL array)
+  for (auto* v : {&tot, &extra, &fin, &gc, &ac}) v->push_back(0.0f);
+  khg_lattices* h = nullptr;
+  if (!ctx) {
+    CApi(khg_lattices_validate(U, so.data(), ao.data(), frame.data(), gstate.data(), tot.data(), extra.data(), fin.data(), abeg.data(), il.data(),
+                               ol.data(), gc.data(), ac.data(), ns.data(), start.data()));
+    return nullptr;
+  }
+  py::gil_scoped_release nogil;
+  CApi(khg_lattices_upload(ctx, U, so.data(), ao.data(), frame.data(), gstate.data(), tot.data(), extra.data(), fin.data(), abeg.data(), il.data(),
+                           ol.data(), gc.data(), ac.data(), ns.data(), start.data(), &h));
+  return h;
+}
+std::pair<std::vector<int64_t>, std::vector<int64_t>> LatSizes(PyDeviceLattices& d) {
+  if (!d.h) throw Error("DeviceLattices: closed");
+  int32_t U = 0;
+  CApi(khg_lattices_num_utts(d.h, &U));
+  std::vector<int64_t> so((size_t)U + 1), ao((size_t)U + 1);
+  CApi(khg_lattices_sizes(d.h, so.data(), ao.data()));
+  return {so, ao};
+}
 }  // namespace
 
 void BindLattice(py::module_& m) {
@@ -289,7 +331,22 @@ void BindLattice(py::module_& m) {
       .def("num_arcs", [](const Lattice& l, int s) { return l.NumArcs(s); }, py::arg("state"))
       .def("arcs", &Lattice::Arcs, py::arg("state"))
       .def("final", &Lattice::Final, py::arg("state"))
-      .def("shortest_path", &Lattice::ShortestPath)
+      .def("shortest_path", &Lattice::ShortestPath, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      // what DeviceLattices.best_path gives for this lattice and one scale pair: status (KHG_LAT_* bits), ali, words, weight (v1, v2)
+      .def("best_path", [](const Lattice& l, float gs, float as) {
+        const LatticeBestPath b = l.BestPath(gs, as);
+        py::dict d;
+        d["status"] = b.status; d["ali"] = py::cast(b.ali); d["words"] = py::cast(b.words); d["weight"] = py::make_tuple(b.v1, b.v2);
+        d["arcs"] = py::cast(b.arcs);
+        return d;
+      }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      .def("prune", [](const Lattice& l, float beam, float gs, float as) { return l.Prune(beam, gs, as); }, py::arg("beam"),
+           py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      .def("prune_with_status", [](const Lattice& l, float beam, float gs, float as) {
+        int st = 0;
+        std::shared_ptr<Lattice> r = l.Prune(beam, gs, as, &st);
+        return py::make_tuple(r, st);
+      }, py::arg("beam"), py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       .def("to_text", &Lattice::ToText)
       .def("__str__", &Lattice::ToText)
       .def_property_readonly("frame", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.frame, l.frame.size()); })
@@ -332,6 +389,99 @@ void BindLattice(py::module_& m) {
     return py::make_tuple(out, t);
   }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"),
      py::arg("scratch_per_frame") = 0, py::arg("return_scores") = false, py::arg("return_times") = false);
+
+  // DeviceLattices: the raw lattices of a batch resident on the device (a khg_lattices handle) and the operations on them
+  py::class_<PyDeviceLattices, std::shared_ptr<PyDeviceLattices>>(m, "DeviceLattices")
+      .def_static("from_lattices", [](std::vector<std::shared_ptr<Lattice>> lats, py::object ctx) {
+        auto d = std::make_shared<PyDeviceLattices>();
+        d->ctx_obj = ctx;
+        d->ctx = ctx.is_none() ? DefaultCtx() : reinterpret_cast<khg_ctx*>(ctx.attr("h").cast<uintptr_t>());
+        d->h = UploadLattices(d->ctx, lats);
+        return d;
+      }, py::arg("lattices"), py::arg("ctx") = py::none())
+      // the host-only half of from_lattices: raises what khg_lattices_upload would refuse
+      .def_static("validate", [](std::vector<std::shared_ptr<Lattice>> lats) { (void)UploadLattices(nullptr, lats); }, py::arg("lattices"))
+      .def_property_readonly("num_utts", [](PyDeviceLattices& d) { return (int)LatSizes(d).first.size() - 1; })
+      .def_property_readonly("state_off", [](PyDeviceLattices& d) { return Vec1(LatSizes(d).first); })
+      .def_property_readonly("arc_off", [](PyDeviceLattices& d) { return Vec1(LatSizes(d).second); })
+      .def_property_readonly("device_bytes", [](PyDeviceLattices& d) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        int64_t b = 0;
+        CApi(khg_lattices_device_bytes(d.h, &b));
+        return b;
+      })
+      // of the prune that made this handle (None otherwise): KHG_LAT_* bits per utterance
+      .def_property_readonly("status", [](PyDeviceLattices& d) -> py::object { if (d.status.empty()) return py::none(); return Vec1(d.status); })
+      .def("best_path", [](PyDeviceLattices& d, Arr<float> gs, Arr<float> as) {
+        const auto so = LatSizes(d);
+        if (gs.ndim() != 1 || as.ndim() != 1 || gs.shape(0) != as.shape(0) || gs.shape(0) < 1)
+          throw Error("DeviceLattices.best_path: graph_scales and acoustic_scales are two lists of the same length >= 1");
+        const int U = (int)so.first.size() - 1, K = (int)gs.shape(0);
+        std::vector<int32_t> st((size_t)K * U);
+        std::vector<int64_t> woff((size_t)K * U + 1);
+        std::vector<float> w(2 * (size_t)K * U);
+        const int64_t wcap = (int64_t)K * so.first.back() + 1;       // a path visits a state once
+        std::unique_ptr<int32_t[]> words(new int32_t[(size_t)wcap]);        // (not zeroed: only the packed words are read)
+        // the alignment layout: the frame of every utterance's last state (a path has one transition-id per frame)
+        std::vector<int64_t> aoff((size_t)U + 1, 0);
+        CApi(khg_lattices_ali_layout(d.ctx, d.h, aoff.data()));
+        const int64_t at = aoff.back();
+        Arr<int32_t> ali({(py::ssize_t)K, (py::ssize_t)at});
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_best_path(d.ctx, d.h, K, gs.data(), as.data(), ali.mutable_data(), words.get(), woff.data(), wcap, w.data(), st.data()));
+        }
+        Arr<int32_t> wa1({(py::ssize_t)woff.back()});
+        if (woff.back() > 0) std::memcpy(wa1.mutable_data(), words.get(), sizeof(int32_t) * (size_t)woff.back());
+        py::dict r;
+        r["ali"] = ali; r["words"] = wa1; r["words_off"] = Vec1(woff); r["status"] = Vec1(st); r["ali_off"] = Vec1(aoff);
+        Arr<float> wa({(py::ssize_t)K * U, (py::ssize_t)2});
+        if (!w.empty()) std::memcpy(wa.mutable_data(), w.data(), sizeof(float) * w.size());
+        r["weight"] = wa;
+        return r;
+      }, py::arg("graph_scales"), py::arg("acoustic_scales"))
+      .def("prune", [](PyDeviceLattices& d, float beam, float gs, float as) {
+        const int U = (int)LatSizes(d).first.size() - 1;
+        auto r = std::make_shared<PyDeviceLattices>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj;
+        r->status.assign((size_t)std::max(U, 1), 0);
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_prune(d.ctx, d.h, gs, as, beam, r->status.data(), &r->h));
+        }
+        r->status.resize((size_t)U);
+        return r;
+      }, py::arg("beam"), py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      .def("download", [](PyDeviceLattices& d) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        std::vector<std::shared_ptr<Lattice>> out;
+        {
+          py::gil_scoped_release nogil;
+          out = DownloadLattices(d.ctx, d.h);
+        }
+        return out;
+      })
+      .def("close", &PyDeviceLattices::close);
+
+  // get_raw_lattice_simple_device_batch(am, tm, fsts, feats_list, config, acoustic_scale, scratch_per_frame=0) -> (one dict per
+  // utterance with decode_lattice_simple_batch's keys, DeviceLattices): get_raw_lattice_simple_batch that keeps the lattices on the device
+  m.def("get_raw_lattice_simple_device_batch", [](std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, py::object fsts, py::list feats_list,
+                                                  const LatticeSimpleDecoderConfig& config, float acoustic_scale, int scratch_per_frame) {
+    BatchArgs b(*am, fsts, feats_list, "get_raw_lattice_simple_device_batch");
+    std::vector<LatticeResult> rs;
+    auto d = std::make_shared<PyDeviceLattices>();
+    d->ctx = DefaultCtx();
+    d->ctx_obj = py::none();
+    {
+      const GraphsCsr csr = b.Csr();
+      py::gil_scoped_release nogil;
+      rs = GetRawLatticeSimpleDeviceBatch(*am, *tm, csr, b.fp, b.nf, config, acoustic_scale, false, scratch_per_frame, &d->h);
+    }
+    py::list out;
+    for (size_t u = 0; u < rs.size(); ++u) out.append(LatticeSimpleToDict(rs[u], b.nf[u], false));
+    return py::make_tuple(out, d);
+  }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"),
+     py::arg("scratch_per_frame") = 0);
 
   // python/csrc/determinize-lattice-pruned.cc:13-25
   py::class_<DeterminizeLatticePhonePrunedOptions>(m, "DeterminizeLatticePhonePrunedOptions")

@@ -1,0 +1,26 @@
+// DeviceLattices of the Python surface: owns a khg_lattices handle (the raw lattices of a batch, resident on the device) and the
+// context its operations run on.  Shared by khg_pybind.cpp (UtteranceSet.raw_lattices_simple_device) and khg_py_align.cpp (the class
+// itself, get_raw_lattice_simple_device_batch).
+#pragma once
+#include <pybind11/numpy.h>
+#include <pybind11/pybind11.h>
+
+#include <vector>
+
+#include "../../include/khg_hip.h"
+
+namespace khg {
+
+struct PyDeviceLattices {
+  khg_lattices* h = nullptr;
+  khg_ctx* ctx = nullptr;
+  pybind11::object ctx_obj;          // keeps a Python Context alive (None: the default context)
+  std::vector<int32_t> status;       // of the prune that made it (empty otherwise)
+  PyDeviceLattices() = default;
+  PyDeviceLattices(const PyDeviceLattices&) = delete;
+  PyDeviceLattices& operator=(const PyDeviceLattices&) = delete;
+  ~PyDeviceLattices() { close(); }
+  void close() { if (h) { khg_lattices_destroy(h); h = nullptr; } }
+};
+
+}  // namespace khg

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/khg_hip.h"
+#include "khg_py_lattices.hpp"
 
 namespace py = pybind11;
 
@@ -77,7 +78,7 @@ struct KContext {
   static int opt_id(const py::object& o) {
     if (py::isinstance<py::int_>(o)) return o.cast<int>();
     static const char* names[KHG_OPT_COUNT] = {"k1_form", "k1_order", "k1_nf", "k1p_ts", "k1_interleave", "k1_dbg", "k2_inorder", "k2_ks", "k2_serial",
-                                               "k2_prof", "k3_bucket", "k3_form", "k3_phase_b", "k3_ny", "debug", "k3_phase_a", "k2_split", "k2s_hub"};
+                                               "k2_prof", "k3_bucket", "k3_form", "k3_phase_b", "k3_ny", "debug", "k3_phase_a", "k2_split", "k2s_hub", "lat_ops_lds"};
     const std::string n = o.cast<std::string>();
     for (int i = 0; i < KHG_OPT_COUNT; ++i) if (n == names[i]) return i;
     if (n == "scratch_bytes") return KHG_INFO_SCRATCH_BYTES;       // read-only
@@ -572,6 +573,30 @@ struct KUtts {
     d["download_s"] = std::chrono::duration<double>(t2 - t1).count();
     return d;
   }
+  // raw_lattice_simple that keeps the lattices on the device: decode_lattice_simple's outputs plus "lattices", a DeviceLattices on this
+  // set's context (best_path / prune / download there); nothing of the lattices is downloaded
+  py::dict raw_lattices_simple_device(KTransitions& tm, float beam, float lattice_beam, int32_t prune_interval, float prune_scale, float acoustic_scale,
+                                      int32_t scratch_per_frame) {
+    khg_lattice_simple_config c;
+    khg_lattice_simple_config_default(&c);
+    c.beam = beam; c.lattice_beam = lattice_beam; c.prune_interval = prune_interval; c.prune_scale = prune_scale; c.acoustic_scale = acoustic_scale;
+    c.scratch_per_frame = scratch_per_frame;
+    const int64_t N = frame_off.at(n_utt), wcap = 2 * N + 1024 * (int64_t)n_utt + 1024 + state_total;
+    Arr<int32_t> ali({(py::ssize_t)(N > 0 ? N : 1)}), words({(py::ssize_t)wcap}), status({(py::ssize_t)n_utt}), ef({(py::ssize_t)n_utt});
+    Arr<int64_t> woff({(py::ssize_t)n_utt + 1});
+    Arr<double> like({(py::ssize_t)n_utt});
+    auto lat = std::make_shared<khg::PyDeviceLattices>();
+    lat->ctx = ctx->h; lat->ctx_obj = ctx_obj;
+    Check(NoGil([&] { return khg_decode_lattice_simple_raw(ctx->h, tm.h, h, &c, ali.mutable_data(), words.mutable_data(), woff.mutable_data(), wcap,
+                                                           like.mutable_data(), status.mutable_data(), ef.mutable_data(), &lat->h); }));
+    py::dict d;
+    d["ali"] = py::array(ali)[py::slice(0, N, 1)];
+    d["like"] = like; d["status"] = status; d["error_frame"] = ef;
+    d["words"] = py::array(words)[py::slice(0, woff.at(n_utt), 1)];
+    d["words_off"] = woff;
+    d["lattices"] = lat;
+    return d;
+  }
   py::object align(KTransitions& tm, float beam, float retry_beam, float acoustic_scale, bool careful, int64_t max_active, int min_active,
                    float beam_delta, float hash_ratio, py::object download) {
     khg_align_config c;
@@ -708,6 +733,8 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
            py::arg("prune_interval") = 25, py::arg("prune_scale") = 0.1f, py::arg("acoustic_scale") = 1.0f, py::arg("allow_partial") = true,
            py::arg("scratch_per_frame") = 0)
       .def("raw_lattice_simple", &KUtts::raw_lattice_simple, py::arg("tm"), py::arg("beam") = 16.0f, py::arg("lattice_beam") = 10.0f,
+           py::arg("prune_interval") = 25, py::arg("prune_scale") = 0.1f, py::arg("acoustic_scale") = 1.0f, py::arg("scratch_per_frame") = 0)
+      .def("raw_lattices_simple_device", &KUtts::raw_lattices_simple_device, py::arg("tm"), py::arg("beam") = 16.0f, py::arg("lattice_beam") = 10.0f,
            py::arg("prune_interval") = 25, py::arg("prune_scale") = 0.1f, py::arg("acoustic_scale") = 1.0f, py::arg("scratch_per_frame") = 0)
       .def("upload_ali", &KUtts::upload_ali).def("download_ali", &KUtts::download_ali)
       .def("acc_stats", &KUtts::acc_stats, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f)

@@ -27,7 +27,14 @@ every repetition: get_raw_lattice_simple_batch (UtteranceSet.raw_lattice_simple 
 arcs and bytes per utterance, the download apart from the decode call (seconds, bytes, effective GB/s), and -- from one more pass of
 each call under the context's kernel timing -- the device time of k2_lattice_simple and of the emission kernels (count, scans, fill).
 
-Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices]
+--sweep LO:HI and --prune-beam B (next to --lattices) keep the batch's lattices on the device (get_raw_lattice_simple_device_batch,
+UtteranceSet.raw_lattices_simple_device) and time, over max(--reps, 5) repetitions after a warm-up: the best path at every integer
+language-model weight w in LO..HI (graph_scale 1, acoustic_scale 1 / w) in ONE DeviceLattices.best_path call, one pair alone, and
+DeviceLattices.prune(B) at the middle weight -- beside what gives the same answers without them: the download of every lattice, the
+Lattice objects and a host ShortestPath per weight and utterance.  Kernel milliseconds come from one more pass under the context's
+kernel timing; the report says how many of the host's paths the device's equal.
+
+Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4]
        python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
@@ -146,6 +153,62 @@ def emission_summary(k_old, k_new):
     emit = sum(v for k, v in k_new.items() if k.startswith("k2_lattice_raw"))
     return {"old_call_kernels_ms": k_old, "raw_call_kernels_ms": k_new, "k2_lattice_simple_ms": k_old.get("k2_lattice_simple"),
             "emission_ms": emit, "emission_over_decoder": emit / k_old["k2_lattice_simple"] if k_old.get("k2_lattice_simple") else None}
+
+
+def lattice_ops(ctx, dl, sweep, prune_beam, reps):
+    """The operations on a DeviceLattices handle beside the host loop that gives the same answers -> the report dict."""
+    reps = max(reps, 5)
+    out = {"repetitions": reps, "device_bytes": int(dl.device_bytes), "utterances": int(dl.num_utts)}
+    U = dl.num_utts
+    if sweep:
+        lo, hi = (int(x) for x in sweep.split(":"))
+        ws = np.arange(lo, hi + 1)
+        gs, as_ = np.ones(len(ws), np.float32), (1.0 / ws).astype(np.float32)
+        dl.best_path(gs, as_); dl.best_path(gs[:1], as_[:1])                       # warm-up
+        t_sweep, t_one, t_host, t_dl = [], [], [], []
+        for _ in range(reps):
+            ctx.sync(); t0 = time.time()
+            many = dl.best_path(gs, as_)
+            t_sweep.append(time.time() - t0)
+            t0 = time.time()
+            dl.best_path(gs[len(ws) // 2: len(ws) // 2 + 1], as_[len(ws) // 2: len(ws) // 2 + 1])
+            t_one.append(time.time() - t0)
+            t0 = time.time()
+            lats = dl.download()                                                    # the download and the Lattice objects
+            t_dl.append(time.time() - t0)
+            host = [[L.best_path(1.0, float(a)) for L in lats] for a in as_]
+            t_host.append(time.time() - t0)
+        same = 0
+        ao, wo = many["ali_off"], many["words_off"]
+        for k in range(len(ws)):
+            for u in range(U):
+                o = k * U + u
+                h = host[k][u]
+                ok = h["status"] == int(many["status"][o]) and h["words"] == many["words"][wo[o]: wo[o + 1]].tolist() \
+                    and np.asarray(h["weight"], np.float32).tobytes() == many["weight"][o].tobytes()
+                same += bool(ok and (h["status"] != 1 or h["ali"] == many["ali"][k, ao[u]: ao[u + 1]].tolist()))
+        k_sweep = kernel_ms(ctx, lambda: dl.best_path(gs, as_))
+        k_one = kernel_ms(ctx, lambda: dl.best_path(gs[:1], as_[:1]))
+        paths = [tuple(many["ali"][k].tolist()) for k in range(len(ws))]
+        out["sweep"] = {"weights": [int(w) for w in ws], "best_path_call": med(t_sweep), "one_pair_call": med(t_one),
+                        "host_download_and_lattices": med(t_dl), "host_download_lattices_and_shortest_paths": med(t_host),
+                        "host_over_device": float(np.median(t_host) / np.median(t_sweep)), "kernels_ms": k_sweep, "one_pair_kernels_ms": k_one,
+                        "entries": len(ws) * U, "entries_equal_to_host": same, "distinct_alignment_rows": len(set(paths)),
+                        "succeeded": int((many["status"] == 1).sum())}
+    if prune_beam is not None:
+        a = float(np.float32(1.0 / ((lo + hi) // 2))) if sweep else 0.1
+        dl.prune(prune_beam, 1.0, a).close()
+        t_p = []
+        for _ in range(reps):
+            ctx.sync(); t0 = time.time()
+            P = dl.prune(prune_beam, 1.0, a)
+            t_p.append(time.time() - t0)
+            kept = (int(P.state_off[-1]), int(P.arc_off[-1]))
+            P.close()
+        k_p = kernel_ms(ctx, lambda: dl.prune(prune_beam, 1.0, a).close())
+        out["prune"] = {"beam": prune_beam, "acoustic_scale": a, "prune_call": med(t_p), "kernels_ms": k_p, "kernels_total_ms": sum(k_p.values()),
+                        "states_before": int(dl.state_off[-1]), "arcs_before": int(dl.arc_off[-1]), "states_after": kept[0], "arcs_after": kept[1]}
+    return out
 
 
 def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
@@ -281,6 +344,10 @@ def shared_graph_main(args):
             finally:
                 ctx.set_option("k2s_hub", out["hub_default"])
             entry["lattices"].update(emission_summary(k_old, k_new), hub=h)
+            if args.sweep or args.prune_beam is not None:
+                d = sh.raw_lattices_simple_device(dtm, beam=13.0, lattice_beam=6.0, acoustic_scale=0.1)
+                entry["lattice_ops"] = lattice_ops(ctx, d["lattices"], args.sweep, args.prune_beam, args.reps)
+                d["lattices"].close()
         if args.check > 0:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
             import lattice_faster_ref as fref
@@ -325,7 +392,11 @@ def main():
     ap.add_argument("--decoder", choices=("faster", "simple"), default="faster")
     ap.add_argument("--check", type=int, default=0)
     ap.add_argument("--lattices", action="store_true", help="also time the raw-lattice call (simple decoder) and report the lattices")
+    ap.add_argument("--sweep", default=None, metavar="LO:HI", help="with --lattices: best paths at the integer LM weights LO..HI in one call")
+    ap.add_argument("--prune-beam", type=float, default=None, help="with --lattices: prune the resident lattices to this beam")
     args = ap.parse_args()
+    if (args.sweep or args.prune_beam is not None) and not args.lattices:
+        ap.error("--sweep / --prune-beam need --lattices")
     if args.lattices and not (args.shared_graph or args.decoder == "simple"):
         ap.error("--lattices needs --decoder simple or --shared-graph")
     if args.shared_graph or args.yesno:
@@ -386,6 +457,10 @@ def main():
             k_new = kernel_ms(ctx, lambda: khg.get_raw_lattice_simple_batch(am, tm, fsts, feats, scfg, 0.1))
             lat.update(emission_summary(k_old, k_new))
             out["lattices"] = lat
+            if args.sweep or args.prune_beam is not None:
+                _, dl = khg.get_raw_lattice_simple_device_batch(am, tm, fsts, feats, scfg, 0.1)
+                out["lattice_ops"] = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps)
+                dl.close()
         if args.check > 0:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
             import lattice_simple_ref as ref
