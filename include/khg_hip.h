@@ -434,6 +434,11 @@ int khg_lattices_upload(khg_ctx *ctx, int32_t n_utt, const int64_t *state_off_h,
  * ali_off_h[u + 1] - ali_off_h[u] = the frame of its last state (0 for an empty lattice) entries of every pair's row */
 int khg_lattices_num_utts(const khg_lattices *l, int32_t *n_utt);
 int khg_lattices_ali_layout(khg_ctx *ctx, const khg_lattices *l, int64_t *ali_off_h);
+/* the launches (chunks of at most 4 GiB of decoder scratch) the handle's lattices were emitted in: a handle from khg_lattices_upload
+ * has one (none when it has no utterance), a pruned handle its input's.  first_utt_h[n_chunks + 1]: the first utterance of every
+ * chunk, n_utt last.  Every operation runs once per chunk.  Read-only, no device work. */
+int khg_lattices_num_chunks(const khg_lattices *l, int32_t *n_chunks);
+int khg_lattices_chunk_utts(const khg_lattices *l, int32_t *first_utt_h);
 /* lattice-scale | lattice-best-path for n_scales (graph_scale, acoustic_scale) pairs in one call (finite, >= 0; else KHG_E_ARG): an
  * arc weighs (fl(graph_scale * graph_cost), fl(acoustic_scale * acoustic_cost)), a final state (fl(graph_scale * final_cost), 0), and
  * the best path is OpenFst ShortestPath by the decoder kernel's tie rule (float, no contraction; at (1, 1) the decoder's own path).

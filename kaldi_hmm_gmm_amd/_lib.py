@@ -160,6 +160,8 @@ SIGNATURES = {
                                       c_f32p, c_i32p, c_i32p, C.POINTER(vp)]),
     "khg_lattices_num_utts": (C.c_int, [vp, c_i32p]),
     "khg_lattices_ali_layout": (C.c_int, [vp, vp, c_i64p]),
+    "khg_lattices_num_chunks": (C.c_int, [vp, c_i32p]),
+    "khg_lattices_chunk_utts": (C.c_int, [vp, c_i32p]),
     "khg_lattices_best_path": (C.c_int, [vp, vp, C.c_int32, c_f32p, c_f32p, c_i32p, c_i32p, c_i64p, C.c_int64, c_f32p, c_i32p]),
     "khg_lattices_prune": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_float, c_i32p, C.POINTER(vp)]),
     "khg_ali_download": (C.c_int, [vp, vp, c_i32p]),

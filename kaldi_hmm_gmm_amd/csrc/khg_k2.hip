@@ -902,6 +902,17 @@ extern "C" int khg_lattices_num_utts(const khg_lattices* l, int32_t* n_utt) {
   *n_utt = l->U;
   return KHG_OK;
 }
+extern "C" int khg_lattices_num_chunks(const khg_lattices* l, int32_t* n_chunks) {
+  if (!l || !n_chunks) return khg_set_error(KHG_E_ARG, "khg_lattices_num_chunks: bad arguments");
+  *n_chunks = (int32_t)l->chunks.size();
+  return KHG_OK;
+}
+extern "C" int khg_lattices_chunk_utts(const khg_lattices* l, int32_t* first_utt) {
+  if (!l || !first_utt) return khg_set_error(KHG_E_ARG, "khg_lattices_chunk_utts: bad arguments");
+  for (size_t c = 0; c < l->chunks.size(); ++c) first_utt[c] = l->chunks[c].u0;
+  first_utt[l->chunks.size()] = l->chunks.empty() ? 0 : l->U;
+  return KHG_OK;
+}
 extern "C" int khg_lattices_ali_layout(khg_ctx* ctx, const khg_lattices* lc, int64_t* ali_off_h) {
   if (ctx_dead(ctx) || !lc || !ali_off_h) return khg_set_error(KHG_E_ARG, "khg_lattices_ali_layout: bad arguments");
   khg_lattices* l = const_cast<khg_lattices*>(lc);

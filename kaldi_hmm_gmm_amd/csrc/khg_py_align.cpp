@@ -404,6 +404,21 @@ void BindLattice(py::module_& m) {
       .def_property_readonly("num_utts", [](PyDeviceLattices& d) { return (int)LatSizes(d).first.size() - 1; })
       .def_property_readonly("state_off", [](PyDeviceLattices& d) { return Vec1(LatSizes(d).first); })
       .def_property_readonly("arc_off", [](PyDeviceLattices& d) { return Vec1(LatSizes(d).second); })
+      // the decoder launches (chunks of <= 4 GiB of scratch) the lattices were emitted in, and the first utterance of each (n_utt last)
+      .def_property_readonly("num_chunks", [](PyDeviceLattices& d) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        int32_t n = 0;
+        CApi(khg_lattices_num_chunks(d.h, &n));
+        return (int)n;
+      })
+      .def_property_readonly("chunk_off", [](PyDeviceLattices& d) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        int32_t n = 0;
+        CApi(khg_lattices_num_chunks(d.h, &n));
+        std::vector<int32_t> first((size_t)n + 1, 0);
+        CApi(khg_lattices_chunk_utts(d.h, first.data()));
+        return std::vector<int>(first.begin(), first.end());
+      })
       .def_property_readonly("device_bytes", [](PyDeviceLattices& d) {
         if (!d.h) throw Error("DeviceLattices: closed");
         int64_t b = 0;

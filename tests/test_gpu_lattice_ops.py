@@ -15,6 +15,7 @@ import lattice_ops_ref as ops  # noqa: E402
 import lattice_simple_ref as ref  # noqa: E402
 import test_shared_graph_cpu as sg  # noqa: E402
 from test_gpu_lattice_raw import OLD_KEYS, _feats, _fst, setup  # noqa: E402,F401
+from lattice_geometry_cases import _wide_lattice  # noqa: E402
 from test_lattice_ops_cpu import hand_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -303,23 +304,6 @@ def test_hand_built_lattices_through_from_lattices(setup):
     dl.close()
     with pytest.raises(RuntimeError, match="closed"):
         dl.best_path([1.0], [1.0])
-
-
-def _wide_lattice(rng, T, W, fan):
-    """T + 1 frames of W states; every state has `fan` emitting arcs into the next frame and an epsilon arc to its right-hand
-    neighbour (weights positive): far more arcs than the LDS-staged form takes"""
-    states = [(f, np.inf if f < T else float(rng.uniform(0, 1))) for f in range(T + 1) for _ in range(W)]
-    arcs = []
-    for f in range(T + 1):
-        for i in range(W):
-            s = f * W + i
-            if f < T:
-                for j in rng.choice(W, fan, replace=False):
-                    arcs.append((s, int(rng.integers(1, 50)), int(rng.integers(0, 3)), float(rng.uniform(0, 3)), float(rng.uniform(0, 9)), (f + 1) * W + int(j)))
-            if i + 1 < W:
-                arcs.append((s, 0, int(rng.integers(0, 2)) * 7, float(rng.uniform(0.1, 1)), 0.0, s + 1))
-    from test_lattice_ops_cpu import _hand
-    return _hand(states, arcs)
 
 
 def test_lds_staged_and_hbm_forms_agree(setup):
