@@ -14,10 +14,10 @@ decode_utterance_lattice_simple and decode_lattice_simple_batch.  The word loop 
 LatticeSimpleDecoder stops at InitDecoding ("no surviving tokens"), so that decoder gets a copy of it with a zero-weight
 input-epsilon self-loop on every state: no path's weight changes.
 
---decoder simple --sweep 7:17 also keeps the batch's raw lattices on the device (get_raw_lattice_simple_device_batch) and prints the
-WER at every integer language-model weight w in 7..17 (graph_scale 1, acoustic_scale 1 / w; the lattices hold costs at acoustic
-scale 0.1, i.e. weight 10 is acoustic_scale 1.0 here) from that ONE decode: one DeviceLattices.best_path call, no lattice leaves the
-device.
+--sweep 7:17 also keeps the batch's raw lattices on the device (get_raw_lattice_faster_device_batch: the word loop as compiled,
+nothing added; with --decoder simple get_raw_lattice_simple_device_batch on the copy with self-loops) and prints the WER at every
+integer language-model weight w in 7..17 (graph_scale 1, acoustic_scale 1 / w; the lattices hold costs at acoustic scale 0.1, i.e.
+weight 10 is acoustic_scale 1.0 here) from that ONE decode: one DeviceLattices.best_path call, no lattice leaves the device.
 
 Usage: python examples/decode_lattice_synthetic.py [--utts 200] [--iters 80] [--decoder faster|simple] [--sweep 7:17]
 """
@@ -41,10 +41,8 @@ def main():
     ap.add_argument("--dim", type=int, default=23)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--decoder", choices=("faster", "simple"), default="faster")
-    ap.add_argument("--sweep", default=None, metavar="LO:HI", help="with --decoder simple: WER at every integer LM weight, from one decode")
+    ap.add_argument("--sweep", default=None, metavar="LO:HI", help="WER at every integer LM weight, from one decode")
     args = ap.parse_args()
-    if args.sweep and args.decoder != "simple":
-        ap.error("--sweep needs --decoder simple (the raw lattice is the lattice-simple decoder's)")
     tm, tree, am, lexicon, test_utts = dx.train(args)
     # decode.py:112,135: transition_scale 1.0, self_loop_scale 1.0 go into the graph
     gc = TrainingGraphCompiler(tm, tree, lexicon, sil_phone=dx.tr.SIL, sil_prob=0.5,
@@ -83,7 +81,8 @@ def main():
         lo, hi = (int(x) for x in args.sweep.split(":"))
         ws = np.arange(lo, hi + 1)
         # the lattices were decoded at acoustic scale 0.1 = LM weight 10: weight w re-weights their acoustic costs by 10 / w
-        _, lats = khg.get_raw_lattice_simple_device_batch(am, tm, graph, [u[2] for u in test_utts], config, 0.1)
+        raw_device_batch = khg.get_raw_lattice_simple_device_batch if args.decoder == "simple" else khg.get_raw_lattice_faster_device_batch
+        _, lats = raw_device_batch(am, tm, graph, [u[2] for u in test_utts], config, 0.1)
         bp = lats.best_path(np.ones(len(ws), np.float32), (10.0 / ws).astype(np.float32))
         U = len(test_utts)
         for k, w in enumerate(ws):

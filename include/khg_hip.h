@@ -416,6 +416,29 @@ int khg_lattices_download(khg_ctx *ctx, const khg_lattices *l, int32_t *frame_h,
 int khg_lattices_device_bytes(const khg_lattices *l, int64_t *bytes);
 int khg_lattices_destroy(khg_lattices *l);
 
+/* ---- K2F: the raw lattice of the lattice-faster decoder ------------------------------------------------------------------------- */
+/* khg_decode_lattice_faster (same arguments, same outputs) that also keeps the raw lattice of every utterance in *out: what
+ * LatticeFasterDecoder::GetRawLattice (csrc/lattice-faster-decoder.cc:101-192) builds, the FST whose best path the call returns.  An
+ * ordinary khg_lattices handle (khg_lattices_sizes / _download / _device_bytes / _best_path / _prune / _num_chunks / _chunk_utts):
+ *   states  one per token that survives FinalizeDecoding, numbered by frame, then in TopSortTokens order inside the frame with the
+ *           gaps removed (its unordered_map walked in creation order, its reprocess set in insertion order); each carries frame,
+ *           graph_state (the graph state the token was created for), tot_cost (Token::tot_cost as stored: cost offsets included),
+ *           extra_cost (after the final pruning), final_cost (last frame: final_costs_[tok], +inf without an entry, 0 on every token
+ *           when no final state was reached -- KHG_LAT_PARTIAL with allow_partial; +inf before the last frame) and arc_begin
+ *   arcs    one per surviving forward link, per state in the link list's order (head first: the link made last comes first): ilabel,
+ *           olabel, graph_cost (with the table's trans_cost when one is set), acoustic_cost (fl(link.acoustic_cost -
+ *           cost_offsets[frame]) for an emitting link, 0 for an epsilon link), nextstate
+ *   start   state 0; -1 for an empty lattice
+ * Unlike K2R's, this lattice is not independent of order: it is the one of the order-faithful decoder (HashList order as the
+ * reference's, the two TopSortTokens choices above).  It is acyclic and top-sorted.  An utterance whose status lacks
+ * KHG_LAT_SUCCEEDED has an empty lattice and keeps its status.  Emitted on the device from the decoder's scratch slices while they are
+ * alive, with one more synchronisation per <= 4 GiB launch of slices; the handle's chunks are the first pass's launches (a chunk
+ * holding utterances of the second pass -- scratch_per_frame = 0 -- is gathered on the device from both passes' blocks).  An utterance
+ * whose lattice has more than 2^31 - 1 states or arcs: KHG_E_ARG, naming it.  Free *out with khg_lattices_destroy. */
+int khg_decode_lattice_faster_raw(khg_ctx *ctx, const khg_tm *tm, khg_utts *u, const khg_lattice_faster_config *cfg,
+                                  int32_t *ali_h, int32_t *words_h, int64_t *words_off_h, int64_t words_cap,
+                                  double *like_h, int32_t *status_h, khg_lattices **out);
+
 /* ---- K2O: best path under scales and beam pruning of resident lattices ---------------------------------------------------------- */
 /* A handle from host arrays, in the layout khg_lattices_download writes: state_off_h / arc_off_h [n_utt + 1], the six per-state and
  * five per-arc arrays, start_h[n_utt].  Every utterance is checked (KHG_E_ARG names the utterance and the check): one arc_begin per

@@ -149,6 +149,8 @@ SIGNATURES = {
                                             c_i32p, c_i32p]),
     "khg_decode_lattice_simple_raw": (C.c_int, [vp, vp, vp, C.POINTER(LatticeSimpleConfigC), c_i32p, c_i32p, c_i64p, C.c_int64, c_f64p,
                                                 c_i32p, c_i32p, C.POINTER(vp)]),
+    "khg_decode_lattice_faster_raw": (C.c_int, [vp, vp, vp, C.POINTER(LatticeFasterConfigC), c_i32p, c_i32p, c_i64p, C.c_int64, c_f64p,
+                                                c_i32p, C.POINTER(vp)]),
     "khg_lattices_sizes": (C.c_int, [vp, c_i64p, c_i64p]),
     "khg_lattices_download": (C.c_int, [vp, vp, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p,
                                         c_i32p]),

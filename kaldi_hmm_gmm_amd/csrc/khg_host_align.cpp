@@ -194,7 +194,7 @@ std::vector<AlignResult> AlignBatch(const AmDiagGmm& am, const TransitionModel& 
 
 std::vector<LatticeResult> DecodeLatticeOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
                                               const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial, int scratch_per_frame,
-                                              int64_t total_states) {
+                                              int64_t total_states, khg_lattices** lattices) {
   const int n_utt = (int)frame_off.size() - 1;
   khg_lattice_faster_config c;
   khg_lattice_faster_config_default(&c);
@@ -207,7 +207,11 @@ std::vector<LatticeResult> DecodeLatticeOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts
   std::vector<double> like((size_t)n_utt);
   // words: the C-ABI keeps at most frames + states + 64 per utterance
   std::vector<int32_t> words((size_t)(N + total_states + 64 * (int64_t)n_utt + 16));
-  CApi(khg_decode_lattice_faster(ctx, tm, us, &c, ali.data(), words.data(), woff.data(), (int64_t)words.size(), like.data(), status.data()));
+  if (lattices)
+    CApi(khg_decode_lattice_faster_raw(ctx, tm, us, &c, ali.data(), words.data(), woff.data(), (int64_t)words.size(), like.data(), status.data(),
+                                       lattices));
+  else
+    CApi(khg_decode_lattice_faster(ctx, tm, us, &c, ali.data(), words.data(), woff.data(), (int64_t)words.size(), like.data(), status.data()));
   std::vector<LatticeResult> out((size_t)n_utt);
   for (int u = 0; u < n_utt; ++u) {
     LatticeResult& r = out[(size_t)u];
@@ -414,6 +418,49 @@ std::vector<LatticeResult> GetRawLatticeSimpleDeviceBatch(const AmDiagGmm& am, c
                       [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
                         return DecodeLatticeSimpleOnSet(ctx, dt, us, frame_off, config, acoustic_scale, true, scratch_per_frame,
                                                         BatchStates(g, n_utt), lattices);
+                      });
+}
+
+std::vector<LatticeResult> GetRawLatticeFasterBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g,
+                                                    const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                    const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial,
+                                                    bool return_scores, int scratch_per_frame, std::vector<std::shared_ptr<Lattice>>* lattices,
+                                                    double* seconds) {
+  config.Check();
+  KHG_REQUIRE(lattices != nullptr, "get_raw_lattice_faster_batch: no place for the lattices");
+  for (int64_t T : nframes) KHG_REQUIRE(T > 0, "num_frames > 0 assertion failed");     // GetRawLattice (lattice-faster-decoder.cc:137)
+  const int n_utt = (int)feats.size();
+  lattices->assign((size_t)n_utt, nullptr);
+  struct LatH { khg_lattices* h = nullptr; ~LatH() { if (h) khg_lattices_destroy(h); } } lh;
+  using Clock = std::chrono::steady_clock;
+  return K1ThenDecode(am, tm, g, feats, nframes, return_scores, "get_raw_lattice_faster_batch",
+                      [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
+                        const Clock::time_point t0 = Clock::now();
+                        std::vector<LatticeResult> out = DecodeLatticeOnSet(ctx, dt, us, frame_off, config, acoustic_scale, allow_partial,
+                                                                            scratch_per_frame, BatchStates(g, n_utt), &lh.h);
+                        const Clock::time_point t1 = Clock::now();
+                        *lattices = DownloadLattices(ctx, lh.h);
+                        if (seconds) {
+                          seconds[0] = std::chrono::duration<double>(t1 - t0).count();
+                          seconds[1] = std::chrono::duration<double>(Clock::now() - t1).count();
+                        }
+                        return out;
+                      });
+}
+
+std::vector<LatticeResult> GetRawLatticeFasterDeviceBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& g,
+                                                          const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                          const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial,
+                                                          bool return_scores, int scratch_per_frame, khg_lattices** lattices) {
+  config.Check();
+  KHG_REQUIRE(lattices != nullptr, "get_raw_lattice_faster_device_batch: no place for the lattices");
+  *lattices = nullptr;
+  for (int64_t T : nframes) KHG_REQUIRE(T > 0, "num_frames > 0 assertion failed");
+  const int n_utt = (int)feats.size();
+  return K1ThenDecode(am, tm, g, feats, nframes, return_scores, "get_raw_lattice_faster_device_batch",
+                      [&](khg_ctx* ctx, khg_tm* dt, khg_utts* us, const std::vector<int64_t>& frame_off) {
+                        return DecodeLatticeOnSet(ctx, dt, us, frame_off, config, acoustic_scale, allow_partial, scratch_per_frame,
+                                                  BatchStates(g, n_utt), lattices);
                       });
 }
 

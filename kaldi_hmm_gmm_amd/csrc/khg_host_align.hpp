@@ -181,7 +181,8 @@ std::vector<LatticeResult> DecodeLatticeBatch(const AmDiagGmm& am, const Transit
 // the C-ABI call on a prepared set (scores resident) -> results without scores
 std::vector<LatticeResult> DecodeLatticeOnSet(khg_ctx* ctx, khg_tm* tm, khg_utts* us, const std::vector<int64_t>& frame_off,
                                               const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial, int scratch_per_frame,
-                                              int64_t total_states);
+                                              int64_t total_states, khg_lattices** lattices = nullptr);
+// (lattices: khg_decode_lattice_faster_raw instead, the batch's raw lattices left on the device for the caller to download and destroy)
 
 // DecodeUtteranceLatticeSimple (csrc/decoder-wrappers.cc:142-182) for a batch: K1 as in DecodeLatticeBatch + the data-parallel
 // lattice-simple decoder (khg_decode_lattice_simple).  scratch_per_frame: the most live tokens a frame may hold (0: no limit).

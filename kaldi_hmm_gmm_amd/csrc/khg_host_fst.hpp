@@ -115,6 +115,10 @@ struct LatticeBestPath {
 // khg_lattices_download hands back: a state per surviving token, numbered by frame, then by graph state (:684-690); state s owns arcs
 // arc_begin[s] .. arc_begin[s + 1], one per surviving forward link in the order of the graph's arcs in its state (:700-722); the last
 // frame's final tokens are final with (final_cost, 0) (:723-733).  Which lattice that is (the order-independent one): DESIGN.md 7d.
+// From the lattice-faster decoder (LatticeFasterDecoder::GetRawLattice, csrc/lattice-faster-decoder.cc:101-192) the
+// second numbering rule holds instead: states by frame, then in TopSortTokens order inside the frame with the gaps removed;
+// graph_state is the state the token was created for; a state's arcs follow its forward-link list, head first; without any final
+// state reached every last-frame state is final with (0, 0).  That lattice is acyclic and top-sorted.
 class Lattice {
  public:
   // per state
@@ -171,6 +175,17 @@ std::vector<LatticeResult> GetRawLatticeSimpleDeviceBatch(const AmDiagGmm& am, c
                                                           const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
                                                           const LatticeSimpleDecoderConfig& config, float acoustic_scale, bool return_scores,
                                                           int scratch_per_frame, khg_lattices** lattices);
+
+// The same two for the lattice-faster decoder (khg_decode_lattice_faster_raw): what DecodeLatticeBatch returns plus the raw lattices
+std::vector<LatticeResult> GetRawLatticeFasterBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& graphs,
+                                                    const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                    const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial,
+                                                    bool return_scores, int scratch_per_frame, std::vector<std::shared_ptr<Lattice>>* lattices,
+                                                    double* seconds = nullptr);
+std::vector<LatticeResult> GetRawLatticeFasterDeviceBatch(const AmDiagGmm& am, const TransitionModel& tm, const GraphsCsr& graphs,
+                                                          const std::vector<const float*>& feats, const std::vector<int64_t>& nframes,
+                                                          const LatticeFasterDecoderConfig& config, float acoustic_scale, bool allow_partial,
+                                                          bool return_scores, int scratch_per_frame, khg_lattices** lattices);
 
 // python/csrc/faster-decoder.cc:33-53 on the GPU path: Decode runs K1 + K2 for the utterance of a DecodableAmDiagGmmScaled (any other
 // DecodableInterface: its sampled scores + K2, AlignDecodable above) with the options' beam / max_active / min_active / beam_delta /

@@ -1,7 +1,8 @@
 // kaldi_hmm_gmm_amd/csrc/khg_k2.hip -- C-ABI (include/khg_hip.h): K2, Viterbi forced alignment (khg_align): kernel selection by graph
 // shape, LDS budgets, the exact DP on the main stream and the order-faithful decoder on a side stream; and the lattice decoder
 // (khg_decode_lattice_faster, khg_k2_lattice.hip.inc) and the data-parallel LatticeSimpleDecoder (khg_decode_lattice_simple,
-// khg_k2_lattice_simple.hip.inc) with its raw lattice (khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc).  gfx950 only.
+// khg_k2_lattice_simple.hip.inc), each with its raw lattice (khg_decode_lattice_faster_raw, khg_k2_lattice_faster_raw.hip.inc;
+// khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
 
 #include <memory>
@@ -10,6 +11,7 @@
 #include "khg_k2_lattice.hip.inc"
 #include "khg_k2_lattice_simple.hip.inc"
 #include "khg_k2_lattice_raw.hip.inc"
+#include "khg_k2_lattice_faster_raw.hip.inc"
 #include "khg_k2_lattice_ops.hip.inc"
 
 // ------------------------------------------------------------------------------------------
@@ -360,6 +362,30 @@ extern "C" int khg_ali_download(khg_ctx* ctx, khg_utts* u, int32_t* ali) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The raw lattices of one batch (khg_decode_lattice_simple_raw, khg_decode_lattice_faster_raw): per chunk of scratch slices one exactly-sized
+// device block holding
+// the six per-state and five per-arc arrays of the chunk's utterances, one after the other.
+struct LatChunk {
+  int u0 = 0, n = 0;              // utterances u0 .. u0 + n
+  int64_t ns = 0, na = 0;         // states, arcs
+  unsigned char* buf = nullptr;
+  // byte offsets of the arrays inside buf: frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin | ilabel, olabel, graph_cost,
+  // acoustic_cost, nextstate
+  int64_t st[6] = {0, 0, 0, 0, 0, 0}, ar[5] = {0, 0, 0, 0, 0};
+};
+struct khg_lattices {
+  int U = 0;
+  std::vector<int64_t> state_off, arc_off;       // [U + 1]
+  std::vector<LatChunk> chunks;
+  int32_t* start_d = nullptr;                    // [U]
+  int64_t bytes = 0;
+  // what the operations on a handle need (khg_lattices_best_path / _prune), made at the first of them: state_off | arc_off on the
+  // device, the frame of every utterance's last state as offsets (the layout of an alignment)
+  int64_t* off_d = nullptr;                      // [2 * (U + 1)]
+  std::vector<int64_t> ali_off;                  // [U + 1]
+};
+
+// ------------------------------------------------------------------------------------------
 // K2L: LatticeFasterDecoder (khg_k2_lattice.hip.inc)
 extern "C" void khg_lattice_faster_config_default(khg_lattice_faster_config* c) {
   c->beam = 16.0f; c->max_active = INT32_MAX; c->min_active = 200; c->lattice_beam = 10.0f; c->prune_interval = 25;
@@ -367,16 +393,19 @@ extern "C" void khg_lattice_faster_config_default(khg_lattice_faster_config* c) 
   c->scratch_per_frame = 0;
 }
 
-extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_faster_config* cfg,
-                                         int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
-                                         double* like_h, int32_t* status_h) {
-  if (ctx_dead(ctx) || !tm || !u || !cfg) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: bad arguments");
-  { int rf = utts_foreign_ctx(ctx, u, "khg_decode_lattice_faster"); if (rf) return rf; }
-  if (!u->has_graphs) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: the utterance set has no decoding graphs");
-  if (!u->ll_valid) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: call khg_loglikes first");
+// khg_decode_lattice_faster (lat_out == nullptr: nothing below about lattices runs, and the slices have no lattice rows) and
+// khg_decode_lattice_faster_raw
+static int decode_lattice_faster_impl(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_faster_config* cfg,
+                                      int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                      double* like_h, int32_t* status_h, khg_lattices** lat_out) {
+  const std::string who = lat_out ? "khg_decode_lattice_faster_raw" : "khg_decode_lattice_faster";      // the call the user made
+  if (ctx_dead(ctx) || !tm || !u || !cfg) return khg_set_error(KHG_E_ARG, who + ": bad arguments");
+  { int rf = utts_foreign_ctx(ctx, u, who.c_str()); if (rf) return rf; }
+  if (!u->has_graphs) return khg_set_error(KHG_E_ARG, who + ": the utterance set has no decoding graphs");
+  if (!u->ll_valid) return khg_set_error(KHG_E_ARG, who + ": call khg_loglikes first");
   // khg_loglikes_band leaves upper bounds in the cells past the band: a token of a partial (or pruned-late) path may read any cell
   if (u->ll_mode == 2)
-    return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: the scores come from khg_loglikes_band; call khg_loglikes (every cell) first");
+    return khg_set_error(KHG_E_ARG, who + ": the scores come from khg_loglikes_band; call khg_loglikes (every cell) first");
   // LatticeFasterDecoderConfig::Check (csrc/lattice-faster-decoder.h:99-104)
   if (!(cfg->beam > 0.0f && cfg->max_active > 1 && cfg->lattice_beam > 0.0f && cfg->min_active <= cfg->max_active &&
         cfg->prune_interval > 0 && cfg->beam_delta > 0.0f && cfg->hash_ratio >= 1.0f && cfg->prune_scale > 0.0f && cfg->prune_scale < 1.0f) ||
@@ -386,7 +415,16 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
   if (!rc) rc = k1_band_check(ctx, u);
   if (rc) return rc;
   const int U = u->n_utt;
-  if (U == 0) return KHG_OK;
+  const bool lat = lat_out != nullptr;
+  struct LatFree { void operator()(khg_lattices* l) const { (void)khg_lattices_destroy(l); } };
+  std::unique_ptr<khg_lattices, LatFree> lats;
+  if (lat) {
+    lats.reset(new khg_lattices);
+    lats->U = U;
+    lats->state_off.assign((size_t)U + 1, 0);
+    lats->arc_off.assign((size_t)U + 1, 0);
+  }
+  if (U == 0) { if (lat) *lat_out = lats.release(); return KHG_OK; }
   const int64_t hb = std::max<int64_t>(1000, (int64_t)((float)u->max_states * cfg->hash_ratio)) + 1;
   const int64_t Amax = u->max_inarcs;     // (the kernel lays every slice out with the same arc bound)
   std::vector<int64_t> wcap_off((size_t)U + 1, 0);
@@ -409,6 +447,19 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
       (rc = dalloc(4 * (size_t)U, reinterpret_cast<void**>(&nw_d))) || (rc = dalloc(4 * (size_t)U, reinterpret_cast<void**>(&status_d))) ||
       (rc = dalloc(8 * (size_t)U, reinterpret_cast<void**>(&like_d))) || (rc = dalloc(8 * ((size_t)U + 1), reinterpret_cast<void**>(&woff_d))))
     return rc;
+  // (lattices) what a launch emitted: an exactly-sized block of the utterances list[ch.u0 .. ch.u0 + ch.n), with their offsets inside it;
+  // a block not handed to the handle is freed on the way out
+  struct EmitBlock { LatChunk ch; std::vector<int64_t> so, ao; };
+  struct Blocks {
+    std::vector<EmitBlock> v;
+    ~Blocks() { for (EmitBlock& b : v) if (b.ch.buf) (void)hipFree(b.ch.buf); }
+  } pass1, pass2;
+  int64_t *lat_tot_d = nullptr, *lat_off_d = nullptr;
+  if (lat) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&lats->start_d), 4 * (size_t)U));
+    if ((rc = dalloc(16 * (size_t)U, reinterpret_cast<void**>(&lat_tot_d))) || (rc = dalloc(16 * ((size_t)U + 1), reinterpret_cast<void**>(&lat_off_d))))
+      return rc;
+  }
   rc = arena_flush(ctx);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(woff_d, wcap_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
@@ -426,7 +477,7 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
   a.max_active = cfg->max_active; a.min_active = cfg->min_active; a.prune_interval = cfg->prune_interval; a.allow_partial = cfg->allow_partial ? 1 : 0;
   // One pass over a list of utterances: each gets a scratch slice of `per_frame` tokens / links per frame (0: the automatic size,
   // -1: the whole graph per frame, i.e. an utterance can never run out); slices are grouped into launches of <= 4 GiB of scratch.
-  auto run = [&](const std::vector<int32_t>& list, int64_t per_frame) -> int {
+  auto run = [&](const std::vector<int32_t>& list, int64_t per_frame, Blocks* blocks) -> int {
     const size_t L = list.size();
     std::vector<int32_t> tcap(L), lcap(L);
     std::vector<int64_t> bytes(L);
@@ -436,9 +487,9 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
       const int64_t pt = per_frame > 0 ? per_frame : per_frame < 0 ? S : std::min<int64_t>(S, 256);
       const int64_t pl = per_frame > 0 ? per_frame : per_frame < 0 ? A : std::min<int64_t>(A, 1024);
       const int64_t tc = (T + 1) * pt + (per_frame > 0 ? 0 : S) + 1, lc = (T + 1) * pl + (per_frame > 0 ? 0 : A) + 1;
-      if (tc > INT32_MAX / 2 || lc > INT32_MAX / 2) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: utterance too large for the scratch");
+      if (tc > INT32_MAX / 2 || lc > INT32_MAX / 2) return khg_set_error(KHG_E_ARG, who + ": utterance too large for the scratch");
       tcap[k] = (int32_t)tc; lcap[k] = (int32_t)lc;
-      bytes[k] = (lat_layout(T, S, Amax, hb, tc, lc).total + 255) & ~int64_t(255);
+      bytes[k] = (lat_layout(T, S, Amax, hb, tc, lc, lat).total + 255) & ~int64_t(255);
     }
     const int64_t budget = int64_t(4) << 30;
     std::vector<size_t> cb{0};
@@ -462,28 +513,86 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
     HIPCHK(hipMemcpyAsync(lcap_d, lcap.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(list_d, list.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
     a.scratch = scratch; a.scr_off = scr_off_d; a.tok_cap = tcap_d; a.link_cap = lcap_d; a.list = list_d;
+    std::vector<int64_t> lat_off_h;
     for (size_t c = 0; c + 1 < cb.size(); ++c) {
-      KernelTimer kt(ctx, "k2_lattice_faster");
-      KHG_LAUNCH(ctx, k2_lattice_faster, dim3((unsigned)(cb[c + 1] - cb[c])), dim3(64), 0, ctx->stream, a, (int)cb[c]);
-      HIPCHK(hipGetLastError());
+      if (!lat) {
+        KernelTimer kt(ctx, "k2_lattice_faster");
+        KHG_LAUNCH(ctx, k2_lattice_faster, dim3((unsigned)(cb[c + 1] - cb[c])), dim3(64), 0, ctx->stream, a, (int)cb[c]);
+        HIPCHK(hipGetLastError());
+        continue;
+      }
+      // the launch's lattices, while its slices are alive: the decoder leaves the rows and the totals, one scan over the utterances,
+      // ONE synchronisation to size the output, the fill
+      const int n = (int)(cb[c + 1] - cb[c]), k0 = (int)cb[c];
+      {
+        KernelTimer kt(ctx, "k2_lattice_faster");
+        KHG_LAUNCH(ctx, k2_lattice_faster_lat, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, k0, lat_tot_d);
+        HIPCHK(hipGetLastError());
+      }
+      {
+        LrArgs sp;       // (K2R's scan over a launch's utterances: it reads n and the two arrays only)
+        std::memset(&sp, 0, sizeof(sp));
+        sp.n = n; sp.utt_tot = lat_tot_d; sp.utt_off = lat_off_d;
+        KernelTimer kt(ctx, "k2_lattice_faster_raw_scan");
+        KHG_LAUNCH(ctx, k2_lattice_raw_scan_utts, dim3(1), dim3(64), 0, ctx->stream, sp);
+        HIPCHK(hipGetLastError());
+      }
+      lat_off_h.assign(2 * ((size_t)n + 1), 0);
+      HIPCHK(hipMemcpyAsync(lat_off_h.data(), lat_off_d, 16 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      blocks->v.emplace_back();
+      EmitBlock& eb = blocks->v.back();
+      LatChunk& ch = eb.ch;
+      ch.u0 = k0; ch.n = n; ch.ns = lat_off_h[(size_t)n]; ch.na = lat_off_h[2 * (size_t)n + 1];
+      eb.so.assign(lat_off_h.begin(), lat_off_h.begin() + n + 1);
+      eb.ao.assign(lat_off_h.begin() + n + 1, lat_off_h.end());
+      int64_t max_n = 0;
+      for (int b = 0; b < n; ++b) {
+        const int64_t ns = eb.so[(size_t)b + 1] - eb.so[(size_t)b], na = eb.ao[(size_t)b + 1] - eb.ao[(size_t)b];
+        if (ns > INT32_MAX || na > INT32_MAX)
+          return khg_set_error(KHG_E_ARG, who + ": the lattice of utterance " + std::to_string(list[(size_t)k0 + b]) +
+                                              " has more than 2^31 - 1 states or arcs");
+        max_n = std::max(max_n, ns);
+      }
+      int64_t o = 0;
+      auto take = [&](int64_t cnt) { const int64_t r = o; o += (4 * cnt + 255) & ~int64_t(255); return r; };
+      for (int j = 0; j < 6; ++j) ch.st[j] = take(ch.ns);
+      for (int j = 0; j < 5; ++j) ch.ar[j] = take(ch.na);
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&ch.buf), (size_t)std::max<int64_t>(o, 16)));
+      LfrArgs p;
+      std::memset(&p, 0, sizeof(p));
+      p.a = a; p.n = n; p.utt_off = lat_off_d; p.start_out = lats->start_d;
+      p.st_frame = reinterpret_cast<int32_t*>(ch.buf + ch.st[0]); p.st_gstate = reinterpret_cast<int32_t*>(ch.buf + ch.st[1]);
+      p.st_tot = reinterpret_cast<float*>(ch.buf + ch.st[2]); p.st_extra = reinterpret_cast<float*>(ch.buf + ch.st[3]);
+      p.st_final = reinterpret_cast<float*>(ch.buf + ch.st[4]); p.st_arc_begin = reinterpret_cast<int32_t*>(ch.buf + ch.st[5]);
+      p.arc_ilabel = reinterpret_cast<int32_t*>(ch.buf + ch.ar[0]); p.arc_olabel = reinterpret_cast<int32_t*>(ch.buf + ch.ar[1]);
+      p.arc_g = reinterpret_cast<float*>(ch.buf + ch.ar[2]); p.arc_ac = reinterpret_cast<float*>(ch.buf + ch.ar[3]);
+      p.arc_next = reinterpret_cast<int32_t*>(ch.buf + ch.ar[4]);
+      // state stripes go to workgroups of their own while the launch has few utterances (k2_lattice_prune_fill's rule)
+      const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_n + LFR_NT - 1) / LFR_NT, std::max<int64_t>(1, 4096 / n)));
+      {
+        KernelTimer kt(ctx, "k2_lattice_faster_raw_fill");
+        KHG_LAUNCH(ctx, k2_lattice_faster_raw_fill, dim3((unsigned)n, gy), dim3(LFR_NT), 0, ctx->stream, p, k0);
+        HIPCHK(hipGetLastError());
+      }
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));    // the slices are freed with `dv` or reused by the next pass
     return KHG_OK;
   };
   std::vector<int32_t> all((size_t)U);
   for (int i = 0; i < U; ++i) all[(size_t)i] = i;
-  rc = run(all, cfg->scratch_per_frame);
-  if (!rc) rc = check_err_flag(ctx, "khg_decode_lattice_faster");     // synchronises
+  rc = run(all, cfg->scratch_per_frame, &pass1);
+  if (!rc) rc = check_err_flag(ctx, who.c_str());     // synchronises
   if (rc) return rc;
   std::vector<int32_t> st((size_t)U), nw((size_t)U), w((size_t)std::max<int64_t>(NW, 1));
   HIPCHK(hipMemcpy(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost));
+  std::vector<int32_t> again;
   if (cfg->scratch_per_frame == 0) {
     // the automatic size ran out: those utterances again with room for every state and arc on every frame (a frame never holds more)
-    std::vector<int32_t> again;
     for (int i = 0; i < U; ++i) if (st[(size_t)i] & KHG_LAT_SCRATCH) again.push_back(i);
     if (!again.empty()) {
-      rc = run(again, -1);
-      if (!rc) rc = check_err_flag(ctx, "khg_decode_lattice_faster");
+      rc = run(again, -1, &pass2);
+      if (!rc) rc = check_err_flag(ctx, who.c_str());
       if (rc) return rc;
       HIPCHK(hipMemcpy(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost));
     }
@@ -501,13 +610,118 @@ extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utt
     for (int i = 0; i < U; ++i) {
       words_off_h[i] = o;
       const int64_t n = (st[(size_t)i] & KHG_LAT_SUCCEEDED) ? nw[(size_t)i] : 0;
-      if (o + n > words_cap) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster: words_cap too small");
+      if (o + n > words_cap) return khg_set_error(KHG_E_ARG, who + ": words_cap too small");
       std::copy(w.begin() + wcap_off[(size_t)i], w.begin() + wcap_off[(size_t)i] + n, words_h + o);
       o += n;
     }
     words_off_h[U] = o;
   }
+  if (!lat) return KHG_OK;
+  // The handle: every utterance in utterance order, its chunks the first pass's launches.  Without a second pass the first pass's
+  // blocks are the chunks.  With one, a chunk that holds a re-decoded utterance is rebuilt on the device from the blocks of both
+  // passes (k2_lattice_faster_raw_gather); only offsets travel.
+  // where every utterance's lattice is: block (first pass's, then second pass's), first state / arc there, sizes
+  std::vector<int32_t> src_blk((size_t)U, 0);
+  std::vector<int64_t> src_off(2 * (size_t)U, 0), ns_u((size_t)U, 0), na_u((size_t)U, 0);
+  std::vector<EmitBlock*> blk;
+  for (EmitBlock& b : pass1.v) blk.push_back(&b);
+  for (EmitBlock& b : pass2.v) blk.push_back(&b);
+  std::vector<char> redone((size_t)U, 0);
+  for (int32_t i : again) redone[(size_t)i] = 1;
+  for (size_t j = 0; j < blk.size(); ++j) {
+    const bool second = j >= pass1.v.size();
+    const EmitBlock& e = *blk[j];
+    for (int b = 0; b < e.ch.n; ++b) {
+      const int i = second ? again[(size_t)e.ch.u0 + b] : e.ch.u0 + b;
+      if (!second && redone[(size_t)i]) continue;        // (empty there: the second pass's is the one)
+      src_blk[(size_t)i] = (int32_t)j;
+      src_off[2 * (size_t)i] = e.so[(size_t)b]; src_off[2 * (size_t)i + 1] = e.ao[(size_t)b];
+      ns_u[(size_t)i] = e.so[(size_t)b + 1] - e.so[(size_t)b]; na_u[(size_t)i] = e.ao[(size_t)b + 1] - e.ao[(size_t)b];
+    }
+  }
+  for (int i = 0; i < U; ++i) {
+    lats->state_off[(size_t)i + 1] = lats->state_off[(size_t)i] + ns_u[(size_t)i];
+    lats->arc_off[(size_t)i + 1] = lats->arc_off[(size_t)i] + na_u[(size_t)i];
+  }
+  LfrBlock* blocks_d = nullptr;
+  std::vector<LfrBlock> blocks_h;
+  std::vector<std::vector<int64_t>> dst_off_keep;      // (host sides of copies in flight until the synchronisation below)
+  if (!again.empty()) {
+    for (const EmitBlock* e : blk) {
+      LfrBlock bd;
+      for (int j = 0; j < 6; ++j) bd.st[j] = reinterpret_cast<const int32_t*>(e->ch.buf + e->ch.st[j]);
+      for (int j = 0; j < 5; ++j) bd.ar[j] = reinterpret_cast<const int32_t*>(e->ch.buf + e->ch.ar[j]);
+      blocks_h.push_back(bd);
+    }
+    if ((rc = dalloc(sizeof(LfrBlock) * blocks_h.size(), reinterpret_cast<void**>(&blocks_d)))) return rc;
+    HIPCHK(hipMemcpyAsync(blocks_d, blocks_h.data(), sizeof(LfrBlock) * blocks_h.size(), hipMemcpyHostToDevice, ctx->stream));
+  }
+  lats->bytes += 4 * (int64_t)U;
+  for (EmitBlock& e : pass1.v) {
+    const int u0 = e.ch.u0, n = e.ch.n;
+    bool rebuild = false;
+    for (int b = 0; b < n; ++b) rebuild = rebuild || redone[(size_t)u0 + b];
+    LatChunk ch;
+    ch.u0 = u0; ch.n = n;
+    if (!rebuild) {
+      ch = e.ch;
+      e.ch.buf = nullptr;        // the handle's from here on
+    } else {
+      dst_off_keep.emplace_back(2 * ((size_t)n + 1), 0);
+      std::vector<int64_t>& dst_off = dst_off_keep.back();
+      for (int b = 0; b < n; ++b) {
+        dst_off[(size_t)b + 1] = dst_off[(size_t)b] + ns_u[(size_t)u0 + b];
+        dst_off[(size_t)n + 2 + b] = dst_off[(size_t)n + 1 + b] + na_u[(size_t)u0 + b];
+      }
+      ch.ns = dst_off[(size_t)n]; ch.na = dst_off[2 * (size_t)n + 1];
+      int64_t o = 0;
+      auto take = [&](int64_t cnt) { const int64_t r = o; o += (4 * cnt + 255) & ~int64_t(255); return r; };
+      for (int j = 0; j < 6; ++j) ch.st[j] = take(ch.ns);
+      for (int j = 0; j < 5; ++j) ch.ar[j] = take(ch.na);
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&ch.buf), (size_t)std::max<int64_t>(o, 16)));
+    }
+    lats->chunks.push_back(ch);
+    for (int j = 0; j < 6; ++j) lats->bytes += (4 * ch.ns + 255) & ~int64_t(255);
+    for (int j = 0; j < 5; ++j) lats->bytes += (4 * ch.na + 255) & ~int64_t(255);
+    if (!rebuild) continue;
+    LfrGather g;
+    std::memset(&g, 0, sizeof(g));
+    int32_t* src_blk_d; int64_t *src_off_d, *dst_off_d;
+    if ((rc = dalloc(4 * (size_t)n, reinterpret_cast<void**>(&src_blk_d))) || (rc = dalloc(16 * (size_t)n, reinterpret_cast<void**>(&src_off_d))) ||
+        (rc = dalloc(16 * ((size_t)n + 1), reinterpret_cast<void**>(&dst_off_d))))
+      return rc;
+    HIPCHK(hipMemcpyAsync(src_blk_d, src_blk.data() + u0, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(src_off_d, src_off.data() + 2 * (size_t)u0, 16 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dst_off_d, dst_off_keep.back().data(), 16 * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    g.blocks = blocks_d; g.src_block = src_blk_d; g.src_off = src_off_d; g.dst_off = dst_off_d; g.n = n;
+    for (int j = 0; j < 6; ++j) g.st[j] = reinterpret_cast<int32_t*>(ch.buf + ch.st[j]);
+    for (int j = 0; j < 5; ++j) g.ar[j] = reinterpret_cast<int32_t*>(ch.buf + ch.ar[j]);
+    int64_t max_n = 1;
+    for (int b = 0; b < n; ++b) max_n = std::max(max_n, std::max(ns_u[(size_t)u0 + b], na_u[(size_t)u0 + b]));
+    const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_n + LFR_NT - 1) / LFR_NT, std::max<int64_t>(1, 4096 / n)));
+    KernelTimer kt(ctx, "k2_lattice_faster_raw_gather");
+    KHG_LAUNCH(ctx, k2_lattice_faster_raw_gather, dim3((unsigned)n, gy), dim3(LFR_NT), 0, ctx->stream, g);
+    HIPCHK(hipGetLastError());
+  }
+  if (!again.empty()) {
+    rc = check_err_flag(ctx, who.c_str());     // synchronises: the blocks the chunks were gathered from go now
+    if (rc) return rc;
+  }
+  *lat_out = lats.release();
   return KHG_OK;
+}
+
+extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_faster_config* cfg,
+                                         int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                         double* like_h, int32_t* status_h) {
+  return decode_lattice_faster_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, nullptr);
+}
+extern "C" int khg_decode_lattice_faster_raw(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_faster_config* cfg,
+                                             int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                             double* like_h, int32_t* status_h, khg_lattices** out) {
+  if (!out) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster_raw: out is NULL");
+  *out = nullptr;
+  return decode_lattice_faster_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -516,28 +730,6 @@ extern "C" void khg_lattice_simple_config_default(khg_lattice_simple_config* c) 
   c->beam = 16.0f; c->lattice_beam = 10.0f; c->prune_interval = 25; c->prune_scale = 0.1f; c->acoustic_scale = 1.0f;
   c->allow_partial = 1; c->scratch_per_frame = 0;
 }
-
-// The raw lattices of one batch (khg_decode_lattice_simple_raw): per chunk of scratch slices one exactly-sized device block holding
-// the six per-state and five per-arc arrays of the chunk's utterances, one after the other.
-struct LatChunk {
-  int u0 = 0, n = 0;              // utterances u0 .. u0 + n
-  int64_t ns = 0, na = 0;         // states, arcs
-  unsigned char* buf = nullptr;
-  // byte offsets of the arrays inside buf: frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin | ilabel, olabel, graph_cost,
-  // acoustic_cost, nextstate
-  int64_t st[6] = {0, 0, 0, 0, 0, 0}, ar[5] = {0, 0, 0, 0, 0};
-};
-struct khg_lattices {
-  int U = 0;
-  std::vector<int64_t> state_off, arc_off;       // [U + 1]
-  std::vector<LatChunk> chunks;
-  int32_t* start_d = nullptr;                    // [U]
-  int64_t bytes = 0;
-  // what the operations on a handle need (khg_lattices_best_path / _prune), made at the first of them: state_off | arc_off on the
-  // device, the frame of every utterance's last state as offsets (the layout of an alignment)
-  int64_t* off_d = nullptr;                      // [2 * (U + 1)]
-  std::vector<int64_t> ali_off;                  // [U + 1]
-};
 
 extern "C" int khg_lattices_destroy(khg_lattices* l) {
   if (!l) return KHG_OK;

@@ -204,6 +204,7 @@ __global__ __launch_bounds__(64) void k2_lattice_raw_scan_frames(LrArgs p, int u
 }
 
 // ---- scan 2: one wave, the utterances' totals -> exclusive offsets over the chunk (int64) ----
+// (also K2F's scan, khg_decode_lattice_faster_raw, through an LrArgs with only these set: it must read nothing but n, utt_tot, utt_off)
 __global__ __launch_bounds__(64) void k2_lattice_raw_scan_utts(LrArgs p) {
   const int lane = (int)threadIdx.x;
   long long ts = 0, ta = 0;

@@ -585,6 +585,53 @@ void BindLattice(py::module_& m) {
     return out;
   }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"), py::arg("allow_partial") = true,
      py::arg("return_scores") = false, py::arg("scratch_per_frame") = 0);
+  // get_raw_lattice_faster_batch(am, tm, fsts, feats_list, config, acoustic_scale, allow_partial=True, scratch_per_frame=0,
+  // return_scores=False, return_times=False) -> decode_lattice_faster_batch's dicts plus "lattice" (a Lattice: GetRawLattice's, no states
+  // unless the utterance succeeded).  return_times: (dicts, {"decode_s", "download_s"}).
+  m.def("get_raw_lattice_faster_batch", [](std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, py::object fsts, py::list feats_list,
+                                           const Cfg& config, float acoustic_scale, bool allow_partial, int scratch_per_frame, bool return_scores,
+                                           bool return_times) -> py::object {
+    BatchArgs b(*am, fsts, feats_list, "get_raw_lattice_faster_batch");
+    std::vector<LatticeResult> rs;
+    std::vector<std::shared_ptr<Lattice>> lats;
+    double sec[2] = {0.0, 0.0};
+    {
+      const GraphsCsr csr = b.Csr();
+      py::gil_scoped_release nogil;
+      rs = GetRawLatticeFasterBatch(*am, *tm, csr, b.fp, b.nf, config, acoustic_scale, allow_partial, return_scores, scratch_per_frame, &lats, sec);
+    }
+    py::list out;
+    for (size_t u = 0; u < rs.size(); ++u) {
+      py::dict d = LatticeToDict(rs[u], b.nf[u], return_scores);
+      d["lattice"] = lats[u];
+      out.append(d);
+    }
+    if (!return_times) return std::move(out);
+    py::dict t;
+    t["decode_s"] = sec[0]; t["download_s"] = sec[1];
+    return py::make_tuple(out, t);
+  }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"), py::arg("allow_partial") = true,
+     py::arg("scratch_per_frame") = 0, py::arg("return_scores") = false, py::arg("return_times") = false);
+
+  // get_raw_lattice_faster_device_batch(...) -> (decode_lattice_faster_batch's dicts, DeviceLattices): the lattices stay on the device
+  m.def("get_raw_lattice_faster_device_batch", [](std::shared_ptr<AmDiagGmm> am, std::shared_ptr<TransitionModel> tm, py::object fsts, py::list feats_list,
+                                                  const Cfg& config, float acoustic_scale, bool allow_partial, int scratch_per_frame, bool return_scores) {
+    BatchArgs b(*am, fsts, feats_list, "get_raw_lattice_faster_device_batch");
+    std::vector<LatticeResult> rs;
+    auto d = std::make_shared<PyDeviceLattices>();
+    d->ctx = DefaultCtx();
+    d->ctx_obj = py::none();
+    {
+      const GraphsCsr csr = b.Csr();
+      py::gil_scoped_release nogil;
+      rs = GetRawLatticeFasterDeviceBatch(*am, *tm, csr, b.fp, b.nf, config, acoustic_scale, allow_partial, return_scores, scratch_per_frame, &d->h);
+    }
+    py::list out;
+    for (size_t u = 0; u < rs.size(); ++u) out.append(LatticeToDict(rs[u], b.nf[u], return_scores));
+    return py::make_tuple(out, d);
+  }, py::arg("am"), py::arg("tm"), py::arg("fsts"), py::arg("feats_list"), py::arg("config"), py::arg("acoustic_scale"), py::arg("allow_partial") = true,
+     py::arg("scratch_per_frame") = 0, py::arg("return_scores") = false);
+
   // python/csrc/lattice-simple-decoder.cc:11-31
   using SCfg = LatticeSimpleDecoderConfig;
   py::class_<SCfg>(m, "LatticeSimpleDecoderConfig")

@@ -511,6 +511,63 @@ struct KUtts {
     d["words_off"] = woff;
     return d;
   }
+  // khg_decode_lattice_faster_raw on the resident scores: decode_lattice_faster's outputs plus the batch's raw lattices
+  // (LatticeFasterDecoder::GetRawLattice), as raw_lattice_simple's flat arrays (device=false) or as "lattices", a DeviceLattices on this
+  // set's context with nothing downloaded (device=true)
+  py::dict raw_lattice_faster_impl(KTransitions& tm, float beam, int32_t max_active, int32_t min_active, float lattice_beam, int32_t prune_interval,
+                                   float beam_delta, float hash_ratio, float prune_scale, float acoustic_scale, bool allow_partial,
+                                   int32_t scratch_per_frame, bool device) {
+    khg_lattice_faster_config c;
+    khg_lattice_faster_config_default(&c);
+    c.beam = beam; c.max_active = max_active; c.min_active = min_active; c.lattice_beam = lattice_beam; c.prune_interval = prune_interval;
+    c.beam_delta = beam_delta; c.hash_ratio = hash_ratio; c.prune_scale = prune_scale; c.acoustic_scale = acoustic_scale;
+    c.allow_partial = allow_partial ? 1 : 0; c.scratch_per_frame = scratch_per_frame;
+    const int64_t N = frame_off.at(n_utt), wcap = 2 * N + 1024 * (int64_t)n_utt + 1024;
+    Arr<int32_t> ali({(py::ssize_t)(N > 0 ? N : 1)}), words({(py::ssize_t)wcap}), status({(py::ssize_t)n_utt});
+    Arr<int64_t> woff({(py::ssize_t)n_utt + 1});
+    Arr<double> like({(py::ssize_t)n_utt});
+    auto lat = std::make_shared<khg::PyDeviceLattices>();       // (frees the handle when it goes)
+    lat->ctx = ctx->h; lat->ctx_obj = ctx_obj;
+    const auto t0 = std::chrono::steady_clock::now();
+    Check(NoGil([&] { return khg_decode_lattice_faster_raw(ctx->h, tm.h, h, &c, ali.mutable_data(), words.mutable_data(), woff.mutable_data(), wcap,
+                                                           like.mutable_data(), status.mutable_data(), &lat->h); }));
+    const auto t1 = std::chrono::steady_clock::now();
+    py::dict d;
+    d["ali"] = py::array(ali)[py::slice(0, N, 1)];
+    d["like"] = like; d["status"] = status;
+    d["words"] = py::array(words)[py::slice(0, woff.at(n_utt), 1)];
+    d["words_off"] = woff;
+    if (device) { d["lattices"] = lat; return d; }
+    Arr<int64_t> so({(py::ssize_t)n_utt + 1}), ao({(py::ssize_t)n_utt + 1});
+    Check(khg_lattices_sizes(lat->h, so.mutable_data(), ao.mutable_data()));
+    const py::ssize_t NS = (py::ssize_t)so.at(n_utt), NA = (py::ssize_t)ao.at(n_utt);
+    Arr<int32_t> frame({NS}), gstate({NS}), abeg({NS}), il({NA}), ol({NA}), ns({NA}), start({(py::ssize_t)n_utt});
+    Arr<float> tot({NS}), extra({NS}), fin({NS}), gc({NA}), ac({NA});
+    Check(NoGil([&] { return khg_lattices_download(ctx->h, lat->h, frame.mutable_data(), gstate.mutable_data(), tot.mutable_data(), extra.mutable_data(),
+                                                   fin.mutable_data(), abeg.mutable_data(), il.mutable_data(), ol.mutable_data(), gc.mutable_data(),
+                                                   ac.mutable_data(), ns.mutable_data(), start.mutable_data()); }));
+    const auto t2 = std::chrono::steady_clock::now();
+    int64_t bytes = 0;
+    Check(khg_lattices_device_bytes(lat->h, &bytes));
+    d["state_off"] = so; d["arc_off"] = ao; d["start"] = start;
+    d["frame"] = frame; d["graph_state"] = gstate; d["tot_cost"] = tot; d["extra_cost"] = extra; d["final_cost"] = fin; d["arc_begin"] = abeg;
+    d["ilabel"] = il; d["olabel"] = ol; d["graph_cost"] = gc; d["acoustic_cost"] = ac; d["nextstate"] = ns;
+    d["device_bytes"] = bytes;
+    d["decode_s"] = std::chrono::duration<double>(t1 - t0).count();
+    d["download_s"] = std::chrono::duration<double>(t2 - t1).count();
+    return d;
+  }
+  py::dict raw_lattice_faster(KTransitions& tm, float beam, int32_t max_active, int32_t min_active, float lattice_beam, int32_t prune_interval,
+                              float beam_delta, float hash_ratio, float prune_scale, float acoustic_scale, bool allow_partial, int32_t scratch_per_frame) {
+    return raw_lattice_faster_impl(tm, beam, max_active, min_active, lattice_beam, prune_interval, beam_delta, hash_ratio, prune_scale, acoustic_scale,
+                                   allow_partial, scratch_per_frame, false);
+  }
+  py::dict raw_lattices_faster_device(KTransitions& tm, float beam, int32_t max_active, int32_t min_active, float lattice_beam, int32_t prune_interval,
+                                      float beam_delta, float hash_ratio, float prune_scale, float acoustic_scale, bool allow_partial,
+                                      int32_t scratch_per_frame) {
+    return raw_lattice_faster_impl(tm, beam, max_active, min_active, lattice_beam, prune_interval, beam_delta, hash_ratio, prune_scale, acoustic_scale,
+                                   allow_partial, scratch_per_frame, true);
+  }
   // khg_decode_lattice_simple on the resident scores (which must not come from loglikes(band=True))
   py::dict decode_lattice_simple(KTransitions& tm, float beam, float lattice_beam, int32_t prune_interval, float prune_scale, float acoustic_scale,
                                  bool allow_partial, int32_t scratch_per_frame) {
@@ -726,6 +783,14 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
            py::arg("careful") = false, py::arg("max_active") = (int64_t)std::numeric_limits<int32_t>::max(), py::arg("min_active") = 20,
            py::arg("beam_delta") = 0.5f, py::arg("hash_ratio") = 2.0f, py::arg("download") = true)
       .def("decode_lattice_faster", &KUtts::decode_lattice_faster, py::arg("tm"), py::arg("beam") = 16.0f,
+           py::arg("max_active") = std::numeric_limits<int32_t>::max(), py::arg("min_active") = 200, py::arg("lattice_beam") = 10.0f,
+           py::arg("prune_interval") = 25, py::arg("beam_delta") = 0.5f, py::arg("hash_ratio") = 2.0f, py::arg("prune_scale") = 0.1f,
+           py::arg("acoustic_scale") = 1.0f, py::arg("allow_partial") = true, py::arg("scratch_per_frame") = 0)
+      .def("raw_lattice_faster", &KUtts::raw_lattice_faster, py::arg("tm"), py::arg("beam") = 16.0f,
+           py::arg("max_active") = std::numeric_limits<int32_t>::max(), py::arg("min_active") = 200, py::arg("lattice_beam") = 10.0f,
+           py::arg("prune_interval") = 25, py::arg("beam_delta") = 0.5f, py::arg("hash_ratio") = 2.0f, py::arg("prune_scale") = 0.1f,
+           py::arg("acoustic_scale") = 1.0f, py::arg("allow_partial") = true, py::arg("scratch_per_frame") = 0)
+      .def("raw_lattices_faster_device", &KUtts::raw_lattices_faster_device, py::arg("tm"), py::arg("beam") = 16.0f,
            py::arg("max_active") = std::numeric_limits<int32_t>::max(), py::arg("min_active") = 200, py::arg("lattice_beam") = 10.0f,
            py::arg("prune_interval") = 25, py::arg("beam_delta") = 0.5f, py::arg("hash_ratio") = 2.0f, py::arg("prune_scale") = 0.1f,
            py::arg("acoustic_scale") = 1.0f, py::arg("allow_partial") = true, py::arg("scratch_per_frame") = 0)

@@ -27,6 +27,10 @@ every repetition: get_raw_lattice_simple_batch (UtteranceSet.raw_lattice_simple 
 arcs and bytes per utterance, the download apart from the decode call (seconds, bytes, effective GB/s), and -- from one more pass of
 each call under the context's kernel timing -- the device time of k2_lattice_simple and of the emission kernels (count, scans, fill).
 
+With the default --decoder faster, --lattices times get_raw_lattice_faster_batch (the order-faithful decoder's own raw lattice, on the
+graphs as they are) beside decode_lattice_faster_batch the same way: sizes, download, the decoder kernel's time in both calls (their
+difference is what the emission adds inside the decoder's lane), the emission kernels, and a hash of the plain call's outputs.
+
 --sweep LO:HI and --prune-beam B (next to --lattices) keep the batch's lattices on the device (get_raw_lattice_simple_device_batch,
 UtteranceSet.raw_lattices_simple_device) and time, over max(--reps, 5) repetitions after a warm-up: the best path at every integer
 language-model weight w in LO..HI (graph_scale 1, acoustic_scale 1 / w) in ONE DeviceLattices.best_path call, one pair alone, and
@@ -38,6 +42,7 @@ Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decode
        python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -391,14 +396,12 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--decoder", choices=("faster", "simple"), default="faster")
     ap.add_argument("--check", type=int, default=0)
-    ap.add_argument("--lattices", action="store_true", help="also time the raw-lattice call (simple decoder) and report the lattices")
+    ap.add_argument("--lattices", action="store_true", help="also time the raw-lattice call of --decoder and report the lattices")
     ap.add_argument("--sweep", default=None, metavar="LO:HI", help="with --lattices: best paths at the integer LM weights LO..HI in one call")
     ap.add_argument("--prune-beam", type=float, default=None, help="with --lattices: prune the resident lattices to this beam")
     args = ap.parse_args()
     if (args.sweep or args.prune_beam is not None) and not args.lattices:
         ap.error("--sweep / --prune-beam need --lattices")
-    if args.lattices and not (args.shared_graph or args.decoder == "simple"):
-        ap.error("--lattices needs --decoder simple or --shared-graph")
     if args.shared_graph or args.yesno:
         shared_graph_main(args)
         return
@@ -438,10 +441,41 @@ def main():
         ali_s.append(time.time() - t0)
     if res is None:
         res = fres
+    if args.lattices and args.decoder == "faster":
+        # the raw-lattice call of the lattice-faster decoder (get_raw_lattice_faster_batch) beside the plain call, as for --decoder simple
+        from kaldi_hmm_gmm_amd import _gpu
+        ctx = _gpu.default_context()
+        khg.get_raw_lattice_faster_batch(am, tm, fsts[:64], feats[:64], cfg, 0.1)           # warm-up
+        raw_s, raw_dec_s, raw_dl_s, raw = [], [], [], None
+        for _ in range(args.reps):
+            t0 = time.time()
+            raw, t = khg.get_raw_lattice_faster_batch(am, tm, fsts, feats, cfg, 0.1, return_times=True)
+            raw_s.append(time.time() - t0); raw_dec_s.append(t["decode_s"]); raw_dl_s.append(t["download_s"])
+        flat = lattice_sizes([r["lattice"].num_states for r in raw], [r["lattice"].num_arcs_total for r in raw], raw_dl_s)
+        flat.update(raw_call=med(raw_s), raw_decode_call=med(raw_dec_s),
+                    same_best_paths_as_old_call=sum(1 for a, b in zip(fres, raw) if all(a[k] == b[k] for k in a)))
+        k_old = kernel_ms(ctx, lambda: khg.decode_lattice_faster_batch(am, tm, fsts, feats, cfg, 0.1))
+        k_new = kernel_ms(ctx, lambda: khg.get_raw_lattice_faster_batch(am, tm, fsts, feats, cfg, 0.1))
+        dec_old, dec_new = k_old.get("k2_lattice_faster", 0.0), k_new.get("k2_lattice_faster", 0.0)
+        emit = sum(v for k, v in k_new.items() if k.startswith("k2_lattice_faster_raw"))
+        flat.update(old_call_kernels_ms=k_old, raw_call_kernels_ms=k_new, k2_lattice_faster_ms=dec_old, decoder_lane_extra_ms=dec_new - dec_old,
+                    emission_kernels_ms=emit, emission_over_decoder=(emit + dec_new - dec_old) / dec_old if dec_old else None)
+        faster_lat = flat
+        faster_ops = None
+        if args.sweep or args.prune_beam is not None:
+            _, dl = khg.get_raw_lattice_faster_device_batch(am, tm, fsts, feats, cfg, 0.1)
+            faster_ops = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps)
+            dl.close()
     st = [r["status"] for r in res]
     out = {"decoder": args.decoder,"utterances": args.utts, "frames": frames, "lattice_s": min(lat_s), "lattice_frames_per_s": frames / min(lat_s),
            "faster_decoder_s": min(ali_s), "ratio": min(lat_s) / min(ali_s),
            "succeeded": sum(1 for s in st if s & 1), "partial": sum(1 for s in st if s & 2), "scratch": sum(1 for s in st if s & 4)}
+    out["lattice"] = med(lat_s)
+    out["lattice_faster_output_sha1"] = hashlib.sha1(repr([(r["status"], r["alignment"], r["words"], r["like"]) for r in fres]).encode()).hexdigest()
+    if args.lattices and args.decoder == "faster":
+        out["lattices"] = faster_lat
+        if faster_ops is not None:
+            out["lattice_ops"] = faster_ops
     if args.decoder == "simple":
         out.update(simple_s=min(simple_s), simple_frames_per_s=frames / min(simple_s), simple_over_lattice_faster=min(simple_s) / min(lat_s),
                    simple_over_faster_decoder=min(simple_s) / min(ali_s),
