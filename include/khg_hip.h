@@ -113,7 +113,7 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
 #define KHG_OPT_K2S_HUB 17       /* khg_decode_lattice_simple: a state with more than this many in-arcs (out-arcs in the backward pass) has its arc
                                     loops strided over by a whole wave instead of walked by one lane (a word loop's hub state); same results
                                     bit for bit.  0: off (every state on one lane).  Default 32                              [KHG_K2S_HUB] */
-#define KHG_OPT_LAT_OPS_LDS 18   /* khg_lattices_best_path / khg_lattices_prune: 0 (DEFAULT) an utterance's lattice is staged into LDS when it takes
+#define KHG_OPT_LAT_OPS_LDS 18   /* khg_lattices_best_path / khg_lattices_prune / khg_lattices_posteriors: 0 (DEFAULT) an utterance's lattice is staged into LDS when it takes
                                     at most 48 KiB there, 1 never (every lattice is read from its HBM arrays); same results bit for
                                     bit                                                                              [KHG_LAT_OPS_LDS] */
 #define KHG_OPT_COUNT 19
@@ -481,6 +481,28 @@ int khg_lattices_best_path(khg_ctx *ctx, const khg_lattices *l, int32_t n_scales
  * cycle (KHG_LAT_EPS_LOOP) gets an empty lattice.  status_h[n_utt] (may be NULL).  Synchronous; the input is untouched. */
 int khg_lattices_prune(khg_ctx *ctx, const khg_lattices *l, float graph_scale, float acoustic_scale, float beam, int32_t *status_h,
                        khg_lattices **out);
+/* LatticeForwardBackward / lattice-to-post under one scale pair (finite, >= 0; else KHG_E_ARG), all in float64: an
+ * arc's log-likelihood is -(graph_scale * graph_cost + acoustic_scale * acoustic_cost) (no acoustic term on an epsilon arc), a final
+ * state's -graph_scale * final_cost on the last frame.  *out is a new handle resident on the device (free it with
+ * khg_posteriors_destroy) holding every arc's posterior in the lattice handle's arc order and, per frame t in 0 .. T - 1, the
+ * posteriors of the emitting arcs that leave frame t merged by ilabel (the transition-id), ascending; an id is listed unless every
+ * arc behind it is unreachable from one side (a weight that underflows to 0.0 stays listed).
+ *   status_h[n_utt]    KHG_LAT_SUCCEEDED; KHG_LAT_EPS_LOOP: an epsilon arc that does not go to a higher state number (the
+ *                      lattice-simple decoder's lattices have such self-loops); KHG_LAT_NO_PATH: empty, or no final state reached.
+ *                      An utterance without KHG_LAT_SUCCEEDED has no frames and no entries, and its arc posteriors are 0.
+ *   tot_like_h[n_utt]  log of the sum over all paths; -inf without KHG_LAT_SUCCEEDED.
+ * The first call on a handle builds its in-arc index on the device and keeps it there.  Synchronous; the input is untouched. */
+typedef struct khg_posteriors khg_posteriors;
+int khg_lattices_posteriors(khg_ctx *ctx, const khg_lattices *l, float graph_scale, float acoustic_scale, int32_t *status_h,
+                            double *tot_like_h, khg_posteriors **out);
+/* frame_off_h / entry_off_h [n_utt + 1]: utterance u owns frames frame_off[u] .. frame_off[u + 1] and entries entry_off[u] .. */
+int khg_posteriors_sizes(const khg_posteriors *p, int64_t *frame_off_h, int64_t *entry_off_h);
+/* entry_begin_h[frames + 1] (frame f owns entries entry_begin[f] .. entry_begin[f + 1]), tid_h / weight_h [entries],
+ * arc_post_h [arcs of the lattice handle, its arc order]; any may be NULL */
+int khg_posteriors_download(khg_ctx *ctx, const khg_posteriors *p, int64_t *entry_begin_h, int32_t *tid_h, double *weight_h,
+                            double *arc_post_h);
+int khg_posteriors_device_bytes(const khg_posteriors *p, int64_t *bytes);
+int khg_posteriors_destroy(khg_posteriors *p);
 
 /* ---- K3: sufficient statistics ---------------------------------------------------------- */
 /* AccumAmDiagGmm (csrc/mle-am-diag-gmm.h:93-96) + transition stats (csrc/transition-model.h:176-189)

@@ -14,6 +14,7 @@ from .align import (DecodableCtc, LatticeSimpleDecoder, LatticeSimpleDecoderConf
                     decode_utterance_lattice_simple)
 from .align import Lattice, get_raw_lattice_simple_batch  # noqa: F401
 from .align import DeviceLattices, get_raw_lattice_simple_device_batch  # noqa: F401
+from .align import DevicePosteriors  # noqa: F401
 from .align import get_raw_lattice_faster_batch, get_raw_lattice_faster_device_batch  # noqa: F401
 from .context_dep import (ContextDependency, ContextDependencyInterface, monophone_context_dependency,  # noqa: F401
                           monophone_context_dependency_shared)

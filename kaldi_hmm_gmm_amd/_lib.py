@@ -166,6 +166,11 @@ SIGNATURES = {
     "khg_lattices_chunk_utts": (C.c_int, [vp, c_i32p]),
     "khg_lattices_best_path": (C.c_int, [vp, vp, C.c_int32, c_f32p, c_f32p, c_i32p, c_i32p, c_i64p, C.c_int64, c_f32p, c_i32p]),
     "khg_lattices_prune": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_float, c_i32p, C.POINTER(vp)]),
+    "khg_lattices_posteriors": (C.c_int, [vp, vp, C.c_float, C.c_float, c_i32p, c_f64p, C.POINTER(vp)]),
+    "khg_posteriors_sizes": (C.c_int, [vp, c_i64p, c_i64p]),
+    "khg_posteriors_download": (C.c_int, [vp, vp, c_i64p, c_i32p, c_f64p, c_f64p]),
+    "khg_posteriors_device_bytes": (C.c_int, [vp, c_i64p]),
+    "khg_posteriors_destroy": (C.c_int, [vp]),
     "khg_ali_download": (C.c_int, [vp, vp, c_i32p]),
     "khg_accs_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     "khg_accs_destroy": (C.c_int, [vp]),

@@ -18,5 +18,6 @@ from ._kaldi_hmm_gmm_amd import (DecodableCtc, LatticeSimpleDecoder, LatticeSimp
                                  decode_utterance_lattice_simple)
 from ._kaldi_hmm_gmm_amd import Lattice, get_raw_lattice_simple_batch  # noqa: F401
 from ._kaldi_hmm_gmm_amd import DeviceLattices, get_raw_lattice_simple_device_batch  # noqa: F401
+from ._kaldi_hmm_gmm_amd import DevicePosteriors  # noqa: F401
 from ._kaldi_hmm_gmm_amd import get_raw_lattice_faster_batch, get_raw_lattice_faster_device_batch  # noqa: F401
 from .device import ALIGN_ERROR, ALIGN_RETRIED, INT32_MAX  # noqa: F401

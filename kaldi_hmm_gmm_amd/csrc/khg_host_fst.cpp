@@ -2,6 +2,7 @@
 #include "khg_host_fst.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 
 namespace khg {
@@ -284,6 +285,95 @@ LinearLattice Lattice::ShortestPath(float gs, float as) const {
   }
   const float fw = gs * final_cost[(size_t)b.final_state];
   out.final_w = LatticeWeight{(double)fw, 0.0};
+  return out;
+}
+
+namespace {
+// log(exp(init) + sum exp(x[i])), the maximum taken out first; -inf when every term is
+double LogSumExp(double init, const std::vector<double>& x) {
+  const double NINF = -std::numeric_limits<double>::infinity();
+  double m = init;
+  for (double v : x) m = std::max(m, v);
+  if (m == NINF) return NINF;
+  double sum = std::exp(init - m);
+  for (double v : x) sum += std::exp(v - m);
+  return m + std::log(sum);
+}
+}  // namespace
+
+LatticePosteriors Lattice::ForwardBackward(float graph_scale, float acoustic_scale) const {
+  KHG_REQUIRE(graph_scale >= 0.0f && acoustic_scale >= 0.0f && graph_scale != std::numeric_limits<float>::infinity() &&
+                  acoustic_scale != std::numeric_limits<float>::infinity(),
+              "Lattice::ForwardBackward: graph_scale and acoustic_scale must be finite and >= 0");
+  const double NINF = -std::numeric_limits<double>::infinity();
+  const float FINF = std::numeric_limits<float>::infinity();
+  const double gs = graph_scale, as = acoustic_scale;
+  LatticePosteriors out;
+  out.status = KHG_LAT_NO_PATH;
+  out.tot_like = NINF;
+  const int N = NumStates();
+  if (N == 0 || start < 0) return out;
+  const int64_t A = NumArcs();
+  std::vector<int32_t> src((size_t)A);
+  for (int s = 0; s < N; ++s)
+    for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) {
+      src[(size_t)a] = s;
+      if (nextstate[(size_t)a] <= s) {
+        KHG_REQUIRE(ilabel[(size_t)a] == 0, "Lattice::ForwardBackward: an emitting arc must go to the next frame");
+        out.status = KHG_LAT_EPS_LOOP;
+      }
+    }
+  if (out.status == KHG_LAT_EPS_LOOP) return out;
+  std::vector<double> w((size_t)A);
+  for (int64_t a = 0; a < A; ++a) {
+    const double g = gs * (double)graph_cost[(size_t)a];
+    const double c = ilabel[(size_t)a] != 0 ? as * (double)acoustic_cost[(size_t)a] : 0.0;
+    w[(size_t)a] = -(g + c);
+  }
+  const int T = frame[(size_t)N - 1];
+  auto fin = [&](int s) { return frame[(size_t)s] == T && final_cost[(size_t)s] != FINF ? -(gs * (double)final_cost[(size_t)s]) : NINF; };
+  // in-arcs of every state in global arc order
+  std::vector<std::vector<int32_t>> in((size_t)N);
+  for (int64_t a = 0; a < A; ++a) in[(size_t)nextstate[(size_t)a]].push_back((int32_t)a);
+  std::vector<double> alpha((size_t)N, NINF), beta((size_t)N, NINF), x;
+  for (int s = 0; s < N; ++s) {
+    x.clear();
+    for (int32_t a : in[(size_t)s]) x.push_back(alpha[(size_t)src[(size_t)a]] + w[(size_t)a]);
+    alpha[(size_t)s] = LogSumExp(s == start ? 0.0 : NINF, x);
+  }
+  x.clear();
+  for (int s = 0; s < N; ++s) if (fin(s) != NINF) x.push_back(alpha[(size_t)s] + fin(s));
+  const double tot = LogSumExp(NINF, x);
+  if (tot == NINF) return out;
+  for (int s = N - 1; s >= 0; --s) {
+    x.clear();
+    for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) x.push_back(w[(size_t)a] + beta[(size_t)nextstate[(size_t)a]]);
+    beta[(size_t)s] = LogSumExp(fin(s), x);
+  }
+  out.status = KHG_LAT_SUCCEEDED;
+  out.tot_like = tot;
+  out.arc_post.assign((size_t)A, 0.0);
+  std::vector<char> live((size_t)A, 0);
+  for (int64_t a = 0; a < A; ++a) {
+    const double al = alpha[(size_t)src[(size_t)a]], be = beta[(size_t)nextstate[(size_t)a]];
+    if (al == NINF || be == NINF) continue;
+    live[(size_t)a] = 1;
+    out.arc_post[(size_t)a] = std::exp(((al + w[(size_t)a]) + be) - tot);
+  }
+  // per frame: the live emitting arcs that leave it, merged by ilabel (weights summed in arc order), ascending
+  out.post.assign((size_t)T, {});
+  for (int64_t a = 0; a < A; ++a) {
+    if (!live[(size_t)a] || ilabel[(size_t)a] == 0) continue;
+    const int t = frame[(size_t)src[(size_t)a]];
+    if (t < 0 || t >= T) continue;
+    auto& row = out.post[(size_t)t];
+    auto it = std::find_if(row.begin(), row.end(), [&](const std::pair<int32_t, double>& e) { return e.first == ilabel[(size_t)a]; });
+    if (it == row.end()) row.emplace_back(ilabel[(size_t)a], out.arc_post[(size_t)a]);
+    else it->second += out.arc_post[(size_t)a];
+  }
+  for (auto& row : out.post) std::sort(row.begin(), row.end(), [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) { return a.first < b.first; });
+  out.alpha = std::move(alpha);
+  out.beta = std::move(beta);
   return out;
 }
 

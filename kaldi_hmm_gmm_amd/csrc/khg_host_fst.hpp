@@ -111,6 +111,16 @@ struct LatticeBestPath {
   std::vector<int32_t> bp;
 };
 
+// Lattice::ForwardBackward (what khg_lattices_posteriors gives for one lattice): KHG_LAT_* status (SUCCEEDED, NO_PATH,
+// EPS_LOOP), the total log-likelihood, alpha / beta per state, the posterior of every arc, and per frame 0 .. T - 1 the emitting arcs'
+// posteriors merged by ilabel, ascending.  Without SUCCEEDED: tot_like = -inf and everything else empty.
+struct LatticePosteriors {
+  int status = 0;
+  double tot_like = 0.0;
+  std::vector<double> alpha, beta, arc_post;
+  std::vector<std::vector<std::pair<int32_t, double>>> post;
+};
+
 // The fst::VectorFst<LatticeArc> LatticeSimpleDecoder::GetRawLattice builds (csrc/lattice-simple-decoder.cc:654-735), as the flat arrays
 // khg_lattices_download hands back: a state per surviving token, numbered by frame, then by graph state (:684-690); state s owns arcs
 // arc_begin[s] .. arc_begin[s + 1], one per surviving forward link in the order of the graph's arcs in its state (:700-722); the last
@@ -149,6 +159,11 @@ class Lattice {
   // best path (sums in the association order of DESIGN.md 7e), plus the best path itself; states and arcs keep their order, costs
   // stay unscaled.  No reachable final state, or a negative epsilon cycle: an empty lattice; *status the KHG_LAT_* bits.
   std::shared_ptr<Lattice> Prune(float beam, float graph_scale = 1.0f, float acoustic_scale = 1.0f, int* status = nullptr) const;
+  // LatticeForwardBackward / lattice-to-post in the log semiring, float64, serially in state order: an arc's
+  // log-likelihood is -(graph_scale * graph_cost + acoustic_scale * acoustic_cost), no acoustic term on an epsilon arc; a final state's
+  // -graph_scale * final_cost on the last frame.  Every arc must go to a higher state: an epsilon arc that does not gives
+  // KHG_LAT_EPS_LOOP (checked on the structure, before any arithmetic).  Each log-sum is max-then-sum over a state's arcs in arc order.
+  LatticePosteriors ForwardBackward(float graph_scale = 1.0f, float acoustic_scale = 1.0f) const;
   // Kaldi's text form of a lattice: "src dst ilabel olabel graph,acoustic" per arc, "state graph,acoustic" per final state
   std::string ToText() const;
 

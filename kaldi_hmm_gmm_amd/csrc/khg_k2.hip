@@ -2,7 +2,8 @@
 // shape, LDS budgets, the exact DP on the main stream and the order-faithful decoder on a side stream; and the lattice decoder
 // (khg_decode_lattice_faster, khg_k2_lattice.hip.inc) and the data-parallel LatticeSimpleDecoder (khg_decode_lattice_simple,
 // khg_k2_lattice_simple.hip.inc), each with its raw lattice (khg_decode_lattice_faster_raw, khg_k2_lattice_faster_raw.hip.inc;
-// khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc).  gfx950 only.
+// khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc), the operations on resident lattices (khg_k2_lattice_ops.hip.inc) and their
+// forward-backward posteriors (khg_lattices_posteriors, khg_k2_lattice_post.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
 
 #include <memory>
@@ -13,6 +14,7 @@
 #include "khg_k2_lattice_raw.hip.inc"
 #include "khg_k2_lattice_faster_raw.hip.inc"
 #include "khg_k2_lattice_ops.hip.inc"
+#include "khg_k2_lattice_post.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // K2
@@ -383,6 +385,9 @@ struct khg_lattices {
   // device, the frame of every utterance's last state as offsets (the layout of an alignment)
   int64_t* off_d = nullptr;                      // [2 * (U + 1)]
   std::vector<int64_t> ali_off;                  // [U + 1]
+  // the in-arc index khg_lattices_posteriors gathers through, made at its first call: per chunk one block
+  // [in_begin: states + utterances | in_arc: arcs | arc_src: arcs] (int32)
+  std::vector<int32_t*> idx_d;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -736,6 +741,7 @@ extern "C" int khg_lattices_destroy(khg_lattices* l) {
   for (LatChunk& c : l->chunks) if (c.buf) (void)hipFree(c.buf);
   if (l->start_d) (void)hipFree(l->start_d);
   if (l->off_d) (void)hipFree(l->off_d);
+  for (int32_t* q : l->idx_d) if (q) (void)hipFree(q);
   delete l;
   return KHG_OK;
 }
@@ -1316,6 +1322,193 @@ extern "C" int khg_lattices_prune(khg_ctx* ctx, const khg_lattices* lc, float gr
   rc = check_err_flag(ctx, "khg_lattices_prune");     // synchronises: the scratch goes with `dv`
   if (rc) return rc;
   if (status_h) std::copy(st.begin(), st.end(), status_h);
+  *out = res.release();
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2P: forward-backward posteriors of device-resident lattices (khg_k2_lattice_post.hip.inc)
+struct PostChunk {
+  int u0 = 0, n = 0;
+  int64_t nf = 0, ne = 0, na = 0;      // frames, entries, arcs
+  double* arc_post = nullptr;          // [na], the lattice handle's arc order
+  unsigned char* buf = nullptr;        // entry_begin int64 [nf + 1] (relative to the chunk) | weight double [ne] | tid int32 [ne]
+  int64_t o_weight = 0, o_tid = 0;
+};
+struct khg_posteriors {
+  int U = 0;
+  std::vector<int64_t> frame_off, entry_off, arc_off;     // [U + 1]
+  std::vector<PostChunk> chunks;
+  int64_t bytes = 0;
+};
+
+namespace {
+struct PostFree { void operator()(khg_posteriors* p) const { (void)khg_posteriors_destroy(p); } };
+// alpha, beta and the Jacobi row (doubles) beside the staged lattice
+int64_t post_lds_need(const khg_lattices* l, int u) {
+  const int64_t N = l->state_off[(size_t)u + 1] - l->state_off[(size_t)u], A = l->arc_off[(size_t)u + 1] - l->arc_off[(size_t)u];
+  return 24 * N + 4 * (3 * N + 4 * A);
+}
+int post_chunk_lds(const khg_ctx* ctx, const khg_lattices* l, const LatChunk& c) {
+  if (ctx->opt[KHG_OPT_LAT_OPS_LDS] == 1) return 0;
+  int64_t best = 0;
+  for (int u = c.u0; u < c.u0 + c.n; ++u) {
+    const int64_t need = post_lds_need(l, u);
+    if (need <= kLatOpsLds) best = std::max(best, need);
+  }
+  return (int)best;
+}
+// the in-arc index, once per handle
+int lat_index(khg_ctx* ctx, khg_lattices* l) {
+  if (l->idx_d.size() == l->chunks.size()) return KHG_OK;
+  DevBlocks dv;
+  for (size_t k = l->idx_d.size(); k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    const int64_t words = c.ns + c.n + 2 * c.na;
+    int32_t* blk = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&blk), (size_t)std::max<int64_t>(4 * words, 16)));
+    l->idx_d.push_back(blk);
+    l->bytes += 4 * words;
+    int32_t* cur = nullptr;
+    int rc = dv.alloc(std::max<int64_t>(c.ns, 1), &cur);
+    if (rc) return rc;
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    KernelTimer kt(ctx, "k2_lattice_post_index");
+    KHG_LAUNCH(ctx, k2_lattice_post_index, dim3((unsigned)c.n), dim3(64), 0, ctx->stream, p, blk, blk + c.ns + c.n, blk + c.ns + c.n + c.na, cur);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // the cursors go with `dv`
+  return KHG_OK;
+}
+}  // namespace
+
+extern "C" int khg_posteriors_destroy(khg_posteriors* p) {
+  if (!p) return KHG_OK;
+  for (PostChunk& c : p->chunks) {
+    if (c.arc_post) (void)hipFree(c.arc_post);
+    if (c.buf) (void)hipFree(c.buf);
+  }
+  delete p;
+  return KHG_OK;
+}
+extern "C" int khg_posteriors_sizes(const khg_posteriors* p, int64_t* frame_off_h, int64_t* entry_off_h) {
+  if (!p) return khg_set_error(KHG_E_ARG, "khg_posteriors_sizes: bad arguments");
+  if (frame_off_h) std::copy(p->frame_off.begin(), p->frame_off.end(), frame_off_h);
+  if (entry_off_h) std::copy(p->entry_off.begin(), p->entry_off.end(), entry_off_h);
+  return KHG_OK;
+}
+extern "C" int khg_posteriors_device_bytes(const khg_posteriors* p, int64_t* bytes) {
+  if (!p || !bytes) return khg_set_error(KHG_E_ARG, "khg_posteriors_device_bytes: bad arguments");
+  *bytes = p->bytes;
+  return KHG_OK;
+}
+extern "C" int khg_posteriors_download(khg_ctx* ctx, const khg_posteriors* p, int64_t* entry_begin_h, int32_t* tid_h, double* weight_h,
+                                       double* arc_post_h) {
+  if (ctx_dead(ctx) || !p) return khg_set_error(KHG_E_ARG, "khg_posteriors_download: bad arguments");
+  if (entry_begin_h) entry_begin_h[0] = 0;
+  for (const PostChunk& c : p->chunks) {
+    const int64_t f0 = p->frame_off[(size_t)c.u0], e0 = p->entry_off[(size_t)c.u0], a0 = p->arc_off[(size_t)c.u0];
+    if (entry_begin_h) HIPCHK(hipMemcpyAsync(entry_begin_h + f0, c.buf, 8 * ((size_t)c.nf + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (weight_h && c.ne) HIPCHK(hipMemcpyAsync(weight_h + e0, c.buf + c.o_weight, 8 * (size_t)c.ne, hipMemcpyDeviceToHost, ctx->stream));
+    if (tid_h && c.ne) HIPCHK(hipMemcpyAsync(tid_h + e0, c.buf + c.o_tid, 4 * (size_t)c.ne, hipMemcpyDeviceToHost, ctx->stream));
+    if (arc_post_h && c.na) HIPCHK(hipMemcpyAsync(arc_post_h + a0, c.arc_post, 8 * (size_t)c.na, hipMemcpyDeviceToHost, ctx->stream));
+    // a chunk's entry_begin counts from the chunk's first entry; chunk k + 1's first element lands on chunk k's last
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (entry_begin_h) for (int64_t f = 0; f <= c.nf; ++f) entry_begin_h[f0 + f] += e0;
+  }
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_posteriors(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, int32_t* status_h,
+                                       double* tot_like_h, khg_posteriors** out) {
+  if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, "khg_lattices_posteriors: bad arguments");
+  *out = nullptr;
+  if (bad_scale(graph_scale) || bad_scale(acoustic_scale))
+    return khg_set_error(KHG_E_ARG, "khg_lattices_posteriors: graph_scale and acoustic_scale must be finite and >= 0");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
+  res->U = U;
+  res->frame_off.assign((size_t)U + 1, 0);
+  res->entry_off.assign((size_t)U + 1, 0);
+  res->arc_off = l->arc_off;
+  if (U == 0) { *out = res.release(); return KHG_OK; }
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc) rc = lat_index(ctx, l);
+  if (rc) return rc;
+  DevBlocks dv;
+  int32_t* status_d; double* tot_d; int64_t* ali_off_d;
+  if ((rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &tot_d)) || (rc = dv.alloc(U + 1, &ali_off_d))) return rc;
+  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  std::vector<int64_t> off_h;
+  for (size_t k = 0; k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    PoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p.lo);
+    p.lo.lds_bytes = post_chunk_lds(ctx, l, c);
+    p.lo.status = status_d; p.lo.ali_off = ali_off_d; p.tot = tot_d;
+    p.in_begin = l->idx_d[k]; p.in_arc = l->idx_d[k] + c.ns + c.n; p.arc_src = l->idx_d[k] + c.ns + c.n + c.na;
+    p.gs = (double)graph_scale; p.as = (double)acoustic_scale;
+    p.f_base = l->ali_off[(size_t)c.u0];
+    const int64_t nfr = l->ali_off[(size_t)c.u0 + c.n] - p.f_base;
+    const int64_t cells = std::max<int64_t>(c.ns, 1), arcs = std::max<int64_t>(c.na, 1);
+    if ((rc = dv.alloc(cells, &p.alpha)) || (rc = dv.alloc(cells, &p.beta)) || (rc = dv.alloc(cells, &p.row)) || (rc = dv.alloc(arcs, &p.flag)) ||
+        (rc = dv.alloc(arcs, &p.rank)) || (rc = dv.alloc(std::max<int64_t>(nfr, 1), &p.fcnt)) || (rc = dv.alloc(nfr + 2 * (int64_t)c.n, &p.fstate)) ||
+        (rc = dv.alloc(2 * (int64_t)c.n, &p.lo.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.lo.utt_off)))
+      return rc;
+    PostChunk pc;
+    pc.u0 = c.u0; pc.n = c.n; pc.na = c.na;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&pc.arc_post), (size_t)(8 * arcs)));
+    res->chunks.push_back(pc);
+    res->bytes += 8 * c.na;
+    p.arc_post = pc.arc_post;
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_fb");
+      KHG_LAUNCH(ctx, k2_lattice_post_fb, dim3((unsigned)c.n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_scan");
+      KHG_LAUNCH(ctx, k2_lattice_prune_scan, dim3(1), dim3(64), 0, ctx->stream, p.lo);     // frames at [b], entries at [n + 1 + b]
+      HIPCHK(hipGetLastError());
+    }
+    off_h.assign(2 * ((size_t)c.n + 1), 0);
+    HIPCHK(hipMemcpyAsync(off_h.data(), p.lo.utt_off, 16 * ((size_t)c.n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));        // the one synchronisation that sizes the output
+    PostChunk& q = res->chunks.back();
+    q.nf = off_h[(size_t)c.n]; q.ne = off_h[2 * (size_t)c.n + 1];
+    for (int b = 0; b < c.n; ++b) {
+      res->frame_off[(size_t)c.u0 + b + 1] = res->frame_off[(size_t)c.u0 + b] + (off_h[(size_t)b + 1] - off_h[(size_t)b]);
+      res->entry_off[(size_t)c.u0 + b + 1] = res->entry_off[(size_t)c.u0 + b] + (off_h[(size_t)c.n + 2 + b] - off_h[(size_t)c.n + 1 + b]);
+    }
+    q.o_weight = (8 * (q.nf + 1) + 255) & ~int64_t(255);
+    q.o_tid = q.o_weight + ((8 * q.ne + 255) & ~int64_t(255));
+    const int64_t total = q.o_tid + 4 * q.ne;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&q.buf), (size_t)std::max<int64_t>(total, 16)));
+    res->bytes += total;
+    p.entry_begin = reinterpret_cast<int64_t*>(q.buf); p.weight = reinterpret_cast<double*>(q.buf + q.o_weight);
+    p.tid = reinterpret_cast<int32_t*>(q.buf + q.o_tid);
+    int64_t max_a = 0;
+    for (int b = 0; b < c.n; ++b) max_a = std::max(max_a, l->arc_off[(size_t)c.u0 + b + 1] - l->arc_off[(size_t)c.u0 + b]);
+    const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_a + PO_NT - 1) / PO_NT, std::max<int64_t>(1, 4096 / c.n)));
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_fill");
+      KHG_LAUNCH(ctx, k2_lattice_post_fill, dim3((unsigned)c.n, gy), dim3(PO_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  std::vector<int32_t> st((size_t)U);
+  std::vector<double> tl((size_t)U);
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(tl.data(), tot_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  rc = check_err_flag(ctx, "khg_lattices_posteriors");     // synchronises: the scratch goes with `dv`
+  if (rc) return rc;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (tot_like_h) std::copy(tl.begin(), tl.end(), tot_like_h);
   *out = res.release();
   return KHG_OK;
 }

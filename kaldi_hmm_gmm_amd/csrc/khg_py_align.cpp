@@ -347,6 +347,20 @@ void BindLattice(py::module_& m) {
         std::shared_ptr<Lattice> r = l.Prune(beam, gs, as, &st);
         return py::make_tuple(r, st);
       }, py::arg("beam"), py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      // what DeviceLattices.posteriors gives for this lattice: status, tot_like, arc_post, post (per frame [(tid, weight), ...]), alpha, beta
+      .def("forward_backward", [](const Lattice& l, float gs, float as) {
+        const LatticePosteriors r = l.ForwardBackward(gs, as);
+        py::dict d;
+        d["status"] = r.status; d["tot_like"] = r.tot_like; d["arc_post"] = Vec1(r.arc_post); d["alpha"] = Vec1(r.alpha); d["beta"] = Vec1(r.beta);
+        py::list post;
+        for (const auto& row : r.post) {
+          py::list e;
+          for (const auto& x : row) e.append(py::make_tuple(x.first, x.second));
+          post.append(e);
+        }
+        d["post"] = post;
+        return d;
+      }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       .def("to_text", &Lattice::ToText)
       .def("__str__", &Lattice::ToText)
       .def_property_readonly("frame", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.frame, l.frame.size()); })
@@ -467,6 +481,21 @@ void BindLattice(py::module_& m) {
         r->status.resize((size_t)U);
         return r;
       }, py::arg("beam"), py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      // LatticeForwardBackward / lattice-to-post under one scale pair -> DevicePosteriors, resident on the device
+      .def("posteriors", [](PyDeviceLattices& d, float gs, float as) {
+        const auto so = LatSizes(d);
+        const int U = (int)so.first.size() - 1;
+        auto r = std::make_shared<PyDevicePosteriors>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj; r->arc_off = so.second;
+        r->status.assign((size_t)std::max(U, 1), 0);
+        r->tot_like.assign((size_t)std::max(U, 1), 0.0);
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_posteriors(d.ctx, d.h, gs, as, r->status.data(), r->tot_like.data(), &r->h));
+        }
+        r->status.resize((size_t)U); r->tot_like.resize((size_t)U);
+        return r;
+      }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       .def("download", [](PyDeviceLattices& d) {
         if (!d.h) throw Error("DeviceLattices: closed");
         std::vector<std::shared_ptr<Lattice>> out;
@@ -477,6 +506,83 @@ void BindLattice(py::module_& m) {
         return out;
       })
       .def("close", &PyDeviceLattices::close);
+
+  // DevicePosteriors: the arc and per-frame transition-id posteriors of a batch of lattices, resident on the device
+  auto post_sizes = [](PyDevicePosteriors& d) {
+    if (!d.h) throw Error("DevicePosteriors: closed");
+    const size_t U = d.status.size();
+    std::vector<int64_t> fo(U + 1), eo(U + 1);
+    CApi(khg_posteriors_sizes(d.h, fo.data(), eo.data()));
+    return std::make_pair(fo, eo);
+  };
+  py::class_<PyDevicePosteriors, std::shared_ptr<PyDevicePosteriors>>(m, "DevicePosteriors")
+      .def_property_readonly("status", [](PyDevicePosteriors& d) { return Vec1(d.status); })
+      .def_property_readonly("tot_like", [](PyDevicePosteriors& d) { return Vec1(d.tot_like); })
+      .def_property_readonly("num_utts", [](PyDevicePosteriors& d) { return (int)d.status.size(); })
+      .def_property_readonly("frame_off", [post_sizes](PyDevicePosteriors& d) { return Vec1(post_sizes(d).first); })
+      .def_property_readonly("entry_off", [post_sizes](PyDevicePosteriors& d) { return Vec1(post_sizes(d).second); })
+      .def_property_readonly("device_bytes", [](PyDevicePosteriors& d) {
+        if (!d.h) throw Error("DevicePosteriors: closed");
+        int64_t b = 0;
+        CApi(khg_posteriors_device_bytes(d.h, &b));
+        return b;
+      })
+      // per utterance a list over its frames of [(tid, weight), ...], ids ascending (no frames without KHG_LAT_SUCCEEDED)
+      .def("download", [post_sizes](PyDevicePosteriors& d) {
+        const auto sz = post_sizes(d);
+        const size_t U = d.status.size();
+        std::vector<int64_t> eb((size_t)sz.first.back() + 1, 0);
+        std::vector<int32_t> tid((size_t)sz.second.back() + 1);
+        std::vector<double> w((size_t)sz.second.back() + 1);
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_posteriors_download(d.ctx, d.h, eb.data(), tid.data(), w.data(), nullptr));
+        }
+        py::list out;
+        for (size_t u = 0; u < U; ++u) {
+          py::list frames;
+          for (int64_t f = sz.first[u]; f < sz.first[u + 1]; ++f) {
+            py::list e;
+            for (int64_t i = eb[(size_t)f]; i < eb[(size_t)f + 1]; ++i) e.append(py::make_tuple(tid[(size_t)i], w[(size_t)i]));
+            frames.append(e);
+          }
+          out.append(frames);
+        }
+        return out;
+      })
+      // the flat arrays of download(): entry_begin [frames + 1], tid, weight [entries]
+      .def("download_arrays", [post_sizes](PyDevicePosteriors& d) {
+        const auto sz = post_sizes(d);
+        std::vector<int64_t> eb((size_t)sz.first.back() + 1, 0);
+        std::vector<int32_t> tid((size_t)sz.second.back() + 1);
+        std::vector<double> w((size_t)sz.second.back() + 1);
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_posteriors_download(d.ctx, d.h, eb.data(), tid.data(), w.data(), nullptr));
+        }
+        tid.pop_back(); w.pop_back();
+        return py::make_tuple(Vec1(eb), Vec1(tid), Vec1(w));
+      })
+      // per utterance a float64 array over its arcs in the lattice's arc order (empty without KHG_LAT_SUCCEEDED)
+      .def("arc_post", [](PyDevicePosteriors& d) {
+        if (!d.h) throw Error("DevicePosteriors: closed");
+        const size_t U = d.status.size();
+        std::vector<double> ap((size_t)(d.arc_off.empty() ? 0 : d.arc_off.back()) + 1);
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_posteriors_download(d.ctx, d.h, nullptr, nullptr, nullptr, ap.data()));
+        }
+        py::list out;
+        for (size_t u = 0; u < U; ++u) {
+          const bool ok = (d.status[u] & KHG_LAT_SUCCEEDED) != 0;
+          const int64_t a0 = d.arc_off[u], a1 = ok ? d.arc_off[u + 1] : a0;
+          Arr<double> a({(py::ssize_t)(a1 - a0)});
+          if (a1 > a0) std::memcpy(a.mutable_data(), ap.data() + a0, sizeof(double) * (size_t)(a1 - a0));
+          out.append(a);
+        }
+        return out;
+      })
+      .def("close", &PyDevicePosteriors::close);
 
   // get_raw_lattice_simple_device_batch(am, tm, fsts, feats_list, config, acoustic_scale, scratch_per_frame=0) -> (one dict per
   // utterance with decode_lattice_simple_batch's keys, DeviceLattices): get_raw_lattice_simple_batch that keeps the lattices on the device

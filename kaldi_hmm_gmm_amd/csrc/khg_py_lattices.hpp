@@ -23,4 +23,19 @@ struct PyDeviceLattices {
   void close() { if (h) { khg_lattices_destroy(h); h = nullptr; } }
 };
 
+// DevicePosteriors: owns a khg_posteriors handle (what DeviceLattices.posteriors made, resident on the device)
+struct PyDevicePosteriors {
+  khg_posteriors* h = nullptr;
+  khg_ctx* ctx = nullptr;
+  pybind11::object ctx_obj;
+  std::vector<int32_t> status;       // KHG_LAT_* bits per utterance
+  std::vector<double> tot_like;
+  std::vector<int64_t> arc_off;      // of the lattices it was made from
+  PyDevicePosteriors() = default;
+  PyDevicePosteriors(const PyDevicePosteriors&) = delete;
+  PyDevicePosteriors& operator=(const PyDevicePosteriors&) = delete;
+  ~PyDevicePosteriors() { close(); }
+  void close() { if (h) { khg_posteriors_destroy(h); h = nullptr; } }
+};
+
 }  // namespace khg

@@ -38,7 +38,13 @@ DeviceLattices.prune(B) at the middle weight -- beside what gives the same answe
 Lattice objects and a host ShortestPath per weight and utterance.  Kernel milliseconds come from one more pass under the context's
 kernel timing; the report says how many of the host's paths the device's equal.
 
-Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4]
+--post (next to --lattices) times DeviceLattices.posteriors(1, 0.1) on the resident lattices the same way, beside the download of every
+lattice plus a host Lattice.forward_backward per utterance and beside the one-pair best path on the same handle; it reports the kernels
+of the first call on the handle (which builds the in-arc index) and of a later one, the posterior handle's bytes, and how many of the
+host's (transition-id, weight) entries the device's agree with to 1e-9.  (The lattice-simple decoder's lattices carry epsilon
+self-loops and are refused with KHG_LAT_EPS_LOOP: use --decoder faster.)
+
+Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post]
        python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
@@ -160,7 +166,7 @@ def emission_summary(k_old, k_new):
             "emission_ms": emit, "emission_over_decoder": emit / k_old["k2_lattice_simple"] if k_old.get("k2_lattice_simple") else None}
 
 
-def lattice_ops(ctx, dl, sweep, prune_beam, reps):
+def lattice_ops(ctx, dl, sweep, prune_beam, reps, post=False):
     """The operations on a DeviceLattices handle beside the host loop that gives the same answers -> the report dict."""
     reps = max(reps, 5)
     out = {"repetitions": reps, "device_bytes": int(dl.device_bytes), "utterances": int(dl.num_utts)}
@@ -213,6 +219,46 @@ def lattice_ops(ctx, dl, sweep, prune_beam, reps):
         k_p = kernel_ms(ctx, lambda: dl.prune(prune_beam, 1.0, a).close())
         out["prune"] = {"beam": prune_beam, "acoustic_scale": a, "prune_call": med(t_p), "kernels_ms": k_p, "kernels_total_ms": sum(k_p.values()),
                         "states_before": int(dl.state_off[-1]), "arcs_before": int(dl.arc_off[-1]), "states_after": kept[0], "arcs_after": kept[1]}
+    if post:
+        a = 0.1
+        k_first = kernel_ms(ctx, lambda: dl.posteriors(1.0, a).close())             # the first call on the handle builds its in-arc index
+        t_post, t_host, t_dl, t_bp = [], [], [], []
+        P = None
+        for _ in range(reps):
+            if P is not None:
+                P.close()
+            ctx.sync(); t0 = time.time()
+            P = dl.posteriors(1.0, a)
+            t_post.append(time.time() - t0)
+            t0 = time.time()
+            dl.best_path([1.0], [a])
+            t_bp.append(time.time() - t0)
+            t0 = time.time()
+            lats = dl.download()
+            t_dl.append(time.time() - t0)
+            host = [L.forward_backward(1.0, a) for L in lats]
+            t_host.append(time.time() - t0)
+        got, st, tl = P.download(), P.status, P.tot_like
+        entries = same = same_status = 0
+        worst_tot = 0.0
+        for u, h in enumerate(host):
+            same_status += h["status"] == int(st[u])
+            if h["status"] == 1:
+                worst_tot = max(worst_tot, abs(h["tot_like"] - float(tl[u])))
+            for hr, gr in zip(h["post"], got[u]):
+                entries += len(hr)
+                same += sum(1 for (t1, w1), (t2, w2) in zip(hr, gr) if t1 == t2 and abs(w1 - w2) <= 1e-9) if len(hr) == len(gr) else 0
+        k_post = kernel_ms(ctx, lambda: dl.posteriors(1.0, a).close())
+        k_bp = kernel_ms(ctx, lambda: dl.best_path([1.0], [a]))
+        out["posteriors"] = {"acoustic_scale": a, "posteriors_call": med(t_post), "one_pair_best_path_call": med(t_bp),
+                             "host_download_and_lattices": med(t_dl), "host_download_lattices_and_forward_backward": med(t_host),
+                             "host_over_device": float(np.median(t_host) / np.median(t_post)), "kernels_ms": k_post,
+                             "first_call_kernels_ms": k_first, "in_arc_index_ms": k_first.get("k2_lattice_post_index"),
+                             "one_pair_best_path_kernels_ms": k_bp, "handle_bytes": int(P.device_bytes),
+                             "handle_bytes_per_utt": int(P.device_bytes) / max(U, 1), "frames": int(P.frame_off[-1]), "entries": entries,
+                             "entries_equal_to_host_within_1e-9": same, "statuses_equal_to_host": same_status, "succeeded": int((st == 1).sum()),
+                             "largest_tot_like_difference": worst_tot}
+        P.close()
     return out
 
 
@@ -349,9 +395,9 @@ def shared_graph_main(args):
             finally:
                 ctx.set_option("k2s_hub", out["hub_default"])
             entry["lattices"].update(emission_summary(k_old, k_new), hub=h)
-            if args.sweep or args.prune_beam is not None:
+            if args.sweep or args.prune_beam is not None or args.post:
                 d = sh.raw_lattices_simple_device(dtm, beam=13.0, lattice_beam=6.0, acoustic_scale=0.1)
-                entry["lattice_ops"] = lattice_ops(ctx, d["lattices"], args.sweep, args.prune_beam, args.reps)
+                entry["lattice_ops"] = lattice_ops(ctx, d["lattices"], args.sweep, args.prune_beam, args.reps, args.post)
                 d["lattices"].close()
         if args.check > 0:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -399,9 +445,10 @@ def main():
     ap.add_argument("--lattices", action="store_true", help="also time the raw-lattice call of --decoder and report the lattices")
     ap.add_argument("--sweep", default=None, metavar="LO:HI", help="with --lattices: best paths at the integer LM weights LO..HI in one call")
     ap.add_argument("--prune-beam", type=float, default=None, help="with --lattices: prune the resident lattices to this beam")
+    ap.add_argument("--post", action="store_true", help="with --lattices: forward-backward posteriors of the resident lattices")
     args = ap.parse_args()
-    if (args.sweep or args.prune_beam is not None) and not args.lattices:
-        ap.error("--sweep / --prune-beam need --lattices")
+    if (args.sweep or args.prune_beam is not None or args.post) and not args.lattices:
+        ap.error("--sweep / --prune-beam / --post need --lattices")
     if args.shared_graph or args.yesno:
         shared_graph_main(args)
         return
@@ -462,9 +509,9 @@ def main():
                     emission_kernels_ms=emit, emission_over_decoder=(emit + dec_new - dec_old) / dec_old if dec_old else None)
         faster_lat = flat
         faster_ops = None
-        if args.sweep or args.prune_beam is not None:
+        if args.sweep or args.prune_beam is not None or args.post:
             _, dl = khg.get_raw_lattice_faster_device_batch(am, tm, fsts, feats, cfg, 0.1)
-            faster_ops = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps)
+            faster_ops = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps, args.post)
             dl.close()
     st = [r["status"] for r in res]
     out = {"decoder": args.decoder,"utterances": args.utts, "frames": frames, "lattice_s": min(lat_s), "lattice_frames_per_s": frames / min(lat_s),
@@ -491,9 +538,9 @@ def main():
             k_new = kernel_ms(ctx, lambda: khg.get_raw_lattice_simple_batch(am, tm, fsts, feats, scfg, 0.1))
             lat.update(emission_summary(k_old, k_new))
             out["lattices"] = lat
-            if args.sweep or args.prune_beam is not None:
+            if args.sweep or args.prune_beam is not None or args.post:
                 _, dl = khg.get_raw_lattice_simple_device_batch(am, tm, fsts, feats, scfg, 0.1)
-                out["lattice_ops"] = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps)
+                out["lattice_ops"] = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps, args.post)
                 dl.close()
         if args.check > 0:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
