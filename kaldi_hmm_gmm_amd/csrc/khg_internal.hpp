@@ -1,8 +1,9 @@
 // kaldi_hmm_gmm_amd/csrc/khg_internal.hpp -- what the translation units of libkhg_hip.so share: the handles behind include/khg_hip.h
 // (khg_ctx / khg_model / khg_tm / khg_utts / khg_accs), the error and allocation helpers and the few functions one unit calls in
 // another.  The units, by handle:  khg_ctx_model.hip (context, model image, transition table), khg_utts.hip (utterance sets: features +
-// graphs), khg_k1.hip (log-likelihoods), khg_k2.hip (Viterbi alignment), khg_k3.hip (accumulators + statistics), khg_c1.hip (RCCL
-// exchange), khg_k4.hip (device M-step).  gfx950 only.
+// graphs), khg_k1.hip (log-likelihoods), khg_k2.hip (Viterbi alignment), khg_lattices.hip (lattice decoders, resident lattices and their
+// posteriors: khg_lattices / khg_posteriors stay private to it), khg_k3.hip (accumulators + statistics), khg_c1.hip (RCCL exchange),
+// khg_k4.hip (device M-step).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 

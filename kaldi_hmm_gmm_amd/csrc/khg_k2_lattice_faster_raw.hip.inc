@@ -9,7 +9,7 @@
 // (One() when no final state was reached).  It is the FST whose best path the decoder kernel returns (DESIGN.md section 7f).
 //
 // The decoder's lane is serial, so the counts it keeps ARE the prefix sums inside the utterance: nothing is counted or scanned again
-// per frame or per state.  Per launch of slices: the decoder, one scan of the utterances' totals (k2_lattice_raw_scan_utts, shared with
+// per frame or per state.  Per launch of slices: the decoder, one scan of the utterances' totals (k2_lattice_scan_pairs, shared with
 // K2R), the one synchronisation that sizes the output, the fill.  No atomics: every position is a prefix sum.  When a second decoding
 // pass re-ran some utterances, k2_lattice_faster_raw_gather rebuilds a chunk from the blocks of both passes.
 
@@ -19,11 +19,7 @@ struct LfrArgs {
   LatArgs a;             // the launch's decode: graph tables, slices (laid out with the lattice rows), status
   int32_t n;             // utterances of the launch (list positions u0 .. u0 + n)
   const int64_t* utt_off;    // [2 * (n + 1)]: exclusive prefix over the launch, states at [b], arcs at [n + 1 + b]
-  // the launch's lattice arrays
-  int32_t *st_frame, *st_gstate, *st_arc_begin;
-  float *st_tot, *st_extra, *st_final;
-  int32_t *arc_ilabel, *arc_olabel, *arc_next;
-  float *arc_g, *arc_ac;
+  LatArrays out;         // the launch's lattice arrays
   int32_t* start_out;    // [U]: the utterance's start state (-1: empty lattice)
 };
 
@@ -52,22 +48,22 @@ __global__ __launch_bounds__(LFR_NT) void k2_lattice_faster_raw_fill(LfrArgs p, 
   for (int s = (int)(blockIdx.y * blockDim.x + threadIdx.x); s < ns; s += (int)(gridDim.y * blockDim.x)) {
     const int t = stok[s], f = sfr[s], ab = sarc[s];
     const int64_t sid = so + s;
-    p.st_frame[sid] = f;
-    p.st_gstate[sid] = gst[t];
-    p.st_tot[sid] = tk[t].tot;
-    p.st_extra[sid] = tk[t].extra;
-    p.st_final[sid] = tk[t].fcost;         // INF before the last frame and where final_costs_ has no entry
-    p.st_arc_begin[sid] = ab;
+    p.out.frame[sid] = f;
+    p.out.gstate[sid] = gst[t];
+    p.out.tot[sid] = tk[t].tot;
+    p.out.extra[sid] = tk[t].extra;
+    p.out.fin[sid] = tk[t].fcost;         // INF before the last frame and where final_costs_ has no entry
+    p.out.arc_begin[sid] = ab;
     const float co = coff[f];
     const int base_eps = fbase[f], base_emit = fbase[f + 1];
     int64_t pos = ao + ab;
     for (int l = tk[t].links; l >= 0; l = lk[l].next, ++pos) {
       const bool emitting = lk[l].ilabel != 0;
-      p.arc_ilabel[pos] = lk[l].ilabel;
-      p.arc_olabel[pos] = lk[l].olabel;
-      p.arc_g[pos] = lk[l].graph_cost;
-      p.arc_ac[pos] = emitting ? lk[l].acoustic_cost - co : 0.0f;
-      p.arc_next[pos] = (emitting ? base_emit : base_eps) + tk[lk[l].next_tok].pos;      // (pos: the rank in its frame by now)
+      p.out.ilabel[pos] = lk[l].ilabel;
+      p.out.olabel[pos] = lk[l].olabel;
+      p.out.g[pos] = lk[l].graph_cost;
+      p.out.ac[pos] = emitting ? lk[l].acoustic_cost - co : 0.0f;
+      p.out.next[pos] = (emitting ? base_emit : base_eps) + tk[lk[l].next_tok].pos;      // (pos: the rank in its frame by now)
     }
   }
 }

@@ -18,11 +18,7 @@
 #define LO_NT 64
 
 struct LoArgs {
-  // the chunk's lattice arrays (LatChunk) and the utterances' ranges in them
-  const int32_t *st_frame, *st_gstate, *st_arc_begin;
-  const float *st_tot, *st_extra, *st_final;
-  const int32_t *arc_ilabel, *arc_olabel, *arc_next;
-  const float *arc_g, *arc_ac;
+  LatArraysIn in;                        // the chunk's lattice arrays (LatChunk); below, the utterances' ranges in them
   const int32_t* start;                  // [U]
   const int64_t *state_off, *arc_off;    // [U + 1] over the handle
   int64_t s_base, a_base;                // state_off[u0], arc_off[u0]
@@ -46,8 +42,8 @@ struct LoArgs {
   int32_t *newid, *nab;                  // [chunk states]
   float* limit;                          // [n]
   int64_t *utt_tot, *utt_off;            // [2 * n], [2 * (n + 1)]
-  int32_t *o_frame, *o_gstate, *o_arc_begin, *o_ilabel, *o_olabel, *o_next, *o_start;
-  float *o_tot, *o_extra, *o_final, *o_g, *o_ac;
+  LatArrays out;                         // the pruned chunk's arrays
+  int32_t* o_start;                      // [U]
 };
 
 // one utterance's lattice: in LDS (staged) or in the HBM arrays
@@ -66,8 +62,8 @@ __device__ __forceinline__ LoView lo_view(const LoArgs& p, int u, int32_t* lds) 
   v.N = (int)(p.state_off[u + 1] - p.state_off[u]);
   v.A = (int)(p.arc_off[u + 1] - p.arc_off[u]);
   v.start = v.N ? p.start[u] : -1;
-  v.frame = p.st_frame + s0; v.abeg = p.st_arc_begin + s0; v.fin = p.st_final + s0;
-  v.il = p.arc_ilabel + a0; v.next = p.arc_next + a0; v.gc = p.arc_g + a0; v.ac = p.arc_ac + a0;
+  v.frame = p.in.frame + s0; v.abeg = p.in.arc_begin + s0; v.fin = p.in.fin + s0;
+  v.il = p.in.ilabel + a0; v.next = p.in.next + a0; v.gc = p.in.g + a0; v.ac = p.in.ac + a0;
   const int64_t need = 4 * (3 * (int64_t)v.N + 4 * (int64_t)v.A);
   if (lds == nullptr || need > (int64_t)p.lds_bytes) return v;          // workgroup-uniform
   int32_t* q = lds;
@@ -228,7 +224,7 @@ __global__ __launch_bounds__(LO_NT) void k2_lattice_best_path(LoArgs p) {
   int32_t* words = p.words + base + (int64_t)k * v.N;
   float v1 = 0.0f, v2 = 0.0f;
   int n = v.start, nw = 0;
-  const int32_t* ol = p.arc_olabel + (p.arc_off[u] - p.a_base);
+  const int32_t* ol = p.in.olabel + (p.arc_off[u] - p.a_base);
   for (int i = 0; i < steps; ++i) {
     const int a = pn[n * L.K];
     const int il = v.il[a];
@@ -285,7 +281,7 @@ __global__ __launch_bounds__(LO_NT) void k2_lattice_ops_last_frame(LoArgs p, int
   if (b >= p.n) return;
   const int u = p.u0 + b;
   const int64_t s1 = p.state_off[u + 1], s0 = p.state_off[u];
-  out[u] = s1 > s0 ? p.st_frame[s1 - 1 - p.s_base] : 0;
+  out[u] = s1 > s0 ? p.in.frame[s1 - 1 - p.s_base] : 0;
 }
 
 // is arc a of the kept state s kept?  (newid: >= 0 for a kept state)
@@ -426,24 +422,6 @@ __global__ __launch_bounds__(LO_NT) void k2_lattice_prune_mark(LoArgs p) {
   if (lane == 0) { p.utt_tot[2 * (int64_t)b] = sbase; p.utt_tot[2 * (int64_t)b + 1] = abase; }
 }
 
-// ---- prune, scan: one wave, the utterances' totals -> exclusive offsets over the chunk (int64), states at [b], arcs at [n + 1 + b] ----
-__global__ __launch_bounds__(64) void k2_lattice_prune_scan(LoArgs p) {
-  const int lane = (int)threadIdx.x;
-  long long ts = 0, ta = 0;
-  for (int bb = 0; bb < p.n; bb += 64) {
-    const int b = bb + lane;
-    const long long c1 = b < p.n ? p.utt_tot[2 * (int64_t)b] : 0, c2 = b < p.n ? p.utt_tot[2 * (int64_t)b + 1] : 0;
-    long long i1 = c1, i2 = c2;
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t1 = __shfl_up(i1, o), t2 = __shfl_up(i2, o);
-      if (lane >= o) { i1 += t1; i2 += t2; }
-    }
-    if (b < p.n) { p.utt_off[b] = ts + i1 - c1; p.utt_off[(int64_t)p.n + 1 + b] = ta + i2 - c2; }
-    ts += __shfl(i1, 63); ta += __shfl(i2, 63);
-  }
-  if (lane == 0) { p.utt_off[p.n] = ts; p.utt_off[2 * (int64_t)p.n + 1] = ta; }
-}
-
 // ---- prune, fill: the kept states and arcs at the positions the prefix sums give; costs as stored ----
 __global__ __launch_bounds__(LO_NT) void k2_lattice_prune_fill(LoArgs p) {
   const int b = (int)blockIdx.x, u = p.u0 + b;
@@ -458,16 +436,16 @@ __global__ __launch_bounds__(LO_NT) void k2_lattice_prune_fill(LoArgs p) {
     const int r = p.newid[s0 + s];
     if (r < 0) continue;
     const int64_t sid = so + r;
-    p.o_frame[sid] = p.st_frame[s0 + s]; p.o_gstate[sid] = p.st_gstate[s0 + s]; p.o_tot[sid] = p.st_tot[s0 + s];
-    p.o_extra[sid] = p.st_extra[s0 + s]; p.o_final[sid] = p.st_final[s0 + s];
-    p.o_arc_begin[sid] = p.nab[s0 + s];
+    p.out.frame[sid] = p.in.frame[s0 + s]; p.out.gstate[sid] = p.in.gstate[s0 + s]; p.out.tot[sid] = p.in.tot[s0 + s];
+    p.out.extra[sid] = p.in.extra[s0 + s]; p.out.fin[sid] = p.in.fin[s0 + s];
+    p.out.arc_begin[sid] = p.nab[s0 + s];
     int64_t pos = ao + p.nab[s0 + s];
     const int ae = lo_aend(v, s);
     for (int a = v.abeg[s]; a < ae; ++a) {
       if (!lo_keep_arc(p, v, s0, s, a, limit)) continue;
-      p.o_ilabel[pos] = p.arc_ilabel[a0 + a]; p.o_olabel[pos] = p.arc_olabel[a0 + a];
-      p.o_g[pos] = p.arc_g[a0 + a]; p.o_ac[pos] = p.arc_ac[a0 + a];
-      p.o_next[pos] = p.newid[s0 + v.next[a]];
+      p.out.ilabel[pos] = p.in.ilabel[a0 + a]; p.out.olabel[pos] = p.in.olabel[a0 + a];
+      p.out.g[pos] = p.in.g[a0 + a]; p.out.ac[pos] = p.in.ac[a0 + a];
+      p.out.next[pos] = p.newid[s0 + v.next[a]];
       ++pos;
     }
   }

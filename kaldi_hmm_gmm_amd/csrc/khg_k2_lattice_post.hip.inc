@@ -48,8 +48,8 @@ __global__ __launch_bounds__(64) void k2_lattice_post_index(LoArgs p, int32_t* i
   const int N = (int)(p.state_off[u + 1] - p.state_off[u]), A = (int)(p.arc_off[u + 1] - p.arc_off[u]);
   int32_t* ib = in_begin + s0 + b;
   int32_t* cu = cur + s0;
-  const int32_t* abeg = p.st_arc_begin + s0;
-  const int32_t* next = p.arc_next + a0;
+  const int32_t* abeg = p.in.arc_begin + s0;
+  const int32_t* next = p.in.next + a0;
   for (int s = lane; s < N; s += 64) {
     const int ae = s + 1 < N ? abeg[s + 1] : A;
     for (int a = abeg[s]; a < ae; ++a) arc_src[a0 + a] = s;

@@ -14,7 +14,7 @@
 //   arcs of a state in the order of the graph's arcs in that state
 // Four launches per chunk of slices, behind the decoder's: count (per frame: the rank of every surviving state among its frame's, by
 // ballot / wave prefix / LDS across waves; the surviving out-links of every state and their prefix), two scans (frames inside an
-// utterance, int32; utterances across the chunk, int64), then -- after the one synchronisation that sizes the output -- the fill,
+// utterance, int32; utterances across the chunk, int64: k2_lattice_scan_pairs), then -- after the one synchronisation that sizes the output -- the fill,
 // straight into exactly-sized arrays.  No atomics: every position is a prefix sum, so the order never depends on timing.  Frames
 // are independent in count and fill, so the grid is (utterance, frame stripe).  States above the hub threshold have their out-arcs
 // counted and filled by a whole wave, 64 arcs at a time by ballot, in arc order: the same arrays at every threshold.
@@ -24,11 +24,7 @@ struct LrArgs {
   int32_t n;             // utterances of the chunk (list positions u0 .. u0 + n)
   int64_t* utt_tot;      // [2 * n]: states, arcs of utterance b of the chunk
   int64_t* utt_off;      // [2 * (n + 1)]: exclusive prefix over the chunk, states at [b], arcs at [n + 1 + b]
-  // the chunk's lattice arrays (fill)
-  int32_t *st_frame, *st_gstate, *st_arc_begin;
-  float *st_tot, *st_extra, *st_final;
-  int32_t *arc_ilabel, *arc_olabel, *arc_next;
-  float *arc_g, *arc_ac;
+  LatArrays out;         // the chunk's lattice arrays (fill)
   int32_t* start_out;    // [U]: the utterance's start state (-1: empty lattice)
 };
 
@@ -184,7 +180,7 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_raw_count(LrArgs p, int u0) 
   }
 }
 
-// ---- scan 1: one wave per utterance, the frames' counts -> exclusive offsets in place (int32), the utterance's totals (int64) ----
+// ---- scan: one wave per utterance, the frames' counts -> exclusive offsets in place (int32), the utterance's totals (int64) ----
 __global__ __launch_bounds__(64) void k2_lattice_raw_scan_frames(LrArgs p, int u0) {
   const int lane = (int)threadIdx.x;
   const LrView v = lr_view(p.a, u0 + (int)blockIdx.x);
@@ -201,25 +197,6 @@ __global__ __launch_bounds__(64) void k2_lattice_raw_scan_frames(LrArgs p, int u
     ts += __shfl(i1, 63); ta += __shfl(i2, 63);
   }
   if (lane == 0) { p.utt_tot[2 * (int64_t)blockIdx.x] = ts; p.utt_tot[2 * (int64_t)blockIdx.x + 1] = ta; }
-}
-
-// ---- scan 2: one wave, the utterances' totals -> exclusive offsets over the chunk (int64) ----
-// (also K2F's scan, khg_decode_lattice_faster_raw, through an LrArgs with only these set: it must read nothing but n, utt_tot, utt_off)
-__global__ __launch_bounds__(64) void k2_lattice_raw_scan_utts(LrArgs p) {
-  const int lane = (int)threadIdx.x;
-  long long ts = 0, ta = 0;
-  for (int bb = 0; bb < p.n; bb += 64) {
-    const int b = bb + lane;
-    const long long c1 = b < p.n ? p.utt_tot[2 * (int64_t)b] : 0, c2 = b < p.n ? p.utt_tot[2 * (int64_t)b + 1] : 0;
-    long long i1 = c1, i2 = c2;
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t1 = __shfl_up(i1, o), t2 = __shfl_up(i2, o);
-      if (lane >= o) { i1 += t1; i2 += t2; }
-    }
-    if (b < p.n) { p.utt_off[b] = ts + i1 - c1; p.utt_off[(int64_t)p.n + 1 + b] = ta + i2 - c2; }
-    ts += __shfl(i1, 63); ta += __shfl(i2, 63);
-  }
-  if (lane == 0) { p.utt_off[p.n] = ts; p.utt_off[2 * (int64_t)p.n + 1] = ta; }
 }
 
 // ---- fill: states and arcs, at the positions the prefix sums give ----
@@ -239,11 +216,11 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_raw_fill(LrArgs p, int u0) {
   if (blockIdx.y == 0 && tid == 0) p.start_out[v.u] = v.rank[v.start];      // frame 0 starts at state 0
   const unsigned long long below = (1ull << lane) - 1ull;
   auto put_arc = [&](int64_t pos, int ai, float g, float ac, int next) {
-    p.arc_ilabel[pos] = a.in_tid[v.in0 + ai];
-    p.arc_olabel[pos] = a.in_olabel[v.in0 + ai];
-    p.arc_g[pos] = g;
-    p.arc_ac[pos] = ac;
-    p.arc_next[pos] = next;
+    p.out.ilabel[pos] = a.in_tid[v.in0 + ai];
+    p.out.olabel[pos] = a.in_olabel[v.in0 + ai];
+    p.out.g[pos] = g;
+    p.out.ac[pos] = ac;
+    p.out.next[pos] = next;
   };
   for (int f = (int)blockIdx.y; f <= v.T; f += (int)gridDim.y) {
     const float* D = v.D + (int64_t)f * v.S;
@@ -259,12 +236,12 @@ __global__ __launch_bounds__(LS_NT) void k2_lattice_raw_fill(LrArgs p, int u0) {
       const int64_t sid = so + tokbase + r;
       const int ab = arcbase + aoff[s];
       const float dm = D[s];
-      p.st_frame[sid] = f;
-      p.st_gstate[sid] = s;
-      p.st_tot[sid] = dm;
-      p.st_extra[sid] = X[s];
-      p.st_final[sid] = f == v.T ? a.final_w[v.s0 + s] : INF;
-      p.st_arc_begin[sid] = ab;
+      p.out.frame[sid] = f;
+      p.out.gstate[sid] = s;
+      p.out.tot[sid] = dm;
+      p.out.extra[sid] = X[s];
+      p.out.fin[sid] = f == v.T ? a.final_w[v.s0 + s] : INF;
+      p.out.arc_begin[sid] = ab;
       const int64_t o0 = a.out_off[v.s0 + s], o1 = a.out_off[v.s0 + s + 1];
       if (o1 - o0 > v.hub_thr) continue;         // a hub state: below
       int64_t pos = ao + ab;

@@ -1,0 +1,1134 @@
+// kaldi_hmm_gmm_amd/csrc/khg_lattices.hip -- C-ABI (include/khg_hip.h): the lattice side.  The lattice decoder
+// (khg_decode_lattice_faster, khg_k2_lattice.hip.inc) and the data-parallel LatticeSimpleDecoder (khg_decode_lattice_simple,
+// khg_k2_lattice_simple.hip.inc), each with its raw lattice (khg_decode_lattice_faster_raw, khg_k2_lattice_faster_raw.hip.inc;
+// khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc); the handle of resident lattices (khg_lattices) with the operations on it
+// (khg_k2_lattice_ops.hip.inc) and its forward-backward posteriors (khg_posteriors, khg_k2_lattice_post.hip.inc).  gfx950 only.
+#include "khg_internal.hpp"
+
+#include <memory>
+
+#include "khg_k2_hashlist.hip.inc"
+#include "khg_k2_lattice.hip.inc"
+#include "khg_k2_lattice_simple.hip.inc"
+#include "khg_k2_lattice_arrays.hip.inc"
+#include "khg_k2_lattice_raw.hip.inc"
+#include "khg_k2_lattice_faster_raw.hip.inc"
+#include "khg_k2_lattice_ops.hip.inc"
+#include "khg_k2_lattice_post.hip.inc"
+
+// ------------------------------------------------------------------------------------------
+// The raw lattices of one batch (khg_decode_lattice_simple_raw, khg_decode_lattice_faster_raw): per chunk of scratch slices one
+// exactly-sized device block holding the six per-state and five per-arc arrays of the chunk's utterances, one after the other.
+struct LatChunk {
+  int u0 = 0, n = 0;              // utterances u0 .. u0 + n
+  int64_t ns = 0, na = 0;         // states, arcs
+  unsigned char* buf = nullptr;
+  // byte offsets of the arrays inside buf: frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin | ilabel, olabel, graph_cost,
+  // acoustic_cost, nextstate
+  int64_t st[6] = {0, 0, 0, 0, 0, 0}, ar[5] = {0, 0, 0, 0, 0};
+};
+struct khg_lattices {
+  int U = 0;
+  std::vector<int64_t> state_off, arc_off;       // [U + 1]
+  std::vector<LatChunk> chunks;
+  int32_t* start_d = nullptr;                    // [U]
+  int64_t bytes = 0;
+  // what the operations on a handle need (khg_lattices_best_path / _prune), made at the first of them: state_off | arc_off on the
+  // device, the frame of every utterance's last state as offsets (the layout of an alignment)
+  int64_t* off_d = nullptr;                      // [2 * (U + 1)]
+  std::vector<int64_t> ali_off;                  // [U + 1]
+  // the in-arc index khg_lattices_posteriors gathers through, made at its first call: per chunk one block
+  // [in_begin: states + utterances | in_arc: arcs | arc_src: arcs] (int32)
+  std::vector<int32_t*> idx_d;
+};
+
+namespace {
+struct LatFree { void operator()(khg_lattices* l) const { (void)khg_lattices_destroy(l); } };
+using LatPtr = std::unique_ptr<khg_lattices, LatFree>;
+// device scratch of one call: freed on the way out
+struct DevBlocks {
+  std::vector<void*> p;
+  ~DevBlocks() { for (void* q : p) if (q) (void)hipFree(q); }
+  template <class T>
+  int alloc(int64_t count, T** out) {
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, (size_t)std::max<int64_t>(count * (int64_t)sizeof(T), 16)));
+    p.push_back(q);
+    *out = static_cast<T*>(q);
+    return KHG_OK;
+  }
+};
+
+// an empty handle of U utterances, with the start states' array
+int new_lattices(int U, LatPtr* out) {
+  LatPtr l(new khg_lattices);
+  l->U = U;
+  l->state_off.assign((size_t)U + 1, 0);
+  l->arc_off.assign((size_t)U + 1, 0);
+  if (U > 0) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&l->start_d), 4 * (size_t)U));
+    l->bytes += 4 * (int64_t)U;
+  }
+  *out = std::move(l);
+  return KHG_OK;
+}
+void lat_chunk_layout(LatChunk* ch, int64_t* total) {
+  int64_t o = 0;
+  auto take = [&](int64_t cnt) { const int64_t r = o; o += (4 * cnt + 255) & ~int64_t(255); return r; };
+  for (int k = 0; k < 6; ++k) ch->st[k] = take(ch->ns);
+  for (int k = 0; k < 5; ++k) ch->ar[k] = take(ch->na);
+  *total = o;
+}
+// the block of a chunk whose u0, n, ns, na are set; its size is added to *bytes
+int lat_chunk_alloc(LatChunk* ch, int64_t* bytes) {
+  int64_t total = 0;
+  lat_chunk_layout(ch, &total);
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&ch->buf), (size_t)std::max<int64_t>(total, 16)));
+  *bytes += total;
+  return KHG_OK;
+}
+// the chunk's arrays as kernel arguments (LatArrays to fill, LatArraysIn to read)
+template <class I, class F>
+void lat_chunk_arrays(const LatChunk& c, LatArraysT<I, F>* a) {
+  auto i = [&](int64_t o) { return reinterpret_cast<I*>(c.buf + o); };
+  auto f = [&](int64_t o) { return reinterpret_cast<F*>(c.buf + o); };
+  a->frame = i(c.st[0]); a->gstate = i(c.st[1]); a->tot = f(c.st[2]); a->extra = f(c.st[3]); a->fin = f(c.st[4]); a->arc_begin = i(c.st[5]);
+  a->ilabel = i(c.ar[0]); a->olabel = i(c.ar[1]); a->g = f(c.ar[2]); a->ac = f(c.ar[3]); a->next = i(c.ar[4]);
+}
+
+// what k2_lattice_scan_pairs left at off_d [2 * (n + 1)], as two prefix arrays [n + 1]: the one copy and the ONE synchronisation that
+// size a chunk's output
+int read_pair_offsets(khg_ctx* ctx, const int64_t* off_d, int n, std::vector<int64_t>* first, std::vector<int64_t>* second) {
+  std::vector<int64_t> h(2 * ((size_t)n + 1), 0);
+  HIPCHK(hipMemcpyAsync(h.data(), off_d, 16 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  first->assign(h.begin(), h.begin() + n + 1);
+  second->assign(h.begin() + n + 1, h.end());
+  return KHG_OK;
+}
+// a lattice's arc_begin and nextstate are int32: utterance ids[b] (nullptr: u0 + b) of a chunk with the prefix arrays so / ao is refused
+// in the name of `who` when it has more states or arcs
+int check_utt_counts(const std::string& who, const int32_t* ids, int u0, const std::vector<int64_t>& so, const std::vector<int64_t>& ao) {
+  for (size_t b = 0; b + 1 < so.size(); ++b)
+    if (so[b + 1] - so[b] > INT32_MAX || ao[b + 1] - ao[b] > INT32_MAX)
+      return khg_set_error(KHG_E_ARG, who + ": the lattice of utterance " + std::to_string(ids ? ids[b] : u0 + (int)b) +
+                                          " has more than 2^31 - 1 states or arcs");
+  return KHG_OK;
+}
+// ... and the counts of the chunk's utterances u0 .. go on a handle's two offset vectors (chunks arrive in utterance order)
+int add_chunk_counts(const std::string& who, int u0, const std::vector<int64_t>& so, const std::vector<int64_t>& ao,
+                     std::vector<int64_t>* state_off, std::vector<int64_t>* arc_off) {
+  int rc = check_utt_counts(who, nullptr, u0, so, ao);
+  if (rc) return rc;
+  for (size_t b = 0; b + 1 < so.size(); ++b) {
+    (*state_off)[(size_t)u0 + b + 1] = (*state_off)[(size_t)u0] + so[b + 1];
+    (*arc_off)[(size_t)u0 + b + 1] = (*arc_off)[(size_t)u0] + ao[b + 1];
+  }
+  return KHG_OK;
+}
+// grid.y of a fill over n utterances whose largest has max_n items: stripes of nt items go to workgroups of their own while the launch
+// has few utterances
+unsigned stripes(int64_t max_n, int nt, int n) {
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_n + nt - 1) / nt, std::max<int64_t>(1, 4096 / n)));
+}
+// Scratch slices of bytes[k] each are grouped into launches of at most 4 GiB (a slice above that is a launch of its own): launch c takes
+// the slices cb[c] .. cb[c + 1], slice k lies rel[k] bytes behind its launch's first, the largest launch needs max_chunk bytes.
+const int64_t kScratchBudget = int64_t(4) << 30;
+void split_by_budget(const std::vector<int64_t>& bytes, std::vector<size_t>* cb, std::vector<int64_t>* rel, int64_t* max_chunk) {
+  cb->assign(1, 0);
+  rel->assign(bytes.size(), 0);
+  int64_t acc = 0;
+  *max_chunk = 0;
+  for (size_t k = 0; k < bytes.size(); ++k) {
+    if (acc > 0 && acc + bytes[k] > kScratchBudget) { *max_chunk = std::max(*max_chunk, acc); cb->push_back(k); acc = 0; }
+    (*rel)[k] = acc;
+    acc += bytes[k];
+  }
+  *max_chunk = std::max(*max_chunk, acc);
+  cb->push_back(bytes.size());
+}
+}  // namespace
+
+extern "C" int khg_lattices_destroy(khg_lattices* l) {
+  if (!l) return KHG_OK;
+  for (LatChunk& c : l->chunks) if (c.buf) (void)hipFree(c.buf);
+  if (l->start_d) (void)hipFree(l->start_d);
+  if (l->off_d) (void)hipFree(l->off_d);
+  for (int32_t* q : l->idx_d) if (q) (void)hipFree(q);
+  delete l;
+  return KHG_OK;
+}
+extern "C" int khg_lattices_sizes(const khg_lattices* l, int64_t* state_off_h, int64_t* arc_off_h) {
+  if (!l) return khg_set_error(KHG_E_ARG, "khg_lattices_sizes: bad arguments");
+  if (state_off_h) std::copy(l->state_off.begin(), l->state_off.end(), state_off_h);
+  if (arc_off_h) std::copy(l->arc_off.begin(), l->arc_off.end(), arc_off_h);
+  return KHG_OK;
+}
+extern "C" int khg_lattices_device_bytes(const khg_lattices* l, int64_t* bytes) {
+  if (!l || !bytes) return khg_set_error(KHG_E_ARG, "khg_lattices_device_bytes: bad arguments");
+  *bytes = l->bytes;
+  return KHG_OK;
+}
+extern "C" int khg_lattices_download(khg_ctx* ctx, const khg_lattices* l, int32_t* frame_h, int32_t* graph_state_h, float* tot_cost_h,
+                                     float* extra_cost_h, float* final_cost_h, int32_t* arc_begin_h, int32_t* ilabel_h, int32_t* olabel_h,
+                                     float* graph_cost_h, float* acoustic_cost_h, int32_t* nextstate_h, int32_t* start_h) {
+  if (ctx_dead(ctx) || !l) return khg_set_error(KHG_E_ARG, "khg_lattices_download: bad arguments");
+  void* st_h[6] = {frame_h, graph_state_h, tot_cost_h, extra_cost_h, final_cost_h, arc_begin_h};
+  void* ar_h[5] = {ilabel_h, olabel_h, graph_cost_h, acoustic_cost_h, nextstate_h};
+  for (const LatChunk& c : l->chunks) {
+    const int64_t s0 = l->state_off[(size_t)c.u0], a0 = l->arc_off[(size_t)c.u0];
+    for (int k = 0; k < 6; ++k)
+      if (st_h[k] && c.ns) HIPCHK(hipMemcpyAsync(static_cast<char*>(st_h[k]) + 4 * s0, c.buf + c.st[k], 4 * (size_t)c.ns, hipMemcpyDeviceToHost, ctx->stream));
+    for (int k = 0; k < 5; ++k)
+      if (ar_h[k] && c.na) HIPCHK(hipMemcpyAsync(static_cast<char*>(ar_h[k]) + 4 * a0, c.buf + c.ar[k], 4 * (size_t)c.na, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (start_h && l->U) HIPCHK(hipMemcpyAsync(start_h, l->start_d, 4 * (size_t)l->U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// What the two lattice decoders share: the argument checks, the result buffers and their way back to the host.
+namespace {
+// `who`: the call the error texts name.  cfg_ok: the decoder's own Config::Check (`config_name` assertion failed).
+template <class Cfg, class Ok>
+int decode_prologue(const std::string& who, khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const Cfg* cfg, const char* config_name, Ok cfg_ok) {
+  if (ctx_dead(ctx) || !tm || !u || !cfg) return khg_set_error(KHG_E_ARG, who + ": bad arguments");
+  { int rf = utts_foreign_ctx(ctx, u, who.c_str()); if (rf) return rf; }
+  if (!u->has_graphs) return khg_set_error(KHG_E_ARG, who + ": the utterance set has no decoding graphs");
+  if (!u->ll_valid) return khg_set_error(KHG_E_ARG, who + ": call khg_loglikes first");
+  // khg_loglikes_band leaves upper bounds in the cells past the band: a token the beam keeps (or of a partial path) may read any cell
+  if (u->ll_mode == 2)
+    return khg_set_error(KHG_E_ARG, who + ": the scores come from khg_loglikes_band; call khg_loglikes (every cell) first");
+  if (!cfg_ok(*cfg)) return khg_set_error(KHG_E_RUNTIME, std::string(config_name) + " assertion failed");
+  int rc = wait_ali(ctx, u);
+  if (!rc) rc = k1_band_check(ctx, u);
+  return rc;
+}
+
+// the decoders' results on the device; the words of utterance i have room for wcap_off[i + 1] - wcap_off[i]
+struct DecodeOut {
+  int32_t *ali = nullptr, *words = nullptr, *num_words = nullptr, *status = nullptr, *err_frame = nullptr;
+  double* like = nullptr;
+  int64_t* words_off = nullptr;
+  std::vector<int64_t> wcap_off;
+  int64_t N = 0, NW = 0;          // frames, word slots
+};
+// allocates them in dv (err_frame: the simple decoder's), flushes the arena and enqueues the word offsets and the cleared alignment
+int decode_out_alloc(khg_ctx* ctx, const khg_utts* u, bool err_frame, DevBlocks* dv, DecodeOut* o) {
+  const int U = u->n_utt;
+  o->wcap_off.assign((size_t)U + 1, 0);
+  for (int i = 0; i < U; ++i) o->wcap_off[(size_t)i + 1] = o->wcap_off[(size_t)i] + (u->frame_off[i + 1] - u->frame_off[i]) + utt_states(u, i) + 64;
+  o->N = u->N; o->NW = o->wcap_off[(size_t)U];
+  int rc;
+  if ((rc = dv->alloc(std::max<int64_t>(o->N, 1), &o->ali)) || (rc = dv->alloc(std::max<int64_t>(o->NW, 1), &o->words)) ||
+      (rc = dv->alloc(U, &o->num_words)) || (rc = dv->alloc(U, &o->status)) || (err_frame && (rc = dv->alloc(U, &o->err_frame))) ||
+      (rc = dv->alloc(U, &o->like)) || (rc = dv->alloc(U + 1, &o->words_off)) || (rc = arena_flush(ctx)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(o->words_off, o->wcap_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(o->ali, 0, 4 * (size_t)std::max<int64_t>(o->N, 1), ctx->stream));
+  return KHG_OK;
+}
+// the graph tables, scores and result buffers of a decoder kernel's arguments (LatArgs, LsArgs)
+template <class Args>
+void decode_args(const khg_tm* tm, const khg_utts* u, const DecodeOut& o, Args* a) {
+  a->frame_off = u->frame_off_d; a->gidx = u->gidx_d; a->state_off = u->state_off_d; a->start = u->start_d;
+  a->in_off = u->in_off_d; a->in_col = u->in_col_d; a->in_tid = u->in_tid_d; a->in_olabel = u->in_olabel_d; a->in_w = u->in_w_d;
+  a->out_off = u->out_off_d; a->out_inidx = u->out_inidx_d; a->final_w = u->final_d;
+  a->trans_cost = tm->has_trans_cost ? tm->trans_cost_d : nullptr;
+  a->ll = u->ll_d; a->ll_off = u->ll_off_d;
+  a->ali = o.ali; a->words = o.words; a->words_off = o.words_off; a->num_words = o.num_words; a->like = o.like; a->status = o.status;
+}
+// the statuses (synchronous), for a decoder that looks at them before the rest comes back
+int decode_out_status(const DecodeOut& o, int U, std::vector<int32_t>* st) {
+  st->resize((size_t)U);
+  HIPCHK(hipMemcpy(st->data(), o.status, 4 * (size_t)U, hipMemcpyDeviceToHost));
+  return KHG_OK;
+}
+// everything the caller asked for, the words of the utterances that succeeded packed one after the other; st: decode_out_status's
+int decode_out_download(khg_ctx* ctx, const std::string& who, const DecodeOut& o, const std::vector<int32_t>& st, int32_t* ali_h,
+                        int32_t* words_h, int64_t* words_off_h, int64_t words_cap, double* like_h, int32_t* status_h, int32_t* err_frame_h) {
+  const size_t U = st.size();
+  std::vector<int32_t> nw(U), w((size_t)std::max<int64_t>(o.NW, 1));
+  if (ali_h && o.N) HIPCHK(hipMemcpyAsync(ali_h, o.ali, 4 * (size_t)o.N, hipMemcpyDeviceToHost, ctx->stream));
+  if (like_h) HIPCHK(hipMemcpyAsync(like_h, o.like, 8 * U, hipMemcpyDeviceToHost, ctx->stream));
+  if (err_frame_h) HIPCHK(hipMemcpyAsync(err_frame_h, o.err_frame, 4 * U, hipMemcpyDeviceToHost, ctx->stream));
+  if (words_h && words_off_h) {
+    HIPCHK(hipMemcpyAsync(nw.data(), o.num_words, 4 * U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(w.data(), o.words, 4 * w.size(), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (words_h && words_off_h) {
+    int64_t pos = 0;
+    for (size_t i = 0; i < U; ++i) {
+      words_off_h[i] = pos;
+      const int64_t n = (st[i] & KHG_LAT_SUCCEEDED) ? nw[i] : 0;
+      if (pos + n > words_cap) return khg_set_error(KHG_E_ARG, who + ": words_cap too small");
+      std::copy(w.begin() + o.wcap_off[i], w.begin() + o.wcap_off[i] + n, words_h + pos);
+      pos += n;
+    }
+    words_off_h[U] = pos;
+  }
+  return KHG_OK;
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
+// K2L: LatticeFasterDecoder (khg_k2_lattice.hip.inc)
+extern "C" void khg_lattice_faster_config_default(khg_lattice_faster_config* c) {
+  c->beam = 16.0f; c->max_active = INT32_MAX; c->min_active = 200; c->lattice_beam = 10.0f; c->prune_interval = 25;
+  c->beam_delta = 0.5f; c->hash_ratio = 2.0f; c->prune_scale = 0.1f; c->acoustic_scale = 1.0f; c->allow_partial = 1;
+  c->scratch_per_frame = 0;
+}
+
+namespace {
+// (lattices) what a launch emitted: an exactly-sized block of the utterances list[ch.u0 .. ch.u0 + ch.n), with their offsets inside it;
+// a block not handed to the handle is freed on the way out
+struct EmitBlock { LatChunk ch; std::vector<int64_t> so, ao; int64_t bytes = 0; };
+struct EmitBlocks {
+  std::vector<EmitBlock> v;
+  ~EmitBlocks() { for (EmitBlock& b : v) if (b.ch.buf) (void)hipFree(b.ch.buf); }
+};
+// one call of the decoder: what its passes share
+struct FasterRun {
+  khg_ctx* ctx; const khg_utts* u;
+  std::string who;                  // the call the user made
+  LatArgs a;
+  int64_t hb;
+  bool lat;                         // khg_decode_lattice_faster_raw: the slices have lattice rows, and what follows
+  int64_t *tot_d = nullptr, *off_d = nullptr;      // the utterances' (states, arcs) of a launch and their prefix
+  int32_t* start_d = nullptr;       // the handle's
+  DevBlocks dv;
+};
+
+// the lattices of the launch over list[k0 .. k0 + n), while its slices are alive: the decoder left the rows and the totals, one scan over
+// the utterances, ONE synchronisation to size the output, the fill
+int faster_emit(FasterRun& r, const std::vector<int32_t>& list, int k0, int n, EmitBlocks* blocks) {
+  khg_ctx* ctx = r.ctx;
+  {
+    KernelTimer kt(ctx, "k2_lattice_faster_raw_scan");
+    KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, r.tot_d, r.off_d, n);
+    HIPCHK(hipGetLastError());
+  }
+  blocks->v.emplace_back();
+  EmitBlock& eb = blocks->v.back();
+  int rc = read_pair_offsets(ctx, r.off_d, n, &eb.so, &eb.ao);
+  if (!rc) rc = check_utt_counts(r.who, list.data() + k0, 0, eb.so, eb.ao);
+  if (rc) return rc;
+  LatChunk& ch = eb.ch;
+  ch.u0 = k0; ch.n = n; ch.ns = eb.so[(size_t)n]; ch.na = eb.ao[(size_t)n];
+  if ((rc = lat_chunk_alloc(&ch, &eb.bytes))) return rc;
+  LfrArgs p;
+  std::memset(&p, 0, sizeof(p));
+  p.a = r.a; p.n = n; p.utt_off = r.off_d; p.start_out = r.start_d;
+  lat_chunk_arrays(ch, &p.out);
+  int64_t max_n = 0;
+  for (int b = 0; b < n; ++b) max_n = std::max(max_n, eb.so[(size_t)b + 1] - eb.so[(size_t)b]);
+  KernelTimer kt(ctx, "k2_lattice_faster_raw_fill");
+  KHG_LAUNCH(ctx, k2_lattice_faster_raw_fill, dim3((unsigned)n, stripes(max_n, LFR_NT, n)), dim3(LFR_NT), 0, ctx->stream, p, k0);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+
+// One pass over a list of utterances: each gets a scratch slice of `per_frame` tokens / links per frame (0: the automatic size,
+// -1: the whole graph per frame, i.e. an utterance can never run out); slices are grouped into launches of <= 4 GiB of scratch.
+int faster_pass(FasterRun& r, const std::vector<int32_t>& list, int64_t per_frame, EmitBlocks* blocks) {
+  khg_ctx* ctx = r.ctx;
+  const khg_utts* u = r.u;
+  LatArgs& a = r.a;
+  const size_t L = list.size();
+  std::vector<int32_t> tcap(L), lcap(L);
+  std::vector<int64_t> bytes(L);
+  for (size_t k = 0; k < L; ++k) {
+    const int i = list[k];
+    const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = utt_states(u, i), A = std::max<int64_t>(a.amax, 1);
+    const int64_t pt = per_frame > 0 ? per_frame : per_frame < 0 ? S : std::min<int64_t>(S, 256);
+    const int64_t pl = per_frame > 0 ? per_frame : per_frame < 0 ? A : std::min<int64_t>(A, 1024);
+    const int64_t tc = (T + 1) * pt + (per_frame > 0 ? 0 : S) + 1, lc = (T + 1) * pl + (per_frame > 0 ? 0 : A) + 1;
+    if (tc > INT32_MAX / 2 || lc > INT32_MAX / 2) return khg_set_error(KHG_E_ARG, r.who + ": utterance too large for the scratch");
+    tcap[k] = (int32_t)tc; lcap[k] = (int32_t)lc;
+    bytes[k] = (lat_layout(T, S, a.amax, r.hb, tc, lc, r.lat).total + 255) & ~int64_t(255);
+  }
+  std::vector<size_t> cb;
+  std::vector<int64_t> rel;
+  int64_t max_chunk = 0;
+  split_by_budget(bytes, &cb, &rel, &max_chunk);
+  unsigned char* scratch; int64_t* scr_off_d; int32_t *tcap_d, *lcap_d, *list_d;
+  int rc;
+  if ((rc = r.dv.alloc(max_chunk, &scratch)) || (rc = r.dv.alloc((int64_t)L, &scr_off_d)) || (rc = r.dv.alloc((int64_t)L, &tcap_d)) ||
+      (rc = r.dv.alloc((int64_t)L, &lcap_d)) || (rc = r.dv.alloc((int64_t)L, &list_d)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(scr_off_d, rel.data(), 8 * L, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(tcap_d, tcap.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(lcap_d, lcap.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(list_d, list.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
+  a.scratch = scratch; a.scr_off = scr_off_d; a.tok_cap = tcap_d; a.link_cap = lcap_d; a.list = list_d;
+  for (size_t c = 0; c + 1 < cb.size(); ++c) {
+    const int n = (int)(cb[c + 1] - cb[c]), k0 = (int)cb[c];
+    {
+      KernelTimer kt(ctx, "k2_lattice_faster");
+      if (r.lat) KHG_LAUNCH(ctx, k2_lattice_faster_lat, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, k0, r.tot_d);
+      else KHG_LAUNCH(ctx, k2_lattice_faster, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, k0);
+      HIPCHK(hipGetLastError());
+    }
+    if (r.lat && (rc = faster_emit(r, list, k0, n, blocks))) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));    // the slices are freed with `dv` or reused by the next pass
+  return KHG_OK;
+}
+
+// The handle: every utterance in utterance order, its chunks the first pass's launches.  Without a second pass (`again` empty) the first
+// pass's blocks are the chunks.  With one, a chunk that holds a re-decoded utterance is rebuilt on the device from the blocks of both
+// passes (k2_lattice_faster_raw_gather); only offsets travel.
+int faster_assemble(FasterRun& r, EmitBlocks& pass1, EmitBlocks& pass2, const std::vector<int32_t>& again, khg_lattices* lats) {
+  khg_ctx* ctx = r.ctx;
+  const size_t U = (size_t)lats->U;
+  // where every utterance's lattice is: block (first pass's, then second pass's), first state / arc there; its sizes go to the handle
+  std::vector<int32_t> src_blk(U, 0);
+  std::vector<int64_t> src_off(2 * U, 0);
+  std::vector<EmitBlock*> blk;
+  for (EmitBlock& b : pass1.v) blk.push_back(&b);
+  for (EmitBlock& b : pass2.v) blk.push_back(&b);
+  std::vector<char> redone(U, 0);
+  for (int32_t i : again) redone[(size_t)i] = 1;
+  for (size_t j = 0; j < blk.size(); ++j) {
+    const bool second = j >= pass1.v.size();
+    const EmitBlock& e = *blk[j];
+    for (size_t b = 0; b < (size_t)e.ch.n; ++b) {
+      const size_t i = second ? (size_t)again[(size_t)e.ch.u0 + b] : (size_t)e.ch.u0 + b;
+      if (!second && redone[i]) continue;        // (empty there: the second pass's is the one)
+      src_blk[i] = (int32_t)j;
+      src_off[2 * i] = e.so[b]; src_off[2 * i + 1] = e.ao[b];
+      lats->state_off[i + 1] = e.so[b + 1] - e.so[b]; lats->arc_off[i + 1] = e.ao[b + 1] - e.ao[b];
+    }
+  }
+  for (size_t i = 0; i < U; ++i) { lats->state_off[i + 1] += lats->state_off[i]; lats->arc_off[i + 1] += lats->arc_off[i]; }
+  LfrBlock* blocks_d = nullptr;
+  std::vector<LfrBlock> blocks_h;
+  std::vector<std::vector<int64_t>> dst_off_keep;      // (host sides of copies in flight until the synchronisation below)
+  int rc;
+  if (!again.empty()) {
+    for (const EmitBlock* e : blk) {
+      LfrBlock bd;
+      for (int j = 0; j < 6; ++j) bd.st[j] = reinterpret_cast<const int32_t*>(e->ch.buf + e->ch.st[j]);
+      for (int j = 0; j < 5; ++j) bd.ar[j] = reinterpret_cast<const int32_t*>(e->ch.buf + e->ch.ar[j]);
+      blocks_h.push_back(bd);
+    }
+    if ((rc = r.dv.alloc((int64_t)blocks_h.size(), &blocks_d))) return rc;
+    HIPCHK(hipMemcpyAsync(blocks_d, blocks_h.data(), sizeof(LfrBlock) * blocks_h.size(), hipMemcpyHostToDevice, ctx->stream));
+  }
+  for (EmitBlock& e : pass1.v) {
+    const size_t u0 = (size_t)e.ch.u0, n = (size_t)e.ch.n;
+    bool rebuild = false;
+    for (size_t b = 0; b < n; ++b) rebuild = rebuild || redone[u0 + b];
+    if (!rebuild) {
+      lats->chunks.push_back(e.ch);
+      lats->bytes += e.bytes;
+      e.ch.buf = nullptr;        // the handle's from here on
+      continue;
+    }
+    dst_off_keep.emplace_back(2 * (n + 1), 0);
+    std::vector<int64_t>& dst_off = dst_off_keep.back();
+    int64_t max_n = 1;
+    for (size_t b = 0; b < n; ++b) {
+      dst_off[b + 1] = lats->state_off[u0 + b + 1] - lats->state_off[u0];
+      dst_off[n + 2 + b] = lats->arc_off[u0 + b + 1] - lats->arc_off[u0];
+      max_n = std::max(max_n, std::max(dst_off[b + 1] - dst_off[b], dst_off[n + 2 + b] - dst_off[n + 1 + b]));
+    }
+    LatChunk ch;
+    ch.u0 = (int)u0; ch.n = (int)n; ch.ns = dst_off[n]; ch.na = dst_off[2 * n + 1];
+    if ((rc = lat_chunk_alloc(&ch, &lats->bytes))) return rc;
+    lats->chunks.push_back(ch);
+    LfrGather g;
+    std::memset(&g, 0, sizeof(g));
+    int32_t* src_blk_d; int64_t *src_off_d, *dst_off_d;
+    if ((rc = r.dv.alloc((int64_t)n, &src_blk_d)) || (rc = r.dv.alloc(2 * (int64_t)n, &src_off_d)) || (rc = r.dv.alloc(2 * ((int64_t)n + 1), &dst_off_d)))
+      return rc;
+    HIPCHK(hipMemcpyAsync(src_blk_d, src_blk.data() + u0, 4 * n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(src_off_d, src_off.data() + 2 * u0, 16 * n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dst_off_d, dst_off.data(), 16 * (n + 1), hipMemcpyHostToDevice, ctx->stream));
+    g.blocks = blocks_d; g.src_block = src_blk_d; g.src_off = src_off_d; g.dst_off = dst_off_d; g.n = (int32_t)n;
+    for (int j = 0; j < 6; ++j) g.st[j] = reinterpret_cast<int32_t*>(ch.buf + ch.st[j]);
+    for (int j = 0; j < 5; ++j) g.ar[j] = reinterpret_cast<int32_t*>(ch.buf + ch.ar[j]);
+    KernelTimer kt(ctx, "k2_lattice_faster_raw_gather");
+    KHG_LAUNCH(ctx, k2_lattice_faster_raw_gather, dim3((unsigned)n, stripes(max_n, LFR_NT, (int)n)), dim3(LFR_NT), 0, ctx->stream, g);
+    HIPCHK(hipGetLastError());
+  }
+  if (!again.empty()) return check_err_flag(ctx, r.who.c_str());     // synchronises: the blocks the chunks were gathered from go now
+  return KHG_OK;
+}
+
+// khg_decode_lattice_faster (lat_out == nullptr: nothing about lattices runs, and the slices have no lattice rows) and
+// khg_decode_lattice_faster_raw
+int decode_lattice_faster_impl(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_faster_config* cfg,
+                               int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                               double* like_h, int32_t* status_h, khg_lattices** lat_out) {
+  FasterRun r;
+  r.ctx = ctx; r.u = u; r.lat = lat_out != nullptr;
+  r.who = r.lat ? "khg_decode_lattice_faster_raw" : "khg_decode_lattice_faster";
+  // LatticeFasterDecoderConfig::Check (csrc/lattice-faster-decoder.h:99-104)
+  int rc = decode_prologue(r.who, ctx, tm, u, cfg, "LatticeFasterDecoderConfig", [](const khg_lattice_faster_config& c) {
+    return c.beam > 0.0f && c.max_active > 1 && c.lattice_beam > 0.0f && c.min_active <= c.max_active && c.prune_interval > 0 &&
+           c.beam_delta > 0.0f && c.hash_ratio >= 1.0f && c.prune_scale > 0.0f && c.prune_scale < 1.0f && c.min_active >= 0 &&
+           c.scratch_per_frame >= 0;
+  });
+  if (rc) return rc;
+  const int U = u->n_utt;
+  LatPtr lats;
+  if (r.lat && (rc = new_lattices(U, &lats))) return rc;
+  if (U == 0) { if (r.lat) *lat_out = lats.release(); return KHG_OK; }
+  if (r.lat) {
+    r.start_d = lats->start_d;
+    if ((rc = r.dv.alloc(2 * (int64_t)U, &r.tot_d)) || (rc = r.dv.alloc(2 * ((int64_t)U + 1), &r.off_d))) return rc;
+  }
+  DecodeOut o;
+  if ((rc = decode_out_alloc(ctx, u, false, &r.dv, &o))) return rc;
+  r.hb = std::max<int64_t>(1000, (int64_t)((float)u->max_states * cfg->hash_ratio)) + 1;
+  LatArgs& a = r.a;
+  decode_args(tm, u, o, &a);
+  a.hb = (int32_t)r.hb; a.amax = u->max_inarcs;     // (the kernel lays every slice out with the same arc bound)
+  a.beam = cfg->beam; a.lattice_beam = cfg->lattice_beam; a.beam_delta = cfg->beam_delta; a.hash_ratio = cfg->hash_ratio;
+  a.prune_scale = cfg->prune_scale; a.acoustic_scale = cfg->acoustic_scale;
+  a.max_active = cfg->max_active; a.min_active = cfg->min_active; a.prune_interval = cfg->prune_interval; a.allow_partial = cfg->allow_partial ? 1 : 0;
+  EmitBlocks pass1, pass2;
+  std::vector<int32_t> all((size_t)U), again, st;
+  for (int i = 0; i < U; ++i) all[(size_t)i] = i;
+  rc = faster_pass(r, all, cfg->scratch_per_frame, &pass1);
+  if (!rc) rc = check_err_flag(ctx, r.who.c_str());     // synchronises
+  if (!rc) rc = decode_out_status(o, U, &st);
+  if (rc) return rc;
+  if (cfg->scratch_per_frame == 0) {
+    // the automatic size ran out: those utterances again with room for every state and arc on every frame (a frame never holds more)
+    for (int i = 0; i < U; ++i) if (st[(size_t)i] & KHG_LAT_SCRATCH) again.push_back(i);
+    if (!again.empty()) {
+      rc = faster_pass(r, again, -1, &pass2);
+      if (!rc) rc = check_err_flag(ctx, r.who.c_str());
+      if (!rc) rc = decode_out_status(o, U, &st);
+      if (rc) return rc;
+    }
+  }
+  rc = decode_out_download(ctx, r.who, o, st, ali_h, words_h, words_off_h, words_cap, like_h, status_h, nullptr);
+  if (rc || !r.lat) return rc;
+  if ((rc = faster_assemble(r, pass1, pass2, again, lats.get()))) return rc;
+  *lat_out = lats.release();
+  return KHG_OK;
+}
+}  // namespace
+
+extern "C" int khg_decode_lattice_faster(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_faster_config* cfg,
+                                         int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                         double* like_h, int32_t* status_h) {
+  return decode_lattice_faster_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, nullptr);
+}
+extern "C" int khg_decode_lattice_faster_raw(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_faster_config* cfg,
+                                             int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                             double* like_h, int32_t* status_h, khg_lattices** out) {
+  if (!out) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_faster_raw: out is NULL");
+  *out = nullptr;
+  return decode_lattice_faster_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, out);
+}
+
+// ------------------------------------------------------------------------------------------
+// K2S: LatticeSimpleDecoder (khg_k2_lattice_simple.hip.inc)
+extern "C" void khg_lattice_simple_config_default(khg_lattice_simple_config* c) {
+  c->beam = 16.0f; c->lattice_beam = 10.0f; c->prune_interval = 25; c->prune_scale = 0.1f; c->acoustic_scale = 1.0f;
+  c->allow_partial = 1; c->scratch_per_frame = 0;
+}
+
+namespace {
+// the lattices of the chunk of utterances u0 .. u0 + p.n, while its slices are alive: count, the two scans, ONE synchronisation to size
+// the output, the fill
+int simple_emit(khg_ctx* ctx, LrArgs p, int u0, int nt, int64_t max_T, khg_lattices* lats) {
+  const int n = p.n;
+  // frames are independent: stripes of them go to workgroups of their own while the chunk has few utterances
+  const unsigned gy = (unsigned)std::min<int64_t>(max_T + 1, std::max<int64_t>(1, 1024 / n));
+  {
+    KernelTimer kt(ctx, "k2_lattice_raw_count");
+    KHG_LAUNCH(ctx, k2_lattice_raw_count, dim3((unsigned)n, gy), dim3(nt), 0, ctx->stream, p, u0);
+    HIPCHK(hipGetLastError());
+  }
+  {
+    KernelTimer kt(ctx, "k2_lattice_raw_scan");
+    KHG_LAUNCH(ctx, k2_lattice_raw_scan_frames, dim3((unsigned)n), dim3(64), 0, ctx->stream, p, u0);
+    KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, p.utt_tot, p.utt_off, n);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<int64_t> so, ao;
+  int rc = read_pair_offsets(ctx, p.utt_off, n, &so, &ao);
+  if (!rc) rc = add_chunk_counts("khg_decode_lattice_simple_raw", u0, so, ao, &lats->state_off, &lats->arc_off);
+  if (rc) return rc;
+  LatChunk ch;
+  ch.u0 = u0; ch.n = n; ch.ns = so[(size_t)n]; ch.na = ao[(size_t)n];
+  if ((rc = lat_chunk_alloc(&ch, &lats->bytes))) return rc;
+  lats->chunks.push_back(ch);
+  lat_chunk_arrays(ch, &p.out);
+  KernelTimer kt(ctx, "k2_lattice_raw_fill");
+  KHG_LAUNCH(ctx, k2_lattice_raw_fill, dim3((unsigned)n, gy), dim3(nt), 0, ctx->stream, p, u0);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+
+// khg_decode_lattice_simple (lat_out == nullptr: nothing about lattices runs) and khg_decode_lattice_simple_raw
+int decode_lattice_simple_impl(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_simple_config* cfg,
+                               int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                               double* like_h, int32_t* status_h, int32_t* err_frame_h, khg_lattices** lat_out) {
+  const std::string who = "khg_decode_lattice_simple";
+  // LatticeSimpleDecoderConfig::Check (csrc/lattice-simple-decoder.h:76-78)
+  int rc = decode_prologue(who, ctx, tm, u, cfg, "LatticeSimpleDecoderConfig", [](const khg_lattice_simple_config& c) {
+    return c.beam > 0.0f && c.lattice_beam > 0.0f && c.prune_interval > 0 && c.scratch_per_frame >= 0;
+  });
+  if (rc) return rc;
+  const int U = u->n_utt;
+  const bool lat = lat_out != nullptr;
+  LatPtr lats;
+  if (lat && (rc = new_lattices(U, &lats))) return rc;
+  if (U == 0) { if (lat) *lat_out = lats.release(); return KHG_OK; }
+  DevBlocks dv;
+  LrArgs p;          // (lattices) the chunks' emit
+  std::memset(&p, 0, sizeof(p));
+  if (lat) {
+    p.start_out = lats->start_d;
+    if ((rc = dv.alloc(2 * (int64_t)U, &p.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)U + 1), &p.utt_off))) return rc;
+  }
+  DecodeOut o;
+  if ((rc = decode_out_alloc(ctx, u, true, &dv, &o))) return rc;
+  LsArgs a;
+  decode_args(tm, u, o, &a);
+  a.in_src = u->in_src_d; a.err_frame = o.err_frame;
+  a.beam = cfg->beam; a.lattice_beam = cfg->lattice_beam; a.acoustic_scale = cfg->acoustic_scale;
+  a.prune_interval = cfg->prune_interval; a.tok_cap = cfg->scratch_per_frame; a.amax = u->max_inarcs;
+  a.hub = ctx->opt[KHG_OPT_K2S_HUB];
+  // every utterance's dense rows, grouped into launches of <= 4 GiB of scratch (an utterance larger than that alone is refused)
+  std::vector<int64_t> bytes((size_t)U);
+  int64_t max_T = 0;
+  for (int i = 0; i < U; ++i) {
+    const int64_t T = u->frame_off[i + 1] - u->frame_off[i], S = utt_states(u, i);
+    bytes[(size_t)i] = ls_layout(T, S, u->max_inarcs, lat).total;     // (the kernel lays every slice out with the same arc bound)
+    if (bytes[(size_t)i] > kScratchBudget)
+      return khg_set_error(KHG_E_ARG, who + ": utterance " + std::to_string(i) + " needs more than 4 GiB of lattice scratch");
+    max_T = std::max(max_T, T);
+  }
+  std::vector<size_t> cb;
+  std::vector<int64_t> rel;
+  int64_t max_chunk = 0;
+  split_by_budget(bytes, &cb, &rel, &max_chunk);
+  unsigned char* scratch; int64_t* scr_off_d; int32_t* list_d;
+  if ((rc = dv.alloc(max_chunk, &scratch)) || (rc = dv.alloc(U, &scr_off_d)) || (rc = dv.alloc(U, &list_d))) return rc;
+  std::vector<int32_t> all((size_t)U);
+  for (int i = 0; i < U; ++i) all[(size_t)i] = i;
+  HIPCHK(hipMemcpyAsync(scr_off_d, rel.data(), 8 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(list_d, all.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+  a.scratch = scratch; a.scr_off = scr_off_d; a.list = list_d;
+  p.a = a;
+  // one wave for small graphs, up to four for larger ones (a lane owns states s = lane, lane + NT, ...)
+  const int nt = u->max_states <= 64 ? 64 : u->max_states <= 128 ? 128 : LS_NT;
+  for (size_t c = 0; c + 1 < cb.size(); ++c) {
+    const int n = (int)(cb[c + 1] - cb[c]), u0 = (int)cb[c];
+    {
+      KernelTimer kt(ctx, "k2_lattice_simple");
+      KHG_LAUNCH(ctx, k2_lattice_simple, dim3((unsigned)n), dim3(nt), 0, ctx->stream, a, u0);
+      HIPCHK(hipGetLastError());
+    }
+    p.n = n;
+    if (lat && (rc = simple_emit(ctx, p, u0, nt, max_T, lats.get()))) return rc;
+    if (c + 2 < cb.size()) HIPCHK(hipStreamSynchronize(ctx->stream));     // the next launch reuses the slices
+  }
+  rc = check_err_flag(ctx, who.c_str());     // synchronises
+  std::vector<int32_t> st;
+  if (!rc) rc = decode_out_status(o, U, &st);
+  if (!rc) rc = decode_out_download(ctx, who, o, st, ali_h, words_h, words_off_h, words_cap, like_h, status_h, err_frame_h);
+  if (rc) return rc;
+  if (lat) *lat_out = lats.release();
+  return KHG_OK;
+}
+}  // namespace
+
+extern "C" int khg_decode_lattice_simple(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_simple_config* cfg,
+                                         int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                         double* like_h, int32_t* status_h, int32_t* err_frame_h) {
+  return decode_lattice_simple_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, err_frame_h, nullptr);
+}
+extern "C" int khg_decode_lattice_simple_raw(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_lattice_simple_config* cfg,
+                                             int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
+                                             double* like_h, int32_t* status_h, int32_t* err_frame_h, khg_lattices** out) {
+  if (!out) return khg_set_error(KHG_E_ARG, "khg_decode_lattice_simple_raw: out is NULL");
+  *out = nullptr;
+  return decode_lattice_simple_impl(ctx, tm, u, cfg, ali_h, words_h, words_off_h, words_cap, like_h, status_h, err_frame_h, out);
+}
+
+// ------------------------------------------------------------------------------------------
+// K2O: operations on device-resident lattices (khg_k2_lattice_ops.hip.inc)
+namespace {
+const int64_t kLatOpsLds = 48 << 10;        // an utterance's lattice is staged into LDS up to this many bytes
+
+void lat_chunk_args(const khg_lattices* l, const LatChunk& c, LoArgs* p) {
+  lat_chunk_arrays(c, &p->in);
+  p->start = l->start_d; p->state_off = l->off_d; p->arc_off = l->off_d + l->U + 1;
+  p->s_base = l->state_off[(size_t)c.u0]; p->a_base = l->arc_off[(size_t)c.u0];
+  p->u0 = c.u0; p->n = c.n; p->U = l->U;
+}
+// the dynamic LDS a launch over chunk c asks for: the largest lattice of the chunk that still fits, with per_state bytes of the kernel's
+// own beside every staged state
+int lat_chunk_lds(const khg_ctx* ctx, const khg_lattices* l, const LatChunk& c, int64_t per_state = 0) {
+  if (ctx->opt[KHG_OPT_LAT_OPS_LDS] == 1) return 0;
+  int64_t best = 0;
+  for (int u = c.u0; u < c.u0 + c.n; ++u) {
+    const int64_t N = l->state_off[(size_t)u + 1] - l->state_off[(size_t)u], A = l->arc_off[(size_t)u + 1] - l->arc_off[(size_t)u];
+    const int64_t need = per_state * N + 4 * (3 * N + 4 * A);
+    if (need <= kLatOpsLds) best = std::max(best, need);
+  }
+  return (int)best;
+}
+// the offsets on the device and the alignment layout, once per handle
+int lat_meta(khg_ctx* ctx, khg_lattices* l) {
+  if (l->off_d || l->U == 0) { if (l->ali_off.empty()) l->ali_off.assign((size_t)l->U + 1, 0); return KHG_OK; }
+  const size_t U = (size_t)l->U;
+  int64_t* off_d = nullptr;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&off_d), 16 * (U + 1)));
+  l->off_d = off_d;
+  l->bytes += 16 * (int64_t)(U + 1);
+  HIPCHK(hipMemcpyAsync(off_d, l->state_off.data(), 8 * (U + 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(off_d + U + 1, l->arc_off.data(), 8 * (U + 1), hipMemcpyHostToDevice, ctx->stream));
+  DevBlocks dv;
+  int32_t* t_d = nullptr;
+  int rc = dv.alloc((int64_t)U, &t_d);
+  if (rc) return rc;
+  for (const LatChunk& c : l->chunks) {
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    KHG_LAUNCH(ctx, k2_lattice_ops_last_frame, dim3((unsigned)((c.n + LO_NT - 1) / LO_NT)), dim3(LO_NT), 0, ctx->stream, p, t_d);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<int32_t> t(U);
+  HIPCHK(hipMemcpyAsync(t.data(), t_d, 4 * U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  l->ali_off.assign(U + 1, 0);
+  for (size_t u = 0; u < U; ++u) l->ali_off[u + 1] = l->ali_off[u] + std::max(t[u], 0);
+  return KHG_OK;
+}
+// the largest count among the chunk's utterances in a handle's offsets
+int64_t chunk_max(const std::vector<int64_t>& off, const LatChunk& c) {
+  int64_t m = 0;
+  for (int u = c.u0; u < c.u0 + c.n; ++u) m = std::max(m, off[(size_t)u + 1] - off[(size_t)u]);
+  return m;
+}
+bool bad_scale(float x) { return !(x >= 0.0f) || x == std::numeric_limits<float>::infinity(); }
+}  // namespace
+
+extern "C" int khg_lattices_validate(int32_t n_utt, const int64_t* state_off, const int64_t* arc_off, const int32_t* frame, const int32_t* graph_state,
+                                     const float* tot_cost, const float* extra_cost, const float* final_cost, const int32_t* arc_begin,
+                                     const int32_t* ilabel, const int32_t* olabel, const float* graph_cost, const float* acoustic_cost,
+                                     const int32_t* nextstate, const int32_t* start) {
+  if (n_utt < 0 || !state_off || !arc_off || state_off[0] != 0 || arc_off[0] != 0)
+    return khg_set_error(KHG_E_ARG, "khg_lattices_upload: bad arguments (offsets start at 0)");
+  const int64_t NS = state_off[n_utt], NA = arc_off[n_utt];
+  if ((NS > 0 && (!frame || !graph_state || !tot_cost || !extra_cost || !final_cost || !arc_begin)) ||
+      (NA > 0 && (!ilabel || !olabel || !graph_cost || !acoustic_cost || !nextstate)) || (n_utt > 0 && !start))
+    return khg_set_error(KHG_E_ARG, "khg_lattices_upload: bad arguments (an array is NULL)");
+  for (int u = 0; u < n_utt; ++u) {
+    const std::string who = "khg_lattices_upload: utterance " + std::to_string(u) + ": ";
+    const int64_t s0 = state_off[u], a0 = arc_off[u], N = state_off[u + 1] - s0, A = arc_off[u + 1] - a0;
+    if (N < 0 || A < 0 || N > INT32_MAX || A > INT32_MAX) return khg_set_error(KHG_E_ARG, who + "state_off / arc_off must not decrease (and stay below 2^31 per utterance)");
+    if (N == 0) {
+      if (A != 0) return khg_set_error(KHG_E_ARG, who + "arcs without states");
+      if (start[u] != -1) return khg_set_error(KHG_E_ARG, who + "start out of range (an empty lattice has start -1)");
+      continue;
+    }
+    if (arc_begin[s0] != 0) return khg_set_error(KHG_E_ARG, who + "arc_begin must run from 0 to the number of arcs");
+    for (int64_t s = 0; s < N; ++s) {
+      const int64_t end = s + 1 < N ? arc_begin[s0 + s + 1] : A;
+      if (arc_begin[s0 + s] > end) return khg_set_error(KHG_E_ARG, who + "arc_begin not monotone");
+      if (frame[s0 + s] < 0 || (s > 0 && frame[s0 + s] < frame[s0 + s - 1])) return khg_set_error(KHG_E_ARG, who + "states must be ordered by frame");
+    }
+    if (start[u] < 0 || start[u] >= N) return khg_set_error(KHG_E_ARG, who + "start out of range");
+    if (frame[s0 + start[u]] != 0) return khg_set_error(KHG_E_ARG, who + "start must be on frame 0");
+    for (int64_t s = 0; s < N; ++s) {
+      const int64_t end = s + 1 < N ? arc_begin[s0 + s + 1] : A;
+      for (int64_t a = arc_begin[s0 + s]; a < end; ++a) {
+        const int32_t k = nextstate[a0 + a];
+        if (k < 0 || k >= N) return khg_set_error(KHG_E_ARG, who + "nextstate out of range");
+        if (ilabel[a0 + a] != 0 && frame[s0 + k] != frame[s0 + s] + 1)
+          return khg_set_error(KHG_E_ARG, who + "an emitting arc must go from frame f to frame f + 1 (arc " + std::to_string(a) + ")");
+        if (ilabel[a0 + a] == 0 && frame[s0 + k] != frame[s0 + s])
+          return khg_set_error(KHG_E_ARG, who + "an epsilon arc must stay in its frame (arc " + std::to_string(a) + ")");
+      }
+    }
+  }
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_num_utts(const khg_lattices* l, int32_t* n_utt) {
+  if (!l || !n_utt) return khg_set_error(KHG_E_ARG, "khg_lattices_num_utts: bad arguments");
+  *n_utt = l->U;
+  return KHG_OK;
+}
+extern "C" int khg_lattices_num_chunks(const khg_lattices* l, int32_t* n_chunks) {
+  if (!l || !n_chunks) return khg_set_error(KHG_E_ARG, "khg_lattices_num_chunks: bad arguments");
+  *n_chunks = (int32_t)l->chunks.size();
+  return KHG_OK;
+}
+extern "C" int khg_lattices_chunk_utts(const khg_lattices* l, int32_t* first_utt) {
+  if (!l || !first_utt) return khg_set_error(KHG_E_ARG, "khg_lattices_chunk_utts: bad arguments");
+  for (size_t c = 0; c < l->chunks.size(); ++c) first_utt[c] = l->chunks[c].u0;
+  first_utt[l->chunks.size()] = l->chunks.empty() ? 0 : l->U;
+  return KHG_OK;
+}
+extern "C" int khg_lattices_ali_layout(khg_ctx* ctx, const khg_lattices* lc, int64_t* ali_off_h) {
+  if (ctx_dead(ctx) || !lc || !ali_off_h) return khg_set_error(KHG_E_ARG, "khg_lattices_ali_layout: bad arguments");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (rc) return rc;
+  std::copy(l->ali_off.begin(), l->ali_off.end(), ali_off_h);
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_upload(khg_ctx* ctx, int32_t n_utt, const int64_t* state_off, const int64_t* arc_off, const int32_t* frame,
+                                   const int32_t* graph_state, const float* tot_cost, const float* extra_cost, const float* final_cost,
+                                   const int32_t* arc_begin, const int32_t* ilabel, const int32_t* olabel, const float* graph_cost,
+                                   const float* acoustic_cost, const int32_t* nextstate, const int32_t* start, khg_lattices** out) {
+  if (ctx_dead(ctx) || !out) return khg_set_error(KHG_E_ARG, "khg_lattices_upload: bad arguments");
+  *out = nullptr;
+  int rc = khg_lattices_validate(n_utt, state_off, arc_off, frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin, ilabel, olabel,
+                                 graph_cost, acoustic_cost, nextstate, start);
+  if (rc) return rc;
+  LatPtr l;
+  if ((rc = new_lattices(n_utt, &l))) return rc;
+  l->state_off.assign(state_off, state_off + n_utt + 1);
+  l->arc_off.assign(arc_off, arc_off + n_utt + 1);
+  if (n_utt == 0) { *out = l.release(); return KHG_OK; }
+  LatChunk ch;
+  ch.u0 = 0; ch.n = n_utt; ch.ns = state_off[n_utt]; ch.na = arc_off[n_utt];
+  if ((rc = lat_chunk_alloc(&ch, &l->bytes))) return rc;
+  l->chunks.push_back(ch);
+  rc = arena_flush(ctx);
+  if (rc) return rc;
+  const void* st_h[6] = {frame, graph_state, tot_cost, extra_cost, final_cost, arc_begin};
+  const void* ar_h[5] = {ilabel, olabel, graph_cost, acoustic_cost, nextstate};
+  for (int k = 0; k < 6; ++k) if (ch.ns) HIPCHK(hipMemcpyAsync(ch.buf + ch.st[k], st_h[k], 4 * (size_t)ch.ns, hipMemcpyHostToDevice, ctx->stream));
+  for (int k = 0; k < 5; ++k) if (ch.na) HIPCHK(hipMemcpyAsync(ch.buf + ch.ar[k], ar_h[k], 4 * (size_t)ch.na, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(l->start_d, start, 4 * (size_t)n_utt, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));        // the host arrays are the caller's again
+  *out = l.release();
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_best_path(khg_ctx* ctx, const khg_lattices* lc, int32_t n_scales, const float* graph_scale, const float* acoustic_scale,
+                                      int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap, float* weight_h, int32_t* status_h) {
+  if (ctx_dead(ctx) || !lc || n_scales < 1 || !graph_scale || !acoustic_scale) return khg_set_error(KHG_E_ARG, "khg_lattices_best_path: bad arguments");
+  for (int k = 0; k < n_scales; ++k)
+    if (bad_scale(graph_scale[k]) || bad_scale(acoustic_scale[k]))
+      return khg_set_error(KHG_E_ARG, "khg_lattices_best_path: scale pair " + std::to_string(k) + ": graph_scale and acoustic_scale must be finite and >= 0");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U, K = n_scales;
+  if (words_off_h) std::fill(words_off_h, words_off_h + (int64_t)K * U + 1, 0);
+  if (U == 0) return KHG_OK;
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (rc) return rc;
+  const int64_t KU = (int64_t)K * U, AT = l->ali_off[(size_t)U];
+  DevBlocks dv;
+  int32_t *ali_d, *nw_d, *status_d, *packed_d;
+  float *weight_d, *gs_d, *as_d;
+  int64_t *ali_off_d, *woff_d;
+  if ((rc = dv.alloc(std::max<int64_t>((int64_t)K * AT, 1), &ali_d)) || (rc = dv.alloc(KU, &nw_d)) || (rc = dv.alloc(KU, &status_d)) ||
+      (rc = dv.alloc(2 * KU, &weight_d)) || (rc = dv.alloc(K, &gs_d)) || (rc = dv.alloc(K, &as_d)) || (rc = dv.alloc(U + 1, &ali_off_d)) ||
+      (rc = dv.alloc(KU + 1, &woff_d)))
+    return rc;
+  HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>((int64_t)K * AT, 1), ctx->stream));
+  HIPCHK(hipMemcpyAsync(gs_d, graph_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(as_d, acoustic_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  std::vector<LoArgs> pcs;
+  for (const LatChunk& c : l->chunks) {
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    p.lds_bytes = lat_chunk_lds(ctx, l, c);
+    p.K = K; p.gs = gs_d; p.as = as_d; p.ali = ali_d; p.ali_off = ali_off_d; p.ali_total = AT;
+    p.nwords = nw_d; p.weight = weight_d; p.status = status_d;
+    const int64_t cells = std::max<int64_t>(c.ns * K, 1);
+    if ((rc = dv.alloc(cells, &p.d1)) || (rc = dv.alloc(cells, &p.d2)) || (rc = dv.alloc(cells, &p.n1)) || (rc = dv.alloc(cells, &p.n2)) ||
+        (rc = dv.alloc(cells, &p.bp)) || (rc = dv.alloc(cells, &p.words)))
+      return rc;
+    {
+      KernelTimer kt(ctx, "k2_lattice_best_path");
+      KHG_LAUNCH(ctx, k2_lattice_best_path, dim3((unsigned)c.n, (unsigned)((K + LO_NT - 1) / LO_NT)), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    pcs.push_back(p);
+  }
+  // the words, packed on the device: a scan of the counts, one synchronisation to size the block, the copy
+  std::vector<int64_t> woff((size_t)KU + 1, 0);
+  std::vector<int32_t> packed, st((size_t)KU);
+  if (words_h && words_off_h) {
+    {
+      KernelTimer kt(ctx, "k2_lattice_ops_words");
+      KHG_LAUNCH(ctx, k2_lattice_ops_scan, dim3(1), dim3(64), 0, ctx->stream, nw_d, woff_d, KU);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(woff.data(), woff_d, 8 * ((size_t)KU + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const int64_t NW = woff[(size_t)KU];
+    if ((rc = dv.alloc(std::max<int64_t>(NW, 1), &packed_d))) return rc;
+    if (NW > 0) {
+      KernelTimer kt(ctx, "k2_lattice_ops_words");
+      for (const LoArgs& p : pcs)
+        KHG_LAUNCH(ctx, k2_lattice_ops_pack_words, dim3((unsigned)p.n, (unsigned)std::min(K, 64)), dim3(LO_NT), 0, ctx->stream, p, woff_d, packed_d);
+      HIPCHK(hipGetLastError());
+      packed.resize((size_t)NW);
+      HIPCHK(hipMemcpyAsync(packed.data(), packed_d, 4 * (size_t)NW, hipMemcpyDeviceToHost, ctx->stream));
+    }
+  }
+  if (ali_h && AT) HIPCHK(hipMemcpyAsync(ali_h, ali_d, 4 * (size_t)((int64_t)K * AT), hipMemcpyDeviceToHost, ctx->stream));
+  if (weight_h) HIPCHK(hipMemcpyAsync(weight_h, weight_d, 8 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
+  rc = check_err_flag(ctx, "khg_lattices_best_path");     // synchronises
+  if (rc) return rc;
+  if (words_h && words_off_h) {
+    int64_t o = 0;
+    for (int64_t i = 0; i < KU; ++i) {
+      words_off_h[i] = o;
+      int64_t n = (st[(size_t)i] & KHG_LAT_SUCCEEDED) ? woff[(size_t)i + 1] - woff[(size_t)i] : 0;
+      if (o + n > words_cap) { st[(size_t)i] = KHG_LAT_WORDS; n = 0; }      // the path's words do not fit: none of them
+      std::copy(packed.begin() + woff[(size_t)i], packed.begin() + woff[(size_t)i] + n, words_h + o);
+      o += n;
+    }
+    words_off_h[KU] = o;
+  }
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_prune(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, float beam, int32_t* status_h,
+                                  khg_lattices** out) {
+  if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, "khg_lattices_prune: bad arguments");
+  *out = nullptr;
+  if (bad_scale(graph_scale) || bad_scale(acoustic_scale))
+    return khg_set_error(KHG_E_ARG, "khg_lattices_prune: graph_scale and acoustic_scale must be finite and >= 0");
+  if (!(beam >= 0.0f)) return khg_set_error(KHG_E_ARG, "khg_lattices_prune: beam must be >= 0 (+inf allowed)");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  LatPtr res;
+  int rc = new_lattices(U, &res);
+  if (rc) return rc;
+  if (U == 0) { *out = res.release(); return KHG_OK; }
+  rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (rc) return rc;
+  DevBlocks dv;
+  int32_t* status_d;
+  if ((rc = dv.alloc(U, &status_d))) return rc;
+  std::vector<int64_t> so, ao;
+  for (const LatChunk& c : l->chunks) {
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    p.lds_bytes = lat_chunk_lds(ctx, l, c);
+    p.K = 1; p.gs1 = graph_scale; p.as1 = acoustic_scale; p.beam = beam; p.status = status_d; p.o_start = res->start_d;
+    const int64_t cells = std::max<int64_t>(c.ns, 1);
+    if ((rc = dv.alloc(cells, &p.d1)) || (rc = dv.alloc(cells, &p.d2)) || (rc = dv.alloc(cells, &p.n1)) || (rc = dv.alloc(cells, &p.n2)) ||
+        (rc = dv.alloc(cells, &p.e1)) || (rc = dv.alloc(cells, &p.e2)) || (rc = dv.alloc(cells, &p.bp)) || (rc = dv.alloc(cells, &p.pn)) ||
+        (rc = dv.alloc(cells, &p.newid)) || (rc = dv.alloc(cells, &p.nab)) || (rc = dv.alloc(c.n, &p.limit)) ||
+        (rc = dv.alloc(2 * (int64_t)c.n, &p.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.utt_off)))
+      return rc;
+    {
+      KernelTimer kt(ctx, "k2_lattice_prune_mark");
+      KHG_LAUNCH(ctx, k2_lattice_prune_mark, dim3((unsigned)c.n), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    {
+      KernelTimer kt(ctx, "k2_lattice_prune_scan");
+      KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, p.utt_tot, p.utt_off, c.n);
+      HIPCHK(hipGetLastError());
+    }
+    rc = read_pair_offsets(ctx, p.utt_off, c.n, &so, &ao);        // the one synchronisation that sizes the output
+    if (!rc) rc = add_chunk_counts("khg_lattices_prune", c.u0, so, ao, &res->state_off, &res->arc_off);
+    if (rc) return rc;
+    LatChunk ch;
+    ch.u0 = c.u0; ch.n = c.n; ch.ns = so[(size_t)c.n]; ch.na = ao[(size_t)c.n];
+    if ((rc = lat_chunk_alloc(&ch, &res->bytes))) return rc;
+    res->chunks.push_back(ch);
+    lat_chunk_arrays(ch, &p.out);
+    {
+      KernelTimer kt(ctx, "k2_lattice_prune_fill");
+      KHG_LAUNCH(ctx, k2_lattice_prune_fill, dim3((unsigned)c.n, stripes(chunk_max(l->state_off, c), LO_NT, c.n)), dim3(LO_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  std::vector<int32_t> st((size_t)U);
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  rc = check_err_flag(ctx, "khg_lattices_prune");     // synchronises: the scratch goes with `dv`
+  if (rc) return rc;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  *out = res.release();
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2P: forward-backward posteriors of device-resident lattices (khg_k2_lattice_post.hip.inc)
+struct PostChunk {
+  int u0 = 0, n = 0;
+  int64_t nf = 0, ne = 0, na = 0;      // frames, entries, arcs
+  double* arc_post = nullptr;          // [na], the lattice handle's arc order
+  unsigned char* buf = nullptr;        // entry_begin int64 [nf + 1] (relative to the chunk) | weight double [ne] | tid int32 [ne]
+  int64_t o_weight = 0, o_tid = 0;
+};
+struct khg_posteriors {
+  int U = 0;
+  std::vector<int64_t> frame_off, entry_off, arc_off;     // [U + 1]
+  std::vector<PostChunk> chunks;
+  int64_t bytes = 0;
+};
+
+namespace {
+struct PostFree { void operator()(khg_posteriors* p) const { (void)khg_posteriors_destroy(p); } };
+// the in-arc index, once per handle
+int lat_index(khg_ctx* ctx, khg_lattices* l) {
+  if (l->idx_d.size() == l->chunks.size()) return KHG_OK;
+  DevBlocks dv;
+  for (size_t k = l->idx_d.size(); k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    const int64_t words = c.ns + c.n + 2 * c.na;
+    int32_t* blk = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&blk), (size_t)std::max<int64_t>(4 * words, 16)));
+    l->idx_d.push_back(blk);
+    l->bytes += 4 * words;
+    int32_t* cur = nullptr;
+    int rc = dv.alloc(std::max<int64_t>(c.ns, 1), &cur);
+    if (rc) return rc;
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    KernelTimer kt(ctx, "k2_lattice_post_index");
+    KHG_LAUNCH(ctx, k2_lattice_post_index, dim3((unsigned)c.n), dim3(64), 0, ctx->stream, p, blk, blk + c.ns + c.n, blk + c.ns + c.n + c.na, cur);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // the cursors go with `dv`
+  return KHG_OK;
+}
+}  // namespace
+
+extern "C" int khg_posteriors_destroy(khg_posteriors* p) {
+  if (!p) return KHG_OK;
+  for (PostChunk& c : p->chunks) {
+    if (c.arc_post) (void)hipFree(c.arc_post);
+    if (c.buf) (void)hipFree(c.buf);
+  }
+  delete p;
+  return KHG_OK;
+}
+extern "C" int khg_posteriors_sizes(const khg_posteriors* p, int64_t* frame_off_h, int64_t* entry_off_h) {
+  if (!p) return khg_set_error(KHG_E_ARG, "khg_posteriors_sizes: bad arguments");
+  if (frame_off_h) std::copy(p->frame_off.begin(), p->frame_off.end(), frame_off_h);
+  if (entry_off_h) std::copy(p->entry_off.begin(), p->entry_off.end(), entry_off_h);
+  return KHG_OK;
+}
+extern "C" int khg_posteriors_device_bytes(const khg_posteriors* p, int64_t* bytes) {
+  if (!p || !bytes) return khg_set_error(KHG_E_ARG, "khg_posteriors_device_bytes: bad arguments");
+  *bytes = p->bytes;
+  return KHG_OK;
+}
+extern "C" int khg_posteriors_download(khg_ctx* ctx, const khg_posteriors* p, int64_t* entry_begin_h, int32_t* tid_h, double* weight_h,
+                                       double* arc_post_h) {
+  if (ctx_dead(ctx) || !p) return khg_set_error(KHG_E_ARG, "khg_posteriors_download: bad arguments");
+  if (entry_begin_h) entry_begin_h[0] = 0;
+  for (const PostChunk& c : p->chunks) {
+    const int64_t f0 = p->frame_off[(size_t)c.u0], e0 = p->entry_off[(size_t)c.u0], a0 = p->arc_off[(size_t)c.u0];
+    if (entry_begin_h) HIPCHK(hipMemcpyAsync(entry_begin_h + f0, c.buf, 8 * ((size_t)c.nf + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (weight_h && c.ne) HIPCHK(hipMemcpyAsync(weight_h + e0, c.buf + c.o_weight, 8 * (size_t)c.ne, hipMemcpyDeviceToHost, ctx->stream));
+    if (tid_h && c.ne) HIPCHK(hipMemcpyAsync(tid_h + e0, c.buf + c.o_tid, 4 * (size_t)c.ne, hipMemcpyDeviceToHost, ctx->stream));
+    if (arc_post_h && c.na) HIPCHK(hipMemcpyAsync(arc_post_h + a0, c.arc_post, 8 * (size_t)c.na, hipMemcpyDeviceToHost, ctx->stream));
+    // a chunk's entry_begin counts from the chunk's first entry; chunk k + 1's first element lands on chunk k's last
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (entry_begin_h) for (int64_t f = 0; f <= c.nf; ++f) entry_begin_h[f0 + f] += e0;
+  }
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_posteriors(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, int32_t* status_h,
+                                       double* tot_like_h, khg_posteriors** out) {
+  if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, "khg_lattices_posteriors: bad arguments");
+  *out = nullptr;
+  if (bad_scale(graph_scale) || bad_scale(acoustic_scale))
+    return khg_set_error(KHG_E_ARG, "khg_lattices_posteriors: graph_scale and acoustic_scale must be finite and >= 0");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
+  res->U = U;
+  res->frame_off.assign((size_t)U + 1, 0);
+  res->entry_off.assign((size_t)U + 1, 0);
+  res->arc_off = l->arc_off;
+  if (U == 0) { *out = res.release(); return KHG_OK; }
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc) rc = lat_index(ctx, l);
+  if (rc) return rc;
+  DevBlocks dv;
+  int32_t* status_d; double* tot_d; int64_t* ali_off_d;
+  if ((rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &tot_d)) || (rc = dv.alloc(U + 1, &ali_off_d))) return rc;
+  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  std::vector<int64_t> fo, eo;
+  for (size_t k = 0; k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    PoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p.lo);
+    p.lo.lds_bytes = lat_chunk_lds(ctx, l, c, 24);       // alpha, beta and the Jacobi row (doubles) beside the staged lattice
+    p.lo.status = status_d; p.lo.ali_off = ali_off_d; p.tot = tot_d;
+    p.in_begin = l->idx_d[k]; p.in_arc = l->idx_d[k] + c.ns + c.n; p.arc_src = l->idx_d[k] + c.ns + c.n + c.na;
+    p.gs = (double)graph_scale; p.as = (double)acoustic_scale;
+    p.f_base = l->ali_off[(size_t)c.u0];
+    const int64_t nfr = l->ali_off[(size_t)c.u0 + c.n] - p.f_base;
+    const int64_t cells = std::max<int64_t>(c.ns, 1), arcs = std::max<int64_t>(c.na, 1);
+    if ((rc = dv.alloc(cells, &p.alpha)) || (rc = dv.alloc(cells, &p.beta)) || (rc = dv.alloc(cells, &p.row)) || (rc = dv.alloc(arcs, &p.flag)) ||
+        (rc = dv.alloc(arcs, &p.rank)) || (rc = dv.alloc(std::max<int64_t>(nfr, 1), &p.fcnt)) || (rc = dv.alloc(nfr + 2 * (int64_t)c.n, &p.fstate)) ||
+        (rc = dv.alloc(2 * (int64_t)c.n, &p.lo.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.lo.utt_off)))
+      return rc;
+    PostChunk pc;
+    pc.u0 = c.u0; pc.n = c.n; pc.na = c.na;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&pc.arc_post), (size_t)(8 * arcs)));
+    res->chunks.push_back(pc);
+    res->bytes += 8 * c.na;
+    p.arc_post = pc.arc_post;
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_fb");
+      KHG_LAUNCH(ctx, k2_lattice_post_fb, dim3((unsigned)c.n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_scan");       // frames at [b], entries at [n + 1 + b]
+      KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, p.lo.utt_tot, p.lo.utt_off, c.n);
+      HIPCHK(hipGetLastError());
+    }
+    rc = read_pair_offsets(ctx, p.lo.utt_off, c.n, &fo, &eo);        // the one synchronisation that sizes the output
+    if (!rc) rc = add_chunk_counts("khg_lattices_posteriors", c.u0, fo, eo, &res->frame_off, &res->entry_off);
+    if (rc) return rc;
+    PostChunk& q = res->chunks.back();
+    q.nf = fo[(size_t)c.n]; q.ne = eo[(size_t)c.n];
+    q.o_weight = (8 * (q.nf + 1) + 255) & ~int64_t(255);
+    q.o_tid = q.o_weight + ((8 * q.ne + 255) & ~int64_t(255));
+    const int64_t total = q.o_tid + 4 * q.ne;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&q.buf), (size_t)std::max<int64_t>(total, 16)));
+    res->bytes += total;
+    p.entry_begin = reinterpret_cast<int64_t*>(q.buf); p.weight = reinterpret_cast<double*>(q.buf + q.o_weight);
+    p.tid = reinterpret_cast<int32_t*>(q.buf + q.o_tid);
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_fill");
+      KHG_LAUNCH(ctx, k2_lattice_post_fill, dim3((unsigned)c.n, stripes(chunk_max(l->arc_off, c), PO_NT, c.n)), dim3(PO_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  std::vector<int32_t> st((size_t)U);
+  std::vector<double> tl((size_t)U);
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(tl.data(), tot_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  rc = check_err_flag(ctx, "khg_lattices_posteriors");     // synchronises: the scratch goes with `dv`
+  if (rc) return rc;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (tot_like_h) std::copy(tl.begin(), tl.end(), tot_like_h);
+  *out = res.release();
+  return KHG_OK;
+}

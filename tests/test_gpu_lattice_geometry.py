@@ -180,7 +180,7 @@ BEAMS3 = [0.0, 0.5, INF]
 
 @pytest.mark.parametrize("U", gc.UTT_CUTS)
 def test_more_utterances_than_a_tile_of_the_scans(setup, U):
-    """U = 64, 65, 129, 162 of the rule lattices with empty ones at 0, 63, 64, 65 (and last): k2_lattice_prune_scan,
+    """U = 64, 65, 129, 162 of the rule lattices with empty ones at 0, 63, 64, 65 (and last): k2_lattice_scan_pairs,
     k2_lattice_ops_scan and k2_lattice_ops_last_frame carry a total from one 64-wide tile to the next."""
     khg = setup[0]
     lats = gc.many_utterances()[:U]
