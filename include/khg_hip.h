@@ -198,6 +198,11 @@ int khg_utts_graph_bytes(const khg_utts *u, int64_t *bytes);
 /* number of distinct pdfs on each utterance's graph, and the list itself (sorted) */
 int khg_utts_num_pdfs(const khg_utts *u, int64_t *pdf_off_h /* [n_utt+1] */);
 int khg_utts_pdfs(const khg_utts *u, int32_t *pdfs_h /* [pdf_off[n_utt]] */);
+/* What khg_align would launch for this set under the context's current options (read-only: launches and allocates nothing; for
+ * tests): out = { KS, DEG, FAST, GMEM, SC -- the template arguments of the exact-DP kernel k2_viterbi_dp --, threads per block,
+ * dynamic LDS bytes, order-faithful decoder for what the DP cannot certify: 0 one-lane LDS, 1 one-lane HBM, 2 wave LDS, 3 wave HBM,
+ * 4 chain }.  The generic form is KS = DEG = 1, FAST = 0. */
+int khg_utts_k2_plan(khg_ctx *ctx, const khg_utts *u, int32_t out[8]);
 /* per listed pdf: the first frame a decoder token can read it at (fewest emitting arcs from the start state
  * to an arc carrying it; INT32_MAX if never; 0 for sets without graphs) -- what khg_loglikes_reachable uses */
 int khg_utts_pdf_first(const khg_utts *u, int32_t *first_h /* [pdf_off[n_utt]] */);

@@ -31,6 +31,118 @@ static int ensure_ali(khg_ctx* ctx, khg_utts* u) {
   return u_alloc(u, &u->ali_d, (size_t)u->N);
 }
 
+// ------------------------------------------------------------------------------------------
+// The ONE dispatch rule of khg_align: which instantiation of k2_viterbi_dp runs a set under the context's current options, its block
+// size and dynamic LDS, and which order-faithful decoder follows for what the DP cannot certify.  khg_align launches what this says;
+// khg_utts_k2_plan hands the same answer to a test (nothing is launched or allocated here).
+struct K2Plan {
+  int KS = 1, DEG = 1;                       // k2_viterbi_dp<KS, DEG, FAST, GMEM, SC>
+  bool FAST = false, GMEM = false, SC = false;
+  int nthr = 64;
+  size_t lds_dp = 0;                         // the DP's tables: dynamic LDS, or (GMEM) its slice of the HBM scratch
+  size_t max_npdf = 0;
+  int faithful = 0;                          // 0 one-lane LDS, 1 one-lane HBM, 2 wave LDS, 3 wave HBM, 4 chain
+  int odeg_w = 0, odeg_c = 1;
+  size_t lds_f = 0, lds_w_mut = 0, lds_w_graph = 0, lds_chain = 0;
+  size_t gscratch_stride = 0;                // HBM scratch per utterance (0: none needed)
+};
+
+static K2Plan k2_plan(const khg_ctx* ctx, const khg_utts* u) {
+  K2Plan p;
+  const size_t S = (size_t)u->max_states, A = (size_t)u->max_inarcs;
+  size_t max_npdf = 0;
+  for (int i = 0; i < u->n_utt; ++i) max_npdf = std::max<size_t>(max_npdf, (size_t)(u->pdf_off[i + 1] - u->pdf_off[i]));
+  p.max_npdf = max_npdf;
+  // threads: one destination state each (up to 1024), KS states per thread beyond that
+  int nthr = (int)std::min<size_t>(1024, (S + 63) / 64 * 64);
+  const int ks_force = ctx->opt[KHG_OPT_K2_KS];   // experiment: states per thread on the register-resident path
+  if (ks_force == 2 || ks_force == 4) nthr = (int)std::min<size_t>(1024, ((S + ks_force - 1) / ks_force + 63) / 64 * 64);
+  p.nthr = nthr;
+  const size_t nwave = nthr / 64;
+  // register-resident path for the whole batch: in-degree <= 3 (up to 4 states per thread) or <= 6 (one state per thread)
+  const bool deg6 = !u->has_eps && u->max_indeg > 3 && u->max_indeg <= 6 && S <= 1024;
+  const bool fast = deg6 || (!u->has_eps && u->max_indeg <= 3 && S <= 4096);
+  const int KSsel = !fast ? 0 : ((ks_force == 2 || ks_force == 4) && !deg6 && S <= (size_t)1024 * ks_force ? ks_force : (S <= 1024 ? 1 : (S <= 2048 ? 2 : 4)));
+  const size_t NSl = fast ? KSsel : 1;
+  // trace-back block: fast = five groups of eight layers, one dword per lane and state slot; generic = 33 layers of bytes
+  // (fast: also the waves' strips of parked layer minima / counts, 2.5 KB each, in the same area during the forward pass)
+  const size_t tb_bytes = fast ? std::max<size_t>(5 * (size_t)nthr * NSl * 4, 2560 * nwave) : (K2_FB + 1) * ((S + 15) & ~size_t(15));
+  // cur | nxt | reductions | arcs | in_off | wave minima/counts | flags | [align] | max(score block (generic), trace-back block)
+  size_t lds_dp = 16 * S + 8 * K2_MAXW + 8 * A + 4 * (S + 1) + 8 * K2_FB * nwave + 32 + 8 * K2_MAXW + 16 +
+                  std::max<size_t>(fast ? 0 : 4 * K2_SB * (max_npdf | 1), tb_bytes) + 64;
+  size_t HB = std::max<size_t>(2 * S, 1000);
+  const size_t lds_f = 32 * S + 8 * HB + 4 * (S + A) + 4 * S + 4 * (S + 1) + 16 * A + A + 64;
+  // The order-faithful decoder for the utterances the DP cannot certify: the wave-parallel form with all its tables in LDS; with the
+  // graph tables in an HBM scratch slice per utterance (> ~1600 states on a chain graph); the one-lane form beyond that.
+  // KHG_K2_SERIAL = 1: always the one-lane form; 2: the HBM-graph wave form wherever its per-frame tables fit (tests, A/B).
+  const int odeg_w = u->max_outdeg <= 8 ? std::max(1, (int)u->max_outdeg) : 0;     // 0: exact slot prefix sums
+  const bool use_pos = u->has_eps || S > 1000;
+  const size_t lds_w_mut = 16 * S + 8 * S + 4 * 4 * S + 4 * S + 4 * max_npdf + (odeg_w ? 0 : 4 * A + 4 * S) + (use_pos ? 4 * S : 0) +
+                           (u->has_eps ? 4 * (S + A + 1) : 0) + 8 + 8 * ((std::max(A, S * (size_t)odeg_w) + 63) / 64 + 1);
+  const size_t lds_w_graph = 8 * (S + 1) + 5 * 4 * A + (u->has_eps ? 4 * (S + 1) + 4 * A : 0) + A + S + 64;
+  const int fmode = ctx->opt[KHG_OPT_K2_SERIAL];
+  // The chain form (k2_viterbi_faithful_chain: no epsilon-input arcs, <= 1000 states, out-degree <= 4 -- a linear transcript's training
+  // graph): a third of the wave form's latency per frame.  KHG_K2_SERIAL = 3: the general wave form also where the chain form applies.
+  const int odeg_c = (int)std::max<int32_t>(1, u->max_outdeg);
+  const size_t S4 = (S + 3) & ~size_t(3);
+  // the frame loop's tables: token costs x 2 + state keys (24) | first / winner (8) | token states x 2 (4): 36 per state; per out-arc slot:
+  // parked cost (8) + record (8) + info (4, GetCutoff's array over it) + ordinal (1); the score row.  Over them, set-up and tail only:
+  // in-arc offsets (4 per state) + sources (2 per arc) + the trace-back's 9 rows.
+  const size_t lds_chain = std::max<size_t>(36 * S4 + 21 * S4 * (size_t)odeg_c + 4 * max_npdf,
+                                            4 * (S4 + 1) + 2 * A + 16 + 9 * ((S + 15) & ~size_t(15))) + 128;
+  const bool chain = fmode == 0 && !u->has_eps && S <= 1000 && u->max_outdeg <= 4 && lds_chain <= 64 * 1024 && max_npdf <= 32767;
+  const bool wave_lds = (fmode == 0 || fmode == 3) && S <= 65535 && lds_w_mut + lds_w_graph <= 160 * 1024;
+  const bool wave_gm = fmode != 1 && !wave_lds && S <= 65535 && lds_w_mut <= 160 * 1024;
+  const bool lane_gm = !wave_lds && !wave_gm && lds_f > 160 * 1024;
+  p.faithful = chain ? 4 : wave_gm ? 3 : wave_lds ? 2 : lane_gm ? 1 : 0;
+  p.odeg_w = odeg_w; p.odeg_c = odeg_c;
+  p.lds_f = lds_f; p.lds_w_mut = lds_w_mut; p.lds_w_graph = lds_w_graph; p.lds_chain = lds_chain;
+  // Graphs whose DP tables exceed the 160 KB of LDS (a large decoding graph, not a training graph): the generic DP runs with its
+  // tables carved out of the same HBM scratch slice.
+  const bool gmem = lds_dp > 160 * 1024;
+  if (gmem) // (the generic DP's carve-up: no register-resident path)
+    lds_dp = 16 * S + 8 * K2_MAXW + 8 * A + 4 * (S + 1) + 8 * K2_FB * nwave + 32 + 8 * K2_MAXW + 16 +
+             std::max<size_t>(4 * K2_SB * (max_npdf | 1), (K2_FB + 1) * ((S + 15) & ~size_t(15))) + 64;
+  p.lds_dp = lds_dp;
+  if (gmem || wave_gm || lane_gm)
+    p.gscratch_stride = (std::max(gmem ? lds_dp : 0, std::max(wave_gm ? lds_w_graph : 0, lane_gm ? lds_f : 0)) + 255) & ~size_t(255);
+  if (gmem) { p.GMEM = true; return p; }     // <1, 1, false, true>
+  // in-degree <= 2 (a linear transcript's chain of HMM states: self-loop + forward arc): the two-slot instantiation, a sixth fewer
+  // instructions per layer than the three-slot one (the layer loop is bound by VALU issue; every slot is evaluated, empty or not)
+  const bool deg2 = fast && !deg6 && KSsel == 1 && u->max_indeg <= 2 && ctx->opt[KHG_OPT_K2_KS] != 3;
+  // (KHG_K2_KS = 3: the general three-slot kernel, for the A/B)
+  const bool sc2 = deg2 && u->same_col;     // ... and one score row per state: one score block / cost conversion per state
+  const bool sc3 = fast && !deg6 && !deg2 && KSsel == 1 && u->same_col && ctx->opt[KHG_OPT_K2_KS] != 3;   // three slots, one score row per state
+  // Two / four states per thread (graphs of more than 1024 / 2048 states): a block of 1024 threads leaves 128 registers per lane;
+  // the three-slot form needs ~180 at two states per thread (84 registers spilled at the one-state kernels' budget of 96: a
+  // transcript of > 340 phones ran 9x slower per frame than one of 330), the two-slot forms of chain graphs fit (round 4)
+  const bool deg2m = fast && !deg6 && KSsel > 1 && u->max_indeg <= 2;
+  auto form = [&](int ks, int deg, bool sc) { p.KS = ks; p.DEG = deg; p.FAST = true; p.SC = sc; };
+  if (deg6) form(1, 6, false);
+  else if (sc2) form(1, 2, true);
+  else if (deg2) form(1, 2, false);
+  else if (sc3) form(1, 3, true);
+  else if (KSsel == 1) form(1, 3, false);
+  else if (KSsel == 2 && deg2m && u->same_col) form(2, 2, true);
+  else if (KSsel == 2 && deg2m) form(2, 2, false);
+  else if (KSsel == 2) form(2, 3, false);
+  else if (KSsel == 4 && deg2m && u->same_col) form(4, 2, true);
+  else if (KSsel == 4 && deg2m) form(4, 2, false);
+  else if (KSsel == 4) form(4, 3, false);
+  // else: the generic LDS form <1, 1, false>
+  return p;
+}
+
+extern "C" int khg_utts_k2_plan(khg_ctx* ctx, const khg_utts* u, int32_t out[8]) {
+  if (ctx_dead(ctx) || !u || !out) return khg_set_error(KHG_E_ARG, "khg_utts_k2_plan: bad arguments");
+  { int rf = utts_foreign_ctx(ctx, u, "khg_utts_k2_plan"); if (rf) return rf; }
+  if (!u->has_graphs) return khg_set_error(KHG_E_ARG, "khg_utts_k2_plan: the utterance set has no decoding graphs");
+  const K2Plan p = k2_plan(ctx, u);
+  out[0] = p.KS; out[1] = p.DEG; out[2] = p.FAST ? 1 : 0; out[3] = p.GMEM ? 1 : 0; out[4] = p.SC ? 1 : 0;
+  out[5] = p.nthr; out[6] = p.GMEM ? 0 : (int32_t)p.lds_dp; out[7] = p.faithful;
+  return KHG_OK;
+}
+
 extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_align_config* cfg,
                          int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
                          float* like_h, int32_t* status_h) {
@@ -115,92 +227,36 @@ extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_
   a.beam_delta = cfg->beam_delta; a.hash_ratio = cfg->hash_ratio;
   a.max_active = cfg->max_active; a.min_active = cfg->min_active;
   a.max_states = u->max_states; a.max_inarcs = u->max_inarcs;
-  const size_t S = (size_t)u->max_states, A = (size_t)u->max_inarcs;
-  size_t max_npdf = 0;
-  for (int i = 0; i < u->n_utt; ++i) max_npdf = std::max<size_t>(max_npdf, (size_t)(u->pdf_off[i + 1] - u->pdf_off[i]));
-  // threads: one destination state each (up to 1024), KS states per thread beyond that
-  int nthr = (int)std::min<size_t>(1024, (S + 63) / 64 * 64);
-  const int ks_force = ctx->opt[KHG_OPT_K2_KS];   // experiment: states per thread on the register-resident path
-  if (ks_force == 2 || ks_force == 4) nthr = (int)std::min<size_t>(1024, ((S + ks_force - 1) / ks_force + 63) / 64 * 64);
-  const size_t nwave = nthr / 64;
-  // register-resident path for the whole batch: in-degree <= 3 (up to 4 states per thread) or <= 6 (one state per thread)
-  const bool deg6 = !u->has_eps && u->max_indeg > 3 && u->max_indeg <= 6 && S <= 1024;
-  const bool fast = deg6 || (!u->has_eps && u->max_indeg <= 3 && S <= 4096);
-  const int KSsel = !fast ? 0 : ((ks_force == 2 || ks_force == 4) && !deg6 && S <= (size_t)1024 * ks_force ? ks_force : (S <= 1024 ? 1 : (S <= 2048 ? 2 : 4)));
-  const size_t NSl = fast ? KSsel : 1;
-  // trace-back block: fast = five groups of eight layers, one dword per lane and state slot; generic = 33 layers of bytes
-  // (fast: also the waves' strips of parked layer minima / counts, 2.5 KB each, in the same area during the forward pass)
-  const size_t tb_bytes = fast ? std::max<size_t>(5 * (size_t)nthr * NSl * 4, 2560 * nwave) : (K2_FB + 1) * ((S + 15) & ~size_t(15));
-  // cur | nxt | reductions | arcs | in_off | wave minima/counts | flags | [align] | max(score block (generic), trace-back block)
-  size_t lds_dp = 16 * S + 8 * K2_MAXW + 8 * A + 4 * (S + 1) + 8 * K2_FB * nwave + 32 + 8 * K2_MAXW + 16 +
-                  std::max<size_t>(fast ? 0 : 4 * K2_SB * (max_npdf | 1), tb_bytes) + 64;
-  size_t HB = std::max<size_t>(2 * S, 1000);
-  size_t lds_f = 32 * S + 8 * HB + 4 * (S + A) + 4 * S + 4 * (S + 1) + 16 * A + A + 64;
-  // The order-faithful decoder for the utterances the DP cannot certify: the wave-parallel form with all its tables in LDS; with the
-  // graph tables in an HBM scratch slice per utterance (> ~1600 states on a chain graph); the one-lane form beyond that.
-  // KHG_K2_SERIAL = 1: always the one-lane form; 2: the HBM-graph wave form wherever its per-frame tables fit (tests, A/B).
-  const int odeg_w = u->max_outdeg <= 8 ? std::max(1, (int)u->max_outdeg) : 0;     // 0: exact slot prefix sums
-  const bool use_pos = u->has_eps || S > 1000;
-  const size_t lds_w_mut = 16 * S + 8 * S + 4 * 4 * S + 4 * S + 4 * max_npdf + (odeg_w ? 0 : 4 * A + 4 * S) + (use_pos ? 4 * S : 0) +
-                           (u->has_eps ? 4 * (S + A + 1) : 0) + 8 + 8 * ((std::max(A, S * (size_t)odeg_w) + 63) / 64 + 1);
-  const size_t lds_w_graph = 8 * (S + 1) + 5 * 4 * A + (u->has_eps ? 4 * (S + 1) + 4 * A : 0) + A + S + 64;
-  const int fmode = ctx->opt[KHG_OPT_K2_SERIAL];
-  // The chain form (k2_viterbi_faithful_chain: no epsilon-input arcs, <= 1000 states, out-degree <= 4 -- a linear transcript's training
-  // graph): a third of the wave form's latency per frame.  KHG_K2_SERIAL = 3: the general wave form also where the chain form applies.
-  const int odeg_c = (int)std::max<int32_t>(1, u->max_outdeg);
-  const size_t S4 = (S + 3) & ~size_t(3);
-  // the frame loop's tables: token costs x 2 + state keys (24) | first / winner (8) | token states x 2 (4): 36 per state; per out-arc slot:
-  // parked cost (8) + record (8) + info (4, GetCutoff's array over it) + ordinal (1); the score row.  Over them, set-up and tail only:
-  // in-arc offsets (4 per state) + sources (2 per arc) + the trace-back's 9 rows.
-  const size_t lds_chain = std::max<size_t>(36 * S4 + 21 * S4 * (size_t)odeg_c + 4 * max_npdf,
-                                            4 * (S4 + 1) + 2 * A + 16 + 9 * ((S + 15) & ~size_t(15))) + 128;
-  const bool chain = fmode == 0 && !u->has_eps && S <= 1000 && u->max_outdeg <= 4 && lds_chain <= 64 * 1024 && max_npdf <= 32767;
-  const bool wave_lds = (fmode == 0 || fmode == 3) && S <= 65535 && lds_w_mut + lds_w_graph <= 160 * 1024;
-  const bool wave_gm = fmode != 1 && !wave_lds && S <= 65535 && lds_w_mut <= 160 * 1024;
-  const bool lane_gm = !wave_lds && !wave_gm && lds_f > 160 * 1024;
-  // Graphs whose DP tables exceed the 160 KB of LDS (a large decoding graph, not a training graph): the generic DP runs with its
-  // tables carved out of the same HBM scratch slice.
-  const bool gmem = lds_dp > 160 * 1024;
+  const K2Plan plan = k2_plan(ctx, u);
+  const int nthr = plan.nthr;
+  const size_t lds_dp = plan.lds_dp, max_npdf = plan.max_npdf;
   a.gscratch = nullptr; a.gscratch_stride = 0;
-  if (gmem) // (the generic DP's carve-up: no register-resident path)
-    lds_dp = 16 * S + 8 * K2_MAXW + 8 * A + 4 * (S + 1) + 8 * K2_FB * nwave + 32 + 8 * K2_MAXW + 16 +
-             std::max<size_t>(4 * K2_SB * (max_npdf | 1), (K2_FB + 1) * ((S + 15) & ~size_t(15))) + 64;
-  if (gmem || wave_gm || lane_gm) {
-    const size_t stride = (std::max(gmem ? lds_dp : 0, std::max(wave_gm ? lds_w_graph : 0, lane_gm ? lds_f : 0)) + 255) & ~size_t(255);
-    const size_t need = stride * (size_t)u->n_utt;
+  if (plan.gscratch_stride) {
+    const size_t need = plan.gscratch_stride * (size_t)u->n_utt;
     if (need > u->k2_gscratch_bytes) {
       DEVFREE(u->k2_gscratch_d);
       { int rg = u_alloc(u, &u->k2_gscratch_d, need); if (rg) return rg; }
       u->k2_gscratch_bytes = need;
     }
-    a.gscratch = u->k2_gscratch_d; a.gscratch_stride = (int64_t)stride;
+    a.gscratch = u->k2_gscratch_d; a.gscratch_stride = (int64_t)plan.gscratch_stride;
   }
-  if (gmem) {
+  if (plan.GMEM) {
     KernelTimer kt(ctx, "k2_viterbi_dp");
     KHG_LAUNCH(ctx, (k2_viterbi_dp<1, 1, false, true>), dim3(u->n_utt), dim3(nthr), 0, ctx->stream, a);
   } else {
-    // in-degree <= 2 (a linear transcript's chain of HMM states: self-loop + forward arc): the two-slot instantiation, a sixth fewer
-    // instructions per layer than the three-slot one (the layer loop is bound by VALU issue; every slot is evaluated, empty or not)
-    const bool deg2 = fast && !deg6 && KSsel == 1 && u->max_indeg <= 2 && ctx->opt[KHG_OPT_K2_KS] != 3;
-    // (KHG_K2_KS = 3: the general three-slot kernel, for the A/B)
-    const bool sc2 = deg2 && u->same_col;     // ... and one score row per state: one score block / cost conversion per state
-    const bool sc3 = fast && !deg6 && !deg2 && KSsel == 1 && u->same_col && ctx->opt[KHG_OPT_K2_KS] != 3;   // three slots, one score row per state
-    // Two / four states per thread (graphs of more than 1024 / 2048 states): a block of 1024 threads leaves 128 registers per lane;
-    // the three-slot form needs ~180 at two states per thread (84 registers spilled at the one-state kernels' budget of 96: a
-    // transcript of > 340 phones ran 9x slower per frame than one of 330), the two-slot forms of chain graphs fit (round 4)
-    const bool deg2m = fast && !deg6 && KSsel > 1 && u->max_indeg <= 2;
+    const int form = plan.FAST ? 100 * plan.KS + 10 * plan.DEG + (plan.SC ? 1 : 0) : 0;     // <KS, DEG, true, false, SC>; 0: the generic form
 #define K2_DP_CASES(X)                                                                                         \
-    if (deg6) X((k2_viterbi_dp<1, 6, true>));                                                                  \
-    else if (sc2) X((k2_viterbi_dp<1, 2, true, false, true>));                                                 \
-    else if (deg2) X((k2_viterbi_dp<1, 2, true>));                                                             \
-    else if (sc3) X((k2_viterbi_dp<1, 3, true, false, true>));                                                 \
-    else if (KSsel == 1) X((k2_viterbi_dp<1, 3, true>));                                                       \
-    else if (KSsel == 2 && deg2m && u->same_col) X((k2_viterbi_dp<2, 2, true, false, true>));                  \
-    else if (KSsel == 2 && deg2m) X((k2_viterbi_dp<2, 2, true>));                                              \
-    else if (KSsel == 2) X((k2_viterbi_dp<2, 3, true>));                                                       \
-    else if (KSsel == 4 && deg2m && u->same_col) X((k2_viterbi_dp<4, 2, true, false, true>));                  \
-    else if (KSsel == 4 && deg2m) X((k2_viterbi_dp<4, 2, true>));                                              \
-    else if (KSsel == 4) X((k2_viterbi_dp<4, 3, true>));                                                       \
+    if (form == 160) X((k2_viterbi_dp<1, 6, true>));                                                           \
+    else if (form == 121) X((k2_viterbi_dp<1, 2, true, false, true>));                                         \
+    else if (form == 120) X((k2_viterbi_dp<1, 2, true>));                                                      \
+    else if (form == 131) X((k2_viterbi_dp<1, 3, true, false, true>));                                         \
+    else if (form == 130) X((k2_viterbi_dp<1, 3, true>));                                                      \
+    else if (form == 221) X((k2_viterbi_dp<2, 2, true, false, true>));                                         \
+    else if (form == 220) X((k2_viterbi_dp<2, 2, true>));                                                      \
+    else if (form == 230) X((k2_viterbi_dp<2, 3, true>));                                                      \
+    else if (form == 421) X((k2_viterbi_dp<4, 2, true, false, true>));                                         \
+    else if (form == 420) X((k2_viterbi_dp<4, 2, true>));                                                      \
+    else if (form == 430) X((k2_viterbi_dp<4, 3, true>));                                                      \
     else X((k2_viterbi_dp<1, 1, false>));
 #define K2_SET_LDS(FN) HIPCHK(hipFuncSetAttribute((const void*)FN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dp))
 #define K2_LAUNCH(FN) KHG_LAUNCH(ctx, FN, dim3(u->n_utt), dim3(nthr), lds_dp, ctx->stream, a)
@@ -230,26 +286,26 @@ extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_
   if (rc) return rc;
   {
     KernelTimer kt(ctx, "k2_viterbi_faithful", side);
-    if (chain) {
+    if (plan.faithful == 4) {
 #define K2_CHAIN(OD)                                                                                                            \
   do {                                                                                                                          \
-    if (lds_chain > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_viterbi_faithful_chain<OD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_chain)); \
-    KHG_LAUNCH(ctx, k2_viterbi_faithful_chain<OD>, dim3(u->n_utt), dim3(64), lds_chain, side, a, (int)max_npdf);                \
+    if (plan.lds_chain > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_viterbi_faithful_chain<OD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_chain)); \
+    KHG_LAUNCH(ctx, k2_viterbi_faithful_chain<OD>, dim3(u->n_utt), dim3(64), plan.lds_chain, side, a, (int)max_npdf);                \
   } while (0)
-      switch (odeg_c) { case 1: K2_CHAIN(1); break; case 2: K2_CHAIN(2); break; case 3: K2_CHAIN(3); break; default: K2_CHAIN(4); break; }
+      switch (plan.odeg_c) { case 1: K2_CHAIN(1); break; case 2: K2_CHAIN(2); break; case 3: K2_CHAIN(3); break; default: K2_CHAIN(4); break; }
 #undef K2_CHAIN
-    } else if (wave_gm) {
-      if (lds_w_mut > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_viterbi_faithful_wave<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w_mut));
-      KHG_LAUNCH(ctx, k2_viterbi_faithful_wave<true>, dim3(u->n_utt), dim3(64), lds_w_mut, side, a, u->has_eps ? 1 : 0, odeg_w, (int)max_npdf);
-    } else if (wave_lds) {
-      const size_t lds_w = lds_w_mut + lds_w_graph;
+    } else if (plan.faithful == 3) {
+      if (plan.lds_w_mut > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_viterbi_faithful_wave<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_w_mut));
+      KHG_LAUNCH(ctx, k2_viterbi_faithful_wave<true>, dim3(u->n_utt), dim3(64), plan.lds_w_mut, side, a, u->has_eps ? 1 : 0, plan.odeg_w, (int)max_npdf);
+    } else if (plan.faithful == 2) {
+      const size_t lds_w = plan.lds_w_mut + plan.lds_w_graph;
       if (lds_w > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_viterbi_faithful_wave<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));
-      KHG_LAUNCH(ctx, k2_viterbi_faithful_wave<false>, dim3(u->n_utt), dim3(64), lds_w, side, a, u->has_eps ? 1 : 0, odeg_w, (int)max_npdf);
-    } else if (lane_gm) {
+      KHG_LAUNCH(ctx, k2_viterbi_faithful_wave<false>, dim3(u->n_utt), dim3(64), lds_w, side, a, u->has_eps ? 1 : 0, plan.odeg_w, (int)max_npdf);
+    } else if (plan.faithful == 1) {
       KHG_LAUNCH(ctx, k2_viterbi_faithful<true>, dim3(u->n_utt), dim3(64), 0, side, a);
     } else {
-      if (lds_f > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_viterbi_faithful<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-      KHG_LAUNCH(ctx, k2_viterbi_faithful<false>, dim3(u->n_utt), dim3(64), lds_f, side, a);
+      if (plan.lds_f > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_viterbi_faithful<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_f));
+      KHG_LAUNCH(ctx, k2_viterbi_faithful<false>, dim3(u->n_utt), dim3(64), plan.lds_f, side, a);
     }
   }
   HIPCHK(hipGetLastError());

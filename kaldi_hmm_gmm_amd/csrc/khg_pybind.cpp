@@ -434,6 +434,15 @@ struct KUtts {
     Check(khg_utts_pdfs(h, pdfs.mutable_data()));
     return py::make_tuple(off, py::array(pdfs)[py::slice(0, n, 1)]);
   }
+  // khg_utts_k2_plan: what align() would launch under the context's current options
+  py::dict k2_plan(py::object ctx_o) {
+    int32_t o[8];
+    Check(khg_utts_k2_plan(ctx_o.cast<KContext*>()->h, h, o));
+    py::dict d;
+    d["KS"] = o[0]; d["DEG"] = o[1]; d["FAST"] = o[2] != 0; d["GMEM"] = o[3] != 0; d["SC"] = o[4] != 0;
+    d["nthr"] = o[5]; d["lds_bytes"] = o[6]; d["faithful_form"] = o[7];
+    return d;
+  }
   py::object pdf_first_frames() {
     Arr<int64_t> off({(py::ssize_t)n_utt + 1});
     Check(khg_utts_num_pdfs(h, off.mutable_data()));
@@ -774,7 +783,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def_property_readonly("h", [](KUtts& x) { return reinterpret_cast<uintptr_t>(x.h); })
       .def_readonly("ctx", &KUtts::ctx_obj).def_readonly("frame_off", &KUtts::frame_off).def_readonly("n_utt", &KUtts::n_utt)
       .def_readonly("dim", &KUtts::dim)
-      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("pdf_first_frames", &KUtts::pdf_first_frames)
+      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("pdf_first_frames", &KUtts::pdf_first_frames)
       .def("pdf_last_frames", &KUtts::pdf_last_frames)
       .def("loglikes", &KUtts::loglikes, py::arg("model"), py::arg("reachable_only") = false, py::arg("band") = false)
       .def("loglikes_layout", &KUtts::loglikes_layout).def("download_loglikes", &KUtts::download_loglikes)

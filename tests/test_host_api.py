@@ -532,7 +532,7 @@ def test_pybind11_module_is_the_host_surface():
     for cls, methods in ((ext.Context, "sync set_timing timings set_k1_form set_option get_option close"),
                          (ext.DeviceModel, "set_weights mle_update scale_weights download close"),
                          (ext.DeviceTransitions, "set_trans_cost close"),
-                         (ext.UtteranceSet, "set_pdf_list pdf_lists pdf_first_frames loglikes loglikes_layout download_loglikes "
+                         (ext.UtteranceSet, "set_pdf_list pdf_lists k2_plan pdf_first_frames loglikes loglikes_layout download_loglikes "
                                             "upload_loglikes align upload_ali download_ali acc_stats close"),
                          (ext.DeviceAccs, "zero device_ptr allreduce split relayout download_range download_occ download_trans download "
                                           "upload close"),
