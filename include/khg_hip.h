@@ -508,6 +508,17 @@ int khg_posteriors_download(khg_ctx *ctx, const khg_posteriors *p, int64_t *entr
                             double *arc_post_h);
 int khg_posteriors_device_bytes(const khg_posteriors *p, int64_t *bytes);
 int khg_posteriors_destroy(khg_posteriors *p);
+/* A handle from host arrays -- the ones khg_posteriors_sizes (frame_off_h[n_utt + 1]) and khg_posteriors_download
+ * (entry_begin_h[frames + 1], absolute; tid_h / weight_h [entry_begin_h[frames]]) give back: how ali-to-post, weight-silence-post and
+ * hand-made posteriors get in.  The handle has no arc posteriors; an utterance without frames counts as KHG_LAT_NO_PATH, every other
+ * as KHG_LAT_SUCCEEDED.  The ids of a frame may come in any order and may repeat; the handle records the largest.  Refused with
+ * KHG_E_ARG (khg_posteriors_validate, host only: n_entries = the length of tid_h / weight_h): frame_off_h or entry_begin_h not
+ * starting at 0 or decreasing, entry_begin_h not ending at n_entries, an id < 1, a weight that is not finite (any sign is taken).
+ * Synchronous. */
+int khg_posteriors_validate(int32_t n_utt, const int64_t *frame_off_h, const int64_t *entry_begin_h, int64_t n_entries,
+                            const int32_t *tid_h, const double *weight_h);
+int khg_posteriors_upload(khg_ctx *ctx, int32_t n_utt, const int64_t *frame_off_h, const int64_t *entry_begin_h,
+                          const int32_t *tid_h, const double *weight_h, khg_posteriors **out);
 
 /* ---- K3: sufficient statistics ---------------------------------------------------------- */
 /* AccumAmDiagGmm (csrc/mle-am-diag-gmm.h:93-96) + transition stats (csrc/transition-model.h:176-189)
@@ -533,6 +544,18 @@ int khg_accs_upload(khg_ctx *ctx, khg_accs *a, const double *buf_h);
  * additive, csrc/mle-am-diag-gmm.cc:41-52; KHG_OPT_K2_SPLIT = 1: one pass after the decoders). */
 int khg_acc_stats(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, float weight,
                   khg_accs *a);
+/* gmm-acc-stats: the same statistics from posteriors resident on the device.  Every entry (utterance u, frame t,
+ * transition-id tid, weight w64) of `p` adds what AccumulateForGmm(am, x[u][t], id2pdf[tid], w) and TransitionModel::Accumulate(w,
+ * tid) add, with w = (float)((double)scale * w64); entries are independent (two ids of one frame that share a pdf are not merged), an
+ * entry whose w is 0 is skipped.  Utterance u of `p` is utterance u of the set; one without frames in `p` adds nothing.  No resident
+ * alignment is needed or touched.  Asynchronous on the context's stream; adds into the same block as khg_acc_stats.  KHG_E_ARG,
+ * before anything is launched (the block stays as it was): a handle of another context, another n_utt, an utterance whose
+ * posterior has frames but not the set's number of them, model / accumulator / feature dimensions that do not match, a scale that
+ * is not finite, an uploaded handle with an id above the transition model's.  (An id above it in a handle made from lattices, and
+ * an entry whose scale * weight overflows a float, are dropped on the device and raise the context's error word: the next
+ * synchronising call answers KHG_E_RUNTIME.) */
+int khg_acc_stats_post(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, const khg_posteriors *p, float scale,
+                       khg_accs *a);
 
 /* ---- C1: cross-GPU sum of the accumulator block (one process per GPU) -------------------- */
 /* AccumAmDiagGmm::Add across jobs (csrc/mle-am-diag-gmm.cc:119-128; what Kaldi's gmm-sum-accs does on

@@ -29,8 +29,9 @@ from .mle import (AccumAmDiagGmm, AccumDiagGmm, GmmUpdateFlags, MapDiagGmmOption
                   mle_am_diag_gmm_update_device, mle_diag_gmm_update,
                   str_to_gmm_flags)
 from .resident import ResidentEm  # noqa: F401
-from .scripts import (gmm_acc_stats_ali, gmm_acc_stats_ali_batch, gmm_align_compiled, gmm_align_compiled_batch,  # noqa: F401
-                      gmm_boost_silence, gmm_est, gmm_info, gmm_init_mono)
+from .posterior import ali_to_post, arrays_to_posts, posts_to_arrays  # noqa: F401
+from .scripts import (gmm_acc_stats, gmm_acc_stats_ali, gmm_acc_stats_ali_batch, gmm_acc_stats_batch, gmm_align_compiled,  # noqa: F401
+                      gmm_align_compiled_batch, gmm_boost_silence, gmm_est, gmm_info, gmm_init_mono)
 from .training_graph import (TrainingGraphCompiler, TrainingGraphCompilerOptions, equal_align, generate_hmm_topo,  # noqa: F401
                              make_lexicon_fst_with_silence)
 from .transition_model import (MleTransitionUpdateConfig, TransitionInformation, TransitionModel, TransitionModelTuple,  # noqa: F401

@@ -172,6 +172,8 @@ SIGNATURES = {
     "khg_posteriors_download": (C.c_int, [vp, vp, c_i64p, c_i32p, c_f64p, c_f64p]),
     "khg_posteriors_device_bytes": (C.c_int, [vp, c_i64p]),
     "khg_posteriors_destroy": (C.c_int, [vp]),
+    "khg_posteriors_validate": (C.c_int, [C.c_int32, c_i64p, c_i64p, C.c_int64, c_i32p, c_f64p]),
+    "khg_posteriors_upload": (C.c_int, [vp, C.c_int32, c_i64p, c_i64p, c_i32p, c_f64p, C.POINTER(vp)]),
     "khg_ali_download": (C.c_int, [vp, vp, c_i32p]),
     "khg_accs_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     "khg_accs_destroy": (C.c_int, [vp]),
@@ -181,6 +183,7 @@ SIGNATURES = {
     "khg_accs_download": (C.c_int, [vp, vp, c_f64p]),
     "khg_accs_upload": (C.c_int, [vp, vp, c_f64p]),
     "khg_acc_stats": (C.c_int, [vp, vp, vp, vp, C.c_float, vp]),
+    "khg_acc_stats_post": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, vp]),
     "khg_accs_allreduce": (C.c_int, [vp, vp, vp]),
     "khg_accs_allreduce_range": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, vp]),
     "khg_acc_stats_reduce": (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, C.c_int32]),

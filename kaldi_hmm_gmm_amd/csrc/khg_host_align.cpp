@@ -476,10 +476,20 @@ double AccumAmDiagGmm::AccumulateAli(const AmDiagGmm& model, const TransitionMod
   return AccumulateOnDevice(model, tm.DeviceTm(DefaultCtx()), nt, feats, frame_off, n_utt, ali, weight);
 }
 
+// gmm-acc-stats through khg_acc_stats_post, into the same block
+double AccumAmDiagGmm::AccumulatePost(const AmDiagGmm& model, const TransitionModel& tm, const float* feats, const int64_t* frame_off, int n_utt,
+                                      const int64_t* entry_begin, const int32_t* tid, const double* post_weight, float scale) {
+  KHG_REQUIRE(n_utt >= 1 && frame_off && frame_off[0] == 0 && entry_begin, "AccumulatePost: bad arguments");
+  if (frame_off[n_utt] == 0 || entry_begin[frame_off[n_utt]] == 0) return 0.0;
+  KHG_REQUIRE(NumAccs() == model.NumPdfs(), "gmm_accs.NumAccs() == am_gmm.NumPdfs() assertion failed");
+  const int nt = tm.NumTransitionIds();
+  return AccumulateOnDevice(model, tm.DeviceTm(DefaultCtx()), nt, feats, frame_off, n_utt, nullptr, scale, entry_begin, tid, post_weight);
+}
+
 // One K3 call into the device-resident block (made for this model version and this many transition-ids); -> the call's own
 // sum of weight * log-like.  `dt` == nullptr: the per-frame entry points' table, transition-id = pdf + 1, owned by the block.
 double AccumAmDiagGmm::AccumulateOnDevice(const AmDiagGmm& model, khg_tm* dt, int nt, const float* feats, const int64_t* frame_off, int n_utt,
-                                          const int32_t* ali, float weight) {
+                                          const int32_t* ali, float weight, const int64_t* entry_begin, const int32_t* tid, const double* post_weight) {
   const int D = model.Dim();
   khg_ctx* ctx = DefaultCtx();
   khg_model* dm = model.DeviceModel(ctx);
@@ -510,8 +520,15 @@ double AccumAmDiagGmm::AccumulateOnDevice(const AmDiagGmm& model, khg_tm* dt, in
   KHG_REQUIRE(dt != nullptr, "AccumAmDiagGmm: the device block was made for a transition model, not for per-frame calls");
   UttsH us;
   CApi(khg_utts_create(ctx, nullptr, n_utt, D, frame_off, feats, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &us.h));
-  CApi(khg_ali_upload(ctx, us.h, ali));
-  CApi(khg_acc_stats(ctx, dm, dt, us.h, weight, dev_->h));
+  if (ali) {
+    CApi(khg_ali_upload(ctx, us.h, ali));
+    CApi(khg_acc_stats(ctx, dm, dt, us.h, weight, dev_->h));
+  } else {
+    struct PostH { khg_posteriors* h = nullptr; ~PostH() { if (h) khg_posteriors_destroy(h); } } post;
+    CApi(khg_posteriors_upload(ctx, n_utt, frame_off, entry_begin, tid, post_weight, &post.h));
+    CApi(khg_acc_stats_post(ctx, dm, dt, us.h, post.h, weight, dev_->h));
+    CApi(khg_ctx_sync(ctx));          // the handle goes with this scope: its kernels first
+  }
   dev_->pending = true;
   double sc[8];
   CApi(khg_accs_download_trans(ctx, dev_->h, nullptr, sc));      // the 8 scalars: [frames, log-like, ...] running totals of the block

@@ -305,8 +305,14 @@ class AccumAmDiagGmm {
   // the host accumulators (Flush: one download per EM pass).  -> the log-likelihood of these frames (tot_like_this_file).
   double AccumulateAli(const AmDiagGmm& model, const TransitionModel& tm, const float* feats, const int64_t* frame_off, int n_utt, const int32_t* ali,
                        float weight = 1.0f);
+  // gmm-acc-stats for the same utterances: every (transition-id, weight) of their Posteriors as flat arrays (entry_begin [frames + 1],
+  // tid / post_weight [entries]; khg_posteriors_upload + khg_acc_stats_post), into the same device-resident block
+  double AccumulatePost(const AmDiagGmm& model, const TransitionModel& tm, const float* feats, const int64_t* frame_off, int n_utt,
+                        const int64_t* entry_begin, const int32_t* tid, const double* post_weight, float scale = 1.0f);
+  // khg_host_align.cpp: the one K3 call behind AccumulateAli, AccumulateForGmm (ali) and AccumulatePost (ali == nullptr: entry_begin,
+  // tid, post_weight; `weight` is the scale)
   double AccumulateOnDevice(const AmDiagGmm& model, khg_tm* dt, int num_tids, const float* feats, const int64_t* frame_off, int n_utt, const int32_t* ali,
-                            float weight);                     // khg_host_align.cpp: the one K3 call behind AccumulateAli and AccumulateForGmm
+                            float weight, const int64_t* entry_begin = nullptr, const int32_t* tid = nullptr, const double* post_weight = nullptr);
   bool HasDeviceStats() const { return dev_ && dev_->pending; }
   void Flush() const;        // pending device sums -> host accumulators (then the device block is zero again)
 

@@ -303,6 +303,11 @@ struct khg_utts {
   void* k3_items_d = nullptr; int32_t* k3_item_off_d = nullptr; size_t k3_items_n = 0, k3_item_off_n = 0;   // K3 work items (k3_make_items)
   int64_t* pdf_start_d = nullptr; unsigned long long* tid_count_d = nullptr;
   int32_t k3_P = 0, k3_tids = 0;
+  // khg_acc_stats_post: the flattened entries (row, id, weight), their sort buffers and bucket bounds -- sized by the ENTRY count and
+  // kept apart from K3's buffers above, which a later khg_acc_stats finds as it left them
+  int32_t *pe_row_d = nullptr, *pe_tid_d = nullptr, *pe_ids_d = nullptr; float* pe_w_d = nullptr; size_t pe_cap = 0;
+  uint32_t *pe_keys_d = nullptr, *pe_keys_out_d = nullptr, *pe_vals_d = nullptr; void* pe_tmp_d = nullptr; size_t pe_tmp_bytes = 0;
+  int64_t* pe_start_d = nullptr; int32_t pe_P = 0;
 };
 
 // states of utterance i's decoding graph (host code sizing scratch)
@@ -356,3 +361,10 @@ int k1_band_check(khg_ctx* ctx, khg_utts* u);             // khg_k1.hip: the ban
 int k1_band_repair(khg_ctx* ctx, khg_utts* u, int32_t* status_d, int repair_bit, hipStream_t side);   // khg_k1.hip
 int accs_allreduce_pieces(khg_ctx* ctx, khg_accs* a, const khg_model* m, int first_pdf, int n_pdf, void* comm, hipStream_t st);   // khg_c1.hip
 int ctx_comm_stream(khg_ctx* ctx);                        // khg_c1.hip
+// khg_lattices.hip: what khg_acc_stats_post (khg_k3.hip) needs of a posteriors handle, whose layout stays private to that unit
+struct PostInfo { const khg_ctx* ctx; int32_t U, max_tid; const int64_t *frame_off, *entry_off; };   // max_tid < 0: made from lattices
+void posteriors_info(const khg_posteriors* p, PostInfo* out);
+// every entry of the handle, in utterance / frame / entry order -> e_row (set_frame_off_d[u] + t), e_tid, e_w = (float)(scale * w64);
+// an id outside 1 .. num_tids or a weight that overflows a float: e_tid = 0, e_w = 0 and the context's error word.  Asynchronous.
+int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set_frame_off_d, double scale, int32_t num_tids,
+                       int32_t* e_row, int32_t* e_tid, float* e_w);

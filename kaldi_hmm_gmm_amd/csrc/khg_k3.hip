@@ -1,10 +1,12 @@
 // kaldi_hmm_gmm_amd/csrc/khg_k3.hip -- C-ABI (include/khg_hip.h): the accumulator block and K3, sufficient statistics
-// (khg_acc_stats / khg_acc_stats_reduce): bucketing of frames by pdf, work items, form selection, the launches.  gfx950 only.
+// (khg_acc_stats / khg_acc_stats_reduce; khg_acc_stats_post from posteriors): bucketing of frames by pdf, work items, form selection,
+// the launches.  gfx950 only.
 #include "khg_internal.hpp"
 
 #include <hipcub/hipcub.hpp>   // DeviceRadixSort: the stable (pdf, frame) sort of K3's bucketing
 
 #include "khg_k3_accstats.hip.inc"
+#include "khg_k3_post.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // accumulators + K3
@@ -102,17 +104,29 @@ static int k3_phase_a_scales(khg_ctx* ctx, khg_model* m, khg_utts* u, bool* use)
 
 // One pass of K3 over the set's resident alignment: all N frames (nsub < 0), or -- the second pass of the split mode -- the nsub frames
 // of the utterances the DP left to the order-faithful decoders (flagged in u->unc_d; their alignments are merged into ali_d by now).
-static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, float weight, khg_accs* acc, void* comm, int nparts, int64_t nsub) {
+// npost >= 0 (khg_acc_stats_post): the pass runs over the npost flattened entries in u->pe_* instead of the alignment -- its own
+// sort buffers and bucket bounds, the POST instantiations of the fp32-chain forms (`weight` is unused: every entry carries its own).
+static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, float weight, khg_accs* acc, void* comm, int nparts, int64_t nsub,
+                          int64_t npost = -1) {
   int rc = KHG_OK;
-  const int64_t Neff = nsub < 0 ? u->N : nsub;
-  HIPCHK(hipMemsetAsync(u->pdf_count_d, 0, sizeof(int32_t) * (size_t)m->P, ctx->stream));
-  HIPCHK(hipMemsetAsync(u->tid_count_d, 0, sizeof(unsigned long long) * ((size_t)tm->num_tids + 1), ctx->stream));
+  const bool post = npost >= 0;
+  const int64_t Neff = post ? npost : nsub < 0 ? u->N : nsub;
+  if (!post) {
+    HIPCHK(hipMemsetAsync(u->pdf_count_d, 0, sizeof(int32_t) * (size_t)m->P, ctx->stream));
+    HIPCHK(hipMemsetAsync(u->tid_count_d, 0, sizeof(unsigned long long) * ((size_t)tm->num_tids + 1), ctx->stream));
+  }
   K3Args a;
-  a.feats = u->feats_d; a.ali = u->ali_d; a.id2pdf = tm->id2pdf_d; a.num_tids = tm->num_tids;
+  a.feats = u->feats_d; a.ali = post ? u->pe_tid_d : u->ali_d; a.id2pdf = tm->id2pdf_d; a.num_tids = tm->num_tids;
   a.N = Neff; a.P = m->P; a.D = m->D;
   a.gauss_off = m->gauss_off_d; a.gconsts = m->gconsts_d; a.means_invvars = m->miv_d; a.inv_vars = m->iv_d; a.nhalf_inv_vars = m->nhiv_d;
-  a.pdf_count = u->pdf_count_d; a.pdf_start = u->pdf_start_d; a.pdf_cursor = u->pdf_cursor_d;
-  a.frame_ids = u->frame_ids_d; a.tid_count = u->tid_count_d;
+  a.pdf_count = u->pdf_count_d; a.pdf_start = post ? u->pe_start_d : u->pdf_start_d; a.pdf_cursor = u->pdf_cursor_d;
+  a.frame_ids = post ? u->pe_ids_d : u->frame_ids_d; a.tid_count = u->tid_count_d;
+  a.e_row = post ? u->pe_row_d : nullptr; a.e_w = post ? u->pe_w_d : nullptr;
+  // the sort's buffers: K3's own, cached on the set for its N frames, or the posteriors' (sized by the caller for the entries)
+  uint32_t *&sort_keys = post ? u->pe_keys_d : u->sort_keys_d, *&sort_keys_out = post ? u->pe_keys_out_d : u->sort_keys_out_d;
+  uint32_t*& sort_vals = post ? u->pe_vals_d : u->sort_vals_d;
+  void*& sort_tmp = post ? u->pe_tmp_d : u->sort_tmp_d;
+  size_t& sort_tmp_bytes = post ? u->pe_tmp_bytes : u->sort_tmp_bytes;
   a.occ = acc->occ(); a.mean_acc = acc->mean(); a.var_acc = acc->var(); a.trans_acc = acc->trans(); a.scalars = acc->scalars();
   a.weight = weight; a.err_flag = ctx->err_flag_d; a.part = nullptr; a.ll_part = nullptr; a.pdf0 = 0; a.npdf = m->P; a.items = nullptr; a.item_off = nullptr;
   a.pa_ex = nullptr; a.pa_S = 0; a.pa_scale = 1.0f; a.pa_inv = 1.0f; a.pa_c1 = 1.44269504088896340736f;
@@ -123,11 +137,11 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
     {
       KernelTimer kt(ctx, nsub < 0 ? "k3_bucket" : "k3_bucket_pass2");
       // KHG_OPT_K3_BUCKET = 1: cursor-bump scatter (bucket order depends on the atomics)
-      if (nsub < 0 && (ctx->opt[KHG_OPT_K3_BUCKET] == 1 || u->N >= (int64_t)INT_MAX)) {
+      if (!post && nsub < 0 && (ctx->opt[KHG_OPT_K3_BUCKET] == 1 || u->N >= (int64_t)INT_MAX)) {
         KHG_LAUNCH(ctx, k3_count, dim3(gb), dim3(256), 0, ctx->stream, a);
         KHG_LAUNCH(ctx, k3_scan, dim3(1), dim3(1024), 0, ctx->stream, a);
         KHG_LAUNCH(ctx, k3_scatter, dim3(gb), dim3(256), 0, ctx->stream, a);
-      } else if (nsub < 0 && ctx->opt[KHG_OPT_K3_BUCKET] == 2 && m->P <= K3_CS_MAXP) {
+      } else if (!post && nsub < 0 && ctx->opt[KHG_OPT_K3_BUCKET] == 2 && m->P <= K3_CS_MAXP) {
         // the library's own stable counting sort (khg_k3_accstats.hip.inc: k3_cs_*; opt-in: 1.27 ms against the radix sort's 0.80 at the
         // bench size): blocks of CB consecutive frames
         const int nw = m->P + 1 <= 7168 ? 4 : 2;                      // waves of a placing block: nw x (P + 1 + 1024) counters of LDS
@@ -156,30 +170,39 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
         // off the sorted keys
         int bits = 1;
         while ((1 << bits) <= m->P) ++bits;            // keys are 0..P
-        if (!u->sort_keys_d) {
-          rc = u_alloc(u, &u->sort_keys_d, (size_t)u->N);
-          if (!rc) rc = u_alloc(u, &u->sort_keys_out_d, (size_t)u->N);
-          if (!rc) rc = u_alloc(u, &u->sort_vals_d, (size_t)u->N);
+        if (!sort_keys) {
+          rc = u_alloc(u, &sort_keys, (size_t)u->N);
+          if (!rc) rc = u_alloc(u, &sort_keys_out, (size_t)u->N);
+          if (!rc) rc = u_alloc(u, &sort_vals, (size_t)u->N);
           if (rc) return rc;
         }
         size_t need = 0;
-        HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, u->sort_keys_d, u->sort_keys_out_d, u->sort_vals_d,
-                                                  reinterpret_cast<uint32_t*>(u->frame_ids_d), (int)Neff, 0, bits, ctx->stream));
-        if (need > u->sort_tmp_bytes) {
-          DEVFREE(u->sort_tmp_d);
-          { int rt = u_alloc(u, reinterpret_cast<char**>(&u->sort_tmp_d), need); if (rt) return rt; }
-          u->sort_tmp_bytes = need;
+        HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, sort_keys, sort_keys_out, sort_vals,
+                                                  reinterpret_cast<uint32_t*>(a.frame_ids), (int)Neff, 0, bits, ctx->stream));
+        if (need > sort_tmp_bytes) {
+          DEVFREE(sort_tmp);
+          { int rt = u_alloc(u, reinterpret_cast<char**>(&sort_tmp), need); if (rt) return rt; }
+          sort_tmp_bytes = need;
         }
-        if (nsub >= 0) {
+        if (post) {
+          // the (pdf, entry) pairs and the weighted transition statistics (khg_k3_post.hip.inc)
+          const bool ldst = tm->num_tids <= K3_LDS_TIDS;
+          if (ldst) KHG_LAUNCH(ctx, k3_post_keys<true>, dim3(std::min(gb, 1024)), dim3(256), sizeof(double) * ((size_t)tm->num_tids + 1), ctx->stream, a, sort_keys, sort_vals);
+          else KHG_LAUNCH(ctx, k3_post_keys<false>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
+        } else if (nsub >= 0) {
           // the (pdf, frame) pairs of the flagged utterances only, utterances in order: positions from an exclusive sum of their lengths
           if (!u->sub_off_d) { rc = u_alloc(u, &u->sub_off_d, (size_t)u->n_utt + 1); if (rc) return rc; }
           KHG_LAUNCH(ctx, k3_sub_scan, dim3(1), dim3(1024), 0, ctx->stream, u->unc_d, u->frame_off_d, u->n_utt, u->sub_off_d);
-          KHG_LAUNCH(ctx, k3_sub_keys, dim3((unsigned)std::min(u->n_utt, 8192)), dim3(64), 0, ctx->stream, a, u->unc_d, u->frame_off_d, u->sub_off_d, u->n_utt, u->sort_keys_d, u->sort_vals_d);
-        } else if (tm->num_tids <= K3_LDS_TIDS) KHG_LAUNCH(ctx, k3_sort_keys<true>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, u->sort_keys_d, u->sort_vals_d);
-        else KHG_LAUNCH(ctx, k3_sort_keys<false>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, u->sort_keys_d, u->sort_vals_d);
-        HIPCHK(hipcub::DeviceRadixSort::SortPairs(u->sort_tmp_d, need, u->sort_keys_d, u->sort_keys_out_d, u->sort_vals_d,
-                                                  reinterpret_cast<uint32_t*>(u->frame_ids_d), (int)Neff, 0, bits, ctx->stream));
-        KHG_LAUNCH(ctx, k3_bounds, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, a, u->sort_keys_out_d);
+          KHG_LAUNCH(ctx, k3_sub_keys, dim3((unsigned)std::min(u->n_utt, 8192)), dim3(64), 0, ctx->stream, a, u->unc_d, u->frame_off_d, u->sub_off_d, u->n_utt, sort_keys, sort_vals);
+        } else if (tm->num_tids <= K3_LDS_TIDS) KHG_LAUNCH(ctx, k3_sort_keys<true>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
+        else KHG_LAUNCH(ctx, k3_sort_keys<false>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
+        HIPCHK(hipcub::DeviceRadixSort::SortPairs(sort_tmp, need, sort_keys, sort_keys_out, sort_vals,
+                                                  reinterpret_cast<uint32_t*>(a.frame_ids), (int)Neff, 0, bits, ctx->stream));
+        if (post) {
+          K3Args b = a;
+          b.num_tids = -1;        // k3_bounds has no integer counts to fold: k3_post_keys added the weighted ones itself
+          KHG_LAUNCH(ctx, k3_bounds, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, b, sort_keys_out);
+        } else KHG_LAUNCH(ctx, k3_bounds, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, a, sort_keys_out);
       }
     }
     // Work items of the accumulate kernels (k3_make_items): ny_base slices per pdf, more for a pdf whose bucket is far above the
@@ -297,7 +320,7 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
     // ---- fp32 + fp64 MFMA form; fewer, longer blocks: the fp64 accumulators stay in registers per block ----
     auto run_mfma = [&](int cls_lo, int cls_hi, int maxG, int n_cls, bool second, void* comm_) -> int {
       const int64_t avg_chunks = (Neff / std::max(1, m->P) + K3_CHUNK - 1) / K3_CHUNK;
-      const size_t lds = sizeof(float) * ((size_t)4 * K3_CHUNK * 2 * m->KQ + 5 * K3_CHUNK);   // 4 planes [64][KH] + reductions
+      const size_t lds = sizeof(float) * ((size_t)4 * K3_CHUNK * 2 * m->KQ + (post ? 6 : 5) * K3_CHUNK);   // 4 planes [64][KH] + reductions (+ the entries' weights)
       // slices per pdf: every block ends with one fp64 atomic per accumulator cell (G*(2D+1) of them), so
       // use as few blocks as still fill the chip (~4096 = 256 CUs x 8 blocks x 2 rounds)
       // (a class of a few pdfs -- the ones a split has grown -- is cut finer: one block walking a whole bucket is a latency of its own)
@@ -309,7 +332,7 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
       // number (the conditions of the wave form's fp16 phases): <= 128 Gaussians at D <= 80, <= 192 at D <= 40.  KHG_K3_PHASEA=f32 or
       // KHG_K3_PHASEB=f64 keep the fp32 / fp64 MFMA form.
       bool b16 = false;
-      if (ctx->opt[KHG_OPT_K3_PHASE_A] == 0 && ctx->opt[KHG_OPT_K3_PHASE_B] == 2 && ((m->KQ == 20 && maxG <= 128) || (m->KQ == 10 && maxG <= 192)) &&
+      if (!post && ctx->opt[KHG_OPT_K3_PHASE_A] == 0 && ctx->opt[KHG_OPT_K3_PHASE_B] == 2 && ((m->KQ == 20 && maxG <= 128) || (m->KQ == 10 && maxG <= 192)) &&
           std::isfinite(weight) && std::fabs(weight) > 1.0e-30f && std::fabs(weight) < 1.0e30f) {
         rc = k3_phase_a_scales(ctx, const_cast<khg_model*>(m), u, &b16);
         if (rc) return rc;
@@ -343,6 +366,13 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
             else if (maxG <= 128) { if (m->KQ == 20) K3_B16(20, 1, 8); else K3_B16(10, 1, 8); }
             else K3_B16(10, 3, 4);         // (four blocks per wave -- 193..256 Gaussians -- spill at 512 registers: the fp32 / fp64 form keeps them)
 #undef K3_B16
+          } else if (post) {
+            if (m->KQ == 10 && maxG <= 64) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 1, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
+            else if (m->KQ == 10 && maxG <= 128) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 2, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
+            else if (m->KQ == 10 && maxG <= 192) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 3, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
+            else if (m->KQ == 10) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 4, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
+            else if (maxG <= 64) KHG_LAUNCH(ctx, (k3_accumulate_mfma<20, 1, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
+            else KHG_LAUNCH(ctx, (k3_accumulate_mfma<20, 2, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
           } else
           if (m->KQ == 10 && maxG <= 64) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 1>), dim3(nblk), dim3(256), lds, ctx->stream, a);
           else if (m->KQ == 10 && maxG <= 128) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 2>), dim3(nblk), dim3(256), lds, ctx->stream, a);
@@ -359,9 +389,10 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
     // ---- the VALU form: any number of Gaussians, any dimension ----
     auto run_valu = [&](int cls_lo, int cls_hi, int maxG, int n_cls, bool second, void* comm_) -> int {
       const int64_t avg_chunks = (Neff / std::max(1, m->P) + K3_CHUNK - 1) / K3_CHUNK;
-      const size_t lds = sizeof(float) * (size_t)K3_CHUNK * ((size_t)(m->KQ ? 4 * m->KQ : (m->D | 1)) + (maxG | 1) + 4);
+      const size_t lds = sizeof(float) * (size_t)K3_CHUNK * ((size_t)(m->KQ ? 4 * m->KQ : (m->D | 1)) + (maxG | 1) + (post ? 5 : 4));
       if (lds > 160 * 1024) return khg_set_error(KHG_E_UNSUPPORTED, "khg_acc_stats: pdf too large for the LDS chunk buffers");
-      const void* k3fn = m->KQ == 10 ? (const void*)k3_accumulate<10> : m->KQ == 20 ? (const void*)k3_accumulate<20> : (const void*)k3_accumulate<0>;
+      const void* k3fn = post ? (m->KQ == 10 ? (const void*)k3_accumulate<10, true> : m->KQ == 20 ? (const void*)k3_accumulate<20, true> : (const void*)k3_accumulate<0, true>)
+                              : m->KQ == 10 ? (const void*)k3_accumulate<10> : m->KQ == 20 ? (const void*)k3_accumulate<20> : (const void*)k3_accumulate<0>;
       if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(k3fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const int ny = (int)std::max<int64_t>(1, std::min<int64_t>(64, (avg_chunks + 3) / 4));
       rc = make_items(ny, false, 0, cls_lo, cls_hi, second);
@@ -373,6 +404,11 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
         const unsigned nblk = (unsigned)((int64_t)std::min(np, n_cls) * ny + k3_extra_blocks);
         {
           KernelTimer kt(ctx, nsub < 0 ? "k3_accumulate" : "k3_accumulate_pass2");
+          if (post) {
+            if (m->KQ == 10) KHG_LAUNCH(ctx, (k3_accumulate<10, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
+            else if (m->KQ == 20) KHG_LAUNCH(ctx, (k3_accumulate<20, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
+            else KHG_LAUNCH(ctx, (k3_accumulate<0, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
+          } else
           if (m->KQ == 10) KHG_LAUNCH(ctx, k3_accumulate<10>, dim3(nblk), dim3(256), lds, ctx->stream, a);
           else if (m->KQ == 20) KHG_LAUNCH(ctx, k3_accumulate<20>, dim3(nblk), dim3(256), lds, ctx->stream, a);
           else KHG_LAUNCH(ctx, k3_accumulate<0>, dim3(nblk), dim3(256), lds, ctx->stream, a);
@@ -391,7 +427,7 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
       if (Gp <= 64) maxG_lo = std::max(maxG_lo, Gp); else ++n_hi;
     }
     const bool mfma_ok = (maxG <= 128 || (maxG <= 256 && m->KQ == 10)) && k3form != 2 && m->KQ != 0;
-    const bool wave_ok = m->KQ == 10 && k3form == 0 && maxG_lo > 0;
+    const bool wave_ok = !post && m->KQ == 10 && k3form == 0 && maxG_lo > 0;       // (the wave forms' fp16 phase B rests on ONE |weight|: 7h)
     if (wave_ok && n_hi == 0) rc = run_wave(0, INT_MAX, maxG, comm);
     else if (wave_ok) {
       rc = run_wave(0, 64, maxG_lo, nullptr);                  // (with an exchange: its pieces follow the second class's kernels)
@@ -460,4 +496,54 @@ extern "C" int khg_acc_stats(khg_ctx* ctx, const khg_model* m, const khg_tm* tm,
 }
 extern "C" int khg_acc_stats_reduce(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, float weight, khg_accs* acc, void* comm, int32_t nparts) {
   return acc_stats_impl(ctx, m, tm, u, weight, acc, comm, nparts <= 0 ? 4 : nparts);
+}
+
+// gmm-acc-stats: every check on the host first, then flatten -> bucket -> accumulate on the context's stream.
+extern "C" int khg_acc_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale, khg_accs* acc) {
+  const std::string who = "khg_acc_stats_post: ";
+  if (ctx_dead(ctx) || !m || !tm || !u || !p || !acc) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  { int rf = utts_foreign_ctx(ctx, u, "khg_acc_stats_post"); if (rf) return rf; }
+  PostInfo pi;
+  posteriors_info(p, &pi);
+  if (pi.ctx != ctx || m->ctx != ctx || tm->ctx != ctx || acc->ctx != ctx || u->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (pi.U != u->n_utt)
+    return khg_set_error(KHG_E_ARG, who + "the posteriors hold " + std::to_string(pi.U) + " utterances, the set " + std::to_string(u->n_utt));
+  for (int i = 0; i < pi.U; ++i) {
+    const int64_t tp = pi.frame_off[i + 1] - pi.frame_off[i], ts = u->frame_off[(size_t)i + 1] - u->frame_off[(size_t)i];
+    if (tp != 0 && tp != ts)
+      return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(i) + " has " + std::to_string(tp) + " frames of posteriors and " + std::to_string(ts) + " frames of features");
+  }
+  if (m->D != u->D || acc->D != m->D || acc->sumG != m->sumG || acc->num_tids != tm->num_tids)
+    return khg_set_error(KHG_E_ARG, who + "accumulator / model / feature dimensions do not match");
+  if (tm->max_pdf >= m->P) return khg_set_error(KHG_E_ARG, who + "transition model refers to pdf-ids the model does not have");
+  if (!std::isfinite(scale)) return khg_set_error(KHG_E_ARG, who + "scale must be finite");
+  if (pi.max_tid > tm->num_tids)
+    return khg_set_error(KHG_E_ARG, who + "the posteriors hold transition-id " + std::to_string(pi.max_tid) + ", the transition model has " + std::to_string(tm->num_tids));
+  const int64_t E = pi.entry_off[pi.U];
+  if (E >= (int64_t)INT_MAX || u->N >= (int64_t)INT_MAX) return khg_set_error(KHG_E_UNSUPPORTED, who + "2^31 - 1 or more entries or frames");
+  if (E == 0) return KHG_OK;
+  int rc = arena_flush(ctx);
+  if (rc) return rc;
+  if ((size_t)E > u->pe_cap) {
+    DEVFREE(u->pe_row_d); DEVFREE(u->pe_tid_d); DEVFREE(u->pe_ids_d); DEVFREE(u->pe_w_d); DEVFREE(u->pe_keys_d); DEVFREE(u->pe_keys_out_d); DEVFREE(u->pe_vals_d);
+    u->pe_cap = 0;
+    rc = u_alloc(u, &u->pe_row_d, (size_t)E);
+    if (!rc) rc = u_alloc(u, &u->pe_tid_d, (size_t)E);
+    if (!rc) rc = u_alloc(u, &u->pe_ids_d, (size_t)E);
+    if (!rc) rc = u_alloc(u, &u->pe_w_d, (size_t)E);
+    if (!rc) rc = u_alloc(u, &u->pe_keys_d, (size_t)E);
+    if (!rc) rc = u_alloc(u, &u->pe_keys_out_d, (size_t)E);
+    if (!rc) rc = u_alloc(u, &u->pe_vals_d, (size_t)E);
+    if (rc) return rc;
+    u->pe_cap = (size_t)E;
+  }
+  if (!u->pe_start_d || u->pe_P != m->P) {
+    DEVFREE(u->pe_start_d);
+    rc = u_alloc(u, &u->pe_start_d, (size_t)m->P + 1);
+    if (rc) return rc;
+    u->pe_P = m->P;
+  }
+  rc = posteriors_flatten(ctx, p, u->frame_off_d, (double)scale, tm->num_tids, u->pe_row_d, u->pe_tid_d, u->pe_w_d);
+  if (rc) return rc;
+  return acc_stats_pass(ctx, m, tm, u, 1.0f, acc, nullptr, 1, -1, E);
 }

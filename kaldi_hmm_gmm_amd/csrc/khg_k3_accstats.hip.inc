@@ -55,6 +55,11 @@ struct K3Args {
   // k3_accumulate_wave16 (phase B on the fp16 matrix cores too): gamma' = gamma 2^SG, |weight| 2^SG in [2^13, 2^14)
   float pb_gscale;             // 2^SG
   int32_t pb_SG;
+  // khg_acc_stats_post (khg_k3_post.hip.inc; the POST instantiations of k3_accumulate / k3_accumulate_mfma): `ali` holds the entries'
+  // transition-ids, N is their number and the buckets (frame_ids) hold ENTRY numbers; entry e reads feature row e_row[e] and carries its
+  // own weight e_w[e] where `weight` stands for an alignment
+  const int32_t* e_row;        // [N]
+  const float* e_w;            // [N]
 };
 
 struct K3Item { int32_t pdf, y, ny, slot; };      // slot: where slice y parks its image (wave forms, ny > 1), else -1
@@ -575,7 +580,7 @@ __global__ void k3_scatter(K3Args a) {
 #define K3_CHUNK 64
 #define K3_DS 10
 
-template <int KQ>
+template <int KQ, bool POST = false>
 __global__ __launch_bounds__(256) void k3_accumulate(K3Args a) {
   extern __shared__ __attribute__((aligned(16))) float k3s[];
   // padded feature-row pitch in LDS (zero filled beyond D); KQ = 0 is the any-dimension form (D > 80): odd runtime pitch,
@@ -594,6 +599,7 @@ __global__ __launch_bounds__(256) void k3_accumulate(K3Args a) {
   float* xs = k3s;                        // [K3_CHUNK][XP]
   float* gam = xs + K3_CHUNK * XP;        // [K3_CHUNK][GP]
   float* red = gam + K3_CHUNK * GP;       // [4][K3_CHUNK] cross-wave max / sum
+  [[maybe_unused]] float* wts = red + 4 * K3_CHUNK;   // POST: [K3_CHUNK] the chunk's entries' weights
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nchunk = (nfr + K3_CHUNK - 1) / K3_CHUNK;
@@ -603,6 +609,7 @@ __global__ __launch_bounds__(256) void k3_accumulate(K3Args a) {
   const int Gq = (G + 3) >> 2;              // Gaussians per wave in phase A
   const int gbeg = wave * Gq, gend = min(G, gbeg + Gq);
   double tot_ll = 0.0;
+  [[maybe_unused]] double tot_w = 0.0;
   double am[K3_DS], av[K3_DS], ao = 0.0;
 #pragma unroll
   for (int k = 0; k < K3_DS; ++k) { am[k] = 0.0; av[k] = 0.0; }
@@ -625,9 +632,12 @@ __global__ __launch_bounds__(256) void k3_accumulate(K3Args a) {
     for (int i = tid; i < K3_CHUNK * XP; i += 256) {
       int f = i / XP, d = i - f * XP;
       // always-valid addresses (last frame of the chunk, last dim), zero fill by select: the loads of the loop issue back to back
-      const float raw = a.feats[(int64_t)a.frame_ids[beg + c * K3_CHUNK + min(f, cf - 1)] * D + min(d, D - 1)];
+      int row = a.frame_ids[beg + c * K3_CHUNK + min(f, cf - 1)];
+      if constexpr (POST) row = a.e_row[row];
+      const float raw = a.feats[(int64_t)row * D + min(d, D - 1)];
       xs[i] = (f < cf && d < D) ? raw : 0.0f;
     }
+    if constexpr (POST) { if (tid < K3_CHUNK) wts[tid] = tid < cf ? a.e_w[a.frame_ids[beg + c * K3_CHUNK + tid]] : 0.0f; }
     __syncthreads();
     // ---- phase A: lane <-> frame ([x | x^2] in registers), wave <-> a quarter of the pdf's
     // Gaussians whose parameters are wave-uniform (scalar loads); no cross-lane traffic ----
@@ -680,13 +690,16 @@ __global__ __launch_bounds__(256) void k3_accumulate(K3Args a) {
       __syncthreads();
       ssum = (red[lane] + red[K3_CHUNK + lane]) + (red[2 * K3_CHUNK + lane] + red[3 * K3_CHUNK + lane]);
       const float ll = __logf(ssum) + m;            // eigen.cc:28
+      float wf = a.weight;                          // POST: the entry's own weight
+      if constexpr (POST) wf = wts[lane];
       if (lane < cf) {
         if (!(fabsf(ll) <= 3.0e38f)) atomicOr(a.err_flag, 1);  // diag-gmm.cc:385-387
-        if (wave == 0) tot_ll += (double)(ll * a.weight);      // mle-am-diag-gmm.cc:49
+        if (wave == 0) tot_ll += (double)(ll * wf);            // mle-am-diag-gmm.cc:49
+        if constexpr (POST) { if (wave == 0) tot_w += (double)wf; }   // :50
       }
       for (int g = gbeg; g < gend; ++g) {
         float p = gam[lane * GP + g] / ssum;        // eigen.cc:31
-        gam[lane * GP + g] = lane < cf ? p * a.weight : 0.0f;  // mle-diag-gmm.cc:153
+        gam[lane * GP + g] = lane < cf ? p * wf : 0.0f;        // mle-diag-gmm.cc:153
       }
     }
     __syncthreads();
@@ -719,7 +732,15 @@ __global__ __launch_bounds__(256) void k3_accumulate(K3Args a) {
     for (int o = 32; o > 0; o >>= 1) tot_ll += __shfl_xor(tot_ll, o);
     if (lane == 0 && tot_ll != 0.0) atomicAdd(&a.scalars[1], tot_ll);
   }
-  if (tid == 0 && it.y == 0) atomicAdd(&a.scalars[0], (double)nfr * (double)a.weight);  // :50
+  if constexpr (POST) {
+    // the sum of the weights of this block's entries, where an alignment has frames x weight
+    if (wave == 0) {
+      for (int o = 32; o > 0; o >>= 1) tot_w += __shfl_xor(tot_w, o);
+      if (lane == 0 && tot_w != 0.0) atomicAdd(&a.scalars[0], tot_w);
+    }
+  } else {
+    if (tid == 0 && it.y == 0) atomicAdd(&a.scalars[0], (double)nfr * (double)a.weight);  // :50
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -763,7 +784,7 @@ __device__ __forceinline__ float k3_row_sum(float v) {
 // gather (two dependent HBM loads, requested a chunk ahead precisely so that nobody waits for them) at the first barrier behind it
 __device__ __forceinline__ void k3_block_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <int KQ, int NBW>
+template <int KQ, int NBW, bool POST = false>
 __global__ __launch_bounds__(256) void k3_accumulate_mfma(K3Args a) {
   extern __shared__ __attribute__((aligned(16))) float k3s[];
   constexpr int XP = 4 * KQ;       // padded feature-row pitch (zero filled beyond D)
@@ -783,6 +804,7 @@ __global__ __launch_bounds__(256) void k3_accumulate_mfma(K3Args a) {
   float* xq = k3s;                          // [4][64][KH]
   float* red = xq + 4 * K3_CHUNK * KH;      // [4][64] per-wave per-frame max / sum
   float* fin = red + 4 * K3_CHUNK;          // [64] combined value per frame
+  [[maybe_unused]] float* wts = fin + K3_CHUNK;       // POST: [64] the chunk's entries' weights
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j16 = lane & 15, q = lane >> 4;
@@ -813,6 +835,7 @@ __global__ __launch_bounds__(256) void k3_accumulate_mfma(K3Args a) {
     for (int db = 0; db < NDB; ++db) acc[k][db] = f64x4{0, 0, 0, 0};
   }
   double tot_ll = 0.0;
+  [[maybe_unused]] double tot_w = 0.0;
 
   // The NEXT chunk's features are requested into registers as soon as this chunk's are parked in LDS (always-valid addresses:
   // last frame of the chunk, last dim; zero fill by select at the staging), so the two dependent HBM loads of the gather
@@ -820,13 +843,17 @@ __global__ __launch_bounds__(256) void k3_accumulate_mfma(K3Args a) {
   constexpr int NI = K3_CHUNK * XP / 256;
   constexpr bool PF = NBW < 4;           // four blocks per wave (193..256 Gaussians) leave no registers for the prefetch: it would spill
   float pre[NI];
+  [[maybe_unused]] float prew = 0.0f;    // POST: the weight of entry `lane` of the requested chunk
   auto request = [&](int c) {
     const int cfn = min(K3_CHUNK, nfr - c * K3_CHUNK);
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       const int i = tid + 256 * j, f = i / XP, d = i - f * XP;
-      pre[j] = a.feats[(int64_t)a.frame_ids[beg + c * K3_CHUNK + min(f, cfn - 1)] * D + min(d, D - 1)];
+      int row = a.frame_ids[beg + c * K3_CHUNK + min(f, cfn - 1)];
+      if constexpr (POST) row = a.e_row[row];
+      pre[j] = a.feats[(int64_t)row * D + min(d, D - 1)];
     }
+    if constexpr (POST) prew = a.e_w[a.frame_ids[beg + c * K3_CHUNK + min(lane, cfn - 1)]];
   };
   if (PF && it.y < nchunk) request(it.y);
   for (int c = it.y; c < nchunk; c += it.ny) {
@@ -841,6 +868,7 @@ __global__ __launch_bounds__(256) void k3_accumulate_mfma(K3Args a) {
       dst[0] = v;
       dst[2 * K3_CHUNK * KH] = v * v;
     }
+    if constexpr (POST) { if (tid < K3_CHUNK) wts[tid] = tid < cf ? prew : 0.0f; }
     if (PF && c + it.ny < nchunk) request(c + it.ny);
     k3_block_sync();
     // ---- phase A: ll[k][ft][reg] for Gaussian 16*(wave+4k)+j16, frame 16*ft + 4*q + reg.  Operands: lane (frame 16*ft + j16,
@@ -918,14 +946,17 @@ __global__ __launch_bounds__(256) void k3_accumulate_mfma(K3Args a) {
       for (int r = 0; r < 4; ++r) {
         const int f = 16 * ft + 4 * q + r;
         const float ssum = fin[f];
+        float wf = a.weight;                                          // POST: the entry's own weight
+        if constexpr (POST) wf = wts[f];
         if (wave == 0 && j16 == 0 && f < cf) {
           const float llf = __logf(ssum) + mx[ft][r];
           if (!(fabsf(llf) <= 3.0e38f)) atomicOr(a.err_flag, 1);      // diag-gmm.cc:385-387
-          tot_ll += (double)(llf * a.weight);                         // mle-am-diag-gmm.cc:49
+          tot_ll += (double)(llf * wf);                               // mle-am-diag-gmm.cc:49
+          if constexpr (POST) tot_w += (double)wf;                    // :50
         }
         // eigen.cc:31 (e / sum) and mle-diag-gmm.cc:153 (* weight) as ONE correctly rounded division per frame
         // and a multiply per Gaussian (<= 1 ulp from the reference's per-element division)
-        const float scale = f < cf ? a.weight / ssum : 0.0f;
+        const float scale = f < cf ? wf / ssum : 0.0f;
 #pragma unroll
         for (int k = 0; k < NBW; ++k) ll[k][ft][r] = ll[k][ft][r] * scale;
       }
@@ -976,7 +1007,15 @@ __global__ __launch_bounds__(256) void k3_accumulate_mfma(K3Args a) {
     for (int o2 = 32; o2 > 0; o2 >>= 1) tot_ll += __shfl_xor(tot_ll, o2);
     if (lane == 0 && tot_ll != 0.0) atomicAdd(&a.scalars[1], tot_ll);
   }
-  if (tid == 0 && it.y == 0) atomicAdd(&a.scalars[0], (double)nfr * (double)a.weight);  // mle-am-diag-gmm.cc:50
+  if constexpr (POST) {
+    // the sum of the weights of this block's entries, where an alignment has frames x weight
+    if (wave == 0) {
+      for (int o2 = 32; o2 > 0; o2 >>= 1) tot_w += __shfl_xor(tot_w, o2);
+      if (lane == 0 && tot_w != 0.0) atomicAdd(&a.scalars[0], tot_w);
+    }
+  } else {
+    if (tid == 0 && it.y == 0) atomicAdd(&a.scalars[0], (double)nfr * (double)a.weight);  // mle-am-diag-gmm.cc:50
+  }
 }
 
 // one global fp64 atomic per accumulator cell from a folded image [NB*16][2*XP] + occ[NB*16] (XP = 40)

@@ -981,6 +981,9 @@ struct khg_posteriors {
   std::vector<int64_t> frame_off, entry_off, arc_off;     // [U + 1]
   std::vector<PostChunk> chunks;
   int64_t bytes = 0;
+  khg_ctx* ctx = nullptr;              // the context it was made on
+  int32_t max_tid = -1;                // khg_posteriors_upload: the largest id (0: no entries); -1: made from lattices (the graph's labels)
+  int64_t* frame_off_d = nullptr;      // [U + 1] frame_off on the device, made with the handle (posteriors_flatten reads it)
 };
 
 namespace {
@@ -1009,6 +1012,13 @@ int lat_index(khg_ctx* ctx, khg_lattices* l) {
   HIPCHK(hipStreamSynchronize(ctx->stream));       // the cursors go with `dv`
   return KHG_OK;
 }
+// the handle's frame offsets on the device (not counted in its bytes: 8 (U + 1)); synchronous, so a handle either has them or is not made
+int post_frame_off_upload(khg_ctx* ctx, khg_posteriors* p) {
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&p->frame_off_d), 8 * ((size_t)p->U + 1)));
+  HIPCHK(hipMemcpyAsync(p->frame_off_d, p->frame_off.data(), 8 * ((size_t)p->U + 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
 }  // namespace
 
 extern "C" int khg_posteriors_destroy(khg_posteriors* p) {
@@ -1017,6 +1027,7 @@ extern "C" int khg_posteriors_destroy(khg_posteriors* p) {
     if (c.arc_post) (void)hipFree(c.arc_post);
     if (c.buf) (void)hipFree(c.buf);
   }
+  if (p->frame_off_d) (void)hipFree(p->frame_off_d);
   delete p;
   return KHG_OK;
 }
@@ -1057,7 +1068,7 @@ extern "C" int khg_lattices_posteriors(khg_ctx* ctx, const khg_lattices* lc, flo
   khg_lattices* l = const_cast<khg_lattices*>(lc);
   const int U = l->U;
   std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
-  res->U = U;
+  res->U = U; res->ctx = ctx;
   res->frame_off.assign((size_t)U + 1, 0);
   res->entry_off.assign((size_t)U + 1, 0);
   res->arc_off = l->arc_off;
@@ -1129,6 +1140,131 @@ extern "C" int khg_lattices_posteriors(khg_ctx* ctx, const khg_lattices* lc, flo
   if (rc) return rc;
   if (status_h) std::copy(st.begin(), st.end(), status_h);
   if (tot_like_h) std::copy(tl.begin(), tl.end(), tot_like_h);
+  if ((rc = post_frame_off_upload(ctx, res.get()))) return rc;
   *out = res.release();
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Posteriors from host arrays (ali-to-post, weight-silence-post, hand-made ones): one chunk in the layout of khg_lattices_posteriors',
+// without arc posteriors.
+extern "C" int khg_posteriors_validate(int32_t n_utt, const int64_t* frame_off_h, const int64_t* entry_begin_h, int64_t n_entries,
+                                       const int32_t* tid_h, const double* weight_h) {
+  const std::string who = "khg_posteriors_validate: ";
+  if (n_utt < 0 || !frame_off_h || !entry_begin_h || n_entries < 0 || (n_entries > 0 && (!tid_h || !weight_h)))
+    return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  if (frame_off_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "frame_off must start at 0");
+  for (int u = 0; u < n_utt; ++u)
+    if (frame_off_h[u + 1] < frame_off_h[u]) return khg_set_error(KHG_E_ARG, who + "frame_off decreases at utterance " + std::to_string(u));
+  const int64_t F = frame_off_h[n_utt];
+  if (entry_begin_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "entry_begin must start at 0");
+  for (int64_t f = 0; f < F; ++f)
+    if (entry_begin_h[f + 1] < entry_begin_h[f]) return khg_set_error(KHG_E_ARG, who + "entry_begin decreases at frame " + std::to_string(f));
+  if (entry_begin_h[F] != n_entries)
+    return khg_set_error(KHG_E_ARG, who + "entry_begin ends at " + std::to_string(entry_begin_h[F]) + ", the entries number " + std::to_string(n_entries));
+  for (int64_t e = 0; e < n_entries; ++e) {
+    if (tid_h[e] < 1) return khg_set_error(KHG_E_ARG, who + "entry " + std::to_string(e) + " has transition-id " + std::to_string(tid_h[e]) + " (ids start at 1)");
+    if (!std::isfinite(weight_h[e])) return khg_set_error(KHG_E_ARG, who + "entry " + std::to_string(e) + " has a weight that is not finite");
+  }
+  return KHG_OK;
+}
+extern "C" int khg_posteriors_upload(khg_ctx* ctx, int32_t n_utt, const int64_t* frame_off_h, const int64_t* entry_begin_h, const int32_t* tid_h,
+                                     const double* weight_h, khg_posteriors** out) {
+  if (ctx_dead(ctx) || !out) return khg_set_error(KHG_E_ARG, "khg_posteriors_upload: bad arguments");
+  *out = nullptr;
+  if (n_utt < 0 || !frame_off_h || !entry_begin_h || frame_off_h[0] != 0) return khg_set_error(KHG_E_ARG, "khg_posteriors_upload: bad arguments");
+  for (int u = 0; u < n_utt; ++u)        // (entry_begin's length comes from frame_off: checked before it is read)
+    if (frame_off_h[u + 1] < frame_off_h[u]) return khg_set_error(KHG_E_ARG, "khg_posteriors_upload: frame_off decreases at utterance " + std::to_string(u));
+  const int64_t F = frame_off_h[n_utt], E = entry_begin_h[F];
+  int rc = khg_posteriors_validate(n_utt, frame_off_h, entry_begin_h, E, tid_h, weight_h);
+  if (rc) return rc;
+  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
+  res->U = n_utt; res->ctx = ctx;
+  res->frame_off.assign(frame_off_h, frame_off_h + n_utt + 1);
+  res->entry_off.resize((size_t)n_utt + 1);
+  for (int u = 0; u <= n_utt; ++u) res->entry_off[(size_t)u] = entry_begin_h[frame_off_h[u]];
+  res->arc_off.assign((size_t)n_utt + 1, 0);
+  res->max_tid = 0;
+  for (int64_t e = 0; e < E; ++e) res->max_tid = std::max(res->max_tid, tid_h[e]);
+  if (n_utt == 0) { *out = res.release(); return KHG_OK; }
+  PostChunk q;
+  q.u0 = 0; q.n = n_utt; q.nf = F; q.ne = E;
+  q.o_weight = (8 * (q.nf + 1) + 255) & ~int64_t(255);
+  q.o_tid = q.o_weight + ((8 * q.ne + 255) & ~int64_t(255));
+  const int64_t total = q.o_tid + 4 * q.ne;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&q.buf), (size_t)std::max<int64_t>(total, 16)));
+  res->chunks.push_back(q);
+  res->bytes += total;
+  HIPCHK(hipMemcpyAsync(q.buf, entry_begin_h, 8 * ((size_t)F + 1), hipMemcpyHostToDevice, ctx->stream));
+  if (E) {
+    HIPCHK(hipMemcpyAsync(q.buf + q.o_weight, weight_h, 8 * (size_t)E, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(q.buf + q.o_tid, tid_h, 4 * (size_t)E, hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));        // the caller's arrays are free again
+  if ((rc = post_frame_off_upload(ctx, res.get()))) return rc;
+  *out = res.release();
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// What khg_acc_stats_post (khg_k3.hip) reads of a handle: its sizes, and its entries flattened into three arrays.
+void posteriors_info(const khg_posteriors* p, PostInfo* out) {
+  out->ctx = p->ctx; out->U = p->U; out->max_tid = p->max_tid;
+  out->frame_off = p->frame_off.data(); out->entry_off = p->entry_off.data();
+}
+struct PostFlatArgs {
+  const int64_t* entry_begin;       // [nf + 1], relative to the chunk
+  const double* weight; const int32_t* tid;
+  const int64_t* post_frame_off;    // [n + 1] the handle's frame offsets of the chunk's utterances; [0] is the chunk's first frame
+  const int64_t* set_frame_off;     // [n + 1] the utterance set's
+  int64_t nf, ne;
+  int32_t n, num_tids;
+  double scale;
+  int32_t* e_row; int32_t* e_tid; float* e_w;      // at the chunk's first entry
+  int32_t* err_flag;
+};
+// One thread per entry: its frame is the last f with entry_begin[f] <= e (empty frames repeat a value), its utterance the last b whose
+// first frame is <= f (utterances without frames repeat one).  No atomics but the error word's.
+__global__ __launch_bounds__(256) void k3_post_flatten(PostFlatArgs p) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t f0 = p.post_frame_off[0];
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < p.ne; e += stride) {
+    int64_t lo = 0, hi = p.nf;                       // entry_begin[lo] <= e < entry_begin[hi]
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (p.entry_begin[mid] <= e) lo = mid; else hi = mid;
+    }
+    const int64_t f = lo;
+    int blo = 0, bhi = p.n;                          // post_frame_off[blo] - f0 <= f < post_frame_off[bhi] - f0
+    while (bhi - blo > 1) {
+      const int mid = (blo + bhi) >> 1;
+      if (p.post_frame_off[mid] - f0 <= f) blo = mid; else bhi = mid;
+    }
+    const int64_t row = p.set_frame_off[blo] + (f - (p.post_frame_off[blo] - f0));
+    int32_t tid = p.tid[e];
+    float w = (float)(p.scale * p.weight[e]);        // one rounding
+    if (tid < 1 || tid > p.num_tids) { atomicOr(p.err_flag, 4); tid = 0; w = 0.0f; }
+    // |scale * w64| beyond float: an infinite weight would poison the block unseen (only ll is checked later): dropped like a bad id,
+    // and the error word says overflow
+    if (!(fabsf(w) <= 3.0e38f)) { atomicOr(p.err_flag, 1); tid = 0; w = 0.0f; }
+    p.e_row[e] = (int32_t)row; p.e_tid[e] = tid; p.e_w[e] = w;
+  }
+}
+int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set_frame_off_d, double scale, int32_t num_tids, int32_t* e_row,
+                       int32_t* e_tid, float* e_w) {
+  if (!p->frame_off_d) return KHG_OK;               // a handle of no utterances
+  KernelTimer kt(ctx, "k3_post_flatten");
+  for (const PostChunk& c : p->chunks) {
+    if (c.ne == 0) continue;
+    const int64_t e0 = p->entry_off[(size_t)c.u0];
+    PostFlatArgs a;
+    a.entry_begin = reinterpret_cast<const int64_t*>(c.buf); a.weight = reinterpret_cast<const double*>(c.buf + c.o_weight);
+    a.tid = reinterpret_cast<const int32_t*>(c.buf + c.o_tid);
+    a.post_frame_off = p->frame_off_d + c.u0; a.set_frame_off = set_frame_off_d + c.u0;
+    a.nf = c.nf; a.ne = c.ne; a.n = c.n; a.num_tids = num_tids; a.scale = scale;
+    a.e_row = e_row + e0; a.e_tid = e_tid + e0; a.e_w = e_w + e0; a.err_flag = ctx->err_flag_d;
+    KHG_LAUNCH(ctx, k3_post_flatten, dim3((unsigned)std::min<int64_t>(4096, (c.ne + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+  }
   return KHG_OK;
 }

@@ -515,7 +515,40 @@ void BindLattice(py::module_& m) {
     CApi(khg_posteriors_sizes(d.h, fo.data(), eo.data()));
     return std::make_pair(fo, eo);
   };
+  // the four flat arrays of a batch of Kaldi Posteriors (posterior.py: posts_to_arrays): checked for shape here, for content by
+  // khg_posteriors_validate
+  auto post_check = [](const Arr<int64_t>& fo, const Arr<int64_t>& eb, const Arr<int32_t>& tid, const Arr<double>& w) {
+    if (fo.ndim() != 1 || eb.ndim() != 1 || tid.ndim() != 1 || w.ndim() != 1 || fo.shape(0) < 1 || tid.shape(0) != w.shape(0))
+      throw Error("DevicePosteriors: frame_off [n_utt + 1], entry_begin [frames + 1], tid and weight [entries] are flat arrays");
+    const py::ssize_t U = fo.shape(0) - 1;
+    // (what sizes entry_begin must be right before khg_posteriors_validate reads it)
+    for (py::ssize_t u = 0; u < U; ++u) if (fo.at(u + 1) < fo.at(u)) throw Error("khg_posteriors_validate: frame_off decreases at utterance " + std::to_string(u));
+    if (fo.at(0) != 0 || eb.shape(0) != fo.at(U) + 1) throw Error("khg_posteriors_validate: frame_off starts at 0 and entry_begin has one element per frame plus one");
+    CApi(khg_posteriors_validate((int32_t)U, fo.data(), eb.data(), (int64_t)tid.shape(0), tid.data(), w.data()));
+  };
+  m.def("posteriors_validate", post_check, py::arg("frame_off"), py::arg("entry_begin"), py::arg("tid"), py::arg("weight"));
   py::class_<PyDevicePosteriors, std::shared_ptr<PyDevicePosteriors>>(m, "DevicePosteriors")
+      // a handle from host arrays (khg_posteriors_upload): no arc posteriors; an utterance without frames has status KHG_LAT_NO_PATH
+      .def_static("from_arrays", [post_check](py::object ctx, Arr<int64_t> fo, Arr<int64_t> eb, Arr<int32_t> tid, Arr<double> w) {
+        post_check(fo, eb, tid, w);
+        const size_t U = (size_t)fo.shape(0) - 1;
+        auto r = std::make_shared<PyDevicePosteriors>();
+        r->ctx_obj = ctx;
+        r->ctx = ctx.is_none() ? DefaultCtx() : reinterpret_cast<khg_ctx*>(ctx.attr("h").cast<uintptr_t>());
+        r->arc_off.assign(U + 1, 0);
+        r->status.resize(U); r->tot_like.assign(U, 0.0);
+        for (size_t u = 0; u < U; ++u) r->status[u] = fo.at(u + 1) > fo.at(u) ? KHG_LAT_SUCCEEDED : KHG_LAT_NO_PATH;
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_posteriors_upload(r->ctx, (int32_t)U, fo.data(), eb.data(), tid.data(), w.data(), &r->h));
+        }
+        return r;
+      }, py::arg("ctx"), py::arg("frame_off"), py::arg("entry_begin"), py::arg("tid"), py::arg("weight"))
+      // ... from Kaldi's Posterior per utterance: posts[u][t] is a list of (tid, weight)
+      .def_static("from_posteriors", [](py::object ctx, py::list posts) {
+        py::object arrays = py::module_::import("kaldi_hmm_gmm_amd.posterior").attr("posts_to_arrays")(posts);
+        return py::module_::import("kaldi_hmm_gmm_amd").attr("DevicePosteriors").attr("from_arrays")(ctx, *arrays);
+      }, py::arg("ctx"), py::arg("posts"))
       .def_property_readonly("status", [](PyDevicePosteriors& d) { return Vec1(d.status); })
       .def_property_readonly("tot_like", [](PyDevicePosteriors& d) { return Vec1(d.tot_like); })
       .def_property_readonly("num_utts", [](PyDevicePosteriors& d) { return (int)d.status.size(); })

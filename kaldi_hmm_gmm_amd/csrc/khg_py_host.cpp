@@ -432,6 +432,29 @@ void BindGmm(py::module_& m) {
         for (int32_t x : ali) tp[x] += 1.0;
         return py::make_tuple(ll, t);
       }, py::arg("am_gmm"), py::arg("transition_model"), py::arg("feats"), py::arg("ali"), py::arg("transition_accs") = py::none())
+      // gmm_acc_stats' device path: the Posterior of one utterance (a list per frame of (tid, weight)) through khg_acc_stats_post into the
+      // same resident statistics; transition_accs[tid] += weight on the host, as TransitionModel.accumulate does -> (log_like, transition_accs)
+      .def("_acc_stats_post", [](AccumAmDiagGmm& a, const AmDiagGmm& am, const TransitionModel& tm, Arr<float> feats, Arr<int64_t> eb, Arr<int32_t> tid,
+                                 Arr<double> w, py::object tacc) {
+        if (feats.ndim() != 2 || eb.ndim() != 1 || eb.shape(0) != feats.shape(0) + 1) throw Error("gmm_acc_stats: feats must be 2-D and len(post) == num_frames");
+        if (feats.shape(0) > 0 && feats.shape(1) != am.Dim()) throw Error("Dim mismatch: data dim = " + std::to_string(feats.shape(1)) + " vs. model dim = " + std::to_string(am.Dim()));
+        if (tid.ndim() != 1 || w.ndim() != 1 || tid.shape(0) != w.shape(0) || eb.at(0) != 0 || eb.at(eb.shape(0) - 1) != tid.shape(0)) throw Error("gmm_acc_stats: malformed posterior arrays");
+        const py::ssize_t nt = tm.NumTransitionIds() + 1;
+        for (py::ssize_t e = 0; e < tid.shape(0); ++e) if (tid.at(e) < 1 || tid.at(e) >= nt) throw Error("gmm_acc_stats: transition-id out of range");
+        const int64_t fo[2] = {0, (int64_t)feats.shape(0)};
+        const double ll = NoGil([&] { return a.AccumulatePost(am, tm, feats.data(), fo, 1, eb.data(), tid.data(), w.data()); });
+        py::array_t<double> t;
+        if (tacc.is_none()) { t = py::array_t<double>(nt); std::fill(t.mutable_data(), t.mutable_data() + nt, 0.0); }
+        else {
+          t = py::array_t<double>::ensure(tacc);
+          if (!t || t.ndim() != 1 || t.shape(0) != nt) throw Error("transition_accs: one count per transition-id (+ entry 0)");
+          if (!t.writeable() || !(t.flags() & py::array::c_style)) t = py::array_t<double, py::array::c_style>(t.attr("copy")());
+        }
+        double* tp = t.mutable_data();
+        for (py::ssize_t e = 0; e < tid.shape(0); ++e) tp[tid.at(e)] += (double)(float)w.at(e);
+        return py::make_tuple(ll, t);
+      }, py::arg("am_gmm"), py::arg("transition_model"), py::arg("feats"), py::arg("entry_begin"), py::arg("tid"), py::arg("weight"),
+         py::arg("transition_accs") = py::none())
       .def("_flush_device_stats", [](AccumAmDiagGmm& a) { NoGil([&] { a.Flush(); return 0; }); })
       .def_property_readonly("_has_device_stats", &AccumAmDiagGmm::HasDeviceStats)
       .def("get_acc", [](AccumAmDiagGmm& a, int i) { return std::make_shared<AccumDiagGmm>(*a.Acc(i)); }, py::arg("index"))   // the binding returns a COPY

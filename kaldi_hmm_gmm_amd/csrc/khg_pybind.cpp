@@ -708,6 +708,12 @@ struct KUtts {
     Check(NoGil([&] { return khg_acc_stats_reduce(ctx->h, m.h, tm.h, h, weight, accs.h, c, nparts); }));
   }
   void acc_stats(KModel& m, KTransitions& tm, KAccs& accs, float weight) { Check(NoGil([&] { return khg_acc_stats(ctx->h, m.h, tm.h, h, weight, accs.h); })); }
+  // gmm-acc-stats (khg_acc_stats_post): the statistics of every (transition-id, weight) of the posteriors, utterance u of `post` on
+  // utterance u of this set; no resident alignment needed
+  void acc_stats_post(KModel& m, KTransitions& tm, khg::PyDevicePosteriors& post, KAccs& accs, float scale) {
+    if (!post.h) throw py::value_error("acc_stats_post: the DevicePosteriors are closed");
+    Check(NoGil([&] { return khg_acc_stats_post(ctx->h, m.h, tm.h, h, post.h, scale, accs.h); }));
+  }
 };
 
 }  // namespace
@@ -812,6 +818,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
            py::arg("prune_interval") = 25, py::arg("prune_scale") = 0.1f, py::arg("acoustic_scale") = 1.0f, py::arg("scratch_per_frame") = 0)
       .def("upload_ali", &KUtts::upload_ali).def("download_ali", &KUtts::download_ali)
       .def("acc_stats", &KUtts::acc_stats, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f)
+      .def("acc_stats_post", &KUtts::acc_stats_post, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("accs"), py::arg("scale") = 1.0f)
       .def("acc_stats_reduce", &KUtts::acc_stats_reduce, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f,
            py::arg("comm") = py::none(), py::arg("nparts") = 4)
       .def("close", &KUtts::close);

@@ -457,6 +457,8 @@ extern "C" int khg_utts_destroy(khg_utts* u) {
   DEVFREE(u->pdf_count_d); DEVFREE(u->pdf_cursor_d); DEVFREE(u->frame_ids_d); DEVFREE(u->pdf_start_d); DEVFREE(u->tid_count_d);
   DEVFREE(u->sort_keys_d); DEVFREE(u->sort_keys_out_d); DEVFREE(u->sort_vals_d); DEVFREE(u->sort_tmp_d); DEVFREE(u->cs_hist_d); DEVFREE(u->cs_tot_d);
   DEVFREE(u->k3_part_d); DEVFREE(u->k3_llpart_d); DEVFREE(u->k3_items_d); DEVFREE(u->k3_item_off_d);
+  DEVFREE(u->pe_row_d); DEVFREE(u->pe_tid_d); DEVFREE(u->pe_ids_d); DEVFREE(u->pe_w_d); DEVFREE(u->pe_keys_d); DEVFREE(u->pe_keys_out_d);
+  DEVFREE(u->pe_vals_d); DEVFREE(u->pe_tmp_d); DEVFREE(u->pe_start_d);
   k1_free_band(u);
   if (u->ev_dp) (void)hipEventDestroy(u->ev_dp);
   if (u->ev_ali) (void)hipEventDestroy(u->ev_ali);

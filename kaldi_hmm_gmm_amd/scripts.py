@@ -13,6 +13,7 @@ from .device import DeviceAccs, DeviceModel, DeviceTransitions, UtteranceSet
 from .diag_gmm import AmDiagGmm, DiagGmm
 from .fst import StdVectorFst
 from .hmm_topology import HmmTopology
+from .posterior import posts_to_arrays
 from .mle import (AccumAmDiagGmm, GmmUpdateFlags, MleDiagGmmOptions, mle_am_diag_gmm_update, str_to_gmm_flags)
 from .transition_model import MleTransitionUpdateConfig, TransitionModel
 
@@ -114,6 +115,28 @@ def gmm_acc_stats_ali_batch(am_gmm: AmDiagGmm, gmm_accs: AccumAmDiagGmm, transit
         transition_accs = transition_model.init_stats()
     for f, a in zip(feats, alis):
         ll, transition_accs = gmm_acc_stats_ali(am_gmm, gmm_accs, transition_model, f, a, transition_accs)
+        tot += ll
+    return tot, transition_accs
+
+
+def gmm_acc_stats(am_gmm: AmDiagGmm, gmm_accs: AccumAmDiagGmm, transition_model: TransitionModel, feats, post,
+                  transition_accs: Optional[np.ndarray] = None):
+    """Kaldi's gmm-acc-stats for one utterance -> (log_like, transition_accs); gmm_accs is updated in place.
+    `post` is a Posterior: per frame a list of (transition-id, weight).  Every entry adds what gmm_acc_stats_ali adds for a frame with
+    that weight; the statistics stay on the device between calls, as gmm_acc_stats_ali's do."""
+    feats = np.ascontiguousarray(feats, np.float32)
+    _, entry_begin, tid, weight = posts_to_arrays([post])
+    return gmm_accs._acc_stats_post(am_gmm, transition_model, feats, entry_begin, tid, weight, transition_accs)
+
+
+def gmm_acc_stats_batch(am_gmm: AmDiagGmm, gmm_accs: AccumAmDiagGmm, transition_model: TransitionModel,
+                        feats: Sequence[np.ndarray], posts: Sequence, transition_accs: Optional[np.ndarray] = None):
+    """Several utterances, same contract: -> (total log_like, transition_accs)."""
+    tot = 0.0
+    if transition_accs is None:
+        transition_accs = transition_model.init_stats()
+    for f, p in zip(feats, posts):
+        ll, transition_accs = gmm_acc_stats(am_gmm, gmm_accs, transition_model, f, p, transition_accs)
         tot += ll
     return tot, transition_accs
 

@@ -38,13 +38,17 @@ DeviceLattices.prune(B) at the middle weight -- beside what gives the same answe
 Lattice objects and a host ShortestPath per weight and utterance.  Kernel milliseconds come from one more pass under the context's
 kernel timing; the report says how many of the host's paths the device's equal.
 
+--acc (next to --lattices --post) times khg_acc_stats_post on those posteriors -- flatten, bucket, accumulate, entries per frame --
+beside khg_acc_stats under k3_form = 1, k3_phase_a = 1 (the same fp32 form) on the best-path alignment of the same set, and reports
+the ratio per entry.
+
 --post (next to --lattices) times DeviceLattices.posteriors(1, 0.1) on the resident lattices the same way, beside the download of every
 lattice plus a host Lattice.forward_backward per utterance and beside the one-pair best path on the same handle; it reports the kernels
 of the first call on the handle (which builds the in-arc index) and of a later one, the posterior handle's bytes, and how many of the
 host's (transition-id, weight) entries the device's agree with to 1e-9.  (The lattice-simple decoder's lattices carry epsilon
 self-loops and are refused with KHG_LAT_EPS_LOOP: use --decoder faster.)
 
-Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post]
+Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post] [--acc]
        python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
@@ -262,6 +266,60 @@ def lattice_ops(ctx, dl, sweep, prune_beam, reps, post=False):
     return out
 
 
+def acc_from_post(ctx, dl, am, tm, feats, alignments, reps):
+    """--acc: khg_acc_stats_post on the posteriors (1, 0.1) of the resident lattices -- device time of flatten, bucket and accumulate --
+    beside khg_acc_stats under k3_form = 1, k3_phase_a = 1 (the same fp32 / fp64 MFMA form, one entry per frame) on the best-path
+    alignment of the same set, in the same process -> the report dict with the ratio per entry."""
+    from kaldi_hmm_gmm_amd import DeviceAccs, DeviceModel, DeviceTransitions, UtteranceSet
+    reps = max(reps, 5)
+    go, gc, w, miv, iv = am.flat()
+    id2pdf = np.asarray(tm.transition_id_to_pdf_array(), np.int32)
+    dm, dt = DeviceModel(ctx, go, gc, miv, iv), DeviceTransitions(ctx, id2pdf)
+    fo = np.concatenate([[0], np.cumsum([len(f) for f in feats])]).astype(np.int64)
+    us = UtteranceSet(ctx, None, fo, np.ascontiguousarray(np.concatenate(feats), np.float32))
+    accs = DeviceAccs(ctx, dm, dt)
+    P = dl.posteriors(1.0, 0.1)
+    ok = (np.asarray(P.status) & 1) != 0
+    pfo = np.asarray(P.frame_off)
+    frames, entries = int(pfo[-1]), int(P.entry_off[-1])
+    eb, tid, _ = P.download_arrays()
+    fr = np.repeat(np.arange(frames, dtype=np.int64), np.diff(np.asarray(eb)))
+    merged = entries - len(np.unique(fr * (int(id2pdf.max()) + 1) + id2pdf[np.asarray(tid)]))
+    us.acc_stats_post(dm, dt, P, accs); ctx.sync()                       # warm-up (allocates the scratch)
+    k_post = [kernel_ms(ctx, lambda: us.acc_stats_post(dm, dt, P, accs)) for _ in range(reps)]
+    t_post = []
+    for _ in range(reps):
+        ctx.sync(); t0 = time.time()
+        us.acc_stats_post(dm, dt, P, accs); ctx.sync()
+        t_post.append(time.time() - t0)
+    # the best-path alignment of the utterances with posteriors (0 = no statistics for a frame of the others)
+    ali = np.zeros(int(fo[-1]), np.int32)
+    for u, a in enumerate(alignments):
+        if ok[u] and len(a) == fo[u + 1] - fo[u]:
+            ali[fo[u]: fo[u + 1]] = a
+    us.upload_ali(ali)
+    # (k3_form = 1 alone lets an alignment pass take the fp16 form k3_accumulate_block16; k3_phase_a = 1 keeps the fp32 / fp64 MFMA form)
+    old, old_a = ctx.set_option("k3_form", 1), ctx.set_option("k3_phase_a", 1)
+    try:
+        us.acc_stats(dm, dt, accs); ctx.sync()
+        k_ali = [kernel_ms(ctx, lambda: us.acc_stats(dm, dt, accs)) for _ in range(reps)]
+    finally:
+        ctx.set_option("k3_form", old); ctx.set_option("k3_phase_a", old_a)
+    names = sorted({k for r in k_post for k in r})
+    post_ms = {k: float(np.median([r.get(k, 0.0) for r in k_post])) for k in names}
+    ali_ms = {k: float(np.median([r.get(k, 0.0) for r in k_ali])) for k in sorted({k for r in k_ali for k in r})}
+    n_ali = int((ali > 0).sum())
+    tot_post, tot_ali = sum(post_ms.values()), sum(ali_ms.values())
+    out = {"repetitions": reps, "frames": frames, "entries": entries, "entries_per_frame": entries / max(frames, 1),
+           "entries_post_to_pdf_post_would_merge": int(merged), "share_merged": merged / max(entries, 1),
+           "acc_stats_post_kernels_ms": post_ms, "acc_stats_post_total_ms": tot_post, "acc_stats_post_call": med(t_post),
+           "acc_stats_fp32_form_kernels_ms": ali_ms, "acc_stats_fp32_form_total_ms": tot_ali, "aligned_frames": n_ali,
+           "ns_per_entry_post": 1e6 * tot_post / max(entries, 1), "ns_per_frame_ali": 1e6 * tot_ali / max(n_ali, 1),
+           "ratio_per_entry": (tot_post / max(entries, 1)) / (tot_ali / max(n_ali, 1)) if tot_ali and n_ali else None}
+    P.close(); us.close(); accs.close(); dm.close(); dt.close()
+    return out
+
+
 def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
     """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
     after one warm-up round; and the last results."""
@@ -446,9 +504,12 @@ def main():
     ap.add_argument("--sweep", default=None, metavar="LO:HI", help="with --lattices: best paths at the integer LM weights LO..HI in one call")
     ap.add_argument("--prune-beam", type=float, default=None, help="with --lattices: prune the resident lattices to this beam")
     ap.add_argument("--post", action="store_true", help="with --lattices: forward-backward posteriors of the resident lattices")
+    ap.add_argument("--acc", action="store_true", help="with --lattices --post: GMM statistics from those posteriors (khg_acc_stats_post)")
     args = ap.parse_args()
     if (args.sweep or args.prune_beam is not None or args.post) and not args.lattices:
         ap.error("--sweep / --prune-beam / --post need --lattices")
+    if args.acc and (not args.post or args.shared_graph):
+        ap.error("--acc needs --lattices --post (and is not timed with --shared-graph)")
     if args.shared_graph or args.yesno:
         shared_graph_main(args)
         return
@@ -512,6 +573,8 @@ def main():
         if args.sweep or args.prune_beam is not None or args.post:
             _, dl = khg.get_raw_lattice_faster_device_batch(am, tm, fsts, feats, cfg, 0.1)
             faster_ops = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps, args.post)
+            if args.acc:
+                faster_ops["acc_stats_post"] = acc_from_post(ctx, dl, am, tm, feats, [r["alignment"] for r in fres], args.reps)
             dl.close()
     st = [r["status"] for r in res]
     out = {"decoder": args.decoder,"utterances": args.utts, "frames": frames, "lattice_s": min(lat_s), "lattice_frames_per_s": frames / min(lat_s),
@@ -541,6 +604,8 @@ def main():
             if args.sweep or args.prune_beam is not None or args.post:
                 _, dl = khg.get_raw_lattice_simple_device_batch(am, tm, fsts, feats, scfg, 0.1)
                 out["lattice_ops"] = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps, args.post)
+                if args.acc:
+                    out["lattice_ops"]["acc_stats_post"] = acc_from_post(ctx, dl, am, tm, feats, [r["alignment"] for r in res], args.reps)
                 dl.close()
         if args.check > 0:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
