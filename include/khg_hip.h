@@ -116,12 +116,25 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
 #define KHG_OPT_LAT_OPS_LDS 18   /* khg_lattices_best_path / khg_lattices_prune / khg_lattices_posteriors: 0 (DEFAULT) an utterance's lattice is staged into LDS when it takes
                                     at most 48 KiB there, 1 never (every lattice is read from its HBM arrays); same results bit for
                                     bit                                                                              [KHG_LAT_OPS_LDS] */
-#define KHG_OPT_COUNT 19
+#define KHG_OPT_K1_LAUNCH 19     /* launch shape of the default (f16x2s) K1: 1 one workgroup per chunk of frame tiles; 2 persistent -- one workgroup per
+                                    CU takes chunks from a counter, in the same order, and copies the next chunk's frame tiles into LDS under
+                                    the tail of the current one; 0 (DEFAULT) automatic: persistent where it measured faster, never for a small
+                                    set or the packed small-pdf kernels; same scores bit for bit             [KHG_K1_LAUNCH=auto|chunk|persistent] */
+#define KHG_OPT_K1_PGRID 20      /* persistent K1: at most this many workgroups (tests: more chunks than workgroups on a small set);
+                                    0 (DEFAULT) as many as the chip holds at once, by the occupancy query                  [KHG_K1_PGRID] */
+#define KHG_OPT_K1_PROF 21       /* 1: boundary stamps of every K1 chunk (entry, barrier, first / last wave out of work), summed per CU,
+                                    to stderr; the call waits for the kernel                                              [KHG_K1_PROF] */
+#define KHG_OPT_COUNT 22
 /* Read-only figures (khg_ctx_get_option only): the per-call scratch block behind small utterance sets (DESIGN.md "per-utterance calls"). */
 #define KHG_INFO_SCRATCH_BYTES 100   /* bytes of the block in use (its top), 0 before the first small set */
 #define KHG_INFO_SCRATCH_BLOCKS 101  /* live allocations inside it */
 int khg_ctx_set_option(khg_ctx *ctx, int option, int value);
 int khg_ctx_get_option(const khg_ctx *ctx, int option, int *value);
+/* The validation behind khg_ctx_set_option, without a context (no device needed): KHG_OK or KHG_E_ARG. */
+int khg_option_check(int option, int value);
+/* What khg_ctx_create makes of the environment variable `name` when it is set to `text`: KHG_OK and the (option, value) it seeds, or
+ * KHG_E_ARG -- no such variable, an unknown word, a value outside the option's range (khg_ctx_create then keeps the default). */
+int khg_option_from_env(const char *name, const char *text, int *option, int *value);
 
 /* ---- acoustic model ------------------------------------------------------------------- */
 /* AmDiagGmm (csrc/am-diag-gmm.h:96) as flat ragged arrays: pdf p owns Gaussians

@@ -108,6 +108,8 @@ SIGNATURES = {
     "khg_ctx_set_k1_form": (C.c_int, [vp, C.c_int]),
     "khg_ctx_set_option": (C.c_int, [vp, C.c_int, C.c_int]),
     "khg_ctx_get_option": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
+    "khg_option_check": (C.c_int, [C.c_int, C.c_int]),
+    "khg_option_from_env": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "khg_ctx_get_timings": (C.c_int, [vp, C.c_char_p, C.c_int64, c_f32p, C.c_int32, c_i32p]),
     "khg_model_create": (C.c_int, [vp, C.c_int32, C.c_int32, c_i32p, c_f32p, c_f32p, c_f32p, C.POINTER(vp)]),
     "khg_model_destroy": (C.c_int, [vp]),

@@ -130,7 +130,7 @@ extern "C" int khg_ctx_destroy(khg_ctx* c) {
       c->arena = KhgArena();
     }
   }
-  DEVFREE(c->err_flag_d); DEVFREE(c->dump_d);
+  DEVFREE(c->err_flag_d); DEVFREE(c->dump_d); DEVFREE(c->k1_next_d);
   if (c->err_host) (void)hipHostFree(c->err_host);
   if (c->arena.dev) (void)hipFree(c->arena.dev);
   if (c->arena.host) (void)hipHostFree(c->arena.host);
@@ -168,11 +168,17 @@ extern "C" int khg_ctx_get_timings(khg_ctx* c, char* names, int64_t names_cap, f
 }
 // valid range of every option (inclusive)
 static const struct { int lo, hi; } k_opt_range[KHG_OPT_COUNT] = {
-  {KHG_K1_AUTO, KHG_K1_F16X2S}, {0, 4}, {0, 6}, {0, 1 << 20}, {-1, 1}, {0, 255}, {0, 1}, {0, 4}, {0, 3}, {0, 1}, {0, 2}, {0, 2}, {0, 2}, {0, 64}, {0, 1}, {0, 1}, {0, 1}, {0, 1 << 20}, {0, 1}};
-extern "C" int khg_ctx_set_option(khg_ctx* c, int opt, int value) {
-  if (!c || opt < 0 || opt >= KHG_OPT_COUNT) return khg_set_error(KHG_E_ARG, "khg_ctx_set_option: bad arguments");
+  {KHG_K1_AUTO, KHG_K1_F16X2S}, {0, 4}, {0, 6}, {0, 1 << 20}, {-1, 1}, {0, 255}, {0, 1}, {0, 4}, {0, 3}, {0, 1}, {0, 2}, {0, 2}, {0, 2}, {0, 64}, {0, 1}, {0, 1}, {0, 1}, {0, 1 << 20}, {0, 1}, {0, 2}, {0, 1 << 16}, {0, 1}};
+extern "C" int khg_option_check(int opt, int value) {
+  if (opt < 0 || opt >= KHG_OPT_COUNT) return khg_set_error(KHG_E_ARG, "khg_option_check: no such option");
   if (value < k_opt_range[opt].lo || value > k_opt_range[opt].hi || (opt == KHG_OPT_K1_FORM && value == 1))      // (1: the removed bf16x3 form)
     return khg_set_error(KHG_E_ARG, "khg_ctx_set_option: option " + std::to_string(opt) + " takes values " + std::to_string(k_opt_range[opt].lo) + " .. " + std::to_string(k_opt_range[opt].hi));
+  return KHG_OK;
+}
+extern "C" int khg_ctx_set_option(khg_ctx* c, int opt, int value) {
+  if (!c || opt < 0 || opt >= KHG_OPT_COUNT) return khg_set_error(KHG_E_ARG, "khg_ctx_set_option: bad arguments");
+  int rc = khg_option_check(opt, value);
+  if (rc) return rc;
   c->opt[opt] = value;
   return KHG_OK;
 }
@@ -188,25 +194,26 @@ extern "C" int khg_ctx_get_option(const khg_ctx* c, int opt, int* value) {
 extern "C" int khg_ctx_set_k1_form(khg_ctx* c, int form) { return khg_ctx_set_option(c, KHG_OPT_K1_FORM, form); }
 // Defaults from the environment, read ONCE per context (A/B runs of an unmodified caller): NAME=value, value an integer or one of the words
 // listed.  Everything else goes through khg_ctx_set_option.
-static void ctx_defaults_from_env(khg_ctx* c) {
-  static const struct { const char* name; int opt; const char* words; } tab[] = {
-    {"KHG_K1", KHG_OPT_K1_FORM, "auto=0,pdf=2,fp32=2,utt=3,f16x2=4,f16x2s=5"},
-    {"KHG_K1_ORDER", KHG_OPT_K1_ORDER, "desc=0,none=1,asc=2,tiles=3,xcd=4"},
-    {"KHG_K1_NF", KHG_OPT_K1_NF, ""}, {"KHG_K1P_TS", KHG_OPT_K1P_TS, ""}, {"KHG_K1_INTERLEAVE", KHG_OPT_K1_INTERLEAVE, ""},
-    {"KHG_K1B_DBG", KHG_OPT_K1_DBG, ""}, {"KHG_K2_INORDER", KHG_OPT_K2_INORDER, ""}, {"KHG_K2_KS", KHG_OPT_K2_KS, ""},
-    {"KHG_K2_SERIAL", KHG_OPT_K2_SERIAL, ""}, {"KHG_K2_PROF", KHG_OPT_K2_PROF, ""},
-    {"KHG_K3_BUCKET", KHG_OPT_K3_BUCKET, "sort=0,atomic=1,count=2"}, {"KHG_K3_FORM", KHG_OPT_K3_FORM, "auto=0,block=1,valu=2"},
-    {"KHG_K3_VALU", KHG_OPT_K3_FORM, "1=2"}, {"KHG_K3_PHASEB", KHG_OPT_K3_PHASE_B, "f64=0,f32=1,f16=2"},
-    {"KHG_K3_NY", KHG_OPT_K3_NY, ""}, {"KHG_DEBUG", KHG_OPT_DEBUG, ""}, {"KHG_K3_PHASEA", KHG_OPT_K3_PHASE_A, "auto=0,f16=0,f32=1"},
-    {"KHG_K2_SPLIT", KHG_OPT_K2_SPLIT, "on=0,off=1"}, {"KHG_K2S_HUB", KHG_OPT_K2S_HUB, ""},
-    {"KHG_LAT_OPS_LDS", KHG_OPT_LAT_OPS_LDS, "on=0,off=1"}};
-  c->opt[KHG_OPT_K1_INTERLEAVE] = -1;
-  c->opt[KHG_OPT_K1P_TS] = 1024;
-  c->opt[KHG_OPT_K2S_HUB] = 32;          // measured: DESIGN.md section 7c
-  c->opt[KHG_OPT_K3_PHASE_B] = 2;        // both phases of K3's wave form on the fp16 matrix cores where they apply (else the fp64 pipe)
-  for (const auto& t : tab) {
-    const char* e = getenv(t.name);
-    if (!e || !*e) continue;
+static const struct { const char* name; int opt; const char* words; } k_env_tab[] = {
+  {"KHG_K1", KHG_OPT_K1_FORM, "auto=0,pdf=2,fp32=2,utt=3,f16x2=4,f16x2s=5"},
+  {"KHG_K1_ORDER", KHG_OPT_K1_ORDER, "desc=0,none=1,asc=2,tiles=3,xcd=4"},
+  {"KHG_K1_NF", KHG_OPT_K1_NF, ""}, {"KHG_K1P_TS", KHG_OPT_K1P_TS, ""}, {"KHG_K1_INTERLEAVE", KHG_OPT_K1_INTERLEAVE, ""},
+  {"KHG_K1B_DBG", KHG_OPT_K1_DBG, ""}, {"KHG_K2_INORDER", KHG_OPT_K2_INORDER, ""}, {"KHG_K2_KS", KHG_OPT_K2_KS, ""},
+  {"KHG_K2_SERIAL", KHG_OPT_K2_SERIAL, ""}, {"KHG_K2_PROF", KHG_OPT_K2_PROF, ""},
+  {"KHG_K3_BUCKET", KHG_OPT_K3_BUCKET, "sort=0,atomic=1,count=2"}, {"KHG_K3_FORM", KHG_OPT_K3_FORM, "auto=0,block=1,valu=2"},
+  {"KHG_K3_VALU", KHG_OPT_K3_FORM, "1=2"}, {"KHG_K3_PHASEB", KHG_OPT_K3_PHASE_B, "f64=0,f32=1,f16=2"},
+  {"KHG_K3_NY", KHG_OPT_K3_NY, ""}, {"KHG_DEBUG", KHG_OPT_DEBUG, ""}, {"KHG_K3_PHASEA", KHG_OPT_K3_PHASE_A, "auto=0,f16=0,f32=1"},
+  {"KHG_K2_SPLIT", KHG_OPT_K2_SPLIT, "on=0,off=1"}, {"KHG_K2S_HUB", KHG_OPT_K2S_HUB, ""},
+  {"KHG_LAT_OPS_LDS", KHG_OPT_LAT_OPS_LDS, "on=0,off=1"},
+  {"KHG_K1_LAUNCH", KHG_OPT_K1_LAUNCH, "auto=0,chunk=1,persistent=2"}, {"KHG_K1_PGRID", KHG_OPT_K1_PGRID, ""},
+  {"KHG_K1_PROF", KHG_OPT_K1_PROF, ""}};
+// What khg_ctx_create makes of the environment variable `name` set to `text`: KHG_OK and (option, value), or KHG_E_ARG -- an unknown
+// variable, an unknown word, a value outside the option's range (khg_ctx_create ignores such a setting: the default stays).
+extern "C" int khg_option_from_env(const char* name, const char* text, int* option, int* value) {
+  if (!name || !text || !*text || !option || !value) return khg_set_error(KHG_E_ARG, "khg_option_from_env: bad arguments");
+  for (const auto& t : k_env_tab) {
+    if (strcmp(t.name, name) != 0) continue;
+    const char* e = text;
     int v = atoi(e);
     bool word = false;
     for (const char* w = t.words; *w;) {                 // "word=value,word=value"
@@ -217,8 +224,25 @@ static void ctx_defaults_from_env(khg_ctx* c) {
       if (!comma) break;
       w = comma + 1;
     }
-    if (!word && *t.words && !(e[0] >= '0' && e[0] <= '9') && e[0] != '-') continue;      // an unknown word: ignored
-    if (v >= k_opt_range[t.opt].lo && v <= k_opt_range[t.opt].hi) c->opt[t.opt] = v;
+    if (!word && *t.words && !(e[0] >= '0' && e[0] <= '9') && e[0] != '-')
+      return khg_set_error(KHG_E_ARG, std::string(name) + ": unknown word '" + text + "'");
+    if (v < k_opt_range[t.opt].lo || v > k_opt_range[t.opt].hi)
+      return khg_set_error(KHG_E_ARG, std::string(name) + " takes values " + std::to_string(k_opt_range[t.opt].lo) + " .. " + std::to_string(k_opt_range[t.opt].hi));
+    *option = t.opt; *value = v;
+    return KHG_OK;
+  }
+  return khg_set_error(KHG_E_ARG, std::string("khg_option_from_env: no such variable: ") + name);
+}
+static void ctx_defaults_from_env(khg_ctx* c) {
+  c->opt[KHG_OPT_K1_INTERLEAVE] = -1;
+  c->opt[KHG_OPT_K1P_TS] = 1024;
+  c->opt[KHG_OPT_K2S_HUB] = 32;          // measured: DESIGN.md section 7c
+  c->opt[KHG_OPT_K3_PHASE_B] = 2;        // both phases of K3's wave form on the fp16 matrix cores where they apply (else the fp64 pipe)
+  for (const auto& t : k_env_tab) {
+    const char* e = getenv(t.name);
+    if (!e || !*e) continue;
+    int opt = 0, v = 0;
+    if (khg_option_from_env(t.name, e, &opt, &v) == KHG_OK) c->opt[opt] = v;      // anything else: ignored
   }
 }
 extern "C" int khg_ctx_sync(khg_ctx* c) {

@@ -60,6 +60,8 @@ struct khg_ctx {
   int32_t* err_flag_d = nullptr;
   int32_t* err_host = nullptr;      // 256 pinned bytes: [0] landing word of check_err_flag, [64..128) the 8 scalars of khg_accs_download_trans
   bool side_dirty[NSIDE] = {false, false, false, false};   // work was enqueued on the side stream since it was last waited for
+  int32_t* k1_next_d = nullptr;     // the persistent K1 launch's chunk counter (k1s_persistent), zeroed on the stream before every launch
+  int k1_pgrid[2] = {0, 0};         // ... and its grid (workgroups the chip holds at once, by the occupancy query) for KS = 5 / 10
   float* dump_d = nullptr;          // 256 floats nobody reads (K1 f16x2s: where the pipeline's first, empty value goes)
   KhgArena arena;
   bool pageable_pending = false;    // a hipMemcpyAsync from pageable host memory may still be reading its source (sync_pageable)

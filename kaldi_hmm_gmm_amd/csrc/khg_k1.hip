@@ -443,6 +443,37 @@ static int loglikes_f16x2(khg_ctx* ctx, khg_model* m, khg_utts* u, bool reachabl
   return KHG_OK;
 }
 
+// KHG_OPT_K1_PROF: the chunks' stamps (K1sArgs::stamps) -> one line on stderr.  Per CU the chunks are put in the order they ran;
+// "boundary" is the time between the moment a chunk's LAST wave found the work-item counter exhausted and the moment the next chunk
+// of that CU passed its barrier (no MFMA of either in between), "tail" the time between a chunk's FIRST and LAST exhausted wave
+// (some SIMDs idle), "fill" entry to barrier; all as shares of the CUs' busy spans (first entry to last exhaustion).
+static void k1_prof_report(const std::vector<long long>& st, const char* launch, int KS) {
+  struct Rec { long long cu, t0, t1, t2, t3; };
+  std::vector<Rec> r;
+  for (size_t i = 0; i + 8 <= st.size(); i += 8)
+    if (st[i + 3] > 0 && st[i + 1] > 0) r.push_back(Rec{st[i + 4], st[i], st[i + 1], st[i + 2], st[i + 3]});
+  std::sort(r.begin(), r.end(), [](const Rec& x, const Rec& y) { return x.cu != y.cu ? x.cu < y.cu : x.t1 < y.t1; });
+  double span = 0, boundary = 0, tail = 0, fill = 0;
+  size_t ncu = 0;
+  for (size_t i = 0; i < r.size();) {
+    size_t j = i;
+    while (j < r.size() && r[j].cu == r[i].cu) ++j;
+    long long end = r[i].t3;
+    for (size_t k = i; k < j; ++k) {
+      if (k > i && r[k].t1 > r[k - 1].t3) boundary += (double)(r[k].t1 - r[k - 1].t3);
+      tail += (double)(r[k].t3 - r[k].t2);
+      fill += (double)(r[k].t1 - r[k].t0);
+      end = std::max(end, r[k].t3);
+    }
+    span += (double)(end - r[i].t0);
+    ++ncu; i = j;
+  }
+  if (span <= 0) { fprintf(stderr, "[KHG_K1_PROF] no stamps\n"); return; }
+  fprintf(stderr, "[KHG_K1_PROF] KS %d, %s: %zu chunks on %zu CUs | shares of the CUs' busy span: boundary (last wave done -> next chunk past its barrier) %.4f, "
+          "tail (first -> last wave done) %.4f, fill (entry -> barrier) %.4f | ticks per chunk: boundary %.0f tail %.0f fill %.0f span %.0f\n",
+          KS, launch, r.size(), ncu, boundary / span, tail / span, fill / span, boundary / r.size(), tail / r.size(), fill / r.size(), span / r.size());
+}
+
 // K1 on the fp16 matrix cores, one accumulator per chain, transposed decomposition (khg_k1_f16x2s.hip.inc; the default).
 // -> KHG_OK, an error, or +1: outside this form's domain (the caller tries the two-accumulator f16x2 form next).
 static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
@@ -609,26 +640,69 @@ static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
   a.c1 = std::ldexp(1.44269504088896340736f, -S);
   a.inv_scale = std::ldexp(1.0f, -S);
   a.mfloor = -3.0e38f / std::max(1.0f, a.c1);
-  a.ubound = (band || tail_shift) ? m->ubound_d : nullptr; a.repair_status = nullptr; a.repair_bit = 0;
+  a.ubound = (band || tail_shift) ? m->ubound_d : nullptr; a.repair_status = nullptr; a.repair_bit = 0; a.stamps = nullptr;
   u->ll_mode = band ? 2 : (reachable_only ? 1 : 0);
   if (u->n_schunks > 0) {
     rc = m->wimgs_sync.before_read(ctx->stream);
     if (rc) return rc;
-    const size_t lds = (size_t)NMAX * k1s_xtile_bytes(KS) + 64;     // + the work-item counter
+    const size_t lds = (size_t)NMAX * k1s_xtile_bytes(KS) + K1S_CTL_BYTES;     // + the control and stamp words
     if (band) {
       if (!u->band_args) u->band_args = new K1sArgs();
       *static_cast<K1sArgs*>(u->band_args) = a; u->band_model = m; u->band_ks = KS; u->band_lds = lds;
       u->band_serial = m->serial; u->band_version = m->version; u->band_key = m->wimgs_key;
     }
+    // KHG_OPT_K1_LAUNCH: 1 one workgroup per chunk, 2 one persistent workgroup per CU (k1s_persistent); 0: persistent where it
+    // measured faster -- at KS = 5 and KS = 10 alike (profiles/r15_k1_chunk_boundary.txt: 54.05 -> 52.78 ms at 100 000 utterances,
+    // 6.92 -> 6.68 at 12 500, 50.4 -> 50.0 at D = 80) -- but never for the packed kernels or a small set (the per-utterance call
+    // pattern: fewer chunks than CUs, and one more stream-ordered memset per call)
+    const int lopt = ctx->opt[KHG_OPT_K1_LAUNCH];
+    const bool persistent = pack == 1 && (lopt == 2 || (lopt == 0 && !u->small));
     const void* fn = pack == 4 ? (const void*)k1s_loglikes_packed<5, 4> : pack == 2 ? (const void*)k1s_loglikes_packed<5, 2>
+                     : persistent ? (KS == 5 ? (const void*)k1s_persistent<5> : (const void*)k1s_persistent<10>)
                      : KS == 5 ? (const void*)k1s_loglikes<5> : (const void*)k1s_loglikes<10>;
     HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int pgrid = 0;
+    if (persistent) {
+      // one workgroup per CU that can hold one: from the occupancy query, once per context and kernel
+      int& cached = ctx->k1_pgrid[KS == 5 ? 0 : 1];
+      if (cached <= 0) {
+        int per_cu = 0, ncu = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 512, lds));
+        HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        if (per_cu <= 0 || ncu <= 0) return khg_set_error(KHG_E_HIP, "khg_loglikes: the persistent K1 kernel does not fit a CU");
+        cached = per_cu * ncu;
+      }
+      pgrid = std::min<int>(cached, u->n_schunks);
+      if (ctx->opt[KHG_OPT_K1_PGRID] > 0) pgrid = std::min(pgrid, ctx->opt[KHG_OPT_K1_PGRID]);
+      if (!ctx->k1_next_d) { rc = dev_alloc(&ctx->k1_next_d, 1); if (rc) return rc; }
+      rc = arena_flush(ctx);
+      if (rc) return rc;
+      HIPCHK(hipMemsetAsync(ctx->k1_next_d, 0, sizeof(int32_t), ctx->stream));
+    }
+    // KHG_OPT_K1_PROF: boundary stamps of every chunk (a diagnostic: the launch is followed by a download and a wait)
+    long long* stamps_d = nullptr;
+    if (ctx->opt[KHG_OPT_K1_PROF] && pack == 1) {
+      rc = dev_alloc(&stamps_d, (size_t)u->n_schunks * 8);
+      if (rc) return rc;
+      HIPCHK(hipMemsetAsync(stamps_d, 0, sizeof(long long) * 8 * (size_t)u->n_schunks, ctx->stream));
+      a.stamps = stamps_d;
+    }
     {
       KernelTimer kt(ctx, "k1_loglikes");
       if (pack == 4) KHG_LAUNCH(ctx, (k1s_loglikes_packed<5, 4>), dim3(u->n_schunks), dim3(512), lds, ctx->stream, a);
       else if (pack == 2) KHG_LAUNCH(ctx, (k1s_loglikes_packed<5, 2>), dim3(u->n_schunks), dim3(512), lds, ctx->stream, a);
+      else if (persistent && KS == 5) KHG_LAUNCH(ctx, (k1s_persistent<5>), dim3(pgrid), dim3(512), lds, ctx->stream, a, (int)u->n_schunks, ctx->k1_next_d);
+      else if (persistent) KHG_LAUNCH(ctx, (k1s_persistent<10>), dim3(pgrid), dim3(512), lds, ctx->stream, a, (int)u->n_schunks, ctx->k1_next_d);
       else if (KS == 5) KHG_LAUNCH(ctx, (k1s_loglikes<5>), dim3(u->n_schunks), dim3(512), lds, ctx->stream, a);
       else KHG_LAUNCH(ctx, (k1s_loglikes<10>), dim3(u->n_schunks), dim3(512), lds, ctx->stream, a);
+    }
+    if (stamps_d) {
+      std::vector<long long> st((size_t)u->n_schunks * 8);
+      hipError_t e = hipMemcpyAsync(st.data(), stamps_d, sizeof(long long) * st.size(), hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      DEVFREE(stamps_d);
+      if (e != hipSuccess) return khg_set_error(KHG_E_HIP, hipGetErrorString(e));
+      k1_prof_report(st, persistent ? "persistent" : "one chunk per workgroup", KS);
     }
     HIPCHK(hipGetLastError());
     rc = m->wimgs_sync.after_read(ctx->stream);
@@ -800,7 +874,7 @@ void k1_free_band(khg_utts* u) {
 int k1_band_repair(khg_ctx* ctx, khg_utts* u, int32_t* status_d, int repair_bit, hipStream_t side) {
   if (u->ll_mode != 2 || !u->band_model || !u->band_args || u->n_schunks <= 0) return KHG_OK;
   K1sArgs ra = *static_cast<K1sArgs*>(u->band_args);
-  ra.repair_status = status_d; ra.repair_bit = repair_bit;
+  ra.repair_status = status_d; ra.repair_bit = repair_bit; ra.stamps = nullptr;
   khg_model* bm = u->band_model;
   int rc = bm->wimgs_sync.before_read(side);
   if (rc) return rc;

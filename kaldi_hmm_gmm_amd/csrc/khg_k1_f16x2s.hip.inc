@@ -51,7 +51,9 @@ typedef float k1s_f32x4 __attribute__((ext_vector_type(4)));
 #endif
 #ifndef K1S_KO
 #define K1S_KO 0          // MEASUREMENT builds only (tools/ab_k1.sh; results are WRONG): knock-outs that price one part of the loop each --
-#endif                    // 1 no score stores, 2 no band fills, 4 B fragments stay in registers (no LDS re-reads), 8 W tiles loaded once, 16 no log-sum-exp
+#endif                    // 1 no score stores, 2 no band fills, 4 B fragments stay in registers (no LDS re-reads), 8 W tiles loaded once, 16 no log-sum-exp,
+                          // 32 no chunk fill (the LDS-DMA copy of the chunk's frame tiles and its wait are skipped: the chains read whatever LDS holds;
+                          //    timed as 33 against 1 -- without the score stores, so that nothing downstream reads those values)
 #ifndef K1S_PRIO
 #define K1S_PRIO 0        // 1: s_setprio 1 for the second-dispatched half of the workgroup (waves 4-7)
 #endif
@@ -101,7 +103,15 @@ struct K1sArgs {
   // order-faithful decoder is about to read EVERY cell a token can reach) are recomputed, without the band's upper limit
   const int32_t* repair_status;
   int32_t repair_bit;
+  // KHG_OPT_K1_PROF: per chunk 8 words -- clock64() at entry | after the barrier | when the FIRST wave found the work-item counter
+  // exhausted | when the LAST one did | (XCC << 16) | HW_ID bits 8-15 (shader engine, array, CU) | frame tiles; nullptr: no stamps
+  long long* stamps;
 };
+
+// LDS behind the NMAX frame-tile slots: 16 control words (one-chunk launch: [0] the work-item counter; persistent launch: two
+// banks of 8, see k1s_persistent), then two banks of stamp words {first, last, waves done} of 32 bytes (KHG_OPT_K1_PROF)
+#define K1S_CTL_BYTES 128
+struct K1sProf { unsigned long long first, last; int done, pad[3]; };
 
 // (ubound[first tile of pdf p] = log sum_g exp(gconst_g + 0.5 sum_d mi_gd^2 / iv_gd) + margin -- every component at its own mean: an
 //  upper bound of DiagGmm::LogLikelihood(x) for every x -- is computed by k0_model_stats, khg_ctx_model.hip, in fp64, once per
@@ -177,34 +187,46 @@ __global__ void k1s_pack_x(const float* __restrict__ feats, const int64_t* __res
 // re-associated into dependent v_pk_add_f32 chains
 #define K1S_PIN(x) asm volatile("" : "+v"(x))
 
-// one chunk (<= NMAX frame tiles of one utterance) by one workgroup: the whole kernel, as a function of the chunk's index
+// frame tiles [f0, f1) of chunk `ck` -> base + f * XTB by LDS-DMA (1 KiB per wave-instruction), dealt to `nw` issuing waves of
+// which this one is number `w`; the caller waits (vmcnt) and meets the barrier
 template <int KS>
-__device__ __forceinline__ void k1s_chunk(const K1sArgs& a, const int chunk_index) {
-  extern __shared__ __attribute__((aligned(1024))) char k1s_lds[];
+__device__ __forceinline__ void k1s_fill(const K1sArgs& a, const K1sChunk& ck, char* base, int f0, int f1, int w, int nw) {
+  constexpr int XTB = k1s_xtile_bytes(KS);
+  const int lane = threadIdx.x & 63;
+  const char* src = reinterpret_cast<const char*>(a.xs) + (a.utt_xtile_off[ck.utt] + ck.tile0) * (int64_t)XTB;
+  for (int i = f0 * 2 * KS + w; i < f1 * 2 * KS; i += nw)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (int64_t)i * 1024 + lane * 16),
+                                     (__attribute__((address_space(3))) void*)(base + i * 1024), 16, 0, 0);
+}
+
+// KHG_OPT_K1_PROF: which CU this workgroup runs on -- (XCC_ID << 16) | HW_ID bits 8-15
+__device__ __forceinline__ long long k1s_cu_id() {
+  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);
+  return (long long)(((xcc & 15u) << 16) | (hw & 0xff00u));
+}
+// ... a wave that found the work-item counter exhausted; the last of the 8 writes the chunk's record out
+__device__ __forceinline__ void k1s_stamp_done(long long* rec, K1sProf* pf) {
+  if ((threadIdx.x & 63) == 0) {
+    const unsigned long long t = (unsigned long long)clock64();
+    atomicMin(&pf->first, t);
+    atomicMax(&pf->last, t);
+    __threadfence_block();
+    if (atomicAdd(&pf->done, 1) == 7) { rec[2] = (long long)atomicMin(&pf->first, ~0ull); rec[3] = (long long)atomicMax(&pf->last, 0ull); }
+  }
+}
+
+// one chunk (<= NMAX frame tiles of one utterance) whose B fragments stand in LDS at `lds` (tile f at lds + f XTB), by one
+// workgroup past its barrier; `ctr`: the chunk's work-item counter in LDS, zero
+template <int KS>
+__device__ __forceinline__ void k1s_body(const K1sArgs& a, const K1sChunk& ck, char* lds, int* ctr) {
   constexpr int XTB = k1s_xtile_bytes(KS), TILEB = k1s_tile_bytes(KS), TPS = k1s_tps(KS), NMF = 3 * KS;
   constexpr float LN2 = 0.69314718055994530942f;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, col = lane & 31, kb = lane >> 5;
-  const K1sChunk ck = a.chunks[chunk_index];
-  const int n = ck.ntiles;
-  if (n <= 0) return;
-  const int u = ck.utt;
-  if (a.repair_status && !(a.repair_status[u] & a.repair_bit)) return;     // repair launch: certified utterances keep their band
+  const int n = ck.ntiles, u = ck.utt;
   const bool band = a.ubound != nullptr && a.repair_status == nullptr;
   const float c1 = a.c1, inv_scale = a.inv_scale, MFLOOR = a.mfloor;
-  char* lds = k1s_lds;
-  int* ctr = reinterpret_cast<int*>(k1s_lds + k1s_nmax(KS) * XTB);     // the work-item counter, behind the feature tiles
-
-  // ---- the chunk's B fragments -> LDS (1 KiB per wave-instruction), one barrier ----
-  {
-    const char* src = reinterpret_cast<const char*>(a.xs) + (a.utt_xtile_off[u] + ck.tile0) * (int64_t)XTB;
-    for (int i = wave; i < n * 2 * KS; i += 8)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (int64_t)i * 1024 + lane * 16),
-                                       (__attribute__((address_space(3))) void*)(lds + i * 1024), 16, 0, 0);
-    if (threadIdx.x == 0) *ctr = 0;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
+  (void)wave;
   const int64_t T = a.frame_off[u + 1] - a.frame_off[u];
   const int tpad = (int)((T + 31) & ~(int64_t)31);
   float* llu = a.ll + a.ll_off[u] + 32 * ck.tile0;
@@ -462,11 +484,116 @@ __device__ __forceinline__ void k1s_chunk(const K1sArgs& a, const int chunk_inde
     Q q;
     ops(KN(), std::integral_constant<int, 0>(), std::integral_constant<int, 70>(), acc1, q);
   }
-  if (bad) atomicOr(a.err_flag, 1);
+  if (bad && !(K1S_KO & 32)) atomicOr(a.err_flag, 1);      // (no chunk fill: the values are whatever LDS held)
+}
+
+// one chunk by one workgroup, from nothing: the whole one-chunk kernel, as a function of the chunk's index
+template <int KS>
+__device__ __forceinline__ void k1s_chunk(const K1sArgs& a, const int chunk_index) {
+  extern __shared__ __attribute__((aligned(1024))) char k1s_lds[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const K1sChunk ck = a.chunks[chunk_index];
+  const int n = ck.ntiles;
+  if (n <= 0) return;
+  if (a.repair_status && !(a.repair_status[ck.utt] & a.repair_bit)) return;     // repair launch: certified utterances keep their band
+  int* ctr = reinterpret_cast<int*>(k1s_lds + k1s_nmax(KS) * k1s_xtile_bytes(KS));     // the work-item counter, behind the feature tiles
+  K1sProf* pf = reinterpret_cast<K1sProf*>(k1s_lds + k1s_nmax(KS) * k1s_xtile_bytes(KS) + 64);
+  long long* rec = a.stamps ? a.stamps + 8 * (int64_t)chunk_index : nullptr;
+  if (rec && threadIdx.x == 0) { rec[0] = clock64(); rec[4] = k1s_cu_id(); rec[5] = n; pf->first = ~0ull; pf->last = 0; pf->done = 0; }
+  // ---- the chunk's B fragments -> LDS, one barrier ----
+  if constexpr (!(K1S_KO & 32)) k1s_fill<KS>(a, ck, k1s_lds, 0, n, wave, 8);
+  if (threadIdx.x == 0) *ctr = 0;
+  if constexpr (!(K1S_KO & 32)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  if (rec && threadIdx.x == 0) rec[1] = clock64();
+  k1s_body<KS>(a, ck, k1s_lds, ctr);
+  if (rec) k1s_stamp_done(rec, pf);
 }
 
 template <int KS>
 __global__ __launch_bounds__(512, 2) void k1s_loglikes(K1sArgs a) { k1s_chunk<KS>(a, (int)blockIdx.x); }
+
+// The PERSISTENT launch (KHG_OPT_K1_LAUNCH): one workgroup per CU that can hold one takes chunks, in the launch order of the
+// one-chunk kernel, from the global counter `next_chunk` (zero at launch), and fills the NEXT chunk's frame tiles into LDS under
+// the tail of the current one.  The NMAX tile slots are used from both ends in turn: a chunk of n tiles stands at slots [0, n), the
+// next one at [NMAX - n', NMAX), the one after at [0, n'') ... -- a chunk is always contiguous (tile f at base + f XTB: the chain
+// code and the shifted-tile read of k1s_body are untouched) and the NMAX - n slots the current chunk leaves free all serve the
+// next one.  The first wave that finds the work-item counter exhausted claims the next chunk (once per workgroup, through an LDS
+// word), issues the LDS-DMA copies of those of its tiles whose slots are free, and publishes (chunk, base, the tile range [lo, hi) it
+// requested); ONE barrier ends the chunk -- all waves done, all requested bytes landed.  Tiles outside [lo, hi) sit in slots the
+// finished chunk was still reading: all waves copy them behind that barrier and meet a second one (no second barrier when
+// everything fitted).  Control words in LDS, two banks of 8 used by alternating chunks, so that the claiming wave can reset the
+// next chunk's bank while the current one is in use: [0] work-item counter, [1] claim flag, [2] the next chunk, [3] its base slot,
+// [4] lo, [5] hi.  Every (pdf, tile) cell is computed by k1s_body exactly as in the one-chunk kernel: only which wave computes it
+// when differs, scores are bit-identical.
+template <int KS>
+__global__ __launch_bounds__(512, 2) void k1s_persistent(K1sArgs a, int nchunks, int* next_chunk) {
+  extern __shared__ __attribute__((aligned(1024))) char k1s_lds[];
+  constexpr int XTB = k1s_xtile_bytes(KS), NMAX = k1s_nmax(KS);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  int* ctl = reinterpret_cast<int*>(k1s_lds + NMAX * XTB);
+  K1sProf* prof = reinterpret_cast<K1sProf*>(k1s_lds + NMAX * XTB + 64);
+  if (threadIdx.x == 0) {
+    for (int i = 0; i < 16; ++i) ctl[i] = 0;
+    ctl[8 + 2] = atomicAdd(next_chunk, 1);      // published as if by a chunk of bank 1: nothing resident, base 0
+    for (int i = 0; i < 2; ++i) { prof[i].first = ~0ull; prof[i].last = 0; prof[i].done = 0; }
+  }
+  __syncthreads();
+  int par = 1;
+  for (;;) {
+    const int c = __builtin_amdgcn_readfirstlane(ctl[8 * par + 2]);
+    if (c >= nchunks) break;
+    const int base = __builtin_amdgcn_readfirstlane(ctl[8 * par + 3]);
+    const int have_lo = __builtin_amdgcn_readfirstlane(ctl[8 * par + 4]), have_hi = __builtin_amdgcn_readfirstlane(ctl[8 * par + 5]);
+    par ^= 1;
+    K1sChunk ck = a.chunks[c];
+    ck.utt = __builtin_amdgcn_readfirstlane(ck.utt); ck.tile0 = __builtin_amdgcn_readfirstlane(ck.tile0);
+    ck.ntiles = __builtin_amdgcn_readfirstlane(ck.ntiles);
+    const int n = ck.ntiles > 0 ? ck.ntiles : 0;
+    long long* rec = a.stamps ? a.stamps + 8 * (int64_t)c : nullptr;
+    if (n > 0) {
+      char* ldsc = k1s_lds + base * XTB;
+      if (rec && threadIdx.x == 0) { rec[0] = clock64(); rec[4] = k1s_cu_id(); rec[5] = n; }
+      if (have_hi - have_lo < n) {               // the tiles whose slots the previous chunk still held (all of them: the first chunk)
+        k1s_fill<KS>(a, ck, ldsc, 0, have_lo, wave, 8);
+        k1s_fill<KS>(a, ck, ldsc, have_hi, n, wave, 8);
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+      }
+      if (rec && threadIdx.x == 0) rec[1] = clock64();
+      k1s_body<KS>(a, ck, ldsc, &ctl[8 * par]);
+      if (rec) k1s_stamp_done(rec, &prof[par]);
+    }
+    // the work-item counter is exhausted: the first wave here claims the workgroup's next chunk and requests what fits
+    int first = 0;
+    if (lane == 0) first = __hip_atomic_fetch_add(&ctl[8 * par + 1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0 ? 1 : 0;
+    if (__builtin_amdgcn_readfirstlane(first)) {
+      int nc = 0;
+      if (lane == 0) nc = atomicAdd(next_chunk, 1);
+      nc = __builtin_amdgcn_readfirstlane(nc);
+      K1sChunk nk = K1sChunk{0, 0, 0, 0};
+      if (nc < nchunks) {
+        nk = a.chunks[nc];
+        nk.utt = __builtin_amdgcn_readfirstlane(nk.utt); nk.tile0 = __builtin_amdgcn_readfirstlane(nk.tile0);
+        nk.ntiles = __builtin_amdgcn_readfirstlane(nk.ntiles);
+      }
+      const int nn = nk.ntiles > 0 ? (nk.ntiles < NMAX ? nk.ntiles : NMAX) : 0;
+      int nbase, lo, hi;
+      if (base == 0) { nbase = NMAX - nn; lo = n - nbase > 0 ? n - nbase : 0; hi = nn; }      // this chunk holds [0, n): the next one stands at the end
+      else { nbase = 0; lo = 0; hi = nn < base ? nn : base; }                                  // this chunk holds [base, NMAX): ... at the front
+      if (hi > lo) k1s_fill<KS>(a, nk, k1s_lds + nbase * XTB, lo, hi, 0, 1);
+      if (lane == 0) {
+        ctl[8 * par + 2] = nc; ctl[8 * par + 3] = nbase; ctl[8 * par + 4] = lo; ctl[8 * par + 5] = hi > lo ? hi : lo;
+        ctl[8 * (par ^ 1) + 0] = 0; ctl[8 * (par ^ 1) + 1] = 0;
+        prof[par ^ 1].first = ~0ull; prof[par ^ 1].last = 0; prof[par ^ 1].done = 0;
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
+}
 
 // The REPAIR launch of the band form (khg_align): the chunks of the few utterances whose status carries `repair_bit`, recomputed
 // without the band's upper limit.  A launch of k1s_loglikes over all chunks would do it -- every other workgroup returns at once --
@@ -475,7 +602,7 @@ __global__ __launch_bounds__(512, 2) void k1s_loglikes(K1sArgs a) { k1s_chunk<KS
 template <int KS>
 __global__ __launch_bounds__(512, 2) void k1s_repair(K1sArgs a, int nchunks) {
   extern __shared__ __attribute__((aligned(1024))) char k1s_lds[];
-  int* list = reinterpret_cast<int*>(k1s_lds + k1s_nmax(KS) * k1s_xtile_bytes(KS) + 64);     // [1 + 512]: count, chunk indices
+  int* list = reinterpret_cast<int*>(k1s_lds + k1s_nmax(KS) * k1s_xtile_bytes(KS) + K1S_CTL_BYTES);     // [1 + 512]: count, chunk indices
   for (int base = (int)blockIdx.x * 512; base < nchunks; base += (int)gridDim.x * 512) {
     if (threadIdx.x == 0) list[0] = 0;
     __syncthreads();
