@@ -570,6 +570,20 @@ int khg_acc_stats(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *
 int khg_acc_stats_post(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, const khg_posteriors *p, float scale,
                        khg_accs *a);
 
+/* Elementwise operations on whole blocks (what Kaldi's gmm-sum-accs and gmm-ismooth-stats do on files), asynchronous on the context's
+ * stream.  Two blocks of one call must belong to `ctx` and have the same layout (Gaussians, dim, transition-ids), and the factor must
+ * be finite: KHG_E_ARG otherwise, before anything is launched.  dst and src may be the same block.
+ *   add:    dst += (double)scale * src over occupancies, mean / variance rows, transition counts and the scalars -- AccumAmDiagGmm::Add
+ *           (csrc/mle-am-diag-gmm.cc:119-128) plus the transition sum of gmm-sum-accs;
+ *   scale:  dst *= (double)f (AccumAmDiagGmm::Scale, :130-138);
+ *   smooth_with_accum: AccumDiagGmm::SmoothWithAccum (csrc/mle-diag-gmm.cc:209-226) for every Gaussian: where src.occ != 0, dst.occ +=
+ *           tau and the mean / variance rows += src row * tau / src.occ; other Gaussians are untouched.  `m` gives the layout the blocks
+ *           must have.  untouched_out (may be NULL) receives the number of Gaussians with src.occ == 0; asking for it synchronises. */
+int khg_accs_add(khg_ctx *ctx, khg_accs *dst, float scale, const khg_accs *src);
+int khg_accs_scale(khg_ctx *ctx, khg_accs *dst, float f);
+int khg_accs_smooth_with_accum(khg_ctx *ctx, khg_accs *dst, float tau, const khg_accs *src, const khg_model *m,
+                               int32_t *untouched_out);
+
 /* ---- C1: cross-GPU sum of the accumulator block (one process per GPU) -------------------- */
 /* AccumAmDiagGmm::Add across jobs (csrc/mle-am-diag-gmm.cc:119-128; what Kaldi's gmm-sum-accs does on
  * files): ONE in-place ncclAllReduce(sum, fp64) of the whole block [occ | mean_acc | var_acc | trans_acc |
@@ -642,6 +656,46 @@ int khg_mle_am_diag_gmm_update(const khg_mle_options *o, int32_t num_pdfs, int32
 int khg_diag_gmm_merge(int32_t *num_gauss, int32_t dim, int32_t target_components, float *weights, float *gconsts,
                        float *means_invvars, float *inv_vars, int32_t *history_out, int32_t *num_history_out);
 
+/* ---- Extended Baum-Welch update (MMI-style discriminative training) -------- */
+/* Kaldi's gmm-est-gmm-ebw / gmm-est-weights-ebw on a numerator and a denominator block of statistics.  The reference has no EBW
+ * update: the rule in DESIGN.md 7i is the specification (tests/ebw_ref.py restates it).  Per Gaussian, with occ = occ_n - occ_d,
+ * x = x_n - x_d, x2 = x2_n - x2_d and the fp64 normal form (mu, var) of the float parameters: D = (tau + E occ_d) / 2 (or
+ * -1.0001 occ + 1e-10 when D + occ <= 0); mu' = (x + D mu) / (occ + D), var' = (x2 + D (var + mu^2)) / (occ + D) - mu'^2; D grows by
+ * 1.1 until every var' > 0, is then doubled, and the values at the doubled D are written back through the float conversion of the
+ * ML update.  A Gaussian with occ_n == occ_d == 0 is skipped; one still failing after 100 tries is left as it was.  Per pdf (flag w)
+ * 50 rounds of w <- n + (k_max - d / w_orig) w, floored and renormalised, unless sum n < min_num_count_weight_update.  gconsts are
+ * recomputed; no Gaussian is removed.  All arithmetic is IEEE fp64 in one fixed order: host and device forms give bit-identical
+ * weights, inv_vars and means_invvars; gconsts go through logf (a few ulps) and the two diagnostics through log and a sum. */
+typedef struct {
+  double E;   /* 2.0: D starts at E occ_den / 2 */
+  double tau; /* 0.0: added to E occ_den before halving (I-smoothing belongs on the numerator block: khg_accs_smooth_with_accum) */
+} khg_ebw_options;
+typedef struct {
+  double min_num_count_weight_update; /* 10.0: pdfs whose numerator count is below keep their weights */
+  double min_gaussian_weight;         /* 1e-5: floor inside every round */
+  double tau;                         /* 0.0: n[g] = occ_n[g] + tau w_orig[g] */
+} khg_ebw_weight_options;
+typedef struct {
+  double auxf_impr_gauss;   /* sum over the updated Gaussians of Q(new) - Q(old) on the smoothed statistics */
+  double count;             /* sum of the numerator occupancies */
+  double auxf_impr_weights; /* sum over the updated pdfs of sum_g n log(w' / w) - d (w' - w) / w */
+  int32_t floored;          /* Gaussians that needed a larger D than the first */
+  int32_t failed;           /* Gaussians left unchanged after 100 tries */
+  int32_t skipped;          /* Gaussians without numerator and denominator counts */
+  int32_t weights_skipped;  /* pdfs below min_num_count_weight_update */
+} khg_ebw_results;
+void khg_ebw_options_default(khg_ebw_options *o);
+void khg_ebw_weight_options_default(khg_ebw_weight_options *o);
+/* The host form over flat arrays laid out like the model (gauss_off); the two accumulator triples are (occ[sumG], mean_acc[sumG][dim],
+ * var_acc[sumG][dim]).  flags: m = 1, v = 2, w = 4 of GmmUpdateFlags (t is ignored; v without m is allowed).  In/out: weights,
+ * means_invvars, inv_vars; out: gconsts, *res (may be NULL).  The four mean / variance accumulators may be NULL when flags has neither
+ * m nor v (a weights-only update reads the occupancies alone).  KHG_E_ARG for an option that is not finite. */
+int khg_ebw_am_diag_gmm_update(const khg_ebw_options *o, const khg_ebw_weight_options *wo, int32_t num_pdfs, int32_t dim,
+                               const int32_t *gauss_off, const double *num_occ, const double *num_mean_acc,
+                               const double *num_var_acc, const double *den_occ, const double *den_mean_acc,
+                               const double *den_var_acc, uint16_t flags, float *weights, float *gconsts,
+                               float *means_invvars, float *inv_vars, khg_ebw_results *res);
+
 /* ---- K4: the same M-step on the device ---------------------------------- */
 /* MleAmDiagGmmUpdate (csrc/mle-am-diag-gmm.cc:153-202; per pdf MleDiagGmmUpdate,
  * csrc/mle-diag-gmm.cc:243-390, DiagGmmNormal csrc/diag-gmm-normal.cc:14-48, ComputeGconsts
@@ -678,6 +732,14 @@ int khg_model_mle_rows_upload(khg_ctx *ctx, khg_model *m, int32_t first_pdf, int
                               const float *gconsts_h, const float *means_invvars_h, const float *inv_vars_h, const void *results_h);
 int khg_model_mle_update_finish(khg_ctx *ctx, khg_model *m, float *objf_change, float *count, int32_t *floored_elems,
                                 int32_t *floored_gauss, int32_t *removed);
+/* The Extended Baum-Welch update above on the device: one workgroup per pdf reads the numerator and denominator blocks where K3 left
+ * them and rewrites the handle IN PLACE (row-major parameters, gconsts, then the K1 tile image and per-parameter-version data, as
+ * khg_model_mle_update does); gauss_off does not change.  Both blocks must belong to `ctx` and be laid out for the handle
+ * (KHG_E_ARG before anything is launched otherwise, as for an option that is not finite or dim > 256).  weights, inv_vars and
+ * means_invvars are bit-identical to khg_ebw_am_diag_gmm_update and so are the counters; gconsts within a few float ulps, the two
+ * diagnostics to the rounding of log and of a reordered fp64 sum.  Synchronous (the results come back). */
+int khg_model_ebw_update(khg_ctx *ctx, khg_model *m, const khg_accs *num, const khg_accs *den, const khg_ebw_options *o,
+                         const khg_ebw_weight_options *wo, uint16_t flags, khg_ebw_results *res);
 /* Mixing up on the handle: AmDiagGmm::SplitByCount's per-pdf DiagGmm::Split (csrc/am-diag-gmm.cc:72-90, csrc/diag-gmm.cc:780-851)
  * to targets_h[p] >= current components (the caller computes them with GetSplitTargets, csrc/model-common.cc:29-70, from
  * the per-pdf occupancies -- khg_accs_download_range(0, sumG)).  The reference draws the perturbations from the process-global

@@ -28,10 +28,13 @@ from .mle import (AccumAmDiagGmm, AccumDiagGmm, GmmUpdateFlags, MapDiagGmmOption
                   get_split_targets, gmm_flags_to_str, map_am_diag_gmm_update, map_diag_gmm_update, ml_objective, mle_am_diag_gmm_update,
                   mle_am_diag_gmm_update_device, mle_diag_gmm_update,
                   str_to_gmm_flags)
+from .mle import (EbwOptions, EbwWeightOptions, ebw_am_diag_gmm_update_device, update_ebw_am_diag_gmm, update_ebw_diag_gmm,  # noqa: F401
+                  update_ebw_weights_am_diag_gmm, update_ebw_weights_diag_gmm)
 from .resident import ResidentEm  # noqa: F401
 from .posterior import ali_to_post, arrays_to_posts, posts_to_arrays  # noqa: F401
 from .scripts import (gmm_acc_stats, gmm_acc_stats_ali, gmm_acc_stats_ali_batch, gmm_acc_stats_batch, gmm_align_compiled,  # noqa: F401
-                      gmm_align_compiled_batch, gmm_boost_silence, gmm_est, gmm_info, gmm_init_mono)
+                      gmm_align_compiled_batch, gmm_boost_silence, gmm_est, gmm_est_gmm_ebw, gmm_est_weights_ebw, gmm_info, gmm_init_mono,
+                      gmm_ismooth_stats, gmm_sum_accs)
 from .training_graph import (TrainingGraphCompiler, TrainingGraphCompilerOptions, equal_align, generate_hmm_topo,  # noqa: F401
                              make_lexicon_fst_with_silence)
 from .transition_model import (MleTransitionUpdateConfig, TransitionInformation, TransitionModel, TransitionModelTuple,  # noqa: F401

@@ -97,6 +97,19 @@ class MleOptionsC(C.Structure):
     ]
 
 
+class EbwOptionsC(C.Structure):
+    _fields_ = [("E", C.c_double), ("tau", C.c_double)]
+
+
+class EbwWeightOptionsC(C.Structure):
+    _fields_ = [("min_num_count_weight_update", C.c_double), ("min_gaussian_weight", C.c_double), ("tau", C.c_double)]
+
+
+class EbwResultsC(C.Structure):
+    _fields_ = [("auxf_impr_gauss", C.c_double), ("count", C.c_double), ("auxf_impr_weights", C.c_double), ("floored", C.c_int32),
+                ("failed", C.c_int32), ("skipped", C.c_int32), ("weights_skipped", C.c_int32)]
+
+
 # every symbol include/khg_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "khg_last_error": (C.c_char_p, []),
@@ -186,6 +199,9 @@ SIGNATURES = {
     "khg_accs_upload": (C.c_int, [vp, vp, c_f64p]),
     "khg_acc_stats": (C.c_int, [vp, vp, vp, vp, C.c_float, vp]),
     "khg_acc_stats_post": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, vp]),
+    "khg_accs_add": (C.c_int, [vp, vp, C.c_float, vp]),
+    "khg_accs_scale": (C.c_int, [vp, vp, C.c_float]),
+    "khg_accs_smooth_with_accum": (C.c_int, [vp, vp, C.c_float, vp, vp, c_i32p]),
     "khg_accs_allreduce": (C.c_int, [vp, vp, vp]),
     "khg_accs_allreduce_range": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, vp]),
     "khg_acc_stats_reduce": (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, C.c_int32]),
@@ -200,6 +216,15 @@ SIGNATURES = {
         [C.POINTER(MleOptionsC), C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p, c_f64p, C.c_uint16, C.c_uint16, c_f32p,
          c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p],
     ),
+    "khg_ebw_options_default": (None, [C.POINTER(EbwOptionsC)]),
+    "khg_ebw_weight_options_default": (None, [C.POINTER(EbwWeightOptionsC)]),
+    "khg_ebw_am_diag_gmm_update": (
+        C.c_int,
+        [C.POINTER(EbwOptionsC), C.POINTER(EbwWeightOptionsC), C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p,
+         c_f64p, C.c_uint16, c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(EbwResultsC)],
+    ),
+    "khg_model_ebw_update": (C.c_int, [vp, vp, vp, vp, C.POINTER(EbwOptionsC), C.POINTER(EbwWeightOptionsC), C.c_uint16,
+                                      C.POINTER(EbwResultsC)]),
     "khg_careful_graph": (C.c_int, [C.c_int32, C.c_int32, c_i64p, c_i32p, c_i32p, c_f32p, c_i32p, c_f32p, c_i32p, c_i32p, c_i64p, c_i32p,
                                     c_i32p, c_f32p, c_i32p, c_f32p]),
     "khg_diag_gmm_merge": (C.c_int, [c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p]),

@@ -1,6 +1,6 @@
 // kaldi_hmm_gmm_amd/csrc/khg_host.cpp -- host-side (no GPU) entry points of include/khg_hip.h:
-// gconsts, the M-step and the transition-model update.  The reference keeps these on the host
-// too (O(P*G*D) once per EM iteration); they run on the all-reduced accumulators.
+// gconsts, the M-step, the Extended Baum-Welch update and the transition-model update.  The
+// reference keeps these on the host too (O(P*G*D) once per EM iteration); they run on the all-reduced accumulators.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -229,6 +229,164 @@ extern "C" int khg_mle_am_diag_gmm_update(const khg_mle_options* o, int32_t P, i
   if (floored_elems) *floored_elems = tfe;
   if (floored_gauss) *floored_gauss = tfg;
   if (removed) *removed = trm;
+  return KHG_OK;
+}
+
+// ---- Extended Baum-Welch: the reference has no EBW update, the rule written there is the specification ----------
+// Every operation below is one IEEE fp64 operation in the written order (no contraction): tests/ebw_ref.py restates it in numpy
+// scalars and khg_k4_ebw.hip.inc on the device, and the three agree bit for bit on the parameters.
+namespace {
+
+struct EbwGaussOut { int status = 0 /* 0 updated, 1 skipped, 2 failed */, iters = 0; double impr = 0.0; };
+
+// try(D) of the rule: the candidate mean / variance rows at smoothing constant Dv -> every variance positive (or v is off)
+inline bool EbwTry(double Dv, uint16_t flags, int D, double occ, const double* x, const double* x2, const double* mu, const double* var,
+                   double* nmu, double* nvar) {
+  const double c = occ + Dv;
+  bool ok = true;
+  for (int d = 0; d < D; ++d) {
+    const double m_new = (flags & kMeans) ? (x[d] + Dv * mu[d]) / c : mu[d];
+    double v_new = var[d];
+    if (flags & kVars) {
+      if (flags & kMeans) v_new = (x2[d] + Dv * (var[d] + mu[d] * mu[d])) / c - m_new * m_new;
+      else v_new = (x2[d] - 2.0 * mu[d] * x[d] + occ * mu[d] * mu[d] + Dv * var[d]) / c;
+      if (!(v_new > 0.0)) ok = false;
+    }
+    nmu[d] = m_new; nvar[d] = v_new;
+  }
+  return ok;
+}
+
+void EbwGaussOne(const khg_ebw_options& o, uint16_t flags, int D, double occ_n, const double* xn, const double* x2n, double occ_d, const double* xd,
+                 const double* x2d, float* miv, float* iv, std::vector<double>& wk, EbwGaussOut* out) {
+  if (occ_n == 0.0 && occ_d == 0.0) { out->status = 1; return; }
+  wk.resize((size_t)6 * D);
+  double *x = wk.data(), *x2 = x + D, *mu = x2 + D, *var = mu + D, *nmu = var + D, *nvar = nmu + D;
+  const double occ = occ_n - occ_d;
+  for (int d = 0; d < D; ++d) {
+    x[d] = xn[d] - xd[d];
+    x2[d] = x2n[d] - x2d[d];
+    var[d] = 1.0 / static_cast<double>(iv[d]);            // DiagGmmNormal::CopyFromDiagGmm (csrc/diag-gmm-normal.cc:14-20)
+    mu[d] = static_cast<double>(miv[d]) * var[d];
+  }
+  double Dv = (o.tau + o.E * occ_d) / 2.0;
+  if (Dv + occ <= 0.0) Dv = -1.0001 * occ + 1e-10;
+  int it = 0;
+  for (; it < 100; ++it) {
+    if (EbwTry(Dv, flags, D, occ, x, x2, mu, var, nmu, nvar)) {
+      Dv = 2.0 * Dv;
+      EbwTry(Dv, flags, D, occ, x, x2, mu, var, nmu, nvar);
+      break;
+    }
+    Dv = 1.1 * Dv;
+  }
+  if (it == 100) { out->status = 2; return; }
+  out->iters = it;
+  // the diagnostic first (it needs the old float rows' normal form, which mu / var hold): Q(new) - Q(old) on the smoothed statistics
+  const double c = occ + Dv;
+  double diff = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const double X = x[d] + Dv * mu[d], X2 = x2[d] + Dv * (var[d] + mu[d] * mu[d]);
+    const double t_new = c * std::log(nvar[d]) + (X2 - 2.0 * nmu[d] * X + c * nmu[d] * nmu[d]) / nvar[d];
+    const double t_old = c * std::log(var[d]) + (X2 - 2.0 * mu[d] * X + c * mu[d] * mu[d]) / var[d];
+    diff = diff + (t_old - t_new);
+  }
+  out->impr = 0.5 * diff;
+  // DiagGmmNormal::CopyToDiagGmm for the flagged parts (csrc/diag-gmm-normal.cc:22-48)
+  for (int d = 0; d < D; ++d) {
+    if (flags & kVars) {
+      iv[d] = static_cast<float>(1.0 / nvar[d]);
+      if (!(flags & kMeans)) miv[d] = static_cast<float>(mu[d]) * iv[d];
+    }
+    if (flags & kMeans) miv[d] = static_cast<float>(nmu[d]) * iv[d];
+  }
+}
+
+// the weights of one pdf -> false when the pdf is below min_num_count_weight_update (weights untouched)
+bool EbwWeightsOne(const khg_ebw_weight_options& o, int G, const double* occ_n, const double* occ_d, float* w, std::vector<double>& wk, double* impr) {
+  wk.resize((size_t)5 * G);
+  double *w0 = wk.data(), *n = w0 + G, *dd = n + G, *ratio = dd + G, *cur = ratio + G;
+  double tot = 0.0;
+  for (int g = 0; g < G; ++g) {
+    w0[g] = static_cast<double>(w[g]);
+    n[g] = occ_n[g] + o.tau * w0[g];
+    dd[g] = occ_d[g];
+    tot = tot + n[g];
+  }
+  if (tot < o.min_num_count_weight_update) return false;
+  for (int g = 0; g < G; ++g) ratio[g] = dd[g] / w0[g];
+  double k_max = ratio[0];
+  for (int g = 1; g < G; ++g) if (ratio[g] > k_max) k_max = ratio[g];
+  for (int g = 0; g < G; ++g) cur[g] = w0[g];
+  for (int round = 0; round < 50; ++round) {
+    for (int g = 0; g < G; ++g) {
+      cur[g] = n[g] + (k_max - ratio[g]) * cur[g];
+      if (cur[g] < o.min_gaussian_weight) cur[g] = o.min_gaussian_weight;
+    }
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s = s + cur[g];
+    for (int g = 0; g < G; ++g) cur[g] = cur[g] / s;
+  }
+  double a = 0.0;
+  for (int g = 0; g < G; ++g) {
+    a = a + (n[g] * std::log(cur[g] / w0[g]) - dd[g] * (cur[g] - w0[g]) / w0[g]);
+    w[g] = static_cast<float>(cur[g]);
+  }
+  *impr = a;
+  return true;
+}
+
+bool EbwFinite(const khg_ebw_options* o, const khg_ebw_weight_options* wo) {
+  return std::isfinite(o->E) && std::isfinite(o->tau) && std::isfinite(wo->min_num_count_weight_update) &&
+         std::isfinite(wo->min_gaussian_weight) && std::isfinite(wo->tau);
+}
+
+}  // namespace
+
+extern "C" void khg_ebw_options_default(khg_ebw_options* o) { o->E = 2.0; o->tau = 0.0; }
+extern "C" void khg_ebw_weight_options_default(khg_ebw_weight_options* o) {
+  o->min_num_count_weight_update = 10.0; o->min_gaussian_weight = 1.0e-05; o->tau = 0.0;
+}
+
+extern "C" int khg_ebw_am_diag_gmm_update(const khg_ebw_options* o, const khg_ebw_weight_options* wo, int32_t P, int32_t D,
+                                          const int32_t* gauss_off, const double* num_occ, const double* num_mean, const double* num_var,
+                                          const double* den_occ, const double* den_mean, const double* den_var, uint16_t flags,
+                                          float* weights, float* gconsts, float* means_invvars, float* inv_vars, khg_ebw_results* res) {
+  if (!o || !wo || P <= 0 || D <= 0 || !gauss_off || !num_occ || !den_occ || !weights || !gconsts || !means_invvars || !inv_vars)
+    return khg_set_error(KHG_E_ARG, "khg_ebw_am_diag_gmm_update: bad arguments");
+  if (!EbwFinite(o, wo)) return khg_set_error(KHG_E_ARG, "khg_ebw_am_diag_gmm_update: an option is not finite");
+  flags &= (kMeans | kVars | kWeights);         // t is ignored
+  if ((flags & (kMeans | kVars)) && (!num_mean || !num_var || !den_mean || !den_var))      // (a weights-only update reads the occupancies alone)
+    return khg_set_error(KHG_E_ARG, "khg_ebw_am_diag_gmm_update: mean / variance accumulators missing");
+  khg_ebw_results r{};
+  std::vector<double> wk;
+  for (int p = 0; p < P; ++p) {
+    const int g0 = gauss_off[p], G = gauss_off[p + 1] - g0;
+    double impr_p = 0.0, count_p = 0.0;
+    for (int g = 0; g < G; ++g) count_p = count_p + num_occ[g0 + g];
+    if (flags & (kMeans | kVars)) {
+      for (int g = g0; g < g0 + G; ++g) {
+        EbwGaussOut go;
+        const size_t row = (size_t)g * D;
+        EbwGaussOne(*o, flags, D, num_occ[g], num_mean + row, num_var + row, den_occ[g], den_mean + row, den_var + row, means_invvars + row,
+                    inv_vars + row, wk, &go);
+        if (go.status == 1) ++r.skipped;
+        else if (go.status == 2) ++r.failed;
+        else { impr_p = impr_p + go.impr; if (go.iters > 0) ++r.floored; }
+      }
+    }
+    r.auxf_impr_gauss = r.auxf_impr_gauss + impr_p;
+    r.count = r.count + count_p;
+    if (flags & kWeights) {
+      double iw = 0.0;
+      if (G > 0 && EbwWeightsOne(*wo, G, num_occ + g0, den_occ + g0, weights + g0, wk, &iw)) r.auxf_impr_weights = r.auxf_impr_weights + iw;
+      else ++r.weights_skipped;
+    }
+    int nb = 0;
+    if (!ComputeGconstsOne(G, D, weights + g0, inv_vars + (size_t)g0 * D, means_invvars + (size_t)g0 * D, gconsts + g0, &nb))
+      return khg_set_error(KHG_E_RUNTIME, "pdf " + std::to_string(p) + ": not a number in gconst computation");
+  }
+  if (res) *res = r;
   return KHG_OK;
 }
 

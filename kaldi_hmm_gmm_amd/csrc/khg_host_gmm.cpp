@@ -730,6 +730,86 @@ float MlObjective(const DiagGmm& gmm, const AccumDiagGmm& acc) {
   return obj;
 }
 
+// ---- Extended Baum-Welch ----------------------------------------------------------------------------------------------
+std::string EbwOptions::ToString() const {
+  char buf[96];
+  std::snprintf(buf, sizeof(buf), "EbwOptions(E=%g, tau=%g)", E, tau);
+  return buf;
+}
+std::string EbwWeightOptions::ToString() const {
+  char buf[160];
+  std::snprintf(buf, sizeof(buf), "EbwWeightOptions(min_num_count_weight_update=%g, min_gaussian_weight=%g, tau=%g)", min_num_count_weight_update,
+                min_gaussian_weight, tau);
+  return buf;
+}
+khg_ebw_results EbwFlatUpdate(const EbwOptions& opts, const EbwWeightOptions& wopts, int P, int D, const int32_t* go, const double* num_occ,
+                              const double* num_mean, const double* num_var, const double* den_occ, const double* den_mean, const double* den_var,
+                              int flags, std::vector<float>* w, std::vector<float>* gc, std::vector<float>* miv, std::vector<float>* iv) {
+  const khg_ebw_options o = opts.C();
+  const khg_ebw_weight_options wo = wopts.C();
+  gc->assign(w->size(), 0.0f);
+  khg_ebw_results r{};
+  CApi(khg_ebw_am_diag_gmm_update(&o, &wo, P, D, go, num_occ, num_mean, num_var, den_occ, den_mean, den_var, (uint16_t)flags, w->data(), gc->data(),
+                                  miv->data(), iv->data(), &r));
+  return r;
+}
+namespace {
+const double* RowsOrNull(const std::vector<double>& v) { return v.empty() ? nullptr : v.data(); }
+khg_ebw_results EbwOnePdf(const AccumDiagGmm& num, const AccumDiagGmm& den, int flags, const EbwOptions& o, const EbwWeightOptions& wo, DiagGmm* gmm) {
+  KHG_REQUIRE(gmm != nullptr, "gmm != NULL assertion failed");
+  KHG_REQUIRE(num.NumGauss() == gmm->NumGauss() && den.NumGauss() == gmm->NumGauss() && num.Dim() == gmm->Dim() && den.Dim() == gmm->Dim(),
+              "num_stats.NumGauss() == gmm->NumGauss() && den_stats.NumGauss() == gmm->NumGauss() assertion failed");
+  if (flags & 3)
+    KHG_REQUIRE((num.Flags() & 3) == 3 && (den.Flags() & 3) == 3, "Flags in argument do not match the active accumulators");
+  const int32_t go[2] = {0, gmm->NumGauss()};
+  std::vector<float> w = gmm->weights(), miv = gmm->means_invvars(), iv = gmm->inv_vars(), gc;
+  const khg_ebw_results r = EbwFlatUpdate(o, wo, 1, gmm->Dim(), go, num.occupancy().data(), RowsOrNull(num.mean_accumulator()),
+                                          RowsOrNull(num.variance_accumulator()), den.occupancy().data(), RowsOrNull(den.mean_accumulator()),
+                                          RowsOrNull(den.variance_accumulator()), flags, &w, &gc, &miv, &iv);
+  gmm->SetRaw(gmm->NumGauss(), gmm->Dim(), w.data(), iv.data(), miv.data(), gc.data());
+  return r;
+}
+khg_ebw_results EbwAm(const AccumAmDiagGmm& num, const AccumAmDiagGmm& den, int flags, const EbwOptions& o, const EbwWeightOptions& wo, AmDiagGmm* am) {
+  num.Flush(); den.Flush();
+  KHG_REQUIRE(am != nullptr && num.NumAccs() == am->NumPdfs() && den.NumAccs() == am->NumPdfs() && num.NumAccs() > 0,
+              "num_stats.NumAccs() == den_stats.NumAccs() == am_gmm->NumPdfs() assertion failed");
+  KHG_REQUIRE(num.Dim() == am->Dim() && den.Dim() == am->Dim(), "accumulator / model dimension mismatch");
+  const int D = am->Dim();
+  std::vector<int32_t> go;
+  std::vector<float> w, miv, iv, gc;
+  am->Flat(&go, nullptr, &w, &miv, &iv);
+  std::vector<double> occ[2], ma[2], va[2];
+  const AccumAmDiagGmm* accs[2] = {&num, &den};
+  for (int k = 0; k < 2; ++k)
+    for (int i = 0; i < am->NumPdfs(); ++i) {
+      const AccumDiagGmm& a = *accs[k]->Acc(i);
+      KHG_REQUIRE(a.NumGauss() == go[(size_t)i + 1] - go[(size_t)i], "diag_gmm_acc.NumGauss() == gmm->NumGauss() assertion failed");
+      if (flags & 3) KHG_REQUIRE((a.Flags() & 3) == 3, "Flags in argument do not match the active accumulators");
+      occ[k].insert(occ[k].end(), a.occupancy().begin(), a.occupancy().end());
+      if (flags & 3) {
+        ma[k].insert(ma[k].end(), a.mean_accumulator().begin(), a.mean_accumulator().end());
+        va[k].insert(va[k].end(), a.variance_accumulator().begin(), a.variance_accumulator().end());
+      }
+    }
+  const khg_ebw_results r = EbwFlatUpdate(o, wo, am->NumPdfs(), D, go.data(), occ[0].data(), RowsOrNull(ma[0]), RowsOrNull(va[0]), occ[1].data(),
+                                          RowsOrNull(ma[1]), RowsOrNull(va[1]), flags, &w, &gc, &miv, &iv);
+  am->SetFlat(go.data(), w.data(), gc.data(), miv.data(), iv.data());
+  return r;
+}
+}  // namespace
+khg_ebw_results UpdateEbwDiagGmm(const AccumDiagGmm& num, const AccumDiagGmm& den, int flags, const EbwOptions& opts, DiagGmm* gmm) {
+  return EbwOnePdf(num, den, flags & 3, opts, EbwWeightOptions(), gmm);
+}
+khg_ebw_results UpdateEbwWeightsDiagGmm(const AccumDiagGmm& num, const AccumDiagGmm& den, const EbwWeightOptions& opts, DiagGmm* gmm) {
+  return EbwOnePdf(num, den, kGmmWeights, EbwOptions(), opts, gmm);
+}
+khg_ebw_results UpdateEbwAmDiagGmm(const AccumAmDiagGmm& num, const AccumAmDiagGmm& den, int flags, const EbwOptions& opts, AmDiagGmm* am) {
+  return EbwAm(num, den, flags & 3, opts, EbwWeightOptions(), am);
+}
+khg_ebw_results UpdateEbwWeightsAmDiagGmm(const AccumAmDiagGmm& num, const AccumAmDiagGmm& den, const EbwWeightOptions& opts, AmDiagGmm* am) {
+  return EbwAm(num, den, kGmmWeights, EbwOptions(), opts, am);
+}
+
 std::string MapDiagGmmOptions::ToString() const {
   char buf[160];
   std::snprintf(buf, sizeof(buf), "MapDiagGmmOptions(mean_tau=%g, variance_tau=%g, weight_tau=%g)", (double)mean_tau, (double)variance_tau, (double)weight_tau);

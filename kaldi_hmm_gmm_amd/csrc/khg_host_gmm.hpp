@@ -261,6 +261,30 @@ float MlObjective(const DiagGmm& gmm, const AccumDiagGmm& acc);   // :479-499
 // fp64 like the reference (a speaker-adaptation-sized update: not on the EM hot path)
 std::pair<float, float> MapDiagGmmUpdate(const MapDiagGmmOptions& cfg, const AccumDiagGmm& acc, int flags, DiagGmm* gmm);
 
+// ---- Extended Baum-Welch (Kaldi's gmm-est-gmm-ebw / gmm-est-weights-ebw; DESIGN.md 7i: the rule there is the specification) --------
+struct EbwOptions {
+  double E = 2.0, tau = 0.0;
+  khg_ebw_options C() const { khg_ebw_options o; o.E = E; o.tau = tau; return o; }
+  std::string ToString() const;
+};
+struct EbwWeightOptions {
+  double min_num_count_weight_update = 10.0, min_gaussian_weight = 1.0e-05, tau = 0.0;
+  khg_ebw_weight_options C() const {
+    khg_ebw_weight_options o;
+    o.min_num_count_weight_update = min_num_count_weight_update; o.min_gaussian_weight = min_gaussian_weight; o.tau = tau;
+    return o;
+  }
+  std::string ToString() const;
+};
+// the flat form every EBW update goes through (khg_ebw_am_diag_gmm_update): w / miv / iv in-out, gc out; the mean / variance
+// accumulators may be NULL when flags has neither m nor v
+khg_ebw_results EbwFlatUpdate(const EbwOptions& opts, const EbwWeightOptions& wopts, int P, int D, const int32_t* gauss_off, const double* num_occ,
+                              const double* num_mean, const double* num_var, const double* den_occ, const double* den_mean, const double* den_var,
+                              int flags, std::vector<float>* w, std::vector<float>* gc, std::vector<float>* miv, std::vector<float>* iv);
+// per pdf: means / variances (flags & (m | v)) and weights
+khg_ebw_results UpdateEbwDiagGmm(const AccumDiagGmm& num_stats, const AccumDiagGmm& den_stats, int flags, const EbwOptions& opts, DiagGmm* gmm);
+khg_ebw_results UpdateEbwWeightsDiagGmm(const AccumDiagGmm& num_stats, const AccumDiagGmm& den_stats, const EbwWeightOptions& opts, DiagGmm* gmm);
+
 // ---- csrc/mle-am-diag-gmm.h:18-97 --------------------------------------------------------------------------------------
 class TransitionModel;
 class AccumAmDiagGmm {
@@ -337,5 +361,10 @@ class AccumAmDiagGmm {
 MleUpdateResult MleAmDiagGmmUpdate(const MleDiagGmmOptions& cfg, const AccumAmDiagGmm& acc, int flags, AmDiagGmm* am_gmm);
 // csrc/mle-am-diag-gmm.cc:204-227: MapDiagGmmUpdate pdf by pdf, the float sums of its two outputs
 std::pair<float, float> MapAmDiagGmmUpdate(const MapDiagGmmOptions& cfg, const AccumAmDiagGmm& acc, int flags, AmDiagGmm* am_gmm);
+
+// the same over every pdf of the model (the totals are added in pdf order)
+khg_ebw_results UpdateEbwAmDiagGmm(const AccumAmDiagGmm& num_stats, const AccumAmDiagGmm& den_stats, int flags, const EbwOptions& opts, AmDiagGmm* am_gmm);
+khg_ebw_results UpdateEbwWeightsAmDiagGmm(const AccumAmDiagGmm& num_stats, const AccumAmDiagGmm& den_stats, const EbwWeightOptions& opts,
+                                          AmDiagGmm* am_gmm);
 
 }  // namespace khg

@@ -7,6 +7,7 @@
 
 #include "khg_k3_accstats.hip.inc"
 #include "khg_k3_post.hip.inc"
+#include "khg_k3_accops.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // accumulators + K3
@@ -40,6 +41,62 @@ extern "C" int khg_accs_upload(khg_ctx* ctx, khg_accs* a, const double* buf) {
   if (ctx_dead(ctx) || !a || !buf) return khg_set_error(KHG_E_ARG, "bad arguments");
   HIPCHK(hipMemcpyAsync(a->buf_d, buf, sizeof(double) * (size_t)a->n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
+
+// gmm-sum-accs / gmm-ismooth-stats on blocks resident in HBM (khg_k3_accops.hip.inc); asynchronous on the context's stream
+static int accs_pair_check(const khg_ctx* ctx, const khg_accs* dst, const khg_accs* src, const char* where) {
+  if (dst->ctx != ctx || src->ctx != ctx) return khg_set_error(KHG_E_ARG, std::string(where) + ": an accumulator block belongs to another context");
+  if (dst->sumG != src->sumG || dst->D != src->D || dst->num_tids != src->num_tids || dst->n != src->n)
+    return khg_set_error(KHG_E_ARG, std::string(where) + ": the two blocks have different layouts");
+  return KHG_OK;
+}
+static inline int accs_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256)); }
+extern "C" int khg_accs_add(khg_ctx* ctx, khg_accs* dst, float scale, const khg_accs* src) {
+  if (ctx_dead(ctx) || !dst || !src) return khg_set_error(KHG_E_ARG, "khg_accs_add: bad arguments");
+  if (!std::isfinite(scale)) return khg_set_error(KHG_E_ARG, "khg_accs_add: the scale is not finite");
+  { int rc = accs_pair_check(ctx, dst, src, "khg_accs_add"); if (rc) return rc; }
+  KernelTimer kt(ctx, "k3_accs_add");
+  KHG_LAUNCH(ctx, k3_accs_add, dim3(accs_grid(dst->n)), dim3(256), 0, ctx->stream, dst->buf_d, src->buf_d, (double)scale, dst->n);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+extern "C" int khg_accs_scale(khg_ctx* ctx, khg_accs* dst, float f) {
+  if (ctx_dead(ctx) || !dst) return khg_set_error(KHG_E_ARG, "khg_accs_scale: bad arguments");
+  if (!std::isfinite(f)) return khg_set_error(KHG_E_ARG, "khg_accs_scale: the scale is not finite");
+  if (dst->ctx != ctx) return khg_set_error(KHG_E_ARG, "khg_accs_scale: the accumulator block belongs to another context");
+  KernelTimer kt(ctx, "k3_accs_scale");
+  KHG_LAUNCH(ctx, k3_accs_scale, dim3(accs_grid(dst->n)), dim3(256), 0, ctx->stream, dst->buf_d, (double)f, dst->n);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+extern "C" int khg_accs_smooth_with_accum(khg_ctx* ctx, khg_accs* dst, float tau, const khg_accs* src, const khg_model* m, int32_t* untouched_out) {
+  if (ctx_dead(ctx) || !dst || !src || !m) return khg_set_error(KHG_E_ARG, "khg_accs_smooth_with_accum: bad arguments");
+  if (!std::isfinite(tau)) return khg_set_error(KHG_E_ARG, "khg_accs_smooth_with_accum: tau is not finite");
+  { int rc = accs_pair_check(ctx, dst, src, "khg_accs_smooth_with_accum"); if (rc) return rc; }
+  if (dst->sumG != m->sumG || dst->D != m->D) return khg_set_error(KHG_E_ARG, "khg_accs_smooth_with_accum: accumulator / model layouts differ");
+  int32_t* cnt_d = nullptr;
+  if (untouched_out) {
+    int rc = dev_alloc(&cnt_d, 1);
+    if (rc) return rc;
+    hipError_t e = hipMemsetAsync(cnt_d, 0, sizeof(int32_t), ctx->stream);
+    if (e != hipSuccess) { DEVFREE(cnt_d); return khg_set_error(KHG_E_HIP, hipGetErrorString(e)); }
+  }
+  hipError_t e = hipSuccess;
+  if (dst->sumG > 0) {
+    KernelTimer kt(ctx, "k3_accs_smooth");
+    KHG_LAUNCH(ctx, k3_accs_smooth, dim3((unsigned)((dst->sumG + 3) / 4)), dim3(256), 0, ctx->stream, dst->occ(), dst->mean(), dst->var(), src->occ(),
+               src->mean(), src->var(), (double)tau, dst->sumG, (int)dst->D, cnt_d);
+    e = hipGetLastError();
+  }
+  if (untouched_out) {
+    int32_t cnt = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&cnt, cnt_d, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    DEVFREE(cnt_d);
+    if (e == hipSuccess) *untouched_out = cnt;
+  }
+  if (e != hipSuccess) return khg_set_error(KHG_E_HIP, hipGetErrorString(e));
   return KHG_OK;
 }
 

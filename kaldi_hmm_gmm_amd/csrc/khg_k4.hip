@@ -4,6 +4,7 @@
 #include "khg_rccl.hpp"
 
 #include "khg_k4_mstep.hip.inc"
+#include "khg_k4_ebw.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // K4: device M-step
@@ -242,6 +243,63 @@ extern "C" int khg_model_mle_update_sharded(khg_ctx* ctx, khg_model* m, khg_accs
     if (r || r2) return rccl_fail("ncclBroadcast (sharded M-step)", r ? r : r2);
   }
   return mle_update_finish(ctx, m, objf_change, count, floored_elems, floored_gauss, removed);
+}
+
+// ------------------------------------------------------------------------------------------
+// K4, discriminative form: the Extended Baum-Welch update on the handle
+static bool accs_fit_model(const khg_accs* a, const khg_model* m) { return a->D == m->D && a->sumG == m->sumG; }
+extern "C" int khg_model_ebw_update(khg_ctx* ctx, khg_model* m, const khg_accs* num, const khg_accs* den, const khg_ebw_options* o,
+                                    const khg_ebw_weight_options* wo, uint16_t flags, khg_ebw_results* out) {
+  if (ctx_dead(ctx) || !m || !num || !den || !o || !wo) return khg_set_error(KHG_E_ARG, "khg_model_ebw_update: bad arguments");
+  if (num->ctx != ctx || den->ctx != ctx) return khg_set_error(KHG_E_ARG, "khg_model_ebw_update: an accumulator block belongs to another context");
+  if (!accs_fit_model(num, m) || !accs_fit_model(den, m) || num->num_tids != den->num_tids)
+    return khg_set_error(KHG_E_ARG, "khg_model_ebw_update: accumulator / model layouts differ");
+  if (!std::isfinite(o->E) || !std::isfinite(o->tau) || !std::isfinite(wo->min_num_count_weight_update) || !std::isfinite(wo->min_gaussian_weight) ||
+      !std::isfinite(wo->tau))
+    return khg_set_error(KHG_E_ARG, "khg_model_ebw_update: an option is not finite");
+  if (!m->has_weights) return khg_set_error(KHG_E_ARG, "khg_model_ebw_update: the model has no weights (khg_model_set_weights)");
+  const int P = m->P, D = m->D;
+  if (D > 256) return khg_set_error(KHG_E_ARG, "khg_model_ebw_update: dim > 256");
+  int maxG = 0;
+  for (int p = 0; p < P; ++p) maxG = std::max(maxG, m->gauss_off[p + 1] - m->gauss_off[p]);
+  const size_t lds = sizeof(double) * (3 * (size_t)maxG + 8) + sizeof(int) * 16;
+  if (lds > 60 * 1024) return khg_set_error(KHG_E_UNSUPPORTED, "khg_model_ebw_update: more than ~2500 Gaussians in one pdf");
+  { int rc = check_err_flag(ctx, "khg_acc_stats"); if (rc) return rc; }
+  K4EbwRes* res_d = nullptr;
+  int rc = dev_alloc(&res_d, (size_t)P);
+  if (rc) return rc;
+  K4EbwArgs a;
+  a.gauss_off = m->gauss_off_d; a.D = D;
+  a.occ_n = num->occ(); a.mean_n = num->mean(); a.var_n = num->var();
+  a.occ_d = den->occ(); a.mean_d = den->mean(); a.var_d = den->var();
+  a.w = m->weights_d; a.gc = m->gconsts_d; a.miv = m->miv_d; a.iv = m->iv_d;
+  a.res = res_d;
+  a.E = o->E; a.tau = o->tau;
+  a.w_min_count = wo->min_num_count_weight_update; a.w_min_weight = wo->min_gaussian_weight; a.w_tau = wo->tau;
+  a.flags = flags & 0x7u;        // t is ignored
+  {
+    KernelTimer kt(ctx, "k4_ebw_update");
+    if (D <= 64) KHG_LAUNCH(ctx, k4_ebw_update<1>, dim3(P), dim3(256), lds, ctx->stream, a);
+    else if (D <= 128) KHG_LAUNCH(ctx, k4_ebw_update<2>, dim3(P), dim3(256), lds, ctx->stream, a);
+    else KHG_LAUNCH(ctx, k4_ebw_update<4>, dim3(P), dim3(256), lds, ctx->stream, a);
+  }
+  std::vector<K4EbwRes> res((size_t)P);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(res.data(), res_d, sizeof(K4EbwRes) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  DEVFREE(res_d);
+  if (e != hipSuccess) return khg_set_error(KHG_E_HIP, hipGetErrorString(e));
+  khg_ebw_results r{};
+  for (int p = 0; p < P; ++p) {       // totals in pdf order, as the host form adds them
+    const K4EbwRes& q = res[(size_t)p];
+    if (q.bad) return khg_set_error(KHG_E_RUNTIME, "pdf " + std::to_string(p) + ": not a number in gconst computation");
+    r.auxf_impr_gauss = r.auxf_impr_gauss + q.impr_gauss; r.count = r.count + q.count; r.auxf_impr_weights = r.auxf_impr_weights + q.impr_w;
+    r.floored += q.floored; r.failed += q.failed; r.skipped += q.skipped; r.weights_skipped += q.w_skipped;
+  }
+  rc = model_pack(ctx, m);   // new K1 tile image + per-parameter-version data, as khg_model_mle_update ends
+  if (rc) return rc;
+  if (out) *out = r;
+  return KHG_OK;
 }
 
 extern "C" int khg_model_split(khg_ctx* ctx, khg_model* m, const int32_t* targets, float perturb, const float* randn, int64_t n_randn) {

@@ -9,6 +9,7 @@
 #include "khg_host_align.hpp"
 #include "khg_host_gmm.hpp"
 #include "khg_host_hmm.hpp"
+#include "khg_py_ebw.hpp"
 
 namespace py = pybind11;
 using namespace khg;
@@ -480,6 +481,55 @@ void BindGmm(py::module_& m) {
           throw Error("add_device_stats: the statistics do not match the accumulators' layout");
         a.AddDeviceStats(go.data(), occ.data(), ma.data(), va.data(), (int)ma.shape(1), st["total_frames"].cast<double>(), st["total_log_like"].cast<double>());
       }, py::arg("st"), py::arg("gauss_off"));
+
+  // ---- Extended Baum-Welch -- options, the flat form, per-pdf and whole-model updates -> dict of khg_ebw_results
+  py::class_<EbwOptions>(m, "EbwOptions")
+      .def(py::init([](double E, double tau) { EbwOptions o; o.E = E; o.tau = tau; return o; }), py::arg("E") = 2.0, py::arg("tau") = 0.0)
+      .def_readwrite("E", &EbwOptions::E).def_readwrite("tau", &EbwOptions::tau)
+      .def("__str__", &EbwOptions::ToString);
+  py::class_<EbwWeightOptions>(m, "EbwWeightOptions")
+      .def(py::init([](double mc, double mw, double tau) {
+             EbwWeightOptions o; o.min_num_count_weight_update = mc; o.min_gaussian_weight = mw; o.tau = tau; return o;
+           }), py::arg("min_num_count_weight_update") = 10.0, py::arg("min_gaussian_weight") = 1.0e-05, py::arg("tau") = 0.0)
+      .def_readwrite("min_num_count_weight_update", &EbwWeightOptions::min_num_count_weight_update)
+      .def_readwrite("min_gaussian_weight", &EbwWeightOptions::min_gaussian_weight)
+      .def_readwrite("tau", &EbwWeightOptions::tau)
+      .def("__str__", &EbwWeightOptions::ToString);
+  static auto EbwO = [](py::object o) { return o.is_none() ? EbwOptions() : o.cast<EbwOptions>(); };
+  static auto EbwW = [](py::object o) { return o.is_none() ? EbwWeightOptions() : o.cast<EbwWeightOptions>(); };
+  // khg_ebw_am_diag_gmm_update over flat arrays -> (w, gc, miv, iv, results)
+  m.def("flat_ebw_update", [](py::object opts, py::object wopts, Arr<int32_t> go, Arr<double> n_occ, Arr<double> n_mean, Arr<double> n_var, Arr<double> d_occ,
+                              Arr<double> d_mean, Arr<double> d_var, int flags, Arr<float> w, Arr<float> miv, Arr<float> iv) {
+    const int P = (int)go.size() - 1;
+    if (P < 1 || miv.ndim() != 2) throw Error("flat_ebw_update: bad arguments");
+    const int D = (int)miv.shape(1);
+    const py::ssize_t G = go.at(P);
+    if (w.size() != G || miv.shape(0) != G || iv.size() != miv.size() || n_occ.size() != G || d_occ.size() != G || n_mean.size() != G * D ||
+        n_var.size() != G * D || d_mean.size() != G * D || d_var.size() != G * D)
+      throw Error("flat_ebw_update: array sizes do not match gauss_off");
+    std::vector<float> wv = FVec(w), mv = FVec(miv), ivv = FVec(iv), gc;
+    const EbwOptions o = EbwO(opts);
+    const EbwWeightOptions wo = EbwW(wopts);
+    const khg_ebw_results r = NoGil([&] {
+      return EbwFlatUpdate(o, wo, P, D, go.data(), n_occ.data(), n_mean.data(), n_var.data(), d_occ.data(), d_mean.data(), d_var.data(), flags, &wv, &gc,
+                           &mv, &ivv);
+    });
+    return py::make_tuple(Vec1(wv), Vec1(gc), Vec2(mv, (size_t)G, (size_t)D), Vec2(ivv, (size_t)G, (size_t)D), EbwResultsDict(r));
+  });
+  m.def("update_ebw_diag_gmm", [](const AccumDiagGmm& num, const AccumDiagGmm& den, int flags, py::object opts, DiagGmm& gmm) {
+    return EbwResultsDict(UpdateEbwDiagGmm(num, den, flags, EbwO(opts), &gmm));
+  }, py::arg("num_stats"), py::arg("den_stats"), py::arg("flags"), py::arg("opts"), py::arg("gmm"));
+  m.def("update_ebw_weights_diag_gmm", [](const AccumDiagGmm& num, const AccumDiagGmm& den, py::object opts, DiagGmm& gmm) {
+    return EbwResultsDict(UpdateEbwWeightsDiagGmm(num, den, EbwW(opts), &gmm));
+  }, py::arg("num_stats"), py::arg("den_stats"), py::arg("opts"), py::arg("gmm"));
+  m.def("update_ebw_am_diag_gmm", [](const AccumAmDiagGmm& num, const AccumAmDiagGmm& den, int flags, py::object opts, AmDiagGmm& am) {
+    const EbwOptions o = EbwO(opts);
+    return EbwResultsDict(NoGil([&] { return UpdateEbwAmDiagGmm(num, den, flags, o, &am); }));
+  }, py::arg("num_stats"), py::arg("den_stats"), py::arg("flags"), py::arg("opts"), py::arg("am_gmm"));
+  m.def("update_ebw_weights_am_diag_gmm", [](const AccumAmDiagGmm& num, const AccumAmDiagGmm& den, py::object opts, AmDiagGmm& am) {
+    const EbwWeightOptions o = EbwW(opts);
+    return EbwResultsDict(NoGil([&] { return UpdateEbwWeightsAmDiagGmm(num, den, o, &am); }));
+  }, py::arg("num_stats"), py::arg("den_stats"), py::arg("opts"), py::arg("am_gmm"));
 
   m.def("map_am_diag_gmm_update", [](const MapDiagGmmOptions& cfg, const AccumAmDiagGmm& acc, int flags, AmDiagGmm& am) { return MapAmDiagGmmUpdate(cfg, acc, flags, &am); },
         py::arg("config"), py::arg("amdiag_gmm_acc"), py::arg("flags"), py::arg("am_gmm"));

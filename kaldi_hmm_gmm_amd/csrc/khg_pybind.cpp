@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/khg_hip.h"
+#include "khg_py_ebw.hpp"
 #include "khg_py_lattices.hpp"
 
 namespace py = pybind11;
@@ -168,6 +169,7 @@ struct KModel {
   py::dict mle_rows_download(int first_pdf, int n_pdf);
   void mle_rows_upload(py::dict d);
   py::dict mle_update_finish();
+  py::dict ebw_update(KAccs& num_accs, KAccs& den_accs, py::object opts, py::object weight_opts, int flags);
   void invalidate() { Check(khg_model_invalidate(h)); }
   void scale_weights(Arr<int32_t> pdfs, float scale) { Check(khg_model_scale_weights(ctx->h, h, (int32_t)pdfs.shape(0), pdfs.data(), scale)); }
   void split(Arr<int32_t> targets, float perturb, py::object randn) {
@@ -292,6 +294,14 @@ struct KAccs {
     if (b.size() != size) throw py::value_error("upload: wrong block size");
     Check(NoGil([&] { return khg_accs_upload(ctx->h, h, b.data()); }));
   }
+  // gmm-sum-accs / gmm-ismooth-stats on the resident block (khg_accs_add / _scale / _smooth_with_accum)
+  void add(float scale, KAccs& src) { Check(khg_accs_add(ctx->h, h, scale, src.h)); }
+  void scale(float f) { Check(khg_accs_scale(ctx->h, h, f)); }
+  py::object smooth_with_accum(float tau, KAccs& src, KModel& m, bool count) {
+    int32_t n = 0;
+    Check(NoGil([&] { return khg_accs_smooth_with_accum(ctx->h, h, tau, src.h, m.h, count ? &n : nullptr); }));
+    return count ? py::object(py::int_(n)) : py::object(py::none());
+  }
 };
 
 static void ParseMleOptions(py::object opts, int dim, khg_mle_options& o, Arr<double>& vfv) {
@@ -328,6 +338,22 @@ py::dict KModel::mle_update(KAccs& accs, py::object opts, int flags) {
   int32_t fe = 0, fg = 0, rm = 0;
   Check(NoGil([&] { return khg_model_mle_update(ctx->h, h, accs.h, &o, (uint16_t)(flags & 0xFFFF), &oc, &cnt, &fe, &fg, &rm); }));
   return mle_result(oc, cnt, fe, fg, rm);
+}
+// the Extended Baum-Welch update (khg_model_ebw_update): opts / weight_opts are EbwOptions / EbwWeightOptions (or None: the defaults)
+py::dict KModel::ebw_update(KAccs& num_accs, KAccs& den_accs, py::object opts, py::object weight_opts, int flags) {
+  khg_ebw_options o;
+  khg_ebw_weight_options wo;
+  khg_ebw_options_default(&o);
+  khg_ebw_weight_options_default(&wo);
+  if (!opts.is_none()) { o.E = opts.attr("E").cast<double>(); o.tau = opts.attr("tau").cast<double>(); }
+  if (!weight_opts.is_none()) {
+    wo.min_num_count_weight_update = weight_opts.attr("min_num_count_weight_update").cast<double>();
+    wo.min_gaussian_weight = weight_opts.attr("min_gaussian_weight").cast<double>();
+    wo.tau = weight_opts.attr("tau").cast<double>();
+  }
+  khg_ebw_results r;
+  Check(NoGil([&] { return khg_model_ebw_update(ctx->h, h, num_accs.h, den_accs.h, &o, &wo, (uint16_t)(flags & 0xFFFF), &r); }));
+  return EbwResultsDict(r);
 }
 // the sharded M-step (khg_model_mle_update_sharded) and its pieces
 py::dict KModel::mle_update_sharded(KAccs& accs, py::object opts, int flags, py::object comm) {
@@ -756,6 +782,8 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("mle_update_range", &KModel::mle_update_range, py::arg("accs"), py::arg("opts"), py::arg("flags"), py::arg("first_pdf"), py::arg("n_pdf"))
       .def("mle_rows_download", &KModel::mle_rows_download).def("mle_rows_upload", &KModel::mle_rows_upload)
       .def("mle_update_finish", &KModel::mle_update_finish)
+      .def("ebw_update", &KModel::ebw_update, py::arg("num_accs"), py::arg("den_accs"), py::arg("opts") = py::none(),
+           py::arg("weight_opts") = py::none(), py::arg("flags") = 0x7)
       .def("scale_weights", &KModel::scale_weights)
       .def("invalidate", &KModel::invalidate)
       .def("split", &KModel::split, py::arg("targets"), py::arg("perturb_factor"), py::arg("randn"))
@@ -780,6 +808,8 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("split", &KAccs::split).def("relayout", &KAccs::relayout).def("download_range", &KAccs::download_range)
       .def("download_occ", [](KAccs& a) { return a.download_range(0, a.sumG); })
       .def("download_trans", &KAccs::download_trans).def("download", &KAccs::download).def("upload", &KAccs::upload)
+      .def("add", &KAccs::add, py::arg("scale"), py::arg("src")).def("scale", &KAccs::scale, py::arg("f"))
+      .def("smooth_with_accum", &KAccs::smooth_with_accum, py::arg("tau"), py::arg("src"), py::arg("model"), py::arg("count") = true)
       .def("close", &KAccs::close);
 
   py::class_<KUtts>(m, "UtteranceSet")

@@ -17,6 +17,8 @@ AccumAmDiagGmm = _ext.AccumAmDiagGmm
 AccumDiagGmm = _ext.AccumDiagGmm
 MleDiagGmmOptions = _ext.MleDiagGmmOptions
 MapDiagGmmOptions = _ext.MapDiagGmmOptions
+EbwOptions = _ext.EbwOptions                # Extended Baum-Welch (Kaldi's gmm-est-gmm-ebw): E = 2.0, tau = 0.0
+EbwWeightOptions = _ext.EbwWeightOptions    # ... and gmm-est-weights-ebw: min_num_count_weight_update = 10, min_gaussian_weight = 1e-5, tau = 0
 ml_objective = _ext.ml_objective
 
 
@@ -91,3 +93,43 @@ def mle_am_diag_gmm_update_device(config, device_accs, flags, device_model, am_g
             raise KhgError("am_gmm->NumPdfs() does not match the device model")
         am_gmm.set_flat(d["gauss_off"], d["weights"], d["gconsts"], d["means_invvars"], d["inv_vars"])
     return r["objf_change"], r["count"]
+
+
+def _flat_ebw_update(opts, weight_opts, gauss_off, num, den, flags, w, miv, iv):
+    """khg_ebw_am_diag_gmm_update over flat arrays; num / den = (occ, mean_acc, var_acc) -> (w, gc, miv, iv, results dict)."""
+    a = [np.ascontiguousarray(x, np.float64) for x in (*num, *den)]
+    return _ext.flat_ebw_update(opts, weight_opts, np.asarray(gauss_off, np.int32), *a, int(flags) & 0x7, w, miv, iv)
+
+
+def update_ebw_diag_gmm(num_stats, den_stats, flags, opts, gmm):
+    """Kaldi's UpdateEbwDiagGmm for one pdf (means / variances by `flags`) -> dict(auxf_impr_gauss, count, floored, failed,
+    skipped, ...); gmm is updated in place."""
+    return _ext.update_ebw_diag_gmm(num_stats, den_stats, int(flags), opts, gmm)
+
+
+def update_ebw_weights_diag_gmm(num_stats, den_stats, opts, gmm):
+    """Kaldi's UpdateEbwWeightsDiagGmm for one pdf -> dict(auxf_impr_weights, count, weights_skipped, ...)."""
+    return _ext.update_ebw_weights_diag_gmm(num_stats, den_stats, opts, gmm)
+
+
+def update_ebw_am_diag_gmm(num_stats, den_stats, flags, opts, am_gmm):
+    """Kaldi's UpdateEbwAmDiagGmm (gmm-est-gmm-ebw): every pdf's means / variances from a numerator and a denominator AccumAmDiagGmm."""
+    return _ext.update_ebw_am_diag_gmm(num_stats, den_stats, int(flags), opts, am_gmm)
+
+
+def update_ebw_weights_am_diag_gmm(num_stats, den_stats, opts, am_gmm):
+    """Kaldi's UpdateEbwWeightsAmDiagGmm (gmm-est-weights-ebw)."""
+    return _ext.update_ebw_weights_am_diag_gmm(num_stats, den_stats, opts, am_gmm)
+
+
+def ebw_am_diag_gmm_update_device(opts, weight_opts, num_accs, den_accs, flags, device_model, am_gmm: AmDiagGmm = None):
+    """The Extended Baum-Welch update run on the GPU from the two DeviceAccs blocks where K3 left the numerator and denominator
+    statistics (khg_model_ebw_update): `device_model` is updated in place and is ready for the next loglikes / align / decode pass; no
+    accumulator leaves the device.  am_gmm (optional) receives the new parameters.  -> the results dict of DeviceModel.ebw_update."""
+    r = device_model.ebw_update(num_accs, den_accs, opts, weight_opts, int(flags) & 0x7)
+    if am_gmm is not None:
+        d = device_model.download()
+        if am_gmm.num_pdfs != device_model.num_pdfs:
+            raise KhgError("am_gmm->NumPdfs() does not match the device model")
+        am_gmm.set_flat(d["gauss_off"], d["weights"], d["gconsts"], d["means_invvars"], d["inv_vars"])
+    return r

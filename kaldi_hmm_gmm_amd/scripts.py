@@ -14,7 +14,8 @@ from .diag_gmm import AmDiagGmm, DiagGmm
 from .fst import StdVectorFst
 from .hmm_topology import HmmTopology
 from .posterior import posts_to_arrays
-from .mle import (AccumAmDiagGmm, GmmUpdateFlags, MleDiagGmmOptions, mle_am_diag_gmm_update, str_to_gmm_flags)
+from .mle import (AccumAmDiagGmm, EbwOptions, EbwWeightOptions, GmmUpdateFlags, MleDiagGmmOptions, mle_am_diag_gmm_update, str_to_gmm_flags,
+                  update_ebw_am_diag_gmm, update_ebw_weights_am_diag_gmm)
 from .transition_model import MleTransitionUpdateConfig, TransitionModel
 
 
@@ -190,3 +191,55 @@ def gmm_boost_silence(am_gmm: AmDiagGmm, transition_model: TransitionModel, sile
     if verbose:
         print("Boosted weights for", len(pdfs), "pdfs, by factor of", boost)
     return dgm
+
+
+def gmm_sum_accs(gmm_accs: Sequence[AccumAmDiagGmm], transition_accs: Optional[Sequence[np.ndarray]] = None):
+    """Kaldi's gmm-sum-accs: the sum of several accumulators (AccumAmDiagGmm::Add with scale 1, csrc/mle-am-diag-gmm.cc:119-128) and
+    of their transition statistics -> (gmm_accs[0], summed transition_accs or None); gmm_accs[0] is updated in place.  Blocks that
+    live on the device are summed there with DeviceAccs.add."""
+    if len(gmm_accs) == 0:
+        raise KhgError("gmm_sum_accs: no accumulators")
+    total = gmm_accs[0]
+    for a in gmm_accs[1:]:
+        total.add(1.0, a)
+    tacc = None
+    if transition_accs is not None and len(transition_accs) > 0:
+        tacc = np.array(transition_accs[0], np.float64)
+        for t in transition_accs[1:]:
+            tacc = tacc + np.asarray(t, np.float64)
+    return total, tacc
+
+
+def gmm_ismooth_stats(gmm_accs: AccumAmDiagGmm, tau: float, src_accs: Optional[AccumAmDiagGmm] = None) -> AccumAmDiagGmm:
+    """Kaldi's gmm-ismooth-stats: I-smoothing of `gmm_accs` (in place) with tau counts per Gaussian of the statistics in src_accs
+    (AccumDiagGmm::SmoothWithAccum, csrc/mle-diag-gmm.cc:209-226); src_accs = None smooths the block with itself (--smooth-from-model
+    is not offered).  On the device: DeviceAccs.smooth_with_accum."""
+    src = gmm_accs if src_accs is None else src_accs
+    if src.num_accs != gmm_accs.num_accs:
+        raise KhgError("gmm_ismooth_stats: the two accumulators have different numbers of pdfs")
+    for i in range(gmm_accs.num_accs):
+        gmm_accs._accs[i].smooth_with_accum(tau, src.get_acc(i))
+    return gmm_accs
+
+
+def gmm_est_gmm_ebw(am_gmm: AmDiagGmm, num_accs: AccumAmDiagGmm, den_accs: AccumAmDiagGmm, ebw_opts: Optional[EbwOptions] = None,
+                    update_flags: str = "mv", verbose: bool = True) -> Dict[str, float]:
+    """Kaldi's gmm-est-gmm-ebw: the Extended Baum-Welch update of the means / variances from a numerator and a
+    denominator accumulator; am_gmm is updated in place.  Returns the printed statistics as a dict as well."""
+    flags = int(str_to_gmm_flags(update_flags)) & 0x3
+    r = update_ebw_am_diag_gmm(num_accs, den_accs, flags, ebw_opts if ebw_opts is not None else EbwOptions(), am_gmm)
+    if verbose:
+        print("GMM update: Overall", r["auxf_impr_gauss"] / r["count"] if r["count"] else float("nan"),
+              "auxiliary-function improvement per frame over", r["count"], "frames;", r["floored"], "Gaussians floored,", r["failed"], "failed,",
+              r["skipped"], "skipped")
+    return r
+
+
+def gmm_est_weights_ebw(am_gmm: AmDiagGmm, num_accs: AccumAmDiagGmm, den_accs: AccumAmDiagGmm,
+                        weight_opts: Optional[EbwWeightOptions] = None, verbose: bool = True) -> Dict[str, float]:
+    """Kaldi's gmm-est-weights-ebw: the Extended Baum-Welch update of the mixture weights; am_gmm is updated in place."""
+    r = update_ebw_weights_am_diag_gmm(num_accs, den_accs, weight_opts if weight_opts is not None else EbwWeightOptions(), am_gmm)
+    if verbose:
+        print("Weight update: Overall", r["auxf_impr_weights"] / r["count"] if r["count"] else float("nan"),
+              "auxiliary-function improvement per frame over", r["count"], "frames;", r["weights_skipped"], "pdfs skipped")
+    return r
