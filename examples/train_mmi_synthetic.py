@@ -17,7 +17,16 @@ likelihood of utterance u's lattice, both at acoustic scale kappa (the lattices 
 the posteriors are taken at scales (1, 1)) -- and the update's floored / failed counts; at the end the WER on the held-out utterances
 before and after.
 
-Usage: python examples/train_mmi_synthetic.py [--utts 200] [--mmi-utts 60] [--mmi-iters 4] [--tau 50] [--E 2.0]
+--rescore: Kaldi's train_mmi.sh does not decode in every iteration.  The denominator lattices are decoded ONCE, before the first
+iteration, with the ML model; every iteration then rescores them with the current model (gmm-rescore-lattice:
+DeviceLattices.rescore at scale 1, only the (frame, pdf) cells the lattices name are evaluated; the decoding set needs no score
+buffer) and takes the posteriors at scales (1, kappa).  The objective F then sums over a FIXED lattice: logZ_u is the total
+likelihood of the paths the first decode kept, under the current model, not of a fresh decode.
+--boost B: boosted MMI.  The lattices' graph costs are boosted once, right after the decode (lattice-boost-ali:
+DeviceLattices.boost, b = B, the numerator alignment of the ML model as the reference, silence errors free); boosting changes graph
+costs only, so it commutes with the rescoring.  logZ_u is then the boosted lattice's.
+
+Usage: python examples/train_mmi_synthetic.py [--utts 200] [--mmi-utts 60] [--mmi-iters 4] [--tau 50] [--E 2.0] [--rescore] [--boost B]
 """
 import argparse
 import os
@@ -39,8 +48,10 @@ class MmiState:
     """Everything one MMI run keeps on the device: the model, the utterances on their numerator graphs (us_ali) and on the shared
     decoding graph (us_dec), the two accumulator blocks."""
 
-    def __init__(self, ctx, tm, am, graph, utts, kappa=0.1, tau=50.0, E=2.0):
+    def __init__(self, ctx, tm, am, graph, utts, kappa=0.1, tau=50.0, E=2.0, rescore=False, boost=0.0):
         self.ctx, self.kappa, self.tau = ctx, float(kappa), float(tau)
+        self.rescore, self.boost, self.lats0 = bool(rescore), float(boost), None
+        self.tid2phone = np.asarray(tm.transition_id_to_phone_array(), np.int32)
         self.opts, self.weight_opts = khg.EbwOptions(E=E), khg.EbwWeightOptions()
         self.refs = [u[1] for u in utts]
         feats = [np.ascontiguousarray(u[2], np.float32) for u in utts]
@@ -71,9 +82,17 @@ class MmiState:
         self.us_ali.loglikes(self.dm, reachable_only=True)
         a = self.us_ali.align(self.dt_ali, beam=10.0, retry_beam=40.0, acoustic_scale=self.kappa)
         self.us_ali.acc_stats(self.dm, self.dt_ali, self.num)
-        self.us_dec.loglikes(self.dm)
-        lats = self.us_dec.raw_lattices_faster_device(self.dt_dec, **self.dec)["lattices"]
-        post = lats.posteriors(1.0, 1.0)
+        if self.rescore:
+            if self.lats0 is None:
+                self.lats0 = self.decode_once()
+            lats = self.lats0.rescore(self.us_dec, self.dm, self.dt_dec, 1.0)       # unscaled costs: the scale goes into the posteriors
+            post = lats.posteriors(1.0, self.kappa)
+        else:
+            self.us_dec.loglikes(self.dm)
+            lats = self.us_dec.raw_lattices_faster_device(self.dt_dec, **self.dec)["lattices"]
+            if self.boost:
+                lats = self.boosted(lats)
+            post = lats.posteriors(1.0, 1.0)
         self.us_dec.acc_stats_post(self.dm, self.dt_dec, post, self.den)
         ok_n = (np.asarray(a["status"]) & khg.ALIGN_ERROR) == 0
         ok_d = (np.asarray(post.status) & 1) != 0
@@ -85,6 +104,18 @@ class MmiState:
         post.close()
         lats.close()
         return info
+
+    def boosted(self, lats):
+        """lattice-boost-ali with the numerator alignment this set holds as the reference; the input handle is closed"""
+        out = lats.boost(self.tid2phone, np.asarray([dx.tr.SIL], np.int32), ali_set=self.us_ali, b=self.boost, max_silence_error=0.0)
+        lats.close()
+        return out
+
+    def decode_once(self):
+        """--rescore: the denominator lattices of the whole run, decoded with the current (ML) model, boosted if asked"""
+        self.us_dec.loglikes(self.dm)
+        lats = self.us_dec.raw_lattices_faster_device(self.dt_dec, **self.dec)["lattices"]
+        return self.boosted(lats) if self.boost else lats
 
     def update(self):
         return self.dm.ebw_update(self.num, self.den, self.opts, self.weight_opts, 0x7)
@@ -105,8 +136,9 @@ class MmiState:
         return errs, nref
 
     def close(self):
-        for h in (self.num, self.den, self.us_ali, self.us_dec, self.dg, self.dm, self.dt_ali, self.dt_dec):
-            h.close()
+        for h in (self.lats0, self.num, self.den, self.us_ali, self.us_dec, self.dg, self.dm, self.dt_ali, self.dt_dec):
+            if h is not None:
+                h.close()
 
 
 def main():
@@ -121,13 +153,16 @@ def main():
     ap.add_argument("--tau", type=float, default=50.0, help="I-smoothing count per Gaussian")
     ap.add_argument("--E", type=float, default=2.0)
     ap.add_argument("--kappa", type=float, default=0.1, help="acoustic scale")
+    ap.add_argument("--rescore", action="store_true", help="decode the denominator lattices once, rescore them in every iteration")
+    ap.add_argument("--boost", type=float, default=0.0, help="boosted MMI: b of lattice-boost-ali (0: off)")
     args = ap.parse_args()
     tm, tree, am, lexicon, test_utts = dx.train(args)
     train_utts = dx.tr.make_data(args.utts + args.test_utts, args.dim, np.random.default_rng(args.seed))[: args.mmi_utts]    # the same draw as train()
     comp = TrainingGraphCompiler(tm, tree, lexicon, sil_phone=dx.tr.SIL, sil_prob=0.5,
                                  opts=TrainingGraphCompilerOptions(transition_scale=1.0, self_loop_scale=1.0))
     graph = comp.compile_word_loop_graph()
-    st = MmiState(khg._gpu.default_context(), tm, am, graph, train_utts, kappa=args.kappa, tau=args.tau, E=args.E)
+    st = MmiState(khg._gpu.default_context(), tm, am, graph, train_utts, kappa=args.kappa, tau=args.tau, E=args.E, rescore=args.rescore,
+                  boost=args.boost)
     e0, n0 = st.wer(test_utts)
     print(f"ML model: WER {100.0 * e0 / max(n0, 1):.2f}% ({e0} / {n0}) on {len(test_utts)} held-out utterances")
     failed = 0

@@ -533,6 +533,55 @@ int khg_posteriors_validate(int32_t n_utt, const int64_t *frame_off_h, const int
 int khg_posteriors_upload(khg_ctx *ctx, int32_t n_utt, const int64_t *frame_off_h, const int64_t *entry_begin_h,
                           const int32_t *tid_h, const double *weight_h, khg_posteriors **out);
 
+/* ---- K2X: rescoring and boosting resident lattices (gmm-rescore-lattice, lattice-boost-ali) ------------------------ */
+/* Both operations return a NEW handle, as khg_lattices_prune does: the input is untouched, the result is an ordinary khg_lattices
+ * with the input's chunks.  If the input has its in-arc index (khg_lattices_posteriors made it) and no utterance was emptied, the
+ * index is copied: the structure is the same. */
+#define KHG_LAT_NO_REF 512       /* the utterance has nothing to be compared with: khg_lattices_boost -- no alignment (length 0, a
+                                    failed utterance), an alignment whose length is not the lattice's frame count or that holds an id
+                                    outside 1 .. num_tids; khg_lattices_rescore FROM_LL -- an arc names a pdf that is not on the
+                                    utterance's pdf list.  Its lattice in the result is EMPTY */
+#define KHG_RESCORE_CELLS 0      /* scores computed from the set's features and the model, for the distinct (frame, pdf) cells the
+                                    lattices name and nothing else: no resident ll buffer, no graph needed (a features-only set works) */
+#define KHG_RESCORE_FROM_LL 1    /* scores gathered from the set's resident ll buffer (khg_loglikes, _reachable, _upload; not _band) */
+typedef struct { int64_t arcs, emitting_arcs, cells; } khg_rescore_stats;   /* arcs of the input; those with ilabel != 0; the distinct
+                                    (feature row, pdf) cells among them.  The last two are counted by the CELLS pipeline (FROM_LL: 0) */
+/* gmm-rescore-lattice.  Every arc with ilabel != 0 of a non-empty lattice of utterance u, leaving a state of frame t:
+ *   acoustic_cost := -(acoustic_scale * ll(u, t, id2pdf[ilabel]))        one float multiply and a sign
+ * Epsilon arcs keep their acoustic_cost; ilabel, olabel, graph_cost, nextstate, every per-state array and start are copied as stored
+ * (tot_cost / extra_cost are the decoder's diagnostics under the OLD scores: stale, and no operation reads them).  acoustic_scale = 1
+ * gives Kaldi's unscaled costs; the caller then takes khg_lattices_posteriors(1, kappa).
+ * KHG_RESCORE_CELLS: ll is the fp32 log-sum-exp over the pdf's Gaussians of the chain s = gconst; then, for d in steps of two,
+ * s = fmaf(M[d], x[d], s); s = fmaf(M[d+1], x[d+1], s); s = fmaf(-V[d]/2, fl(x[d]^2), s); s = fmaf(-V[d+1]/2, fl(x[d+1]^2), s) --
+ * the strict-fp32 K1's (KHG_K1_FP32_PDF) per-Gaussian value bit for bit -- reduced in a fixed order that depends on the pdf's number of
+ * Gaussians only: a cell's value depends on (feature row, pdf, model) and on nothing else (not on the batch, not on the lattice).
+ * |error| <= 1e-5 + 1e-6 B against fp64, as every K1 form.  Arcs that share a cell get the same bits.  A NaN / Inf value:
+ * KHG_E_RUNTIME.  An ilabel outside 1 .. num_tids: KHG_E_RUNTIME (pdf-id out of range).
+ * KHG_RESCORE_FROM_LL: ll is read from the resident buffer, ll[j * tpad + t] with j found by binary search in the utterance's sorted
+ * pdf list; an utterance with an arc whose pdf is not listed gets KHG_LAT_NO_REF and an empty lattice.
+ * KHG_E_ARG before anything is launched (naming the utterance where there is one): a handle of another context; n_utt differing
+ * between set and lattices; a non-empty lattice whose frame count (khg_lattices_ali_layout) is not the set's for that utterance;
+ * model / set dimension mismatch; a transition table that names pdfs the model lacks; non-finite acoustic_scale; unknown mode;
+ * FROM_LL without resident scores, or with khg_loglikes_band's.
+ * stats (may be NULL): host counts, on the synchronisation the call has anyway (cells: CELLS mode only, else 0).  Synchronous. */
+int khg_lattices_rescore(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, const khg_lattices *l,
+                         float acoustic_scale, int mode, khg_rescore_stats *stats, khg_lattices **out);
+/* Per-utterance KHG_LAT_* bits of the khg_lattices_rescore / khg_lattices_boost call that made `l` (status_h[n_utt]): KHG_LAT_SUCCEEDED,
+ * KHG_LAT_NO_PATH for an utterance whose input lattice was empty, KHG_LAT_NO_REF.  A handle made otherwise: KHG_E_ARG. */
+int khg_lattices_op_status(const khg_lattices *l, int32_t *status_h);
+/* lattice-boost-ali (Kaldi's LatticeBoost).  Every arc with ilabel != 0 leaving a state of frame t of utterance u, with
+ * ref = tid2phone[ali[u][t]] and ph = tid2phone[ilabel]:  e = 0 if ph == ref; max_silence_error if ph != ref and ph is a silence phone;
+ * 1 otherwise;  graph_cost := fl(graph_cost + fl(-b * e)).  Everything else is copied.  tid2phone_h[num_tids + 1] (entry 0 unused).
+ * The alignment: EITHER host arrays (ali_off_h[n_utt + 1], ali_h[ali_off_h[n_utt]]) OR, both NULL, ali_set -- the alignment the last
+ * khg_align / khg_ali_upload left resident in that set (same context, same n_utt).  Anything else: KHG_E_ARG.
+ * status_h[n_utt] (may be NULL): KHG_LAT_SUCCEEDED; KHG_LAT_NO_PATH for an empty input (stays empty); KHG_LAT_NO_REF (above; such an
+ * utterance gets an EMPTY lattice, as lattice-boost-ali skips it).
+ * KHG_E_ARG: non-finite b or max_silence_error, a lattice ilabel above num_tids, a silence phone that no id maps to.
+ * Boosting changes graph costs only: it commutes with rescoring and is done once, after the decode.  Synchronous. */
+int khg_lattices_boost(khg_ctx *ctx, const khg_lattices *l, int32_t num_tids, const int32_t *tid2phone_h,
+                       int32_t n_sil, const int32_t *silence_phones_h, const int64_t *ali_off_h, const int32_t *ali_h,
+                       const khg_utts *ali_set, float b, float max_silence_error, int32_t *status_h, khg_lattices **out);
+
 /* ---- K3: sufficient statistics ---------------------------------------------------------- */
 /* AccumAmDiagGmm (csrc/mle-am-diag-gmm.h:93-96) + transition stats (csrc/transition-model.h:176-189)
  * as ONE contiguous fp64 device buffer (a single RCCL all-reduce sums it across GPUs =

@@ -110,6 +110,10 @@ class EbwResultsC(C.Structure):
                 ("failed", C.c_int32), ("skipped", C.c_int32), ("weights_skipped", C.c_int32)]
 
 
+class RescoreStatsC(C.Structure):
+    _fields_ = [("arcs", C.c_int64), ("emitting_arcs", C.c_int64), ("cells", C.c_int64)]
+
+
 # every symbol include/khg_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "khg_last_error": (C.c_char_p, []),
@@ -183,6 +187,10 @@ SIGNATURES = {
     "khg_lattices_best_path": (C.c_int, [vp, vp, C.c_int32, c_f32p, c_f32p, c_i32p, c_i32p, c_i64p, C.c_int64, c_f32p, c_i32p]),
     "khg_lattices_prune": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_float, c_i32p, C.POINTER(vp)]),
     "khg_lattices_posteriors": (C.c_int, [vp, vp, C.c_float, C.c_float, c_i32p, c_f64p, C.POINTER(vp)]),
+    "khg_lattices_rescore": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, C.c_int, C.POINTER(RescoreStatsC), C.POINTER(vp)]),
+    "khg_lattices_op_status": (C.c_int, [vp, c_i32p]),
+    "khg_lattices_boost": (C.c_int, [vp, vp, C.c_int32, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p, vp, C.c_float, C.c_float, c_i32p,
+                                     C.POINTER(vp)]),
     "khg_posteriors_sizes": (C.c_int, [vp, c_i64p, c_i64p]),
     "khg_posteriors_download": (C.c_int, [vp, vp, c_i64p, c_i32p, c_f64p, c_f64p]),
     "khg_posteriors_device_bytes": (C.c_int, [vp, c_i64p]),

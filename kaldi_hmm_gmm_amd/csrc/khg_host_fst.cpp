@@ -377,6 +377,46 @@ LatticePosteriors Lattice::ForwardBackward(float graph_scale, float acoustic_sca
   return out;
 }
 
+std::shared_ptr<Lattice> Lattice::Rescore(const std::function<float(int, int)>& loglike, float acoustic_scale) const {
+  KHG_REQUIRE(std::isfinite(acoustic_scale), "Lattice::Rescore: acoustic_scale must be finite");
+  auto r = std::make_shared<Lattice>(*this);
+  for (int s = 0; s < NumStates(); ++s)
+    for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a)
+      if (ilabel[(size_t)a] != 0) {
+        const float prod = acoustic_scale * loglike(frame[(size_t)s], ilabel[(size_t)a]);
+        r->acoustic_cost[(size_t)a] = -prod;
+      }
+  return r;
+}
+
+std::shared_ptr<Lattice> Lattice::Boost(const std::vector<int32_t>& tid2phone, const std::vector<int32_t>& silence_phones,
+                                        const std::vector<int32_t>& alignment, float b, float max_silence_error) const {
+  KHG_REQUIRE(std::isfinite(b) && std::isfinite(max_silence_error), "Lattice::Boost: b and max_silence_error must be finite");
+  KHG_REQUIRE(!tid2phone.empty(), "Lattice::Boost: tid2phone needs an entry per transition-id, and entry 0");
+  const int32_t num_tids = (int32_t)tid2phone.size() - 1;
+  for (int32_t sp : silence_phones)
+    KHG_REQUIRE(std::find(tid2phone.begin() + 1, tid2phone.end(), sp) != tid2phone.end(),
+                "Lattice::Boost: silence phone " + std::to_string(sp) + " is the phone of no transition-id");
+  const int T = NumStates() ? frame.back() : 0;
+  KHG_REQUIRE((int64_t)alignment.size() == (int64_t)T, "Lattice::Boost: the alignment has " + std::to_string(alignment.size()) +
+                                                           " frames, the lattice " + std::to_string(T));
+  for (int32_t x : alignment) KHG_REQUIRE(x >= 1 && x <= num_tids, "Lattice::Boost: the alignment holds an id outside 1 .. num_tids");
+  auto r = std::make_shared<Lattice>(*this);
+  const float nb = -b;
+  for (int s = 0; s < NumStates(); ++s)
+    for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) {
+      const int32_t il = ilabel[(size_t)a];
+      if (il == 0) continue;
+      KHG_REQUIRE(il >= 1 && il <= num_tids, "Lattice::Boost: an arc carries an ilabel outside 0 .. num_tids");
+      KHG_REQUIRE(frame[(size_t)s] < T, "Lattice::Boost: an emitting arc leaves the last frame");
+      const int32_t ph = tid2phone[(size_t)il], ref = tid2phone[(size_t)alignment[(size_t)frame[(size_t)s]]];
+      const float e = ph == ref ? 0.0f : std::find(silence_phones.begin(), silence_phones.end(), ph) != silence_phones.end() ? max_silence_error : 1.0f;
+      const float term = nb * e;
+      r->graph_cost[(size_t)a] = graph_cost[(size_t)a] + term;
+    }
+  return r;
+}
+
 std::shared_ptr<Lattice> Lattice::Prune(float beam, float gs, float as, int* status) const {
   KHG_REQUIRE(beam >= 0.0f, "Lattice::Prune: beam must be >= 0");
   auto out = std::make_shared<Lattice>();

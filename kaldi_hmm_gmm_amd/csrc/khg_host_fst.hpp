@@ -6,6 +6,8 @@
 // ModifyGraphForCarefulAlignment (decoder-wrappers.cc:111-140), and FasterDecoder's host side (faster-decoder.cc:33-53 decode /
 // :346-423 ReachedFinal / GetBestPath; python/csrc/faster-decoder.cc:14-53) over K1 + K2.
 #pragma once
+#include <functional>
+
 #include "khg_host_align.hpp"
 
 namespace khg {
@@ -164,6 +166,16 @@ class Lattice {
   // -graph_scale * final_cost on the last frame.  Every arc must go to a higher state: an epsilon arc that does not gives
   // KHG_LAT_EPS_LOOP (checked on the structure, before any arithmetic).  Each log-sum is max-then-sum over a state's arcs in arc order.
   LatticePosteriors ForwardBackward(float graph_scale = 1.0f, float acoustic_scale = 1.0f) const;
+  // gmm-rescore-lattice (what khg_lattices_rescore gives for one lattice): a copy in which every arc with ilabel != 0
+  // leaving a state of frame t has acoustic_cost = -(acoustic_scale * loglike(t, ilabel)), one float multiply and a sign; everything
+  // else as stored (tot_cost / extra_cost are then stale)
+  std::shared_ptr<Lattice> Rescore(const std::function<float(int, int)>& loglike, float acoustic_scale = 1.0f) const;
+  // lattice-boost-ali (Kaldi's LatticeBoost; what khg_lattices_boost gives for one lattice): a copy in which every arc with ilabel != 0
+  // at frame t has graph_cost = fl(graph_cost + fl(-b * e)), e = 0 where tid2phone[ilabel] == tid2phone[alignment[t]], max_silence_error
+  // where they differ and the arc's phone is a silence phone, 1 otherwise.  tid2phone[0] is unused.  The alignment has one id in
+  // 1 .. tid2phone.size() - 1 per frame of the lattice, and every ilabel lies in that range.
+  std::shared_ptr<Lattice> Boost(const std::vector<int32_t>& tid2phone, const std::vector<int32_t>& silence_phones,
+                                 const std::vector<int32_t>& alignment, float b, float max_silence_error) const;
   // Kaldi's text form of a lattice: "src dst ilabel olabel graph,acoustic" per arc, "state graph,acoustic" per final state
   std::string ToText() const;
 

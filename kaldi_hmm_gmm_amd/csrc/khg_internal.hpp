@@ -310,6 +310,12 @@ struct khg_utts {
   int32_t *pe_row_d = nullptr, *pe_tid_d = nullptr, *pe_ids_d = nullptr; float* pe_w_d = nullptr; size_t pe_cap = 0;
   uint32_t *pe_keys_d = nullptr, *pe_keys_out_d = nullptr, *pe_vals_d = nullptr; void* pe_tmp_d = nullptr; size_t pe_tmp_bytes = 0;
   int64_t* pe_start_d = nullptr; int32_t pe_P = 0;
+  // khg_lattices_rescore, CELLS mode (khg_k1_cells.hip.inc): (pdf, row) keys of the arcs and their sort, the inclusive scan of the cell
+  // heads, the distinct cells' rows and values -- sized by the ARC count, kept, grown on demand; per-pdf bounds and work items by P
+  uint64_t *rc_keys_d = nullptr, *rc_keys_out_d = nullptr; uint32_t *rc_vals_d = nullptr, *rc_vals_out_d = nullptr;
+  int32_t *rc_flag_d = nullptr, *rc_inc_d = nullptr, *rc_row_d = nullptr; float* rc_cell_d = nullptr; size_t rc_cap = 0;
+  void* rc_tmp_d = nullptr; size_t rc_tmp_bytes = 0;
+  int32_t *rc_cell_start_d = nullptr, *rc_item_off_d = nullptr; int64_t* rc_stats_d = nullptr; int32_t rc_P = -1;
 };
 
 // states of utterance i's decoding graph (host code sizing scratch)

@@ -2,7 +2,8 @@
 // (khg_decode_lattice_faster, khg_k2_lattice.hip.inc) and the data-parallel LatticeSimpleDecoder (khg_decode_lattice_simple,
 // khg_k2_lattice_simple.hip.inc), each with its raw lattice (khg_decode_lattice_faster_raw, khg_k2_lattice_faster_raw.hip.inc;
 // khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc); the handle of resident lattices (khg_lattices) with the operations on it
-// (khg_k2_lattice_ops.hip.inc) and its forward-backward posteriors (khg_posteriors, khg_k2_lattice_post.hip.inc).  gfx950 only.
+// (khg_k2_lattice_ops.hip.inc), its forward-backward posteriors (khg_posteriors, khg_k2_lattice_post.hip.inc), and rescoring / boosting
+// (khg_lattices_rescore, khg_lattices_boost: khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
 
 #include <memory>
@@ -15,6 +16,8 @@
 #include "khg_k2_lattice_faster_raw.hip.inc"
 #include "khg_k2_lattice_ops.hip.inc"
 #include "khg_k2_lattice_post.hip.inc"
+#include "khg_k1_cells.hip.inc"
+#include "khg_k2_lattice_rescore.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // The raw lattices of one batch (khg_decode_lattice_simple_raw, khg_decode_lattice_faster_raw): per chunk of scratch slices one
@@ -40,6 +43,8 @@ struct khg_lattices {
   // the in-arc index khg_lattices_posteriors gathers through, made at its first call: per chunk one block
   // [in_begin: states + utterances | in_arc: arcs | arc_src: arcs] (int32)
   std::vector<int32_t*> idx_d;
+  khg_ctx* ctx = nullptr;                        // the context it was made on
+  std::vector<int32_t> op_status;                // [U] KHG_LAT_* bits of the khg_lattices_rescore / _boost that made it (empty otherwise)
 };
 
 namespace {
@@ -60,9 +65,9 @@ struct DevBlocks {
 };
 
 // an empty handle of U utterances, with the start states' array
-int new_lattices(int U, LatPtr* out) {
+int new_lattices(khg_ctx* ctx, int U, LatPtr* out) {
   LatPtr l(new khg_lattices);
-  l->U = U;
+  l->U = U; l->ctx = ctx;
   l->state_off.assign((size_t)U + 1, 0);
   l->arc_off.assign((size_t)U + 1, 0);
   if (U > 0) {
@@ -476,7 +481,7 @@ int decode_lattice_faster_impl(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, cons
   if (rc) return rc;
   const int U = u->n_utt;
   LatPtr lats;
-  if (r.lat && (rc = new_lattices(U, &lats))) return rc;
+  if (r.lat && (rc = new_lattices(ctx, U, &lats))) return rc;
   if (U == 0) { if (r.lat) *lat_out = lats.release(); return KHG_OK; }
   if (r.lat) {
     r.start_d = lats->start_d;
@@ -582,7 +587,7 @@ int decode_lattice_simple_impl(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, cons
   const int U = u->n_utt;
   const bool lat = lat_out != nullptr;
   LatPtr lats;
-  if (lat && (rc = new_lattices(U, &lats))) return rc;
+  if (lat && (rc = new_lattices(ctx, U, &lats))) return rc;
   if (U == 0) { if (lat) *lat_out = lats.release(); return KHG_OK; }
   DevBlocks dv;
   LrArgs p;          // (lattices) the chunks' emit
@@ -795,7 +800,7 @@ extern "C" int khg_lattices_upload(khg_ctx* ctx, int32_t n_utt, const int64_t* s
                                  graph_cost, acoustic_cost, nextstate, start);
   if (rc) return rc;
   LatPtr l;
-  if ((rc = new_lattices(n_utt, &l))) return rc;
+  if ((rc = new_lattices(ctx, n_utt, &l))) return rc;
   l->state_off.assign(state_off, state_off + n_utt + 1);
   l->arc_off.assign(arc_off, arc_off + n_utt + 1);
   if (n_utt == 0) { *out = l.release(); return KHG_OK; }
@@ -912,7 +917,7 @@ extern "C" int khg_lattices_prune(khg_ctx* ctx, const khg_lattices* lc, float gr
   khg_lattices* l = const_cast<khg_lattices*>(lc);
   const int U = l->U;
   LatPtr res;
-  int rc = new_lattices(U, &res);
+  int rc = new_lattices(ctx, U, &res);
   if (rc) return rc;
   if (U == 0) { *out = res.release(); return KHG_OK; }
   rc = arena_flush(ctx);
@@ -1266,5 +1271,308 @@ int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set
     KHG_LAUNCH(ctx, k3_post_flatten, dim3((unsigned)std::min<int64_t>(4096, (c.ne + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
   }
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2X: rescoring and boosting (khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc).  Both make a copy of the handle
+// -- the utterances in `drop` left empty -- and then change one per-arc array of the copy in place.
+namespace {
+// A new handle with l's chunks; the lattice of an utterance u with drop[u] != 0 is left empty.  Whole arrays are copied on the device
+// (a chunk with dropped utterances: the runs of kept ones).  Without a dropped utterance the offsets on the device, the alignment layout
+// and the in-arc index go along when l has them: the structure is the same.
+int lat_clone(khg_ctx* ctx, const khg_lattices* l, const std::vector<char>& drop, LatPtr* out) {
+  const int U = l->U;
+  LatPtr r;
+  int rc = new_lattices(ctx, U, &r);
+  if (rc) return rc;
+  bool any = false;
+  for (int u = 0; u < U; ++u) {
+    const bool d = drop[(size_t)u] != 0;
+    any = any || d;
+    r->state_off[(size_t)u + 1] = r->state_off[(size_t)u] + (d ? 0 : l->state_off[(size_t)u + 1] - l->state_off[(size_t)u]);
+    r->arc_off[(size_t)u + 1] = r->arc_off[(size_t)u] + (d ? 0 : l->arc_off[(size_t)u + 1] - l->arc_off[(size_t)u]);
+  }
+  if (U > 0) HIPCHK(hipMemcpyAsync(r->start_d, l->start_d, 4 * (size_t)U, hipMemcpyDeviceToDevice, ctx->stream));
+  for (int u = 0; u < U; ++u)
+    if (drop[(size_t)u]) HIPCHK(hipMemsetAsync(r->start_d + u, 0xFF, 4, ctx->stream));      // -1
+  for (const LatChunk& c : l->chunks) {
+    LatChunk ch;
+    ch.u0 = c.u0; ch.n = c.n;
+    ch.ns = r->state_off[(size_t)c.u0 + c.n] - r->state_off[(size_t)c.u0];
+    ch.na = r->arc_off[(size_t)c.u0 + c.n] - r->arc_off[(size_t)c.u0];
+    if ((rc = lat_chunk_alloc(&ch, &r->bytes))) return rc;
+    r->chunks.push_back(ch);
+    for (int ua = c.u0; ua < c.u0 + c.n;) {          // runs of kept utterances
+      if (drop[(size_t)ua]) { ++ua; continue; }
+      int ub = ua;
+      while (ub < c.u0 + c.n && !drop[(size_t)ub]) ++ub;
+      const int64_t ss = l->state_off[(size_t)ua] - l->state_off[(size_t)c.u0], ds = r->state_off[(size_t)ua] - r->state_off[(size_t)c.u0];
+      const int64_t sa = l->arc_off[(size_t)ua] - l->arc_off[(size_t)c.u0], da = r->arc_off[(size_t)ua] - r->arc_off[(size_t)c.u0];
+      const int64_t ns = l->state_off[(size_t)ub] - l->state_off[(size_t)ua], na = l->arc_off[(size_t)ub] - l->arc_off[(size_t)ua];
+      for (int k = 0; k < 6 && ns > 0; ++k)
+        HIPCHK(hipMemcpyAsync(ch.buf + ch.st[k] + 4 * ds, c.buf + c.st[k] + 4 * ss, 4 * (size_t)ns, hipMemcpyDeviceToDevice, ctx->stream));
+      for (int k = 0; k < 5 && na > 0; ++k)
+        HIPCHK(hipMemcpyAsync(ch.buf + ch.ar[k] + 4 * da, c.buf + c.ar[k] + 4 * sa, 4 * (size_t)na, hipMemcpyDeviceToDevice, ctx->stream));
+      ua = ub;
+    }
+  }
+  if (!any && U > 0) {
+    if (l->off_d) {
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->off_d), 16 * ((size_t)U + 1)));
+      r->bytes += 16 * ((int64_t)U + 1);
+      HIPCHK(hipMemcpyAsync(r->off_d, l->off_d, 16 * ((size_t)U + 1), hipMemcpyDeviceToDevice, ctx->stream));
+      r->ali_off = l->ali_off;
+    }
+    if (!l->chunks.empty() && l->idx_d.size() == l->chunks.size()) {
+      for (size_t k = 0; k < l->chunks.size(); ++k) {
+        const LatChunk& c = l->chunks[k];
+        const int64_t words = c.ns + c.n + 2 * c.na;
+        int32_t* blk = nullptr;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&blk), (size_t)std::max<int64_t>(4 * words, 16)));
+        r->idx_d.push_back(blk);
+        r->bytes += 4 * words;
+        HIPCHK(hipMemcpyAsync(blk, l->idx_d[k], 4 * (size_t)words, hipMemcpyDeviceToDevice, ctx->stream));
+      }
+    }
+  }
+  *out = std::move(r);
+  return KHG_OK;
+}
+void k2x_chunk(const khg_lattices* l, const LatChunk& c, K2xChunk* p) {
+  lat_chunk_arrays(c, &p->io);
+  p->state_off = l->off_d; p->arc_off = l->off_d + l->U + 1;
+  p->s_base = l->state_off[(size_t)c.u0]; p->a_base = l->arc_off[(size_t)c.u0]; p->na = c.na;
+  p->u0 = c.u0; p->n = c.n;
+}
+unsigned k2x_grid(int64_t na) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (na + K2X_NT - 1) / K2X_NT)); }
+// the statuses of a rescored / boosted handle: KHG_LAT_NO_REF where dropped, KHG_LAT_NO_PATH for an empty input
+void k2x_status(const khg_lattices* in, const std::vector<char>& drop, khg_lattices* res) {
+  res->op_status.resize((size_t)in->U);
+  for (int u = 0; u < in->U; ++u)
+    res->op_status[(size_t)u] = in->state_off[(size_t)u + 1] == in->state_off[(size_t)u] ? KHG_LAT_NO_PATH : drop[(size_t)u] ? KHG_LAT_NO_REF : KHG_LAT_SUCCEEDED;
+}
+}  // namespace
+
+extern "C" int khg_lattices_op_status(const khg_lattices* l, int32_t* status_h) {
+  if (!l || !status_h) return khg_set_error(KHG_E_ARG, "khg_lattices_op_status: bad arguments");
+  if ((int)l->op_status.size() != l->U) return khg_set_error(KHG_E_ARG, "khg_lattices_op_status: the handle was not made by khg_lattices_rescore or khg_lattices_boost");
+  std::copy(l->op_status.begin(), l->op_status.end(), status_h);
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_rescore(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_lattices* lc, float acoustic_scale,
+                                    int mode, khg_rescore_stats* stats, khg_lattices** out) {
+  const std::string who = "khg_lattices_rescore: ";
+  if (ctx_dead(ctx) || !m || !tm || !u || !lc || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  *out = nullptr;
+  { int rf = utts_foreign_ctx(ctx, u, "khg_lattices_rescore"); if (rf) return rf; }
+  if (m->ctx != ctx || tm->ctx != ctx || u->ctx != ctx || lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (mode != KHG_RESCORE_CELLS && mode != KHG_RESCORE_FROM_LL) return khg_set_error(KHG_E_ARG, who + "unknown mode " + std::to_string(mode));
+  if (!std::isfinite(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "acoustic_scale must be finite");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  if (U != u->n_utt) return khg_set_error(KHG_E_ARG, who + "the lattices hold " + std::to_string(U) + " utterances, the set " + std::to_string(u->n_utt));
+  if (m->D != u->D) return khg_set_error(KHG_E_ARG, who + "model / feature dimensions do not match");
+  if (tm->max_pdf >= m->P) return khg_set_error(KHG_E_ARG, who + "transition model refers to pdf-ids the model does not have");
+  if (mode == KHG_RESCORE_FROM_LL) {
+    if (!u->ll_valid) return khg_set_error(KHG_E_ARG, who + "KHG_RESCORE_FROM_LL needs resident scores: call khg_loglikes first");
+    if (u->ll_mode == 2) return khg_set_error(KHG_E_ARG, who + "the scores come from khg_loglikes_band; call khg_loglikes (every cell) first");
+  }
+  const int64_t NA = l->arc_off[(size_t)U];
+  if (NA >= (int64_t)INT_MAX || u->N >= (int64_t)INT_MAX) return khg_set_error(KHG_E_UNSUPPORTED, who + "2^31 - 1 or more arcs or frames");
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (rc) return rc;
+  for (int i = 0; i < U; ++i) {
+    if (l->state_off[(size_t)i + 1] == l->state_off[(size_t)i]) continue;
+    const int64_t tl = l->ali_off[(size_t)i + 1] - l->ali_off[(size_t)i], ts = u->frame_off[(size_t)i + 1] - u->frame_off[(size_t)i];
+    if (tl != ts)
+      return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(i) + ": the lattice spans " + std::to_string(tl) + " frames, the set has " + std::to_string(ts));
+  }
+  if (stats) { stats->arcs = NA; stats->emitting_arcs = 0; stats->cells = 0; }
+  std::vector<char> drop((size_t)U, 0);
+  LatPtr res;
+  DevBlocks dv;
+  if (mode == KHG_RESCORE_FROM_LL && NA > 0) {
+    if ((rc = wait_ali(ctx, u))) return rc;
+    int32_t* flag_d;
+    if ((rc = dv.alloc(U, &flag_d))) return rc;
+    HIPCHK(hipMemsetAsync(flag_d, 0, 4 * (size_t)U, ctx->stream));
+    K2xLl p;
+    std::memset(&p, 0, sizeof(p));
+    p.set_frame_off = u->frame_off_d; p.pdf_off = u->pdf_off_d; p.ll_off = u->ll_off_d; p.pdfs = u->pdfs_d; p.ll = u->ll_d;
+    p.id2pdf = tm->id2pdf_d; p.num_tids = tm->num_tids; p.scale = acoustic_scale; p.flag = flag_d; p.err_flag = ctx->err_flag_d;
+    {
+      KernelTimer kt(ctx, "k2x_ll_check");
+      for (const LatChunk& c : l->chunks) {
+        if (c.na == 0) continue;
+        k2x_chunk(l, c, &p.c);
+        KHG_LAUNCH(ctx, k2x_ll<false>, dim3(k2x_grid(c.na)), dim3(K2X_NT), 0, ctx->stream, p);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    std::vector<int32_t> flag((size_t)U);
+    HIPCHK(hipMemcpyAsync(flag.data(), flag_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = check_err_flag(ctx, "khg_lattices_rescore"))) return rc;      // synchronises
+    for (int i = 0; i < U; ++i) drop[(size_t)i] = flag[(size_t)i] != 0;
+    if ((rc = lat_clone(ctx, l, drop, &res)) || (rc = lat_meta(ctx, res.get()))) return rc;
+    KernelTimer kt(ctx, "k2x_ll_gather");
+    for (const LatChunk& c : res->chunks) {
+      if (c.na == 0) continue;
+      k2x_chunk(res.get(), c, &p.c);
+      KHG_LAUNCH(ctx, k2x_ll<true>, dim3(k2x_grid(c.na)), dim3(K2X_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+  } else {
+    if ((rc = lat_clone(ctx, l, drop, &res))) return rc;
+  }
+  int64_t st[4] = {NA, 0, 0, 0};
+  std::vector<int64_t> base;
+  std::vector<float*> acp;
+  if (mode == KHG_RESCORE_CELLS && NA > 0) {
+    if ((rc = lat_meta(ctx, res.get())) || (rc = k1_cells_scratch(u, NA, m->P)) || (rc = arena_flush(ctx))) return rc;
+    K2xFlat f;
+    std::memset(&f, 0, sizeof(f));
+    f.set_frame_off = u->frame_off_d; f.id2pdf = tm->id2pdf_d; f.num_tids = tm->num_tids; f.P = m->P;
+    f.keys = u->rc_keys_d; f.vals = u->rc_vals_d; f.err_flag = ctx->err_flag_d;
+    {
+      KernelTimer kt(ctx, "k2x_flatten");
+      for (const LatChunk& c : res->chunks) {
+        if (c.na == 0) continue;
+        k2x_chunk(res.get(), c, &f.c);
+        KHG_LAUNCH(ctx, k2x_flatten, dim3(k2x_grid(c.na)), dim3(K2X_NT), 0, ctx->stream, f);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    for (const LatChunk& c : res->chunks) {
+      base.push_back(res->arc_off[(size_t)c.u0]);
+      acp.push_back(reinterpret_cast<float*>(c.buf + c.ar[3]));
+    }
+    base.push_back(NA);
+    K1cTargets tg;
+    int64_t* base_d; float** acp_d;
+    if ((rc = dv.alloc((int64_t)base.size(), &base_d)) || (rc = dv.alloc((int64_t)acp.size(), &acp_d))) return rc;
+    HIPCHK(hipMemcpyAsync(base_d, base.data(), 8 * base.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(acp_d, acp.data(), sizeof(float*) * acp.size(), hipMemcpyHostToDevice, ctx->stream));
+    tg.base = base_d; tg.ac = acp_d; tg.n = (int32_t)acp.size();
+    if ((rc = k1_cells_run(ctx, m, u, NA, acoustic_scale, tg, st))) return rc;
+  }
+  if ((rc = check_err_flag(ctx, "khg_lattices_rescore"))) return rc;      // synchronises: the scratch goes with `dv`
+  if (stats) { stats->arcs = NA; stats->emitting_arcs = st[1]; stats->cells = st[2]; }
+  k2x_status(l, drop, res.get());
+  *out = res.release();
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t num_tids, const int32_t* tid2phone_h, int32_t n_sil,
+                                  const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set, float b,
+                                  float max_silence_error, int32_t* status_h, khg_lattices** out) {
+  const std::string who = "khg_lattices_boost: ";
+  if (ctx_dead(ctx) || !lc || !out || num_tids < 0 || !tid2phone_h || n_sil < 0 || (n_sil > 0 && !silence_phones_h))
+    return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  *out = nullptr;
+  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  const bool host_ali = ali_off_h && ali_h;
+  if ((ali_off_h != nullptr) != (ali_h != nullptr) || host_ali == (ali_set != nullptr))
+    return khg_set_error(KHG_E_ARG, who + "give either the host alignment (ali_off_h and ali_h) or ali_set, not both and not neither");
+  if (!std::isfinite(b) || !std::isfinite(max_silence_error)) return khg_set_error(KHG_E_ARG, who + "b and max_silence_error must be finite");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  khg_utts* as = const_cast<khg_utts*>(ali_set);
+  if (as) {
+    { int rf = utts_foreign_ctx(ctx, as, "khg_lattices_boost"); if (rf) return rf; }
+    if (as->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+    if (as->n_utt != U) return khg_set_error(KHG_E_ARG, who + "the lattices hold " + std::to_string(U) + " utterances, ali_set " + std::to_string(as->n_utt));
+    if (!as->ali_valid) return khg_set_error(KHG_E_ARG, who + "ali_set has no resident alignment: call khg_align (or khg_ali_upload) first");
+  } else {
+    if (ali_off_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "ali_off_h must start at 0");
+    for (int i = 0; i < U; ++i)
+      if (ali_off_h[i + 1] < ali_off_h[i]) return khg_set_error(KHG_E_ARG, who + "ali_off_h decreases at utterance " + std::to_string(i));
+  }
+  // the phone map and the silence set as one table: 2 * phone + (silence)
+  std::vector<int32_t> tab((size_t)num_tids + 1, 0);
+  for (int t = 1; t <= num_tids; ++t) {
+    if (tid2phone_h[t] < 0 || tid2phone_h[t] > INT32_MAX / 2) return khg_set_error(KHG_E_ARG, who + "tid2phone[" + std::to_string(t) + "] out of range");
+    tab[(size_t)t] = 2 * tid2phone_h[t];
+  }
+  for (int k = 0; k < n_sil; ++k) {
+    bool seen = false;
+    for (int t = 1; t <= num_tids; ++t)
+      if (tid2phone_h[t] == silence_phones_h[k]) { tab[(size_t)t] |= 1; seen = true; }
+    if (!seen) return khg_set_error(KHG_E_ARG, who + "silence phone " + std::to_string(silence_phones_h[k]) + " is the phone of no transition-id");
+  }
+  LatPtr res;
+  std::vector<char> drop((size_t)U, 0);
+  if (U == 0) {
+    int rc = lat_clone(ctx, l, drop, &res);
+    if (rc) return rc;
+    *out = res.release();
+    return KHG_OK;
+  }
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc && as) rc = wait_ali(ctx, as);
+  if (rc) return rc;
+  DevBlocks dv;
+  const int32_t* ali_d = nullptr; const int64_t* aoff_d = nullptr;
+  int32_t *flag_d, *tab_d;
+  if ((rc = dv.alloc(U + 1, &flag_d)) || (rc = dv.alloc((int64_t)tab.size(), &tab_d))) return rc;      // [U]: the label word
+  HIPCHK(hipMemsetAsync(flag_d, 0, 4 * ((size_t)U + 1), ctx->stream));
+  HIPCHK(hipMemcpyAsync(tab_d, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice, ctx->stream));
+  // what the host knows: the alignment's length against the lattice's frame count (and, of a host alignment, its ids)
+  for (int i = 0; i < U; ++i) {
+    const int64_t tl = l->ali_off[(size_t)i + 1] - l->ali_off[(size_t)i];
+    const int64_t ta = as ? as->frame_off[(size_t)i + 1] - as->frame_off[(size_t)i] : ali_off_h[i + 1] - ali_off_h[i];
+    if (ta == 0 || ta != tl) drop[(size_t)i] = 1;
+    if (!as && !drop[(size_t)i])
+      for (int64_t k = ali_off_h[i]; k < ali_off_h[i + 1]; ++k)
+        if (ali_h[k] < 1 || ali_h[k] > num_tids) { drop[(size_t)i] = 1; break; }
+  }
+  if (as) {
+    ali_d = as->ali_d; aoff_d = as->frame_off_d;
+    KernelTimer kt(ctx, "k2x_ali_check");
+    KHG_LAUNCH(ctx, k2x_ali_check, dim3((unsigned)U), dim3(K2X_NT), 0, ctx->stream, ali_d, aoff_d, num_tids, flag_d);
+    HIPCHK(hipGetLastError());
+  } else {
+    int32_t* a_d; int64_t* o_d;
+    const int64_t n = ali_off_h[U];
+    if ((rc = dv.alloc(std::max<int64_t>(n, 1), &a_d)) || (rc = dv.alloc(U + 1, &o_d))) return rc;
+    if (n > 0) HIPCHK(hipMemcpyAsync(a_d, ali_h, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(o_d, ali_off_h, 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+    ali_d = a_d; aoff_d = o_d;
+  }
+  {
+    KernelTimer kt(ctx, "k2x_label_check");
+    for (const LatChunk& c : l->chunks) {
+      if (c.na == 0) continue;
+      K2xChunk kc;
+      k2x_chunk(l, c, &kc);
+      KHG_LAUNCH(ctx, k2x_label_check, dim3(k2x_grid(c.na)), dim3(K2X_NT), 0, ctx->stream, kc, num_tids, flag_d + U);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  std::vector<int32_t> flag((size_t)U + 1);
+  HIPCHK(hipMemcpyAsync(flag.data(), flag_d, 4 * ((size_t)U + 1), hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = check_err_flag(ctx, "khg_lattices_boost"))) return rc;      // synchronises (the caller's arrays are free again)
+  if (flag[(size_t)U]) return khg_set_error(KHG_E_ARG, who + "a lattice arc carries an ilabel outside 0 .. num_tids = " + std::to_string(num_tids));
+  for (int i = 0; i < U; ++i) drop[(size_t)i] = drop[(size_t)i] || flag[(size_t)i] != 0;
+  if ((rc = lat_clone(ctx, l, drop, &res)) || (rc = lat_meta(ctx, res.get()))) return rc;
+  K2xBoost p;
+  std::memset(&p, 0, sizeof(p));
+  p.ali = ali_d; p.ali_off = aoff_d; p.tab = tab_d; p.neg_b = -b; p.max_sil_err = max_silence_error;
+  {
+    KernelTimer kt(ctx, "k2x_boost");
+    for (const LatChunk& c : res->chunks) {
+      if (c.na == 0) continue;
+      k2x_chunk(res.get(), c, &p.c);
+      KHG_LAUNCH(ctx, k2x_boost, dim3(k2x_grid(c.na)), dim3(K2X_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  if ((rc = check_err_flag(ctx, "khg_lattices_boost"))) return rc;      // synchronises: the scratch goes with `dv`
+  k2x_status(l, drop, res.get());
+  if (status_h) std::copy(res->op_status.begin(), res->op_status.end(), status_h);
+  *out = res.release();
   return KHG_OK;
 }

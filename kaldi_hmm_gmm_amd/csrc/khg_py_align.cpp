@@ -361,6 +361,24 @@ void BindLattice(py::module_& m) {
         d["post"] = post;
         return d;
       }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      // gmm-rescore-lattice on the host (what DeviceLattices.rescore gives for this lattice): loglikes is a [num_tids + 1][T] array of
+      // log-likelihoods by (transition-id, frame), or a callable (frame, transition-id) -> float
+      .def("rescore", [](const Lattice& l, py::object loglikes, float acoustic_scale) {
+        if (PyCallable_Check(loglikes.ptr()))
+          return l.Rescore([&](int t, int tid) { return loglikes(t, tid).cast<float>(); }, acoustic_scale);
+        Arr<float> a = loglikes.cast<Arr<float>>();
+        if (a.ndim() != 2) throw Error("Lattice.rescore: loglikes is a [num_tids + 1][T] array or a callable (frame, tid) -> float");
+        const py::ssize_t n = a.shape(0), T = a.shape(1);
+        const float* d = a.data();
+        return l.Rescore([&](int t, int tid) {
+          if (tid < 0 || tid >= n || t < 0 || t >= T) throw Error("Lattice.rescore: (frame " + std::to_string(t) + ", transition-id " + std::to_string(tid) + ") outside loglikes");
+          return d[(size_t)tid * (size_t)T + (size_t)t];
+        }, acoustic_scale);
+      }, py::arg("loglikes"), py::arg("acoustic_scale") = 1.0f)
+      // lattice-boost-ali on the host (what DeviceLattices.boost gives for this lattice)
+      .def("boost", [](const Lattice& l, std::vector<int32_t> tid2phone, std::vector<int32_t> silence_phones, std::vector<int32_t> alignment, float b,
+                       float max_silence_error) { return l.Boost(tid2phone, silence_phones, alignment, b, max_silence_error); },
+           py::arg("tid2phone"), py::arg("silence_phones"), py::arg("alignment"), py::arg("b") = 0.1f, py::arg("max_silence_error") = 0.0f)
       .def("to_text", &Lattice::ToText)
       .def("__str__", &Lattice::ToText)
       .def_property_readonly("frame", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.frame, l.frame.size()); })
@@ -496,6 +514,72 @@ void BindLattice(py::module_& m) {
         r->status.resize((size_t)U); r->tot_like.resize((size_t)U);
         return r;
       }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      // gmm-rescore-lattice -> a new DeviceLattices: every emitting arc's acoustic_cost = -(acoustic_scale * loglike of
+      // its (frame, pdf)).  mode "cells": computed from the set's features and the model for the distinct cells the lattices name (a
+      // features-only set works); "from_ll": gathered from the set's resident scores.  The result carries .status and .rescore_stats
+      .def("rescore", [](PyDeviceLattices& d, py::object utts, py::object model, py::object transitions, float acoustic_scale, const std::string& mode) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        int md;
+        if (mode == "cells") md = KHG_RESCORE_CELLS;
+        else if (mode == "from_ll") md = KHG_RESCORE_FROM_LL;
+        else throw Error("DeviceLattices.rescore: mode is \"cells\" or \"from_ll\"");
+        khg_utts* uh = reinterpret_cast<khg_utts*>(utts.attr("h").cast<uintptr_t>());
+        khg_model* mh = reinterpret_cast<khg_model*>(model.attr("h").cast<uintptr_t>());
+        khg_tm* th = reinterpret_cast<khg_tm*>(transitions.attr("h").cast<uintptr_t>());
+        auto r = std::make_shared<PyDeviceLattices>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj;
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_rescore(d.ctx, mh, th, uh, d.h, acoustic_scale, md, &r->rescore_stats, &r->h));
+        }
+        r->has_rescore_stats = true;
+        int32_t U = 0;
+        CApi(khg_lattices_num_utts(r->h, &U));
+        r->status.assign((size_t)std::max(U, 1), 0);
+        CApi(khg_lattices_op_status(r->h, r->status.data()));
+        r->status.resize((size_t)U);
+        return r;
+      }, py::arg("utts"), py::arg("model"), py::arg("transitions"), py::arg("acoustic_scale") = 1.0f, py::arg("mode") = "cells")
+      // {"arcs", "emitting_arcs", "cells"} of the rescore that made this handle (None otherwise)
+      .def_property_readonly("rescore_stats", [](PyDeviceLattices& d) -> py::object {
+        if (!d.has_rescore_stats) return py::none();
+        py::dict s;
+        s["arcs"] = d.rescore_stats.arcs; s["emitting_arcs"] = d.rescore_stats.emitting_arcs; s["cells"] = d.rescore_stats.cells;
+        return std::move(s);
+      })
+      // lattice-boost-ali -> a new DeviceLattices with graph_cost += -b * e per emitting arc.  alignment: one array of
+      // transition-ids per utterance (a list), or ali_set: an UtteranceSet whose resident alignment (align / upload_ali) is the reference
+      .def("boost", [](PyDeviceLattices& d, Arr<int32_t> tid2phone, Arr<int32_t> silence_phones, py::object alignment, py::object ali_set, float b,
+                       float max_silence_error) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        if (tid2phone.ndim() != 1 || tid2phone.shape(0) < 1 || silence_phones.ndim() != 1) throw Error("DeviceLattices.boost: tid2phone [num_tids + 1] and silence_phones are flat arrays");
+        const int U = (int)LatSizes(d).first.size() - 1;
+        std::vector<int64_t> aoff;
+        std::vector<int32_t> ali;
+        if (!alignment.is_none()) {
+          py::list al = alignment.cast<py::list>();
+          if ((int)al.size() != U) throw Error("DeviceLattices.boost: " + std::to_string(al.size()) + " alignments for " + std::to_string(U) + " lattices");
+          aoff.assign(1, 0);
+          for (py::handle h : al) {
+            Arr<int32_t> a = py::reinterpret_borrow<py::object>(h).cast<Arr<int32_t>>();
+            ali.insert(ali.end(), a.data(), a.data() + a.size());
+            aoff.push_back((int64_t)ali.size());
+          }
+          ali.push_back(0);      // (never a NULL array)
+        }
+        const khg_utts* sh = ali_set.is_none() ? nullptr : reinterpret_cast<const khg_utts*>(ali_set.attr("h").cast<uintptr_t>());
+        auto r = std::make_shared<PyDeviceLattices>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj;
+        r->status.assign((size_t)std::max(U, 1), 0);
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_boost(d.ctx, d.h, (int32_t)tid2phone.shape(0) - 1, tid2phone.data(), (int32_t)silence_phones.shape(0), silence_phones.data(),
+                                  aoff.empty() ? nullptr : aoff.data(), aoff.empty() ? nullptr : ali.data(), sh, b, max_silence_error, r->status.data(), &r->h));
+        }
+        r->status.resize((size_t)U);
+        return r;
+      }, py::arg("tid2phone"), py::arg("silence_phones"), py::arg("alignment") = py::none(), py::arg("ali_set") = py::none(), py::arg("b") = 0.1f,
+         py::arg("max_silence_error") = 0.0f)
       .def("download", [](PyDeviceLattices& d) {
         if (!d.h) throw Error("DeviceLattices: closed");
         std::vector<std::shared_ptr<Lattice>> out;

@@ -159,6 +159,12 @@ void BindHmm(py::module_& m) {
       }, py::arg("topo"), py::arg("tuples"), py::arg("log_probs"))
       .def("transition_id_to_pdf", &TransitionModel::TransitionIdToPdf, py::arg("trans_id"))
       .def("transition_id_to_pdf_array", [](TransitionModel& t) { return t.id2pdf(); })
+      // [num_transition_ids + 1], entry 0 unused (0): what lattice_boost_ali maps an arc and the reference alignment through
+      .def("transition_id_to_phone_array", [](TransitionModel& t) {
+        std::vector<int32_t> v((size_t)t.NumTransitionIds() + 1, 0);
+        for (int i = 1; i <= t.NumTransitionIds(); ++i) v[(size_t)i] = t.TransitionIdToPhone(i);
+        return v;
+      })
       .def("transition_id_to_phone", &TransitionModel::TransitionIdToPhone, py::arg("trans_id"))
       .def("transition_id_to_hmm_state", &TransitionModel::TransitionIdToHmmState, py::arg("trans_id"))
       .def("transition_ids_equivalent", &TransitionModel::TransitionIdsEquivalent)

@@ -459,6 +459,8 @@ extern "C" int khg_utts_destroy(khg_utts* u) {
   DEVFREE(u->k3_part_d); DEVFREE(u->k3_llpart_d); DEVFREE(u->k3_items_d); DEVFREE(u->k3_item_off_d);
   DEVFREE(u->pe_row_d); DEVFREE(u->pe_tid_d); DEVFREE(u->pe_ids_d); DEVFREE(u->pe_w_d); DEVFREE(u->pe_keys_d); DEVFREE(u->pe_keys_out_d);
   DEVFREE(u->pe_vals_d); DEVFREE(u->pe_tmp_d); DEVFREE(u->pe_start_d);
+  DEVFREE(u->rc_keys_d); DEVFREE(u->rc_keys_out_d); DEVFREE(u->rc_vals_d); DEVFREE(u->rc_vals_out_d); DEVFREE(u->rc_flag_d); DEVFREE(u->rc_inc_d);
+  DEVFREE(u->rc_row_d); DEVFREE(u->rc_cell_d); DEVFREE(u->rc_tmp_d); DEVFREE(u->rc_cell_start_d); DEVFREE(u->rc_item_off_d); DEVFREE(u->rc_stats_d);
   k1_free_band(u);
   if (u->ev_dp) (void)hipEventDestroy(u->ev_dp);
   if (u->ev_ali) (void)hipEventDestroy(u->ev_ali);

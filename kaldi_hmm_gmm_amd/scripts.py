@@ -243,3 +243,67 @@ def gmm_est_weights_ebw(am_gmm: AmDiagGmm, num_accs: AccumAmDiagGmm, den_accs: A
         print("Weight update: Overall", r["auxf_impr_weights"] / r["count"] if r["count"] else float("nan"),
               "auxiliary-function improvement per frame over", r["count"], "frames;", r["weights_skipped"], "pdfs skipped")
     return r
+
+
+def gmm_rescore_lattice_batch(am_gmm: AmDiagGmm, transition_model: TransitionModel, lattices, feats: Sequence[np.ndarray],
+                              acoustic_scale: float = 1.0):
+    """Kaldi's gmm-rescore-lattice for several utterances on the device (khg_lattices_rescore): every arc with a
+    transition-id gets acoustic_cost = -(acoustic_scale * loglike(frame, pdf of the id)) under `am_gmm`; only the (frame, pdf) cells
+    the lattices name are evaluated.  lattices: a list of Lattice (-> a list of Lattice; an utterance's status is not reported, an
+    empty lattice stays empty) or a DeviceLattices on the default context (-> a DeviceLattices with .status and .rescore_stats)."""
+    from .align import DeviceLattices
+    ctx = _gpu.default_context()
+    feats = [np.ascontiguousarray(f, np.float32) for f in feats]
+    go, gc, _, miv, iv = am_gmm.flat()
+    dm = DeviceModel(ctx, go, gc, miv, iv)
+    dt = DeviceTransitions(ctx, np.asarray(transition_model.transition_id_to_pdf_array(), np.int32))
+    fo = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64)
+    allf = np.concatenate(feats) if feats else np.zeros((0, am_gmm.dim), np.float32)
+    us = UtteranceSet(ctx, None, fo, np.ascontiguousarray(allf, np.float32))
+    on_device = isinstance(lattices, DeviceLattices)
+    dl = lattices if on_device else DeviceLattices.from_lattices(list(lattices), ctx)
+    try:
+        res = dl.rescore(us, dm, dt, float(acoustic_scale), "cells")
+    finally:
+        us.close(); dm.close(); dt.close()
+        if not on_device:
+            dl.close()
+    if on_device:
+        return res
+    out = res.download()
+    res.close()
+    return out
+
+
+def gmm_rescore_lattice(am_gmm: AmDiagGmm, transition_model: TransitionModel, lattice, feats, acoustic_scale: float = 1.0):
+    """Kaldi's gmm-rescore-lattice for one utterance -> the rescored Lattice (gmm_rescore_lattice_batch of one)."""
+    return gmm_rescore_lattice_batch(am_gmm, transition_model, [lattice], [feats], acoustic_scale)[0]
+
+
+def lattice_boost_ali_batch(transition_model: TransitionModel, lattices, alignments: Sequence[Sequence[int]], silence_phones: Sequence[int],
+                            b: float = 0.1, max_silence_error: float = 0.0):
+    """Kaldi's lattice-boost-ali for several utterances on the device (khg_lattices_boost): every arc with a
+    transition-id at frame t gets graph_cost += -b * e, e = 0 where its phone is the phone of alignments[u][t], max_silence_error
+    where it differs and is a silence phone, 1 otherwise.  An utterance whose alignment is missing, of another length than its lattice
+    or holds a bad id gets an empty lattice, as lattice-boost-ali skips it.  lattices: a list of Lattice (-> a list of Lattice) or a
+    DeviceLattices on the default context (-> a DeviceLattices with .status)."""
+    from .align import DeviceLattices
+    on_device = isinstance(lattices, DeviceLattices)
+    dl = lattices if on_device else DeviceLattices.from_lattices(list(lattices), _gpu.default_context())
+    try:
+        res = dl.boost(np.asarray(transition_model.transition_id_to_phone_array(), np.int32), np.asarray(list(silence_phones), np.int32),
+                       alignment=[np.asarray(a, np.int32) for a in alignments], b=float(b), max_silence_error=float(max_silence_error))
+    finally:
+        if not on_device:
+            dl.close()
+    if on_device:
+        return res
+    out = res.download()
+    res.close()
+    return out
+
+
+def lattice_boost_ali(transition_model: TransitionModel, lattice, alignment: Sequence[int], silence_phones: Sequence[int], b: float = 0.1,
+                      max_silence_error: float = 0.0):
+    """Kaldi's lattice-boost-ali for one utterance -> the boosted Lattice (lattice_boost_ali_batch of one)."""
+    return lattice_boost_ali_batch(transition_model, [lattice], [alignment], silence_phones, b, max_silence_error)[0]

@@ -320,6 +320,79 @@ def acc_from_post(ctx, dl, am, tm, feats, alignments, reps):
     return out
 
 
+def rescore_bench(ctx, dl, am, tm, fsts, feats, alignments, cfg, reps, boost):
+    """--rescore: khg_lattices_rescore (CELLS) on the resident lattices -- device time of flatten / sort / heads / score / scatter, the
+    call from the host, arcs / emitting arcs / distinct cells per frame -- and one MMI iteration's denominator side both ways, alternated
+    in this process: rescore + posteriors(1, 0.1) + acc_stats_post against loglikes + raw_lattices_faster_device + posteriors(1, 1) +
+    acc_stats_post.  Memory: the device bytes of a decoding set's dense score buffer (khg_loglikes_layout), which the rescoring path
+    never allocates.  --boost B: the call of khg_lattices_boost with the best paths as the reference."""
+    from kaldi_hmm_gmm_amd import DeviceAccs, DeviceModel, DeviceTransitions, UtteranceSet
+    reps = max(reps, 3)
+    go, gc, w, miv, iv = am.flat()
+    id2pdf = np.asarray(tm.transition_id_to_pdf_array(), np.int32)
+    dm, dt = DeviceModel(ctx, go, gc, miv, iv), DeviceTransitions(ctx, id2pdf)
+    fo = np.concatenate([[0], np.cumsum([len(f) for f in feats])]).astype(np.int64)
+    allf = np.ascontiguousarray(np.concatenate(feats), np.float32)
+    us = UtteranceSet(ctx, None, fo, allf)                               # features only: no graph, no score buffer
+    accs = DeviceAccs(ctx, dm, dt)
+    frames = int(fo[-1])
+    dl.rescore(us, dm, dt, 1.0).close(); ctx.sync()                      # warm-up (allocates the scratch)
+    k_res, t_res, stats = [], [], None
+    for _ in range(reps):
+        k_res.append(kernel_ms(ctx, lambda: dl.rescore(us, dm, dt, 1.0).close()))
+        ctx.sync(); t0 = time.time()
+        R = dl.rescore(us, dm, dt, 1.0)
+        t_res.append(time.time() - t0)
+        stats = R.rescore_stats
+        R.close()
+    res_ms = {k: float(np.median([r.get(k, 0.0) for r in k_res])) for k in sorted({k for r in k_res for k in r})}
+    out = {"repetitions": reps, "frames": frames, "arcs": stats["arcs"], "emitting_arcs": stats["emitting_arcs"], "cells": stats["cells"],
+           "arcs_per_frame": stats["arcs"] / max(frames, 1), "emitting_arcs_per_frame": stats["emitting_arcs"] / max(frames, 1),
+           "cells_per_frame": stats["cells"] / max(frames, 1), "rescore_kernels_ms": res_ms, "rescore_kernels_total_ms": sum(res_ms.values()),
+           "rescore_call": med(t_res)}
+    if boost:
+        tid2phone = np.asarray(tm.transition_id_to_phone_array(), np.int32)
+        ali = [np.asarray(a, np.int32) for a in alignments]
+        t_b = []
+        for _ in range(reps):
+            ctx.sync(); t0 = time.time()
+            B = dl.boost(tid2phone, np.asarray([1], np.int32), alignment=ali, b=boost)
+            t_b.append(time.time() - t0)
+            nref = int((np.asarray(B.status) & 512 != 0).sum())
+            B.close()
+        out.update(boost_call=med(t_b), boost_b=boost, boost_no_ref=nref,
+                   boost_kernels_ms=kernel_ms(ctx, lambda: dl.boost(tid2phone, np.asarray([1], np.int32), alignment=ali, b=boost).close()))
+    # one iteration's denominator side, both ways, alternated
+    from kaldi_hmm_gmm_amd.fst import concat_graphs
+    usg = UtteranceSet(ctx, dt, fo, allf, graphs=concat_graphs(fsts))
+    dec = dict(beam=cfg.beam, max_active=cfg.max_active, lattice_beam=cfg.lattice_beam, acoustic_scale=0.1)
+
+    def iter_rescore():
+        R = dl.rescore(us, dm, dt, 1.0)
+        P = R.posteriors(1.0, 0.1)
+        us.acc_stats_post(dm, dt, P, accs); ctx.sync()
+        P.close(); R.close()
+
+    def iter_decode():
+        usg.loglikes(dm)
+        L = usg.raw_lattices_faster_device(dt, **dec)["lattices"]
+        P = L.posteriors(1.0, 1.0)
+        usg.acc_stats_post(dm, dt, P, accs); ctx.sync()
+        P.close(); L.close()
+
+    iter_rescore(); iter_decode()
+    t_r, t_d = [], []
+    for _ in range(reps):
+        ctx.sync(); t0 = time.time(); iter_rescore(); t_r.append(time.time() - t0)
+        ctx.sync(); t0 = time.time(); iter_decode(); t_d.append(time.time() - t0)
+    ll_off, ll_total = usg.loglikes_layout()
+    out.update(iteration_rescore_post_acc=med(t_r), iteration_decode_post_acc=med(t_d), iteration_ratio=float(np.median(t_d) / np.median(t_r)),
+               iteration_rescore_kernels_ms=kernel_ms(ctx, iter_rescore), iteration_decode_kernels_ms=kernel_ms(ctx, iter_decode),
+               dense_score_buffer_bytes=int(4 * ll_total), features_bytes=int(allf.nbytes))
+    usg.close(); us.close(); accs.close(); dm.close(); dt.close()
+    return out
+
+
 def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
     """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
     after one warm-up round; and the last results."""
@@ -505,9 +578,14 @@ def main():
     ap.add_argument("--prune-beam", type=float, default=None, help="with --lattices: prune the resident lattices to this beam")
     ap.add_argument("--post", action="store_true", help="with --lattices: forward-backward posteriors of the resident lattices")
     ap.add_argument("--acc", action="store_true", help="with --lattices --post: GMM statistics from those posteriors (khg_acc_stats_post)")
+    ap.add_argument("--rescore", action="store_true", help="with --lattices (--decoder faster): khg_lattices_rescore on the resident lattices, and "
+                    "one MMI iteration's denominator side with it against decoding again")
+    ap.add_argument("--boost", type=float, default=0.0, metavar="B", help="with --rescore: also khg_lattices_boost at this b")
     args = ap.parse_args()
     if (args.sweep or args.prune_beam is not None or args.post) and not args.lattices:
         ap.error("--sweep / --prune-beam / --post need --lattices")
+    if args.rescore and (not args.lattices or args.decoder != "faster" or args.shared_graph or args.yesno):
+        ap.error("--rescore needs --lattices with --decoder faster (and is not timed with --shared-graph / --yesno)")
     if args.acc and (not args.post or args.shared_graph):
         ap.error("--acc needs --lattices --post (and is not timed with --shared-graph)")
     if args.shared_graph or args.yesno:
@@ -570,11 +648,15 @@ def main():
                     emission_kernels_ms=emit, emission_over_decoder=(emit + dec_new - dec_old) / dec_old if dec_old else None)
         faster_lat = flat
         faster_ops = None
-        if args.sweep or args.prune_beam is not None or args.post:
+        if args.sweep or args.prune_beam is not None or args.post or args.rescore:
             _, dl = khg.get_raw_lattice_faster_device_batch(am, tm, fsts, feats, cfg, 0.1)
-            faster_ops = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps, args.post)
+            faster_ops = {}
+            if args.sweep or args.prune_beam is not None or args.post:
+                faster_ops = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps, args.post)
             if args.acc:
                 faster_ops["acc_stats_post"] = acc_from_post(ctx, dl, am, tm, feats, [r["alignment"] for r in fres], args.reps)
+            if args.rescore:
+                faster_ops["rescore"] = rescore_bench(ctx, dl, am, tm, fsts, feats, [r["alignment"] for r in fres], cfg, args.reps, args.boost)
             dl.close()
     st = [r["status"] for r in res]
     out = {"decoder": args.decoder,"utterances": args.utts, "frames": frames, "lattice_s": min(lat_s), "lattice_frames_per_s": frames / min(lat_s),
