@@ -26,7 +26,16 @@ likelihood of the paths the first decode kept, under the current model, not of a
 DeviceLattices.boost, b = B, the numerator alignment of the ML model as the reference, silence errors free); boosting changes graph
 costs only, so it commutes with the rescoring.  logZ_u is then the boosted lattice's.
 
+--criterion mpe|smbr (default mmi: everything above, unchanged): MPE / sMBR training (Kaldi's train_mpe.sh).  The lattices are
+decoded once with the ML model; every iteration aligns the transcripts (the alignment is the reference and its acc_stats the ML
+block), rescores the lattices with the current model, takes the signed posteriors of the expected frame accuracy
+(DeviceLattices.mpe_posteriors at scales (1, kappa), ali_set = the aligned set: lattice-to-mpe-post / lattice-to-smbr-post), sends
+the positive weights to the numerator block and the negated negative ones to the denominator block (UtteranceSet.acc_stats_post2:
+gmm-acc-stats2), I-smooths the numerator block with the ML block (num.smooth_with_accum(tau, ml)) and runs the same EBW update.
+Per iteration it prints the criterion: the mean over the utterances of avg_acc / T, the expected fraction of correct frames.
+
 Usage: python examples/train_mmi_synthetic.py [--utts 200] [--mmi-utts 60] [--mmi-iters 4] [--tau 50] [--E 2.0] [--rescore] [--boost B]
+                                              [--criterion mmi|mpe|smbr]
 """
 import argparse
 import os
@@ -48,9 +57,11 @@ class MmiState:
     """Everything one MMI run keeps on the device: the model, the utterances on their numerator graphs (us_ali) and on the shared
     decoding graph (us_dec), the two accumulator blocks."""
 
-    def __init__(self, ctx, tm, am, graph, utts, kappa=0.1, tau=50.0, E=2.0, rescore=False, boost=0.0):
+    def __init__(self, ctx, tm, am, graph, utts, kappa=0.1, tau=50.0, E=2.0, rescore=False, boost=0.0, criterion="mmi"):
+        assert criterion in ("mmi", "mpe", "smbr")
         self.ctx, self.kappa, self.tau = ctx, float(kappa), float(tau)
         self.rescore, self.boost, self.lats0 = bool(rescore), float(boost), None
+        self.criterion, self.ml = criterion, None
         self.tid2phone = np.asarray(tm.transition_id_to_phone_array(), np.int32)
         self.opts, self.weight_opts = khg.EbwOptions(E=E), khg.EbwWeightOptions()
         self.refs = [u[1] for u in utts]
@@ -73,6 +84,9 @@ class MmiState:
         self.us_dec = khg.UtteranceSet(ctx, self.dt_dec, fo, allf, graph=self.dg)
         self.num = khg.DeviceAccs(ctx, self.dm, self.dt_ali)
         self.den = khg.DeviceAccs(ctx, self.dm, self.dt_dec)
+        if criterion != "mmi":
+            self.tid2pdf = id2pdf
+            self.ml = khg.DeviceAccs(ctx, self.dm, self.dt_ali)
         self.dec = dict(beam=13.0, max_active=7000, lattice_beam=6.0, acoustic_scale=self.kappa)
 
     def accumulate(self, check=True):
@@ -101,6 +115,32 @@ class MmiState:
         info = dict(F=F, n_ok=int(ok.sum()), num_frames=float(self.T[ok_n].sum()), den_weight=float(self.T[ok_d].sum()))
         if check:
             info["den_weight"] = float(sum(w for p in post.download() for f in p for _, w in f))
+        post.close()
+        lats.close()
+        return info
+
+    def accumulate_mpe(self, check=True):
+        """--criterion mpe|smbr: the reference alignment and the ML block, the rescored lattices' signed posteriors, the two blocks
+        -> dict(crit (the mean avg_acc / T), n_ok, pos_weight, neg_weight (check=True: the posteriors' sums by sign, downloaded))."""
+        self.num.zero()
+        self.den.zero()
+        self.ml.zero()
+        self.us_ali.loglikes(self.dm, reachable_only=True)
+        self.us_ali.align(self.dt_ali, beam=10.0, retry_beam=40.0, acoustic_scale=self.kappa)
+        self.us_ali.acc_stats(self.dm, self.dt_ali, self.ml)
+        if self.lats0 is None:
+            self.lats0 = self.decode_once()
+        lats = self.lats0.rescore(self.us_dec, self.dm, self.dt_dec, 1.0)
+        post = lats.mpe_posteriors(self.tid2phone, np.asarray([dx.tr.SIL], np.int32), ali_set=self.us_ali,
+                                   criterion="mpfe" if self.criterion == "mpe" else "smbr", tid2pdf=self.tid2pdf, one_silence_class=True,
+                                   graph_scale=1.0, acoustic_scale=self.kappa)
+        self.us_dec.acc_stats_post2(self.dm, self.dt_dec, post, self.num, self.den)
+        ok = (np.asarray(post.status) & 1) != 0
+        crit = float(np.mean(np.asarray(post.avg_acc, np.float64)[ok] / self.T[ok])) if ok.any() else 0.0
+        info = dict(crit=crit, n_ok=int(ok.sum()))
+        if check:
+            w = [x for p in post.download() for f in p for _, x in f]
+            info["pos_weight"], info["neg_weight"] = float(sum(x for x in w if x > 0)), float(-sum(x for x in w if x < 0))
         post.close()
         lats.close()
         return info
@@ -136,7 +176,7 @@ class MmiState:
         return errs, nref
 
     def close(self):
-        for h in (self.lats0, self.num, self.den, self.us_ali, self.us_dec, self.dg, self.dm, self.dt_ali, self.dt_dec):
+        for h in (self.lats0, self.ml, self.num, self.den, self.us_ali, self.us_dec, self.dg, self.dm, self.dt_ali, self.dt_dec):
             if h is not None:
                 h.close()
 
@@ -155,6 +195,7 @@ def main():
     ap.add_argument("--kappa", type=float, default=0.1, help="acoustic scale")
     ap.add_argument("--rescore", action="store_true", help="decode the denominator lattices once, rescore them in every iteration")
     ap.add_argument("--boost", type=float, default=0.0, help="boosted MMI: b of lattice-boost-ali (0: off)")
+    ap.add_argument("--criterion", choices=("mmi", "mpe", "smbr"), default="mmi", help="mpe / smbr: signed posteriors, gmm-acc-stats2")
     args = ap.parse_args()
     tm, tree, am, lexicon, test_utts = dx.train(args)
     train_utts = dx.tr.make_data(args.utts + args.test_utts, args.dim, np.random.default_rng(args.seed))[: args.mmi_utts]    # the same draw as train()
@@ -162,10 +203,24 @@ def main():
                                  opts=TrainingGraphCompilerOptions(transition_scale=1.0, self_loop_scale=1.0))
     graph = comp.compile_word_loop_graph()
     st = MmiState(khg._gpu.default_context(), tm, am, graph, train_utts, kappa=args.kappa, tau=args.tau, E=args.E, rescore=args.rescore,
-                  boost=args.boost)
+                  boost=args.boost, criterion=args.criterion)
     e0, n0 = st.wer(test_utts)
     print(f"ML model: WER {100.0 * e0 / max(n0, 1):.2f}% ({e0} / {n0}) on {len(test_utts)} held-out utterances")
     failed = 0
+    if args.criterion != "mmi":
+        for it in range(args.mmi_iters):
+            info = st.accumulate_mpe(check=False)
+            untouched = st.num.smooth_with_accum(st.tau, st.ml, st.dm)
+            r = st.update()
+            failed += r["failed"]
+            print(f"{args.criterion} iteration {it}: mean avg_acc / T = {info['crit']:.6f} over {info['n_ok']} utterances; "
+                  f"update: {r['floored']} Gaussians floored, {r['failed']} failed, {r['skipped']} skipped, {untouched} without ML counts")
+        info = st.accumulate_mpe(check=False)
+        print(f"after {args.mmi_iters} iterations: mean avg_acc / T = {info['crit']:.6f}")
+        e1, n1 = st.wer(test_utts)
+        print(f"{args.criterion} model: WER {100.0 * e1 / max(n1, 1):.2f}% ({e1} / {n1})")
+        st.close()
+        return 0 if failed == 0 and e1 <= max(e0, 0.05 * n1) else 1
     for it in range(args.mmi_iters):
         info = st.accumulate(check=False)
         untouched = st.num.smooth_with_accum(st.tau, st.num, st.dm)

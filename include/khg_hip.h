@@ -582,6 +582,26 @@ int khg_lattices_boost(khg_ctx *ctx, const khg_lattices *l, int32_t num_tids, co
                        int32_t n_sil, const int32_t *silence_phones_h, const int64_t *ali_off_h, const int32_t *ali_h,
                        const khg_utts *ali_set, float b, float max_silence_error, int32_t *status_h, khg_lattices **out);
 
+/* ---- K2M: MPE / sMBR posteriors of resident lattices (lattice-to-mpe-post, lattice-to-smbr-post) ------------------- */
+#define KHG_MPE_MPFE 0           /* an arc is correct when its phone is the reference's at that frame */
+#define KHG_MPE_SMBR 1           /* ... when its pdf is (needs tid2pdf_h) */
+/* LatticeForwardBackwardMpeVariants under one (graph_scale, acoustic_scale) pair.  The likelihood part -- statuses, tot_like_h, which
+ * arcs are live, the frames and ids listed -- is khg_lattices_posteriors', bit for bit.  Beside it runs the expected frame accuracy:
+ * acc(arc) = 1 where the arc's class (phone or pdf of its ilabel) is the class of the reference id of its frame and, with
+ * one_silence_class == 0, the arc's phone is no silence phone; with one_silence_class != 0 also where both phones are silence phones.
+ * avg_acc_h[n_utt]: the expected accuracy of a path (0 without KHG_LAT_SUCCEEDED).  The handle's arc values and weights are SIGNED:
+ * d(arc) = posterior(arc) * (expected accuracy of the paths through the arc - avg_acc); a frame's weights sum to zero.  Feed it to
+ * khg_acc_stats_post2.  tid2phone_h / tid2pdf_h [num_tids + 1] (entry 0 unused; tid2pdf_h may be NULL for KHG_MPE_MPFE).  The
+ * reference is given as khg_lattices_boost takes it, and KHG_LAT_NO_REF applies under the same three conditions; such an utterance has
+ * no frames and no entries, tot_like = -inf and avg_acc = 0 (the input handle is untouched: nothing is emptied).
+ * KHG_E_ARG before anything is launched: khg_lattices_boost's and khg_lattices_posteriors' refusals, an unknown criterion,
+ * KHG_MPE_SMBR without tid2pdf_h.  Synchronous. */
+int khg_lattices_mpe_posteriors(khg_ctx *ctx, const khg_lattices *l, int32_t num_tids, const int32_t *tid2phone_h,
+                                const int32_t *tid2pdf_h, int32_t n_sil, const int32_t *silence_phones_h,
+                                const int64_t *ali_off_h, const int32_t *ali_h, const khg_utts *ali_set, int32_t criterion,
+                                int32_t one_silence_class, float graph_scale, float acoustic_scale, int32_t *status_h,
+                                double *tot_like_h, double *avg_acc_h, khg_posteriors **out);
+
 /* ---- K3: sufficient statistics ---------------------------------------------------------- */
 /* AccumAmDiagGmm (csrc/mle-am-diag-gmm.h:93-96) + transition stats (csrc/transition-model.h:176-189)
  * as ONE contiguous fp64 device buffer (a single RCCL all-reduce sums it across GPUs =
@@ -618,6 +638,12 @@ int khg_acc_stats(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *
  * synchronising call answers KHG_E_RUNTIME.) */
 int khg_acc_stats_post(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, const khg_posteriors *p, float scale,
                        khg_accs *a);
+/* gmm-acc-stats2: signed posteriors into two blocks.  With w = (float)((double)scale * w64), an entry with w > 0 adds
+ * to `num` what khg_acc_stats_post adds with weight w, one with w < 0 adds to `den` with weight -w (statistics, transition counts and
+ * scalars alike: TransitionModel::Accumulate(fabs(w), tid) into the matching block).  khg_acc_stats_post's refusals, for both blocks;
+ * num == den: KHG_E_ARG.  Asynchronous on the context's stream. */
+int khg_acc_stats_post2(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, const khg_posteriors *p, float scale,
+                        khg_accs *num, khg_accs *den);
 
 /* Elementwise operations on whole blocks (what Kaldi's gmm-sum-accs and gmm-ismooth-stats do on files), asynchronous on the context's
  * stream.  Two blocks of one call must belong to `ctx` and have the same layout (Gaussians, dim, transition-ids), and the factor must

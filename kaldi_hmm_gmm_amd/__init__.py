@@ -35,7 +35,8 @@ from .posterior import ali_to_post, arrays_to_posts, posts_to_arrays  # noqa: F4
 from .scripts import (gmm_acc_stats, gmm_acc_stats_ali, gmm_acc_stats_ali_batch, gmm_acc_stats_batch, gmm_align_compiled,  # noqa: F401
                       gmm_align_compiled_batch, gmm_boost_silence, gmm_est, gmm_est_gmm_ebw, gmm_est_weights_ebw, gmm_info, gmm_init_mono,
                       gmm_ismooth_stats, gmm_rescore_lattice, gmm_rescore_lattice_batch, gmm_sum_accs, lattice_boost_ali,
-                      lattice_boost_ali_batch)
+                      lattice_boost_ali_batch, gmm_acc_stats2, gmm_acc_stats2_batch, lattice_to_mpe_post, lattice_to_mpe_post_batch,
+                      lattice_to_smbr_post, lattice_to_smbr_post_batch)
 from .training_graph import (TrainingGraphCompiler, TrainingGraphCompilerOptions, equal_align, generate_hmm_topo,  # noqa: F401
                              make_lexicon_fst_with_silence)
 from .transition_model import (MleTransitionUpdateConfig, TransitionInformation, TransitionModel, TransitionModelTuple,  # noqa: F401

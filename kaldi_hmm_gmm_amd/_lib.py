@@ -191,6 +191,8 @@ SIGNATURES = {
     "khg_lattices_op_status": (C.c_int, [vp, c_i32p]),
     "khg_lattices_boost": (C.c_int, [vp, vp, C.c_int32, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p, vp, C.c_float, C.c_float, c_i32p,
                                      C.POINTER(vp)]),
+    "khg_lattices_mpe_posteriors": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p, vp, C.c_int32, C.c_int32,
+                                              C.c_float, C.c_float, c_i32p, c_f64p, c_f64p, C.POINTER(vp)]),
     "khg_posteriors_sizes": (C.c_int, [vp, c_i64p, c_i64p]),
     "khg_posteriors_download": (C.c_int, [vp, vp, c_i64p, c_i32p, c_f64p, c_f64p]),
     "khg_posteriors_device_bytes": (C.c_int, [vp, c_i64p]),
@@ -207,6 +209,7 @@ SIGNATURES = {
     "khg_accs_upload": (C.c_int, [vp, vp, c_f64p]),
     "khg_acc_stats": (C.c_int, [vp, vp, vp, vp, C.c_float, vp]),
     "khg_acc_stats_post": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, vp]),
+    "khg_acc_stats_post2": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, vp, vp]),
     "khg_accs_add": (C.c_int, [vp, vp, C.c_float, vp]),
     "khg_accs_scale": (C.c_int, [vp, vp, C.c_float]),
     "khg_accs_smooth_with_accum": (C.c_int, [vp, vp, C.c_float, vp, vp, c_i32p]),

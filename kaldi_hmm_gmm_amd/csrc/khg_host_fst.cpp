@@ -377,6 +377,111 @@ LatticePosteriors Lattice::ForwardBackward(float graph_scale, float acoustic_sca
   return out;
 }
 
+LatticeMpePosteriors Lattice::ForwardBackwardMpe(const std::vector<int32_t>& tid2phone, const std::vector<int32_t>& tid2pdf,
+                                                 const std::vector<int32_t>& silence_phones, const std::vector<int32_t>& alignment, bool smbr,
+                                                 bool one_silence_class, float graph_scale, float acoustic_scale) const {
+  const std::string who = "Lattice::ForwardBackwardMpe: ";
+  KHG_REQUIRE(graph_scale >= 0.0f && acoustic_scale >= 0.0f && graph_scale != std::numeric_limits<float>::infinity() &&
+                  acoustic_scale != std::numeric_limits<float>::infinity(),
+              who + "graph_scale and acoustic_scale must be finite and >= 0");
+  KHG_REQUIRE(!tid2phone.empty(), who + "tid2phone needs an entry per transition-id, and entry 0");
+  KHG_REQUIRE(!smbr || tid2pdf.size() == tid2phone.size(), who + "sMBR needs tid2pdf, of tid2phone's length");
+  const int32_t num_tids = (int32_t)tid2phone.size() - 1;
+  for (int32_t sp : silence_phones)
+    KHG_REQUIRE(std::find(tid2phone.begin() + 1, tid2phone.end(), sp) != tid2phone.end(),
+                who + "silence phone " + std::to_string(sp) + " is the phone of no transition-id");
+  for (int32_t il : ilabel) KHG_REQUIRE(il >= 0 && il <= num_tids, who + "an arc carries an ilabel outside 0 .. num_tids");
+  const double NINF = -std::numeric_limits<double>::infinity();
+  LatticeMpePosteriors out;
+  out.status = KHG_LAT_NO_PATH;
+  out.tot_like = NINF;
+  const int N = NumStates();
+  if (N == 0 || start < 0) return out;
+  const int T = frame[(size_t)N - 1];
+  bool ref_ok = !alignment.empty() && (int64_t)alignment.size() == (int64_t)T;
+  for (int32_t x : alignment) ref_ok = ref_ok && x >= 1 && x <= num_tids;
+  if (!ref_ok) { out.status = KHG_LAT_NO_REF; return out; }
+  // the likelihood part: alpha, beta, the total and the plain arc posteriors g
+  const LatticePosteriors fb = ForwardBackward(graph_scale, acoustic_scale);
+  out.status = fb.status;
+  if (fb.status != KHG_LAT_SUCCEEDED) return out;
+  out.tot_like = fb.tot_like;
+  const double gs = graph_scale, as = acoustic_scale, tot = fb.tot_like;
+  const float FINF = std::numeric_limits<float>::infinity();
+  const int64_t A = NumArcs();
+  const std::vector<double>&alpha = fb.alpha, &beta = fb.beta;
+  std::vector<int32_t> src((size_t)A);
+  std::vector<double> w((size_t)A), acc((size_t)A, 0.0);
+  auto sil = [&](int32_t tid) { return std::find(silence_phones.begin(), silence_phones.end(), tid2phone[(size_t)tid]) != silence_phones.end(); };
+  for (int s = 0; s < N; ++s)
+    for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) {
+      src[(size_t)a] = s;
+      const double g = gs * (double)graph_cost[(size_t)a];
+      const double c = ilabel[(size_t)a] != 0 ? as * (double)acoustic_cost[(size_t)a] : 0.0;
+      w[(size_t)a] = -(g + c);
+      const int32_t il = ilabel[(size_t)a];
+      if (il == 0 || frame[(size_t)s] >= T) continue;
+      const int32_t r = alignment[(size_t)frame[(size_t)s]];
+      const bool match = smbr ? tid2pdf[(size_t)il] == tid2pdf[(size_t)r] : tid2phone[(size_t)il] == tid2phone[(size_t)r];
+      const bool ok = one_silence_class ? (match || (sil(il) && sil(r))) : (match && !sil(il));
+      acc[(size_t)a] = ok ? 1.0 : 0.0;
+    }
+  std::vector<std::vector<int32_t>> in((size_t)N);
+  for (int64_t a = 0; a < A; ++a) in[(size_t)nextstate[(size_t)a]].push_back((int32_t)a);
+  std::vector<double> fwd((size_t)N, 0.0), bwd((size_t)N, 0.0);
+  for (int s = 0; s < N; ++s) {
+    if (s == start || alpha[(size_t)s] == NINF) continue;
+    double sum = 0.0;
+    for (int32_t a : in[(size_t)s]) {
+      const double al = alpha[(size_t)src[(size_t)a]];
+      if (al == NINF) continue;
+      sum += std::exp((al + w[(size_t)a]) - alpha[(size_t)s]) * (fwd[(size_t)src[(size_t)a]] + acc[(size_t)a]);
+    }
+    fwd[(size_t)s] = sum;
+  }
+  double avg = 0.0;
+  for (int s = 0; s < N; ++s) {
+    if (frame[(size_t)s] != T || final_cost[(size_t)s] == FINF || alpha[(size_t)s] == NINF) continue;
+    avg += std::exp((alpha[(size_t)s] + -(gs * (double)final_cost[(size_t)s])) - tot) * fwd[(size_t)s];
+  }
+  for (int s = N - 1; s >= 0; --s) {
+    if (beta[(size_t)s] == NINF) continue;
+    double sum = 0.0;
+    for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) {
+      const double be = beta[(size_t)nextstate[(size_t)a]];
+      if (be == NINF) continue;
+      sum += std::exp((w[(size_t)a] + be) - beta[(size_t)s]) * (acc[(size_t)a] + bwd[(size_t)nextstate[(size_t)a]]);
+    }
+    bwd[(size_t)s] = sum;
+  }
+  out.avg_acc = avg;
+  out.arc_post.assign((size_t)A, 0.0);
+  std::vector<char> live((size_t)A, 0);
+  for (int64_t a = 0; a < A; ++a) {
+    const double al = alpha[(size_t)src[(size_t)a]], be = beta[(size_t)nextstate[(size_t)a]];
+    if (al == NINF || be == NINF) continue;
+    live[(size_t)a] = 1;
+    const double g = std::exp(((al + w[(size_t)a]) + be) - tot);
+    out.arc_post[(size_t)a] = g * (((fwd[(size_t)src[(size_t)a]] + acc[(size_t)a]) + bwd[(size_t)nextstate[(size_t)a]]) - avg);
+  }
+  out.post.assign((size_t)T, {});
+  for (int64_t a = 0; a < A; ++a) {
+    if (!live[(size_t)a] || ilabel[(size_t)a] == 0) continue;
+    const int t = frame[(size_t)src[(size_t)a]];
+    if (t < 0 || t >= T) continue;
+    auto& row = out.post[(size_t)t];
+    auto it = std::find_if(row.begin(), row.end(), [&](const std::pair<int32_t, double>& e) { return e.first == ilabel[(size_t)a]; });
+    if (it == row.end()) row.emplace_back(ilabel[(size_t)a], out.arc_post[(size_t)a]);
+    else it->second += out.arc_post[(size_t)a];
+  }
+  for (auto& row : out.post) std::sort(row.begin(), row.end(), [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) { return a.first < b.first; });
+  out.alpha = alpha;
+  out.beta = beta;
+  out.acc_fwd = std::move(fwd);
+  out.acc_bwd = std::move(bwd);
+  return out;
+}
+
 std::shared_ptr<Lattice> Lattice::Rescore(const std::function<float(int, int)>& loglike, float acoustic_scale) const {
   KHG_REQUIRE(std::isfinite(acoustic_scale), "Lattice::Rescore: acoustic_scale must be finite");
   auto r = std::make_shared<Lattice>(*this);

@@ -123,6 +123,14 @@ struct LatticePosteriors {
   std::vector<std::vector<std::pair<int32_t, double>>> post;
 };
 
+// Lattice::ForwardBackwardMpe (what khg_lattices_mpe_posteriors gives for one lattice): ForwardBackward's fields -- here
+// arc_post holds the SIGNED values d and post their per-frame sums -- plus the expected accuracy of a path and the forward / backward
+// accuracies per state.  KHG_LAT_NO_REF: the alignment is empty, not of the lattice's frame count, or holds an id outside 1 .. num_tids.
+struct LatticeMpePosteriors : LatticePosteriors {
+  double avg_acc = 0.0;
+  std::vector<double> acc_fwd, acc_bwd;      // A, B
+};
+
 // The fst::VectorFst<LatticeArc> LatticeSimpleDecoder::GetRawLattice builds (csrc/lattice-simple-decoder.cc:654-735), as the flat arrays
 // khg_lattices_download hands back: a state per surviving token, numbered by frame, then by graph state (:684-690); state s owns arcs
 // arc_begin[s] .. arc_begin[s + 1], one per surviving forward link in the order of the graph's arcs in its state (:700-722); the last
@@ -166,6 +174,12 @@ class Lattice {
   // -graph_scale * final_cost on the last frame.  Every arc must go to a higher state: an epsilon arc that does not gives
   // KHG_LAT_EPS_LOOP (checked on the structure, before any arithmetic).  Each log-sum is max-then-sum over a state's arcs in arc order.
   LatticePosteriors ForwardBackward(float graph_scale = 1.0f, float acoustic_scale = 1.0f) const;
+  // LatticeForwardBackwardMpeVariants: ForwardBackward's likelihood part, and beside it the expected frame accuracy in
+  // the linear domain, serially in state order.  smbr: an arc matches the reference by pdf (tid2pdf), else by phone; the alignment has
+  // one id per frame.  tid2phone / tid2pdf have an entry per transition-id and entry 0 (tid2pdf may be empty unless smbr).
+  LatticeMpePosteriors ForwardBackwardMpe(const std::vector<int32_t>& tid2phone, const std::vector<int32_t>& tid2pdf,
+                                          const std::vector<int32_t>& silence_phones, const std::vector<int32_t>& alignment, bool smbr,
+                                          bool one_silence_class, float graph_scale = 1.0f, float acoustic_scale = 1.0f) const;
   // gmm-rescore-lattice (what khg_lattices_rescore gives for one lattice): a copy in which every arc with ilabel != 0
   // leaving a state of frame t has acoustic_cost = -(acoustic_scale * loglike(t, ilabel)), one float multiply and a sign; everything
   // else as stored (tot_cost / extra_cost are then stale)

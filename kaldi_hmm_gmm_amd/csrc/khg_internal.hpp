@@ -374,5 +374,7 @@ struct PostInfo { const khg_ctx* ctx; int32_t U, max_tid; const int64_t *frame_o
 void posteriors_info(const khg_posteriors* p, PostInfo* out);
 // every entry of the handle, in utterance / frame / entry order -> e_row (set_frame_off_d[u] + t), e_tid, e_w = (float)(scale * w64);
 // an id outside 1 .. num_tids or a weight that overflows a float: e_tid = 0, e_w = 0 and the context's error word.  Asynchronous.
+// sign (khg_acc_stats_post2): 0 every entry as it is; +1 the positive ones (the others get weight 0, which the key pass drops); -1 the
+// negative ones, negated.
 int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set_frame_off_d, double scale, int32_t num_tids,
-                       int32_t* e_row, int32_t* e_tid, float* e_w);
+                       int32_t* e_row, int32_t* e_tid, float* e_w, int sign = 0);

@@ -555,14 +555,18 @@ extern "C" int khg_acc_stats_reduce(khg_ctx* ctx, const khg_model* m, const khg_
   return acc_stats_impl(ctx, m, tm, u, weight, acc, comm, nparts <= 0 ? 4 : nparts);
 }
 
-// gmm-acc-stats: every check on the host first, then flatten -> bucket -> accumulate on the context's stream.
-extern "C" int khg_acc_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale, khg_accs* acc) {
-  const std::string who = "khg_acc_stats_post: ";
-  if (ctx_dead(ctx) || !m || !tm || !u || !p || !acc) return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  { int rf = utts_foreign_ctx(ctx, u, "khg_acc_stats_post"); if (rf) return rf; }
+// gmm-acc-stats and gmm-acc-stats2 (7k): every check on the host first, then flatten -> bucket -> accumulate on the
+// context's stream -- once into `acc`, or (acc2 != nullptr) the positive entries into `acc` and the negated negative ones into `acc2`.
+static int acc_stats_post_impl(const std::string& name, khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale,
+                               khg_accs* acc, khg_accs* acc2, bool two) {
+  const std::string who = name + ": ";
+  if (ctx_dead(ctx) || !m || !tm || !u || !p || !acc || (two && !acc2)) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  if (two && acc == acc2) return khg_set_error(KHG_E_ARG, who + "num_accs and den_accs are the same block");
+  { int rf = utts_foreign_ctx(ctx, u, name.c_str()); if (rf) return rf; }
   PostInfo pi;
   posteriors_info(p, &pi);
-  if (pi.ctx != ctx || m->ctx != ctx || tm->ctx != ctx || acc->ctx != ctx || u->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (pi.ctx != ctx || m->ctx != ctx || tm->ctx != ctx || acc->ctx != ctx || u->ctx != ctx || (two && acc2->ctx != ctx))
+    return khg_set_error(KHG_E_ARG, who + "a handle of another context");
   if (pi.U != u->n_utt)
     return khg_set_error(KHG_E_ARG, who + "the posteriors hold " + std::to_string(pi.U) + " utterances, the set " + std::to_string(u->n_utt));
   for (int i = 0; i < pi.U; ++i) {
@@ -570,7 +574,8 @@ extern "C" int khg_acc_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm
     if (tp != 0 && tp != ts)
       return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(i) + " has " + std::to_string(tp) + " frames of posteriors and " + std::to_string(ts) + " frames of features");
   }
-  if (m->D != u->D || acc->D != m->D || acc->sumG != m->sumG || acc->num_tids != tm->num_tids)
+  if (m->D != u->D || acc->D != m->D || acc->sumG != m->sumG || acc->num_tids != tm->num_tids ||
+      (two && (acc2->D != m->D || acc2->sumG != m->sumG || acc2->num_tids != tm->num_tids)))
     return khg_set_error(KHG_E_ARG, who + "accumulator / model / feature dimensions do not match");
   if (tm->max_pdf >= m->P) return khg_set_error(KHG_E_ARG, who + "transition model refers to pdf-ids the model does not have");
   if (!std::isfinite(scale)) return khg_set_error(KHG_E_ARG, who + "scale must be finite");
@@ -600,7 +605,18 @@ extern "C" int khg_acc_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm
     if (rc) return rc;
     u->pe_P = m->P;
   }
-  rc = posteriors_flatten(ctx, p, u->frame_off_d, (double)scale, tm->num_tids, u->pe_row_d, u->pe_tid_d, u->pe_w_d);
-  if (rc) return rc;
-  return acc_stats_pass(ctx, m, tm, u, 1.0f, acc, nullptr, 1, -1, E);
+  // (two blocks: the flattened entries are made twice, once per sign; the stream orders the second flatten behind the first pass)
+  rc = posteriors_flatten(ctx, p, u->frame_off_d, (double)scale, tm->num_tids, u->pe_row_d, u->pe_tid_d, u->pe_w_d, two ? 1 : 0);
+  if (!rc) rc = acc_stats_pass(ctx, m, tm, u, 1.0f, acc, nullptr, 1, -1, E);
+  if (rc || !two) return rc;
+  rc = posteriors_flatten(ctx, p, u->frame_off_d, (double)scale, tm->num_tids, u->pe_row_d, u->pe_tid_d, u->pe_w_d, -1);
+  if (!rc) rc = acc_stats_pass(ctx, m, tm, u, 1.0f, acc2, nullptr, 1, -1, E);
+  return rc;
+}
+extern "C" int khg_acc_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale, khg_accs* acc) {
+  return acc_stats_post_impl("khg_acc_stats_post", ctx, m, tm, u, p, scale, acc, nullptr, false);
+}
+extern "C" int khg_acc_stats_post2(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale, khg_accs* num_accs,
+                                   khg_accs* den_accs) {
+  return acc_stats_post_impl("khg_acc_stats_post2", ctx, m, tm, u, p, scale, num_accs, den_accs, true);
 }

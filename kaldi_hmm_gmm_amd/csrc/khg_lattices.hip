@@ -18,6 +18,7 @@
 #include "khg_k2_lattice_post.hip.inc"
 #include "khg_k1_cells.hip.inc"
 #include "khg_k2_lattice_rescore.hip.inc"
+#include "khg_k2_lattice_mpe.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // The raw lattices of one batch (khg_decode_lattice_simple_raw, khg_decode_lattice_faster_raw): per chunk of scratch slices one
@@ -1255,8 +1256,17 @@ __global__ __launch_bounds__(256) void k3_post_flatten(PostFlatArgs p) {
     p.e_row[e] = (int32_t)row; p.e_tid[e] = tid; p.e_w[e] = w;
   }
 }
+// khg_acc_stats_post2's sign selection over a chunk's flattened weights, in place: the entries of the wanted sign keep |w|, the others
+// get 0.  A kernel of its own, so that what khg_acc_stats_post launches stays the code it was.
+__global__ __launch_bounds__(256) void k3_post_sign(float* __restrict__ e_w, int64_t ne, int32_t sign) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < ne; e += stride) {
+    const float w = e_w[e];
+    e_w[e] = sign > 0 ? (w > 0.0f ? w : 0.0f) : (w < 0.0f ? -w : 0.0f);
+  }
+}
 int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set_frame_off_d, double scale, int32_t num_tids, int32_t* e_row,
-                       int32_t* e_tid, float* e_w) {
+                       int32_t* e_tid, float* e_w, int sign) {
   if (!p->frame_off_d) return KHG_OK;               // a handle of no utterances
   KernelTimer kt(ctx, "k3_post_flatten");
   for (const PostChunk& c : p->chunks) {
@@ -1270,6 +1280,10 @@ int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set
     a.e_row = e_row + e0; a.e_tid = e_tid + e0; a.e_w = e_w + e0; a.err_flag = ctx->err_flag_d;
     KHG_LAUNCH(ctx, k3_post_flatten, dim3((unsigned)std::min<int64_t>(4096, (c.ne + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
+    if (sign != 0) {
+      KHG_LAUNCH(ctx, k3_post_sign, dim3((unsigned)std::min<int64_t>(4096, (c.ne + 255) / 256)), dim3(256), 0, ctx->stream, a.e_w, c.ne, (int32_t)sign);
+      HIPCHK(hipGetLastError());
+    }
   }
   return KHG_OK;
 }
@@ -1465,23 +1479,27 @@ extern "C" int khg_lattices_rescore(khg_ctx* ctx, const khg_model* m, const khg_
   return KHG_OK;
 }
 
-extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t num_tids, const int32_t* tid2phone_h, int32_t n_sil,
-                                  const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set, float b,
-                                  float max_silence_error, int32_t* status_h, khg_lattices** out) {
-  const std::string who = "khg_lattices_boost: ";
-  if (ctx_dead(ctx) || !lc || !out || num_tids < 0 || !tid2phone_h || n_sil < 0 || (n_sil > 0 && !silence_phones_h))
-    return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  *out = nullptr;
-  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+namespace {
+// The reference of khg_lattices_boost and khg_lattices_mpe_posteriors: per utterance an alignment of transition-ids, from host arrays or
+// resident in an utterance set, and the table 2 * class + (silence) per transition-id.  `drop` marks the utterances without a usable
+// one: no alignment, one whose length is not the lattice's frame count, an id outside 1 .. num_tids.
+struct LatRef {
+  DevBlocks dv;
+  const int32_t* ali_d = nullptr; const int64_t* aoff_d = nullptr;
+  int32_t* tab_d = nullptr;
+  std::vector<int32_t> tab;
+  std::vector<char> drop;
+};
+// the host-only checks: every refusal is KHG_E_ARG before any launch.  cls_h[t] is the class of transition-id t (boost, MPFE: its phone)
+int lat_ref_check(const std::string& who, khg_ctx* ctx, const khg_lattices* l, int32_t num_tids, const int32_t* cls_h, const int32_t* tid2phone_h, int32_t n_sil,
+                  const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set, LatRef* r) {
   const bool host_ali = ali_off_h && ali_h;
   if ((ali_off_h != nullptr) != (ali_h != nullptr) || host_ali == (ali_set != nullptr))
     return khg_set_error(KHG_E_ARG, who + "give either the host alignment (ali_off_h and ali_h) or ali_set, not both and not neither");
-  if (!std::isfinite(b) || !std::isfinite(max_silence_error)) return khg_set_error(KHG_E_ARG, who + "b and max_silence_error must be finite");
-  khg_lattices* l = const_cast<khg_lattices*>(lc);
   const int U = l->U;
   khg_utts* as = const_cast<khg_utts*>(ali_set);
   if (as) {
-    { int rf = utts_foreign_ctx(ctx, as, "khg_lattices_boost"); if (rf) return rf; }
+    { int rf = utts_foreign_ctx(ctx, as, who.substr(0, who.size() - 2).c_str()); if (rf) return rf; }
     if (as->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
     if (as->n_utt != U) return khg_set_error(KHG_E_ARG, who + "the lattices hold " + std::to_string(U) + " utterances, ali_set " + std::to_string(as->n_utt));
     if (!as->ali_valid) return khg_set_error(KHG_E_ARG, who + "ali_set has no resident alignment: call khg_align (or khg_ali_upload) first");
@@ -1490,57 +1508,55 @@ extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t 
     for (int i = 0; i < U; ++i)
       if (ali_off_h[i + 1] < ali_off_h[i]) return khg_set_error(KHG_E_ARG, who + "ali_off_h decreases at utterance " + std::to_string(i));
   }
-  // the phone map and the silence set as one table: 2 * phone + (silence)
-  std::vector<int32_t> tab((size_t)num_tids + 1, 0);
+  // the class map and the silence set as one table: 2 * class + (silence)
+  r->tab.assign((size_t)num_tids + 1, 0);
   for (int t = 1; t <= num_tids; ++t) {
     if (tid2phone_h[t] < 0 || tid2phone_h[t] > INT32_MAX / 2) return khg_set_error(KHG_E_ARG, who + "tid2phone[" + std::to_string(t) + "] out of range");
-    tab[(size_t)t] = 2 * tid2phone_h[t];
+    if (cls_h[t] < 0 || cls_h[t] > INT32_MAX / 2) return khg_set_error(KHG_E_ARG, who + "tid2pdf[" + std::to_string(t) + "] out of range");
+    r->tab[(size_t)t] = 2 * cls_h[t];
   }
   for (int k = 0; k < n_sil; ++k) {
     bool seen = false;
     for (int t = 1; t <= num_tids; ++t)
-      if (tid2phone_h[t] == silence_phones_h[k]) { tab[(size_t)t] |= 1; seen = true; }
+      if (tid2phone_h[t] == silence_phones_h[k]) { r->tab[(size_t)t] |= 1; seen = true; }
     if (!seen) return khg_set_error(KHG_E_ARG, who + "silence phone " + std::to_string(silence_phones_h[k]) + " is the phone of no transition-id");
   }
-  LatPtr res;
-  std::vector<char> drop((size_t)U, 0);
-  if (U == 0) {
-    int rc = lat_clone(ctx, l, drop, &res);
-    if (rc) return rc;
-    *out = res.release();
-    return KHG_OK;
-  }
-  int rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (!rc && as) rc = wait_ali(ctx, as);
+  r->drop.assign((size_t)U, 0);
+  return KHG_OK;
+}
+// the device half (U > 0, after lat_meta): the table and the alignment on the device, the ids and the lattices' labels checked there
+int lat_ref_device(const std::string& who, khg_ctx* ctx, khg_lattices* l, int32_t num_tids, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set,
+                   LatRef* r) {
+  const int U = l->U;
+  khg_utts* as = const_cast<khg_utts*>(ali_set);
+  const std::string name = who.substr(0, who.size() - 2);
+  int rc = as ? wait_ali(ctx, as) : KHG_OK;
   if (rc) return rc;
-  DevBlocks dv;
-  const int32_t* ali_d = nullptr; const int64_t* aoff_d = nullptr;
-  int32_t *flag_d, *tab_d;
-  if ((rc = dv.alloc(U + 1, &flag_d)) || (rc = dv.alloc((int64_t)tab.size(), &tab_d))) return rc;      // [U]: the label word
+  int32_t* flag_d;
+  if ((rc = r->dv.alloc(U + 1, &flag_d)) || (rc = r->dv.alloc((int64_t)r->tab.size(), &r->tab_d))) return rc;      // [U]: the label word
   HIPCHK(hipMemsetAsync(flag_d, 0, 4 * ((size_t)U + 1), ctx->stream));
-  HIPCHK(hipMemcpyAsync(tab_d, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(r->tab_d, r->tab.data(), 4 * r->tab.size(), hipMemcpyHostToDevice, ctx->stream));
   // what the host knows: the alignment's length against the lattice's frame count (and, of a host alignment, its ids)
   for (int i = 0; i < U; ++i) {
     const int64_t tl = l->ali_off[(size_t)i + 1] - l->ali_off[(size_t)i];
     const int64_t ta = as ? as->frame_off[(size_t)i + 1] - as->frame_off[(size_t)i] : ali_off_h[i + 1] - ali_off_h[i];
-    if (ta == 0 || ta != tl) drop[(size_t)i] = 1;
-    if (!as && !drop[(size_t)i])
+    if (ta == 0 || ta != tl) r->drop[(size_t)i] = 1;
+    if (!as && !r->drop[(size_t)i])
       for (int64_t k = ali_off_h[i]; k < ali_off_h[i + 1]; ++k)
-        if (ali_h[k] < 1 || ali_h[k] > num_tids) { drop[(size_t)i] = 1; break; }
+        if (ali_h[k] < 1 || ali_h[k] > num_tids) { r->drop[(size_t)i] = 1; break; }
   }
   if (as) {
-    ali_d = as->ali_d; aoff_d = as->frame_off_d;
+    r->ali_d = as->ali_d; r->aoff_d = as->frame_off_d;
     KernelTimer kt(ctx, "k2x_ali_check");
-    KHG_LAUNCH(ctx, k2x_ali_check, dim3((unsigned)U), dim3(K2X_NT), 0, ctx->stream, ali_d, aoff_d, num_tids, flag_d);
+    KHG_LAUNCH(ctx, k2x_ali_check, dim3((unsigned)U), dim3(K2X_NT), 0, ctx->stream, r->ali_d, r->aoff_d, num_tids, flag_d);
     HIPCHK(hipGetLastError());
   } else {
     int32_t* a_d; int64_t* o_d;
     const int64_t n = ali_off_h[U];
-    if ((rc = dv.alloc(std::max<int64_t>(n, 1), &a_d)) || (rc = dv.alloc(U + 1, &o_d))) return rc;
+    if ((rc = r->dv.alloc(std::max<int64_t>(n, 1), &a_d)) || (rc = r->dv.alloc(U + 1, &o_d))) return rc;
     if (n > 0) HIPCHK(hipMemcpyAsync(a_d, ali_h, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(o_d, ali_off_h, 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
-    ali_d = a_d; aoff_d = o_d;
+    r->ali_d = a_d; r->aoff_d = o_d;
   }
   {
     KernelTimer kt(ctx, "k2x_label_check");
@@ -1554,13 +1570,41 @@ extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t 
   }
   std::vector<int32_t> flag((size_t)U + 1);
   HIPCHK(hipMemcpyAsync(flag.data(), flag_d, 4 * ((size_t)U + 1), hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = check_err_flag(ctx, "khg_lattices_boost"))) return rc;      // synchronises (the caller's arrays are free again)
+  if ((rc = check_err_flag(ctx, name.c_str()))) return rc;      // synchronises (the caller's arrays are free again)
   if (flag[(size_t)U]) return khg_set_error(KHG_E_ARG, who + "a lattice arc carries an ilabel outside 0 .. num_tids = " + std::to_string(num_tids));
-  for (int i = 0; i < U; ++i) drop[(size_t)i] = drop[(size_t)i] || flag[(size_t)i] != 0;
-  if ((rc = lat_clone(ctx, l, drop, &res)) || (rc = lat_meta(ctx, res.get()))) return rc;
+  for (int i = 0; i < U; ++i) r->drop[(size_t)i] = r->drop[(size_t)i] || flag[(size_t)i] != 0;
+  return KHG_OK;
+}
+}  // namespace
+
+extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t num_tids, const int32_t* tid2phone_h, int32_t n_sil,
+                                  const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set, float b,
+                                  float max_silence_error, int32_t* status_h, khg_lattices** out) {
+  const std::string who = "khg_lattices_boost: ";
+  if (ctx_dead(ctx) || !lc || !out || num_tids < 0 || !tid2phone_h || n_sil < 0 || (n_sil > 0 && !silence_phones_h))
+    return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  *out = nullptr;
+  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (!std::isfinite(b) || !std::isfinite(max_silence_error)) return khg_set_error(KHG_E_ARG, who + "b and max_silence_error must be finite");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  LatRef ref;
+  int rc = lat_ref_check(who, ctx, l, num_tids, tid2phone_h, tid2phone_h, n_sil, silence_phones_h, ali_off_h, ali_h, ali_set, &ref);
+  if (rc) return rc;
+  LatPtr res;
+  if (U == 0) {
+    if ((rc = lat_clone(ctx, l, ref.drop, &res))) return rc;
+    *out = res.release();
+    return KHG_OK;
+  }
+  rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc) rc = lat_ref_device(who, ctx, l, num_tids, ali_off_h, ali_h, ali_set, &ref);
+  if (rc) return rc;
+  if ((rc = lat_clone(ctx, l, ref.drop, &res)) || (rc = lat_meta(ctx, res.get()))) return rc;
   K2xBoost p;
   std::memset(&p, 0, sizeof(p));
-  p.ali = ali_d; p.ali_off = aoff_d; p.tab = tab_d; p.neg_b = -b; p.max_sil_err = max_silence_error;
+  p.ali = ref.ali_d; p.ali_off = ref.aoff_d; p.tab = ref.tab_d; p.neg_b = -b; p.max_sil_err = max_silence_error;
   {
     KernelTimer kt(ctx, "k2x_boost");
     for (const LatChunk& c : res->chunks) {
@@ -1570,9 +1614,118 @@ extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t 
       HIPCHK(hipGetLastError());
     }
   }
-  if ((rc = check_err_flag(ctx, "khg_lattices_boost"))) return rc;      // synchronises: the scratch goes with `dv`
-  k2x_status(l, drop, res.get());
+  if ((rc = check_err_flag(ctx, "khg_lattices_boost"))) return rc;      // synchronises: the scratch goes with `ref`
+  k2x_status(l, ref.drop, res.get());
   if (status_h) std::copy(res->op_status.begin(), res->op_status.end(), status_h);
+  *out = res.release();
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2M: MPE / sMBR posteriors (khg_k2_lattice_mpe.hip.inc): khg_lattices_posteriors' launches with k2_lattice_post_mpe in
+// k2_lattice_post_fb's place; the handle's arc_post and weights are the signed values.
+extern "C" int khg_lattices_mpe_posteriors(khg_ctx* ctx, const khg_lattices* lc, int32_t num_tids, const int32_t* tid2phone_h, const int32_t* tid2pdf_h,
+                                           int32_t n_sil, const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h,
+                                           const khg_utts* ali_set, int32_t criterion, int32_t one_silence_class, float graph_scale, float acoustic_scale,
+                                           int32_t* status_h, double* tot_like_h, double* avg_acc_h, khg_posteriors** out) {
+  const std::string who = "khg_lattices_mpe_posteriors: ";
+  if (ctx_dead(ctx) || !lc || !out || num_tids < 0 || !tid2phone_h || n_sil < 0 || (n_sil > 0 && !silence_phones_h))
+    return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  *out = nullptr;
+  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (criterion != KHG_MPE_MPFE && criterion != KHG_MPE_SMBR) return khg_set_error(KHG_E_ARG, who + "unknown criterion " + std::to_string(criterion));
+  if (criterion == KHG_MPE_SMBR && !tid2pdf_h) return khg_set_error(KHG_E_ARG, who + "KHG_MPE_SMBR needs tid2pdf_h");
+  if (bad_scale(graph_scale) || bad_scale(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "graph_scale and acoustic_scale must be finite and >= 0");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  LatRef ref;
+  int rc = lat_ref_check(who, ctx, l, num_tids, criterion == KHG_MPE_SMBR ? tid2pdf_h : tid2phone_h, tid2phone_h, n_sil, silence_phones_h, ali_off_h, ali_h,
+                         ali_set, &ref);
+  if (rc) return rc;
+  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
+  res->U = U; res->ctx = ctx;
+  res->frame_off.assign((size_t)U + 1, 0);
+  res->entry_off.assign((size_t)U + 1, 0);
+  res->arc_off = l->arc_off;
+  if (U == 0) { *out = res.release(); return KHG_OK; }
+  rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc) rc = lat_ref_device(who, ctx, l, num_tids, ali_off_h, ali_h, ali_set, &ref);
+  if (!rc) rc = lat_index(ctx, l);
+  if (rc) return rc;
+  DevBlocks dv;
+  int32_t *status_d, *no_ref_d; double *tot_d, *avg_d; int64_t* ali_off_d;
+  if ((rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &tot_d)) || (rc = dv.alloc(U, &avg_d)) || (rc = dv.alloc(U, &no_ref_d)) ||
+      (rc = dv.alloc(U + 1, &ali_off_d)))
+    return rc;
+  std::vector<int32_t> no_ref(ref.drop.begin(), ref.drop.end());
+  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(no_ref_d, no_ref.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<int64_t> fo, eo;
+  for (size_t k = 0; k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    PoMpeArgs q;
+    std::memset(&q, 0, sizeof(q));
+    PoArgs& p = q.po;
+    lat_chunk_args(l, c, &p.lo);
+    p.lo.lds_bytes = lat_chunk_lds(ctx, l, c, 40);       // alpha, beta, the Jacobi row, A and B (doubles) beside the staged lattice
+    p.lo.status = status_d; p.lo.ali_off = ali_off_d; p.tot = tot_d;
+    p.in_begin = l->idx_d[k]; p.in_arc = l->idx_d[k] + c.ns + c.n; p.arc_src = l->idx_d[k] + c.ns + c.n + c.na;
+    p.gs = (double)graph_scale; p.as = (double)acoustic_scale;
+    p.f_base = l->ali_off[(size_t)c.u0];
+    q.ref = ref.ali_d; q.ref_off = ref.aoff_d; q.tab = ref.tab_d; q.no_ref = no_ref_d; q.avg = avg_d; q.one_silence_class = one_silence_class != 0;
+    const int64_t nfr = l->ali_off[(size_t)c.u0 + c.n] - p.f_base;
+    const int64_t cells = std::max<int64_t>(c.ns, 1), arcs = std::max<int64_t>(c.na, 1);
+    if ((rc = dv.alloc(cells, &p.alpha)) || (rc = dv.alloc(cells, &p.beta)) || (rc = dv.alloc(cells, &p.row)) || (rc = dv.alloc(cells, &q.accA)) ||
+        (rc = dv.alloc(cells, &q.accB)) || (rc = dv.alloc(arcs, &p.flag)) || (rc = dv.alloc(arcs, &p.rank)) ||
+        (rc = dv.alloc(std::max<int64_t>(nfr, 1), &p.fcnt)) || (rc = dv.alloc(nfr + 2 * (int64_t)c.n, &p.fstate)) ||
+        (rc = dv.alloc(2 * (int64_t)c.n, &p.lo.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.lo.utt_off)))
+      return rc;
+    PostChunk pc;
+    pc.u0 = c.u0; pc.n = c.n; pc.na = c.na;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&pc.arc_post), (size_t)(8 * arcs)));
+    res->chunks.push_back(pc);
+    res->bytes += 8 * c.na;
+    p.arc_post = pc.arc_post;
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_mpe");
+      KHG_LAUNCH(ctx, k2_lattice_post_mpe, dim3((unsigned)c.n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, q);
+      HIPCHK(hipGetLastError());
+    }
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_scan");       // frames at [b], entries at [n + 1 + b]
+      KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, p.lo.utt_tot, p.lo.utt_off, c.n);
+      HIPCHK(hipGetLastError());
+    }
+    rc = read_pair_offsets(ctx, p.lo.utt_off, c.n, &fo, &eo);        // the one synchronisation that sizes the output
+    if (!rc) rc = add_chunk_counts("khg_lattices_mpe_posteriors", c.u0, fo, eo, &res->frame_off, &res->entry_off);
+    if (rc) return rc;
+    PostChunk& pq = res->chunks.back();
+    pq.nf = fo[(size_t)c.n]; pq.ne = eo[(size_t)c.n];
+    pq.o_weight = (8 * (pq.nf + 1) + 255) & ~int64_t(255);
+    pq.o_tid = pq.o_weight + ((8 * pq.ne + 255) & ~int64_t(255));
+    const int64_t total = pq.o_tid + 4 * pq.ne;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&pq.buf), (size_t)std::max<int64_t>(total, 16)));
+    res->bytes += total;
+    p.entry_begin = reinterpret_cast<int64_t*>(pq.buf); p.weight = reinterpret_cast<double*>(pq.buf + pq.o_weight);
+    p.tid = reinterpret_cast<int32_t*>(pq.buf + pq.o_tid);
+    {
+      KernelTimer kt(ctx, "k2_lattice_post_fill");       // the summed array is arc_post: here the signed values
+      KHG_LAUNCH(ctx, k2_lattice_post_fill, dim3((unsigned)c.n, stripes(chunk_max(l->arc_off, c), PO_NT, c.n)), dim3(PO_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  std::vector<int32_t> st((size_t)U);
+  std::vector<double> tl((size_t)U), av((size_t)U);
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(tl.data(), tot_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(av.data(), avg_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  rc = check_err_flag(ctx, "khg_lattices_mpe_posteriors");     // synchronises: the scratch goes with `dv` and `ref`
+  if (rc) return rc;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (tot_like_h) std::copy(tl.begin(), tl.end(), tot_like_h);
+  if (avg_acc_h) std::copy(av.begin(), av.end(), avg_acc_h);
+  if ((rc = post_frame_off_upload(ctx, res.get()))) return rc;
   *out = res.release();
   return KHG_OK;
 }

@@ -361,6 +361,25 @@ void BindLattice(py::module_& m) {
         d["post"] = post;
         return d;
       }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      // what DeviceLattices.mpe_posteriors gives for this lattice: forward_backward's keys -- arc_post and post hold the
+      // signed values -- plus avg_acc, acc_fwd (A) and acc_bwd (B)
+      .def("forward_backward_mpe", [](const Lattice& l, std::vector<int32_t> tid2phone, std::vector<int32_t> silence_phones, std::vector<int32_t> alignment,
+                                      const std::string& criterion, std::vector<int32_t> tid2pdf, bool one_silence_class, float gs, float as) {
+        if (criterion != "smbr" && criterion != "mpfe") throw Error("Lattice.forward_backward_mpe: criterion is \"smbr\" or \"mpfe\"");
+        const LatticeMpePosteriors r = l.ForwardBackwardMpe(tid2phone, tid2pdf, silence_phones, alignment, criterion == "smbr", one_silence_class, gs, as);
+        py::dict d;
+        d["status"] = r.status; d["tot_like"] = r.tot_like; d["arc_post"] = Vec1(r.arc_post); d["alpha"] = Vec1(r.alpha); d["beta"] = Vec1(r.beta);
+        d["avg_acc"] = r.avg_acc; d["acc_fwd"] = Vec1(r.acc_fwd); d["acc_bwd"] = Vec1(r.acc_bwd);
+        py::list post;
+        for (const auto& row : r.post) {
+          py::list e;
+          for (const auto& x : row) e.append(py::make_tuple(x.first, x.second));
+          post.append(e);
+        }
+        d["post"] = post;
+        return d;
+      }, py::arg("tid2phone"), py::arg("silence_phones"), py::arg("alignment"), py::arg("criterion") = "smbr", py::arg("tid2pdf") = std::vector<int32_t>(),
+         py::arg("one_silence_class") = true, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       // gmm-rescore-lattice on the host (what DeviceLattices.rescore gives for this lattice): loglikes is a [num_tids + 1][T] array of
       // log-likelihoods by (transition-id, frame), or a callable (frame, transition-id) -> float
       .def("rescore", [](const Lattice& l, py::object loglikes, float acoustic_scale) {
@@ -580,6 +599,56 @@ void BindLattice(py::module_& m) {
         return r;
       }, py::arg("tid2phone"), py::arg("silence_phones"), py::arg("alignment") = py::none(), py::arg("ali_set") = py::none(), py::arg("b") = 0.1f,
          py::arg("max_silence_error") = 0.0f)
+      // lattice-to-mpe-post / lattice-to-smbr-post -> DevicePosteriors with SIGNED weights, carrying .avg_acc (the expected
+      // frame accuracy per utterance).  The reference as boost takes it: alignment (a list of arrays) or ali_set
+      .def("mpe_posteriors", [](PyDeviceLattices& d, Arr<int32_t> tid2phone, Arr<int32_t> silence_phones, py::object alignment, py::object ali_set,
+                                const std::string& criterion, py::object tid2pdf, bool one_silence_class, float gs, float as) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        if (tid2phone.ndim() != 1 || tid2phone.shape(0) < 1 || silence_phones.ndim() != 1)
+          throw Error("DeviceLattices.mpe_posteriors: tid2phone [num_tids + 1] and silence_phones are flat arrays");
+        int crit;
+        if (criterion == "smbr") crit = KHG_MPE_SMBR;
+        else if (criterion == "mpfe") crit = KHG_MPE_MPFE;
+        else throw Error("DeviceLattices.mpe_posteriors: criterion is \"smbr\" or \"mpfe\"");
+        Arr<int32_t> t2pdf;
+        const bool has_pdf = !tid2pdf.is_none();
+        if (has_pdf) {
+          t2pdf = tid2pdf.cast<Arr<int32_t>>();
+          if (t2pdf.ndim() != 1 || t2pdf.shape(0) != tid2phone.shape(0)) throw Error("DeviceLattices.mpe_posteriors: tid2pdf has tid2phone's length");
+        }
+        const auto so = LatSizes(d);
+        const int U = (int)so.first.size() - 1;
+        std::vector<int64_t> aoff;
+        std::vector<int32_t> ali;
+        if (!alignment.is_none()) {
+          py::list al = alignment.cast<py::list>();
+          if ((int)al.size() != U) throw Error("DeviceLattices.mpe_posteriors: " + std::to_string(al.size()) + " alignments for " + std::to_string(U) + " lattices");
+          aoff.assign(1, 0);
+          for (py::handle h : al) {
+            Arr<int32_t> a = py::reinterpret_borrow<py::object>(h).cast<Arr<int32_t>>();
+            ali.insert(ali.end(), a.data(), a.data() + a.size());
+            aoff.push_back((int64_t)ali.size());
+          }
+          ali.push_back(0);      // (never a NULL array)
+        }
+        const khg_utts* sh = ali_set.is_none() ? nullptr : reinterpret_cast<const khg_utts*>(ali_set.attr("h").cast<uintptr_t>());
+        auto r = std::make_shared<PyDevicePosteriors>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj; r->arc_off = so.second;
+        r->status.assign((size_t)std::max(U, 1), 0);
+        r->tot_like.assign((size_t)std::max(U, 1), 0.0);
+        r->avg_acc.assign((size_t)std::max(U, 1), 0.0);
+        r->has_avg_acc = true;
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_mpe_posteriors(d.ctx, d.h, (int32_t)tid2phone.shape(0) - 1, tid2phone.data(), has_pdf ? t2pdf.data() : nullptr,
+                                           (int32_t)silence_phones.shape(0), silence_phones.data(), aoff.empty() ? nullptr : aoff.data(),
+                                           aoff.empty() ? nullptr : ali.data(), sh, crit, one_silence_class ? 1 : 0, gs, as, r->status.data(),
+                                           r->tot_like.data(), r->avg_acc.data(), &r->h));
+        }
+        r->status.resize((size_t)U); r->tot_like.resize((size_t)U); r->avg_acc.resize((size_t)U);
+        return r;
+      }, py::arg("tid2phone"), py::arg("silence_phones"), py::arg("alignment") = py::none(), py::arg("ali_set") = py::none(), py::arg("criterion") = "smbr",
+         py::arg("tid2pdf") = py::none(), py::arg("one_silence_class") = true, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       .def("download", [](PyDeviceLattices& d) {
         if (!d.h) throw Error("DeviceLattices: closed");
         std::vector<std::shared_ptr<Lattice>> out;
@@ -635,6 +704,8 @@ void BindLattice(py::module_& m) {
       }, py::arg("ctx"), py::arg("posts"))
       .def_property_readonly("status", [](PyDevicePosteriors& d) { return Vec1(d.status); })
       .def_property_readonly("tot_like", [](PyDevicePosteriors& d) { return Vec1(d.tot_like); })
+      // of the mpe_posteriors that made this handle (None otherwise): the expected frame accuracy of a path, per utterance
+      .def_property_readonly("avg_acc", [](PyDevicePosteriors& d) -> py::object { if (!d.has_avg_acc) return py::none(); return Vec1(d.avg_acc); })
       .def_property_readonly("num_utts", [](PyDevicePosteriors& d) { return (int)d.status.size(); })
       .def_property_readonly("frame_off", [post_sizes](PyDevicePosteriors& d) { return Vec1(post_sizes(d).first); })
       .def_property_readonly("entry_off", [post_sizes](PyDevicePosteriors& d) { return Vec1(post_sizes(d).second); })

@@ -32,6 +32,8 @@ struct PyDevicePosteriors {
   pybind11::object ctx_obj;
   std::vector<int32_t> status;       // KHG_LAT_* bits per utterance
   std::vector<double> tot_like;
+  std::vector<double> avg_acc;       // made by mpe_posteriors: the expected accuracy per utterance (empty otherwise)
+  bool has_avg_acc = false;
   std::vector<int64_t> arc_off;      // of the lattices it was made from
   PyDevicePosteriors() = default;
   PyDevicePosteriors(const PyDevicePosteriors&) = delete;

@@ -740,6 +740,11 @@ struct KUtts {
     if (!post.h) throw py::value_error("acc_stats_post: the DevicePosteriors are closed");
     Check(NoGil([&] { return khg_acc_stats_post(ctx->h, m.h, tm.h, h, post.h, scale, accs.h); }));
   }
+  // gmm-acc-stats2 (khg_acc_stats_post2): the positive weights into num_accs, the negated negative ones into den_accs
+  void acc_stats_post2(KModel& m, KTransitions& tm, khg::PyDevicePosteriors& post, KAccs& num_accs, KAccs& den_accs, float scale) {
+    if (!post.h) throw py::value_error("acc_stats_post2: the DevicePosteriors are closed");
+    Check(NoGil([&] { return khg_acc_stats_post2(ctx->h, m.h, tm.h, h, post.h, scale, num_accs.h, den_accs.h); }));
+  }
 };
 
 }  // namespace
@@ -849,6 +854,8 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("upload_ali", &KUtts::upload_ali).def("download_ali", &KUtts::download_ali)
       .def("acc_stats", &KUtts::acc_stats, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f)
       .def("acc_stats_post", &KUtts::acc_stats_post, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("accs"), py::arg("scale") = 1.0f)
+      .def("acc_stats_post2", &KUtts::acc_stats_post2, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("num_accs"), py::arg("den_accs"),
+           py::arg("scale") = 1.0f)
       .def("acc_stats_reduce", &KUtts::acc_stats_reduce, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f,
            py::arg("comm") = py::none(), py::arg("nparts") = 4)
       .def("close", &KUtts::close);

@@ -307,3 +307,77 @@ def lattice_boost_ali(transition_model: TransitionModel, lattice, alignment: Seq
                       max_silence_error: float = 0.0):
     """Kaldi's lattice-boost-ali for one utterance -> the boosted Lattice (lattice_boost_ali_batch of one)."""
     return lattice_boost_ali_batch(transition_model, [lattice], [alignment], silence_phones, b, max_silence_error)[0]
+
+
+def _lattice_to_mpe_post_batch(criterion, transition_model, lattices, alignments, silence_phones, one_silence_class, acoustic_scale, lm_scale):
+    from .align import DeviceLattices
+    on_device = isinstance(lattices, DeviceLattices)
+    dl = lattices if on_device else DeviceLattices.from_lattices(list(lattices), _gpu.default_context())
+    try:
+        res = dl.mpe_posteriors(np.asarray(transition_model.transition_id_to_phone_array(), np.int32), np.asarray(list(silence_phones), np.int32),
+                                alignment=[np.asarray(a, np.int32) for a in alignments], criterion=criterion,
+                                tid2pdf=np.asarray(transition_model.transition_id_to_pdf_array(), np.int32), one_silence_class=bool(one_silence_class),
+                                graph_scale=float(lm_scale), acoustic_scale=float(acoustic_scale))
+    finally:
+        if not on_device:
+            dl.close()
+    if on_device:
+        return res
+    out = (res.download(), np.asarray(res.avg_acc, np.float64))
+    res.close()
+    return out
+
+
+def lattice_to_mpe_post_batch(transition_model: TransitionModel, lattices, alignments: Sequence[Sequence[int]], silence_phones: Sequence[int],
+                              one_silence_class: bool = True, acoustic_scale: float = 1.0, lm_scale: float = 1.0):
+    """Kaldi's lattice-to-mpe-post for several utterances on the device (khg_lattices_mpe_posteriors with KHG_MPE_MPFE):
+    the signed posteriors of the expected phone frame accuracy against alignments[u].  lattices: a list of Lattice (-> (a list of
+    Posterior, the expected accuracy per utterance)) or a DeviceLattices on the default context (-> a DevicePosteriors with .avg_acc).
+    An utterance whose alignment is missing, of another length than its lattice or holds a bad id has no frames (KHG_LAT_NO_REF)."""
+    return _lattice_to_mpe_post_batch("mpfe", transition_model, lattices, alignments, silence_phones, one_silence_class, acoustic_scale, lm_scale)
+
+
+def lattice_to_smbr_post_batch(transition_model: TransitionModel, lattices, alignments: Sequence[Sequence[int]], silence_phones: Sequence[int],
+                               one_silence_class: bool = True, acoustic_scale: float = 1.0, lm_scale: float = 1.0):
+    """Kaldi's lattice-to-smbr-post: lattice_to_mpe_post_batch with an arc counted correct when its pdf is the reference's (KHG_MPE_SMBR)."""
+    return _lattice_to_mpe_post_batch("smbr", transition_model, lattices, alignments, silence_phones, one_silence_class, acoustic_scale, lm_scale)
+
+
+def lattice_to_mpe_post(transition_model: TransitionModel, lattice, alignment: Sequence[int], silence_phones: Sequence[int],
+                        one_silence_class: bool = True, acoustic_scale: float = 1.0, lm_scale: float = 1.0):
+    """Kaldi's lattice-to-mpe-post for one utterance -> (Posterior, expected accuracy)."""
+    posts, avg = lattice_to_mpe_post_batch(transition_model, [lattice], [alignment], silence_phones, one_silence_class, acoustic_scale, lm_scale)
+    return posts[0], float(avg[0])
+
+
+def lattice_to_smbr_post(transition_model: TransitionModel, lattice, alignment: Sequence[int], silence_phones: Sequence[int],
+                         one_silence_class: bool = True, acoustic_scale: float = 1.0, lm_scale: float = 1.0):
+    """Kaldi's lattice-to-smbr-post for one utterance -> (Posterior, expected accuracy)."""
+    posts, avg = lattice_to_smbr_post_batch(transition_model, [lattice], [alignment], silence_phones, one_silence_class, acoustic_scale, lm_scale)
+    return posts[0], float(avg[0])
+
+
+def gmm_acc_stats2(am_gmm: AmDiagGmm, num_accs: AccumAmDiagGmm, den_accs: AccumAmDiagGmm, transition_model: TransitionModel, feats, post,
+                   num_transition_accs: Optional[np.ndarray] = None, den_transition_accs: Optional[np.ndarray] = None):
+    """Kaldi's gmm-acc-stats2 for one utterance -> (num_transition_accs, den_transition_accs); the two accumulators are updated in place.
+    `post` is a signed Posterior (lattice_to_mpe_post / lattice_to_smbr_post): an entry with a positive weight adds to num_accs what
+    gmm_acc_stats adds, one with a negative weight adds to den_accs with the weight negated (the rule of khg_acc_stats_post2, DESIGN.md
+    7k, which UtteranceSet.acc_stats_post2 runs for posteriors resident on the device; this per-utterance form splits the Posterior on
+    the host and makes gmm_acc_stats's call once per block)."""
+    if num_accs is den_accs:
+        raise KhgError("gmm_acc_stats2: num_accs and den_accs are the same accumulator")
+    pos = [[(t, w) for t, w in f if w > 0] for f in post]
+    neg = [[(t, -w) for t, w in f if w < 0] for f in post]
+    _, num_transition_accs = gmm_acc_stats(am_gmm, num_accs, transition_model, feats, pos, num_transition_accs)
+    _, den_transition_accs = gmm_acc_stats(am_gmm, den_accs, transition_model, feats, neg, den_transition_accs)
+    return num_transition_accs, den_transition_accs
+
+
+def gmm_acc_stats2_batch(am_gmm: AmDiagGmm, num_accs: AccumAmDiagGmm, den_accs: AccumAmDiagGmm, transition_model: TransitionModel,
+                         feats: Sequence[np.ndarray], posts: Sequence, num_transition_accs: Optional[np.ndarray] = None,
+                         den_transition_accs: Optional[np.ndarray] = None):
+    """Several utterances, same contract."""
+    for f, p in zip(feats, posts):
+        num_transition_accs, den_transition_accs = gmm_acc_stats2(am_gmm, num_accs, den_accs, transition_model, f, p, num_transition_accs,
+                                                                  den_transition_accs)
+    return num_transition_accs, den_transition_accs

@@ -48,7 +48,10 @@ of the first call on the handle (which builds the in-arc index) and of a later o
 host's (transition-id, weight) entries the device's agree with to 1e-9.  (The lattice-simple decoder's lattices carry epsilon
 self-loops and are refused with KHG_LAT_EPS_LOOP: use --decoder faster.)
 
-Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post] [--acc]
+--mpe [--criterion mpe|smbr] (next to --lattices) times DeviceLattices.mpe_posteriors(1, 0.1) alternated with posteriors(1, 0.1) on
+the same handle, and khg_acc_stats_post2 alternated with khg_acc_stats_post on the signed posteriors.
+
+Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post] [--acc] [--mpe]
        python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
@@ -263,6 +266,52 @@ def lattice_ops(ctx, dl, sweep, prune_beam, reps, post=False):
                              "entries_equal_to_host_within_1e-9": same, "statuses_equal_to_host": same_status, "succeeded": int((st == 1).sum()),
                              "largest_tot_like_difference": worst_tot}
         P.close()
+    return out
+
+
+def mpe_bench(ctx, dl, am, tm, feats, alignments, criterion, reps):
+    """--mpe: DeviceLattices.mpe_posteriors(1, 0.1) (the best-path alignments as the reference) alternated in this process with
+    posteriors(1, 0.1) on the same handle, and acc_stats_post2 of the signed posteriors alternated with acc_stats_post of the same
+    handle -> medians of the kernel times and the two ratios."""
+    from kaldi_hmm_gmm_amd import DeviceAccs, DeviceModel, DeviceTransitions, UtteranceSet
+    reps = max(reps, 5)
+    tid2phone = np.asarray(tm.transition_id_to_phone_array(), np.int32)
+    tid2pdf = np.asarray(tm.transition_id_to_pdf_array(), np.int32)
+    sil = np.asarray([int(tid2phone[1])], np.int32)
+    alis = [np.asarray(a, np.int32) for a in alignments]
+    crit = "mpfe" if criterion == "mpe" else "smbr"
+    call = lambda: dl.mpe_posteriors(tid2phone, sil, alignment=alis, criterion=crit, tid2pdf=tid2pdf, acoustic_scale=0.1)  # noqa: E731
+    dl.posteriors(1.0, 0.1).close()                                       # builds the in-arc index
+    call().close()
+    k_fb, k_mpe = [], []
+    for _ in range(reps):
+        k_fb.append(kernel_ms(ctx, lambda: dl.posteriors(1.0, 0.1).close()))
+        k_mpe.append(kernel_ms(ctx, lambda: call().close()))
+    medians = lambda rows: {k: float(np.median([r.get(k, 0.0) for r in rows])) for k in sorted({k for r in rows for k in r})}  # noqa: E731
+    fb_ms, mpe_ms = medians(k_fb), medians(k_mpe)
+    go, gc, w, miv, iv = am.flat()
+    dm, dt = DeviceModel(ctx, go, gc, miv, iv), DeviceTransitions(ctx, tid2pdf)
+    fo = np.concatenate([[0], np.cumsum([len(f) for f in feats])]).astype(np.int64)
+    us = UtteranceSet(ctx, None, fo, np.ascontiguousarray(np.concatenate(feats), np.float32))
+    one, num, den = DeviceAccs(ctx, dm, dt), DeviceAccs(ctx, dm, dt), DeviceAccs(ctx, dm, dt)
+    P = call()
+    ok = (np.asarray(P.status) & 1) != 0
+    us.acc_stats_post(dm, dt, P, one); us.acc_stats_post2(dm, dt, P, num, den); ctx.sync()          # warm-up (allocates the scratch)
+    k_one, k_two = [], []
+    for _ in range(reps):
+        k_one.append(kernel_ms(ctx, lambda: us.acc_stats_post(dm, dt, P, one)))
+        k_two.append(kernel_ms(ctx, lambda: us.acc_stats_post2(dm, dt, P, num, den)))
+    one_ms, two_ms = medians(k_one), medians(k_two)
+    out = {"criterion": crit, "repetitions": reps, "succeeded": int(ok.sum()), "frames": int(P.frame_off[-1]), "entries": int(P.entry_off[-1]),
+           "mean_avg_acc_per_frame": float(np.mean(np.asarray(P.avg_acc)[ok] / np.diff(np.asarray(P.frame_off))[ok])) if ok.any() else None,
+           "posteriors_kernels_ms": fb_ms, "mpe_posteriors_kernels_ms": mpe_ms,
+           "k2_lattice_post_fb_ms": fb_ms.get("k2_lattice_post_fb"), "k2_lattice_post_mpe_ms": mpe_ms.get("k2_lattice_post_mpe"),
+           "mpe_over_fb": mpe_ms.get("k2_lattice_post_mpe", 0.0) / fb_ms["k2_lattice_post_fb"] if fb_ms.get("k2_lattice_post_fb") else None,
+           "acc_stats_post_kernels_ms": one_ms, "acc_stats_post2_kernels_ms": two_ms,
+           "acc_stats_post_total_ms": sum(one_ms.values()), "acc_stats_post2_total_ms": sum(two_ms.values()),
+           "post2_over_post": sum(two_ms.values()) / sum(one_ms.values()) if sum(one_ms.values()) else None}
+    for h in (P, us, one, num, den, dm, dt):
+        h.close()
     return out
 
 
@@ -578,6 +627,9 @@ def main():
     ap.add_argument("--prune-beam", type=float, default=None, help="with --lattices: prune the resident lattices to this beam")
     ap.add_argument("--post", action="store_true", help="with --lattices: forward-backward posteriors of the resident lattices")
     ap.add_argument("--acc", action="store_true", help="with --lattices --post: GMM statistics from those posteriors (khg_acc_stats_post)")
+    ap.add_argument("--mpe", action="store_true", help="with --lattices (--decoder faster): MPE / sMBR posteriors beside posteriors(), and "
+                    "khg_acc_stats_post2 beside khg_acc_stats_post")
+    ap.add_argument("--criterion", choices=("mpe", "smbr"), default="smbr", help="with --mpe")
     ap.add_argument("--rescore", action="store_true", help="with --lattices (--decoder faster): khg_lattices_rescore on the resident lattices, and "
                     "one MMI iteration's denominator side with it against decoding again")
     ap.add_argument("--boost", type=float, default=0.0, metavar="B", help="with --rescore: also khg_lattices_boost at this b")
@@ -586,6 +638,8 @@ def main():
         ap.error("--sweep / --prune-beam / --post need --lattices")
     if args.rescore and (not args.lattices or args.decoder != "faster" or args.shared_graph or args.yesno):
         ap.error("--rescore needs --lattices with --decoder faster (and is not timed with --shared-graph / --yesno)")
+    if args.mpe and (not args.lattices or args.decoder != "faster" or args.shared_graph or args.yesno):
+        ap.error("--mpe needs --lattices with --decoder faster (and is not timed with --shared-graph / --yesno)")
     if args.acc and (not args.post or args.shared_graph):
         ap.error("--acc needs --lattices --post (and is not timed with --shared-graph)")
     if args.shared_graph or args.yesno:
@@ -648,13 +702,15 @@ def main():
                     emission_kernels_ms=emit, emission_over_decoder=(emit + dec_new - dec_old) / dec_old if dec_old else None)
         faster_lat = flat
         faster_ops = None
-        if args.sweep or args.prune_beam is not None or args.post or args.rescore:
+        if args.sweep or args.prune_beam is not None or args.post or args.rescore or args.mpe:
             _, dl = khg.get_raw_lattice_faster_device_batch(am, tm, fsts, feats, cfg, 0.1)
             faster_ops = {}
             if args.sweep or args.prune_beam is not None or args.post:
                 faster_ops = lattice_ops(ctx, dl, args.sweep, args.prune_beam, args.reps, args.post)
             if args.acc:
                 faster_ops["acc_stats_post"] = acc_from_post(ctx, dl, am, tm, feats, [r["alignment"] for r in fres], args.reps)
+            if args.mpe:
+                faster_ops["mpe"] = mpe_bench(ctx, dl, am, tm, feats, [r["alignment"] for r in fres], args.criterion, args.reps)
             if args.rescore:
                 faster_ops["rescore"] = rescore_bench(ctx, dl, am, tm, fsts, feats, [r["alignment"] for r in fres], cfg, args.reps, args.boost)
             dl.close()
