@@ -862,6 +862,80 @@ int khg_scaled_trans_cost(int32_t num_tids, const float *log_probs,
                           const uint8_t *is_self_loop, float transition_scale,
                           float self_loop_scale, float *out_cost);
 
+/* ---- fMLLR speaker adaptation (gmm-est-fmllr, transform-feats) --------------------------------------------------- */
+/* The reference has no fMLLR: the rule in DESIGN.md 7l is the specification (tests/fmllr_ref.py restates it).  Notation: x+ = [x, 1],
+ * W is dim x (dim + 1), A = W[:, :dim].  Feature dimensions up to KHG_FMLLR_MAX_DIM (the MFMA range of K1 / K3); above: KHG_E_UNSUPPORTED. */
+#define KHG_FMLLR_MAX_DIM 80
+#define KHG_FMLLR_OK 0           /* the transform was estimated                                                        */
+#define KHG_FMLLR_LOW_COUNT 1    /* beta < min_count: W = [I | 0]                                                      */
+#define KHG_FMLLR_SINGULAR 2     /* a pivot of some G[d] (or of A) not finite or not > 0: W = [I | 0]                  */
+/* Kaldi's FmllrDiagGmmAccs for n_spk speakers, resident on the device, all fp64: per speaker beta, K[dim][dim + 1] and G[dim], each
+ * G[d] the symmetric (dim + 1) x (dim + 1) matrix as Kaldi's packed lower triangle ((i, j <= i) at i (i + 1) / 2 + j):
+ * (dim + 1)(dim + 2) / 2 doubles.  Host layout of download / upload: beta_h[n_spk], K_h[n_spk][dim][dim + 1], G_h[n_spk][dim][packed];
+ * download takes NULL for an array that is not wanted and synchronises (deferred kernel errors: KHG_E_RUNTIME), upload needs all
+ * three.  add: dst += (double)scale * src elementwise (one product, one add), asynchronous; the handles must agree in speakers and
+ * dimension and belong to `ctx` (KHG_E_ARG). */
+typedef struct khg_fmllr_stats khg_fmllr_stats;
+int khg_fmllr_stats_create(khg_ctx *ctx, int32_t n_spk, int32_t dim, khg_fmllr_stats **out);
+int khg_fmllr_stats_destroy(khg_fmllr_stats *s);
+int khg_fmllr_stats_zero(khg_ctx *ctx, khg_fmllr_stats *s);
+int khg_fmllr_stats_download(khg_ctx *ctx, const khg_fmllr_stats *s, double *beta_h, double *K_h, double *G_h);
+int khg_fmllr_stats_upload(khg_ctx *ctx, khg_fmllr_stats *s, const double *beta_h, const double *K_h, const double *G_h);
+int khg_fmllr_stats_add(khg_ctx *ctx, khg_fmllr_stats *dst, float scale, const khg_fmllr_stats *src);
+/* The accumulation's scratch is bounded by a chunk of `frames` frames (default 2^18; at least one 1024-frame slice, at most 2^24):
+ * frames x (8 dim + 12) bytes of frame vectors plus min(2 max(1, frames / 1024) parked slice images of a speaker's block, 256 MiB), beside 4 bytes
+ * per frame of the set, one more block per speaker for the call's sums and (8 dim + 8) bytes per entry of a chunk (at most 2 x frames
+ * entries plus one slice's utterances').  The statistics do not depend on it, bit for bit.
+ * num_chunks: how many chunks the last accumulation into the handle ran (tests). */
+int khg_fmllr_stats_set_chunk_frames(khg_fmllr_stats *s, int64_t frames);
+int khg_fmllr_stats_num_chunks(const khg_fmllr_stats *s, int32_t *n_chunks);
+/* gmm-est-fmllr's accumulation from posteriors resident on the device.  Every entry (utterance u, frame t, transition-id, weight w64)
+ * of `p` with utt2spk_h[u] = s >= 0 counts for speaker s with w = (float)((double)scale * w64), as in khg_acc_stats_post.  Per entry,
+ * fp32: the component posteriors gamma_g of the entry's pdf at x as K3's POST forms compute them, ea[d] = sum_g gamma_g inv_var[g][d],
+ * eb[d] = sum_g gamma_g mean_invvar[g][d], ec = sum_g gamma_g, in Gaussian order.  Per frame: a_t, b_t the float sums of the frame's
+ * entries in entry order, c_t their double sum.  Per speaker, fp64, over its frames in set order: beta += c_t, K[d][j] += b_t[d] x+[j],
+ * G[d][i][j] += a_t[d] (x+[i] x+[j]) for j <= i (the product of two floats is exact in a double; the order of the sum is fixed by the
+ * speaker's own frame list: 1024-frame slices on the fp64 matrix pipe, added in slice order).  The statistics of a speaker have the
+ * same bits whatever else is in the call, whatever the chunk size, and from run to run.  An entry with w == 0, an utterance with
+ * utt2spk < 0 and an utterance without frames in `p` add nothing; negative weights are taken as they are.  Adds into `stats`;
+ * asynchronous on the context's stream once the plan is uploaded.  khg_acc_stats_post's refusals (KHG_E_ARG before anything is
+ * launched), and KHG_E_ARG for a utt2spk value >= n_spk or statistics of another dimension. */
+int khg_acc_fmllr_stats_post(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, const khg_posteriors *p, float scale,
+                             const int32_t *utt2spk_h, khg_fmllr_stats *stats);
+typedef struct {
+  double min_count;   /* 500: speakers with beta below it keep W = [I | 0] */
+  int32_t num_iters;  /* 40: sweeps over the rows of W */
+} khg_fmllr_options;
+void khg_fmllr_options_default(khg_fmllr_options *o);
+/* Kaldi's ComputeFmllrMatrixDiagGmmFull (update type "full") on host arrays laid out as khg_fmllr_stats_download gives them; needs no
+ * device.  Per speaker: invG[d] by Gauss-Jordan without pivoting; from W = [I | 0], num_iters sweeps of the row update of DESIGN.md 7l
+ * (c = row d of (A^T)^-1 by Gauss-Jordan with partial pivoting, the two roots of the quadratic, the one with the larger auxiliary
+ * value).  All fp64, one operation at a time in index order.  Outputs (any may be NULL, but one of W_h / W64_h is needed):
+ * W_h[n_spk][dim][dim + 1] floats, W64_h the same before narrowing, objf_impr_h[n_spk] = Q(W) - Q([I | 0]), count_h[n_spk] = beta,
+ * status_h[n_spk] KHG_FMLLR_*.  o == NULL: the defaults.  Speakers run on up to 16 threads; results do not depend on that. */
+int khg_fmllr_compute(const khg_fmllr_options *o, int32_t n_spk, int32_t dim, const double *beta_h, const double *K_h, const double *G_h,
+                      float *W_h, double *W64_h, double *objf_impr_h, double *count_h, int32_t *status_h);
+/* The same estimate on the device, on the statistics where the accumulation left them: one kernel inverts the n_spk x dim matrices
+ * G[d] into HBM scratch (one workgroup per matrix), one runs one workgroup per speaker for the sweeps.  Every operation is the host
+ * form's, in its order, with contraction off: W, the statuses and the counts are bit-identical to khg_fmllr_compute on the downloaded
+ * statistics wherever the two roots do not tie; objf_impr agrees to the rounding of log.  W_h (host) and / or W_d (a
+ * caller-owned device buffer that keeps the transforms resident for khg_utts_transform_feats), [n_spk][dim][dim + 1] floats, and the
+ * other outputs may each be NULL.  o == NULL: the defaults.  Synchronous. */
+int khg_fmllr_stats_estimate(khg_ctx *ctx, const khg_fmllr_stats *stats, const khg_fmllr_options *o, float *W_h, float *W_d,
+                             double *objf_impr_h, double *count_h, int32_t *status_h);
+/* ali-to-post on the device: a posteriors handle (free it with khg_posteriors_destroy) with one entry of weight 1 per frame from the
+ * set's resident alignment (khg_align, khg_ali_upload), so an SAT loop never brings the ids down.  An utterance whose alignment failed
+ * (ids 0) gets no frames.  One flag per utterance is read back: synchronous.  KHG_E_ARG without a resident alignment. */
+int khg_posteriors_from_ali(khg_ctx *ctx, khg_utts *u, khg_posteriors **out);
+/* transform-feats on the set's resident rows: y = A x + b with W = [A | b] of the utterance's speaker, in float -- y[d] = b[d], then
+ * y[d] = fmaf(A[d][j], x[j], y[d]) for j = 0 .. dim - 1.  An utterance with utt2spk_h[u] < 0 is copied.  Exactly one of W_h (host) and
+ * W_d (a caller-owned device buffer: the transforms stay resident) is given, [n_spk][dim][dim + 1] floats.  With out_d the rows go
+ * to that device buffer (the set's size) and the set is untouched; with out_d == NULL the set's own rows are rewritten in place
+ * (borrowed device features included) and the set is told so, as by khg_utts_features_changed.  KHG_E_ARG for a utt2spk value
+ * >= n_spk.  Synchronous. */
+int khg_utts_transform_feats(khg_ctx *ctx, khg_utts *u, int32_t n_spk, const int32_t *utt2spk_h, const float *W_h, const float *W_d,
+                             float *out_d);
+
 #ifdef __cplusplus
 }
 #endif

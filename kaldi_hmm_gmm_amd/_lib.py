@@ -110,6 +110,10 @@ class EbwResultsC(C.Structure):
                 ("failed", C.c_int32), ("skipped", C.c_int32), ("weights_skipped", C.c_int32)]
 
 
+class FmllrOptionsC(C.Structure):
+    _fields_ = [("min_count", C.c_double), ("num_iters", C.c_int32)]
+
+
 class RescoreStatsC(C.Structure):
     _fields_ = [("arcs", C.c_int64), ("emitting_arcs", C.c_int64), ("cells", C.c_int64)]
 
@@ -261,6 +265,21 @@ SIGNATURES = {
         [C.c_int32, c_i32p, c_i32p, c_f64p, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p],
     ),
     "khg_scaled_trans_cost": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_i32p, c_u8p, C.c_float, C.c_float, c_f32p]),
+    "khg_fmllr_stats_create": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(vp)]),
+    "khg_fmllr_stats_destroy": (C.c_int, [vp]),
+    "khg_fmllr_stats_zero": (C.c_int, [vp, vp]),
+    "khg_fmllr_stats_download": (C.c_int, [vp, vp, c_f64p, c_f64p, c_f64p]),
+    "khg_fmllr_stats_upload": (C.c_int, [vp, vp, c_f64p, c_f64p, c_f64p]),
+    "khg_fmllr_stats_add": (C.c_int, [vp, vp, C.c_float, vp]),
+    "khg_fmllr_stats_set_chunk_frames": (C.c_int, [vp, C.c_int64]),
+    "khg_fmllr_stats_num_chunks": (C.c_int, [vp, c_i32p]),
+    "khg_acc_fmllr_stats_post": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, c_i32p, vp]),
+    "khg_fmllr_options_default": (None, [C.POINTER(FmllrOptionsC)]),
+    "khg_fmllr_compute": (C.c_int, [C.POINTER(FmllrOptionsC), C.c_int32, C.c_int32, c_f64p, c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p,
+                                    c_i32p]),
+    "khg_fmllr_stats_estimate": (C.c_int, [vp, vp, C.POINTER(FmllrOptionsC), c_f32p, vp, c_f64p, c_f64p, c_i32p]),
+    "khg_posteriors_from_ali": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "khg_utts_transform_feats": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_f32p, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -601,3 +601,163 @@ extern "C" int khg_careful_graph(int32_t S, int32_t start, const int64_t* arc_of
   *ostart = start;
   return KHG_OK;
 }
+
+// ---- fMLLR estimate: the reference has no fMLLR, the rule written there is the specification -----------------------
+// Kaldi's ComputeFmllrMatrixDiagGmmFull on one speaker's statistics.  Every operation below is one IEEE fp64 operation in the written
+// order (no contraction), every sum runs in index order: tests/fmllr_ref.py restates it and agrees on the bits of W.
+#pragma clang fp contract(off)
+namespace {
+
+// the inverse of the symmetric matrix behind a packed lower triangle, by Gauss-Jordan without pivoting; false: a pivot that is not
+// finite or not > 0.  M and inv are n x n.
+bool FmInvSym(int n, const double* packed, double* M, double* inv) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) { M[i * n + j] = packed[i * (i + 1) / 2 + j]; M[j * n + i] = M[i * n + j]; }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) inv[i * n + j] = i == j ? 1.0 : 0.0;
+  for (int p = 0; p < n; ++p) {
+    const double piv = M[p * n + p];
+    if (!(std::isfinite(piv) && piv > 0.0)) return false;
+    for (int j = 0; j < n; ++j) { M[p * n + j] = M[p * n + j] / piv; inv[p * n + j] = inv[p * n + j] / piv; }
+    for (int r = 0; r < n; ++r) {
+      if (r == p) continue;
+      const double f = M[r * n + p];
+      for (int j = 0; j < n; ++j) { M[r * n + j] = M[r * n + j] - f * M[p * n + j]; inv[r * n + j] = inv[r * n + j] - f * inv[p * n + j]; }
+    }
+  }
+  return true;
+}
+// inv = M^-1 by Gauss-Jordan with partial pivoting (the largest magnitude wins, the lowest row among equals); M is destroyed;
+// *logabsdet = sum over the pivots of log |pivot|, in order.  false: a pivot that is zero or not finite.
+bool FmInvPiv(int n, double* M, double* inv, double* logabsdet) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) inv[i * n + j] = i == j ? 1.0 : 0.0;
+  double ld = 0.0;
+  for (int p = 0; p < n; ++p) {
+    int best = p;
+    double bv = std::fabs(M[p * n + p]);
+    for (int r = p + 1; r < n; ++r) { const double v = std::fabs(M[r * n + p]); if (v > bv) { bv = v; best = r; } }
+    if (best != p)
+      for (int j = 0; j < n; ++j) { std::swap(M[p * n + j], M[best * n + j]); std::swap(inv[p * n + j], inv[best * n + j]); }
+    const double piv = M[p * n + p];
+    if (!(std::isfinite(piv)) || piv == 0.0) return false;
+    ld = ld + std::log(std::fabs(piv));
+    for (int j = 0; j < n; ++j) { M[p * n + j] = M[p * n + j] / piv; inv[p * n + j] = inv[p * n + j] / piv; }
+    for (int r = 0; r < n; ++r) {
+      if (r == p) continue;
+      const double f = M[r * n + p];
+      for (int j = 0; j < n; ++j) { M[r * n + j] = M[r * n + j] - f * M[p * n + j]; inv[r * n + j] = inv[r * n + j] - f * inv[p * n + j]; }
+    }
+  }
+  *logabsdet = ld;
+  return true;
+}
+// Q(W) = beta log |det A| + sum_d (W[d] . K[d] - 1/2 W[d] G[d] W[d]^T); false: A is singular
+bool FmAuxf(int D, double beta, const double* K, const double* G, const double* W, double* q, double* M, double* inv) {
+  const int D1 = D + 1, NP = D1 * (D1 + 1) / 2;
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) M[i * D + j] = W[j * D1 + i];
+  double ld = 0.0;
+  if (!FmInvPiv(D, M, inv, &ld)) return false;
+  double acc = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const double* g = G + (size_t)d * NP;
+    const double* w = W + (size_t)d * D1;
+    double t1 = 0.0, t2 = 0.0;
+    for (int i = 0; i < D1; ++i) t1 = t1 + w[i] * K[d * D1 + i];
+    for (int i = 0; i < D1; ++i) {
+      double r = 0.0;
+      for (int j = 0; j < D1; ++j) r = r + g[j <= i ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i] * w[j];
+      t2 = t2 + w[i] * r;
+    }
+    acc = acc + (t1 - 0.5 * t2);
+  }
+  *q = beta * ld + acc;
+  return true;
+}
+
+// one speaker; W: D x (D + 1) doubles
+int32_t FmllrOne(const khg_fmllr_options* o, int D, double beta, const double* K, const double* G, double* W, double* objf_impr) {
+  const int D1 = D + 1, NP = D1 * (D1 + 1) / 2;
+  auto identity = [&] {
+    for (int d = 0; d < D; ++d)
+      for (int j = 0; j < D1; ++j) W[d * D1 + j] = d == j ? 1.0 : 0.0;
+  };
+  identity();
+  *objf_impr = 0.0;
+  if (beta < o->min_count) return KHG_FMLLR_LOW_COUNT;
+  std::vector<double> invG((size_t)D * D1 * D1), M((size_t)D1 * D1), inv((size_t)D1 * D1), c(D1), cg(D1), v(D1);
+  for (int d = 0; d < D; ++d)
+    if (!FmInvSym(D1, G + (size_t)d * NP, M.data(), invG.data() + (size_t)d * D1 * D1)) return KHG_FMLLR_SINGULAR;
+  double q0 = 0.0;
+  if (!FmAuxf(D, beta, K, G, W, &q0, M.data(), inv.data())) return KHG_FMLLR_SINGULAR;
+  for (int it = 0; it < o->num_iters; ++it)
+    for (int d = 0; d < D; ++d) {
+      for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; ++j) M[i * D + j] = W[j * D1 + i];            // A^T
+      double ld = 0.0;
+      if (!FmInvPiv(D, M.data(), inv.data(), &ld)) { identity(); return KHG_FMLLR_SINGULAR; }
+      for (int j = 0; j < D; ++j) c[j] = inv[d * D + j];
+      c[D] = 0.0;
+      const double* ig = invG.data() + (size_t)d * D1 * D1;
+      const double* k = K + (size_t)d * D1;
+      for (int i = 0; i < D1; ++i) {
+        double r = 0.0;
+        for (int j = 0; j < D1; ++j) r = r + ig[i * D1 + j] * c[j];
+        cg[i] = r;
+      }
+      double e1 = 0.0, e2 = 0.0;
+      for (int i = 0; i < D1; ++i) e1 = e1 + cg[i] * c[i];
+      for (int i = 0; i < D1; ++i) e2 = e2 + cg[i] * k[i];
+      const double disc = std::sqrt(e2 * e2 + (4.0 * e1) * beta);
+      const double a1 = (-e2 + disc) / (2.0 * e1), a2 = (-e2 - disc) / (2.0 * e1);
+      const double f1 = beta * std::log(std::fabs(a1 * e1 + e2)) - ((0.5 * a1) * a1) * e1;
+      const double f2 = beta * std::log(std::fabs(a2 * e1 + e2)) - ((0.5 * a2) * a2) * e1;
+      const double alpha = f1 > f2 ? a1 : a2;
+      for (int i = 0; i < D1; ++i) v[i] = alpha * c[i] + k[i];
+      for (int i = 0; i < D1; ++i) {
+        double r = 0.0;
+        for (int j = 0; j < D1; ++j) r = r + ig[i * D1 + j] * v[j];
+        W[d * D1 + i] = r;
+      }
+    }
+  double q1 = 0.0;
+  if (!FmAuxf(D, beta, K, G, W, &q1, M.data(), inv.data())) { identity(); return KHG_FMLLR_SINGULAR; }
+  *objf_impr = q1 - q0;
+  return KHG_FMLLR_OK;
+}
+
+}  // namespace
+
+extern "C" void khg_fmllr_options_default(khg_fmllr_options* o) { o->min_count = 500.0; o->num_iters = 40; }
+
+extern "C" int khg_fmllr_compute(const khg_fmllr_options* o, int32_t n_spk, int32_t dim, const double* beta_h, const double* K_h, const double* G_h,
+                                 float* W_h, double* W64_h, double* objf_impr_h, double* count_h, int32_t* status_h) {
+  khg_fmllr_options def;
+  khg_fmllr_options_default(&def);
+  if (!o) o = &def;
+  if (n_spk < 1 || dim < 1 || dim > KHG_FMLLR_MAX_DIM || !beta_h || !K_h || !G_h || (!W_h && !W64_h))
+    return khg_set_error(KHG_E_ARG, "khg_fmllr_compute: bad arguments");
+  if (!std::isfinite(o->min_count) || o->num_iters < 0) return khg_set_error(KHG_E_ARG, "khg_fmllr_compute: an option is not finite or negative");
+  const int D = dim, D1 = D + 1;
+  const size_t nk = (size_t)D * D1, ng = (size_t)D * (D1 * (D1 + 1) / 2);
+  auto work = [&](int s0, int step) {
+    std::vector<double> W(nk);
+    for (int s = s0; s < n_spk; s += step) {
+      double impr = 0.0;
+      const int32_t st = FmllrOne(o, D, beta_h[s], K_h + (size_t)s * nk, G_h + (size_t)s * ng, W.data(), &impr);
+      if (status_h) status_h[s] = st;
+      if (objf_impr_h) objf_impr_h[s] = impr;
+      if (count_h) count_h[s] = beta_h[s];
+      if (W64_h) memcpy(W64_h + (size_t)s * nk, W.data(), sizeof(double) * nk);
+      if (W_h) for (size_t i = 0; i < nk; ++i) W_h[(size_t)s * nk + i] = (float)W[i];
+    }
+  };
+  // speakers are independent: up to 16 threads, each its own speakers (the results do not depend on the thread count)
+  const int nthr = (int)std::max(1u, std::min({16u, std::thread::hardware_concurrency(), (unsigned)n_spk}));
+  if (nthr == 1) { work(0, 1); return KHG_OK; }
+  std::vector<std::thread> th;
+  for (int t = 0; t < nthr; ++t) th.emplace_back(work, t, nthr);
+  for (auto& t : th) t.join();
+  return KHG_OK;
+}

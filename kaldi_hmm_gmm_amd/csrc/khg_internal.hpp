@@ -3,7 +3,7 @@
 // another.  The units, by handle:  khg_ctx_model.hip (context, model image, transition table), khg_utts.hip (utterance sets: features +
 // graphs), khg_k1.hip (log-likelihoods), khg_k2.hip (Viterbi alignment), khg_lattices.hip (lattice decoders, resident lattices and their
 // posteriors: khg_lattices / khg_posteriors stay private to it), khg_k3.hip (accumulators + statistics), khg_c1.hip (RCCL exchange),
-// khg_k4.hip (device M-step).  gfx950 only.
+// khg_k4.hip (device M-step), khg_fmllr.hip (fMLLR statistics and feature transform: khg_fmllr_stats stays private to it).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -378,3 +378,23 @@ void posteriors_info(const khg_posteriors* p, PostInfo* out);
 // negative ones, negated.
 int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set_frame_off_d, double scale, int32_t num_tids,
                        int32_t* e_row, int32_t* e_tid, float* e_w, int sign = 0);
+// a handle of one entry per frame whose single chunk the caller fills on the device (khg_posteriors_from_ali, khg_fmllr.hip)
+int posteriors_make_unit(khg_ctx* ctx, int32_t n_utt, const int64_t* frame_off_h, int64_t** entry_begin_d, double** weight_d, int32_t** tid_d,
+                         const int64_t** frame_off_d, khg_posteriors** out);
+// the set's flattened-entry buffers (pe_row / pe_tid / pe_ids / pe_w / pe_keys / pe_keys_out / pe_vals) grown together to E entries:
+// what khg_acc_stats_post and khg_acc_fmllr_stats_post both start with
+inline int utts_grow_pe(khg_utts* u, size_t E) {
+  if (E <= u->pe_cap) return KHG_OK;
+  DEVFREE(u->pe_row_d); DEVFREE(u->pe_tid_d); DEVFREE(u->pe_ids_d); DEVFREE(u->pe_w_d); DEVFREE(u->pe_keys_d); DEVFREE(u->pe_keys_out_d); DEVFREE(u->pe_vals_d);
+  u->pe_cap = 0;
+  int rc = u_alloc(u, &u->pe_row_d, E);
+  if (!rc) rc = u_alloc(u, &u->pe_tid_d, E);
+  if (!rc) rc = u_alloc(u, &u->pe_ids_d, E);
+  if (!rc) rc = u_alloc(u, &u->pe_w_d, E);
+  if (!rc) rc = u_alloc(u, &u->pe_keys_d, E);
+  if (!rc) rc = u_alloc(u, &u->pe_keys_out_d, E);
+  if (!rc) rc = u_alloc(u, &u->pe_vals_d, E);
+  if (rc) return rc;
+  u->pe_cap = E;
+  return KHG_OK;
+}

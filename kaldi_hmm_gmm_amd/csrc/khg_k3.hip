@@ -586,19 +586,8 @@ static int acc_stats_post_impl(const std::string& name, khg_ctx* ctx, const khg_
   if (E == 0) return KHG_OK;
   int rc = arena_flush(ctx);
   if (rc) return rc;
-  if ((size_t)E > u->pe_cap) {
-    DEVFREE(u->pe_row_d); DEVFREE(u->pe_tid_d); DEVFREE(u->pe_ids_d); DEVFREE(u->pe_w_d); DEVFREE(u->pe_keys_d); DEVFREE(u->pe_keys_out_d); DEVFREE(u->pe_vals_d);
-    u->pe_cap = 0;
-    rc = u_alloc(u, &u->pe_row_d, (size_t)E);
-    if (!rc) rc = u_alloc(u, &u->pe_tid_d, (size_t)E);
-    if (!rc) rc = u_alloc(u, &u->pe_ids_d, (size_t)E);
-    if (!rc) rc = u_alloc(u, &u->pe_w_d, (size_t)E);
-    if (!rc) rc = u_alloc(u, &u->pe_keys_d, (size_t)E);
-    if (!rc) rc = u_alloc(u, &u->pe_keys_out_d, (size_t)E);
-    if (!rc) rc = u_alloc(u, &u->pe_vals_d, (size_t)E);
-    if (rc) return rc;
-    u->pe_cap = (size_t)E;
-  }
+  rc = utts_grow_pe(u, (size_t)E);
+  if (rc) return rc;
   if (!u->pe_start_d || u->pe_P != m->P) {
     DEVFREE(u->pe_start_d);
     rc = u_alloc(u, &u->pe_start_d, (size_t)m->P + 1);

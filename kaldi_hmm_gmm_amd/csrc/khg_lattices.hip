@@ -1212,6 +1212,35 @@ extern "C" int khg_posteriors_upload(khg_ctx* ctx, int32_t n_utt, const int64_t*
   return KHG_OK;
 }
 
+// A handle of one entry per frame whose arrays the CALLER fills on the device (khg_posteriors_from_ali, khg_fmllr.hip): frame_off_h
+// [n_utt + 1] as in khg_posteriors_upload; the three arrays of the single chunk (entry_begin [F + 1], weight / tid [F]) and the
+// handle's frame offsets on the device come back.  max_tid = -1: the ids are checked where they are read, as a lattice's are.
+int posteriors_make_unit(khg_ctx* ctx, int32_t n_utt, const int64_t* frame_off_h, int64_t** entry_begin_d, double** weight_d, int32_t** tid_d,
+                         const int64_t** frame_off_d, khg_posteriors** out) {
+  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
+  res->U = n_utt; res->ctx = ctx;
+  res->frame_off.assign(frame_off_h, frame_off_h + n_utt + 1);
+  res->entry_off = res->frame_off;
+  res->arc_off.assign((size_t)n_utt + 1, 0);
+  res->max_tid = -1;
+  *entry_begin_d = nullptr; *weight_d = nullptr; *tid_d = nullptr; *frame_off_d = nullptr;
+  if (n_utt == 0) { *out = res.release(); return KHG_OK; }
+  PostChunk q;
+  q.u0 = 0; q.n = n_utt; q.nf = q.ne = frame_off_h[n_utt];
+  q.o_weight = (8 * (q.nf + 1) + 255) & ~int64_t(255);
+  q.o_tid = q.o_weight + ((8 * q.ne + 255) & ~int64_t(255));
+  const int64_t total = q.o_tid + 4 * q.ne;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&q.buf), (size_t)std::max<int64_t>(total, 16)));
+  res->chunks.push_back(q);
+  res->bytes += total;
+  int rc = post_frame_off_upload(ctx, res.get());
+  if (rc) return rc;
+  *entry_begin_d = reinterpret_cast<int64_t*>(q.buf); *weight_d = reinterpret_cast<double*>(q.buf + q.o_weight);
+  *tid_d = reinterpret_cast<int32_t*>(q.buf + q.o_tid); *frame_off_d = res->frame_off_d;
+  *out = res.release();
+  return KHG_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // What khg_acc_stats_post (khg_k3.hip) reads of a handle: its sizes, and its entries flattened into three arrays.
 void posteriors_info(const khg_posteriors* p, PostInfo* out) {

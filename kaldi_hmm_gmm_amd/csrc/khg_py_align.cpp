@@ -697,6 +697,27 @@ void BindLattice(py::module_& m) {
         }
         return r;
       }, py::arg("ctx"), py::arg("frame_off"), py::arg("entry_begin"), py::arg("tid"), py::arg("weight"))
+      // ali-to-post on the device (khg_posteriors_from_ali): one entry of weight 1 per frame of the set's resident alignment; an
+      // utterance whose alignment failed has no frames (status KHG_LAT_NO_PATH)
+      .def_static("from_alignment", [](py::object utts) {
+        py::object ctx = utts.attr("ctx");
+        auto r = std::make_shared<PyDevicePosteriors>();
+        r->ctx_obj = ctx;
+        r->ctx = reinterpret_cast<khg_ctx*>(ctx.attr("h").cast<uintptr_t>());
+        khg_utts* uh = reinterpret_cast<khg_utts*>(utts.attr("h").cast<uintptr_t>());
+        if (!uh) throw Error("DevicePosteriors.from_alignment: the UtteranceSet is closed");
+        const size_t U = (size_t)utts.attr("n_utt").cast<int>();
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_posteriors_from_ali(r->ctx, uh, &r->h));
+        }
+        std::vector<int64_t> fo(U + 1), eo(U + 1);
+        CApi(khg_posteriors_sizes(r->h, fo.data(), eo.data()));
+        r->arc_off.assign(U + 1, 0);
+        r->status.resize(U); r->tot_like.assign(U, 0.0);
+        for (size_t u = 0; u < U; ++u) r->status[u] = fo[u + 1] > fo[u] ? KHG_LAT_SUCCEEDED : KHG_LAT_NO_PATH;
+        return r;
+      }, py::arg("utts"))
       // ... from Kaldi's Posterior per utterance: posts[u][t] is a list of (tid, weight)
       .def_static("from_posteriors", [](py::object ctx, py::list posts) {
         py::object arrays = py::module_::import("kaldi_hmm_gmm_amd.posterior").attr("posts_to_arrays")(posts);

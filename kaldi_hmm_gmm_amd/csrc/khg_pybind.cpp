@@ -402,6 +402,50 @@ py::dict KModel::mle_update_finish() {
   return mle_result(oc, cnt, fe, fg, rm);
 }
 
+// FmllrDiagGmmAccs of n_spk speakers resident in HBM (khg_fmllr_stats)
+struct KFmllrStats {
+  khg_fmllr_stats* h = nullptr;
+  py::object ctx_obj;
+  KContext* ctx;
+  int n_spk = 0, dim = 0;
+  KFmllrStats(py::object ctx_o, int n, int d) : ctx_obj(ctx_o), ctx(ctx_o.cast<KContext*>()), n_spk(n), dim(d) {
+    Check(khg_fmllr_stats_create(ctx->h, n, d, &h));
+  }
+  ~KFmllrStats() { close(); }
+  void close() { if (h) { khg_fmllr_stats_destroy(h); h = nullptr; } }
+  void zero() { Check(khg_fmllr_stats_zero(ctx->h, h)); }
+  py::ssize_t packed() const { return (py::ssize_t)(dim + 1) * (dim + 2) / 2; }
+  py::dict download() {
+    Arr<double> beta({(py::ssize_t)n_spk}), K({(py::ssize_t)n_spk, (py::ssize_t)dim, (py::ssize_t)dim + 1}), G({(py::ssize_t)n_spk, (py::ssize_t)dim, packed()});
+    Check(NoGil([&] { return khg_fmllr_stats_download(ctx->h, h, beta.mutable_data(), K.mutable_data(), G.mutable_data()); }));
+    py::dict d;
+    d["beta"] = beta; d["K"] = K; d["G"] = G;
+    return d;
+  }
+  void upload(Arr<double> beta, Arr<double> K, Arr<double> G) {
+    if (beta.size() != n_spk || K.size() != (py::ssize_t)n_spk * dim * (dim + 1) || G.size() != (py::ssize_t)n_spk * dim * packed())
+      throw py::value_error("DeviceFmllrStats.upload: beta [n_spk], K [n_spk, dim, dim + 1], G [n_spk, dim, (dim + 1)(dim + 2) / 2]");
+    Check(NoGil([&] { return khg_fmllr_stats_upload(ctx->h, h, beta.data(), K.data(), G.data()); }));
+  }
+  // the estimate on the device (khg_fmllr_stats_estimate); W_d: a device pointer that receives the float transforms, or None
+  py::dict estimate(double min_count, int num_iters, py::object W_d) {
+    khg_fmllr_options o;
+    khg_fmllr_options_default(&o);
+    o.min_count = min_count; o.num_iters = num_iters;
+    Arr<float> W({(py::ssize_t)n_spk, (py::ssize_t)dim, (py::ssize_t)dim + 1});
+    Arr<double> impr({(py::ssize_t)n_spk}), count({(py::ssize_t)n_spk});
+    Arr<int32_t> status({(py::ssize_t)n_spk});
+    float* wd = W_d.is_none() ? nullptr : reinterpret_cast<float*>(W_d.cast<uintptr_t>());
+    Check(NoGil([&] { return khg_fmllr_stats_estimate(ctx->h, h, &o, W.mutable_data(), wd, impr.mutable_data(), count.mutable_data(), status.mutable_data()); }));
+    py::dict d;
+    d["W"] = W; d["objf_impr"] = impr; d["count"] = count; d["status"] = status;
+    return d;
+  }
+  void add(float scale, KFmllrStats& src) { Check(khg_fmllr_stats_add(ctx->h, h, scale, src.h)); }
+  void set_chunk_frames(int64_t frames) { Check(khg_fmllr_stats_set_chunk_frames(h, frames)); }
+  int num_chunks() { int32_t n = 0; Check(khg_fmllr_stats_num_chunks(h, &n)); return n; }
+};
+
 struct KUtts {
   khg_utts* h = nullptr;
   py::object ctx_obj, keep, keep_model;
@@ -745,6 +789,30 @@ struct KUtts {
     if (!post.h) throw py::value_error("acc_stats_post2: the DevicePosteriors are closed");
     Check(NoGil([&] { return khg_acc_stats_post2(ctx->h, m.h, tm.h, h, post.h, scale, num_accs.h, den_accs.h); }));
   }
+  // gmm-est-fmllr's accumulation (khg_acc_fmllr_stats_post): utterance u of `post` counts for speaker utt2spk[u] (< 0: for nobody)
+  void acc_fmllr_stats_post(KModel& m, KTransitions& tm, khg::PyDevicePosteriors& post, Arr<int32_t> utt2spk, KFmllrStats& stats, float scale) {
+    if (!post.h) throw py::value_error("acc_fmllr_stats_post: the DevicePosteriors are closed");
+    if (utt2spk.size() != n_utt) throw py::value_error("acc_fmllr_stats_post: one speaker per utterance");
+    Check(NoGil([&] { return khg_acc_fmllr_stats_post(ctx->h, m.h, tm.h, h, post.h, scale, utt2spk.data(), stats.h); }));
+  }
+  // transform-feats (khg_utts_transform_feats): W [n_spk, dim, dim + 1] from the host or, as an integer, a device pointer; out: a device
+  // pointer for the transformed rows, or None for the set's own rows in place
+  void transform_feats(Arr<int32_t> utt2spk, py::object W, py::object out, int n_spk) {
+    if (utt2spk.size() != n_utt) throw py::value_error("transform_feats: one speaker per utterance");
+    const float *wh = nullptr, *wd = nullptr;
+    Arr<float> wa;
+    if (py::isinstance<py::int_>(W)) {
+      if (n_spk < 1) throw py::value_error("transform_feats: n_spk is required with a device pointer");
+      wd = reinterpret_cast<const float*>(W.cast<uintptr_t>());
+    } else {
+      wa = W.cast<Arr<float>>();
+      if (wa.ndim() != 3 || wa.shape(1) != dim || wa.shape(2) != dim + 1) throw py::value_error("transform_feats: W must be [n_spk, dim, dim + 1]");
+      n_spk = (int)wa.shape(0);
+      wh = wa.data();
+    }
+    float* od = out.is_none() ? nullptr : reinterpret_cast<float*>(out.cast<uintptr_t>());
+    Check(NoGil([&] { return khg_utts_transform_feats(ctx->h, h, n_spk, utt2spk.data(), wh, wd, od); }));
+  }
 };
 
 }  // namespace
@@ -858,7 +926,21 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
            py::arg("scale") = 1.0f)
       .def("acc_stats_reduce", &KUtts::acc_stats_reduce, py::arg("model"), py::arg("tm"), py::arg("accs"), py::arg("weight") = 1.0f,
            py::arg("comm") = py::none(), py::arg("nparts") = 4)
+      .def("acc_fmllr_stats_post", &KUtts::acc_fmllr_stats_post, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("utt2spk"), py::arg("stats"),
+           py::arg("scale") = 1.0f)
+      .def("transform_feats", &KUtts::transform_feats, py::arg("utt2spk"), py::arg("W"), py::arg("out") = py::none(), py::arg("n_spk") = 0)
       .def("close", &KUtts::close);
+
+  py::class_<KFmllrStats>(m, "DeviceFmllrStats")
+      .def(py::init<py::object, int, int>(), py::arg("ctx"), py::arg("n_spk"), py::arg("dim"))
+      .def_property_readonly("h", [](KFmllrStats& x) { return reinterpret_cast<uintptr_t>(x.h); })
+      .def_readonly("ctx", &KFmllrStats::ctx_obj).def_readonly("n_spk", &KFmllrStats::n_spk).def_readonly("dim", &KFmllrStats::dim)
+      .def("zero", &KFmllrStats::zero).def("download", &KFmllrStats::download)
+      .def("upload", &KFmllrStats::upload, py::arg("beta"), py::arg("K"), py::arg("G"))
+      .def("add", &KFmllrStats::add, py::arg("scale"), py::arg("src"))
+      .def("estimate", &KFmllrStats::estimate, py::arg("min_count") = 500.0, py::arg("num_iters") = 40, py::arg("W_d") = py::none())
+      .def("set_chunk_frames", &KFmllrStats::set_chunk_frames, py::arg("frames")).def("num_chunks", &KFmllrStats::num_chunks)
+      .def("close", &KFmllrStats::close);
 
   // ---- host-side functions (no GPU): gconsts, M-step, merge, transition update, AddTransitionProbs costs ----
   m.def("compute_gconsts", [](Arr<int32_t> go, Arr<float> w, Arr<float> iv, Arr<float> miv) {
@@ -880,6 +962,26 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
     d["num_gauss"] = G; d["weights"] = w2; d["gconsts"] = gc; d["means_invvars"] = miv2; d["inv_vars"] = iv2; d["history"] = hist;
     return d;
   }, "DiagGmm::Merge (csrc/diag-gmm.cc:557-759): the first num_gauss rows of the returned arrays are the merged model");
+  m.def("fmllr_compute", [](Arr<double> beta, Arr<double> K, Arr<double> G, double min_count, int num_iters) {
+    if (K.ndim() != 3 || G.ndim() != 3 || K.shape(0) != beta.shape(0) || G.shape(0) != beta.shape(0) || K.shape(2) != K.shape(1) + 1 ||
+        G.shape(1) != K.shape(1) || G.shape(2) != (K.shape(1) + 1) * (K.shape(1) + 2) / 2)
+      throw py::value_error("fmllr_compute: beta [n_spk], K [n_spk, dim, dim + 1], G [n_spk, dim, (dim + 1)(dim + 2) / 2]");
+    const py::ssize_t S = beta.shape(0), D = K.shape(1);
+    khg_fmllr_options o;
+    khg_fmllr_options_default(&o);
+    o.min_count = min_count; o.num_iters = num_iters;
+    Arr<float> W({S, D, D + 1});
+    Arr<double> W64({S, D, D + 1}), impr({S}), count({S});
+    Arr<int32_t> status({S});
+    Check(NoGil([&] { return khg_fmllr_compute(&o, (int32_t)S, (int32_t)D, beta.data(), K.data(), G.data(), W.mutable_data(), W64.mutable_data(),
+                                               impr.mutable_data(), count.mutable_data(), status.mutable_data()); }));
+    py::dict d;
+    d["W"] = W; d["W64"] = W64; d["objf_impr"] = impr; d["count"] = count; d["status"] = status;
+    return d;
+  }, py::arg("beta"), py::arg("K"), py::arg("G"), py::arg("min_count") = 500.0, py::arg("num_iters") = 40,
+     "ComputeFmllrMatrixDiagGmmFull per speaker on host statistics (khg_fmllr_compute; DESIGN.md 7l)");
+  m.attr("FMLLR_OK") = KHG_FMLLR_OK; m.attr("FMLLR_LOW_COUNT") = KHG_FMLLR_LOW_COUNT; m.attr("FMLLR_SINGULAR") = KHG_FMLLR_SINGULAR;
+  m.attr("FMLLR_MAX_DIM") = KHG_FMLLR_MAX_DIM;
   m.def("scaled_trans_cost", [](Arr<float> lp, Arr<float> nsl, Arr<int32_t> id2state, Arr<uint8_t> isl, float ts, float sls) {
     const int nt = (int)lp.shape(0) - 1;
     Arr<float> out({(py::ssize_t)nt + 1});

@@ -26,6 +26,7 @@ DeviceModel = _ext.DeviceModel              # AmDiagGmm resident in HBM (+ mle_u
 DeviceTransitions = _ext.DeviceTransitions  # TransitionIdToPdf + scaled transition costs
 UtteranceSet = _ext.UtteranceSet            # features + compiled graphs of a shard; loglikes / align / acc_stats
 DecodingGraph = _ext.DecodingGraph          # khg_graph: ONE decoding graph resident in HBM, shared by sets (graph=) and batch calls
+DeviceFmllrStats = _ext.DeviceFmllrStats    # khg_fmllr_stats: FmllrDiagGmmAccs per speaker in HBM; download() -> numpy beta / K / G
 
 
 class DeviceAccs(_ext.DeviceAccs):
