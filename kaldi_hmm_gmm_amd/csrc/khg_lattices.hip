@@ -2,8 +2,9 @@
 // (khg_decode_lattice_faster, khg_k2_lattice.hip.inc) and the data-parallel LatticeSimpleDecoder (khg_decode_lattice_simple,
 // khg_k2_lattice_simple.hip.inc), each with its raw lattice (khg_decode_lattice_faster_raw, khg_k2_lattice_faster_raw.hip.inc;
 // khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc); the handle of resident lattices (khg_lattices) with the operations on it
-// (khg_k2_lattice_ops.hip.inc), its forward-backward posteriors (khg_posteriors, khg_k2_lattice_post.hip.inc), and rescoring / boosting
-// (khg_lattices_rescore, khg_lattices_boost: khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc).  gfx950 only.
+// (khg_k2_lattice_ops.hip.inc), its forward-backward posteriors (khg_posteriors, khg_k2_lattice_post.hip.inc) and their MPE / sMBR form
+// (khg_k2_lattice_mpe.hip.inc: the same device functions and the same host steps per chunk around a kernel of its own), and rescoring /
+// boosting (khg_lattices_rescore, khg_lattices_boost: khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
 
 #include <memory>
@@ -111,6 +112,16 @@ int read_pair_offsets(khg_ctx* ctx, const int64_t* off_d, int n, std::vector<int
   first->assign(h.begin(), h.begin() + n + 1);
   second->assign(h.begin() + n + 1, h.end());
   return KHG_OK;
+}
+// the exclusive prefixes of n pairs tot_d [2 n] (k2_lattice_scan_pairs, timed as `timer_name`) to off_d, and read_pair_offsets of them
+int scan_pairs_and_read(khg_ctx* ctx, const char* timer_name, const int64_t* tot_d, int64_t* off_d, int n, std::vector<int64_t>* first,
+                        std::vector<int64_t>* second) {
+  {
+    KernelTimer kt(ctx, timer_name);
+    KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, tot_d, off_d, n);
+    HIPCHK(hipGetLastError());
+  }
+  return read_pair_offsets(ctx, off_d, n, first, second);
 }
 // a lattice's arc_begin and nextstate are int32: utterance ids[b] (nullptr: u0 + b) of a chunk with the prefix arrays so / ao is refused
 // in the name of `who` when it has more states or arcs
@@ -312,14 +323,9 @@ struct FasterRun {
 // the utterances, ONE synchronisation to size the output, the fill
 int faster_emit(FasterRun& r, const std::vector<int32_t>& list, int k0, int n, EmitBlocks* blocks) {
   khg_ctx* ctx = r.ctx;
-  {
-    KernelTimer kt(ctx, "k2_lattice_faster_raw_scan");
-    KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, r.tot_d, r.off_d, n);
-    HIPCHK(hipGetLastError());
-  }
   blocks->v.emplace_back();
   EmitBlock& eb = blocks->v.back();
-  int rc = read_pair_offsets(ctx, r.off_d, n, &eb.so, &eb.ao);
+  int rc = scan_pairs_and_read(ctx, "k2_lattice_faster_raw_scan", r.tot_d, r.off_d, n, &eb.so, &eb.ao);
   if (!rc) rc = check_utt_counts(r.who, list.data() + k0, 0, eb.so, eb.ao);
   if (rc) return rc;
   LatChunk& ch = eb.ch;
@@ -557,11 +563,10 @@ int simple_emit(khg_ctx* ctx, LrArgs p, int u0, int nt, int64_t max_T, khg_latti
   {
     KernelTimer kt(ctx, "k2_lattice_raw_scan");
     KHG_LAUNCH(ctx, k2_lattice_raw_scan_frames, dim3((unsigned)n), dim3(64), 0, ctx->stream, p, u0);
-    KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, p.utt_tot, p.utt_off, n);
     HIPCHK(hipGetLastError());
   }
   std::vector<int64_t> so, ao;
-  int rc = read_pair_offsets(ctx, p.utt_off, n, &so, &ao);
+  int rc = scan_pairs_and_read(ctx, "k2_lattice_raw_scan", p.utt_tot, p.utt_off, n, &so, &ao);
   if (!rc) rc = add_chunk_counts("khg_decode_lattice_simple_raw", u0, so, ao, &lats->state_off, &lats->arc_off);
   if (rc) return rc;
   LatChunk ch;
@@ -945,12 +950,7 @@ extern "C" int khg_lattices_prune(khg_ctx* ctx, const khg_lattices* lc, float gr
       KHG_LAUNCH(ctx, k2_lattice_prune_mark, dim3((unsigned)c.n), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, p);
       HIPCHK(hipGetLastError());
     }
-    {
-      KernelTimer kt(ctx, "k2_lattice_prune_scan");
-      KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, p.utt_tot, p.utt_off, c.n);
-      HIPCHK(hipGetLastError());
-    }
-    rc = read_pair_offsets(ctx, p.utt_off, c.n, &so, &ao);        // the one synchronisation that sizes the output
+    rc = scan_pairs_and_read(ctx, "k2_lattice_prune_scan", p.utt_tot, p.utt_off, c.n, &so, &ao);      // the one synchronisation that sizes the output
     if (!rc) rc = add_chunk_counts("khg_lattices_prune", c.u0, so, ao, &res->state_off, &res->arc_off);
     if (rc) return rc;
     LatChunk ch;
@@ -994,25 +994,57 @@ struct khg_posteriors {
 
 namespace {
 struct PostFree { void operator()(khg_posteriors* p) const { (void)khg_posteriors_destroy(p); } };
+using PostPtr = std::unique_ptr<khg_posteriors, PostFree>;
+// an empty handle of U utterances: every offset 0
+void new_posteriors(khg_ctx* ctx, int U, PostPtr* out) {
+  out->reset(new khg_posteriors);
+  (*out)->U = U; (*out)->ctx = ctx;
+  (*out)->frame_off.assign((size_t)U + 1, 0);
+  (*out)->entry_off.assign((size_t)U + 1, 0);
+  (*out)->arc_off.assign((size_t)U + 1, 0);
+}
+// the entry block of a chunk whose nf and ne are set: entry_begin | weight | tid, each at a multiple of 256 bytes; its size is added to *bytes
+int post_chunk_alloc(PostChunk* q, int64_t* bytes) {
+  q->o_weight = (8 * (q->nf + 1) + 255) & ~int64_t(255);
+  q->o_tid = q->o_weight + ((8 * q->ne + 255) & ~int64_t(255));
+  const int64_t total = q->o_tid + 4 * q->ne;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&q->buf), (size_t)std::max<int64_t>(total, 16)));
+  *bytes += total;
+  return KHG_OK;
+}
+struct PostArrays { int64_t* entry_begin; double* weight; int32_t* tid; };
+PostArrays post_chunk_arrays(const PostChunk& c) {
+  return {reinterpret_cast<int64_t*>(c.buf), reinterpret_cast<double*>(c.buf + c.o_weight), reinterpret_cast<int32_t*>(c.buf + c.o_tid)};
+}
+
+// The in-arc index block of a lattice chunk (int32): in_begin [ns + n] (N + 1 per utterance) | in_arc [na] | arc_src [na]
+struct LatIndex { int32_t *in_begin, *in_arc, *arc_src; };
+int64_t lat_index_words(const LatChunk& c) { return c.ns + c.n + 2 * c.na; }
+LatIndex lat_index_arrays(int32_t* blk, const LatChunk& c) { return {blk, blk + c.ns + c.n, blk + c.ns + c.n + c.na}; }
+// chunk c's block, as the next of l's; counted in l's bytes
+int lat_index_alloc(khg_lattices* l, const LatChunk& c, int32_t** blk) {
+  *blk = nullptr;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(blk), (size_t)std::max<int64_t>(4 * lat_index_words(c), 16)));
+  l->idx_d.push_back(*blk);
+  l->bytes += 4 * lat_index_words(c);
+  return KHG_OK;
+}
 // the in-arc index, once per handle
 int lat_index(khg_ctx* ctx, khg_lattices* l) {
   if (l->idx_d.size() == l->chunks.size()) return KHG_OK;
   DevBlocks dv;
   for (size_t k = l->idx_d.size(); k < l->chunks.size(); ++k) {
     const LatChunk& c = l->chunks[k];
-    const int64_t words = c.ns + c.n + 2 * c.na;
-    int32_t* blk = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&blk), (size_t)std::max<int64_t>(4 * words, 16)));
-    l->idx_d.push_back(blk);
-    l->bytes += 4 * words;
-    int32_t* cur = nullptr;
-    int rc = dv.alloc(std::max<int64_t>(c.ns, 1), &cur);
+    int32_t *blk, *cur = nullptr;
+    int rc = lat_index_alloc(l, c, &blk);
+    if (!rc) rc = dv.alloc(std::max<int64_t>(c.ns, 1), &cur);
     if (rc) return rc;
+    const LatIndex ix = lat_index_arrays(blk, c);
     LoArgs p;
     std::memset(&p, 0, sizeof(p));
     lat_chunk_args(l, c, &p);
     KernelTimer kt(ctx, "k2_lattice_post_index");
-    KHG_LAUNCH(ctx, k2_lattice_post_index, dim3((unsigned)c.n), dim3(64), 0, ctx->stream, p, blk, blk + c.ns + c.n, blk + c.ns + c.n + c.na, cur);
+    KHG_LAUNCH(ctx, k2_lattice_post_index, dim3((unsigned)c.n), dim3(64), 0, ctx->stream, p, ix.in_begin, ix.in_arc, ix.arc_src, cur);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));       // the cursors go with `dv`
@@ -1065,90 +1097,119 @@ extern "C" int khg_posteriors_download(khg_ctx* ctx, const khg_posteriors* p, in
   return KHG_OK;
 }
 
+namespace {
+// One call of khg_lattices_posteriors / khg_lattices_mpe_posteriors: what its chunks share.  Per chunk the caller runs post_chunk_begin,
+// its own kernel (k2_lattice_post_fb, k2_lattice_post_mpe) under its own timer, and post_chunk_finish; post_run_finish ends the call.
+struct PostRun {
+  khg_ctx* ctx; khg_lattices* l;
+  const char* who;                     // the call that the errors name
+  double gs, as;
+  PostPtr res;
+  DevBlocks dv;                        // the call's scratch, every chunk's: freed on the way out
+  int32_t* status_d = nullptr; double* tot_d = nullptr; int64_t* ali_off_d = nullptr;      // [U], [U], [U + 1]
+};
+// (U > 0, after lat_meta) the per-utterance results and the alignment layout on the device
+int post_run_begin(PostRun& r) {
+  const int U = r.l->U;
+  int rc;
+  if ((rc = r.dv.alloc(U, &r.status_d)) || (rc = r.dv.alloc(U, &r.tot_d)) || (rc = r.dv.alloc(U + 1, &r.ali_off_d))) return rc;
+  HIPCHK(hipMemcpyAsync(r.ali_off_d, r.l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, r.ctx->stream));
+  return KHG_OK;
+}
+// chunk k's kernel arguments (*p zeroed by the caller) with the scratch both kernels need, and the result's chunk with its arc_post.
+// per_state: the bytes a kernel keeps in LDS beside every staged state (its doubles: 24 or 40)
+int post_chunk_begin(PostRun& r, size_t k, int64_t per_state, PoArgs* p) {
+  khg_lattices* l = r.l;
+  const LatChunk& c = l->chunks[k];
+  lat_chunk_args(l, c, &p->lo);
+  p->lo.lds_bytes = lat_chunk_lds(r.ctx, l, c, per_state);
+  p->lo.status = r.status_d; p->lo.ali_off = r.ali_off_d; p->tot = r.tot_d;
+  const LatIndex ix = lat_index_arrays(l->idx_d[k], c);
+  p->in_begin = ix.in_begin; p->in_arc = ix.in_arc; p->arc_src = ix.arc_src;
+  p->gs = r.gs; p->as = r.as;
+  p->f_base = l->ali_off[(size_t)c.u0];
+  const int64_t nfr = l->ali_off[(size_t)c.u0 + c.n] - p->f_base;
+  const int64_t cells = std::max<int64_t>(c.ns, 1), arcs = std::max<int64_t>(c.na, 1);
+  int rc;
+  if ((rc = r.dv.alloc(cells, &p->alpha)) || (rc = r.dv.alloc(cells, &p->beta)) || (rc = r.dv.alloc(cells, &p->row)) || (rc = r.dv.alloc(arcs, &p->flag)) ||
+      (rc = r.dv.alloc(arcs, &p->rank)) || (rc = r.dv.alloc(std::max<int64_t>(nfr, 1), &p->fcnt)) || (rc = r.dv.alloc(nfr + 2 * (int64_t)c.n, &p->fstate)) ||
+      (rc = r.dv.alloc(2 * (int64_t)c.n, &p->lo.utt_tot)) || (rc = r.dv.alloc(2 * ((int64_t)c.n + 1), &p->lo.utt_off)))
+    return rc;
+  PostChunk pc;
+  pc.u0 = c.u0; pc.n = c.n; pc.na = c.na;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&pc.arc_post), (size_t)(8 * arcs)));
+  r.res->chunks.push_back(pc);
+  r.res->bytes += 8 * c.na;
+  p->arc_post = pc.arc_post;
+  return KHG_OK;
+}
+// after the chunk's kernel: the scan of its (frames, entries) pairs, the ONE synchronisation that sizes the entry block, the fill (which
+// sums arc_post as the kernel left it)
+int post_chunk_finish(PostRun& r, size_t k, PoArgs* p) {
+  khg_ctx* ctx = r.ctx;
+  const LatChunk& c = r.l->chunks[k];
+  std::vector<int64_t> fo, eo;       // frames at [b], entries at [n + 1 + b]
+  int rc = scan_pairs_and_read(ctx, "k2_lattice_post_scan", p->lo.utt_tot, p->lo.utt_off, c.n, &fo, &eo);
+  if (!rc) rc = add_chunk_counts(r.who, c.u0, fo, eo, &r.res->frame_off, &r.res->entry_off);
+  if (rc) return rc;
+  PostChunk& q = r.res->chunks.back();
+  q.nf = fo[(size_t)c.n]; q.ne = eo[(size_t)c.n];
+  if ((rc = post_chunk_alloc(&q, &r.res->bytes))) return rc;
+  const PostArrays pa = post_chunk_arrays(q);
+  p->entry_begin = pa.entry_begin; p->weight = pa.weight; p->tid = pa.tid;
+  KernelTimer kt(ctx, "k2_lattice_post_fill");
+  KHG_LAUNCH(ctx, k2_lattice_post_fill, dim3((unsigned)c.n, stripes(chunk_max(r.l->arc_off, c), PO_NT, c.n)), dim3(PO_NT), 0, ctx->stream, *p);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+// the statuses and totals back -- and one more double per utterance, extra_d to extra_h, when the caller has one -- and the handle out
+int post_run_finish(PostRun& r, int32_t* status_h, double* tot_like_h, const double* extra_d, double* extra_h, khg_posteriors** out) {
+  const size_t U = (size_t)r.l->U;
+  std::vector<int32_t> st(U);
+  std::vector<double> tl(U), ex(extra_d ? U : 0);
+  HIPCHK(hipMemcpyAsync(st.data(), r.status_d, 4 * U, hipMemcpyDeviceToHost, r.ctx->stream));
+  HIPCHK(hipMemcpyAsync(tl.data(), r.tot_d, 8 * U, hipMemcpyDeviceToHost, r.ctx->stream));
+  if (extra_d) HIPCHK(hipMemcpyAsync(ex.data(), extra_d, 8 * U, hipMemcpyDeviceToHost, r.ctx->stream));
+  int rc = check_err_flag(r.ctx, r.who);     // synchronises: the scratch goes with the run
+  if (rc) return rc;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (tot_like_h) std::copy(tl.begin(), tl.end(), tot_like_h);
+  if (extra_h) std::copy(ex.begin(), ex.end(), extra_h);
+  if ((rc = post_frame_off_upload(r.ctx, r.res.get()))) return rc;
+  *out = r.res.release();
+  return KHG_OK;
+}
+}  // namespace
+
 extern "C" int khg_lattices_posteriors(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, int32_t* status_h,
                                        double* tot_like_h, khg_posteriors** out) {
   if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, "khg_lattices_posteriors: bad arguments");
   *out = nullptr;
   if (bad_scale(graph_scale) || bad_scale(acoustic_scale))
     return khg_set_error(KHG_E_ARG, "khg_lattices_posteriors: graph_scale and acoustic_scale must be finite and >= 0");
-  khg_lattices* l = const_cast<khg_lattices*>(lc);
-  const int U = l->U;
-  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
-  res->U = U; res->ctx = ctx;
-  res->frame_off.assign((size_t)U + 1, 0);
-  res->entry_off.assign((size_t)U + 1, 0);
-  res->arc_off = l->arc_off;
-  if (U == 0) { *out = res.release(); return KHG_OK; }
+  PostRun r;
+  r.ctx = ctx; r.l = const_cast<khg_lattices*>(lc); r.who = "khg_lattices_posteriors";
+  r.gs = (double)graph_scale; r.as = (double)acoustic_scale;
+  new_posteriors(ctx, r.l->U, &r.res);
+  r.res->arc_off = r.l->arc_off;
+  if (r.l->U == 0) { *out = r.res.release(); return KHG_OK; }
   int rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (!rc) rc = lat_index(ctx, l);
+  if (!rc) rc = lat_meta(ctx, r.l);
+  if (!rc) rc = lat_index(ctx, r.l);
+  if (!rc) rc = post_run_begin(r);
   if (rc) return rc;
-  DevBlocks dv;
-  int32_t* status_d; double* tot_d; int64_t* ali_off_d;
-  if ((rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &tot_d)) || (rc = dv.alloc(U + 1, &ali_off_d))) return rc;
-  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
-  std::vector<int64_t> fo, eo;
-  for (size_t k = 0; k < l->chunks.size(); ++k) {
-    const LatChunk& c = l->chunks[k];
+  for (size_t k = 0; k < r.l->chunks.size(); ++k) {
     PoArgs p;
     std::memset(&p, 0, sizeof(p));
-    lat_chunk_args(l, c, &p.lo);
-    p.lo.lds_bytes = lat_chunk_lds(ctx, l, c, 24);       // alpha, beta and the Jacobi row (doubles) beside the staged lattice
-    p.lo.status = status_d; p.lo.ali_off = ali_off_d; p.tot = tot_d;
-    p.in_begin = l->idx_d[k]; p.in_arc = l->idx_d[k] + c.ns + c.n; p.arc_src = l->idx_d[k] + c.ns + c.n + c.na;
-    p.gs = (double)graph_scale; p.as = (double)acoustic_scale;
-    p.f_base = l->ali_off[(size_t)c.u0];
-    const int64_t nfr = l->ali_off[(size_t)c.u0 + c.n] - p.f_base;
-    const int64_t cells = std::max<int64_t>(c.ns, 1), arcs = std::max<int64_t>(c.na, 1);
-    if ((rc = dv.alloc(cells, &p.alpha)) || (rc = dv.alloc(cells, &p.beta)) || (rc = dv.alloc(cells, &p.row)) || (rc = dv.alloc(arcs, &p.flag)) ||
-        (rc = dv.alloc(arcs, &p.rank)) || (rc = dv.alloc(std::max<int64_t>(nfr, 1), &p.fcnt)) || (rc = dv.alloc(nfr + 2 * (int64_t)c.n, &p.fstate)) ||
-        (rc = dv.alloc(2 * (int64_t)c.n, &p.lo.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.lo.utt_off)))
-      return rc;
-    PostChunk pc;
-    pc.u0 = c.u0; pc.n = c.n; pc.na = c.na;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&pc.arc_post), (size_t)(8 * arcs)));
-    res->chunks.push_back(pc);
-    res->bytes += 8 * c.na;
-    p.arc_post = pc.arc_post;
+    if ((rc = post_chunk_begin(r, k, 24, &p))) return rc;       // alpha, beta and the Jacobi row (doubles) beside the staged lattice
     {
       KernelTimer kt(ctx, "k2_lattice_post_fb");
-      KHG_LAUNCH(ctx, k2_lattice_post_fb, dim3((unsigned)c.n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, p);
+      KHG_LAUNCH(ctx, k2_lattice_post_fb, dim3((unsigned)r.l->chunks[k].n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, p);
       HIPCHK(hipGetLastError());
     }
-    {
-      KernelTimer kt(ctx, "k2_lattice_post_scan");       // frames at [b], entries at [n + 1 + b]
-      KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, p.lo.utt_tot, p.lo.utt_off, c.n);
-      HIPCHK(hipGetLastError());
-    }
-    rc = read_pair_offsets(ctx, p.lo.utt_off, c.n, &fo, &eo);        // the one synchronisation that sizes the output
-    if (!rc) rc = add_chunk_counts("khg_lattices_posteriors", c.u0, fo, eo, &res->frame_off, &res->entry_off);
-    if (rc) return rc;
-    PostChunk& q = res->chunks.back();
-    q.nf = fo[(size_t)c.n]; q.ne = eo[(size_t)c.n];
-    q.o_weight = (8 * (q.nf + 1) + 255) & ~int64_t(255);
-    q.o_tid = q.o_weight + ((8 * q.ne + 255) & ~int64_t(255));
-    const int64_t total = q.o_tid + 4 * q.ne;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&q.buf), (size_t)std::max<int64_t>(total, 16)));
-    res->bytes += total;
-    p.entry_begin = reinterpret_cast<int64_t*>(q.buf); p.weight = reinterpret_cast<double*>(q.buf + q.o_weight);
-    p.tid = reinterpret_cast<int32_t*>(q.buf + q.o_tid);
-    {
-      KernelTimer kt(ctx, "k2_lattice_post_fill");
-      KHG_LAUNCH(ctx, k2_lattice_post_fill, dim3((unsigned)c.n, stripes(chunk_max(l->arc_off, c), PO_NT, c.n)), dim3(PO_NT), 0, ctx->stream, p);
-      HIPCHK(hipGetLastError());
-    }
+    if ((rc = post_chunk_finish(r, k, &p))) return rc;
   }
-  std::vector<int32_t> st((size_t)U);
-  std::vector<double> tl((size_t)U);
-  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(tl.data(), tot_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  rc = check_err_flag(ctx, "khg_lattices_posteriors");     // synchronises: the scratch goes with `dv`
-  if (rc) return rc;
-  if (status_h) std::copy(st.begin(), st.end(), status_h);
-  if (tot_like_h) std::copy(tl.begin(), tl.end(), tot_like_h);
-  if ((rc = post_frame_off_upload(ctx, res.get()))) return rc;
-  *out = res.release();
-  return KHG_OK;
+  return post_run_finish(r, status_h, tot_like_h, nullptr, nullptr, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1184,27 +1245,22 @@ extern "C" int khg_posteriors_upload(khg_ctx* ctx, int32_t n_utt, const int64_t*
   const int64_t F = frame_off_h[n_utt], E = entry_begin_h[F];
   int rc = khg_posteriors_validate(n_utt, frame_off_h, entry_begin_h, E, tid_h, weight_h);
   if (rc) return rc;
-  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
-  res->U = n_utt; res->ctx = ctx;
+  PostPtr res;
+  new_posteriors(ctx, n_utt, &res);
   res->frame_off.assign(frame_off_h, frame_off_h + n_utt + 1);
-  res->entry_off.resize((size_t)n_utt + 1);
   for (int u = 0; u <= n_utt; ++u) res->entry_off[(size_t)u] = entry_begin_h[frame_off_h[u]];
-  res->arc_off.assign((size_t)n_utt + 1, 0);
   res->max_tid = 0;
   for (int64_t e = 0; e < E; ++e) res->max_tid = std::max(res->max_tid, tid_h[e]);
   if (n_utt == 0) { *out = res.release(); return KHG_OK; }
   PostChunk q;
   q.u0 = 0; q.n = n_utt; q.nf = F; q.ne = E;
-  q.o_weight = (8 * (q.nf + 1) + 255) & ~int64_t(255);
-  q.o_tid = q.o_weight + ((8 * q.ne + 255) & ~int64_t(255));
-  const int64_t total = q.o_tid + 4 * q.ne;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&q.buf), (size_t)std::max<int64_t>(total, 16)));
+  if ((rc = post_chunk_alloc(&q, &res->bytes))) return rc;
   res->chunks.push_back(q);
-  res->bytes += total;
-  HIPCHK(hipMemcpyAsync(q.buf, entry_begin_h, 8 * ((size_t)F + 1), hipMemcpyHostToDevice, ctx->stream));
+  const PostArrays pa = post_chunk_arrays(q);
+  HIPCHK(hipMemcpyAsync(pa.entry_begin, entry_begin_h, 8 * ((size_t)F + 1), hipMemcpyHostToDevice, ctx->stream));
   if (E) {
-    HIPCHK(hipMemcpyAsync(q.buf + q.o_weight, weight_h, 8 * (size_t)E, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(q.buf + q.o_tid, tid_h, 4 * (size_t)E, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(pa.weight, weight_h, 8 * (size_t)E, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(pa.tid, tid_h, 4 * (size_t)E, hipMemcpyHostToDevice, ctx->stream));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));        // the caller's arrays are free again
   if ((rc = post_frame_off_upload(ctx, res.get()))) return rc;
@@ -1217,26 +1273,20 @@ extern "C" int khg_posteriors_upload(khg_ctx* ctx, int32_t n_utt, const int64_t*
 // handle's frame offsets on the device come back.  max_tid = -1: the ids are checked where they are read, as a lattice's are.
 int posteriors_make_unit(khg_ctx* ctx, int32_t n_utt, const int64_t* frame_off_h, int64_t** entry_begin_d, double** weight_d, int32_t** tid_d,
                          const int64_t** frame_off_d, khg_posteriors** out) {
-  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
-  res->U = n_utt; res->ctx = ctx;
+  PostPtr res;
+  new_posteriors(ctx, n_utt, &res);
   res->frame_off.assign(frame_off_h, frame_off_h + n_utt + 1);
   res->entry_off = res->frame_off;
-  res->arc_off.assign((size_t)n_utt + 1, 0);
-  res->max_tid = -1;
   *entry_begin_d = nullptr; *weight_d = nullptr; *tid_d = nullptr; *frame_off_d = nullptr;
   if (n_utt == 0) { *out = res.release(); return KHG_OK; }
   PostChunk q;
   q.u0 = 0; q.n = n_utt; q.nf = q.ne = frame_off_h[n_utt];
-  q.o_weight = (8 * (q.nf + 1) + 255) & ~int64_t(255);
-  q.o_tid = q.o_weight + ((8 * q.ne + 255) & ~int64_t(255));
-  const int64_t total = q.o_tid + 4 * q.ne;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&q.buf), (size_t)std::max<int64_t>(total, 16)));
-  res->chunks.push_back(q);
-  res->bytes += total;
-  int rc = post_frame_off_upload(ctx, res.get());
+  int rc = post_chunk_alloc(&q, &res->bytes);
   if (rc) return rc;
-  *entry_begin_d = reinterpret_cast<int64_t*>(q.buf); *weight_d = reinterpret_cast<double*>(q.buf + q.o_weight);
-  *tid_d = reinterpret_cast<int32_t*>(q.buf + q.o_tid); *frame_off_d = res->frame_off_d;
+  res->chunks.push_back(q);
+  if ((rc = post_frame_off_upload(ctx, res.get()))) return rc;
+  const PostArrays pa = post_chunk_arrays(q);
+  *entry_begin_d = pa.entry_begin; *weight_d = pa.weight; *tid_d = pa.tid; *frame_off_d = res->frame_off_d;
   *out = res.release();
   return KHG_OK;
 }
@@ -1255,6 +1305,8 @@ struct PostFlatArgs {
   int64_t nf, ne;
   int32_t n, num_tids;
   double scale;
+  int32_t sign;                     // khg_acc_stats_post2's selection: > 0 the positive weights as they are, < 0 the negative ones as |w|,
+                                    // the others 0; 0: every weight as it is
   int32_t* e_row; int32_t* e_tid; float* e_w;      // at the chunk's first entry
   int32_t* err_flag;
 };
@@ -1282,16 +1334,8 @@ __global__ __launch_bounds__(256) void k3_post_flatten(PostFlatArgs p) {
     // |scale * w64| beyond float: an infinite weight would poison the block unseen (only ll is checked later): dropped like a bad id,
     // and the error word says overflow
     if (!(fabsf(w) <= 3.0e38f)) { atomicOr(p.err_flag, 1); tid = 0; w = 0.0f; }
+    if (p.sign != 0) w = p.sign > 0 ? (w > 0.0f ? w : 0.0f) : (w < 0.0f ? -w : 0.0f);
     p.e_row[e] = (int32_t)row; p.e_tid[e] = tid; p.e_w[e] = w;
-  }
-}
-// khg_acc_stats_post2's sign selection over a chunk's flattened weights, in place: the entries of the wanted sign keep |w|, the others
-// get 0.  A kernel of its own, so that what khg_acc_stats_post launches stays the code it was.
-__global__ __launch_bounds__(256) void k3_post_sign(float* __restrict__ e_w, int64_t ne, int32_t sign) {
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < ne; e += stride) {
-    const float w = e_w[e];
-    e_w[e] = sign > 0 ? (w > 0.0f ? w : 0.0f) : (w < 0.0f ? -w : 0.0f);
   }
 }
 int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set_frame_off_d, double scale, int32_t num_tids, int32_t* e_row,
@@ -1302,17 +1346,13 @@ int posteriors_flatten(khg_ctx* ctx, const khg_posteriors* p, const int64_t* set
     if (c.ne == 0) continue;
     const int64_t e0 = p->entry_off[(size_t)c.u0];
     PostFlatArgs a;
-    a.entry_begin = reinterpret_cast<const int64_t*>(c.buf); a.weight = reinterpret_cast<const double*>(c.buf + c.o_weight);
-    a.tid = reinterpret_cast<const int32_t*>(c.buf + c.o_tid);
+    const PostArrays pa = post_chunk_arrays(c);
+    a.entry_begin = pa.entry_begin; a.weight = pa.weight; a.tid = pa.tid;
     a.post_frame_off = p->frame_off_d + c.u0; a.set_frame_off = set_frame_off_d + c.u0;
-    a.nf = c.nf; a.ne = c.ne; a.n = c.n; a.num_tids = num_tids; a.scale = scale;
+    a.nf = c.nf; a.ne = c.ne; a.n = c.n; a.num_tids = num_tids; a.scale = scale; a.sign = (int32_t)sign;
     a.e_row = e_row + e0; a.e_tid = e_tid + e0; a.e_w = e_w + e0; a.err_flag = ctx->err_flag_d;
     KHG_LAUNCH(ctx, k3_post_flatten, dim3((unsigned)std::min<int64_t>(4096, (c.ne + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
-    if (sign != 0) {
-      KHG_LAUNCH(ctx, k3_post_sign, dim3((unsigned)std::min<int64_t>(4096, (c.ne + 255) / 256)), dim3(256), 0, ctx->stream, a.e_w, c.ne, (int32_t)sign);
-      HIPCHK(hipGetLastError());
-    }
   }
   return KHG_OK;
 }
@@ -1370,12 +1410,9 @@ int lat_clone(khg_ctx* ctx, const khg_lattices* l, const std::vector<char>& drop
     if (!l->chunks.empty() && l->idx_d.size() == l->chunks.size()) {
       for (size_t k = 0; k < l->chunks.size(); ++k) {
         const LatChunk& c = l->chunks[k];
-        const int64_t words = c.ns + c.n + 2 * c.na;
-        int32_t* blk = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&blk), (size_t)std::max<int64_t>(4 * words, 16)));
-        r->idx_d.push_back(blk);
-        r->bytes += 4 * words;
-        HIPCHK(hipMemcpyAsync(blk, l->idx_d[k], 4 * (size_t)words, hipMemcpyDeviceToDevice, ctx->stream));
+        int32_t* blk;
+        if ((rc = lat_index_alloc(r.get(), c, &blk))) return rc;
+        HIPCHK(hipMemcpyAsync(blk, l->idx_d[k], 4 * (size_t)lat_index_words(c), hipMemcpyDeviceToDevice, ctx->stream));
       }
     }
   }
@@ -1651,8 +1688,8 @@ extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t 
 }
 
 // ------------------------------------------------------------------------------------------
-// K2M: MPE / sMBR posteriors (khg_k2_lattice_mpe.hip.inc): khg_lattices_posteriors' launches with k2_lattice_post_mpe in
-// k2_lattice_post_fb's place; the handle's arc_post and weights are the signed values.
+// K2M: MPE / sMBR posteriors (khg_k2_lattice_mpe.hip.inc): khg_lattices_posteriors' chunk steps around k2_lattice_post_mpe
+// in k2_lattice_post_fb's place; the handle's arc_post and weights are the signed values.
 extern "C" int khg_lattices_mpe_posteriors(khg_ctx* ctx, const khg_lattices* lc, int32_t num_tids, const int32_t* tid2phone_h, const int32_t* tid2pdf_h,
                                            int32_t n_sil, const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h,
                                            const khg_utts* ali_set, int32_t criterion, int32_t one_silence_class, float graph_scale, float acoustic_scale,
@@ -1665,96 +1702,42 @@ extern "C" int khg_lattices_mpe_posteriors(khg_ctx* ctx, const khg_lattices* lc,
   if (criterion != KHG_MPE_MPFE && criterion != KHG_MPE_SMBR) return khg_set_error(KHG_E_ARG, who + "unknown criterion " + std::to_string(criterion));
   if (criterion == KHG_MPE_SMBR && !tid2pdf_h) return khg_set_error(KHG_E_ARG, who + "KHG_MPE_SMBR needs tid2pdf_h");
   if (bad_scale(graph_scale) || bad_scale(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "graph_scale and acoustic_scale must be finite and >= 0");
-  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  PostRun r;
+  r.ctx = ctx; r.l = const_cast<khg_lattices*>(lc); r.who = "khg_lattices_mpe_posteriors";
+  r.gs = (double)graph_scale; r.as = (double)acoustic_scale;
+  khg_lattices* l = r.l;
   const int U = l->U;
   LatRef ref;
   int rc = lat_ref_check(who, ctx, l, num_tids, criterion == KHG_MPE_SMBR ? tid2pdf_h : tid2phone_h, tid2phone_h, n_sil, silence_phones_h, ali_off_h, ali_h,
                          ali_set, &ref);
   if (rc) return rc;
-  std::unique_ptr<khg_posteriors, PostFree> res(new khg_posteriors);
-  res->U = U; res->ctx = ctx;
-  res->frame_off.assign((size_t)U + 1, 0);
-  res->entry_off.assign((size_t)U + 1, 0);
-  res->arc_off = l->arc_off;
-  if (U == 0) { *out = res.release(); return KHG_OK; }
+  new_posteriors(ctx, U, &r.res);
+  r.res->arc_off = l->arc_off;
+  if (U == 0) { *out = r.res.release(); return KHG_OK; }
   rc = arena_flush(ctx);
   if (!rc) rc = lat_meta(ctx, l);
   if (!rc) rc = lat_ref_device(who, ctx, l, num_tids, ali_off_h, ali_h, ali_set, &ref);
   if (!rc) rc = lat_index(ctx, l);
+  if (!rc) rc = post_run_begin(r);
   if (rc) return rc;
-  DevBlocks dv;
-  int32_t *status_d, *no_ref_d; double *tot_d, *avg_d; int64_t* ali_off_d;
-  if ((rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &tot_d)) || (rc = dv.alloc(U, &avg_d)) || (rc = dv.alloc(U, &no_ref_d)) ||
-      (rc = dv.alloc(U + 1, &ali_off_d)))
-    return rc;
+  int32_t* no_ref_d; double* avg_d;
+  if ((rc = r.dv.alloc(U, &avg_d)) || (rc = r.dv.alloc(U, &no_ref_d))) return rc;
   std::vector<int32_t> no_ref(ref.drop.begin(), ref.drop.end());
-  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(no_ref_d, no_ref.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
-  std::vector<int64_t> fo, eo;
   for (size_t k = 0; k < l->chunks.size(); ++k) {
     const LatChunk& c = l->chunks[k];
     PoMpeArgs q;
     std::memset(&q, 0, sizeof(q));
-    PoArgs& p = q.po;
-    lat_chunk_args(l, c, &p.lo);
-    p.lo.lds_bytes = lat_chunk_lds(ctx, l, c, 40);       // alpha, beta, the Jacobi row, A and B (doubles) beside the staged lattice
-    p.lo.status = status_d; p.lo.ali_off = ali_off_d; p.tot = tot_d;
-    p.in_begin = l->idx_d[k]; p.in_arc = l->idx_d[k] + c.ns + c.n; p.arc_src = l->idx_d[k] + c.ns + c.n + c.na;
-    p.gs = (double)graph_scale; p.as = (double)acoustic_scale;
-    p.f_base = l->ali_off[(size_t)c.u0];
+    if ((rc = post_chunk_begin(r, k, 40, &q.po))) return rc;       // alpha, beta, the Jacobi row, A and B (doubles) beside the staged lattice
     q.ref = ref.ali_d; q.ref_off = ref.aoff_d; q.tab = ref.tab_d; q.no_ref = no_ref_d; q.avg = avg_d; q.one_silence_class = one_silence_class != 0;
-    const int64_t nfr = l->ali_off[(size_t)c.u0 + c.n] - p.f_base;
-    const int64_t cells = std::max<int64_t>(c.ns, 1), arcs = std::max<int64_t>(c.na, 1);
-    if ((rc = dv.alloc(cells, &p.alpha)) || (rc = dv.alloc(cells, &p.beta)) || (rc = dv.alloc(cells, &p.row)) || (rc = dv.alloc(cells, &q.accA)) ||
-        (rc = dv.alloc(cells, &q.accB)) || (rc = dv.alloc(arcs, &p.flag)) || (rc = dv.alloc(arcs, &p.rank)) ||
-        (rc = dv.alloc(std::max<int64_t>(nfr, 1), &p.fcnt)) || (rc = dv.alloc(nfr + 2 * (int64_t)c.n, &p.fstate)) ||
-        (rc = dv.alloc(2 * (int64_t)c.n, &p.lo.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.lo.utt_off)))
-      return rc;
-    PostChunk pc;
-    pc.u0 = c.u0; pc.n = c.n; pc.na = c.na;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&pc.arc_post), (size_t)(8 * arcs)));
-    res->chunks.push_back(pc);
-    res->bytes += 8 * c.na;
-    p.arc_post = pc.arc_post;
+    const int64_t cells = std::max<int64_t>(c.ns, 1);
+    if ((rc = r.dv.alloc(cells, &q.accA)) || (rc = r.dv.alloc(cells, &q.accB))) return rc;
     {
       KernelTimer kt(ctx, "k2_lattice_post_mpe");
-      KHG_LAUNCH(ctx, k2_lattice_post_mpe, dim3((unsigned)c.n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, q);
+      KHG_LAUNCH(ctx, k2_lattice_post_mpe, dim3((unsigned)c.n), dim3(PO_NT), (size_t)q.po.lo.lds_bytes, ctx->stream, q);
       HIPCHK(hipGetLastError());
     }
-    {
-      KernelTimer kt(ctx, "k2_lattice_post_scan");       // frames at [b], entries at [n + 1 + b]
-      KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, p.lo.utt_tot, p.lo.utt_off, c.n);
-      HIPCHK(hipGetLastError());
-    }
-    rc = read_pair_offsets(ctx, p.lo.utt_off, c.n, &fo, &eo);        // the one synchronisation that sizes the output
-    if (!rc) rc = add_chunk_counts("khg_lattices_mpe_posteriors", c.u0, fo, eo, &res->frame_off, &res->entry_off);
-    if (rc) return rc;
-    PostChunk& pq = res->chunks.back();
-    pq.nf = fo[(size_t)c.n]; pq.ne = eo[(size_t)c.n];
-    pq.o_weight = (8 * (pq.nf + 1) + 255) & ~int64_t(255);
-    pq.o_tid = pq.o_weight + ((8 * pq.ne + 255) & ~int64_t(255));
-    const int64_t total = pq.o_tid + 4 * pq.ne;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&pq.buf), (size_t)std::max<int64_t>(total, 16)));
-    res->bytes += total;
-    p.entry_begin = reinterpret_cast<int64_t*>(pq.buf); p.weight = reinterpret_cast<double*>(pq.buf + pq.o_weight);
-    p.tid = reinterpret_cast<int32_t*>(pq.buf + pq.o_tid);
-    {
-      KernelTimer kt(ctx, "k2_lattice_post_fill");       // the summed array is arc_post: here the signed values
-      KHG_LAUNCH(ctx, k2_lattice_post_fill, dim3((unsigned)c.n, stripes(chunk_max(l->arc_off, c), PO_NT, c.n)), dim3(PO_NT), 0, ctx->stream, p);
-      HIPCHK(hipGetLastError());
-    }
+    if ((rc = post_chunk_finish(r, k, &q.po))) return rc;       // the fill sums arc_post: here the signed values
   }
-  std::vector<int32_t> st((size_t)U);
-  std::vector<double> tl((size_t)U), av((size_t)U);
-  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(tl.data(), tot_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(av.data(), avg_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  rc = check_err_flag(ctx, "khg_lattices_mpe_posteriors");     // synchronises: the scratch goes with `dv` and `ref`
-  if (rc) return rc;
-  if (status_h) std::copy(st.begin(), st.end(), status_h);
-  if (tot_like_h) std::copy(tl.begin(), tl.end(), tot_like_h);
-  if (avg_acc_h) std::copy(av.begin(), av.end(), avg_acc_h);
-  if ((rc = post_frame_off_upload(ctx, res.get()))) return rc;
-  *out = res.release();
-  return KHG_OK;
+  return post_run_finish(r, status_h, tot_like_h, avg_d, avg_acc_h, out);       // synchronises: the scratch goes with `r` and `ref`
 }

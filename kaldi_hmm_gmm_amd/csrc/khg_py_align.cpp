@@ -297,6 +297,33 @@ std::pair<std::vector<int64_t>, std::vector<int64_t>> LatSizes(PyDeviceLattices&
   CApi(khg_lattices_sizes(d.h, so.data(), ao.data()));
   return {so, ao};
 }
+// what Lattice.forward_backward and .forward_backward_mpe share: status, tot_like, arc_post, alpha, beta, post (per frame [(tid, weight), ...])
+py::dict PosteriorsDict(const LatticePosteriors& r) {
+  py::dict d;
+  d["status"] = r.status; d["tot_like"] = r.tot_like; d["arc_post"] = Vec1(r.arc_post); d["alpha"] = Vec1(r.alpha); d["beta"] = Vec1(r.beta);
+  py::list post;
+  for (const auto& row : r.post) {
+    py::list e;
+    for (const auto& x : row) e.append(py::make_tuple(x.first, x.second));
+    post.append(e);
+  }
+  d["post"] = post;
+  return d;
+}
+// the reference of DeviceLattices.boost / .mpe_posteriors (`who` in the error text): None, or a list of U arrays of transition-ids ->
+// (aoff [U + 1], ali); aoff stays empty for None
+void FlattenAlignments(const std::string& who, py::object alignment, int U, std::vector<int64_t>* aoff, std::vector<int32_t>* ali) {
+  if (alignment.is_none()) return;
+  py::list al = alignment.cast<py::list>();
+  if ((int)al.size() != U) throw Error(who + ": " + std::to_string(al.size()) + " alignments for " + std::to_string(U) + " lattices");
+  aoff->assign(1, 0);
+  for (py::handle h : al) {
+    Arr<int32_t> a = py::reinterpret_borrow<py::object>(h).cast<Arr<int32_t>>();
+    ali->insert(ali->end(), a.data(), a.data() + a.size());
+    aoff->push_back((int64_t)ali->size());
+  }
+  ali->push_back(0);      // (never a NULL array)
+}
 }  // namespace
 
 void BindLattice(py::module_& m) {
@@ -349,17 +376,7 @@ void BindLattice(py::module_& m) {
       }, py::arg("beam"), py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       // what DeviceLattices.posteriors gives for this lattice: status, tot_like, arc_post, post (per frame [(tid, weight), ...]), alpha, beta
       .def("forward_backward", [](const Lattice& l, float gs, float as) {
-        const LatticePosteriors r = l.ForwardBackward(gs, as);
-        py::dict d;
-        d["status"] = r.status; d["tot_like"] = r.tot_like; d["arc_post"] = Vec1(r.arc_post); d["alpha"] = Vec1(r.alpha); d["beta"] = Vec1(r.beta);
-        py::list post;
-        for (const auto& row : r.post) {
-          py::list e;
-          for (const auto& x : row) e.append(py::make_tuple(x.first, x.second));
-          post.append(e);
-        }
-        d["post"] = post;
-        return d;
+        return PosteriorsDict(l.ForwardBackward(gs, as));
       }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       // what DeviceLattices.mpe_posteriors gives for this lattice: forward_backward's keys -- arc_post and post hold the
       // signed values -- plus avg_acc, acc_fwd (A) and acc_bwd (B)
@@ -367,16 +384,8 @@ void BindLattice(py::module_& m) {
                                       const std::string& criterion, std::vector<int32_t> tid2pdf, bool one_silence_class, float gs, float as) {
         if (criterion != "smbr" && criterion != "mpfe") throw Error("Lattice.forward_backward_mpe: criterion is \"smbr\" or \"mpfe\"");
         const LatticeMpePosteriors r = l.ForwardBackwardMpe(tid2phone, tid2pdf, silence_phones, alignment, criterion == "smbr", one_silence_class, gs, as);
-        py::dict d;
-        d["status"] = r.status; d["tot_like"] = r.tot_like; d["arc_post"] = Vec1(r.arc_post); d["alpha"] = Vec1(r.alpha); d["beta"] = Vec1(r.beta);
+        py::dict d = PosteriorsDict(r);
         d["avg_acc"] = r.avg_acc; d["acc_fwd"] = Vec1(r.acc_fwd); d["acc_bwd"] = Vec1(r.acc_bwd);
-        py::list post;
-        for (const auto& row : r.post) {
-          py::list e;
-          for (const auto& x : row) e.append(py::make_tuple(x.first, x.second));
-          post.append(e);
-        }
-        d["post"] = post;
         return d;
       }, py::arg("tid2phone"), py::arg("silence_phones"), py::arg("alignment"), py::arg("criterion") = "smbr", py::arg("tid2pdf") = std::vector<int32_t>(),
          py::arg("one_silence_class") = true, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
@@ -575,17 +584,7 @@ void BindLattice(py::module_& m) {
         const int U = (int)LatSizes(d).first.size() - 1;
         std::vector<int64_t> aoff;
         std::vector<int32_t> ali;
-        if (!alignment.is_none()) {
-          py::list al = alignment.cast<py::list>();
-          if ((int)al.size() != U) throw Error("DeviceLattices.boost: " + std::to_string(al.size()) + " alignments for " + std::to_string(U) + " lattices");
-          aoff.assign(1, 0);
-          for (py::handle h : al) {
-            Arr<int32_t> a = py::reinterpret_borrow<py::object>(h).cast<Arr<int32_t>>();
-            ali.insert(ali.end(), a.data(), a.data() + a.size());
-            aoff.push_back((int64_t)ali.size());
-          }
-          ali.push_back(0);      // (never a NULL array)
-        }
+        FlattenAlignments("DeviceLattices.boost", alignment, U, &aoff, &ali);
         const khg_utts* sh = ali_set.is_none() ? nullptr : reinterpret_cast<const khg_utts*>(ali_set.attr("h").cast<uintptr_t>());
         auto r = std::make_shared<PyDeviceLattices>();
         r->ctx = d.ctx; r->ctx_obj = d.ctx_obj;
@@ -620,17 +619,7 @@ void BindLattice(py::module_& m) {
         const int U = (int)so.first.size() - 1;
         std::vector<int64_t> aoff;
         std::vector<int32_t> ali;
-        if (!alignment.is_none()) {
-          py::list al = alignment.cast<py::list>();
-          if ((int)al.size() != U) throw Error("DeviceLattices.mpe_posteriors: " + std::to_string(al.size()) + " alignments for " + std::to_string(U) + " lattices");
-          aoff.assign(1, 0);
-          for (py::handle h : al) {
-            Arr<int32_t> a = py::reinterpret_borrow<py::object>(h).cast<Arr<int32_t>>();
-            ali.insert(ali.end(), a.data(), a.data() + a.size());
-            aoff.push_back((int64_t)ali.size());
-          }
-          ali.push_back(0);      // (never a NULL array)
-        }
+        FlattenAlignments("DeviceLattices.mpe_posteriors", alignment, U, &aoff, &ali);
         const khg_utts* sh = ali_set.is_none() ? nullptr : reinterpret_cast<const khg_utts*>(ali_set.attr("h").cast<uintptr_t>());
         auto r = std::make_shared<PyDevicePosteriors>();
         r->ctx = d.ctx; r->ctx_obj = d.ctx_obj; r->arc_off = so.second;
