@@ -936,6 +936,73 @@ int khg_posteriors_from_ali(khg_ctx *ctx, khg_utts *u, khg_posteriors **out);
 int khg_utts_transform_feats(khg_ctx *ctx, khg_utts *u, int32_t n_spk, const int32_t *utt2spk_h, const float *W_h, const float *W_d,
                              float *out_d);
 
+/* ---- MLLT / semi-tied covariance (gmm-acc-mllt, est-mllt, gmm-transform-means) ------------------------------------- */
+/* The reference has no MLLT: the rule in DESIGN.md 7m is the specification (tests/mllt_ref.py restates it).  One global dim x dim
+ * matrix M that makes the diagonal-covariance assumption fit: features become M x, means M mu.  Feature dimensions up to
+ * KHG_MLLT_MAX_DIM (the MFMA range of the fMLLR Gram kernel); above: KHG_E_UNSUPPORTED. */
+#define KHG_MLLT_MAX_DIM 80
+#define KHG_MLLT_OK 0            /* the transform was estimated                                                         */
+#define KHG_MLLT_SINGULAR 1      /* beta <= 0, or a pivot of some G[d] (or of A) not finite or not > 0: M = I           */
+/* Kaldi's MlltAccs resident on the device, all fp64: beta and G[dim], each G[d] a symmetric dim x dim matrix as Kaldi's packed lower
+ * triangle ((i, j <= i) at i (i + 1) / 2 + j): dim (dim + 1) / 2 doubles.  Host layout of download / upload: *beta_h, G_h[dim][packed];
+ * download takes NULL for what is not wanted and synchronises (deferred kernel errors: KHG_E_RUNTIME), upload needs both.
+ * add: dst += (double)scale * src elementwise (one product, one add), asynchronous; the handles must agree in dimension and belong
+ * to `ctx` (KHG_E_ARG). */
+typedef struct khg_mllt_stats khg_mllt_stats;
+int khg_mllt_stats_create(khg_ctx *ctx, int32_t dim, khg_mllt_stats **out);
+int khg_mllt_stats_destroy(khg_mllt_stats *s);
+int khg_mllt_stats_zero(khg_ctx *ctx, khg_mllt_stats *s);
+int khg_mllt_stats_download(khg_ctx *ctx, const khg_mllt_stats *s, double *beta_h, double *G_h);
+int khg_mllt_stats_upload(khg_ctx *ctx, khg_mllt_stats *s, const double *beta_h, const double *G_h);
+int khg_mllt_stats_add(khg_ctx *ctx, khg_mllt_stats *dst, float scale, const khg_mllt_stats *src);
+/* The frame side's scratch is bounded by a chunk of `frames` frames exactly as khg_fmllr_stats_set_chunk_frames bounds fMLLR's (the
+ * per-frame and per-entry vectors are the same; a parked slice image is dim^2 (dim + 1) / 2 + 1 doubles here).  The statistics do not
+ * depend on it, bit for bit.  num_chunks: how many chunks the last accumulation into the handle ran (tests). */
+int khg_mllt_stats_set_chunk_frames(khg_mllt_stats *s, int64_t frames);
+int khg_mllt_stats_num_chunks(const khg_mllt_stats *s, int32_t *n_chunks);
+/* gmm-acc-mllt from posteriors resident on the device, over ALL the data (no random pruning).  Every entry of `p` counts with
+ * w = (float)((double)scale * w64) and the component posteriors gamma_g of its pdf at x as khg_acc_fmllr_stats_post defines them:
+ * beta += sum_g gamma_g, G[d] += sum_g gamma_g inv_var[g][d] (x - mu_g)(x - mu_g)^T.  Computed as a frame side minus a Gaussian side,
+ * both shifted by c = the (float) mean of the model's means so that the terms do not cancel:
+ *   frame side     S[d][i][j] = sum_t a_t[d] (x'[i] x'[j]), x' = (double)x - (double)c (exact), a_t fMLLR's frame vector: fMLLR's Gram sum for one
+ *                  speaker who owns every utterance, 1024-frame slices of the call's frame list in set order, added in slice order;
+ *   Gaussian side  C[d][i][j] = sum_g inv_var[g][d] (m'_g[i] mu'_g[j] + mu'_g[i] m'_g[j] - occ_g mu'_g[i] mu'_g[j]) with occ_g / m_g
+ *                  the call's own occupancies and mean sums as khg_acc_stats_post computes them for the same entries -- here with
+ *                  ONE workgroup per pdf however many entries the pdf has, which fixes the order of its sums --, shifted in fp64;
+ *                  1024-Gaussian slices of the model in (pdf, g) order on the fp64 matrix pipe, added in slice order;
+ *   G += S - C, beta += sum_t c_t.
+ * The kernels of this call use no atomics, and the fp64 atomics that end khg_acc_stats_post's workgroups have one writer per cell
+ * here: the same bits from run to run and whatever the chunk size.  The price is that the pdf with the most entries is one
+ * workgroup's walk (DESIGN.md 7m has the figures).  Calls under ONE model add; a handle accumulated under two
+ * models is the caller's error.  Scratch owned by the handle, allocated on first use and kept: one accumulator block in khg_accs
+ * layout for the call's occ_g / m_g (8 (sumG (2 dim + 1) + num_tids + 9) bytes, zeroed per call), the fMLLR chunk scratch above, two
+ * blocks of the handle's size for the call's S and C, and parked slice images shared by the two sides (at most 256 MiB).
+ * khg_acc_stats_post's refusals, before anything is launched (the handle keeps its bits): KHG_E_ARG, KHG_E_ARG too for statistics of
+ * another dimension, and KHG_E_UNSUPPORTED for 2^31 - 1 or more entries or frames and for a model khg_acc_stats_post cannot take: a pdf
+ * too wide for its any-size form, whose 64 (row pitch + Gaussians + 5) floats of LDS end at 160 KiB: 596 Gaussians and more at
+ * dim <= 40, 556 and more at dim <= 80 (khg_acc_fmllr_stats_post accepts such models; this call does not).  Asynchronous on the context's stream once the plan is uploaded. */
+int khg_acc_mllt_stats_post(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, const khg_posteriors *p, float scale,
+                            khg_mllt_stats *stats);
+typedef struct {
+  int32_t num_iters;  /* 200: sweeps over the rows of A */
+} khg_mllt_options;
+void khg_mllt_options_default(khg_mllt_options *o);
+/* Kaldi's MlltAccs::Update on host arrays laid out as khg_mllt_stats_download gives them; needs no device (one dim x dim problem per
+ * training iteration is not worth a kernel).  invG[d] by Gauss-Jordan without pivoting; from A = I, num_iters sweeps over the rows:
+ * c = row d of (A^T)^-1 by Gauss-Jordan with partial pivoting, v = invG[d] c, A[d] = v sqrt(beta / (c . v)).  All fp64, one operation
+ * at a time in index order.  Outputs (any may be NULL, but one of M_h / M64_h is needed): M_h[dim][dim] floats, M64_h the same before
+ * narrowing, *objf_impr = Q(A) - Q(I) with Q(A) = beta log |det A| - 1/2 sum_d A[d] G[d] A[d]^T, *count = beta, *status KHG_MLLT_*.
+ * o == NULL: the defaults.  KHG_E_UNSUPPORTED for dim > KHG_MLLT_MAX_DIM, KHG_E_ARG for num_iters < 0 or nowhere to put M. */
+int khg_mllt_compute(const khg_mllt_options *o, int32_t dim, double beta, const double *G_h, float *M_h, double *M64_h,
+                     double *objf_impr, double *count, int32_t *status);
+/* gmm-transform-means on the handle: per Gaussian, in float, mu = means_invvars / inv_vars, y[d] = 0 then y[d] = fmaf(M[d][j], mu[j],
+ * y[d]) for j = 0 .. dim - 1, means_invvars = y * inv_vars (DiagGmm::SetMeans); weights and variances stay, gconsts are recomputed
+ * (within a few float ulps of the host's: logf).  M_h: dim x dim floats on the host.  The handle is rewritten IN PLACE as
+ * khg_model_ebw_update does it (row-major parameters, gconsts, the K1 tile image and per-parameter-version data).  The mixture weights
+ * must have been set (khg_model_set_weights).  Synchronous.  KHG_E_RUNTIME when a recomputed gconst is not a number: the handle then
+ * holds the transformed parameters, all its images consistent with one another, and is the caller's to replace. */
+int khg_model_transform_means(khg_ctx *ctx, khg_model *m, const float *M_h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,10 @@ class FmllrOptionsC(C.Structure):
     _fields_ = [("min_count", C.c_double), ("num_iters", C.c_int32)]
 
 
+class MlltOptionsC(C.Structure):
+    _fields_ = [("num_iters", C.c_int32)]
+
+
 class RescoreStatsC(C.Structure):
     _fields_ = [("arcs", C.c_int64), ("emitting_arcs", C.c_int64), ("cells", C.c_int64)]
 
@@ -280,6 +284,18 @@ SIGNATURES = {
     "khg_fmllr_stats_estimate": (C.c_int, [vp, vp, C.POINTER(FmllrOptionsC), c_f32p, vp, c_f64p, c_f64p, c_i32p]),
     "khg_posteriors_from_ali": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "khg_utts_transform_feats": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_f32p, vp, vp]),
+    "khg_mllt_stats_create": (C.c_int, [vp, C.c_int32, C.POINTER(vp)]),
+    "khg_mllt_stats_destroy": (C.c_int, [vp]),
+    "khg_mllt_stats_zero": (C.c_int, [vp, vp]),
+    "khg_mllt_stats_download": (C.c_int, [vp, vp, c_f64p, c_f64p]),
+    "khg_mllt_stats_upload": (C.c_int, [vp, vp, c_f64p, c_f64p]),
+    "khg_mllt_stats_add": (C.c_int, [vp, vp, C.c_float, vp]),
+    "khg_mllt_stats_set_chunk_frames": (C.c_int, [vp, C.c_int64]),
+    "khg_mllt_stats_num_chunks": (C.c_int, [vp, c_i32p]),
+    "khg_acc_mllt_stats_post": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, vp]),
+    "khg_mllt_options_default": (None, [C.POINTER(MlltOptionsC)]),
+    "khg_mllt_compute": (C.c_int, [C.POINTER(MlltOptionsC), C.c_int32, C.c_double, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, c_i32p]),
+    "khg_model_transform_means": (C.c_int, [vp, vp, c_f32p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,6 +1,8 @@
 // kaldi_hmm_gmm_amd/csrc/khg_fmllr.hip -- fMLLR speaker adaptation (gmm-est-fmllr / transform-feats): the per-speaker
 // statistics handle (khg_fmllr_stats), their accumulation from posteriors resident on the device and the feature transform.  The
-// estimate's host form (khg_fmllr_compute) lives in khg_host.cpp.  gfx950 only.
+// estimate's host form (khg_fmllr_compute) lives in khg_host.cpp.  MLLT (gmm-acc-mllt / gmm-transform-means) shares the
+// accumulation's plan and per-entry stage and lives at the end of this unit; its estimate (khg_mllt_compute) is in khg_host.cpp too.
+// gfx950 only.
 #include "khg_internal.hpp"
 
 #include <hipcub/hipcub.hpp>   // DeviceRadixSort: the stable (pdf, entry) sort of the per-entry stage, as K3's bucketing
@@ -9,6 +11,7 @@
 #include "khg_fmllr_entry.hip.inc"
 #include "khg_fmllr_transform.hip.inc"
 #include "khg_fmllr_estimate.hip.inc"
+#include "khg_mllt_stats.hip.inc"
 
 struct khg_fmllr_stats {
   khg_ctx* ctx = nullptr;
@@ -119,6 +122,13 @@ static int fm_grow(T** p, size_t* cap, size_t need) {
 }
 
 template <int NDT>
+static int mt_launch_gram(khg_ctx* ctx, const FmArgs& a, const FmItem* items, int nitems, int ngroups, size_t lds, const float* shift) {
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_mllt_gram<NDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KHG_LAUNCH(ctx, k_mllt_gram<NDT>, dim3((unsigned)nitems, (unsigned)ngroups), dim3(256), lds, ctx->stream, a, items, shift);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+template <int NDT>
 static int fm_launch_gram(khg_ctx* ctx, const FmArgs& a, const FmItem* items, int nitems, int ngroups, size_t lds) {
   if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_fmllr_gram<NDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KHG_LAUNCH(ctx, k_fmllr_gram<NDT>, dim3((unsigned)nitems, (unsigned)ngroups), dim3(256), lds, ctx->stream, a, items);
@@ -126,16 +136,15 @@ static int fm_launch_gram(khg_ctx* ctx, const FmArgs& a, const FmItem* items, in
   return KHG_OK;
 }
 
-// gmm-est-fmllr's accumulation: every check on the host first; then flatten -> heads -> per chunk of slices
-// posrow / frame / gram / reduce -> the call's sums into the handle, all on the context's stream.
-extern "C" int khg_acc_fmllr_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale,
-                                        const int32_t* utt2spk_h, khg_fmllr_stats* st) {
-  const std::string who = "khg_acc_fmllr_stats_post: ";
-  if (ctx_dead(ctx) || !m || !tm || !u || !p || !utt2spk_h || !st) return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  { int rf = utts_foreign_ctx(ctx, u, "khg_acc_fmllr_stats_post"); if (rf) return rf; }
-  PostInfo pi;
+// The checks of the two accumulations below: khg_acc_stats_post's refusals, before anything is launched.  n_spk, st_ctx, st_D: the
+// speakers, context and dimension of the statistics handle the caller was given.
+static int fm_check_post(const char* name, khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale,
+                         const int32_t* utt2spk_h, int32_t n_spk, const khg_ctx* st_ctx, int32_t st_D, PostInfo* pinfo) {
+  const std::string who = std::string(name) + ": ";
+  { int rf = utts_foreign_ctx(ctx, u, name); if (rf) return rf; }
+  PostInfo& pi = *pinfo;
   posteriors_info(p, &pi);
-  if (pi.ctx != ctx || m->ctx != ctx || tm->ctx != ctx || st->ctx != ctx || u->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (pi.ctx != ctx || m->ctx != ctx || tm->ctx != ctx || st_ctx != ctx || u->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
   if (pi.U != u->n_utt)
     return khg_set_error(KHG_E_ARG, who + "the posteriors hold " + std::to_string(pi.U) + " utterances, the set " + std::to_string(u->n_utt));
   for (int i = 0; i < pi.U; ++i) {
@@ -143,16 +152,28 @@ extern "C" int khg_acc_fmllr_stats_post(khg_ctx* ctx, const khg_model* m, const 
     if (tp != 0 && tp != ts)
       return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(i) + " has " + std::to_string(tp) + " frames of posteriors and " + std::to_string(ts) + " frames of features");
   }
-  if (m->D != u->D || st->D != m->D) return khg_set_error(KHG_E_ARG, who + "statistics / model / feature dimensions do not match");
+  if (m->D != u->D || st_D != m->D) return khg_set_error(KHG_E_ARG, who + "statistics / model / feature dimensions do not match");
   if (tm->max_pdf >= m->P) return khg_set_error(KHG_E_ARG, who + "transition model refers to pdf-ids the model does not have");
   if (!std::isfinite(scale)) return khg_set_error(KHG_E_ARG, who + "scale must be finite");
   if (pi.max_tid > tm->num_tids)
     return khg_set_error(KHG_E_ARG, who + "the posteriors hold transition-id " + std::to_string(pi.max_tid) + ", the transition model has " + std::to_string(tm->num_tids));
   for (int i = 0; i < pi.U; ++i)
-    if (utt2spk_h[i] >= st->S)
-      return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(i) + " belongs to speaker " + std::to_string(utt2spk_h[i]) + ", the statistics hold " + std::to_string(st->S));
+    if (utt2spk_h[i] >= n_spk)
+      return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(i) + " belongs to speaker " + std::to_string(utt2spk_h[i]) + ", the statistics hold " + std::to_string(n_spk));
   const int64_t E = pi.entry_off[pi.U];
   if (E >= (int64_t)INT_MAX || u->N >= (int64_t)INT_MAX) return khg_set_error(KHG_E_UNSUPPORTED, who + "2^31 - 1 or more entries or frames");
+  return KHG_OK;
+}
+// The accumulation shared by gmm-est-fmllr and the frame side of gmm-acc-mllt (7m, shift_d != nullptr: one speaker, the
+// Gram kernel on x - shift without K and the border column, the call's sums left in st->call_d for the caller to fold): every check on
+// the host first (fm_check_post, by the caller: pi is what it filled); then flatten -> heads -> per chunk of slices posrow / frame /
+// gram / reduce -> the call's sums, all on the context's stream.  The MLLT call comes here behind its khg_acc_stats_post on the same
+// posteriors and scale, which left the flattened entries in the set's buffers: they are not made again.  *ran: the call's sums were made.
+static int fm_acc_post(const char* name, khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale,
+                       const int32_t* utt2spk_h, khg_fmllr_stats* st, const PostInfo& pi, const float* shift_d, bool* ran) {
+  const std::string who = std::string(name) + ": ";
+  *ran = false;
+  const int64_t E = pi.entry_off[pi.U];
   st->n_chunks_last = 0;
   if (E == 0) return KHG_OK;
 
@@ -243,8 +264,10 @@ extern "C" int khg_acc_fmllr_stats_post(khg_ctx* ctx, const khg_model* m, const 
   rc = sync_pageable(ctx);                           // the plan's host vectors go out of scope with the call
   if (rc) return rc;
 
-  rc = posteriors_flatten(ctx, p, u->frame_off_d, (double)scale, tm->num_tids, u->pe_row_d, u->pe_tid_d, u->pe_w_d, 0);
-  if (rc) return rc;
+  if (!shift_d) {
+    rc = posteriors_flatten(ctx, p, u->frame_off_d, (double)scale, tm->num_tids, u->pe_row_d, u->pe_tid_d, u->pe_w_d, 0);
+    if (rc) return rc;
+  }
   HIPCHK(hipMemsetAsync(st->row_first_d, 0xFF, sizeof(int32_t) * (size_t)u->N, ctx->stream));
   HIPCHK(hipMemsetAsync(st->call_d, 0, sizeof(double) * (size_t)st->S * (size_t)st->SZ, ctx->stream));
   FmArgs a;
@@ -281,6 +304,8 @@ extern "C" int khg_acc_fmllr_stats_post(khg_ctx* ctx, const khg_model* m, const 
   while ((1 << sort_bits) <= m->P) ++sort_bits;        // keys are 0 .. P
   const int D1 = D + 1, NP = D1 * (D1 + 1) / 2, NT = (NP + 15) / 16 + (D1 + 15) / 16, ngroups = (NT + FM_TPG - 1) / FM_TPG;
   const size_t lds_gram = sizeof(float) * (size_t)FM_TB * (size_t)((D1 | 1) + 2 * 16 * NDT);
+  const int mt_ngroups = ((D * D1 / 2 + 15) / 16 + FM_TPG - 1) / FM_TPG;
+  const size_t mt_lds_gram = sizeof(float) * (size_t)FM_TB * (size_t)((D1 | 1) + 16 * NDT);
   for (const Chunk& c : chunks) {
     const int nseg = (int)(c.seg1 - c.seg0), nit = (int)(c.item1 - c.item0), nrun = (int)(c.run1 - c.run0);
     {
@@ -323,7 +348,18 @@ extern "C" int khg_acc_fmllr_stats_post(khg_ctx* ctx, const khg_model* m, const 
       KHG_LAUNCH(ctx, k_fmllr_frame, dim3((unsigned)std::min<int64_t>(65536, (c.frames + 3) / 4)), dim3(256), lds_frame, ctx->stream, a, (int32_t)c.frames, DPf, GM);
       HIPCHK(hipGetLastError());
     }
-    {
+    if (shift_d) {
+      KernelTimer kt(ctx, "k_mllt_gram");
+      const FmItem* it = st->items_d + c.item0;
+      switch (NDT) {
+        case 1: rc = mt_launch_gram<1>(ctx, a, it, nit, mt_ngroups, mt_lds_gram, shift_d); break;
+        case 2: rc = mt_launch_gram<2>(ctx, a, it, nit, mt_ngroups, mt_lds_gram, shift_d); break;
+        case 3: rc = mt_launch_gram<3>(ctx, a, it, nit, mt_ngroups, mt_lds_gram, shift_d); break;
+        case 4: rc = mt_launch_gram<4>(ctx, a, it, nit, mt_ngroups, mt_lds_gram, shift_d); break;
+        default: rc = mt_launch_gram<5>(ctx, a, it, nit, mt_ngroups, mt_lds_gram, shift_d); break;
+      }
+      if (rc) return rc;
+    } else {
       KernelTimer kt(ctx, "k_fmllr_gram");
       const FmItem* it = st->items_d + c.item0;
       switch (NDT) {
@@ -342,14 +378,25 @@ extern "C" int khg_acc_fmllr_stats_post(khg_ctx* ctx, const khg_model* m, const 
       HIPCHK(hipGetLastError());
     }
   }
-  {
+  if (!shift_d) {
     KernelTimer kt(ctx, "k_fmllr_axpy");
     const int64_t n = (int64_t)st->S * st->SZ;
     KHG_LAUNCH(ctx, k_fmllr_axpy, dim3(fm_grid(n)), dim3(256), 0, ctx->stream, st->buf_d, st->call_d, 1.0, n);
     HIPCHK(hipGetLastError());
   }
   st->n_chunks_last = (int32_t)chunks.size();
+  *ran = true;
   return KHG_OK;
+}
+extern "C" int khg_acc_fmllr_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale,
+                                        const int32_t* utt2spk_h, khg_fmllr_stats* st) {
+  if (ctx_dead(ctx) || !m || !tm || !u || !p || !utt2spk_h || !st) return khg_set_error(KHG_E_ARG, "khg_acc_fmllr_stats_post: bad arguments");
+  const char* name = "khg_acc_fmllr_stats_post";
+  PostInfo pi;
+  int rc = fm_check_post(name, ctx, m, tm, u, p, scale, utt2spk_h, st->S, st->ctx, st->D, &pi);
+  if (rc) return rc;
+  bool ran = false;
+  return fm_acc_post(name, ctx, m, tm, u, p, scale, utt2spk_h, st, pi, nullptr, &ran);
 }
 
 // transform-feats: the rows of every utterance through its speaker's W.  W_h (host, [n_spk][D][D + 1]) or W_d (device, the same
@@ -499,4 +546,210 @@ extern "C" int khg_fmllr_stats_estimate(khg_ctx* ctx, const khg_fmllr_stats* st,
   cleanup();
   if (e != hipSuccess) return khg_set_error(KHG_E_HIP, who + hipGetErrorString(e));
   return KHG_OK;
+}
+
+// ---- MLLT -------------------------------------------------------------------------------------------------------------
+struct khg_mllt_stats {
+  khg_ctx* ctx = nullptr;
+  int32_t D = 0;
+  int64_t SZ = 0;                    // doubles: G | beta
+  double* buf_d = nullptr;           // [SZ]
+  khg_fmllr_stats fm;                // the frame side's plan scratch: one speaker, blocks of SZ doubles; fm.call_d holds the call's S
+  double* gcall_d = nullptr;         // [SZ] the call's C
+  khg_accs* acc = nullptr;           // the call's occ_g / m_g, laid out for the model of the last call
+  float* shift_d = nullptr;          // [D]
+  double* shift_part_d = nullptr; size_t shift_cap = 0;   // [slices][D]
+};
+
+static inline int64_t mt_block_size(int D) { return (int64_t)D * ((int64_t)D * (D + 1) / 2) + 1; }
+static void mt_free_scratch(khg_fmllr_stats* s) {
+  DEVFREE(s->call_d); DEVFREE(s->pos_row_d); DEVFREE(s->a_d); DEVFREE(s->b_d); DEVFREE(s->c_d); DEVFREE(s->part_d);
+  DEVFREE(s->cnt_d); DEVFREE(s->ent_id_d); DEVFREE(s->ea_d); DEVFREE(s->eb_d); DEVFREE(s->ec_d);
+  DEVFREE(s->row_first_d); DEVFREE(s->segs_d); DEVFREE(s->items_d); DEVFREE(s->runs_d);
+}
+
+extern "C" int khg_mllt_stats_create(khg_ctx* ctx, int32_t dim, khg_mllt_stats** out) {
+  if (ctx_dead(ctx) || !out || dim < 1) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_create: bad arguments");
+  if (dim > KHG_MLLT_MAX_DIM)
+    return khg_set_error(KHG_E_UNSUPPORTED, "khg_mllt_stats_create: dim " + std::to_string(dim) + " is above KHG_MLLT_MAX_DIM");
+  khg_mllt_stats* s = new khg_mllt_stats();
+  s->ctx = ctx; s->D = dim; s->SZ = mt_block_size(dim);
+  s->fm.ctx = ctx; s->fm.S = 1; s->fm.D = dim; s->fm.SZ = s->SZ;
+  int rc = dev_alloc(&s->buf_d, (size_t)s->SZ);
+  if (!rc) rc = dev_alloc(&s->gcall_d, (size_t)s->SZ);
+  if (!rc) rc = dev_alloc(&s->shift_d, (size_t)dim);
+  if (rc) { (void)khg_mllt_stats_destroy(s); return rc; }
+  *out = s;
+  return khg_mllt_stats_zero(ctx, s);
+}
+extern "C" int khg_mllt_stats_destroy(khg_mllt_stats* s) {
+  if (!s) return KHG_OK;
+  DEVFREE(s->buf_d); DEVFREE(s->gcall_d); DEVFREE(s->shift_d); DEVFREE(s->shift_part_d);
+  mt_free_scratch(&s->fm);
+  if (s->acc) (void)khg_accs_destroy(s->acc);
+  delete s;
+  return KHG_OK;
+}
+extern "C" int khg_mllt_stats_zero(khg_ctx* ctx, khg_mllt_stats* s) {
+  if (ctx_dead(ctx) || !s || s->ctx != ctx) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_zero: bad arguments");
+  HIPCHK(hipMemsetAsync(s->buf_d, 0, sizeof(double) * (size_t)s->SZ, ctx->stream));
+  return KHG_OK;
+}
+extern "C" int khg_mllt_stats_set_chunk_frames(khg_mllt_stats* s, int64_t frames) {
+  if (!s || frames < 1) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_set_chunk_frames: bad arguments");
+  return khg_fmllr_stats_set_chunk_frames(&s->fm, frames);
+}
+extern "C" int khg_mllt_stats_num_chunks(const khg_mllt_stats* s, int32_t* n) {
+  if (!s || !n) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_num_chunks: bad arguments");
+  *n = s->fm.n_chunks_last;
+  return KHG_OK;
+}
+extern "C" int khg_mllt_stats_download(khg_ctx* ctx, const khg_mllt_stats* s, double* beta_h, double* G_h) {
+  if (ctx_dead(ctx) || !s || s->ctx != ctx) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_download: bad arguments");
+  { int rc = check_err_flag(ctx, "khg_acc_mllt_stats_post"); if (rc) return rc; }
+  if (G_h) HIPCHK(hipMemcpyAsync(G_h, s->buf_d, sizeof(double) * (size_t)(s->SZ - 1), hipMemcpyDeviceToHost, ctx->stream));
+  if (beta_h) HIPCHK(hipMemcpyAsync(beta_h, s->buf_d + s->SZ - 1, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
+extern "C" int khg_mllt_stats_upload(khg_ctx* ctx, khg_mllt_stats* s, const double* beta_h, const double* G_h) {
+  if (ctx_dead(ctx) || !s || s->ctx != ctx || !beta_h || !G_h) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_upload: bad arguments");
+  HIPCHK(hipMemcpyAsync(s->buf_d, G_h, sizeof(double) * (size_t)(s->SZ - 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(s->buf_d + s->SZ - 1, beta_h, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
+extern "C" int khg_mllt_stats_add(khg_ctx* ctx, khg_mllt_stats* dst, float scale, const khg_mllt_stats* src) {
+  if (ctx_dead(ctx) || !dst || !src) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_add: bad arguments");
+  if (!std::isfinite(scale)) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_add: the scale is not finite");
+  if (dst->ctx != ctx || src->ctx != ctx) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_add: a handle of another context");
+  if (dst->D != src->D) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_add: the two handles differ in dimension");
+  if (dst == src) return khg_set_error(KHG_E_ARG, "khg_mllt_stats_add: dst and src are the same handle");
+  KernelTimer kt(ctx, "k_fmllr_axpy");
+  KHG_LAUNCH(ctx, k_fmllr_axpy, dim3(fm_grid(dst->SZ)), dim3(256), 0, ctx->stream, dst->buf_d, src->buf_d, (double)scale, dst->SZ);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+
+template <int NDT>
+static int mt_launch_gauss(khg_ctx* ctx, const MtGaussArgs& a, int nslice, int ngroups, size_t lds) {
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_mllt_gauss<NDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KHG_LAUNCH(ctx, k_mllt_gauss<NDT>, dim3((unsigned)nslice, (unsigned)ngroups), dim3(256), lds, ctx->stream, a);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+
+// gmm-acc-mllt: the checks; occ_g / m_g of the call (K3); the shift; the frame side (fm_acc_post); the Gaussian side per
+// chunk of slices; S - C into the handle.
+extern "C" int khg_acc_mllt_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale,
+                                       khg_mllt_stats* st) {
+  const char* name = "khg_acc_mllt_stats_post";
+  if (ctx_dead(ctx) || !m || !tm || !u || !p || !st) return khg_set_error(KHG_E_ARG, std::string(name) + ": bad arguments");
+  std::vector<int32_t> one((size_t)std::max(u->n_utt, 1), 0);        // every utterance belongs to the one speaker
+  PostInfo pi;
+  int rc = fm_check_post(name, ctx, m, tm, u, p, scale, one.data(), 1, st->ctx, st->D, &pi);
+  if (!rc) rc = k3_post_check(ctx, m, std::string(name) + ": ");
+  if (rc) return rc;
+  st->fm.n_chunks_last = 0;
+  if (pi.entry_off[pi.U] == 0 || m->sumG == 0) return KHG_OK;
+  const int D = m->D;
+  // scratch: the accumulator block for this model's layout, the slices' shift sums, the parked images of both sides
+  if (st->acc && (st->acc->sumG != m->sumG || st->acc->D != D || st->acc->num_tids != tm->num_tids)) { (void)khg_accs_destroy(st->acc); st->acc = nullptr; }
+  if (!st->acc) { rc = khg_accs_create(ctx, m, tm, &st->acc); if (rc) return rc; }
+  const int64_t nslice = (m->sumG + MT_GSLICE - 1) / MT_GSLICE;
+  const int64_t CI = std::max<int64_t>(1, std::min<int64_t>(nslice, (int64_t(256) << 20) / (8 * st->SZ)));     // Gaussian-side slices of a chunk
+  rc = fm_grow(&st->shift_part_d, &st->shift_cap, (size_t)nslice * (size_t)D);
+  if (!rc) rc = fm_grow(&st->fm.part_d, &st->fm.part_cap, (size_t)CI * (size_t)st->SZ);
+  if (rc) return rc;
+  // K3 from posteriors with ONE work item per pdf, however many entries its bucket holds (ctx->k3_one_block): a cell of the block
+  // then receives one workgroup's sum, made in chunk order over the stably sorted entries, so occ_g / m_g -- and with them C -- have
+  // the same bits from run to run.  K3's own choice cuts a bucket into several items, which end with fp64 atomics into the same cells
+  // in whatever order they finish.  The price: the pdf with the most entries (silence) is one workgroup's walk.
+  rc = khg_accs_zero(ctx, st->acc);
+  if (!rc) {
+    ctx->k3_one_block = true;
+    rc = khg_acc_stats_post(ctx, m, tm, u, p, scale, st->acc);
+    ctx->k3_one_block = false;
+  }
+  if (rc) return rc;
+  {
+    KernelTimer kt(ctx, "k_mllt_shift");
+    KHG_LAUNCH(ctx, k_mllt_shift_part, dim3((unsigned)nslice), dim3(128), 0, ctx->stream, m->miv_d, m->iv_d, m->sumG, D, st->shift_part_d);
+    KHG_LAUNCH(ctx, k_mllt_shift, dim3(1), dim3(128), 0, ctx->stream, st->shift_part_d, (int32_t)nslice, m->sumG, D, st->shift_d);
+    HIPCHK(hipGetLastError());
+  }
+  bool ran = false;
+  rc = fm_acc_post(name, ctx, m, tm, u, p, scale, one.data(), &st->fm, pi, st->shift_d, &ran);
+  if (rc) return rc;
+  if (!ran) return KHG_OK;                                           // no utterance with frames
+  HIPCHK(hipMemsetAsync(st->gcall_d, 0, sizeof(double) * (size_t)st->SZ, ctx->stream));
+  const int NDT = (D + 15) / 16, NP = D * (D + 1) / 2, ngroups = ((NP + 15) / 16 + FM_TPG - 1) / FM_TPG, XS = (D + 1) | 1;
+  const size_t lds = sizeof(double) * (size_t)(2 * MT_GB * XS + MT_GB) + sizeof(float) * (size_t)MT_GB * 16 * (size_t)NDT;
+  MtGaussArgs ga;
+  ga.miv = m->miv_d; ga.iv = m->iv_d; ga.occ = st->acc->occ(); ga.mean = st->acc->mean(); ga.shift = st->shift_d;
+  ga.sumG = m->sumG; ga.D = D; ga.part = st->fm.part_d; ga.SZ = st->SZ;
+  for (int64_t s0 = 0; s0 < nslice; s0 += CI) {
+    const int ns = (int)std::min<int64_t>(CI, nslice - s0);
+    ga.g_first = s0 * MT_GSLICE;
+    {
+      KernelTimer kt(ctx, "k_mllt_gauss");
+      switch (NDT) {
+        case 1: rc = mt_launch_gauss<1>(ctx, ga, ns, ngroups, lds); break;
+        case 2: rc = mt_launch_gauss<2>(ctx, ga, ns, ngroups, lds); break;
+        case 3: rc = mt_launch_gauss<3>(ctx, ga, ns, ngroups, lds); break;
+        case 4: rc = mt_launch_gauss<4>(ctx, ga, ns, ngroups, lds); break;
+        default: rc = mt_launch_gauss<5>(ctx, ga, ns, ngroups, lds); break;
+      }
+      if (rc) return rc;
+    }
+    {
+      KernelTimer kt(ctx, "k_mllt_greduce");
+      const unsigned gy = (unsigned)std::min<int64_t>(64, (st->SZ + 255) / 256);
+      KHG_LAUNCH(ctx, k_mllt_greduce, dim3(gy), dim3(256), 0, ctx->stream, st->fm.part_d, ns, st->gcall_d, st->SZ);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  {
+    KernelTimer kt(ctx, "k_mllt_fold");
+    KHG_LAUNCH(ctx, k_mllt_fold, dim3(fm_grid(st->SZ)), dim3(256), 0, ctx->stream, st->buf_d, st->fm.call_d, st->gcall_d, st->SZ);
+    HIPCHK(hipGetLastError());
+  }
+  return KHG_OK;
+}
+
+extern "C" int khg_model_transform_means(khg_ctx* ctx, khg_model* m, const float* M_h) {
+  const std::string who = "khg_model_transform_means: ";
+  if (ctx_dead(ctx) || !m || !M_h) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  if (m->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (m->D > KHG_MLLT_MAX_DIM) return khg_set_error(KHG_E_UNSUPPORTED, who + "dim " + std::to_string(m->D) + " is above KHG_MLLT_MAX_DIM");
+  if (!m->has_weights) return khg_set_error(KHG_E_ARG, who + "the model has no weights (khg_model_set_weights)");
+  const int D = m->D;
+  for (int i = 0; i < D * D; ++i)
+    if (!std::isfinite(M_h[i])) return khg_set_error(KHG_E_ARG, who + "the matrix is not finite");
+  if (m->sumG == 0) return KHG_OK;
+  float* M_d = nullptr; int32_t* bad_d = nullptr;
+  int rc = dev_alloc(&M_d, (size_t)D * D);
+  if (!rc) rc = dev_alloc(&bad_d, 1);
+  int32_t bad = 0;
+  if (!rc) {
+    hipError_t e = hipMemcpyAsync(M_d, M_h, sizeof(float) * (size_t)D * D, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(bad_d, 0, sizeof(int32_t), ctx->stream);
+    if (e == hipSuccess) {
+      KernelTimer kt(ctx, "k_model_transform_means");
+      const size_t lds = sizeof(float) * ((size_t)D * (D | 1) + 8 * (size_t)D);
+      const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (m->sumG + 3) / 4));
+      KHG_LAUNCH(ctx, k_model_transform_means, dim3(grid), dim3(256), lds, ctx->stream, M_d, m->sumG, D, m->weights_d, m->iv_d, m->miv_d, m->gconsts_d, bad_d);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, bad_d, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = khg_set_error(KHG_E_HIP, who + hipGetErrorString(e));
+  }
+  DEVFREE(M_d); DEVFREE(bad_d);
+  if (rc) return rc;
+  // new K1 tile image + per-parameter-version data, as khg_model_ebw_update ends -- also behind a gconst that is not a number: the
+  // kernel has rewritten the rows by then, and the handle's images must not disagree with them
+  rc = model_pack(ctx, m);
+  if (bad) return khg_set_error(KHG_E_RUNTIME, who + "not a number in gconst computation (the handle holds the transformed parameters)");
+  return rc;
 }

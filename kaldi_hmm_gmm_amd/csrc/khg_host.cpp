@@ -761,3 +761,95 @@ extern "C" int khg_fmllr_compute(const khg_fmllr_options* o, int32_t n_spk, int3
   for (auto& t : th) t.join();
   return KHG_OK;
 }
+
+// ---- MLLT estimate: the reference has no MLLT, the rule written there is the specification -------------------------
+// Kaldi's MlltAccs::Update on the statistics of khg_mllt_stats_download, with the Gauss-Jordan forms of the fMLLR estimate above.  One
+// IEEE fp64 operation at a time in the written order (contraction is off for this file from the fMLLR section on), every sum in index
+// order: tests/mllt_ref.py restates it and agrees on the bits of M.
+namespace {
+
+// Q(A) = beta log |det A| - 1/2 sum_d A[d] G[d] A[d]^T; false: A is singular
+bool MlltAuxf(int D, double beta, const double* G, const double* A, double* q, double* M, double* inv) {
+  const int NP = D * (D + 1) / 2;
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) M[i * D + j] = A[j * D + i];
+  double ld = 0.0;
+  if (!FmInvPiv(D, M, inv, &ld)) return false;
+  double acc = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const double* g = G + (size_t)d * NP;
+    const double* a = A + (size_t)d * D;
+    double t2 = 0.0;
+    for (int i = 0; i < D; ++i) {
+      double r = 0.0;
+      for (int j = 0; j < D; ++j) r = r + g[j <= i ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i] * a[j];
+      t2 = t2 + a[i] * r;
+    }
+    acc = acc + t2;
+  }
+  *q = beta * ld - 0.5 * acc;
+  return true;
+}
+
+int32_t MlltOne(const khg_mllt_options* o, int D, double beta, const double* G, double* A, double* objf_impr) {
+  const int NP = D * (D + 1) / 2;
+  auto identity = [&] {
+    for (int d = 0; d < D; ++d)
+      for (int j = 0; j < D; ++j) A[d * D + j] = d == j ? 1.0 : 0.0;
+  };
+  identity();
+  *objf_impr = 0.0;
+  if (!(beta > 0.0) || !std::isfinite(beta)) return KHG_MLLT_SINGULAR;
+  std::vector<double> invG((size_t)D * D * D), M((size_t)D * D), inv((size_t)D * D), c(D), v(D);
+  for (int d = 0; d < D; ++d)
+    if (!FmInvSym(D, G + (size_t)d * NP, M.data(), invG.data() + (size_t)d * D * D)) return KHG_MLLT_SINGULAR;
+  double q0 = 0.0;
+  if (!MlltAuxf(D, beta, G, A, &q0, M.data(), inv.data())) return KHG_MLLT_SINGULAR;
+  for (int it = 0; it < o->num_iters; ++it)
+    for (int d = 0; d < D; ++d) {
+      for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; ++j) M[i * D + j] = A[j * D + i];              // A^T
+      double ld = 0.0;
+      if (!FmInvPiv(D, M.data(), inv.data(), &ld)) { identity(); return KHG_MLLT_SINGULAR; }
+      for (int j = 0; j < D; ++j) c[j] = inv[d * D + j];
+      const double* ig = invG.data() + (size_t)d * D * D;
+      for (int i = 0; i < D; ++i) {
+        double r = 0.0;
+        for (int j = 0; j < D; ++j) r = r + ig[i * D + j] * c[j];
+        v[i] = r;
+      }
+      double cv = 0.0;
+      for (int i = 0; i < D; ++i) cv = cv + c[i] * v[i];
+      const double s = std::sqrt(beta / cv);
+      if (!std::isfinite(s)) { identity(); return KHG_MLLT_SINGULAR; }
+      for (int i = 0; i < D; ++i) A[d * D + i] = v[i] * s;
+    }
+  double q1 = 0.0;
+  if (!MlltAuxf(D, beta, G, A, &q1, M.data(), inv.data())) { identity(); return KHG_MLLT_SINGULAR; }
+  *objf_impr = q1 - q0;
+  return KHG_MLLT_OK;
+}
+
+}  // namespace
+
+extern "C" void khg_mllt_options_default(khg_mllt_options* o) { o->num_iters = 200; }
+
+extern "C" int khg_mllt_compute(const khg_mllt_options* o, int32_t dim, double beta, const double* G_h, float* M_h, double* M64_h, double* objf_impr,
+                                double* count, int32_t* status) {
+  khg_mllt_options def;
+  khg_mllt_options_default(&def);
+  if (!o) o = &def;
+  if (dim < 1 || !G_h || (!M_h && !M64_h)) return khg_set_error(KHG_E_ARG, "khg_mllt_compute: bad arguments");
+  if (dim > KHG_MLLT_MAX_DIM) return khg_set_error(KHG_E_UNSUPPORTED, "khg_mllt_compute: dim " + std::to_string(dim) + " is above KHG_MLLT_MAX_DIM");
+  if (o->num_iters < 0) return khg_set_error(KHG_E_ARG, "khg_mllt_compute: num_iters is negative");
+  const size_t n = (size_t)dim * dim;
+  std::vector<double> A(n);
+  double impr = 0.0;
+  const int32_t st = MlltOne(o, dim, beta, G_h, A.data(), &impr);
+  if (status) *status = st;
+  if (objf_impr) *objf_impr = impr;
+  if (count) *count = beta;
+  if (M64_h) memcpy(M64_h, A.data(), sizeof(double) * n);
+  if (M_h) for (size_t i = 0; i < n; ++i) M_h[i] = (float)A[i];
+  return KHG_OK;
+}

@@ -449,6 +449,22 @@ void DiagGmm::Perturb(float perturb_factor, const RandnFn& randn) {
   }
   ComputeGconsts();
 }
+void DiagGmm::TransformMeans(const float* M, size_t rows, size_t cols) {
+  KHG_REQUIRE((int)rows == D_ && (int)cols == D_, "TransformMeans: the matrix must be dim x dim");
+  Touch();
+  std::vector<float> mu((size_t)D_);
+  for (int g = 0; g < G_; ++g) {
+    float* mi = means_invvars_.data() + (size_t)g * D_;
+    const float* iv = inv_vars_.data() + (size_t)g * D_;
+    for (int d = 0; d < D_; ++d) mu[(size_t)d] = mi[d] / iv[d];
+    for (int d = 0; d < D_; ++d) {
+      float y = 0.0f;
+      for (int j = 0; j < D_; ++j) y = std::fmaf(M[(size_t)d * D_ + j], mu[(size_t)j], y);
+      mi[d] = y * iv[d];
+    }
+  }
+  ComputeGconsts();
+}
 std::vector<float> DiagGmm::Generate(const RandnFn& randn) const {
   const float tot = NpSum(weights_.data(), weights_.size());
   KHG_REQUIRE(tot > 0.0f, "tot > 0.0 assertion failed");

@@ -140,6 +140,9 @@ class DiagGmm {
   void Split(int target_components, float perturb_factor, std::vector<int>* history, const RandnFn& randn);   // :780-851
   std::vector<int> Merge(int target_components);               // :557-759 (khg_diag_gmm_merge) -> history
   void Perturb(float perturb_factor, const RandnFn& randn);    // :463-484
+  // gmm-transform-means: every mean through the dim x dim matrix M, in float -- mu = GetMeans(), y[d] = 0 then
+  // y[d] = fmaf(M[d][j], mu[j], y[d]) in j order, SetMeans(y) --, gconsts recomputed: the bits of khg_model_transform_means
+  void TransformMeans(const float* M, size_t rows, size_t cols);
   std::vector<float> Generate(const RandnFn& randn) const;     // :410-446
   void Interpolate(float rho, const DiagGmm& source, int flags);   // :486-520
 
@@ -168,6 +171,7 @@ class AmDiagGmm {
     return pdfs_[i];
   }
   int ComputeGconsts() { int n = 0; for (auto& p : pdfs_) n += p->ComputeGconsts(); return n; }
+  void TransformMeans(const float* M, size_t rows, size_t cols) { for (auto& p : pdfs_) p->TransformMeans(M, rows, cols); }
   void SplitByCount(const std::vector<float>& state_occs, int target, float perturb, float power, double min_count,
                     const RandnFn& randn);                     // csrc/am-diag-gmm.cc:72-90
   void MergeByCount(const std::vector<float>& state_occs, int target, float power, double min_count);   // :91-108

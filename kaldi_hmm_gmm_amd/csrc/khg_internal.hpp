@@ -3,7 +3,7 @@
 // another.  The units, by handle:  khg_ctx_model.hip (context, model image, transition table), khg_utts.hip (utterance sets: features +
 // graphs), khg_k1.hip (log-likelihoods), khg_k2.hip (Viterbi alignment), khg_lattices.hip (lattice decoders, resident lattices and their
 // posteriors: khg_lattices / khg_posteriors stay private to it), khg_k3.hip (accumulators + statistics), khg_c1.hip (RCCL exchange),
-// khg_k4.hip (device M-step), khg_fmllr.hip (fMLLR statistics and feature transform: khg_fmllr_stats stays private to it).  gfx950 only.
+// khg_k4.hip (device M-step), khg_fmllr.hip (fMLLR statistics and feature transform, MLLT statistics and gmm-transform-means: khg_fmllr_stats / khg_mllt_stats stay private to it).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,6 +67,7 @@ struct khg_ctx {
   bool pageable_pending = false;    // a hipMemcpyAsync from pageable host memory may still be reading its source (sync_pageable)
   bool timing = false;
   std::vector<khg_timing> timings;
+  bool k3_one_block = false;        // set by khg_acc_mllt_stats_post around its K3 pass: ONE work item per pdf whatever its bucket holds
   int opt[KHG_OPT_COUNT] = {};    // khg_ctx_set_option (KHG_OPT_*); the environment variables of include/khg_hip.h only seed the defaults, once, at khg_ctx_create
 };
 int arena_flush(khg_ctx* ctx);                             // khg_ctx_model.hip: staged uploads -> device, one copy on the context's stream
@@ -369,6 +370,9 @@ int k1_band_check(khg_ctx* ctx, khg_utts* u);             // khg_k1.hip: the ban
 int k1_band_repair(khg_ctx* ctx, khg_utts* u, int32_t* status_d, int repair_bit, hipStream_t side);   // khg_k1.hip
 int accs_allreduce_pieces(khg_ctx* ctx, khg_accs* a, const khg_model* m, int first_pdf, int n_pdf, void* comm, hipStream_t st);   // khg_c1.hip
 int ctx_comm_stream(khg_ctx* ctx);                        // khg_c1.hip
+// khg_k3.hip: KHG_E_UNSUPPORTED where khg_acc_stats_post refuses the model (a pdf too wide for the any-size form's LDS buffers), for a
+// caller that wants the refusal among its own up-front checks
+int k3_post_check(khg_ctx* ctx, const khg_model* m, const std::string& who);
 // khg_lattices.hip: what khg_acc_stats_post (khg_k3.hip) needs of a posteriors handle, whose layout stays private to that unit
 struct PostInfo { const khg_ctx* ctx; int32_t U, max_tid; const int64_t *frame_off, *entry_off; };   // max_tid < 0: made from lattices
 void posteriors_info(const khg_posteriors* p, PostInfo* out);

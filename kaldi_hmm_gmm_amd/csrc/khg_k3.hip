@@ -159,6 +159,22 @@ static int k3_phase_a_scales(khg_ctx* ctx, khg_model* m, khg_utts* u, bool* use)
   return KHG_OK;
 }
 
+// LDS of the VALU form (k3_accumulate) for a widest pdf of maxG Gaussians: the chunk's rows, gammas and reductions
+static size_t k3_valu_lds(const khg_model* m, int maxG, bool post) {
+  return sizeof(float) * (size_t)K3_CHUNK * ((size_t)(m->KQ ? 4 * m->KQ : (m->D | 1)) + (maxG | 1) + (post ? 5 : 4));
+}
+#define K3_VALU_LDS_MAX (160 * 1024)
+// The one refusal khg_acc_stats_post raises behind its argument checks, for khg_acc_mllt_stats_post to raise among its own: the
+// posterior pass sends a model to the chunk-per-block MFMA form or, past that form's sizes, to the VALU form, whose LDS bounds the pdf.
+int k3_post_check(khg_ctx* ctx, const khg_model* m, const std::string& who) {
+  int maxG = 0;
+  for (int p = 0; p < m->P; ++p) maxG = std::max(maxG, m->gauss_off[(size_t)p + 1] - m->gauss_off[(size_t)p]);
+  const bool mfma_ok = (maxG <= 128 || (maxG <= 256 && m->KQ == 10)) && ctx->opt[KHG_OPT_K3_FORM] != 2 && m->KQ != 0;
+  if (!mfma_ok && k3_valu_lds(m, maxG, true) > K3_VALU_LDS_MAX)
+    return khg_set_error(KHG_E_UNSUPPORTED, who + "a pdf of " + std::to_string(maxG) + " Gaussians is too large for the LDS chunk buffers of the statistics pass");
+  return KHG_OK;
+}
+
 // One pass of K3 over the set's resident alignment: all N frames (nsub < 0), or -- the second pass of the split mode -- the nsub frames
 // of the utterances the DP left to the order-faithful decoders (flagged in u->unc_d; their alignments are merged into ali_d by now).
 // npost >= 0 (khg_acc_stats_post): the pass runs over the npost flattened entries in u->pe_* instead of the alignment -- its own
@@ -271,7 +287,9 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
     // keep their item lists side by side in the same buffers (second = true: the upper halves).
     auto make_items = [&](int ny_base, bool parked, size_t nsum1, int cls_lo, int cls_hi, bool second) -> int {
       const int64_t avg = Neff / std::max(1, m->P);
-      const int target = (int)std::min<int64_t>(1 << 30, std::max<int64_t>(512, 2 * avg / ny_base));
+      // (k3_one_block: no bucket is cut, so every cell of the block receives ONE work item's sum, made in chunk order -- the fp64 atomics
+      //  that end an item then have no second item to race with, and the statistics have the same bits from run to run)
+      const int target = ctx->k3_one_block ? INT_MAX : (int)std::min<int64_t>(1 << 30, std::max<int64_t>(512, 2 * avg / ny_base));
       const int64_t per_t = Neff / target;
       k3_extra_blocks = std::min<int64_t>(per_t + m->P, 2 * per_t) + 1;
       const int64_t max_items = (int64_t)m->P * ny_base + k3_extra_blocks;
@@ -383,6 +401,7 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
       // (a class of a few pdfs -- the ones a split has grown -- is cut finer: one block walking a whole bucket is a latency of its own)
       int ny = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(32, avg_chunks), (4096 + n_cls - 1) / std::max(1, n_cls)));
       if (ctx->opt[KHG_OPT_K3_NY] > 0) ny = ctx->opt[KHG_OPT_K3_NY];
+      if (ctx->k3_one_block) ny = 1;
       rc = make_items(ny, false, 0, cls_lo, cls_hi, second);
       if (rc) return rc;
       // Both phases on the fp16 matrix cores (k3_accumulate_block16) where the model-derived scales hold and the weight is an ordinary
@@ -446,12 +465,13 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
     // ---- the VALU form: any number of Gaussians, any dimension ----
     auto run_valu = [&](int cls_lo, int cls_hi, int maxG, int n_cls, bool second, void* comm_) -> int {
       const int64_t avg_chunks = (Neff / std::max(1, m->P) + K3_CHUNK - 1) / K3_CHUNK;
-      const size_t lds = sizeof(float) * (size_t)K3_CHUNK * ((size_t)(m->KQ ? 4 * m->KQ : (m->D | 1)) + (maxG | 1) + (post ? 5 : 4));
-      if (lds > 160 * 1024) return khg_set_error(KHG_E_UNSUPPORTED, "khg_acc_stats: pdf too large for the LDS chunk buffers");
+      const size_t lds = k3_valu_lds(m, maxG, post);
+      if (lds > K3_VALU_LDS_MAX) return khg_set_error(KHG_E_UNSUPPORTED, "khg_acc_stats: pdf too large for the LDS chunk buffers");
       const void* k3fn = post ? (m->KQ == 10 ? (const void*)k3_accumulate<10, true> : m->KQ == 20 ? (const void*)k3_accumulate<20, true> : (const void*)k3_accumulate<0, true>)
                               : m->KQ == 10 ? (const void*)k3_accumulate<10> : m->KQ == 20 ? (const void*)k3_accumulate<20> : (const void*)k3_accumulate<0>;
       if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(k3fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      const int ny = (int)std::max<int64_t>(1, std::min<int64_t>(64, (avg_chunks + 3) / 4));
+      int ny = (int)std::max<int64_t>(1, std::min<int64_t>(64, (avg_chunks + 3) / 4));
+      if (ctx->k3_one_block) ny = 1;
       rc = make_items(ny, false, 0, cls_lo, cls_hi, second);
       if (rc) return rc;
       const int nparts_ = comm_ ? nparts : 1;

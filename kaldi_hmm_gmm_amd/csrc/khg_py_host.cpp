@@ -217,6 +217,10 @@ void BindGmm(py::module_& m) {
       }, py::arg("data"), py::arg("preselect"), py::arg("num_gselect"))
       .def("merge", &DiagGmm::Merge, py::arg("target_components"), py::call_guard<py::gil_scoped_release>())
       .def("perturb", [](DiagGmm& g, float pf, py::object randn) { g.Perturb(pf, MakeRandn(randn)); }, py::arg("perturb_factor"), py::arg("randn") = py::none())
+      .def("transform_means", [](DiagGmm& g, Arr<float> M) {
+        if (M.ndim() != 2) throw Error("transform_means: M must be [dim, dim]");
+        g.TransformMeans(M.data(), (size_t)M.shape(0), (size_t)M.shape(1));
+      }, py::arg("M"))
       .def("generate", [](DiagGmm& g, py::object randn) { return Vec1(g.Generate(MakeRandn(randn))); }, py::arg("randn") = py::none())
       .def("interpolate", [](DiagGmm& g, float rho, const DiagGmm& src, int flags) { g.Interpolate(rho, src, flags); }, py::arg("rho"), py::arg("source"),
            py::arg("flags") = (int)kGmmAll)
@@ -244,6 +248,10 @@ void BindGmm(py::module_& m) {
       .def("get_pdf", [](AmDiagGmm& a, int i) { return a.GetPdf(i); }, py::arg("pdf_index"))      // reference-returning, like the reference's binding
       .def_property("_pdfs", [](const AmDiagGmm& a) { return a.pdfs(); }, [](AmDiagGmm& a, std::vector<std::shared_ptr<DiagGmm>> v) { a.pdfs() = std::move(v); })
       .def("compute_gconsts", &AmDiagGmm::ComputeGconsts)
+      .def("transform_means", [](AmDiagGmm& a, Arr<float> M) {
+        if (M.ndim() != 2) throw Error("transform_means: M must be [dim, dim]");
+        a.TransformMeans(M.data(), (size_t)M.shape(0), (size_t)M.shape(1));
+      }, py::arg("M"))
       .def("log_likelihood", [](AmDiagGmm& a, int i, Arr<float> x) { return NoGil([&] { return a.GetPdf(i)->LogLikelihood(x.data(), (size_t)x.size()); }); }, py::arg("pdf_index"), py::arg("data"))
       .def("get_gaussian_mean", [](AmDiagGmm& a, int i, int g) { return Vec1(a.GetPdf(i)->GetComponentMean(g)); }, py::arg("pdf_index"), py::arg("gauss"))
       .def("get_gaussian_variance", [](AmDiagGmm& a, int i, int g) { return Vec1(a.GetPdf(i)->GetComponentVariance(g)); }, py::arg("pdf_index"), py::arg("gauss"))

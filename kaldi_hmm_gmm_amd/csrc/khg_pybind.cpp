@@ -171,6 +171,11 @@ struct KModel {
   py::dict mle_update_finish();
   py::dict ebw_update(KAccs& num_accs, KAccs& den_accs, py::object opts, py::object weight_opts, int flags);
   void invalidate() { Check(khg_model_invalidate(h)); }
+  // gmm-transform-means on the handle (khg_model_transform_means): M [dim, dim]
+  void transform_means(Arr<float> M) {
+    if (M.ndim() != 2 || M.shape(0) != dim || M.shape(1) != dim) throw py::value_error("transform_means: M must be [dim, dim]");
+    Check(NoGil([&] { return khg_model_transform_means(ctx->h, h, M.data()); }));
+  }
   void scale_weights(Arr<int32_t> pdfs, float scale) { Check(khg_model_scale_weights(ctx->h, h, (int32_t)pdfs.shape(0), pdfs.data(), scale)); }
   void split(Arr<int32_t> targets, float perturb, py::object randn) {
     if (targets.shape(0) != num_pdfs) throw py::value_error("split: one target per pdf");
@@ -444,6 +449,34 @@ struct KFmllrStats {
   void add(float scale, KFmllrStats& src) { Check(khg_fmllr_stats_add(ctx->h, h, scale, src.h)); }
   void set_chunk_frames(int64_t frames) { Check(khg_fmllr_stats_set_chunk_frames(h, frames)); }
   int num_chunks() { int32_t n = 0; Check(khg_fmllr_stats_num_chunks(h, &n)); return n; }
+};
+
+// MlltAccs resident in HBM (khg_mllt_stats)
+struct KMlltStats {
+  khg_mllt_stats* h = nullptr;
+  py::object ctx_obj;
+  KContext* ctx;
+  int dim = 0;
+  KMlltStats(py::object ctx_o, int d) : ctx_obj(ctx_o), ctx(ctx_o.cast<KContext*>()), dim(d) { Check(khg_mllt_stats_create(ctx->h, d, &h)); }
+  ~KMlltStats() { close(); }
+  void close() { if (h) { khg_mllt_stats_destroy(h); h = nullptr; } }
+  void zero() { Check(khg_mllt_stats_zero(ctx->h, h)); }
+  py::ssize_t packed() const { return (py::ssize_t)dim * (dim + 1) / 2; }
+  py::dict download() {
+    Arr<double> G({(py::ssize_t)dim, packed()});
+    double beta = 0.0;
+    Check(NoGil([&] { return khg_mllt_stats_download(ctx->h, h, &beta, G.mutable_data()); }));
+    py::dict d;
+    d["beta"] = beta; d["G"] = G;
+    return d;
+  }
+  void upload(double beta, Arr<double> G) {
+    if (G.size() != (py::ssize_t)dim * packed()) throw py::value_error("DeviceMlltStats.upload: beta, G [dim, dim (dim + 1) / 2]");
+    Check(NoGil([&] { return khg_mllt_stats_upload(ctx->h, h, &beta, G.data()); }));
+  }
+  void add(float scale, KMlltStats& src) { Check(khg_mllt_stats_add(ctx->h, h, scale, src.h)); }
+  void set_chunk_frames(int64_t frames) { Check(khg_mllt_stats_set_chunk_frames(h, frames)); }
+  int num_chunks() { int32_t n = 0; Check(khg_mllt_stats_num_chunks(h, &n)); return n; }
 };
 
 struct KUtts {
@@ -795,6 +828,11 @@ struct KUtts {
     if (utt2spk.size() != n_utt) throw py::value_error("acc_fmllr_stats_post: one speaker per utterance");
     Check(NoGil([&] { return khg_acc_fmllr_stats_post(ctx->h, m.h, tm.h, h, post.h, scale, utt2spk.data(), stats.h); }));
   }
+  // gmm-acc-mllt (khg_acc_mllt_stats_post)
+  void acc_mllt_stats_post(KModel& m, KTransitions& tm, khg::PyDevicePosteriors& post, KMlltStats& stats, float scale) {
+    if (!post.h) throw py::value_error("acc_mllt_stats_post: the DevicePosteriors are closed");
+    Check(NoGil([&] { return khg_acc_mllt_stats_post(ctx->h, m.h, tm.h, h, post.h, scale, stats.h); }));
+  }
   // transform-feats (khg_utts_transform_feats): W [n_spk, dim, dim + 1] from the host or, as an integer, a device pointer; out: a device
   // pointer for the transformed rows, or None for the set's own rows in place
   void transform_feats(Arr<int32_t> utt2spk, py::object W, py::object out, int n_spk) {
@@ -859,6 +897,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
            py::arg("weight_opts") = py::none(), py::arg("flags") = 0x7)
       .def("scale_weights", &KModel::scale_weights)
       .def("invalidate", &KModel::invalidate)
+      .def("transform_means", &KModel::transform_means, py::arg("M"))
       .def("split", &KModel::split, py::arg("targets"), py::arg("perturb_factor"), py::arg("randn"))
       .def("merge", &KModel::merge, py::arg("targets"))
       .def("download", &KModel::download, py::arg("weights") = true)
@@ -928,6 +967,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
            py::arg("comm") = py::none(), py::arg("nparts") = 4)
       .def("acc_fmllr_stats_post", &KUtts::acc_fmllr_stats_post, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("utt2spk"), py::arg("stats"),
            py::arg("scale") = 1.0f)
+      .def("acc_mllt_stats_post", &KUtts::acc_mllt_stats_post, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("stats"), py::arg("scale") = 1.0f)
       .def("transform_feats", &KUtts::transform_feats, py::arg("utt2spk"), py::arg("W"), py::arg("out") = py::none(), py::arg("n_spk") = 0)
       .def("close", &KUtts::close);
 
@@ -941,6 +981,16 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("estimate", &KFmllrStats::estimate, py::arg("min_count") = 500.0, py::arg("num_iters") = 40, py::arg("W_d") = py::none())
       .def("set_chunk_frames", &KFmllrStats::set_chunk_frames, py::arg("frames")).def("num_chunks", &KFmllrStats::num_chunks)
       .def("close", &KFmllrStats::close);
+
+  py::class_<KMlltStats>(m, "DeviceMlltStats")
+      .def(py::init<py::object, int>(), py::arg("ctx"), py::arg("dim"))
+      .def_property_readonly("h", [](KMlltStats& x) { return reinterpret_cast<uintptr_t>(x.h); })
+      .def_readonly("ctx", &KMlltStats::ctx_obj).def_readonly("dim", &KMlltStats::dim)
+      .def("zero", &KMlltStats::zero).def("download", &KMlltStats::download)
+      .def("upload", &KMlltStats::upload, py::arg("beta"), py::arg("G"))
+      .def("add", &KMlltStats::add, py::arg("scale"), py::arg("src"))
+      .def("set_chunk_frames", &KMlltStats::set_chunk_frames, py::arg("frames")).def("num_chunks", &KMlltStats::num_chunks)
+      .def("close", &KMlltStats::close);
 
   // ---- host-side functions (no GPU): gconsts, M-step, merge, transition update, AddTransitionProbs costs ----
   m.def("compute_gconsts", [](Arr<int32_t> go, Arr<float> w, Arr<float> iv, Arr<float> miv) {
@@ -982,6 +1032,23 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
      "ComputeFmllrMatrixDiagGmmFull per speaker on host statistics (khg_fmllr_compute; DESIGN.md 7l)");
   m.attr("FMLLR_OK") = KHG_FMLLR_OK; m.attr("FMLLR_LOW_COUNT") = KHG_FMLLR_LOW_COUNT; m.attr("FMLLR_SINGULAR") = KHG_FMLLR_SINGULAR;
   m.attr("FMLLR_MAX_DIM") = KHG_FMLLR_MAX_DIM;
+  m.def("mllt_compute", [](double beta, Arr<double> G, int num_iters) {
+    if (G.ndim() != 2 || G.shape(0) < 1 || G.shape(1) != G.shape(0) * (G.shape(0) + 1) / 2)
+      throw py::value_error("mllt_compute: beta, G [dim, dim (dim + 1) / 2]");
+    const py::ssize_t D = G.shape(0);
+    khg_mllt_options o;
+    khg_mllt_options_default(&o);
+    o.num_iters = num_iters;
+    Arr<float> M({D, D});
+    Arr<double> M64({D, D});
+    double impr = 0.0, count = 0.0;
+    int32_t status = 0;
+    Check(NoGil([&] { return khg_mllt_compute(&o, (int32_t)D, beta, G.data(), M.mutable_data(), M64.mutable_data(), &impr, &count, &status); }));
+    py::dict d;
+    d["M"] = M; d["M64"] = M64; d["objf_impr"] = impr; d["count"] = count; d["status"] = (int)status;
+    return d;
+  }, py::arg("beta"), py::arg("G"), py::arg("num_iters") = 200, "MlltAccs::Update on host statistics (khg_mllt_compute; DESIGN.md 7m)");
+  m.attr("MLLT_OK") = KHG_MLLT_OK; m.attr("MLLT_SINGULAR") = KHG_MLLT_SINGULAR; m.attr("MLLT_MAX_DIM") = KHG_MLLT_MAX_DIM;
   m.def("scaled_trans_cost", [](Arr<float> lp, Arr<float> nsl, Arr<int32_t> id2state, Arr<uint8_t> isl, float ts, float sls) {
     const int nt = (int)lp.shape(0) - 1;
     Arr<float> out({(py::ssize_t)nt + 1});

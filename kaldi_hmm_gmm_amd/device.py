@@ -27,6 +27,7 @@ DeviceTransitions = _ext.DeviceTransitions  # TransitionIdToPdf + scaled transit
 UtteranceSet = _ext.UtteranceSet            # features + compiled graphs of a shard; loglikes / align / acc_stats
 DecodingGraph = _ext.DecodingGraph          # khg_graph: ONE decoding graph resident in HBM, shared by sets (graph=) and batch calls
 DeviceFmllrStats = _ext.DeviceFmllrStats    # khg_fmllr_stats: FmllrDiagGmmAccs per speaker in HBM; download() -> numpy beta / K / G
+DeviceMlltStats = _ext.DeviceMlltStats      # khg_mllt_stats: MlltAccs in HBM; download() -> beta, numpy G
 
 
 class DeviceAccs(_ext.DeviceAccs):
