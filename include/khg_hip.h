@@ -1003,6 +1003,73 @@ int khg_mllt_compute(const khg_mllt_options *o, int32_t dim, double beta, const 
  * holds the transformed parameters, all its images consistent with one another, and is the caller's to replace. */
 int khg_model_transform_means(khg_ctx *ctx, khg_model *m, const float *M_h);
 
+/* ---- LDA on spliced features (splice-feats, acc-lda, est-lda, transform-feats) ------------------------------------ */
+/* The reference has no LDA: the rule in DESIGN.md 7n is the specification (tests/lda_ref.py restates it).  Notation: dim = the set's
+ * feature dimension, left / right >= 0 the context, Dz = dim (left + right + 1) the spliced dimension; the spliced frame is
+ * z_t[k dim + j] = x[clamp(t + k - left, 0, T - 1)][j], k = 0 .. left + right: edge frames are replicated inside the utterance, a
+ * neighbouring utterance's row is never read.  The spliced matrix is never written to device memory.  Dz up to
+ * KHG_LDA_MAX_SPLICED_DIM: the second-order kernel stages 64 spliced rows of 16 ceil(Dz / 16) + 1 floats in LDS (129 KiB of the 160 at
+ * 512); its registers do not depend on Dz.  Above: KHG_E_UNSUPPORTED. */
+#define KHG_LDA_MAX_SPLICED_DIM 512
+#define KHG_LDA_TRANSFORM_LDS_BYTES 147456   /* what khg_utts_splice_transform_feats stages: 4 ((64 + left + right) dim + out_dim ((Dz + 1) | 1)) bytes */
+#define KHG_LDA_OK 0             /* the transform was estimated                                                         */
+#define KHG_LDA_SINGULAR 1       /* N <= 0, a Cholesky pivot not finite or not > 0, or Jacobi not converged: M = [I | 0] */
+/* Kaldi's LdaEstimate accumulators resident on the device, all fp64, in Kaldi's layout: zero_acc[num_classes],
+ * first_acc[num_classes][Dz], total_second_acc as Kaldi's packed lower triangle ((i, j <= i) at i (i + 1) / 2 + j): Dz (Dz + 1) / 2
+ * doubles.  download takes NULL for what is not wanted and synchronises (deferred kernel errors: KHG_E_RUNTIME), upload needs all
+ * three.  add: dst += (double)scale * src elementwise (one product, one add), asynchronous; the handles must agree in classes,
+ * dimension and context and belong to `ctx` (KHG_E_ARG). */
+typedef struct khg_lda_stats khg_lda_stats;
+int khg_lda_stats_create(khg_ctx *ctx, int32_t num_classes, int32_t dim, int32_t left, int32_t right, khg_lda_stats **out);
+int khg_lda_stats_destroy(khg_lda_stats *s);
+int khg_lda_stats_zero(khg_ctx *ctx, khg_lda_stats *s);
+int khg_lda_stats_download(khg_ctx *ctx, const khg_lda_stats *s, double *zero_h, double *first_h, double *second_h);
+int khg_lda_stats_upload(khg_ctx *ctx, khg_lda_stats *s, const double *zero_h, const double *first_h, const double *second_h);
+int khg_lda_stats_add(khg_ctx *ctx, khg_lda_stats *dst, float scale, const khg_lda_stats *src);
+/* The second-order sum parks one image of Dz (Dz + 1) / 2 doubles per 1024-frame slice; a chunk of `frames` frames (default 2^18, at
+ * least one slice, at most 2^24) holds min(frames / 1024, 256 MiB of images) slices.  The statistics do not depend on it, bit for bit.
+ * num_chunks: how many chunks the last accumulation into the handle ran (tests). */
+int khg_lda_stats_set_chunk_frames(khg_lda_stats *s, int64_t frames);
+int khg_lda_stats_num_chunks(const khg_lda_stats *s, int32_t *n_chunks);
+/* acc-lda from posteriors resident on the device.  No model is involved: the transition model alone names the class.  Every entry
+ * (utterance u, frame t, transition-id, weight w64) of `p` counts with w = (float)((double)scale * w64), as in khg_acc_stats_post, for
+ * class c = id2pdf[transition-id]: zero_acc[c] += w, first_acc[c] += w z_t, total_second_acc += w z_t z_t^T.  Computed form: the
+ * second-order term is sum_t (W_t z_t[i]) z_t[j] with W_t the double sum of the frame's w in entry order, W_t z_t[i] rounded once in
+ * double, over 1024-frame slices of the call's frame list (the utterances with frames in `p`, in set order) on the fp64 matrix pipe,
+ * the slices added in slice order; the class sums run over the call's entries bucketed by class with K3's stable sort, one chain per
+ * (class, element) in sorted order over slices of <= 1024 entries, added in slice order.  No atomics: the same bits from run to run
+ * and whatever the chunk size.  An entry with w == 0, an utterance without frames in `p` and a frame without entries add nothing;
+ * negative weights are taken as they are; there is no random pruning.  Adds into `stats`.  khg_acc_stats_post's refusals, before
+ * anything is launched (the handle keeps its bits): KHG_E_ARG, KHG_E_ARG too for statistics of another dimension or context or whose
+ * class count is not the transition model's number of pdfs, KHG_E_UNSUPPORTED for 2^31 - 1 or more entries or frames.  One word per
+ * class is read back for the class plan (synchronises once); the rest is asynchronous on the context's stream. */
+int khg_acc_lda_stats_post(khg_ctx *ctx, const khg_tm *tm, khg_utts *u, const khg_posteriors *p, float scale, khg_lda_stats *stats);
+typedef struct {
+  int32_t target_dim;          /* 40: rows of M */
+  int32_t remove_offset;       /* 0; otherwise a last column -M mu is appended */
+  double within_class_factor;  /* 1.0; f != 1 scales row i by sqrt((f + lambda_i) / (1 + lambda_i)) */
+} khg_lda_options;
+void khg_lda_options_default(khg_lda_options *o);
+/* Kaldi's LdaEstimate::Estimate on host arrays laid out as khg_lda_stats_download gives them; needs no device (one Dz x Dz problem per
+ * training stage).  All fp64, one operation at a time, sums in index order: N = sum zero, mu = sum_c first[c] / N, Tc = second / N - mu
+ * mu^T, Bc = sum_{c: zero[c] != 0} first[c] first[c]^T / (N zero[c]) - mu mu^T, Wc = Tc - Bc = Lc Lc^T (Cholesky), P = Lc^-1 Bc Lc^-T,
+ * its eigen-decomposition by cyclic Jacobi (stops when a full sweep rotates nothing; 64 sweeps without that: SINGULAR), eigenvalues
+ * descending (ties by original index), M_full = U^T Lc^-1, the within_class_factor scaling, every row's sign fixed so that its element
+ * of largest magnitude (lowest index among equals) is positive, M = the first target_dim rows, with remove_offset a last column -M mu.
+ * Outputs (any may be NULL, but one of M_h / M64_h is needed): M_h[target_dim][dim_z + remove_offset] floats, M64_h the same before
+ * narrowing, Mfull64_h[dim_z][dim_z], eig_h[dim_z], *count = N, *status KHG_LDA_*.  SINGULAR gives M = [I_target | 0], M_full = I and
+ * zero eigenvalues.  o == NULL: the defaults.  KHG_E_ARG for target_dim < 1 or > dim_z, an option that is not finite, nowhere to put
+ * M; KHG_E_UNSUPPORTED for dim_z > KHG_LDA_MAX_SPLICED_DIM. */
+int khg_lda_compute(const khg_lda_options *o, int32_t num_classes, int32_t dim_z, const double *zero_h, const double *first_h,
+                    const double *second_h, float *M_h, double *M64_h, double *Mfull64_h, double *eig_h, double *count, int32_t *status);
+/* splice-feats | transform-feats on the set's resident rows, out of place: y_t[r] = M[r][Dz] with an offset column (has_offset), 0
+ * without, then y_t[r] = fmaf(M[r][c], z_t[c], y_t[r]) for c = 0 .. Dz - 1, in float (7l's transform rule).  M_h: out_dim x
+ * (Dz + has_offset) floats on the host; M_h == NULL is splice-feats: out_dim must be Dz and the spliced rows are copied.  out_d: a
+ * caller-owned device buffer of [rows of the set][out_dim] floats; the set is untouched.  KHG_E_UNSUPPORTED, naming the limit, for
+ * Dz > KHG_LDA_MAX_SPLICED_DIM or when the matrix and the rows do not fit KHG_LDA_TRANSFORM_LDS_BYTES.  Synchronous. */
+int khg_utts_splice_transform_feats(khg_ctx *ctx, khg_utts *u, int32_t left, int32_t right, int32_t out_dim, int32_t has_offset,
+                                    const float *M_h, float *out_d);
+
 #ifdef __cplusplus
 }
 #endif

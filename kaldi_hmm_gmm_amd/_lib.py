@@ -118,6 +118,10 @@ class MlltOptionsC(C.Structure):
     _fields_ = [("num_iters", C.c_int32)]
 
 
+class LdaOptionsC(C.Structure):
+    _fields_ = [("target_dim", C.c_int32), ("remove_offset", C.c_int32), ("within_class_factor", C.c_double)]
+
+
 class RescoreStatsC(C.Structure):
     _fields_ = [("arcs", C.c_int64), ("emitting_arcs", C.c_int64), ("cells", C.c_int64)]
 
@@ -296,6 +300,19 @@ SIGNATURES = {
     "khg_mllt_options_default": (None, [C.POINTER(MlltOptionsC)]),
     "khg_mllt_compute": (C.c_int, [C.POINTER(MlltOptionsC), C.c_int32, C.c_double, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, c_i32p]),
     "khg_model_transform_means": (C.c_int, [vp, vp, c_f32p]),
+    "khg_lda_stats_create": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]),
+    "khg_lda_stats_destroy": (C.c_int, [vp]),
+    "khg_lda_stats_zero": (C.c_int, [vp, vp]),
+    "khg_lda_stats_download": (C.c_int, [vp, vp, c_f64p, c_f64p, c_f64p]),
+    "khg_lda_stats_upload": (C.c_int, [vp, vp, c_f64p, c_f64p, c_f64p]),
+    "khg_lda_stats_add": (C.c_int, [vp, vp, C.c_float, vp]),
+    "khg_lda_stats_set_chunk_frames": (C.c_int, [vp, C.c_int64]),
+    "khg_lda_stats_num_chunks": (C.c_int, [vp, c_i32p]),
+    "khg_acc_lda_stats_post": (C.c_int, [vp, vp, vp, vp, C.c_float, vp]),
+    "khg_lda_options_default": (None, [C.POINTER(LdaOptionsC)]),
+    "khg_lda_compute": (C.c_int, [C.POINTER(LdaOptionsC), C.c_int32, C.c_int32, c_f64p, c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p,
+                                  c_i32p]),
+    "khg_utts_splice_transform_feats": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

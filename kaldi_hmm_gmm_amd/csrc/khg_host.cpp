@@ -853,3 +853,189 @@ extern "C" int khg_mllt_compute(const khg_mllt_options* o, int32_t dim, double b
   if (M_h) for (size_t i = 0; i < n; ++i) M_h[i] = (float)A[i];
   return KHG_OK;
 }
+
+// ---- LDA estimate: the reference has no LDA, the rule written there is the specification ---------------------------
+// Kaldi's LdaEstimate::Estimate on the statistics of khg_lda_stats_download.  One IEEE fp64 operation at a time in the written order
+// (contraction is off for this file from the fMLLR section on), every sum in index order.  tests/lda_ref.py restates the rule with
+// numpy's Cholesky and eigh; the two agree to the residuals 7n records, not on the bits.
+namespace {
+
+constexpr int kLdaMaxSweeps = 64;
+
+// The eigen-decomposition of the symmetric n x n matrix A by cyclic Jacobi (rows p < q in index order).  A is destroyed (its diagonal
+// ends as the eigenvalues); Vt's ROWS end as the eigenvectors.  A pair is left alone when its off-diagonal element is exactly zero,
+// is lost in the rounding of both its diagonal elements, or is below 2^-100 of the largest diagonal magnitude the matrix started
+// with (then it is set to zero).  true: a full sweep rotated nothing.  false: kLdaMaxSweeps sweeps did not get there, or a value
+// stopped being finite.
+bool LdaJacobi(int n, double* A, double* Vt) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) Vt[(size_t)i * n + j] = i == j ? 1.0 : 0.0;
+  double anorm = 0.0;
+  for (int i = 0; i < n; ++i) anorm = std::max(anorm, std::fabs(A[(size_t)i * n + i]));
+  if (!std::isfinite(anorm)) return false;
+  const double tiny = std::ldexp(anorm, -100);
+  for (int sweep = 0; sweep < kLdaMaxSweeps; ++sweep) {
+    int rotated = 0;
+    for (int p = 0; p + 1 < n; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        const double apq = A[(size_t)p * n + q];
+        if (apq == 0.0) continue;
+        const double app = A[(size_t)p * n + p], aqq = A[(size_t)q * n + q], g = std::fabs(apq);
+        if (!std::isfinite(apq)) return false;
+        if (g <= tiny || (std::fabs(app) + g == std::fabs(app) && std::fabs(aqq) + g == std::fabs(aqq))) {
+          A[(size_t)p * n + q] = 0.0; A[(size_t)q * n + p] = 0.0;
+          continue;
+        }
+        ++rotated;
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        double* rp = A + (size_t)p * n;
+        double* rq = A + (size_t)q * n;
+        for (int k = 0; k < n; ++k) {
+          const double akp = rp[k], akq = rq[k];
+          rp[k] = c * akp - s * akq;
+          rq[k] = s * akp + c * akq;
+        }
+        rp[p] = app - t * apq; rq[q] = aqq + t * apq; rp[q] = 0.0; rq[p] = 0.0;
+        for (int k = 0; k < n; ++k) { A[(size_t)k * n + p] = rp[k]; A[(size_t)k * n + q] = rq[k]; }
+        double* vp = Vt + (size_t)p * n;
+        double* vq = Vt + (size_t)q * n;
+        for (int k = 0; k < n; ++k) {
+          const double vkp = vp[k], vkq = vq[k];
+          vp[k] = c * vkp - s * vkq;
+          vq[k] = s * vkp + c * vkq;
+        }
+      }
+    if (rotated == 0) return true;
+  }
+  return false;
+}
+
+// Mfull: n x n, eig: n, mu: n.  KHG_LDA_OK or KHG_LDA_SINGULAR (then the outputs are untouched).
+int32_t LdaOne(const khg_lda_options* o, int C, int n, const double* zero, const double* first, const double* second, double* Mfull, double* eig,
+               double* mu, double* count) {
+  double N = 0.0;
+  for (int c = 0; c < C; ++c) N = N + zero[c];
+  *count = N;
+  if (!(N > 0.0) || !std::isfinite(N)) return KHG_LDA_SINGULAR;
+  const size_t nn = (size_t)n * n;
+  std::vector<double> Bc(nn), Wc(nn), Lc(nn, 0.0), Li(nn, 0.0), T1(nn), P(nn), Vt(nn);
+  for (int i = 0; i < n; ++i) {
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s = s + first[(size_t)c * n + i];
+    mu[i] = s / N;
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      const double mm = mu[i] * mu[j];
+      double b = 0.0;
+      for (int c = 0; c < C; ++c)
+        if (zero[c] != 0.0) b = b + (first[(size_t)c * n + i] * first[(size_t)c * n + j]) / (N * zero[c]);
+      b = b - mm;
+      const double tc = second[(size_t)i * (i + 1) / 2 + j] / N - mm;
+      Bc[(size_t)i * n + j] = b; Bc[(size_t)j * n + i] = b;
+      Wc[(size_t)i * n + j] = tc - b; Wc[(size_t)j * n + i] = tc - b;
+    }
+  // Wc = Lc Lc^T
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double s = Wc[(size_t)i * n + j];
+      for (int k = 0; k < j; ++k) s = s - Lc[(size_t)i * n + k] * Lc[(size_t)j * n + k];
+      if (i == j) {
+        if (!(std::isfinite(s) && s > 0.0)) return KHG_LDA_SINGULAR;
+        Lc[(size_t)i * n + i] = std::sqrt(s);
+      } else {
+        Lc[(size_t)i * n + j] = s / Lc[(size_t)j * n + j];
+      }
+    }
+  // Li = Lc^-1 (lower triangular), column by column
+  for (int j = 0; j < n; ++j) {
+    Li[(size_t)j * n + j] = 1.0 / Lc[(size_t)j * n + j];
+    for (int i = j + 1; i < n; ++i) {
+      double s = 0.0;
+      for (int k = j; k < i; ++k) s = s + Lc[(size_t)i * n + k] * Li[(size_t)k * n + j];
+      Li[(size_t)i * n + j] = -s / Lc[(size_t)i * n + i];
+    }
+  }
+  // P = Li Bc Li^T, the lower triangle computed and mirrored
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {
+      double s = 0.0;
+      for (int k = 0; k <= i; ++k) s = s + Li[(size_t)i * n + k] * Bc[(size_t)k * n + j];
+      T1[(size_t)i * n + j] = s;
+    }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double s = 0.0;
+      for (int k = 0; k <= j; ++k) s = s + T1[(size_t)i * n + k] * Li[(size_t)j * n + k];
+      P[(size_t)i * n + j] = s; P[(size_t)j * n + i] = s;
+    }
+  if (!LdaJacobi(n, P.data(), Vt.data())) return KHG_LDA_SINGULAR;      // NOT_CONVERGED is treated as SINGULAR
+  std::vector<int> order(n);
+  for (int i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return P[(size_t)a * n + a] > P[(size_t)b * n + b]; });
+  const double f = o->within_class_factor;
+  for (int i = 0; i < n; ++i) {
+    const double lam = P[(size_t)order[i] * n + order[i]];
+    if (!std::isfinite(lam)) return KHG_LDA_SINGULAR;
+    const double* v = Vt.data() + (size_t)order[i] * n;
+    double* row = T1.data() + (size_t)i * n;                              // T1 is free again: the rows of M_full before they are accepted
+    for (int j = 0; j < n; ++j) {
+      double s = 0.0;
+      for (int k = j; k < n; ++k) s = s + v[k] * Li[(size_t)k * n + j];
+      row[j] = s;
+    }
+    if (f != 1.0) {
+      const double sc = std::sqrt((f + lam) / (1.0 + lam));
+      if (!std::isfinite(sc)) return KHG_LDA_SINGULAR;
+      for (int j = 0; j < n; ++j) row[j] = row[j] * sc;
+    }
+    int best = 0;
+    for (int j = 1; j < n; ++j)
+      if (std::fabs(row[j]) > std::fabs(row[best])) best = j;
+    if (row[best] < 0.0)
+      for (int j = 0; j < n; ++j) row[j] = -row[j];
+    Wc[i] = lam;                                                          // Wc is free again: the sorted eigenvalues
+  }
+  memcpy(Mfull, T1.data(), sizeof(double) * nn);
+  memcpy(eig, Wc.data(), sizeof(double) * (size_t)n);
+  return KHG_LDA_OK;
+}
+
+}  // namespace
+
+extern "C" void khg_lda_options_default(khg_lda_options* o) { o->target_dim = 40; o->remove_offset = 0; o->within_class_factor = 1.0; }
+
+extern "C" int khg_lda_compute(const khg_lda_options* o, int32_t num_classes, int32_t dim_z, const double* zero_h, const double* first_h,
+                               const double* second_h, float* M_h, double* M64_h, double* Mfull64_h, double* eig_h, double* count, int32_t* status) {
+  khg_lda_options def;
+  khg_lda_options_default(&def);
+  if (!o) o = &def;
+  if (num_classes < 1 || dim_z < 1 || !zero_h || !first_h || !second_h || (!M_h && !M64_h)) return khg_set_error(KHG_E_ARG, "khg_lda_compute: bad arguments");
+  if (dim_z > KHG_LDA_MAX_SPLICED_DIM)
+    return khg_set_error(KHG_E_UNSUPPORTED, "khg_lda_compute: dim " + std::to_string(dim_z) + " is above KHG_LDA_MAX_SPLICED_DIM");
+  if (o->target_dim < 1 || o->target_dim > dim_z)
+    return khg_set_error(KHG_E_ARG, "khg_lda_compute: target_dim " + std::to_string(o->target_dim) + " is outside 1 .. " + std::to_string(dim_z));
+  if (!std::isfinite(o->within_class_factor)) return khg_set_error(KHG_E_ARG, "khg_lda_compute: within_class_factor is not finite");
+  const int n = dim_z, T = o->target_dim, MW = n + (o->remove_offset ? 1 : 0);
+  std::vector<double> Mfull((size_t)n * n, 0.0), eig((size_t)n, 0.0), mu((size_t)n, 0.0), M((size_t)T * MW, 0.0);
+  for (int i = 0; i < n; ++i) Mfull[(size_t)i * n + i] = 1.0;
+  double N = 0.0;
+  const int32_t st = LdaOne(o, num_classes, n, zero_h, first_h, second_h, Mfull.data(), eig.data(), mu.data(), &N);
+  for (int i = 0; i < T; ++i) {
+    for (int j = 0; j < n; ++j) M[(size_t)i * MW + j] = Mfull[(size_t)i * n + j];
+    if (o->remove_offset && st == KHG_LDA_OK) {
+      double s = 0.0;
+      for (int j = 0; j < n; ++j) s = s + Mfull[(size_t)i * n + j] * mu[j];
+      M[(size_t)i * MW + n] = -s;
+    }
+  }
+  if (status) *status = st;
+  if (count) *count = N;
+  if (M64_h) memcpy(M64_h, M.data(), sizeof(double) * M.size());
+  if (M_h) for (size_t i = 0; i < M.size(); ++i) M_h[i] = (float)M[i];
+  if (Mfull64_h) memcpy(Mfull64_h, Mfull.data(), sizeof(double) * Mfull.size());
+  if (eig_h) memcpy(eig_h, eig.data(), sizeof(double) * eig.size());
+  return KHG_OK;
+}

@@ -479,6 +479,37 @@ struct KMlltStats {
   int num_chunks() { int32_t n = 0; Check(khg_mllt_stats_num_chunks(h, &n)); return n; }
 };
 
+// LdaEstimate accumulators resident in HBM (khg_lda_stats)
+struct KLdaStats {
+  khg_lda_stats* h = nullptr;
+  py::object ctx_obj;
+  KContext* ctx;
+  int num_classes = 0, dim = 0, left = 0, right = 0, dim_z = 0;
+  KLdaStats(py::object ctx_o, int c, int d, int l, int r) : ctx_obj(ctx_o), ctx(ctx_o.cast<KContext*>()), num_classes(c), dim(d), left(l), right(r) {
+    Check(khg_lda_stats_create(ctx->h, c, d, l, r, &h));
+    dim_z = d * (l + r + 1);
+  }
+  ~KLdaStats() { close(); }
+  void close() { if (h) { khg_lda_stats_destroy(h); h = nullptr; } }
+  void zero() { Check(khg_lda_stats_zero(ctx->h, h)); }
+  py::ssize_t packed() const { return (py::ssize_t)dim_z * (dim_z + 1) / 2; }
+  py::dict download() {
+    Arr<double> z({(py::ssize_t)num_classes}), f({(py::ssize_t)num_classes, (py::ssize_t)dim_z}), s2({packed()});
+    Check(NoGil([&] { return khg_lda_stats_download(ctx->h, h, z.mutable_data(), f.mutable_data(), s2.mutable_data()); }));
+    py::dict d;
+    d["zero_acc"] = z; d["first_acc"] = f; d["total_second_acc"] = s2;
+    return d;
+  }
+  void upload(Arr<double> z, Arr<double> f, Arr<double> s2) {
+    if (z.size() != num_classes || f.size() != (py::ssize_t)num_classes * dim_z || s2.size() != packed())
+      throw py::value_error("DeviceLdaStats.upload: zero_acc [num_classes], first_acc [num_classes, dim_z], total_second_acc [dim_z (dim_z + 1) / 2]");
+    Check(NoGil([&] { return khg_lda_stats_upload(ctx->h, h, z.data(), f.data(), s2.data()); }));
+  }
+  void add(float scale, KLdaStats& src) { Check(khg_lda_stats_add(ctx->h, h, scale, src.h)); }
+  void set_chunk_frames(int64_t frames) { Check(khg_lda_stats_set_chunk_frames(h, frames)); }
+  int num_chunks() { int32_t n = 0; Check(khg_lda_stats_num_chunks(h, &n)); return n; }
+};
+
 struct KUtts {
   khg_utts* h = nullptr;
   py::object ctx_obj, keep, keep_model;
@@ -833,6 +864,27 @@ struct KUtts {
     if (!post.h) throw py::value_error("acc_mllt_stats_post: the DevicePosteriors are closed");
     Check(NoGil([&] { return khg_acc_mllt_stats_post(ctx->h, m.h, tm.h, h, post.h, scale, stats.h); }));
   }
+  // acc-lda (khg_acc_lda_stats_post): no model, the transition model names the class
+  void acc_lda_stats_post(KTransitions& tm, khg::PyDevicePosteriors& post, KLdaStats& stats, float scale) {
+    if (!post.h) throw py::value_error("acc_lda_stats_post: the DevicePosteriors are closed");
+    Check(NoGil([&] { return khg_acc_lda_stats_post(ctx->h, tm.h, h, post.h, scale, stats.h); }));
+  }
+  // splice-feats | transform-feats (khg_utts_splice_transform_feats): M [out_dim, dim_z (+ 1)] from the host, or None for the spliced
+  // rows themselves; out: a device pointer for [rows, out_dim] floats
+  void splice_transform_feats(int left, int right, py::object M, uintptr_t out) {
+    if (left < 0 || right < 0) throw py::value_error("splice_transform_feats: left and right must be >= 0");
+    const int dz = dim * (left + right + 1);
+    Arr<float> ma;
+    const float* mh = nullptr;
+    int out_dim = dz, has_offset = 0;
+    if (!M.is_none()) {
+      ma = M.cast<Arr<float>>();
+      if (ma.ndim() != 2 || (ma.shape(1) != dz && ma.shape(1) != dz + 1) || ma.shape(0) < 1)
+        throw py::value_error("splice_transform_feats: M must be [out_dim, dim (left + right + 1)] or one column more");
+      out_dim = (int)ma.shape(0); has_offset = ma.shape(1) == dz + 1; mh = ma.data();
+    }
+    Check(NoGil([&] { return khg_utts_splice_transform_feats(ctx->h, h, left, right, out_dim, has_offset, mh, reinterpret_cast<float*>(out)); }));
+  }
   // transform-feats (khg_utts_transform_feats): W [n_spk, dim, dim + 1] from the host or, as an integer, a device pointer; out: a device
   // pointer for the transformed rows, or None for the set's own rows in place
   void transform_feats(Arr<int32_t> utt2spk, py::object W, py::object out, int n_spk) {
@@ -968,6 +1020,8 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("acc_fmllr_stats_post", &KUtts::acc_fmllr_stats_post, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("utt2spk"), py::arg("stats"),
            py::arg("scale") = 1.0f)
       .def("acc_mllt_stats_post", &KUtts::acc_mllt_stats_post, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("stats"), py::arg("scale") = 1.0f)
+      .def("acc_lda_stats_post", &KUtts::acc_lda_stats_post, py::arg("tm"), py::arg("post"), py::arg("stats"), py::arg("scale") = 1.0f)
+      .def("splice_transform_feats", &KUtts::splice_transform_feats, py::arg("left"), py::arg("right"), py::arg("M"), py::arg("out"))
       .def("transform_feats", &KUtts::transform_feats, py::arg("utt2spk"), py::arg("W"), py::arg("out") = py::none(), py::arg("n_spk") = 0)
       .def("close", &KUtts::close);
 
@@ -991,6 +1045,17 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("add", &KMlltStats::add, py::arg("scale"), py::arg("src"))
       .def("set_chunk_frames", &KMlltStats::set_chunk_frames, py::arg("frames")).def("num_chunks", &KMlltStats::num_chunks)
       .def("close", &KMlltStats::close);
+
+  py::class_<KLdaStats>(m, "DeviceLdaStats")
+      .def(py::init<py::object, int, int, int, int>(), py::arg("ctx"), py::arg("num_classes"), py::arg("dim"), py::arg("left") = 4, py::arg("right") = 4)
+      .def_property_readonly("h", [](KLdaStats& x) { return reinterpret_cast<uintptr_t>(x.h); })
+      .def_readonly("ctx", &KLdaStats::ctx_obj).def_readonly("num_classes", &KLdaStats::num_classes).def_readonly("dim", &KLdaStats::dim)
+      .def_readonly("left", &KLdaStats::left).def_readonly("right", &KLdaStats::right).def_readonly("dim_z", &KLdaStats::dim_z)
+      .def("zero", &KLdaStats::zero).def("download", &KLdaStats::download)
+      .def("upload", &KLdaStats::upload, py::arg("zero_acc"), py::arg("first_acc"), py::arg("total_second_acc"))
+      .def("add", &KLdaStats::add, py::arg("scale"), py::arg("src"))
+      .def("set_chunk_frames", &KLdaStats::set_chunk_frames, py::arg("frames")).def("num_chunks", &KLdaStats::num_chunks)
+      .def("close", &KLdaStats::close);
 
   // ---- host-side functions (no GPU): gconsts, M-step, merge, transition update, AddTransitionProbs costs ----
   m.def("compute_gconsts", [](Arr<int32_t> go, Arr<float> w, Arr<float> iv, Arr<float> miv) {
@@ -1049,6 +1114,28 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
     return d;
   }, py::arg("beta"), py::arg("G"), py::arg("num_iters") = 200, "MlltAccs::Update on host statistics (khg_mllt_compute; DESIGN.md 7m)");
   m.attr("MLLT_OK") = KHG_MLLT_OK; m.attr("MLLT_SINGULAR") = KHG_MLLT_SINGULAR; m.attr("MLLT_MAX_DIM") = KHG_MLLT_MAX_DIM;
+  m.def("lda_compute", [](Arr<double> zero, Arr<double> first, Arr<double> second, int target_dim, bool remove_offset, double within_class_factor) {
+    if (first.ndim() != 2 || zero.ndim() != 1 || second.ndim() != 1 || first.shape(0) != zero.shape(0) || first.shape(0) < 1 || first.shape(1) < 1 ||
+        second.shape(0) != first.shape(1) * (first.shape(1) + 1) / 2)
+      throw py::value_error("lda_compute: zero_acc [num_classes], first_acc [num_classes, dim_z], total_second_acc [dim_z (dim_z + 1) / 2]");
+    const py::ssize_t C = first.shape(0), n = first.shape(1);
+    khg_lda_options o;
+    khg_lda_options_default(&o);
+    o.target_dim = target_dim; o.remove_offset = remove_offset ? 1 : 0; o.within_class_factor = within_class_factor;
+    if (target_dim < 1 || target_dim > n) throw py::value_error("lda_compute: target_dim must be in 1 .. dim_z");
+    const py::ssize_t MW = n + (remove_offset ? 1 : 0);
+    Arr<float> M({(py::ssize_t)target_dim, MW});
+    Arr<double> M64({(py::ssize_t)target_dim, MW}), Mfull({n, n}), eig({n});
+    double count = 0.0;
+    int32_t status = 0;
+    Check(NoGil([&] { return khg_lda_compute(&o, (int32_t)C, (int32_t)n, zero.data(), first.data(), second.data(), M.mutable_data(), M64.mutable_data(),
+                                             Mfull.mutable_data(), eig.mutable_data(), &count, &status); }));
+    py::dict d;
+    d["M"] = M; d["M64"] = M64; d["M_full"] = Mfull; d["eig"] = eig; d["count"] = count; d["status"] = (int)status;
+    return d;
+  }, py::arg("zero_acc"), py::arg("first_acc"), py::arg("total_second_acc"), py::arg("target_dim") = 40, py::arg("remove_offset") = false,
+     py::arg("within_class_factor") = 1.0, "LdaEstimate::Estimate on host statistics (khg_lda_compute; DESIGN.md 7n)");
+  m.attr("LDA_OK") = KHG_LDA_OK; m.attr("LDA_SINGULAR") = KHG_LDA_SINGULAR; m.attr("LDA_MAX_SPLICED_DIM") = KHG_LDA_MAX_SPLICED_DIM;
   m.def("scaled_trans_cost", [](Arr<float> lp, Arr<float> nsl, Arr<int32_t> id2state, Arr<uint8_t> isl, float ts, float sls) {
     const int nt = (int)lp.shape(0) - 1;
     Arr<float> out({(py::ssize_t)nt + 1});

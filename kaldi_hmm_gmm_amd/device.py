@@ -28,6 +28,10 @@ UtteranceSet = _ext.UtteranceSet            # features + compiled graphs of a sh
 DecodingGraph = _ext.DecodingGraph          # khg_graph: ONE decoding graph resident in HBM, shared by sets (graph=) and batch calls
 DeviceFmllrStats = _ext.DeviceFmllrStats    # khg_fmllr_stats: FmllrDiagGmmAccs per speaker in HBM; download() -> numpy beta / K / G
 DeviceMlltStats = _ext.DeviceMlltStats      # khg_mllt_stats: MlltAccs in HBM; download() -> beta, numpy G
+DeviceLdaStats = _ext.DeviceLdaStats        # khg_lda_stats: LdaEstimate accumulators in HBM; download() -> zero_acc / first_acc / total_second_acc
+LDA_OK = _ext.LDA_OK
+LDA_SINGULAR = _ext.LDA_SINGULAR
+LDA_MAX_SPLICED_DIM = _ext.LDA_MAX_SPLICED_DIM
 
 
 class DeviceAccs(_ext.DeviceAccs):
