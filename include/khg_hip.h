@@ -1070,6 +1070,67 @@ int khg_lda_compute(const khg_lda_options *o, int32_t num_classes, int32_t dim_z
 int khg_utts_splice_transform_feats(khg_ctx *ctx, khg_utts *u, int32_t left, int32_t right, int32_t out_dim, int32_t has_offset,
                                     const float *M_h, float *out_d);
 
+/* ---- Decision-tree building (acc-tree-stats, build-tree) ------------------------------------------------------------ */
+/* The reference has no tree training: the rule in DESIGN.md 7o is the specification (tests/tree_ref.py restates it).  An event is
+ * (window[0 .. N), pdf-class): the phones of the N-wide context window with the central phone at position P, 0 where the window
+ * reaches outside the utterance.  Supported: N in 1 .. KHG_TREE_MAX_CONTEXT, 0 <= P < N, phones 1 .. KHG_TREE_MAX_PHONE, pdf-classes
+ * 0 .. KHG_TREE_MAX_PDF_CLASS, fewer than 2^31 - 1 frames in a set; anything else is KHG_E_ARG before any launch. */
+#define KHG_TREE_MAX_CONTEXT 3
+#define KHG_TREE_MAX_PHONE 65535
+#define KHG_TREE_MAX_PDF_CLASS 255
+#define KHG_TREE_TID_SELF_LOOP 1   /* tid_flags: the transition-id is a self-loop                                       */
+#define KHG_TREE_TID_FINAL 2       /* tid_flags: the transition-id enters the final state of its phone's topology       */
+#define KHG_TREE_STATUS_NO_ALI 1   /* status bits of an utterance khg_acc_tree_stats skipped: an id outside 1 .. num_tids (a failed khg_align leaves 0) */
+#define KHG_TREE_STATUS_MIXED_PHONES 2 /* ... two phones inside one segment                                              */
+#define KHG_TREE_STATUS_OPEN_END 4 /* ... the last segment does not end in a final transition-id followed by self-loops only */
+/* The statistics: the distinct events seen, ascending in (window[0], .., window[N - 1], pdf-class), each with count, x[dim] and
+ * x2[dim] in fp64, resident on the device.  zero empties the handle.  download: keys_h[num_keys][N + 1] int32 (the window, then the
+ * pdf-class), count_h[num_keys], x_h / x2_h[num_keys][dim]; NULL for what is not wanted; synchronises.  upload replaces the contents;
+ * the keys must ascend strictly (KHG_E_ARG).  add: dst = dst + (double)scale * src over the union of the keys -- a key of both gets
+ * a + scale b (one product, one add, not fused), a key of one side a or scale b; the handles must agree in dim, N, P and belong to
+ * `ctx`.  Synchronous. */
+typedef struct khg_tree_stats khg_tree_stats;
+int khg_tree_stats_create(khg_ctx *ctx, int32_t dim, int32_t N, int32_t P, khg_tree_stats **out);
+int khg_tree_stats_destroy(khg_tree_stats *s);
+int khg_tree_stats_zero(khg_ctx *ctx, khg_tree_stats *s);
+int khg_tree_stats_num_keys(khg_ctx *ctx, const khg_tree_stats *s, int64_t *num_keys);
+int khg_tree_stats_download(khg_ctx *ctx, const khg_tree_stats *s, int32_t *keys_h, double *count_h, double *x_h, double *x2_h);
+int khg_tree_stats_upload(khg_ctx *ctx, khg_tree_stats *s, int64_t num_keys, const int32_t *keys_h, const double *count_h, const double *x_h,
+                          const double *x2_h);
+int khg_tree_stats_add(khg_ctx *ctx, khg_tree_stats *dst, float scale, const khg_tree_stats *src);
+/* acc-tree-stats from the set's resident alignment (khg_align, khg_ali_upload) and feature rows; no model, no posteriors.
+ * tid2phone_h / tid2pdf_class_h / tid_flags_h: [num_tids + 1], index 0 unused.  ci_phones_h[n_ci]: context-independent phones.
+ * Segments: an utterance's ids are cut where a non-self-loop id follows a final one as its nearest preceding non-self-loop id (and at
+ * frame 0) -- Kaldi's SplitToPhones for reordered graphs.  Segment i of S has the phone of its ids; a frame of it has
+ * window[j] = phone of segment i - P + j (0 outside 0 .. S - 1; 0 for every j != P when the central phone is context-independent) and
+ * the pdf-class of its own id, and adds count += 1, x += row, x2 += row^2 with the float row widened to double (exact products).
+ * An utterance with KHG_TREE_STATUS_* set in status_h[n_utt] (may be NULL) adds nothing; the others add what they add without it, bit
+ * for bit.  The sum of a key with n entries, in sorted (utterance, frame) order: slices of 1024 consecutive entries; in a slice, with
+ * R = 256 / dim chains (1 for dim > 256), chain r adds entries r, r + R, .. in order, the chains are added in order 0 .. R - 1; the
+ * slices are added in slice order (for n <= R that is 0 + x_0 + .. + x_(n-1) in entry order).  No atomics: the bits depend on the key's own entry list only.  A call into a handle that holds
+ * keys merges as khg_tree_stats_add(handle, 1, the call's sums).  Reads back the key ranges for its work plan (synchronises). */
+int khg_acc_tree_stats(khg_ctx *ctx, khg_utts *u, int32_t num_tids, const int32_t *tid2phone_h, const int32_t *tid2pdf_class_h,
+                       const int32_t *tid_flags_h, int32_t n_ci, const int32_t *ci_phones_h, khg_tree_stats *stats, int32_t *status_h);
+/* Kaldi's BuildTree on host statistics laid out as khg_tree_stats_download gives them; needs no device.  Questions: for question key
+ * qkey_h[i] (-1 = the pdf-class, 0 .. N - 1 a window position; ascending, each once) the sets number qkey_off_h[i] ..
+ * qkey_off_h[i + 1]; set q holds q_vals_h[q_off_h[q] .. q_off_h[q + 1]).  Roots: phone set r holds set_phones_h[set_off_h[r] ..
+ * set_off_h[r + 1]) (sorted), with share_roots_h[r] and do_split_h[r]; phone2num_pdf_classes_h[num_phones].  GetStubMap, then
+ * best-first splitting (improvement Objf(yes) + Objf(no) - Objf(leaf) of the diagonal Gaussian with variance floor var_floor, in
+ * double; a question with an empty side is no candidate; first candidate wins ties; stops at improvement <= thresh or at max_leaves
+ * leaves, max_leaves <= 0: no limit), then merging of leaves under one stub leaf while the smallest loss is < cluster_thresh
+ * (cluster_thresh < 0: the smallest improvement split on; the merged leaf keeps the lower id) and renumbering.  The tree is written
+ * as Kaldi's binary ContextDependency stream: *tree_bytes is always set; the stream is copied when tree_h holds tree_cap >= that.
+ * Nothing is kept between calls: a call with tree_h == NULL (or too small a buffer) is a size query that costs a full build, so a
+ * caller that can bound the stream -- <= 48 + 4 (largest question) bytes a split, 8 a leaf, the stub's nodes -- passes that once.
+ * *objf_impr: the improvements split on, summed; *cluster_loss: the losses merged on, summed; *num_leaves; *num_removed merges.
+ * KHG_E_ARG for malformed arguments and for statistics whose central phone is in no phone set. */
+int khg_build_tree(int32_t N, int32_t P, int32_t dim, int64_t num_keys, const int32_t *keys_h, const double *count_h, const double *x_h,
+                   const double *x2_h, int32_t num_qkeys, const int32_t *qkey_h, const int64_t *qkey_off_h, const int64_t *q_off_h,
+                   const int32_t *q_vals_h, int32_t num_sets, const int64_t *set_off_h, const int32_t *set_phones_h,
+                   const int32_t *share_roots_h, const int32_t *do_split_h, int32_t num_phones, const int32_t *phone2num_pdf_classes_h,
+                   double thresh, int32_t max_leaves, double cluster_thresh, double var_floor, unsigned char *tree_h, int64_t tree_cap,
+                   int64_t *tree_bytes, double *objf_impr, double *cluster_loss, int32_t *num_leaves, int32_t *num_removed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,8 @@ from .align import get_raw_lattice_faster_batch, get_raw_lattice_faster_device_b
 from .context_dep import (ContextDependency, ContextDependencyInterface, monophone_context_dependency,  # noqa: F401
                           monophone_context_dependency_shared)
 from .device import (ALIGN_DONE, ALIGN_ERROR, ALIGN_EXACT_DP, ALIGN_FALLBACK, ALIGN_RETRIED, Comm, Context, DeviceAccs,  # noqa: F401
-                     DecodingGraph, DeviceFmllrStats, DeviceLdaStats, DeviceMlltStats, DeviceModel, DeviceTransitions, UtteranceSet)
+                     DecodingGraph, DeviceFmllrStats, DeviceLdaStats, DeviceMlltStats, DeviceModel, DeviceTransitions, DeviceTreeStats,
+                     UtteranceSet)
 from .diag_gmm import AmDiagGmm, DiagGmm  # noqa: F401
 from .fst import StdArc, StdVectorFst, modify_graph_for_careful_alignment  # noqa: F401
 from .hmm_topology import HmmState, HmmTopology  # noqa: F401
@@ -38,6 +39,9 @@ from .mllt import (MLLT_MAX_DIM, MLLT_OK, MLLT_SINGULAR, est_mllt, gmm_acc_mllt,
                    mllt_compute)
 from .lda import (LDA_MAX_SPLICED_DIM, LDA_OK, LDA_SINGULAR, acc_lda, acc_lda_batch, compose_with_lda, est_lda, lda_compute,  # noqa: F401
                   splice_feats, splice_transform_feats, splice_transform_feats_batch)
+from .tree import (TREE_MAX_CONTEXT, TREE_MAX_PDF_CLASS, TREE_MAX_PHONE, TREE_STATUS_MIXED_PHONES, TREE_STATUS_NO_ALI,  # noqa: F401
+                   TREE_STATUS_OPEN_END, acc_tree_stats, acc_tree_stats_batch, build_tree, convert_ali, gmm_init_model, leaf_stats,
+                   pdf_class_questions, split_to_phones, tid_tables)
 from .scripts import (gmm_acc_stats, gmm_acc_stats_ali, gmm_acc_stats_ali_batch, gmm_acc_stats_batch, gmm_align_compiled,  # noqa: F401
                       gmm_align_compiled_batch, gmm_boost_silence, gmm_est, gmm_est_gmm_ebw, gmm_est_weights_ebw, gmm_info, gmm_init_mono,
                       gmm_ismooth_stats, gmm_rescore_lattice, gmm_rescore_lattice_batch, gmm_sum_accs, lattice_boost_ali,

@@ -313,6 +313,17 @@ SIGNATURES = {
     "khg_lda_compute": (C.c_int, [C.POINTER(LdaOptionsC), C.c_int32, C.c_int32, c_f64p, c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p,
                                   c_i32p]),
     "khg_utts_splice_transform_feats": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, vp]),
+    "khg_tree_stats_create": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]),
+    "khg_tree_stats_destroy": (C.c_int, [vp]),
+    "khg_tree_stats_zero": (C.c_int, [vp, vp]),
+    "khg_tree_stats_num_keys": (C.c_int, [vp, vp, C.POINTER(C.c_int64)]),
+    "khg_tree_stats_download": (C.c_int, [vp, vp, c_i32p, c_f64p, c_f64p, c_f64p]),
+    "khg_tree_stats_upload": (C.c_int, [vp, vp, C.c_int64, c_i32p, c_f64p, c_f64p, c_f64p]),
+    "khg_tree_stats_add": (C.c_int, [vp, vp, C.c_float, vp]),
+    "khg_acc_tree_stats": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p, vp, c_i32p]),
+    "khg_build_tree": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, c_i32p, c_f64p, c_f64p, c_f64p, C.c_int32, c_i32p, c_i64p, c_i64p, c_i32p, C.c_int32,
+                                 c_i64p, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p, C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_ubyte), C.c_int64,
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), c_i32p, c_i32p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -510,6 +510,36 @@ struct KLdaStats {
   int num_chunks() { int32_t n = 0; Check(khg_lda_stats_num_chunks(h, &n)); return n; }
 };
 
+// decision-tree statistics resident in HBM (khg_tree_stats)
+struct KTreeStats {
+  khg_tree_stats* h = nullptr;
+  py::object ctx_obj;
+  KContext* ctx;
+  int dim = 0, N = 0, P = 0;
+  KTreeStats(py::object ctx_o, int d, int n, int p) : ctx_obj(ctx_o), ctx(ctx_o.cast<KContext*>()), dim(d), N(n), P(p) { Check(khg_tree_stats_create(ctx->h, d, n, p, &h)); }
+  ~KTreeStats() { close(); }
+  void close() { if (h) { khg_tree_stats_destroy(h); h = nullptr; } }
+  void zero() { Check(khg_tree_stats_zero(ctx->h, h)); }
+  int64_t num_keys() { int64_t n = 0; Check(khg_tree_stats_num_keys(ctx->h, h, &n)); return n; }
+  py::dict download() {
+    const py::ssize_t K = (py::ssize_t)num_keys(), K1 = K > 0 ? K : 1;
+    Arr<int32_t> keys({K1, (py::ssize_t)N + 1});
+    Arr<double> cnt({K1}), x({K1, (py::ssize_t)dim}), x2({K1, (py::ssize_t)dim});
+    Check(NoGil([&] { return khg_tree_stats_download(ctx->h, h, keys.mutable_data(), cnt.mutable_data(), x.mutable_data(), x2.mutable_data()); }));
+    py::dict d;
+    const py::slice sl(0, K, 1);
+    d["keys"] = py::array(keys)[sl]; d["count"] = py::array(cnt)[sl]; d["x"] = py::array(x)[sl]; d["x2"] = py::array(x2)[sl];
+    return d;
+  }
+  void upload(Arr<int32_t> keys, Arr<double> cnt, Arr<double> x, Arr<double> x2) {
+    const py::ssize_t K = cnt.size();
+    if (keys.size() != K * (N + 1) || x.size() != K * dim || x2.size() != K * dim)
+      throw py::value_error("DeviceTreeStats.upload: keys [num_keys, N + 1], count [num_keys], x and x2 [num_keys, dim]");
+    Check(NoGil([&] { return khg_tree_stats_upload(ctx->h, h, (int64_t)K, keys.data(), cnt.data(), x.data(), x2.data()); }));
+  }
+  void add(float scale, KTreeStats& src) { Check(NoGil([&] { return khg_tree_stats_add(ctx->h, h, scale, src.h); })); }
+};
+
 struct KUtts {
   khg_utts* h = nullptr;
   py::object ctx_obj, keep, keep_model;
@@ -869,6 +899,15 @@ struct KUtts {
     if (!post.h) throw py::value_error("acc_lda_stats_post: the DevicePosteriors are closed");
     Check(NoGil([&] { return khg_acc_lda_stats_post(ctx->h, tm.h, h, post.h, scale, stats.h); }));
   }
+  // acc-tree-stats (khg_acc_tree_stats): from the resident alignment; the tables are [num_tids + 1], index 0 unused -> status [n_utt]
+  py::object acc_tree_stats(Arr<int32_t> tid2phone, Arr<int32_t> tid2pdf_class, Arr<int32_t> tid_flags, Arr<int32_t> ci_phones, KTreeStats& stats) {
+    if (tid2phone.size() < 2 || tid2pdf_class.size() != tid2phone.size() || tid_flags.size() != tid2phone.size())
+      throw py::value_error("acc_tree_stats: tid2phone, tid2pdf_class and tid_flags must be [num_tids + 1]");
+    Arr<int32_t> status({(py::ssize_t)(n_utt > 0 ? n_utt : 1)});
+    Check(NoGil([&] { return khg_acc_tree_stats(ctx->h, h, (int32_t)tid2phone.size() - 1, tid2phone.data(), tid2pdf_class.data(), tid_flags.data(), (int32_t)ci_phones.size(),
+                                                ci_phones.data(), stats.h, status.mutable_data()); }));
+    return py::array(status)[py::slice(0, n_utt, 1)];
+  }
   // splice-feats | transform-feats (khg_utts_splice_transform_feats): M [out_dim, dim_z (+ 1)] from the host, or None for the spliced
   // rows themselves; out: a device pointer for [rows, out_dim] floats
   void splice_transform_feats(int left, int right, py::object M, uintptr_t out) {
@@ -1021,6 +1060,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
            py::arg("scale") = 1.0f)
       .def("acc_mllt_stats_post", &KUtts::acc_mllt_stats_post, py::arg("model"), py::arg("tm"), py::arg("post"), py::arg("stats"), py::arg("scale") = 1.0f)
       .def("acc_lda_stats_post", &KUtts::acc_lda_stats_post, py::arg("tm"), py::arg("post"), py::arg("stats"), py::arg("scale") = 1.0f)
+      .def("_acc_tree_stats", &KUtts::acc_tree_stats, py::arg("tid2phone"), py::arg("tid2pdf_class"), py::arg("tid_flags"), py::arg("ci_phones"), py::arg("stats"))
       .def("splice_transform_feats", &KUtts::splice_transform_feats, py::arg("left"), py::arg("right"), py::arg("M"), py::arg("out"))
       .def("transform_feats", &KUtts::transform_feats, py::arg("utt2spk"), py::arg("W"), py::arg("out") = py::none(), py::arg("n_spk") = 0)
       .def("close", &KUtts::close);
@@ -1056,6 +1096,15 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("add", &KLdaStats::add, py::arg("scale"), py::arg("src"))
       .def("set_chunk_frames", &KLdaStats::set_chunk_frames, py::arg("frames")).def("num_chunks", &KLdaStats::num_chunks)
       .def("close", &KLdaStats::close);
+
+  py::class_<KTreeStats>(m, "DeviceTreeStats", py::dynamic_attr())
+      .def(py::init<py::object, int, int, int>(), py::arg("ctx"), py::arg("dim"), py::arg("N") = 3, py::arg("P") = 1)
+      .def_property_readonly("h", [](KTreeStats& x) { return reinterpret_cast<uintptr_t>(x.h); })
+      .def_readonly("ctx", &KTreeStats::ctx_obj).def_readonly("dim", &KTreeStats::dim).def_readonly("N", &KTreeStats::N).def_readonly("P", &KTreeStats::P)
+      .def("zero", &KTreeStats::zero).def("num_keys", &KTreeStats::num_keys).def("download", &KTreeStats::download)
+      .def("upload", &KTreeStats::upload, py::arg("keys"), py::arg("count"), py::arg("x"), py::arg("x2"))
+      .def("add", &KTreeStats::add, py::arg("scale"), py::arg("src"))
+      .def("close", &KTreeStats::close);
 
   // ---- host-side functions (no GPU): gconsts, M-step, merge, transition update, AddTransitionProbs costs ----
   m.def("compute_gconsts", [](Arr<int32_t> go, Arr<float> w, Arr<float> iv, Arr<float> miv) {
@@ -1136,6 +1185,48 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
   }, py::arg("zero_acc"), py::arg("first_acc"), py::arg("total_second_acc"), py::arg("target_dim") = 40, py::arg("remove_offset") = false,
      py::arg("within_class_factor") = 1.0, "LdaEstimate::Estimate on host statistics (khg_lda_compute; DESIGN.md 7n)");
   m.attr("LDA_OK") = KHG_LDA_OK; m.attr("LDA_SINGULAR") = KHG_LDA_SINGULAR; m.attr("LDA_MAX_SPLICED_DIM") = KHG_LDA_MAX_SPLICED_DIM;
+  m.def("build_tree", [](int N, int P, Arr<int32_t> keys, Arr<double> cnt, Arr<double> x, Arr<double> x2, Arr<int32_t> qkeys, Arr<int64_t> qkey_off, Arr<int64_t> q_off,
+                         Arr<int32_t> q_vals, Arr<int64_t> set_off, Arr<int32_t> set_phones, Arr<int32_t> share_roots, Arr<int32_t> do_split, Arr<int32_t> p2n, double thresh,
+                         int max_leaves, double cluster_thresh, double var_floor) {
+    const py::ssize_t K = cnt.size(), nq = qkeys.size(), ns = share_roots.size();
+    if (x.ndim() != 2 || x2.ndim() != 2 || x.shape(0) != K || x2.shape(0) != K || x.shape(1) != x2.shape(1) || x.shape(1) < 1 || keys.size() != K * ((py::ssize_t)N + 1))
+      throw py::value_error("build_tree: keys [num_keys, N + 1], count [num_keys], x and x2 [num_keys, dim]");
+    if (qkey_off.size() != nq + 1 || q_off.size() < 1 || (nq > 0 && q_off.size() != qkey_off.at(nq) + 1) || (q_vals.size() != q_off.at(q_off.size() - 1)))
+      throw py::value_error("build_tree: the question offset lists do not fit together");
+    if (ns < 1 || do_split.size() != ns || set_off.size() != ns + 1 || set_phones.size() != set_off.at(ns))
+      throw py::value_error("build_tree: one share_roots / do_split entry per phone set, set_off [num_sets + 1]");
+    // One build: the first buffer holds any stream these arguments can give -- the header, per phone set its stub nodes (a table over
+    // the pdf-classes, a split on the central phone with a yes-set of at most every phone), the table over the phones, and per split an
+    // SE node with the largest question as its yes-set and one new leaf -- unless that bound is above 64 MiB; only then can a second
+    // build be needed (khg_build_tree's size query costs a full build).
+    int64_t max_pc = 1, max_q = 0, highest = 0;
+    for (py::ssize_t i = 0; i < p2n.size(); ++i) max_pc = std::max<int64_t>(max_pc, p2n.at(i));
+    for (py::ssize_t i = 0; i + 1 < q_off.size(); ++i) max_q = std::max<int64_t>(max_q, q_off.at(i + 1) - q_off.at(i));
+    for (py::ssize_t i = 0; i < set_phones.size(); ++i) highest = std::max<int64_t>(highest, set_phones.at(i));
+    const int64_t splits = max_leaves > 0 ? (int64_t)max_leaves : std::max<int64_t>((int64_t)K, 1);
+    const bool multi = set_phones.size() > ns;     // a set of several phones: the stub splits the sets in halves, and a half of single phones is a table of its own
+    const int64_t bound = 128 + (int64_t)ns * (64 + 8 * max_pc + (multi ? 4 * (int64_t)set_phones.size() + 5 * (highest + 2) : 0)) + 5 * (highest + 2) +
+                          splits * (48 + 4 * max_q);
+    std::string buf((size_t)std::min<int64_t>(std::max<int64_t>(bound, 1 << 16), (int64_t)64 << 20), '\0');
+    int64_t nbytes = 0;
+    double impr = 0.0, loss = 0.0;
+    int32_t nl = 0, nr = 0;
+    auto run = [&] {
+      return khg_build_tree(N, P, (int32_t)x.shape(1), (int64_t)K, keys.data(), cnt.data(), x.data(), x2.data(), (int32_t)nq, qkeys.data(), qkey_off.data(), q_off.data(),
+                            q_vals.data(), (int32_t)ns, set_off.data(), set_phones.data(), share_roots.data(), do_split.data(), (int32_t)p2n.size(), p2n.data(), thresh,
+                            max_leaves, cluster_thresh, var_floor, reinterpret_cast<unsigned char*>(&buf[0]), (int64_t)buf.size(), &nbytes, &impr, &loss, &nl, &nr);
+    };
+    Check(NoGil(run));
+    if (nbytes > (int64_t)buf.size()) { buf.assign((size_t)nbytes, '\0'); Check(NoGil(run)); }
+    py::dict d;
+    d["tree"] = py::bytes(buf.data(), (size_t)nbytes); d["objf_impr"] = impr; d["cluster_loss"] = loss; d["num_leaves"] = (int)nl; d["num_removed"] = (int)nr;
+    return d;
+  }, py::arg("N"), py::arg("P"), py::arg("keys"), py::arg("count"), py::arg("x"), py::arg("x2"), py::arg("qkeys"), py::arg("qkey_off"), py::arg("q_off"), py::arg("q_vals"),
+     py::arg("set_off"), py::arg("set_phones"), py::arg("share_roots"), py::arg("do_split"), py::arg("phone2num_pdf_classes"), py::arg("thresh"), py::arg("max_leaves"),
+     py::arg("cluster_thresh"), py::arg("var_floor") = 0.01, "BuildTree on host statistics (khg_build_tree; DESIGN.md 7o) -> the binary ContextDependency stream and its figures");
+  m.attr("TREE_MAX_CONTEXT") = KHG_TREE_MAX_CONTEXT; m.attr("TREE_MAX_PHONE") = KHG_TREE_MAX_PHONE; m.attr("TREE_MAX_PDF_CLASS") = KHG_TREE_MAX_PDF_CLASS;
+  m.attr("TREE_TID_SELF_LOOP") = KHG_TREE_TID_SELF_LOOP; m.attr("TREE_TID_FINAL") = KHG_TREE_TID_FINAL;
+  m.attr("TREE_STATUS_NO_ALI") = KHG_TREE_STATUS_NO_ALI; m.attr("TREE_STATUS_MIXED_PHONES") = KHG_TREE_STATUS_MIXED_PHONES; m.attr("TREE_STATUS_OPEN_END") = KHG_TREE_STATUS_OPEN_END;
   m.def("scaled_trans_cost", [](Arr<float> lp, Arr<float> nsl, Arr<int32_t> id2state, Arr<uint8_t> isl, float ts, float sls) {
     const int nt = (int)lp.shape(0) - 1;
     Arr<float> out({(py::ssize_t)nt + 1});

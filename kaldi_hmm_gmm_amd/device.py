@@ -29,6 +29,7 @@ DecodingGraph = _ext.DecodingGraph          # khg_graph: ONE decoding graph resi
 DeviceFmllrStats = _ext.DeviceFmllrStats    # khg_fmllr_stats: FmllrDiagGmmAccs per speaker in HBM; download() -> numpy beta / K / G
 DeviceMlltStats = _ext.DeviceMlltStats      # khg_mllt_stats: MlltAccs in HBM; download() -> beta, numpy G
 DeviceLdaStats = _ext.DeviceLdaStats        # khg_lda_stats: LdaEstimate accumulators in HBM; download() -> zero_acc / first_acc / total_second_acc
+DeviceTreeStats = _ext.DeviceTreeStats      # khg_tree_stats: (window, pdf-class) event statistics in HBM; download() -> keys / count / x / x2
 LDA_OK = _ext.LDA_OK
 LDA_SINGULAR = _ext.LDA_SINGULAR
 LDA_MAX_SPLICED_DIM = _ext.LDA_MAX_SPLICED_DIM

@@ -1,6 +1,6 @@
 """Training-graph builder and equal-align for linear transcripts.
 
-Replaces, for monophone trees and word-level transcripts, what the reference gets from kaldifst:
+Replaces, for trees of context width 1 to 3 and word-level transcripts, what the reference gets from kaldifst:
 
   * ``generate_hmm_topo``                     scripts/prepare_lang.py:514-600
   * ``Lexicon`` + optional silence            scripts/prepare_lang.py:329-456 (make_lexicon_fst_with_silence)
@@ -85,8 +85,10 @@ class TrainingGraphCompiler:
 
     def __init__(self, trans_model, ctx_dep, lex_fst, disambig_syms: Optional[Sequence[int]] = None,
                  opts: Optional[TrainingGraphCompilerOptions] = None, *, sil_phone: Optional[int] = None, sil_prob: float = 0.5):
-        if ctx_dep.context_width != 1 or ctx_dep.central_position != 0:
-            raise KhgError("TrainingGraphCompiler: only monophone context (N=1, P=0) is supported")
+        if not (1 <= ctx_dep.context_width <= 3 and 0 <= ctx_dep.central_position < ctx_dep.context_width):
+            raise KhgError("TrainingGraphCompiler: supported are context widths N in 1 .. 3 with 0 <= P < N, got N=%d, P=%d"
+                           % (ctx_dep.context_width, ctx_dep.central_position))
+        self.N, self.P = ctx_dep.context_width, ctx_dep.central_position
         self.tm = trans_model
         self.ctx_dep = ctx_dep
         if isinstance(lex_fst, dict):
@@ -104,17 +106,21 @@ class TrainingGraphCompiler:
         self._hmm_cache = {}
 
     # ---- one phone as an FSA without self-loops (csrc/hmm-utils.cc:40-158) ----
-    def _phone_hmm(self, phone: int):
-        """-> (num_hmm_states, [(src_hmm_state, dst_hmm_state, tid, cost)]) ; last state is final."""
-        if phone in self._hmm_cache:
-            return self._hmm_cache[phone]
+    def _phone_hmm(self, phone: int, window: Optional[Tuple[int, ...]] = None):
+        """-> (num_hmm_states, [(src_hmm_state, dst_hmm_state, tid, cost)]) ; last state is final.  `window`: the phone's context
+        window (None: the monophone window), cached by (window, phone)."""
+        window = (phone,) if window is None else tuple(window)
+        key = (window, phone)
+        if key in self._hmm_cache:
+            return self._hmm_cache[key]
         topo = self.tm.topo
         entry = topo.topology_for_phone(phone)
         pdfs = []
         for pc in range(topo.num_pdf_classes(phone)):
-            ok, pdf = self.ctx_dep.compute([phone], pc)
+            ok, pdf = self.ctx_dep.compute(list(window), pc)
             if not ok:
-                raise KhgError(f"GetHmmAsFsa: context-dependency object could not produce an answer: pdf-class = {pc} ctx-window = {phone}")
+                raise KhgError("GetHmmAsFsa: context-dependency object could not produce an answer: pdf-class = %d ctx-window = %s"
+                               % (pc, " ".join(str(x) for x in window)))
             pdfs.append(pdf)
         arcs = []
         for h, st in enumerate(entry):
@@ -131,8 +137,82 @@ class TrainingGraphCompiler:
                 logp = self.tm.get_transition_log_prob_ignoring_self_loops(tid)
                 # ApplyProbabilityScale(transition_scale) on the float32 arc weight
                 arcs.append((h, dst, tid, float(np.float32(np.float32(-logp) * np.float32(self.opts.transition_scale)))))
-        self._hmm_cache[phone] = (len(entry), arcs)
-        return self._hmm_cache[phone]
+        self._hmm_cache[key] = (len(entry), arcs)
+        return self._hmm_cache[key]
+
+    # ---- the context expansion of a phone-level graph (the C of H o C o L o G) ----
+    def _context_expand(self, nodes: int, parcs, finals: Dict[int, float], start: int):
+        """(nodes, arcs[(src, dst, phone, olabel, cost)], finals, start) -> the same with one copy of every phone arc per distinct
+        (left phones, right phones) it can be traversed with; every arc gains a sixth field, its window.  A node of the result is
+        (node, the last P phones, the next N - 1 - P phones); 0 stands for "before the start" and "after a final node".  Node 0 is
+        a fresh start that has not yet chosen its future.  Arcs into nodes that reach no final node are dropped."""
+        L, R = self.P, self.N - 1 - self.P
+        out: Dict[int, list] = {}
+        for a in parcs:
+            out.setdefault(a[0], []).append(a)
+        memo: Dict[Tuple[int, int], list] = {}
+
+        def futures(v, k):
+            """the phone sequences of length k that can be taken from node v, 0-padded after a final node (sorted)"""
+            if k == 0:
+                return [()]
+            if (v, k) not in memo:
+                res = set()
+                if v in finals:
+                    res.add((0,) * k)
+                for a in out.get(v, []):
+                    for t in futures(a[1], k - 1):
+                        res.add((a[2],) + t)
+                memo[(v, k)] = sorted(res)
+            return memo[(v, k)]
+
+        index, order = {}, []
+
+        def get(v, hist, fut):
+            key = (v, hist, fut)
+            if key not in index:
+                index[key] = len(order) + 1
+                order.append(key)
+            return index[key]
+
+        arcs, new_finals = [], {}
+
+        def emit(src_id, v, hist, fut):
+            for a in out.get(v, []):
+                ph = a[2]
+                if R and ph != fut[0]:
+                    continue
+                h2 = (hist + (ph,))[-L:] if L else ()
+                for f2 in futures(a[1], R):
+                    if R and f2[:-1] != fut[1:]:
+                        continue
+                    arcs.append((src_id, get(a[1], h2, f2), ph, a[3], a[4], hist + (ph,) + f2))
+
+        hist0 = (0,) * L
+        if start in finals:
+            new_finals[0] = finals[start]
+        for fut in futures(start, R):
+            emit(0, start, hist0, fut)
+        i = 0
+        while i < len(order):
+            v, hist, fut = order[i]
+            i += 1
+            if v in finals and not any(fut):
+                new_finals[i] = finals[v]
+            if R and fut[0] == 0:
+                continue
+            emit(i, v, hist, fut)
+        # co-accessible nodes only
+        into: Dict[int, list] = {}
+        for a in arcs:
+            into.setdefault(a[1], []).append(a[0])
+        live, stack = set(new_finals), list(new_finals)
+        while stack:
+            for s in into.get(stack.pop(), []):
+                if s not in live:
+                    live.add(s)
+                    stack.append(s)
+        return len(order) + 1, [a for a in arcs if a[1] in live], new_finals, 0
 
     # ---- phone-level graph of L o G for a linear transcript (eps-free) ----
     def _phone_graph(self, transcript: Sequence[int]):
@@ -348,6 +428,8 @@ class TrainingGraphCompiler:
     def _expand(self, nodes: int, parcs, finals: Dict[int, float], start: int) -> StdVectorFst:
         """Phone-level graph -> transition-id graph: GetHmmAsFsa per phone arc, then
         MakePrecedingInputSymbolsSameClass + AddSelfLoopsReorder (csrc/hmm-utils.cc:293-369)."""
+        if self.N > 1:
+            nodes, parcs, finals, start = self._context_expand(nodes, parcs, finals, start)
         # --- expand phones into transition-id arcs (no self-loops yet) ---
         out = [[] for _ in range(nodes)]      # per state: (dst, tid, olabel, cost)
 
@@ -355,8 +437,9 @@ class TrainingGraphCompiler:
             out.append([])
             return len(out) - 1
 
-        for (src, dst, ph, ol, cost) in parcs:
-            nst, harcs = self._phone_hmm(ph)
+        for parc in parcs:
+            src, dst, ph, ol, cost = parc[:5]
+            nst, harcs = self._phone_hmm(ph, parc[5] if len(parc) > 5 else None)
             ids = {0: src, nst - 1: dst}
             for (h, d, tid, c) in harcs:
                 for x in (h, d):
