@@ -124,7 +124,10 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
                                     0 (DEFAULT) as many as the chip holds at once, by the occupancy query                  [KHG_K1_PGRID] */
 #define KHG_OPT_K1_PROF 21       /* 1: boundary stamps of every K1 chunk (entry, barrier, first / last wave out of work), summed per CU,
                                     to stderr; the call waits for the kernel                                              [KHG_K1_PROF] */
-#define KHG_OPT_COUNT 22
+#define KHG_OPT_K2_LADDER 22     /* K2's exact DP on batches of chain-ordered graphs (every in-arc of state s from s or s - 1, <= 256 states): 0 (DEFAULT)
+                                    the ladder form -- costs move between lanes in registers, one workgroup barrier per eight layers --, 1 the
+                                    general body; same results bit for bit                                            [KHG_K2_LADDER=on|off] */
+#define KHG_OPT_COUNT 23
 /* Read-only figures (khg_ctx_get_option only): the per-call scratch block behind small utterance sets (DESIGN.md "per-utterance calls"). */
 #define KHG_INFO_SCRATCH_BYTES 100   /* bytes of the block in use (its top), 0 before the first small set */
 #define KHG_INFO_SCRATCH_BLOCKS 101  /* live allocations inside it */
@@ -216,6 +219,8 @@ int khg_utts_pdfs(const khg_utts *u, int32_t *pdfs_h /* [pdf_off[n_utt]] */);
  * dynamic LDS bytes, order-faithful decoder for what the DP cannot certify: 0 one-lane LDS, 1 one-lane HBM, 2 wave LDS, 3 wave HBM,
  * 4 chain }.  The generic form is KS = DEG = 1, FAST = 0. */
 int khg_utts_k2_plan(khg_ctx *ctx, const khg_utts *u, int32_t out[8]);
+/* ... and whether it would run the ladder form of that kernel (KHG_OPT_K2_LADDER): *out = 1, else 0. */
+int khg_utts_k2_ladder(khg_ctx *ctx, const khg_utts *u, int32_t *out);
 /* per listed pdf: the first frame a decoder token can read it at (fewest emitting arcs from the start state
  * to an arc carrying it; INT32_MAX if never; 0 for sets without graphs) -- what khg_loglikes_reachable uses */
 int khg_utts_pdf_first(const khg_utts *u, int32_t *first_h /* [pdf_off[n_utt]] */);

@@ -222,7 +222,7 @@ struct khg_graph {
   int32_t refs = 1;
   int64_t S = 0, A = 0, nwords = 0, device_bytes = 0;
   int32_t start = -1, max_indeg = 0, max_outdeg = 0;
-  bool same_col = true, has_eps = false;
+  bool same_col = true, has_eps = false, ladder = true;
   std::vector<int32_t> pdfs, pdf_first, pdf_dfin;   // sorted pdf list; per pdf: first frame it can be read at, fewest emitting arcs left after an arc carrying it (INT32_MAX: never)
   int64_t *state_off_d = nullptr, *in_off_d = nullptr, *out_off_d = nullptr;    // state_off_d = {0, S}
   int32_t *start_d = nullptr, *in_src_d = nullptr, *in_col_d = nullptr, *in_tid_d = nullptr, *in_olabel_d = nullptr, *out_inidx_d = nullptr;
@@ -243,6 +243,7 @@ struct khg_utts {
   std::vector<int32_t> pdfs;
   int32_t max_states = 0, max_inarcs = 0, max_indeg = 0, max_outdeg = 0;
   bool same_col = true;          // every state's in-arcs read one score row (reorder = true training graphs)
+  bool ladder = true;            // every graph's states are in chain order: in-arcs of state s from s or s - 1 only, one of either, no epsilon
   int32_t pdfs_checked_P = -1;   // model size the pdf lists were last validated against
   bool has_eps = false;
   // device

@@ -38,6 +38,7 @@ static int ensure_ali(khg_ctx* ctx, khg_utts* u) {
 struct K2Plan {
   int KS = 1, DEG = 1;                       // k2_viterbi_dp<KS, DEG, FAST, GMEM, SC>
   bool FAST = false, GMEM = false, SC = false;
+  bool LAD = false;                          // the ladder form of <1, 2, true, false, *> (an inner choice: same tables, same LDS, same block)
   int nthr = 64;
   size_t lds_dp = 0;                         // the DP's tables: dynamic LDS, or (GMEM) its slice of the HBM scratch
   size_t max_npdf = 0;
@@ -130,6 +131,9 @@ static K2Plan k2_plan(const khg_ctx* ctx, const khg_utts* u) {
   else if (KSsel == 4 && deg2m) form(4, 2, false);
   else if (KSsel == 4) form(4, 3, false);
   // else: the generic LDS form <1, 1, false>
+  // The ladder form of the two-slot, one-state-per-thread kernels: every graph of the batch in chain order (khg_utts::ladder) and at
+  // most four waves.  KHG_K2_LADDER = off: the general body (A/B, tests).
+  p.LAD = p.FAST && p.KS == 1 && p.DEG == 2 && u->ladder && nthr <= 256 && ctx->opt[KHG_OPT_K2_LADDER] == 0;
   return p;
 }
 
@@ -140,6 +144,15 @@ extern "C" int khg_utts_k2_plan(khg_ctx* ctx, const khg_utts* u, int32_t out[8])
   const K2Plan p = k2_plan(ctx, u);
   out[0] = p.KS; out[1] = p.DEG; out[2] = p.FAST ? 1 : 0; out[3] = p.GMEM ? 1 : 0; out[4] = p.SC ? 1 : 0;
   out[5] = p.nthr; out[6] = p.GMEM ? 0 : (int32_t)p.lds_dp; out[7] = p.faithful;
+  return KHG_OK;
+}
+
+// Beside the plan: whether khg_align would run the ladder form of the kernel the plan names (1) or its general body (0).
+extern "C" int khg_utts_k2_ladder(khg_ctx* ctx, const khg_utts* u, int32_t* out) {
+  if (ctx_dead(ctx) || !u || !out) return khg_set_error(KHG_E_ARG, "khg_utts_k2_ladder: bad arguments");
+  { int rf = utts_foreign_ctx(ctx, u, "khg_utts_k2_ladder"); if (rf) return rf; }
+  if (!u->has_graphs) return khg_set_error(KHG_E_ARG, "khg_utts_k2_ladder: the utterance set has no decoding graphs");
+  *out = k2_plan(ctx, u).LAD ? 1 : 0;
   return KHG_OK;
 }
 
@@ -244,9 +257,11 @@ extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_
     KernelTimer kt(ctx, "k2_viterbi_dp");
     KHG_LAUNCH(ctx, (k2_viterbi_dp<1, 1, false, true>), dim3(u->n_utt), dim3(nthr), 0, ctx->stream, a);
   } else {
-    const int form = plan.FAST ? 100 * plan.KS + 10 * plan.DEG + (plan.SC ? 1 : 0) : 0;     // <KS, DEG, true, false, SC>; 0: the generic form
+    const int form = plan.FAST ? 100 * plan.KS + 10 * plan.DEG + (plan.SC ? 1 : 0) + (plan.LAD ? 1000 : 0) : 0;     // <KS, DEG, true, false, SC>, + 1000: its ladder form; 0: the generic form
 #define K2_DP_CASES(X)                                                                                         \
-    if (form == 160) X((k2_viterbi_dp<1, 6, true>));                                                           \
+    if (form == 1121) X((k2_viterbi_dp<1, 2, true, false, true, true>));                                       \
+    else if (form == 1120) X((k2_viterbi_dp<1, 2, true, false, false, true>));                                 \
+    else if (form == 160) X((k2_viterbi_dp<1, 6, true>));                                                      \
     else if (form == 121) X((k2_viterbi_dp<1, 2, true, false, true>));                                         \
     else if (form == 120) X((k2_viterbi_dp<1, 2, true>));                                                      \
     else if (form == 131) X((k2_viterbi_dp<1, 3, true, false, true>));                                         \

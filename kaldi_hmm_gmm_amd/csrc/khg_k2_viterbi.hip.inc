@@ -212,6 +212,13 @@ __device__ __forceinline__ double k2_wave_min(double v) {
   for (int o = 32; o > 0; o >>= 1) { double t = __shfl_xor(v, o); v = t < v ? t : v; }
   return v;
 }
+// a double moved across lanes by DPP (two 32-bit moves); a lane whose source lane does not exist keeps `old`
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ double k2_dpp_d(double old, double v) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, ROWMASK, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, ROWMASK, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
 __device__ __forceinline__ int k2_wave_sum(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -233,8 +240,19 @@ __device__ __forceinline__ void k2_decode_nibble(int nib, int& ord, int& tie) {
 // SC: every state's in-arcs read the SAME score row (what AddSelfLoops with reorder = true leaves: the forward arc into a state and
 // the state's self-loop carry transition-ids of one pdf) -- one score block and one cost conversion per state instead of one per slot.
 // (one state per thread: K2_WAVES_PER_EU waves per SIMD; more: blocks of up to 1024 threads, four waves per SIMD = 128 registers)
-template <int KS, int DEG, bool FAST, bool GMEM = false, bool SC = false>
+//
+// LAD, the ladder form of <1, 2, true, false, *> (chosen on the host, k2_plan: every graph of the batch has its states in chain
+// order -- the in-arcs of state s come from s itself and from s - 1, at most one of either -- and at most 256 states): a layer needs no
+// exchange through LDS.  The self-loop's source cost is the lane's own register, the forward arc's is the neighbouring lane's, one
+// wave shift (DPP) away; only lane 0 of wave w > 0 needs a value of another wave, lane 63 of wave w - 1.  The waves therefore run one
+// group of eight layers apart: wave w - 1 leaves its lane-63 cost of every layer of a group in an 8-entry LDS strip (two strips, by
+// group parity), ONE workgroup barrier per group publishes it, and wave w reads the strip a group later -- off the dependent chain,
+// as the `old` operand of the shift, which lane 0 keeps.  T / 8 + nwave barriers per utterance instead of T, and no LDS write,
+// barrier and gather between a layer's minimum and the next layer's adds.  Same candidates, same association, same tie rule: the two
+// in-arc slots are only re-slotted (self, previous) in registers, each keeping the nibble bit of its own slot.
+template <int KS, int DEG, bool FAST, bool GMEM = false, bool SC = false, bool LAD = false>
 __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) void k2_viterbi_dp(K2Args a) {
+  static_assert(!LAD || (FAST && KS == 1 && DEG == 2 && !GMEM), "the ladder form is a variant of <1, 2, true, false, *>");
   extern __shared__ __attribute__((aligned(16))) unsigned char k2_lds[];
   unsigned char* const smem = GMEM ? a.gscratch + (size_t)blockIdx.x * a.gscratch_stride : k2_lds;
   constexpr int NS = FAST ? KS : 1;
@@ -300,6 +318,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
     if (col < 0) s_flags[1] = 1;
   }
   for (int s = tid; s < S; s += nthr) cur[s] = (s == start) ? 0.0 : INFINITY;
+  if (LAD && tid < 8) s_red[tid] = INFINITY;          // wave 0's boundary strip: no state before state 0 (s_red is free until the loop ends)
   k2_block_sync();
   const bool has_eps = !FAST && s_flags[1] != 0;
   const float* llu = a.ll + a.ll_off[u];
@@ -329,6 +348,16 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
     }
   } else {
     for (int s = tid; s < S; s += nthr) bp[s] = K2_BP_NONE;
+  }
+  // LAD: slot 0 becomes the self-loop, slot 1 the arc from state tid - 1 (an empty slot stays weight +inf, column 0); lad_bit[] is
+  // the nibble bit each stands for, 1 << its own in-arc slot: the in-arc order and the tie rule are those of the general form
+  int lad_bit[2] = {1, 2};
+  if constexpr (LAD) {
+    if (e_src[0] != tid) {             // slot 0 is the arc from tid - 1 (or both slots are empty)
+      const double tw = e_w[0]; e_w[0] = e_w[1]; e_w[1] = tw;
+      if (!SC) { const int tc = e_col[0]; e_col[0] = e_col[1]; e_col[1] = tc; }   // SC: one score row per state, slot 0 names it
+      lad_bit[0] = 2; lad_bit[1] = 1;
+    }
   }
   if (a.prof && tid == 0) a.prof[u * 8 + 1] = clock64();
   int tie = 0;
@@ -371,6 +400,33 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
     }
   }
 
+  // FAST: the score requests of one layer step (SUB8 = layer & 7), shared by the general layer step and the ladder's
+  auto score_fetch = [&](const int layer, auto subc) {
+    constexpr int SUB8 = decltype(subc)::value;
+    constexpr int SUB = SUB8 & 3;
+    if constexpr (SC3) {
+      if constexpr (SUB8 == 0) {
+#pragma unroll
+        for (int i = 0; i < NSC; ++i) sc_b[i] = sc_c[i];
+      }
+      if constexpr (SUB8 == 4) {
+#pragma unroll
+        for (int i = 0; i < NSC; ++i)
+          if (have_ll && layer + 4 < tpad) {   // rows are padded to tpad (multiple of 32): the whole next group of eight frames is in bounds
+            const float* src = llu + (int64_t)e_col[SC ? i * DEG : i] * tpad + layer + 4;
+            sc_a[i] = *reinterpret_cast<const f32x4*>(src);
+            sc_c[i] = *reinterpret_cast<const f32x4*>(src + 4);
+          }
+      }
+    } else if (SUB == 0) {               // entering a block: request the NEXT block into the other buffer
+#pragma unroll
+      for (int i = 0; i < NSC; ++i)
+        if (have_ll && layer + 4 < tpad) {   // rows are padded to tpad (multiple of 32)
+          const f32x4 v = *reinterpret_cast<const f32x4*>(llu + (int64_t)e_col[SC ? i * DEG : i] * tpad + layer + 4);
+          if constexpr ((SUB8 & 4) != 0) sc_a[i] = v; else sc_b[i] = v;
+        }
+    }
+  };
   // One layer.  FAST instantiates it eight times (two 16-byte score blocks; SUB8 = layer & 7 is a compile-time
   // constant there: no dynamic vector indexing, no register shuffles, buffer parity and score block known statically).
   auto layer_step = [&](const int layer, auto subc) -> bool {
@@ -472,28 +528,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
     if (layer == T) return false;
     if (FAST) {
       // ---- emitting arcs: layer -> layer+1, one state per thread, everything in registers ----
-      if constexpr (SC3) {
-        if constexpr (SUB8 == 0) {
-#pragma unroll
-          for (int i = 0; i < NSC; ++i) sc_b[i] = sc_c[i];
-        }
-        if constexpr (SUB8 == 4) {
-#pragma unroll
-          for (int i = 0; i < NSC; ++i)
-            if (have_ll && layer + 4 < tpad) {   // rows are padded to tpad (multiple of 32): the whole next group of eight frames is in bounds
-              const float* src = llu + (int64_t)e_col[SC ? i * DEG : i] * tpad + layer + 4;
-              sc_a[i] = *reinterpret_cast<const f32x4*>(src);
-              sc_c[i] = *reinterpret_cast<const f32x4*>(src + 4);
-            }
-        }
-      } else if (SUB == 0) {               // entering a block: request the NEXT block into the other buffer
-#pragma unroll
-        for (int i = 0; i < NSC; ++i)
-          if (have_ll && layer + 4 < tpad) {   // rows are padded to tpad (multiple of 32)
-            const f32x4 v = *reinterpret_cast<const f32x4*>(llu + (int64_t)e_col[SC ? i * DEG : i] * tpad + layer + 4);
-            if constexpr ((SUB8 & 4) != 0) sc_a[i] = v; else sc_b[i] = v;
-          }
-      }
+      score_fetch(layer, subc);
       double cc[NSD];
 #pragma unroll
       for (int i = 0; i < NSD; ++i) cc[i] = (SUB & 1) ? *g_odd[i] : *g_even[i];   // gathers issued back to back
@@ -595,7 +630,102 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
     double* tsw = cur; cur = nxt; nxt = tsw;
     return true;
   };
-  if constexpr (FAST) {
+  if constexpr (LAD) {
+    // ---- the ladder: wave w works on group (step - w) of eight layers; one workgroup barrier per step ----
+    const int ngrp = (T >> 3) + 1;                                    // layers 0 .. T
+    float* const pm = s_ac + wave * 640;                              // this wave's strip of parked minima / counts, as in layer_step
+    uint8_t* const pc = reinterpret_cast<uint8_t*>(pm + 512);
+    // Boundary strips, [2 group parities][8 layers] doubles each: wave w writes strip w (its lane-63 cost of every layer), wave w + 1
+    // reads it one step later.  They lie over cur / nxt, which the ladder does not use before the loop ends (nwave - 1 strips of 128
+    // bytes in 16 S bytes: S > 64 (nwave - 1)).  Wave 0 reads the eight +inf of s_red: state 0 has no state below it.
+    const double* const bin = wave == 0 ? s_red : cur + (wave - 1) * 16;
+    const int bpar = wave == 0 ? 0 : 8;
+    double* const bout = cur + wave * 16;
+    const bool pub = lane == 63 && wave + 1 < nwave;
+    // Certificate: the waves deliver a layer one step apart, so the fold over waves is a running (minimum, count) per layer that
+    // wave 0 starts, every later wave joins one step later and the LAST wave finishes and writes out -- the same minimum and the
+    // same sum as the block-wide fold of the general form, then the same step down.  Four groups of eight slots (nwave <= 4).
+    float* const acc_m = s_wmin;
+    int32_t* const acc_c = s_wcnt;
+    auto vmin = [](float x, float y) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; };
+    for (int step = 0; step < ngrp + nwave - 1; ++step) {
+      const int g = step - wave;
+      if (g >= 0 && g < ngrp) {                                       // wave-uniform
+        const int base = 8 * g;
+        const double* const bi = bin + (g & 1) * bpar;
+        double* const bo = bout + (g & 1) * 8;
+        // boundary values: written a step ago, requested two layers ahead of their use -- never on the dependent chain
+        double bv[8];
+        bv[0] = bi[0]; bv[1] = bi[1];
+        auto lad_step = [&](auto subc) -> bool {
+          constexpr int SUB8 = decltype(subc)::value;
+          constexpr int SUB = SUB8 & 3;
+          const int layer = base + SUB8;
+          pm[SUB8 * 64 + lane] = (float)mine[0];
+          pc[SUB8 * 64 + lane] = (uint8_t)mine_live[0];
+          if (pub) bo[SUB8] = mine[0];
+          if (layer == T) return false;
+          if constexpr (SUB8 + 2 < 8) bv[SUB8 + 2] = bi[SUB8 + 2];
+          score_fetch(layer, subc);
+          float sc0, sc1;
+          if constexpr ((SUB8 & 4) != 0) { sc0 = sc_b[0][SUB]; sc1 = sc_b[SC ? 0 : 1][SUB]; } else { sc0 = sc_a[0][SUB]; sc1 = sc_a[SC ? 0 : 1][SUB]; }
+          const float ac0 = -1 * (a.acoustic_scale * sc0);            // decodable-am-diag-gmm.h:96, faster-decoder.cc:208
+          const float ac1 = SC ? ac0 : -1 * (a.acoustic_scale * sc1);
+          const double prev = k2_dpp_d<0x138, 0xf>(bv[SUB8], mine[0]);   // wave_shr:1 -- lane 0 keeps the boundary value
+          const double n_self = (mine[0] + e_w[0]) + ac0;             // faster-decoder.h:125
+          const double n_prev = (prev + e_w[1]) + ac1;
+          double best = INFINITY;
+          best = __builtin_fmin(best, n_self);
+          best = __builtin_fmin(best, n_prev);
+          const bool live = __double2hiint(best) != 0x7FF00000;
+          const bool e_s = live && n_self == best, e_p = live && n_prev == best;
+          const int code = (e_s ? lad_bit[0] : 0) | (e_p ? lad_bit[1] : 0);
+          mine[0] = best;
+          mine_live[0] = live ? 1 : 0;
+          bpw[0] = (bpw[0] >> 4) | ((unsigned)code << 28);
+          const int lb = layer + 1;
+          if ((lb & 7) == 7 || lb == T) {
+            const unsigned wv = (lb & 7) == 7 ? bpw[0] : bpw[0] >> (4 * (7 - (lb & 7)));   // a partial last group is right-aligned
+            reinterpret_cast<unsigned*>(bp)[(int64_t)(lb >> 3) * GW + tid] = wv;
+          }
+          return true;
+        };
+        (void)(lad_step(std::integral_constant<int, 0>{}) && lad_step(std::integral_constant<int, 1>{}) &&
+               lad_step(std::integral_constant<int, 2>{}) && lad_step(std::integral_constant<int, 3>{}) &&
+               lad_step(std::integral_constant<int, 4>{}) && lad_step(std::integral_constant<int, 5>{}) &&
+               lad_step(std::integral_constant<int, 6>{}) && lad_step(std::integral_constant<int, 7>{}));
+        // fold this wave's strip (as layer_step does), join the running fold over waves
+        const int lastsub = min(7, T - base);
+        k2_lds_sync();
+        const int ly = lane >> 3, sub = lane & 7;
+        const f32x4 m0 = *reinterpret_cast<const f32x4*>(pm + ly * 64 + sub * 8), m1 = *reinterpret_cast<const f32x4*>(pm + ly * 64 + sub * 8 + 4);
+        const uint2 cb = *reinterpret_cast<const uint2*>(pc + ly * 64 + sub * 8);
+        float m = vmin(vmin(vmin(m0[0], m0[1]), vmin(m0[2], m0[3])), vmin(vmin(m1[0], m1[1]), vmin(m1[2], m1[3])));
+        int cn = (int)__builtin_amdgcn_sad_u8(cb.y, 0u, __builtin_amdgcn_sad_u8(cb.x, 0u, 0u));
+        m = vmin(m, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0xB1, 0xf, 0xf, false)));
+        cn += __builtin_amdgcn_update_dpp(0, cn, 0xB1, 0xf, 0xf, false);
+        m = vmin(m, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x4E, 0xf, 0xf, false)));
+        cn += __builtin_amdgcn_update_dpp(0, cn, 0x4E, 0xf, 0xf, false);
+        m = vmin(m, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x141, 0xf, 0xf, false)));
+        cn += __builtin_amdgcn_update_dpp(0, cn, 0x141, 0xf, 0xf, false);
+        if (sub == 0 && ly <= lastsub) {
+          const int sl = (g & 3) * 8 + ly;
+          if (wave > 0) { m = vmin(m, acc_m[sl]); cn += acc_c[sl]; }
+          if (wave + 1 < nwave) {
+            acc_m[sl] = m; acc_c[sl] = cn;
+          } else {
+            // m = (float)(exact layer minimum), rounded to nearest: the next float below it is <= the exact minimum
+            if (m == INFINITY) { if (cn > 0) m = 3.402823466e38f; }
+            else m = __int_as_float(__float_as_int(m) + (m > 0.0f ? -1 : (m < 0.0f ? 1 : (int)0x80000001)));
+            lbest[base + ly] = (double)m;
+            lcnt[base + ly] = cn;
+          }
+        }
+      }
+      k2_block_sync();
+    }
+    if (tid < S) cur[tid] = mine[0];                                  // for the best-final search below
+  } else if constexpr (FAST) {
     for (int base = 0; base <= T; base += 8) {
       if (!layer_step(base, std::integral_constant<int, 0>{})) break;
       if (!layer_step(base + 1, std::integral_constant<int, 1>{})) break;
@@ -1801,12 +1931,6 @@ __device__ int k2_finish_wave(const K2Args& a, int u, int best_state, const int3
 
 struct K2ChainArc { float w; int16_t col; uint16_t dst; };        // col < 0: the state has no such out-arc
 
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double k2_dpp_d(double old, double v) {
-  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, ROWMASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, ROWMASK, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
 // inclusive prefix-minimum over the 64 lanes (NaN candidates are ignored, like the reference's `x < cutoff` tests)
 __device__ __forceinline__ double k2_scan_min_d(double v) {
   const double inf = INFINITY;

@@ -30,6 +30,7 @@ struct GraphTables {
 struct GraphFacts {
   int32_t max_indeg = 0, max_outdeg = 0;
   bool same_col = true, has_eps = false;
+  bool ladder = true;            // states in chain order: every in-arc of state s comes from s or from s - 1 (K2's ladder form, khg_k2.hip)
   int64_t nwords = 0;
   std::vector<int32_t> pdfs, pdf_first, pdf_dfin;
 };
@@ -145,6 +146,15 @@ static int plan_graph(const std::string& where, const khg_tm* tm, bool aligner_l
   for (int64_t s = 0; s < S && gf->same_col; ++s)
     for (int64_t k = in_off[s0 + s] + 1; k < in_off[s0 + s + 1]; ++k)
       if (gt->in_col[k] != gt->in_col[in_off[s0 + s]]) { gf->same_col = false; break; }
+  // ladder: no epsilon-input arc, at most two in-arcs per state, each from the state itself or from the one numbered just below it
+  // (at most one of either: the kernel keeps one weight per kind)
+  gf->ladder = !gf->has_eps;
+  for (int64_t s = 0; s < S && gf->ladder; ++s) {
+    const int64_t k0 = in_off[s0 + s], n = in_off[s0 + s + 1] - k0;
+    if (n > 2 || (n == 2 && gt->in_src[k0] == gt->in_src[k0 + 1])) gf->ladder = false;
+    for (int64_t k = k0; k < k0 + n && gf->ladder; ++k)
+      if (gt->in_src[k] != s && gt->in_src[k] != s - 1) gf->ladder = false;
+  }
   return KHG_OK;
 }
 
@@ -259,6 +269,7 @@ extern "C" int khg_utts_create(khg_ctx* ctx, const khg_tm* tm, int32_t n_utt, in
       u->max_indeg = std::max(u->max_indeg, gf.max_indeg);
       u->has_eps = u->has_eps || gf.has_eps;
       u->same_col = u->same_col && gf.same_col;
+      u->ladder = u->ladder && gf.ladder;
       plan_utt_on_graph(u, i, T, S, gf);
     }
     gt.in_off[NS] = NA;
@@ -307,7 +318,7 @@ extern "C" int khg_graph_create(khg_ctx* ctx, const khg_tm* tm, int32_t num_stat
   gt.in_off[S] = A;
   khg_graph* g = new khg_graph();
   g->ctx = ctx; g->S = S; g->A = A; g->start = start; g->nwords = gf.nwords;
-  g->max_indeg = gf.max_indeg; g->max_outdeg = gf.max_outdeg; g->same_col = gf.same_col; g->has_eps = gf.has_eps;
+  g->max_indeg = gf.max_indeg; g->max_outdeg = gf.max_outdeg; g->same_col = gf.same_col; g->ladder = gf.ladder; g->has_eps = gf.has_eps;
   g->pdfs = gf.pdfs; g->pdf_first = gf.pdf_first; g->pdf_dfin = gf.pdf_dfin;
   std::vector<int64_t> so{0, S}, out_off(arc_off, arc_off + S + 1);
   std::vector<int32_t> startv{start};
@@ -364,7 +375,7 @@ extern "C" int khg_utts_create_on_graph(khg_ctx* ctx, const khg_tm* tm, khg_grap
   u->graph = g; ++g->refs;
   u->state_off.assign({0, g->S});
   u->max_states = (int32_t)g->S; u->max_inarcs = (int32_t)g->A; u->max_indeg = g->max_indeg; u->max_outdeg = g->max_outdeg;
-  u->has_eps = g->has_eps; u->same_col = g->same_col;
+  u->has_eps = g->has_eps; u->same_col = g->same_col; u->ladder = g->ladder;
   u->bp_off.assign(n_utt + 1, 0); u->path_off.assign(n_utt + 1, 0); u->words_off.assign(n_utt + 1, 0);
   GraphFacts gf;
   gf.pdfs = g->pdfs; gf.pdf_first = g->pdf_first; gf.pdf_dfin = g->pdf_dfin; gf.nwords = g->nwords;
