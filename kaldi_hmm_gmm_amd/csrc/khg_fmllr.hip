@@ -661,16 +661,12 @@ extern "C" int khg_acc_mllt_stats_post(khg_ctx* ctx, const khg_model* m, const k
   rc = fm_grow(&st->shift_part_d, &st->shift_cap, (size_t)nslice * (size_t)D);
   if (!rc) rc = fm_grow(&st->fm.part_d, &st->fm.part_cap, (size_t)CI * (size_t)st->SZ);
   if (rc) return rc;
-  // K3 from posteriors with ONE work item per pdf, however many entries its bucket holds (ctx->k3_one_block): a cell of the block
+  // K3 from posteriors with ONE work item per pdf, however many entries its bucket holds (k3_acc_stats_post_one_block): a cell of the block
   // then receives one workgroup's sum, made in chunk order over the stably sorted entries, so occ_g / m_g -- and with them C -- have
   // the same bits from run to run.  K3's own choice cuts a bucket into several items, which end with fp64 atomics into the same cells
   // in whatever order they finish.  The price: the pdf with the most entries (silence) is one workgroup's walk.
   rc = khg_accs_zero(ctx, st->acc);
-  if (!rc) {
-    ctx->k3_one_block = true;
-    rc = khg_acc_stats_post(ctx, m, tm, u, p, scale, st->acc);
-    ctx->k3_one_block = false;
-  }
+  if (!rc) rc = k3_acc_stats_post_one_block(ctx, m, tm, u, p, scale, st->acc);
   if (rc) return rc;
   {
     KernelTimer kt(ctx, "k_mllt_shift");

@@ -69,7 +69,6 @@ struct khg_ctx {
   bool pageable_pending = false;    // a hipMemcpyAsync from pageable host memory may still be reading its source (sync_pageable)
   bool timing = false;
   std::vector<khg_timing> timings;
-  bool k3_one_block = false;        // set by khg_acc_mllt_stats_post around its K3 pass: ONE work item per pdf whatever its bucket holds
   int opt[KHG_OPT_COUNT] = {};    // khg_ctx_set_option (KHG_OPT_*); the environment variables of include/khg_hip.h only seed the defaults, once, at khg_ctx_create
 };
 int arena_flush(khg_ctx* ctx);                             // khg_ctx_model.hip: staged uploads -> device, one copy on the context's stream
@@ -376,6 +375,9 @@ int ctx_comm_stream(khg_ctx* ctx);                        // khg_c1.hip
 // khg_k3.hip: KHG_E_UNSUPPORTED where khg_acc_stats_post refuses the model (a pdf too wide for the any-size form's LDS buffers), for a
 // caller that wants the refusal among its own up-front checks
 int k3_post_check(khg_ctx* ctx, const khg_model* m, const std::string& who);
+// khg_k3.hip: khg_acc_stats_post -- its checks and error texts under that name -- with ONE work item per pdf whatever its bucket holds
+// (khg_acc_mllt_stats_post).  (hidden: the library's dynamic symbols stay the C-ABI's and what they were)
+__attribute__((visibility("hidden"))) int k3_acc_stats_post_one_block(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale, khg_accs* acc);
 // khg_lattices.hip: what khg_acc_stats_post (khg_k3.hip) needs of a posteriors handle, whose layout stays private to that unit
 struct PostInfo { const khg_ctx* ctx; int32_t U, max_tid; const int64_t *frame_off, *entry_off; };   // max_tid < 0: made from lattices
 void posteriors_info(const khg_posteriors* p, PostInfo* out);

@@ -100,8 +100,6 @@ extern "C" int khg_accs_smooth_with_accum(khg_ctx* ctx, khg_accs* dst, float tau
   return KHG_OK;
 }
 
-// K3, optionally with C1 pipelined behind it: the pdfs are cut into `nparts` ranges; the accumulate kernels of range i + 1 run on
-// the context's stream while the all-reduce of range i's accumulator rows runs on the context's communication stream.
 // K3's phase A on the fp16 matrix cores (khg_k3_accstats.hip.inc, k3_accumulate_wave<NB, true>): the scale exponents come from the
 // MODEL alone -- every rank of a sharded run derives the same ones, so the statistics do not depend on the sharding: per
 // dimension the features are expected inside xb = max_g (|mean| + 8 sigma); x' = x 2^ex peaks in [2^12, 2^13) there (fp16 overflows
@@ -164,30 +162,174 @@ static size_t k3_valu_lds(const khg_model* m, int maxG, bool post) {
   return sizeof(float) * (size_t)K3_CHUNK * ((size_t)(m->KQ ? 4 * m->KQ : (m->D | 1)) + (maxG | 1) + (post ? 5 : 4));
 }
 #define K3_VALU_LDS_MAX (160 * 1024)
+// ------------------------------------------------------------------------------------------
+// The ONE dispatch rule of the statistics pass: which accumulate form takes which pdfs, with how many slices per pdf, which bounds
+// for the work-item buffers, which block size and dynamic LDS.  The form is chosen per pdf, so the answer is one RUN -- a class of
+// pdfs (cls_lo < Gaussians <= cls_hi) with its form -- or two: one pdf that Split (csrc/diag-gmm.cc:780-851) pushed past 64
+// Gaussians does not take every other pdf off the wave form.  acc_stats_pass launches what this says and k3_post_check asks it for
+// the one refusal; nothing is launched or allocated here.
+enum K3Form { K3F_WAVE, K3F_MFMA, K3F_VALU };
+struct K3Run {
+  int form = K3F_VALU;
+  int cls_lo = 0, cls_hi = INT_MAX;          // the run's class of pdfs; the others get no work item
+  int maxG = 0, n_cls = 0;                   // the widest pdf of the class; the pdfs a range's grid counts at most (wave form: all P)
+  bool second = false;                       // the second class of a mixed call keeps its items in the upper halves of the buffers
+  int NB = 0, NB16 = 0, nwv16 = 4;           // Gaussian blocks: of 16 per block (wave), of 64 per wave (MFMA); k3_accumulate_block16's, and its waves (else 4)
+  int ny = 1;                                // slices per pdf, before k3_make_items cuts a far-above-average bucket finer
+  bool parked = false;                       // the slices park images (wave form), of nsum1 doubles each
+  size_t nsum1 = 0;
+  int target = 0;                            // work items, from N and P alone (the bucket sizes stay on the device): frames per extra slice,
+  int64_t extra_blocks = 0, max_items = 0, max_slots = 0;   // ... blocks beyond pdfs x ny, and what the buffers must hold
+  // The fp16 phases rest on model-derived scales (k3_phase_a_scales: device work, cached per parameter version) and on the weight
+  // being an ordinary number: the plan says what MAY run, the run settles it once when it starts.
+  bool may_f16a = false, may_f16b = false;
+  size_t lds[3] = {0, 0, 0};                 // dynamic LDS: fp32 phase A | fp16 phase A | both phases on the fp16 matrix cores
+  bool too_wide = false;                     // VALU form: the widest pdf does not fit the LDS chunk buffers
+};
+struct K3Plan { int nruns = 0; K3Run run[2]; };
+
+static K3Plan k3_plan(const khg_ctx* ctx, const khg_model* m, bool post, int64_t Neff, bool one_block) {
+  const int P = m->P, KQ = m->KQ;
+  const int k3form = ctx->opt[KHG_OPT_K3_FORM];     // 1: the chunk-per-block MFMA form for every shape; 2: the VALU form
+  const int pha = ctx->opt[KHG_OPT_K3_PHASE_A], phb = ctx->opt[KHG_OPT_K3_PHASE_B], ny_opt = ctx->opt[KHG_OPT_K3_NY];
+  const int64_t avg = Neff / std::max(1, P);
+  // Work items (k3_make_items): ny slices per pdf, more for a pdf whose bucket is far above the average slice (2 x; silence in real
+  // transcripts).  (one_block: no bucket is cut, so every cell of the block receives ONE work item's sum, made in chunk order -- the
+  // fp64 atomics that end an item then have no second item to race with, and the statistics have the same bits from run to run)
+  auto items = [&](K3Run& r) {
+    r.target = one_block ? INT_MAX : (int)std::min<int64_t>(1 << 30, std::max<int64_t>(512, 2 * avg / r.ny));
+    const int64_t per_t = Neff / r.target;
+    r.extra_blocks = std::min<int64_t>(per_t + P, 2 * per_t) + 1;
+    r.max_items = (int64_t)P * r.ny + r.extra_blocks;
+    r.max_slots = !r.parked ? INT_MAX : r.ny > 1 ? r.max_items : 2 * per_t + 1;
+  };
+  // ---- the wave-local form (pdfs of <= 64 Gaussians at D <= 40): W in LDS + per-wave planes during the tile loop, the fp64 fold image afterwards ----
+  auto wave = [&](int cls_lo, int cls_hi, int maxG) {
+    K3Run r;
+    r.form = K3F_WAVE; r.cls_lo = cls_lo; r.cls_hi = cls_hi; r.maxG = maxG; r.n_cls = P;
+    const size_t nb = (size_t)(r.NB = (maxG + 15) / 16);
+    // phase A on the fp16 matrix cores where the model-derived scales hold (KHG_K3_PHASEA=f32 keeps the fp32 chain; so does
+    // KHG_OPT_K3_PHASE_B = 1); phase B there as well (k3_accumulate_wave16; KHG_OPT_K3_PHASE_B = 2) where phase A's split planes exist
+    // (pdfs of <= 32 Gaussians keep the fp32 chain: 40 MFMAs per tile are not worth the split, and the two-waves-per-SIMD instantiations have no registers for the fp16 W pieces)
+    r.may_f16a = nb >= 3 && pha == 0 && phb != 1; r.may_f16b = phb == 2;
+    // fp32 phase A: W + the waves' planes; fp16 phase A: the waves' planes + their split planes; k3_accumulate_wave16: per wave two
+    // tiles' phase-A planes + the phase-B planes (halves), then the split W operands; then, in each, the fold image
+    const size_t fold = sizeof(double) * (nb * 16 * 80 + nb * 16);
+    r.lds[0] = std::max<size_t>(sizeof(float) * (nb * 20 * 64 + 4 * 4 * 16 * 20), fold);
+    r.lds[1] = std::max<size_t>(sizeof(float) * (4 * 4 * 16 * 20) + 2 * (size_t)(4 * 2 * 16 * K3_XH_ROW), fold);
+    r.lds[2] = std::max<size_t>(2 * (size_t)4 * (2 * (2 * 16 * K3_XH_ROW) + 2 * 2 * 40 * 36) + nb * 3 * 2 * 64 * 16, fold);
+    const int64_t avg_tiles = (avg + 15) / 16;
+    r.ny = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(32, (avg_tiles + 15) / 16), (4096 + P - 1) / P));
+    if (ny_opt > 0) r.ny = ny_opt;
+    // per-pdf log-like partials (always) and, with several blocks per pdf, the slice images they park
+    r.parked = true; r.nsum1 = nb * 16 * 80 + nb * 16 + 1;
+    items(r);
+    return r;
+  };
+  // ---- the chunk-per-block forms: fp32 + fp64 MFMA (fewer, longer blocks: the fp64 accumulators stay in registers per block); VALU (any size) ----
+  auto block = [&](int form, int cls_lo, int cls_hi, int maxG, int n_cls, bool second) {
+    K3Run r;
+    r.form = form; r.cls_lo = cls_lo; r.cls_hi = cls_hi; r.maxG = maxG; r.n_cls = n_cls; r.second = second;
+    const int64_t avg_chunks = (avg + K3_CHUNK - 1) / K3_CHUNK;
+    if (form == K3F_MFMA) {
+      r.NB = std::max(1, (maxG + 63) / 64);
+      r.lds[0] = sizeof(float) * ((size_t)4 * K3_CHUNK * 2 * KQ + (post ? 6 : 5) * K3_CHUNK);   // 4 planes [64][KH] + reductions (+ the entries' weights)
+      // slices per pdf: every block ends with one fp64 atomic per accumulator cell (G*(2D+1) of them), so use as few blocks as still fill the chip (~4096 = 256 CUs x 8 blocks x 2 rounds)
+      // (a class of a few pdfs -- the ones a split has grown -- is cut finer: one block walking a whole bucket is a latency of its own)
+      r.ny = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(32, avg_chunks), (4096 + n_cls - 1) / std::max(1, n_cls)));
+      if (ny_opt > 0) r.ny = ny_opt;
+      // Both phases on the fp16 matrix cores (k3_accumulate_block16) under the conditions of the wave form's fp16 phases: <= 128
+      // Gaussians at D <= 80, <= 192 at D <= 40.  KHG_K3_PHASEA=f32 or KHG_K3_PHASEB=f64 keep the fp32 / fp64 MFMA form.
+      r.may_f16a = r.may_f16b = !post && pha == 0 && phb == 2 && ((KQ == 20 && maxG <= 128) || (KQ == 10 && maxG <= 192));
+      // (one Gaussian block per wave: < 256 registers, so a block of eight waves runs two per SIMD; four blocks per wave -- 193..256
+      //  Gaussians -- spill at 512 registers: the fp32 / fp64 form keeps them)
+      r.NB16 = maxG <= 128 ? 1 : 3; r.nwv16 = maxG > 64 && maxG <= 128 ? 8 : 4;
+      // split planes of a chunk in both layouts + the softmax's exchange: [2][64][KPAD + 8] + [2][2 XP][72] halves, 5 x 64 floats
+      // ... or, before the chunk loop, the pdf's parameter rows [2][lanes' Gaussians][D | 1] + the columns' exponents
+      const size_t kpad = ((size_t)8 * KQ + 31) / 32 * 32, gp_b16 = maxG <= 64 ? 64 : (maxG <= 128 ? 128 : 192);
+      r.lds[2] = std::max<size_t>(2 * (2 * (size_t)K3_CHUNK * (kpad + 8) + 2 * (size_t)8 * KQ * (K3_CHUNK + 8)) + sizeof(float) * 9 * K3_CHUNK,
+                                  sizeof(float) * (2 * gp_b16 * (size_t)(m->D | 1) + 8 * (size_t)KQ));
+    } else {
+      r.lds[0] = k3_valu_lds(m, maxG, post); r.too_wide = r.lds[0] > K3_VALU_LDS_MAX;
+      r.ny = (int)std::max<int64_t>(1, std::min<int64_t>(64, (avg_chunks + 3) / 4));
+    }
+    if (one_block) r.ny = 1;
+    items(r);
+    return r;
+  };
+  // Form per pdf: the wave form takes every pdf of <= 64 Gaussians (D <= 40); what is left -- a few pdfs a split grew, or a model
+  // of wide pdfs throughout -- goes to the chunk-per-block MFMA form (<= 256 Gaussians at D <= 40, <= 128 at D <= 80) or the VALU form.
+  int maxG = 0, maxG_lo = 0, n_hi = 0;
+  for (int p = 0; p < P; ++p) {
+    const int Gp = m->gauss_off[(size_t)p + 1] - m->gauss_off[(size_t)p];
+    maxG = std::max(maxG, Gp);
+    if (Gp <= 64) maxG_lo = std::max(maxG_lo, Gp); else ++n_hi;
+  }
+  const bool mfma_ok = (maxG <= 128 || (maxG <= 256 && KQ == 10)) && k3form != 2 && KQ != 0;
+  const bool wave_ok = !post && KQ == 10 && k3form == 0 && maxG_lo > 0;       // (the wave forms' fp16 phase B rests on ONE |weight|: 7h)
+  const int rest = mfma_ok ? K3F_MFMA : K3F_VALU;
+  K3Plan pl;
+  if (wave_ok && n_hi == 0) pl.run[pl.nruns++] = wave(0, INT_MAX, maxG);
+  else if (wave_ok) {
+    pl.run[pl.nruns++] = wave(0, 64, maxG_lo);
+    pl.run[pl.nruns++] = block(rest, 64, INT_MAX, maxG, n_hi, true);
+  } else pl.run[pl.nruns++] = block(rest, 0, INT_MAX, maxG, P, false);
+  return pl;
+}
+
 // The one refusal khg_acc_stats_post raises behind its argument checks, for khg_acc_mllt_stats_post to raise among its own: the
 // posterior pass sends a model to the chunk-per-block MFMA form or, past that form's sizes, to the VALU form, whose LDS bounds the pdf.
 int k3_post_check(khg_ctx* ctx, const khg_model* m, const std::string& who) {
-  int maxG = 0;
-  for (int p = 0; p < m->P; ++p) maxG = std::max(maxG, m->gauss_off[(size_t)p + 1] - m->gauss_off[(size_t)p]);
-  const bool mfma_ok = (maxG <= 128 || (maxG <= 256 && m->KQ == 10)) && ctx->opt[KHG_OPT_K3_FORM] != 2 && m->KQ != 0;
-  if (!mfma_ok && k3_valu_lds(m, maxG, true) > K3_VALU_LDS_MAX)
-    return khg_set_error(KHG_E_UNSUPPORTED, who + "a pdf of " + std::to_string(maxG) + " Gaussians is too large for the LDS chunk buffers of the statistics pass");
+  const K3Run r = k3_plan(ctx, m, true, 0, false).run[0];     // (from posteriors: one run)
+  if (r.too_wide) return khg_set_error(KHG_E_UNSUPPORTED, who + "a pdf of " + std::to_string(r.maxG) + " Gaussians is too large for the LDS chunk buffers of the statistics pass");
   return KHG_OK;
 }
 
-// One pass of K3 over the set's resident alignment: all N frames (nsub < 0), or -- the second pass of the split mode -- the nsub frames
-// of the utterances the DP left to the order-faithful decoders (flagged in u->unc_d; their alignments are merged into ali_d by now).
-// npost >= 0 (khg_acc_stats_post): the pass runs over the npost flattened entries in u->pe_* instead of the alignment -- its own
-// sort buffers and bucket bounds, the POST instantiations of the fp32-chain forms (`weight` is unused: every entry carries its own).
-static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, float weight, khg_accs* acc, void* comm, int nparts, int64_t nsub,
-                          int64_t npost = -1) {
-  int rc = KHG_OK;
-  const bool post = npost >= 0;
-  const int64_t Neff = post ? npost : nsub < 0 ? u->N : nsub;
-  if (!post) {
-    HIPCHK(hipMemsetAsync(u->pdf_count_d, 0, sizeof(int32_t) * (size_t)m->P, ctx->stream));
-    HIPCHK(hipMemsetAsync(u->tid_count_d, 0, sizeof(unsigned long long) * ((size_t)tm->num_tids + 1), ctx->stream));
+// Every instantiation of the accumulate kernels, once: (variant, KQ, Gaussian blocks, waves, POST, fp16 phase A) -> the kernel.
+typedef void (*K3Kernel)(K3Args);
+enum K3Variant { K3V_WAVE, K3V_WAVE16, K3V_FINALIZE, K3V_MFMA, K3V_BLOCK16, K3V_VALU };
+struct K3Inst { int variant, KQ, NB, nwv; bool post, f16a; K3Kernel fn; };
+#define K3_WAVE_ROWS(NB)                                                                                                           \
+  {K3V_WAVE, 10, NB, 4, false, false, k3_accumulate_wave<NB>}, {K3V_WAVE, 10, NB, 4, false, true, k3_accumulate_wave<NB, true>}, \
+  {K3V_WAVE16, 10, NB, 4, false, true, k3_accumulate_wave16<NB>}, {K3V_FINALIZE, 10, NB, 4, false, false, k3_wave_finalize<NB>}
+#define K3_MFMA_ROWS(KQ, NBW) {K3V_MFMA, KQ, NBW, 4, false, false, k3_accumulate_mfma<KQ, NBW>}, {K3V_MFMA, KQ, NBW, 4, true, false, k3_accumulate_mfma<KQ, NBW, true>}
+#define K3_VALU_ROWS(KQ) {K3V_VALU, KQ, 0, 4, false, false, k3_accumulate<KQ>}, {K3V_VALU, KQ, 0, 4, true, false, k3_accumulate<KQ, true>}
+static const K3Inst k3_insts[] = {
+  K3_WAVE_ROWS(1), K3_WAVE_ROWS(2), K3_WAVE_ROWS(3), K3_WAVE_ROWS(4),
+  K3_MFMA_ROWS(10, 1), K3_MFMA_ROWS(10, 2), K3_MFMA_ROWS(10, 3), K3_MFMA_ROWS(10, 4), K3_MFMA_ROWS(20, 1), K3_MFMA_ROWS(20, 2),
+  {K3V_BLOCK16, 20, 1, 4, false, true, k3_accumulate_block16<20, 1, 4>}, {K3V_BLOCK16, 10, 1, 4, false, true, k3_accumulate_block16<10, 1, 4>},
+  {K3V_BLOCK16, 20, 1, 8, false, true, k3_accumulate_block16<20, 1, 8>}, {K3V_BLOCK16, 10, 1, 8, false, true, k3_accumulate_block16<10, 1, 8>},
+  {K3V_BLOCK16, 10, 3, 4, false, true, k3_accumulate_block16<10, 3, 4>},
+  K3_VALU_ROWS(10), K3_VALU_ROWS(20), K3_VALU_ROWS(0),
+};
+static K3Kernel k3_kernel(int variant, int KQ, int NB, int nwv, bool post, bool f16a) {
+  for (const K3Inst& i : k3_insts)
+    if (i.variant == variant && i.KQ == KQ && i.NB == NB && i.nwv == nwv && i.post == post && i.f16a == f16a) return i.fn;
+  return nullptr;
+}
+// ... and the one launch of them
+static int k3_launch(khg_ctx* ctx, K3Kernel fn, unsigned grid, int nthr, size_t lds, const K3Args& a) {
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KHG_LAUNCH(ctx, fn, dim3(grid), dim3(nthr), lds, ctx->stream, a);
+  return KHG_OK;
+}
+
+// K3, optionally with C1 pipelined behind it: the pdfs are cut into `nparts` ranges; launch(p0, np) enqueues the accumulate kernels of
+// one range on the context's stream, and they run while the all-reduce of the previous range's accumulator rows runs on the context's
+// communication stream.  The sequence of collectives is a function of (P, nparts) only, whatever `launch` does.
+template <class Launch>
+static int k3_for_ranges(khg_ctx* ctx, const khg_model* m, khg_accs* acc, void* comm, int nparts, Launch&& launch) {
+  const int n = comm ? nparts : 1;
+  for (int part = 0; part < n; ++part) {
+    const int p0 = (int)((int64_t)m->P * part / n), np = (int)((int64_t)m->P * (part + 1) / n) - p0;
+    int rc = launch(p0, np);
+    if (!rc && comm && n > 1) rc = accs_allreduce_pieces(ctx, acc, m, p0, np, comm, nullptr);
+    if (rc) return rc;
   }
+  return KHG_OK;
+}
+
+static K3Args k3_args(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, const khg_utts* u, khg_accs* acc, float weight, bool post, int64_t Neff) {
   K3Args a;
   a.feats = u->feats_d; a.ali = post ? u->pe_tid_d : u->ali_d; a.id2pdf = tm->id2pdf_d; a.num_tids = tm->num_tids;
   a.N = Neff; a.P = m->P; a.D = m->D;
@@ -195,332 +337,185 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
   a.pdf_count = u->pdf_count_d; a.pdf_start = post ? u->pe_start_d : u->pdf_start_d; a.pdf_cursor = u->pdf_cursor_d;
   a.frame_ids = post ? u->pe_ids_d : u->frame_ids_d; a.tid_count = u->tid_count_d;
   a.e_row = post ? u->pe_row_d : nullptr; a.e_w = post ? u->pe_w_d : nullptr;
+  a.occ = acc->occ(); a.mean_acc = acc->mean(); a.var_acc = acc->var(); a.trans_acc = acc->trans(); a.scalars = acc->scalars();
+  a.weight = weight; a.err_flag = ctx->err_flag_d; a.part = nullptr; a.ll_part = nullptr; a.pdf0 = 0; a.npdf = m->P; a.items = nullptr; a.item_off = nullptr;
+  a.pa_ex = nullptr; a.pa_S = 0; a.pa_scale = 1.0f; a.pa_inv = 1.0f; a.pa_c1 = 1.44269504088896340736f; a.pb_gscale = 1.0f; a.pb_SG = 0;   // (k3_set_scales)
+  return a;
+}
+// the fp16 phases' scales: the model's for phase A (k3_phase_a_scales said they hold), the weight's for phase B
+static bool k3_weight_ordinary(float weight) { return std::isfinite(weight) && std::fabs(weight) > 1.0e-30f && std::fabs(weight) < 1.0e30f; }
+static void k3_set_scales(K3Args& a, const khg_model* m, bool f16a, bool f16b) {
+  if (f16a) {
+    a.pa_ex = m->k3_ex_d; a.pa_S = m->k3_S;
+    a.pa_scale = std::ldexp(1.0f, m->k3_S); a.pa_inv = std::ldexp(1.0f, -m->k3_S); a.pa_c1 = std::ldexp(1.44269504088896340736f, -m->k3_S);
+  }
+  if (f16b) { a.pb_SG = 13 - std::ilogb(std::fabs(a.weight)); a.pb_gscale = std::ldexp(1.0f, a.pb_SG); }
+}
+
+// Frames (entries) -> buckets by pdf, one of three ways; the transition statistics on the way
+template int u_alloc<uint32_t>(khg_utts*, uint32_t**, size_t);     // (one copy out of line for the sort's buffers, as it always was: the library's dynamic symbols stay what they were)
+static int k3_bucket(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const K3Args& a, bool post, int64_t nsub, int64_t Neff) {
+  int rc = KHG_OK;
   // the sort's buffers: K3's own, cached on the set for its N frames, or the posteriors' (sized by the caller for the entries)
   uint32_t *&sort_keys = post ? u->pe_keys_d : u->sort_keys_d, *&sort_keys_out = post ? u->pe_keys_out_d : u->sort_keys_out_d;
   uint32_t*& sort_vals = post ? u->pe_vals_d : u->sort_vals_d;
   void*& sort_tmp = post ? u->pe_tmp_d : u->sort_tmp_d;
   size_t& sort_tmp_bytes = post ? u->pe_tmp_bytes : u->sort_tmp_bytes;
-  a.occ = acc->occ(); a.mean_acc = acc->mean(); a.var_acc = acc->var(); a.trans_acc = acc->trans(); a.scalars = acc->scalars();
-  a.weight = weight; a.err_flag = ctx->err_flag_d; a.part = nullptr; a.ll_part = nullptr; a.pdf0 = 0; a.npdf = m->P; a.items = nullptr; a.item_off = nullptr;
-  a.pa_ex = nullptr; a.pa_S = 0; a.pa_scale = 1.0f; a.pa_inv = 1.0f; a.pa_c1 = 1.44269504088896340736f;
+  const int gb = (int)std::min<int64_t>(4096, (Neff + 255) / 256);
+  {
+    KernelTimer kt(ctx, nsub < 0 ? "k3_bucket" : "k3_bucket_pass2");
+    // KHG_OPT_K3_BUCKET = 1: cursor-bump scatter (bucket order depends on the atomics)
+    if (!post && nsub < 0 && (ctx->opt[KHG_OPT_K3_BUCKET] == 1 || u->N >= (int64_t)INT_MAX)) {
+      KHG_LAUNCH(ctx, k3_count, dim3(gb), dim3(256), 0, ctx->stream, a);
+      KHG_LAUNCH(ctx, k3_scan, dim3(1), dim3(1024), 0, ctx->stream, a);
+      KHG_LAUNCH(ctx, k3_scatter, dim3(gb), dim3(256), 0, ctx->stream, a);
+    } else if (!post && nsub < 0 && ctx->opt[KHG_OPT_K3_BUCKET] == 2 && m->P <= K3_CS_MAXP) {
+      // the library's own stable counting sort (khg_k3_accstats.hip.inc: k3_cs_*; opt-in: 1.27 ms against the radix sort's 0.80 at the
+      // bench size): blocks of CB consecutive frames
+      const int nw = m->P + 1 <= 7168 ? 4 : 2;                      // waves of a placing block: nw x (P + 1 + 1024) counters of LDS
+      int64_t CB = 32768;
+      while (CB > 64 * nw * 4 && (u->N + CB - 1) / CB < 1024) CB /= 2;   // enough blocks to fill the chip on small sets
+      const int nblk = (int)((u->N + CB - 1) / CB);
+      const size_t hist_n = (size_t)nblk * ((size_t)m->P + 1);
+      if (u->cs_hist_n < hist_n) { DEVFREE(u->cs_hist_d); rc = u_alloc(u, &u->cs_hist_d, hist_n); if (rc) return rc; u->cs_hist_n = hist_n; }
+      if (u->cs_tot_n < (size_t)m->P + 1) { DEVFREE(u->cs_tot_d); rc = u_alloc(u, &u->cs_tot_d, (size_t)m->P + 1); if (rc) return rc; u->cs_tot_n = (size_t)m->P + 1; }
+      K3CsArgs c{u->cs_hist_d, u->cs_tot_d, (int32_t)CB, nblk};
+      const bool ldst = tm->num_tids <= K3_LDS_TIDS;
+      const size_t lds_h = sizeof(unsigned int) * ((size_t)m->P + 1 + (ldst ? (size_t)tm->num_tids + 1 : 0));
+      const size_t lds_p = sizeof(unsigned int) * (size_t)nw * ((size_t)m->P + 1 + 1024);     // per-wave counters + the run-head hash tags
+      if (lds_h > 48 * 1024) {
+        HIPCHK(hipFuncSetAttribute((const void*)k3_cs_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
+        HIPCHK(hipFuncSetAttribute((const void*)k3_cs_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
+      }
+      if (lds_p > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k3_cs_place, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
+      if (ldst) KHG_LAUNCH(ctx, k3_cs_hist<true>, dim3(nblk), dim3(256), lds_h, ctx->stream, a, c);
+      else KHG_LAUNCH(ctx, k3_cs_hist<false>, dim3(nblk), dim3(256), lds_h, ctx->stream, a, c);
+      KHG_LAUNCH(ctx, k3_cs_scan, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, a, c);
+      KHG_LAUNCH(ctx, k3_cs_starts, dim3(1), dim3(1024), 0, ctx->stream, a, c);
+      KHG_LAUNCH(ctx, k3_cs_place, dim3(nblk), dim3(64 * nw), lds_p, ctx->stream, a, c);
+    } else {
+      // stable sort of (pdf, frame) pairs: frames of a pdf stay in frame order; the bucket boundaries are read
+      // off the sorted keys
+      int bits = 1;
+      while ((1 << bits) <= m->P) ++bits;            // keys are 0..P
+      if (!sort_keys) {
+        rc = u_alloc(u, &sort_keys, (size_t)u->N);
+        if (!rc) rc = u_alloc(u, &sort_keys_out, (size_t)u->N);
+        if (!rc) rc = u_alloc(u, &sort_vals, (size_t)u->N);
+        if (rc) return rc;
+      }
+      size_t need = 0;
+      HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, sort_keys, sort_keys_out, sort_vals,
+                                                reinterpret_cast<uint32_t*>(a.frame_ids), (int)Neff, 0, bits, ctx->stream));
+      if (need > sort_tmp_bytes) {
+        DEVFREE(sort_tmp);
+        { int rt = u_alloc(u, reinterpret_cast<char**>(&sort_tmp), need); if (rt) return rt; }
+        sort_tmp_bytes = need;
+      }
+      if (post) {
+        // the (pdf, entry) pairs and the weighted transition statistics (khg_k3_post.hip.inc)
+        const bool ldst = tm->num_tids <= K3_LDS_TIDS;
+        if (ldst) KHG_LAUNCH(ctx, k3_post_keys<true>, dim3(std::min(gb, 1024)), dim3(256), sizeof(double) * ((size_t)tm->num_tids + 1), ctx->stream, a, sort_keys, sort_vals);
+        else KHG_LAUNCH(ctx, k3_post_keys<false>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
+      } else if (nsub >= 0) {
+        // the (pdf, frame) pairs of the flagged utterances only, utterances in order: positions from an exclusive sum of their lengths
+        if (!u->sub_off_d) { rc = u_alloc(u, &u->sub_off_d, (size_t)u->n_utt + 1); if (rc) return rc; }
+        KHG_LAUNCH(ctx, k3_sub_scan, dim3(1), dim3(1024), 0, ctx->stream, u->unc_d, u->frame_off_d, u->n_utt, u->sub_off_d);
+        KHG_LAUNCH(ctx, k3_sub_keys, dim3((unsigned)std::min(u->n_utt, 8192)), dim3(64), 0, ctx->stream, a, u->unc_d, u->frame_off_d, u->sub_off_d, u->n_utt, sort_keys, sort_vals);
+      } else if (tm->num_tids <= K3_LDS_TIDS) KHG_LAUNCH(ctx, k3_sort_keys<true>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
+      else KHG_LAUNCH(ctx, k3_sort_keys<false>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
+      HIPCHK(hipcub::DeviceRadixSort::SortPairs(sort_tmp, need, sort_keys, sort_keys_out, sort_vals,
+                                                reinterpret_cast<uint32_t*>(a.frame_ids), (int)Neff, 0, bits, ctx->stream));
+      if (post) {
+        K3Args b = a;
+        b.num_tids = -1;        // k3_bounds has no integer counts to fold: k3_post_keys added the weighted ones itself
+        KHG_LAUNCH(ctx, k3_bounds, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, b, sort_keys_out);
+      } else KHG_LAUNCH(ctx, k3_bounds, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, a, sort_keys_out);
+    }
+  }
+  return KHG_OK;
+}
+// Work items of one run (k3_make_items) into the set's buffers, grown to the plan's bounds; two classes keep their item lists side by
+// side in the same buffers (r.second: the upper halves).  -> *items, *item_off: the run's lists
+static int k3_make_work_items(khg_ctx* ctx, const khg_model* m, khg_utts* u, const K3Args& a, const K3Run& r, K3Item** items, int32_t** item_off) {
+  if (r.max_items >= INT_MAX / 2) return khg_set_error(KHG_E_UNSUPPORTED, "khg_acc_stats: too many work items");
+  const size_t n_items = (size_t)r.max_items, n_off = (size_t)m->P + 1, n_part = r.parked ? (size_t)r.max_slots * r.nsum1 : 0;
+  int rc = KHG_OK;
+  if (u->k3_items_n < n_items) { DEVFREE(u->k3_items_d); rc = u_alloc(u, reinterpret_cast<K3Item**>(&u->k3_items_d), 2 * n_items); if (rc) return rc; u->k3_items_n = n_items; }
+  if (u->k3_item_off_n < n_off) { DEVFREE(u->k3_item_off_d); rc = u_alloc(u, &u->k3_item_off_d, 2 * n_off); if (rc) return rc; u->k3_item_off_n = n_off; }
+  if (u->k3_part_n < n_part) { DEVFREE(u->k3_part_d); rc = u_alloc(u, &u->k3_part_d, n_part); if (rc) return rc; u->k3_part_n = n_part; }
+  *items = reinterpret_cast<K3Item*>(u->k3_items_d) + (r.second ? u->k3_items_n : 0);
+  *item_off = u->k3_item_off_d + (r.second ? u->k3_item_off_n : 0);
+  KHG_LAUNCH(ctx, k3_make_items, dim3(1), dim3(1024), 0, ctx->stream, a, r.ny, r.target, (int)r.max_items, (int)std::min<int64_t>(r.max_slots, INT_MAX),
+             *items, *item_off, r.cls_lo, r.cls_hi);
+  return KHG_OK;
+}
+// One run of the plan: the fp16 phases settled, its work items, its kernels range by range.  `a` carries on from run to run.
+static int k3_run(khg_ctx* ctx, const khg_model* m, khg_utts* u, khg_accs* acc, K3Args& a, const K3Run& r, bool post, const char* timer, void* comm, int nparts) {
+  if (r.too_wide) return khg_set_error(KHG_E_UNSUPPORTED, "khg_acc_stats: pdf too large for the LDS chunk buffers");
+  const bool wave = r.form == K3F_WAVE;
+  // (the MFMA form has both phases on the fp16 matrix cores or neither, so the weight is asked first; the wave form keeps phase A alone)
+  const bool wt = k3_weight_ordinary(a.weight);
+  bool f16a = false;
+  if (r.may_f16a && (wave || wt)) { int rs = k3_phase_a_scales(ctx, const_cast<khg_model*>(m), u, &f16a); if (rs) return rs; }
+  const bool f16b = f16a && r.may_f16b && wt;
+  k3_set_scales(a, m, f16a, f16b);
+  const int variant = wave ? (f16b ? K3V_WAVE16 : K3V_WAVE) : r.form == K3F_VALU ? K3V_VALU : f16b ? K3V_BLOCK16 : K3V_MFMA;
+  const int nwv = variant == K3V_BLOCK16 ? r.nwv16 : 4;     // the block size
+  const K3Kernel fn = k3_kernel(variant, m->KQ, variant == K3V_BLOCK16 ? r.NB16 : r.NB, nwv, post, f16a);
+  const K3Kernel fin = wave ? k3_kernel(K3V_FINALIZE, m->KQ, r.NB, 4, false, false) : nullptr;
+  if (!fn || (wave && !fin)) return khg_set_error(KHG_E_RUNTIME, "khg_acc_stats: no kernel for the planned form");
+  const size_t lds = r.lds[f16b ? 2 : f16a ? 1 : 0];
+  int rc = KHG_OK;
+  if (wave && u->k3_llpart_n < (size_t)m->P) { DEVFREE(u->k3_llpart_d); rc = u_alloc(u, &u->k3_llpart_d, (size_t)m->P); if (rc) return rc; u->k3_llpart_n = (size_t)m->P; }
+  K3Item* items = nullptr; int32_t* item_off = nullptr;
+  rc = k3_make_work_items(ctx, m, u, a, r, &items, &item_off); if (rc) return rc;
+  a.items = items; a.item_off = item_off;
+  if (wave) {
+    HIPCHK(hipMemsetAsync(u->k3_llpart_d, 0, sizeof(double) * (size_t)m->P, ctx->stream));
+    a.ll_part = u->k3_llpart_d; a.part = u->k3_part_d;
+  }
+  rc = k3_for_ranges(ctx, m, acc, comm, nparts, [&](int p0, int np) -> int {
+    a.pdf0 = p0; a.npdf = np;
+    const unsigned nblk = (unsigned)((int64_t)std::min(np, r.n_cls) * r.ny + r.extra_blocks);
+    KernelTimer kt(ctx, timer);
+    int rl = k3_launch(ctx, fn, nblk, 64 * nwv, lds, a);
+    if (!rl && wave) rl = k3_launch(ctx, fin, (unsigned)np, 256, 0, a);
+    return rl;
+  });
+  if (rc) return rc;
+  a.pdf0 = 0; a.npdf = m->P;
+  if (wave) KHG_LAUNCH(ctx, k3_wave_scalars, dim3(1), dim3(1024), 0, ctx->stream, a, r.cls_lo, r.cls_hi);
+  return KHG_OK;
+}
+// One pass of K3 over the set's resident alignment: all N frames (nsub < 0), or -- the second pass of the split mode -- the nsub frames
+// of the utterances the DP left to the order-faithful decoders (flagged in u->unc_d; their alignments are merged into ali_d by now).
+// npost >= 0 (khg_acc_stats_post): the pass runs over the npost flattened entries in u->pe_* instead of the alignment -- its own
+// sort buffers and bucket bounds, the POST instantiations of the fp32-chain forms (`weight` is unused: every entry carries its own);
+// one_block: ONE work item per pdf whatever its bucket holds (khg_acc_mllt_stats_post).
+static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, float weight, khg_accs* acc, void* comm, int nparts, int64_t nsub,
+                          int64_t npost = -1, bool one_block = false) {
+  int rc = KHG_OK;
+  const bool post = npost >= 0;
+  const int64_t Neff = post ? npost : nsub < 0 ? u->N : nsub;
+  if (!post) {
+    HIPCHK(hipMemsetAsync(u->pdf_count_d, 0, sizeof(int32_t) * (size_t)m->P, ctx->stream));
+    HIPCHK(hipMemsetAsync(u->tid_count_d, 0, sizeof(unsigned long long) * ((size_t)tm->num_tids + 1), ctx->stream));
+  }
+  K3Args a = k3_args(ctx, m, tm, u, acc, weight, post, Neff);
   nparts = std::max(1, std::min(nparts, m->P));
   if (comm && nparts > 1) { rc = ctx_comm_stream(ctx); if (rc) return rc; }
   if (Neff > 0) {
-    const int gb = (int)std::min<int64_t>(4096, (Neff + 255) / 256);
-    {
-      KernelTimer kt(ctx, nsub < 0 ? "k3_bucket" : "k3_bucket_pass2");
-      // KHG_OPT_K3_BUCKET = 1: cursor-bump scatter (bucket order depends on the atomics)
-      if (!post && nsub < 0 && (ctx->opt[KHG_OPT_K3_BUCKET] == 1 || u->N >= (int64_t)INT_MAX)) {
-        KHG_LAUNCH(ctx, k3_count, dim3(gb), dim3(256), 0, ctx->stream, a);
-        KHG_LAUNCH(ctx, k3_scan, dim3(1), dim3(1024), 0, ctx->stream, a);
-        KHG_LAUNCH(ctx, k3_scatter, dim3(gb), dim3(256), 0, ctx->stream, a);
-      } else if (!post && nsub < 0 && ctx->opt[KHG_OPT_K3_BUCKET] == 2 && m->P <= K3_CS_MAXP) {
-        // the library's own stable counting sort (khg_k3_accstats.hip.inc: k3_cs_*; opt-in: 1.27 ms against the radix sort's 0.80 at the
-        // bench size): blocks of CB consecutive frames
-        const int nw = m->P + 1 <= 7168 ? 4 : 2;                      // waves of a placing block: nw x (P + 1 + 1024) counters of LDS
-        int64_t CB = 32768;
-        while (CB > 64 * nw * 4 && (u->N + CB - 1) / CB < 1024) CB /= 2;   // enough blocks to fill the chip on small sets
-        const int nblk = (int)((u->N + CB - 1) / CB);
-        const size_t hist_n = (size_t)nblk * ((size_t)m->P + 1);
-        if (u->cs_hist_n < hist_n) { DEVFREE(u->cs_hist_d); rc = u_alloc(u, &u->cs_hist_d, hist_n); if (rc) return rc; u->cs_hist_n = hist_n; }
-        if (u->cs_tot_n < (size_t)m->P + 1) { DEVFREE(u->cs_tot_d); rc = u_alloc(u, &u->cs_tot_d, (size_t)m->P + 1); if (rc) return rc; u->cs_tot_n = (size_t)m->P + 1; }
-        K3CsArgs c{u->cs_hist_d, u->cs_tot_d, (int32_t)CB, nblk};
-        const bool ldst = tm->num_tids <= K3_LDS_TIDS;
-        const size_t lds_h = sizeof(unsigned int) * ((size_t)m->P + 1 + (ldst ? (size_t)tm->num_tids + 1 : 0));
-        const size_t lds_p = sizeof(unsigned int) * (size_t)nw * ((size_t)m->P + 1 + 1024);     // per-wave counters + the run-head hash tags
-        if (lds_h > 48 * 1024) {
-          HIPCHK(hipFuncSetAttribute((const void*)k3_cs_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
-          HIPCHK(hipFuncSetAttribute((const void*)k3_cs_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
-        }
-        if (lds_p > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k3_cs_place, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-        if (ldst) KHG_LAUNCH(ctx, k3_cs_hist<true>, dim3(nblk), dim3(256), lds_h, ctx->stream, a, c);
-        else KHG_LAUNCH(ctx, k3_cs_hist<false>, dim3(nblk), dim3(256), lds_h, ctx->stream, a, c);
-        KHG_LAUNCH(ctx, k3_cs_scan, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, a, c);
-        KHG_LAUNCH(ctx, k3_cs_starts, dim3(1), dim3(1024), 0, ctx->stream, a, c);
-        KHG_LAUNCH(ctx, k3_cs_place, dim3(nblk), dim3(64 * nw), lds_p, ctx->stream, a, c);
-      } else {
-        // stable sort of (pdf, frame) pairs: frames of a pdf stay in frame order; the bucket boundaries are read
-        // off the sorted keys
-        int bits = 1;
-        while ((1 << bits) <= m->P) ++bits;            // keys are 0..P
-        if (!sort_keys) {
-          rc = u_alloc(u, &sort_keys, (size_t)u->N);
-          if (!rc) rc = u_alloc(u, &sort_keys_out, (size_t)u->N);
-          if (!rc) rc = u_alloc(u, &sort_vals, (size_t)u->N);
-          if (rc) return rc;
-        }
-        size_t need = 0;
-        HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, sort_keys, sort_keys_out, sort_vals,
-                                                  reinterpret_cast<uint32_t*>(a.frame_ids), (int)Neff, 0, bits, ctx->stream));
-        if (need > sort_tmp_bytes) {
-          DEVFREE(sort_tmp);
-          { int rt = u_alloc(u, reinterpret_cast<char**>(&sort_tmp), need); if (rt) return rt; }
-          sort_tmp_bytes = need;
-        }
-        if (post) {
-          // the (pdf, entry) pairs and the weighted transition statistics (khg_k3_post.hip.inc)
-          const bool ldst = tm->num_tids <= K3_LDS_TIDS;
-          if (ldst) KHG_LAUNCH(ctx, k3_post_keys<true>, dim3(std::min(gb, 1024)), dim3(256), sizeof(double) * ((size_t)tm->num_tids + 1), ctx->stream, a, sort_keys, sort_vals);
-          else KHG_LAUNCH(ctx, k3_post_keys<false>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
-        } else if (nsub >= 0) {
-          // the (pdf, frame) pairs of the flagged utterances only, utterances in order: positions from an exclusive sum of their lengths
-          if (!u->sub_off_d) { rc = u_alloc(u, &u->sub_off_d, (size_t)u->n_utt + 1); if (rc) return rc; }
-          KHG_LAUNCH(ctx, k3_sub_scan, dim3(1), dim3(1024), 0, ctx->stream, u->unc_d, u->frame_off_d, u->n_utt, u->sub_off_d);
-          KHG_LAUNCH(ctx, k3_sub_keys, dim3((unsigned)std::min(u->n_utt, 8192)), dim3(64), 0, ctx->stream, a, u->unc_d, u->frame_off_d, u->sub_off_d, u->n_utt, sort_keys, sort_vals);
-        } else if (tm->num_tids <= K3_LDS_TIDS) KHG_LAUNCH(ctx, k3_sort_keys<true>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
-        else KHG_LAUNCH(ctx, k3_sort_keys<false>, dim3(std::min(gb, 1024)), dim3(256), 0, ctx->stream, a, sort_keys, sort_vals);
-        HIPCHK(hipcub::DeviceRadixSort::SortPairs(sort_tmp, need, sort_keys, sort_keys_out, sort_vals,
-                                                  reinterpret_cast<uint32_t*>(a.frame_ids), (int)Neff, 0, bits, ctx->stream));
-        if (post) {
-          K3Args b = a;
-          b.num_tids = -1;        // k3_bounds has no integer counts to fold: k3_post_keys added the weighted ones itself
-          KHG_LAUNCH(ctx, k3_bounds, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, b, sort_keys_out);
-        } else KHG_LAUNCH(ctx, k3_bounds, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, a, sort_keys_out);
-      }
-    }
-    // Work items of the accumulate kernels (k3_make_items): ny_base slices per pdf, more for a pdf whose bucket is far above the
-    // average slice (2 x; silence in real transcripts).  -> the number of blocks to launch for a range of np pdfs (an upper bound
-    // from N and P alone: the bucket sizes stay on the device) in *extra_blocks; parked: the slices park images (wave forms).
-    int64_t k3_extra_blocks = 0;
-    // Work items of one CLASS of pdfs (cls_lo < Gaussians <= cls_hi; the others get none): the form is chosen per pdf, so one pdf
-    // that Split (csrc/diag-gmm.cc:780-851) pushed past 64 Gaussians does not take every other pdf off the wave form.  Two classes
-    // keep their item lists side by side in the same buffers (second = true: the upper halves).
-    auto make_items = [&](int ny_base, bool parked, size_t nsum1, int cls_lo, int cls_hi, bool second) -> int {
-      const int64_t avg = Neff / std::max(1, m->P);
-      // (k3_one_block: no bucket is cut, so every cell of the block receives ONE work item's sum, made in chunk order -- the fp64 atomics
-      //  that end an item then have no second item to race with, and the statistics have the same bits from run to run)
-      const int target = ctx->k3_one_block ? INT_MAX : (int)std::min<int64_t>(1 << 30, std::max<int64_t>(512, 2 * avg / ny_base));
-      const int64_t per_t = Neff / target;
-      k3_extra_blocks = std::min<int64_t>(per_t + m->P, 2 * per_t) + 1;
-      const int64_t max_items = (int64_t)m->P * ny_base + k3_extra_blocks;
-      const int64_t max_slots = !parked ? INT_MAX : ny_base > 1 ? max_items : 2 * per_t + 1;
-      if (max_items >= INT_MAX / 2) return khg_set_error(KHG_E_UNSUPPORTED, "khg_acc_stats: too many work items");
-      if (u->k3_items_n < (size_t)max_items) {
-        DEVFREE(u->k3_items_d);
-        { int ri = u_alloc(u, reinterpret_cast<K3Item**>(&u->k3_items_d), 2 * (size_t)max_items); if (ri) return ri; }
-        u->k3_items_n = (size_t)max_items;
-      }
-      if (u->k3_item_off_n < (size_t)m->P + 1) {
-        DEVFREE(u->k3_item_off_d);
-        int rc2 = u_alloc(u, &u->k3_item_off_d, 2 * ((size_t)m->P + 1));
-        if (rc2) return rc2;
-        u->k3_item_off_n = (size_t)m->P + 1;
-      }
-      if (parked && u->k3_part_n < (size_t)max_slots * nsum1) {
-        DEVFREE(u->k3_part_d);
-        int rc2 = u_alloc(u, &u->k3_part_d, (size_t)max_slots * nsum1);
-        if (rc2) return rc2;
-        u->k3_part_n = (size_t)max_slots * nsum1;
-      }
-      K3Item* items = reinterpret_cast<K3Item*>(u->k3_items_d) + (second ? u->k3_items_n : 0);
-      int32_t* item_off = u->k3_item_off_d + (second ? u->k3_item_off_n : 0);
-      KHG_LAUNCH(ctx, k3_make_items, dim3(1), dim3(1024), 0, ctx->stream, a, ny_base, target, (int)max_items, (int)std::min<int64_t>(max_slots, INT_MAX),
-                         items, item_off, cls_lo, cls_hi);
-      a.items = items; a.item_off = item_off;
-      return KHG_OK;
-    };
-    const int k3form = ctx->opt[KHG_OPT_K3_FORM];     // 1: the chunk-per-block MFMA form for every shape; 2: the VALU form
-    // ---- the wave-local form (pdfs of <= 64 Gaussians at D <= 40): W in LDS + per-wave planes during the tile loop, the fp64 fold image afterwards ----
-    auto run_wave = [&](int cls_lo, int cls_hi, int maxG, void* comm_) -> int {
-      const int nb = (maxG + 15) / 16;
-      // phase A on the fp16 matrix cores where the model-derived scales hold (KHG_K3_PHASEA=f32 keeps the fp32 chain)
-      bool f16a = false;
-      // (pdfs of <= 32 Gaussians keep the fp32 chain: 40 MFMAs per tile are not worth the split, and the two-waves-per-SIMD
-      //  instantiations have no registers for the fp16 W pieces)
-      if (nb >= 3 && ctx->opt[KHG_OPT_K3_PHASE_A] == 0 && ctx->opt[KHG_OPT_K3_PHASE_B] != 1) { rc = k3_phase_a_scales(ctx, const_cast<khg_model*>(m), u, &f16a); if (rc) return rc; }
-      if (f16a) {
-        a.pa_ex = m->k3_ex_d; a.pa_S = m->k3_S;
-        a.pa_scale = std::ldexp(1.0f, m->k3_S); a.pa_inv = std::ldexp(1.0f, -m->k3_S); a.pa_c1 = std::ldexp(1.44269504088896340736f, -m->k3_S);
-      }
-      // phase B on the fp16 matrix cores as well (k3_accumulate_wave16; KHG_OPT_K3_PHASE_B = 2): where phase A's split planes exist
-      // and the weight is an ordinary number
-      const bool f16b = f16a && ctx->opt[KHG_OPT_K3_PHASE_B] == 2 && std::isfinite(weight) && std::fabs(weight) > 1.0e-30f && std::fabs(weight) < 1.0e30f;
-      if (f16b) { a.pb_SG = 13 - std::ilogb(std::fabs(weight)); a.pb_gscale = std::ldexp(1.0f, a.pb_SG); }
-      // fp32 phase A: W + the waves' planes; fp16 phase A: the waves' planes + their split planes; then the fold image
-      const size_t lds = std::max<size_t>(f16a ? sizeof(float) * (4 * 4 * 16 * 20) + 2 * (size_t)(4 * 2 * 16 * K3_XH_ROW)
-                                               : sizeof(float) * ((size_t)nb * 20 * 64 + 4 * 4 * 16 * 20),
-                                          sizeof(double) * ((size_t)nb * 16 * 80 + (size_t)nb * 16));
-      const int64_t avg_tiles = (Neff / std::max(1, m->P) + 15) / 16;
-      int ny = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(32, (avg_tiles + 15) / 16), (4096 + m->P - 1) / m->P));
-      if (ctx->opt[KHG_OPT_K3_NY] > 0) ny = ctx->opt[KHG_OPT_K3_NY];
-      // per-pdf log-like partials (always) and, with several blocks per pdf, the slice images they park
-      const size_t nsum1 = (size_t)nb * 16 * 80 + (size_t)nb * 16 + 1;
-      if (u->k3_llpart_n < (size_t)m->P) {
-        DEVFREE(u->k3_llpart_d);
-        rc = u_alloc(u, &u->k3_llpart_d, (size_t)m->P);
-        if (rc) return rc;
-        u->k3_llpart_n = (size_t)m->P;
-      }
-      rc = make_items(ny, true, nsum1, cls_lo, cls_hi, false);
-      if (rc) return rc;
-      HIPCHK(hipMemsetAsync(u->k3_llpart_d, 0, sizeof(double) * (size_t)m->P, ctx->stream));
-      a.ll_part = u->k3_llpart_d;
-      a.part = u->k3_part_d;
-      const int nparts_ = comm_ ? nparts : 1;
-      for (int part = 0; part < nparts_; ++part) {
-      const int p0 = (int)((int64_t)m->P * part / nparts_), np = (int)((int64_t)m->P * (part + 1) / nparts_) - p0;
-      a.pdf0 = p0; a.npdf = np;
-      const unsigned nblk = (unsigned)((int64_t)np * ny + k3_extra_blocks);
-      {
-      KernelTimer kt(ctx, nsub < 0 ? "k3_accumulate" : "k3_accumulate_pass2");
-      // phase B on the fp64 matrix pipe (products exact, N ranks sum to the one-rank statistics to 1e-12) or on the fp16 matrix
-      // cores (default where they apply)
-      const bool exact_b = true;
-      // k3_accumulate_wave16: per wave two tiles' phase-A planes + the phase-B planes (halves), then the split W operands
-      const size_t lds16 = std::max<size_t>(2 * (size_t)4 * (2 * (2 * 16 * K3_XH_ROW) + 2 * 2 * 40 * 36) + (size_t)nb * 3 * 2 * 64 * 16,
-                                            sizeof(double) * ((size_t)nb * 16 * 80 + (size_t)nb * 16));
-#define K3_WAVE_LAUNCH(NBV)                                                                                            \
-  do {                                                                                                                  \
-    if (f16b) {                                                                                                          \
-      HIPCHK(hipFuncSetAttribute((const void*)k3_accumulate_wave16<NBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16)); \
-      KHG_LAUNCH(ctx, (k3_accumulate_wave16<NBV>), dim3(nblk), dim3(256), lds16, ctx->stream, a);                     \
-    } else if (exact_b && f16a) KHG_LAUNCH(ctx, (k3_accumulate_wave<NBV, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);    \
-    else KHG_LAUNCH(ctx, (k3_accumulate_wave<NBV>), dim3(nblk), dim3(256), lds, ctx->stream, a);                      \
-    KHG_LAUNCH(ctx, (k3_wave_finalize<NBV>), dim3(np), dim3(256), 0, ctx->stream, a);                                 \
-  } while (0)
-      switch (nb) {
-        case 1: K3_WAVE_LAUNCH(1); break;
-        case 2: K3_WAVE_LAUNCH(2); break;
-        case 3: K3_WAVE_LAUNCH(3); break;
-        default: K3_WAVE_LAUNCH(4); break;
-      }
-#undef K3_WAVE_LAUNCH
-      }
-      if (comm_ && nparts_ > 1) { rc = accs_allreduce_pieces(ctx, acc, m, p0, np, comm_, nullptr); if (rc) return rc; }
-      }
-      a.pdf0 = 0; a.npdf = m->P;
-      KHG_LAUNCH(ctx, k3_wave_scalars, dim3(1), dim3(1024), 0, ctx->stream, a, cls_lo, cls_hi);
-      return KHG_OK;
-    };
-    // ---- fp32 + fp64 MFMA form; fewer, longer blocks: the fp64 accumulators stay in registers per block ----
-    auto run_mfma = [&](int cls_lo, int cls_hi, int maxG, int n_cls, bool second, void* comm_) -> int {
-      const int64_t avg_chunks = (Neff / std::max(1, m->P) + K3_CHUNK - 1) / K3_CHUNK;
-      const size_t lds = sizeof(float) * ((size_t)4 * K3_CHUNK * 2 * m->KQ + (post ? 6 : 5) * K3_CHUNK);   // 4 planes [64][KH] + reductions (+ the entries' weights)
-      // slices per pdf: every block ends with one fp64 atomic per accumulator cell (G*(2D+1) of them), so
-      // use as few blocks as still fill the chip (~4096 = 256 CUs x 8 blocks x 2 rounds)
-      // (a class of a few pdfs -- the ones a split has grown -- is cut finer: one block walking a whole bucket is a latency of its own)
-      int ny = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(32, avg_chunks), (4096 + n_cls - 1) / std::max(1, n_cls)));
-      if (ctx->opt[KHG_OPT_K3_NY] > 0) ny = ctx->opt[KHG_OPT_K3_NY];
-      if (ctx->k3_one_block) ny = 1;
-      rc = make_items(ny, false, 0, cls_lo, cls_hi, second);
-      if (rc) return rc;
-      // Both phases on the fp16 matrix cores (k3_accumulate_block16) where the model-derived scales hold and the weight is an ordinary
-      // number (the conditions of the wave form's fp16 phases): <= 128 Gaussians at D <= 80, <= 192 at D <= 40.  KHG_K3_PHASEA=f32 or
-      // KHG_K3_PHASEB=f64 keep the fp32 / fp64 MFMA form.
-      bool b16 = false;
-      if (!post && ctx->opt[KHG_OPT_K3_PHASE_A] == 0 && ctx->opt[KHG_OPT_K3_PHASE_B] == 2 && ((m->KQ == 20 && maxG <= 128) || (m->KQ == 10 && maxG <= 192)) &&
-          std::isfinite(weight) && std::fabs(weight) > 1.0e-30f && std::fabs(weight) < 1.0e30f) {
-        rc = k3_phase_a_scales(ctx, const_cast<khg_model*>(m), u, &b16);
-        if (rc) return rc;
-      }
-      if (b16) {
-        a.pa_ex = m->k3_ex_d; a.pa_S = m->k3_S;
-        a.pa_scale = std::ldexp(1.0f, m->k3_S); a.pa_inv = std::ldexp(1.0f, -m->k3_S); a.pa_c1 = std::ldexp(1.44269504088896340736f, -m->k3_S);
-        a.pb_SG = 13 - std::ilogb(std::fabs(weight)); a.pb_gscale = std::ldexp(1.0f, a.pb_SG);
-      }
-      // split planes of a chunk in both layouts + the softmax's exchange: [2][64][KPAD + 8] + [2][2 XP][72] halves, 5 x 64 floats
-      const size_t kpad = ((size_t)8 * m->KQ + 31) / 32 * 32;
-      // ... or, before the chunk loop, the pdf's parameter rows [2][lanes' Gaussians][D | 1] + the columns' exponents
-      const size_t gp_b16 = maxG <= 64 ? 64 : (maxG <= 128 ? 128 : 192);
-      const size_t lds_b16 = std::max<size_t>(2 * (2 * (size_t)K3_CHUNK * (kpad + 8) + 2 * (size_t)8 * m->KQ * (K3_CHUNK + 8)) + sizeof(float) * 9 * K3_CHUNK,
-                                              sizeof(float) * (2 * gp_b16 * (size_t)(m->D | 1) + 8 * (size_t)m->KQ));
-      const int nparts_ = comm_ ? nparts : 1;
-      for (int part = 0; part < nparts_; ++part) {
-        const int p0 = (int)((int64_t)m->P * part / nparts_), np = (int)((int64_t)m->P * (part + 1) / nparts_) - p0;
-        a.pdf0 = p0; a.npdf = np;
-        const unsigned nblk = (unsigned)((int64_t)std::min(np, n_cls) * ny + k3_extra_blocks);
-        {
-          KernelTimer kt(ctx, nsub < 0 ? "k3_accumulate" : "k3_accumulate_pass2");
-          if (b16) {
-#define K3_B16(KQV, NBWV, NWVV)                                                                                                 \
-  do {                                                                                                                          \
-    HIPCHK(hipFuncSetAttribute((const void*)k3_accumulate_block16<KQV, NBWV, NWVV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b16)); \
-    KHG_LAUNCH(ctx, (k3_accumulate_block16<KQV, NBWV, NWVV>), dim3(nblk), dim3(64 * NWVV), lds_b16, ctx->stream, a);            \
-  } while (0)
-            // (one Gaussian block per wave: < 256 registers, so a block of eight waves runs two per SIMD)
-            if (maxG <= 64) { if (m->KQ == 20) K3_B16(20, 1, 4); else K3_B16(10, 1, 4); }
-            else if (maxG <= 128) { if (m->KQ == 20) K3_B16(20, 1, 8); else K3_B16(10, 1, 8); }
-            else K3_B16(10, 3, 4);         // (four blocks per wave -- 193..256 Gaussians -- spill at 512 registers: the fp32 / fp64 form keeps them)
-#undef K3_B16
-          } else if (post) {
-            if (m->KQ == 10 && maxG <= 64) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 1, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-            else if (m->KQ == 10 && maxG <= 128) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 2, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-            else if (m->KQ == 10 && maxG <= 192) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 3, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-            else if (m->KQ == 10) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 4, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-            else if (maxG <= 64) KHG_LAUNCH(ctx, (k3_accumulate_mfma<20, 1, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-            else KHG_LAUNCH(ctx, (k3_accumulate_mfma<20, 2, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-          } else
-          if (m->KQ == 10 && maxG <= 64) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 1>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-          else if (m->KQ == 10 && maxG <= 128) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 2>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-          else if (m->KQ == 10 && maxG <= 192) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 3>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-          else if (m->KQ == 10) KHG_LAUNCH(ctx, (k3_accumulate_mfma<10, 4>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-          else if (maxG <= 64) KHG_LAUNCH(ctx, (k3_accumulate_mfma<20, 1>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-          else KHG_LAUNCH(ctx, (k3_accumulate_mfma<20, 2>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-        }
-        if (comm_ && nparts_ > 1) { rc = accs_allreduce_pieces(ctx, acc, m, p0, np, comm_, nullptr); if (rc) return rc; }
-      }
-      a.pdf0 = 0; a.npdf = m->P;
-      return KHG_OK;
-    };
-    // ---- the VALU form: any number of Gaussians, any dimension ----
-    auto run_valu = [&](int cls_lo, int cls_hi, int maxG, int n_cls, bool second, void* comm_) -> int {
-      const int64_t avg_chunks = (Neff / std::max(1, m->P) + K3_CHUNK - 1) / K3_CHUNK;
-      const size_t lds = k3_valu_lds(m, maxG, post);
-      if (lds > K3_VALU_LDS_MAX) return khg_set_error(KHG_E_UNSUPPORTED, "khg_acc_stats: pdf too large for the LDS chunk buffers");
-      const void* k3fn = post ? (m->KQ == 10 ? (const void*)k3_accumulate<10, true> : m->KQ == 20 ? (const void*)k3_accumulate<20, true> : (const void*)k3_accumulate<0, true>)
-                              : m->KQ == 10 ? (const void*)k3_accumulate<10> : m->KQ == 20 ? (const void*)k3_accumulate<20> : (const void*)k3_accumulate<0>;
-      if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(k3fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      int ny = (int)std::max<int64_t>(1, std::min<int64_t>(64, (avg_chunks + 3) / 4));
-      if (ctx->k3_one_block) ny = 1;
-      rc = make_items(ny, false, 0, cls_lo, cls_hi, second);
-      if (rc) return rc;
-      const int nparts_ = comm_ ? nparts : 1;
-      for (int part = 0; part < nparts_; ++part) {
-        const int p0 = (int)((int64_t)m->P * part / nparts_), np = (int)((int64_t)m->P * (part + 1) / nparts_) - p0;
-        a.pdf0 = p0; a.npdf = np;
-        const unsigned nblk = (unsigned)((int64_t)std::min(np, n_cls) * ny + k3_extra_blocks);
-        {
-          KernelTimer kt(ctx, nsub < 0 ? "k3_accumulate" : "k3_accumulate_pass2");
-          if (post) {
-            if (m->KQ == 10) KHG_LAUNCH(ctx, (k3_accumulate<10, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-            else if (m->KQ == 20) KHG_LAUNCH(ctx, (k3_accumulate<20, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-            else KHG_LAUNCH(ctx, (k3_accumulate<0, true>), dim3(nblk), dim3(256), lds, ctx->stream, a);
-          } else
-          if (m->KQ == 10) KHG_LAUNCH(ctx, k3_accumulate<10>, dim3(nblk), dim3(256), lds, ctx->stream, a);
-          else if (m->KQ == 20) KHG_LAUNCH(ctx, k3_accumulate<20>, dim3(nblk), dim3(256), lds, ctx->stream, a);
-          else KHG_LAUNCH(ctx, k3_accumulate<0>, dim3(nblk), dim3(256), lds, ctx->stream, a);
-        }
-        if (comm_ && nparts_ > 1) { rc = accs_allreduce_pieces(ctx, acc, m, p0, np, comm_, nullptr); if (rc) return rc; }
-      }
-      a.pdf0 = 0; a.npdf = m->P;
-      return KHG_OK;
-    };
-    // Form per pdf: the wave form takes every pdf of <= 64 Gaussians (D <= 40); what is left -- a few pdfs a split grew, or a model
-    // of wide pdfs throughout -- goes to the chunk-per-block MFMA form (<= 256 Gaussians at D <= 40, <= 128 at D <= 80) or the VALU form.
-    int maxG = 0, maxG_lo = 0, n_hi = 0;
-    for (int p = 0; p < m->P; ++p) {
-      const int Gp = m->gauss_off[p + 1] - m->gauss_off[p];
-      maxG = std::max(maxG, Gp);
-      if (Gp <= 64) maxG_lo = std::max(maxG_lo, Gp); else ++n_hi;
-    }
-    const bool mfma_ok = (maxG <= 128 || (maxG <= 256 && m->KQ == 10)) && k3form != 2 && m->KQ != 0;
-    const bool wave_ok = !post && m->KQ == 10 && k3form == 0 && maxG_lo > 0;       // (the wave forms' fp16 phase B rests on ONE |weight|: 7h)
-    if (wave_ok && n_hi == 0) rc = run_wave(0, INT_MAX, maxG, comm);
-    else if (wave_ok) {
-      rc = run_wave(0, 64, maxG_lo, nullptr);                  // (with an exchange: its pieces follow the second class's kernels)
-      if (!rc) rc = mfma_ok ? run_mfma(64, INT_MAX, maxG, n_hi, true, comm) : run_valu(64, INT_MAX, maxG, n_hi, true, comm);
-    } else if (mfma_ok) rc = run_mfma(0, INT_MAX, maxG, m->P, false, comm);
-    else rc = run_valu(0, INT_MAX, maxG, m->P, false, comm);
+    rc = k3_bucket(ctx, m, tm, u, a, post, nsub, Neff); if (rc) return rc;
+    const K3Plan pl = k3_plan(ctx, m, post, Neff, one_block);
+    // (a mixed call with an exchange: the first class runs without it, the pieces follow the second class's kernels)
+    for (int i = 0; i < pl.nruns && !rc; ++i)
+      rc = k3_run(ctx, m, u, acc, a, pl.run[i], post, nsub < 0 ? "k3_accumulate" : "k3_accumulate_pass2", i + 1 == pl.nruns ? comm : nullptr, nparts);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
-  } else if (comm && nparts > 1) {
-    // a rank without frames launches nothing but takes part in the same collectives, in the same order, as every other rank: the
-    // sequence is a function of (P, nparts) only
-    for (int part = 0; part < nparts; ++part) {
-      const int p0 = (int)((int64_t)m->P * part / nparts), np = (int)((int64_t)m->P * (part + 1) / nparts) - p0;
-      rc = accs_allreduce_pieces(ctx, acc, m, p0, np, comm, nullptr);
-      if (rc) return rc;
-    }
+  } else {
+    // a rank without frames launches nothing but takes part in the same collectives, in the same order, as every other rank
+    rc = k3_for_ranges(ctx, m, acc, nparts > 1 ? comm : nullptr, nparts, [](int, int) { return (int)KHG_OK; }); if (rc) return rc;
   }
   if (comm) {
     // the rest of the block: all of it when nothing was pipelined, else the transition counts and the scalars; then the kernels'
@@ -578,7 +573,7 @@ extern "C" int khg_acc_stats_reduce(khg_ctx* ctx, const khg_model* m, const khg_
 // gmm-acc-stats and gmm-acc-stats2 (7k): every check on the host first, then flatten -> bucket -> accumulate on the
 // context's stream -- once into `acc`, or (acc2 != nullptr) the positive entries into `acc` and the negated negative ones into `acc2`.
 static int acc_stats_post_impl(const std::string& name, khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale,
-                               khg_accs* acc, khg_accs* acc2, bool two) {
+                               khg_accs* acc, khg_accs* acc2, bool two, bool one_block = false) {
   const std::string who = name + ": ";
   if (ctx_dead(ctx) || !m || !tm || !u || !p || !acc || (two && !acc2)) return khg_set_error(KHG_E_ARG, who + "bad arguments");
   if (two && acc == acc2) return khg_set_error(KHG_E_ARG, who + "num_accs and den_accs are the same block");
@@ -616,14 +611,17 @@ static int acc_stats_post_impl(const std::string& name, khg_ctx* ctx, const khg_
   }
   // (two blocks: the flattened entries are made twice, once per sign; the stream orders the second flatten behind the first pass)
   rc = posteriors_flatten(ctx, p, u->frame_off_d, (double)scale, tm->num_tids, u->pe_row_d, u->pe_tid_d, u->pe_w_d, two ? 1 : 0);
-  if (!rc) rc = acc_stats_pass(ctx, m, tm, u, 1.0f, acc, nullptr, 1, -1, E);
+  if (!rc) rc = acc_stats_pass(ctx, m, tm, u, 1.0f, acc, nullptr, 1, -1, E, one_block);
   if (rc || !two) return rc;
   rc = posteriors_flatten(ctx, p, u->frame_off_d, (double)scale, tm->num_tids, u->pe_row_d, u->pe_tid_d, u->pe_w_d, -1);
-  if (!rc) rc = acc_stats_pass(ctx, m, tm, u, 1.0f, acc2, nullptr, 1, -1, E);
+  if (!rc) rc = acc_stats_pass(ctx, m, tm, u, 1.0f, acc2, nullptr, 1, -1, E, one_block);
   return rc;
 }
 extern "C" int khg_acc_stats_post(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale, khg_accs* acc) {
   return acc_stats_post_impl("khg_acc_stats_post", ctx, m, tm, u, p, scale, acc, nullptr, false);
+}
+int k3_acc_stats_post_one_block(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale, khg_accs* acc) {
+  return acc_stats_post_impl("khg_acc_stats_post", ctx, m, tm, u, p, scale, acc, nullptr, false, true);
 }
 extern "C" int khg_acc_stats_post2(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_posteriors* p, float scale, khg_accs* num_accs,
                                    khg_accs* den_accs) {
