@@ -1136,6 +1136,74 @@ int khg_build_tree(int32_t N, int32_t P, int32_t dim, int64_t num_keys, const in
                    double thresh, int32_t max_leaves, double cluster_thresh, double var_floor, unsigned char *tree_h, int64_t tree_cap,
                    int64_t *tree_bytes, double *objf_impr, double *cluster_loss, int32_t *num_leaves, int32_t *num_removed);
 
+/* ---- CMVN and delta features (compute-cmvn-stats, apply-cmvn, add-deltas) ------------------------------------------- */
+/* The reference has no feature pipeline: the rule in DESIGN.md 7p is the specification (tests/feat_ref.py restates it).  Notation:
+ * dim = the set's feature dimension, utt2spk_h[u] = s in [0, n_spk) or < 0 for "no speaker" (per-utterance CMVN: utt2spk = 0 ..
+ * n_utt - 1).  The delta kernel stages 64 rows of an utterance with a halo of order x window rows each side in LDS:
+ * 4 (64 + 2 order window) dim bytes, at most KHG_FEAT_TILE_LDS_BYTES (dim 128, order 3, window 4 take 44 KiB); above:
+ * KHG_E_UNSUPPORTED. */
+#define KHG_FEAT_TILE_LDS_BYTES 65536
+#define KHG_CMVN_OK 0            /* the normaliser was computed                                                          */
+#define KHG_CMVN_NO_DATA 1       /* count < 1: offset 0, scale 1                                                         */
+#define KHG_CMVN_NONFINITE 2     /* a scale or an offset that is NaN or infinite: offset 0, scale 1                      */
+/* Kaldi's CMVN statistics for n_spk speakers, resident on the device, fp64, in Kaldi's layout stats[n_spk][2][dim + 1]:
+ * [s][0][d] = sum x[d], [s][0][dim] = the frame count, [s][1][d] = sum x[d] x[d], [s][1][dim] = 0.  download synchronises (deferred
+ * kernel errors: KHG_E_RUNTIME); upload replaces the contents.  add: dst += (double)scale * src elementwise (one product, one add),
+ * asynchronous; the handles must agree in speakers and dimension and belong to `ctx` (KHG_E_ARG). */
+typedef struct khg_cmvn_stats khg_cmvn_stats;
+int khg_cmvn_stats_create(khg_ctx *ctx, int32_t n_spk, int32_t dim, khg_cmvn_stats **out);
+int khg_cmvn_stats_destroy(khg_cmvn_stats *s);
+int khg_cmvn_stats_zero(khg_ctx *ctx, khg_cmvn_stats *s);
+int khg_cmvn_stats_download(khg_ctx *ctx, const khg_cmvn_stats *s, double *stats_h);
+int khg_cmvn_stats_upload(khg_ctx *ctx, khg_cmvn_stats *s, const double *stats_h);
+int khg_cmvn_stats_add(khg_ctx *ctx, khg_cmvn_stats *dst, float scale, const khg_cmvn_stats *src);
+/* One 1024-frame slice of a speaker parks 2 dim doubles; a chunk of `frames` frames (default and most 2^24, at least one slice) holds
+ * frames / 1024 slices, short ones counting as whole.  The statistics do not depend on it, bit for bit.
+ * num_chunks: how many chunks the last accumulation into the handle ran (tests). */
+int khg_cmvn_stats_set_chunk_frames(khg_cmvn_stats *s, int64_t frames);
+int khg_cmvn_stats_num_chunks(const khg_cmvn_stats *s, int32_t *n_chunks);
+/* compute-cmvn-stats on the set's resident rows.  Every row of an utterance with utt2spk_h[u] = s >= 0 adds, widened to double,
+ * x[d] and x[d] x[d] (exact in a double) to speaker s, and 1 to its count.  The order of the sum is fixed by the speaker's own frame
+ * list (its utterances in set order, frames ascending), cut every 1024 frames into slices.  A slice of n frames, with R = 256 / dim
+ * chains (1 for dim > 256): chain r starts at +0 and adds frames r, r + R, .. of the slice in order; the R chains are added in order
+ * 0 .. R - 1; the slices are added in slice order, starting from +0.  No atomics: a speaker's statistics have the same bits whatever
+ * else is in the call, whatever the chunk size, and from run to run.  An utterance with utt2spk < 0 and one without frames add
+ * nothing.  Adds the call's sums into `stats`; asynchronous on the context's stream once the plan is uploaded.  Before anything is
+ * launched (the handle keeps its bits): KHG_E_ARG for a utt2spk value >= n_spk, statistics of another dimension or context. */
+int khg_acc_cmvn_stats(khg_ctx *ctx, khg_utts *u, const int32_t *utt2spk_h, khg_cmvn_stats *stats);
+/* Kaldi's ApplyCmvn normaliser from host statistics laid out as khg_cmvn_stats_download gives them; needs no device.  In double, one
+ * operation at a time: count = stats[s][0][dim], mean = stats[s][0][d] / count; without norm_vars scale = 1, offset = -mean; with it
+ * var = stats[s][1][d] / count - mean mean, raised to the floor 1e-20, scale = 1 / sqrt(var), offset = -(mean scale); with reverse
+ * scale = sqrt(var) (1 without norm_vars), offset = mean.  norm_means == 0 (Kaldi's --norm-means=false) leaves the mean in: the
+ * offset is 0 and the scale and the status are what they are with norm_means (the variance is taken about the true mean).  Both narrowed to float: norm_h[n_spk][2][dim], [s][0][d] = offset, [s][1][d] =
+ * scale.  status_h[n_spk] (may be NULL): KHG_CMVN_*; a speaker that is not OK gets offset 0 and scale 1 and is to be treated as
+ * utt2spk < 0 (khg_utts_apply_cmvn and khg_utts_add_deltas do so when given the statuses). */
+int khg_cmvn_compute(int32_t n_spk, int32_t dim, const double *stats_h, int32_t norm_means, int32_t norm_vars, int32_t reverse,
+                     float *norm_h, int32_t *status_h);
+/* Kaldi's DeltaFeatures coefficient tables, in float: scales[0] = [1]; for order i, with prev = scales[i - 1] of half-width po, cur
+ * of half-width po + window starts at 0, normalizer = 0; for j = -window .. window ascending: normalizer += (float)(j j), and for
+ * k = -po .. po ascending: cur[j + k] += (float)j * prev[k] (one float product, one float add); then every element is multiplied by
+ * (float)(1.0 / normalizer).  scales_h: the tables one after the other, table i of 2 i window + 1 floats at offset
+ * i + window i (i - 1): (order + 1) + window order (order + 1) floats.  KHG_E_ARG for order < 0 or window < 1.  Host only. */
+int khg_delta_scales(int32_t order, int32_t window, float *scales_h);
+/* apply-cmvn on the set's resident rows: y = fl(fl(x scale) + offset) in float, two roundings, never fused, with the normaliser
+ * norm_h[n_spk][2][dim] of the utterance's speaker.  An utterance with utt2spk_h[u] < 0, or whose speaker's status_h (may be NULL:
+ * every speaker OK) is not KHG_CMVN_OK, is copied bit for bit.  With out_d the rows go to that device buffer (the set's size) and
+ * the set is untouched; with out_d == NULL the set's own rows are rewritten in place (borrowed device features included) and the
+ * set is told so, as by khg_utts_features_changed.  It stages nothing: any dim.  KHG_E_ARG for a utt2spk value >= n_spk.
+ * Synchronous. */
+int khg_utts_apply_cmvn(khg_ctx *ctx, khg_utts *u, int32_t n_spk, const int32_t *utt2spk_h, const float *norm_h, const int32_t *status_h,
+                        float *out_d);
+/* add-deltas on the set's resident rows, out of place: for frame t of an utterance of T frames, block i = 0 .. order, H_i = i window:
+ * out[t][i dim + d] = y with y = 0, then for j = -H_i .. H_i ascending and scales[i][j] != 0: y = fmaf(scales[i][j],
+ * v[clamp(t + j, 0, T - 1)][d], y) -- zero coefficients are skipped, not multiplied; the clamp is inside the utterance, a
+ * neighbouring utterance's row is never read.  v = x, or with norm_h != NULL the CMVN value of x as khg_utts_apply_cmvn forms it
+ * (n_spk, utt2spk_h, status_h as there; all ignored with norm_h == NULL), applied while the tile is staged and never written to
+ * memory.  out_d: a caller-owned device buffer of [rows of the set][dim (order + 1)] floats; the set is untouched.  KHG_E_ARG for
+ * order < 0, window < 1, a utt2spk value >= n_spk; KHG_E_UNSUPPORTED, naming the limit, above KHG_FEAT_TILE_LDS_BYTES.  Synchronous. */
+int khg_utts_add_deltas(khg_ctx *ctx, khg_utts *u, int32_t order, int32_t window, int32_t n_spk, const int32_t *utt2spk_h,
+                        const float *norm_h, const int32_t *status_h, float *out_d);
+
 #ifdef __cplusplus
 }
 #endif

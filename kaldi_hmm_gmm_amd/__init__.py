@@ -19,7 +19,7 @@ from .align import get_raw_lattice_faster_batch, get_raw_lattice_faster_device_b
 from .context_dep import (ContextDependency, ContextDependencyInterface, monophone_context_dependency,  # noqa: F401
                           monophone_context_dependency_shared)
 from .device import (ALIGN_DONE, ALIGN_ERROR, ALIGN_EXACT_DP, ALIGN_FALLBACK, ALIGN_RETRIED, Comm, Context, DeviceAccs,  # noqa: F401
-                     DecodingGraph, DeviceFmllrStats, DeviceLdaStats, DeviceMlltStats, DeviceModel, DeviceTransitions, DeviceTreeStats,
+                     DecodingGraph, DeviceCmvnStats, DeviceFmllrStats, DeviceLdaStats, DeviceMlltStats, DeviceModel, DeviceTransitions, DeviceTreeStats,
                      UtteranceSet)
 from .diag_gmm import AmDiagGmm, DiagGmm  # noqa: F401
 from .fst import StdArc, StdVectorFst, modify_graph_for_careful_alignment  # noqa: F401
@@ -39,6 +39,8 @@ from .mllt import (MLLT_MAX_DIM, MLLT_OK, MLLT_SINGULAR, est_mllt, gmm_acc_mllt,
                    mllt_compute)
 from .lda import (LDA_MAX_SPLICED_DIM, LDA_OK, LDA_SINGULAR, acc_lda, acc_lda_batch, compose_with_lda, est_lda, lda_compute,  # noqa: F401
                   splice_feats, splice_transform_feats, splice_transform_feats_batch)
+from .feat import (CMVN_NO_DATA, CMVN_NONFINITE, CMVN_OK, FEAT_TILE_LDS_BYTES, add_deltas, add_deltas_batch, apply_cmvn,  # noqa: F401
+                   apply_cmvn_batch, cmvn_compute, compute_cmvn_stats, compute_cmvn_stats_batch, delta_scales)
 from .tree import (TREE_MAX_CONTEXT, TREE_MAX_PDF_CLASS, TREE_MAX_PHONE, TREE_STATUS_MIXED_PHONES, TREE_STATUS_NO_ALI,  # noqa: F401
                    TREE_STATUS_OPEN_END, acc_tree_stats, acc_tree_stats_batch, build_tree, convert_ali, gmm_init_model, leaf_stats,
                    pdf_class_questions, split_to_phones, tid_tables)

@@ -325,6 +325,19 @@ SIGNATURES = {
     "khg_build_tree": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, c_i32p, c_f64p, c_f64p, c_f64p, C.c_int32, c_i32p, c_i64p, c_i64p, c_i32p, C.c_int32,
                                  c_i64p, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p, C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_ubyte), C.c_int64,
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), c_i32p, c_i32p]),
+    "khg_cmvn_stats_create": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(vp)]),
+    "khg_cmvn_stats_destroy": (C.c_int, [vp]),
+    "khg_cmvn_stats_zero": (C.c_int, [vp, vp]),
+    "khg_cmvn_stats_download": (C.c_int, [vp, vp, c_f64p]),
+    "khg_cmvn_stats_upload": (C.c_int, [vp, vp, c_f64p]),
+    "khg_cmvn_stats_add": (C.c_int, [vp, vp, C.c_float, vp]),
+    "khg_cmvn_stats_set_chunk_frames": (C.c_int, [vp, C.c_int64]),
+    "khg_cmvn_stats_num_chunks": (C.c_int, [vp, c_i32p]),
+    "khg_acc_cmvn_stats": (C.c_int, [vp, vp, c_i32p, vp]),
+    "khg_cmvn_compute": (C.c_int, [C.c_int32, C.c_int32, c_f64p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_i32p]),
+    "khg_delta_scales": (C.c_int, [C.c_int32, C.c_int32, c_f32p]),
+    "khg_utts_apply_cmvn": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_f32p, c_i32p, vp]),
+    "khg_utts_add_deltas": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, c_i32p, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

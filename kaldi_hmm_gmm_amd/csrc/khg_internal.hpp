@@ -5,7 +5,8 @@
 // posteriors: khg_lattices / khg_posteriors stay private to it), khg_k3.hip (accumulators + statistics), khg_c1.hip (RCCL exchange),
 // khg_k4.hip (device M-step), khg_fmllr.hip (fMLLR statistics and feature transform, MLLT statistics and gmm-transform-means: khg_fmllr_stats / khg_mllt_stats stay private to it),
 // khg_lda.hip (LDA statistics on spliced features and the fused splice-and-project: khg_lda_stats stays private to it),
-// khg_tree.hip (decision-tree statistics from the resident alignment: khg_tree_stats stays private to it).  gfx950 only.
+// khg_tree.hip (decision-tree statistics from the resident alignment: khg_tree_stats stays private to it),
+// khg_feat.hip (CMVN statistics, apply-cmvn and add-deltas on the resident rows: khg_cmvn_stats stays private to it).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 

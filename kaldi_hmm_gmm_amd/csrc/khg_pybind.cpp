@@ -510,6 +510,30 @@ struct KLdaStats {
   int num_chunks() { int32_t n = 0; Check(khg_lda_stats_num_chunks(h, &n)); return n; }
 };
 
+// CMVN statistics per speaker resident in HBM (khg_cmvn_stats)
+struct KCmvnStats {
+  khg_cmvn_stats* h = nullptr;
+  py::object ctx_obj;
+  KContext* ctx;
+  int n_spk = 0, dim = 0;
+  KCmvnStats(py::object ctx_o, int s, int d) : ctx_obj(ctx_o), ctx(ctx_o.cast<KContext*>()), n_spk(s), dim(d) { Check(khg_cmvn_stats_create(ctx->h, s, d, &h)); }
+  ~KCmvnStats() { close(); }
+  void close() { if (h) { khg_cmvn_stats_destroy(h); h = nullptr; } }
+  void zero() { Check(khg_cmvn_stats_zero(ctx->h, h)); }
+  Arr<double> download() {
+    Arr<double> st({(py::ssize_t)n_spk, (py::ssize_t)2, (py::ssize_t)dim + 1});
+    Check(NoGil([&] { return khg_cmvn_stats_download(ctx->h, h, st.mutable_data()); }));
+    return st;
+  }
+  void upload(Arr<double> st) {
+    if (st.size() != (py::ssize_t)n_spk * 2 * (dim + 1)) throw py::value_error("DeviceCmvnStats.upload: stats [n_spk, 2, dim + 1]");
+    Check(NoGil([&] { return khg_cmvn_stats_upload(ctx->h, h, st.data()); }));
+  }
+  void add(float scale, KCmvnStats& src) { Check(khg_cmvn_stats_add(ctx->h, h, scale, src.h)); }
+  void set_chunk_frames(int64_t frames) { Check(khg_cmvn_stats_set_chunk_frames(h, frames)); }
+  int num_chunks() { int32_t n = 0; Check(khg_cmvn_stats_num_chunks(h, &n)); return n; }
+};
+
 // decision-tree statistics resident in HBM (khg_tree_stats)
 struct KTreeStats {
   khg_tree_stats* h = nullptr;
@@ -948,6 +972,44 @@ struct KUtts {
     float* od = out.is_none() ? nullptr : reinterpret_cast<float*>(out.cast<uintptr_t>());
     Check(NoGil([&] { return khg_utts_transform_feats(ctx->h, h, n_spk, utt2spk.data(), wh, wd, od); }));
   }
+  // compute-cmvn-stats (khg_acc_cmvn_stats): one speaker number per utterance (< 0: none)
+  void acc_cmvn_stats(Arr<int32_t> utt2spk, KCmvnStats& stats) {
+    if (utt2spk.size() != n_utt) throw py::value_error("acc_cmvn_stats: one speaker per utterance");
+    if (!stats.h) throw py::value_error("acc_cmvn_stats: the DeviceCmvnStats are closed");
+    Check(NoGil([&] { return khg_acc_cmvn_stats(ctx->h, h, utt2spk.data(), stats.h); }));
+  }
+  // the normaliser arguments of apply_cmvn / add_deltas: norm [n_spk, 2, dim], one speaker per utterance, status [n_spk] or None
+  void norm_args(const char* who, const Arr<float>& norm, const Arr<int32_t>& utt2spk, const py::object& status, Arr<int32_t>* st, const int32_t** sp) {
+    if (norm.ndim() != 3 || norm.shape(1) != 2 || norm.shape(2) != dim) throw py::value_error(std::string(who) + ": norm must be [n_spk, 2, dim]");
+    if (utt2spk.size() != n_utt) throw py::value_error(std::string(who) + ": one speaker per utterance");
+    *sp = nullptr;
+    if (!status.is_none()) {
+      *st = status.cast<Arr<int32_t>>();
+      if (st->size() != norm.shape(0)) throw py::value_error(std::string(who) + ": one status per speaker");
+      *sp = st->data();
+    }
+  }
+  // apply-cmvn (khg_utts_apply_cmvn): out: a device pointer for the normalised rows, or None for the set's own rows in place
+  void apply_cmvn(Arr<int32_t> utt2spk, Arr<float> norm, py::object status, py::object out) {
+    Arr<int32_t> st;
+    const int32_t* sp = nullptr;
+    norm_args("apply_cmvn", norm, utt2spk, status, &st, &sp);
+    float* od = out.is_none() ? nullptr : reinterpret_cast<float*>(out.cast<uintptr_t>());
+    Check(NoGil([&] { return khg_utts_apply_cmvn(ctx->h, h, (int32_t)norm.shape(0), utt2spk.data(), norm.data(), sp, od); }));
+  }
+  // add-deltas (khg_utts_add_deltas): out: a device pointer for [rows, dim (order + 1)] floats; norm None: no CMVN
+  void add_deltas(int order, int window, uintptr_t out, py::object norm, py::object utt2spk, py::object status) {
+    if (norm.is_none()) {
+      Check(NoGil([&] { return khg_utts_add_deltas(ctx->h, h, order, window, 0, nullptr, nullptr, nullptr, reinterpret_cast<float*>(out)); }));
+      return;
+    }
+    if (utt2spk.is_none()) throw py::value_error("add_deltas: a normaliser needs utt2spk");
+    Arr<float> na = norm.cast<Arr<float>>();
+    Arr<int32_t> ua = utt2spk.cast<Arr<int32_t>>(), st;
+    const int32_t* sp = nullptr;
+    norm_args("add_deltas", na, ua, status, &st, &sp);
+    Check(NoGil([&] { return khg_utts_add_deltas(ctx->h, h, order, window, (int32_t)na.shape(0), ua.data(), na.data(), sp, reinterpret_cast<float*>(out)); }));
+  }
 };
 
 }  // namespace
@@ -1069,6 +1131,10 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("_acc_tree_stats", &KUtts::acc_tree_stats, py::arg("tid2phone"), py::arg("tid2pdf_class"), py::arg("tid_flags"), py::arg("ci_phones"), py::arg("stats"))
       .def("splice_transform_feats", &KUtts::splice_transform_feats, py::arg("left"), py::arg("right"), py::arg("M"), py::arg("out"))
       .def("transform_feats", &KUtts::transform_feats, py::arg("utt2spk"), py::arg("W"), py::arg("out") = py::none(), py::arg("n_spk") = 0)
+      .def("acc_cmvn_stats", &KUtts::acc_cmvn_stats, py::arg("utt2spk"), py::arg("stats"))
+      .def("apply_cmvn", &KUtts::apply_cmvn, py::arg("utt2spk"), py::arg("norm"), py::arg("status") = py::none(), py::arg("out") = py::none())
+      .def("add_deltas", &KUtts::add_deltas, py::arg("order"), py::arg("window"), py::arg("out"), py::arg("norm") = py::none(), py::arg("utt2spk") = py::none(),
+           py::arg("status") = py::none())
       .def("close", &KUtts::close);
 
   py::class_<KFmllrStats>(m, "DeviceFmllrStats")
@@ -1102,6 +1168,16 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def("add", &KLdaStats::add, py::arg("scale"), py::arg("src"))
       .def("set_chunk_frames", &KLdaStats::set_chunk_frames, py::arg("frames")).def("num_chunks", &KLdaStats::num_chunks)
       .def("close", &KLdaStats::close);
+
+  py::class_<KCmvnStats>(m, "DeviceCmvnStats")
+      .def(py::init<py::object, int, int>(), py::arg("ctx"), py::arg("n_spk"), py::arg("dim"))
+      .def_property_readonly("h", [](KCmvnStats& x) { return reinterpret_cast<uintptr_t>(x.h); })
+      .def_readonly("ctx", &KCmvnStats::ctx_obj).def_readonly("n_spk", &KCmvnStats::n_spk).def_readonly("dim", &KCmvnStats::dim)
+      .def("zero", &KCmvnStats::zero).def("download", &KCmvnStats::download)
+      .def("upload", &KCmvnStats::upload, py::arg("stats"))
+      .def("add", &KCmvnStats::add, py::arg("scale"), py::arg("src"))
+      .def("set_chunk_frames", &KCmvnStats::set_chunk_frames, py::arg("frames")).def("num_chunks", &KCmvnStats::num_chunks)
+      .def("close", &KCmvnStats::close);
 
   py::class_<KTreeStats>(m, "DeviceTreeStats", py::dynamic_attr())
       .def(py::init<py::object, int, int, int>(), py::arg("ctx"), py::arg("dim"), py::arg("N") = 3, py::arg("P") = 1)
@@ -1191,6 +1267,32 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
   }, py::arg("zero_acc"), py::arg("first_acc"), py::arg("total_second_acc"), py::arg("target_dim") = 40, py::arg("remove_offset") = false,
      py::arg("within_class_factor") = 1.0, "LdaEstimate::Estimate on host statistics (khg_lda_compute; DESIGN.md 7n)");
   m.attr("LDA_OK") = KHG_LDA_OK; m.attr("LDA_SINGULAR") = KHG_LDA_SINGULAR; m.attr("LDA_MAX_SPLICED_DIM") = KHG_LDA_MAX_SPLICED_DIM;
+  m.def("cmvn_compute", [](Arr<double> stats, bool norm_means, bool norm_vars, bool reverse) {
+    if (stats.ndim() != 3 || stats.shape(1) != 2 || stats.shape(2) < 2) throw py::value_error("cmvn_compute: stats [n_spk, 2, dim + 1]");
+    const py::ssize_t S = stats.shape(0), D = stats.shape(2) - 1;
+    Arr<float> norm({S, (py::ssize_t)2, D});
+    Arr<int32_t> status({S});
+    Check(NoGil([&] { return khg_cmvn_compute((int32_t)S, (int32_t)D, stats.data(), norm_means ? 1 : 0, norm_vars ? 1 : 0, reverse ? 1 : 0, norm.mutable_data(),
+                                              status.mutable_data()); }));
+    py::dict d;
+    d["norm"] = norm; d["status"] = status;
+    return d;
+  }, py::arg("stats"), py::arg("norm_means") = true, py::arg("norm_vars") = false, py::arg("reverse") = false,
+     "ApplyCmvn's offsets and scales from host statistics (khg_cmvn_compute; DESIGN.md 7p)");
+  m.def("delta_scales", [](int order, int window) {
+    if (order < 0 || window < 1) throw py::value_error("delta_scales: order must be >= 0 and window >= 1");
+    std::vector<float> flat((size_t)(order + 1) + (size_t)window * order * (order + 1));
+    Check(khg_delta_scales(order, window, flat.data()));
+    py::list out;
+    for (int i = 0; i <= order; ++i) {
+      Arr<float> a({(py::ssize_t)(2 * i * window + 1)});
+      std::memcpy(a.mutable_data(), flat.data() + i + (size_t)window * i * (i - 1), sizeof(float) * (size_t)a.size());
+      out.append(a);
+    }
+    return out;
+  }, py::arg("order"), py::arg("window"), "DeltaFeatures' coefficient tables, one float32 array per order 0 .. order (khg_delta_scales; DESIGN.md 7p)");
+  m.attr("CMVN_OK") = KHG_CMVN_OK; m.attr("CMVN_NO_DATA") = KHG_CMVN_NO_DATA; m.attr("CMVN_NONFINITE") = KHG_CMVN_NONFINITE;
+  m.attr("FEAT_TILE_LDS_BYTES") = KHG_FEAT_TILE_LDS_BYTES;
   m.def("build_tree", [](int N, int P, Arr<int32_t> keys, Arr<double> cnt, Arr<double> x, Arr<double> x2, Arr<int32_t> qkeys, Arr<int64_t> qkey_off, Arr<int64_t> q_off,
                          Arr<int32_t> q_vals, Arr<int64_t> set_off, Arr<int32_t> set_phones, Arr<int32_t> share_roots, Arr<int32_t> do_split, Arr<int32_t> p2n, double thresh,
                          int max_leaves, double cluster_thresh, double var_floor) {
