@@ -1204,6 +1204,70 @@ int khg_utts_apply_cmvn(khg_ctx *ctx, khg_utts *u, int32_t n_spk, const int32_t 
 int khg_utts_add_deltas(khg_ctx *ctx, khg_utts *u, int32_t order, int32_t window, int32_t n_spk, const int32_t *utt2spk_h,
                         const float *norm_h, const int32_t *status_h, float *out_d);
 
+/* ---- MFCC and filterbank features from waveforms (compute-mfcc-feats, compute-fbank-feats) --------------------------- */
+#define KHG_FE_MFCC 0
+#define KHG_FE_FBANK 1
+#define KHG_WIN_POVEY 0
+#define KHG_WIN_HAMMING 1
+#define KHG_WIN_HANNING 2
+#define KHG_WIN_RECTANGULAR 3
+#define KHG_WIN_BLACKMAN 4
+#define KHG_WAVE_F32 0           /* samples are float (Kaldi's scale: +-32768)                                           */
+#define KHG_WAVE_I16 1           /* samples are int16, converted exactly                                                 */
+#define KHG_FE_TILE_FRAMES 16    /* frames of one utterance that one workgroup takes                                     */
+/* One struct for both tools, Kaldi's option names.  Refused with KHG_E_UNSUPPORTED, naming the option: dither != 0,
+ * round_to_power_of_two == 0, vtln_warp != 1, htk_compat != 0, a padded window outside {256, 512, 1024}, num_mel_bins outside
+ * 3 .. 128, num_ceps > num_mel_bins (MFCC).  KHG_E_ARG for values that make no sense (an unknown kind or window, a frame shift
+ * below one sample, a frame below two, low_freq / high_freq outside 0 .. Nyquist or crossed, a value that is not finite). */
+typedef struct khg_frontend_opts {
+  int32_t kind;                  /* KHG_FE_MFCC                                                                           */
+  float samp_freq;               /* 16000                                                                                 */
+  float frame_length_ms;         /* 25                                                                                    */
+  float frame_shift_ms;          /* 10                                                                                    */
+  float preemph_coeff;           /* 0.97                                                                                  */
+  int32_t remove_dc_offset;      /* 1                                                                                     */
+  int32_t window_type;           /* KHG_WIN_POVEY                                                                         */
+  float blackman_coeff;          /* 0.42                                                                                  */
+  int32_t snip_edges;            /* 1                                                                                     */
+  int32_t round_to_power_of_two; /* 1 (0: refused)                                                                        */
+  float dither;                  /* 0 (Kaldi: 1; anything else than 0 is refused -- dither is random)                     */
+  int32_t num_mel_bins;          /* 23                                                                                    */
+  float low_freq;                /* 20                                                                                    */
+  float high_freq;               /* 0: Nyquist; <= 0: Nyquist is added                                                    */
+  float vtln_warp;               /* 1 (anything else: refused)                                                            */
+  int32_t htk_compat;            /* 0 (1: refused)                                                                        */
+  int32_t num_ceps;              /* 13 (MFCC)                                                                             */
+  float cepstral_lifter;         /* 22 (MFCC; 0: none)                                                                    */
+  int32_t use_energy;            /* 0: MFCC keeps C0, FBANK has no energy column; 1: column 0 is the log-energy           */
+  int32_t raw_energy;            /* 1: the energy before pre-emphasis and windowing                                       */
+  float energy_floor;            /* 0: none                                                                               */
+  int32_t use_log_fbank;         /* 1 (FBANK)                                                                             */
+  int32_t use_power;             /* 1 (FBANK; 0: the magnitude spectrum)                                                  */
+} khg_frontend_opts;
+void khg_frontend_opts_default(khg_frontend_opts *o);
+/* The sizes the options imply; host only.  dims_h[8]: L (samples of a frame), S (samples of a shift), N (the padded window), the
+ * number of mel bins, of cepstra (0 for FBANK), of output columns, of mel weights (the sum of the filters' lengths), 0. */
+int khg_frontend_dims(const khg_frontend_opts *o, int32_t *dims_h);
+/* Frames of an utterance of n_samples; host only.  snip_edges: 0 below L, else 1 + (n - L) / S; otherwise (n + S / 2) / S. */
+int khg_frontend_num_frames(const khg_frontend_opts *o, int64_t n_samples, int64_t *num_frames);
+/* The tables of DESIGN.md 7q, computed in double and narrowed once; host only.  Every buffer may be NULL.  window_h[L], mel_off_h /
+ * mel_len_h[bins] (a filter's first spectrum bin and its run), mel_w_h[sum of the lengths], dct_h[num_ceps][bins], lifter_h[num_ceps],
+ * twiddle_h[N / 2][2] (cos, -sin of 2 pi k / N). */
+int khg_frontend_tables(const khg_frontend_opts *o, float *window_h, int32_t *mel_off_h, int32_t *mel_len_h, float *mel_w_h, float *dct_h,
+                        float *lifter_h, float *twiddle_h);
+/* The tables resident on the device. */
+typedef struct khg_frontend khg_frontend;
+int khg_frontend_create(khg_ctx *ctx, const khg_frontend_opts *o, khg_frontend **out);
+int khg_frontend_destroy(khg_frontend *fe);
+/* Features of n_utt waveforms: utterance u owns samples [sample_off_h[u], sample_off_h[u + 1]) of samples_h (host) or samples_d
+ * (device) -- exactly one of the two is given --, of sample_type KHG_WAVE_*.  frame_off_h[n_utt + 1] (out): the rows' prefix sums
+ * (khg_frontend_num_frames of every utterance); out_d: a caller-owned device buffer of [rows][output columns] floats.  With
+ * out_d == NULL only frame_off_h is filled, so that the caller can size the buffer.  A frame depends on its own samples only
+ * (reflected inside its utterance without snip_edges): its bits are the same alone and in any batch.  Every refusal comes before
+ * any launch and leaves out_d untouched.  Synchronous. */
+int khg_frontend_compute(khg_ctx *ctx, khg_frontend *fe, int32_t n_utt, const int64_t *sample_off_h, const void *samples_h, const void *samples_d,
+                         int32_t sample_type, int64_t *frame_off_h, float *out_d);
+
 #ifdef __cplusplus
 }
 #endif

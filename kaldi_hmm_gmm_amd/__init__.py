@@ -41,6 +41,9 @@ from .lda import (LDA_MAX_SPLICED_DIM, LDA_OK, LDA_SINGULAR, acc_lda, acc_lda_ba
                   splice_feats, splice_transform_feats, splice_transform_feats_batch)
 from .feat import (CMVN_NO_DATA, CMVN_NONFINITE, CMVN_OK, FEAT_TILE_LDS_BYTES, add_deltas, add_deltas_batch, apply_cmvn,  # noqa: F401
                    apply_cmvn_batch, cmvn_compute, compute_cmvn_stats, compute_cmvn_stats_batch, delta_scales)
+from .wave import (FE_FBANK, FE_MFCC, FE_TILE_FRAMES, WAVE_F32, WAVE_I16, WIN_BLACKMAN, WIN_HAMMING, WIN_HANNING, WIN_POVEY,  # noqa: F401
+                   WIN_RECTANGULAR, DeviceFrontend, FrontendOptions, compute_fbank_feats, compute_fbank_feats_batch, compute_mfcc_feats,
+                   compute_mfcc_feats_batch, frame_offsets, frame_starts, frontend_dims, frontend_tables, num_frames)
 from .tree import (TREE_MAX_CONTEXT, TREE_MAX_PDF_CLASS, TREE_MAX_PHONE, TREE_STATUS_MIXED_PHONES, TREE_STATUS_NO_ALI,  # noqa: F401
                    TREE_STATUS_OPEN_END, acc_tree_stats, acc_tree_stats_batch, build_tree, convert_ali, gmm_init_model, leaf_stats,
                    pdf_class_questions, split_to_phones, tid_tables)

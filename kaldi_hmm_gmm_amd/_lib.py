@@ -122,6 +122,14 @@ class LdaOptionsC(C.Structure):
     _fields_ = [("target_dim", C.c_int32), ("remove_offset", C.c_int32), ("within_class_factor", C.c_double)]
 
 
+class FrontendOptsC(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("samp_freq", C.c_float), ("frame_length_ms", C.c_float), ("frame_shift_ms", C.c_float), ("preemph_coeff", C.c_float),
+                ("remove_dc_offset", C.c_int32), ("window_type", C.c_int32), ("blackman_coeff", C.c_float), ("snip_edges", C.c_int32),
+                ("round_to_power_of_two", C.c_int32), ("dither", C.c_float), ("num_mel_bins", C.c_int32), ("low_freq", C.c_float), ("high_freq", C.c_float),
+                ("vtln_warp", C.c_float), ("htk_compat", C.c_int32), ("num_ceps", C.c_int32), ("cepstral_lifter", C.c_float), ("use_energy", C.c_int32),
+                ("raw_energy", C.c_int32), ("energy_floor", C.c_float), ("use_log_fbank", C.c_int32), ("use_power", C.c_int32)]
+
+
 class RescoreStatsC(C.Structure):
     _fields_ = [("arcs", C.c_int64), ("emitting_arcs", C.c_int64), ("cells", C.c_int64)]
 
@@ -338,6 +346,13 @@ SIGNATURES = {
     "khg_delta_scales": (C.c_int, [C.c_int32, C.c_int32, c_f32p]),
     "khg_utts_apply_cmvn": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_f32p, c_i32p, vp]),
     "khg_utts_add_deltas": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, c_i32p, vp]),
+    "khg_frontend_opts_default": (None, [C.POINTER(FrontendOptsC)]),
+    "khg_frontend_dims": (C.c_int, [C.POINTER(FrontendOptsC), c_i32p]),
+    "khg_frontend_num_frames": (C.c_int, [C.POINTER(FrontendOptsC), C.c_int64, c_i64p]),
+    "khg_frontend_tables": (C.c_int, [C.POINTER(FrontendOptsC), c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p]),
+    "khg_frontend_create": (C.c_int, [vp, C.POINTER(FrontendOptsC), C.POINTER(vp)]),
+    "khg_frontend_destroy": (C.c_int, [vp]),
+    "khg_frontend_compute": (C.c_int, [vp, vp, C.c_int32, c_i64p, vp, vp, C.c_int32, c_i64p, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,11 +1,16 @@
 // kaldi_hmm_gmm_amd/csrc/khg_feat.hip -- the feature stage in front of the acoustic model (compute-cmvn-stats, apply-cmvn, add-deltas;
 // DESIGN.md 7p): the per-speaker statistics handle (khg_cmvn_stats), its accumulation from a set's resident rows and the fused
 // normalise-and-delta of those rows.  The normaliser (khg_cmvn_compute) and the coefficient tables (khg_delta_scales) are host code
-// and live in khg_host_feat.cpp.  gfx950 only.
+// and live in khg_host_feat.cpp.  Also the waveform front end in front of that stage (compute-mfcc-feats, compute-fbank-feats; DESIGN.md
+// 7q): the resident tables (khg_frontend) and khg_frontend_compute; its options and tables are host code in khg_host_feat.cpp too.
+// gfx950 only.
 #include "khg_internal.hpp"
+
+#include <cfloat>
 
 #include "khg_feat_stats.hip.inc"
 #include "khg_feat_tile.hip.inc"
+#include "khg_feat_wave.hip.inc"
 
 struct khg_cmvn_stats {
   khg_ctx* ctx = nullptr;
@@ -258,4 +263,127 @@ extern "C" int khg_utts_apply_cmvn(khg_ctx* ctx, khg_utts* u, int32_t n_spk, con
 extern "C" int khg_utts_add_deltas(khg_ctx* ctx, khg_utts* u, int32_t order, int32_t window, int32_t n_spk, const int32_t* utt2spk_h, const float* norm_h,
                                    const int32_t* status_h, float* out_d) {
   return feat_tile("khg_utts_add_deltas", ctx, u, order, window, n_spk, utt2spk_h, norm_h, status_h, out_d, false);
+}
+
+// ---- the waveform front end: the tables resident on a handle, and compute-mfcc-feats / compute-fbank-feats ----
+struct khg_frontend {
+  khg_ctx* ctx = nullptr;
+  khg_frontend_opts opts;
+  FeParams p;
+  size_t lds_bytes = 0;
+  float* tab_d = nullptr;            // window [L], twiddles [N], mel weights [n_w]
+  int32_t* runs_d = nullptr;         // [3][B]: first bin, length, first weight
+  float* dctT_d = nullptr;           // [B][C]
+  float* lifter_d = nullptr;         // [C]
+};
+
+extern "C" int khg_frontend_create(khg_ctx* ctx, const khg_frontend_opts* o, khg_frontend** out) {
+  const std::string who = "khg_frontend_create: ";
+  if (ctx_dead(ctx) || !o || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  int32_t d[8];
+  int rc = khg_frontend_dims(o, d);
+  if (rc) return rc;
+  FeParams p{};
+  p.L = d[0]; p.S = d[1]; p.N = d[2]; p.B = d[3]; p.C = d[4]; p.out_dim = d[5]; p.n_w = d[6];
+  p.logM = 0;
+  while ((2 << p.logM) < p.N) p.logM++;
+  p.mfcc = o->kind == KHG_FE_MFCC; p.remove_dc = o->remove_dc_offset != 0; p.snip = o->snip_edges != 0; p.use_energy = o->use_energy != 0;
+  p.raw_energy = o->raw_energy != 0; p.use_log = p.mfcc || o->use_log_fbank; p.use_power = p.mfcc || o->use_power; p.i16 = 0;
+  p.has_floor = o->energy_floor > 0.0f; p.preemph = o->preemph_coeff; p.inv_L = (float)(1.0 / p.L);
+  p.log_floor = p.has_floor ? (float)std::log((double)o->energy_floor) : 0.0f;
+  const int64_t lds = 4 * fe_lds_floats(p);
+  if (lds > KHG_FEAT_TILE_LDS_BYTES)
+    return khg_set_error(KHG_E_UNSUPPORTED, who + "frame_shift_ms and frame_length_ms need " + std::to_string(lds) + " bytes of LDS for " + std::to_string(FE_TILE) +
+                                                " frames and the tables, above KHG_FEAT_TILE_LDS_BYTES (" + std::to_string(KHG_FEAT_TILE_LDS_BYTES) + ")");
+  std::vector<float> tab((size_t)p.L + p.N + p.n_w), dct((size_t)p.C * p.B), dctT((size_t)p.C * p.B), lifter((size_t)p.C);
+  std::vector<int32_t> runs((size_t)3 * p.B);
+  rc = khg_frontend_tables(o, tab.data(), runs.data(), runs.data() + p.B, tab.data() + p.L + p.N, dct.data(), lifter.data(), tab.data() + p.L);
+  if (rc) return rc;
+  for (int b = 0, at = 0; b < p.B; ++b) { runs[(size_t)2 * p.B + b] = at; at += runs[(size_t)p.B + b]; }
+  for (int c = 0; c < p.C; ++c)
+    for (int b = 0; b < p.B; ++b) dctT[(size_t)b * p.C + c] = dct[(size_t)c * p.B + b];
+  for (int b = 0; b < p.B; ++b)                              // the kernel walks pw[off .. off + len): inside the N / 2 bins
+    if (runs[b] < 0 || runs[(size_t)p.B + b] < 0 || runs[b] + runs[(size_t)p.B + b] > p.N / 2) return khg_set_error(KHG_E_RUNTIME, who + "a mel filter leaves the spectrum");
+  khg_frontend* fe = new khg_frontend();
+  fe->ctx = ctx; fe->opts = *o; fe->p = p; fe->lds_bytes = (size_t)lds;
+  rc = arena_flush(ctx);
+  if (!rc) rc = dev_alloc(&fe->tab_d, tab.size());
+  if (!rc) rc = dev_alloc(&fe->runs_d, runs.size());
+  if (!rc) rc = dev_alloc(&fe->dctT_d, dctT.size());
+  if (!rc) rc = dev_alloc(&fe->lifter_d, lifter.size());
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    e = hipMemcpyAsync(fe->tab_d, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fe->runs_d, runs.data(), sizeof(int32_t) * runs.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && p.C) e = hipMemcpyAsync(fe->dctT_d, dctT.data(), sizeof(float) * dctT.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && p.C) e = hipMemcpyAsync(fe->lifter_d, lifter.data(), sizeof(float) * lifter.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  }
+  if (rc || e != hipSuccess) {
+    (void)khg_frontend_destroy(fe);
+    return rc ? rc : khg_set_error(KHG_E_HIP, who + hipGetErrorString(e));
+  }
+  *out = fe;
+  return KHG_OK;
+}
+extern "C" int khg_frontend_destroy(khg_frontend* fe) {
+  if (!fe) return KHG_OK;
+  DEVFREE(fe->tab_d); DEVFREE(fe->runs_d); DEVFREE(fe->dctT_d); DEVFREE(fe->lifter_d);
+  delete fe;
+  return KHG_OK;
+}
+
+extern "C" int khg_frontend_compute(khg_ctx* ctx, khg_frontend* fe, int32_t n_utt, const int64_t* sample_off_h, const void* samples_h, const void* samples_d,
+                                    int32_t sample_type, int64_t* frame_off_h, float* out_d) {
+  const std::string who = "khg_frontend_compute: ";
+  if (ctx_dead(ctx) || !fe || n_utt < 0 || !sample_off_h || !frame_off_h) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  if (fe->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (sample_type != KHG_WAVE_F32 && sample_type != KHG_WAVE_I16) return khg_set_error(KHG_E_ARG, who + "sample_type must be KHG_WAVE_F32 or KHG_WAVE_I16");
+  if (sample_off_h[0] < 0) return khg_set_error(KHG_E_ARG, who + "sample_off must start at or above 0");
+  for (int i = 0; i < n_utt; ++i)
+    if (sample_off_h[i + 1] < sample_off_h[i]) return khg_set_error(KHG_E_ARG, who + "sample_off must not descend (utterance " + std::to_string(i) + ")");
+  const int64_t n_samples = sample_off_h[n_utt];
+  FeParams p = fe->p;
+  p.i16 = sample_type == KHG_WAVE_I16;
+  std::vector<int64_t> fo((size_t)n_utt + 1, 0);
+  for (int i = 0; i < n_utt; ++i) {                          // khg_frontend_num_frames' rule on the handle's own L, S and snip_edges
+    const int64_t n = sample_off_h[i + 1] - sample_off_h[i];
+    const int64_t T = p.snip ? (n < p.L ? 0 : 1 + (n - p.L) / p.S) : (n + p.S / 2) / p.S;
+    if (T > INT_MAX - FE_TILE) return khg_set_error(KHG_E_UNSUPPORTED, who + "utterance " + std::to_string(i) + " has 2^31 or more frames");
+    fo[(size_t)i + 1] = fo[(size_t)i] + T;
+  }
+  if (out_d && fo[(size_t)n_utt] > 0 && n_samples > 0 && ((samples_h != nullptr) == (samples_d != nullptr)))
+    return khg_set_error(KHG_E_ARG, who + "exactly one of samples_h and samples_d must be given");
+  for (int i = 0; i <= n_utt; ++i) frame_off_h[i] = fo[(size_t)i];
+  if (!out_d || fo[(size_t)n_utt] == 0) return KHG_OK;
+  std::vector<FeItem> items;
+  for (int i = 0; i < n_utt; ++i) {
+    const int64_t T = fo[(size_t)i + 1] - fo[(size_t)i];
+    for (int64_t t = 0; t < T; t += FE_TILE)
+      items.push_back(FeItem{sample_off_h[i], sample_off_h[i + 1] - sample_off_h[i], fo[(size_t)i] + t, (int32_t)t, (int32_t)std::min<int64_t>(FE_TILE, T - t)});
+  }
+  if (items.size() >= (size_t)INT_MAX) return khg_set_error(KHG_E_UNSUPPORTED, who + "too many frames in one call");
+  int rc = arena_flush(ctx);
+  if (rc) return rc;
+  FeItem* items_d = nullptr; char* up_d = nullptr;
+  auto cleanup = [&] { DEVFREE(items_d); DEVFREE(up_d); };
+  const size_t ssz = p.i16 ? sizeof(int16_t) : sizeof(float);
+  rc = dev_alloc(&items_d, items.size());
+  if (!rc && samples_h) rc = dev_alloc(&up_d, (size_t)n_samples * ssz);
+  if (rc) { cleanup(); return rc; }
+  hipError_t e = hipMemcpyAsync(items_d, items.data(), sizeof(FeItem) * items.size(), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && samples_h) e = hipMemcpyAsync(up_d, samples_h, (size_t)n_samples * ssz, hipMemcpyHostToDevice, ctx->stream);
+  // a per-function attribute that another handle may have set lower: set for this launch, as khg_utts_add_deltas does
+  if (e == hipSuccess && fe->lds_bytes > 48 * 1024) e = hipFuncSetAttribute((const void*)k_fe_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fe->lds_bytes);
+  if (e != hipSuccess) { cleanup(); return khg_set_error(KHG_E_HIP, who + hipGetErrorString(e)); }
+  {
+    KernelTimer kt(ctx, "k_fe_wave");
+    KHG_LAUNCH(ctx, k_fe_wave, dim3((unsigned)items.size()), dim3(256), fe->lds_bytes, ctx->stream, items_d, p, samples_h ? (const void*)up_d : samples_d, fe->tab_d,
+               fe->runs_d, fe->dctT_d, fe->lifter_d, out_d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // the temporaries and the caller's host arrays are free again
+  cleanup();
+  if (e != hipSuccess) return khg_set_error(KHG_E_HIP, who + hipGetErrorString(e));
+  return KHG_OK;
 }

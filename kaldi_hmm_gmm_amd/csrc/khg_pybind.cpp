@@ -534,6 +534,44 @@ struct KCmvnStats {
   int num_chunks() { int32_t n = 0; Check(khg_cmvn_stats_num_chunks(h, &n)); return n; }
 };
 
+// the waveform front end's tables resident in HBM (khg_frontend)
+struct KFrontend {
+  khg_frontend* h = nullptr;
+  py::object ctx_obj;
+  KContext* ctx;
+  khg_frontend_opts opts;
+  int dim = 0;
+  KFrontend(py::object ctx_o, const khg_frontend_opts& o) : ctx_obj(ctx_o), ctx(ctx_o.cast<KContext*>()), opts(o) {
+    int32_t d[8];
+    Check(khg_frontend_dims(&o, d));
+    dim = d[5];
+    Check(khg_frontend_create(ctx->h, &o, &h));
+  }
+  ~KFrontend() { close(); }
+  void close() { if (h) { khg_frontend_destroy(h); h = nullptr; } }
+  // samples: a host array (float32 or int16, by sample_type) or None with samples_d, a device pointer; out: a device pointer or None
+  // (then only the frame offsets are computed)
+  Arr<int64_t> compute(Arr<int64_t> sample_off, py::object samples_h, uintptr_t samples_d, int sample_type, py::object out) {
+    if (!h) throw py::value_error("DeviceFrontend.compute: the handle is closed");
+    if (sample_off.ndim() != 1 || sample_off.size() < 1) throw py::value_error("DeviceFrontend.compute: sample_off [n_utt + 1]");
+    const int32_t n_utt = (int32_t)sample_off.size() - 1;
+    const void* sh = nullptr;
+    py::array keep;
+    if (!samples_h.is_none()) {
+      keep = py::array::ensure(samples_h, py::array::c_style);
+      const bool i16 = sample_type == KHG_WAVE_I16;
+      if (!keep || keep.ndim() != 1 || !keep.dtype().is(i16 ? py::dtype::of<int16_t>() : py::dtype::of<float>()))
+        throw py::value_error("DeviceFrontend.compute: samples must be a contiguous 1-d array of the sample type");
+      if (keep.size() < sample_off.at(n_utt)) throw py::value_error("DeviceFrontend.compute: fewer samples than sample_off says");
+      sh = keep.data();
+    }
+    float* od = out.is_none() ? nullptr : reinterpret_cast<float*>(out.cast<uintptr_t>());
+    Arr<int64_t> fo((py::ssize_t)n_utt + 1);
+    Check(NoGil([&] { return khg_frontend_compute(ctx->h, h, n_utt, sample_off.data(), sh, reinterpret_cast<const void*>(samples_d), sample_type, fo.mutable_data(), od); }));
+    return fo;
+  }
+};
+
 // decision-tree statistics resident in HBM (khg_tree_stats)
 struct KTreeStats {
   khg_tree_stats* h = nullptr;
@@ -1293,6 +1331,56 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
   }, py::arg("order"), py::arg("window"), "DeltaFeatures' coefficient tables, one float32 array per order 0 .. order (khg_delta_scales; DESIGN.md 7p)");
   m.attr("CMVN_OK") = KHG_CMVN_OK; m.attr("CMVN_NO_DATA") = KHG_CMVN_NO_DATA; m.attr("CMVN_NONFINITE") = KHG_CMVN_NONFINITE;
   m.attr("FEAT_TILE_LDS_BYTES") = KHG_FEAT_TILE_LDS_BYTES;
+  // the waveform front end
+  py::class_<khg_frontend_opts>(m, "FrontendOptions", "Kaldi's MFCC / filterbank options (khg_frontend_opts); keyword arguments set fields")
+      .def(py::init([](py::kwargs kw) {
+        khg_frontend_opts o;
+        khg_frontend_opts_default(&o);
+        py::object po = py::cast(&o, py::return_value_policy::reference);
+        for (auto kv : kw) py::setattr(po, kv.first, kv.second);
+        return o;
+      }))
+      .def("copy", [](const khg_frontend_opts& o) { return o; })
+#define FE_FIELD(f) .def_readwrite(#f, &khg_frontend_opts::f)
+      FE_FIELD(kind) FE_FIELD(samp_freq) FE_FIELD(frame_length_ms) FE_FIELD(frame_shift_ms) FE_FIELD(preemph_coeff) FE_FIELD(remove_dc_offset)
+      FE_FIELD(window_type) FE_FIELD(blackman_coeff) FE_FIELD(snip_edges) FE_FIELD(round_to_power_of_two) FE_FIELD(dither) FE_FIELD(num_mel_bins)
+      FE_FIELD(low_freq) FE_FIELD(high_freq) FE_FIELD(vtln_warp) FE_FIELD(htk_compat) FE_FIELD(num_ceps) FE_FIELD(cepstral_lifter) FE_FIELD(use_energy)
+      FE_FIELD(raw_energy) FE_FIELD(energy_floor) FE_FIELD(use_log_fbank) FE_FIELD(use_power);
+#undef FE_FIELD
+  m.attr("FE_MFCC") = KHG_FE_MFCC; m.attr("FE_FBANK") = KHG_FE_FBANK; m.attr("FE_TILE_FRAMES") = KHG_FE_TILE_FRAMES;
+  m.attr("WIN_POVEY") = KHG_WIN_POVEY; m.attr("WIN_HAMMING") = KHG_WIN_HAMMING; m.attr("WIN_HANNING") = KHG_WIN_HANNING;
+  m.attr("WIN_RECTANGULAR") = KHG_WIN_RECTANGULAR; m.attr("WIN_BLACKMAN") = KHG_WIN_BLACKMAN;
+  m.attr("WAVE_F32") = KHG_WAVE_F32; m.attr("WAVE_I16") = KHG_WAVE_I16;
+  m.def("frontend_dims", [](const khg_frontend_opts& o) {
+    int32_t d[8];
+    Check(khg_frontend_dims(&o, d));
+    py::dict r;
+    r["L"] = d[0]; r["S"] = d[1]; r["N"] = d[2]; r["num_mel_bins"] = d[3]; r["num_ceps"] = d[4]; r["dim"] = d[5]; r["num_weights"] = d[6];
+    return r;
+  }, py::arg("opts"), "frame length, shift, padded window and the table sizes the options imply (khg_frontend_dims)");
+  m.def("num_frames", [](const khg_frontend_opts& o, int64_t n) {
+    int64_t T = 0;
+    Check(khg_frontend_num_frames(&o, n, &T));
+    return T;
+  }, py::arg("opts"), py::arg("n_samples"), "frames of an utterance of n_samples (khg_frontend_num_frames; DESIGN.md 7q)");
+  m.def("frontend_tables", [](const khg_frontend_opts& o) {
+    int32_t d[8];
+    Check(khg_frontend_dims(&o, d));
+    Arr<float> win((py::ssize_t)d[0]), w((py::ssize_t)d[6]), dct({(py::ssize_t)d[4], (py::ssize_t)d[3]}), lif((py::ssize_t)d[4]), tw({(py::ssize_t)d[2] / 2, (py::ssize_t)2});
+    Arr<int32_t> off((py::ssize_t)d[3]), len((py::ssize_t)d[3]);
+    Check(khg_frontend_tables(&o, win.mutable_data(), off.mutable_data(), len.mutable_data(), w.mutable_data(), dct.mutable_data(), lif.mutable_data(), tw.mutable_data()));
+    py::dict r;
+    r["L"] = d[0]; r["S"] = d[1]; r["N"] = d[2];
+    r["window"] = win; r["mel_off"] = off; r["mel_len"] = len; r["mel_w"] = w; r["dct"] = dct; r["lifter"] = lif; r["twiddles"] = tw;
+    return r;
+  }, py::arg("opts"), "the window, mel filters (first bin, length, weights one after the other), DCT rows, lifter and FFT twiddles (khg_frontend_tables)");
+  py::class_<KFrontend>(m, "DeviceFrontend")
+      .def(py::init<py::object, const khg_frontend_opts&>(), py::arg("ctx"), py::arg("opts"))
+      .def_property_readonly("h", [](KFrontend& x) { return reinterpret_cast<uintptr_t>(x.h); })
+      .def_readonly("ctx", &KFrontend::ctx_obj).def_readonly("dim", &KFrontend::dim)
+      .def_property_readonly("opts", [](KFrontend& x) { return x.opts; })
+      .def("compute", &KFrontend::compute, py::arg("sample_off"), py::arg("samples_h"), py::arg("samples_d"), py::arg("sample_type"), py::arg("out") = py::none())
+      .def("close", &KFrontend::close);
   m.def("build_tree", [](int N, int P, Arr<int32_t> keys, Arr<double> cnt, Arr<double> x, Arr<double> x2, Arr<int32_t> qkeys, Arr<int64_t> qkey_off, Arr<int64_t> q_off,
                          Arr<int32_t> q_vals, Arr<int64_t> set_off, Arr<int32_t> set_phones, Arr<int32_t> share_roots, Arr<int32_t> do_split, Arr<int32_t> p2n, double thresh,
                          int max_leaves, double cluster_thresh, double var_floor) {

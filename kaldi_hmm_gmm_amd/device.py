@@ -30,6 +30,7 @@ DeviceFmllrStats = _ext.DeviceFmllrStats    # khg_fmllr_stats: FmllrDiagGmmAccs 
 DeviceMlltStats = _ext.DeviceMlltStats      # khg_mllt_stats: MlltAccs in HBM; download() -> beta, numpy G
 DeviceLdaStats = _ext.DeviceLdaStats        # khg_lda_stats: LdaEstimate accumulators in HBM; download() -> zero_acc / first_acc / total_second_acc
 DeviceTreeStats = _ext.DeviceTreeStats      # khg_tree_stats: (window, pdf-class) event statistics in HBM; download() -> keys / count / x / x2
+DeviceFrontend = _ext.DeviceFrontend        # khg_frontend: the waveform front end's tables in HBM; compute() -> frame offsets
 DeviceCmvnStats = _ext.DeviceCmvnStats      # khg_cmvn_stats: CMVN statistics per speaker in HBM; download() -> numpy [n_spk, 2, dim + 1]
 LDA_OK = _ext.LDA_OK
 LDA_SINGULAR = _ext.LDA_SINGULAR

@@ -313,3 +313,44 @@ def utt_fst(graphs, u):
     a0, a1 = int(ao[0]), int(ao[-1])
     return StdVectorFst.from_csr(int(graphs["start"][u]), (ao - a0).astype(np.int64), graphs["ilabel"][a0:a1], graphs["olabel"][a0:a1],
                                  graphs["weight"][a0:a1], graphs["nextstate"][a0:a1], graphs["final"][s0:s1])
+
+
+# ---- waveforms for the YES/NO task: phones SIL, Y, N as in egs/yesno; words YES, NO ----
+YESNO_SIL, YESNO_Y, YESNO_N = 1, 2, 3
+YESNO_YES, YESNO_NO = 1, 2
+# two tones (Hz) per HMM state of a phone: Y glides upwards, N stays low and falls; silence is noise alone
+_YESNO_TONES = {YESNO_Y: [(350.0, 1900.0), (450.0, 2200.0), (550.0, 2500.0)], YESNO_N: [(300.0, 1300.0), (260.0, 1100.0), (220.0, 900.0)],
+                YESNO_SIL: [None] * 5}
+
+
+def make_yesno_waves(n_utt, seed=0, samp_freq=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, tone_amp=4000.0, noise=300.0):
+    """A small waveform synthesiser for the YES/NO task: each utterance is 3..8 random words with silence around them with
+    probability 0.5; every state of a phone sounds its own two tones for 3..8 frame shifts over Gaussian noise, with a random
+    phase, a per-utterance gain and a per-utterance pitch factor.  The tail is padded with noise so that, with snip_edges, the
+    utterance has exactly one frame per state-frame.  -> [(name, words, int16 samples)]"""
+    rng = np.random.default_rng(seed)
+    S = int(samp_freq * 0.001 * frame_shift_ms)
+    L = int(samp_freq * 0.001 * frame_length_ms)
+    utts = []
+    for u in range(n_utt):
+        words = [int(w) for w in rng.integers(1, 3, size=int(rng.integers(3, 9)))]
+        phones = [YESNO_SIL] if rng.random() < 0.5 else []
+        for w in words:
+            phones.append(YESNO_Y if w == YESNO_YES else YESNO_N)
+            if rng.random() < 0.5:
+                phones.append(YESNO_SIL)
+        gain, pitch = float(np.exp(0.3 * rng.standard_normal())), float(np.exp(0.05 * rng.standard_normal()))
+        parts = []
+        for ph in phones:
+            for tones in _YESNO_TONES[ph]:
+                n = int(rng.integers(3, 9)) * S
+                x = noise * rng.standard_normal(n)
+                if tones is not None:
+                    t = np.arange(n) / samp_freq
+                    for f in tones:
+                        x = x + tone_amp * np.sin(2.0 * np.pi * f * pitch * t + rng.uniform(0.0, 2.0 * np.pi))
+                parts.append(x)
+        parts.append(noise * rng.standard_normal(max(L - S, 0)))
+        x = gain * np.concatenate(parts)
+        utts.append((f"utt{u:04d}", words, np.clip(np.round(x), -32768, 32767).astype(np.int16)))
+    return utts
