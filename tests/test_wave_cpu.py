@@ -267,3 +267,144 @@ def test_symbols_exported_and_declared():
     assert _lib.lib.khg_frontend_create(None, None, None) != 0
     assert _lib.lib.khg_frontend_compute(None, None, 0, None, None, None, 0, None, None) != 0
     assert _lib.lib.khg_frontend_destroy(None) == 0
+
+
+# ---- every option branch and FFT size (cases.OPTION_CASES) ----
+CASES = list(cases.OPTION_CASES)
+
+
+def test_option_case_constants_are_the_librarys():
+    import kaldi_hmm_gmm_amd as khg
+    assert (cases.TILE_FRAMES, cases.TILE_LDS_BYTES) == (khg.FE_TILE_FRAMES, khg.FEAT_TILE_LDS_BYTES)
+    want = {"n1024": (551, 220, 1024), "n256_l160": (160, 80, 256), "l_eq_n_256": (256, 160, 256), "l_eq_n_512": (512, 160, 512),
+            "shift_gt_len": (400, 480, 512), "shift_1": (400, 1, 512), "b128_8k": (200, 80, 256)}
+    for name in CASES:
+        o = cases.case_opts(name)
+        d = khg.frontend_dims(cases.lib_opts(o))
+        assert (d["L"], d["S"], d["N"]) == ref.dims(o) == want.get(name, (400, ref.dims(o)[1], 512)), name
+        assert d["dim"] == cases.out_dim(o)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_option_case_tables_equal_the_restatement_on_the_bits(name):
+    import kaldi_hmm_gmm_amd as khg
+    o = cases.case_opts(name)
+    got, want = khg.frontend_tables(cases.lib_opts(o)), ref.tables_f32(o)
+    N, B, C = ref.dims(o)[2], o["num_mel_bins"], o["num_ceps"]
+    assert got["dct"].shape == (C, B) and got["lifter"].shape == (C,)
+    for tname in ("window", "mel_w", "dct", "lifter", "twiddles"):
+        assert got[tname].dtype == np.float32 and got[tname].shape == want[tname].shape, tname
+        assert (_bits(got[tname]) == _bits(want[tname])).all(), (tname, int((_bits(got[tname]) != _bits(want[tname])).sum()))
+    for tname in ("mel_off", "mel_len"):
+        assert got[tname].dtype == np.int32 and (got[tname] == want[tname]).all(), tname
+    assert int(got["mel_len"].sum()) == len(got["mel_w"]) and (got["mel_off"] >= 0).all() and (got["mel_off"] + got["mel_len"] <= N // 2).all()
+    assert (got["mel_w"] > 0).all() and (got["mel_w"] <= 1).all()      # every stored weight: an empty run stores none
+    if name == "lifter0":
+        assert (got["lifter"] == 1.0).all()
+    if name in ("b128_16k", "b128_8k", "c128"):
+        empty = [b for b, (_, ws) in enumerate(ref.mel_filters(o)) if not ws]
+        assert len(empty) >= 1 and (got["mel_len"][empty] == 0).all()
+        assert int((got["mel_len"] == 0).sum()) == len(empty) == {"b128_16k": 1, "b128_8k": 4, "c128": 1}[name]
+    else:
+        assert (got["mel_len"] > 0).all()
+
+
+def _case_wave(name, o):
+    L, S, N = ref.dims(o)
+    n = L + (5 if N == 1024 else 20) * S + 17
+    return cases.noise(n, 11, tone=True, samp_freq=o["samp_freq"], dc=cases.case_dc(name))
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_option_case_host_form_within_the_derived_bound(name):
+    """the float32 host form against the float64 restatement under every option set: every log-mel cell and every cepstrum within its
+    own bound with K = ref.bound_roundings (counted in DESIGN.md 7q), the bound itself at most 0.1; for three cases also with the
+    energy in column 0, raw and windowed, within the energy's bound of test_host_form_without_snip_edges_and_with_energies.
+    Measured: largest error / bound 0.20 (FBANK at 128 bins), 0.059 at preemph0 (K = 57), 0.061 at nodc_rect_c0, below 0.014 elsewhere."""
+    import kaldi_hmm_gmm_amd as khg
+    variants = [dict()]
+    if name in ("c1", "b128_16k", "nodc"):
+        variants += [dict(use_energy=True, raw_energy=True), dict(use_energy=True, raw_energy=False)]
+    for kw in variants:
+        for kind in ("fbank", "mfcc"):
+            o = cases.case_opts(name, kind=kind, **kw)
+            x = _case_wave(name, o)
+            lo = cases.lib_opts(o)
+            got = khg.compute_mfcc_feats(x, lo) if kind == "mfcc" else khg.compute_fbank_feats(x, lo)
+            want, det = ref.features(x, o, detail=True)
+            assert got.dtype == np.float32 and got.shape == want.shape == (6 if name == "n1024" else ref.num_frames(o, len(x)), cases.out_dim(o))
+            assert np.isfinite(got).all()
+            lmb = ref.log_mel_bound(o, det)
+            bound = ref.cepstra_bound(o, lmb) if kind == "mfcc" else lmb
+            err = np.abs(got - want)
+            if kw:
+                assert (err[:, 0] <= 40 * 2.0 ** -24 + 2.0 ** -23 * np.abs(want[:, 0])).all()
+                err, want = err[:, 1:], want[:, 1:]
+                bound = bound[:, 1:] if kind == "mfcc" else bound
+            if err.shape[1] == 0:                                    # c1 with use_energy: the energy alone
+                assert (name, kind) == ("c1", "mfcc")
+                continue
+            ratio = err / bound
+            print("%s %s %s: largest error %.3g, largest error / bound %.3g, largest log-mel bound %.3g (K = %d)" %
+                  (name, kind, kw, float(err.max()), float(ratio.max()), float(lmb.max()), ref.bound_roundings(o)))
+            assert lmb.max() <= 0.1
+            assert (ratio <= 1.0).all()
+
+
+@pytest.mark.parametrize("name", cases.KEEP_SHAPE + ["lifter0"])
+def test_each_option_case_discriminates(name):
+    """a condition on the inputs: the restatement under the case's options, on the case's own signal, differs from the restatement at
+    the defaults beyond the case's own bound in at least half of the cells (some cell for nodc: under the povey window and c = 0.97 a
+    constant offset reaches few bins) -- or a host form that ignored the option would agree with a kernel that ignores it"""
+    kind = "mfcc" if name == "lifter0" else "fbank"
+    o = cases.case_opts(name, kind=kind)
+    base = ref.opts(kind=kind, num_ceps=o["num_ceps"])
+    x = _case_wave(name, o)
+    want, det = ref.features(x, o, detail=True)
+    lmb = ref.log_mel_bound(o, det)
+    bound = ref.cepstra_bound(o, lmb) if kind == "mfcc" else lmb
+    moved = np.abs(ref.features(x, base) - want)
+    if name == "lifter0":                                        # the lifter is 1 at c = 0 whatever Q is
+        moved, bound = moved[:, 1:], bound[:, 1:]
+    frac = float((moved > bound).mean())
+    print("%s: largest move %.3g, largest move / bound %.3g, cells beyond the bound %.0f %%" % (name, float(moved.max()), float((moved / bound).max()), 100 * frac))
+    assert (moved > bound).any()
+    if name != "nodc":
+        assert frac >= 0.5
+
+
+def test_option_batch_lengths_hold_every_tile_shape():
+    F = cases.TILE_FRAMES
+    for name in CASES:
+        for snip in (True, False):
+            o = cases.case_opts(name, snip_edges=snip)
+            lens = cases.option_batch_lengths(o)
+            T = [ref.num_frames(o, n) for n in lens]
+            assert T[:11] == [0, 1, 2, 3, 4, 5, F - 1, F, F + 1, 2 * F + 1, 37], (name, snip, T)
+            assert len(lens) <= 13 and sum(T) <= 135 and max(T) == 37
+            tiles = [min(F, t - a) for t in T for a in range(0, t, F)]
+            assert {n % 4 for n in tiles} == {0, 1, 2, 3} and F in tiles
+            if not snip:
+                S = ref.dims(o)[1]
+                assert lens[11:] == [n for n in (S // 2, S // 2 - 1) if n >= 0]
+
+
+@pytest.mark.parametrize("snip", [True, False])
+@pytest.mark.parametrize("name", ["shift_gt_len", "shift_1", "n1024", "l_eq_n_256"])
+def test_option_case_frame_offsets_and_starts(name, snip):
+    """frame_offsets, num_frames and frame_starts against the restatement where S > L, S = 1, L is odd (551: S / 2 - L / 2 = 110 - 275
+    truncates as C does) and L == N"""
+    import kaldi_hmm_gmm_amd as khg
+    o = cases.case_opts(name, snip_edges=snip)
+    lo = cases.lib_opts(o)
+    L, S, _ = ref.dims(o)
+    lens = cases.option_batch_lengths(o)
+    T = [ref.num_frames(o, n) for n in lens]
+    fo = khg.frame_offsets(lo, np.concatenate([[0], np.cumsum(lens)]))
+    assert fo.dtype == np.int64 and fo.tolist() == np.concatenate([[0], np.cumsum(T)]).tolist()
+    for n, t in zip(lens, T):
+        assert khg.num_frames(lo, n) == t
+        st = khg.frame_starts(lo, n)
+        assert st.dtype == np.int64 and st.tolist() == [ref.frame_start(o, i) for i in range(t)], n
+    if name == "n1024" and not snip:
+        assert khg.frame_starts(lo, lens[1]).tolist() == [110 - 275]

@@ -203,12 +203,25 @@ def features(wave, o, variant=None, detail=False):
     return out
 
 
+def bound_roundings(o):
+    """K of DESIGN.md 7q, the roundings (a relative 2^-24 each) on the longest path from a sample to a bin.  4 log2 N + 6 for the
+    path itself: the mean's subtraction 1, pre-emphasis 2, the window 2, 4 for each of the log2 N - 1 stages, the post-pass 5.  The
+    mean's own error -- ceil(L / 64) chain additions, 6 lane steps, inv_L's narrowing, one product -- enters every sample alike and
+    pre-emphasis scales it by 1 - c: with c > 0 it is counted as 1 (0.26 of a rounding at c = 0.97; a c between 0 and 0.89 would
+    need more and is not among the tests' cases), without remove_dc_offset there is no mean and the 1 is slack, and with c = 0 it
+    keeps its full ceil(L / 64) + 8."""
+    L, _, N = dims(o)
+    K = 4 * int(round(math.log2(N))) + 6
+    if o["remove_dc_offset"] and f32(o["preemph_coeff"]) == 0.0:
+        return K + -(-L // 64) + 8
+    return K + 1
+
+
 def log_mel_bound(o, det):
-    """|dX_k| <= delta = K 2^-24 sum_n (|x_n| + |mean|) (1 + c) win_n with K = 4 log2 N + 7 roundings on the longest
-    path from a sample to a bin, and |d log e_b| <= [sum_k w_bk (2 |X_k| delta + delta^2)] / e_b + (len_b + 4) 2^-24 +
-    2^-23 max(1, |log e_b|).  -> [T, B]"""
-    _, _, N = dims(o)
-    K = 4 * int(round(math.log2(N))) + 7
+    """|dX_k| <= delta = K 2^-24 sum_n (|x_n| + |mean|) (1 + c) win_n with K = bound_roundings(o) (4 log2 N + 7 at the
+    defaults), and |d log e_b| <= [sum_k w_bk (2 |X_k| delta + delta^2)] / e_b + (len_b + 4) 2^-24 + 2^-23 max(1, |log e_b|).
+    -> [T, B]"""
+    K = bound_roundings(o)
     u = 2.0 ** -24
     delta = K * u * ((np.abs(det["frames"]) + np.abs(det["mean"])[:, None]) * (1.0 + det["c"]) * det["win"][None, :]).sum(1)      # [T]
     T, B = det["e"].shape
