@@ -571,8 +571,9 @@ typedef struct { int64_t arcs, emitting_arcs, cells; } khg_rescore_stats;   /* a
  * stats (may be NULL): host counts, on the synchronisation the call has anyway (cells: CELLS mode only, else 0).  Synchronous. */
 int khg_lattices_rescore(khg_ctx *ctx, const khg_model *m, const khg_tm *tm, khg_utts *u, const khg_lattices *l,
                          float acoustic_scale, int mode, khg_rescore_stats *stats, khg_lattices **out);
-/* Per-utterance KHG_LAT_* bits of the khg_lattices_rescore / khg_lattices_boost call that made `l` (status_h[n_utt]): KHG_LAT_SUCCEEDED,
- * KHG_LAT_NO_PATH for an utterance whose input lattice was empty, KHG_LAT_NO_REF.  A handle made otherwise: KHG_E_ARG. */
+/* Per-utterance KHG_LAT_* bits of the khg_lattices_rescore / khg_lattices_boost / khg_lattices_lm_rescore call that made `l`
+ * (status_h[n_utt]): KHG_LAT_SUCCEEDED, KHG_LAT_NO_PATH for an utterance whose input lattice was empty, KHG_LAT_NO_REF; from
+ * khg_lattices_lm_rescore also KHG_LAT_EPS_LOOP, KHG_LAT_LM_OOV, KHG_LAT_SCRATCH.  A handle made otherwise: KHG_E_ARG. */
 int khg_lattices_op_status(const khg_lattices *l, int32_t *status_h);
 /* lattice-boost-ali (Kaldi's LatticeBoost).  Every arc with ilabel != 0 leaving a state of frame t of utterance u, with
  * ref = tid2phone[ali[u][t]] and ph = tid2phone[ilabel]:  e = 0 if ph == ref; max_silence_error if ph != ref and ph is a silence phone;
@@ -586,6 +587,60 @@ int khg_lattices_op_status(const khg_lattices *l, int32_t *status_h);
 int khg_lattices_boost(khg_ctx *ctx, const khg_lattices *l, int32_t num_tids, const int32_t *tid2phone_h,
                        int32_t n_sil, const int32_t *silence_phones_h, const int64_t *ali_off_h, const int32_t *ali_h,
                        const khg_utts *ali_set, float b, float max_silence_error, int32_t *status_h, khg_lattices **out);
+
+/* ---- K2N: rescoring resident lattices with a backoff n-gram language model (lattice-lmrescore) -------------------- */
+/* The LM is a deterministic backoff automaton in flat arrays.  States 0 .. n_states - 1 are histories, state 0 the empty one:
+ *   backoff_h[n_states]       backoff_h[0] = -1; for h > 0, 0 <= backoff_h[h] < h (every backoff chain ends in state 0)
+ *   backoff_cost_h[n_states]  the cost of taking that step (entry 0 is unused but finite)
+ *   arc_begin_h[n_states + 1] state h owns arcs arc_begin_h[h] .. arc_begin_h[h + 1]; from 0, monotone
+ *   word_h / cost_h / next_h [arc_begin_h[n_states]]   word > 0, strictly ascending inside a state; cost = -ln P; next a state
+ *   final_cost_h[n_states]    the cost of the sentence end from h, already resolved through the backoff chain
+ *   start                     the state of the history <s>
+ * Every float is finite.  khg_lm_validate (host only) checks all of this; KHG_E_ARG names the state or arc and the check.
+ * advance(h, w), w > 0, all float, one rounding per addition:  c = +0; search w among the arcs of h (binary); found: c = fl(c + cost),
+ * the result is (next, c); else h == 0: w is out of vocabulary; else c = fl(c + backoff_cost[h]), h = backoff[h], search again. */
+typedef struct khg_lm khg_lm;
+int khg_lm_validate(int32_t n_states, const int32_t *backoff_h, const float *backoff_cost_h, const int32_t *arc_begin_h,
+                    const int32_t *word_h, const float *cost_h, const int32_t *next_h, const float *final_cost_h, int32_t start);
+/* khg_lm_validate, then the arrays to the device.  The handle belongs to `ctx`.  Synchronous.  Free it with khg_lm_destroy. */
+int khg_lm_create(khg_ctx *ctx, int32_t n_states, const int32_t *backoff_h, const float *backoff_cost_h, const int32_t *arc_begin_h,
+                  const int32_t *word_h, const float *cost_h, const int32_t *next_h, const float *final_cost_h, int32_t start,
+                  khg_lm **out);
+int khg_lm_destroy(khg_lm *lm);
+int khg_lm_num_states(const khg_lm *lm, int32_t *n_states);
+int khg_lm_device_bytes(const khg_lm *lm, int64_t *bytes);
+/* Host only: the cost of the sentence words_h[n_words] (<s> implied, the sentence end added).  h = start, t = +0; per word
+ * (h, c) = advance(h, w), t = fl(t + c); at the end t = fl(t + final_cost[h]).  The arrays are validated first.  KHG_E_ARG for a word
+ * <= 0 or out of vocabulary, naming its position. */
+int khg_lm_score(int32_t n_states, const int32_t *backoff_h, const float *backoff_cost_h, const int32_t *arc_begin_h,
+                 const int32_t *word_h, const float *cost_h, const int32_t *next_h, const float *final_cost_h, int32_t start,
+                 int32_t n_words, const int32_t *words_h, float *cost_out);
+#define KHG_LAT_LM_OOV 1024      /* khg_lattices_lm_rescore: a reachable arc carries a word the LM does not have.  EMPTY lattice */
+typedef struct { int64_t in_states, in_arcs, out_states, out_arcs, max_hist; } khg_lm_rescore_stats;   /* states and arcs of the
+                                    input and of the result; the largest |H(s)| among the utterances that succeeded */
+/* lattice-lmrescore: a NEW handle (the input is untouched; the result keeps the input's chunks, as khg_lattices_prune's does) in
+ * which every state is split by LM history and every arc with a word carries fl(scale * the LM's cost of the word) more graph cost.
+ * scale is finite, of either sign: -1 removes an LM whose costs the graph costs hold.  Per utterance, in this order:
+ *   empty input                                 KHG_LAT_NO_PATH, stays empty
+ *   an arc that does not go to a higher state   KHG_LAT_EPS_LOOP, empty (the lattice-simple decoder's lattices; those of the
+ *                                               lattice-faster decoder and what prune / rescore / boost make of them are admissible)
+ *   H(start) = {lm start}; for the states d in ascending order H(d) = the set of h' over the in-arcs (s -> d, olabel w) and the
+ *   h in H(s): h' = h when w == 0, else the state of advance(h, w).  Sorted ascending, unique.
+ *   a word out of vocabulary among them         KHG_LAT_LM_OOV, empty (an arc that leaves an unreachable state is never looked at)
+ *   the sets of the states 0 .. d together hold more than min(hist_factor * states, 2^31 - 1) entries: KHG_LAT_SCRATCH, empty (the
+ *                                               decoders' convention: call again with a larger hist_factor)
+ *   otherwise                                   KHG_LAT_SUCCEEDED
+ * Result: for old s ascending, for h in H(s) ascending, one state (a state with an empty H -- unreachable -- is dropped) with
+ * frame, graph_state, tot_cost, extra_cost of s (the last two stale, as after khg_lattices_rescore) and final_cost +inf where s has
+ * +inf, else fl(final_cost + fl(scale * lm final_cost[h])).  Its arcs are the arcs of s in their order: ilabel, olabel and
+ * acoustic_cost copied, nextstate the new number of (d, h'), graph_cost copied when olabel == 0, else fl(graph_cost + fl(scale * c)),
+ * c from advance.  start: the new number of (start, lm start).  The result is top-sorted, as the input was.
+ * status_h[n_utt], stats (either may be NULL); khg_lattices_op_status answers for the handle.  An utterance whose result has more
+ * than 2^31 - 1 states or arcs: KHG_E_ARG.  KHG_E_ARG before anything is launched: a handle or LM of another context, a scale that
+ * is not finite, hist_factor < 1.  The first call on a handle builds its in-arc index (as khg_lattices_posteriors does) and keeps it.
+ * Synchronous: one synchronisation per chunk sizes the output. */
+int khg_lattices_lm_rescore(khg_ctx *ctx, const khg_lattices *l, const khg_lm *lm, float scale, int32_t hist_factor,
+                            int32_t *status_h, khg_lm_rescore_stats *stats, khg_lattices **out);
 
 /* ---- K2M: MPE / sMBR posteriors of resident lattices (lattice-to-mpe-post, lattice-to-smbr-post) ------------------- */
 #define KHG_MPE_MPFE 0           /* an arc is correct when its phone is the reference's at that frame */

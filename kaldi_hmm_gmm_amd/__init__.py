@@ -15,6 +15,8 @@ from .align import (DecodableCtc, LatticeSimpleDecoder, LatticeSimpleDecoderConf
 from .align import Lattice, get_raw_lattice_simple_batch  # noqa: F401
 from .align import DeviceLattices, get_raw_lattice_simple_device_batch  # noqa: F401
 from .align import DevicePosteriors  # noqa: F401
+from .align import DeviceLm  # noqa: F401
+from .lm import NgramLm, estimate_ngram_lm  # noqa: F401
 from .align import get_raw_lattice_faster_batch, get_raw_lattice_faster_device_batch  # noqa: F401
 from .context_dep import (ContextDependency, ContextDependencyInterface, monophone_context_dependency,  # noqa: F401
                           monophone_context_dependency_shared)
@@ -51,7 +53,7 @@ from .scripts import (gmm_acc_stats, gmm_acc_stats_ali, gmm_acc_stats_ali_batch,
                       gmm_align_compiled_batch, gmm_boost_silence, gmm_est, gmm_est_gmm_ebw, gmm_est_weights_ebw, gmm_info, gmm_init_mono,
                       gmm_ismooth_stats, gmm_rescore_lattice, gmm_rescore_lattice_batch, gmm_sum_accs, lattice_boost_ali,
                       lattice_boost_ali_batch, gmm_acc_stats2, gmm_acc_stats2_batch, lattice_to_mpe_post, lattice_to_mpe_post_batch,
-                      lattice_to_smbr_post, lattice_to_smbr_post_batch)
+                      lattice_to_smbr_post, lattice_to_smbr_post_batch, lattice_lmrescore, lattice_lmrescore_batch)
 from .training_graph import (TrainingGraphCompiler, TrainingGraphCompilerOptions, equal_align, generate_hmm_topo,  # noqa: F401
                              make_lexicon_fst_with_silence)
 from .transition_model import (MleTransitionUpdateConfig, TransitionInformation, TransitionModel, TransitionModelTuple,  # noqa: F401

@@ -134,6 +134,10 @@ class RescoreStatsC(C.Structure):
     _fields_ = [("arcs", C.c_int64), ("emitting_arcs", C.c_int64), ("cells", C.c_int64)]
 
 
+class LmRescoreStatsC(C.Structure):
+    _fields_ = [("in_states", C.c_int64), ("in_arcs", C.c_int64), ("out_states", C.c_int64), ("out_arcs", C.c_int64), ("max_hist", C.c_int64)]
+
+
 # every symbol include/khg_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "khg_last_error": (C.c_char_p, []),
@@ -212,6 +216,13 @@ SIGNATURES = {
     "khg_lattices_op_status": (C.c_int, [vp, c_i32p]),
     "khg_lattices_boost": (C.c_int, [vp, vp, C.c_int32, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p, vp, C.c_float, C.c_float, c_i32p,
                                      C.POINTER(vp)]),
+    "khg_lm_validate": (C.c_int, [C.c_int32, c_i32p, c_f32p, c_i32p, c_i32p, c_f32p, c_i32p, c_f32p, C.c_int32]),
+    "khg_lm_create": (C.c_int, [vp, C.c_int32, c_i32p, c_f32p, c_i32p, c_i32p, c_f32p, c_i32p, c_f32p, C.c_int32, C.POINTER(vp)]),
+    "khg_lm_destroy": (C.c_int, [vp]),
+    "khg_lm_num_states": (C.c_int, [vp, c_i32p]),
+    "khg_lm_device_bytes": (C.c_int, [vp, c_i64p]),
+    "khg_lm_score": (C.c_int, [C.c_int32, c_i32p, c_f32p, c_i32p, c_i32p, c_f32p, c_i32p, c_f32p, C.c_int32, C.c_int32, c_i32p, c_f32p]),
+    "khg_lattices_lm_rescore": (C.c_int, [vp, vp, vp, C.c_float, C.c_int32, c_i32p, C.POINTER(LmRescoreStatsC), C.POINTER(vp)]),
     "khg_lattices_mpe_posteriors": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p, vp, C.c_int32, C.c_int32,
                                               C.c_float, C.c_float, c_i32p, c_f64p, c_f64p, C.POINTER(vp)]),
     "khg_posteriors_sizes": (C.c_int, [vp, c_i64p, c_i64p]),

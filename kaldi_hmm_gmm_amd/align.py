@@ -19,5 +19,6 @@ from ._kaldi_hmm_gmm_amd import (DecodableCtc, LatticeSimpleDecoder, LatticeSimp
 from ._kaldi_hmm_gmm_amd import Lattice, get_raw_lattice_simple_batch  # noqa: F401
 from ._kaldi_hmm_gmm_amd import DeviceLattices, get_raw_lattice_simple_device_batch  # noqa: F401
 from ._kaldi_hmm_gmm_amd import DevicePosteriors  # noqa: F401
+from ._kaldi_hmm_gmm_amd import DeviceLm  # noqa: F401
 from ._kaldi_hmm_gmm_amd import get_raw_lattice_faster_batch, get_raw_lattice_faster_device_batch  # noqa: F401
 from .device import ALIGN_ERROR, ALIGN_RETRIED, INT32_MAX  # noqa: F401

@@ -522,6 +522,83 @@ std::shared_ptr<Lattice> Lattice::Boost(const std::vector<int32_t>& tid2phone, c
   return r;
 }
 
+int BackoffLm::Advance(int h, int w, float* c) const {
+  float acc = 0.0f;
+  for (;;) {
+    const auto b = word.begin() + arc_begin[(size_t)h], e = word.begin() + arc_begin[(size_t)h + 1];
+    const auto it = std::lower_bound(b, e, w);
+    if (it != e && *it == w) { *c = acc + cost[(size_t)(it - word.begin())]; return next[(size_t)(it - word.begin())]; }
+    if (h == 0) { *c = acc; return -1; }
+    acc = acc + backoff_cost[(size_t)h];
+    h = backoff[(size_t)h];
+  }
+}
+
+LatticeLmRescored Lattice::LmRescore(const BackoffLm& lm, float scale, int hist_factor) const {
+  KHG_REQUIRE(std::isfinite(scale), "Lattice::LmRescore: scale must be finite");
+  KHG_REQUIRE(hist_factor >= 1, "Lattice::LmRescore: hist_factor must be >= 1");
+  LatticeLmRescored out;
+  auto r = std::make_shared<Lattice>();
+  r->arc_begin.push_back(0);
+  out.lattice = r;
+  const int N = NumStates();
+  if (N == 0) { out.status = KHG_LAT_NO_PATH; return out; }
+  for (int s = 0; s < N; ++s)
+    for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a)
+      if (nextstate[(size_t)a] <= s) { out.status = KHG_LAT_EPS_LOOP; return out; }
+  // the history sets in state order; an arc is looked at when its source's set is known, so every set is complete when its turn comes
+  const int64_t cap = std::min<int64_t>((int64_t)hist_factor * N, INT32_MAX);
+  std::vector<std::vector<int32_t>> H((size_t)N);
+  H[(size_t)start].push_back(lm.start);
+  int64_t used = 0, max_hist = 0;
+  for (int d = 0; d < N; ++d) {
+    std::vector<int32_t>& hd = H[(size_t)d];
+    if (std::find(hd.begin(), hd.end(), -1) != hd.end()) { out.status = KHG_LAT_LM_OOV; return out; }
+    std::sort(hd.begin(), hd.end());
+    hd.erase(std::unique(hd.begin(), hd.end()), hd.end());
+    used += (int64_t)hd.size();
+    if (used > cap) { out.status = KHG_LAT_SCRATCH; return out; }
+    max_hist = std::max<int64_t>(max_hist, (int64_t)hd.size());
+    for (int32_t a = arc_begin[(size_t)d]; a < arc_begin[(size_t)d + 1]; ++a)
+      for (int32_t h : hd) {
+        float c;
+        H[(size_t)nextstate[(size_t)a]].push_back(olabel[(size_t)a] == 0 ? h : lm.Advance(h, olabel[(size_t)a], &c));
+      }
+  }
+  std::vector<int64_t> first((size_t)N + 1, 0);
+  for (int s = 0; s < N; ++s) first[(size_t)s + 1] = first[(size_t)s] + (int64_t)H[(size_t)s].size();
+  const float INF = std::numeric_limits<float>::infinity();
+  for (int s = 0; s < N; ++s)
+    for (int32_t h : H[(size_t)s]) {
+      r->frame.push_back(frame[(size_t)s]); r->graph_state.push_back(graph_state[(size_t)s]);
+      r->tot_cost.push_back(tot_cost[(size_t)s]); r->extra_cost.push_back(extra_cost[(size_t)s]);
+      float f = final_cost[(size_t)s];
+      if (f != INF) { const float t = scale * lm.final_cost[(size_t)h]; f = f + t; }
+      r->final_cost.push_back(f);
+      for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) {
+        const int d = nextstate[(size_t)a], w = olabel[(size_t)a];
+        float g = graph_cost[(size_t)a];
+        int32_t hh = h;
+        if (w != 0) {
+          float c;
+          hh = lm.Advance(h, w, &c);
+          const float t = scale * c;
+          g = g + t;
+        }
+        const std::vector<int32_t>& hd = H[(size_t)d];
+        r->ilabel.push_back(ilabel[(size_t)a]); r->olabel.push_back(w); r->graph_cost.push_back(g);
+        r->acoustic_cost.push_back(acoustic_cost[(size_t)a]);
+        r->nextstate.push_back((int32_t)(first[(size_t)d] + (std::lower_bound(hd.begin(), hd.end(), hh) - hd.begin())));
+      }
+      KHG_REQUIRE(r->ilabel.size() <= (size_t)INT32_MAX, "Lattice::LmRescore: more than 2^31 - 1 arcs");
+      r->arc_begin.push_back((int32_t)r->ilabel.size());
+    }
+  r->start = (int32_t)first[(size_t)start];
+  out.status = KHG_LAT_SUCCEEDED;
+  out.max_hist = max_hist;
+  return out;
+}
+
 std::shared_ptr<Lattice> Lattice::Prune(float beam, float gs, float as, int* status) const {
   KHG_REQUIRE(beam >= 0.0f, "Lattice::Prune: beam must be >= 0");
   auto out = std::make_shared<Lattice>();

@@ -131,6 +131,23 @@ struct LatticeMpePosteriors : LatticePosteriors {
   std::vector<double> acc_fwd, acc_bwd;      // A, B
 };
 
+// A backoff n-gram LM as the flat arrays of khg_lm_create (include/khg_hip.h): state 0 is the empty history, state h
+// owns the arcs arc_begin[h] .. arc_begin[h + 1] with words ascending.  Not validated here: khg_lm_validate does that.
+struct BackoffLm {
+  std::vector<int32_t> backoff, arc_begin, word, next;
+  std::vector<float> backoff_cost, cost, final_cost;
+  int32_t start = 0;
+  // advance(h, w): -> the next state and *c (float sums, one rounding each), or -1: out of vocabulary
+  int Advance(int h, int w, float* c) const;
+};
+class Lattice;
+// Lattice::LmRescore: the KHG_LAT_* status, the rescored lattice (empty without KHG_LAT_SUCCEEDED) and the largest |H(s)|
+struct LatticeLmRescored {
+  int status = 0;
+  std::shared_ptr<Lattice> lattice;
+  int64_t max_hist = 0;
+};
+
 // The fst::VectorFst<LatticeArc> LatticeSimpleDecoder::GetRawLattice builds (csrc/lattice-simple-decoder.cc:654-735), as the flat arrays
 // khg_lattices_download hands back: a state per surviving token, numbered by frame, then by graph state (:684-690); state s owns arcs
 // arc_begin[s] .. arc_begin[s + 1], one per surviving forward link in the order of the graph's arcs in its state (:700-722); the last
@@ -190,6 +207,10 @@ class Lattice {
   // 1 .. tid2phone.size() - 1 per frame of the lattice, and every ilabel lies in that range.
   std::shared_ptr<Lattice> Boost(const std::vector<int32_t>& tid2phone, const std::vector<int32_t>& silence_phones,
                                  const std::vector<int32_t>& alignment, float b, float max_silence_error) const;
+  // lattice-lmrescore (what khg_lattices_lm_rescore gives for one lattice): every state split by the LM histories that
+  // reach it, every arc with a word given fl(scale * the LM's cost of the word) more graph cost; the rule is stated at
+  // khg_lattices_lm_rescore.  The history sets may hold min(hist_factor * states, 2^31 - 1) entries together (KHG_LAT_SCRATCH).
+  LatticeLmRescored LmRescore(const BackoffLm& lm, float scale = 1.0f, int hist_factor = 8) const;
   // Kaldi's text form of a lattice: "src dst ilabel olabel graph,acoustic" per arc, "state graph,acoustic" per final state
   std::string ToText() const;
 

@@ -4,7 +4,8 @@
 // khg_decode_lattice_simple_raw, khg_k2_lattice_raw.hip.inc); the handle of resident lattices (khg_lattices) with the operations on it
 // (khg_k2_lattice_ops.hip.inc), its forward-backward posteriors (khg_posteriors, khg_k2_lattice_post.hip.inc) and their MPE / sMBR form
 // (khg_k2_lattice_mpe.hip.inc: the same device functions and the same host steps per chunk around a kernel of its own), and rescoring /
-// boosting (khg_lattices_rescore, khg_lattices_boost: khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc).  gfx950 only.
+// boosting (khg_lattices_rescore, khg_lattices_boost: khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc), and the backoff n-gram LM
+// (khg_lm) with khg_lattices_lm_rescore (khg_k2_lattice_lm.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
 
 #include <memory>
@@ -20,6 +21,7 @@
 #include "khg_k1_cells.hip.inc"
 #include "khg_k2_lattice_rescore.hip.inc"
 #include "khg_k2_lattice_mpe.hip.inc"
+#include "khg_k2_lattice_lm.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // The raw lattices of one batch (khg_decode_lattice_simple_raw, khg_decode_lattice_faster_raw): per chunk of scratch slices one
@@ -46,7 +48,7 @@ struct khg_lattices {
   // [in_begin: states + utterances | in_arc: arcs | arc_src: arcs] (int32)
   std::vector<int32_t*> idx_d;
   khg_ctx* ctx = nullptr;                        // the context it was made on
-  std::vector<int32_t> op_status;                // [U] KHG_LAT_* bits of the khg_lattices_rescore / _boost that made it (empty otherwise)
+  std::vector<int32_t> op_status;                // [U] KHG_LAT_* bits of the khg_lattices_rescore / _boost / _lm_rescore that made it (empty otherwise)
 };
 
 namespace {
@@ -1436,7 +1438,7 @@ void k2x_status(const khg_lattices* in, const std::vector<char>& drop, khg_latti
 
 extern "C" int khg_lattices_op_status(const khg_lattices* l, int32_t* status_h) {
   if (!l || !status_h) return khg_set_error(KHG_E_ARG, "khg_lattices_op_status: bad arguments");
-  if ((int)l->op_status.size() != l->U) return khg_set_error(KHG_E_ARG, "khg_lattices_op_status: the handle was not made by khg_lattices_rescore or khg_lattices_boost");
+  if ((int)l->op_status.size() != l->U) return khg_set_error(KHG_E_ARG, "khg_lattices_op_status: the handle was not made by khg_lattices_rescore, khg_lattices_boost or khg_lattices_lm_rescore");
   std::copy(l->op_status.begin(), l->op_status.end(), status_h);
   return KHG_OK;
 }
@@ -1740,4 +1742,183 @@ extern "C" int khg_lattices_mpe_posteriors(khg_ctx* ctx, const khg_lattices* lc,
     if ((rc = post_chunk_finish(r, k, &q.po))) return rc;       // the fill sums arc_post: here the signed values
   }
   return post_run_finish(r, status_h, tot_like_h, avg_d, avg_acc_h, out);       // synchronises: the scratch goes with `r` and `ref`
+}
+
+// ------------------------------------------------------------------------------------------
+// K2N: the backoff n-gram LM and lattice-lmrescore (khg_k2_lattice_lm.hip.inc)
+struct khg_lm {
+  khg_ctx* ctx = nullptr;
+  int32_t n_states = 0, start = 0;
+  int64_t n_arcs = 0, bytes = 0;
+  unsigned char* buf = nullptr;       // backoff | backoff_cost | final_cost | arc_begin | word | cost | next, each at a multiple of 256 bytes
+  LmDev dev;
+};
+
+extern "C" int khg_lm_validate(int32_t n_states, const int32_t* backoff, const float* backoff_cost, const int32_t* arc_begin, const int32_t* word,
+                               const float* cost, const int32_t* next, const float* final_cost, int32_t start) {
+  const std::string who = "khg_lm_validate: ";
+  if (n_states < 1 || !backoff || !backoff_cost || !arc_begin || !final_cost) return khg_set_error(KHG_E_ARG, who + "bad arguments (at least the empty history, no NULL array)");
+  if (arc_begin[0] != 0) return khg_set_error(KHG_E_ARG, who + "arc_begin must start at 0");
+  for (int32_t h = 0; h < n_states; ++h)
+    if (arc_begin[h + 1] < arc_begin[h]) return khg_set_error(KHG_E_ARG, who + "arc_begin not monotone at state " + std::to_string(h));
+  if (arc_begin[n_states] > 0 && (!word || !cost || !next)) return khg_set_error(KHG_E_ARG, who + "bad arguments (an arc array is NULL)");
+  if (start < 0 || start >= n_states) return khg_set_error(KHG_E_ARG, who + "start out of range");
+  if (backoff[0] != -1) return khg_set_error(KHG_E_ARG, who + "backoff[0] must be -1 (the empty history backs off to nothing)");
+  for (int32_t h = 0; h < n_states; ++h) {
+    const std::string at = "state " + std::to_string(h) + ": ";
+    if (h > 0 && (backoff[h] < 0 || backoff[h] >= h)) return khg_set_error(KHG_E_ARG, who + at + "backoff must name a lower state");
+    if (!std::isfinite(backoff_cost[h])) return khg_set_error(KHG_E_ARG, who + at + "backoff_cost is not finite");
+    if (!std::isfinite(final_cost[h])) return khg_set_error(KHG_E_ARG, who + at + "final_cost is not finite");
+    for (int32_t a = arc_begin[h]; a < arc_begin[h + 1]; ++a) {
+      const std::string arc = at + "arc " + std::to_string(a) + ": ";
+      if (word[a] <= 0) return khg_set_error(KHG_E_ARG, who + arc + "word must be > 0");
+      if (a > arc_begin[h] && word[a] <= word[a - 1]) return khg_set_error(KHG_E_ARG, who + arc + "words must ascend strictly inside a state");
+      if (!std::isfinite(cost[a])) return khg_set_error(KHG_E_ARG, who + arc + "cost is not finite");
+      if (next[a] < 0 || next[a] >= n_states) return khg_set_error(KHG_E_ARG, who + arc + "next out of range");
+    }
+  }
+  return KHG_OK;
+}
+
+extern "C" int khg_lm_score(int32_t n_states, const int32_t* backoff, const float* backoff_cost, const int32_t* arc_begin, const int32_t* word,
+                            const float* cost, const int32_t* next, const float* final_cost, int32_t start, int32_t n_words, const int32_t* words,
+                            float* cost_out) {
+  int rc = khg_lm_validate(n_states, backoff, backoff_cost, arc_begin, word, cost, next, final_cost, start);
+  if (rc) return rc;
+  if (n_words < 0 || (n_words > 0 && !words) || !cost_out) return khg_set_error(KHG_E_ARG, "khg_lm_score: bad arguments");
+  int32_t h = start;
+  volatile float total = 0.0f;       // (volatile: every sum is rounded to float where it is written)
+  for (int32_t i = 0; i < n_words; ++i) {
+    const int32_t w = words[i];
+    if (w <= 0) return khg_set_error(KHG_E_ARG, "khg_lm_score: word " + std::to_string(i) + " is not > 0");
+    volatile float c = 0.0f;
+    for (;;) {
+      const int32_t* lo = std::lower_bound(word + arc_begin[h], word + arc_begin[h + 1], w);
+      if (lo != word + arc_begin[h + 1] && *lo == w) { c = c + cost[lo - word]; h = next[lo - word]; break; }
+      if (h == 0) return khg_set_error(KHG_E_ARG, "khg_lm_score: word " + std::to_string(i) + " (" + std::to_string(w) + ") is out of vocabulary");
+      c = c + backoff_cost[h];
+      h = backoff[h];
+    }
+    total = total + c;
+  }
+  total = total + final_cost[h];
+  *cost_out = total;
+  return KHG_OK;
+}
+
+extern "C" int khg_lm_destroy(khg_lm* lm) {
+  if (!lm) return KHG_OK;
+  if (lm->buf) (void)hipFree(lm->buf);
+  delete lm;
+  return KHG_OK;
+}
+extern "C" int khg_lm_num_states(const khg_lm* lm, int32_t* n_states) {
+  if (!lm || !n_states) return khg_set_error(KHG_E_ARG, "khg_lm_num_states: bad arguments");
+  *n_states = lm->n_states;
+  return KHG_OK;
+}
+extern "C" int khg_lm_device_bytes(const khg_lm* lm, int64_t* bytes) {
+  if (!lm || !bytes) return khg_set_error(KHG_E_ARG, "khg_lm_device_bytes: bad arguments");
+  *bytes = lm->bytes;
+  return KHG_OK;
+}
+
+extern "C" int khg_lm_create(khg_ctx* ctx, int32_t n_states, const int32_t* backoff, const float* backoff_cost, const int32_t* arc_begin,
+                             const int32_t* word, const float* cost, const int32_t* next, const float* final_cost, int32_t start, khg_lm** out) {
+  if (ctx_dead(ctx) || !out) return khg_set_error(KHG_E_ARG, "khg_lm_create: bad arguments");
+  *out = nullptr;
+  int rc = khg_lm_validate(n_states, backoff, backoff_cost, arc_begin, word, cost, next, final_cost, start);
+  if (rc) return rc;
+  struct LmFree { void operator()(khg_lm* m) const { (void)khg_lm_destroy(m); } };
+  std::unique_ptr<khg_lm, LmFree> lm(new khg_lm);
+  lm->ctx = ctx; lm->n_states = n_states; lm->start = start; lm->n_arcs = arc_begin[n_states];
+  const int64_t S = n_states, A = lm->n_arcs;
+  const int64_t cnt[7] = {S, S, S, S + 1, A, A, A};
+  const void* src[7] = {backoff, backoff_cost, final_cost, arc_begin, word, cost, next};
+  int64_t o[7], total = 0;
+  for (int k = 0; k < 7; ++k) { o[k] = total; total += (4 * cnt[k] + 255) & ~int64_t(255); }
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&lm->buf), (size_t)std::max<int64_t>(total, 16)));
+  lm->bytes = total;
+  if ((rc = arena_flush(ctx))) return rc;
+  for (int k = 0; k < 7; ++k)
+    if (cnt[k]) HIPCHK(hipMemcpyAsync(lm->buf + o[k], src[k], 4 * (size_t)cnt[k], hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));        // the host arrays are the caller's again
+  auto i = [&](int k) { return reinterpret_cast<const int32_t*>(lm->buf + o[k]); };
+  auto f = [&](int k) { return reinterpret_cast<const float*>(lm->buf + o[k]); };
+  lm->dev.backoff = i(0); lm->dev.backoff_cost = f(1); lm->dev.fin = f(2); lm->dev.arc_begin = i(3); lm->dev.word = i(4); lm->dev.cost = f(5);
+  lm->dev.next = i(6); lm->dev.start = start;
+  *out = lm.release();
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_lm_rescore(khg_ctx* ctx, const khg_lattices* lc, const khg_lm* lm, float scale, int32_t hist_factor, int32_t* status_h,
+                                       khg_lm_rescore_stats* stats, khg_lattices** out) {
+  const std::string who = "khg_lattices_lm_rescore: ";
+  if (ctx_dead(ctx) || !lc || !lm || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  *out = nullptr;
+  if (lc->ctx != ctx || lm->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (!std::isfinite(scale)) return khg_set_error(KHG_E_ARG, who + "scale must be finite");
+  if (hist_factor < 1) return khg_set_error(KHG_E_ARG, who + "hist_factor must be >= 1");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  LatPtr res;
+  int rc = new_lattices(ctx, U, &res);
+  if (rc) return rc;
+  if (stats) *stats = khg_lm_rescore_stats{0, 0, 0, 0, 0};
+  if (U == 0) { *out = res.release(); return KHG_OK; }
+  rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc) rc = lat_index(ctx, l);
+  if (rc) return rc;
+  DevBlocks dv;
+  int32_t *status_d, *maxh_d;
+  if ((rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &maxh_d))) return rc;
+  std::vector<int64_t> so, ao;
+  for (size_t k = 0; k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    LmArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p.lo);
+    p.lo.status = status_d; p.lo.o_start = res->start_d;
+    p.lm = lm->dev; p.scale = scale; p.hist_factor = hist_factor; p.max_hist = maxh_d;
+    const LatIndex ix = lat_index_arrays(l->idx_d[k], c);
+    p.in_begin = ix.in_begin; p.in_arc = ix.in_arc; p.arc_src = ix.arc_src;
+    const int64_t cells = std::max<int64_t>(c.ns, 1);
+    if ((rc = dv.alloc((int64_t)hist_factor * cells, &p.arena)) || (rc = dv.alloc((int64_t)hist_factor * cells, &p.tmp)) ||
+        (rc = dv.alloc(cells + c.n, &p.set_off)) || (rc = dv.alloc(cells, &p.arc_base)) || (rc = dv.alloc(2 * (int64_t)c.n, &p.lo.utt_tot)) ||
+        (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.lo.utt_off)))
+      return rc;
+    {
+      KernelTimer kt(ctx, "k2_lattice_lm_mark");
+      KHG_LAUNCH(ctx, k2_lattice_lm_mark, dim3((unsigned)c.n), dim3(LM_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    rc = scan_pairs_and_read(ctx, "k2_lattice_lm_scan", p.lo.utt_tot, p.lo.utt_off, c.n, &so, &ao);      // the one synchronisation that sizes the output
+    if (!rc) rc = add_chunk_counts("khg_lattices_lm_rescore", c.u0, so, ao, &res->state_off, &res->arc_off);
+    if (rc) return rc;
+    LatChunk ch;
+    ch.u0 = c.u0; ch.n = c.n; ch.ns = so[(size_t)c.n]; ch.na = ao[(size_t)c.n];
+    if ((rc = lat_chunk_alloc(&ch, &res->bytes))) return rc;
+    res->chunks.push_back(ch);
+    lat_chunk_arrays(ch, &p.lo.out);
+    {
+      KernelTimer kt(ctx, "k2_lattice_lm_fill");
+      KHG_LAUNCH(ctx, k2_lattice_lm_fill, dim3((unsigned)c.n, stripes(chunk_max(res->state_off, c), LM_NT, c.n)), dim3(LM_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  std::vector<int32_t> st((size_t)U), mh((size_t)U);
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(mh.data(), maxh_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  rc = check_err_flag(ctx, "khg_lattices_lm_rescore");     // synchronises: the scratch goes with `dv`
+  if (rc) return rc;
+  res->op_status = st;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (stats) {
+    stats->in_states = l->state_off[(size_t)U]; stats->in_arcs = l->arc_off[(size_t)U];
+    stats->out_states = res->state_off[(size_t)U]; stats->out_arcs = res->arc_off[(size_t)U];
+    for (int32_t m : mh) stats->max_hist = std::max<int64_t>(stats->max_hist, m);
+  }
+  *out = res.release();
+  return KHG_OK;
 }

@@ -324,6 +324,40 @@ void FlattenAlignments(const std::string& who, py::object alignment, int U, std:
   }
   ali->push_back(0);      // (never a NULL array)
 }
+// an NgramLm (anything with to_arrays() -> {"backoff", "backoff_cost", "arc_begin", "word", "cost", "next", "final_cost", "start"}) as
+// the host's BackoffLm; checked by khg_lm_validate
+BackoffLm LmOf(py::object lm) {
+  py::dict d = lm.attr("to_arrays")().cast<py::dict>();
+  BackoffLm r;
+  r.backoff = VecOf<int32_t>(d["backoff"]); r.backoff_cost = VecOf<float>(d["backoff_cost"]); r.arc_begin = VecOf<int32_t>(d["arc_begin"]);
+  r.word = VecOf<int32_t>(d["word"]); r.cost = VecOf<float>(d["cost"]); r.next = VecOf<int32_t>(d["next"]);
+  r.final_cost = VecOf<float>(d["final_cost"]); r.start = d["start"].cast<int32_t>();
+  const size_t S = r.backoff.size();
+  if (S < 1 || r.backoff_cost.size() != S || r.final_cost.size() != S || r.arc_begin.size() != S + 1)
+    throw Error("khg_lm_validate: one backoff, backoff_cost and final_cost per state, one arc_begin more");
+  for (size_t h = 0; h < S; ++h) if (r.arc_begin[h + 1] < r.arc_begin[h] || r.arc_begin[0] != 0) throw Error("khg_lm_validate: arc_begin must run from 0, monotone");
+  const size_t A = (size_t)r.arc_begin[S];
+  if (r.word.size() != A || r.cost.size() != A || r.next.size() != A) throw Error("khg_lm_validate: one word, cost and next per arc");
+  CApi(khg_lm_validate((int32_t)S, r.backoff.data(), r.backoff_cost.data(), r.arc_begin.data(), r.word.data(), r.cost.data(), r.next.data(),
+                       r.final_cost.data(), r.start));
+  return r;
+}
+// DeviceLm: owns a khg_lm handle (a backoff n-gram LM resident on the device)
+struct PyDeviceLm {
+  khg_lm* h = nullptr;
+  khg_ctx* ctx = nullptr;
+  py::object ctx_obj;
+  PyDeviceLm() = default;
+  PyDeviceLm(const PyDeviceLm&) = delete;
+  PyDeviceLm& operator=(const PyDeviceLm&) = delete;
+  ~PyDeviceLm() { close(); }
+  void close() { if (h) { khg_lm_destroy(h); h = nullptr; } }
+};
+py::dict LmStatsDict(const khg_lm_rescore_stats& s) {
+  py::dict d;
+  d["in_states"] = s.in_states; d["in_arcs"] = s.in_arcs; d["out_states"] = s.out_states; d["out_arcs"] = s.out_arcs; d["max_hist"] = s.max_hist;
+  return d;
+}
 }  // namespace
 
 void BindLattice(py::module_& m) {
@@ -407,6 +441,14 @@ void BindLattice(py::module_& m) {
       .def("boost", [](const Lattice& l, std::vector<int32_t> tid2phone, std::vector<int32_t> silence_phones, std::vector<int32_t> alignment, float b,
                        float max_silence_error) { return l.Boost(tid2phone, silence_phones, alignment, b, max_silence_error); },
            py::arg("tid2phone"), py::arg("silence_phones"), py::arg("alignment"), py::arg("b") = 0.1f, py::arg("max_silence_error") = 0.0f)
+      // lattice-lmrescore on the host (what DeviceLattices.lm_rescore gives for this lattice): lm is an NgramLm ->
+      // (Lattice, status, stats)
+      .def("lm_rescore", [](const Lattice& l, py::object lm, float scale, int hist_factor) {
+        const BackoffLm b = LmOf(lm);
+        const LatticeLmRescored r = l.LmRescore(b, scale, hist_factor);
+        khg_lm_rescore_stats s = {l.NumStates(), l.NumArcs(), r.lattice->NumStates(), r.lattice->NumArcs(), r.max_hist};
+        return py::make_tuple(r.lattice, r.status, LmStatsDict(s));
+      }, py::arg("lm"), py::arg("scale") = 1.0f, py::arg("hist_factor") = 8)
       .def("to_text", &Lattice::ToText)
       .def("__str__", &Lattice::ToText)
       .def_property_readonly("frame", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.frame, l.frame.size()); })
@@ -638,6 +680,22 @@ void BindLattice(py::module_& m) {
         return r;
       }, py::arg("tid2phone"), py::arg("silence_phones"), py::arg("alignment") = py::none(), py::arg("ali_set") = py::none(), py::arg("criterion") = "smbr",
          py::arg("tid2pdf") = py::none(), py::arg("one_silence_class") = true, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      // lattice-lmrescore -> (a new DeviceLattices carrying .status, status, stats): lm is a DeviceLm of the same context
+      .def("lm_rescore", [](PyDeviceLattices& d, PyDeviceLm& lm, float scale, int hist_factor) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        if (!lm.h) throw Error("DeviceLm: closed");
+        const int U = (int)LatSizes(d).first.size() - 1;
+        auto r = std::make_shared<PyDeviceLattices>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj;
+        r->status.assign((size_t)std::max(U, 1), 0);
+        khg_lm_rescore_stats st = {0, 0, 0, 0, 0};
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_lm_rescore(d.ctx, d.h, lm.h, scale, hist_factor, r->status.data(), &st, &r->h));
+        }
+        r->status.resize((size_t)U);
+        return py::make_tuple(r, Vec1(r->status), LmStatsDict(st));
+      }, py::arg("lm"), py::arg("scale") = 1.0f, py::arg("hist_factor") = 8)
       .def("download", [](PyDeviceLattices& d) {
         if (!d.h) throw Error("DeviceLattices: closed");
         std::vector<std::shared_ptr<Lattice>> out;
@@ -648,6 +706,33 @@ void BindLattice(py::module_& m) {
         return out;
       })
       .def("close", &PyDeviceLattices::close);
+
+  // DeviceLm(lm, ctx=None): an NgramLm uploaded (khg_lm_create); the handle belongs to its context
+  py::class_<PyDeviceLm, std::shared_ptr<PyDeviceLm>>(m, "DeviceLm")
+      .def(py::init([](py::object lm, py::object ctx) {
+        const BackoffLm b = LmOf(lm);
+        auto d = std::make_shared<PyDeviceLm>();
+        d->ctx_obj = ctx;
+        d->ctx = ctx.is_none() ? DefaultCtx() : reinterpret_cast<khg_ctx*>(ctx.attr("h").cast<uintptr_t>());
+        CApi(khg_lm_create(d->ctx, (int32_t)b.backoff.size(), b.backoff.data(), b.backoff_cost.data(), b.arc_begin.data(), b.word.data(), b.cost.data(),
+                           b.next.data(), b.final_cost.data(), b.start, &d->h));
+        return d;
+      }), py::arg("lm"), py::arg("ctx") = py::none())
+      .def_property_readonly("h", [](PyDeviceLm& d) { return reinterpret_cast<uintptr_t>(d.h); })
+      .def_readonly("ctx", &PyDeviceLm::ctx_obj)
+      .def_property_readonly("num_states", [](PyDeviceLm& d) {
+        if (!d.h) throw Error("DeviceLm: closed");
+        int32_t n = 0;
+        CApi(khg_lm_num_states(d.h, &n));
+        return (int)n;
+      })
+      .def_property_readonly("device_bytes", [](PyDeviceLm& d) {
+        if (!d.h) throw Error("DeviceLm: closed");
+        int64_t b = 0;
+        CApi(khg_lm_device_bytes(d.h, &b));
+        return b;
+      })
+      .def("close", &PyDeviceLm::close);
 
   // DevicePosteriors: the arc and per-frame transition-id posteriors of a batch of lattices, resident on the device
   auto post_sizes = [](PyDevicePosteriors& d) {

@@ -15,7 +15,7 @@ struct PyDeviceLattices {
   khg_lattices* h = nullptr;
   khg_ctx* ctx = nullptr;
   pybind11::object ctx_obj;          // keeps a Python Context alive (None: the default context)
-  std::vector<int32_t> status;       // of the prune / rescore / boost that made it (empty otherwise)
+  std::vector<int32_t> status;       // of the prune / rescore / boost / lm_rescore that made it (empty otherwise)
   bool has_rescore_stats = false;    // made by rescore: the counts of khg_rescore_stats
   khg_rescore_stats rescore_stats = {0, 0, 0};
   PyDeviceLattices() = default;

@@ -309,6 +309,35 @@ def lattice_boost_ali(transition_model: TransitionModel, lattice, alignment: Seq
     return lattice_boost_ali_batch(transition_model, [lattice], [alignment], silence_phones, b, max_silence_error)[0]
 
 
+def lattice_lmrescore_batch(lm, lattices, scale: float = 1.0, hist_factor: int = 8):
+    """Kaldi's lattice-lmrescore for several utterances on the device (khg_lattices_lm_rescore): every state is split by
+    the histories of the backoff n-gram `lm` (an NgramLm) that reach it, every arc with a word gets graph_cost += scale * the LM's cost
+    of the word; scale -1 takes an LM out again.  An utterance with a word the LM lacks (or whose history sets outgrow hist_factor
+    entries per state) gets an empty lattice.  lattices: a list of Lattice (-> a list of Lattice) or a DeviceLattices on the default
+    context (-> a DeviceLattices with .status)."""
+    from .align import DeviceLattices, DeviceLm
+    ctx = _gpu.default_context()
+    on_device = isinstance(lattices, DeviceLattices)
+    dl = lattices if on_device else DeviceLattices.from_lattices(list(lattices), ctx)
+    dlm = DeviceLm(lm, ctx)
+    try:
+        res, _, _ = dl.lm_rescore(dlm, float(scale), int(hist_factor))
+    finally:
+        dlm.close()
+        if not on_device:
+            dl.close()
+    if on_device:
+        return res
+    out = res.download()
+    res.close()
+    return out
+
+
+def lattice_lmrescore(lm, lattice, scale: float = 1.0, hist_factor: int = 8):
+    """Kaldi's lattice-lmrescore for one utterance -> the rescored Lattice (lattice_lmrescore_batch of one)."""
+    return lattice_lmrescore_batch(lm, [lattice], scale, hist_factor)[0]
+
+
 def _lattice_to_mpe_post_batch(criterion, transition_model, lattices, alignments, silence_phones, one_silence_class, acoustic_scale, lm_scale):
     from .align import DeviceLattices
     on_device = isinstance(lattices, DeviceLattices)

@@ -51,7 +51,12 @@ self-loops and are refused with KHG_LAT_EPS_LOOP: use --decoder faster.)
 --mpe [--criterion mpe|smbr] (next to --lattices) times DeviceLattices.mpe_posteriors(1, 0.1) alternated with posteriors(1, 0.1) on
 the same handle, and khg_acc_stats_post2 alternated with khg_acc_stats_post on the signed posteriors.
 
-Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post] [--acc] [--mpe]
+--lmrescore [ORDER] (next to --lattices) times DeviceLattices.lm_rescore on the resident lattices with a backoff n-gram of that order
+(default 2) estimated from the decoded word sequences: mark / scan / fill device times, the call beside a fresh decode, the growth in
+states and arcs and the largest history set (DESIGN.md 7r).  The linear training graphs carry no words (every state keeps one history);
+with --shared-graph the lattices come from the --words word loop, whose words the n-gram covers.
+
+Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post] [--acc] [--mpe] [--lmrescore [ORDER]]
        python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
@@ -442,6 +447,33 @@ def rescore_bench(ctx, dl, am, tm, fsts, feats, alignments, cfg, reps, boost):
     return out
 
 
+def lmrescore_bench(ctx, dl, transcripts, vocab, order, reps, decode_call_s):
+    """--lmrescore [ORDER]: khg_lattices_lm_rescore on the resident lattices with a backoff n-gram estimated from the decoded word
+    sequences over the graphs' vocabulary -- device time of mark / scan / fill, the call from the host beside a fresh decode of the same
+    set, the growth in states and arcs and the largest history set."""
+    reps = max(reps, 3)
+    lm = khg.estimate_ngram_lm(transcripts, order, vocab, 0.5)
+    dlm = khg.DeviceLm(lm, ctx)
+    dl.lm_rescore(dlm, 1.0)[0].close(); ctx.sync()                       # warm-up (builds the in-arc index once)
+    k_ms, t_call, stats, st = [], [], None, None
+    for _ in range(reps):
+        k_ms.append(kernel_ms(ctx, lambda: dl.lm_rescore(dlm, 1.0)[0].close()))
+        ctx.sync(); t0 = time.time()
+        R, st, stats = dl.lm_rescore(dlm, 1.0)
+        t_call.append(time.time() - t0)
+        R.close()
+    ms = {k: float(np.median([r.get(k, 0.0) for r in k_ms])) for k in sorted({k for r in k_ms for k in r})}
+    out = {"order": order, "lm_states": lm.num_states, "lm_arcs": lm.num_arcs, "lm_device_bytes": dlm.device_bytes, "repetitions": reps,
+           "kernels_ms": ms, "kernels_total_ms": sum(ms.values()), "call": med(t_call), "decode_call": decode_call_s,
+           "call_over_decode": float(np.median(t_call)) / decode_call_s["median_s"] if decode_call_s else None,
+           "succeeded": int((np.asarray(st) & 1 != 0).sum()), "oov": int((np.asarray(st) & 1024 != 0).sum()),
+           "scratch": int((np.asarray(st) & 4 != 0).sum()),
+           "state_growth": stats["out_states"] / max(stats["in_states"], 1), "arc_growth": stats["out_arcs"] / max(stats["in_arcs"], 1)}
+    out.update(stats)
+    dlm.close()
+    return out
+
+
 def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
     """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
     after one warm-up round; and the last results."""
@@ -601,6 +633,20 @@ def shared_graph_main(args):
                 match += (r["succeeded"], r["alignment"], r["words"], r["like"]) == (want["succeeded"], want["alignment"], want["words"], want["like"]) \
                     and last[key]["ali"][fo[u]: fo[u + 1]].tolist() == r["alignment"]
             entry.update(checked_against_restatement=n, restatement_matches=match)
+        if args.lmrescore and name == "faster":
+            # lattice-lmrescore on the lattices the shared set leaves on the device, beside decoding that set again
+            dec = dict(beam=13.0, max_active=7000, lattice_beam=6.0, acoustic_scale=0.1)
+            L = sh.raw_lattices_faster_device(dtm, **dec)["lattices"]
+            t_dec = []
+            for _ in range(max(args.reps, 3)):
+                ctx.sync(); t0 = time.time()
+                sh.raw_lattices_faster_device(dtm, **dec)["lattices"].close()
+                t_dec.append(time.time() - t0)
+            bp = L.best_path(np.ones(1, np.float32), np.ones(1, np.float32))
+            wo = bp["words_off"]
+            transcripts = [bp["words"][wo[u]: wo[u + 1]].tolist() for u in range(U)]
+            entry["lmrescore"] = lmrescore_bench(ctx, L, transcripts, range(1, args.words + 1), args.lmrescore, args.reps, med(t_dec))
+            L.close()
         for us in sets.values():
             us.close()
         dg.close()
@@ -633,6 +679,8 @@ def main():
     ap.add_argument("--rescore", action="store_true", help="with --lattices (--decoder faster): khg_lattices_rescore on the resident lattices, and "
                     "one MMI iteration's denominator side with it against decoding again")
     ap.add_argument("--boost", type=float, default=0.0, metavar="B", help="with --rescore: also khg_lattices_boost at this b")
+    ap.add_argument("--lmrescore", type=int, nargs="?", const=2, default=0, metavar="ORDER", help="with --lattices (--decoder faster): "
+                    "khg_lattices_lm_rescore on the resident lattices with an n-gram of this order (2) estimated from the decoded words")
     args = ap.parse_args()
     if (args.sweep or args.prune_beam is not None or args.post) and not args.lattices:
         ap.error("--sweep / --prune-beam / --post need --lattices")
@@ -640,6 +688,8 @@ def main():
         ap.error("--rescore needs --lattices with --decoder faster (and is not timed with --shared-graph / --yesno)")
     if args.mpe and (not args.lattices or args.decoder != "faster" or args.shared_graph or args.yesno):
         ap.error("--mpe needs --lattices with --decoder faster (and is not timed with --shared-graph / --yesno)")
+    if args.lmrescore and (not args.lattices or args.decoder != "faster" or args.yesno):
+        ap.error("--lmrescore needs --lattices with --decoder faster (and is not timed with --yesno)")
     if args.acc and (not args.post or args.shared_graph):
         ap.error("--acc needs --lattices --post (and is not timed with --shared-graph)")
     if args.shared_graph or args.yesno:
@@ -702,7 +752,7 @@ def main():
                     emission_kernels_ms=emit, emission_over_decoder=(emit + dec_new - dec_old) / dec_old if dec_old else None)
         faster_lat = flat
         faster_ops = None
-        if args.sweep or args.prune_beam is not None or args.post or args.rescore or args.mpe:
+        if args.sweep or args.prune_beam is not None or args.post or args.rescore or args.mpe or args.lmrescore:
             _, dl = khg.get_raw_lattice_faster_device_batch(am, tm, fsts, feats, cfg, 0.1)
             faster_ops = {}
             if args.sweep or args.prune_beam is not None or args.post:
@@ -713,6 +763,9 @@ def main():
                 faster_ops["mpe"] = mpe_bench(ctx, dl, am, tm, feats, [r["alignment"] for r in fres], args.criterion, args.reps)
             if args.rescore:
                 faster_ops["rescore"] = rescore_bench(ctx, dl, am, tm, fsts, feats, [r["alignment"] for r in fres], cfg, args.reps, args.boost)
+            if args.lmrescore:
+                vocab = sorted(set(int(w) for w in np.unique(ut.graphs["olabel"]) if w > 0))
+                faster_ops["lmrescore"] = lmrescore_bench(ctx, dl, [r["words"] for r in fres], vocab, args.lmrescore, args.reps, flat["raw_decode_call"])
             dl.close()
     st = [r["status"] for r in res]
     out = {"decoder": args.decoder,"utterances": args.utts, "frames": frames, "lattice_s": min(lat_s), "lattice_frames_per_s": frames / min(lat_s),
