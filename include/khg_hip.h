@@ -127,7 +127,12 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
 #define KHG_OPT_K2_LADDER 22     /* K2's exact DP on batches of chain-ordered graphs (every in-arc of state s from s or s - 1, <= 256 states): 0 (DEFAULT)
                                     the ladder form -- costs move between lanes in registers, one workgroup barrier per eight layers --, 1 the
                                     general body; same results bit for bit                                            [KHG_K2_LADDER=on|off] */
-#define KHG_OPT_COUNT 23
+#define KHG_OPT_K3_PLANES 23     /* K3's wave form with both phases on the fp16 matrix cores (KHG_OPT_K3_PHASE_B = 2) reads the features as split fp16
+                                    records kept on the utterance set (320 B per frame, made once per set and set of model-derived exponents)
+                                    instead of splitting the raw features in every pass: 0 (DEFAULT) automatic -- where the records fit half of
+                                    the free device memory at the first pass, never for a small set; 1 off; 2 on (still the in-loop split when
+                                    the allocation fails); same statistics bit for bit                          [KHG_K3_PLANES=auto|off|on] */
+#define KHG_OPT_COUNT 24
 /* Read-only figures (khg_ctx_get_option only): the per-call scratch block behind small utterance sets (DESIGN.md "per-utterance calls"). */
 #define KHG_INFO_SCRATCH_BYTES 100   /* bytes of the block in use (its top), 0 before the first small set */
 #define KHG_INFO_SCRATCH_BLOCKS 101  /* live allocations inside it */
@@ -221,6 +226,9 @@ int khg_utts_pdfs(const khg_utts *u, int32_t *pdfs_h /* [pdf_off[n_utt]] */);
 int khg_utts_k2_plan(khg_ctx *ctx, const khg_utts *u, int32_t out[8]);
 /* ... and whether it would run the ladder form of that kernel (KHG_OPT_K2_LADDER): *out = 1, else 0. */
 int khg_utts_k2_ladder(khg_ctx *ctx, const khg_utts *u, int32_t *out);
+/* K3's split feature records on the set (KHG_OPT_K3_PLANES): *bytes of the buffer (0: none), *packs = how often it was filled so far,
+ * *used = 1 when the last khg_acc_stats pass read it.  Launches nothing. */
+int khg_utts_k3_planes(const khg_utts *u, int64_t *bytes, int64_t *packs, int32_t *used);
 /* per listed pdf: the first frame a decoder token can read it at (fewest emitting arcs from the start state
  * to an arc carrying it; INT32_MAX if never; 0 for sets without graphs) -- what khg_loglikes_reachable uses */
 int khg_utts_pdf_first(const khg_utts *u, int32_t *first_h /* [pdf_off[n_utt]] */);

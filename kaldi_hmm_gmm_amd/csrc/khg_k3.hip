@@ -183,6 +183,7 @@ struct K3Run {
   // The fp16 phases rest on model-derived scales (k3_phase_a_scales: device work, cached per parameter version) and on the weight
   // being an ordinary number: the plan says what MAY run, the run settles it once when it starts.
   bool may_f16a = false, may_f16b = false;
+  bool may_planes = false;                   // k3_accumulate_wave16 may read the set's split feature records (k3_planes settles it when the run starts)
   size_t lds[3] = {0, 0, 0};                 // dynamic LDS: fp32 phase A | fp16 phase A | both phases on the fp16 matrix cores
   bool too_wide = false;                     // VALU form: the widest pdf does not fit the LDS chunk buffers
 };
@@ -213,11 +214,12 @@ static K3Plan k3_plan(const khg_ctx* ctx, const khg_model* m, bool post, int64_t
     // (pdfs of <= 32 Gaussians keep the fp32 chain: 40 MFMAs per tile are not worth the split, and the two-waves-per-SIMD instantiations have no registers for the fp16 W pieces)
     r.may_f16a = nb >= 3 && pha == 0 && phb != 1; r.may_f16b = phb == 2;
     // fp32 phase A: W + the waves' planes; fp16 phase A: the waves' planes + their split planes; k3_accumulate_wave16: per wave two
-    // tiles' phase-A planes + the phase-B planes (halves), then the split W operands; then, in each, the fold image
+    // tiles' split planes (halves; one frame-major image for both phases), then the split W operands; then, in each, the fold image
     const size_t fold = sizeof(double) * (nb * 16 * 80 + nb * 16);
     r.lds[0] = std::max<size_t>(sizeof(float) * (nb * 20 * 64 + 4 * 4 * 16 * 20), fold);
     r.lds[1] = std::max<size_t>(sizeof(float) * (4 * 4 * 16 * 20) + 2 * (size_t)(4 * 2 * 16 * K3_XH_ROW), fold);
-    r.lds[2] = std::max<size_t>(2 * (size_t)4 * (2 * (2 * 16 * K3_XH_ROW) + 2 * 2 * 40 * 36) + nb * 3 * 2 * 64 * 16, fold);
+    r.lds[2] = std::max<size_t>(2 * (size_t)4 * (2 * (2 * 16 * K3_X16_ROW)) + nb * 3 * 2 * 64 * 16, fold);
+    r.may_planes = r.may_f16b && ctx->opt[KHG_OPT_K3_PLANES] != 1;
     const int64_t avg_tiles = (avg + 15) / 16;
     r.ny = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(32, (avg_tiles + 15) / 16), (4096 + P - 1) / P));
     if (ny_opt > 0) r.ny = ny_opt;
@@ -287,11 +289,12 @@ int k3_post_check(khg_ctx* ctx, const khg_model* m, const std::string& who) {
 
 // Every instantiation of the accumulate kernels, once: (variant, KQ, Gaussian blocks, waves, POST, fp16 phase A) -> the kernel.
 typedef void (*K3Kernel)(K3Args);
-enum K3Variant { K3V_WAVE, K3V_WAVE16, K3V_FINALIZE, K3V_MFMA, K3V_BLOCK16, K3V_VALU };
+enum K3Variant { K3V_WAVE, K3V_WAVE16, K3V_WAVE16P, K3V_FINALIZE, K3V_MFMA, K3V_BLOCK16, K3V_VALU };
 struct K3Inst { int variant, KQ, NB, nwv; bool post, f16a; K3Kernel fn; };
 #define K3_WAVE_ROWS(NB)                                                                                                           \
   {K3V_WAVE, 10, NB, 4, false, false, k3_accumulate_wave<NB>}, {K3V_WAVE, 10, NB, 4, false, true, k3_accumulate_wave<NB, true>}, \
-  {K3V_WAVE16, 10, NB, 4, false, true, k3_accumulate_wave16<NB>}, {K3V_FINALIZE, 10, NB, 4, false, false, k3_wave_finalize<NB>}
+  {K3V_WAVE16, 10, NB, 4, false, true, k3_accumulate_wave16<NB>}, {K3V_WAVE16P, 10, NB, 4, false, true, k3_accumulate_wave16<NB, true>}, \
+  {K3V_FINALIZE, 10, NB, 4, false, false, k3_wave_finalize<NB>}
 #define K3_MFMA_ROWS(KQ, NBW) {K3V_MFMA, KQ, NBW, 4, false, false, k3_accumulate_mfma<KQ, NBW>}, {K3V_MFMA, KQ, NBW, 4, true, false, k3_accumulate_mfma<KQ, NBW, true>}
 #define K3_VALU_ROWS(KQ) {K3V_VALU, KQ, 0, 4, false, false, k3_accumulate<KQ>}, {K3V_VALU, KQ, 0, 4, true, false, k3_accumulate<KQ, true>}
 static const K3Inst k3_insts[] = {
@@ -340,6 +343,7 @@ static K3Args k3_args(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, const 
   a.occ = acc->occ(); a.mean_acc = acc->mean(); a.var_acc = acc->var(); a.trans_acc = acc->trans(); a.scalars = acc->scalars();
   a.weight = weight; a.err_flag = ctx->err_flag_d; a.part = nullptr; a.ll_part = nullptr; a.pdf0 = 0; a.npdf = m->P; a.items = nullptr; a.item_off = nullptr;
   a.pa_ex = nullptr; a.pa_S = 0; a.pa_scale = 1.0f; a.pa_inv = 1.0f; a.pa_c1 = 1.44269504088896340736f; a.pb_gscale = 1.0f; a.pb_SG = 0;   // (k3_set_scales)
+  a.xrec = nullptr; a.xrec_zero = 0;         // (k3_planes)
   return a;
 }
 // the fp16 phases' scales: the model's for phase A (k3_phase_a_scales said they hold), the weight's for phase B
@@ -350,6 +354,45 @@ static void k3_set_scales(K3Args& a, const khg_model* m, bool f16a, bool f16b) {
     a.pa_scale = std::ldexp(1.0f, m->k3_S); a.pa_inv = std::ldexp(1.0f, -m->k3_S); a.pa_c1 = std::ldexp(1.44269504088896340736f, -m->k3_S);
   }
   if (f16b) { a.pb_SG = 13 - std::ilogb(std::fabs(a.weight)); a.pb_gscale = std::ldexp(1.0f, a.pb_SG); }
+}
+
+// The set's split feature records for k3_accumulate_wave16 (KHG_OPT_K3_PLANES): N + 1 records of 320 B, the pieces phase A stages --
+// x' = x 2^ex, fl(x^2) 2^ex2, each as two fp16 pieces -- made ONCE per (set, exponents) instead of in every pass over every frame: the
+// features of a set do not change from EM iteration to EM iteration, and the exponents (m->k3_ex, from the model's envelope alone)
+// move only when a dimension's envelope crosses a power of two.  Built when absent or keyed by other exponents; dropped by
+// khg_utts_features_changed.  auto: only where the records fit half of the free device memory at that moment; a set from the context's
+// arena (one call each) never.  *use = false -- the pass splits in its loop, same bits -- whenever there are no records.
+static int k3_planes(khg_ctx* ctx, const khg_model* m, khg_utts* u, bool* use) {
+  *use = false;
+  const int mode = ctx->opt[KHG_OPT_K3_PLANES];
+  if (mode == 1 || u->N >= (int64_t)INT_MAX - 1 || (mode == 0 && u->small)) return KHG_OK;
+  const size_t bytes = sizeof(_Float16) * K3_XREC * ((size_t)u->N + 1);
+  if (u->k3x_d && u->k3x_key == m->k3_ex) { *use = true; return KHG_OK; }
+  if (!u->k3x_d) {
+    if (mode == 0) {
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return KHG_OK; }
+      if (bytes > free_b / 2) return KHG_OK;
+    }
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return KHG_OK; }     // no room: not an error
+    u->k3x_d = p; u->k3x_bytes = (int64_t)bytes;
+  }
+  {
+    KernelTimer kt(ctx, "k3_pack_x");
+    const int64_t nthr = ((int64_t)u->N + 1) * 5;
+    KHG_LAUNCH(ctx, k3_pack_x, dim3((unsigned)std::min<int64_t>(65536, (nthr + 255) / 256)), dim3(256), 0, ctx->stream, u->feats_d, u->N, (int)u->D, m->k3_ex_d,
+               reinterpret_cast<_Float16*>(u->k3x_d));
+  }
+  HIPCHK(hipGetLastError());
+  u->k3x_key = m->k3_ex; ++u->k3x_packs;
+  *use = true;
+  return KHG_OK;
+}
+extern "C" int khg_utts_k3_planes(const khg_utts* u, int64_t* bytes, int64_t* packs, int32_t* used) {
+  if (!u || !bytes || !packs || !used) return khg_set_error(KHG_E_ARG, "khg_utts_k3_planes: bad arguments");
+  *bytes = u->k3x_d ? u->k3x_bytes : 0; *packs = u->k3x_packs; *used = u->k3x_used ? 1 : 0;
+  return KHG_OK;
 }
 
 // Frames (entries) -> buckets by pdf, one of three ways; the transition statistics on the way
@@ -460,7 +503,12 @@ static int k3_run(khg_ctx* ctx, const khg_model* m, khg_utts* u, khg_accs* acc, 
   if (r.may_f16a && (wave || wt)) { int rs = k3_phase_a_scales(ctx, const_cast<khg_model*>(m), u, &f16a); if (rs) return rs; }
   const bool f16b = f16a && r.may_f16b && wt;
   k3_set_scales(a, m, f16a, f16b);
-  const int variant = wave ? (f16b ? K3V_WAVE16 : K3V_WAVE) : r.form == K3F_VALU ? K3V_VALU : f16b ? K3V_BLOCK16 : K3V_MFMA;
+  int variant = wave ? (f16b ? K3V_WAVE16 : K3V_WAVE) : r.form == K3F_VALU ? K3V_VALU : f16b ? K3V_BLOCK16 : K3V_MFMA;
+  if (variant == K3V_WAVE16 && r.may_planes) {
+    bool planes = false;
+    { int rp = k3_planes(ctx, m, u, &planes); if (rp) return rp; }
+    if (planes) { variant = K3V_WAVE16P; a.xrec = reinterpret_cast<const _Float16*>(u->k3x_d); a.xrec_zero = (int32_t)u->N; u->k3x_used = true; }
+  }
   const int nwv = variant == K3V_BLOCK16 ? r.nwv16 : 4;     // the block size
   const K3Kernel fn = k3_kernel(variant, m->KQ, variant == K3V_BLOCK16 ? r.NB16 : r.NB, nwv, post, f16a);
   const K3Kernel fin = wave ? k3_kernel(K3V_FINALIZE, m->KQ, r.NB, 4, false, false) : nullptr;
@@ -503,6 +551,7 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
     HIPCHK(hipMemsetAsync(u->tid_count_d, 0, sizeof(unsigned long long) * ((size_t)tm->num_tids + 1), ctx->stream));
   }
   K3Args a = k3_args(ctx, m, tm, u, acc, weight, post, Neff);
+  if (!post) u->k3x_used = false;              // (khg_utts_k3_planes: whether THIS pass read the split feature records)
   nparts = std::max(1, std::min(nparts, m->P));
   if (comm && nparts > 1) { rc = ctx_comm_stream(ctx); if (rc) return rc; }
   if (Neff > 0) {

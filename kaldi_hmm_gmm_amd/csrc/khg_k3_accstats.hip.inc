@@ -55,6 +55,9 @@ struct K3Args {
   // k3_accumulate_wave16 (phase B on the fp16 matrix cores too): gamma' = gamma 2^SG, |weight| 2^SG in [2^13, 2^14)
   float pb_gscale;             // 2^SG
   int32_t pb_SG;
+  // ... from the set's split feature records (k3_pack_x; the PLANES instantiation): [N + 1][K3_XREC] halves, record xrec_zero = N is zeros
+  const _Float16* xrec;
+  int32_t xrec_zero;
   // khg_acc_stats_post (khg_k3_post.hip.inc; the POST instantiations of k3_accumulate / k3_accumulate_mfma): `ali` holds the entries'
   // transition-ids, N is their number and the buckets (frame_ids) hold ENTRY numbers; entry e reads feature row e_row[e] and carries its
   // own weight e_w[e] where `weight` stands for an alignment
@@ -1022,6 +1025,10 @@ __global__ __launch_bounds__(256) void k3_accumulate_mfma(K3Args a) {
 // (the per-dimension feature envelope max_g |mean| + 8 sigma the fp16 phase A scales by is read by k0_model_stats, khg_ctx_model.hip,
 //  in the one pass per parameter version that also reads the column maxima)
 typedef _Float16 k3_f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 k3_f16x4 __attribute__((ext_vector_type(4)));
+typedef __fp16 k3_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+typedef __attribute__((address_space(3))) k3_fp16x4 k3_lds_h4;     // an LDS operand of ds_read_b64_tr_b16
+__device__ __forceinline__ k3_f16x4 k3_read_tr16(k3_lds_h4* p) { return __builtin_bit_cast(k3_f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(p)); }
 #define K3_XH_ROW 104          // fp16 elements per frame row of the split planes (96 used; 208 B: conflict-free 16-byte reads)
 
 template <int NB>
@@ -1339,12 +1346,48 @@ __global__ __launch_bounds__(256, NB <= 2 ? 2 : 1) void k3_accumulate_wave(K3Arg
 // fp64 add -- relative differences of ~1e-7 in a cell, far inside the 2e-5 the statistics are compared at; the sums depend on how
 // frames fall into 32-frame groups, so N ranks' statistics add up to the one-rank statistics to ~1e-7, not 1e-12.  occ, the
 // transition counts and the log-likelihood are computed exactly as in the fp64 form.  Run-to-run reproducible (fixed order).
-template <int NB>
+// ONE LDS image serves both phases: the split planes are staged frame-major ([piece][frame][K3_X16_ROW]); phase A reads a frame's
+// row (ds_read_b128), phase B reads the same rows through ds_read_b64_tr_b16, which hands lane 16 q + n column n of the four frames
+// 4 q .. 4 q + 3 -- the K-slot order (q, e) of the B operand.  Rows of 224 B: the eight rows a 32-lane half of a transposed read
+// touches start 56 banks apart (eight distinct 32-byte slots of the 256-byte bank row), and the 16-lane groups of the 16-byte row
+// reads see sixteen distinct 16-byte slots (14 j + q mod 16 over a group's lanes); at 208 B the transposed reads are two-way.
+// The instruction needs EXEC all ones and 8-byte addresses: every lane's address lies inside the image (rows 0..15, columns < 80)
+// and the pair loop is wave-uniform.
+// PLANES (KHG_OPT_K3_PLANES): the image is copied from the set's split feature records (k3_pack_x: 320 B per frame, made once per
+// (set, exponents)) by 16-byte loads and ds_write_b128 -- no conversion in the loop; record N (zeros) stands for the frames past a
+// tile's end.  Without them the loop splits the raw features itself, as it always did: same bits either way.
+#define K3_X16_ROW 112        // fp16 elements per frame row of k3_accumulate_wave16's image (96 used; 224 B)
+#define K3_XREC 160           // fp16 elements of a split feature record: [x'1 (40) | x^2'1 (40) | x'2 (40) | x^2'2 (40)]
+__device__ __forceinline__ void k3_split_cell(float v, float sx, float sx2, _Float16& h1, _Float16& h2, _Float16& g1, _Float16& g2) {
+  const float s1 = v * sx, s2 = (v * v) * sx2;        // fl(x^2) first (the reference's squares)
+  h1 = (_Float16)s1; g1 = (_Float16)s2;
+  h2 = (_Float16)(s1 - (float)h1); g2 = (_Float16)(s2 - (float)g1);
+}
+// The records of frames [0, N) and the zero record N: one thread per (record, 8 dims) writes its 16 bytes of each of the four parts
+__global__ __launch_bounds__(256) void k3_pack_x(const float* __restrict__ feats, int64_t N, int D, const int32_t* __restrict__ ex, _Float16* __restrict__ rec) {
+  const int64_t n = (N + 1) * 5;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t f = i / 5;
+    const int d0 = 8 * (int)(i - 5 * f);
+    k3_f16x8 h1, h2, g1, g2;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int d = d0 + e, dc = min(d, D - 1);
+      const float v = (f < N && d < D) ? feats[f * D + dc] : 0.0f;
+      _Float16 a1, a2, b1, b2;
+      k3_split_cell(v, ldexpf(1.0f, ex[2 * dc]), ldexpf(1.0f, ex[2 * dc + 1]), a1, a2, b1, b2);
+      h1[e] = a1; h2[e] = a2; g1[e] = b1; g2[e] = b2;
+    }
+    _Float16* r = rec + f * K3_XREC + d0;
+    *reinterpret_cast<k3_f16x8*>(r) = h1; *reinterpret_cast<k3_f16x8*>(r + 40) = g1;
+    *reinterpret_cast<k3_f16x8*>(r + 80) = h2; *reinterpret_cast<k3_f16x8*>(r + 120) = g2;
+  }
+}
+template <int NB, bool PLANES = false>
 __global__ __launch_bounds__(256, 1) void k3_accumulate_wave16(K3Args a) {
   extern __shared__ __attribute__((aligned(16))) float k3s[];
-  constexpr int KQ = 10, XP = 4 * KQ, NDB = KQ / 2, TF = 16;
-  constexpr int XHH = 2 * TF * K3_XH_ROW;          // halves of one tile's phase-A planes [piece 2][frame 16][K3_XH_ROW]
-  constexpr int XTR = 36, XTH = 2 * 2 * XP * XTR;  // phase-B planes [piece 2][column 80][XTR]: 32 frames (tile 0 | tile 1) + 4 halves of padding
+  constexpr int KQ = 10, XP = 4 * KQ, NDB = KQ / 2, TF = 16, ROW = K3_X16_ROW;
+  constexpr int XHH = 2 * TF * ROW;                // halves of one tile's planes [piece 2][frame 16][ROW]
   K3Item it;
   if (!k3_take_item(a, it)) return;
   const int pdf = it.pdf;
@@ -1356,14 +1399,13 @@ __global__ __launch_bounds__(256, 1) void k3_accumulate_wave16(K3Args a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j16 = lane & 15, q = lane >> 4;
-  _Float16* xh = reinterpret_cast<_Float16*>(k3s) + wave * (2 * XHH + XTH);       // this wave's phase-A planes of the pair's two tiles
-  _Float16* xt = xh + 2 * XHH;                                                      // ... and its phase-B planes
+  _Float16* xh = reinterpret_cast<_Float16*>(k3s) + wave * (2 * XHH);               // this wave's planes of the pair's two tiles
   float gcv[NB];
 #pragma unroll
   for (int k = 0; k < NB; ++k) gcv[k] = ((16 * k + j16 < G) ? a.gconsts[g0 + 16 * k + j16] : -INFINITY) * a.pa_scale;
   // phase A's split W operands ([block][step][piece][lane] x 16 B = 6 NB KiB, shared by the four waves) sit in LDS behind the waves'
   // planes: the fp64 totals, two tiles' posteriors and the split gamma operands leave no room for 24 NB more registers
-  char* wl16 = reinterpret_cast<char*>(reinterpret_cast<_Float16*>(k3s) + 4 * (2 * XHH + XTH));
+  char* wl16 = reinterpret_cast<char*>(reinterpret_cast<_Float16*>(k3s) + 4 * (2 * XHH));
   for (int e0 = tid; e0 < NB * 3 * 64; e0 += 256) {
     const int l = e0 & 63, st = (e0 >> 6) % 3, k = e0 / (3 * 64), jl = l & 15, ql = l >> 4;
     k3_f16x8 p1, p2;
@@ -1382,9 +1424,9 @@ __global__ __launch_bounds__(256, 1) void k3_accumulate_wave16(K3Args a) {
     *reinterpret_cast<k3_f16x8*>(wl16 + (((k * 3 + st) * 2 + 1) * 64 + l) * 16) = p2;
   }
   {                                                                         // padding columns / padding dims stay zero
-    static_assert((2 * XHH + XTH) % 8 == 0, "the wave's planes are whole 16-byte words");
+    static_assert((2 * XHH) % 8 == 0 && ROW % 8 == 0, "the wave's planes and their rows are whole 16-byte words");
     const k3_f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = lane; i < (2 * XHH + XTH) / 8; i += 64) reinterpret_cast<k3_f16x8*>(xh)[i] = z;
+    for (int i = lane; i < (2 * XHH) / 8; i += 64) reinterpret_cast<k3_f16x8*>(xh)[i] = z;
   }
   __syncthreads();
 
@@ -1402,21 +1444,28 @@ __global__ __launch_bounds__(256, 1) void k3_accumulate_wave16(K3Args a) {
   // A lane stages 2 x 2 MICRO-TILES (two adjacent frames x two adjacent dims) of the pair's 2 x 16 x 40 cells: micro-tile
   // i = lane + 64 j, j < NM = 5: tile i / 160, frame pair (i % 160) / 20, dim pair i % 20.  The kernel is bound by the LDS
   // pipe (SQ_ACTIVE_INST_LDS = busy cycles with one cell per lane and eight 2-byte writes per cell): a micro-tile's four cells go
-  // out as 4-byte writes -- two dims of one frame into the frame-major planes, two frames of one dim into the column-major ones --
-  // half the LDS instructions per cell, half the lane shuffles for the frame ids, 8-byte feature loads.
-  constexpr int NM = 2 * TF * XP / (4 * 64);
+  // out as 4-byte writes -- two dims of one frame are neighbours in the frame-major planes --, half the lane shuffles for the frame
+  // ids, 8-byte feature loads.
+  // PLANES: a lane copies 16-byte chunks of the pair's 32 records: chunk i = lane + 64 j, j < NR = 10: frame slot i / 20 (tile 0:
+  // j < 5), chunk i % 20 of its record (piece (i % 20) / 10, columns 8 ((i % 20) % 10) ..) -- a record is read by 20 neighbouring lanes.
+  constexpr int NM = 2 * TF * XP / (4 * 64), NR = 2 * TF * (K3_XREC / 8) / 64;
   static_assert(NM * 4 * 64 == 2 * TF * XP, "micro-tiles cover the pair exactly");
+  static_assert(NR * 64 == 2 * TF * (K3_XREC / 8) && (NR & 1) == 0, "record chunks cover the pair exactly, a tile per half of them");
   const int pstride = 4 * it.ny;
   float pre[NM][4];                       // [micro-tile][frame 2][dim 2]
   float sx[NM][2], sx2[NM][2];            // 2^ex of the micro-tile's two dims (x', x^2')
+  k1b_u32x4 rec[NR];                      // PLANES: the pair's record chunks
   const bool even_d = (D & 1) == 0;       // 8-byte feature loads need even row lengths
+  if constexpr (!PLANES) {
 #pragma unroll
-  for (int j = 0; j < NM; ++j)
+    for (int j = 0; j < NM; ++j)
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int d = min(2 * ((lane + 64 * j) % 20) + c, D - 1);
-      sx[j][c] = ldexpf(1.0f, a.pa_ex[2 * d]); sx2[j][c] = ldexpf(1.0f, a.pa_ex[2 * d + 1]);
-    }
+      for (int c = 0; c < 2; ++c) {
+        const int d = min(2 * ((lane + 64 * j) % 20) + c, D - 1);
+        sx[j][c] = ldexpf(1.0f, a.pa_ex[2 * d]); sx2[j][c] = ldexpf(1.0f, a.pa_ex[2 * d + 1]);
+      }
+  }
+  const int fid_none = PLANES ? a.xrec_zero : 0;      // what a lane past a tile's end asks for: the zero record / any valid row
   const float gs = a.pb_gscale;
   // pair p of the loop is pair (p + rot) mod npair of the bucket (see k3_accumulate_wave: neighbouring pdfs' blocks would otherwise
   // sweep the feature matrix in lock-step); its tiles are 2 p and 2 p + 1
@@ -1426,11 +1475,22 @@ __global__ __launch_bounds__(256, 1) void k3_accumulate_wave16(K3Args a) {
   auto fid_of = [&](int pl, int tau) -> int {
     const int n = cf_of(pl, tau);
     const int t = pl < npair ? 2 * pair_of(pl) + tau : 0;
-    return lane < n ? a.frame_ids[beg + t * TF + lane] : 0;
+    return lane < n ? a.frame_ids[beg + t * TF + lane] : fid_none;
   };
   // the pair's features into pre[]: fid0 / fid1 = this lane's frame id of tile 0 / tile 1 (lane < 16); always-valid addresses (a lane past
   // a tile's end carries frame id 0, a padding dim reads dim D - 1), the zero fill happens when the pair is parked in LDS
+  // (PLANES: the pair's record chunks into rec[]; a lane past a tile's end carries the zero record)
   auto request = [&](int fid0, int fid1) {
+    if constexpr (PLANES) {
+      const k1b_u32x4* src = reinterpret_cast<const k1b_u32x4*>(a.xrec);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        const int i = lane + 64 * j, fs = i / 20, kk = i - 20 * fs;
+        const int fid = __shfl(j < NR / 2 ? fid0 : fid1, fs & (TF - 1));
+        rec[j] = src[(int64_t)fid * (K3_XREC / 8) + kk];
+      }
+      return;
+    }
     int fa[NM], fb[NM];
 #pragma unroll
     for (int j = 0; j < NM; ++j) {
@@ -1464,38 +1524,35 @@ __global__ __launch_bounds__(256, 1) void k3_accumulate_wave16(K3Args a) {
   if (p < npair) { request(fid_of(p, 0), fid_of(p, 1)); fidn0 = fid_of(p + pstride, 0); fidn1 = fid_of(p + pstride, 1); }
   for (; p < npair; p += pstride) {
     const int cf[2] = {cf_of(p, 0), cf_of(p, 1)};
-    // ---- stage both tiles: the split planes in phase A's layout (frame rows) and in phase B's (column rows) ----
+    // ---- stage both tiles: the split planes, frame-major ([piece][frame][column]) ----
+    if constexpr (PLANES) {
 #pragma unroll
-    for (int j = 0; j < NM; ++j) {
-      typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-      const int i = lane + 64 * j, tau = i / 160, r = i % 160, f0 = 2 * (r / 20), d0 = 2 * (r % 20);
-      const int cft = tau ? cf[1] : cf[0];
-      _Float16 h1[4], h2[4], g1[4], g2[4];                        // [frame 2][dim 2]: the two pieces of x' and of x^2'
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int f = f0 + (e >> 1), d = d0 + (e & 1);
-        const float v = (f < cft && d < D) ? pre[j][e] : 0.0f;
-        const float s1 = v * sx[j][e & 1], s2 = (v * v) * sx2[j][e & 1];        // fl(x^2) first (the reference's squares)
-        h1[e] = (_Float16)s1; g1[e] = (_Float16)s2;
-        h2[e] = (_Float16)(s1 - (float)h1[e]); g2[e] = (_Float16)(s2 - (float)g1[e]);
+      for (int j = 0; j < NR; ++j) {
+        const int i = lane + 64 * j, fs = i / 20, kk = i - 20 * fs, pc = kk >= K3_XREC / 16, tau = j >= NR / 2;
+        *reinterpret_cast<k1b_u32x4*>(xh + tau * XHH + (pc * TF + (fs & (TF - 1))) * ROW + 8 * (kk - pc * (K3_XREC / 16))) = rec[j];
       }
-      // phase A's layout: [piece][frame][column] -- dims d0, d0 + 1 of one frame are neighbours
+    } else {
 #pragma unroll
-      for (int ff = 0; ff < 2; ++ff) {
-        _Float16* r1 = xh + tau * XHH + (f0 + ff) * K3_XH_ROW + d0;
-        *reinterpret_cast<h2v*>(r1) = h2v{h1[2 * ff], h1[2 * ff + 1]};
-        *reinterpret_cast<h2v*>(r1 + TF * K3_XH_ROW) = h2v{h2[2 * ff], h2[2 * ff + 1]};
-        *reinterpret_cast<h2v*>(r1 + XP) = h2v{g1[2 * ff], g1[2 * ff + 1]};
-        *reinterpret_cast<h2v*>(r1 + TF * K3_XH_ROW + XP) = h2v{g2[2 * ff], g2[2 * ff + 1]};
-      }
-      // phase B's layout: [piece][column][frame of the pair] -- frames f0, f0 + 1 of one column are neighbours
+      for (int j = 0; j < NM; ++j) {
+        typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+        const int i = lane + 64 * j, tau = i / 160, r = i % 160, f0 = 2 * (r / 20), d0 = 2 * (r % 20);
+        const int cft = tau ? cf[1] : cf[0];
+        _Float16 h1[4], h2[4], g1[4], g2[4];                        // [frame 2][dim 2]: the two pieces of x' and of x^2'
 #pragma unroll
-      for (int dd = 0; dd < 2; ++dd) {
-        _Float16* c1 = xt + (d0 + dd) * XTR + tau * TF + f0;
-        *reinterpret_cast<h2v*>(c1) = h2v{h1[dd], h1[2 + dd]};
-        *reinterpret_cast<h2v*>(c1 + 2 * XP * XTR) = h2v{h2[dd], h2[2 + dd]};
-        *reinterpret_cast<h2v*>(c1 + XP * XTR) = h2v{g1[dd], g1[2 + dd]};
-        *reinterpret_cast<h2v*>(c1 + 2 * XP * XTR + XP * XTR) = h2v{g2[dd], g2[2 + dd]};
+        for (int e = 0; e < 4; ++e) {
+          const int f = f0 + (e >> 1), d = d0 + (e & 1);
+          const float v = (f < cft && d < D) ? pre[j][e] : 0.0f;
+          k3_split_cell(v, sx[j][e & 1], sx2[j][e & 1], h1[e], h2[e], g1[e], g2[e]);
+        }
+        // dims d0, d0 + 1 of one frame are neighbours
+#pragma unroll
+        for (int ff = 0; ff < 2; ++ff) {
+          _Float16* r1 = xh + tau * XHH + (f0 + ff) * ROW + d0;
+          *reinterpret_cast<h2v*>(r1) = h2v{h1[2 * ff], h1[2 * ff + 1]};
+          *reinterpret_cast<h2v*>(r1 + TF * ROW) = h2v{h2[2 * ff], h2[2 * ff + 1]};
+          *reinterpret_cast<h2v*>(r1 + XP) = h2v{g1[2 * ff], g1[2 * ff + 1]};
+          *reinterpret_cast<h2v*>(r1 + TF * ROW + XP) = h2v{g2[2 * ff], g2[2 * ff + 1]};
+        }
       }
     }
     if (p + pstride < npair) { request(fidn0, fidn1); fidn0 = fid_of(p + 2 * pstride, 0); fidn1 = fid_of(p + 2 * pstride, 1); }
@@ -1511,8 +1568,8 @@ __global__ __launch_bounds__(256, 1) void k3_accumulate_wave16(K3Args a) {
       k3_f16x8 x1[2], x2[2];
 #pragma unroll
       for (int tau = 0; tau < 2; ++tau) {
-        x1[tau] = *reinterpret_cast<const k3_f16x8*>(xh + tau * XHH + j16 * K3_XH_ROW + 32 * st + 8 * q);
-        x2[tau] = *reinterpret_cast<const k3_f16x8*>(xh + tau * XHH + (TF + j16) * K3_XH_ROW + 32 * st + 8 * q);
+        x1[tau] = *reinterpret_cast<const k3_f16x8*>(xh + tau * XHH + j16 * ROW + 32 * st + 8 * q);
+        x2[tau] = *reinterpret_cast<const k3_f16x8*>(xh + tau * XHH + (TF + j16) * ROW + 32 * st + 8 * q);
       }
 #pragma unroll
       for (int k = 0; k < NB; ++k) {
@@ -1568,12 +1625,15 @@ __global__ __launch_bounds__(256, 1) void k3_accumulate_wave16(K3Args a) {
     }
 #pragma unroll
     for (int db = 0; db < NDB; ++db) {
-      const _Float16* cb = xt + (16 * db + j16) * XTR + 4 * q;                  // this lane's column: frames 4 q .. 4 q + 3 of tile 0, then of tile 1
+      // transposed reads of the frame-major image: lane 4 qq + pp of a 16-lane group names row qq of the group's block (frame 4 q + qq),
+      // columns 4 pp .. of the column block; lane 16 q + j16 receives column 16 db + j16 of frames 4 q .. 4 q + 3 -- tile 0, then tile 1
+      k3_lds_h4* cb = (k3_lds_h4*)(xh + (4 * q + (j16 >> 2)) * ROW + 16 * db + 4 * (j16 & 3));
       k3_f16x8 xb1, xb2;
       {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        const h4 a0 = *reinterpret_cast<const h4*>(cb), a1 = *reinterpret_cast<const h4*>(cb + TF);
-        const h4 b0 = *reinterpret_cast<const h4*>(cb + 2 * XP * XTR), b1 = *reinterpret_cast<const h4*>(cb + 2 * XP * XTR + TF);
+        typedef k3_f16x4 h4;
+        constexpr int T1 = XHH / 4, P2 = TF * ROW / 4;                            // tile 1, piece 2: in 8-byte words
+        const h4 a0 = k3_read_tr16(cb), a1 = k3_read_tr16(cb + T1);
+        const h4 b0 = k3_read_tr16(cb + P2), b1 = k3_read_tr16(cb + T1 + P2);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { xb1[e] = a0[e]; xb1[4 + e] = a1[e]; xb2[e] = b0[e]; xb2[4 + e] = b1[e]; }
       }

@@ -79,7 +79,7 @@ struct KContext {
   static int opt_id(const py::object& o) {
     if (py::isinstance<py::int_>(o)) return o.cast<int>();
     static const char* names[KHG_OPT_COUNT] = {"k1_form", "k1_order", "k1_nf", "k1p_ts", "k1_interleave", "k1_dbg", "k2_inorder", "k2_ks", "k2_serial",
-                                               "k2_prof", "k3_bucket", "k3_form", "k3_phase_b", "k3_ny", "debug", "k3_phase_a", "k2_split", "k2s_hub", "lat_ops_lds", "k1_launch", "k1_pgrid", "k1_prof", "k2_ladder"};
+                                               "k2_prof", "k3_bucket", "k3_form", "k3_phase_b", "k3_ny", "debug", "k3_phase_a", "k2_split", "k2s_hub", "lat_ops_lds", "k1_launch", "k1_pgrid", "k1_prof", "k2_ladder", "k3_planes"};
     const std::string n = o.cast<std::string>();
     for (int i = 0; i < KHG_OPT_COUNT; ++i) if (n == names[i]) return i;
     if (n == "scratch_bytes") return KHG_INFO_SCRATCH_BYTES;       // read-only
@@ -669,6 +669,14 @@ struct KUtts {
     d["nthr"] = o[5]; d["lds_bytes"] = o[6]; d["faithful_form"] = o[7];
     return d;
   }
+  // khg_utts_k3_planes: K3's split feature records on the set
+  py::dict k3_planes() {
+    int64_t bytes = 0, packs = 0; int32_t used = 0;
+    Check(khg_utts_k3_planes(h, &bytes, &packs, &used));
+    py::dict d;
+    d["bytes"] = bytes; d["packs"] = packs; d["used"] = used != 0;
+    return d;
+  }
   // khg_utts_k2_ladder: align() would run the ladder form of that kernel
   bool k2_ladder(py::object ctx_o) {
     int32_t o = 0;
@@ -1128,7 +1136,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def_property_readonly("h", [](KUtts& x) { return reinterpret_cast<uintptr_t>(x.h); })
       .def_readonly("ctx", &KUtts::ctx_obj).def_readonly("frame_off", &KUtts::frame_off).def_readonly("n_utt", &KUtts::n_utt)
       .def_readonly("dim", &KUtts::dim)
-      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("k2_ladder", &KUtts::k2_ladder, py::arg("ctx")).def("pdf_first_frames", &KUtts::pdf_first_frames)
+      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("k2_ladder", &KUtts::k2_ladder, py::arg("ctx")).def("k3_planes", &KUtts::k3_planes).def("pdf_first_frames", &KUtts::pdf_first_frames)
       .def("pdf_last_frames", &KUtts::pdf_last_frames)
       .def("loglikes", &KUtts::loglikes, py::arg("model"), py::arg("reachable_only") = false, py::arg("band") = false)
       .def("loglikes_layout", &KUtts::loglikes_layout).def("download_loglikes", &KUtts::download_loglikes)

@@ -416,12 +416,14 @@ extern "C" int khg_utts_set_pdf_list(khg_utts* u, int32_t n, const int32_t* pdfs
 }
 
 // Borrowed device features were rewritten in place: drop everything derived from them (column maxima, the fp16 / bf16 planes of the
-// split K1 forms); the next khg_loglikes re-packs.  K3 and the fp32 K1 forms read feats_d live.
+// split K1 forms, K3's split feature records); the next khg_loglikes / khg_acc_stats re-packs.  The fp32 K1 forms and every K3 form
+// but k3_accumulate_wave16 on its records read feats_d live.
 extern "C" int khg_utts_features_changed(khg_utts* u) {
   if (!u) return khg_set_error(KHG_E_ARG, "khg_utts_features_changed: bad arguments");
   u->xmax.clear();
   u->xs_ks = 0; u->xs_ex.clear();
   u->xh_ks = 0; u->xh_ex.clear();
+  u->k3x_key.clear();                 // (the buffer stays: same N, the next pass fills it again)
   u->ll_valid = false;
   return KHG_OK;
 }
@@ -467,7 +469,7 @@ extern "C" int khg_utts_destroy(khg_utts* u) {
   DEVFREE(u->ali_d); DEVFREE(u->words_d); DEVFREE(u->num_words_d); DEVFREE(u->status_d); DEVFREE(u->like_d);
   DEVFREE(u->pdf_count_d); DEVFREE(u->pdf_cursor_d); DEVFREE(u->frame_ids_d); DEVFREE(u->pdf_start_d); DEVFREE(u->tid_count_d);
   DEVFREE(u->sort_keys_d); DEVFREE(u->sort_keys_out_d); DEVFREE(u->sort_vals_d); DEVFREE(u->sort_tmp_d); DEVFREE(u->cs_hist_d); DEVFREE(u->cs_tot_d);
-  DEVFREE(u->k3_part_d); DEVFREE(u->k3_llpart_d); DEVFREE(u->k3_items_d); DEVFREE(u->k3_item_off_d);
+  DEVFREE(u->k3x_d); DEVFREE(u->k3_part_d); DEVFREE(u->k3_llpart_d); DEVFREE(u->k3_items_d); DEVFREE(u->k3_item_off_d);
   DEVFREE(u->pe_row_d); DEVFREE(u->pe_tid_d); DEVFREE(u->pe_ids_d); DEVFREE(u->pe_w_d); DEVFREE(u->pe_keys_d); DEVFREE(u->pe_keys_out_d);
   DEVFREE(u->pe_vals_d); DEVFREE(u->pe_tmp_d); DEVFREE(u->pe_start_d);
   DEVFREE(u->rc_keys_d); DEVFREE(u->rc_keys_out_d); DEVFREE(u->rc_vals_d); DEVFREE(u->rc_vals_out_d); DEVFREE(u->rc_flag_d); DEVFREE(u->rc_inc_d);
