@@ -115,7 +115,9 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
                                     bit for bit.  0: off (every state on one lane).  Default 32                              [KHG_K2S_HUB] */
 #define KHG_OPT_LAT_OPS_LDS 18   /* khg_lattices_best_path / khg_lattices_prune / khg_lattices_posteriors: 0 (DEFAULT) an utterance's lattice is staged into LDS when it takes
                                     at most 48 KiB there, 1 never (every lattice is read from its HBM arrays); same results bit for
-                                    bit                                                                              [KHG_LAT_OPS_LDS] */
+                                    bit.  khg_lattices_oracle: 0 the rows of two frames are kept in LDS when they fit, 1 never (read
+                                    back from the HBM table); khg_lattices_wer: 0 a table of at most 48 KiB stays in LDS, 1 never;
+                                    same results bit for bit                                                         [KHG_LAT_OPS_LDS] */
 #define KHG_OPT_K1_LAUNCH 19     /* launch shape of the default (f16x2s) K1: 1 one workgroup per chunk of frame tiles; 2 persistent -- one workgroup per
                                     CU takes chunks from a counter, in the same order, and copies the next chunk's frame tiles into LDS under
                                     the tail of the current one; 0 (DEFAULT) automatic: persistent where it measured faster, never for a small
@@ -649,6 +651,66 @@ typedef struct { int64_t in_states, in_arcs, out_states, out_arcs, max_hist; } k
  * Synchronous: one synchronisation per chunk sizes the output. */
 int khg_lattices_lm_rescore(khg_ctx *ctx, const khg_lattices *l, const khg_lm *lm, float scale, int32_t hist_factor,
                             int32_t *status_h, khg_lm_rescore_stats *stats, khg_lattices **out);
+
+/* ---- K2W: scoring resident lattices (lattice-add-penalty, lattice-oracle, score.sh's sweep, compute-wer) ---------- */
+/* lattice-add-penalty: a NEW handle, as khg_lattices_prune and khg_lattices_boost return one (the input is untouched; the chunks, the
+ * device offsets and the in-arc index go along).  Every arc with olabel != 0 gets graph_cost := fl(graph_cost + word_ins_penalty), one
+ * float add; every other field is copied (tot_cost / extra_cost are then stale, as after khg_lattices_rescore).  The penalty is finite,
+ * of either sign; otherwise KHG_E_ARG.  An empty lattice stays empty.  Synchronous. */
+int khg_lattices_add_penalty(khg_ctx *ctx, const khg_lattices *l, float word_ins_penalty, khg_lattices **out);
+/* lattice-oracle: per utterance the path of the lattice with the fewest word errors against a reference, by a dynamic program over
+ * (lattice state, reference position).  ref_h / ref_off_h[n_utt + 1]: the reference words of utterance u are
+ * ref_h[ref_off_h[u] .. ref_off_h[u + 1]), every word > 0 (an empty reference is legal).  The costs of the arcs are ignored.
+ * THE RULE.  R is the reference's length; E[s][q], q = 0 .. R, is an int32; values >= INF = 2^30 mean unreachable, and a candidate from
+ * an unreachable cell is skipped.  The states are visited in ascending number.  For a state s:
+ *   C[s][q] = INF, except 0 at (start, 0).
+ *   Every in-arc is tried in ascending arc number (source state, then arc: the in-arc index's order); it comes from p with olabel w:
+ *     w == 0:             the candidate E[p][q]                                   (move EPS)
+ *     w != 0, q >= 1:     first the candidate E[p][q-1] + (w != ref[q-1])         (move DIAG)
+ *     w != 0:             then the candidate E[p][q] + 1                          (move INS: a word of the lattice the reference lacks)
+ *     a candidate replaces the incumbent only when strictly smaller.
+ *   Then for q = 1 .. R ascending E[s][q] = min(C[s][q], E[s][q-1] + 1), the deletion (move DEL) taken only when strictly smaller
+ *   (E[s][0] = C[s][0]).
+ * The end state is the final state -- as khg_lattices_best_path takes final states: a state of the last frame with final_cost != +inf --
+ * with the least E[f][R]; the lowest state number wins ties.  The trace-back follows the recorded moves to (start, 0):
+ *   words = the path's olabels != 0; ali = its ilabels != 0, by the frame of the arc's source; substitutions = DIAG moves with a
+ *   mismatch, insertions = INS moves, deletions = DEL moves, errors = their sum = E[f][R].
+ * The split into insertions, deletions and substitutions among paths and alignments of equal errors is THIS rule's; the total is unique.
+ * Outputs (host; any may be NULL):
+ *   counts_h[n_utt][4]   errors, insertions, deletions, substitutions
+ *   words_h / words_off_h[n_utt + 1] / words_cap   khg_lattices_best_path's convention, KHG_LAT_WORDS included
+ *   ali_h                khg_lattices_ali_layout's layout: the oracle path's transition-ids by frame, 0 without a path
+ *   status_h[n_utt]      KHG_LAT_SUCCEEDED; KHG_LAT_NO_PATH: the lattice is empty or no final state is reachable; KHG_LAT_EPS_LOOP: an arc
+ *                        does not go to a higher state number (the lattice-simple decoder's epsilon self-loops: the refusal of
+ *                        khg_lattices_posteriors and khg_lattices_lm_rescore); KHG_LAT_SCRATCH: the utterance's own table --
+ *                        8 * states * (R + 1) bytes -- exceeds scratch_bytes.  With any of these three the counts are (R, 0, R, 0) and
+ *                        there are no words, so that sums over a set mean what compute-wer --mode=all means.
+ * scratch_bytes: the tables of one launch stay within it (a chunk is split into as many launches as that takes); 0: 1 GiB.
+ * The rows of the current frame and the one before are kept in LDS when they fit, unless KHG_OPT_LAT_OPS_LDS = 1; same results bit for bit.
+ * KHG_E_ARG before any launch: n_utt is not the handle's utterance count; scratch_bytes < 0; a reference word <= 0 (naming the
+ * utterance); an utterance with states + R >= 2^29, or with more than 2^31 - 4 arcs.  The first call on a handle builds its in-arc
+ * index (as khg_lattices_posteriors does) and keeps it.  Synchronous; the input is untouched. */
+int khg_lattices_oracle(khg_ctx *ctx, const khg_lattices *l, int32_t n_utt, const int32_t *ref_h, const int64_t *ref_off_h,
+                        int64_t scratch_bytes, int32_t *counts_h, int32_t *words_h, int64_t *words_off_h, int64_t words_cap,
+                        int32_t *ali_h, int32_t *status_h);
+/* score.sh's sweep in one call: for n_points triples (graph_scale, acoustic_scale, word_ins_penalty) -- scales finite and >= 0, the
+ * penalty finite -- the best path as khg_lattices_best_path finds it, with w1 = fl(fl(graph_scale * graph_cost) + word_ins_penalty) on
+ * the arcs with olabel != 0 (scale first, then penalty: the order of lattice-scale | lattice-add-penalty), and then the edit distance of
+ * the path's words against the reference by khg_edit_distance's rule, all on the device.  Only the counts come back:
+ *   counts_h[n_points * n_utt][4], nwords_h[n_points * n_utt] (the hypothesis's length), status_h[n_points * n_utt] (best_path's);
+ *   entry k * n_utt + u is point k of utterance u.  An utterance without a path counts as an empty hypothesis: (R, 0, R, 0).
+ * At penalty 0 the words scored are khg_lattices_best_path's at the same pair; at graph_scale 1 they are those of
+ * khg_lattices_add_penalty(p) followed by khg_lattices_best_path(1, acoustic_scale).  References as for khg_lattices_oracle.  Synchronous. */
+int khg_lattices_wer(khg_ctx *ctx, const khg_lattices *l, int32_t n_utt, const int32_t *ref_h, const int64_t *ref_off_h, int32_t n_points,
+                     const float *graph_scale, const float *acoustic_scale, const float *word_ins_penalty, int32_t *counts_h,
+                     int32_t *nwords_h, int32_t *status_h);
+/* compute-wer's core, host only (no context, no device): counts_h[n_pairs][4] = errors, insertions, deletions, substitutions of
+ * hyp_h[hyp_off_h[i] .. hyp_off_h[i + 1]) against ref_h[ref_off_h[i] .. ref_off_h[i + 1]).  The rule is khg_lattices_oracle's on the
+ * chain of the hypothesis words: per cell DIAG, then INS, then DEL, a candidate winning only when strictly better -- so the oracle of a
+ * single-path lattice and the edit distance of that path give the same four counts.  KHG_E_ARG: a NULL array, offsets that do not
+ * start at 0 or decrease, a pair whose lengths reach 2^29 together. */
+int khg_edit_distance(int32_t n_pairs, const int32_t *ref_h, const int64_t *ref_off_h, const int32_t *hyp_h, const int64_t *hyp_off_h,
+                      int32_t *counts_h);
 
 /* ---- K2M: MPE / sMBR posteriors of resident lattices (lattice-to-mpe-post, lattice-to-smbr-post) ------------------- */
 #define KHG_MPE_MPFE 0           /* an arc is correct when its phone is the reference's at that frame */

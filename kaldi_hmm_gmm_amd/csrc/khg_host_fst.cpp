@@ -599,6 +599,85 @@ LatticeLmRescored Lattice::LmRescore(const BackoffLm& lm, float scale, int hist_
   return out;
 }
 
+std::shared_ptr<Lattice> Lattice::AddPenalty(float word_ins_penalty) const {
+  KHG_REQUIRE(std::isfinite(word_ins_penalty), "Lattice::AddPenalty: word_ins_penalty must be finite");
+  auto r = std::make_shared<Lattice>(*this);
+  for (size_t a = 0; a < olabel.size(); ++a)
+    if (olabel[a] != 0) r->graph_cost[a] = graph_cost[a] + word_ins_penalty;
+  return r;
+}
+
+LatticeOracle Lattice::Oracle(const std::vector<int32_t>& ref) const {
+  for (int32_t w : ref) KHG_REQUIRE(w > 0, "Lattice::Oracle: a reference word is not > 0");
+  const int N = NumStates();
+  const int64_t R = (int64_t)ref.size(), W = R + 1;
+  KHG_REQUIRE((int64_t)N + R < (int64_t(1) << 29), "Lattice::Oracle: states + reference words reach 2^29");
+  LatticeOracle out;
+  out.status = KHG_LAT_NO_PATH;
+  out.counts[0] = out.counts[2] = (int32_t)R;
+  if (N == 0 || start < 0) return out;
+  out.ali.assign((size_t)std::max(frame[(size_t)N - 1], 0), 0);
+  for (int s = 0; s < N; ++s)
+    for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a)
+      if (nextstate[(size_t)a] <= s) { out.status = KHG_LAT_EPS_LOOP; return out; }
+  const int32_t INF = 1 << 30, NONE = -1, DEL = -2;
+  // the in-arcs of every state in ascending arc number, with their sources
+  std::vector<std::vector<int32_t>> in((size_t)N);
+  std::vector<int32_t> src((size_t)NumArcs());
+  for (int s = 0; s < N; ++s)
+    for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) { src[(size_t)a] = s; in[(size_t)nextstate[(size_t)a]].push_back(a); }
+  std::vector<int32_t> E((size_t)((int64_t)N * W), INF), M((size_t)((int64_t)N * W), NONE);      // a move: the arc (EPS, DIAG), -3 - arc (INS), NONE or DEL
+  for (int s = 0; s < N; ++s) {
+    int32_t* Es = E.data() + (int64_t)s * W;
+    int32_t* Ms = M.data() + (int64_t)s * W;
+    for (int64_t q = 0; q < W; ++q) {
+      int32_t C = s == start && q == 0 ? 0 : INF, mv = NONE;
+      for (int32_t a : in[(size_t)s]) {
+        const int32_t* Ep = E.data() + (int64_t)src[(size_t)a] * W;
+        const int32_t w = olabel[(size_t)a];
+        if (w == 0) {
+          if (Ep[q] < INF && Ep[q] < C) { C = Ep[q]; mv = a; }
+        } else {
+          if (q >= 1 && Ep[q - 1] < INF) { const int32_t c = Ep[q - 1] + (w != ref[(size_t)q - 1] ? 1 : 0); if (c < C) { C = c; mv = a; } }
+          if (Ep[q] < INF) { const int32_t c = Ep[q] + 1; if (c < C) { C = c; mv = -3 - a; } }
+        }
+      }
+      if (q >= 1 && Es[q - 1] < INF && Es[q - 1] + 1 < C) { C = Es[q - 1] + 1; mv = DEL; }
+      Es[q] = C; Ms[q] = mv;
+    }
+  }
+  const int T = frame[(size_t)N - 1];
+  const float FINF = std::numeric_limits<float>::infinity();
+  int fin = -1;
+  for (int s = 0; s < N; ++s) {
+    if (frame[(size_t)s] != T || final_cost[(size_t)s] == FINF) continue;
+    const int32_t e = E[(size_t)((int64_t)s * W + R)];
+    if (e < INF && (fin < 0 || e < E[(size_t)((int64_t)fin * W + R)])) fin = s;
+  }
+  if (fin < 0) return out;
+  int32_t ins = 0, del = 0, sub = 0;
+  int s = fin;
+  int64_t q = R;
+  for (;;) {
+    const int32_t mv = M[(size_t)((int64_t)s * W + q)];
+    if (mv == NONE) break;
+    if (mv == DEL) { ++del; --q; continue; }
+    const int32_t a = mv >= 0 ? mv : -3 - mv, w = olabel[(size_t)a];
+    if (mv < 0) ++ins;
+    else if (w != 0) { --q; if (w != ref[(size_t)q]) ++sub; }
+    if (w != 0) out.words.push_back(w);
+    out.arcs.push_back(a);
+    const int f = frame[(size_t)src[(size_t)a]];
+    if (ilabel[(size_t)a] != 0 && f >= 0 && f < T) out.ali[(size_t)f] = ilabel[(size_t)a];
+    s = src[(size_t)a];
+  }
+  std::reverse(out.words.begin(), out.words.end());
+  std::reverse(out.arcs.begin(), out.arcs.end());
+  out.counts[0] = ins + del + sub; out.counts[1] = ins; out.counts[2] = del; out.counts[3] = sub;
+  out.status = KHG_LAT_SUCCEEDED;
+  return out;
+}
+
 std::shared_ptr<Lattice> Lattice::Prune(float beam, float gs, float as, int* status) const {
   KHG_REQUIRE(beam >= 0.0f, "Lattice::Prune: beam must be >= 0");
   auto out = std::make_shared<Lattice>();

@@ -148,6 +148,15 @@ struct LatticeLmRescored {
   int64_t max_hist = 0;
 };
 
+// Lattice::Oracle (what khg_lattices_oracle gives for one lattice): KHG_LAT_* status (SUCCEEDED, NO_PATH, EPS_LOOP), the
+// counts (errors, insertions, deletions, substitutions; (R, 0, R, 0) without a path), the oracle path's words, its arcs, and its
+// transition-ids by frame (one entry per frame of the lattice, 0 where the path has none)
+struct LatticeOracle {
+  int status = 0;
+  int32_t counts[4] = {0, 0, 0, 0};
+  std::vector<int32_t> words, arcs, ali;
+};
+
 // The fst::VectorFst<LatticeArc> LatticeSimpleDecoder::GetRawLattice builds (csrc/lattice-simple-decoder.cc:654-735), as the flat arrays
 // khg_lattices_download hands back: a state per surviving token, numbered by frame, then by graph state (:684-690); state s owns arcs
 // arc_begin[s] .. arc_begin[s + 1], one per surviving forward link in the order of the graph's arcs in its state (:700-722); the last
@@ -211,6 +220,12 @@ class Lattice {
   // reach it, every arc with a word given fl(scale * the LM's cost of the word) more graph cost; the rule is stated at
   // khg_lattices_lm_rescore.  The history sets may hold min(hist_factor * states, 2^31 - 1) entries together (KHG_LAT_SCRATCH).
   LatticeLmRescored LmRescore(const BackoffLm& lm, float scale = 1.0f, int hist_factor = 8) const;
+  // lattice-add-penalty (what khg_lattices_add_penalty gives for one lattice): a copy in which every arc with olabel != 0 has
+  // graph_cost = fl(graph_cost + word_ins_penalty); everything else as stored
+  std::shared_ptr<Lattice> AddPenalty(float word_ins_penalty) const;
+  // lattice-oracle: the path with the fewest word errors against `ref` (words > 0), sequentially, cell by cell, by the
+  // rule written at khg_lattices_oracle in include/khg_hip.h
+  LatticeOracle Oracle(const std::vector<int32_t>& ref) const;
   // Kaldi's text form of a lattice: "src dst ilabel olabel graph,acoustic" per arc, "state graph,acoustic" per final state
   std::string ToText() const;
 

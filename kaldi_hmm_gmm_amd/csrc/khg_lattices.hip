@@ -5,7 +5,8 @@
 // (khg_k2_lattice_ops.hip.inc), its forward-backward posteriors (khg_posteriors, khg_k2_lattice_post.hip.inc) and their MPE / sMBR form
 // (khg_k2_lattice_mpe.hip.inc: the same device functions and the same host steps per chunk around a kernel of its own), and rescoring /
 // boosting (khg_lattices_rescore, khg_lattices_boost: khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc), and the backoff n-gram LM
-// (khg_lm) with khg_lattices_lm_rescore (khg_k2_lattice_lm.hip.inc).  gfx950 only.
+// (khg_lm) with khg_lattices_lm_rescore (khg_k2_lattice_lm.hip.inc), and scoring (khg_lattices_add_penalty, khg_lattices_oracle,
+// khg_lattices_wer, khg_edit_distance: khg_k2_lattice_score.hip.inc).  gfx950 only.
 #include "khg_internal.hpp"
 
 #include <memory>
@@ -22,6 +23,7 @@
 #include "khg_k2_lattice_rescore.hip.inc"
 #include "khg_k2_lattice_mpe.hip.inc"
 #include "khg_k2_lattice_lm.hip.inc"
+#include "khg_k2_lattice_score.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // The raw lattices of one batch (khg_decode_lattice_simple_raw, khg_decode_lattice_faster_raw): per chunk of scratch slices one
@@ -49,6 +51,9 @@ struct khg_lattices {
   std::vector<int32_t*> idx_d;
   khg_ctx* ctx = nullptr;                        // the context it was made on
   std::vector<int32_t> op_status;                // [U] KHG_LAT_* bits of the khg_lattices_rescore / _boost / _lm_rescore that made it (empty otherwise)
+  // the widest frame (states) of every utterance, made at the first khg_lattices_oracle: it sizes the oracle's ring of rows in LDS
+  int32_t* width_d = nullptr;                    // [U]
+  std::vector<int32_t> width;                    // [U]
 };
 
 namespace {
@@ -174,6 +179,7 @@ extern "C" int khg_lattices_destroy(khg_lattices* l) {
   if (l->start_d) (void)hipFree(l->start_d);
   if (l->off_d) (void)hipFree(l->off_d);
   for (int32_t* q : l->idx_d) if (q) (void)hipFree(q);
+  if (l->width_d) (void)hipFree(l->width_d);
   delete l;
   return KHG_OK;
 }
@@ -1920,5 +1926,338 @@ extern "C" int khg_lattices_lm_rescore(khg_ctx* ctx, const khg_lattices* lc, con
     for (int32_t m : mh) stats->max_hist = std::max<int64_t>(stats->max_hist, m);
   }
   *out = res.release();
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2W: scoring (khg_k2_lattice_score.hip.inc): the word insertion penalty, the oracle path, the sweep of score.sh
+namespace {
+const int64_t kScoreScratch = int64_t(1) << 30;       // khg_lattices_oracle's tables per launch when the caller names no size
+const int64_t kScoreWerLds = 48 << 10;                // khg_lattices_wer: a (triple, utterance) table stays in LDS up to this many bytes
+
+// the most dynamic LDS a workgroup of the current device may ask for: all 160 KiB of a gfx950 CU
+int score_lds_cap(int64_t* cap) {
+  int dev = 0, v = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  *cap = std::min<int64_t>(160 << 10, v);
+  return KHG_OK;
+}
+// the widest frame of every utterance, once per handle (after lat_meta)
+int lat_width(khg_ctx* ctx, khg_lattices* l) {
+  if (l->width_d || l->U == 0) return KHG_OK;
+  const size_t U = (size_t)l->U;
+  int32_t* w_d = nullptr;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&w_d), 4 * U));
+  l->width_d = w_d;
+  l->bytes += 4 * (int64_t)U;
+  for (const LatChunk& c : l->chunks) {
+    LoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p);
+    KHG_LAUNCH(ctx, k2_lattice_score_width, dim3((unsigned)((c.n + 63) / 64)), dim3(64), 0, ctx->stream, p, w_d);
+    HIPCHK(hipGetLastError());
+  }
+  l->width.assign(U, 0);
+  HIPCHK(hipMemcpyAsync(l->width.data(), w_d, 4 * U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
+// the references of a scoring call: n_utt is the handle's, offsets from 0 and monotone, words > 0
+int score_ref_check(const std::string& who, const khg_lattices* l, int32_t n_utt, const int32_t* ref_h, const int64_t* ref_off_h) {
+  if (n_utt != l->U) return khg_set_error(KHG_E_ARG, who + "the lattices hold " + std::to_string(l->U) + " utterances, the references " + std::to_string(n_utt));
+  if (!ref_off_h || ref_off_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "ref_off_h must start at 0");
+  for (int u = 0; u < n_utt; ++u)
+    if (ref_off_h[u + 1] < ref_off_h[u]) return khg_set_error(KHG_E_ARG, who + "ref_off_h decreases at utterance " + std::to_string(u));
+  if (ref_off_h[n_utt] > 0 && !ref_h) return khg_set_error(KHG_E_ARG, who + "ref_h is NULL");
+  for (int u = 0; u < n_utt; ++u) {
+    for (int64_t i = ref_off_h[u]; i < ref_off_h[u + 1]; ++i)
+      if (ref_h[i] <= 0) return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(u) + ": a reference word is not > 0");
+    if ((l->state_off[(size_t)u + 1] - l->state_off[(size_t)u]) + (ref_off_h[u + 1] - ref_off_h[u]) >= (int64_t(1) << 29))
+      return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(u) + ": states + reference words reach 2^29");
+  }
+  return KHG_OK;
+}
+// the references on the device
+int score_ref_upload(khg_ctx* ctx, int U, const int32_t* ref_h, const int64_t* ref_off_h, DevBlocks* dv, int32_t** ref_d, int64_t** ref_off_d) {
+  const int64_t n = ref_off_h[U];
+  int rc;
+  if ((rc = dv->alloc(std::max<int64_t>(n, 1), ref_d)) || (rc = dv->alloc(U + 1, ref_off_d))) return rc;
+  if (n > 0) HIPCHK(hipMemcpyAsync(*ref_d, ref_h, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(*ref_off_d, ref_off_h, 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  return KHG_OK;
+}
+}  // namespace
+
+extern "C" int khg_lattices_add_penalty(khg_ctx* ctx, const khg_lattices* lc, float word_ins_penalty, khg_lattices** out) {
+  const std::string who = "khg_lattices_add_penalty: ";
+  if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  *out = nullptr;
+  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (!std::isfinite(word_ins_penalty)) return khg_set_error(KHG_E_ARG, who + "word_ins_penalty must be finite");
+  int rc = arena_flush(ctx);
+  if (rc) return rc;
+  LatPtr res;
+  if ((rc = lat_clone(ctx, lc, std::vector<char>((size_t)lc->U, 0), &res))) return rc;
+  {
+    KernelTimer kt(ctx, "k2_lattice_score_add_penalty");
+    for (const LatChunk& c : res->chunks) {
+      if (c.na == 0) continue;
+      KHG_LAUNCH(ctx, k2_lattice_score_add_penalty, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (c.na + 255) / 256))), dim3(256), 0, ctx->stream,
+                 reinterpret_cast<float*>(c.buf + c.ar[2]), reinterpret_cast<const int32_t*>(c.buf + c.ar[1]), c.na, word_ins_penalty);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  if ((rc = check_err_flag(ctx, "khg_lattices_add_penalty"))) return rc;      // synchronises
+  *out = res.release();
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_oracle(khg_ctx* ctx, const khg_lattices* lc, int32_t n_utt, const int32_t* ref_h, const int64_t* ref_off_h, int64_t scratch_bytes,
+                                   int32_t* counts_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap, int32_t* ali_h, int32_t* status_h) {
+  const std::string who = "khg_lattices_oracle: ";
+  if (!lc) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  int rc = score_ref_check(who, lc, n_utt, ref_h, ref_off_h);
+  if (rc) return rc;
+  if (scratch_bytes < 0) return khg_set_error(KHG_E_ARG, who + "scratch_bytes must be >= 0");
+  if (ctx_dead(ctx)) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  if (words_off_h) std::fill(words_off_h, words_off_h + U + 1, 0);
+  if (U == 0) return KHG_OK;
+  for (int u = 0; u < U; ++u)
+    if (l->arc_off[(size_t)u + 1] - l->arc_off[(size_t)u] > (int64_t)INT32_MAX - 3)
+      return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(u) + ": more than 2^31 - 4 arcs");
+  const int64_t budget = scratch_bytes ? scratch_bytes : kScoreScratch;
+  int64_t lds_cap = 0;
+  rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc) rc = lat_index(ctx, l);
+  if (!rc) rc = lat_width(ctx, l);
+  if (!rc) rc = score_lds_cap(&lds_cap);
+  if (rc) return rc;
+  const int64_t AT = l->ali_off[(size_t)U];
+  DevBlocks dv;
+  int32_t *ref_d, *counts_d, *nw_d, *status_d, *ali_d, *list_d, *tab_d;
+  int64_t *ref_off_d, *ali_off_d, *tab_off_d;
+  // the utterances whose own table fits the budget, chunk by chunk, grouped into launches whose tables fit it together
+  std::vector<int32_t> list;
+  std::vector<int64_t> tab_off;
+  struct Launch { size_t chunk, first, n; int64_t cells, lds; };
+  std::vector<Launch> launches;
+  std::vector<char> too_big((size_t)U, 0);
+  int64_t max_cells = 1;
+  for (size_t k = 0; k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    Launch cur{k, list.size(), 0, 0, 0};
+    for (int u = c.u0; u < c.u0 + c.n; ++u) {
+      const int64_t N = l->state_off[(size_t)u + 1] - l->state_off[(size_t)u], W = ref_off_h[u + 1] - ref_off_h[u] + 1;
+      const int64_t cells = 2 * N * W;
+      if (4 * cells > budget) { too_big[(size_t)u] = 1; continue; }
+      if (cur.n > 0 && 4 * (cur.cells + cells) > budget) { launches.push_back(cur); cur = Launch{k, list.size(), 0, 0, 0}; }
+      list.push_back(u);
+      tab_off.push_back(cur.cells);
+      cur.cells += cells; ++cur.n;
+      const int64_t ring = 8 * (int64_t)l->width[(size_t)u] * W;
+      if (ctx->opt[KHG_OPT_LAT_OPS_LDS] != 1 && ring <= lds_cap) cur.lds = std::max(cur.lds, ring);
+    }
+    if (cur.n > 0) launches.push_back(cur);
+  }
+  for (const Launch& L : launches) max_cells = std::max(max_cells, L.cells);
+  const int64_t nl = std::max<int64_t>((int64_t)list.size(), 1);
+  if ((rc = score_ref_upload(ctx, U, ref_h, ref_off_h, &dv, &ref_d, &ref_off_d)) || (rc = dv.alloc(4 * (int64_t)U, &counts_d)) || (rc = dv.alloc(U, &nw_d)) ||
+      (rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(std::max<int64_t>(AT, 1), &ali_d)) || (rc = dv.alloc(U + 1, &ali_off_d)) || (rc = dv.alloc(nl, &list_d)) ||
+      (rc = dv.alloc(nl, &tab_off_d)) || (rc = dv.alloc(max_cells, &tab_d)))
+    return rc;
+  HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>(AT, 1), ctx->stream));
+  HIPCHK(hipMemsetAsync(status_d, 0, 4 * (size_t)U, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+  if (!list.empty()) {
+    HIPCHK(hipMemcpyAsync(list_d, list.data(), 4 * list.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tab_off_d, tab_off.data(), 8 * tab_off.size(), hipMemcpyHostToDevice, ctx->stream));
+  }
+  std::vector<int32_t*> words_d(l->chunks.size(), nullptr);
+  for (size_t k = 0; k < l->chunks.size(); ++k)
+    if ((rc = dv.alloc(std::max<int64_t>(l->chunks[k].ns, 1), &words_d[k]))) return rc;
+  for (const Launch& L : launches) {
+    const LatChunk& c = l->chunks[L.chunk];
+    ScArgs p;
+    std::memset(&p, 0, sizeof(p));
+    lat_chunk_args(l, c, &p.lo);
+    p.lo.lds_bytes = (int32_t)L.lds;
+    p.lo.status = status_d; p.lo.ali = ali_d; p.lo.ali_off = ali_off_d; p.lo.ali_total = AT; p.lo.words = words_d[L.chunk];
+    const LatIndex ix = lat_index_arrays(l->idx_d[L.chunk], c);
+    p.in_begin = ix.in_begin; p.in_arc = ix.in_arc; p.arc_src = ix.arc_src;
+    p.list = list_d + L.first; p.tab_off = tab_off_d + L.first; p.tab = tab_d; p.width = l->width_d;
+    p.ref = ref_d; p.ref_off = ref_off_d; p.counts = counts_d; p.nwords = nw_d;
+    if (L.lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_lattice_score_oracle, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    KernelTimer kt(ctx, "k2_lattice_score_oracle");
+    KHG_LAUNCH(ctx, k2_lattice_score_oracle, dim3((unsigned)L.n), dim3(SC_NT), (size_t)L.lds, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<int32_t> counts(4 * (size_t)U), nw((size_t)U), st((size_t)U), words;
+  HIPCHK(hipMemcpyAsync(counts.data(), counts_d, 16 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(nw.data(), nw_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  if (ali_h && AT) HIPCHK(hipMemcpyAsync(ali_h, ali_d, 4 * (size_t)AT, hipMemcpyDeviceToHost, ctx->stream));
+  const bool want_words = words_h && words_off_h;
+  if (want_words) {
+    words.resize((size_t)std::max<int64_t>(l->state_off[(size_t)U], 1));
+    for (size_t k = 0; k < l->chunks.size(); ++k) {
+      const LatChunk& c = l->chunks[k];
+      if (c.ns) HIPCHK(hipMemcpyAsync(words.data() + l->state_off[(size_t)c.u0], words_d[k], 4 * (size_t)c.ns, hipMemcpyDeviceToHost, ctx->stream));
+    }
+  }
+  rc = check_err_flag(ctx, "khg_lattices_oracle");     // synchronises: the scratch goes with `dv`
+  if (rc) return rc;
+  int64_t o = 0;
+  for (int u = 0; u < U; ++u) {
+    if (too_big[(size_t)u]) {
+      const int32_t R = (int32_t)(ref_off_h[u + 1] - ref_off_h[u]);
+      st[(size_t)u] = KHG_LAT_SCRATCH; nw[(size_t)u] = 0;
+      counts[4 * (size_t)u] = R; counts[4 * (size_t)u + 1] = 0; counts[4 * (size_t)u + 2] = R; counts[4 * (size_t)u + 3] = 0;
+    }
+    if (!want_words) continue;
+    words_off_h[u] = o;
+    int64_t n = (st[(size_t)u] & KHG_LAT_SUCCEEDED) ? nw[(size_t)u] : 0;
+    if (o + n > words_cap) { st[(size_t)u] = KHG_LAT_WORDS; n = 0; }      // the path's words do not fit: none of them
+    const int64_t end = l->state_off[(size_t)u + 1];       // (the kernel filled the utterance's slice from its end)
+    std::copy(words.begin() + (end - n), words.begin() + end, words_h + o);
+    o += n;
+  }
+  if (want_words) words_off_h[U] = o;
+  if (counts_h) std::copy(counts.begin(), counts.end(), counts_h);
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_wer(khg_ctx* ctx, const khg_lattices* lc, int32_t n_utt, const int32_t* ref_h, const int64_t* ref_off_h, int32_t n_points,
+                                const float* graph_scale, const float* acoustic_scale, const float* word_ins_penalty, int32_t* counts_h, int32_t* nwords_h,
+                                int32_t* status_h) {
+  const std::string who = "khg_lattices_wer: ";
+  if (!lc || n_points < 1 || !graph_scale || !acoustic_scale || !word_ins_penalty) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  int rc = score_ref_check(who, lc, n_utt, ref_h, ref_off_h);
+  if (rc) return rc;
+  for (int k = 0; k < n_points; ++k)
+    if (bad_scale(graph_scale[k]) || bad_scale(acoustic_scale[k]) || !std::isfinite(word_ins_penalty[k]))
+      return khg_set_error(KHG_E_ARG, who + "point " + std::to_string(k) + ": graph_scale and acoustic_scale must be finite and >= 0, word_ins_penalty finite");
+  if (ctx_dead(ctx)) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U, K = n_points;
+  if (U == 0) return KHG_OK;
+  rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (rc) return rc;
+  const int64_t KU = (int64_t)K * U;
+  DevBlocks dv;
+  int32_t *ref_d, *nw_d, *status_d, *counts_d;
+  float *gs_d, *as_d, *pen_d;
+  int64_t *ref_off_d, *hb_off_d;
+  unsigned char* hb_d;
+  if ((rc = score_ref_upload(ctx, U, ref_h, ref_off_h, &dv, &ref_d, &ref_off_d)) || (rc = dv.alloc(KU, &nw_d)) || (rc = dv.alloc(KU, &status_d)) ||
+      (rc = dv.alloc(4 * KU, &counts_d)) || (rc = dv.alloc(K, &gs_d)) || (rc = dv.alloc(K, &as_d)) || (rc = dv.alloc(K, &pen_d)) || (rc = dv.alloc(KU, &hb_off_d)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(gs_d, graph_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(as_d, acoustic_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(pen_d, word_ins_penalty, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<ScWerArgs> pcs;
+  for (const LatChunk& c : l->chunks) {
+    ScBpArgs q;
+    std::memset(&q, 0, sizeof(q));
+    LoArgs& p = q.lo;
+    lat_chunk_args(l, c, &p);
+    p.lds_bytes = lat_chunk_lds(ctx, l, c);
+    p.K = K; p.gs = gs_d; p.as = as_d; p.nwords = nw_d; p.status = status_d;
+    q.pen = pen_d;
+    const int64_t cells = std::max<int64_t>(c.ns * K, 1);
+    if ((rc = dv.alloc(cells, &p.d1)) || (rc = dv.alloc(cells, &p.d2)) || (rc = dv.alloc(cells, &p.n1)) || (rc = dv.alloc(cells, &p.n2)) ||
+        (rc = dv.alloc(cells, &p.bp)) || (rc = dv.alloc(cells, &p.words)))
+      return rc;
+    {
+      KernelTimer kt(ctx, "k2_lattice_score_best_path");
+      KHG_LAUNCH(ctx, k2_lattice_score_best_path, dim3((unsigned)c.n, (unsigned)((K + LO_NT - 1) / LO_NT)), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, q);
+      HIPCHK(hipGetLastError());
+    }
+    ScWerArgs w;
+    std::memset(&w, 0, sizeof(w));
+    w.lo = p;
+    pcs.push_back(w);
+  }
+  // the hypotheses' lengths size the tables: one synchronisation
+  std::vector<int32_t> nw((size_t)KU), st((size_t)KU), counts(4 * (size_t)KU);
+  HIPCHK(hipMemcpyAsync(nw.data(), nw_d, 4 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = check_err_flag(ctx, "khg_lattices_wer"))) return rc;
+  std::vector<int64_t> hb_off((size_t)KU, -1);
+  int64_t hb_total = 0, lds = 0;
+  const bool no_lds = ctx->opt[KHG_OPT_LAT_OPS_LDS] == 1;
+  for (int k = 0; k < K; ++k)
+    for (int u = 0; u < U; ++u) {
+      const size_t o = (size_t)k * U + u;
+      const int64_t H = (st[o] & KHG_LAT_SUCCEEDED) ? nw[o] : 0, W = ref_off_h[u + 1] - ref_off_h[u] + 1;
+      const int64_t need = 8 * W + (H + 1) * W;
+      if (!no_lds && need <= kScoreWerLds) lds = std::max(lds, need);
+      else { hb_off[o] = hb_total; hb_total += (need + 255) & ~int64_t(255); }
+    }
+  if ((rc = dv.alloc(std::max<int64_t>(hb_total, 1), &hb_d))) return rc;
+  HIPCHK(hipMemcpyAsync(hb_off_d, hb_off.data(), 8 * (size_t)KU, hipMemcpyHostToDevice, ctx->stream));
+  for (ScWerArgs& w : pcs) {
+    w.ref = ref_d; w.ref_off = ref_off_d; w.hb = hb_d; w.hb_off = hb_off_d; w.counts = counts_d;
+    KernelTimer kt(ctx, "k2_lattice_score_wer");
+    KHG_LAUNCH(ctx, k2_lattice_score_wer, dim3((unsigned)w.lo.n, (unsigned)K), dim3(SC_NT), (size_t)lds, ctx->stream, w);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(counts.data(), counts_d, 16 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = check_err_flag(ctx, "khg_lattices_wer"))) return rc;      // synchronises: the scratch goes with `dv`
+  if (counts_h) std::copy(counts.begin(), counts.end(), counts_h);
+  if (nwords_h) for (size_t o = 0; o < (size_t)KU; ++o) nwords_h[o] = (st[o] & KHG_LAT_SUCCEEDED) ? nw[o] : 0;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  return KHG_OK;
+}
+
+// compute-wer's core, on the host: the rule of khg_lattices_oracle on the chain of the hypothesis words, cell by cell as written
+extern "C" int khg_edit_distance(int32_t n_pairs, const int32_t* ref_h, const int64_t* ref_off_h, const int32_t* hyp_h, const int64_t* hyp_off_h, int32_t* counts_h) {
+  const std::string who = "khg_edit_distance: ";
+  if (n_pairs < 0 || !ref_off_h || !hyp_off_h || (n_pairs > 0 && !counts_h) || ref_off_h[0] != 0 || hyp_off_h[0] != 0)
+    return khg_set_error(KHG_E_ARG, who + "bad arguments (offsets start at 0)");
+  for (int i = 0; i < n_pairs; ++i)
+    if (ref_off_h[i + 1] < ref_off_h[i] || hyp_off_h[i + 1] < hyp_off_h[i]) return khg_set_error(KHG_E_ARG, who + "offsets decrease at pair " + std::to_string(i));
+  if ((ref_off_h[n_pairs] > 0 && !ref_h) || (hyp_off_h[n_pairs] > 0 && !hyp_h)) return khg_set_error(KHG_E_ARG, who + "bad arguments (an array is NULL)");
+  const int32_t INF = 1 << 30;
+  std::vector<int32_t> prev, row;
+  std::vector<unsigned char> mv;
+  for (int i = 0; i < n_pairs; ++i) {
+    const int32_t* ref = ref_h + ref_off_h[i];
+    const int32_t* hyp = hyp_h + hyp_off_h[i];
+    const int64_t R = ref_off_h[i + 1] - ref_off_h[i], H = hyp_off_h[i + 1] - hyp_off_h[i], W = R + 1;
+    if (R + H >= (int64_t(1) << 29)) return khg_set_error(KHG_E_ARG, who + "pair " + std::to_string(i) + ": the two lengths reach 2^29");
+    prev.assign((size_t)W, INF); row.assign((size_t)W, INF);
+    mv.assign((size_t)((H + 1) * W), 0);
+    for (int64_t h = 0; h <= H; ++h) {
+      for (int64_t q = 0; q < W; ++q) {
+        int32_t C = h == 0 && q == 0 ? 0 : INF;
+        unsigned char m = 0;
+        if (h > 0) {
+          if (q > 0 && prev[(size_t)q - 1] < INF) { const int32_t c = prev[(size_t)q - 1] + (hyp[h - 1] != ref[q - 1] ? 1 : 0); if (c < C) { C = c; m = 1; } }
+          if (prev[(size_t)q] < INF) { const int32_t c = prev[(size_t)q] + 1; if (c < C) { C = c; m = 2; } }
+        }
+        if (q > 0 && row[(size_t)q - 1] < INF && row[(size_t)q - 1] + 1 < C) { C = row[(size_t)q - 1] + 1; m = 3; }
+        row[(size_t)q] = C;
+        mv[(size_t)(h * W + q)] = m;
+      }
+      prev.swap(row);
+    }
+    int64_t h = H, q = R;
+    int32_t ins = 0, del = 0, sub = 0;
+    while (h > 0 || q > 0) {
+      const unsigned char m = mv[(size_t)(h * W + q)];
+      if (m == 1) { --h; --q; if (hyp[h] != ref[q]) ++sub; }
+      else if (m == 2) { --h; ++ins; }
+      else { --q; ++del; }
+    }
+    counts_h[4 * (size_t)i] = ins + del + sub; counts_h[4 * (size_t)i + 1] = ins; counts_h[4 * (size_t)i + 2] = del; counts_h[4 * (size_t)i + 3] = sub;
+  }
   return KHG_OK;
 }

@@ -324,6 +324,16 @@ void FlattenAlignments(const std::string& who, py::object alignment, int U, std:
   }
   ali->push_back(0);      // (never a NULL array)
 }
+// the references of DeviceLattices.oracle / .wer: a sequence of word sequences -> (off [n + 1], words)
+void FlattenRefs(py::object refs, std::vector<int64_t>* off, std::vector<int32_t>* words) {
+  off->assign(1, 0);
+  for (py::handle h : refs) {
+    Arr<int32_t> a = py::reinterpret_borrow<py::object>(h).cast<Arr<int32_t>>();
+    words->insert(words->end(), a.data(), a.data() + a.size());
+    off->push_back((int64_t)words->size());
+  }
+  words->push_back(0);      // (never a NULL array)
+}
 // an NgramLm (anything with to_arrays() -> {"backoff", "backoff_cost", "arc_begin", "word", "cost", "next", "final_cost", "start"}) as
 // the host's BackoffLm; checked by khg_lm_validate
 BackoffLm LmOf(py::object lm) {
@@ -449,6 +459,17 @@ void BindLattice(py::module_& m) {
         khg_lm_rescore_stats s = {l.NumStates(), l.NumArcs(), r.lattice->NumStates(), r.lattice->NumArcs(), r.max_hist};
         return py::make_tuple(r.lattice, r.status, LmStatsDict(s));
       }, py::arg("lm"), py::arg("scale") = 1.0f, py::arg("hist_factor") = 8)
+      // lattice-add-penalty on the host (what DeviceLattices.add_penalty gives for this lattice)
+      .def("add_penalty", [](const Lattice& l, float p) { return l.AddPenalty(p); }, py::arg("word_ins_penalty"))
+      // lattice-oracle on the host (what DeviceLattices.oracle gives for this lattice): status (KHG_LAT_* bits), counts
+      // (errors, insertions, deletions, substitutions), words, ali (one transition-id per frame, 0 where the path has none), arcs
+      .def("oracle", [](const Lattice& l, std::vector<int32_t> ref) {
+        const LatticeOracle r = l.Oracle(ref);
+        py::dict d;
+        d["status"] = r.status; d["counts"] = Vec1(std::vector<int32_t>(r.counts, r.counts + 4)); d["words"] = Vec1(r.words); d["ali"] = Vec1(r.ali);
+        d["arcs"] = Vec1(r.arcs);
+        return d;
+      }, py::arg("ref"))
       .def("to_text", &Lattice::ToText)
       .def("__str__", &Lattice::ToText)
       .def_property_readonly("frame", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.frame, l.frame.size()); })
@@ -696,6 +717,67 @@ void BindLattice(py::module_& m) {
         r->status.resize((size_t)U);
         return py::make_tuple(r, Vec1(r->status), LmStatsDict(st));
       }, py::arg("lm"), py::arg("scale") = 1.0f, py::arg("hist_factor") = 8)
+      // lattice-add-penalty -> a new DeviceLattices: graph_cost += word_ins_penalty on every arc with a word
+      .def("add_penalty", [](PyDeviceLattices& d, float p) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        auto r = std::make_shared<PyDeviceLattices>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj;
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_add_penalty(d.ctx, d.h, p, &r->h));
+        }
+        return r;
+      }, py::arg("word_ins_penalty"))
+      // lattice-oracle: refs is one word sequence per utterance -> counts [U][4] (errors, insertions, deletions,
+      // substitutions), words / words_off, ali / ali_off (the oracle path's transition-ids by frame), status
+      .def("oracle", [](PyDeviceLattices& d, py::object refs, int64_t scratch_bytes) {
+        const auto so = LatSizes(d);
+        const int U = (int)so.first.size() - 1;
+        std::vector<int64_t> roff;
+        std::vector<int32_t> rw;
+        FlattenRefs(refs, &roff, &rw);
+        std::vector<int64_t> aoff((size_t)U + 1, 0), woff((size_t)U + 1, 0);
+        std::vector<int32_t> st((size_t)std::max(U, 1), 0);
+        Arr<int32_t> counts({(py::ssize_t)U, (py::ssize_t)4});
+        const int64_t wcap = so.first.back() + 1;       // a path visits a state once
+        std::unique_ptr<int32_t[]> words(new int32_t[(size_t)wcap]);
+        if ((int)roff.size() - 1 == U) CApi(khg_lattices_ali_layout(d.ctx, d.h, aoff.data()));
+        Arr<int32_t> ali({(py::ssize_t)aoff.back()});
+        if (aoff.back() > 0) std::memset(ali.mutable_data(), 0, sizeof(int32_t) * (size_t)aoff.back());
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_oracle(d.ctx, d.h, (int32_t)roff.size() - 1, rw.data(), roff.data(), scratch_bytes, counts.mutable_data(), words.get(), woff.data(),
+                                   wcap, ali.mutable_data(), st.data()));
+        }
+        st.resize((size_t)U);
+        Arr<int32_t> wa({(py::ssize_t)woff.back()});
+        if (woff.back() > 0) std::memcpy(wa.mutable_data(), words.get(), sizeof(int32_t) * (size_t)woff.back());
+        py::dict r;
+        r["counts"] = counts; r["words"] = wa; r["words_off"] = Vec1(woff); r["ali"] = ali; r["ali_off"] = Vec1(aoff); r["status"] = Vec1(st);
+        return r;
+      }, py::arg("refs"), py::arg("scratch_bytes") = 0)
+      // score.sh's sweep: for every (graph_scale, acoustic_scale, penalty) triple the best path's word errors against refs
+      // -> counts [K * U][4], nwords [K * U], status [K * U]; entry k * U + u is triple k of utterance u
+      .def("wer", [](PyDeviceLattices& d, py::object refs, Arr<float> gs, Arr<float> as, Arr<float> pen) {
+        const auto so = LatSizes(d);
+        if (gs.ndim() != 1 || as.ndim() != 1 || pen.ndim() != 1 || gs.shape(0) != as.shape(0) || gs.shape(0) != pen.shape(0) || gs.shape(0) < 1)
+          throw Error("DeviceLattices.wer: graph_scales, acoustic_scales and penalties are three lists of the same length >= 1");
+        const int U = (int)so.first.size() - 1, K = (int)gs.shape(0);
+        std::vector<int64_t> roff;
+        std::vector<int32_t> rw;
+        FlattenRefs(refs, &roff, &rw);
+        Arr<int32_t> counts({(py::ssize_t)K * U, (py::ssize_t)4});
+        std::vector<int32_t> nw((size_t)K * U + 1, 0), st((size_t)K * U + 1, 0);
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_wer(d.ctx, d.h, (int32_t)roff.size() - 1, rw.data(), roff.data(), K, gs.data(), as.data(), pen.data(), counts.mutable_data(),
+                                nw.data(), st.data()));
+        }
+        nw.resize((size_t)K * U); st.resize((size_t)K * U);
+        py::dict r;
+        r["counts"] = counts; r["nwords"] = Vec1(nw); r["status"] = Vec1(st);
+        return r;
+      }, py::arg("refs"), py::arg("graph_scales"), py::arg("acoustic_scales"), py::arg("penalties"))
       .def("download", [](PyDeviceLattices& d) {
         if (!d.h) throw Error("DeviceLattices: closed");
         std::vector<std::shared_ptr<Lattice>> out;
@@ -706,6 +788,16 @@ void BindLattice(py::module_& m) {
         return out;
       })
       .def("close", &PyDeviceLattices::close);
+
+  // compute-wer's core on the host (khg_edit_distance): (errors, insertions, deletions, substitutions) of hyp against ref
+  m.def("edit_distance_counts", [](Arr<int32_t> ref, Arr<int32_t> hyp) {
+    if (ref.ndim() != 1 || hyp.ndim() != 1) throw Error("edit_distance_counts: ref and hyp are flat sequences of word ids");
+    const int64_t roff[2] = {0, (int64_t)ref.shape(0)}, hoff[2] = {0, (int64_t)hyp.shape(0)};
+    const int32_t none = 0;
+    Arr<int32_t> counts({(py::ssize_t)4});
+    CApi(khg_edit_distance(1, ref.shape(0) ? ref.data() : &none, roff, hyp.shape(0) ? hyp.data() : &none, hoff, counts.mutable_data()));
+    return counts;
+  }, py::arg("ref"), py::arg("hyp"));
 
   // DeviceLm(lm, ctx=None): an NgramLm uploaded (khg_lm_create); the handle belongs to its context
   py::class_<PyDeviceLm, std::shared_ptr<PyDeviceLm>>(m, "DeviceLm")

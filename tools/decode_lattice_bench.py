@@ -56,7 +56,14 @@ the same handle, and khg_acc_stats_post2 alternated with khg_acc_stats_post on t
 states and arcs and the largest history set (DESIGN.md 7r).  The linear training graphs carry no words (every state keeps one history);
 with --shared-graph the lattices come from the --words word loop, whose words the n-gram covers.
 
-Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post] [--acc] [--mpe] [--lmrescore [ORDER]]
+--oracle and --score LO:HI (next to --lattices) time scoring on the resident lattices: DeviceLattices.oracle beside the
+download plus a loop of the host form Lattice.oracle; DeviceLattices.wer at the LM weights LO..HI x penalties {0, 0.5, 1} beside
+add_penalty + best_path with the words downloaded + khg_edit_distance on the host; add_penalty beside a device-to-device copy of the
+same bytes.  The references are the words that were said (--shared-graph: the word loop's; the linear training graphs carry none), the
+report gives the table bytes per utterance, the lane occupancy (R + 1 over 64) and the states per frame, and with --shared-graph the
+same again on a denser set decoded at --dense-lattice-beam.
+
+Usage: python tools/decode_lattice_bench.py [--utts 100000] [--reps 2] [--decoder faster|simple] [--check N] [--lattices] [--sweep 7:17] [--prune-beam 4] [--post] [--acc] [--mpe] [--lmrescore [ORDER]] [--oracle] [--score 7:17]
        python tools/decode_lattice_bench.py --shared-graph --words 1000 --utts 2000 [--reps 3] [--hub 0,32] [--check N] [--yesno]
 """
 import argparse
@@ -474,6 +481,115 @@ def lmrescore_bench(ctx, dl, transcripts, vocab, order, reps, decode_call_s):
     return out
 
 
+def score_bench(ctx, dl, refs, score, oracle, reps):
+    """--oracle / --score LO:HI on resident lattices, both sides in this process and alternated.  --oracle:
+    DeviceLattices.oracle beside the download of every lattice and a loop of the host form Lattice.oracle.  --score: DeviceLattices.wer at
+    the LM weights LO..HI x penalties {0, 0.5, 1} beside the same points formed the old way -- add_penalty, best_path, the words
+    downloaded, khg_edit_distance on the host -- and add_penalty beside a device-to-device copy of the handle's bytes."""
+    import ctypes as C
+    from kaldi_hmm_gmm_amd import _lib
+    reps = max(reps, 3)
+    U = dl.num_utts
+    refs = [np.asarray(r, np.int32) for r in refs]
+    so, ao = np.asarray(dl.state_off), np.asarray(dl.arc_off)
+    N, R = np.diff(so), np.asarray([len(r) for r in refs])
+    out = {"utterances": U, "states_mean": float(N.mean()), "arcs_mean": float(np.diff(ao).mean()), "ref_words_mean": float(R.mean()), "repetitions": reps,
+           "table_bytes_per_utt_mean": float((8 * N * (R + 1)).mean()), "table_bytes_per_utt_max": int((8 * N * (R + 1)).max()),
+           "lane_occupancy_mean": float(((R + 1) / (64.0 * np.ceil((R + 1) / 64.0))).mean())}
+    if oracle:
+        r = dl.oracle(refs); ctx.sync()                                  # warm-up (builds the in-arc index once)
+        frames = np.maximum(np.diff(r["ali_off"]), 0) + 1
+        out["states_per_frame_mean"] = float((N / frames).mean())
+        t_dev, t_dl, t_host, k_ms, same = [], [], [], [], 0
+        for _ in range(reps):
+            k_ms.append(kernel_ms(ctx, lambda: dl.oracle(refs)))
+            ctx.sync(); t0 = time.time()
+            r = dl.oracle(refs)
+            t_dev.append(time.time() - t0)
+            t0 = time.time()
+            lats = dl.download()
+            t_dl.append(time.time() - t0)
+            t0 = time.time()
+            host = [L.oracle(x) for L, x in zip(lats, refs)]
+            t_host.append(time.time() - t0)
+            same = sum(1 for u, h in enumerate(host) if h["counts"].tolist() == r["counts"][u].tolist() and int(r["status"][u]) == h["status"])
+        ms = {k: float(np.median([x.get(k, 0.0) for x in k_ms])) for k in sorted({k for x in k_ms for k in x})}
+        c = r["counts"].astype(np.int64).sum(axis=0)
+        out["oracle"] = {"kernels_ms": ms, "call": med(t_dev), "download": med(t_dl), "host_loop": med(t_host), "same_as_host": same,
+                         "host_over_device": float(np.median(t_host)) / float(np.median(t_dev)), "succeeded": int((r["status"] & 1 != 0).sum()),
+                         "errors": int(c[0]), "ref_words": int(R.sum())}
+    if score:
+        lo, hi = (int(x) for x in score.split(":"))
+        pens = (0.0, 0.5, 1.0)
+        pts = [(w, p) for w in range(lo, hi + 1) for p in pens]
+        gs = np.ones(len(pts), np.float32)
+        as_ = np.asarray([1.0 / w for w, _ in pts], np.float32)
+        pn = np.asarray([p for _, p in pts], np.float32)
+        ro = np.concatenate([[0], np.cumsum(R)]).astype(np.int64)
+        rf = np.concatenate(refs + [np.zeros(1, np.int32)]).astype(np.int32)
+        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+
+        def old_way():
+            """-> counts [points * U][4] in wer's order"""
+            res = np.zeros((len(pts) * U, 4), np.int32)
+            for j, p in enumerate(pens):
+                d = dl.add_penalty(p)
+                ws = list(range(lo, hi + 1))
+                bp = d.best_path(np.ones(len(ws), np.float32), np.asarray([1.0 / w for w in ws], np.float32))
+                d.close()
+                ho = np.asarray(bp["words_off"], np.int64)
+                hf = np.concatenate([bp["words"], np.zeros(1, np.int32)]).astype(np.int32)
+                cnt = np.zeros((len(ws) * U, 4), np.int32)
+                rr = np.concatenate([[0], np.cumsum(np.tile(R, len(ws)))]).astype(np.int64)
+                rt = np.concatenate([np.concatenate(refs)] * len(ws) + [np.zeros(1, np.int32)]).astype(np.int32)
+                rc = _lib.lib.khg_edit_distance(len(ws) * U, rt.ctypes.data_as(p32), rr.ctypes.data_as(p64), hf.ctypes.data_as(p32), ho.ctypes.data_as(p64),
+                                                cnt.ctypes.data_as(p32))
+                assert rc == 0
+                for i in range(len(ws)):
+                    k = i * len(pens) + j
+                    res[k * U: (k + 1) * U] = cnt[i * U: (i + 1) * U]
+            return res
+
+        dl.wer(refs, gs, as_, pn); old_way(); ctx.sync()                  # warm-up
+        t_new, t_old, k_ms, same = [], [], [], False
+        for _ in range(reps):
+            k_ms.append(kernel_ms(ctx, lambda: dl.wer(refs, gs, as_, pn)))
+            ctx.sync(); t0 = time.time()
+            w = dl.wer(refs, gs, as_, pn)
+            t_new.append(time.time() - t0)
+            t0 = time.time()
+            o = old_way()
+            t_old.append(time.time() - t0)
+            same = bool((o == w["counts"]).all())
+        ms = {k: float(np.median([x.get(k, 0.0) for x in k_ms])) for k in sorted({k for x in k_ms for k in x})}
+        err = w["counts"][:, 0].reshape(len(pts), U).astype(np.int64).sum(axis=1)
+        out["wer"] = {"points": len(pts), "kernels_ms": ms, "call": med(t_new), "old_way": med(t_old), "same_counts_as_old_way": same,
+                      "old_over_new": float(np.median(t_old)) / float(np.median(t_new)), "best_point": list(pts[int(err.argmin())]),
+                      "best_errors": int(err.min()), "ref_words": int(R.sum()), "bytes_back": int(w["counts"].nbytes + w["nwords"].nbytes + w["status"].nbytes)}
+        # add_penalty beside a device-to-device copy of the same bytes
+        nbytes = 4 * (6 * int(so[-1]) + 5 * int(ao[-1]))
+        t_pen, t_copy, k_pen = [], [], []
+        try:
+            import torch
+            a = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+            b = torch.empty_like(a)
+        except Exception:
+            torch = None
+        for _ in range(reps):
+            k_pen.append(kernel_ms(ctx, lambda: dl.add_penalty(0.5).close()))
+            ctx.sync(); t0 = time.time()
+            d = dl.add_penalty(0.5)
+            t_pen.append(time.time() - t0)
+            d.close()
+            if torch is not None:
+                torch.cuda.synchronize(); t0 = time.time()
+                b.copy_(a); torch.cuda.synchronize()
+                t_copy.append(time.time() - t0)
+        out["add_penalty"] = {"bytes": nbytes, "call": med(t_pen), "device_copy": med(t_copy) if t_copy else None,
+                              "kernel_ms": float(np.median([x.get("k2_lattice_score_add_penalty", 0.0) for x in k_pen]))}
+    return out
+
+
 def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
     """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
     after one warm-up round; and the last results."""
@@ -545,7 +661,8 @@ def shared_graph_main(args):
     g, pdfs = word_loop(m, args.words, args.seed + 7, False, args.loop_states)
     gl, _ = word_loop(m, args.words, args.seed + 7, True, args.loop_states)
     rng = np.random.default_rng(args.seed + 1000)
-    seqs = [np.concatenate([pdfs[int(k)] for k in rng.integers(0, args.words, size=int(rng.integers(2, 5)))]) for _ in range(args.utts)]
+    picks = [rng.integers(0, args.words, size=int(rng.integers(2, 5))) for _ in range(args.utts)]          # the words said: word k carries the id k + 1
+    seqs = [np.concatenate([pdfs[int(k)] for k in p]) for p in picks]
     durs = [rng.geometric(0.25, size=len(sq)) for sq in seqs]
     frame_pdf = np.concatenate([np.repeat(sq, d) for sq, d in zip(seqs, durs)])
     fo = np.concatenate([[0], np.cumsum([int(d.sum()) for d in durs])]).astype(np.int64)
@@ -647,6 +764,13 @@ def shared_graph_main(args):
             transcripts = [bp["words"][wo[u]: wo[u + 1]].tolist() for u in range(U)]
             entry["lmrescore"] = lmrescore_bench(ctx, L, transcripts, range(1, args.words + 1), args.lmrescore, args.reps, med(t_dec))
             L.close()
+        if (args.oracle or args.score) and name == "faster":
+            # scoring the lattices the shared set leaves on the device against the words that were said; again at a wider lattice beam
+            entry["score"] = {}
+            for lb in (6.0, args.dense_lattice_beam):
+                L = sh.raw_lattices_faster_device(dtm, beam=13.0, max_active=7000, lattice_beam=lb, acoustic_scale=0.1)["lattices"]
+                entry["score"]["lattice_beam_%g" % lb] = score_bench(ctx, L, [p + 1 for p in picks], args.score, args.oracle, args.reps)
+                L.close()
         for us in sets.values():
             us.close()
         dg.close()
@@ -681,7 +805,14 @@ def main():
     ap.add_argument("--boost", type=float, default=0.0, metavar="B", help="with --rescore: also khg_lattices_boost at this b")
     ap.add_argument("--lmrescore", type=int, nargs="?", const=2, default=0, metavar="ORDER", help="with --lattices (--decoder faster): "
                     "khg_lattices_lm_rescore on the resident lattices with an n-gram of this order (2) estimated from the decoded words")
+    ap.add_argument("--oracle", action="store_true", help="with --lattices (--decoder faster): DeviceLattices.oracle on the resident lattices beside the "
+                    "download and a loop of the host form Lattice.oracle (DESIGN.md 7s)")
+    ap.add_argument("--score", default=None, metavar="LO:HI", help="with --lattices (--decoder faster): DeviceLattices.wer at the LM weights LO..HI x "
+                    "penalties {0, 0.5, 1} beside add_penalty + best_path + the host's khg_edit_distance; add_penalty beside a device copy")
+    ap.add_argument("--dense-lattice-beam", type=float, default=12.0, help="with --shared-graph --oracle / --score: the second, denser set's lattice beam")
     args = ap.parse_args()
+    if (args.oracle or args.score) and (not args.lattices or args.decoder != "faster" or args.yesno):
+        ap.error("--oracle / --score need --lattices with --decoder faster (and are not timed with --yesno)")
     if (args.sweep or args.prune_beam is not None or args.post) and not args.lattices:
         ap.error("--sweep / --prune-beam / --post need --lattices")
     if args.rescore and (not args.lattices or args.decoder != "faster" or args.shared_graph or args.yesno):
@@ -752,7 +883,7 @@ def main():
                     emission_kernels_ms=emit, emission_over_decoder=(emit + dec_new - dec_old) / dec_old if dec_old else None)
         faster_lat = flat
         faster_ops = None
-        if args.sweep or args.prune_beam is not None or args.post or args.rescore or args.mpe or args.lmrescore:
+        if args.sweep or args.prune_beam is not None or args.post or args.rescore or args.mpe or args.lmrescore or args.oracle or args.score:
             _, dl = khg.get_raw_lattice_faster_device_batch(am, tm, fsts, feats, cfg, 0.1)
             faster_ops = {}
             if args.sweep or args.prune_beam is not None or args.post:
@@ -766,6 +897,8 @@ def main():
             if args.lmrescore:
                 vocab = sorted(set(int(w) for w in np.unique(ut.graphs["olabel"]) if w > 0))
                 faster_ops["lmrescore"] = lmrescore_bench(ctx, dl, [r["words"] for r in fres], vocab, args.lmrescore, args.reps, flat["raw_decode_call"])
+            if args.oracle or args.score:
+                faster_ops["score"] = score_bench(ctx, dl, [r["words"] for r in fres], args.score, args.oracle, args.reps)
             dl.close()
     st = [r["status"] for r in res]
     out = {"decoder": args.decoder,"utterances": args.utts, "frames": frames, "lattice_s": min(lat_s), "lattice_frames_per_s": frames / min(lat_s),
