@@ -134,7 +134,11 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
                                     instead of splitting the raw features in every pass: 0 (DEFAULT) automatic -- where the records fit half of
                                     the free device memory at the first pass, never for a small set; 1 off; 2 on (still the in-loop split when
                                     the allocation fails); same statistics bit for bit                          [KHG_K3_PLANES=auto|off|on] */
-#define KHG_OPT_COUNT 24
+#define KHG_OPT_K2_TAIL 24       /* the single-wave tail of K2's exact DP (trace-back and forward replay of the best path): 0 (DEFAULT) the trace-back
+                                    decodes one packed source word per cell (in-degree <= 3, one state per thread, <= 256 states) and the
+                                    replay's fp64 cost chain runs as a wave scan wherever that is exact, 1 the loops they replaced; same
+                                    results bit for bit                                                                 [KHG_K2_TAIL=on|off] */
+#define KHG_OPT_COUNT 25
 /* Read-only figures (khg_ctx_get_option only): the per-call scratch block behind small utterance sets (DESIGN.md "per-utterance calls"). */
 #define KHG_INFO_SCRATCH_BYTES 100   /* bytes of the block in use (its top), 0 before the first small set */
 #define KHG_INFO_SCRATCH_BLOCKS 101  /* live allocations inside it */
@@ -228,6 +232,10 @@ int khg_utts_pdfs(const khg_utts *u, int32_t *pdfs_h /* [pdf_off[n_utt]] */);
 int khg_utts_k2_plan(khg_ctx *ctx, const khg_utts *u, int32_t out[8]);
 /* ... and whether it would run the ladder form of that kernel (KHG_OPT_K2_LADDER): *out = 1, else 0. */
 int khg_utts_k2_ladder(khg_ctx *ctx, const khg_utts *u, int32_t *out);
+/* After a khg_align under KHG_OPT_K2_PROF: per utterance, how many 64-entry batches of the exact DP's replay ran their cost chain as a
+   wave scan (out[2 u]) and how many as the serial loop (out[2 u + 1]) -- KHG_OPT_K2_TAIL; zeros for an utterance the kernel left
+   before its replay.  cap: int32 entries of out, >= 2 * utterances.  KHG_E_ARG without such a call. */
+int khg_utts_k2_tail(const khg_utts *u, int32_t *out, int64_t cap);
 /* K3's split feature records on the set (KHG_OPT_K3_PLANES): *bytes of the buffer (0: none), *packs = how often it was filled so far,
  * *used = 1 when the last khg_acc_stats pass read it.  Launches nothing. */
 int khg_utts_k3_planes(const khg_utts *u, int64_t *bytes, int64_t *packs, int32_t *used);

@@ -301,6 +301,7 @@ struct khg_utts {
   int32_t *ali2_d = nullptr, *unc_d = nullptr, *unc_cnt_h = nullptr, *unc_cnt_dev = nullptr;
   int64_t* sub_off_d = nullptr;     // [U + 1] first position of an uncertified utterance's frames in the second K3 pass
   bool ali_split = false;
+  std::vector<int32_t> k2_tail;     // khg_utts_k2_tail: (scanned, serial) replay batches per utterance of the last khg_align under KHG_OPT_K2_PROF
   // K3 scratch
   int32_t *pdf_count_d = nullptr, *pdf_cursor_d = nullptr, *frame_ids_d = nullptr;
   uint32_t *sort_keys_d = nullptr, *sort_keys_out_d = nullptr, *sort_vals_d = nullptr; void* sort_tmp_d = nullptr; size_t sort_tmp_bytes = 0;

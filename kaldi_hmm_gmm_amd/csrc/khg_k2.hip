@@ -156,6 +156,14 @@ extern "C" int khg_utts_k2_ladder(khg_ctx* ctx, const khg_utts* u, int32_t* out)
   return KHG_OK;
 }
 
+extern "C" int khg_utts_k2_tail(const khg_utts* u, int32_t* out, int64_t cap) {
+  if (!u || !out) return khg_set_error(KHG_E_ARG, "khg_utts_k2_tail: bad arguments");
+  if (u->k2_tail.empty()) return khg_set_error(KHG_E_ARG, "khg_utts_k2_tail: no khg_align under KHG_OPT_K2_PROF on this set yet");
+  if (cap < (int64_t)u->k2_tail.size()) return khg_set_error(KHG_E_ARG, "khg_utts_k2_tail: cap too small");
+  std::copy(u->k2_tail.begin(), u->k2_tail.end(), out);
+  return KHG_OK;
+}
+
 extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_align_config* cfg,
                          int32_t* ali_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap,
                          float* like_h, int32_t* status_h) {
@@ -206,6 +214,7 @@ extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_
   a.ali = u->ali_d; a.ali_fb = u->ali_d; a.unc = nullptr; a.unc_cnt = nullptr; a.words = u->words_d; a.words_off = u->words_off_d; a.num_words = u->num_words_d;
   a.like = u->like_d; a.status = u->status_d; a.err_flag = ctx->err_flag_d;
   a.prof = nullptr;
+  a.tail_off = ctx->opt[KHG_OPT_K2_TAIL];
   // launch order of the DP kernel: longest utterances first (built once per set)
   if (!u->k2_order_d && u->n_utt > 1) {
     std::vector<int32_t> ord((size_t)u->n_utt);
@@ -334,9 +343,16 @@ extern "C" int khg_align(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, const khg_
     HIPCHK(hipMemcpy(pr.data(), a.prof, pr.size() * 8, hipMemcpyDeviceToHost));
     (void)hipFree(a.prof);
     double ph[4] = {0, 0, 0, 0}, sT = 0, sS = 0, sf = 0; int n = 0;
-    for (int i = 0; i < u->n_utt; ++i) if (pr[i * 8 + 4]) { for (int k = 0; k < 4; ++k) ph[k] += (double)(pr[i * 8 + k + 1] - pr[i * 8 + k]); sT += pr[i * 8 + 5]; sS += pr[i * 8 + 6]; sf += pr[i * 8 + 7]; ++n; }
-    if (n) fprintf(stderr, "[KHG_K2_PROF] %d utts, avg T %.1f S %.1f fast %.2f threads %d lds %zu | ticks: setup %.0f forward %.0f traceback %.0f replay %.0f\n",
-                   n, sT / n, sS / n, sf / n, nthr, lds_dp, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n);
+    for (int i = 0; i < u->n_utt; ++i) if (pr[i * 8 + 4]) { for (int k = 0; k < 4; ++k) ph[k] += (double)(pr[i * 8 + k + 1] - pr[i * 8 + k]); sT += pr[i * 8 + 5]; sS += pr[i * 8 + 6]; sf += (double)(pr[i * 8 + 7] & 0xff); ++n; }
+    // word 7: FAST | replay batches whose cost chain was scanned << 8 | those that took the serial loop << 32 (KHG_OPT_K2_TAIL)
+    u->k2_tail.assign(2 * (size_t)u->n_utt, 0);
+    long long bs = 0, bl = 0;
+    for (int i = 0; i < u->n_utt; ++i) {
+      u->k2_tail[2 * (size_t)i] = (int32_t)((pr[i * 8 + 7] >> 8) & 0xffffff); u->k2_tail[2 * (size_t)i + 1] = (int32_t)(pr[i * 8 + 7] >> 32);
+      bs += u->k2_tail[2 * (size_t)i]; bl += u->k2_tail[2 * (size_t)i + 1];
+    }
+    if (n) fprintf(stderr, "[KHG_K2_PROF] %d utts, avg T %.1f S %.1f fast %.2f threads %d lds %zu | ticks: setup %.0f forward %.0f traceback %.0f replay %.0f | replay batches: %lld scanned, %lld serial\n",
+                   n, sT / n, sS / n, sf / n, nthr, lds_dp, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, bs, bl);
     const long long* pc = pr.data() + 8 * (size_t)u->n_utt;     // chain decoder: 0 start, 1 set-up done, 2 frames done (all attempts), 3 finished, 4 frames decoded
     double cs[3] = {0, 0, 0}, cf = 0, cp[3] = {0, 0, 0}; int nc = 0;
     for (int i = 0; i < u->n_utt; ++i) if (pc[i * 8 + 3]) { for (int k = 0; k < 3; ++k) { cs[k] += (double)(pc[i * 8 + k + 1] - pc[i * 8 + k]); cp[k] += (double)pc[i * 8 + 5 + k]; } cf += (double)pc[i * 8 + 4]; ++nc; }

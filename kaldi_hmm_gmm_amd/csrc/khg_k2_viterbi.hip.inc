@@ -71,10 +71,19 @@ struct K2Args {
   int64_t gscratch_stride;
   // k2_viterbi_dp: workgroup b takes utterance order[b] (longest first: the grid then drains on short utterances), or b
   const int32_t* order;
+  // k2_viterbi_dp's tail (KHG_OPT_K2_TAIL): 0 the trace-back on packed source words and the scanned replay, 1 the loops they replaced
+  int32_t tail_off;
 };
 
 #ifndef K2_WAVES_PER_EU
 #define K2_WAVES_PER_EU 5          // register budget of the DP kernel: 5 waves per SIMD = 96 VGPRs (it used 104: four waves)
+#endif
+// measurement builds: either part of the tail (KHG_OPT_K2_TAIL) alone
+#ifndef K2_TAIL_TRACE
+#define K2_TAIL_TRACE 1
+#endif
+#ifndef K2_TAIL_REPLAY
+#define K2_TAIL_REPLAY 1
 #endif
 #define K2_BP_NONE 255
 #define K2_ST_NEED_FALLBACK 16   // internal: certificate failed, run the faithful kernel
@@ -218,6 +227,31 @@ __device__ __forceinline__ double k2_dpp_d(double old, double v) {
   const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, ROWMASK, 0xf, false);
   const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, ROWMASK, 0xf, false);
   return __hiloint2double(hi, lo);
+}
+// Inclusive wave scan of doubles by DPP, lane k <- v[0] + ... + v[k] in tree order: four shifts inside the rows of 16 lanes, then lane
+// 15 of rows 0 / 2 into rows 1 / 3 and lane 31 into rows 2 and 3.  A lane without a source adds +0.  (The replay's cost chain, where
+// every one of these additions is exact, and its running sum of magnitudes.)
+__device__ __forceinline__ double k2_wave_scand(double v) {
+  v += k2_dpp_d<0x111, 0xf>(0.0, v);      // row_shr:1
+  v += k2_dpp_d<0x112, 0xf>(0.0, v);      // row_shr:2
+  v += k2_dpp_d<0x114, 0xf>(0.0, v);      // row_shr:4
+  v += k2_dpp_d<0x118, 0xf>(0.0, v);      // row_shr:8
+  v += k2_dpp_d<0x142, 0xa>(0.0, v);      // row_bcast:15 -> rows 1, 3
+  v += k2_dpp_d<0x143, 0xc>(0.0, v);      // row_bcast:31 -> rows 2, 3
+  return v;
+}
+__device__ __forceinline__ double k2_readlane_d(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ double k2_wave_sumd(double v) { return k2_readlane_d(k2_wave_scand(v), 63); }   // uniform
+__device__ __forceinline__ unsigned k2_wave_minu(unsigned v) {                                             // uniform
+  v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));
+  v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));
+  v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));
+  v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));
+  v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));
+  v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));
+  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 __device__ __forceinline__ int k2_wave_sum(int v) {
 #pragma unroll
@@ -808,6 +842,73 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
           wn[q] = 0u;
         }
         int sst = __builtin_amdgcn_readfirstlane(st);
+        // The tail (KHG_OPT_K2_TAIL = 0), in-degree <= 3, one state per thread: the chain needs ONE thing of a cell, the source state
+        // of the arc its nibble names.  The <= DEG candidates of a lane's state are loaded once per utterance into registers (already
+        // shifted), a cell costs a bit-field extract, a select among them and an OR -- source << NBITS | raw nibble bits in one
+        // register, no arc index, no flag packing, no LDS read -- and a hop is one v_readlane whose word is taken apart in scalar code
+        // by k2_decode_nibble's rule.  Lane cnt keeps (state << NBITS | ordinal) of its step; the arc indices path[] holds are formed
+        // after the eight hops, one LDS read per lane.  path[], n, bad, ptie and st are those of the loop below for every input.
+        if constexpr (K2_TAIL_TRACE && DEG <= 3 && KS == 1) {
+          if (!a.tail_off) {
+            constexpr int NBITS = NB + 1;
+            int srcr[NSLOT][DEG], srcx[NSLOT][DEG];
+#pragma unroll
+            for (int q = 0; q < NSLOT; ++q) {
+              const int sq = lane + 64 * q;
+              const int ib = sq < S ? s_in_off[sq] : 0, ie = sq < S ? s_in_off[sq + 1] : 0;
+#pragma unroll
+              for (int j = 0; j < DEG; ++j) srcr[q][j] = ib + j < ie ? (int)((arcw[2 * (ib + j)] & 0xffffu) << NBITS) : 0;
+#pragma unroll
+              for (int j = 0; j + 1 < DEG; ++j) srcx[q][j] = srcr[q][j] ^ srcr[q][DEG - 1];      // candidate j against the last one
+            }
+            for (; g >= 0 && !bad; --g) {
+              if (g > 0) {
+#pragma unroll
+                for (int q = 0; q < NSLOT; ++q) wn[q] = W[(int64_t)(g - 1) * GW + min(lane + 64 * q, GW - 1)];  // next word: in flight under this one
+              }
+              int pk[8][NSLOT];
+#pragma unroll
+              for (int k = 0; k < 8; ++k)
+#pragma unroll
+                for (int q = 0; q < NSLOT; ++q) {
+                  // (masks, not selects between array elements: those become indexed loads from a stack copy of srcr)
+                  const int nib = (int)((w[q] >> (4 * k)) & (unsigned)((1 << NBITS) - 1));
+                  int sel = srcr[q][0];
+                  if constexpr (DEG == 2) sel = srcr[q][1] ^ (srcx[q][0] & -(nib & 1));
+                  if constexpr (DEG == 3) { const int o = nib & BNONE; sel = srcr[q][2] ^ (srcx[q][0] & -(int)(o == 0)) ^ (srcx[q][1] & -(int)(o == 1)); }
+                  pk[k][q] = sel | nib;
+                }
+              int pv = 0, cnt = 0;
+#pragma unroll
+              for (int k = 7; k >= 0; --k) {
+                const int L = 8 * g + k;
+                if (L <= T && L >= 1 && !bad) {
+                  const int q = sst >> 6, l = sst & 63;
+                  int pw = __builtin_amdgcn_readlane(pk[k][0], l);
+#pragma unroll
+                  for (int qq = 1; qq < NSLOT; ++qq)
+                    if (q == qq) pw = __builtin_amdgcn_readlane(pk[k][qq], l);
+                  int ord, tieb;
+                  k2_decode_nibble<DEG, NB>(pw & ((1 << NBITS) - 1), ord, tieb);
+                  if (ord == BNONE) {
+                    bad = 1;                                 // a dead cell on the walk (cannot happen from a reachable final state)
+                  } else {
+                    ptie |= tieb;
+                    pv = lane == cnt ? ((sst << NBITS) | ord) : pv;    // lane cnt keeps (state, ordinal) of this step
+                    ++cnt;
+                    sst = pw >> NBITS;
+                  }
+                }
+              }
+              if (lane < cnt) path[n + lane] = s_in_off[pv >> NBITS] + (pv & BNONE);     // coalesced, path order
+              n += cnt;
+#pragma unroll
+              for (int q = 0; q < NSLOT; ++q) w[q] = wn[q];
+            }
+            st = sst;
+            return;
+          }
+        }
         for (; g >= 0 && !bad; --g) {
           if (g > 0) {
 #pragma unroll
@@ -928,9 +1029,101 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
   const int64_t wcap = a.words_off[u + 1] - a.words_off[u];
   int32_t* words = a.words + a.words_off[u];
   k2_global_sync();   // path[] written by lane 0 is read by every lane below
-  if (!bad) {
+  int nscan = 0, nserial = 0;     // replay batches whose cost chain ran as a wave scan / as the serial loop (KHG_OPT_K2_PROF)
+  bool replayed = false;
+  // ---- the tail's replay (KHG_OPT_K2_TAIL = 0), register-resident forms: no epsilon arcs, every entry emits (no col >= 0 tests), and
+  // the fp64 cost chain ((cost + w) + ac per entry, 64 dependent iterations a batch) runs as a six-step wave scan of
+  // d = (double)w + (double)ac seeded with the incoming cost in lane 0 -- WHERE THAT IS EXACT:
+  //   let the addends of the utterance so far be the floats w_i, ac_i, e_min the smallest binary exponent among the non-zero ones
+  //   (all normal, >= 2^-100, finite) and q = 2^(e_min - 23).  (1) Every addend is an integer multiple of q: a normal float of
+  //   exponent e >= e_min is a multiple of 2^(e - 23).  (2) If sum |addend| <= 2^52 q, every sum of a subset of the addends, in any
+  //   order and association, is an integer multiple of q of magnitude < 2^53 q: a binary64 number.  (3) So no addition of the
+  //   reference's chain rounds, nor any of the scan's: both give the exact sums -- the same bits; a zero sum is +0 in both, since the
+  //   chain starts from +0 and every scanned value includes lane 0's.
+  // The running sum |addend| is itself rounded (relative error <= 2^-53 per add, a few thousand adds): the bound is 2^52 q, not
+  // 2^53 q, a margin no such error reaches.  The first batch that fails the rule (NaN fails the comparison) and every later one of
+  // the utterance take the serial loop: once an addition has rounded, the incoming cost is off the grid.  The float sums of the
+  // LatticeWeight round at every step: they stay a serial chain, both in one packed add. ----
+  if constexpr (FAST && K2_TAIL_REPLAY) {
+    if (!bad && !a.tail_off) {
+      replayed = true;
+      ok = (0.0 < lbest[0] + beam) || lcnt[0] <= a.min_active;
+      unsigned emin1 = 0xffffffffu;      // (bits of the smallest non-zero |addend| so far) - 1; all ones: none yet
+      double sumabs = 0.0;               // running sum |addend|
+      bool serial = false;
+      f32x2 vv = {0.0f, 0.0f};
+      for (int base = n - 1; base >= 0; base -= 64) {
+        const int idx = base - lane;                     // lane k handles path[base-k] (forward order)
+        const bool mine = idx >= 0;
+        int ai = 0, col = 0, tidl = 0, ol = 0; float w = 0.0f, ac = 0.0f;
+        if (mine) {
+          ai = path[idx];
+          K2Arc ar = s_arc[ai];
+          col = ar.col; w = ar.w;
+          tidl = a.in_tid[in0 + ai];
+          ol = a.in_olabel[in0 + ai];
+        }
+        const int tf = t + lane;                         // every entry emits: entry k of the batch is frame t + k
+        if (mine) {
+          ac = -1 * (a.acoustic_scale * llu[(int64_t)col * tpad + tf]);
+          a.ali[f0 + tf] = tidl;
+        }
+        const int cnt = base >= 63 ? 64 : base + 1;
+        const int tl = tf + (mine ? 1 : 0);              // certificate operands of this entry's END node (layer tl)
+        double lb = 0.0; int small = 0;
+        if (mine) {
+          lb = lbest[tl] + beam;
+          small = lcnt[tl] <= a.min_active && (tl == 0 || lcnt[tl - 1] <= a.min_active);
+        }
+        const double cost_in = cost;
+        double ca = 0.0;
+        if (!serial) {
+          const unsigned aw = __float_as_uint(w) & 0x7fffffffu, aa = __float_as_uint(ac) & 0x7fffffffu;
+          const unsigned m1 = k2_wave_minu(min(aw - 1u, aa - 1u));          // zero -> all ones: not an addend
+          emin1 = min(emin1, m1);
+          sumabs += k2_wave_sumd((double)__uint_as_float(aw) + (double)__uint_as_float(aa));
+          const unsigned eb = (emin1 + 1u) >> 23;                           // biased exponent of the smallest non-zero |addend|; 0: none
+          const double bound = __hiloint2double((int)((eb + 925u) << 20), 0);   // 2^52 q = 2^(eb - 127 + 29)
+          serial = !((emin1 == 0xffffffffu || eb >= 27u) && sumabs <= bound);
+        }
+        if (!serial) {
+          ++nscan;
+          double d = (double)w + (double)ac;
+          d = lane == 0 ? cost_in + d : d;
+          ca = k2_wave_scand(d);
+          cost = k2_readlane_d(ca, cnt - 1);
+        } else {
+          ++nserial;
+          for (int k = 0; k < cnt; ++k) {
+            const float wk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), k));
+            const float ack = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ac), k));
+            const double ncost = (cost + wk) + ack;                          // faster-decoder.h:125
+            ca = lane == k ? ncost : ca;
+            cost = ncost;
+          }
+        }
+        const double cb = k2_dpp_d<0x138, 0xf>(cost_in, ca);                 // wave_shr:1 -- the cost BEFORE this lane's entry
+        const float tot_cost = (float)(ca - cb);                               // faster-decoder.cc:393
+        const float ac_cost = tot_cost - w;
+        if (__ballot(mine && !(ca < lb) && !small) != 0ull) ok = false;        // beam certificate of every entry's end node
+        t += cnt;
+        {
+          const unsigned long long wm = __ballot(mine && ol != 0);             // word labels, path order
+          if (mine && ol != 0) { const int pos = nw + __popcll(wm & ((1ull << lane) - 1ull)); if (pos < wcap) words[pos] = ol; }
+          nw += __popcll(wm);
+        }
+        for (int k = 0; k < cnt; ++k) {                                        // LatticeWeight Times, path order
+          const f32x2 r = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), k)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ac_cost), k))};
+          vv = r + vv;
+        }
+      }
+      v1 = vv[0]; v2 = vv[1];
+    }
+  }
+  if (!bad && !replayed) {
     ok = (0.0 < lbest[0] + beam) || lcnt[0] <= a.min_active;
     for (int base = n - 1; base >= 0; base -= 64) {
+      ++nserial;
       const int idx = base - lane;                     // lane k handles path[base-k] (forward order)
       int ai = 0, col = -1, tidl = 0, ol = 0; float w = 0.0f, ac = 0.0f;
       if (idx >= 0) {
@@ -989,7 +1182,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
       }
     }
   }
-  if (a.prof && tid == 0) { a.prof[u * 8 + 4] = clock64(); a.prof[u * 8 + 5] = T; a.prof[u * 8 + 6] = S; a.prof[u * 8 + 7] = FAST; }
+  if (a.prof && tid == 0) { a.prof[u * 8 + 4] = clock64(); a.prof[u * 8 + 5] = T; a.prof[u * 8 + 6] = S; a.prof[u * 8 + 7] = (long long)FAST | ((long long)nscan << 8) | ((long long)nserial << 32); }   // word 7: FAST | replay batches scanned << 8 | serial << 32
   int stt = 0;
   if (lane == 0) {
     if (bad || nw > wcap) {

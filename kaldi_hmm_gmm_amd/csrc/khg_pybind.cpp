@@ -79,7 +79,7 @@ struct KContext {
   static int opt_id(const py::object& o) {
     if (py::isinstance<py::int_>(o)) return o.cast<int>();
     static const char* names[KHG_OPT_COUNT] = {"k1_form", "k1_order", "k1_nf", "k1p_ts", "k1_interleave", "k1_dbg", "k2_inorder", "k2_ks", "k2_serial",
-                                               "k2_prof", "k3_bucket", "k3_form", "k3_phase_b", "k3_ny", "debug", "k3_phase_a", "k2_split", "k2s_hub", "lat_ops_lds", "k1_launch", "k1_pgrid", "k1_prof", "k2_ladder", "k3_planes"};
+                                               "k2_prof", "k3_bucket", "k3_form", "k3_phase_b", "k3_ny", "debug", "k3_phase_a", "k2_split", "k2s_hub", "lat_ops_lds", "k1_launch", "k1_pgrid", "k1_prof", "k2_ladder", "k3_planes", "k2_tail"};
     const std::string n = o.cast<std::string>();
     for (int i = 0; i < KHG_OPT_COUNT; ++i) if (n == names[i]) return i;
     if (n == "scratch_bytes") return KHG_INFO_SCRATCH_BYTES;       // read-only
@@ -683,6 +683,12 @@ struct KUtts {
     Check(khg_utts_k2_ladder(ctx_o.cast<KContext*>()->h, h, &o));
     return o != 0;
   }
+  // khg_utts_k2_tail: (scanned, serial) replay batches per utterance of the last align() under option k2_prof
+  py::array k2_tail() {
+    Arr<int32_t> o({(py::ssize_t)n_utt, (py::ssize_t)2});
+    Check(khg_utts_k2_tail(h, o.mutable_data(), 2 * (int64_t)n_utt));
+    return o;
+  }
   py::object pdf_first_frames() {
     Arr<int64_t> off({(py::ssize_t)n_utt + 1});
     Check(khg_utts_num_pdfs(h, off.mutable_data()));
@@ -1136,7 +1142,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def_property_readonly("h", [](KUtts& x) { return reinterpret_cast<uintptr_t>(x.h); })
       .def_readonly("ctx", &KUtts::ctx_obj).def_readonly("frame_off", &KUtts::frame_off).def_readonly("n_utt", &KUtts::n_utt)
       .def_readonly("dim", &KUtts::dim)
-      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("k2_ladder", &KUtts::k2_ladder, py::arg("ctx")).def("k3_planes", &KUtts::k3_planes).def("pdf_first_frames", &KUtts::pdf_first_frames)
+      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("k2_ladder", &KUtts::k2_ladder, py::arg("ctx")).def("k3_planes", &KUtts::k3_planes).def("k2_tail", &KUtts::k2_tail).def("pdf_first_frames", &KUtts::pdf_first_frames)
       .def("pdf_last_frames", &KUtts::pdf_last_frames)
       .def("loglikes", &KUtts::loglikes, py::arg("model"), py::arg("reachable_only") = false, py::arg("band") = false)
       .def("loglikes_layout", &KUtts::loglikes_layout).def("download_loglikes", &KUtts::download_loglikes)
