@@ -720,6 +720,73 @@ int khg_lattices_wer(khg_ctx *ctx, const khg_lattices *l, int32_t n_utt, const i
 int khg_edit_distance(int32_t n_pairs, const int32_t *ref_h, const int64_t *ref_off_h, const int32_t *hyp_h, const int64_t *hyp_off_h,
                       int32_t *counts_h);
 
+/* ---- K2B: minimum Bayes risk decoding and word confidences of resident lattices (lattice-mbr-decode, the confidence column of
+ *      lattice-to-ctm-conf: Kaldi's MinimumBayesRisk) ------------------------------------------------------------- */
+#define KHG_LAT_NOT_CONVERGED 2048 /* khg_lattices_mbr: max_iter updates were made and the next one would still change the hypothesis;
+                                      set together with KHG_LAT_SUCCEEDED, the outputs are those of the last accumulation */
+/* Per utterance: the hypothesis of least expected word error under one (graph_scale, acoustic_scale) pair (as for
+ * khg_lattices_posteriors), a confidence per word, and the confusion bins ("sausages").  All arithmetic is float64.
+ * decode_mbr == 0: one accumulation on the initial hypothesis (confidences only).  max_iter >= 0 bounds the updates.
+ * init_h / init_off_h[n_utt + 1] / init_given_h[n_utt]: the initial hypothesis of utterance u is init_h[init_off_h[u] ..
+ * init_off_h[u + 1]) (words > 0; empty is legal) when init_off_h is not NULL and init_given_h is NULL or init_given_h[u] != 0;
+ * otherwise it is the words of khg_lattices_best_path at the same pair (none when that finds no path).
+ * THE RULE.
+ * Weights.  alpha, tot and the arc log-likelihood w_a are khg_lattices_posteriors' (DESIGN.md 7g).  For every arc a: s -> d with
+ *   alpha[s] finite (and alpha[d], which follows when the costs are finite) p_a = exp((alpha[s] + w_a) - alpha[d]); otherwise p_a = 0.
+ *   For every final state f of the last frame with alpha[f] finite pf_f = exp((alpha[f] + fin_f) - tot); otherwise 0.  A virtual end
+ *   state N (the real states are 0 .. N - 1) has one in-arc per state f of the last frame, ascending, with word 0 and weight pf_f.  An
+ *   arc of weight 0 is skipped everywhere below.  The weights are the ONLY place where exp enters; everything after them is +, *, <
+ *   and <= on doubles in the written order, without contraction.
+ * Hypothesis.  The words h_1 .. h_W are normalised to r(1 .. Q), Q = 2 W + 1: r(q) = 0 (epsilon) for odd q, r(2 i) = h_i.
+ *   sub(w, x) = 0 if w == x else 1;  del(w) = 0 if w == 0 else 1 + 1e-5 (Kaldi's delta);  ins(x) = 0 if x == 0 else 1.
+ * Forward.  AD[n][0 .. Q], the states in ascending order.  AD[start][0] = 0, AD[start][q] = AD[start][q-1] + ins(r(q)); every other
+ *   row starts at 0.  For each in-arc of n in the in-arc index's order (ascending arc number), with source s, word w and weight p:
+ *     arc[0] = AD[s][0] + del(w);  for q >= 1:  a1 = AD[s][q-1] + sub(w, r(q)),  a2 = AD[s][q] + del(w),  a3 = arc[q-1] + ins(r(q));
+ *     b[q] = 1 if a1 <= a2 and a1 <= a3;  b[q] = 2 if a2 < a1 and a2 <= a3;  otherwise b[q] = 3;  arc[q] is the chosen value;
+ *     then AD[n][q] = fl(AD[n][q] + fl(p * arc[q])) for every q.
+ *   The virtual state N comes last.  bayes_risk = AD[N][Q].
+ * Backward.  BD is 0 except BD[N][Q] = 1; gamma[q][word], q = 1 .. Q, is 0.  The states go N down to 0 without the start; a state's
+ *   in-arcs in ascending order; the arc row and b are recomputed from AD.  With ba[Q+1] = 0, for q = Q .. 1:
+ *     ba[q] = (b[q+1] == 3 ? ba[q+1] : 0) + p * BD[n][q];
+ *     b[q] == 1: BD[s][q-1] += ba[q], gamma[q][w] += ba[q];   b[q] == 2: BD[s][q] += ba[q];   b[q] == 3: gamma[q][0] += ba[q].
+ *   Finally ba[0] = (b[1] == 3 ? ba[1] : 0) + p * BD[n][0] and BD[s][0] += ba[0].  A cell BD[s][q] can receive two additions from
+ *   one arc: first the move-1 term from q + 1, then the move-2 term from q.  After all states the start row is drained:
+ *   for q = Q .. 1, ba[q] = ba[q+1] + BD[start][q] and gamma[q][0] += ba[q].
+ * Update.  pick(q) is the word of largest gamma[q][.], the lowest word id among equals (epsilon is 0); h' is the picks that are not 0,
+ *   in order.  If decode_mbr == 0 or h' == h: stop.  If max_iter updates have been made: stop with KHG_LAT_NOT_CONVERGED.  If h' is
+ *   longer than the cap: KHG_LAT_WORDS.  Otherwise h = h' and the rule repeats from Hypothesis.  The outputs always belong to the
+ *   last accumulation.  The cap on W is max_words if > 0, else max(the initial hypothesis's length, the greatest number of words on
+ *   any path from the start to a final state of the last frame: an int32 pass over the states); at most 2047 either way.
+ * Statuses.  KHG_LAT_NO_PATH and KHG_LAT_EPS_LOOP exactly as khg_lattices_posteriors gives them; then KHG_LAT_WORDS: the initial
+ *   hypothesis (or a later one) is longer than the cap, or the cap is above 2047; then KHG_LAT_SCRATCH: the utterance's table --
+ *   8 * (2 * (states + 1) + len(vocab)) * (2 * cap + 2) bytes -- exceeds scratch_bytes (0: 1 GiB; the tables of one launch stay within
+ *   it, as for khg_lattices_oracle); otherwise KHG_LAT_SUCCEEDED, with KHG_LAT_NOT_CONVERGED beside it where that applies.  An
+ *   utterance without KHG_LAT_SUCCEEDED has no words and no table, and bayes_risk = +inf.
+ * The result is a handle resident on the device (free it with khg_mbr_destroy).  khg_mbr_sizes: words_off_h / vocab_off_h /
+ * gamma_off_h [n_utt + 1], any may be NULL -- utterance u owns words (and confidences) words_off[u] .. words_off[u + 1], vocabulary
+ * entries vocab_off[u] .. and table cells gamma_off[u] .. .  khg_mbr_download (any output may be NULL): status_h / iters_h (the
+ * number of updates made) / bayes_risk_h [n_utt]; words_h and conf_h (conf[i] = gamma[2 i][h_i]); vocab_h: the utterance's distinct
+ * olabels ascending with 0 first; gamma_h: per utterance gamma[Q][len(vocab)], dense, row q - 1 for position q; arc_cond_h [arcs, the
+ * lattice handle's arc order] and final_cond_h [states]: the weights p_a and pf_f that were used (0 for a refused utterance).
+ * Handing the weights back is part of the interface: the rule takes an arg-min at every (arc, position) and an arg-max at every
+ * position, expected distances cluster at integers, and one ulp in a weight can move a tie; so the device form and the host form
+ * (Lattice::Mbr) agree BIT FOR BIT given the same weights, and only the weights are compared under a tolerance.
+ * Nothing depends on the batch, on scratch_bytes or on timing: no atomics.
+ * Cost: the vocabulary of an utterance is found by one wave with a scan that is quadratic in the utterance's arcs that carry a word
+ * (1.4 ms for 2000 utterances of 167 arcs); on lattices of about 10^4 arcs that step dominates the call.
+ * KHG_E_ARG before any launch: scales not finite or negative; max_iter < 0; max_words outside 0 .. 2047; scratch_bytes < 0; n_utt
+ * not the handle's utterance count; init_off_h not starting at 0 or decreasing; an initial word <= 0 (naming the utterance).  The
+ * first call on a handle builds its in-arc index (as khg_lattices_posteriors does) and keeps it.  Synchronous; the input is untouched. */
+typedef struct khg_mbr khg_mbr;
+int khg_lattices_mbr(khg_ctx *ctx, const khg_lattices *l, float graph_scale, float acoustic_scale, int32_t decode_mbr,
+                     int32_t max_iter, int32_t n_utt, const int32_t *init_h, const int64_t *init_off_h, const int32_t *init_given_h,
+                     int32_t max_words, int64_t scratch_bytes, khg_mbr **out);
+int khg_mbr_sizes(const khg_mbr *m, int64_t *words_off_h, int64_t *vocab_off_h, int64_t *gamma_off_h);
+int khg_mbr_download(khg_ctx *ctx, const khg_mbr *m, int32_t *status_h, int32_t *iters_h, double *bayes_risk_h, int32_t *words_h,
+                     double *conf_h, int32_t *vocab_h, double *gamma_h, double *arc_cond_h, double *final_cond_h);
+int khg_mbr_device_bytes(const khg_mbr *m, int64_t *bytes);
+int khg_mbr_destroy(khg_mbr *m);
+
 /* ---- K2M: MPE / sMBR posteriors of resident lattices (lattice-to-mpe-post, lattice-to-smbr-post) ------------------- */
 #define KHG_MPE_MPFE 0           /* an arc is correct when its phone is the reference's at that frame */
 #define KHG_MPE_SMBR 1           /* ... when its pdf is (needs tid2pdf_h) */

@@ -19,6 +19,7 @@ from .align import DeviceLm  # noqa: F401
 from .lm import NgramLm, estimate_ngram_lm  # noqa: F401
 from .score import (compute_wer, edit_distance_counts, lattice_add_penalty, lattice_add_penalty_batch, lattice_oracle,  # noqa: F401
                     lattice_oracle_batch, score_lattices)
+from .score import lattice_mbr_decode, lattice_mbr_decode_batch, mbr_utterances  # noqa: F401
 from .align import get_raw_lattice_faster_batch, get_raw_lattice_faster_device_batch  # noqa: F401
 from .context_dep import (ContextDependency, ContextDependencyInterface, monophone_context_dependency,  # noqa: F401
                           monophone_context_dependency_shared)

@@ -229,6 +229,12 @@ SIGNATURES = {
     "khg_lattices_oracle": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i64p, C.c_int64, c_i32p, c_i32p, c_i64p, C.c_int64, c_i32p, c_i32p]),
     "khg_lattices_wer": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i64p, C.c_int32, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p]),
     "khg_edit_distance": (C.c_int, [C.c_int32, c_i32p, c_i64p, c_i32p, c_i64p, c_i32p]),
+    "khg_lattices_mbr": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i64p, c_i32p, C.c_int32, C.c_int64,
+                                   C.POINTER(vp)]),
+    "khg_mbr_sizes": (C.c_int, [vp, c_i64p, c_i64p, c_i64p]),
+    "khg_mbr_download": (C.c_int, [vp, vp, c_i32p, c_i32p, c_f64p, c_i32p, c_f64p, c_i32p, c_f64p, c_f64p, c_f64p]),
+    "khg_mbr_device_bytes": (C.c_int, [vp, c_i64p]),
+    "khg_mbr_destroy": (C.c_int, [vp]),
     "khg_lattices_mpe_posteriors": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p, vp, C.c_int32, C.c_int32,
                                               C.c_float, C.c_float, c_i32p, c_f64p, c_f64p, C.POINTER(vp)]),
     "khg_posteriors_sizes": (C.c_int, [vp, c_i64p, c_i64p]),

@@ -678,6 +678,162 @@ LatticeOracle Lattice::Oracle(const std::vector<int32_t>& ref) const {
   return out;
 }
 
+LatticeMbr Lattice::Mbr(float graph_scale, float acoustic_scale, bool decode_mbr, int max_iter, const std::vector<int32_t>* init, int max_words,
+                        const std::vector<double>* arc_cond, const std::vector<double>* final_cond) const {
+  KHG_REQUIRE(max_iter >= 0, "Lattice::Mbr: max_iter must be >= 0");
+  KHG_REQUIRE(max_words >= 0 && max_words <= 2047, "Lattice::Mbr: max_words must lie in 0 .. 2047");
+  KHG_REQUIRE((arc_cond == nullptr) == (final_cond == nullptr), "Lattice::Mbr: arc_cond and final_cond come together");
+  if (init) for (int32_t w : *init) KHG_REQUIRE(w > 0, "Lattice::Mbr: an initial word is not > 0");
+  const double INF = std::numeric_limits<double>::infinity(), NINF = -INF;
+  const float FINF = std::numeric_limits<float>::infinity();
+  const double gs = graph_scale, as = acoustic_scale;
+  LatticeMbr out;
+  out.bayes_risk = INF;
+  const LatticePosteriors fb = ForwardBackward(graph_scale, acoustic_scale);      // (refuses bad scales)
+  out.status = fb.status;
+  const int N = NumStates();
+  const int64_t A = NumArcs();
+  out.arc_cond.assign((size_t)A, 0.0);
+  out.final_cond.assign((size_t)N, 0.0);
+  if (!(fb.status & KHG_LAT_SUCCEEDED)) return out;
+  std::vector<int32_t> src((size_t)A);
+  std::vector<std::vector<int32_t>> in((size_t)N);      // ascending arc number
+  for (int s = 0; s < N; ++s)
+    for (int a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) { src[(size_t)a] = s; in[(size_t)nextstate[(size_t)a]].push_back(a); }
+  const int T = frame[(size_t)N - 1];
+  int last_lo = N - 1;
+  while (last_lo > 0 && frame[(size_t)last_lo - 1] == T) --last_lo;
+  if (arc_cond) {
+    KHG_REQUIRE((int64_t)arc_cond->size() == A && (int)final_cond->size() == N, "Lattice::Mbr: one arc_cond per arc, one final_cond per state");
+    out.arc_cond = *arc_cond; out.final_cond = *final_cond;
+  } else {
+    for (int64_t a = 0; a < A; ++a) {
+      const double al = fb.alpha[(size_t)src[(size_t)a]], ad = fb.alpha[(size_t)nextstate[(size_t)a]];
+      if (al == NINF || ad == NINF) continue;
+      const double g = gs * (double)graph_cost[(size_t)a];
+      const double c = ilabel[(size_t)a] != 0 ? as * (double)acoustic_cost[(size_t)a] : 0.0;
+      out.arc_cond[(size_t)a] = std::exp((al + -(g + c)) - ad);
+    }
+    for (int s = last_lo; s < N; ++s)
+      if (final_cost[(size_t)s] != FINF && fb.alpha[(size_t)s] != NINF)
+        out.final_cond[(size_t)s] = std::exp((fb.alpha[(size_t)s] + -(gs * (double)final_cost[(size_t)s])) - fb.tot_like);
+  }
+  // the vocabulary, every arc's index into it, the longest path's words
+  out.vocab.assign(1, 0);
+  for (int32_t w : olabel) if (w != 0) out.vocab.push_back(w);
+  std::sort(out.vocab.begin() + 1, out.vocab.end());
+  out.vocab.erase(std::unique(out.vocab.begin() + 1, out.vocab.end()), out.vocab.end());
+  const int V = (int)out.vocab.size();
+  auto index_of = [&](int32_t w) { const auto it = std::lower_bound(out.vocab.begin() + 1, out.vocab.end(), w); return it != out.vocab.end() && *it == w ? (int)(it - out.vocab.begin()) : (w == 0 ? 0 : -1); };
+  int32_t longest = 0;
+  {
+    std::vector<int32_t> L((size_t)N, -1);
+    L[(size_t)start] = 0;
+    for (int64_t a = 0; a < A; ++a) {
+      const int s = src[(size_t)a], d = nextstate[(size_t)a];
+      if (L[(size_t)s] >= 0) L[(size_t)d] = std::max(L[(size_t)d], L[(size_t)s] + (olabel[(size_t)a] != 0 ? 1 : 0));
+    }
+    for (int s = last_lo; s < N; ++s) if (final_cost[(size_t)s] != FINF) longest = std::max(longest, L[(size_t)s]);
+  }
+  std::vector<int32_t> h;
+  if (init) h = *init;
+  else { const LatticeBestPath b = BestPath(graph_scale, acoustic_scale); if (b.status & KHG_LAT_SUCCEEDED) h = b.words; }
+  const int64_t cap = max_words > 0 ? max_words : std::max<int64_t>((int64_t)h.size(), longest);
+  out.cap = (int32_t)std::min<int64_t>(cap, INT32_MAX);
+  if ((int64_t)h.size() > cap || cap > 2047) { out.status = KHG_LAT_WORDS; return out; }
+  const double DEL = 1.0 + 1e-5;
+  // in-arc j of state n (n == N: the virtual end state): source, word, weight
+  auto degree = [&](int n) { return n < N ? (int)in[(size_t)n].size() : N - last_lo; };
+  auto in_arc = [&](int n, int j, int* s, int32_t* w, double* p) {
+    if (n < N) { const int a = in[(size_t)n][(size_t)j]; *s = src[(size_t)a]; *w = olabel[(size_t)a]; *p = out.arc_cond[(size_t)a]; }
+    else { *s = last_lo + j; *w = 0; *p = out.final_cond[(size_t)(last_lo + j)]; }
+  };
+  std::vector<double> AD, BD, G, arc, ba;
+  std::vector<unsigned char> b;
+  for (;;) {
+    const int W = (int)h.size(), Q = 2 * W + 1, C = Q + 1;
+    auto r = [&](int q) { return (q & 1) ? 0 : h[(size_t)(q / 2 - 1)]; };
+    auto row = [&](const double* ADs, int32_t w) {      // arc[0 .. Q] and b[1 .. Q]
+      const double delw = w != 0 ? DEL : 0.0;
+      arc[0] = ADs[0] + delw;
+      for (int q = 1; q <= Q; ++q) {
+        const int32_t rq = r(q);
+        const double a1 = ADs[q - 1] + (w == rq ? 0.0 : 1.0), a2 = ADs[q] + delw, a3 = arc[(size_t)q - 1] + (rq != 0 ? 1.0 : 0.0);
+        if (a1 <= a2 && a1 <= a3) { b[(size_t)q] = 1; arc[(size_t)q] = a1; }
+        else if (a2 < a1 && a2 <= a3) { b[(size_t)q] = 2; arc[(size_t)q] = a2; }
+        else { b[(size_t)q] = 3; arc[(size_t)q] = a3; }
+      }
+    };
+    AD.assign((size_t)(N + 1) * C, 0.0); BD.assign((size_t)(N + 1) * C, 0.0); G.assign((size_t)Q * V, 0.0);
+    arc.assign((size_t)C, 0.0); ba.assign((size_t)C + 1, 0.0); b.assign((size_t)C + 1, 0);
+    for (int q = 1; q <= Q; ++q) AD[(size_t)start * C + q] = AD[(size_t)start * C + q - 1] + (r(q) != 0 ? 1.0 : 0.0);
+    for (int n = 0; n <= N; ++n) {
+      if (n == start) continue;
+      for (int j = 0; j < degree(n); ++j) {
+        int s; int32_t w; double p;
+        in_arc(n, j, &s, &w, &p);
+        if (p == 0.0) continue;
+        row(&AD[(size_t)s * C], w);
+        for (int q = 0; q <= Q; ++q) { const double pv = p * arc[(size_t)q]; AD[(size_t)n * C + q] = AD[(size_t)n * C + q] + pv; }
+      }
+    }
+    const double risk = AD[(size_t)N * C + Q];
+    out.risks.push_back(risk);
+    BD[(size_t)N * C + Q] = 1.0;
+    for (int n = N; n >= 0; --n) {
+      if (n == start) continue;
+      for (int j = 0; j < degree(n); ++j) {
+        int s; int32_t w; double p;
+        in_arc(n, j, &s, &w, &p);
+        if (p == 0.0) continue;
+        row(&AD[(size_t)s * C], w);
+        const int wi = index_of(w);
+        b[(size_t)Q + 1] = 0; ba[(size_t)Q + 1] = 0.0;
+        for (int q = Q; q >= 1; --q) {
+          const double t = p * BD[(size_t)n * C + q];
+          const double x = (b[(size_t)q + 1] == 3 ? ba[(size_t)q + 1] : 0.0) + t;
+          ba[(size_t)q] = x;
+          if (b[(size_t)q] == 1) { BD[(size_t)s * C + q - 1] = BD[(size_t)s * C + q - 1] + x; G[(size_t)(q - 1) * V + wi] = G[(size_t)(q - 1) * V + wi] + x; }
+          else if (b[(size_t)q] == 2) BD[(size_t)s * C + q] = BD[(size_t)s * C + q] + x;
+          else G[(size_t)(q - 1) * V] = G[(size_t)(q - 1) * V] + x;
+        }
+        const double t0 = p * BD[(size_t)n * C];
+        const double x0 = (b[1] == 3 ? ba[1] : 0.0) + t0;
+        BD[(size_t)s * C] = BD[(size_t)s * C] + x0;
+      }
+    }
+    {
+      double x = 0.0;
+      for (int q = Q; q >= 1; --q) { x = x + BD[(size_t)start * C + q]; G[(size_t)(q - 1) * V] = G[(size_t)(q - 1) * V] + x; }
+    }
+    bool stop = !decode_mbr;
+    std::vector<int32_t> hn;
+    if (!stop) {
+      for (int q = 1; q <= Q; ++q) {
+        int bi = 0;
+        for (int x = 1; x < V; ++x) if (G[(size_t)(q - 1) * V + bi] < G[(size_t)(q - 1) * V + x]) bi = x;
+        if (out.vocab[(size_t)bi] != 0) hn.push_back(out.vocab[(size_t)bi]);
+      }
+      if (hn == h) stop = true;
+      else if (out.iters == max_iter) { out.status |= KHG_LAT_NOT_CONVERGED; stop = true; }
+      else if ((int64_t)hn.size() > cap) {
+        out.status = KHG_LAT_WORDS;
+        return out;
+      }
+    }
+    if (stop) {
+      out.bayes_risk = risk;
+      out.words = h;
+      out.gamma = G;
+      out.conf.assign((size_t)W, 0.0);
+      for (int i = 0; i < W; ++i) { const int wi = index_of(h[(size_t)i]); if (wi >= 0) out.conf[(size_t)i] = G[(size_t)(2 * i + 1) * V + wi]; }
+      return out;
+    }
+    h.swap(hn);
+    ++out.iters;
+  }
+}
+
 std::shared_ptr<Lattice> Lattice::Prune(float beam, float gs, float as, int* status) const {
   KHG_REQUIRE(beam >= 0.0f, "Lattice::Prune: beam must be >= 0");
   auto out = std::make_shared<Lattice>();

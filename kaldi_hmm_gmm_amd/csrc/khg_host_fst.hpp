@@ -157,6 +157,17 @@ struct LatticeOracle {
   std::vector<int32_t> words, arcs, ali;
 };
 
+// Lattice::Mbr (what khg_lattices_mbr gives for one lattice): KHG_LAT_* status, the number of updates made, the Bayes
+// risk (+inf without SUCCEEDED), the hypothesis, a confidence per word, the distinct olabels (0 first) and gamma [Q][vocab.size()]
+// row-major, the weights used (arc_cond per arc, final_cond per state), the cap on the words, and the risk of every accumulation
+struct LatticeMbr {
+  int status = 0, iters = 0;
+  double bayes_risk = 0.0;
+  std::vector<int32_t> words, vocab;
+  std::vector<double> conf, gamma, arc_cond, final_cond, risks;
+  int32_t cap = 0;
+};
+
 // The fst::VectorFst<LatticeArc> LatticeSimpleDecoder::GetRawLattice builds (csrc/lattice-simple-decoder.cc:654-735), as the flat arrays
 // khg_lattices_download hands back: a state per surviving token, numbered by frame, then by graph state (:684-690); state s owns arcs
 // arc_begin[s] .. arc_begin[s + 1], one per surviving forward link in the order of the graph's arcs in its state (:700-722); the last
@@ -226,6 +237,12 @@ class Lattice {
   // lattice-oracle: the path with the fewest word errors against `ref` (words > 0), sequentially, cell by cell, by the
   // rule written at khg_lattices_oracle in include/khg_hip.h
   LatticeOracle Oracle(const std::vector<int32_t>& ref) const;
+  // lattice-mbr-decode and the confidences of lattice-to-ctm-conf: the rule written at khg_lattices_mbr in
+  // include/khg_hip.h, serially.  init: the initial hypothesis (nullptr: BestPath's words at the same pair).  arc_cond / final_cond
+  // (one per arc / per state; both or neither) replace the weights the host would compute from ForwardBackward's alpha: given the
+  // device's, every other output equals the device's bit for bit.
+  LatticeMbr Mbr(float graph_scale, float acoustic_scale, bool decode_mbr = true, int max_iter = 32, const std::vector<int32_t>* init = nullptr,
+                 int max_words = 0, const std::vector<double>* arc_cond = nullptr, const std::vector<double>* final_cond = nullptr) const;
   // Kaldi's text form of a lattice: "src dst ilabel olabel graph,acoustic" per arc, "state graph,acoustic" per final state
   std::string ToText() const;
 

@@ -24,6 +24,7 @@
 #include "khg_k2_lattice_mpe.hip.inc"
 #include "khg_k2_lattice_lm.hip.inc"
 #include "khg_k2_lattice_score.hip.inc"
+#include "khg_k2_lattice_mbr.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // The raw lattices of one batch (khg_decode_lattice_simple_raw, khg_decode_lattice_faster_raw): per chunk of scratch slices one
@@ -2259,5 +2260,263 @@ extern "C" int khg_edit_distance(int32_t n_pairs, const int32_t* ref_h, const in
     }
     counts_h[4 * (size_t)i] = ins + del + sub; counts_h[4 * (size_t)i + 1] = ins; counts_h[4 * (size_t)i + 2] = del; counts_h[4 * (size_t)i + 3] = sub;
   }
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2B: minimum Bayes risk decoding and word confidences (khg_k2_lattice_mbr.hip.inc)
+struct khg_mbr {
+  int U = 0;
+  khg_ctx* ctx = nullptr;
+  int64_t bytes = 0;
+  std::vector<int64_t> state_off, arc_off;              // the lattice handle's
+  std::vector<int32_t> status, iters, nwords, nvocab;   // [U]
+  std::vector<double> risk;                             // [U]
+  std::vector<int64_t> cap_off, gout_off;               // [U + 1]: the slots of an utterance's words / conf, and of its table
+  double *arc_cond_d = nullptr, *final_cond_d = nullptr, *conf_d = nullptr, *gamma_d = nullptr;      // [arcs], [states], [cap_off[U]], [gout_off[U]]
+  int32_t *vocab_d = nullptr, *hyp_d = nullptr;         // [arcs + U] (utterance u's slot at arc_off[u] + u), [2 * cap_off[U]]
+};
+
+namespace {
+struct MbrFree { void operator()(khg_mbr* m) const { (void)khg_mbr_destroy(m); } };
+using MbrPtr = std::unique_ptr<khg_mbr, MbrFree>;
+template <class T>
+int mbr_alloc(khg_mbr* m, int64_t count, T** out) {
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(out), (size_t)std::max<int64_t>(count * (int64_t)sizeof(T), 16)));
+  m->bytes += count * (int64_t)sizeof(T);
+  return KHG_OK;
+}
+}  // namespace
+
+extern "C" int khg_mbr_destroy(khg_mbr* m) {
+  if (!m) return KHG_OK;
+  void* blocks[6] = {m->arc_cond_d, m->final_cond_d, m->conf_d, m->gamma_d, m->vocab_d, m->hyp_d};
+  for (void* q : blocks) if (q) (void)hipFree(q);
+  delete m;
+  return KHG_OK;
+}
+extern "C" int khg_mbr_device_bytes(const khg_mbr* m, int64_t* bytes) {
+  if (!m || !bytes) return khg_set_error(KHG_E_ARG, "khg_mbr_device_bytes: bad arguments");
+  *bytes = m->bytes;
+  return KHG_OK;
+}
+extern "C" int khg_mbr_sizes(const khg_mbr* m, int64_t* words_off_h, int64_t* vocab_off_h, int64_t* gamma_off_h) {
+  if (!m) return khg_set_error(KHG_E_ARG, "khg_mbr_sizes: bad arguments");
+  int64_t w = 0, v = 0, g = 0;
+  for (int u = 0; u <= m->U; ++u) {
+    if (words_off_h) words_off_h[u] = w;
+    if (vocab_off_h) vocab_off_h[u] = v;
+    if (gamma_off_h) gamma_off_h[u] = g;
+    if (u == m->U || !(m->status[(size_t)u] & KHG_LAT_SUCCEEDED)) continue;
+    const int64_t W = m->nwords[(size_t)u], V = m->nvocab[(size_t)u];
+    w += W; v += V; g += (2 * W + 1) * V;
+  }
+  return KHG_OK;
+}
+extern "C" int khg_mbr_download(khg_ctx* ctx, const khg_mbr* m, int32_t* status_h, int32_t* iters_h, double* bayes_risk_h, int32_t* words_h, double* conf_h,
+                                int32_t* vocab_h, double* gamma_h, double* arc_cond_h, double* final_cond_h) {
+  if (ctx_dead(ctx) || !m) return khg_set_error(KHG_E_ARG, "khg_mbr_download: bad arguments");
+  if (m->ctx != ctx) return khg_set_error(KHG_E_ARG, "khg_mbr_download: a handle of another context");
+  const size_t U = (size_t)m->U;
+  if (status_h) std::copy(m->status.begin(), m->status.end(), status_h);
+  if (iters_h) std::copy(m->iters.begin(), m->iters.end(), iters_h);
+  if (bayes_risk_h) std::copy(m->risk.begin(), m->risk.end(), bayes_risk_h);
+  if (U == 0) return KHG_OK;
+  const int64_t NA = m->arc_off[U], NS = m->state_off[U];
+  if (arc_cond_h && NA) HIPCHK(hipMemcpyAsync(arc_cond_h, m->arc_cond_d, 8 * (size_t)NA, hipMemcpyDeviceToHost, ctx->stream));
+  if (final_cond_h && NS) HIPCHK(hipMemcpyAsync(final_cond_h, m->final_cond_d, 8 * (size_t)NS, hipMemcpyDeviceToHost, ctx->stream));
+  // an utterance's results lie at the head of its slot: the slots come back in one copy per array and are packed here
+  const int64_t CT = m->cap_off[U], GT = m->gout_off[U];
+  std::vector<int32_t> hyp(words_h ? (size_t)(2 * CT) : 0), voc(vocab_h ? (size_t)(NA + (int64_t)U) : 0);
+  std::vector<double> conf(conf_h ? (size_t)CT : 0), gam(gamma_h ? (size_t)GT : 0);
+  if (!hyp.empty()) HIPCHK(hipMemcpyAsync(hyp.data(), m->hyp_d, 4 * hyp.size(), hipMemcpyDeviceToHost, ctx->stream));
+  if (!voc.empty()) HIPCHK(hipMemcpyAsync(voc.data(), m->vocab_d, 4 * voc.size(), hipMemcpyDeviceToHost, ctx->stream));
+  if (!conf.empty()) HIPCHK(hipMemcpyAsync(conf.data(), m->conf_d, 8 * conf.size(), hipMemcpyDeviceToHost, ctx->stream));
+  if (!gam.empty()) HIPCHK(hipMemcpyAsync(gam.data(), m->gamma_d, 8 * gam.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  int64_t w = 0, v = 0, g = 0;
+  for (size_t u = 0; u < U; ++u) {
+    if (!(m->status[u] & KHG_LAT_SUCCEEDED)) continue;
+    const int64_t W = m->nwords[u], V = m->nvocab[u], G = (2 * W + 1) * V;
+    if (words_h) std::copy_n(hyp.begin() + 2 * m->cap_off[u], W, words_h + w);
+    if (conf_h) std::copy_n(conf.begin() + m->cap_off[u], W, conf_h + w);
+    if (vocab_h) std::copy_n(voc.begin() + m->arc_off[u] + (int64_t)u, V, vocab_h + v);
+    if (gamma_h) std::copy_n(gam.begin() + m->gout_off[u], G, gamma_h + g);
+    w += W; v += V; g += G;
+  }
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_mbr(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, int32_t decode_mbr, int32_t max_iter,
+                                int32_t n_utt, const int32_t* init_h, const int64_t* init_off_h, const int32_t* init_given_h, int32_t max_words,
+                                int64_t scratch_bytes, khg_mbr** out) {
+  const std::string who = "khg_lattices_mbr: ";
+  if (out) *out = nullptr;
+  if (bad_scale(graph_scale) || bad_scale(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "graph_scale and acoustic_scale must be finite and >= 0");
+  if (max_iter < 0) return khg_set_error(KHG_E_ARG, who + "max_iter must be >= 0");
+  if (max_words < 0 || max_words > MB_MAX_WORDS) return khg_set_error(KHG_E_ARG, who + "max_words must lie in 0 .. " + std::to_string(MB_MAX_WORDS));
+  if (scratch_bytes < 0) return khg_set_error(KHG_E_ARG, who + "scratch_bytes must be >= 0");
+  if (!lc || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  if (n_utt != U) return khg_set_error(KHG_E_ARG, who + "the lattices hold " + std::to_string(U) + " utterances, the call names " + std::to_string(n_utt));
+  if (init_off_h) {
+    if (init_off_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "init_off_h must start at 0");
+    for (int u = 0; u < U; ++u)
+      if (init_off_h[u + 1] < init_off_h[u]) return khg_set_error(KHG_E_ARG, who + "init_off_h decreases at utterance " + std::to_string(u));
+    if (init_off_h[U] > 0 && !init_h) return khg_set_error(KHG_E_ARG, who + "init_h is NULL");
+    for (int u = 0; u < U; ++u)
+      for (int64_t i = init_off_h[u]; i < init_off_h[u + 1]; ++i)
+        if (init_h[i] <= 0) return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(u) + ": an initial word is not > 0");
+  }
+  if (ctx_dead(ctx)) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  if (l->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  MbrPtr res(new khg_mbr);
+  khg_mbr* m = res.get();
+  m->U = U; m->ctx = ctx; m->state_off = l->state_off; m->arc_off = l->arc_off;
+  m->status.assign((size_t)U, 0); m->iters.assign((size_t)U, 0); m->nwords.assign((size_t)U, 0); m->nvocab.assign((size_t)U, 0);
+  m->risk.assign((size_t)U, std::numeric_limits<double>::infinity());
+  m->cap_off.assign((size_t)U + 1, 0); m->gout_off.assign((size_t)U + 1, 0);
+  if (U == 0) { *out = res.release(); return KHG_OK; }
+  const int64_t budget = scratch_bytes ? scratch_bytes : kScoreScratch;
+  const int64_t NS = l->state_off[(size_t)U], NA = l->arc_off[(size_t)U];
+  // the initial hypotheses: the caller's, or the best path's words at the same pair
+  std::vector<std::vector<int32_t>> init((size_t)U);
+  bool need_best = false;
+  for (int u = 0; u < U; ++u) {
+    if (init_off_h && (!init_given_h || init_given_h[u])) init[(size_t)u].assign(init_h + init_off_h[u], init_h + init_off_h[u + 1]);
+    else need_best = true;
+  }
+  if (need_best) {
+    std::vector<int32_t> words((size_t)NS + 1), st((size_t)U);
+    std::vector<int64_t> woff((size_t)U + 1, 0);
+    int rc = khg_lattices_best_path(ctx, lc, 1, &graph_scale, &acoustic_scale, nullptr, words.data(), woff.data(), NS + 1, nullptr, st.data());
+    if (rc) return rc;
+    for (int u = 0; u < U; ++u)
+      if (!(init_off_h && (!init_given_h || init_given_h[u])) && (st[(size_t)u] & KHG_LAT_SUCCEEDED))
+        init[(size_t)u].assign(words.begin() + woff[(size_t)u], words.begin() + woff[(size_t)u + 1]);
+  }
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc) rc = lat_index(ctx, l);
+  if (rc) return rc;
+  if ((rc = mbr_alloc(m, NA, &m->arc_cond_d)) || (rc = mbr_alloc(m, NS, &m->final_cond_d)) || (rc = mbr_alloc(m, NA + U, &m->vocab_d))) return rc;
+  DevBlocks dv;
+  int32_t *nv_d, *mw_d, *widx_d;
+  if ((rc = dv.alloc(U, &nv_d)) || (rc = dv.alloc(U, &mw_d)) || (rc = dv.alloc(std::max<int64_t>(NA, 1), &widx_d))) return rc;
+  std::vector<int32_t> st((size_t)U), nv((size_t)U), mw((size_t)U);
+  {
+    // the weights: khg_lattices_posteriors' chunk steps around k2_lattice_mbr_weights (the run's own result handle is dropped)
+    PostRun r;
+    r.ctx = ctx; r.l = l; r.who = "khg_lattices_mbr";
+    r.gs = (double)graph_scale; r.as = (double)acoustic_scale;
+    new_posteriors(ctx, U, &r.res);
+    if ((rc = post_run_begin(r))) return rc;
+    for (size_t k = 0; k < l->chunks.size(); ++k) {
+      const LatChunk& c = l->chunks[k];
+      const int64_t cs0 = l->state_off[(size_t)c.u0], ca0 = l->arc_off[(size_t)c.u0];
+      PoArgs p;
+      std::memset(&p, 0, sizeof(p));
+      if ((rc = post_chunk_begin(r, k, 24, &p))) return rc;
+      p.arc_post = m->arc_cond_d + ca0;
+      {
+        KernelTimer kt(ctx, "k2_lattice_mbr_weights");
+        KHG_LAUNCH(ctx, k2_lattice_mbr_weights, dim3((unsigned)c.n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, p, m->final_cond_d + cs0);
+        HIPCHK(hipGetLastError());
+      }
+      int32_t *len_d, *first_d;
+      if ((rc = r.dv.alloc(std::max<int64_t>(c.ns, 1), &len_d)) || (rc = r.dv.alloc(std::max<int64_t>(c.na, 1), &first_d))) return rc;
+      const LatIndex ix = lat_index_arrays(l->idx_d[k], c);
+      KernelTimer kt(ctx, "k2_lattice_mbr_prepare");
+      KHG_LAUNCH(ctx, k2_lattice_mbr_prepare, dim3((unsigned)c.n), dim3(MB_NT), 0, ctx->stream, p.lo, ix.arc_src, len_d, first_d, m->vocab_d, widx_d + ca0, nv_d, mw_d);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(st.data(), r.status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(nv.data(), nv_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(mw.data(), mw_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = check_err_flag(ctx, "khg_lattices_mbr"))) return rc;      // synchronises: the run's scratch goes with `r`
+  }
+  // the caps, the slots, and the utterances that run, grouped into launches whose tables fit the budget together
+  std::vector<int32_t> cap((size_t)U, 0), w0((size_t)U, 0), list;
+  std::vector<int64_t> tab_off;
+  struct Launch { size_t chunk, first, n; int64_t cells; };
+  std::vector<Launch> launches;
+  int64_t max_cells = 1;
+  for (size_t k = 0; k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    Launch cur{k, list.size(), 0, 0};
+    for (int u = c.u0; u < c.u0 + c.n; ++u) {
+      const size_t su = (size_t)u;
+      m->status[su] = st[su]; m->nvocab[su] = nv[su];
+      m->cap_off[su + 1] = m->cap_off[su]; m->gout_off[su + 1] = m->gout_off[su];
+      if (!(st[su] & KHG_LAT_SUCCEEDED)) continue;
+      const int64_t W0 = (int64_t)init[su].size();
+      const int64_t cp = max_words > 0 ? max_words : std::max<int64_t>(W0, mw[su]);
+      if (W0 > cp || cp > MB_MAX_WORDS) { m->status[su] = KHG_LAT_WORDS; continue; }
+      const int64_t N = l->state_off[su + 1] - l->state_off[su], C = 2 * cp + 2, cells = (2 * (N + 1) + nv[su]) * C;
+      if (8 * cells > budget) { m->status[su] = KHG_LAT_SCRATCH; continue; }
+      cap[su] = (int32_t)cp; w0[su] = (int32_t)W0;
+      m->cap_off[su + 1] += cp; m->gout_off[su + 1] += (2 * cp + 1) * nv[su];
+      if (cur.n > 0 && 8 * (cur.cells + cells) > budget) { launches.push_back(cur); cur = Launch{k, list.size(), 0, 0}; }
+      list.push_back(u);
+      tab_off.push_back(cur.cells);
+      cur.cells += cells; ++cur.n;
+    }
+    if (cur.n > 0) launches.push_back(cur);
+  }
+  for (const Launch& L : launches) max_cells = std::max(max_cells, L.cells);
+  const int64_t CT = m->cap_off[(size_t)U], GT = m->gout_off[(size_t)U], nl = std::max<int64_t>((int64_t)list.size(), 1);
+  if ((rc = mbr_alloc(m, CT, &m->conf_d)) || (rc = mbr_alloc(m, GT, &m->gamma_d)) || (rc = mbr_alloc(m, 2 * CT, &m->hyp_d))) return rc;
+  if (!list.empty()) {
+    std::vector<int32_t> hyp((size_t)std::max<int64_t>(2 * CT, 1), 0);
+    for (int u : list) std::copy(init[(size_t)u].begin(), init[(size_t)u].end(), hyp.begin() + 2 * m->cap_off[(size_t)u]);
+    int32_t *cap_d, *w0_d, *status_d, *iters_d, *nw_d, *list_d;
+    int64_t *cap_off_d, *gout_off_d, *tab_off_d;
+    double *risk_d, *tab_d;
+    if ((rc = dv.alloc(U, &cap_d)) || (rc = dv.alloc(U, &w0_d)) || (rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &iters_d)) || (rc = dv.alloc(U, &nw_d)) ||
+        (rc = dv.alloc(nl, &list_d)) || (rc = dv.alloc(U + 1, &cap_off_d)) || (rc = dv.alloc(U + 1, &gout_off_d)) || (rc = dv.alloc(nl, &tab_off_d)) ||
+        (rc = dv.alloc(U, &risk_d)) || (rc = dv.alloc(max_cells, &tab_d)))
+      return rc;
+    HIPCHK(hipMemcpyAsync(m->hyp_d, hyp.data(), 4 * (size_t)(2 * CT), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(cap_d, cap.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(w0_d, w0.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(cap_off_d, m->cap_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(gout_off_d, m->gout_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(list_d, list.data(), 4 * list.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tab_off_d, tab_off.data(), 8 * tab_off.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(status_d, 0, 4 * (size_t)U, ctx->stream));
+    for (const Launch& L : launches) {
+      const LatChunk& c = l->chunks[L.chunk];
+      const int64_t cs0 = l->state_off[(size_t)c.u0], ca0 = l->arc_off[(size_t)c.u0];
+      MbArgs p;
+      std::memset(&p, 0, sizeof(p));
+      lat_chunk_args(l, c, &p.lo);
+      const LatIndex ix = lat_index_arrays(l->idx_d[L.chunk], c);
+      p.in_begin = ix.in_begin; p.in_arc = ix.in_arc; p.arc_src = ix.arc_src;
+      p.list = list_d + L.first; p.tab_off = tab_off_d + L.first; p.tab = tab_d;
+      p.arc_cond = m->arc_cond_d + ca0; p.final_cond = m->final_cond_d + cs0;
+      p.widx = widx_d + ca0; p.vocab = m->vocab_d; p.nvocab = nv_d;
+      p.cap = cap_d; p.w0 = w0_d; p.cap_off = cap_off_d; p.gout_off = gout_off_d;
+      p.hyp = m->hyp_d; p.conf = m->conf_d; p.gamma_out = m->gamma_d;
+      p.status = status_d; p.iters = iters_d; p.nwords = nw_d; p.risk = risk_d;
+      p.decode_mbr = decode_mbr ? 1 : 0; p.max_iter = max_iter;
+      KernelTimer kt(ctx, "k2_lattice_mbr");
+      KHG_LAUNCH(ctx, k2_lattice_mbr, dim3((unsigned)L.n), dim3(MB_NT), 0, ctx->stream, p);
+      HIPCHK(hipGetLastError());
+    }
+    std::vector<int32_t> st2((size_t)U), it((size_t)U), nw((size_t)U);
+    std::vector<double> rk((size_t)U);
+    HIPCHK(hipMemcpyAsync(st2.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(it.data(), iters_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(nw.data(), nw_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(rk.data(), risk_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = check_err_flag(ctx, "khg_lattices_mbr"))) return rc;      // synchronises: the scratch goes with `dv`
+    for (int u : list) {
+      const size_t su = (size_t)u;
+      m->status[su] = st2[su]; m->iters[su] = it[su];
+      if (st2[su] & KHG_LAT_SUCCEEDED) { m->nwords[su] = nw[su]; m->risk[su] = rk[su]; }
+    }
+  }
+  *out = res.release();
   return KHG_OK;
 }

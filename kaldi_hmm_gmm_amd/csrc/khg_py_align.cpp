@@ -470,6 +470,30 @@ void BindLattice(py::module_& m) {
         d["arcs"] = Vec1(r.arcs);
         return d;
       }, py::arg("ref"))
+      // lattice-mbr-decode and the word confidences on the host (what DeviceLattices.mbr gives for this lattice): status,
+      // iters, bayes_risk, words, conf, vocab, gamma [Q][len(vocab)], arc_cond, final_cond, cap, risks (one per accumulation).  init: the
+      // initial hypothesis (None: the best path's words); arc_cond / final_cond replace the host's own weights (the device's, to compare
+      // bit for bit)
+      .def("mbr", [](const Lattice& l, float gs, float as, bool decode_mbr, int max_iter, py::object init, int max_words, py::object arc_cond,
+                     py::object final_cond) {
+        std::vector<int32_t> h;
+        std::vector<double> ac, fc;
+        if (!init.is_none()) h = VecOf<int32_t>(init);
+        if (!arc_cond.is_none()) ac = VecOf<double>(arc_cond);
+        if (!final_cond.is_none()) fc = VecOf<double>(final_cond);
+        const LatticeMbr r = l.Mbr(gs, as, decode_mbr, max_iter, init.is_none() ? nullptr : &h, max_words, arc_cond.is_none() ? nullptr : &ac,
+                                   final_cond.is_none() ? nullptr : &fc);
+        const bool ok = (r.status & KHG_LAT_SUCCEEDED) != 0;
+        const py::ssize_t V = ok ? (py::ssize_t)r.vocab.size() : 0, Q = ok ? 2 * (py::ssize_t)r.words.size() + 1 : 0;
+        py::dict d;
+        d["status"] = r.status; d["iters"] = r.iters; d["bayes_risk"] = r.bayes_risk; d["words"] = Vec1(r.words); d["conf"] = Vec1(r.conf);
+        d["vocab"] = Vec1(ok ? r.vocab : std::vector<int32_t>());
+        Arr<double> g({Q, V});
+        if (ok && !r.gamma.empty()) std::memcpy(g.mutable_data(), r.gamma.data(), sizeof(double) * r.gamma.size());
+        d["gamma"] = g; d["arc_cond"] = Vec1(r.arc_cond); d["final_cond"] = Vec1(r.final_cond); d["cap"] = r.cap; d["risks"] = Vec1(r.risks);
+        return d;
+      }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f, py::arg("decode_mbr") = true, py::arg("max_iter") = 32, py::arg("init") = py::none(),
+         py::arg("max_words") = 0, py::arg("arc_cond") = py::none(), py::arg("final_cond") = py::none())
       .def("to_text", &Lattice::ToText)
       .def("__str__", &Lattice::ToText)
       .def_property_readonly("frame", [](py::object s) { auto& l = s.cast<Lattice&>(); return LatView(s, l.frame, l.frame.size()); })
@@ -778,6 +802,56 @@ void BindLattice(py::module_& m) {
         r["counts"] = counts; r["nwords"] = Vec1(nw); r["status"] = Vec1(st);
         return r;
       }, py::arg("refs"), py::arg("graph_scales"), py::arg("acoustic_scales"), py::arg("penalties"))
+      // lattice-mbr-decode and word confidences.  init: None, or one word sequence (or None: the best path's words) per
+      // utterance -> status, iters, bayes_risk [U]; words / conf with words_off; vocab with vocab_off; gamma (flat; utterance u's
+      // [Q][len(vocab)] table at gamma_off[u]); arc_cond / final_cond with arc_off / state_off: the weights the device used
+      .def("mbr", [](PyDeviceLattices& d, float gs, float as, bool decode_mbr, int max_iter, py::object init, int max_words, int64_t scratch_bytes) {
+        const auto so = LatSizes(d);
+        const int U = (int)so.first.size() - 1;
+        std::vector<int64_t> ioff;
+        std::vector<int32_t> iw, given;
+        int32_t n_utt = U;
+        if (!init.is_none()) {
+          ioff.assign(1, 0);
+          for (py::handle h : init) {
+            py::object o = py::reinterpret_borrow<py::object>(h);
+            given.push_back(o.is_none() ? 0 : 1);
+            if (!o.is_none()) {
+              Arr<int32_t> a = o.cast<Arr<int32_t>>();
+              iw.insert(iw.end(), a.data(), a.data() + a.size());
+            }
+            ioff.push_back((int64_t)iw.size());
+          }
+          n_utt = (int32_t)given.size();
+          given.push_back(0);
+        }
+        iw.push_back(0);      // (never a NULL array)
+        khg_mbr* mh = nullptr;
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_mbr(d.ctx, d.h, gs, as, decode_mbr ? 1 : 0, max_iter, n_utt, iw.data(), ioff.empty() ? nullptr : ioff.data(),
+                                ioff.empty() ? nullptr : given.data(), max_words, scratch_bytes, &mh));
+        }
+        std::unique_ptr<khg_mbr, int (*)(khg_mbr*)> guard(mh, khg_mbr_destroy);
+        std::vector<int64_t> woff((size_t)U + 1, 0), voff((size_t)U + 1, 0), goff((size_t)U + 1, 0);
+        CApi(khg_mbr_sizes(mh, woff.data(), voff.data(), goff.data()));
+        std::vector<int32_t> st((size_t)U + 1, 0), it((size_t)U + 1, 0);
+        Arr<double> risk({(py::ssize_t)U}), conf({(py::ssize_t)woff.back()}), gamma({(py::ssize_t)goff.back()}), ac({(py::ssize_t)so.second.back()}),
+            fc({(py::ssize_t)so.first.back()});
+        Arr<int32_t> words({(py::ssize_t)woff.back()}), vocab({(py::ssize_t)voff.back()});
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_mbr_download(d.ctx, mh, st.data(), it.data(), risk.mutable_data(), words.mutable_data(), conf.mutable_data(), vocab.mutable_data(),
+                                gamma.mutable_data(), ac.mutable_data(), fc.mutable_data()));
+        }
+        st.resize((size_t)U); it.resize((size_t)U);
+        py::dict r;
+        r["status"] = Vec1(st); r["iters"] = Vec1(it); r["bayes_risk"] = risk; r["words"] = words; r["words_off"] = Vec1(woff); r["conf"] = conf;
+        r["vocab"] = vocab; r["vocab_off"] = Vec1(voff); r["gamma"] = gamma; r["gamma_off"] = Vec1(goff); r["arc_cond"] = ac; r["final_cond"] = fc;
+        r["arc_off"] = Vec1(so.second); r["state_off"] = Vec1(so.first);
+        return r;
+      }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f, py::arg("decode_mbr") = true, py::arg("max_iter") = 32, py::arg("init") = py::none(),
+         py::arg("max_words") = 0, py::arg("scratch_bytes") = 0)
       .def("download", [](PyDeviceLattices& d) {
         if (!d.h) throw Error("DeviceLattices: closed");
         std::vector<std::shared_ptr<Lattice>> out;

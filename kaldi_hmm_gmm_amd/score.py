@@ -60,6 +60,45 @@ def lattice_oracle(lattice, ref: Sequence[int], scratch_bytes: int = 0):
     return lattice_oracle_batch([lattice], [ref], scratch_bytes)[0]
 
 
+def mbr_utterances(r):
+    """DeviceLattices.mbr's dict of arrays -> one dict per utterance: status, iters, bayes_risk, words, conf, vocab, gamma [Q][len(vocab)],
+    arc_cond, final_cond, and sausage: per position q = 1 .. Q the (word, prob) pairs with prob > 0, by descending prob, then ascending id"""
+    wo, vo, go, ao, so = r["words_off"], r["vocab_off"], r["gamma_off"], r["arc_off"], r["state_off"]
+    out = []
+    for u in range(len(r["status"])):
+        vocab = r["vocab"][vo[u]:vo[u + 1]].copy()
+        gamma = r["gamma"][go[u]:go[u + 1]].reshape(-1, max(len(vocab), 1))[:, :len(vocab)].copy()
+        sausage = [sorted(((int(vocab[k]), float(row[k])) for k in np.flatnonzero(row > 0)), key=lambda x: (-x[1], x[0])) for row in gamma]
+        out.append({"status": int(r["status"][u]), "iters": int(r["iters"][u]), "bayes_risk": float(r["bayes_risk"][u]),
+                    "words": r["words"][wo[u]:wo[u + 1]].copy(), "conf": r["conf"][wo[u]:wo[u + 1]].copy(), "vocab": vocab, "gamma": gamma,
+                    "arc_cond": r["arc_cond"][ao[u]:ao[u + 1]].copy(), "final_cond": r["final_cond"][so[u]:so[u + 1]].copy(), "sausage": sausage})
+    return out
+
+
+def lattice_mbr_decode_batch(lattices, graph_scale: float = 1.0, acoustic_scale: float = 1.0, decode_mbr: bool = True, max_iter: int = 32,
+                             init=None, max_words: int = 0, scratch_bytes: int = 0):
+    """Kaldi's lattice-mbr-decode and the confidences of lattice-to-ctm-conf for several utterances on the device (khg_lattices_mbr;
+    DESIGN.md section 7t): per utterance the hypothesis of least expected word error under the scale pair, a confidence per word and the
+    confusion bins.  init: None, or per utterance a word sequence or None (the best path's words).  decode_mbr=False: confidences of the
+    initial hypothesis only.  -> one dict per utterance (mbr_utterances).  lattices: a list of Lattice or a DeviceLattices."""
+    on, dl = _on_device(lattices)
+    if init is not None:
+        init = [None if h is None else np.asarray(h, np.int32).reshape(-1) for h in init]
+    try:
+        r = dl.mbr(float(graph_scale), float(acoustic_scale), bool(decode_mbr), int(max_iter), init, int(max_words), int(scratch_bytes))
+    finally:
+        if not on:
+            dl.close()
+    return mbr_utterances(r)
+
+
+def lattice_mbr_decode(lattice, graph_scale: float = 1.0, acoustic_scale: float = 1.0, decode_mbr: bool = True, max_iter: int = 32, init=None,
+                       max_words: int = 0, scratch_bytes: int = 0):
+    """lattice-mbr-decode for one utterance (lattice_mbr_decode_batch of one); init: a word sequence or None"""
+    return lattice_mbr_decode_batch([lattice], graph_scale, acoustic_scale, decode_mbr, max_iter, None if init is None else [init], max_words,
+                                    scratch_bytes)[0]
+
+
 def compute_wer(refs, hyps):
     """Kaldi's compute-wer --mode=all on word ids, on the host (khg_edit_distance) -> (the WER in percent, the summed counts: errors,
     insertions, deletions, substitutions, and the reference's words)."""

@@ -590,6 +590,48 @@ def score_bench(ctx, dl, refs, score, oracle, reps):
     return out
 
 
+def mbr_bench(ctx, dl, reps, gs=1.0, as_=0.1):
+    """--mbr on resident lattices, both sides in this process and alternated: DeviceLattices.mbr at (gs, as_) from the
+    best path beside the download of every lattice and a loop of the host form Lattice.mbr; then the host form once more with the
+    device's weights, which must give the device's outputs bit for bit."""
+    reps = max(reps, 3)
+    U = dl.num_utts
+    so, ao = np.asarray(dl.state_off), np.asarray(dl.arc_off)
+    r = dl.mbr(gs, as_); ctx.sync()                                      # warm-up (builds the in-arc index once)
+    t_dev, t_dl, t_host, k_ms = [], [], [], []
+    for _ in range(reps):
+        k_ms.append(kernel_ms(ctx, lambda: dl.mbr(gs, as_)))
+        ctx.sync(); t0 = time.time()
+        r = dl.mbr(gs, as_)
+        t_dev.append(time.time() - t0)
+        t0 = time.time()
+        lats = dl.download()
+        t_dl.append(time.time() - t0)
+        t0 = time.time()
+        host = [L.mbr(gs, as_) for L in lats]
+        t_host.append(time.time() - t0)
+    per = khg.mbr_utterances(r)
+    same = same_words = 0
+    for L, d, h in zip(lats, per, host):
+        g = L.mbr(gs, as_, arc_cond=d["arc_cond"], final_cond=d["final_cond"])
+        same += g["status"] == d["status"] and g["iters"] == d["iters"] and g["bayes_risk"] == d["bayes_risk"] and g["words"].tolist() == d["words"].tolist() \
+            and g["conf"].tobytes() == d["conf"].tobytes() and g["gamma"].tobytes() == d["gamma"].tobytes()
+        same_words += h["words"].tolist() == d["words"].tolist()
+    ok = [d for d in per if d["status"] & 1]
+    W = np.asarray([len(d["words"]) for d in ok] or [0])
+    V = np.asarray([len(d["vocab"]) for d in ok] or [1])
+    it = np.asarray([d["iters"] for d in ok] or [0])
+    ms = {k: float(np.median([x.get(k, 0.0) for x in k_ms])) for k in sorted({k for x in k_ms for k in x})}
+    return {"utterances": U, "graph_scale": gs, "acoustic_scale": as_, "states_mean": float(np.diff(so).mean()), "arcs_mean": float(np.diff(ao).mean()),
+            "repetitions": reps, "succeeded": len(ok), "not_converged": sum(1 for d in ok if d["status"] & 2048), "words_mean": float(W.mean()),
+            "vocab_mean": float(V.mean()), "vocab_max": int(V.max()), "iters_mean": float(it.mean()), "iters_max": int(it.max()),
+            "iters_histogram": np.bincount(it).tolist(), "lane_occupancy_mean": float(((2 * W + 2) / (64.0 * np.ceil((2 * W + 2) / 64.0))).mean()),
+            "positions_mean": float((2 * W + 2).mean()), "bayes_risk_mean": float(np.mean([d["bayes_risk"] for d in ok] or [0.0])),
+            "kernels_ms": ms, "call": med(t_dev), "download": med(t_dl), "host_loop": med(t_host),
+            "host_over_device": float(np.median(t_host)) / float(np.median(t_dev)), "same_as_host_given_device_weights": same,
+            "same_words_as_host_with_its_own_weights": same_words}
+
+
 def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
     """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
     after one warm-up round; and the last results."""
@@ -771,6 +813,13 @@ def shared_graph_main(args):
                 L = sh.raw_lattices_faster_device(dtm, beam=13.0, max_active=7000, lattice_beam=lb, acoustic_scale=0.1)["lattices"]
                 entry["score"]["lattice_beam_%g" % lb] = score_bench(ctx, L, [p + 1 for p in picks], args.score, args.oracle, args.reps)
                 L.close()
+        if args.mbr and name == "faster":
+            # minimum Bayes risk decoding of the lattices the shared set leaves on the device; again at a wider lattice beam
+            entry["mbr"] = {}
+            for lb in (6.0, args.dense_lattice_beam):
+                L = sh.raw_lattices_faster_device(dtm, beam=13.0, max_active=7000, lattice_beam=lb, acoustic_scale=0.1)["lattices"]
+                entry["mbr"]["lattice_beam_%g" % lb] = mbr_bench(ctx, L, args.reps)
+                L.close()
         for us in sets.values():
             us.close()
         dg.close()
@@ -809,8 +858,12 @@ def main():
                     "download and a loop of the host form Lattice.oracle (DESIGN.md 7s)")
     ap.add_argument("--score", default=None, metavar="LO:HI", help="with --lattices (--decoder faster): DeviceLattices.wer at the LM weights LO..HI x "
                     "penalties {0, 0.5, 1} beside add_penalty + best_path + the host's khg_edit_distance; add_penalty beside a device copy")
-    ap.add_argument("--dense-lattice-beam", type=float, default=12.0, help="with --shared-graph --oracle / --score: the second, denser set's lattice beam")
+    ap.add_argument("--mbr", action="store_true", help="with --lattices (--decoder faster): DeviceLattices.mbr on the resident lattices beside the "
+                    "download and a loop of the host form Lattice.mbr (DESIGN.md 7t)")
+    ap.add_argument("--dense-lattice-beam", type=float, default=12.0, help="with --shared-graph --oracle / --score / --mbr: the second, denser set's lattice beam")
     args = ap.parse_args()
+    if args.mbr and (not args.lattices or args.decoder != "faster" or args.yesno):
+        ap.error("--mbr needs --lattices with --decoder faster (and is not timed with --yesno)")
     if (args.oracle or args.score) and (not args.lattices or args.decoder != "faster" or args.yesno):
         ap.error("--oracle / --score need --lattices with --decoder faster (and are not timed with --yesno)")
     if (args.sweep or args.prune_beam is not None or args.post) and not args.lattices:
@@ -883,7 +936,7 @@ def main():
                     emission_kernels_ms=emit, emission_over_decoder=(emit + dec_new - dec_old) / dec_old if dec_old else None)
         faster_lat = flat
         faster_ops = None
-        if args.sweep or args.prune_beam is not None or args.post or args.rescore or args.mpe or args.lmrescore or args.oracle or args.score:
+        if args.sweep or args.prune_beam is not None or args.post or args.rescore or args.mpe or args.lmrescore or args.oracle or args.score or args.mbr:
             _, dl = khg.get_raw_lattice_faster_device_batch(am, tm, fsts, feats, cfg, 0.1)
             faster_ops = {}
             if args.sweep or args.prune_beam is not None or args.post:
@@ -899,6 +952,8 @@ def main():
                 faster_ops["lmrescore"] = lmrescore_bench(ctx, dl, [r["words"] for r in fres], vocab, args.lmrescore, args.reps, flat["raw_decode_call"])
             if args.oracle or args.score:
                 faster_ops["score"] = score_bench(ctx, dl, [r["words"] for r in fres], args.score, args.oracle, args.reps)
+            if args.mbr:
+                faster_ops["mbr"] = mbr_bench(ctx, dl, args.reps)
             dl.close()
     st = [r["status"] for r in res]
     out = {"decoder": args.decoder,"utterances": args.utts, "frames": frames, "lattice_s": min(lat_s), "lattice_frames_per_s": frames / min(lat_s),
