@@ -6,7 +6,34 @@
 // (khg_k2_lattice_mpe.hip.inc: the same device functions and the same host steps per chunk around a kernel of its own), and rescoring /
 // boosting (khg_lattices_rescore, khg_lattices_boost: khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc), and the backoff n-gram LM
 // (khg_lm) with khg_lattices_lm_rescore (khg_k2_lattice_lm.hip.inc), and scoring (khg_lattices_add_penalty, khg_lattices_oracle,
-// khg_lattices_wer, khg_edit_distance: khg_k2_lattice_score.hip.inc).  gfx950 only.
+// khg_lattices_wer, khg_edit_distance: khg_k2_lattice_score.hip.inc), and minimum Bayes risk decoding (khg_lattices_mbr:
+// khg_k2_lattice_mbr.hip.inc).  gfx950 only.
+//
+// The host steps the families share, each written once (helpers take the bare name of the call the error texts name, "khg_x"):
+//   DevBlocks::alloc / upload / zeroed, download   a call's device scratch with the copy or the clearing that fills it, and the copy back
+//                                                  into a vector: every entry point below
+//   launch                                         one launch under one timer; loops of launches under one timer (k2x_*, add_penalty,
+//                                                  the words' packing, k3_post_flatten) and the launches without a timer (lat_meta,
+//                                                  lat_width) are written out
+//   scan_pairs_and_read, size_out_chunk            mark -> scan, ONE synchronisation, the output chunk -> fill: simple_emit,
+//                                                  khg_lattices_prune, khg_lattices_lm_rescore (faster_emit and post_chunk_finish size a
+//                                                  block that is not a handle's next chunk: they call the scan themselves)
+//   split_by_budget                                the decoders' slices in launches of <= 4 GiB: faster_pass, decode_lattice_simple_impl
+//   group_tables                                   utterances' tables in launches under a caller's budget: khg_lattices_oracle, _mbr
+//   pack_words                                     the words of the entries that succeeded under words_cap: decode_out_download (over
+//                                                  the cap: refused), khg_lattices_best_path and khg_lattices_oracle (KHG_LAT_WORDS)
+//   best_path_args                                 the scale pairs and the per-chunk best-path scratch: khg_lattices_best_path, _wer
+//   check_offsets                                  offsets from 0 that never decrease, over data that is there: lat_ref_check,
+//                                                  score_ref_check, khg_lattices_mbr, khg_posteriors_validate, khg_posteriors_upload
+//   lat_ready                                      arena_flush, lat_meta and on request lat_index / lat_width, at the entry of
+//                                                  khg_lattices_ali_layout, _best_path, _prune, _posteriors, _rescore, _boost,
+//                                                  _mpe_posteriors, _lm_rescore, _oracle, _wer and _mbr (_add_penalty reads no
+//                                                  offsets: arena_flush alone; _rescore and _boost call lat_meta again for the
+//                                                  copy they make, _mpe_posteriors calls lat_index after the reference's checks)
+//   other_ctx                                      the refusal of a handle of another context: khg_lattices_rescore, _boost,
+//                                                  _mpe_posteriors (and lat_ref_check for their ali_set), _lm_rescore, _add_penalty,
+//                                                  _oracle, _wer, _mbr, khg_mbr_download
+//   decode_prologue, DecodeOut, PostRun            the two decoders; khg_lattices_posteriors, _mpe_posteriors and _mbr's weights
 #include "khg_internal.hpp"
 
 #include <memory>
@@ -72,7 +99,74 @@ struct DevBlocks {
     *out = static_cast<T*>(q);
     return KHG_OK;
   }
+  // a block of `count` elements and the copy of src[0 .. count) into it, enqueued on the context's stream
+  template <class T>
+  int upload(khg_ctx* ctx, const T* src, int64_t count, T** out) {
+    int rc = alloc(count, out);
+    if (rc) return rc;
+    if (count > 0) HIPCHK(hipMemcpyAsync(*out, src, sizeof(T) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    return KHG_OK;
+  }
+  template <class T>
+  int upload(khg_ctx* ctx, const std::vector<T>& src, T** out) { return upload(ctx, src.data(), (int64_t)src.size(), out); }
+  // a block of `count` elements, cleared on the context's stream
+  template <class T>
+  int zeroed(khg_ctx* ctx, int64_t count, T** out) {
+    int rc = alloc(count, out);
+    if (rc) return rc;
+    if (count > 0) HIPCHK(hipMemsetAsync(*out, 0, sizeof(T) * (size_t)count, ctx->stream));
+    return KHG_OK;
+  }
 };
+// dst sized to `count` elements and the copy of src_d[0 .. count) into it, enqueued on the context's stream: dst holds them after the
+// next synchronisation
+template <class T>
+int download(khg_ctx* ctx, const T* src_d, int64_t count, std::vector<T>* dst) {
+  dst->resize((size_t)count);
+  if (count > 0) HIPCHK(hipMemcpyAsync(dst->data(), src_d, sizeof(T) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+  return KHG_OK;
+}
+// One launch under a timer of its own: the entry `name` of the context's timings, the staged uploads, the launch on the context's
+// stream, its error.  (A loop of launches under one timer, and a launch without a timer, are written out where they stand.)
+template <class... P, class... A>
+int launch(khg_ctx* ctx, const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A&... args) {
+  KernelTimer kt(ctx, name);
+  KHG_LAUNCH(ctx, kernel, grid, block, lds, ctx->stream, args...);
+  HIPCHK(hipGetLastError());
+  return KHG_OK;
+}
+// the refusal of a handle that was made on another context, in the name of the call `who`
+int other_ctx(const std::string& who) { return khg_set_error(KHG_E_ARG, who + ": a handle of another context"); }
+// Offsets off[0 .. n] (the argument `name`, one entry per `what`): they start at 0 and never decrease; data_name != nullptr: `data`,
+// which they index, is there when they end above 0
+int check_offsets(const std::string& who, const char* name, const int64_t* off, int64_t n, const char* what, const void* data = nullptr,
+                  const char* data_name = nullptr) {
+  if (!off || off[0] != 0) return khg_set_error(KHG_E_ARG, who + ": " + name + " must start at 0");
+  for (int64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return khg_set_error(KHG_E_ARG, who + ": " + name + " decreases at " + what + " " + std::to_string(i));
+  if (data_name && off[n] > 0 && !data) return khg_set_error(KHG_E_ARG, who + ": " + data_name + " is NULL");
+  return KHG_OK;
+}
+// The words of the entries that succeeded, packed one after the other: entry i of st.size() brings n = count(i) words, the ones at
+// src(i, n), when st[i] has KHG_LAT_SUCCEEDED, none otherwise; words_off_h [entries + 1] says where they went in words_h [words_cap].
+// An entry whose words do not fit: with `over`, (*over)[i] = KHG_LAT_WORDS and none of them; without, the call `who` is refused.
+template <class Cnt, class Src>
+int pack_words(const std::string& who, const std::vector<int32_t>& st, std::vector<int32_t>* over, Cnt count, Src src, int32_t* words_h,
+               int64_t* words_off_h, int64_t words_cap) {
+  int64_t pos = 0;
+  for (size_t i = 0; i < st.size(); ++i) {
+    words_off_h[i] = pos;
+    int64_t n = (st[i] & KHG_LAT_SUCCEEDED) ? (int64_t)count(i) : 0;
+    if (pos + n > words_cap) {
+      if (!over) return khg_set_error(KHG_E_ARG, who + ": words_cap too small");
+      (*over)[i] = KHG_LAT_WORDS; n = 0;
+    }
+    std::copy_n(src(i, n), n, words_h + pos);
+    pos += n;
+  }
+  words_off_h[st.size()] = pos;
+  return KHG_OK;
+}
 
 // an empty handle of U utterances, with the start states' array
 int new_lattices(khg_ctx* ctx, int U, LatPtr* out) {
@@ -124,12 +218,8 @@ int read_pair_offsets(khg_ctx* ctx, const int64_t* off_d, int n, std::vector<int
 // the exclusive prefixes of n pairs tot_d [2 n] (k2_lattice_scan_pairs, timed as `timer_name`) to off_d, and read_pair_offsets of them
 int scan_pairs_and_read(khg_ctx* ctx, const char* timer_name, const int64_t* tot_d, int64_t* off_d, int n, std::vector<int64_t>* first,
                         std::vector<int64_t>* second) {
-  {
-    KernelTimer kt(ctx, timer_name);
-    KHG_LAUNCH(ctx, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, ctx->stream, tot_d, off_d, n);
-    HIPCHK(hipGetLastError());
-  }
-  return read_pair_offsets(ctx, off_d, n, first, second);
+  int rc = launch(ctx, timer_name, k2_lattice_scan_pairs, dim3(1), dim3(64), 0, tot_d, off_d, n);
+  return rc ? rc : read_pair_offsets(ctx, off_d, n, first, second);
 }
 // a lattice's arc_begin and nextstate are int32: utterance ids[b] (nullptr: u0 + b) of a chunk with the prefix arrays so / ao is refused
 // in the name of `who` when it has more states or arcs
@@ -149,6 +239,20 @@ int add_chunk_counts(const std::string& who, int u0, const std::vector<int64_t>&
     (*state_off)[(size_t)u0 + b + 1] = (*state_off)[(size_t)u0] + so[b + 1];
     (*arc_off)[(size_t)u0 + b + 1] = (*arc_off)[(size_t)u0] + ao[b + 1];
   }
+  return KHG_OK;
+}
+// Between a mark kernel and its fill kernel: a mark left the (states, arcs) of the n utterances u0 .. at utt_tot [2 n].  Their scan to
+// utt_off (timed as `scan_name`) with the ONE synchronisation that sizes the output, the counts onto res's offsets (an utterance above
+// 2^31 - 1 is refused in the name of `who`), and res's next chunk, allocated: *ch, for the fill to write
+int size_out_chunk(khg_ctx* ctx, const std::string& who, const char* scan_name, const int64_t* utt_tot, int64_t* utt_off, int u0, int n,
+                   khg_lattices* res, LatChunk* ch) {
+  std::vector<int64_t> so, ao;
+  int rc = scan_pairs_and_read(ctx, scan_name, utt_tot, utt_off, n, &so, &ao);
+  if (!rc) rc = add_chunk_counts(who, u0, so, ao, &res->state_off, &res->arc_off);
+  if (rc) return rc;
+  ch->u0 = u0; ch->n = n; ch->ns = so[(size_t)n]; ch->na = ao[(size_t)n];
+  if ((rc = lat_chunk_alloc(ch, &res->bytes))) return rc;
+  res->chunks.push_back(*ch);
   return KHG_OK;
 }
 // grid.y of a fill over n utterances whose largest has max_n items: stripes of nt items go to workgroups of their own while the launch
@@ -285,18 +389,9 @@ int decode_out_download(khg_ctx* ctx, const std::string& who, const DecodeOut& o
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (status_h) std::copy(st.begin(), st.end(), status_h);
-  if (words_h && words_off_h) {
-    int64_t pos = 0;
-    for (size_t i = 0; i < U; ++i) {
-      words_off_h[i] = pos;
-      const int64_t n = (st[i] & KHG_LAT_SUCCEEDED) ? nw[i] : 0;
-      if (pos + n > words_cap) return khg_set_error(KHG_E_ARG, who + ": words_cap too small");
-      std::copy(w.begin() + o.wcap_off[i], w.begin() + o.wcap_off[i] + n, words_h + pos);
-      pos += n;
-    }
-    words_off_h[U] = pos;
-  }
-  return KHG_OK;
+  if (!(words_h && words_off_h)) return KHG_OK;
+  return pack_words(who, st, nullptr, [&](size_t i) { return nw[i]; }, [&](size_t i, int64_t) { return w.begin() + o.wcap_off[i]; }, words_h,
+                    words_off_h, words_cap);
 }
 }  // namespace
 
@@ -340,16 +435,12 @@ int faster_emit(FasterRun& r, const std::vector<int32_t>& list, int k0, int n, E
   LatChunk& ch = eb.ch;
   ch.u0 = k0; ch.n = n; ch.ns = eb.so[(size_t)n]; ch.na = eb.ao[(size_t)n];
   if ((rc = lat_chunk_alloc(&ch, &eb.bytes))) return rc;
-  LfrArgs p;
-  std::memset(&p, 0, sizeof(p));
+  LfrArgs p{};
   p.a = r.a; p.n = n; p.utt_off = r.off_d; p.start_out = r.start_d;
   lat_chunk_arrays(ch, &p.out);
   int64_t max_n = 0;
   for (int b = 0; b < n; ++b) max_n = std::max(max_n, eb.so[(size_t)b + 1] - eb.so[(size_t)b]);
-  KernelTimer kt(ctx, "k2_lattice_faster_raw_fill");
-  KHG_LAUNCH(ctx, k2_lattice_faster_raw_fill, dim3((unsigned)n, stripes(max_n, LFR_NT, n)), dim3(LFR_NT), 0, ctx->stream, p, k0);
-  HIPCHK(hipGetLastError());
-  return KHG_OK;
+  return launch(ctx, "k2_lattice_faster_raw_fill", k2_lattice_faster_raw_fill, dim3((unsigned)n, stripes(max_n, LFR_NT, n)), dim3(LFR_NT), 0, p, k0);
 }
 
 // One pass over a list of utterances: each gets a scratch slice of `per_frame` tokens / links per frame (0: the automatic size,
@@ -377,23 +468,16 @@ int faster_pass(FasterRun& r, const std::vector<int32_t>& list, int64_t per_fram
   split_by_budget(bytes, &cb, &rel, &max_chunk);
   unsigned char* scratch; int64_t* scr_off_d; int32_t *tcap_d, *lcap_d, *list_d;
   int rc;
-  if ((rc = r.dv.alloc(max_chunk, &scratch)) || (rc = r.dv.alloc((int64_t)L, &scr_off_d)) || (rc = r.dv.alloc((int64_t)L, &tcap_d)) ||
-      (rc = r.dv.alloc((int64_t)L, &lcap_d)) || (rc = r.dv.alloc((int64_t)L, &list_d)))
+  if ((rc = r.dv.alloc(max_chunk, &scratch)) || (rc = r.dv.upload(ctx, rel, &scr_off_d)) || (rc = r.dv.upload(ctx, tcap, &tcap_d)) ||
+      (rc = r.dv.upload(ctx, lcap, &lcap_d)) || (rc = r.dv.upload(ctx, list, &list_d)))
     return rc;
-  HIPCHK(hipMemcpyAsync(scr_off_d, rel.data(), 8 * L, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(tcap_d, tcap.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(lcap_d, lcap.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(list_d, list.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream));
   a.scratch = scratch; a.scr_off = scr_off_d; a.tok_cap = tcap_d; a.link_cap = lcap_d; a.list = list_d;
   for (size_t c = 0; c + 1 < cb.size(); ++c) {
     const int n = (int)(cb[c + 1] - cb[c]), k0 = (int)cb[c];
-    {
-      KernelTimer kt(ctx, "k2_lattice_faster");
-      if (r.lat) KHG_LAUNCH(ctx, k2_lattice_faster_lat, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, k0, r.tot_d);
-      else KHG_LAUNCH(ctx, k2_lattice_faster, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, k0);
-      HIPCHK(hipGetLastError());
-    }
-    if (r.lat && (rc = faster_emit(r, list, k0, n, blocks))) return rc;
+    rc = r.lat ? launch(ctx, "k2_lattice_faster", k2_lattice_faster_lat, dim3((unsigned)n), dim3(64), 0, a, k0, r.tot_d)
+               : launch(ctx, "k2_lattice_faster", k2_lattice_faster, dim3((unsigned)n), dim3(64), 0, a, k0);
+    if (!rc && r.lat) rc = faster_emit(r, list, k0, n, blocks);
+    if (rc) return rc;
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));    // the slices are freed with `dv` or reused by the next pass
   return KHG_OK;
@@ -436,8 +520,7 @@ int faster_assemble(FasterRun& r, EmitBlocks& pass1, EmitBlocks& pass2, const st
       for (int j = 0; j < 5; ++j) bd.ar[j] = reinterpret_cast<const int32_t*>(e->ch.buf + e->ch.ar[j]);
       blocks_h.push_back(bd);
     }
-    if ((rc = r.dv.alloc((int64_t)blocks_h.size(), &blocks_d))) return rc;
-    HIPCHK(hipMemcpyAsync(blocks_d, blocks_h.data(), sizeof(LfrBlock) * blocks_h.size(), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = r.dv.upload(ctx, blocks_h, &blocks_d))) return rc;
   }
   for (EmitBlock& e : pass1.v) {
     const size_t u0 = (size_t)e.ch.u0, n = (size_t)e.ch.n;
@@ -461,20 +544,16 @@ int faster_assemble(FasterRun& r, EmitBlocks& pass1, EmitBlocks& pass2, const st
     ch.u0 = (int)u0; ch.n = (int)n; ch.ns = dst_off[n]; ch.na = dst_off[2 * n + 1];
     if ((rc = lat_chunk_alloc(&ch, &lats->bytes))) return rc;
     lats->chunks.push_back(ch);
-    LfrGather g;
-    std::memset(&g, 0, sizeof(g));
+    LfrGather g{};
     int32_t* src_blk_d; int64_t *src_off_d, *dst_off_d;
-    if ((rc = r.dv.alloc((int64_t)n, &src_blk_d)) || (rc = r.dv.alloc(2 * (int64_t)n, &src_off_d)) || (rc = r.dv.alloc(2 * ((int64_t)n + 1), &dst_off_d)))
+    if ((rc = r.dv.upload(ctx, src_blk.data() + u0, (int64_t)n, &src_blk_d)) || (rc = r.dv.upload(ctx, src_off.data() + 2 * u0, 2 * (int64_t)n, &src_off_d)) ||
+        (rc = r.dv.upload(ctx, dst_off, &dst_off_d)))
       return rc;
-    HIPCHK(hipMemcpyAsync(src_blk_d, src_blk.data() + u0, 4 * n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(src_off_d, src_off.data() + 2 * u0, 16 * n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(dst_off_d, dst_off.data(), 16 * (n + 1), hipMemcpyHostToDevice, ctx->stream));
     g.blocks = blocks_d; g.src_block = src_blk_d; g.src_off = src_off_d; g.dst_off = dst_off_d; g.n = (int32_t)n;
     for (int j = 0; j < 6; ++j) g.st[j] = reinterpret_cast<int32_t*>(ch.buf + ch.st[j]);
     for (int j = 0; j < 5; ++j) g.ar[j] = reinterpret_cast<int32_t*>(ch.buf + ch.ar[j]);
-    KernelTimer kt(ctx, "k2_lattice_faster_raw_gather");
-    KHG_LAUNCH(ctx, k2_lattice_faster_raw_gather, dim3((unsigned)n, stripes(max_n, LFR_NT, (int)n)), dim3(LFR_NT), 0, ctx->stream, g);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch(ctx, "k2_lattice_faster_raw_gather", k2_lattice_faster_raw_gather, dim3((unsigned)n, stripes(max_n, LFR_NT, (int)n)), dim3(LFR_NT), 0, g)))
+      return rc;
   }
   if (!again.empty()) return check_err_flag(ctx, r.who.c_str());     // synchronises: the blocks the chunks were gathered from go now
   return KHG_OK;
@@ -564,29 +643,13 @@ int simple_emit(khg_ctx* ctx, LrArgs p, int u0, int nt, int64_t max_T, khg_latti
   const int n = p.n;
   // frames are independent: stripes of them go to workgroups of their own while the chunk has few utterances
   const unsigned gy = (unsigned)std::min<int64_t>(max_T + 1, std::max<int64_t>(1, 1024 / n));
-  {
-    KernelTimer kt(ctx, "k2_lattice_raw_count");
-    KHG_LAUNCH(ctx, k2_lattice_raw_count, dim3((unsigned)n, gy), dim3(nt), 0, ctx->stream, p, u0);
-    HIPCHK(hipGetLastError());
-  }
-  {
-    KernelTimer kt(ctx, "k2_lattice_raw_scan");
-    KHG_LAUNCH(ctx, k2_lattice_raw_scan_frames, dim3((unsigned)n), dim3(64), 0, ctx->stream, p, u0);
-    HIPCHK(hipGetLastError());
-  }
-  std::vector<int64_t> so, ao;
-  int rc = scan_pairs_and_read(ctx, "k2_lattice_raw_scan", p.utt_tot, p.utt_off, n, &so, &ao);
-  if (!rc) rc = add_chunk_counts("khg_decode_lattice_simple_raw", u0, so, ao, &lats->state_off, &lats->arc_off);
-  if (rc) return rc;
   LatChunk ch;
-  ch.u0 = u0; ch.n = n; ch.ns = so[(size_t)n]; ch.na = ao[(size_t)n];
-  if ((rc = lat_chunk_alloc(&ch, &lats->bytes))) return rc;
-  lats->chunks.push_back(ch);
+  int rc = launch(ctx, "k2_lattice_raw_count", k2_lattice_raw_count, dim3((unsigned)n, gy), dim3(nt), 0, p, u0);
+  if (!rc) rc = launch(ctx, "k2_lattice_raw_scan", k2_lattice_raw_scan_frames, dim3((unsigned)n), dim3(64), 0, p, u0);
+  if (!rc) rc = size_out_chunk(ctx, "khg_decode_lattice_simple_raw", "k2_lattice_raw_scan", p.utt_tot, p.utt_off, u0, n, lats, &ch);
+  if (rc) return rc;
   lat_chunk_arrays(ch, &p.out);
-  KernelTimer kt(ctx, "k2_lattice_raw_fill");
-  KHG_LAUNCH(ctx, k2_lattice_raw_fill, dim3((unsigned)n, gy), dim3(nt), 0, ctx->stream, p, u0);
-  HIPCHK(hipGetLastError());
-  return KHG_OK;
+  return launch(ctx, "k2_lattice_raw_fill", k2_lattice_raw_fill, dim3((unsigned)n, gy), dim3(nt), 0, p, u0);
 }
 
 // khg_decode_lattice_simple (lat_out == nullptr: nothing about lattices runs) and khg_decode_lattice_simple_raw
@@ -605,8 +668,7 @@ int decode_lattice_simple_impl(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, cons
   if (lat && (rc = new_lattices(ctx, U, &lats))) return rc;
   if (U == 0) { if (lat) *lat_out = lats.release(); return KHG_OK; }
   DevBlocks dv;
-  LrArgs p;          // (lattices) the chunks' emit
-  std::memset(&p, 0, sizeof(p));
+  LrArgs p{};        // (lattices) the chunks' emit
   if (lat) {
     p.start_out = lats->start_d;
     if ((rc = dv.alloc(2 * (int64_t)U, &p.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)U + 1), &p.utt_off))) return rc;
@@ -634,22 +696,16 @@ int decode_lattice_simple_impl(khg_ctx* ctx, const khg_tm* tm, khg_utts* u, cons
   int64_t max_chunk = 0;
   split_by_budget(bytes, &cb, &rel, &max_chunk);
   unsigned char* scratch; int64_t* scr_off_d; int32_t* list_d;
-  if ((rc = dv.alloc(max_chunk, &scratch)) || (rc = dv.alloc(U, &scr_off_d)) || (rc = dv.alloc(U, &list_d))) return rc;
   std::vector<int32_t> all((size_t)U);
   for (int i = 0; i < U; ++i) all[(size_t)i] = i;
-  HIPCHK(hipMemcpyAsync(scr_off_d, rel.data(), 8 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(list_d, all.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = dv.alloc(max_chunk, &scratch)) || (rc = dv.upload(ctx, rel, &scr_off_d)) || (rc = dv.upload(ctx, all, &list_d))) return rc;
   a.scratch = scratch; a.scr_off = scr_off_d; a.list = list_d;
   p.a = a;
   // one wave for small graphs, up to four for larger ones (a lane owns states s = lane, lane + NT, ...)
   const int nt = u->max_states <= 64 ? 64 : u->max_states <= 128 ? 128 : LS_NT;
   for (size_t c = 0; c + 1 < cb.size(); ++c) {
     const int n = (int)(cb[c + 1] - cb[c]), u0 = (int)cb[c];
-    {
-      KernelTimer kt(ctx, "k2_lattice_simple");
-      KHG_LAUNCH(ctx, k2_lattice_simple, dim3((unsigned)n), dim3(nt), 0, ctx->stream, a, u0);
-      HIPCHK(hipGetLastError());
-    }
+    if ((rc = launch(ctx, "k2_lattice_simple", k2_lattice_simple, dim3((unsigned)n), dim3(nt), 0, a, u0))) return rc;
     p.n = n;
     if (lat && (rc = simple_emit(ctx, p, u0, nt, max_T, lats.get()))) return rc;
     if (c + 2 < cb.size()) HIPCHK(hipStreamSynchronize(ctx->stream));     // the next launch reuses the slices
@@ -715,17 +771,50 @@ int lat_meta(khg_ctx* ctx, khg_lattices* l) {
   int rc = dv.alloc((int64_t)U, &t_d);
   if (rc) return rc;
   for (const LatChunk& c : l->chunks) {
-    LoArgs p;
-    std::memset(&p, 0, sizeof(p));
+    LoArgs p{};
     lat_chunk_args(l, c, &p);
     KHG_LAUNCH(ctx, k2_lattice_ops_last_frame, dim3((unsigned)((c.n + LO_NT - 1) / LO_NT)), dim3(LO_NT), 0, ctx->stream, p, t_d);
     HIPCHK(hipGetLastError());
   }
-  std::vector<int32_t> t(U);
-  HIPCHK(hipMemcpyAsync(t.data(), t_d, 4 * U, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<int32_t> t;
+  if ((rc = download(ctx, t_d, (int64_t)U, &t))) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   l->ali_off.assign(U + 1, 0);
   for (size_t u = 0; u < U; ++u) l->ali_off[u + 1] = l->ali_off[u] + std::max(t[u], 0);
+  return KHG_OK;
+}
+// The entry of an operation on a resident handle: the staged uploads out, then what the operation reads of the handle beside its
+// arrays, each made once per handle -- always the offsets and the alignment layout (lat_meta), on request the in-arc index (lat_index)
+// and the widest frames (lat_width)
+enum { kWithIndex = 1, kWithWidth = 2 };
+int lat_index(khg_ctx* ctx, khg_lattices* l);
+int lat_width(khg_ctx* ctx, khg_lattices* l);
+int lat_ready(khg_ctx* ctx, khg_lattices* l, int with = 0) {
+  int rc = arena_flush(ctx);
+  if (!rc) rc = lat_meta(ctx, l);
+  if (!rc && (with & kWithIndex)) rc = lat_index(ctx, l);
+  if (!rc && (with & kWithWidth)) rc = lat_width(ctx, l);
+  return rc;
+}
+// What khg_lattices_best_path and khg_lattices_wer share: the K scale pairs on the device, and per chunk of l the arguments of a
+// best-path kernel -- the chunk, its LDS, the pairs, the per-(pair, utterance) word counts and statuses, and the six arrays of a cell
+// per (state, pair) -- in *pcs; the scratch is dv's
+int best_path_args(khg_ctx* ctx, const khg_lattices* l, int K, const float* graph_scale, const float* acoustic_scale, int32_t* nw_d, int32_t* status_d,
+                   DevBlocks* dv, std::vector<LoArgs>* pcs) {
+  float *gs_d, *as_d;
+  int rc;
+  if ((rc = dv->upload(ctx, graph_scale, K, &gs_d)) || (rc = dv->upload(ctx, acoustic_scale, K, &as_d))) return rc;
+  for (const LatChunk& c : l->chunks) {
+    LoArgs p{};
+    lat_chunk_args(l, c, &p);
+    p.lds_bytes = lat_chunk_lds(ctx, l, c);
+    p.K = K; p.gs = gs_d; p.as = as_d; p.nwords = nw_d; p.status = status_d;
+    const int64_t cells = std::max<int64_t>(c.ns * K, 1);
+    if ((rc = dv->alloc(cells, &p.d1)) || (rc = dv->alloc(cells, &p.d2)) || (rc = dv->alloc(cells, &p.n1)) || (rc = dv->alloc(cells, &p.n2)) ||
+        (rc = dv->alloc(cells, &p.bp)) || (rc = dv->alloc(cells, &p.words)))
+      return rc;
+    pcs->push_back(p);
+  }
   return KHG_OK;
 }
 // the largest count among the chunk's utterances in a handle's offsets
@@ -798,8 +887,7 @@ extern "C" int khg_lattices_chunk_utts(const khg_lattices* l, int32_t* first_utt
 extern "C" int khg_lattices_ali_layout(khg_ctx* ctx, const khg_lattices* lc, int64_t* ali_off_h) {
   if (ctx_dead(ctx) || !lc || !ali_off_h) return khg_set_error(KHG_E_ARG, "khg_lattices_ali_layout: bad arguments");
   khg_lattices* l = const_cast<khg_lattices*>(lc);
-  int rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
+  int rc = lat_ready(ctx, l);
   if (rc) return rc;
   std::copy(l->ali_off.begin(), l->ali_off.end(), ali_off_h);
   return KHG_OK;
@@ -845,51 +933,29 @@ extern "C" int khg_lattices_best_path(khg_ctx* ctx, const khg_lattices* lc, int3
   const int U = l->U, K = n_scales;
   if (words_off_h) std::fill(words_off_h, words_off_h + (int64_t)K * U + 1, 0);
   if (U == 0) return KHG_OK;
-  int rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
+  int rc = lat_ready(ctx, l);
   if (rc) return rc;
   const int64_t KU = (int64_t)K * U, AT = l->ali_off[(size_t)U];
   DevBlocks dv;
   int32_t *ali_d, *nw_d, *status_d, *packed_d;
-  float *weight_d, *gs_d, *as_d;
+  float* weight_d;
   int64_t *ali_off_d, *woff_d;
-  if ((rc = dv.alloc(std::max<int64_t>((int64_t)K * AT, 1), &ali_d)) || (rc = dv.alloc(KU, &nw_d)) || (rc = dv.alloc(KU, &status_d)) ||
-      (rc = dv.alloc(2 * KU, &weight_d)) || (rc = dv.alloc(K, &gs_d)) || (rc = dv.alloc(K, &as_d)) || (rc = dv.alloc(U + 1, &ali_off_d)) ||
-      (rc = dv.alloc(KU + 1, &woff_d)))
-    return rc;
-  HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>((int64_t)K * AT, 1), ctx->stream));
-  HIPCHK(hipMemcpyAsync(gs_d, graph_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(as_d, acoustic_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
   std::vector<LoArgs> pcs;
-  for (const LatChunk& c : l->chunks) {
-    LoArgs p;
-    std::memset(&p, 0, sizeof(p));
-    lat_chunk_args(l, c, &p);
-    p.lds_bytes = lat_chunk_lds(ctx, l, c);
-    p.K = K; p.gs = gs_d; p.as = as_d; p.ali = ali_d; p.ali_off = ali_off_d; p.ali_total = AT;
-    p.nwords = nw_d; p.weight = weight_d; p.status = status_d;
-    const int64_t cells = std::max<int64_t>(c.ns * K, 1);
-    if ((rc = dv.alloc(cells, &p.d1)) || (rc = dv.alloc(cells, &p.d2)) || (rc = dv.alloc(cells, &p.n1)) || (rc = dv.alloc(cells, &p.n2)) ||
-        (rc = dv.alloc(cells, &p.bp)) || (rc = dv.alloc(cells, &p.words)))
+  if ((rc = dv.zeroed(ctx, std::max<int64_t>((int64_t)K * AT, 1), &ali_d)) || (rc = dv.alloc(KU, &nw_d)) || (rc = dv.alloc(KU, &status_d)) ||
+      (rc = dv.alloc(2 * KU, &weight_d)) || (rc = best_path_args(ctx, l, K, graph_scale, acoustic_scale, nw_d, status_d, &dv, &pcs)) ||
+      (rc = dv.upload(ctx, l->ali_off, &ali_off_d)) || (rc = dv.alloc(KU + 1, &woff_d)))
+    return rc;
+  for (LoArgs& p : pcs) {
+    p.ali = ali_d; p.ali_off = ali_off_d; p.ali_total = AT; p.weight = weight_d;
+    if ((rc = launch(ctx, "k2_lattice_best_path", k2_lattice_best_path, dim3((unsigned)p.n, (unsigned)((K + LO_NT - 1) / LO_NT)), dim3(LO_NT), (size_t)p.lds_bytes, p)))
       return rc;
-    {
-      KernelTimer kt(ctx, "k2_lattice_best_path");
-      KHG_LAUNCH(ctx, k2_lattice_best_path, dim3((unsigned)c.n, (unsigned)((K + LO_NT - 1) / LO_NT)), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, p);
-      HIPCHK(hipGetLastError());
-    }
-    pcs.push_back(p);
   }
   // the words, packed on the device: a scan of the counts, one synchronisation to size the block, the copy
   std::vector<int64_t> woff((size_t)KU + 1, 0);
-  std::vector<int32_t> packed, st((size_t)KU);
+  std::vector<int32_t> packed, st;
   if (words_h && words_off_h) {
-    {
-      KernelTimer kt(ctx, "k2_lattice_ops_words");
-      KHG_LAUNCH(ctx, k2_lattice_ops_scan, dim3(1), dim3(64), 0, ctx->stream, nw_d, woff_d, KU);
-      HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(woff.data(), woff_d, 8 * ((size_t)KU + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = launch(ctx, "k2_lattice_ops_words", k2_lattice_ops_scan, dim3(1), dim3(64), 0, nw_d, woff_d, KU)) || (rc = download(ctx, woff_d, KU + 1, &woff)))
+      return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     const int64_t NW = woff[(size_t)KU];
     if ((rc = dv.alloc(std::max<int64_t>(NW, 1), &packed_d))) return rc;
@@ -898,26 +964,16 @@ extern "C" int khg_lattices_best_path(khg_ctx* ctx, const khg_lattices* lc, int3
       for (const LoArgs& p : pcs)
         KHG_LAUNCH(ctx, k2_lattice_ops_pack_words, dim3((unsigned)p.n, (unsigned)std::min(K, 64)), dim3(LO_NT), 0, ctx->stream, p, woff_d, packed_d);
       HIPCHK(hipGetLastError());
-      packed.resize((size_t)NW);
-      HIPCHK(hipMemcpyAsync(packed.data(), packed_d, 4 * (size_t)NW, hipMemcpyDeviceToHost, ctx->stream));
+      if ((rc = download(ctx, packed_d, NW, &packed))) return rc;
     }
   }
   if (ali_h && AT) HIPCHK(hipMemcpyAsync(ali_h, ali_d, 4 * (size_t)((int64_t)K * AT), hipMemcpyDeviceToHost, ctx->stream));
   if (weight_h) HIPCHK(hipMemcpyAsync(weight_h, weight_d, 8 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
-  rc = check_err_flag(ctx, "khg_lattices_best_path");     // synchronises
-  if (rc) return rc;
-  if (words_h && words_off_h) {
-    int64_t o = 0;
-    for (int64_t i = 0; i < KU; ++i) {
-      words_off_h[i] = o;
-      int64_t n = (st[(size_t)i] & KHG_LAT_SUCCEEDED) ? woff[(size_t)i + 1] - woff[(size_t)i] : 0;
-      if (o + n > words_cap) { st[(size_t)i] = KHG_LAT_WORDS; n = 0; }      // the path's words do not fit: none of them
-      std::copy(packed.begin() + woff[(size_t)i], packed.begin() + woff[(size_t)i] + n, words_h + o);
-      o += n;
-    }
-    words_off_h[KU] = o;
-  }
+  if ((rc = download(ctx, status_d, KU, &st)) || (rc = check_err_flag(ctx, "khg_lattices_best_path"))) return rc;     // synchronises
+  if (words_h && words_off_h &&       // (a path whose words do not fit: KHG_LAT_WORDS and none of them)
+      (rc = pack_words("khg_lattices_best_path", st, &st, [&](size_t i) { return woff[i + 1] - woff[i]; },
+                       [&](size_t i, int64_t) { return packed.begin() + woff[i]; }, words_h, words_off_h, words_cap)))
+    return rc;
   if (status_h) std::copy(st.begin(), st.end(), status_h);
   return KHG_OK;
 }
@@ -935,16 +991,12 @@ extern "C" int khg_lattices_prune(khg_ctx* ctx, const khg_lattices* lc, float gr
   int rc = new_lattices(ctx, U, &res);
   if (rc) return rc;
   if (U == 0) { *out = res.release(); return KHG_OK; }
-  rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (rc) return rc;
+  if ((rc = lat_ready(ctx, l))) return rc;
   DevBlocks dv;
   int32_t* status_d;
   if ((rc = dv.alloc(U, &status_d))) return rc;
-  std::vector<int64_t> so, ao;
   for (const LatChunk& c : l->chunks) {
-    LoArgs p;
-    std::memset(&p, 0, sizeof(p));
+    LoArgs p{};
     lat_chunk_args(l, c, &p);
     p.lds_bytes = lat_chunk_lds(ctx, l, c);
     p.K = 1; p.gs1 = graph_scale; p.as1 = acoustic_scale; p.beam = beam; p.status = status_d; p.o_start = res->start_d;
@@ -954,29 +1006,16 @@ extern "C" int khg_lattices_prune(khg_ctx* ctx, const khg_lattices* lc, float gr
         (rc = dv.alloc(cells, &p.newid)) || (rc = dv.alloc(cells, &p.nab)) || (rc = dv.alloc(c.n, &p.limit)) ||
         (rc = dv.alloc(2 * (int64_t)c.n, &p.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.utt_off)))
       return rc;
-    {
-      KernelTimer kt(ctx, "k2_lattice_prune_mark");
-      KHG_LAUNCH(ctx, k2_lattice_prune_mark, dim3((unsigned)c.n), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, p);
-      HIPCHK(hipGetLastError());
-    }
-    rc = scan_pairs_and_read(ctx, "k2_lattice_prune_scan", p.utt_tot, p.utt_off, c.n, &so, &ao);      // the one synchronisation that sizes the output
-    if (!rc) rc = add_chunk_counts("khg_lattices_prune", c.u0, so, ao, &res->state_off, &res->arc_off);
-    if (rc) return rc;
     LatChunk ch;
-    ch.u0 = c.u0; ch.n = c.n; ch.ns = so[(size_t)c.n]; ch.na = ao[(size_t)c.n];
-    if ((rc = lat_chunk_alloc(&ch, &res->bytes))) return rc;
-    res->chunks.push_back(ch);
+    if ((rc = launch(ctx, "k2_lattice_prune_mark", k2_lattice_prune_mark, dim3((unsigned)c.n), dim3(LO_NT), (size_t)p.lds_bytes, p)) ||
+        (rc = size_out_chunk(ctx, "khg_lattices_prune", "k2_lattice_prune_scan", p.utt_tot, p.utt_off, c.u0, c.n, res.get(), &ch)))      // the one synchronisation that sizes the output
+      return rc;
     lat_chunk_arrays(ch, &p.out);
-    {
-      KernelTimer kt(ctx, "k2_lattice_prune_fill");
-      KHG_LAUNCH(ctx, k2_lattice_prune_fill, dim3((unsigned)c.n, stripes(chunk_max(l->state_off, c), LO_NT, c.n)), dim3(LO_NT), 0, ctx->stream, p);
-      HIPCHK(hipGetLastError());
-    }
+    if ((rc = launch(ctx, "k2_lattice_prune_fill", k2_lattice_prune_fill, dim3((unsigned)c.n, stripes(chunk_max(l->state_off, c), LO_NT, c.n)), dim3(LO_NT), 0, p)))
+      return rc;
   }
-  std::vector<int32_t> st((size_t)U);
-  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  rc = check_err_flag(ctx, "khg_lattices_prune");     // synchronises: the scratch goes with `dv`
-  if (rc) return rc;
+  std::vector<int32_t> st;
+  if ((rc = download(ctx, status_d, U, &st)) || (rc = check_err_flag(ctx, "khg_lattices_prune"))) return rc;     // synchronises: the scratch goes with `dv`
   if (status_h) std::copy(st.begin(), st.end(), status_h);
   *out = res.release();
   return KHG_OK;
@@ -1049,12 +1088,9 @@ int lat_index(khg_ctx* ctx, khg_lattices* l) {
     if (!rc) rc = dv.alloc(std::max<int64_t>(c.ns, 1), &cur);
     if (rc) return rc;
     const LatIndex ix = lat_index_arrays(blk, c);
-    LoArgs p;
-    std::memset(&p, 0, sizeof(p));
+    LoArgs p{};
     lat_chunk_args(l, c, &p);
-    KernelTimer kt(ctx, "k2_lattice_post_index");
-    KHG_LAUNCH(ctx, k2_lattice_post_index, dim3((unsigned)c.n), dim3(64), 0, ctx->stream, p, ix.in_begin, ix.in_arc, ix.arc_src, cur);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch(ctx, "k2_lattice_post_index", k2_lattice_post_index, dim3((unsigned)c.n), dim3(64), 0, p, ix.in_begin, ix.in_arc, ix.arc_src, cur))) return rc;
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));       // the cursors go with `dv`
   return KHG_OK;
@@ -1121,9 +1157,8 @@ struct PostRun {
 int post_run_begin(PostRun& r) {
   const int U = r.l->U;
   int rc;
-  if ((rc = r.dv.alloc(U, &r.status_d)) || (rc = r.dv.alloc(U, &r.tot_d)) || (rc = r.dv.alloc(U + 1, &r.ali_off_d))) return rc;
-  HIPCHK(hipMemcpyAsync(r.ali_off_d, r.l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, r.ctx->stream));
-  return KHG_OK;
+  if ((rc = r.dv.alloc(U, &r.status_d)) || (rc = r.dv.alloc(U, &r.tot_d))) return rc;
+  return r.dv.upload(r.ctx, r.l->ali_off, &r.ali_off_d);
 }
 // chunk k's kernel arguments (*p zeroed by the caller) with the scratch both kernels need, and the result's chunk with its arc_post.
 // per_state: the bytes a kernel keeps in LDS beside every staged state (its doubles: 24 or 40)
@@ -1166,21 +1201,17 @@ int post_chunk_finish(PostRun& r, size_t k, PoArgs* p) {
   if ((rc = post_chunk_alloc(&q, &r.res->bytes))) return rc;
   const PostArrays pa = post_chunk_arrays(q);
   p->entry_begin = pa.entry_begin; p->weight = pa.weight; p->tid = pa.tid;
-  KernelTimer kt(ctx, "k2_lattice_post_fill");
-  KHG_LAUNCH(ctx, k2_lattice_post_fill, dim3((unsigned)c.n, stripes(chunk_max(r.l->arc_off, c), PO_NT, c.n)), dim3(PO_NT), 0, ctx->stream, *p);
-  HIPCHK(hipGetLastError());
-  return KHG_OK;
+  return launch(ctx, "k2_lattice_post_fill", k2_lattice_post_fill, dim3((unsigned)c.n, stripes(chunk_max(r.l->arc_off, c), PO_NT, c.n)), dim3(PO_NT), 0, *p);
 }
 // the statuses and totals back -- and one more double per utterance, extra_d to extra_h, when the caller has one -- and the handle out
 int post_run_finish(PostRun& r, int32_t* status_h, double* tot_like_h, const double* extra_d, double* extra_h, khg_posteriors** out) {
-  const size_t U = (size_t)r.l->U;
-  std::vector<int32_t> st(U);
-  std::vector<double> tl(U), ex(extra_d ? U : 0);
-  HIPCHK(hipMemcpyAsync(st.data(), r.status_d, 4 * U, hipMemcpyDeviceToHost, r.ctx->stream));
-  HIPCHK(hipMemcpyAsync(tl.data(), r.tot_d, 8 * U, hipMemcpyDeviceToHost, r.ctx->stream));
-  if (extra_d) HIPCHK(hipMemcpyAsync(ex.data(), extra_d, 8 * U, hipMemcpyDeviceToHost, r.ctx->stream));
-  int rc = check_err_flag(r.ctx, r.who);     // synchronises: the scratch goes with the run
-  if (rc) return rc;
+  const int64_t U = r.l->U;
+  std::vector<int32_t> st;
+  std::vector<double> tl, ex;
+  int rc;
+  if ((rc = download(r.ctx, r.status_d, U, &st)) || (rc = download(r.ctx, r.tot_d, U, &tl)) || (rc = download(r.ctx, extra_d, extra_d ? U : 0, &ex)) ||
+      (rc = check_err_flag(r.ctx, r.who)))     // synchronises: the scratch goes with the run
+    return rc;
   if (status_h) std::copy(st.begin(), st.end(), status_h);
   if (tot_like_h) std::copy(tl.begin(), tl.end(), tot_like_h);
   if (extra_h) std::copy(ex.begin(), ex.end(), extra_h);
@@ -1202,21 +1233,15 @@ extern "C" int khg_lattices_posteriors(khg_ctx* ctx, const khg_lattices* lc, flo
   new_posteriors(ctx, r.l->U, &r.res);
   r.res->arc_off = r.l->arc_off;
   if (r.l->U == 0) { *out = r.res.release(); return KHG_OK; }
-  int rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, r.l);
-  if (!rc) rc = lat_index(ctx, r.l);
+  int rc = lat_ready(ctx, r.l, kWithIndex);
   if (!rc) rc = post_run_begin(r);
   if (rc) return rc;
   for (size_t k = 0; k < r.l->chunks.size(); ++k) {
-    PoArgs p;
-    std::memset(&p, 0, sizeof(p));
-    if ((rc = post_chunk_begin(r, k, 24, &p))) return rc;       // alpha, beta and the Jacobi row (doubles) beside the staged lattice
-    {
-      KernelTimer kt(ctx, "k2_lattice_post_fb");
-      KHG_LAUNCH(ctx, k2_lattice_post_fb, dim3((unsigned)r.l->chunks[k].n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, p);
-      HIPCHK(hipGetLastError());
-    }
-    if ((rc = post_chunk_finish(r, k, &p))) return rc;
+    PoArgs p{};
+    if ((rc = post_chunk_begin(r, k, 24, &p)) ||       // alpha, beta and the Jacobi row (doubles) beside the staged lattice
+        (rc = launch(ctx, "k2_lattice_post_fb", k2_lattice_post_fb, dim3((unsigned)r.l->chunks[k].n), dim3(PO_NT), (size_t)p.lo.lds_bytes, p)) ||
+        (rc = post_chunk_finish(r, k, &p)))
+      return rc;
   }
   return post_run_finish(r, status_h, tot_like_h, nullptr, nullptr, out);
 }
@@ -1229,13 +1254,10 @@ extern "C" int khg_posteriors_validate(int32_t n_utt, const int64_t* frame_off_h
   const std::string who = "khg_posteriors_validate: ";
   if (n_utt < 0 || !frame_off_h || !entry_begin_h || n_entries < 0 || (n_entries > 0 && (!tid_h || !weight_h)))
     return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  if (frame_off_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "frame_off must start at 0");
-  for (int u = 0; u < n_utt; ++u)
-    if (frame_off_h[u + 1] < frame_off_h[u]) return khg_set_error(KHG_E_ARG, who + "frame_off decreases at utterance " + std::to_string(u));
+  int rc = check_offsets("khg_posteriors_validate", "frame_off", frame_off_h, n_utt, "utterance");
+  if (rc) return rc;
   const int64_t F = frame_off_h[n_utt];
-  if (entry_begin_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "entry_begin must start at 0");
-  for (int64_t f = 0; f < F; ++f)
-    if (entry_begin_h[f + 1] < entry_begin_h[f]) return khg_set_error(KHG_E_ARG, who + "entry_begin decreases at frame " + std::to_string(f));
+  if ((rc = check_offsets("khg_posteriors_validate", "entry_begin", entry_begin_h, F, "frame"))) return rc;
   if (entry_begin_h[F] != n_entries)
     return khg_set_error(KHG_E_ARG, who + "entry_begin ends at " + std::to_string(entry_begin_h[F]) + ", the entries number " + std::to_string(n_entries));
   for (int64_t e = 0; e < n_entries; ++e) {
@@ -1249,11 +1271,10 @@ extern "C" int khg_posteriors_upload(khg_ctx* ctx, int32_t n_utt, const int64_t*
   if (ctx_dead(ctx) || !out) return khg_set_error(KHG_E_ARG, "khg_posteriors_upload: bad arguments");
   *out = nullptr;
   if (n_utt < 0 || !frame_off_h || !entry_begin_h || frame_off_h[0] != 0) return khg_set_error(KHG_E_ARG, "khg_posteriors_upload: bad arguments");
-  for (int u = 0; u < n_utt; ++u)        // (entry_begin's length comes from frame_off: checked before it is read)
-    if (frame_off_h[u + 1] < frame_off_h[u]) return khg_set_error(KHG_E_ARG, "khg_posteriors_upload: frame_off decreases at utterance " + std::to_string(u));
-  const int64_t F = frame_off_h[n_utt], E = entry_begin_h[F];
-  int rc = khg_posteriors_validate(n_utt, frame_off_h, entry_begin_h, E, tid_h, weight_h);
+  int rc = check_offsets("khg_posteriors_upload", "frame_off", frame_off_h, n_utt, "utterance");      // (entry_begin's length comes from frame_off: checked before it is read)
   if (rc) return rc;
+  const int64_t F = frame_off_h[n_utt], E = entry_begin_h[F];
+  if ((rc = khg_posteriors_validate(n_utt, frame_off_h, entry_begin_h, E, tid_h, weight_h))) return rc;
   PostPtr res;
   new_posteriors(ctx, n_utt, &res);
   res->frame_off.assign(frame_off_h, frame_off_h + n_utt + 1);
@@ -1452,11 +1473,11 @@ extern "C" int khg_lattices_op_status(const khg_lattices* l, int32_t* status_h) 
 
 extern "C" int khg_lattices_rescore(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utts* u, const khg_lattices* lc, float acoustic_scale,
                                     int mode, khg_rescore_stats* stats, khg_lattices** out) {
-  const std::string who = "khg_lattices_rescore: ";
+  const std::string name = "khg_lattices_rescore", who = name + ": ";      // (helpers take the name, the texts written here the prefix)
   if (ctx_dead(ctx) || !m || !tm || !u || !lc || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
   *out = nullptr;
-  { int rf = utts_foreign_ctx(ctx, u, "khg_lattices_rescore"); if (rf) return rf; }
-  if (m->ctx != ctx || tm->ctx != ctx || u->ctx != ctx || lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  { int rf = utts_foreign_ctx(ctx, u, name.c_str()); if (rf) return rf; }
+  if (m->ctx != ctx || tm->ctx != ctx || u->ctx != ctx || lc->ctx != ctx) return other_ctx(name);
   if (mode != KHG_RESCORE_CELLS && mode != KHG_RESCORE_FROM_LL) return khg_set_error(KHG_E_ARG, who + "unknown mode " + std::to_string(mode));
   if (!std::isfinite(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "acoustic_scale must be finite");
   khg_lattices* l = const_cast<khg_lattices*>(lc);
@@ -1470,8 +1491,7 @@ extern "C" int khg_lattices_rescore(khg_ctx* ctx, const khg_model* m, const khg_
   }
   const int64_t NA = l->arc_off[(size_t)U];
   if (NA >= (int64_t)INT_MAX || u->N >= (int64_t)INT_MAX) return khg_set_error(KHG_E_UNSUPPORTED, who + "2^31 - 1 or more arcs or frames");
-  int rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
+  int rc = lat_ready(ctx, l);
   if (rc) return rc;
   for (int i = 0; i < U; ++i) {
     if (l->state_off[(size_t)i + 1] == l->state_off[(size_t)i]) continue;
@@ -1486,10 +1506,8 @@ extern "C" int khg_lattices_rescore(khg_ctx* ctx, const khg_model* m, const khg_
   if (mode == KHG_RESCORE_FROM_LL && NA > 0) {
     if ((rc = wait_ali(ctx, u))) return rc;
     int32_t* flag_d;
-    if ((rc = dv.alloc(U, &flag_d))) return rc;
-    HIPCHK(hipMemsetAsync(flag_d, 0, 4 * (size_t)U, ctx->stream));
-    K2xLl p;
-    std::memset(&p, 0, sizeof(p));
+    if ((rc = dv.zeroed(ctx, U, &flag_d))) return rc;
+    K2xLl p{};
     p.set_frame_off = u->frame_off_d; p.pdf_off = u->pdf_off_d; p.ll_off = u->ll_off_d; p.pdfs = u->pdfs_d; p.ll = u->ll_d;
     p.id2pdf = tm->id2pdf_d; p.num_tids = tm->num_tids; p.scale = acoustic_scale; p.flag = flag_d; p.err_flag = ctx->err_flag_d;
     {
@@ -1501,9 +1519,8 @@ extern "C" int khg_lattices_rescore(khg_ctx* ctx, const khg_model* m, const khg_
         HIPCHK(hipGetLastError());
       }
     }
-    std::vector<int32_t> flag((size_t)U);
-    HIPCHK(hipMemcpyAsync(flag.data(), flag_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = check_err_flag(ctx, "khg_lattices_rescore"))) return rc;      // synchronises
+    std::vector<int32_t> flag;
+    if ((rc = download(ctx, flag_d, U, &flag)) || (rc = check_err_flag(ctx, name.c_str()))) return rc;      // synchronises
     for (int i = 0; i < U; ++i) drop[(size_t)i] = flag[(size_t)i] != 0;
     if ((rc = lat_clone(ctx, l, drop, &res)) || (rc = lat_meta(ctx, res.get()))) return rc;
     KernelTimer kt(ctx, "k2x_ll_gather");
@@ -1521,8 +1538,7 @@ extern "C" int khg_lattices_rescore(khg_ctx* ctx, const khg_model* m, const khg_
   std::vector<float*> acp;
   if (mode == KHG_RESCORE_CELLS && NA > 0) {
     if ((rc = lat_meta(ctx, res.get())) || (rc = k1_cells_scratch(u, NA, m->P)) || (rc = arena_flush(ctx))) return rc;
-    K2xFlat f;
-    std::memset(&f, 0, sizeof(f));
+    K2xFlat f{};
     f.set_frame_off = u->frame_off_d; f.id2pdf = tm->id2pdf_d; f.num_tids = tm->num_tids; f.P = m->P;
     f.keys = u->rc_keys_d; f.vals = u->rc_vals_d; f.err_flag = ctx->err_flag_d;
     {
@@ -1541,9 +1557,7 @@ extern "C" int khg_lattices_rescore(khg_ctx* ctx, const khg_model* m, const khg_
     base.push_back(NA);
     K1cTargets tg;
     int64_t* base_d; float** acp_d;
-    if ((rc = dv.alloc((int64_t)base.size(), &base_d)) || (rc = dv.alloc((int64_t)acp.size(), &acp_d))) return rc;
-    HIPCHK(hipMemcpyAsync(base_d, base.data(), 8 * base.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(acp_d, acp.data(), sizeof(float*) * acp.size(), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = dv.upload(ctx, base, &base_d)) || (rc = dv.upload(ctx, acp, &acp_d))) return rc;
     tg.base = base_d; tg.ac = acp_d; tg.n = (int32_t)acp.size();
     if ((rc = k1_cells_run(ctx, m, u, NA, acoustic_scale, tg, st))) return rc;
   }
@@ -1566,22 +1580,22 @@ struct LatRef {
   std::vector<char> drop;
 };
 // the host-only checks: every refusal is KHG_E_ARG before any launch.  cls_h[t] is the class of transition-id t (boost, MPFE: its phone)
-int lat_ref_check(const std::string& who, khg_ctx* ctx, const khg_lattices* l, int32_t num_tids, const int32_t* cls_h, const int32_t* tid2phone_h, int32_t n_sil,
+int lat_ref_check(const std::string& name, khg_ctx* ctx, const khg_lattices* l, int32_t num_tids, const int32_t* cls_h, const int32_t* tid2phone_h, int32_t n_sil,
                   const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set, LatRef* r) {
+  const std::string who = name + ": ";
   const bool host_ali = ali_off_h && ali_h;
   if ((ali_off_h != nullptr) != (ali_h != nullptr) || host_ali == (ali_set != nullptr))
     return khg_set_error(KHG_E_ARG, who + "give either the host alignment (ali_off_h and ali_h) or ali_set, not both and not neither");
   const int U = l->U;
   khg_utts* as = const_cast<khg_utts*>(ali_set);
   if (as) {
-    { int rf = utts_foreign_ctx(ctx, as, who.substr(0, who.size() - 2).c_str()); if (rf) return rf; }
-    if (as->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+    { int rf = utts_foreign_ctx(ctx, as, name.c_str()); if (rf) return rf; }
+    if (as->ctx != ctx) return other_ctx(name);
     if (as->n_utt != U) return khg_set_error(KHG_E_ARG, who + "the lattices hold " + std::to_string(U) + " utterances, ali_set " + std::to_string(as->n_utt));
     if (!as->ali_valid) return khg_set_error(KHG_E_ARG, who + "ali_set has no resident alignment: call khg_align (or khg_ali_upload) first");
   } else {
-    if (ali_off_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "ali_off_h must start at 0");
-    for (int i = 0; i < U; ++i)
-      if (ali_off_h[i + 1] < ali_off_h[i]) return khg_set_error(KHG_E_ARG, who + "ali_off_h decreases at utterance " + std::to_string(i));
+    int rc = check_offsets(name, "ali_off_h", ali_off_h, U, "utterance");
+    if (rc) return rc;
   }
   // the class map and the silence set as one table: 2 * class + (silence)
   r->tab.assign((size_t)num_tids + 1, 0);
@@ -1600,17 +1614,14 @@ int lat_ref_check(const std::string& who, khg_ctx* ctx, const khg_lattices* l, i
   return KHG_OK;
 }
 // the device half (U > 0, after lat_meta): the table and the alignment on the device, the ids and the lattices' labels checked there
-int lat_ref_device(const std::string& who, khg_ctx* ctx, khg_lattices* l, int32_t num_tids, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set,
+int lat_ref_device(const std::string& name, khg_ctx* ctx, khg_lattices* l, int32_t num_tids, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set,
                    LatRef* r) {
   const int U = l->U;
   khg_utts* as = const_cast<khg_utts*>(ali_set);
-  const std::string name = who.substr(0, who.size() - 2);
   int rc = as ? wait_ali(ctx, as) : KHG_OK;
   if (rc) return rc;
   int32_t* flag_d;
-  if ((rc = r->dv.alloc(U + 1, &flag_d)) || (rc = r->dv.alloc((int64_t)r->tab.size(), &r->tab_d))) return rc;      // [U]: the label word
-  HIPCHK(hipMemsetAsync(flag_d, 0, 4 * ((size_t)U + 1), ctx->stream));
-  HIPCHK(hipMemcpyAsync(r->tab_d, r->tab.data(), 4 * r->tab.size(), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = r->dv.zeroed(ctx, U + 1, &flag_d)) || (rc = r->dv.upload(ctx, r->tab, &r->tab_d))) return rc;      // [U]: the label word
   // what the host knows: the alignment's length against the lattice's frame count (and, of a host alignment, its ids)
   for (int i = 0; i < U; ++i) {
     const int64_t tl = l->ali_off[(size_t)i + 1] - l->ali_off[(size_t)i];
@@ -1622,15 +1633,10 @@ int lat_ref_device(const std::string& who, khg_ctx* ctx, khg_lattices* l, int32_
   }
   if (as) {
     r->ali_d = as->ali_d; r->aoff_d = as->frame_off_d;
-    KernelTimer kt(ctx, "k2x_ali_check");
-    KHG_LAUNCH(ctx, k2x_ali_check, dim3((unsigned)U), dim3(K2X_NT), 0, ctx->stream, r->ali_d, r->aoff_d, num_tids, flag_d);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch(ctx, "k2x_ali_check", k2x_ali_check, dim3((unsigned)U), dim3(K2X_NT), 0, r->ali_d, r->aoff_d, num_tids, flag_d))) return rc;
   } else {
     int32_t* a_d; int64_t* o_d;
-    const int64_t n = ali_off_h[U];
-    if ((rc = r->dv.alloc(std::max<int64_t>(n, 1), &a_d)) || (rc = r->dv.alloc(U + 1, &o_d))) return rc;
-    if (n > 0) HIPCHK(hipMemcpyAsync(a_d, ali_h, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(o_d, ali_off_h, 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = r->dv.upload(ctx, ali_h, ali_off_h[U], &a_d)) || (rc = r->dv.upload(ctx, ali_off_h, U + 1, &o_d))) return rc;
     r->ali_d = a_d; r->aoff_d = o_d;
   }
   {
@@ -1643,10 +1649,9 @@ int lat_ref_device(const std::string& who, khg_ctx* ctx, khg_lattices* l, int32_
       HIPCHK(hipGetLastError());
     }
   }
-  std::vector<int32_t> flag((size_t)U + 1);
-  HIPCHK(hipMemcpyAsync(flag.data(), flag_d, 4 * ((size_t)U + 1), hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = check_err_flag(ctx, name.c_str()))) return rc;      // synchronises (the caller's arrays are free again)
-  if (flag[(size_t)U]) return khg_set_error(KHG_E_ARG, who + "a lattice arc carries an ilabel outside 0 .. num_tids = " + std::to_string(num_tids));
+  std::vector<int32_t> flag;
+  if ((rc = download(ctx, flag_d, U + 1, &flag)) || (rc = check_err_flag(ctx, name.c_str()))) return rc;      // synchronises (the caller's arrays are free again)
+  if (flag[(size_t)U]) return khg_set_error(KHG_E_ARG, name + ": a lattice arc carries an ilabel outside 0 .. num_tids = " + std::to_string(num_tids));
   for (int i = 0; i < U; ++i) r->drop[(size_t)i] = r->drop[(size_t)i] || flag[(size_t)i] != 0;
   return KHG_OK;
 }
@@ -1655,16 +1660,16 @@ int lat_ref_device(const std::string& who, khg_ctx* ctx, khg_lattices* l, int32_
 extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t num_tids, const int32_t* tid2phone_h, int32_t n_sil,
                                   const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h, const khg_utts* ali_set, float b,
                                   float max_silence_error, int32_t* status_h, khg_lattices** out) {
-  const std::string who = "khg_lattices_boost: ";
+  const std::string name = "khg_lattices_boost", who = name + ": ";
   if (ctx_dead(ctx) || !lc || !out || num_tids < 0 || !tid2phone_h || n_sil < 0 || (n_sil > 0 && !silence_phones_h))
     return khg_set_error(KHG_E_ARG, who + "bad arguments");
   *out = nullptr;
-  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (lc->ctx != ctx) return other_ctx(name);
   if (!std::isfinite(b) || !std::isfinite(max_silence_error)) return khg_set_error(KHG_E_ARG, who + "b and max_silence_error must be finite");
   khg_lattices* l = const_cast<khg_lattices*>(lc);
   const int U = l->U;
   LatRef ref;
-  int rc = lat_ref_check(who, ctx, l, num_tids, tid2phone_h, tid2phone_h, n_sil, silence_phones_h, ali_off_h, ali_h, ali_set, &ref);
+  int rc = lat_ref_check(name, ctx, l, num_tids, tid2phone_h, tid2phone_h, n_sil, silence_phones_h, ali_off_h, ali_h, ali_set, &ref);
   if (rc) return rc;
   LatPtr res;
   if (U == 0) {
@@ -1672,13 +1677,10 @@ extern "C" int khg_lattices_boost(khg_ctx* ctx, const khg_lattices* lc, int32_t 
     *out = res.release();
     return KHG_OK;
   }
-  rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (!rc) rc = lat_ref_device(who, ctx, l, num_tids, ali_off_h, ali_h, ali_set, &ref);
-  if (rc) return rc;
-  if ((rc = lat_clone(ctx, l, ref.drop, &res)) || (rc = lat_meta(ctx, res.get()))) return rc;
-  K2xBoost p;
-  std::memset(&p, 0, sizeof(p));
+  if ((rc = lat_ready(ctx, l)) || (rc = lat_ref_device(name, ctx, l, num_tids, ali_off_h, ali_h, ali_set, &ref)) ||
+      (rc = lat_clone(ctx, l, ref.drop, &res)) || (rc = lat_meta(ctx, res.get())))
+    return rc;
+  K2xBoost p{};
   p.ali = ref.ali_d; p.ali_off = ref.aoff_d; p.tab = ref.tab_d; p.neg_b = -b; p.max_sil_err = max_silence_error;
   {
     KernelTimer kt(ctx, "k2x_boost");
@@ -1703,11 +1705,11 @@ extern "C" int khg_lattices_mpe_posteriors(khg_ctx* ctx, const khg_lattices* lc,
                                            int32_t n_sil, const int32_t* silence_phones_h, const int64_t* ali_off_h, const int32_t* ali_h,
                                            const khg_utts* ali_set, int32_t criterion, int32_t one_silence_class, float graph_scale, float acoustic_scale,
                                            int32_t* status_h, double* tot_like_h, double* avg_acc_h, khg_posteriors** out) {
-  const std::string who = "khg_lattices_mpe_posteriors: ";
+  const std::string name = "khg_lattices_mpe_posteriors", who = name + ": ";
   if (ctx_dead(ctx) || !lc || !out || num_tids < 0 || !tid2phone_h || n_sil < 0 || (n_sil > 0 && !silence_phones_h))
     return khg_set_error(KHG_E_ARG, who + "bad arguments");
   *out = nullptr;
-  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (lc->ctx != ctx) return other_ctx(name);
   if (criterion != KHG_MPE_MPFE && criterion != KHG_MPE_SMBR) return khg_set_error(KHG_E_ARG, who + "unknown criterion " + std::to_string(criterion));
   if (criterion == KHG_MPE_SMBR && !tid2pdf_h) return khg_set_error(KHG_E_ARG, who + "KHG_MPE_SMBR needs tid2pdf_h");
   if (bad_scale(graph_scale) || bad_scale(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "graph_scale and acoustic_scale must be finite and >= 0");
@@ -1717,36 +1719,29 @@ extern "C" int khg_lattices_mpe_posteriors(khg_ctx* ctx, const khg_lattices* lc,
   khg_lattices* l = r.l;
   const int U = l->U;
   LatRef ref;
-  int rc = lat_ref_check(who, ctx, l, num_tids, criterion == KHG_MPE_SMBR ? tid2pdf_h : tid2phone_h, tid2phone_h, n_sil, silence_phones_h, ali_off_h, ali_h,
+  int rc = lat_ref_check(name, ctx, l, num_tids, criterion == KHG_MPE_SMBR ? tid2pdf_h : tid2phone_h, tid2phone_h, n_sil, silence_phones_h, ali_off_h, ali_h,
                          ali_set, &ref);
   if (rc) return rc;
   new_posteriors(ctx, U, &r.res);
   r.res->arc_off = l->arc_off;
   if (U == 0) { *out = r.res.release(); return KHG_OK; }
-  rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (!rc) rc = lat_ref_device(who, ctx, l, num_tids, ali_off_h, ali_h, ali_set, &ref);
-  if (!rc) rc = lat_index(ctx, l);
-  if (!rc) rc = post_run_begin(r);
-  if (rc) return rc;
+  // (the in-arc index after the reference's checks: the order of the launches)
+  if ((rc = lat_ready(ctx, l)) || (rc = lat_ref_device(name, ctx, l, num_tids, ali_off_h, ali_h, ali_set, &ref)) || (rc = lat_index(ctx, l)) ||
+      (rc = post_run_begin(r)))
+    return rc;
   int32_t* no_ref_d; double* avg_d;
-  if ((rc = r.dv.alloc(U, &avg_d)) || (rc = r.dv.alloc(U, &no_ref_d))) return rc;
-  std::vector<int32_t> no_ref(ref.drop.begin(), ref.drop.end());
-  HIPCHK(hipMemcpyAsync(no_ref_d, no_ref.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+  const std::vector<int32_t> no_ref(ref.drop.begin(), ref.drop.end());
+  if ((rc = r.dv.alloc(U, &avg_d)) || (rc = r.dv.upload(ctx, no_ref, &no_ref_d))) return rc;
   for (size_t k = 0; k < l->chunks.size(); ++k) {
     const LatChunk& c = l->chunks[k];
-    PoMpeArgs q;
-    std::memset(&q, 0, sizeof(q));
+    PoMpeArgs q{};
     if ((rc = post_chunk_begin(r, k, 40, &q.po))) return rc;       // alpha, beta, the Jacobi row, A and B (doubles) beside the staged lattice
     q.ref = ref.ali_d; q.ref_off = ref.aoff_d; q.tab = ref.tab_d; q.no_ref = no_ref_d; q.avg = avg_d; q.one_silence_class = one_silence_class != 0;
     const int64_t cells = std::max<int64_t>(c.ns, 1);
-    if ((rc = r.dv.alloc(cells, &q.accA)) || (rc = r.dv.alloc(cells, &q.accB))) return rc;
-    {
-      KernelTimer kt(ctx, "k2_lattice_post_mpe");
-      KHG_LAUNCH(ctx, k2_lattice_post_mpe, dim3((unsigned)c.n), dim3(PO_NT), (size_t)q.po.lo.lds_bytes, ctx->stream, q);
-      HIPCHK(hipGetLastError());
-    }
-    if ((rc = post_chunk_finish(r, k, &q.po))) return rc;       // the fill sums arc_post: here the signed values
+    if ((rc = r.dv.alloc(cells, &q.accA)) || (rc = r.dv.alloc(cells, &q.accB)) ||
+        (rc = launch(ctx, "k2_lattice_post_mpe", k2_lattice_post_mpe, dim3((unsigned)c.n), dim3(PO_NT), (size_t)q.po.lo.lds_bytes, q)) ||
+        (rc = post_chunk_finish(r, k, &q.po)))       // the fill sums arc_post: here the signed values
+      return rc;
   }
   return post_run_finish(r, status_h, tot_like_h, avg_d, avg_acc_h, out);       // synchronises: the scratch goes with `r` and `ref`
 }
@@ -1860,10 +1855,10 @@ extern "C" int khg_lm_create(khg_ctx* ctx, int32_t n_states, const int32_t* back
 
 extern "C" int khg_lattices_lm_rescore(khg_ctx* ctx, const khg_lattices* lc, const khg_lm* lm, float scale, int32_t hist_factor, int32_t* status_h,
                                        khg_lm_rescore_stats* stats, khg_lattices** out) {
-  const std::string who = "khg_lattices_lm_rescore: ";
+  const std::string name = "khg_lattices_lm_rescore", who = name + ": ";
   if (ctx_dead(ctx) || !lc || !lm || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
   *out = nullptr;
-  if (lc->ctx != ctx || lm->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (lc->ctx != ctx || lm->ctx != ctx) return other_ctx(name);
   if (!std::isfinite(scale)) return khg_set_error(KHG_E_ARG, who + "scale must be finite");
   if (hist_factor < 1) return khg_set_error(KHG_E_ARG, who + "hist_factor must be >= 1");
   khg_lattices* l = const_cast<khg_lattices*>(lc);
@@ -1873,18 +1868,13 @@ extern "C" int khg_lattices_lm_rescore(khg_ctx* ctx, const khg_lattices* lc, con
   if (rc) return rc;
   if (stats) *stats = khg_lm_rescore_stats{0, 0, 0, 0, 0};
   if (U == 0) { *out = res.release(); return KHG_OK; }
-  rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (!rc) rc = lat_index(ctx, l);
-  if (rc) return rc;
+  if ((rc = lat_ready(ctx, l, kWithIndex))) return rc;
   DevBlocks dv;
   int32_t *status_d, *maxh_d;
   if ((rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &maxh_d))) return rc;
-  std::vector<int64_t> so, ao;
   for (size_t k = 0; k < l->chunks.size(); ++k) {
     const LatChunk& c = l->chunks[k];
-    LmArgs p;
-    std::memset(&p, 0, sizeof(p));
+    LmArgs p{};
     lat_chunk_args(l, c, &p.lo);
     p.lo.status = status_d; p.lo.o_start = res->start_d;
     p.lm = lm->dev; p.scale = scale; p.hist_factor = hist_factor; p.max_hist = maxh_d;
@@ -1895,30 +1885,16 @@ extern "C" int khg_lattices_lm_rescore(khg_ctx* ctx, const khg_lattices* lc, con
         (rc = dv.alloc(cells + c.n, &p.set_off)) || (rc = dv.alloc(cells, &p.arc_base)) || (rc = dv.alloc(2 * (int64_t)c.n, &p.lo.utt_tot)) ||
         (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.lo.utt_off)))
       return rc;
-    {
-      KernelTimer kt(ctx, "k2_lattice_lm_mark");
-      KHG_LAUNCH(ctx, k2_lattice_lm_mark, dim3((unsigned)c.n), dim3(LM_NT), 0, ctx->stream, p);
-      HIPCHK(hipGetLastError());
-    }
-    rc = scan_pairs_and_read(ctx, "k2_lattice_lm_scan", p.lo.utt_tot, p.lo.utt_off, c.n, &so, &ao);      // the one synchronisation that sizes the output
-    if (!rc) rc = add_chunk_counts("khg_lattices_lm_rescore", c.u0, so, ao, &res->state_off, &res->arc_off);
-    if (rc) return rc;
     LatChunk ch;
-    ch.u0 = c.u0; ch.n = c.n; ch.ns = so[(size_t)c.n]; ch.na = ao[(size_t)c.n];
-    if ((rc = lat_chunk_alloc(&ch, &res->bytes))) return rc;
-    res->chunks.push_back(ch);
+    if ((rc = launch(ctx, "k2_lattice_lm_mark", k2_lattice_lm_mark, dim3((unsigned)c.n), dim3(LM_NT), 0, p)) ||
+        (rc = size_out_chunk(ctx, name, "k2_lattice_lm_scan", p.lo.utt_tot, p.lo.utt_off, c.u0, c.n, res.get(), &ch)))      // the one synchronisation that sizes the output
+      return rc;
     lat_chunk_arrays(ch, &p.lo.out);
-    {
-      KernelTimer kt(ctx, "k2_lattice_lm_fill");
-      KHG_LAUNCH(ctx, k2_lattice_lm_fill, dim3((unsigned)c.n, stripes(chunk_max(res->state_off, c), LM_NT, c.n)), dim3(LM_NT), 0, ctx->stream, p);
-      HIPCHK(hipGetLastError());
-    }
+    if ((rc = launch(ctx, "k2_lattice_lm_fill", k2_lattice_lm_fill, dim3((unsigned)c.n, stripes(chunk_max(res->state_off, c), LM_NT, c.n)), dim3(LM_NT), 0, p)))
+      return rc;
   }
-  std::vector<int32_t> st((size_t)U), mh((size_t)U);
-  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(mh.data(), maxh_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  rc = check_err_flag(ctx, "khg_lattices_lm_rescore");     // synchronises: the scratch goes with `dv`
-  if (rc) return rc;
+  std::vector<int32_t> st, mh;
+  if ((rc = download(ctx, status_d, U, &st)) || (rc = download(ctx, maxh_d, U, &mh)) || (rc = check_err_flag(ctx, name.c_str()))) return rc;     // synchronises: the scratch goes with `dv`
   res->op_status = st;
   if (status_h) std::copy(st.begin(), st.end(), status_h);
   if (stats) {
@@ -1953,24 +1929,22 @@ int lat_width(khg_ctx* ctx, khg_lattices* l) {
   l->width_d = w_d;
   l->bytes += 4 * (int64_t)U;
   for (const LatChunk& c : l->chunks) {
-    LoArgs p;
-    std::memset(&p, 0, sizeof(p));
+    LoArgs p{};
     lat_chunk_args(l, c, &p);
     KHG_LAUNCH(ctx, k2_lattice_score_width, dim3((unsigned)((c.n + 63) / 64)), dim3(64), 0, ctx->stream, p, w_d);
     HIPCHK(hipGetLastError());
   }
-  l->width.assign(U, 0);
-  HIPCHK(hipMemcpyAsync(l->width.data(), w_d, 4 * U, hipMemcpyDeviceToHost, ctx->stream));
+  int rc = download(ctx, w_d, (int64_t)U, &l->width);
+  if (rc) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return KHG_OK;
 }
 // the references of a scoring call: n_utt is the handle's, offsets from 0 and monotone, words > 0
-int score_ref_check(const std::string& who, const khg_lattices* l, int32_t n_utt, const int32_t* ref_h, const int64_t* ref_off_h) {
+int score_ref_check(const std::string& name, const khg_lattices* l, int32_t n_utt, const int32_t* ref_h, const int64_t* ref_off_h) {
+  const std::string who = name + ": ";
   if (n_utt != l->U) return khg_set_error(KHG_E_ARG, who + "the lattices hold " + std::to_string(l->U) + " utterances, the references " + std::to_string(n_utt));
-  if (!ref_off_h || ref_off_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "ref_off_h must start at 0");
-  for (int u = 0; u < n_utt; ++u)
-    if (ref_off_h[u + 1] < ref_off_h[u]) return khg_set_error(KHG_E_ARG, who + "ref_off_h decreases at utterance " + std::to_string(u));
-  if (ref_off_h[n_utt] > 0 && !ref_h) return khg_set_error(KHG_E_ARG, who + "ref_h is NULL");
+  int rc = check_offsets(name, "ref_off_h", ref_off_h, n_utt, "utterance", ref_h, "ref_h");
+  if (rc) return rc;
   for (int u = 0; u < n_utt; ++u) {
     for (int64_t i = ref_off_h[u]; i < ref_off_h[u + 1]; ++i)
       if (ref_h[i] <= 0) return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(u) + ": a reference word is not > 0");
@@ -1981,20 +1955,49 @@ int score_ref_check(const std::string& who, const khg_lattices* l, int32_t n_utt
 }
 // the references on the device
 int score_ref_upload(khg_ctx* ctx, int U, const int32_t* ref_h, const int64_t* ref_off_h, DevBlocks* dv, int32_t** ref_d, int64_t** ref_off_d) {
-  const int64_t n = ref_off_h[U];
-  int rc;
-  if ((rc = dv->alloc(std::max<int64_t>(n, 1), ref_d)) || (rc = dv->alloc(U + 1, ref_off_d))) return rc;
-  if (n > 0) HIPCHK(hipMemcpyAsync(*ref_d, ref_h, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(*ref_off_d, ref_off_h, 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
-  return KHG_OK;
+  int rc = dv->upload(ctx, ref_h, ref_off_h[U], ref_d);
+  return rc ? rc : dv->upload(ctx, ref_off_h, U + 1, ref_off_d);
+}
+// Utterances whose tables share one scratch block, a launch at a time (khg_lattices_oracle, khg_lattices_mbr): a launch runs the n
+// utterances list[first .. first + n) of chunk `chunk`; the table of list[j] starts tab_off[j] cells into the block; the launch's
+// tables are `cells` together, the largest launch's max_cells.
+struct TableLaunch { size_t chunk, first, n; int64_t cells; };
+struct TableLaunches {
+  std::vector<int32_t> list;
+  std::vector<int64_t> tab_off;
+  std::vector<TableLaunch> launches;
+  int64_t max_cells = 1;
+};
+// Chunk by chunk, the utterances that run -- cells_of(u), called once per utterance in order: the cells of u's table, or < 0 when u does
+// not run (no path, or a table that alone is over the budget: the caller's status) -- grouped into launches whose tables, cell_bytes
+// a cell, fit `budget` bytes together.  (The decoders group scratch SLICES of a whole batch, by bytes and without skipping:
+// split_by_budget.)
+template <class F>
+TableLaunches group_tables(const std::vector<LatChunk>& chunks, int64_t cell_bytes, int64_t budget, F cells_of) {
+  TableLaunches g;
+  for (size_t k = 0; k < chunks.size(); ++k) {
+    const LatChunk& c = chunks[k];
+    TableLaunch cur{k, g.list.size(), 0, 0};
+    for (int u = c.u0; u < c.u0 + c.n; ++u) {
+      const int64_t cells = cells_of(u);
+      if (cells < 0) continue;
+      if (cur.n > 0 && cell_bytes * (cur.cells + cells) > budget) { g.launches.push_back(cur); cur = TableLaunch{k, g.list.size(), 0, 0}; }
+      g.list.push_back(u);
+      g.tab_off.push_back(cur.cells);
+      cur.cells += cells; ++cur.n;
+    }
+    if (cur.n > 0) g.launches.push_back(cur);
+  }
+  for (const TableLaunch& L : g.launches) g.max_cells = std::max(g.max_cells, L.cells);
+  return g;
 }
 }  // namespace
 
 extern "C" int khg_lattices_add_penalty(khg_ctx* ctx, const khg_lattices* lc, float word_ins_penalty, khg_lattices** out) {
-  const std::string who = "khg_lattices_add_penalty: ";
+  const std::string name = "khg_lattices_add_penalty", who = name + ": ";
   if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
   *out = nullptr;
-  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (lc->ctx != ctx) return other_ctx(name);
   if (!std::isfinite(word_ins_penalty)) return khg_set_error(KHG_E_ARG, who + "word_ins_penalty must be finite");
   int rc = arena_flush(ctx);
   if (rc) return rc;
@@ -2009,20 +2012,20 @@ extern "C" int khg_lattices_add_penalty(khg_ctx* ctx, const khg_lattices* lc, fl
       HIPCHK(hipGetLastError());
     }
   }
-  if ((rc = check_err_flag(ctx, "khg_lattices_add_penalty"))) return rc;      // synchronises
+  if ((rc = check_err_flag(ctx, name.c_str()))) return rc;      // synchronises
   *out = res.release();
   return KHG_OK;
 }
 
 extern "C" int khg_lattices_oracle(khg_ctx* ctx, const khg_lattices* lc, int32_t n_utt, const int32_t* ref_h, const int64_t* ref_off_h, int64_t scratch_bytes,
                                    int32_t* counts_h, int32_t* words_h, int64_t* words_off_h, int64_t words_cap, int32_t* ali_h, int32_t* status_h) {
-  const std::string who = "khg_lattices_oracle: ";
+  const std::string name = "khg_lattices_oracle", who = name + ": ";
   if (!lc) return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  int rc = score_ref_check(who, lc, n_utt, ref_h, ref_off_h);
+  int rc = score_ref_check(name, lc, n_utt, ref_h, ref_off_h);
   if (rc) return rc;
   if (scratch_bytes < 0) return khg_set_error(KHG_E_ARG, who + "scratch_bytes must be >= 0");
   if (ctx_dead(ctx)) return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (lc->ctx != ctx) return other_ctx(name);
   khg_lattices* l = const_cast<khg_lattices*>(lc);
   const int U = l->U;
   if (words_off_h) std::fill(words_off_h, words_off_h + U + 1, 0);
@@ -2032,75 +2035,48 @@ extern "C" int khg_lattices_oracle(khg_ctx* ctx, const khg_lattices* lc, int32_t
       return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(u) + ": more than 2^31 - 4 arcs");
   const int64_t budget = scratch_bytes ? scratch_bytes : kScoreScratch;
   int64_t lds_cap = 0;
-  rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (!rc) rc = lat_index(ctx, l);
-  if (!rc) rc = lat_width(ctx, l);
-  if (!rc) rc = score_lds_cap(&lds_cap);
-  if (rc) return rc;
+  if ((rc = lat_ready(ctx, l, kWithIndex | kWithWidth)) || (rc = score_lds_cap(&lds_cap))) return rc;
   const int64_t AT = l->ali_off[(size_t)U];
   DevBlocks dv;
   int32_t *ref_d, *counts_d, *nw_d, *status_d, *ali_d, *list_d, *tab_d;
   int64_t *ref_off_d, *ali_off_d, *tab_off_d;
   // the utterances whose own table fits the budget, chunk by chunk, grouped into launches whose tables fit it together
-  std::vector<int32_t> list;
-  std::vector<int64_t> tab_off;
-  struct Launch { size_t chunk, first, n; int64_t cells, lds; };
-  std::vector<Launch> launches;
   std::vector<char> too_big((size_t)U, 0);
-  int64_t max_cells = 1;
-  for (size_t k = 0; k < l->chunks.size(); ++k) {
-    const LatChunk& c = l->chunks[k];
-    Launch cur{k, list.size(), 0, 0, 0};
-    for (int u = c.u0; u < c.u0 + c.n; ++u) {
-      const int64_t N = l->state_off[(size_t)u + 1] - l->state_off[(size_t)u], W = ref_off_h[u + 1] - ref_off_h[u] + 1;
-      const int64_t cells = 2 * N * W;
-      if (4 * cells > budget) { too_big[(size_t)u] = 1; continue; }
-      if (cur.n > 0 && 4 * (cur.cells + cells) > budget) { launches.push_back(cur); cur = Launch{k, list.size(), 0, 0, 0}; }
-      list.push_back(u);
-      tab_off.push_back(cur.cells);
-      cur.cells += cells; ++cur.n;
-      const int64_t ring = 8 * (int64_t)l->width[(size_t)u] * W;
-      if (ctx->opt[KHG_OPT_LAT_OPS_LDS] != 1 && ring <= lds_cap) cur.lds = std::max(cur.lds, ring);
-    }
-    if (cur.n > 0) launches.push_back(cur);
-  }
-  for (const Launch& L : launches) max_cells = std::max(max_cells, L.cells);
-  const int64_t nl = std::max<int64_t>((int64_t)list.size(), 1);
+  auto row = [&](int u) -> int64_t { return ref_off_h[u + 1] - ref_off_h[u] + 1; };       // the cells of a table's row: the reference and one
+  const TableLaunches g = group_tables(l->chunks, 4, budget, [&](int u) -> int64_t {
+    const int64_t N = l->state_off[(size_t)u + 1] - l->state_off[(size_t)u];
+    const int64_t cells = 2 * N * row(u);
+    if (4 * cells > budget) { too_big[(size_t)u] = 1; return -1; }
+    return cells;
+  });
   if ((rc = score_ref_upload(ctx, U, ref_h, ref_off_h, &dv, &ref_d, &ref_off_d)) || (rc = dv.alloc(4 * (int64_t)U, &counts_d)) || (rc = dv.alloc(U, &nw_d)) ||
-      (rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(std::max<int64_t>(AT, 1), &ali_d)) || (rc = dv.alloc(U + 1, &ali_off_d)) || (rc = dv.alloc(nl, &list_d)) ||
-      (rc = dv.alloc(nl, &tab_off_d)) || (rc = dv.alloc(max_cells, &tab_d)))
+      (rc = dv.zeroed(ctx, std::max<int64_t>(AT, 1), &ali_d)) || (rc = dv.zeroed(ctx, U, &status_d)) || (rc = dv.upload(ctx, l->ali_off, &ali_off_d)) ||
+      (rc = dv.upload(ctx, g.list, &list_d)) || (rc = dv.upload(ctx, g.tab_off, &tab_off_d)) || (rc = dv.alloc(g.max_cells, &tab_d)))
     return rc;
-  HIPCHK(hipMemsetAsync(ali_d, 0, 4 * (size_t)std::max<int64_t>(AT, 1), ctx->stream));
-  HIPCHK(hipMemsetAsync(status_d, 0, 4 * (size_t)U, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ali_off_d, l->ali_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
-  if (!list.empty()) {
-    HIPCHK(hipMemcpyAsync(list_d, list.data(), 4 * list.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(tab_off_d, tab_off.data(), 8 * tab_off.size(), hipMemcpyHostToDevice, ctx->stream));
-  }
   std::vector<int32_t*> words_d(l->chunks.size(), nullptr);
   for (size_t k = 0; k < l->chunks.size(); ++k)
     if ((rc = dv.alloc(std::max<int64_t>(l->chunks[k].ns, 1), &words_d[k]))) return rc;
-  for (const Launch& L : launches) {
+  for (const TableLaunch& L : g.launches) {
     const LatChunk& c = l->chunks[L.chunk];
-    ScArgs p;
-    std::memset(&p, 0, sizeof(p));
+    int64_t lds = 0;       // the ring of rows of the launch's utterances in LDS: the largest that fits
+    for (size_t j = L.first; j < L.first + L.n; ++j) {
+      const int u = g.list[j];
+      const int64_t ring = 8 * (int64_t)l->width[(size_t)u] * row(u);
+      if (ctx->opt[KHG_OPT_LAT_OPS_LDS] != 1 && ring <= lds_cap) lds = std::max(lds, ring);
+    }
+    ScArgs p{};
     lat_chunk_args(l, c, &p.lo);
-    p.lo.lds_bytes = (int32_t)L.lds;
+    p.lo.lds_bytes = (int32_t)lds;
     p.lo.status = status_d; p.lo.ali = ali_d; p.lo.ali_off = ali_off_d; p.lo.ali_total = AT; p.lo.words = words_d[L.chunk];
     const LatIndex ix = lat_index_arrays(l->idx_d[L.chunk], c);
     p.in_begin = ix.in_begin; p.in_arc = ix.in_arc; p.arc_src = ix.arc_src;
     p.list = list_d + L.first; p.tab_off = tab_off_d + L.first; p.tab = tab_d; p.width = l->width_d;
     p.ref = ref_d; p.ref_off = ref_off_d; p.counts = counts_d; p.nwords = nw_d;
-    if (L.lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_lattice_score_oracle, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
-    KernelTimer kt(ctx, "k2_lattice_score_oracle");
-    KHG_LAUNCH(ctx, k2_lattice_score_oracle, dim3((unsigned)L.n), dim3(SC_NT), (size_t)L.lds, ctx->stream, p);
-    HIPCHK(hipGetLastError());
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_lattice_score_oracle, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if ((rc = launch(ctx, "k2_lattice_score_oracle", k2_lattice_score_oracle, dim3((unsigned)L.n), dim3(SC_NT), (size_t)lds, p))) return rc;
   }
-  std::vector<int32_t> counts(4 * (size_t)U), nw((size_t)U), st((size_t)U), words;
-  HIPCHK(hipMemcpyAsync(counts.data(), counts_d, 16 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(nw.data(), nw_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<int32_t> counts, nw, st, words;
+  if ((rc = download(ctx, counts_d, 4 * (int64_t)U, &counts)) || (rc = download(ctx, nw_d, U, &nw)) || (rc = download(ctx, status_d, U, &st))) return rc;
   if (ali_h && AT) HIPCHK(hipMemcpyAsync(ali_h, ali_d, 4 * (size_t)AT, hipMemcpyDeviceToHost, ctx->stream));
   const bool want_words = words_h && words_off_h;
   if (want_words) {
@@ -2110,24 +2086,18 @@ extern "C" int khg_lattices_oracle(khg_ctx* ctx, const khg_lattices* lc, int32_t
       if (c.ns) HIPCHK(hipMemcpyAsync(words.data() + l->state_off[(size_t)c.u0], words_d[k], 4 * (size_t)c.ns, hipMemcpyDeviceToHost, ctx->stream));
     }
   }
-  rc = check_err_flag(ctx, "khg_lattices_oracle");     // synchronises: the scratch goes with `dv`
+  rc = check_err_flag(ctx, name.c_str());     // synchronises: the scratch goes with `dv`
   if (rc) return rc;
-  int64_t o = 0;
   for (int u = 0; u < U; ++u) {
-    if (too_big[(size_t)u]) {
-      const int32_t R = (int32_t)(ref_off_h[u + 1] - ref_off_h[u]);
-      st[(size_t)u] = KHG_LAT_SCRATCH; nw[(size_t)u] = 0;
-      counts[4 * (size_t)u] = R; counts[4 * (size_t)u + 1] = 0; counts[4 * (size_t)u + 2] = R; counts[4 * (size_t)u + 3] = 0;
-    }
-    if (!want_words) continue;
-    words_off_h[u] = o;
-    int64_t n = (st[(size_t)u] & KHG_LAT_SUCCEEDED) ? nw[(size_t)u] : 0;
-    if (o + n > words_cap) { st[(size_t)u] = KHG_LAT_WORDS; n = 0; }      // the path's words do not fit: none of them
-    const int64_t end = l->state_off[(size_t)u + 1];       // (the kernel filled the utterance's slice from its end)
-    std::copy(words.begin() + (end - n), words.begin() + end, words_h + o);
-    o += n;
+    if (!too_big[(size_t)u]) continue;
+    const int32_t R = (int32_t)(ref_off_h[u + 1] - ref_off_h[u]);
+    st[(size_t)u] = KHG_LAT_SCRATCH; nw[(size_t)u] = 0;
+    counts[4 * (size_t)u] = R; counts[4 * (size_t)u + 1] = 0; counts[4 * (size_t)u + 2] = R; counts[4 * (size_t)u + 3] = 0;
   }
-  if (want_words) words_off_h[U] = o;
+  // (a path whose words do not fit: KHG_LAT_WORDS and none of them; the kernel filled an utterance's slice from its end)
+  if (want_words && (rc = pack_words(name, st, &st, [&](size_t u) { return nw[u]; },
+                                     [&](size_t u, int64_t n) { return words.begin() + (l->state_off[u + 1] - n); }, words_h, words_off_h, words_cap)))
+    return rc;
   if (counts_h) std::copy(counts.begin(), counts.end(), counts_h);
   if (status_h) std::copy(st.begin(), st.end(), status_h);
   return KHG_OK;
@@ -2136,61 +2106,40 @@ extern "C" int khg_lattices_oracle(khg_ctx* ctx, const khg_lattices* lc, int32_t
 extern "C" int khg_lattices_wer(khg_ctx* ctx, const khg_lattices* lc, int32_t n_utt, const int32_t* ref_h, const int64_t* ref_off_h, int32_t n_points,
                                 const float* graph_scale, const float* acoustic_scale, const float* word_ins_penalty, int32_t* counts_h, int32_t* nwords_h,
                                 int32_t* status_h) {
-  const std::string who = "khg_lattices_wer: ";
+  const std::string name = "khg_lattices_wer", who = name + ": ";
   if (!lc || n_points < 1 || !graph_scale || !acoustic_scale || !word_ins_penalty) return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  int rc = score_ref_check(who, lc, n_utt, ref_h, ref_off_h);
+  int rc = score_ref_check(name, lc, n_utt, ref_h, ref_off_h);
   if (rc) return rc;
   for (int k = 0; k < n_points; ++k)
     if (bad_scale(graph_scale[k]) || bad_scale(acoustic_scale[k]) || !std::isfinite(word_ins_penalty[k]))
       return khg_set_error(KHG_E_ARG, who + "point " + std::to_string(k) + ": graph_scale and acoustic_scale must be finite and >= 0, word_ins_penalty finite");
   if (ctx_dead(ctx)) return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  if (lc->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (lc->ctx != ctx) return other_ctx(name);
   khg_lattices* l = const_cast<khg_lattices*>(lc);
   const int U = l->U, K = n_points;
   if (U == 0) return KHG_OK;
-  rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (rc) return rc;
+  if ((rc = lat_ready(ctx, l))) return rc;
   const int64_t KU = (int64_t)K * U;
   DevBlocks dv;
   int32_t *ref_d, *nw_d, *status_d, *counts_d;
-  float *gs_d, *as_d, *pen_d;
+  float* pen_d;
   int64_t *ref_off_d, *hb_off_d;
   unsigned char* hb_d;
+  std::vector<LoArgs> pcs;
   if ((rc = score_ref_upload(ctx, U, ref_h, ref_off_h, &dv, &ref_d, &ref_off_d)) || (rc = dv.alloc(KU, &nw_d)) || (rc = dv.alloc(KU, &status_d)) ||
-      (rc = dv.alloc(4 * KU, &counts_d)) || (rc = dv.alloc(K, &gs_d)) || (rc = dv.alloc(K, &as_d)) || (rc = dv.alloc(K, &pen_d)) || (rc = dv.alloc(KU, &hb_off_d)))
+      (rc = dv.alloc(4 * KU, &counts_d)) || (rc = best_path_args(ctx, l, K, graph_scale, acoustic_scale, nw_d, status_d, &dv, &pcs)) ||
+      (rc = dv.upload(ctx, word_ins_penalty, K, &pen_d)))
     return rc;
-  HIPCHK(hipMemcpyAsync(gs_d, graph_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(as_d, acoustic_scale, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(pen_d, word_ins_penalty, 4 * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
-  std::vector<ScWerArgs> pcs;
-  for (const LatChunk& c : l->chunks) {
-    ScBpArgs q;
-    std::memset(&q, 0, sizeof(q));
-    LoArgs& p = q.lo;
-    lat_chunk_args(l, c, &p);
-    p.lds_bytes = lat_chunk_lds(ctx, l, c);
-    p.K = K; p.gs = gs_d; p.as = as_d; p.nwords = nw_d; p.status = status_d;
-    q.pen = pen_d;
-    const int64_t cells = std::max<int64_t>(c.ns * K, 1);
-    if ((rc = dv.alloc(cells, &p.d1)) || (rc = dv.alloc(cells, &p.d2)) || (rc = dv.alloc(cells, &p.n1)) || (rc = dv.alloc(cells, &p.n2)) ||
-        (rc = dv.alloc(cells, &p.bp)) || (rc = dv.alloc(cells, &p.words)))
+  for (const LoArgs& p : pcs) {
+    ScBpArgs q{};
+    q.lo = p; q.pen = pen_d;
+    if ((rc = launch(ctx, "k2_lattice_score_best_path", k2_lattice_score_best_path, dim3((unsigned)p.n, (unsigned)((K + LO_NT - 1) / LO_NT)), dim3(LO_NT),
+                     (size_t)p.lds_bytes, q)))
       return rc;
-    {
-      KernelTimer kt(ctx, "k2_lattice_score_best_path");
-      KHG_LAUNCH(ctx, k2_lattice_score_best_path, dim3((unsigned)c.n, (unsigned)((K + LO_NT - 1) / LO_NT)), dim3(LO_NT), (size_t)p.lds_bytes, ctx->stream, q);
-      HIPCHK(hipGetLastError());
-    }
-    ScWerArgs w;
-    std::memset(&w, 0, sizeof(w));
-    w.lo = p;
-    pcs.push_back(w);
   }
   // the hypotheses' lengths size the tables: one synchronisation
-  std::vector<int32_t> nw((size_t)KU), st((size_t)KU), counts(4 * (size_t)KU);
-  HIPCHK(hipMemcpyAsync(nw.data(), nw_d, 4 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(st.data(), status_d, 4 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = check_err_flag(ctx, "khg_lattices_wer"))) return rc;
+  std::vector<int32_t> nw, st, counts;
+  if ((rc = download(ctx, nw_d, KU, &nw)) || (rc = download(ctx, status_d, KU, &st)) || (rc = check_err_flag(ctx, name.c_str()))) return rc;
   std::vector<int64_t> hb_off((size_t)KU, -1);
   int64_t hb_total = 0, lds = 0;
   const bool no_lds = ctx->opt[KHG_OPT_LAT_OPS_LDS] == 1;
@@ -2202,16 +2151,13 @@ extern "C" int khg_lattices_wer(khg_ctx* ctx, const khg_lattices* lc, int32_t n_
       if (!no_lds && need <= kScoreWerLds) lds = std::max(lds, need);
       else { hb_off[o] = hb_total; hb_total += (need + 255) & ~int64_t(255); }
     }
-  if ((rc = dv.alloc(std::max<int64_t>(hb_total, 1), &hb_d))) return rc;
-  HIPCHK(hipMemcpyAsync(hb_off_d, hb_off.data(), 8 * (size_t)KU, hipMemcpyHostToDevice, ctx->stream));
-  for (ScWerArgs& w : pcs) {
-    w.ref = ref_d; w.ref_off = ref_off_d; w.hb = hb_d; w.hb_off = hb_off_d; w.counts = counts_d;
-    KernelTimer kt(ctx, "k2_lattice_score_wer");
-    KHG_LAUNCH(ctx, k2_lattice_score_wer, dim3((unsigned)w.lo.n, (unsigned)K), dim3(SC_NT), (size_t)lds, ctx->stream, w);
-    HIPCHK(hipGetLastError());
+  if ((rc = dv.alloc(std::max<int64_t>(hb_total, 1), &hb_d)) || (rc = dv.upload(ctx, hb_off, &hb_off_d))) return rc;
+  for (const LoArgs& p : pcs) {
+    ScWerArgs w{};
+    w.lo = p; w.ref = ref_d; w.ref_off = ref_off_d; w.hb = hb_d; w.hb_off = hb_off_d; w.counts = counts_d;
+    if ((rc = launch(ctx, "k2_lattice_score_wer", k2_lattice_score_wer, dim3((unsigned)p.n, (unsigned)K), dim3(SC_NT), (size_t)lds, w))) return rc;
   }
-  HIPCHK(hipMemcpyAsync(counts.data(), counts_d, 16 * (size_t)KU, hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = check_err_flag(ctx, "khg_lattices_wer"))) return rc;      // synchronises: the scratch goes with `dv`
+  if ((rc = download(ctx, counts_d, 4 * KU, &counts)) || (rc = check_err_flag(ctx, name.c_str()))) return rc;      // synchronises: the scratch goes with `dv`
   if (counts_h) std::copy(counts.begin(), counts.end(), counts_h);
   if (nwords_h) for (size_t o = 0; o < (size_t)KU; ++o) nwords_h[o] = (st[o] & KHG_LAT_SUCCEEDED) ? nw[o] : 0;
   if (status_h) std::copy(st.begin(), st.end(), status_h);
@@ -2316,7 +2262,7 @@ extern "C" int khg_mbr_sizes(const khg_mbr* m, int64_t* words_off_h, int64_t* vo
 extern "C" int khg_mbr_download(khg_ctx* ctx, const khg_mbr* m, int32_t* status_h, int32_t* iters_h, double* bayes_risk_h, int32_t* words_h, double* conf_h,
                                 int32_t* vocab_h, double* gamma_h, double* arc_cond_h, double* final_cond_h) {
   if (ctx_dead(ctx) || !m) return khg_set_error(KHG_E_ARG, "khg_mbr_download: bad arguments");
-  if (m->ctx != ctx) return khg_set_error(KHG_E_ARG, "khg_mbr_download: a handle of another context");
+  if (m->ctx != ctx) return other_ctx("khg_mbr_download");
   const size_t U = (size_t)m->U;
   if (status_h) std::copy(m->status.begin(), m->status.end(), status_h);
   if (iters_h) std::copy(m->iters.begin(), m->iters.end(), iters_h);
@@ -2327,12 +2273,12 @@ extern "C" int khg_mbr_download(khg_ctx* ctx, const khg_mbr* m, int32_t* status_
   if (final_cond_h && NS) HIPCHK(hipMemcpyAsync(final_cond_h, m->final_cond_d, 8 * (size_t)NS, hipMemcpyDeviceToHost, ctx->stream));
   // an utterance's results lie at the head of its slot: the slots come back in one copy per array and are packed here
   const int64_t CT = m->cap_off[U], GT = m->gout_off[U];
-  std::vector<int32_t> hyp(words_h ? (size_t)(2 * CT) : 0), voc(vocab_h ? (size_t)(NA + (int64_t)U) : 0);
-  std::vector<double> conf(conf_h ? (size_t)CT : 0), gam(gamma_h ? (size_t)GT : 0);
-  if (!hyp.empty()) HIPCHK(hipMemcpyAsync(hyp.data(), m->hyp_d, 4 * hyp.size(), hipMemcpyDeviceToHost, ctx->stream));
-  if (!voc.empty()) HIPCHK(hipMemcpyAsync(voc.data(), m->vocab_d, 4 * voc.size(), hipMemcpyDeviceToHost, ctx->stream));
-  if (!conf.empty()) HIPCHK(hipMemcpyAsync(conf.data(), m->conf_d, 8 * conf.size(), hipMemcpyDeviceToHost, ctx->stream));
-  if (!gam.empty()) HIPCHK(hipMemcpyAsync(gam.data(), m->gamma_d, 8 * gam.size(), hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<int32_t> hyp, voc;
+  std::vector<double> conf, gam;
+  int rc;
+  if ((rc = download(ctx, m->hyp_d, words_h ? 2 * CT : 0, &hyp)) || (rc = download(ctx, m->vocab_d, vocab_h ? NA + (int64_t)U : 0, &voc)) ||
+      (rc = download(ctx, m->conf_d, conf_h ? CT : 0, &conf)) || (rc = download(ctx, m->gamma_d, gamma_h ? GT : 0, &gam)))
+    return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   int64_t w = 0, v = 0, g = 0;
   for (size_t u = 0; u < U; ++u) {
@@ -2350,7 +2296,7 @@ extern "C" int khg_mbr_download(khg_ctx* ctx, const khg_mbr* m, int32_t* status_
 extern "C" int khg_lattices_mbr(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, int32_t decode_mbr, int32_t max_iter,
                                 int32_t n_utt, const int32_t* init_h, const int64_t* init_off_h, const int32_t* init_given_h, int32_t max_words,
                                 int64_t scratch_bytes, khg_mbr** out) {
-  const std::string who = "khg_lattices_mbr: ";
+  const std::string name = "khg_lattices_mbr", who = name + ": ";
   if (out) *out = nullptr;
   if (bad_scale(graph_scale) || bad_scale(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "graph_scale and acoustic_scale must be finite and >= 0");
   if (max_iter < 0) return khg_set_error(KHG_E_ARG, who + "max_iter must be >= 0");
@@ -2361,16 +2307,14 @@ extern "C" int khg_lattices_mbr(khg_ctx* ctx, const khg_lattices* lc, float grap
   const int U = l->U;
   if (n_utt != U) return khg_set_error(KHG_E_ARG, who + "the lattices hold " + std::to_string(U) + " utterances, the call names " + std::to_string(n_utt));
   if (init_off_h) {
-    if (init_off_h[0] != 0) return khg_set_error(KHG_E_ARG, who + "init_off_h must start at 0");
-    for (int u = 0; u < U; ++u)
-      if (init_off_h[u + 1] < init_off_h[u]) return khg_set_error(KHG_E_ARG, who + "init_off_h decreases at utterance " + std::to_string(u));
-    if (init_off_h[U] > 0 && !init_h) return khg_set_error(KHG_E_ARG, who + "init_h is NULL");
+    int rc = check_offsets(name, "init_off_h", init_off_h, U, "utterance", init_h, "init_h");
+    if (rc) return rc;
     for (int u = 0; u < U; ++u)
       for (int64_t i = init_off_h[u]; i < init_off_h[u + 1]; ++i)
         if (init_h[i] <= 0) return khg_set_error(KHG_E_ARG, who + "utterance " + std::to_string(u) + ": an initial word is not > 0");
   }
   if (ctx_dead(ctx)) return khg_set_error(KHG_E_ARG, who + "bad arguments");
-  if (l->ctx != ctx) return khg_set_error(KHG_E_ARG, who + "a handle of another context");
+  if (l->ctx != ctx) return other_ctx(name);
   MbrPtr res(new khg_mbr);
   khg_mbr* m = res.get();
   m->U = U; m->ctx = ctx; m->state_off = l->state_off; m->arc_off = l->arc_off;
@@ -2396,15 +2340,13 @@ extern "C" int khg_lattices_mbr(khg_ctx* ctx, const khg_lattices* lc, float grap
       if (!(init_off_h && (!init_given_h || init_given_h[u])) && (st[(size_t)u] & KHG_LAT_SUCCEEDED))
         init[(size_t)u].assign(words.begin() + woff[(size_t)u], words.begin() + woff[(size_t)u + 1]);
   }
-  int rc = arena_flush(ctx);
-  if (!rc) rc = lat_meta(ctx, l);
-  if (!rc) rc = lat_index(ctx, l);
+  int rc = lat_ready(ctx, l, kWithIndex);
   if (rc) return rc;
   if ((rc = mbr_alloc(m, NA, &m->arc_cond_d)) || (rc = mbr_alloc(m, NS, &m->final_cond_d)) || (rc = mbr_alloc(m, NA + U, &m->vocab_d))) return rc;
   DevBlocks dv;
   int32_t *nv_d, *mw_d, *widx_d;
   if ((rc = dv.alloc(U, &nv_d)) || (rc = dv.alloc(U, &mw_d)) || (rc = dv.alloc(std::max<int64_t>(NA, 1), &widx_d))) return rc;
-  std::vector<int32_t> st((size_t)U), nv((size_t)U), mw((size_t)U);
+  std::vector<int32_t> st, nv, mw;
   {
     // the weights: khg_lattices_posteriors' chunk steps around k2_lattice_mbr_weights (the run's own result handle is dropped)
     PostRun r;
@@ -2415,57 +2357,39 @@ extern "C" int khg_lattices_mbr(khg_ctx* ctx, const khg_lattices* lc, float grap
     for (size_t k = 0; k < l->chunks.size(); ++k) {
       const LatChunk& c = l->chunks[k];
       const int64_t cs0 = l->state_off[(size_t)c.u0], ca0 = l->arc_off[(size_t)c.u0];
-      PoArgs p;
-      std::memset(&p, 0, sizeof(p));
+      PoArgs p{};
       if ((rc = post_chunk_begin(r, k, 24, &p))) return rc;
       p.arc_post = m->arc_cond_d + ca0;
-      {
-        KernelTimer kt(ctx, "k2_lattice_mbr_weights");
-        KHG_LAUNCH(ctx, k2_lattice_mbr_weights, dim3((unsigned)c.n), dim3(PO_NT), (size_t)p.lo.lds_bytes, ctx->stream, p, m->final_cond_d + cs0);
-        HIPCHK(hipGetLastError());
-      }
       int32_t *len_d, *first_d;
-      if ((rc = r.dv.alloc(std::max<int64_t>(c.ns, 1), &len_d)) || (rc = r.dv.alloc(std::max<int64_t>(c.na, 1), &first_d))) return rc;
       const LatIndex ix = lat_index_arrays(l->idx_d[k], c);
-      KernelTimer kt(ctx, "k2_lattice_mbr_prepare");
-      KHG_LAUNCH(ctx, k2_lattice_mbr_prepare, dim3((unsigned)c.n), dim3(MB_NT), 0, ctx->stream, p.lo, ix.arc_src, len_d, first_d, m->vocab_d, widx_d + ca0, nv_d, mw_d);
-      HIPCHK(hipGetLastError());
+      if ((rc = launch(ctx, "k2_lattice_mbr_weights", k2_lattice_mbr_weights, dim3((unsigned)c.n), dim3(PO_NT), (size_t)p.lo.lds_bytes, p, m->final_cond_d + cs0)) ||
+          (rc = r.dv.alloc(std::max<int64_t>(c.ns, 1), &len_d)) || (rc = r.dv.alloc(std::max<int64_t>(c.na, 1), &first_d)) ||
+          (rc = launch(ctx, "k2_lattice_mbr_prepare", k2_lattice_mbr_prepare, dim3((unsigned)c.n), dim3(MB_NT), 0, p.lo, ix.arc_src, len_d, first_d, m->vocab_d,
+                       widx_d + ca0, nv_d, mw_d)))
+        return rc;
     }
-    HIPCHK(hipMemcpyAsync(st.data(), r.status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(nv.data(), nv_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(mw.data(), mw_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = check_err_flag(ctx, "khg_lattices_mbr"))) return rc;      // synchronises: the run's scratch goes with `r`
+    if ((rc = download(ctx, r.status_d, U, &st)) || (rc = download(ctx, nv_d, U, &nv)) || (rc = download(ctx, mw_d, U, &mw)) ||
+        (rc = check_err_flag(ctx, name.c_str())))      // synchronises: the run's scratch goes with `r`
+      return rc;
   }
   // the caps, the slots, and the utterances that run, grouped into launches whose tables fit the budget together
-  std::vector<int32_t> cap((size_t)U, 0), w0((size_t)U, 0), list;
-  std::vector<int64_t> tab_off;
-  struct Launch { size_t chunk, first, n; int64_t cells; };
-  std::vector<Launch> launches;
-  int64_t max_cells = 1;
-  for (size_t k = 0; k < l->chunks.size(); ++k) {
-    const LatChunk& c = l->chunks[k];
-    Launch cur{k, list.size(), 0, 0};
-    for (int u = c.u0; u < c.u0 + c.n; ++u) {
-      const size_t su = (size_t)u;
-      m->status[su] = st[su]; m->nvocab[su] = nv[su];
-      m->cap_off[su + 1] = m->cap_off[su]; m->gout_off[su + 1] = m->gout_off[su];
-      if (!(st[su] & KHG_LAT_SUCCEEDED)) continue;
-      const int64_t W0 = (int64_t)init[su].size();
-      const int64_t cp = max_words > 0 ? max_words : std::max<int64_t>(W0, mw[su]);
-      if (W0 > cp || cp > MB_MAX_WORDS) { m->status[su] = KHG_LAT_WORDS; continue; }
-      const int64_t N = l->state_off[su + 1] - l->state_off[su], C = 2 * cp + 2, cells = (2 * (N + 1) + nv[su]) * C;
-      if (8 * cells > budget) { m->status[su] = KHG_LAT_SCRATCH; continue; }
-      cap[su] = (int32_t)cp; w0[su] = (int32_t)W0;
-      m->cap_off[su + 1] += cp; m->gout_off[su + 1] += (2 * cp + 1) * nv[su];
-      if (cur.n > 0 && 8 * (cur.cells + cells) > budget) { launches.push_back(cur); cur = Launch{k, list.size(), 0, 0}; }
-      list.push_back(u);
-      tab_off.push_back(cur.cells);
-      cur.cells += cells; ++cur.n;
-    }
-    if (cur.n > 0) launches.push_back(cur);
-  }
-  for (const Launch& L : launches) max_cells = std::max(max_cells, L.cells);
-  const int64_t CT = m->cap_off[(size_t)U], GT = m->gout_off[(size_t)U], nl = std::max<int64_t>((int64_t)list.size(), 1);
+  std::vector<int32_t> cap((size_t)U, 0), w0((size_t)U, 0);
+  const TableLaunches g = group_tables(l->chunks, 8, budget, [&](int u) -> int64_t {
+    const size_t su = (size_t)u;
+    m->status[su] = st[su]; m->nvocab[su] = nv[su];
+    m->cap_off[su + 1] = m->cap_off[su]; m->gout_off[su + 1] = m->gout_off[su];
+    if (!(st[su] & KHG_LAT_SUCCEEDED)) return -1;
+    const int64_t W0 = (int64_t)init[su].size();
+    const int64_t cp = max_words > 0 ? max_words : std::max<int64_t>(W0, mw[su]);
+    if (W0 > cp || cp > MB_MAX_WORDS) { m->status[su] = KHG_LAT_WORDS; return -1; }
+    const int64_t N = l->state_off[su + 1] - l->state_off[su], C = 2 * cp + 2, cells = (2 * (N + 1) + nv[su]) * C;
+    if (8 * cells > budget) { m->status[su] = KHG_LAT_SCRATCH; return -1; }
+    cap[su] = (int32_t)cp; w0[su] = (int32_t)W0;
+    m->cap_off[su + 1] += cp; m->gout_off[su + 1] += (2 * cp + 1) * nv[su];
+    return cells;
+  });
+  const std::vector<int32_t>& list = g.list;
+  const int64_t CT = m->cap_off[(size_t)U], GT = m->gout_off[(size_t)U];
   if ((rc = mbr_alloc(m, CT, &m->conf_d)) || (rc = mbr_alloc(m, GT, &m->gamma_d)) || (rc = mbr_alloc(m, 2 * CT, &m->hyp_d))) return rc;
   if (!list.empty()) {
     std::vector<int32_t> hyp((size_t)std::max<int64_t>(2 * CT, 1), 0);
@@ -2473,23 +2397,16 @@ extern "C" int khg_lattices_mbr(khg_ctx* ctx, const khg_lattices* lc, float grap
     int32_t *cap_d, *w0_d, *status_d, *iters_d, *nw_d, *list_d;
     int64_t *cap_off_d, *gout_off_d, *tab_off_d;
     double *risk_d, *tab_d;
-    if ((rc = dv.alloc(U, &cap_d)) || (rc = dv.alloc(U, &w0_d)) || (rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &iters_d)) || (rc = dv.alloc(U, &nw_d)) ||
-        (rc = dv.alloc(nl, &list_d)) || (rc = dv.alloc(U + 1, &cap_off_d)) || (rc = dv.alloc(U + 1, &gout_off_d)) || (rc = dv.alloc(nl, &tab_off_d)) ||
-        (rc = dv.alloc(U, &risk_d)) || (rc = dv.alloc(max_cells, &tab_d)))
-      return rc;
     HIPCHK(hipMemcpyAsync(m->hyp_d, hyp.data(), 4 * (size_t)(2 * CT), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(cap_d, cap.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(w0_d, w0.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(cap_off_d, m->cap_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(gout_off_d, m->gout_off.data(), 8 * ((size_t)U + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(list_d, list.data(), 4 * list.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(tab_off_d, tab_off.data(), 8 * tab_off.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(status_d, 0, 4 * (size_t)U, ctx->stream));
-    for (const Launch& L : launches) {
+    if ((rc = dv.upload(ctx, cap, &cap_d)) || (rc = dv.upload(ctx, w0, &w0_d)) || (rc = dv.upload(ctx, m->cap_off, &cap_off_d)) ||
+        (rc = dv.upload(ctx, m->gout_off, &gout_off_d)) || (rc = dv.upload(ctx, list, &list_d)) || (rc = dv.upload(ctx, g.tab_off, &tab_off_d)) ||
+        (rc = dv.zeroed(ctx, U, &status_d)) || (rc = dv.alloc(U, &iters_d)) || (rc = dv.alloc(U, &nw_d)) || (rc = dv.alloc(U, &risk_d)) ||
+        (rc = dv.alloc(g.max_cells, &tab_d)))
+      return rc;
+    for (const TableLaunch& L : g.launches) {
       const LatChunk& c = l->chunks[L.chunk];
       const int64_t cs0 = l->state_off[(size_t)c.u0], ca0 = l->arc_off[(size_t)c.u0];
-      MbArgs p;
-      std::memset(&p, 0, sizeof(p));
+      MbArgs p{};
       lat_chunk_args(l, c, &p.lo);
       const LatIndex ix = lat_index_arrays(l->idx_d[L.chunk], c);
       p.in_begin = ix.in_begin; p.in_arc = ix.in_arc; p.arc_src = ix.arc_src;
@@ -2500,17 +2417,13 @@ extern "C" int khg_lattices_mbr(khg_ctx* ctx, const khg_lattices* lc, float grap
       p.hyp = m->hyp_d; p.conf = m->conf_d; p.gamma_out = m->gamma_d;
       p.status = status_d; p.iters = iters_d; p.nwords = nw_d; p.risk = risk_d;
       p.decode_mbr = decode_mbr ? 1 : 0; p.max_iter = max_iter;
-      KernelTimer kt(ctx, "k2_lattice_mbr");
-      KHG_LAUNCH(ctx, k2_lattice_mbr, dim3((unsigned)L.n), dim3(MB_NT), 0, ctx->stream, p);
-      HIPCHK(hipGetLastError());
+      if ((rc = launch(ctx, "k2_lattice_mbr", k2_lattice_mbr, dim3((unsigned)L.n), dim3(MB_NT), 0, p))) return rc;
     }
-    std::vector<int32_t> st2((size_t)U), it((size_t)U), nw((size_t)U);
-    std::vector<double> rk((size_t)U);
-    HIPCHK(hipMemcpyAsync(st2.data(), status_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(it.data(), iters_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(nw.data(), nw_d, 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(rk.data(), risk_d, 8 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = check_err_flag(ctx, "khg_lattices_mbr"))) return rc;      // synchronises: the scratch goes with `dv`
+    std::vector<int32_t> st2, it, nw;
+    std::vector<double> rk;
+    if ((rc = download(ctx, status_d, U, &st2)) || (rc = download(ctx, iters_d, U, &it)) || (rc = download(ctx, nw_d, U, &nw)) ||
+        (rc = download(ctx, risk_d, U, &rk)) || (rc = check_err_flag(ctx, name.c_str())))      // synchronises: the scratch goes with `dv`
+      return rc;
     for (int u : list) {
       const size_t su = (size_t)u;
       m->status[su] = st2[su]; m->iters[su] = it[su];
