@@ -239,6 +239,26 @@ int khg_utts_k2_tail(const khg_utts *u, int32_t *out, int64_t cap);
 /* K3's split feature records on the set (KHG_OPT_K3_PLANES): *bytes of the buffer (0: none), *packs = how often it was filled so far,
  * *used = 1 when the last khg_acc_stats pass read it.  Launches nothing. */
 int khg_utts_k3_planes(const khg_utts *u, int64_t *bytes, int64_t *packs, int32_t *used);
+/* The accumulate kernels of the statistics pass (K3), by variant: the wave form with the fp32 / fp64 phase B, the wave form with both
+ * phases on the fp16 matrix cores splitting the features in its loop / reading the set's split feature records, the wave forms' fold
+ * (k3_wave_finalize, launched behind each of them), the chunk-per-block fp32 + fp64 MFMA form, its fp16 form, the VALU form. */
+#define KHG_K3V_WAVE 0
+#define KHG_K3V_WAVE16 1
+#define KHG_K3V_WAVE16P 2
+#define KHG_K3V_FINALIZE 3
+#define KHG_K3V_MFMA 4
+#define KHG_K3V_BLOCK16 5
+#define KHG_K3V_VALU 6
+/* Every instantiation the pass can launch: rows[i] = { variant, KQ, Gaussian blocks, waves per block, POST, fp16 phase A } -- the
+ * library's own table, for tests; needs no context and no device.  *n = the number of rows; rows == NULL: *n alone; cap: rows of 6
+ * int32 that `rows` holds (KHG_E_ARG when fewer than *n). */
+int khg_k3_forms(int32_t *rows, int32_t cap, int32_t *n);
+/* What the LAST statistics pass over this set launched (khg_acc_stats -- in split mode its second pass --, khg_acc_stats_post /
+ * _post2, the K3 pass of khg_acc_mllt_stats_post), written where the pass decided it: *nruns = 0 (before any pass, after a pass over
+ * zero frames), 1, or 2 for a model whose pdfs go to two forms; per run out[i] = { variant, KQ, Gaussian blocks, waves per block,
+ * POST, fp16 phase A, fp16 phase B, 1 when the split feature records were read, slices per pdf, cls_lo, cls_hi (the run takes the
+ * pdfs of cls_lo < Gaussians <= cls_hi), dynamic LDS bytes }.  Launches nothing. */
+int khg_utts_k3_last(const khg_utts *u, int32_t out[2][12], int32_t *nruns);
 /* per listed pdf: the first frame a decoder token can read it at (fewest emitting arcs from the start state
  * to an arc carrying it; INT32_MAX if never; 0 for sets without graphs) -- what khg_loglikes_reachable uses */
 int khg_utts_pdf_first(const khg_utts *u, int32_t *first_h /* [pdf_off[n_utt]] */);

@@ -25,7 +25,7 @@ from .context_dep import (ContextDependency, ContextDependencyInterface, monopho
                           monophone_context_dependency_shared)
 from .device import (ALIGN_DONE, ALIGN_ERROR, ALIGN_EXACT_DP, ALIGN_FALLBACK, ALIGN_RETRIED, Comm, Context, DeviceAccs,  # noqa: F401
                      DecodingGraph, DeviceCmvnStats, DeviceFmllrStats, DeviceLdaStats, DeviceMlltStats, DeviceModel, DeviceTransitions, DeviceTreeStats,
-                     UtteranceSet)
+                     UtteranceSet, k3_forms)
 from .diag_gmm import AmDiagGmm, DiagGmm  # noqa: F401
 from .fst import StdArc, StdVectorFst, modify_graph_for_careful_alignment  # noqa: F401
 from .hmm_topology import HmmState, HmmTopology  # noqa: F401

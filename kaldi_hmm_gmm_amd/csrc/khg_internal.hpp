@@ -310,6 +310,8 @@ struct khg_utts {
   void* k3_items_d = nullptr; int32_t* k3_item_off_d = nullptr; size_t k3_items_n = 0, k3_item_off_n = 0;   // K3 work items (k3_make_items)
   int64_t* pdf_start_d = nullptr; unsigned long long* tid_count_d = nullptr;
   int32_t k3_P = 0, k3_tids = 0;
+  // khg_utts_k3_last: what the last statistics pass over this set launched, per run of its plan (k3_run writes a row where it has settled it)
+  int32_t k3_last[2][12] = {}; int32_t k3_last_n = 0;
   // k3_accumulate_wave16's split feature records (khg_k3.hip: k3_planes), keyed by the model-derived exponents they were made with
   void* k3x_d = nullptr; int64_t k3x_bytes = 0, k3x_packs = 0; std::vector<int32_t> k3x_key; bool k3x_used = false;
   // khg_acc_stats_post: the flattened entries (row, id, weight), their sort buffers and bucket bounds -- sized by the ENTRY count and

@@ -288,17 +288,20 @@ int k3_post_check(khg_ctx* ctx, const khg_model* m, const std::string& who) {
 }
 
 // Every instantiation of the accumulate kernels, once: (variant, KQ, Gaussian blocks, waves, POST, fp16 phase A) -> the kernel.
+// (the fp16 phases of the wave form exist for three and four Gaussian blocks only: k3_plan allows them for nb >= 3, so there is no
+//  row -- and no code object -- for one or two blocks; khg_k3_forms hands the table to a test)
 typedef void (*K3Kernel)(K3Args);
-enum K3Variant { K3V_WAVE, K3V_WAVE16, K3V_WAVE16P, K3V_FINALIZE, K3V_MFMA, K3V_BLOCK16, K3V_VALU };
+enum K3Variant { K3V_WAVE = KHG_K3V_WAVE, K3V_WAVE16 = KHG_K3V_WAVE16, K3V_WAVE16P = KHG_K3V_WAVE16P, K3V_FINALIZE = KHG_K3V_FINALIZE,
+                 K3V_MFMA = KHG_K3V_MFMA, K3V_BLOCK16 = KHG_K3V_BLOCK16, K3V_VALU = KHG_K3V_VALU };
 struct K3Inst { int variant, KQ, NB, nwv; bool post, f16a; K3Kernel fn; };
-#define K3_WAVE_ROWS(NB)                                                                                                           \
-  {K3V_WAVE, 10, NB, 4, false, false, k3_accumulate_wave<NB>}, {K3V_WAVE, 10, NB, 4, false, true, k3_accumulate_wave<NB, true>}, \
-  {K3V_WAVE16, 10, NB, 4, false, true, k3_accumulate_wave16<NB>}, {K3V_WAVE16P, 10, NB, 4, false, true, k3_accumulate_wave16<NB, true>}, \
-  {K3V_FINALIZE, 10, NB, 4, false, false, k3_wave_finalize<NB>}
+#define K3_WAVE_ROWS(NB) {K3V_WAVE, 10, NB, 4, false, false, k3_accumulate_wave<NB>}, {K3V_FINALIZE, 10, NB, 4, false, false, k3_wave_finalize<NB>}
+#define K3_WAVE_F16_ROWS(NB)                                                                                                        \
+  {K3V_WAVE, 10, NB, 4, false, true, k3_accumulate_wave<NB, true>}, {K3V_WAVE16, 10, NB, 4, false, true, k3_accumulate_wave16<NB>}, \
+  {K3V_WAVE16P, 10, NB, 4, false, true, k3_accumulate_wave16<NB, true>}
 #define K3_MFMA_ROWS(KQ, NBW) {K3V_MFMA, KQ, NBW, 4, false, false, k3_accumulate_mfma<KQ, NBW>}, {K3V_MFMA, KQ, NBW, 4, true, false, k3_accumulate_mfma<KQ, NBW, true>}
 #define K3_VALU_ROWS(KQ) {K3V_VALU, KQ, 0, 4, false, false, k3_accumulate<KQ>}, {K3V_VALU, KQ, 0, 4, true, false, k3_accumulate<KQ, true>}
 static const K3Inst k3_insts[] = {
-  K3_WAVE_ROWS(1), K3_WAVE_ROWS(2), K3_WAVE_ROWS(3), K3_WAVE_ROWS(4),
+  K3_WAVE_ROWS(1), K3_WAVE_ROWS(2), K3_WAVE_ROWS(3), K3_WAVE_ROWS(4), K3_WAVE_F16_ROWS(3), K3_WAVE_F16_ROWS(4),
   K3_MFMA_ROWS(10, 1), K3_MFMA_ROWS(10, 2), K3_MFMA_ROWS(10, 3), K3_MFMA_ROWS(10, 4), K3_MFMA_ROWS(20, 1), K3_MFMA_ROWS(20, 2),
   {K3V_BLOCK16, 20, 1, 4, false, true, k3_accumulate_block16<20, 1, 4>}, {K3V_BLOCK16, 10, 1, 4, false, true, k3_accumulate_block16<10, 1, 4>},
   {K3V_BLOCK16, 20, 1, 8, false, true, k3_accumulate_block16<20, 1, 8>}, {K3V_BLOCK16, 10, 1, 8, false, true, k3_accumulate_block16<10, 1, 8>},
@@ -309,6 +312,24 @@ static K3Kernel k3_kernel(int variant, int KQ, int NB, int nwv, bool post, bool 
   for (const K3Inst& i : k3_insts)
     if (i.variant == variant && i.KQ == KQ && i.NB == NB && i.nwv == nwv && i.post == post && i.f16a == f16a) return i.fn;
   return nullptr;
+}
+extern "C" int khg_k3_forms(int32_t* rows, int32_t cap, int32_t* n) {
+  const int32_t cnt = (int32_t)(sizeof(k3_insts) / sizeof(k3_insts[0]));
+  if (!n || (rows && cap < cnt)) return khg_set_error(KHG_E_ARG, "khg_k3_forms: bad arguments");
+  *n = cnt;
+  if (!rows) return KHG_OK;
+  for (int32_t i = 0; i < cnt; ++i) {
+    const K3Inst& k = k3_insts[i];
+    int32_t* o = rows + 6 * (size_t)i;
+    o[0] = k.variant; o[1] = k.KQ; o[2] = k.NB; o[3] = k.nwv; o[4] = k.post; o[5] = k.f16a;
+  }
+  return KHG_OK;
+}
+extern "C" int khg_utts_k3_last(const khg_utts* u, int32_t out[2][12], int32_t* nruns) {
+  if (!u || !out || !nruns) return khg_set_error(KHG_E_ARG, "khg_utts_k3_last: bad arguments");
+  *nruns = u->k3_last_n;
+  for (int i = 0; i < u->k3_last_n; ++i) std::copy(u->k3_last[i], u->k3_last[i] + 12, out[i]);
+  return KHG_OK;
 }
 // ... and the one launch of them
 static int k3_launch(khg_ctx* ctx, K3Kernel fn, unsigned grid, int nthr, size_t lds, const K3Args& a) {
@@ -514,6 +535,11 @@ static int k3_run(khg_ctx* ctx, const khg_model* m, khg_utts* u, khg_accs* acc, 
   const K3Kernel fin = wave ? k3_kernel(K3V_FINALIZE, m->KQ, r.NB, 4, false, false) : nullptr;
   if (!fn || (wave && !fin)) return khg_set_error(KHG_E_RUNTIME, "khg_acc_stats: no kernel for the planned form");
   const size_t lds = r.lds[f16b ? 2 : f16a ? 1 : 0];
+  if (u->k3_last_n < 2) {                       // khg_utts_k3_last: what this run launches, as settled above
+    int32_t* o = u->k3_last[u->k3_last_n++];
+    o[0] = variant; o[1] = m->KQ; o[2] = variant == K3V_BLOCK16 ? r.NB16 : r.NB; o[3] = nwv; o[4] = post; o[5] = f16a; o[6] = f16b;
+    o[7] = variant == K3V_WAVE16P; o[8] = r.ny; o[9] = r.cls_lo; o[10] = r.cls_hi; o[11] = (int32_t)lds;
+  }
   int rc = KHG_OK;
   if (wave && u->k3_llpart_n < (size_t)m->P) { DEVFREE(u->k3_llpart_d); rc = u_alloc(u, &u->k3_llpart_d, (size_t)m->P); if (rc) return rc; u->k3_llpart_n = (size_t)m->P; }
   K3Item* items = nullptr; int32_t* item_off = nullptr;
@@ -552,6 +578,7 @@ static int acc_stats_pass(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, kh
   }
   K3Args a = k3_args(ctx, m, tm, u, acc, weight, post, Neff);
   if (!post) u->k3x_used = false;              // (khg_utts_k3_planes: whether THIS pass read the split feature records)
+  u->k3_last_n = 0;                            // (khg_utts_k3_last: the runs of THIS pass; none over zero frames)
   nparts = std::max(1, std::min(nparts, m->P));
   if (comm && nparts > 1) { rc = ctx_comm_stream(ctx); if (rc) return rc; }
   if (Neff > 0) {
@@ -647,7 +674,7 @@ static int acc_stats_post_impl(const std::string& name, khg_ctx* ctx, const khg_
     return khg_set_error(KHG_E_ARG, who + "the posteriors hold transition-id " + std::to_string(pi.max_tid) + ", the transition model has " + std::to_string(tm->num_tids));
   const int64_t E = pi.entry_off[pi.U];
   if (E >= (int64_t)INT_MAX || u->N >= (int64_t)INT_MAX) return khg_set_error(KHG_E_UNSUPPORTED, who + "2^31 - 1 or more entries or frames");
-  if (E == 0) return KHG_OK;
+  if (E == 0) { u->k3_last_n = 0; return KHG_OK; }
   int rc = arena_flush(ctx);
   if (rc) return rc;
   rc = utts_grow_pe(u, (size_t)E);

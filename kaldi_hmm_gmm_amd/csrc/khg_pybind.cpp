@@ -602,6 +602,11 @@ struct KTreeStats {
   void add(float scale, KTreeStats& src) { Check(NoGil([&] { return khg_tree_stats_add(ctx->h, h, scale, src.h); })); }
 };
 
+// the variants of khg_hip.h (KHG_K3V_*) by name, for khg_k3_forms / khg_utts_k3_last
+static const char* K3VariantName(int v) {
+  static const char* const names[] = {"wave", "wave16", "wave16_records", "finalize", "mfma", "block16", "valu"};
+  return v >= 0 && v < 7 ? names[v] : "?";
+}
 struct KUtts {
   khg_utts* h = nullptr;
   py::object ctx_obj, keep, keep_model;
@@ -676,6 +681,20 @@ struct KUtts {
     py::dict d;
     d["bytes"] = bytes; d["packs"] = packs; d["used"] = used != 0;
     return d;
+  }
+  // khg_utts_k3_last: what the last statistics pass over the set launched, one dict per run of its plan
+  py::list k3_last() {
+    int32_t o[2][12]; int32_t n = 0;
+    Check(khg_utts_k3_last(h, o, &n));
+    py::list out;
+    for (int i = 0; i < n; ++i) {
+      py::dict d;
+      d["variant"] = K3VariantName(o[i][0]); d["KQ"] = o[i][1]; d["NB"] = o[i][2]; d["waves"] = o[i][3]; d["POST"] = o[i][4] != 0;
+      d["f16a"] = o[i][5] != 0; d["f16b"] = o[i][6] != 0; d["planes"] = o[i][7] != 0; d["ny"] = o[i][8]; d["cls_lo"] = o[i][9];
+      d["cls_hi"] = o[i][10]; d["lds_bytes"] = o[i][11];
+      out.append(d);
+    }
+    return out;
   }
   // khg_utts_k2_ladder: align() would run the ladder form of that kernel
   bool k2_ladder(py::object ctx_o) {
@@ -1073,6 +1092,21 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
   m.def("_set_error_class", [](py::object cls) { g_khg_error = cls; });
   BindHost(m, &g_khg_error);
   m.def("version", [] { return khg_version(); });
+  // khg_k3_forms: the library's table of K3 accumulate instantiations, one dict per row (no context, no device)
+  m.def("k3_forms", [] {
+    int32_t n = 0;
+    Check(khg_k3_forms(nullptr, 0, &n));
+    std::vector<int32_t> rows((size_t)6 * n);
+    Check(khg_k3_forms(rows.data(), n, &n));
+    py::list out;
+    for (int i = 0; i < n; ++i) {
+      const int32_t* o = rows.data() + 6 * (size_t)i;
+      py::dict d;
+      d["variant"] = K3VariantName(o[0]); d["KQ"] = o[1]; d["NB"] = o[2]; d["waves"] = o[3]; d["POST"] = o[4] != 0; d["f16a"] = o[5] != 0;
+      out.append(d);
+    }
+    return out;
+  });
   m.attr("ALIGN_DONE") = KHG_ALIGN_DONE; m.attr("ALIGN_ERROR") = KHG_ALIGN_ERROR; m.attr("ALIGN_RETRIED") = KHG_ALIGN_RETRIED;
   m.attr("ALIGN_EXACT_DP") = KHG_ALIGN_EXACT_DP; m.attr("ALIGN_FALLBACK") = KHG_ALIGN_FALLBACK;
 
@@ -1142,7 +1176,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def_property_readonly("h", [](KUtts& x) { return reinterpret_cast<uintptr_t>(x.h); })
       .def_readonly("ctx", &KUtts::ctx_obj).def_readonly("frame_off", &KUtts::frame_off).def_readonly("n_utt", &KUtts::n_utt)
       .def_readonly("dim", &KUtts::dim)
-      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("k2_ladder", &KUtts::k2_ladder, py::arg("ctx")).def("k3_planes", &KUtts::k3_planes).def("k2_tail", &KUtts::k2_tail).def("pdf_first_frames", &KUtts::pdf_first_frames)
+      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("k2_ladder", &KUtts::k2_ladder, py::arg("ctx")).def("k3_planes", &KUtts::k3_planes).def("k3_last", &KUtts::k3_last).def("k2_tail", &KUtts::k2_tail).def("pdf_first_frames", &KUtts::pdf_first_frames)
       .def("pdf_last_frames", &KUtts::pdf_last_frames)
       .def("loglikes", &KUtts::loglikes, py::arg("model"), py::arg("reachable_only") = false, py::arg("band") = false)
       .def("loglikes_layout", &KUtts::loglikes_layout).def("download_loglikes", &KUtts::download_loglikes)

@@ -25,6 +25,7 @@ Comm = _ext.Comm                            # an RCCL communicator owned by the 
 DeviceModel = _ext.DeviceModel              # AmDiagGmm resident in HBM (+ mle_update, split, scale_weights)
 DeviceTransitions = _ext.DeviceTransitions  # TransitionIdToPdf + scaled transition costs
 UtteranceSet = _ext.UtteranceSet            # features + compiled graphs of a shard; loglikes / align / acc_stats
+k3_forms = _ext.k3_forms                    # khg_k3_forms: every instantiation the statistics pass can launch, one dict per row
 DecodingGraph = _ext.DecodingGraph          # khg_graph: ONE decoding graph resident in HBM, shared by sets (graph=) and batch calls
 DeviceFmllrStats = _ext.DeviceFmllrStats    # khg_fmllr_stats: FmllrDiagGmmAccs per speaker in HBM; download() -> numpy beta / K / G
 DeviceMlltStats = _ext.DeviceMlltStats      # khg_mllt_stats: MlltAccs in HBM; download() -> beta, numpy G
