@@ -259,6 +259,34 @@ int khg_k3_forms(int32_t *rows, int32_t cap, int32_t *n);
  * POST, fp16 phase A, fp16 phase B, 1 when the split feature records were read, slices per pdf, cls_lo, cls_hi (the run takes the
  * pdfs of cls_lo < Gaussians <= cls_hi), dynamic LDS bytes }.  Launches nothing. */
 int khg_utts_k3_last(const khg_utts *u, int32_t out[2][12], int32_t *nruns);
+/* What the LAST khg_loglikes / _reachable / _band call on this set chose and launched (K1), written on the host where each decision
+ * is settled and cleared at the start of every such call (a call that fails leaves the form at NONE):
+ *   out[0]  1 once a call was made (0: none yet, the rest is zero)
+ *   out[1]  the form that ran: KHG_K1L_NONE (no frames or no pdfs: nothing launched), _F16X2S, _F16X2, _PDF, _UTT, _WIDE (D > 80)
+ *   out[2]  the form the option asked for, same codes (KHG_K1_AUTO asks for f16x2s)
+ *   out[3]  why earlier forms handed over, a bit mask: 1 outside the split forms' domain, 2 f16x2s: the common scale or the absolute
+ *           part of its error bound (> 2e-6), 4 f16x2: no scaling fits fp16, 8 pdf-major: a pdf of more than 128 Gaussians
+ *   out[4]  KS (5 / 10) of the split forms, KQ (10 / 20) of the fp32 forms, 0 for the wide form
+ *   out[5]  cells: 0 all, 1 from a pdf's first needed tile on, 2 the band between its first and last needed tile
+ *   out[6]  f16x2s: pdfs per MFMA tile (4 / 2 / 1); other forms 0
+ *   out[7]  f16x2s: 1 when the persistent kernel ran;  out[8] workgroups of the main launch (pdf-major: summed over its launches)
+ *   out[9]  work units planned (chunks -- the empty ones of order 4 included --, pdf-major: slices);  out[10] the cap a unit was cut to
+ *           (32-frame tiles for the split forms, 16-frame tiles for the fp32 forms, frames for the wide form)
+ *   out[11] the effective KHG_OPT_K1_ORDER of the split forms (4 when f16x2s chose it by itself)
+ *   out[12] f16x2s: 1 when _reachable ran the shifted-tile form;  out[13] its shift mode (0 none, 1 sixteen frames only, 2 any)
+ *   out[14] utterance-major: 16-frame tiles per wave;  out[15] 1 for its aligned loads;  out[16] 1 when tiles are dealt round-robin
+ *   out[17 .. 24]  pdf-major: slices of the pdfs of 1 .. 8 blocks of sixteen Gaussians
+ *   out[25] bit 1: this call packed the set's feature planes, bit 2: it packed the model's image
+ *   out[26] 1 when khg_align's repair launch recomputed band scores since (cleared by the next khg_loglikes* call)
+ * Launches nothing, copies nothing to or from the device. */
+#define KHG_K1_LAST_WORDS 27
+#define KHG_K1L_NONE 0
+#define KHG_K1L_F16X2S 1
+#define KHG_K1L_F16X2 2
+#define KHG_K1L_PDF 3
+#define KHG_K1L_UTT 4
+#define KHG_K1L_WIDE 5
+int khg_utts_k1_last(const khg_utts *u, int32_t out[KHG_K1_LAST_WORDS]);
 /* per listed pdf: the first frame a decoder token can read it at (fewest emitting arcs from the start state
  * to an arc carrying it; INT32_MAX if never; 0 for sets without graphs) -- what khg_loglikes_reachable uses */
 int khg_utts_pdf_first(const khg_utts *u, int32_t *first_h /* [pdf_off[n_utt]] */);

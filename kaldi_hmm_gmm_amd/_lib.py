@@ -175,6 +175,7 @@ SIGNATURES = {
     "khg_utts_k3_planes": (C.c_int, [vp, c_i64p, c_i64p, c_i32p]),
     "khg_k3_forms": (C.c_int, [c_i32p, C.c_int32, c_i32p]),
     "khg_utts_k3_last": (C.c_int, [vp, c_i32p, c_i32p]),
+    "khg_utts_k1_last": (C.c_int, [vp, c_i32p]),
     "khg_utts_k2_tail": (C.c_int, [vp, c_i32p, C.c_int64]),
     "khg_utts_pdf_first": (C.c_int, [vp, c_i32p]),
     "khg_loglikes": (C.c_int, [vp, vp, vp]),

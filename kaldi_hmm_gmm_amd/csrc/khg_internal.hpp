@@ -312,6 +312,9 @@ struct khg_utts {
   int32_t k3_P = 0, k3_tids = 0;
   // khg_utts_k3_last: what the last statistics pass over this set launched, per run of its plan (k3_run writes a row where it has settled it)
   int32_t k3_last[2][12] = {}; int32_t k3_last_n = 0;
+  // khg_utts_k1_last: what the last khg_loglikes* call on this set chose and launched (khg_k1.hip writes each word where the decision is
+  // settled; the K1L_* indices there); k1_last[0] = 0 until the first call
+  int32_t k1_last[KHG_K1_LAST_WORDS] = {};
   // k3_accumulate_wave16's split feature records (khg_k3.hip: k3_planes), keyed by the model-derived exponents they were made with
   void* k3x_d = nullptr; int64_t k3x_bytes = 0, k3x_packs = 0; std::vector<int32_t> k3x_key; bool k3x_used = false;
   // khg_acc_stats_post: the flattened entries (row, id, weight), their sort buffers and bucket bounds -- sized by the ENTRY count and

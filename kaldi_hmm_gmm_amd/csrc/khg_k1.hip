@@ -11,6 +11,18 @@
 
 // ------------------------------------------------------------------------------------------
 // K1
+// khg_utts_k1_last: the words of khg_utts::k1_last (include/khg_hip.h), stored on the host where each decision is settled
+enum { K1L_SET, K1L_FORM, K1L_ASKED, K1L_DECLINED, K1L_K, K1L_MODE, K1L_PACK, K1L_PERSISTENT, K1L_GRID, K1L_CHUNKS, K1L_PER, K1L_ORDER,
+       K1L_TAIL_SHIFT, K1L_SHIFT_MODE, K1L_NF, K1L_ALIGNED, K1L_INTERLEAVE, K1L_NB_SLICES /* 8 words */, K1L_REPACKED = K1L_NB_SLICES + 8, K1L_REPAIRED };
+static_assert(K1L_REPAIRED + 1 == KHG_K1_LAST_WORDS, "khg_utts_k1_last: the record's layout");
+static int k1l_form(int form) {
+  return form == KHG_K1_F16X2 ? KHG_K1L_F16X2 : form == KHG_K1_FP32_PDF ? KHG_K1L_PDF : form == KHG_K1_FP32_UTT ? KHG_K1L_UTT : KHG_K1L_F16X2S;
+}
+extern "C" int khg_utts_k1_last(const khg_utts* u, int32_t out[KHG_K1_LAST_WORDS]) {
+  if (!u || !out) return khg_set_error(KHG_E_ARG, "khg_utts_k1_last: bad arguments");
+  std::copy(u->k1_last, u->k1_last + KHG_K1_LAST_WORDS, out);
+  return KHG_OK;
+}
 template <int KQ, int NF, int WPS>
 static void launch_k1(khg_ctx* ctx, const K1Args& a, int nchunks, bool aligned, hipStream_t s) {
   if (aligned) KHG_LAUNCH(ctx, (k1_loglikes<KQ, NF, true, WPS>), dim3(nchunks), dim3(256), 0, s, a);
@@ -40,6 +52,7 @@ static int loglikes_wide(khg_ctx* ctx, const khg_model* m, khg_utts* u) {
   a.ll = u->ll_d; a.ll_off = u->ll_off_d; a.err_flag = ctx->err_flag_d; a.D = m->D;
   const size_t lds = sizeof(float) * 64 * (size_t)(m->D | 1);
   if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k1w_loglikes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  u->k1_last[K1L_FORM] = KHG_K1L_WIDE; u->k1_last[K1L_CHUNKS] = u->k1_last[K1L_GRID] = u->n_wchunks; u->k1_last[K1L_PER] = 64;
   if (u->n_wchunks > 0) {
     KernelTimer kt(ctx, "k1_loglikes");
     KHG_LAUNCH(ctx, k1w_loglikes, dim3(u->n_wchunks), dim3(256), lds, ctx->stream, a);
@@ -76,6 +89,7 @@ static int loglikes_pdf_major(khg_ctx* ctx, const khg_model* m, khg_utts* u, boo
     DEVFREE(xutt_d);
     if (rc) return rc;
     u->xpl_kq = m->KQ;
+    if (nx > 0) u->k1_last[K1L_REPACKED] |= 1;
   }
   if (!u->p_ents_d || u->p_reach != (int)reachable_only || u->p_P != m->P || u->p_goff != m->gauss_off) {
     DEVFREE(u->p_ents_d); DEVFREE(u->p_slices_d);
@@ -138,6 +152,9 @@ static int loglikes_pdf_major(khg_ctx* ctx, const khg_model* m, khg_utts* u, boo
   a.xpl = u->xpl_d; a.utt_xtile_off = u->utt_xtile_off_d; a.frame_off = u->frame_off_d;
   a.ents = u->p_ents_d; a.slices = u->p_slices_d; a.wimg = m->wimg_d; a.pdf_tile_off = m->pdf_tile_off_d;
   a.gauss_off = m->gauss_off_d; a.ll = u->ll_d; a.ll_off = u->ll_off_d; a.err_flag = ctx->err_flag_d;
+  u->k1_last[K1L_FORM] = KHG_K1L_PDF; u->k1_last[K1L_K] = m->KQ; u->k1_last[K1L_CHUNKS] = u->k1_last[K1L_GRID] = u->p_nslices;
+  u->k1_last[K1L_PER] = std::max(1, ctx->opt[KHG_OPT_K1P_TS]);
+  for (int nb = 1; nb <= 8; ++nb) u->k1_last[K1L_NB_SLICES + nb - 1] = u->p_grp[nb];
   if (u->p_nslices > 0) {
     KernelTimer kt(ctx, "k1_loglikes");
     int first = 0;
@@ -343,7 +360,7 @@ static int loglikes_f16x2(khg_ctx* ctx, khg_model* m, khg_utts* u, bool reachabl
   std::vector<float> xk;
   int rc = k1_maxima(ctx, m, u, &xk);
   if (rc) return rc;
-  if (!k1_split_domain(m, xk)) return 1;
+  if (!k1_split_domain(m, xk)) { u->k1_last[K1L_DECLINED] |= 1; return 1; }
   rc = ensure_x32(ctx, u, NTMAX);
   if (rc) return rc;
   // the set's planes are kept while the model still fits their scales
@@ -351,7 +368,7 @@ static int loglikes_f16x2(khg_ctx* ctx, khg_model* m, khg_utts* u, bool reachabl
   if (!have_x || !k1h_fits(u->xh_ex, xk, m->wmax)) {
     std::vector<int32_t> ex;
     k1h_balance(xk, m->wmax, &ex);
-    if (!k1h_fits(ex, xk, m->wmax)) return 1;
+    if (!k1h_fits(ex, xk, m->wmax)) { u->k1_last[K1L_DECLINED] |= 4; return 1; }
     const int64_t nx = u->n_x32;
     if (!u->xh_d || u->xh_ks != KS) {
       DEVFREE(u->xh_d);
@@ -370,6 +387,7 @@ static int loglikes_f16x2(khg_ctx* ctx, khg_model* m, khg_utts* u, bool reachabl
     }
     { int rs = sync_pageable(ctx); if (rs) return rs; }    // `ex` (pageable) is free after this
     u->xh_ks = KS; u->xh_ex = ex;
+    if (nx > 0) u->k1_last[K1L_REPACKED] |= 1;
   }
   if (m->wimgh_ex != u->xh_ex) {
     if (!m->wimgh_d || m->wimgh_tiles < m->ntiles) {
@@ -387,6 +405,7 @@ static int loglikes_f16x2(khg_ctx* ctx, khg_model* m, khg_utts* u, bool reachabl
     rc = m->wimgh_sync.after_pack(ctx->stream);
     if (rc) return rc;
     m->wimgh_ex = u->xh_ex;
+    u->k1_last[K1L_REPACKED] |= 2;
   }
   rc = ensure_walk(ctx, m, u, reachable_only);
   if (rc) return rc;
@@ -396,6 +415,8 @@ static int loglikes_f16x2(khg_ctx* ctx, khg_model* m, khg_utts* u, bool reachabl
   a.ll = u->ll_d; a.ll_off = u->ll_off_d; a.err_flag = ctx->err_flag_d;
   a.dbg = ctx->opt[KHG_OPT_K1_DBG];
   a.tbuf = nullptr;
+  u->k1_last[K1L_FORM] = KHG_K1L_F16X2; u->k1_last[K1L_K] = KS; u->k1_last[K1L_CHUNKS] = u->k1_last[K1L_GRID] = u->n_bchunks;
+  u->k1_last[K1L_PER] = 8 * NTMAX; u->k1_last[K1L_ORDER] = ctx->opt[KHG_OPT_K1_ORDER];
 #ifdef K1H_TIMING
   uint64_t* tbuf_d = nullptr;
   if (u->n_bchunks > 0) {
@@ -482,7 +503,7 @@ static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
   std::vector<float> xk;
   int rc = k1_maxima(ctx, m, u, &xk);
   if (rc) return rc;
-  if (!k1_split_domain(m, xk)) return 1;
+  if (!k1_split_domain(m, xk)) { u->k1_last[K1L_DECLINED] |= 1; return 1; }
   // exponents: every feature column peaks in [2^14, 2^15) (the set's own property), the largest weight column too (S)
   std::vector<int32_t> ex((size_t)K, 0), ew((size_t)K, 0);
   for (int k = 0; k < K; ++k) if (xk[(size_t)k] > 0.0f) ex[(size_t)k] = 14 - std::ilogb(xk[(size_t)k]);
@@ -510,13 +531,16 @@ static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
   bool shared = m->xs_ex_seen.size() == ex.size();
   if (shared) for (int k = 0; k < K; ++k) ex[(size_t)k] = std::min(ex[(size_t)k], m->xs_ex_seen[(size_t)k]);
   if (!scales()) {
-    if (!shared || ex == ex_own) return 1;
+    if (!shared || ex == ex_own) { u->k1_last[K1L_DECLINED] |= 2; return 1; }
     ex = ex_own;
-    if (!scales()) return 1;
+    if (!scales()) { u->k1_last[K1L_DECLINED] |= 2; return 1; }
   }
   m->xs_ex_seen = ex;
   rc = ensure_x32_layout(ctx, u);
   if (rc) return rc;
+  // (the order and the cap are the plan's: the chunks are planned once per set)
+  const int order = (ctx->opt[KHG_OPT_K1_ORDER] == 0 && KS == 10 && !u->small) ? 4 : ctx->opt[KHG_OPT_K1_ORDER];
+  const int per = (u->small && u->n_utt <= 2) ? std::min(NMAX, 3) : NMAX;
   if (!u->schunks_d || u->schunk_nmax != NMAX) {
     DEVFREE(u->schunks_d);
     std::vector<K1sChunk> ch;
@@ -524,8 +548,7 @@ static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
     //  over more workgroups; the W tiles are re-read per chunk from the cache, a band that crosses chunks keeps its aligned tiles)
     // (D > 40: the W image does not fit the Infinity Cache and an utterance is two or three chunks -- their order puts siblings on one XCD:
     //  K1 55.6 -> 52.2 ms at 10 000 x 128 x 80 / 20 000 utterances; at D <= 40 it changes nothing: 56.9 ms either way)
-    const int order = (ctx->opt[KHG_OPT_K1_ORDER] == 0 && KS == 10 && !u->small) ? 4 : ctx->opt[KHG_OPT_K1_ORDER];
-    plan_x32_chunks(u, (u->small && u->n_utt <= 2) ? std::min(NMAX, 3) : NMAX, order, &ch);
+    plan_x32_chunks(u, per, order, &ch);
     rc = u_upload(ctx, u, &u->schunks_d, ch);
     if (rc) return rc;
     { int rs = sync_pageable(ctx); if (rs) return rs; }
@@ -551,6 +574,7 @@ static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
     }
     { int rs = sync_pageable(ctx); if (rs) return rs; }    // `ex` (pageable) is free after this
     u->xs_ks = KS; u->xs_ex = ex;
+    if (nx > 0) u->k1_last[K1L_REPACKED] |= 1;
   }
   // the model's image for these exponents
   std::vector<int32_t> key(ex);
@@ -581,6 +605,7 @@ static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
     rc = m->wimgs_sync.after_pack(ctx->stream);
     if (rc) return rc;
     m->wimgs_key = key;
+    u->k1_last[K1L_REPACKED] |= 2;
   }
   // models of small pdfs (all <= 8 / <= 16 Gaussians, D <= 40): 4 / 2 pdfs share one MFMA tile (k1s_loglikes_packed)
   int maxG = 0;
@@ -642,6 +667,9 @@ static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
   a.mfloor = -3.0e38f / std::max(1.0f, a.c1);
   a.ubound = (band || tail_shift) ? m->ubound_d : nullptr; a.repair_status = nullptr; a.repair_bit = 0; a.stamps = nullptr;
   u->ll_mode = band ? 2 : (reachable_only ? 1 : 0);
+  u->k1_last[K1L_MODE] = u->ll_mode;
+  u->k1_last[K1L_FORM] = KHG_K1L_F16X2S; u->k1_last[K1L_K] = KS; u->k1_last[K1L_PACK] = pack; u->k1_last[K1L_CHUNKS] = u->n_schunks;
+  u->k1_last[K1L_PER] = per; u->k1_last[K1L_ORDER] = order; u->k1_last[K1L_TAIL_SHIFT] = tail_shift; u->k1_last[K1L_SHIFT_MODE] = shift_mode;
   if (u->n_schunks > 0) {
     rc = m->wimgs_sync.before_read(ctx->stream);
     if (rc) return rc;
@@ -679,6 +707,7 @@ static int loglikes_f16x2s(khg_ctx* ctx, khg_model* m, khg_utts* u, int reach) {
       if (rc) return rc;
       HIPCHK(hipMemsetAsync(ctx->k1_next_d, 0, sizeof(int32_t), ctx->stream));
     }
+    u->k1_last[K1L_PERSISTENT] = persistent; u->k1_last[K1L_GRID] = persistent ? pgrid : u->n_schunks;
     // KHG_OPT_K1_PROF: boundary stamps of every chunk (a diagnostic: the launch is followed by a download and a wait)
     long long* stamps_d = nullptr;
     if (ctx->opt[KHG_OPT_K1_PROF] && pack == 1) {
@@ -718,6 +747,9 @@ static int loglikes_impl(khg_ctx* ctx, const khg_model* m, khg_utts* u, int reac
   if (u->pdf_first.size() != u->pdfs.size()) reach = 0;
   const bool reachable_only = reach != 0;
   u->ll_mode = reachable_only ? 1 : 0;
+  std::fill(u->k1_last, u->k1_last + KHG_K1_LAST_WORDS, 0);      // khg_utts_k1_last: this call's record from here on
+  u->k1_last[K1L_SET] = 1; u->k1_last[K1L_FORM] = KHG_K1L_NONE; u->k1_last[K1L_ASKED] = k1l_form(ctx->opt[KHG_OPT_K1_FORM]);
+  u->k1_last[K1L_MODE] = u->ll_mode;
   if (m->D != u->D) return khg_set_error(KHG_E_RUNTIME, "Dim mismatch: data dim = " + std::to_string(u->D) + " vs. model dim = " + std::to_string(m->D));
   if (u->pdfs_checked_P != m->P) {     // once per (set, model size): 7 M entries at the bench size, 1.5 ms of host time per call
     for (int32_t p : u->pdfs)
@@ -753,6 +785,7 @@ static int loglikes_impl(khg_ctx* ctx, const khg_model* m, khg_utts* u, int reac
     int maxG = 0;
     for (int p = 0; p < m->P; ++p) maxG = std::max(maxG, m->gauss_off[p + 1] - m->gauss_off[p]);
     if (form == KHG_K1_FP32_PDF && maxG <= 128) return loglikes_pdf_major(ctx, m, u, reachable_only);
+    if (form == KHG_K1_FP32_PDF) u->k1_last[K1L_DECLINED] |= 8;
   }
   if (!u->chunks_d || u->chunk_kq != m->KQ * 16 + k1_nf(ctx, m->KQ)) {
     DEVFREE(u->chunks_d);
@@ -786,6 +819,8 @@ static int loglikes_impl(khg_ctx* ctx, const khg_model* m, khg_utts* u, int reac
   a.interleave = reachable_only ? 1 : 0;
   if (ctx->opt[KHG_OPT_K1_INTERLEAVE] >= 0) a.interleave = ctx->opt[KHG_OPT_K1_INTERLEAVE];
   const bool aligned = (m->D % 4 == 0) && ((reinterpret_cast<uintptr_t>(u->feats_d) & 15) == 0);
+  u->k1_last[K1L_FORM] = KHG_K1L_UTT; u->k1_last[K1L_K] = m->KQ; u->k1_last[K1L_CHUNKS] = u->k1_last[K1L_GRID] = u->n_chunks;
+  u->k1_last[K1L_NF] = k1_nf(ctx, m->KQ); u->k1_last[K1L_PER] = 4 * k1_nf(ctx, m->KQ); u->k1_last[K1L_ALIGNED] = aligned; u->k1_last[K1L_INTERLEAVE] = a.interleave;
   if (u->n_chunks > 0) {
     KernelTimer kt(ctx, "k1_loglikes");
     if (m->KQ == 10 && k1_nf(ctx, 10) == 6) launch_k1<10, 6, 2>(ctx, a, u->n_chunks, aligned, ctx->stream);
@@ -889,6 +924,7 @@ int k1_band_repair(khg_ctx* ctx, khg_utts* u, int32_t* status_d, int repair_bit,
       HIPCHK(hipFuncSetAttribute((const void*)k1s_repair<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
       KHG_LAUNCH(ctx, (k1s_repair<10>), dim3(gr), dim3(512), lds_r, side, ra, (int)u->n_schunks);
     }
+    u->k1_last[K1L_REPAIRED] = 1;
   }
   HIPCHK(hipGetLastError());
   return bm->wimgs_sync.after_read(side);

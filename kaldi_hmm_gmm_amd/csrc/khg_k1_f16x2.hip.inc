@@ -244,8 +244,8 @@ __device__ __forceinline__ void k1h_wave(const K1hArgs& a, const K1bChunk& ck, c
 #pragma unroll
   for (int f = 0; f < NX; ++f) { m_run[f] = K1_MFLOOR; s_run[f] = 0.0f; }
   k1b_f32x16 accm[2], accc[2];
-  struct Pend { int live, last, jrow; };       // the chain whose epilogue is still owed (wave-uniform)
-  Pend pend{0, 0, 0};
+  struct Pend { int live, last, jrow, ef; };   // the chain whose epilogue is still owed (wave-uniform); ef: its pdf's first needed 16-frame tile
+  Pend pend{0, 0, 0, 0};
 
   // online log-sum-exp update of frame tile F from accumulator pair R (pure VALU, no memory: it is meant to be interleaved)
   auto lse_update = [&](auto r_c, auto f_c) {
@@ -269,12 +269,13 @@ __device__ __forceinline__ void k1h_wave(const K1hArgs& a, const K1bChunk& ck, c
     m_run[F] = mnew;
   };
   // the pdf's last W tile went through lse_update: LL = max + log(sum), 32 consecutive floats per tile
-  auto finish = [&](auto f_c, int jrow) {
+  // (the 16 frames of a tile in front of the pdf's first needed 16-frame tile are not written: nobody reads them)
+  auto finish = [&](auto f_c, int jrow, int ef) {
     constexpr int F = decltype(f_c)::value;
     const float st = k1b_pair_sum(s_run[F]);
     const float v = m_run[F] + __builtin_amdgcn_logf(st) * LN2;
     const int t = 32 * (ck.tile0 + wk.tile[F]) + col;
-    if (kb == 0) llu[(int64_t)jrow * tpad + t] = v;
+    if (kb == 0 && (t >> 4) >= ef) llu[(int64_t)jrow * tpad + t] = v;
     if (kb == 0 && t < T && !(fabsf(v) <= 3.0e38f) && epi_on) atomicOr(a.err_flag, 1);
     m_run[F] = K1_MFLOOR;
     s_run[F] = 0.0f;
@@ -340,33 +341,33 @@ __device__ __forceinline__ void k1h_wave(const K1hArgs& a, const K1bChunk& ck, c
 
   int par = 1;                                 // NT == 1: pair holding the owed result (the first chain writes pair 0)
   auto compute = [&](const Frags& fr, int e, int jrow, int fs, bool last_on) {
-    const int last = e < 0 ? 1 : 0;
+    const int last = e < 0 ? 1 : 0, ef = (e >> 22) & 0x7f;
     if constexpr (NT == 2) {
       const bool l0 = fs == 0, l1 = fs <= 1 && last_on;
       if (l0 && l1) {
         chain(fr, I0(), I0(), I1(), pend.live && epi_on);
-        if (pend.live && pend.last) finish(I1(), pend.jrow);
+        if (pend.live && pend.last) finish(I1(), pend.jrow, pend.ef);
         chain(fr, I1(), I1(), I0(), epi_on);
-        if (last) finish(I0(), jrow);
-        pend = Pend{1, last, jrow};
+        if (last) finish(I0(), jrow, ef);
+        pend = Pend{1, last, jrow, ef};
       } else if (l1) {
-        if (pend.live) { if (epi_on) lse_update(I1(), I1()); if (pend.last) finish(I1(), pend.jrow); }
+        if (pend.live) { if (epi_on) lse_update(I1(), I1()); if (pend.last) finish(I1(), pend.jrow, pend.ef); }
         chain(fr, I1(), I1(), I0(), false);
-        pend = Pend{1, last, jrow};
+        pend = Pend{1, last, jrow, ef};
       } else if (l0) {
         chain(fr, I0(), I0(), I1(), pend.live && epi_on);
-        if (pend.live && pend.last) finish(I1(), pend.jrow);
+        if (pend.live && pend.last) finish(I1(), pend.jrow, pend.ef);
         if (epi_on) lse_update(I0(), I0());
-        if (last) finish(I0(), jrow);
-        pend = Pend{0, 0, 0};
+        if (last) finish(I0(), jrow, ef);
+        pend = Pend{0, 0, 0, 0};
       }
     } else if constexpr (NT == 1) {
       if (fs == 0 && last_on) {
         if (par) { chain(fr, I0(), I0(), I0(), pend.live && epi_on); }
         else { chain(fr, I1(), I0(), I0(), pend.live && epi_on); }
         par ^= 1;
-        if (pend.live && pend.last) finish(I0(), pend.jrow);
-        pend = Pend{1, last, jrow};
+        if (pend.live && pend.last) finish(I0(), pend.jrow, pend.ef);
+        pend = Pend{1, last, jrow, ef};
       }
     }
   };
@@ -427,11 +428,11 @@ __device__ __forceinline__ void k1h_wave(const K1hArgs& a, const K1bChunk& ck, c
     wait_group(en);
   }
   if constexpr (NT == 2) {
-    if (pend.live) { if (epi_on) lse_update(I1(), I1()); if (pend.last) finish(I1(), pend.jrow); }
+    if (pend.live) { if (epi_on) lse_update(I1(), I1()); if (pend.last) finish(I1(), pend.jrow, pend.ef); }
   } else if constexpr (NT == 1) {
     if (pend.live) {
       if (epi_on) { if (par) lse_update(I1(), I0()); else lse_update(I0(), I0()); }
-      if (pend.last) finish(I0(), pend.jrow);
+      if (pend.last) finish(I0(), pend.jrow, pend.ef);
     }
   }
 #ifdef K1H_TIMING

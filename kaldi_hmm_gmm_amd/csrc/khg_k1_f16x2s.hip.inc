@@ -767,7 +767,9 @@ __global__ __launch_bounds__(512, 2) void k1s_loglikes_packed(K1sArgs a) {
   while (cur < nitems) {
     const int nxt_item = grab();
     // the group's pdfs (the last group repeats the utterance's last pdf: the same values go to the same row twice)
-    int tile[PACK], need = 255;
+    // (the group is computed from the earliest first needed tile among its pdfs; a pdf's own earlier tiles are not WRITTEN: their
+    //  values go to the dump line, the cells nobody reads stay as they were, as in the one-pdf kernel)
+    int tile[PACK], ndq[PACK], need = 255;
     float* row[PACK];
 #pragma unroll
     for (int q = 0; q < PACK; ++q) {
@@ -775,6 +777,7 @@ __global__ __launch_bounds__(512, 2) void k1s_loglikes_packed(K1sArgs a) {
       const K1sUnit* pu = units + j;
       tile[q] = __builtin_amdgcn_readfirstlane(pu->tile0);
       const int nd = (__builtin_amdgcn_readfirstlane(pu->info) >> 16) & 0xff;
+      ndq[q] = nd - ck.tile0;
       need = nd < need ? nd : need;
       row[q] = llu + (int64_t)j * tpad;
     }
@@ -810,15 +813,15 @@ __global__ __launch_bounds__(512, 2) void k1s_loglikes_packed(K1sArgs a) {
       for (; f + 1 < n; f += 2) {
         chain(acc0, gc, A, acc1, lds + (f + 1) * XTB);
 #pragma unroll
-        for (int q = 0; q < PACK; ++q) pend[q] = row[q] + 32 * f;
+        for (int q = 0; q < PACK; ++q) pend[q] = f >= ndq[q] ? row[q] + 32 * f : a.dump;
         chain(acc1, gc, A, acc0, lds + (f + 2 < n ? f + 2 : 0) * XTB);
 #pragma unroll
-        for (int q = 0; q < PACK; ++q) pend[q] = row[q] + 32 * (f + 1);
+        for (int q = 0; q < PACK; ++q) pend[q] = f + 1 >= ndq[q] ? row[q] + 32 * (f + 1) : a.dump;
       }
       if (f < n) {
         chain(acc0, gc, A, acc1, lds);
 #pragma unroll
-        for (int q = 0; q < PACK; ++q) pend[q] = row[q] + 32 * f;
+        for (int q = 0; q < PACK; ++q) pend[q] = f >= ndq[q] ? row[q] + 32 * f : a.dump;
         acc1 = acc0;
       }
       btile = 0;

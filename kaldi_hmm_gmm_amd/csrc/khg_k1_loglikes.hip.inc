@@ -259,7 +259,9 @@ __device__ __forceinline__ void k1_wave(const K1Args& a, const K1Chunk& ck, floa
   // wave-private LDS transpose ([f][frame][quarter]) so that each LANE finishes one (tile, frame)
   // pair -- 64 pairs per round instead of 16 -- and the LL row is written 256 B contiguous.
   // LL = max + log(sum).
-  auto epilogue_merge = [&](int wj, int fs) {
+  // (efa: the pdf's first needed 16-frame tile of the utterance; tiles in front of it that were computed all the same -- the
+  //  compiled variants skip at most KFS -- are not written: nobody reads them)
+  auto epilogue_merge = [&](int wj, int fs, int efa) {
     float* mm_ = mrg;                             // [NX][16][4] maxima
     float* ms_ = mrg + ((NX + 3) / 4) * 256;      // [NX][16][4] sums (regions padded to whole rounds)
 #pragma unroll
@@ -288,7 +290,7 @@ __device__ __forceinline__ void k1_wave(const K1Args& a, const K1Chunk& ck, floa
       const int f = 4 * rd + q;
       const bool live = f < NA && f >= fs;       // tiles the pdf does not need yet were skipped: nothing to write
       const int t = ck.t0 + (f == NA - 1 ? wk.last_tile : wk.first + wk.stride * f) * 16 + r;
-      if (live && t < tpad) llu[(int64_t)wj * tpad + t] = v;
+      if (live && t < tpad && (t >> 4) >= efa) llu[(int64_t)wj * tpad + t] = v;
       if (live && t < T && !(fabsf(v) <= 3.0e38f)) atomicOr(a.err_flag, 1);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -304,7 +306,7 @@ __device__ __forceinline__ void k1_wave(const K1Args& a, const K1Chunk& ck, floa
     m_h = K1_MFLOOR;
     s_h = 0.0f;
   };
-  auto half_finish = [&](int par, int tip, int wj) {
+  auto half_finish = [&](int par, int tip, int wj, int efa) {
     const float* sl = shr + ((wk.sidx * 2 + par) * 2 + tip) * 256;
     const f32x4 ma = *reinterpret_cast<const f32x4*>(sl + r * 4), sa = *reinterpret_cast<const f32x4*>(sl + 64 + r * 4);
     const f32x4 mb = *reinterpret_cast<const f32x4*>(sl + 128 + r * 4), sb = *reinterpret_cast<const f32x4*>(sl + 192 + r * 4);
@@ -320,7 +322,7 @@ __device__ __forceinline__ void k1_wave(const K1Args& a, const K1Chunk& ck, floa
     const f32x2 tt = (t0 + t1) + (t2 + t3);
     const float v = M + __builtin_amdgcn_logf(tt[0] + tt[1]) * 0.69314718055994530942f;
     const int t = ck.t0 + wk.half_tile * 16 + r;
-    if (q == 0 && t < tpad) llu[(int64_t)wj * tpad + t] = v;
+    if (q == 0 && t < tpad && (t >> 4) >= efa) llu[(int64_t)wj * tpad + t] = v;
     if (q == 0 && t < T && !(fabsf(v) <= 3.0e38f)) atomicOr(a.err_flag, 1);
   };
 
@@ -329,6 +331,7 @@ __device__ __forceinline__ void k1_wave(const K1Args& a, const K1Chunk& ck, floa
   int pair = 0;                               // which pair of LDS buffers holds the current two tiles
   int j = 0;                                  // local pdf index of tile `it`
   int pend0 = -1, pend1 = -1;                 // pdfs whose half-tile partials were published in the previous interval
+  int pend0e = 0, pend1e = 0;                 // ... and their first needed 16-frame tiles
   for (int it = 0; it < ntl; it += 2) {
     // entries it, it+1 come from ent_cur; it+2, it+3 from ent_cur or (at a block edge) ent_nxt
     const int li = it & 63;
@@ -345,15 +348,15 @@ __device__ __forceinline__ void k1_wave(const K1Args& a, const K1Chunk& ck, floa
       const int nb = (it + 2) + 64 + lane;
       ent_nxt = nb < ntl ? tl[nb] : 0;
     }
-    int cur0 = -1, cur1 = -1;
+    int cur0 = -1, cur1 = -1, cur0e = 0, cur1e = 0;
     if (WORK) {
       if (HALF) {                             // finish what both halves published before the last barrier
-        if (pend0 >= 0 && (pend0 & 1) == wk.hsel) half_finish(pair ^ 1, 0, pend0);   // the two owners alternate by pdf
-        if (pend1 >= 0 && (pend1 & 1) == wk.hsel) half_finish(pair ^ 1, 1, pend1);
+        if (pend0 >= 0 && (pend0 & 1) == wk.hsel) half_finish(pair ^ 1, 0, pend0, pend0e);   // the two owners alternate by pdf
+        if (pend1 >= 0 && (pend1 & 1) == wk.hsel) half_finish(pair ^ 1, 1, pend1, pend1e);
       }
       // one W tile: MFMA phase + epilogue over the wave's tiles the pdf needs (full tile f is frame tile
       // first + stride*f of the chunk; needed iff it is not wholly before the pdf's first readable frame)
-      auto step = [&](int e, int bufidx, int tip, int& cur) {
+      auto step = [&](int e, int bufidx, int tip, int& cur, int& cure) {
         const int ef = ((e >> 22) & 0x7f) - ef0;                       // first needed frame tile, chunk-relative
         int fs = ef <= wk.first ? 0 : (wk.stride == 4 ? (ef - wk.first + 3) >> 2 : ef - wk.first);
         fs = fs > KFS ? KFS : fs;                                      // compiled variants: 0..KFS (less skipping is still correct)
@@ -361,21 +364,21 @@ __device__ __forceinline__ void k1_wave(const K1Args& a, const K1Chunk& ck, floa
         else if (fs == 1) { mfma_phase(bufidx, std::integral_constant<int, (NA > 1 ? 1 : 0)>()); epilogue_main(std::integral_constant<int, (NA > 1 ? 1 : 0)>()); }
         else { mfma_phase(bufidx, std::integral_constant<int, 0>()); epilogue_main(std::integral_constant<int, 0>()); }
         if (e < 0) {
-          if (NA > 0) epilogue_merge(j, fs);
-          if (HALF) { half_publish(pair, tip); cur = j; }
+          if (NA > 0) epilogue_merge(j, fs, (e >> 22) & 0x7f);
+          if (HALF) { half_publish(pair, tip); cur = j; cure = (e >> 22) & 0x7f; }
           ++j;
         }
       };
-      step(e0, 2 * pair, 0, cur0);
-      if (has1) step(e1, 2 * pair + 1, 1, cur1);
+      step(e0, 2 * pair, 0, cur0, cur0e);
+      if (has1) step(e1, 2 * pair + 1, 1, cur1, cur1e);
     }
-    pend0 = cur0; pend1 = cur1;
+    pend0 = cur0; pend1 = cur1; pend0e = cur0e; pend1e = cur1e;
     __syncthreads();  // the next pair's DMA has landed (vmcnt(0) + barrier); this pair is free
     pair ^= 1;
   }
   if (HALF) {
-    if (pend0 >= 0 && (pend0 & 1) == wk.hsel) half_finish(pair ^ 1, 0, pend0);
-    if (pend1 >= 0 && (pend1 & 1) == wk.hsel) half_finish(pair ^ 1, 1, pend1);
+    if (pend0 >= 0 && (pend0 & 1) == wk.hsel) half_finish(pair ^ 1, 0, pend0, pend0e);
+    if (pend1 >= 0 && (pend1 & 1) == wk.hsel) half_finish(pair ^ 1, 1, pend1, pend1e);
   }
 }
 

@@ -696,6 +696,22 @@ struct KUtts {
     }
     return out;
   }
+  // khg_utts_k1_last: what the last loglikes() call on the set chose and launched; None before the first call
+  py::object k1_last() {
+    static const char* const forms[] = {"none", "f16x2s", "f16x2", "pdf", "utt", "wide"};
+    static const char* const keys[] = {"declined", "K", "mode", "pack", "persistent", "grid", "chunks", "per", "order", "tail_shift", "shift_mode",
+                                       "nf", "aligned", "interleave"};
+    int32_t o[KHG_K1_LAST_WORDS];
+    Check(khg_utts_k1_last(h, o));
+    if (!o[0]) return py::none();
+    py::dict d;
+    d["form"] = forms[o[1] >= 0 && o[1] < 6 ? o[1] : 0]; d["asked"] = forms[o[2] >= 0 && o[2] < 6 ? o[2] : 0];
+    for (int i = 0; i < 14; ++i) d[keys[i]] = o[3 + i];
+    py::list nb;
+    for (int i = 0; i < 8; ++i) nb.append(o[17 + i]);
+    d["nb_slices"] = nb; d["repacked"] = o[25]; d["repaired"] = o[26];
+    return d;
+  }
   // khg_utts_k2_ladder: align() would run the ladder form of that kernel
   bool k2_ladder(py::object ctx_o) {
     int32_t o = 0;
@@ -1176,7 +1192,7 @@ PYBIND11_MODULE(_kaldi_hmm_gmm_amd, m) {
       .def_property_readonly("h", [](KUtts& x) { return reinterpret_cast<uintptr_t>(x.h); })
       .def_readonly("ctx", &KUtts::ctx_obj).def_readonly("frame_off", &KUtts::frame_off).def_readonly("n_utt", &KUtts::n_utt)
       .def_readonly("dim", &KUtts::dim)
-      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("k2_ladder", &KUtts::k2_ladder, py::arg("ctx")).def("k3_planes", &KUtts::k3_planes).def("k3_last", &KUtts::k3_last).def("k2_tail", &KUtts::k2_tail).def("pdf_first_frames", &KUtts::pdf_first_frames)
+      .def("set_pdf_list", &KUtts::set_pdf_list).def("features_changed", &KUtts::features_changed).def("pdf_lists", &KUtts::pdf_lists).def("k2_plan", &KUtts::k2_plan, py::arg("ctx")).def("k2_ladder", &KUtts::k2_ladder, py::arg("ctx")).def("k3_planes", &KUtts::k3_planes).def("k3_last", &KUtts::k3_last).def("k1_last", &KUtts::k1_last).def("k2_tail", &KUtts::k2_tail).def("pdf_first_frames", &KUtts::pdf_first_frames)
       .def("pdf_last_frames", &KUtts::pdf_last_frames)
       .def("loglikes", &KUtts::loglikes, py::arg("model"), py::arg("reachable_only") = false, py::arg("band") = false)
       .def("loglikes_layout", &KUtts::loglikes_layout).def("download_loglikes", &KUtts::download_loglikes)

@@ -173,3 +173,10 @@ def test_script_function_matches_reference(f):
         if a["has_default"]:
             assert repr(p.default) == a["default"] or p.default == eval(a["default"]), "%s.%s default %r vs %s" % (f["name"], a["name"], p.default, a["default"])
     assert all(p.default is not p.empty for p in ps[len(want):])
+
+
+@pytest.mark.parametrize("name", ["k1_last", "k3_last", "k2_tail", "k3_planes"])
+def test_device_set_reports_what_ran(name):
+    """the library's own getters on UtteranceSet (no counterpart in the reference): bound, no argument besides the set"""
+    ovl = overloads(getattr(khg.UtteranceSet, name), name)
+    assert ovl == [([], [])], ovl
