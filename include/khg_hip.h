@@ -708,6 +708,51 @@ typedef struct { int64_t in_states, in_arcs, out_states, out_arcs, max_hist; } k
 int khg_lattices_lm_rescore(khg_ctx *ctx, const khg_lattices *l, const khg_lm *lm, float scale, int32_t hist_factor,
                             int32_t *status_h, khg_lm_rescore_stats *stats, khg_lattices **out);
 
+/* ---- K2D: determinizing resident lattices (lattice-determinize-pruned) ------------------------------------------- */
+typedef struct {
+  int64_t in_states, in_arcs;      /* of the input */
+  int64_t pruned_states;           /* of X, the beam-pruned input (every utterance that reached step 2) */
+  int64_t det_states;              /* determinized states D, summed over the utterances that succeeded */
+  int64_t out_states, out_arcs;    /* of the result */
+  int64_t max_subset, max_closure; /* the largest |K| and the largest closure among the utterances that succeeded */
+} khg_det_stats;
+/* lattice-determinize-pruned: a NEW, ordinary handle in which, under the pair (graph_scale, acoustic_scale), every word sequence of
+ * the beam-pruned input has exactly ONE path, the cheapest one it has there, and every arc is a copy of an input arc (a path costs in
+ * the result, bit for bit, what it costs in the input).  No compact lattice and no string repository: every input state s is split
+ * by the determinized states D whose closure holds it, and an element (D, s) keeps its single best in-arc.
+ * Everything is float, one rounding per operation, no contraction.  A weight is a pair (a, b); (a, b) is BETTER than (a', b') when
+ * fl(a + b) < fl(a' + b'), or they are equal and a < a' (khg_lattices_best_path's order).  An arc weighs (fl(gs * graph_cost),
+ * fl(as * acoustic_cost)), the second 0 on an arc with ilabel 0, as for best_path; sums are taken component by component.
+ * Per utterance, in this order:
+ *   empty input                                 KHG_LAT_NO_PATH, stays empty
+ *   an arc that does not go to a higher state   KHG_LAT_EPS_LOOP, empty (as khg_lattices_lm_rescore)
+ *   1. X = khg_lattices_prune(l, gs, as, beam); without a path its status (KHG_LAT_NO_PATH), empty.  T = the frame of X's last state.
+ *   2. An ARRIVAL is a set I = {s -> cost}.  Normalise: subtract, component by component, the best cost of I (ties: the lowest s).
+ *      Closure, over the states s of X in ascending number: the incumbent of s is its normalised initial cost if it has one; then every
+ *      in-arc of s with olabel == 0 whose source p is in the closure is tried in ascending arc number, its candidate being
+ *      (fl(E[p].a + w.a), fl(E[p].b + w.b)); a candidate replaces the incumbent only when BETTER (always when there is none).  A state
+ *      with an incumbent is in the closure: E[s], and pred[s] = the arc that gave it, or "external".  An initial state whose pred is an
+ *      arc is DOMINATED.  K = the other initial states ascending, R = their E.  The arrival IS the lowest-numbered D with the same K and
+ *      fabs(fl(R_i.a - R'_i.a)) <= delta and the same for .b, for every i; otherwise it becomes a new D, the next number, which keeps
+ *      K, R, E and pred.
+ *   3. D0 = the arrival of {start: (0, 0)}.  For the D in ascending number: every arc (p -> dest, olabel w != 0) of the closure states
+ *      p, ascending arc number, is a candidate fl(E[p] + weight) for (w, dest), kept only when BETTER than the one kept before.  For
+ *      w ascending, the kept {dest -> cost} is an arrival D'; for each of its dest that is not dominated the kept arc becomes the
+ *      arc (D, p) -> (D', dest) of the result.
+ *      Scratch: the elements (D, s) of all closures together number more than min(state_factor * states(X), 2^31 - 1), or their
+ *      states' arcs more than min(state_factor * arcs(X), 2^31 - 1): KHG_LAT_SCRATCH, empty (call again with a larger state_factor).
+ *   4. Per D, the closure state of frame T with a final cost that has the best (fl(E[s].a + fl(gs * final_cost)), E[s].b) (ties: the
+ *      lowest s) keeps its final_cost; every other element's becomes +inf.
+ *   5. Y: one state per element, ordered by (s, D); frame, graph_state, tot_cost, extra_cost of s (the last two stale).  The arcs of
+ *      (D, p) are those arcs of p, in p's order, that are kept: one with olabel == 0 iff pred_D[dest] is that arc (to (D, dest)), one
+ *      with a word iff step 3 made it.  Fields copied, nextstate renumbered.  start = (start, D0).  Y is top-sorted.
+ *   6. The result is khg_lattices_prune(Y, gs, as, beam): it trims the dead ends and the finals that lost.  KHG_LAT_SUCCEEDED.
+ * graph_scale / acoustic_scale as for khg_lattices_prune; beam and delta finite and >= 0; state_factor >= 1; otherwise KHG_E_ARG.
+ * status_h[n_utt], stats (either may be NULL); khg_lattices_op_status answers for the handle.  The result does not depend on the
+ * batch and repeats from run to run.  Synchronous: the two prunes and one synchronisation per chunk that sizes Y. */
+int khg_lattices_determinize(khg_ctx *ctx, const khg_lattices *l, float graph_scale, float acoustic_scale, float beam, float delta,
+                             int32_t state_factor, int32_t *status_h, khg_det_stats *stats, khg_lattices **out);
+
 /* ---- K2W: scoring resident lattices (lattice-add-penalty, lattice-oracle, score.sh's sweep, compute-wer) ---------- */
 /* lattice-add-penalty: a NEW handle, as khg_lattices_prune and khg_lattices_boost return one (the input is untouched; the chunks, the
  * device offsets and the in-arc index go along).  Every arc with olabel != 0 gets graph_cost := fl(graph_cost + word_ins_penalty), one

@@ -138,6 +138,10 @@ class LmRescoreStatsC(C.Structure):
     _fields_ = [("in_states", C.c_int64), ("in_arcs", C.c_int64), ("out_states", C.c_int64), ("out_arcs", C.c_int64), ("max_hist", C.c_int64)]
 
 
+class DetStatsC(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("in_states", "in_arcs", "pruned_states", "det_states", "out_states", "out_arcs", "max_subset", "max_closure")]
+
+
 # every symbol include/khg_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "khg_last_error": (C.c_char_p, []),
@@ -228,6 +232,7 @@ SIGNATURES = {
     "khg_lm_device_bytes": (C.c_int, [vp, c_i64p]),
     "khg_lm_score": (C.c_int, [C.c_int32, c_i32p, c_f32p, c_i32p, c_i32p, c_f32p, c_i32p, c_f32p, C.c_int32, C.c_int32, c_i32p, c_f32p]),
     "khg_lattices_lm_rescore": (C.c_int, [vp, vp, vp, C.c_float, C.c_int32, c_i32p, C.POINTER(LmRescoreStatsC), C.POINTER(vp)]),
+    "khg_lattices_determinize": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, c_i32p, C.POINTER(DetStatsC), C.POINTER(vp)]),
     "khg_lattices_add_penalty": (C.c_int, [vp, vp, C.c_float, C.POINTER(vp)]),
     "khg_lattices_oracle": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i64p, C.c_int64, c_i32p, c_i32p, c_i64p, C.c_int64, c_i32p, c_i32p]),
     "khg_lattices_wer": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i64p, C.c_int32, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p]),

@@ -599,6 +599,202 @@ LatticeLmRescored Lattice::LmRescore(const BackoffLm& lm, float scale, int hist_
   return out;
 }
 
+namespace {
+// a determinized state: K / R, and the closure in ascending state number with E, pred (-1: external) and, per arc of every closure
+// state, the determinized state its copy leads to (-1: the arc is not kept)
+struct DetState {
+  std::vector<int32_t> K, s, pred, slot_off, slot;
+  std::vector<float> Ra, Rb, a, b;
+  int32_t fin = -1;       // the closure state that keeps its final cost
+};
+
+// steps 2 to 5 of khg_lattices_determinize on the pruned lattice X (at least one state, every arc to a higher state); false: scratch
+bool DetSplit(const Lattice& X, float gs, float as, float delta, int state_factor, Lattice* Y, khg_det_stats* stats) {
+  const int N = X.NumStates();
+  const int64_t A = X.NumArcs();
+  const float INF = std::numeric_limits<float>::infinity();
+  const std::vector<int32_t>&ab = X.arc_begin, &nxt = X.nextstate, &ol = X.olabel;
+  std::vector<float> wa((size_t)A), wb((size_t)A);
+  std::vector<int32_t> src((size_t)A), in_off((size_t)N + 1, 0), in_arc((size_t)A);
+  for (int s = 0; s < N; ++s)
+    for (int32_t a = ab[(size_t)s]; a < ab[(size_t)s + 1]; ++a) {
+      src[(size_t)a] = s;
+      wa[(size_t)a] = gs * X.graph_cost[(size_t)a];
+      wb[(size_t)a] = X.ilabel[(size_t)a] != 0 ? as * X.acoustic_cost[(size_t)a] : 0.0f;
+      in_off[(size_t)nxt[(size_t)a] + 1]++;
+    }
+  for (int s = 0; s < N; ++s) in_off[(size_t)s + 1] += in_off[(size_t)s];
+  {
+    std::vector<int32_t> cur(in_off.begin(), in_off.end() - 1);
+    for (int64_t a = 0; a < A; ++a) in_arc[(size_t)cur[(size_t)nxt[(size_t)a]]++] = (int32_t)a;
+  }
+  const int64_t cap_s = std::min<int64_t>((int64_t)state_factor * N, INT32_MAX), cap_a = std::min<int64_t>((int64_t)state_factor * A, INT32_MAX);
+  const int T = X.frame[(size_t)N - 1];
+  std::vector<DetState> Ds;
+  std::vector<int32_t> cl_stamp((size_t)N, 0), in_stamp((size_t)N, 0), cl_pred((size_t)N), cl_idx((size_t)N);
+  std::vector<float> cl_a((size_t)N), cl_b((size_t)N), in_a((size_t)N), in_b((size_t)N);
+  int32_t stamp = 0;
+  int64_t used_s = 0, used_a = 0;
+  // the arrival of I (ascending states): -> the number of its determinized state, -1: scratch; cl_pred holds the arrival's own pred
+  auto arrive = [&](const std::vector<int32_t>& Is, const std::vector<float>& Ia, const std::vector<float>& Ib) -> int {
+    ++stamp;
+    size_t best = 0;
+    for (size_t i = 1; i < Is.size(); ++i)
+      if (LatLess(Ia[i], Ib[i], Ia[best], Ib[best])) best = i;
+    for (size_t i = 0; i < Is.size(); ++i) {
+      in_stamp[(size_t)Is[i]] = stamp;
+      in_a[(size_t)Is[i]] = Ia[i] - Ia[best]; in_b[(size_t)Is[i]] = Ib[i] - Ib[best];
+    }
+    DetState c;
+    int hi = Is.back();       // the highest state the closure can still reach
+    int64_t arcs = 0;
+    for (int s = Is[0]; s <= hi; ++s) {
+      bool has = in_stamp[(size_t)s] == stamp;
+      float ca = has ? in_a[(size_t)s] : 0.0f, cb = has ? in_b[(size_t)s] : 0.0f;
+      int32_t pr = -1;
+      for (int32_t j = in_off[(size_t)s]; j < in_off[(size_t)s + 1]; ++j) {
+        const int32_t a = in_arc[(size_t)j], p = src[(size_t)a];
+        if (ol[(size_t)a] != 0 || cl_stamp[(size_t)p] != stamp) continue;
+        const float ta = cl_a[(size_t)p] + wa[(size_t)a], tb = cl_b[(size_t)p] + wb[(size_t)a];
+        if (!has || LatLess(ta, tb, ca, cb)) { has = true; ca = ta; cb = tb; pr = a; }
+      }
+      if (!has) continue;
+      cl_stamp[(size_t)s] = stamp; cl_a[(size_t)s] = ca; cl_b[(size_t)s] = cb; cl_pred[(size_t)s] = pr; cl_idx[(size_t)s] = (int32_t)c.s.size();
+      c.s.push_back(s); c.a.push_back(ca); c.b.push_back(cb); c.pred.push_back(pr);
+      c.slot_off.push_back((int32_t)arcs);
+      arcs += ab[(size_t)s + 1] - ab[(size_t)s];
+      for (int32_t a = ab[(size_t)s]; a < ab[(size_t)s + 1]; ++a)
+        if (ol[(size_t)a] == 0) hi = std::max(hi, nxt[(size_t)a]);
+    }
+    for (int32_t s : Is)
+      if (cl_pred[(size_t)s] < 0) { c.K.push_back(s); c.Ra.push_back(cl_a[(size_t)s]); c.Rb.push_back(cl_b[(size_t)s]); }
+    for (size_t d = 0; d < Ds.size(); ++d) {
+      const DetState& D = Ds[d];
+      if (D.K != c.K) continue;
+      bool same = true;
+      for (size_t i = 0; i < c.K.size() && same; ++i) {
+        const float da = c.Ra[i] - D.Ra[i], db = c.Rb[i] - D.Rb[i];
+        same = std::fabs(da) <= delta && std::fabs(db) <= delta;
+      }
+      if (same) return (int)d;
+    }
+    used_s += (int64_t)c.s.size(); used_a += arcs;
+    if (used_s > cap_s || used_a > cap_a) return -1;
+    const int32_t me = (int32_t)Ds.size();
+    c.slot.assign((size_t)arcs, -1);
+    float f1 = 0.0f, f2 = 0.0f;
+    for (size_t i = 0; i < c.s.size(); ++i) {
+      const int32_t s = c.s[i], pr = c.pred[i];
+      if (pr >= 0) { const int32_t p = src[(size_t)pr]; c.slot[(size_t)(c.slot_off[(size_t)cl_idx[(size_t)p]] + (pr - ab[(size_t)p]))] = me; }
+      if (X.final_cost[(size_t)s] == INF || X.frame[(size_t)s] != T) continue;
+      const float fw = gs * X.final_cost[(size_t)s];
+      const float v1 = c.a[i] + fw, v2 = c.b[i];
+      if (c.fin < 0 || LatLess(v1, v2, f1, f2)) { c.fin = s; f1 = v1; f2 = v2; }
+    }
+    stats->max_subset = std::max<int64_t>(stats->max_subset, (int64_t)c.K.size());
+    stats->max_closure = std::max<int64_t>(stats->max_closure, (int64_t)c.s.size());
+    Ds.push_back(std::move(c));
+    return me;
+  };
+  if (arrive({X.start}, {0.0f}, {0.0f}) < 0) return false;
+  struct Cand { int32_t w, dest, arc, elem; float a, b; };
+  std::vector<Cand> cand;
+  std::vector<int32_t> Is, Iarc, Ielem;
+  std::vector<float> Ia, Ib;
+  for (size_t d = 0; d < Ds.size(); ++d) {
+    cand.clear();
+    for (size_t i = 0; i < Ds[d].s.size(); ++i) {
+      const int32_t p = Ds[d].s[i];
+      for (int32_t a = ab[(size_t)p]; a < ab[(size_t)p + 1]; ++a)
+        if (ol[(size_t)a] != 0) {
+          const float ta = Ds[d].a[i] + wa[(size_t)a], tb = Ds[d].b[i] + wb[(size_t)a];
+          cand.push_back(Cand{ol[(size_t)a], nxt[(size_t)a], a, (int32_t)i, ta, tb});
+        }
+    }
+    // by (word, dest); inside a pair the candidates stay in ascending arc number
+    std::stable_sort(cand.begin(), cand.end(), [](const Cand& x, const Cand& y) { return x.w != y.w ? x.w < y.w : x.dest < y.dest; });
+    for (size_t i = 0; i < cand.size();) {
+      Is.clear(); Ia.clear(); Ib.clear(); Iarc.clear(); Ielem.clear();
+      const int32_t w = cand[i].w;
+      while (i < cand.size() && cand[i].w == w) {
+        size_t k = i;
+        for (size_t j = i + 1; j < cand.size() && cand[j].w == w && cand[j].dest == cand[i].dest; ++j)
+          if (LatLess(cand[j].a, cand[j].b, cand[k].a, cand[k].b)) k = j;
+        Is.push_back(cand[k].dest); Ia.push_back(cand[k].a); Ib.push_back(cand[k].b); Iarc.push_back(cand[k].arc); Ielem.push_back(cand[k].elem);
+        const int32_t dest = cand[i].dest;
+        while (i < cand.size() && cand[i].w == w && cand[i].dest == dest) ++i;
+      }
+      const int d2 = arrive(Is, Ia, Ib);
+      if (d2 < 0) return false;
+      DetState& D = Ds[d];
+      for (size_t k = 0; k < Is.size(); ++k)
+        if (cl_pred[(size_t)Is[k]] < 0) D.slot[(size_t)(D.slot_off[(size_t)Ielem[k]] + (Iarc[k] - ab[(size_t)D.s[(size_t)Ielem[k]]]))] = d2;
+    }
+  }
+  stats->det_states = (int64_t)Ds.size();
+  // Y: the elements ordered by (s, D)
+  std::vector<std::vector<std::pair<int32_t, int32_t>>> of((size_t)N);      // per state: (D, its place in D's closure), D ascending
+  for (size_t d = 0; d < Ds.size(); ++d)
+    for (size_t i = 0; i < Ds[d].s.size(); ++i) of[(size_t)Ds[d].s[i]].emplace_back((int32_t)d, (int32_t)i);
+  std::vector<int64_t> first((size_t)N + 1, 0);
+  for (int s = 0; s < N; ++s) first[(size_t)s + 1] = first[(size_t)s] + (int64_t)of[(size_t)s].size();
+  Y->arc_begin.clear();
+  for (int s = 0; s < N; ++s)
+    for (const auto& e : of[(size_t)s]) {
+      const DetState& D = Ds[(size_t)e.first];
+      Y->frame.push_back(X.frame[(size_t)s]); Y->graph_state.push_back(X.graph_state[(size_t)s]);
+      Y->tot_cost.push_back(X.tot_cost[(size_t)s]); Y->extra_cost.push_back(X.extra_cost[(size_t)s]);
+      Y->final_cost.push_back(D.fin == s ? X.final_cost[(size_t)s] : INF);
+      Y->arc_begin.push_back((int32_t)Y->ilabel.size());
+      for (int32_t a = ab[(size_t)s]; a < ab[(size_t)s + 1]; ++a) {
+        const int32_t t = D.slot[(size_t)(D.slot_off[(size_t)e.second] + (a - ab[(size_t)s]))];
+        if (t < 0) continue;
+        const auto& od = of[(size_t)nxt[(size_t)a]];
+        const auto it = std::lower_bound(od.begin(), od.end(), std::make_pair(t, (int32_t)0));
+        Y->ilabel.push_back(X.ilabel[(size_t)a]); Y->olabel.push_back(ol[(size_t)a]); Y->graph_cost.push_back(X.graph_cost[(size_t)a]);
+        Y->acoustic_cost.push_back(X.acoustic_cost[(size_t)a]);
+        Y->nextstate.push_back((int32_t)(first[(size_t)nxt[(size_t)a]] + (it - od.begin())));
+      }
+    }
+  Y->arc_begin.push_back((int32_t)Y->ilabel.size());
+  Y->start = (int32_t)first[(size_t)X.start];
+  return true;
+}
+}  // namespace
+
+LatticeDeterminized Lattice::Determinize(float gs, float as, float beam, float delta, int state_factor) const {
+  const std::string who = "Lattice::Determinize: ";
+  KHG_REQUIRE(gs >= 0.0f && as >= 0.0f && std::isfinite(gs) && std::isfinite(as), who + "graph_scale and acoustic_scale must be finite and >= 0");
+  KHG_REQUIRE(std::isfinite(beam) && beam >= 0.0f, who + "beam must be finite and >= 0");
+  KHG_REQUIRE(std::isfinite(delta) && delta >= 0.0f, who + "delta must be finite and >= 0");
+  KHG_REQUIRE(state_factor >= 1, who + "state_factor must be >= 1");
+  LatticeDeterminized out;
+  auto none = std::make_shared<Lattice>();
+  none->arc_begin.push_back(0);
+  out.lattice = none;
+  const int N = NumStates();
+  out.stats.in_states = N; out.stats.in_arcs = NumArcs();
+  if (N == 0) { out.status = KHG_LAT_NO_PATH; return out; }
+  for (int s = 0; s < N; ++s)
+    for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a)
+      if (nextstate[(size_t)a] <= s) { out.status = KHG_LAT_EPS_LOOP; return out; }
+  int st = 0;
+  const std::shared_ptr<Lattice> X = Prune(beam, gs, as, &st);
+  out.status = st;
+  if (st != KHG_LAT_SUCCEEDED) return out;
+  out.stats.pruned_states = X->NumStates();
+  Lattice Y;
+  khg_det_stats ds = out.stats;
+  if (!DetSplit(*X, gs, as, delta, state_factor, &Y, &ds)) { out.status = KHG_LAT_SCRATCH; return out; }
+  const std::shared_ptr<Lattice> res = Y.Prune(beam, gs, as, &st);
+  out.status = st;
+  if (st != KHG_LAT_SUCCEEDED) return out;
+  out.stats = ds;
+  out.stats.out_states = res->NumStates(); out.stats.out_arcs = res->NumArcs();
+  out.lattice = res;
+  return out;
+}
+
 std::shared_ptr<Lattice> Lattice::AddPenalty(float word_ins_penalty) const {
   KHG_REQUIRE(std::isfinite(word_ins_penalty), "Lattice::AddPenalty: word_ins_penalty must be finite");
   auto r = std::make_shared<Lattice>(*this);

@@ -148,6 +148,13 @@ struct LatticeLmRescored {
   int64_t max_hist = 0;
 };
 
+// Lattice::Determinize: the KHG_LAT_* status, the determinized lattice (empty without KHG_LAT_SUCCEEDED) and the counts
+struct LatticeDeterminized {
+  int status = 0;
+  std::shared_ptr<Lattice> lattice;
+  khg_det_stats stats = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 // Lattice::Oracle (what khg_lattices_oracle gives for one lattice): KHG_LAT_* status (SUCCEEDED, NO_PATH, EPS_LOOP), the
 // counts (errors, insertions, deletions, substitutions; (R, 0, R, 0) without a path), the oracle path's words, its arcs, and its
 // transition-ids by frame (one entry per frame of the lattice, 0 where the path has none)
@@ -231,6 +238,10 @@ class Lattice {
   // reach it, every arc with a word given fl(scale * the LM's cost of the word) more graph cost; the rule is stated at
   // khg_lattices_lm_rescore.  The history sets may hold min(hist_factor * states, 2^31 - 1) entries together (KHG_LAT_SCRATCH).
   LatticeLmRescored LmRescore(const BackoffLm& lm, float scale = 1.0f, int hist_factor = 8) const;
+  // lattice-determinize-pruned (what khg_lattices_determinize gives for one lattice): one path per word sequence of the
+  // beam-pruned lattice, the cheapest, made of copies of its arcs; the rule is stated at khg_lattices_determinize, and this is it, serially
+  LatticeDeterminized Determinize(float graph_scale = 1.0f, float acoustic_scale = 1.0f, float beam = 10.0f, float delta = 1.0f / 1024.0f,
+                                  int state_factor = 8) const;
   // lattice-add-penalty (what khg_lattices_add_penalty gives for one lattice): a copy in which every arc with olabel != 0 has
   // graph_cost = fl(graph_cost + word_ins_penalty); everything else as stored
   std::shared_ptr<Lattice> AddPenalty(float word_ins_penalty) const;

@@ -5,7 +5,8 @@
 // (khg_k2_lattice_ops.hip.inc), its forward-backward posteriors (khg_posteriors, khg_k2_lattice_post.hip.inc) and their MPE / sMBR form
 // (khg_k2_lattice_mpe.hip.inc: the same device functions and the same host steps per chunk around a kernel of its own), and rescoring /
 // boosting (khg_lattices_rescore, khg_lattices_boost: khg_k2_lattice_rescore.hip.inc, khg_k1_cells.hip.inc), and the backoff n-gram LM
-// (khg_lm) with khg_lattices_lm_rescore (khg_k2_lattice_lm.hip.inc), and scoring (khg_lattices_add_penalty, khg_lattices_oracle,
+// (khg_lm) with khg_lattices_lm_rescore (khg_k2_lattice_lm.hip.inc), determinization (khg_lattices_determinize,
+// khg_k2_lattice_det.hip.inc), and scoring (khg_lattices_add_penalty, khg_lattices_oracle,
 // khg_lattices_wer, khg_edit_distance: khg_k2_lattice_score.hip.inc), and minimum Bayes risk decoding (khg_lattices_mbr:
 // khg_k2_lattice_mbr.hip.inc).  gfx950 only.
 //
@@ -50,6 +51,7 @@
 #include "khg_k2_lattice_rescore.hip.inc"
 #include "khg_k2_lattice_mpe.hip.inc"
 #include "khg_k2_lattice_lm.hip.inc"
+#include "khg_k2_lattice_det.hip.inc"
 #include "khg_k2_lattice_score.hip.inc"
 #include "khg_k2_lattice_mbr.hip.inc"
 
@@ -1901,6 +1903,103 @@ extern "C" int khg_lattices_lm_rescore(khg_ctx* ctx, const khg_lattices* lc, con
     stats->in_states = l->state_off[(size_t)U]; stats->in_arcs = l->arc_off[(size_t)U];
     stats->out_states = res->state_off[(size_t)U]; stats->out_arcs = res->arc_off[(size_t)U];
     for (int32_t m : mh) stats->max_hist = std::max<int64_t>(stats->max_hist, m);
+  }
+  *out = res.release();
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2D: lattice-determinize-pruned (khg_k2_lattice_det.hip.inc): prune, split every state by the determinized states that
+// hold it, prune again
+extern "C" int khg_lattices_determinize(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, float beam, float delta,
+                                        int32_t state_factor, int32_t* status_h, khg_det_stats* stats, khg_lattices** out) {
+  const std::string name = "khg_lattices_determinize", who = name + ": ";
+  if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  *out = nullptr;
+  if (lc->ctx != ctx) return other_ctx(name);
+  if (bad_scale(graph_scale) || bad_scale(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "graph_scale and acoustic_scale must be finite and >= 0");
+  if (!std::isfinite(beam) || beam < 0.0f) return khg_set_error(KHG_E_ARG, who + "beam must be finite and >= 0");
+  if (!std::isfinite(delta) || delta < 0.0f) return khg_set_error(KHG_E_ARG, who + "delta must be finite and >= 0");
+  if (state_factor < 1) return khg_set_error(KHG_E_ARG, who + "state_factor must be >= 1");
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  if (stats) *stats = khg_det_stats{0, 0, 0, 0, 0, 0, 0, 0};
+  if (U == 0) {
+    LatPtr res;
+    int rc = new_lattices(ctx, U, &res);
+    if (rc) return rc;
+    *out = res.release();
+    return KHG_OK;
+  }
+  int rc = lat_ready(ctx, l);
+  if (rc) return rc;
+  DevBlocks dv;
+  int32_t *status0_d, *status_d, *det_d, *maxk_d, *maxc_d;
+  if ((rc = dv.alloc(U, &status0_d)) || (rc = dv.alloc(U, &status_d)) || (rc = dv.alloc(U, &det_d)) || (rc = dv.alloc(U, &maxk_d)) ||
+      (rc = dv.alloc(U, &maxc_d)))
+    return rc;
+  // what is refused before anything else: an empty lattice, an arc that does not go to a higher state
+  for (const LatChunk& c : l->chunks) {
+    LoArgs q{};
+    lat_chunk_args(l, c, &q);
+    if ((rc = launch(ctx, "k2_lattice_det_check", k2_lattice_det_check, dim3((unsigned)c.n), dim3(DT_NT), 0, q, status0_d))) return rc;
+  }
+  std::vector<int32_t> st0, stx((size_t)U, 0);
+  if ((rc = download(ctx, status0_d, U, &st0))) return rc;
+  // 1. X
+  khg_lattices* xp = nullptr;
+  if ((rc = khg_lattices_prune(ctx, l, graph_scale, acoustic_scale, beam, stx.data(), &xp))) return rc;       // synchronises: st0 is there
+  LatPtr X(xp);
+  for (int u = 0; u < U; ++u)
+    if (st0[(size_t)u] == 0 && stx[(size_t)u] != KHG_LAT_SUCCEEDED) st0[(size_t)u] = stx[(size_t)u];
+  HIPCHK(hipMemcpyAsync(status0_d, st0.data(), 4 * (size_t)U, hipMemcpyHostToDevice, ctx->stream));
+  // 2. to 5. Y
+  LatPtr Y;
+  if ((rc = new_lattices(ctx, U, &Y)) || (rc = lat_ready(ctx, X.get(), kWithIndex))) return rc;
+  for (size_t k = 0; k < X->chunks.size(); ++k) {
+    const LatChunk& c = X->chunks[k];
+    DtArgs p{};
+    lat_chunk_args(X.get(), c, &p.lo);
+    p.lo.status = status_d; p.lo.o_start = Y->start_d;
+    p.status0 = status0_d; p.gs = graph_scale; p.as = acoustic_scale; p.delta = delta; p.factor = state_factor;
+    p.det_states = det_d; p.max_subset = maxk_d; p.max_closure = maxc_d;
+    const LatIndex ix = lat_index_arrays(X->idx_d[k], c);
+    p.in_begin = ix.in_begin; p.in_arc = ix.in_arc; p.arc_src = ix.arc_src;
+    p.e_stride = (int64_t)state_factor * c.ns + c.n; p.s_stride = std::max<int64_t>(c.ns, 1); p.a_stride = std::max<int64_t>(c.na, 1);
+    if ((rc = dv.alloc(DT_PER_E * p.e_stride, &p.per_e)) || (rc = dv.alloc(DT_PER_S * p.s_stride, &p.per_s)) ||
+        (rc = dv.alloc(DT_PER_A * p.a_stride, &p.per_a)) || (rc = dv.alloc(std::max<int64_t>((int64_t)state_factor * c.na, 1), &p.slot)) ||
+        (rc = dv.alloc(2 * (int64_t)c.n, &p.lo.utt_tot)) || (rc = dv.alloc(2 * ((int64_t)c.n + 1), &p.lo.utt_off)))
+      return rc;
+    LatChunk ch;
+    if ((rc = launch(ctx, "k2_lattice_det_mark", k2_lattice_det_mark, dim3((unsigned)c.n), dim3(DT_NT), 0, p)) ||
+        (rc = size_out_chunk(ctx, name, "k2_lattice_det_scan", p.lo.utt_tot, p.lo.utt_off, c.u0, c.n, Y.get(), &ch)))      // the one synchronisation that sizes Y
+      return rc;
+    lat_chunk_arrays(ch, &p.lo.out);
+    if ((rc = launch(ctx, "k2_lattice_det_fill", k2_lattice_det_fill, dim3((unsigned)c.n, stripes(chunk_max(Y->state_off, c), DT_NT, c.n)), dim3(DT_NT), 0, p)))
+      return rc;
+  }
+  std::vector<int32_t> st, nd, mk, mc;
+  if ((rc = download(ctx, status_d, U, &st)) || (rc = download(ctx, det_d, U, &nd)) || (rc = download(ctx, maxk_d, U, &mk)) ||
+      (rc = download(ctx, maxc_d, U, &mc)) || (rc = check_err_flag(ctx, name.c_str())))       // synchronises: the scratch goes with `dv`
+    return rc;
+  // 6. the result
+  khg_lattices* rp = nullptr;
+  if ((rc = khg_lattices_prune(ctx, Y.get(), graph_scale, acoustic_scale, beam, stx.data(), &rp))) return rc;
+  LatPtr res(rp);
+  for (int u = 0; u < U; ++u)
+    if (st[(size_t)u] == KHG_LAT_SUCCEEDED) st[(size_t)u] = stx[(size_t)u];
+  res->op_status = st;
+  if (status_h) std::copy(st.begin(), st.end(), status_h);
+  if (stats) {
+    stats->in_states = l->state_off[(size_t)U]; stats->in_arcs = l->arc_off[(size_t)U];
+    stats->out_states = res->state_off[(size_t)U]; stats->out_arcs = res->arc_off[(size_t)U];
+    for (int u = 0; u < U; ++u) {
+      if (st0[(size_t)u] == 0) stats->pruned_states += X->state_off[(size_t)u + 1] - X->state_off[(size_t)u];
+      if (st[(size_t)u] != KHG_LAT_SUCCEEDED) continue;
+      stats->det_states += nd[(size_t)u];
+      stats->max_subset = std::max<int64_t>(stats->max_subset, mk[(size_t)u]);
+      stats->max_closure = std::max<int64_t>(stats->max_closure, mc[(size_t)u]);
+    }
   }
   *out = res.release();
   return KHG_OK;

@@ -368,6 +368,12 @@ py::dict LmStatsDict(const khg_lm_rescore_stats& s) {
   d["in_states"] = s.in_states; d["in_arcs"] = s.in_arcs; d["out_states"] = s.out_states; d["out_arcs"] = s.out_arcs; d["max_hist"] = s.max_hist;
   return d;
 }
+py::dict DetStatsDict(const khg_det_stats& s) {
+  py::dict d;
+  d["in_states"] = s.in_states; d["in_arcs"] = s.in_arcs; d["pruned_states"] = s.pruned_states; d["det_states"] = s.det_states;
+  d["out_states"] = s.out_states; d["out_arcs"] = s.out_arcs; d["max_subset"] = s.max_subset; d["max_closure"] = s.max_closure;
+  return d;
+}
 }  // namespace
 
 void BindLattice(py::module_& m) {
@@ -459,6 +465,13 @@ void BindLattice(py::module_& m) {
         khg_lm_rescore_stats s = {l.NumStates(), l.NumArcs(), r.lattice->NumStates(), r.lattice->NumArcs(), r.max_hist};
         return py::make_tuple(r.lattice, r.status, LmStatsDict(s));
       }, py::arg("lm"), py::arg("scale") = 1.0f, py::arg("hist_factor") = 8)
+      // lattice-determinize-pruned on the host (what DeviceLattices.determinize gives for this lattice) ->
+      // (Lattice, status, stats)
+      .def("determinize", [](const Lattice& l, float gs, float as, float beam, float delta, int state_factor) {
+        const LatticeDeterminized r = l.Determinize(gs, as, beam, delta, state_factor);
+        return py::make_tuple(r.lattice, r.status, DetStatsDict(r.stats));
+      }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f, py::arg("beam") = 10.0f, py::arg("delta") = 1.0f / 1024.0f,
+         py::arg("state_factor") = 8)
       // lattice-add-penalty on the host (what DeviceLattices.add_penalty gives for this lattice)
       .def("add_penalty", [](const Lattice& l, float p) { return l.AddPenalty(p); }, py::arg("word_ins_penalty"))
       // lattice-oracle on the host (what DeviceLattices.oracle gives for this lattice): status (KHG_LAT_* bits), counts
@@ -741,6 +754,22 @@ void BindLattice(py::module_& m) {
         r->status.resize((size_t)U);
         return py::make_tuple(r, Vec1(r->status), LmStatsDict(st));
       }, py::arg("lm"), py::arg("scale") = 1.0f, py::arg("hist_factor") = 8)
+      // lattice-determinize-pruned -> (a new DeviceLattices carrying .status, status, stats)
+      .def("determinize", [](PyDeviceLattices& d, float gs, float as, float beam, float delta, int state_factor) {
+        if (!d.h) throw Error("DeviceLattices: closed");
+        const int U = (int)LatSizes(d).first.size() - 1;
+        auto r = std::make_shared<PyDeviceLattices>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj;
+        r->status.assign((size_t)std::max(U, 1), 0);
+        khg_det_stats st = {0, 0, 0, 0, 0, 0, 0, 0};
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_determinize(d.ctx, d.h, gs, as, beam, delta, state_factor, r->status.data(), &st, &r->h));
+        }
+        r->status.resize((size_t)U);
+        return py::make_tuple(r, Vec1(r->status), DetStatsDict(st));
+      }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f, py::arg("beam") = 10.0f, py::arg("delta") = 1.0f / 1024.0f,
+         py::arg("state_factor") = 8)
       // lattice-add-penalty -> a new DeviceLattices: graph_cost += word_ins_penalty on every arc with a word
       .def("add_penalty", [](PyDeviceLattices& d, float p) {
         if (!d.h) throw Error("DeviceLattices: closed");

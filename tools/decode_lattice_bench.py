@@ -632,6 +632,42 @@ def mbr_bench(ctx, dl, reps, gs=1.0, as_=0.1):
             "same_words_as_host_with_its_own_weights": same_words}
 
 
+def det_bench(ctx, dl, reps, beam, delta=1.0 / 1024, state_factor=8):
+    """--det on resident lattices, both sides in this process and alternated: DeviceLattices.determinize at (1, 1, beam)
+    beside the download of every lattice and a loop of the host form Lattice.determinize, which must give the device's lattices bit
+    for bit; states before and after."""
+    reps = max(reps, 3)
+    U = dl.num_utts
+    so, ao = np.asarray(dl.state_off), np.asarray(dl.arc_off)
+    res, st, stats = dl.determinize(1.0, 1.0, beam, delta, state_factor); ctx.sync()       # warm-up
+    res.close()
+    t_dev, t_dl, t_host, k_ms = [], [], [], []
+    for _ in range(reps):
+        def call():
+            dl.determinize(1.0, 1.0, beam, delta, state_factor)[0].close()
+        k_ms.append(kernel_ms(ctx, call))
+        ctx.sync(); t0 = time.time()
+        res, st, stats = dl.determinize(1.0, 1.0, beam, delta, state_factor)
+        t_dev.append(time.time() - t0)
+        t0 = time.time()
+        lats = dl.download()
+        t_dl.append(time.time() - t0)
+        t0 = time.time()
+        host = [L.determinize(1.0, 1.0, beam, delta, state_factor) for L in lats]
+        t_host.append(time.time() - t0)
+        got = res.download()
+        res.close()
+    fields = ("frame", "graph_state", "tot_cost", "extra_cost", "final_cost", "arc_begin", "ilabel", "olabel", "graph_cost", "acoustic_cost", "nextstate")
+    same = sum(1 for G, (H, hst, _), s in zip(got, host, st)
+               if hst == int(s) and G.start == H.start and all(np.asarray(getattr(G, f)).tobytes() == np.asarray(getattr(H, f)).tobytes() for f in fields))
+    ms = {k: float(np.median([x.get(k, 0.0) for x in k_ms])) for k in sorted({k for x in k_ms for k in x})}
+    return {"utterances": U, "beam": beam, "delta": delta, "state_factor": state_factor, "repetitions": reps, "succeeded": int((np.asarray(st) == 1).sum()),
+            "scratch": int((np.asarray(st) == 4).sum()), "states_before_mean": float(np.diff(so).mean()), "arcs_before_mean": float(np.diff(ao).mean()),
+            "states_after_mean": stats["out_states"] / max(U, 1), "arcs_after_mean": stats["out_arcs"] / max(U, 1), "stats": {k: int(v) for k, v in stats.items()},
+            "kernels_ms": ms, "call": med(t_dev), "download": med(t_dl), "host_loop": med(t_host),
+            "host_over_device": float(np.median(t_host)) / float(np.median(t_dev)), "same_as_host": same}
+
+
 def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
     """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
     after one warm-up round; and the last results."""
@@ -820,6 +856,13 @@ def shared_graph_main(args):
                 L = sh.raw_lattices_faster_device(dtm, beam=13.0, max_active=7000, lattice_beam=lb, acoustic_scale=0.1)["lattices"]
                 entry["mbr"]["lattice_beam_%g" % lb] = mbr_bench(ctx, L, args.reps)
                 L.close()
+        if args.det and name == "faster":
+            # determinizing the lattices the shared set leaves on the device, each set at its own lattice beam (what GetLattice does)
+            entry["det"] = {}
+            for lb in (6.0, args.dense_lattice_beam):
+                L = sh.raw_lattices_faster_device(dtm, beam=13.0, max_active=7000, lattice_beam=lb, acoustic_scale=0.1)["lattices"]
+                entry["det"]["lattice_beam_%g" % lb] = det_bench(ctx, L, args.reps, lb if args.det_beam is None else args.det_beam)
+                L.close()
         for us in sets.values():
             us.close()
         dg.close()
@@ -860,8 +903,13 @@ def main():
                     "penalties {0, 0.5, 1} beside add_penalty + best_path + the host's khg_edit_distance; add_penalty beside a device copy")
     ap.add_argument("--mbr", action="store_true", help="with --lattices (--decoder faster): DeviceLattices.mbr on the resident lattices beside the "
                     "download and a loop of the host form Lattice.mbr (DESIGN.md 7t)")
-    ap.add_argument("--dense-lattice-beam", type=float, default=12.0, help="with --shared-graph --oracle / --score / --mbr: the second, denser set's lattice beam")
+    ap.add_argument("--det", action="store_true", help="with --shared-graph --lattices (--decoder faster): DeviceLattices.determinize on the resident "
+                    "lattices beside the download and a loop of the host form Lattice.determinize (DESIGN.md 7u)")
+    ap.add_argument("--det-beam", type=float, default=None, metavar="B", help="with --det: the determinization beam (default: each set's lattice beam)")
+    ap.add_argument("--dense-lattice-beam", type=float, default=12.0, help="with --shared-graph --oracle / --score / --mbr / --det: the second, denser set's lattice beam")
     args = ap.parse_args()
+    if args.det and (not args.lattices or args.decoder != "faster" or not args.shared_graph or args.yesno):
+        ap.error("--det needs --shared-graph --lattices with --decoder faster (and is not timed with --yesno)")
     if args.mbr and (not args.lattices or args.decoder != "faster" or args.yesno):
         ap.error("--mbr needs --lattices with --decoder faster (and is not timed with --yesno)")
     if (args.oracle or args.score) and (not args.lattices or args.decoder != "faster" or args.yesno):
