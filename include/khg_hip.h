@@ -259,8 +259,8 @@ int khg_k3_forms(int32_t *rows, int32_t cap, int32_t *n);
  * POST, fp16 phase A, fp16 phase B, 1 when the split feature records were read, slices per pdf, cls_lo, cls_hi (the run takes the
  * pdfs of cls_lo < Gaussians <= cls_hi), dynamic LDS bytes }.  Launches nothing. */
 int khg_utts_k3_last(const khg_utts *u, int32_t out[2][12], int32_t *nruns);
-/* What the LAST khg_loglikes / _reachable / _band call on this set chose and launched (K1), written on the host where each decision
- * is settled and cleared at the start of every such call (a call that fails leaves the form at NONE):
+/* What the LAST khg_loglikes / _reachable / _band call on this set chose and launched (K1), written on the host from the call's plan
+ * before anything is launched and cleared at the start of every such call (a call that fails leaves the form at NONE):
  *   out[0]  1 once a call was made (0: none yet, the rest is zero)
  *   out[1]  the form that ran: KHG_K1L_NONE (no frames or no pdfs: nothing launched), _F16X2S, _F16X2, _PDF, _UTT, _WIDE (D > 80)
  *   out[2]  the form the option asked for, same codes (KHG_K1_AUTO asks for f16x2s)

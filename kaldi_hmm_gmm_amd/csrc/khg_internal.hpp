@@ -124,7 +124,7 @@ inline int sync_pageable(khg_ctx* ctx) {
 #define DEVFREE(p) do { if (p) { khg_dev_free((void*)(p)); (p) = nullptr; } } while (0)
 
 // kernel-side plan / result records the handles only hold pointers to (defined beside their kernels, khg_k*.hip.inc)
-struct KwChunk; struct K1Chunk; struct K1pEntry; struct K1pSlice; struct K1bChunk; struct K1sChunk; struct K1sUnit; struct K4Res;
+struct KwChunk; struct K1Chunk; struct K1pEntry; struct K1pSlice; struct K1bChunk; struct K1sChunk; struct K1sUnit; struct K1sArgs; struct K4Res;
 
 // A model image that K1 launches on several contexts' streams read and that is re-packed in place when the parameters or the
 // scale exponents change: the pack waits for every recorded reader, a reader on another stream waits for the pack.
@@ -230,6 +230,34 @@ struct khg_graph {
 };
 void khg_graph_release(khg_graph* g);                      // khg_utts.hip: drops one reference
 
+// K1's per-set state (khg_k1.hip plans, packs and drops it: k1_lists_changed, k1_features_changed, k1_free).  K1Planes: the B fragments of a split form, packed for KS
+// with the scale exponents ex (per k = 2 d + kind).  K1Band: what khg_align needs of khg_loglikes_band's launch to recompute the utterances whose beam certificate fails.
+struct K1Planes { k1b_u32x4* d = nullptr; int32_t ks = 0; std::vector<int32_t> ex; int32_t* ex_d = nullptr; };
+struct K1Band {
+  K1sArgs* args = nullptr; khg_model* model = nullptr; int ks = 0;   // the band launch's arguments (owned; k1_free), the model they point into, its KS
+  uint64_t serial = 0, version = 0; std::vector<int32_t> key;        // ... and which handle / parameter version / fp16 image that was
+};
+struct __attribute__((visibility("hidden"))) K1Set {
+  KwChunk* wchunks_d = nullptr; int32_t n_wchunks = 0;   // 64-frame chunks of the any-dimension K1 (khg_k1_wide.hip.inc)
+  // utterance-major form: workgroup chunks; with the f16x2 form: the W-tile walk per utterance
+  K1Chunk* chunks_d = nullptr; int32_t n_chunks = 0; int32_t chunk_kq = 0;
+  int64_t* tile_off_d = nullptr; int32_t* tiles_d = nullptr; int tiles_reach = -1;   // ... with each pdf's first needed frame (reachable-only K1) or zeros
+  std::vector<int32_t> tiles_pto;  // the model tile layout (pdf_tile_off) the walk lists were built for
+  // pdf-major form: repacked features (once), work plan (per reachable flag)
+  float* xpl_d = nullptr; int64_t* utt_xtile_off_d = nullptr; int32_t xpl_kq = 0;
+  K1pEntry* p_ents_d = nullptr; K1pSlice* p_slices_d = nullptr; int32_t p_nslices = 0; int p_reach = -1; int32_t p_P = -1;
+  int32_t p_grp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; std::vector<int32_t> p_goff;   // slices per block count (index 1..8); the model's gauss_off the plan was made for
+  // split forms: the set's 32-frame tile layout, workgroup chunks
+  int64_t* utt_x32_off_d = nullptr; int32_t* x32_utt_d = nullptr; int64_t n_x32 = 0;        // tile offsets per utterance, tile -> utterance
+  K1bChunk* bchunks_d = nullptr; int32_t n_bchunks = 0, bchunk_nt = 0;
+  std::vector<float> xmax;         // per feature dimension: max |x| over the set (empty: not computed)
+  K1Planes xh;                     // f16x2 form: exponents balanced between the set and the model
+  K1Planes xs;                     // f16x2s form: packed once with the set's own exponents (feature columns peak in [2^14, 2^15)) or the model's shared ones
+  K1sChunk* schunks_d = nullptr; int32_t n_schunks = 0, schunk_nmax = 0;                   // ... workgroup chunks of <= k1s_nmax tiles
+  K1sUnit* sunits_d = nullptr; std::vector<int32_t> sunits_pto; int sunits_reach = -1;     // ... one unit per (utterance, listed pdf)
+  K1Band band;
+};
+
 struct khg_utts {
   khg_ctx* ctx = nullptr;
   khg_graph* graph = nullptr;    // set created by khg_utts_create_on_graph: the graph tables below are the graph's (borrowed), state_off = {0, S}
@@ -250,40 +278,15 @@ struct khg_utts {
   const float* feats_d = nullptr; bool own_feats = false;
   int64_t *frame_off_d = nullptr, *state_off_d = nullptr, *pdf_off_d = nullptr, *ll_off_d = nullptr;
   int32_t *pdfs_d = nullptr, *start_d = nullptr;
-  KwChunk* wchunks_d = nullptr;   // 64-frame chunks of the any-dimension K1 (khg_k1_wide.hip.inc)
-  int32_t n_wchunks = 0;
   int64_t *in_off_d = nullptr, *out_off_d = nullptr;
   int32_t *in_src_d = nullptr, *in_col_d = nullptr, *in_tid_d = nullptr, *in_olabel_d = nullptr, *out_inidx_d = nullptr;
   float *in_w_d = nullptr, *final_d = nullptr;
-  // K1
-  K1Chunk* chunks_d = nullptr; int32_t n_chunks = 0; int32_t chunk_kq = 0;
-  int64_t* tile_off_d = nullptr; int32_t* tiles_d = nullptr;
+  // K1: the score block and the per-(utterance, pdf) frame bounds K2 / K3 read as well; K1's own per-set plans and planes are `k1`
   std::vector<int32_t> pdf_first;  // per (utterance, listed pdf): first frame at which any state emitting it can hold a token
   std::vector<int32_t> pdf_last;   // ... last frame at which an arc carrying it can still lead to a final state by the utterance's end (-1: never)
-  // BAND form of the default K1 (khg_loglikes_band): what khg_align needs to recompute the utterances whose beam certificate fails
   int ll_mode = 0;                 // how the resident scores were computed: 0 every cell, 1 from the first needed tile, 2 band
-  void* band_args = nullptr;       // K1sArgs of the band launch (khg_k1.hip owns it)
-  khg_model* band_model = nullptr; int band_ks = 0; size_t band_lds = 0; uint64_t band_serial = 0, band_version = 0; std::vector<int32_t> band_key;   // ... and which model / parameter version / fp16 image they belong to int band_ks = 0; size_t band_lds = 0;
-  int tiles_reach = -1;            // whether the walk lists carry those first frames (reachable-only K1) or zeros
-  std::vector<int32_t> tiles_pto;  // the model tile layout (pdf_tile_off) the walk lists were built for
   float* ll_d = nullptr; int64_t ll_total = 0; bool ll_valid = false;
-  // K1, pdf-major form: repacked features (once), work plan (per reachable flag)
-  float* xpl_d = nullptr; int64_t* utt_xtile_off_d = nullptr; int32_t xpl_kq = 0;
-  K1pEntry* p_ents_d = nullptr; K1pSlice* p_slices_d = nullptr; int32_t p_nslices = 0; int p_reach = -1; int32_t p_P = -1;
-  int32_t p_grp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // slices per block count (index 1..8); the plan also depends on the model's gauss_off
-  std::vector<int32_t> p_goff;
-  // K1, split forms: the set's 32-frame tile layout, workgroup chunks
-  int64_t* utt_x32_off_d = nullptr;
-  K1bChunk* bchunks_d = nullptr; int32_t n_bchunks = 0, bchunk_nt = 0;
-  int32_t* x32_utt_d = nullptr; int64_t n_x32 = 0;        // 32-frame tile -> utterance
-  // K1, f16x2 form: B fragments packed with the scale exponents xh_ex (per k = 2 d + kind)
-  k1b_u32x4* xh_d = nullptr; int32_t xh_ks = 0; std::vector<int32_t> xh_ex; int32_t* xh_ex_d = nullptr;
-  std::vector<float> xmax;         // per feature dimension: max |x| over the set (empty: not computed)
-  // K1, f16x2s form: B fragments packed once with the set's own exponents xs_ex (feature columns peak in [2^14, 2^15)),
-  // workgroup chunks of <= k1s_nmax tiles, one unit per (utterance, listed pdf)
-  k1b_u32x4* xs_d = nullptr; int32_t xs_ks = 0; std::vector<int32_t> xs_ex; int32_t* xs_ex_d = nullptr;
-  K1sChunk* schunks_d = nullptr; int32_t n_schunks = 0, schunk_nmax = 0;
-  K1sUnit* sunits_d = nullptr; std::vector<int32_t> sunits_pto; int sunits_reach = -1;
+  K1Set k1;
   // K2 scratch / outputs
   uint8_t* bp_d = nullptr; int64_t *bp_off_d = nullptr, *path_off_d = nullptr, *words_off_d = nullptr;
   double* layer_best_d = nullptr; int32_t* layer_cnt_d = nullptr; int32_t* path_d = nullptr;
@@ -312,8 +315,8 @@ struct khg_utts {
   int32_t k3_P = 0, k3_tids = 0;
   // khg_utts_k3_last: what the last statistics pass over this set launched, per run of its plan (k3_run writes a row where it has settled it)
   int32_t k3_last[2][12] = {}; int32_t k3_last_n = 0;
-  // khg_utts_k1_last: what the last khg_loglikes* call on this set chose and launched (khg_k1.hip writes each word where the decision is
-  // settled; the K1L_* indices there); k1_last[0] = 0 until the first call
+  // khg_utts_k1_last: what the last khg_loglikes* call on this set chose and launched (khg_k1.hip: k1_record writes it from the call's
+  // K1Plan, the run functions add what device-side planning settles; the K1L_* indices there); k1_last[0] = 0 until the first call
   int32_t k1_last[KHG_K1_LAST_WORDS] = {};
   // k3_accumulate_wave16's split feature records (khg_k3.hip: k3_planes), keyed by the model-derived exponents they were made with
   void* k3x_d = nullptr; int64_t k3x_bytes = 0, k3x_packs = 0; std::vector<int32_t> k3x_key; bool k3x_used = false;
@@ -374,7 +377,11 @@ int check_err_flag(khg_ctx* c, const char* where);        // khg_ctx_model.hip: 
 int model_pack(khg_ctx* ctx, khg_model* m);               // khg_ctx_model.hip: everything derived from gauss_off + the row-major parameters
 int model_stats(khg_ctx* ctx, khg_model* m);              // khg_ctx_model.hip: per parameter version, one pass: column maxima, feature envelope, band upper bounds
 int wait_ali(khg_ctx* ctx, khg_utts* u);                  // khg_utts.hip: the main stream waits for the side-stream decoder
-void k1_free_band(khg_utts* u);                           // khg_k1.hip: the BAND form's saved launch arguments
+// khg_k1.hip: what of khg_utts::k1 goes stale when the pdf lists are replaced / the borrowed features were rewritten, and its release (hidden,
+// as K1Set is: the library's dynamic symbols stay what they were)
+__attribute__((visibility("hidden"))) void k1_lists_changed(khg_utts* u);
+__attribute__((visibility("hidden"))) void k1_features_changed(khg_utts* u);
+__attribute__((visibility("hidden"))) void k1_free(khg_utts* u);
 int k1_maxima(khg_ctx* ctx, khg_model* m, khg_utts* u, std::vector<float>* xk);   // khg_k1.hip: column maxima of features / parameters
 khg_model* khg_model_lookup(uint64_t serial);             // khg_ctx_model.hip: the live handle with this serial, or NULL
 int k1_band_check(khg_ctx* ctx, khg_utts* u);             // khg_k1.hip: the band's model is alive and unchanged (re-scores when only its image was re-packed)

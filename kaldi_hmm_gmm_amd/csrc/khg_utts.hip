@@ -205,13 +205,13 @@ static int utts_begin(const char* where, khg_ctx* ctx, int32_t n_utt, int32_t D,
       }
     }
     if (u->small && u->N > 0) {      // the column maxima the split K1 forms scale by: a pass over 48 kB here instead of a kernel + a download
-      u->xmax.assign((size_t)D, 0.0f);
+      u->k1.xmax.assign((size_t)D, 0.0f);
       for (int64_t t = 0; t < u->N; ++t) {
         const float* x = feats_h + (size_t)t * D;
         for (int d = 0; d < D; ++d) {        // k1h_absmax's rule: -inf skipped, NaN / +inf come out as +inf
-          const float v = x[d], m = u->xmax[(size_t)d];
+          const float v = x[d], m = u->k1.xmax[(size_t)d];
           if (v == -std::numeric_limits<float>::infinity()) continue;
-          u->xmax[(size_t)d] = (std::fabs(v) <= 3.0e38f) ? std::fmax(m, std::fabs(v)) : std::numeric_limits<float>::infinity();
+          u->k1.xmax[(size_t)d] = (std::fabs(v) <= 3.0e38f) ? std::fmax(m, std::fabs(v)) : std::numeric_limits<float>::infinity();
         }
       }
     }
@@ -405,12 +405,9 @@ extern "C" int khg_utts_set_pdf_list(khg_utts* u, int32_t n, const int32_t* pdfs
   u->pdf_first.clear(); u->pdf_last.clear();     // no graphs behind an explicit list: every frame is needed
   for (int i = 0; i < u->n_utt; ++i) { u->pdf_off[i + 1] = u->pdf_off[i] + n; u->pdfs.insert(u->pdfs.end(), pdfs, pdfs + n); }
   plan_ll(u);
-  DEVFREE(u->pdf_off_d); DEVFREE(u->pdfs_d); DEVFREE(u->ll_off_d); DEVFREE(u->ll_d); DEVFREE(u->chunks_d); DEVFREE(u->wchunks_d);
-  DEVFREE(u->tile_off_d); DEVFREE(u->tiles_d); u->tiles_pto.clear(); u->tiles_reach = -1;
-  DEVFREE(u->p_ents_d); DEVFREE(u->p_slices_d); u->p_reach = -1;
-  // the default K1's per-set unit table is indexed through pdf_off, and the id range check is cached per model size: both are stale now
-  DEVFREE(u->sunits_d); u->sunits_pto.clear(); u->sunits_reach = -1;
-  u->pdfs_checked_P = -1;
+  DEVFREE(u->pdf_off_d); DEVFREE(u->pdfs_d); DEVFREE(u->ll_off_d); DEVFREE(u->ll_d);
+  k1_lists_changed(u);
+  u->pdfs_checked_P = -1;      // (the id range check is cached per model size)
   u->ll_valid = false;
   return KHG_OK;
 }
@@ -420,9 +417,7 @@ extern "C" int khg_utts_set_pdf_list(khg_utts* u, int32_t n, const int32_t* pdfs
 // but k3_accumulate_wave16 on its records read feats_d live.
 extern "C" int khg_utts_features_changed(khg_utts* u) {
   if (!u) return khg_set_error(KHG_E_ARG, "khg_utts_features_changed: bad arguments");
-  u->xmax.clear();
-  u->xs_ks = 0; u->xs_ex.clear();
-  u->xh_ks = 0; u->xh_ex.clear();
+  k1_features_changed(u);
   u->k3x_key.clear();                 // (the buffer stays: same N, the next pass fills it again)
   u->ll_valid = false;
   return KHG_OK;
@@ -456,12 +451,9 @@ extern "C" int khg_utts_destroy(khg_utts* u) {
   }
   DEVFREE(u->gidx_d);
   DEVFREE(u->frame_off_d); DEVFREE(u->state_off_d); DEVFREE(u->pdf_off_d); DEVFREE(u->ll_off_d);
-  DEVFREE(u->pdfs_d); DEVFREE(u->wchunks_d); DEVFREE(u->start_d); DEVFREE(u->in_off_d); DEVFREE(u->out_off_d);
+  DEVFREE(u->pdfs_d); DEVFREE(u->start_d); DEVFREE(u->in_off_d); DEVFREE(u->out_off_d);
   DEVFREE(u->in_src_d); DEVFREE(u->in_col_d); DEVFREE(u->in_tid_d); DEVFREE(u->in_olabel_d); DEVFREE(u->out_inidx_d);
-  DEVFREE(u->in_w_d); DEVFREE(u->final_d); DEVFREE(u->chunks_d); DEVFREE(u->ll_d); DEVFREE(u->tile_off_d); DEVFREE(u->tiles_d);
-  DEVFREE(u->xpl_d); DEVFREE(u->utt_xtile_off_d); DEVFREE(u->p_ents_d); DEVFREE(u->p_slices_d);
-  DEVFREE(u->utt_x32_off_d); DEVFREE(u->bchunks_d); DEVFREE(u->x32_utt_d); DEVFREE(u->xh_d); DEVFREE(u->xh_ex_d);
-  DEVFREE(u->xs_d); DEVFREE(u->xs_ex_d); DEVFREE(u->schunks_d); DEVFREE(u->sunits_d);
+  DEVFREE(u->in_w_d); DEVFREE(u->final_d); DEVFREE(u->ll_d);
   DEVFREE(u->bp_d); DEVFREE(u->bp_off_d); DEVFREE(u->path_off_d); DEVFREE(u->words_off_d);
   DEVFREE(u->ali2_d); DEVFREE(u->unc_d); DEVFREE(u->sub_off_d);
   if (u->unc_cnt_h) { (void)hipHostFree(u->unc_cnt_h); u->unc_cnt_h = nullptr; }
@@ -474,7 +466,7 @@ extern "C" int khg_utts_destroy(khg_utts* u) {
   DEVFREE(u->pe_vals_d); DEVFREE(u->pe_tmp_d); DEVFREE(u->pe_start_d);
   DEVFREE(u->rc_keys_d); DEVFREE(u->rc_keys_out_d); DEVFREE(u->rc_vals_d); DEVFREE(u->rc_vals_out_d); DEVFREE(u->rc_flag_d); DEVFREE(u->rc_inc_d);
   DEVFREE(u->rc_row_d); DEVFREE(u->rc_cell_d); DEVFREE(u->rc_tmp_d); DEVFREE(u->rc_cell_start_d); DEVFREE(u->rc_item_off_d); DEVFREE(u->rc_stats_d);
-  k1_free_band(u);
+  k1_free(u);
   if (u->ev_dp) (void)hipEventDestroy(u->ev_dp);
   if (u->ev_ali) (void)hipEventDestroy(u->ev_ali);
   delete u;

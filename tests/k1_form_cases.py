@@ -442,7 +442,7 @@ def split_domain(xk, wk, gcmax):
 
 
 def f16x2s_scales(xk, wk):
-    """the scales() lambda of loglikes_f16x2s for a model that has scored no other set"""
+    """the scales() lambda of k1_plan_f16x2s for a model that has scored no other set"""
     ex = [14 - _ilogb(v) if v > 0 else 0 for v in xk]
     cand = [14 - _ilogb(w) + e for w, e in zip(wk, ex) if w > 0]
     Sc = min(cand) if cand else 0
@@ -519,7 +519,7 @@ def utt_chunks(lens, nlist, maxtiles):
 
 
 def pdf_slices(b, reach, TS):
-    """the slice planner of loglikes_pdf_major: [(pdf, first entry, entries, first tile offset, tiles)] in pdf order"""
+    """the slice planner of run_pdf_major: [(pdf, first entry, entries, first tile offset, tiles)] in pdf order"""
     P = len(b.case.gauss)
     ents = [[] for _ in range(P)]
     lens = np.diff(b.frame_off)
