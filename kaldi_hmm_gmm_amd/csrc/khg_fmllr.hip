@@ -123,14 +123,16 @@ static int fm_grow(T** p, size_t* cap, size_t need) {
 
 template <int NDT>
 static int mt_launch_gram(khg_ctx* ctx, const FmArgs& a, const FmItem* items, int nitems, int ngroups, size_t lds, const float* shift) {
-  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_mllt_gram<NDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc = khg_lds_attribute((const void*)k_mllt_gram<NDT>, lds);
+  if (rc) return rc;
   KHG_LAUNCH(ctx, k_mllt_gram<NDT>, dim3((unsigned)nitems, (unsigned)ngroups), dim3(256), lds, ctx->stream, a, items, shift);
   HIPCHK(hipGetLastError());
   return KHG_OK;
 }
 template <int NDT>
 static int fm_launch_gram(khg_ctx* ctx, const FmArgs& a, const FmItem* items, int nitems, int ngroups, size_t lds) {
-  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_fmllr_gram<NDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc = khg_lds_attribute((const void*)k_fmllr_gram<NDT>, lds);
+  if (rc) return rc;
   KHG_LAUNCH(ctx, k_fmllr_gram<NDT>, dim3((unsigned)nitems, (unsigned)ngroups), dim3(256), lds, ctx->stream, a, items);
   HIPCHK(hipGetLastError());
   return KHG_OK;
@@ -633,7 +635,8 @@ extern "C" int khg_mllt_stats_add(khg_ctx* ctx, khg_mllt_stats* dst, float scale
 
 template <int NDT>
 static int mt_launch_gauss(khg_ctx* ctx, const MtGaussArgs& a, int nslice, int ngroups, size_t lds) {
-  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_mllt_gauss<NDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc = khg_lds_attribute((const void*)k_mllt_gauss<NDT>, lds);
+  if (rc) return rc;
   KHG_LAUNCH(ctx, k_mllt_gauss<NDT>, dim3((unsigned)nslice, (unsigned)ngroups), dim3(256), lds, ctx->stream, a);
   HIPCHK(hipGetLastError());
   return KHG_OK;

@@ -86,6 +86,12 @@ static inline bool ctx_dead(const khg_ctx* ctx) { return !ctx || !khg_ctx_alive(
 int utts_foreign_ctx(const khg_ctx* ctx, const struct khg_utts* u, const char* where);     // khg_utts.hip
 // Every kernel launch of the library goes through this: uploads staged in the arena since the last launch reach the device first.
 #define KHG_LAUNCH(ctx_, ...) do { (void)arena_flush(ctx_); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+// ... and a launch with more than 48 KB of dynamic LDS calls this first: the one place that knows the threshold.  Set on every such
+// launch, not once: the attribute is per function and sticky, and another handle may have set it lower.
+static inline int khg_lds_attribute(const void* fn, size_t lds) {
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return KHG_OK;
+}
 // scoped HIP-event pair around a kernel launch, on the launching stream (only when enabled); staged uploads go out first
 struct KernelTimer {
   khg_ctx* c; size_t idx = 0; bool on; hipStream_t s;

@@ -72,14 +72,10 @@ static K1Kernel<F> k1_kernel(int K, int p1 = 0, int p2 = 0) {
   return {nullptr, 0, 0};
 }
 // ... and the one launch of them (a missing kernel is an error)
-static int k1_lds_attribute(const void* fn, size_t lds) {
-  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return KHG_OK;
-}
 template <class... Params, class... Args>
 static int k1_launch(khg_ctx* ctx, void (*fn)(Params...), unsigned grid, int nthr, size_t lds, hipStream_t s, const Args&... args) {
   if (!fn) return khg_set_error(KHG_E_UNSUPPORTED, "khg_loglikes: no kernel of this form was built");
-  int rc = k1_lds_attribute((const void*)fn, lds);
+  int rc = khg_lds_attribute((const void*)fn, lds);
   if (rc) return rc;
   KHG_LAUNCH(ctx, fn, dim3(grid), dim3(nthr), lds, s, args...);
   return KHG_OK;
@@ -763,7 +759,7 @@ static int k1_persistent_grid(khg_ctx* ctx, const K1Kernel<K1_S_PERSISTENT>& k, 
   int& cached = ctx->k1_pgrid[KS == 5 ? 0 : 1];
   if (cached <= 0) {
     int per_cu = 0, ncu = 0;
-    int rc = k1_lds_attribute((const void*)k.fn, k.lds);
+    int rc = khg_lds_attribute((const void*)k.fn, k.lds);
     if (rc) return rc;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k.fn, k.nthr, k.lds));
     HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));

@@ -257,7 +257,7 @@ int k1_cells_run(khg_ctx* ctx, const khg_model* m, khg_utts* u, int64_t NA, floa
     for (int p = 0; p < P; ++p) maxgd = std::max<int64_t>(maxgd, (int64_t)(m->gauss_off[(size_t)p + 1] - m->gauss_off[(size_t)p]) * m->D);
     const size_t lds = (size_t)std::min<int64_t>(K1C_LDS_MAX, 8 * maxgd);
     a.lds_floats = (int32_t)(lds / 4);
-    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k1c_score, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    { int rc = khg_lds_attribute((const void*)k1c_score, lds); if (rc) return rc; }
     // every pdf may leave one short slice: an upper bound from the arc count and P alone (the cell counts stay on the device); a
     // workgroup past the last item returns at once
     const int64_t max_items = (int64_t)P + NA / K1C_CS + 1;

@@ -319,6 +319,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(KS == 1 ? K2_WAVES_PER_EU : 4))) v
   const int LB = Sp;                                  // generic path: bytes per layer of the global back-pointer image
 
   // LDS carve-up (sized by the host for the batch maximum; FAST needs no score block)
+  // (its byte count: k2_lds_dp / k2_lds_dp_fast / k2_lds_dp_generic, khg_k2.hip)
   double* cur = reinterpret_cast<double*>(smem);                          // [max_states]
   double* nxt = cur + a.max_states;
   double* s_red = nxt + a.max_states;                 // [K2_MAXW] best-final reduction
@@ -1240,6 +1241,7 @@ __global__ void k2_viterbi_faithful(K2Args a) {
   uint8_t* bp = a.bp + a.bp_off[u];
 
   // LDS: two elem pools (current / previous layer), bucket table, work queue, graph tables
+  // (its byte count: k2_lds_lane, khg_k2.hip)
   const int HB = a.max_states * 2 > 1000 ? a.max_states * 2 : 1000;   // upper bound of hash_size
   K2Elem* pool0 = reinterpret_cast<K2Elem*>(smem);
   K2Elem* pool1 = pool0 + a.max_states;
@@ -1514,6 +1516,7 @@ __global__ __launch_bounds__(64) void k2_viterbi_faithful_wave(K2Args a, int eps
   const bool use_pos = eps || MS > 1000;      // state -> list position table: epsilon worklist, shared hash buckets
 
   // ---- per-frame tables (LDS) ----
+  // (their byte count: k2_lds_wave_mut, the graph tables' below: k2_lds_wave_graph, khg_k2.hip)
   double* tkc0 = reinterpret_cast<double*>(smem);                       // token costs, list order (two layers)
   double* tkc1 = tkc0 + MS;
   unsigned long long* st_key = reinterpret_cast<unsigned long long*>(tkc1 + MS);   // per state: min token cost (ordered key)
@@ -2173,6 +2176,7 @@ __global__ __launch_bounds__(64) void k2_viterbi_faithful_chain(K2Args a, int ma
   // ---- LDS (sized by the host for the batch maxima).  The frame loop's tables: 8-byte arrays first, then 4-byte, 2-byte, bytes.  What only
   // the set-up and the tail need (in-arc offsets and sources, the trace-back's rows) lies OVER them, from the start of the block: the
   // decoder is bound by how many utterances a CU keeps in flight, i.e. by LDS per utterance (10 KB at 121 states: 15 per CU) ----
+  // (its byte count: k2_lds_chain, khg_k2.hip)
   double* tkc0 = reinterpret_cast<double*>(smem);                       // token costs, list order (two layers)
   double* tkc1 = tkc0 + MS;
   unsigned long long* st_key = reinterpret_cast<unsigned long long*>(tkc1 + MS);   // per state: min token cost (ordered key)

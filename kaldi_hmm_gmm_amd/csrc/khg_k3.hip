@@ -333,7 +333,8 @@ extern "C" int khg_utts_k3_last(const khg_utts* u, int32_t out[2][12], int32_t* 
 }
 // ... and the one launch of them
 static int k3_launch(khg_ctx* ctx, K3Kernel fn, unsigned grid, int nthr, size_t lds, const K3Args& a) {
-  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc = khg_lds_attribute((const void*)fn, lds);
+  if (rc) return rc;
   KHG_LAUNCH(ctx, fn, dim3(grid), dim3(nthr), lds, ctx->stream, a);
   return KHG_OK;
 }
@@ -447,11 +448,8 @@ static int k3_bucket(khg_ctx* ctx, const khg_model* m, const khg_tm* tm, khg_utt
       const bool ldst = tm->num_tids <= K3_LDS_TIDS;
       const size_t lds_h = sizeof(unsigned int) * ((size_t)m->P + 1 + (ldst ? (size_t)tm->num_tids + 1 : 0));
       const size_t lds_p = sizeof(unsigned int) * (size_t)nw * ((size_t)m->P + 1 + 1024);     // per-wave counters + the run-head hash tags
-      if (lds_h > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute((const void*)k3_cs_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
-        HIPCHK(hipFuncSetAttribute((const void*)k3_cs_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
-      }
-      if (lds_p > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k3_cs_place, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
+      if ((rc = khg_lds_attribute((const void*)k3_cs_hist<true>, lds_h)) || (rc = khg_lds_attribute((const void*)k3_cs_hist<false>, lds_h)) ||
+          (rc = khg_lds_attribute((const void*)k3_cs_place, lds_p))) return rc;
       if (ldst) KHG_LAUNCH(ctx, k3_cs_hist<true>, dim3(nblk), dim3(256), lds_h, ctx->stream, a, c);
       else KHG_LAUNCH(ctx, k3_cs_hist<false>, dim3(nblk), dim3(256), lds_h, ctx->stream, a, c);
       KHG_LAUNCH(ctx, k3_cs_scan, dim3((m->P + 256) / 256), dim3(256), 0, ctx->stream, a, c);

@@ -2171,7 +2171,7 @@ extern "C" int khg_lattices_oracle(khg_ctx* ctx, const khg_lattices* lc, int32_t
     p.in_begin = ix.in_begin; p.in_arc = ix.in_arc; p.arc_src = ix.arc_src;
     p.list = list_d + L.first; p.tab_off = tab_off_d + L.first; p.tab = tab_d; p.width = l->width_d;
     p.ref = ref_d; p.ref_off = ref_off_d; p.counts = counts_d; p.nwords = nw_d;
-    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k2_lattice_score_oracle, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if ((rc = khg_lds_attribute((const void*)k2_lattice_score_oracle, (size_t)lds))) return rc;
     if ((rc = launch(ctx, "k2_lattice_score_oracle", k2_lattice_score_oracle, dim3((unsigned)L.n), dim3(SC_NT), (size_t)lds, p))) return rc;
   }
   std::vector<int32_t> counts, nw, st, words;

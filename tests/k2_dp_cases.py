@@ -178,6 +178,36 @@ def generic_eps_case():
     return c
 
 
+def walk_graph(rng, S, back=None):
+    """Out-degree 1: state s goes to s + 1, the last state -- the final one -- back to state `back` (None: nowhere, a plain chain).
+    One path per length, so T frames end in the final state for T = S - 1 and every S - back frames after.  Word labels on a fifth of
+    the arcs before the cycle: the aligner sizes an utterance's word buffer by the graph's labelled arcs, each taken once."""
+    n = S - 1 + (back is not None)
+    dst = np.concatenate([np.arange(1, S), [] if back is None else [back]]).astype(np.int32)
+    final = np.full(S, np.inf, np.float32)
+    final[S - 1] = float(rng.random())
+    olabel = np.where(rng.random(n) < 0.2, rng.integers(1, 50, size=n), 0).astype(np.int32)
+    if back is not None:
+        olabel[back:] = 0
+    return {"start": 0, "arc_off": np.minimum(np.arange(S + 1), n).astype(np.int64),
+            "ilabel": rng.integers(1, 2 * NP + 1, size=n).astype(np.int32), "olabel": olabel,
+            "weight": rng.random(n).astype(np.float32), "nextstate": dst, "final": final}
+
+
+@functools.lru_cache(maxsize=None)
+def chain_case(odeg):
+    """Three utterances for k2_viterbi_faithful_chain<odeg> at the out-degrees no batch above has (1 and 4; the batches of hop 1 and 2
+    run <2> and <3>): no epsilon arcs, at most 20 states, the largest out-degree exactly odeg, 8 to 30 frames."""
+    rng = np.random.default_rng(3100 + odeg)
+    c = Case()
+    c.name, c.k2_ks, c.hop = "chain_odeg%d" % odeg, 0, odeg - 1
+    if odeg == 1:
+        c.graphs, c.T = [walk_graph(rng, 9), walk_graph(rng, 12, back=5), walk_graph(rng, 20)], [8, 18, 19]
+    else:       # self-loop + hops of 1 .. odeg - 1
+        c.graphs, c.T = [ltr_graph(rng, 20, odeg - 1, False), permute_states(ltr_graph(rng, 13, odeg - 1, True), rng), ltr_graph(rng, 7, odeg - 1, False)], [30, 9, 8]
+    return _finish(c, rng, False)
+
+
 def case(name):
     return generic_eps_case() if name == "generic_eps" else natural_case(name) if name in NATURAL else form_case(name)
 

@@ -4,7 +4,8 @@ one the case names (UtteranceSet.k2_plan), its answers are the oracle's FasterDe
 batch and with min_active in play, and its certificate bit (KHG_ALIGN_EXACT_DP) is the restatement's certified(...) -- both are
 fixed arithmetic, so on every utterance: a certificate too lax would hand out a path the reference prunes, one too strict would
 send everything to the order-faithful decoders unnoticed.  The HBM-scratch form keeps its own test
-(tests/test_gpu_shared_graph.py)."""
+(tests/test_gpu_shared_graph.py).  These batches send what they do not certify to the chain decoder at out-degree 2 and 3;
+test_chain_decoder_at_out_degree runs it at 1 and 4."""
 import json
 import os
 import sys
@@ -120,4 +121,28 @@ def test_form(ctx, opt, name):
         for kw, forced in zip(c.cfgs, results):
             _same_bytes(us.align(tm, acoustic_scale=c.scale, **kw), forced, ("k2_ks", c.k2_ks, kw))
     print("k2_dp_form_record " + json.dumps(record))
+    us.close(); tm.close()
+
+
+@pytest.mark.parametrize("odeg", [1, 4])
+def test_chain_decoder_at_out_degree(ctx, opt, odeg):
+    """k2_viterbi_faithful_chain<1> and <4>, the two rows of the kernel table (k2_insts, csrc/khg_k2.hip) that no batch of test_form
+    reaches (theirs have out-degree 2, 3 or 6): with max_active set nothing is certified and the chain decoder decides every
+    utterance -- the oracle's FasterDecoder's answers, and byte for byte the one-lane emulation's (k2_serial = 1).  The plan says
+    "chain" and the batch has the out-degree; WHICH instantiation ran is not observable from here: that the table's row for ODEG
+    points at chain<ODEG> rests on the kernel trace of these two tests (profiles/k2_table_ab.txt, part 4)."""
+    c = kc.chain_case(odeg)
+    tm, us = _device(ctx, c)
+    f = kc.batch_facts(c)
+    assert len(c.T) == 3 and all(8 <= t <= 30 for t in c.T) and not f["eps"] and f["S"] <= 20 and f["outdeg"] == odeg
+    for kw in (dict(beam=200.0, max_active=1000), dict(beam=4.0, max_active=1000, min_active=0)):
+        opt("k2_serial", 0)
+        assert us.k2_plan(ctx)["faithful_form"] == 4
+        res = us.align(tm, acoustic_scale=c.scale, **kw)
+        assert not (res["status"] & EXACT_DP).any()
+        for u in range(3):
+            _against_oracle(c, res, u, kw)
+        opt("k2_serial", 1)
+        assert us.k2_plan(ctx)["faithful_form"] == 0
+        _same_bytes(us.align(tm, acoustic_scale=c.scale, **kw), res, ("one-lane emulation", odeg, kw))
     us.close(); tm.close()

@@ -139,3 +139,18 @@ def test_restatement_against_the_oracle(name):
                 checked[1] += 1
     print(name, "paths compared at beam 200: %d, certified answers compared at narrow beams: %d" % tuple(checked))
     assert checked[0] >= 3 and checked[1] >= 3
+
+
+@pytest.mark.parametrize("odeg", [1, 4])
+def test_chain_cases_have_the_out_degree_they_are_named_after(odeg):
+    """the batches of test_chain_decoder_at_out_degree (tests/test_gpu_k2_dp_forms.py): what selects k2_viterbi_faithful_chain<odeg>,
+    and every utterance reaches a final state -- the restatement's path is the oracle's with max_active set as that test sets it"""
+    c = kc.chain_case(odeg)
+    f = kc.batch_facts(c)
+    assert len(c.T) == 3 and all(8 <= t <= 30 for t in c.T) and not f["eps"] and f["S"] <= 20 and f["outdeg"] == odeg
+    assert len({int(np.diff(g["arc_off"]).max()) for g in c.graphs}) == 1        # every graph of the batch, not only the largest
+    for u, r in enumerate(c.ref):
+        want = kc.oracle_align(c, u, beam=200.0, max_active=1000)
+        assert r.ok and want["status"] & 3 == 0
+        if not (r.path_tie or r.final_tie):
+            _same(r, want, (odeg, u))
