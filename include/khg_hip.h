@@ -117,7 +117,9 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
                                     at most 48 KiB there, 1 never (every lattice is read from its HBM arrays); same results bit for
                                     bit.  khg_lattices_oracle: 0 the rows of two frames are kept in LDS when they fit, 1 never (read
                                     back from the HBM table); khg_lattices_wer: 0 a table of at most 48 KiB stays in LDS, 1 never;
-                                    same results bit for bit                                                         [KHG_LAT_OPS_LDS] */
+                                    same results bit for bit.  khg_lattices_nbest: 0 an utterance's running lists (52 n bytes) are
+                                    kept in LDS when the device gives that much, 1 never (HBM rows); same results bit for
+                                    bit                                                                              [KHG_LAT_OPS_LDS] */
 #define KHG_OPT_K1_LAUNCH 19     /* launch shape of the default (f16x2s) K1: 1 one workgroup per chunk of frame tiles; 2 persistent -- one workgroup per
                                     CU takes chunks from a counter, in the same order, and copies the next chunk's frame tiles into LDS under
                                     the tail of the current one; 0 (DEFAULT) automatic: persistent where it measured faster, never for a small
@@ -138,7 +140,10 @@ int khg_ctx_set_k1_form(khg_ctx *ctx, int form);     /* = khg_ctx_set_option(ctx
                                     decodes one packed source word per cell (in-degree <= 3, one state per thread, <= 256 states) and the
                                     replay's fp64 cost chain runs as a wave scan wherever that is exact, 1 the loops they replaced; same
                                     results bit for bit                                                                 [KHG_K2_TAIL=on|off] */
-#define KHG_OPT_COUNT 25
+#define KHG_OPT_NBEST_ARENA 25   /* khg_lattices_nbest: the lists of the utterances of ONE launch may take this many KiB together (an utterance above it is a
+                                    launch of its own); a chunk whose lists take more runs in several launches (tests: more than one launch on
+                                    small lattices).  0 (DEFAULT): 1 GiB; same results bit for bit                          [KHG_NBEST_ARENA] */
+#define KHG_OPT_COUNT 26
 /* Read-only figures (khg_ctx_get_option only): the per-call scratch block behind small utterance sets (DESIGN.md "per-utterance calls"). */
 #define KHG_INFO_SCRATCH_BYTES 100   /* bytes of the block in use (its top), 0 before the first small set */
 #define KHG_INFO_SCRATCH_BLOCKS 101  /* live allocations inside it */
@@ -879,6 +884,61 @@ int khg_mbr_download(khg_ctx *ctx, const khg_mbr *m, int32_t *status_h, int32_t 
                      double *conf_h, int32_t *vocab_h, double *gamma_h, double *arc_cond_h, double *final_cond_h);
 int khg_mbr_device_bytes(const khg_mbr *m, int64_t *bytes);
 int khg_mbr_destroy(khg_mbr *m);
+
+/* ---- K2N: the n best paths of resident lattices (lattice-to-nbest | nbest-to-linear) ---------------------------- */
+#define KHG_NBEST_MAX 1024
+/* The n cheapest paths of every utterance under the pair (graph_scale, acoustic_scale) = (gs, as), each with its alignment, its words,
+ * its weight pair and its total.  On a handle made by khg_lattices_determinize every word sequence has one path, so the entries are
+ * the n best DISTINCT word sequences (Kaldi's n-best on a CompactLattice); on a raw lattice they are the n best alignments.  The
+ * reference has no n-best code: this text is the specification.
+ * Everything is float, one rounding per operation, no contraction.  gs and as finite and >= 0, 1 <= n <= KHG_NBEST_MAX; otherwise
+ * KHG_E_ARG.  Per utterance, in this order:
+ *   empty lattice                               KHG_LAT_NO_PATH, 0 entries
+ *   an arc that does not go to a higher state   KHG_LAT_EPS_LOOP, 0 entries (the test of khg_lattices_lm_rescore and _determinize; it
+ *                                               refuses the lattices of the lattice-simple decoder)
+ *   An arc weighs wa = fl(gs * graph_cost) and wb = fl(as * acoustic_cost), wb = 0 on an arc with ilabel 0 (as in
+ *   khg_lattices_best_path); its scalar cost is c = fl(wa + wb).
+ *   A PREFIX at state s is (t, a, b, nw, e, j): t the ordering key, (a, b) the two sums khg_lattices_best_path reports, nw the words so
+ *   far, e the in-arc it came through (the utterance's arc number), j its rank in the list of e's source.  The list of the start
+ *   state is the one prefix (0, 0, 0, 0, none, 0); the in-arcs of the start are not looked at (their sources lie below it, and nothing
+ *   reaches them).  For every other state s, ascending: every in-arc e of s, from p, and every rank j of A[p] give the candidate
+ *   t' = fl(A[p][j].t + c), a' = fl(a + wa), b' = fl(b + wb), nw' = nw + (olabel != 0); a candidate whose t' is not < +inf is dropped
+ *   (NaN and +inf); A[s] is the n least candidates under the key (t', e, j), lexicographic, ascending (floats compare as floats:
+ *   -0 == +0), fewer when there are fewer.
+ *   T = the frame of the last state.  Every state s of frame T with a finite final_cost, and every rank j of A[s], give a complete
+ *   path: total = fl(t + fw), fw = fl(gs * final_cost), dropped unless < +inf; weight (fl(a + fw), b).  The ENTRIES are the n least
+ *   under (total, s, j), ascending.  None: KHG_LAT_NO_PATH; otherwise KHG_LAT_SUCCEEDED with 1 to n entries.
+ *   An utterance whose lists together hold more than 2^31 - 1 elements: KHG_LAT_SCRATCH, 0 entries.
+ * Two facts make this the right rule.
+ *   1. A scalar key survives rounding: x <= y implies fl(x + c) <= fl(y + c).  So a state's list extended along an arc is still sorted
+ *      under (t', j), cutting every list at n loses nothing, and the sorted totals of the result are EXACTLY the n least totals over all
+ *      paths, each total taken left to right (tested with ==).  The pair order of khg_lattices_best_path -- fl(a + b), then a -- does
+ *      not have this property after a component-wise add; that is why the key is the scalar t and the pair is only carried.
+ *   2. The result is a function of the lattice alone: the key (t', e, j) is total, so it does not matter in which order arcs are
+ *      merged; a serial loop that sorts (Lattice::Nbest) and the device's parallel merge by rank give the same lists, bit for bit.
+ * Entry 0 is the best path under t, NOT under khg_lattices_best_path's pair order.  The two can differ only when two paths lie within
+ * the accumulated rounding of each other; when entry 0 is best_path's path, its weight pair is best_path's bit for bit (the same sums
+ * in the same order).
+ * An entry's outputs, laid out as khg_lattices_best_path's: its non-zero ilabels by frame (T of them: the ilabel of the arc leaving
+ * a state of frame f at position f, 0 where the path has none), its non-zero olabels, its weight pair, its total.
+ * The result is a handle resident on the device (free it with khg_nbest_destroy); khg_lattices_op_status is not involved, the status
+ * comes back through status_h [n_utt] (may be NULL).  khg_nbest_sizes: entry_off_h [n_utt + 1] -- utterance u owns the entries
+ * entry_off[u] .. entry_off[u + 1] -- and words_off_h [entries + 1]; either may be NULL.  The alignments follow from
+ * khg_lattices_ali_layout (T_u = ali_off[u + 1] - ali_off[u]) and the entry counts: entry k of utterance u owns the T_u cells from
+ * sum over v < u of (entry_off[v + 1] - entry_off[v]) * T_v, plus k * T_u.  khg_nbest_download: ali_h, words_h, weight_h [entries][2],
+ * total_h [entries]; any may be NULL.
+ * The running lists of an utterance live in LDS (52 n bytes), or in HBM rows when the device gives less or KHG_OPT_LAT_OPS_LDS = 1:
+ * the same bits.  Nothing depends on the batch or on timing: no atomics.  The first call on a handle builds its in-arc index (as
+ * khg_lattices_posteriors does) and keeps it.  Synchronous: one synchronisation per chunk sizes the lists, one per launch sizes the
+ * entries, and one ends the launch before its lists are freed (a chunk is one launch unless its lists exceed 1 GiB, or
+ * KHG_OPT_NBEST_ARENA KiB when that is set). */
+typedef struct khg_nbest khg_nbest;
+int khg_lattices_nbest(khg_ctx *ctx, const khg_lattices *l, float graph_scale, float acoustic_scale, int32_t n, int32_t *status_h,
+                       khg_nbest **out);
+int khg_nbest_sizes(const khg_nbest *nb, int64_t *entry_off_h, int64_t *words_off_h);
+int khg_nbest_download(khg_ctx *ctx, const khg_nbest *nb, int32_t *ali_h, int32_t *words_h, float *weight_h, float *total_h);
+int khg_nbest_device_bytes(const khg_nbest *nb, int64_t *bytes);
+int khg_nbest_destroy(khg_nbest *nb);
 
 /* ---- K2M: MPE / sMBR posteriors of resident lattices (lattice-to-mpe-post, lattice-to-smbr-post) ------------------- */
 #define KHG_MPE_MPFE 0           /* an arc is correct when its phone is the reference's at that frame */

@@ -23,6 +23,7 @@ from .score import lattice_mbr_decode, lattice_mbr_decode_batch, mbr_utterances 
 from .align import get_raw_lattice_faster_batch, get_raw_lattice_faster_device_batch  # noqa: F401
 from .determinize import (get_lattice_faster_batch, get_lattice_faster_device_batch, lattice_determinize_pruned,  # noqa: F401
                           lattice_determinize_pruned_batch)
+from .nbest import KHG_NBEST_MAX, DeviceNbest, NbestList, lattice_to_nbest, lattice_to_nbest_batch  # noqa: F401
 from .context_dep import (ContextDependency, ContextDependencyInterface, monophone_context_dependency,  # noqa: F401
                           monophone_context_dependency_shared)
 from .device import (ALIGN_DONE, ALIGN_ERROR, ALIGN_EXACT_DP, ALIGN_FALLBACK, ALIGN_RETRIED, Comm, Context, DeviceAccs,  # noqa: F401

@@ -243,6 +243,11 @@ SIGNATURES = {
     "khg_mbr_download": (C.c_int, [vp, vp, c_i32p, c_i32p, c_f64p, c_i32p, c_f64p, c_i32p, c_f64p, c_f64p, c_f64p]),
     "khg_mbr_device_bytes": (C.c_int, [vp, c_i64p]),
     "khg_mbr_destroy": (C.c_int, [vp]),
+    "khg_lattices_nbest": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_int32, c_i32p, C.POINTER(vp)]),
+    "khg_nbest_sizes": (C.c_int, [vp, c_i64p, c_i64p]),
+    "khg_nbest_download": (C.c_int, [vp, vp, c_i32p, c_i32p, c_f32p, c_f32p]),
+    "khg_nbest_device_bytes": (C.c_int, [vp, c_i64p]),
+    "khg_nbest_destroy": (C.c_int, [vp]),
     "khg_lattices_mpe_posteriors": (C.c_int, [vp, vp, C.c_int32, c_i32p, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p, vp, C.c_int32, C.c_int32,
                                               C.c_float, C.c_float, c_i32p, c_f64p, c_f64p, C.POINTER(vp)]),
     "khg_posteriors_sizes": (C.c_int, [vp, c_i64p, c_i64p]),

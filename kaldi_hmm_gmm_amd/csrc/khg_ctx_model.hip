@@ -168,7 +168,7 @@ extern "C" int khg_ctx_get_timings(khg_ctx* c, char* names, int64_t names_cap, f
 }
 // valid range of every option (inclusive)
 static const struct { int lo, hi; } k_opt_range[KHG_OPT_COUNT] = {
-  {KHG_K1_AUTO, KHG_K1_F16X2S}, {0, 4}, {0, 6}, {0, 1 << 20}, {-1, 1}, {0, 255}, {0, 1}, {0, 4}, {0, 3}, {0, 1}, {0, 2}, {0, 2}, {0, 2}, {0, 64}, {0, 1}, {0, 1}, {0, 1}, {0, 1 << 20}, {0, 1}, {0, 2}, {0, 1 << 16}, {0, 1}, {0, 1}, {0, 2}, {0, 1}};
+  {KHG_K1_AUTO, KHG_K1_F16X2S}, {0, 4}, {0, 6}, {0, 1 << 20}, {-1, 1}, {0, 255}, {0, 1}, {0, 4}, {0, 3}, {0, 1}, {0, 2}, {0, 2}, {0, 2}, {0, 64}, {0, 1}, {0, 1}, {0, 1}, {0, 1 << 20}, {0, 1}, {0, 2}, {0, 1 << 16}, {0, 1}, {0, 1}, {0, 2}, {0, 1}, {0, 1 << 20}};
 extern "C" int khg_option_check(int opt, int value) {
   if (opt < 0 || opt >= KHG_OPT_COUNT) return khg_set_error(KHG_E_ARG, "khg_option_check: no such option");
   if (value < k_opt_range[opt].lo || value > k_opt_range[opt].hi || (opt == KHG_OPT_K1_FORM && value == 1))      // (1: the removed bf16x3 form)
@@ -207,7 +207,8 @@ static const struct { const char* name; int opt; const char* words; } k_env_tab[
   {"KHG_LAT_OPS_LDS", KHG_OPT_LAT_OPS_LDS, "on=0,off=1"},
   {"KHG_K1_LAUNCH", KHG_OPT_K1_LAUNCH, "auto=0,chunk=1,persistent=2"}, {"KHG_K1_PGRID", KHG_OPT_K1_PGRID, ""},
   {"KHG_K1_PROF", KHG_OPT_K1_PROF, ""}, {"KHG_K2_LADDER", KHG_OPT_K2_LADDER, "on=0,off=1"},
-  {"KHG_K3_PLANES", KHG_OPT_K3_PLANES, "auto=0,off=1,on=2"}, {"KHG_K2_TAIL", KHG_OPT_K2_TAIL, "on=0,off=1"}};
+  {"KHG_K3_PLANES", KHG_OPT_K3_PLANES, "auto=0,off=1,on=2"}, {"KHG_K2_TAIL", KHG_OPT_K2_TAIL, "on=0,off=1"},
+  {"KHG_NBEST_ARENA", KHG_OPT_NBEST_ARENA, ""}};
 // What khg_ctx_create makes of the environment variable `name` set to `text`: KHG_OK and (option, value), or KHG_E_ARG -- an unknown
 // variable, an unknown word, a value outside the option's range (khg_ctx_create ignores such a setting: the default stays).
 extern "C" int khg_option_from_env(const char* name, const char* text, int* option, int* value) {

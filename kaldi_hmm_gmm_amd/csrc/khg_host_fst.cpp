@@ -795,6 +795,99 @@ LatticeDeterminized Lattice::Determinize(float gs, float as, float beam, float d
   return out;
 }
 
+std::vector<LatticeNbestEntry> Lattice::Nbest(int n, float gs, float as, int* status) const {
+  const std::string who = "Lattice::Nbest: ";
+  KHG_REQUIRE(gs >= 0.0f && as >= 0.0f && std::isfinite(gs) && std::isfinite(as), who + "graph_scale and acoustic_scale must be finite and >= 0");
+  KHG_REQUIRE(n >= 1 && n <= KHG_NBEST_MAX, who + "n must lie in 1 .. " + std::to_string(KHG_NBEST_MAX));
+  std::vector<LatticeNbestEntry> out;
+  int st_local = 0;
+  int& st = status ? *status : st_local;
+  const int N = NumStates();
+  if (N == 0) { st = KHG_LAT_NO_PATH; return out; }
+  for (int s = 0; s < N; ++s)
+    for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a)
+      if (nextstate[(size_t)a] <= s) { st = KHG_LAT_EPS_LOOP; return out; }
+  const float INF = std::numeric_limits<float>::infinity();
+  struct Prefix { float t, a, b; int32_t nw, e, j; };
+  const auto by_key = [](const Prefix& x, const Prefix& y) {
+    if (x.t < y.t) return true;
+    if (y.t < x.t) return false;
+    return x.e != y.e ? x.e < y.e : x.j < y.j;
+  };
+  // the in-arcs of every state
+  std::vector<std::vector<int32_t>> in((size_t)N);
+  std::vector<int32_t> src((size_t)NumArcs());
+  for (int s = 0; s < N; ++s)
+    for (int32_t a = arc_begin[(size_t)s]; a < arc_begin[(size_t)s + 1]; ++a) { in[(size_t)nextstate[(size_t)a]].push_back(a); src[(size_t)a] = s; }
+  // the scratch bound is on the lists' bounds len[s] = min(n, sum of len[p]), which do not know of dropped candidates
+  {
+    std::vector<int64_t> len((size_t)N, 0);
+    int64_t tot = 0;
+    for (int s = 0; s < N; ++s) {
+      int64_t c = s == start ? 1 : 0;
+      if (s != start) for (int32_t e : in[(size_t)s]) c += len[(size_t)src[(size_t)e]];
+      len[(size_t)s] = std::min<int64_t>(c, n);
+      tot += len[(size_t)s];
+    }
+    if (tot > (int64_t)INT32_MAX) { st = KHG_LAT_SCRATCH; return out; }
+  }
+  std::vector<std::vector<Prefix>> A((size_t)N);
+  for (int s = 0; s < N; ++s) {
+    std::vector<Prefix>& L = A[(size_t)s];
+    if (s == start) L.push_back(Prefix{0.0f, 0.0f, 0.0f, 0, -1, 0});
+    else
+      for (int32_t e : in[(size_t)s]) {
+        const float wa = gs * graph_cost[(size_t)e];
+        const float wb = ilabel[(size_t)e] != 0 ? as * acoustic_cost[(size_t)e] : 0.0f;
+        const float c = wa + wb;
+        const std::vector<Prefix>& P = A[(size_t)src[(size_t)e]];
+        for (size_t j = 0; j < P.size(); ++j) {
+          const float t = P[j].t + c;
+          if (!(t < INF)) continue;
+          L.push_back(Prefix{t, P[j].a + wa, P[j].b + wb, P[j].nw + (olabel[(size_t)e] != 0 ? 1 : 0), e, (int32_t)j});
+        }
+      }
+    std::sort(L.begin(), L.end(), by_key);
+    if (L.size() > (size_t)n) L.resize((size_t)n);
+  }
+  const int T = frame[(size_t)N - 1];
+  std::vector<Prefix> F;
+  for (int s = 0; s < N; ++s) {
+    const float fc = final_cost[(size_t)s];
+    if (frame[(size_t)s] != T || !std::isfinite(fc)) continue;
+    const float fw = gs * fc;
+    const std::vector<Prefix>& P = A[(size_t)s];
+    for (size_t j = 0; j < P.size(); ++j) {
+      const float t = P[j].t + fw;
+      if (!(t < INF)) continue;
+      F.push_back(Prefix{t, P[j].a + fw, P[j].b, P[j].nw, s, (int32_t)j});
+    }
+  }
+  std::sort(F.begin(), F.end(), by_key);
+  if (F.size() > (size_t)n) F.resize((size_t)n);
+  if (F.empty()) { st = KHG_LAT_NO_PATH; return out; }
+  for (const Prefix& f : F) {
+    LatticeNbestEntry x;
+    x.a = f.a; x.b = f.b; x.total = f.t; x.end_state = f.e; x.rank = f.j;
+    x.ali.assign((size_t)std::max(T, 0), 0);
+    int s = f.e, j = f.j;
+    for (;;) {
+      const Prefix& q = A[(size_t)s][(size_t)j];
+      if (q.e < 0) break;
+      const int32_t e = q.e;
+      s = src[(size_t)e]; j = q.j;
+      x.arcs.push_back(e);
+      if (ilabel[(size_t)e] != 0 && frame[(size_t)s] >= 0 && frame[(size_t)s] < T) x.ali[(size_t)frame[(size_t)s]] = ilabel[(size_t)e];
+      if (olabel[(size_t)e] != 0) x.words.push_back(olabel[(size_t)e]);
+    }
+    std::reverse(x.arcs.begin(), x.arcs.end());
+    std::reverse(x.words.begin(), x.words.end());
+    out.push_back(std::move(x));
+  }
+  st = KHG_LAT_SUCCEEDED;
+  return out;
+}
+
 std::shared_ptr<Lattice> Lattice::AddPenalty(float word_ins_penalty) const {
   KHG_REQUIRE(std::isfinite(word_ins_penalty), "Lattice::AddPenalty: word_ins_penalty must be finite");
   auto r = std::make_shared<Lattice>(*this);

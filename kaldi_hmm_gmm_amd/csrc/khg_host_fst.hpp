@@ -155,6 +155,14 @@ struct LatticeDeterminized {
   khg_det_stats stats = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// One entry of Lattice::Nbest: the path's transition-ids by frame (one per frame of the lattice, 0 where the path has none), its
+// words, its arcs, its weight pair (a, b) and its total, the final state it ends in and its rank in that state's list
+struct LatticeNbestEntry {
+  std::vector<int32_t> ali, words, arcs;
+  float a = 0.0f, b = 0.0f, total = 0.0f;
+  int end_state = -1, rank = 0;
+};
+
 // Lattice::Oracle (what khg_lattices_oracle gives for one lattice): KHG_LAT_* status (SUCCEEDED, NO_PATH, EPS_LOOP), the
 // counts (errors, insertions, deletions, substitutions; (R, 0, R, 0) without a path), the oracle path's words, its arcs, and its
 // transition-ids by frame (one entry per frame of the lattice, 0 where the path has none)
@@ -242,6 +250,10 @@ class Lattice {
   // beam-pruned lattice, the cheapest, made of copies of its arcs; the rule is stated at khg_lattices_determinize, and this is it, serially
   LatticeDeterminized Determinize(float graph_scale = 1.0f, float acoustic_scale = 1.0f, float beam = 10.0f, float delta = 1.0f / 1024.0f,
                                   int state_factor = 8) const;
+  // lattice-to-nbest | nbest-to-linear (what khg_lattices_nbest gives for one lattice): the n cheapest paths under the
+  // scalar key of the rule stated at khg_lattices_nbest, and this is it, serially -- every candidate of a state is generated, the lot
+  // is sorted by (t', e, j) and cut at n; no merge.  *status: the KHG_LAT_* bits (SUCCEEDED, NO_PATH, EPS_LOOP, SCRATCH).
+  std::vector<LatticeNbestEntry> Nbest(int n, float graph_scale = 1.0f, float acoustic_scale = 1.0f, int* status = nullptr) const;
   // lattice-add-penalty (what khg_lattices_add_penalty gives for one lattice): a copy in which every arc with olabel != 0 has
   // graph_cost = fl(graph_cost + word_ins_penalty); everything else as stored
   std::shared_ptr<Lattice> AddPenalty(float word_ins_penalty) const;

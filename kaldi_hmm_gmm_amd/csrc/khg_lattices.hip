@@ -54,6 +54,7 @@
 #include "khg_k2_lattice_det.hip.inc"
 #include "khg_k2_lattice_score.hip.inc"
 #include "khg_k2_lattice_mbr.hip.inc"
+#include "khg_k2_lattice_nbest.hip.inc"
 
 // ------------------------------------------------------------------------------------------
 // The raw lattices of one batch (khg_decode_lattice_simple_raw, khg_decode_lattice_faster_raw): per chunk of scratch slices one
@@ -2009,6 +2010,7 @@ extern "C" int khg_lattices_determinize(khg_ctx* ctx, const khg_lattices* lc, fl
 // K2W: scoring (khg_k2_lattice_score.hip.inc): the word insertion penalty, the oracle path, the sweep of score.sh
 namespace {
 const int64_t kScoreScratch = int64_t(1) << 30;       // khg_lattices_oracle's tables per launch when the caller names no size
+const int64_t kNbestArena = int64_t(1) << 30;        // khg_lattices_nbest: the lists of one launch's utterances (24 bytes per element) unless KHG_OPT_NBEST_ARENA names a size
 const int64_t kScoreWerLds = 48 << 10;                // khg_lattices_wer: a (triple, utterance) table stays in LDS up to this many bytes
 
 // the most dynamic LDS a workgroup of the current device may ask for: all 160 KiB of a gfx950 CU
@@ -2529,6 +2531,185 @@ extern "C" int khg_lattices_mbr(khg_ctx* ctx, const khg_lattices* lc, float grap
       if (st2[su] & KHG_LAT_SUCCEEDED) { m->nwords[su] = nw[su]; m->risk[su] = rk[su]; }
     }
   }
+  *out = res.release();
+  return KHG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K2N: the n best paths (khg_k2_lattice_nbest.hip.inc)
+// The entries of the utterances u0 .. u0 + n, made by one launch of the fill: exactly-sized blocks, the utterances one after the other
+struct NbBlock {
+  int u0 = 0, n = 0;
+  int64_t e0 = 0, ne = 0, w0 = 0, nw = 0, a0 = 0, na = 0;       // first entry / word / alignment cell in the handle's order, and how many
+  int32_t *ali_d = nullptr, *words_d = nullptr, *nw_d = nullptr;
+  float *weight_d = nullptr, *total_d = nullptr;
+};
+struct khg_nbest {
+  int U = 0;
+  khg_ctx* ctx = nullptr;
+  int64_t bytes = 0;
+  std::vector<int32_t> status;                          // [U]
+  std::vector<int64_t> entry_off, words_off;            // [U + 1], [entries + 1]
+  std::vector<NbBlock> blocks;
+};
+
+namespace {
+struct NbFree { void operator()(khg_nbest* m) const { (void)khg_nbest_destroy(m); } };
+using NbPtr = std::unique_ptr<khg_nbest, NbFree>;
+template <class T>
+int nb_alloc(khg_nbest* m, int64_t count, T** out) {
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(out), (size_t)std::max<int64_t>(count * (int64_t)sizeof(T), 16)));
+  m->bytes += count * (int64_t)sizeof(T);
+  return KHG_OK;
+}
+}  // namespace
+
+extern "C" int khg_nbest_destroy(khg_nbest* m) {
+  if (!m) return KHG_OK;
+  for (NbBlock& b : m->blocks) {
+    void* blocks[5] = {b.ali_d, b.words_d, b.nw_d, b.weight_d, b.total_d};
+    for (void* q : blocks) if (q) (void)hipFree(q);
+  }
+  delete m;
+  return KHG_OK;
+}
+extern "C" int khg_nbest_device_bytes(const khg_nbest* m, int64_t* bytes) {
+  if (!m || !bytes) return khg_set_error(KHG_E_ARG, "khg_nbest_device_bytes: bad arguments");
+  *bytes = m->bytes;
+  return KHG_OK;
+}
+extern "C" int khg_nbest_sizes(const khg_nbest* m, int64_t* entry_off_h, int64_t* words_off_h) {
+  if (!m) return khg_set_error(KHG_E_ARG, "khg_nbest_sizes: bad arguments");
+  if (entry_off_h) std::copy(m->entry_off.begin(), m->entry_off.end(), entry_off_h);
+  if (words_off_h) std::copy(m->words_off.begin(), m->words_off.end(), words_off_h);
+  return KHG_OK;
+}
+extern "C" int khg_nbest_download(khg_ctx* ctx, const khg_nbest* m, int32_t* ali_h, int32_t* words_h, float* weight_h, float* total_h) {
+  if (ctx_dead(ctx) || !m) return khg_set_error(KHG_E_ARG, "khg_nbest_download: bad arguments");
+  if (m->ctx != ctx) return other_ctx("khg_nbest_download");
+  for (const NbBlock& b : m->blocks) {
+    if (ali_h && b.na) HIPCHK(hipMemcpyAsync(ali_h + b.a0, b.ali_d, 4 * (size_t)b.na, hipMemcpyDeviceToHost, ctx->stream));
+    if (words_h && b.nw) HIPCHK(hipMemcpyAsync(words_h + b.w0, b.words_d, 4 * (size_t)b.nw, hipMemcpyDeviceToHost, ctx->stream));
+    if (weight_h && b.ne) HIPCHK(hipMemcpyAsync(weight_h + 2 * b.e0, b.weight_d, 8 * (size_t)b.ne, hipMemcpyDeviceToHost, ctx->stream));
+    if (total_h && b.ne) HIPCHK(hipMemcpyAsync(total_h + b.e0, b.total_d, 4 * (size_t)b.ne, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return KHG_OK;
+}
+
+extern "C" int khg_lattices_nbest(khg_ctx* ctx, const khg_lattices* lc, float graph_scale, float acoustic_scale, int32_t n, int32_t* status_h,
+                                  khg_nbest** out) {
+  const std::string name = "khg_lattices_nbest", who = name + ": ";
+  if (ctx_dead(ctx) || !lc || !out) return khg_set_error(KHG_E_ARG, who + "bad arguments");
+  *out = nullptr;
+  if (lc->ctx != ctx) return other_ctx(name);
+  if (bad_scale(graph_scale) || bad_scale(acoustic_scale)) return khg_set_error(KHG_E_ARG, who + "graph_scale and acoustic_scale must be finite and >= 0");
+  if (n < 1 || n > KHG_NBEST_MAX) return khg_set_error(KHG_E_ARG, who + "n must lie in 1 .. " + std::to_string(KHG_NBEST_MAX));
+  khg_lattices* l = const_cast<khg_lattices*>(lc);
+  const int U = l->U;
+  NbPtr res(new khg_nbest);
+  khg_nbest* m = res.get();
+  m->U = U; m->ctx = ctx;
+  m->status.assign((size_t)U, 0); m->entry_off.assign((size_t)U + 1, 0); m->words_off.assign(1, 0);
+  if (U == 0) { *out = res.release(); return KHG_OK; }
+  int rc = lat_ready(ctx, l, kWithIndex);
+  if (rc) return rc;
+  // the running lists: in LDS when the device gives 52 n bytes (and KHG_OPT_LAT_OPS_LDS is not 1), else in HBM rows
+  int64_t lds_cap = 0;
+  if ((rc = score_lds_cap(&lds_cap))) return rc;
+  const int64_t lds_need = 4 * (int64_t)NB_ROW_WORDS * n;
+  const bool use_lds = ctx->opt[KHG_OPT_LAT_OPS_LDS] != 1 && lds_need <= lds_cap;
+  const int64_t arena = ctx->opt[KHG_OPT_NBEST_ARENA] > 0 ? (int64_t)ctx->opt[KHG_OPT_NBEST_ARENA] << 10 : kNbestArena;
+  DevBlocks dv;
+  int32_t* status_d;
+  int64_t* ali_off_d;
+  if ((rc = dv.alloc(U, &status_d)) || (rc = dv.upload(ctx, l->ali_off, &ali_off_d))) return rc;
+  std::vector<std::vector<int64_t>> ali_bases;      // (a launch's upload lives until the launch is done)
+  std::vector<std::vector<int32_t>> nws;            // per block, the entries' word counts
+  int64_t E = 0, W = 0, AL = 0;
+  for (size_t k = 0; k < l->chunks.size(); ++k) {
+    const LatChunk& c = l->chunks[k];
+    NbArgs p{};
+    lat_chunk_args(l, c, &p.lo);
+    const LatIndex ix = lat_index_arrays(l->idx_d[k], c);
+    p.in_begin = ix.in_begin; p.in_arc = ix.in_arc; p.arc_src = ix.arc_src;
+    p.gs = graph_scale; p.as = acoustic_scale; p.nb = n; p.status = status_d; p.ali_off = ali_off_d;
+    const int64_t cs = std::max<int64_t>(c.ns, 1);
+    int64_t* utt_off;
+    if ((rc = dv.alloc(cs, &p.len)) || (rc = dv.alloc(cs, &p.loff)) || (rc = dv.alloc(cs, &p.alen)) || (rc = dv.alloc(2 * (int64_t)c.n, &p.utt_tot)) ||
+        (rc = dv.alloc(2 * ((int64_t)c.n + 1), &utt_off)) || (rc = dv.alloc(2 * (int64_t)c.n, &p.utt_tot2)))
+      return rc;
+    p.utt_off = utt_off;
+    // 1. and 2. the bounds, and the one synchronisation that sizes the arena
+    std::vector<int64_t> ro, so;
+    if ((rc = launch(ctx, "k2_lattice_nbest_count", k2_lattice_nbest_count, dim3((unsigned)c.n), dim3(NB_NT), 0, p)) ||
+        (rc = scan_pairs_and_read(ctx, "k2_lattice_nbest_scan", p.utt_tot, utt_off, c.n, &ro, &so)))
+      return rc;
+    const int64_t slots = std::max<int64_t>(so[(size_t)c.n], 1);
+    if ((rc = dv.alloc(slots, &p.s_end)) || (rc = dv.alloc(slots, &p.s_rank)) || (rc = dv.alloc(slots, &p.s_nw)) || (rc = dv.alloc(slots, &p.s_woff)) ||
+        (rc = dv.alloc(slots, &p.s_a)) || (rc = dv.alloc(slots, &p.s_b)) || (rc = dv.alloc(slots, &p.s_tot)))
+      return rc;
+    // the chunk's utterances in launches whose lists fit the budget together (an utterance above it is a launch of its own)
+    for (size_t g0 = 0; g0 < (size_t)c.n;) {
+      size_t g1 = g0 + 1;
+      while (g1 < (size_t)c.n && 24 * (ro[g1 + 1] - ro[g0]) <= arena) ++g1;
+      const int gn = (int)(g1 - g0);
+      const int64_t R = ro[g1] - ro[g0], rows = std::max<int64_t>(R, 1);
+      DevBlocks ga;       // the launch's arena
+      int64_t* utt_off2;
+      if ((rc = ga.alloc(rows, &p.r_t)) || (rc = ga.alloc(rows, &p.r_a)) || (rc = ga.alloc(rows, &p.r_b)) || (rc = ga.alloc(rows, &p.r_nw)) ||
+          (rc = ga.alloc(rows, &p.r_e)) || (rc = ga.alloc(rows, &p.r_j)) || (rc = ga.alloc(2 * ((int64_t)gn + 1), &utt_off2)))
+        return rc;
+      p.rows = nullptr;
+      if (!use_lds && (rc = ga.alloc((int64_t)gn * NB_ROW_WORDS * n, &p.rows))) return rc;
+      p.b0 = (int)g0; p.gn = gn; p.arena_base = ro[g0]; p.arena_size = R; p.utt_off2 = utt_off2;
+      // 3. the lists and the entries; 4. the scan of the entries and their words, with the synchronisation that sizes the block
+      if (use_lds) {
+        if ((rc = khg_lds_attribute(reinterpret_cast<const void*>(k2_lattice_nbest_fill<true>), (size_t)lds_need)) ||
+            (rc = launch(ctx, "k2_lattice_nbest_fill", k2_lattice_nbest_fill<true>, dim3((unsigned)gn), dim3(NB_NT), (size_t)lds_need, p)))
+          return rc;
+      } else if ((rc = launch(ctx, "k2_lattice_nbest_fill", k2_lattice_nbest_fill<false>, dim3((unsigned)gn), dim3(NB_NT), 0, p))) {
+        return rc;
+      }
+      std::vector<int64_t> eo, wo;
+      if ((rc = scan_pairs_and_read(ctx, "k2_lattice_nbest_words", p.utt_tot2 + 2 * g0, utt_off2, gn, &eo, &wo))) return rc;
+      NbBlock bl;
+      bl.u0 = c.u0 + (int)g0; bl.n = gn; bl.e0 = E; bl.w0 = W; bl.a0 = AL; bl.ne = eo[(size_t)gn]; bl.nw = wo[(size_t)gn];
+      ali_bases.emplace_back((size_t)gn, 0);
+      std::vector<int64_t>& ab = ali_bases.back();
+      for (int g = 0; g < gn; ++g) {
+        const size_t u = (size_t)bl.u0 + (size_t)g;
+        const int64_t cnt = eo[(size_t)g + 1] - eo[(size_t)g];
+        ab[(size_t)g] = bl.na;
+        bl.na += cnt * (l->ali_off[u + 1] - l->ali_off[u]);
+        m->entry_off[u + 1] = m->entry_off[u] + cnt;
+      }
+      m->blocks.push_back(bl);
+      NbBlock& B = m->blocks.back();
+      if ((rc = nb_alloc(m, B.na, &B.ali_d)) || (rc = nb_alloc(m, B.nw, &B.words_d)) || (rc = nb_alloc(m, B.ne, &B.nw_d)) ||
+          (rc = nb_alloc(m, 2 * B.ne, &B.weight_d)) || (rc = nb_alloc(m, B.ne, &B.total_d)))
+        return rc;
+      if (B.na) HIPCHK(hipMemsetAsync(B.ali_d, 0, 4 * (size_t)B.na, ctx->stream));
+      int64_t* ab_d;
+      if ((rc = ga.upload(ctx, ab, &ab_d))) return rc;
+      p.ali_base = ab_d;
+      p.o_ali = B.ali_d; p.o_words = B.words_d; p.o_nw = B.nw_d; p.o_weight = B.weight_d; p.o_total = B.total_d;
+      p.o_ne = B.ne; p.o_nwords = B.nw; p.o_na = B.na;
+      nws.emplace_back();
+      if (B.ne > 0 &&
+          ((rc = launch(ctx, "k2_lattice_nbest_trace", k2_lattice_nbest_trace, dim3((unsigned)gn, (unsigned)((n + NB_NT - 1) / NB_NT)), dim3(NB_NT), 0, p)) ||
+           (rc = download(ctx, B.nw_d, B.ne, &nws.back()))))
+        return rc;
+      HIPCHK(hipStreamSynchronize(ctx->stream));       // the arena goes with `ga`
+      E += B.ne; W += B.nw; AL += B.na;
+      g0 = g1;
+    }
+  }
+  if ((rc = download(ctx, status_d, U, &m->status)) || (rc = check_err_flag(ctx, name.c_str()))) return rc;     // synchronises: the scratch goes with `dv`
+  m->words_off.reserve((size_t)E + 1);
+  for (const std::vector<int32_t>& v : nws)
+    for (int32_t w : v) m->words_off.push_back(m->words_off.back() + w);
+  if (status_h) std::copy(m->status.begin(), m->status.end(), status_h);
   *out = res.release();
   return KHG_OK;
 }

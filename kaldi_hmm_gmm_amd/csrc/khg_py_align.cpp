@@ -368,6 +368,31 @@ py::dict LmStatsDict(const khg_lm_rescore_stats& s) {
   d["in_states"] = s.in_states; d["in_arcs"] = s.in_arcs; d["out_states"] = s.out_states; d["out_arcs"] = s.out_arcs; d["max_hist"] = s.max_hist;
   return d;
 }
+py::list NbestList(const std::vector<LatticeNbestEntry>& v) {
+  py::list r;
+  for (const LatticeNbestEntry& x : v) r.append(py::make_tuple(py::cast(x.words), py::cast(x.ali), py::make_tuple(x.a, x.b), x.total));
+  return r;
+}
+// DeviceNbest: owns a khg_nbest handle (what DeviceLattices.nbest made, resident on the device)
+struct PyDeviceNbest {
+  khg_nbest* h = nullptr;
+  khg_ctx* ctx = nullptr;
+  py::object ctx_obj;
+  int U = 0;
+  std::vector<int32_t> status;       // KHG_LAT_* bits per utterance
+  std::vector<int64_t> frames;       // [U]: the frames of every utterance's lattice (an alignment's length)
+  PyDeviceNbest() = default;
+  PyDeviceNbest(const PyDeviceNbest&) = delete;
+  PyDeviceNbest& operator=(const PyDeviceNbest&) = delete;
+  ~PyDeviceNbest() { close(); }
+  void close() { if (h) { khg_nbest_destroy(h); h = nullptr; } }
+};
+std::vector<int64_t> NbestEntryOff(PyDeviceNbest& d) {
+  if (!d.h) throw Error("DeviceNbest: closed");
+  std::vector<int64_t> eo((size_t)d.U + 1, 0);
+  CApi(khg_nbest_sizes(d.h, eo.data(), nullptr));
+  return eo;
+}
 py::dict DetStatsDict(const khg_det_stats& s) {
   py::dict d;
   d["in_states"] = s.in_states; d["in_arcs"] = s.in_arcs; d["pruned_states"] = s.pruned_states; d["det_states"] = s.det_states;
@@ -472,6 +497,21 @@ void BindLattice(py::module_& m) {
         return py::make_tuple(r.lattice, r.status, DetStatsDict(r.stats));
       }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f, py::arg("beam") = 10.0f, py::arg("delta") = 1.0f / 1024.0f,
          py::arg("state_factor") = 8)
+      // lattice-to-nbest on the host (what DeviceLattices.nbest gives for this lattice) -> a list of (words, alignment,
+      // (graph, acoustic), total), cheapest first; nbest_with_status -> (that list, status, per entry its arcs with the final state last)
+      .def("nbest", [](const Lattice& l, int n, float gs, float as) { return NbestList(l.Nbest(n, gs, as)); }, py::arg("n"),
+           py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
+      .def("nbest_with_status", [](const Lattice& l, int n, float gs, float as) {
+        int st = 0;
+        const std::vector<LatticeNbestEntry> v = l.Nbest(n, gs, as, &st);
+        py::list paths;
+        for (const LatticeNbestEntry& x : v) {
+          std::vector<int32_t> p = x.arcs;
+          p.push_back(x.end_state);
+          paths.append(py::tuple(py::cast(p)));
+        }
+        return py::make_tuple(NbestList(v), st, paths);
+      }, py::arg("n"), py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       // lattice-add-penalty on the host (what DeviceLattices.add_penalty gives for this lattice)
       .def("add_penalty", [](const Lattice& l, float p) { return l.AddPenalty(p); }, py::arg("word_ins_penalty"))
       // lattice-oracle on the host (what DeviceLattices.oracle gives for this lattice): status (KHG_LAT_* bits), counts
@@ -881,6 +921,22 @@ void BindLattice(py::module_& m) {
         return r;
       }, py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f, py::arg("decode_mbr") = true, py::arg("max_iter") = 32, py::arg("init") = py::none(),
          py::arg("max_words") = 0, py::arg("scratch_bytes") = 0)
+      // lattice-to-nbest -> a DeviceNbest: the n cheapest paths of every utterance, resident on the device
+      .def("nbest", [](PyDeviceLattices& d, int n, float gs, float as) {
+        const int U = (int)LatSizes(d).first.size() - 1;
+        auto r = std::make_shared<PyDeviceNbest>();
+        r->ctx = d.ctx; r->ctx_obj = d.ctx_obj; r->U = U;
+        r->status.assign((size_t)std::max(U, 1), 0);
+        std::vector<int64_t> aoff((size_t)U + 1, 0);
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_lattices_nbest(d.ctx, d.h, gs, as, n, r->status.data(), &r->h));
+          CApi(khg_lattices_ali_layout(d.ctx, d.h, aoff.data()));
+        }
+        r->status.resize((size_t)U);
+        for (int u = 0; u < U; ++u) r->frames.push_back(aoff[(size_t)u + 1] - aoff[(size_t)u]);
+        return r;
+      }, py::arg("n"), py::arg("graph_scale") = 1.0f, py::arg("acoustic_scale") = 1.0f)
       .def("download", [](PyDeviceLattices& d) {
         if (!d.h) throw Error("DeviceLattices: closed");
         std::vector<std::shared_ptr<Lattice>> out;
@@ -891,6 +947,44 @@ void BindLattice(py::module_& m) {
         return out;
       })
       .def("close", &PyDeviceLattices::close);
+
+  // DeviceNbest: the n-best lists of a batch resident on the device (a khg_nbest handle)
+  py::class_<PyDeviceNbest, std::shared_ptr<PyDeviceNbest>>(m, "DeviceNbest")
+      .def_property_readonly("num_utts", [](PyDeviceNbest& d) { return d.U; })
+      // the entries of every utterance
+      .def_property_readonly("counts", [](PyDeviceNbest& d) {
+        const std::vector<int64_t> eo = NbestEntryOff(d);
+        std::vector<int64_t> c((size_t)d.U);
+        for (int u = 0; u < d.U; ++u) c[(size_t)u] = eo[(size_t)u + 1] - eo[(size_t)u];
+        return Vec1(c);
+      })
+      .def_property_readonly("status", [](PyDeviceNbest& d) { return Vec1(d.status); })
+      .def_property_readonly("device_bytes", [](PyDeviceNbest& d) {
+        if (!d.h) throw Error("DeviceNbest: closed");
+        int64_t b = 0;
+        CApi(khg_nbest_device_bytes(d.h, &b));
+        return b;
+      })
+      // -> the flat arrays: status [U], entry_off [U + 1], and per entry words (words_off), ali (ali_off), weight [entries][2], total
+      .def("download", [](PyDeviceNbest& d) {
+        const std::vector<int64_t> eo = NbestEntryOff(d);
+        const int64_t E = eo.back();
+        std::vector<int64_t> wo((size_t)E + 1, 0), ao((size_t)E + 1, 0);
+        CApi(khg_nbest_sizes(d.h, nullptr, wo.data()));
+        for (int u = 0; u < d.U; ++u)
+          for (int64_t e = eo[(size_t)u]; e < eo[(size_t)u + 1]; ++e) ao[(size_t)e + 1] = ao[(size_t)e] + d.frames[(size_t)u];
+        Arr<int32_t> ali({(py::ssize_t)ao.back()}), words({(py::ssize_t)wo.back()});
+        Arr<float> weight({(py::ssize_t)E, (py::ssize_t)2}), total({(py::ssize_t)E});
+        {
+          py::gil_scoped_release nogil;
+          CApi(khg_nbest_download(d.ctx, d.h, ali.mutable_data(), words.mutable_data(), weight.mutable_data(), total.mutable_data()));
+        }
+        py::dict r;
+        r["status"] = Vec1(d.status); r["entry_off"] = Vec1(eo); r["words"] = words; r["words_off"] = Vec1(wo); r["ali"] = ali; r["ali_off"] = Vec1(ao);
+        r["weight"] = weight; r["total"] = total;
+        return r;
+      })
+      .def("close", &PyDeviceNbest::close);
 
   // compute-wer's core on the host (khg_edit_distance): (errors, insertions, deletions, substitutions) of hyp against ref
   m.def("edit_distance_counts", [](Arr<int32_t> ref, Arr<int32_t> hyp) {

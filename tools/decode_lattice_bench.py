@@ -56,6 +56,9 @@ the same handle, and khg_acc_stats_post2 alternated with khg_acc_stats_post on t
 states and arcs and the largest history set (DESIGN.md 7r).  The linear training graphs carry no words (every state keeps one history);
 with --shared-graph the lattices come from the --words word loop, whose words the n-gram covers.
 
+--nbest N (next to --shared-graph --lattices) times DeviceLattices.nbest(N) on the resident lattices, determinized first:
+the call with everything downloaded beside the download of the lattices and a loop of the host form Lattice.nbest, and counts the
+utterances whose entries equal the host's bit for bit.
 --oracle and --score LO:HI (next to --lattices) time scoring on the resident lattices: DeviceLattices.oracle beside the
 download plus a loop of the host form Lattice.oracle; DeviceLattices.wer at the LM weights LO..HI x penalties {0, 0.5, 1} beside
 add_penalty + best_path with the words downloaded + khg_edit_distance on the host; add_penalty beside a device-to-device copy of the
@@ -668,6 +671,45 @@ def det_bench(ctx, dl, reps, beam, delta=1.0 / 1024, state_factor=8):
             "host_over_device": float(np.median(t_host)) / float(np.median(t_dev)), "same_as_host": same}
 
 
+def nbest_bench(ctx, dl, reps, n, beam, delta=1.0 / 1024, state_factor=8):
+    """--nbest N on resident lattices, both sides in this process and alternated: the lattices are determinized once at
+    (1, 1, beam); then DeviceLattices.nbest(N) with everything downloaded beside the download of every determinized lattice and a loop
+    of the host form Lattice.nbest, which must give the device's entries bit for bit."""
+    from kaldi_hmm_gmm_amd import NbestList
+    reps = max(reps, 3)
+    det, dst, _ = dl.determinize(1.0, 1.0, beam, delta, state_factor)
+    U = det.num_utts
+    so, ao = np.asarray(det.state_off), np.asarray(det.arc_off)
+    det.nbest(n).close(); ctx.sync()       # warm-up (builds the handle's in-arc index)
+    t_dev, t_dl, t_host, k_ms = [], [], [], []
+    for _ in range(reps):
+        def call():
+            nb = det.nbest(n); nb.download(); nb.close()
+        k_ms.append(kernel_ms(ctx, call))
+        ctx.sync(); t0 = time.time()
+        nb = det.nbest(n)
+        arrays = nb.download()
+        t_dev.append(time.time() - t0)
+        nbytes = nb.device_bytes
+        nb.close()
+        t0 = time.time()
+        lats = det.download()
+        t_dl.append(time.time() - t0)
+        t0 = time.time()
+        host = [L.nbest_with_status(n) for L in lats]
+        t_host.append(time.time() - t0)
+    nl = NbestList(arrays)
+    same = sum(1 for u, (got, hst, _) in enumerate(host) if hst == int(nl.status[u]) and [tuple(x) for x in got] == [tuple(x) for x in nl.entries(u)])
+    ms = {k: float(np.median([x.get(k, 0.0) for x in k_ms])) for k in sorted({k for x in k_ms for k in x})}
+    counts = np.asarray(nl.counts)
+    det.close()
+    return {"utterances": U, "n": n, "beam": beam, "repetitions": reps, "succeeded": int((np.asarray(nl.status) == 1).sum()),
+            "determinize_succeeded": int((np.asarray(dst) == 1).sum()), "states_mean": float(np.diff(so).mean()), "arcs_mean": float(np.diff(ao).mean()),
+            "entries": int(counts.sum()), "entries_mean": float(counts.mean()), "lists_full": int((counts == n).sum()), "device_bytes": int(nbytes),
+            "kernels_ms": ms, "call_with_download": med(t_dev), "download_lattices": med(t_dl), "host_loop": med(t_host),
+            "host_over_device": (float(np.median(t_host)) + float(np.median(t_dl))) / float(np.median(t_dev)), "same_as_host": same}
+
+
 def time_paths(ctx, dtm, sets, hubs, reps, with_faster=True, lattices=False):
     """sets: {path: UtteranceSet with resident scores}.  -> {path: {what: [seconds]}}, paths and options alternated inside every repetition
     after one warm-up round; and the last results."""
@@ -863,6 +905,13 @@ def shared_graph_main(args):
                 L = sh.raw_lattices_faster_device(dtm, beam=13.0, max_active=7000, lattice_beam=lb, acoustic_scale=0.1)["lattices"]
                 entry["det"]["lattice_beam_%g" % lb] = det_bench(ctx, L, args.reps, lb if args.det_beam is None else args.det_beam)
                 L.close()
+        if args.nbest and name == "faster":
+            # the n-best lists of the lattices the shared set leaves on the device, determinized, each set at its own lattice beam
+            entry["nbest"] = {}
+            for lb in (6.0, args.dense_lattice_beam):
+                L = sh.raw_lattices_faster_device(dtm, beam=13.0, max_active=7000, lattice_beam=lb, acoustic_scale=0.1)["lattices"]
+                entry["nbest"]["lattice_beam_%g" % lb] = nbest_bench(ctx, L, args.reps, args.nbest, lb if args.det_beam is None else args.det_beam)
+                L.close()
         for us in sets.values():
             us.close()
         dg.close()
@@ -905,9 +954,13 @@ def main():
                     "download and a loop of the host form Lattice.mbr (DESIGN.md 7t)")
     ap.add_argument("--det", action="store_true", help="with --shared-graph --lattices (--decoder faster): DeviceLattices.determinize on the resident "
                     "lattices beside the download and a loop of the host form Lattice.determinize (DESIGN.md 7u)")
+    ap.add_argument("--nbest", type=int, default=0, metavar="N", help="with --shared-graph --lattices (--decoder faster): DeviceLattices.nbest(N) on the "
+                    "resident lattices, determinized, beside their download and a loop of the host form Lattice.nbest (DESIGN.md 7v)")
     ap.add_argument("--det-beam", type=float, default=None, metavar="B", help="with --det: the determinization beam (default: each set's lattice beam)")
     ap.add_argument("--dense-lattice-beam", type=float, default=12.0, help="with --shared-graph --oracle / --score / --mbr / --det: the second, denser set's lattice beam")
     args = ap.parse_args()
+    if args.nbest and (not args.lattices or args.decoder != "faster" or not args.shared_graph or args.yesno or not 1 <= args.nbest <= 1024):
+        ap.error("--nbest N needs --shared-graph --lattices with --decoder faster, 1 <= N <= 1024 (and is not timed with --yesno)")
     if args.det and (not args.lattices or args.decoder != "faster" or not args.shared_graph or args.yesno):
         ap.error("--det needs --shared-graph --lattices with --decoder faster (and is not timed with --yesno)")
     if args.mbr and (not args.lattices or args.decoder != "faster" or args.yesno):
